@@ -5,14 +5,16 @@
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
-A "step" is one pass of the hot path over one batch whose activations / gradients are already resident
-in HBM: ``KFAC.update()`` (factor build, all layers) + ``KFAC.invert(1.0, 1000.0)`` +
-``KFAC.sample_and_replace()`` on a random-init ImageNet ResNet-50 (54 layers, N = 32, synthetic
-3x224x224 inputs).  With N > 1 GPUs the layers are sharded across ranks (disjoint layer groups, replicated
-forward/backward, one RCCL all-gather of the sampled weights per step): total work is fixed, so scaling is
-"strong".  Rank 0 prints ONE JSON line; see DESIGN.md section "Measurement" for every field.
+A "step" is one pass of the hot path over one batch whose activations / gradients are already resident in HBM
+(made by one forward / backward pass on the CPU, so that they are the same in every run): ``KFAC.update()``
+(factor build, all layers) + ``KFAC.invert(1.0, 1000.0)`` + ``KFAC.sample_and_replace()`` on a random-init
+ImageNet ResNet-50 (54 layers, N = 32, synthetic 3x224x224 inputs). With N > 1 GPUs the layers are sharded across
+ranks (disjoint layer groups, replicated forward/backward, one RCCL all-gather of the sampled weights per step):
+total work is fixed, so scaling is "strong". Rank 0 prints ONE JSON line; see DESIGN.md section "Measurement" for
+every field.
 """
 import argparse
+import copy
 import json
 import os
 import sys
@@ -632,6 +634,51 @@ def syrk_source_sha16() -> str:
     return h.hexdigest()[:16]
 
 
+DUMP_SAMPLE = 1 << 20          # entries drawn per output group by --dump-outputs (<= 4 MB each in float32)
+
+
+def _dump_sample(tensors, seed):
+    """float32 values of the concatenation of `tensors` (flattened, in order) at a fixed, seeded, sorted set of indices:
+    the same positions for every run with the same shapes.  Everything when the whole is no larger than the sample."""
+    import numpy as np
+    sizes = [t.numel() for t in tensors]
+    total = sum(sizes)
+    if total <= DUMP_SAMPLE:
+        return torch.cat([t.detach().reshape(-1).float().cpu() for t in tensors]).numpy()
+    idx = np.unique(np.random.default_rng(seed).integers(0, total, size=DUMP_SAMPLE))
+    parts, off = [], 0
+    for t, n in zip(tensors, sizes):
+        lo, hi = np.searchsorted(idx, [off, off + n])
+        if hi > lo:
+            local = torch.from_numpy(idx[lo:hi] - off).to(t.device)
+            parts.append(t.detach().reshape(-1)[local].float().cpu())
+        off += n
+    return torch.cat(parts).numpy()
+
+
+def dump_outputs(out_dir, layers, kfac, owned):
+    """--dump-outputs: what the timed path handed its caller in the last timed step, as DIR/<name>.npy.
+    `weights`: the parameters sample_and_replace() wrote (every layer's weight, then its bias, in layer order);
+    `factor_A` / `factor_G`: KFAC.state (update()); `inverse_A` / `inverse_G`: KFAC.inv_state (invert()), of the layers
+    this rank owns (`factor_layers`, global layer indices).  Each is a fixed, seeded sample of 2^20 entries of the
+    flattened concatenation (float32); `<name>_norms` holds the float64 Frobenius norm of every layer's tensor, over all
+    of its entries.  About 21 MB in all."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    params = [p for l in layers for p in (l.weight, l.bias) if p is not None]
+    keys = [l for _, l in owned]
+    groups = {"weights": params,
+              "factor_A": [kfac.state[l][0] for l in keys], "factor_G": [kfac.state[l][1] for l in keys],
+              "inverse_A": [kfac.inv_state[l][0] for l in keys], "inverse_G": [kfac.inv_state[l][1] for l in keys]}
+    arrays = {"factor_layers": np.array([i for i, _ in owned], dtype=np.float64)}
+    for seed, (name, tensors) in enumerate(groups.items()):
+        arrays[name] = _dump_sample(tensors, seed)
+        arrays[name + "_norms"] = np.array([float(torch.linalg.norm(t.detach().double())) for t in tensors])
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return {"dir": os.path.abspath(out_dir), "arrays": sorted(arrays), "bytes": int(sum(a.nbytes for a in arrays.values()))}
+
+
 def spawn_ranks(args) -> int:
     """`python bench.py --gpus N` without a torchrun environment: start N fresh rank processes (one per GPU) with
     torch.distributed.run and return its exit code.  Called before this process has made any HIP call (torch is
@@ -651,6 +698,8 @@ def spawn_ranks(args) -> int:
         cmd.append("--no-cpu-baseline")
     if args.no_other_configs:
         cmd.append("--no-other-configs")
+    if args.dump_outputs:
+        cmd += ["--dump-outputs", os.path.abspath(args.dump_outputs)]
     env = dict(os.environ)
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     return subprocess.call(cmd, env=env)
@@ -667,8 +716,13 @@ def main():
                     help="skip the untimed-region legs for BASELINE.json's configs 2, 3 and 5 (`other_configs`)")
     ap.add_argument("--cpu-baseline-only", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--cpu-other-only", action="store_true", help=argparse.SUPPRESS)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (sampled weights, factors and inverse "
+                         "factors: fixed seeded samples plus per-layer norms) as DIR/<name>.npy")
     ap.add_argument("--stream-probe", default=None, choices=["none", "before", "after"], help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.stream_probe is not None:               # child of stream_probe_subprocess
         stream_probe(args.stream_probe, args.batch)
         return
@@ -710,15 +764,29 @@ def main():
     torch.manual_seed(seed)
     # BatchNorm in batch-statistics mode: a random-init network in eval mode (running stats 0/1) lets the
     # activations explode with depth, which no trained network does; train mode keeps them O(1)
-    model = models.resnet50().to(dev).train()
+    twin = models.resnet50().train()
+    model = copy.deepcopy(twin).to(dev)
     kfac = KFAC(model)
     layers = kfac._layers()
     x = torch.randn(args.batch, 3, 224, 224, device=dev)
-    logits = model(x)
-    labels = torch.distributions.Categorical(logits=logits.detach()).sample()      # scripts/test.py:39-40
-    loss = torch.nn.functional.cross_entropy(logits, labels)
-    model.zero_grad()
-    loss.backward()                       # activations / gradients of every layer now resident in HBM
+    # The forward / backward pass that produces the step's inputs runs on the CPU twin: the GPU convolution and
+    # BatchNorm kernels of torch are not bitwise reproducible from run to run, the CPU pass is, so every run with the
+    # same arguments feeds the timed path the same activations and gradients (what --dump-outputs relies on).  A KFAC
+    # on the twin records them with the estimator's own hooks; it computes nothing.
+    tap = KFAC(twin)
+    logits = twin(x.cpu())
+    labels = torch.distributions.Categorical(logits=logits.detach().to(dev)).sample()      # scripts/test.py:39-40
+    loss = torch.nn.functional.cross_entropy(logits, labels.cpu())
+    twin.zero_grad()
+    loss.backward()
+    with torch.no_grad():
+        for p, q in zip(model.parameters(), twin.parameters()):
+            p.grad = None if q.grad is None else q.grad.to(dev)
+        for b, c in zip(model.buffers(), twin.buffers()):             # BatchNorm statistics of the pass
+            b.copy_(c)
+    for layer, twin_layer in zip(layers, tap._layers()):
+        kfac.record[layer] = [t.detach().to(dev).contiguous() for t in tap.record[twin_layer]]
+    del tap, twin, logits, loss           # activations / gradients of every layer now resident in HBM
     dims = layer_dims(layers, kfac.record)
     if world > 1:
         kfac.shard = sharding.make_layer_shard(dims, rank, world)
@@ -838,6 +906,9 @@ def main():
             except Exception:
                 traffic = None
 
+    # the last timed step's outputs, before other_configs_gpu() below runs more work on this model and estimator
+    dumped = dump_outputs(args.dump_outputs, layers, kfac, kfac._owned()) if args.dump_outputs and rank == 0 else None
+
     if rank == 0:
         n_layers = len(layers)
         out = {
@@ -881,6 +952,8 @@ def main():
         }
         if rank_phases is not None:
             out["ranks"] = rank_phases
+        if dumped is not None:
+            out["outputs_dumped"] = dumped
         if world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline_subprocess(args.batch)
         if world == 1 and not args.no_other_configs:

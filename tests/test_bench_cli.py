@@ -64,3 +64,61 @@ def test_world_size_must_match_gpus(monkeypatch):
     with pytest.raises(SystemExit) as exc:
         bench.main()
     assert "WORLD_SIZE=2" in str(exc.value.code)
+
+
+def test_dump_outputs_is_passed_to_the_ranks(monkeypatch, tmp_path):
+    bench = load_bench()
+    import subprocess
+    seen = {}
+    monkeypatch.setattr(subprocess, "call", lambda cmd, env=None, **kw: seen.setdefault("cmd", list(cmd)) and 0)
+    monkeypatch.setattr(bench.torch.cuda, "device_count", lambda: 2)
+    for var in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
+        monkeypatch.delenv(var, raising=False)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "2", "--dump-outputs", str(tmp_path / "out")])
+    with pytest.raises(SystemExit):
+        bench.main()
+    tail = seen["cmd"][seen["cmd"].index(os.path.join(ROOT, "bench.py")) + 1:]
+    assert tail[tail.index("--dump-outputs") + 1] == str(tmp_path / "out")
+
+
+def test_zero_steps_is_refused(monkeypatch):
+    bench = load_bench()
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "0"])
+    with pytest.raises(SystemExit) as exc:
+        bench.main()
+    assert exc.value.code == 2
+
+
+def test_dump_outputs_writes_the_same_sample_every_time(tmp_path):
+    """dump_outputs on CPU stand-ins of the estimator: float arrays only, a fixed sample of large outputs, whole small
+    ones, per-layer norms over every entry, identical files for identical inputs, well under 64 MB."""
+    import numpy as np
+    import torch
+    bench = load_bench()
+    torch.manual_seed(0)
+    layers = [torch.nn.Linear(700, 900), torch.nn.Conv2d(64, 96, 3, bias=False), torch.nn.Linear(1200, 10)]
+
+    class Est:
+        state = {l: [torch.randn(k, k), torch.randn(n, n)] for l, k, n in ((layers[0], 701, 900), (layers[1], 576, 96),
+                                                                          (layers[2], 1201, 10))}
+        inv_state = {l: (torch.randn_like(a), torch.randn_like(g)) for l, (a, g) in state.items()}
+    owned = list(enumerate(layers))
+    infos = [bench.dump_outputs(str(tmp_path / f"d{r}"), layers, Est, owned) for r in range(2)]
+    assert infos[0]["bytes"] == infos[1]["bytes"] < 64 << 20
+    names = ["factor_layers"] + [n + s for n in ("weights", "factor_A", "factor_G", "inverse_A", "inverse_G")
+                                 for s in ("", "_norms")]
+    assert sorted(infos[0]["arrays"]) == sorted(names)
+    for name in names:
+        a, b = (np.load(tmp_path / f"d{r}" / f"{name}.npy") for r in range(2))
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, b), name
+    w = np.load(tmp_path / "d0" / "weights.npy")
+    assert w.size == sum(p.numel() for l in layers for p in l.parameters())              # 0.9 M entries: all of them
+    assert np.array_equal(w, torch.cat([p.detach().reshape(-1) for l in layers for p in (l.weight, l.bias)
+                                        if p is not None]).numpy())
+    fa = np.load(tmp_path / "d0" / "factor_A.npy")                                         # 2.1 M entries: a sample
+    assert 0.7 * bench.DUMP_SAMPLE < fa.size <= bench.DUMP_SAMPLE               # distinct indices of 2^20 draws
+    flat = torch.cat([Est.state[l][0].reshape(-1) for l in layers]).numpy()
+    assert np.isin(fa, flat).all()
+    norms = np.load(tmp_path / "d0" / "inverse_G_norms.npy")
+    assert np.allclose(norms, [float(torch.linalg.norm(Est.inv_state[l][1].double())) for l in layers])
+    assert np.array_equal(np.load(tmp_path / "d0" / "factor_layers.npy"), [0.0, 1.0, 2.0])
