@@ -13,7 +13,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc")
 INCLUDE = os.path.normpath(os.path.join(_HERE, "..", "include"))
 LIB_PATH = os.path.join(CSRC, "libcurv_hip.so")
-SOURCES = ["api.cpp", "collective.cpp", "elementwise.hip", "syrk.hip", "syrk_flat.hip", "syrk_corr.hip", "syrk_pre.hip", "syrk_small.hip", "invert.hip", "gemm.hip", "inf.hip", "eigh.hip", "eigh_lowrank.hip"]
+SOURCES = ["api.cpp", "collective.cpp", "elementwise.hip", "syrk.hip", "syrk_flat.hip", "syrk_corr.hip", "syrk_pre.hip", "syrk_small.hip", "group_factor.hip", "invert.hip", "gemm.hip", "inf.hip", "eigh.hip", "eigh_lowrank.hip"]
 HIPCC_FLAGS = ["-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC", "-shared", "-Wall",
                "-Wno-unused-function", "-ldl"]
 
@@ -121,6 +121,17 @@ class curv_factor_desc(ctypes.Structure):
     ]
 
 
+class curv_group_factor_desc(ctypes.Structure):
+    """Mirror of ``curv_group_factor_desc`` in include/curv_hip.h."""
+    _fields_ = [
+        ("src", ctypes.c_void_p), ("dst", ctypes.c_void_p),
+        ("N", ctypes.c_int32), ("C", ctypes.c_int32), ("H", ctypes.c_int32), ("W", ctypes.c_int32),
+        ("groups", ctypes.c_int32), ("kh", ctypes.c_int32), ("kw", ctypes.c_int32), ("sh", ctypes.c_int32),
+        ("sw", ctypes.c_int32), ("ph", ctypes.c_int32), ("pw", ctypes.c_int32),
+        ("has_bias", ctypes.c_int32), ("first", ctypes.c_int32), ("scale", ctypes.c_float),
+    ]
+
+
 class curv_inv_desc(ctypes.Structure):
     """Mirror of ``curv_inv_desc`` in include/curv_hip.h."""
     _fields_ = [("F", ctypes.c_void_p), ("L", ctypes.c_void_p), ("n", ctypes.c_int32), ("reserved", ctypes.c_int32),
@@ -190,6 +201,9 @@ SIGNATURES = {
     "curv_kfac_accumulate": (_i, [_vp, ctypes.POINTER(curv_factor_desc), _i, _vp, _sz]),
     "curv_kfac_accumulate_timed": (_i, [_vp, ctypes.POINTER(curv_factor_desc), _i, _vp, _sz, _vp, _vp]),
     "curv_kfac_accumulate_ex": (_i, [_vp, ctypes.POINTER(curv_factor_desc), _i, _vp, _sz, ctypes.c_uint, _vp, _vp]),
+    "curv_kfac_group_workspace_bytes": (_sz, [ctypes.POINTER(curv_group_factor_desc), _i]),
+    "curv_kfac_group_plan_flops": (_i, [ctypes.POINTER(curv_group_factor_desc), _i, ctypes.POINTER(ctypes.c_longlong)]),
+    "curv_kfac_group_accumulate": (_i, [_vp, ctypes.POINTER(curv_group_factor_desc), _i, _vp, _sz]),
     "curv_event_create": (_vp, []),
     "curv_event_destroy": (None, [_vp]),
     "curv_event_elapsed_ms": (_i, [_vp, _vp, ctypes.POINTER(ctypes.c_float)]),
@@ -232,7 +246,7 @@ SIGNATURES = {
 }
 
 
-ABI_VERSION = 10                     # CURV_ABI_VERSION of include/curv_hip.h
+ABI_VERSION = 11                     # CURV_ABI_VERSION of include/curv_hip.h
 KFAC_TABLE_RESIDENT = 1             # CURV_KFAC_TABLE_RESIDENT
 PATH_AUTO, PATH_SMALL, PATH_GROUPED = 0, 1, 2     # CURV_PATH_* (curv_factor_desc.path_hint)
 SMALL_MAX_FLOP = 2.0e9              # CURV_SMALL_MAX_FLOP

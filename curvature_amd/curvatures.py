@@ -670,6 +670,27 @@ class BlockDiagonal(Curvature):
         self._allgather_sampled()
 
 
+def _groups_of(layer) -> int:
+    """`groups` of a Conv2d (1 for every other layer)."""
+    return int(getattr(layer, "groups", 1)) if layer.__class__.__name__ == 'Conv2d' else 1
+
+
+def _reject_grouped(est, what: str) -> None:
+    """EFB / INF have no eigen-correction for the block-diagonal factors of grouped convolutions (yet)."""
+    names = {mod: name for name, mod in est.model.named_modules()}
+    for layer in est._layers():
+        if _groups_of(layer) > 1:
+            raise NotImplementedError(f"{what}: grouped convolution '{names.get(layer, '?')}' (groups={layer.groups}) is not "
+                                      "supported; select other layer types or use KFAC")
+
+
+def _pairs(first: Tensor, second: Tensor):
+    """(L_A, L_G) of a layer as per-group lists of 2-D views: one pair for an ordinary layer, G for a grouped one."""
+    if first.dim() == 3:
+        return [(first[g], second[g]) for g in range(first.shape[0])]
+    return [(first, second)]
+
+
 class KFAC(Curvature):
     """Kronecker-factored Fisher (curvatures.py:264-392).
 
@@ -688,9 +709,11 @@ class KFAC(Curvature):
             name = layer.__class__.__name__
             if name in self.layer_types:
                 if name in ('Linear', 'Conv2d'):
-                    if name == 'Conv2d' and (tuple(layer.dilation) != (1, 1) or layer.groups != 1):
-                        # the reference silently ignores both (curvatures.py:329)
-                        raise NotImplementedError("KFAC: dilated or grouped convolutions are not supported")
+                    if name == 'Conv2d' and tuple(layer.dilation) != (1, 1):
+                        # the reference silently ignores it (curvatures.py:329)
+                        raise NotImplementedError("KFAC: dilated convolutions are not supported")
+                    # grouped convolutions (groups > 1): block-diagonal KFAC, one Kronecker pair per group (the
+                    # reference ignores `groups` and then fails in _replace): state[layer] = [A, G] stacked (G, n, n)
                     if name == 'Conv2d' and not all(isinstance(p, int) for p in layer.padding):
                         raise NotImplementedError("KFAC: string padding modes are not supported")
                     self.record[layer] = [None, None]
@@ -723,7 +746,7 @@ class KFAC(Curvature):
         (``curvature_amd.factors.compute_factors``): the A side depends only on the layer inputs, so it is
         built once per forward with ``input_weight`` = number of backward passes (``inputs=False`` for the
         others), instead of adding the same matrix again and again."""
-        jobs = []
+        jobs, group_jobs = [], []
         fresh = getattr(self, "_fresh", None)
         if fresh is None:
             fresh = self._fresh = set()              # factors allocated here that nothing has written yet
@@ -743,9 +766,10 @@ class KFAC(Curvature):
                 if g.dtype != torch.float32:
                     raise RuntimeError("KFAC.update expects float32 activations and gradients")
                 g = g.contiguous()
+            groups = _groups_of(layer)
             if layer.__class__.__name__ == 'Conv2d':
                 kernel, stride, padding = layer.kernel_size, layer.stride, layer.padding
-                C, m = layer.in_channels, layer.out_channels
+                C, m = layer.in_channels // groups, layer.out_channels // groups
                 N = (x if x is not None else g).shape[0]
                 if g is not None:
                     L = g.shape[2] * g.shape[3]
@@ -766,11 +790,24 @@ class KFAC(Curvature):
             if layer not in self.state:
                 # a side that is not written by this call must start from zero, not from garbage
                 alloc = torch.empty if (inputs and grads) else torch.zeros
-                self.state[layer] = [alloc(n, n, dtype=torch.float32, device=dev),
-                                     alloc(m, m, dtype=torch.float32, device=dev)]
+                lead = (groups,) if groups > 1 else ()
+                self.state[layer] = [alloc(*lead, n, n, dtype=torch.float32, device=dev),
+                                     alloc(*lead, m, m, dtype=torch.float32, device=dev)]
                 if inputs and grads:
                     fresh.update(((layer, 0), (layer, 1)))
             A, G = self.state[layer]
+            if groups > 1:
+                # one Kronecker pair per group (curv_kfac_group_accumulate); same scales as an ordinary layer
+                if inputs:
+                    first = (layer, 0) in fresh
+                    fresh.discard((layer, 0))
+                    group_jobs.append(ops.GroupFactorJob(x, A, groups, kernel, stride, padding, has_bias,
+                                                         float(input_weight) / (N * L), first))
+                if grads:
+                    first = (layer, 1) in fresh
+                    fresh.discard((layer, 1))
+                    group_jobs.append(ops.GroupFactorJob(g, G, groups, (1, 1), (1, 1), (0, 0), False, float(N) / L, first))
+                continue
             if inputs:
                 first = (layer, 0) in fresh
                 fresh.discard((layer, 0))
@@ -786,6 +823,8 @@ class KFAC(Curvature):
             # flops - on the geometry of ALL selected layers: the hooks record every layer on every rank)
             geoms, known = [], True
             for layer in self._layers():
+                if _groups_of(layer) > 1:                        # built by curv_kfac_group_accumulate
+                    continue
                 forward, backward = self.record[layer]
                 if (inputs and forward is None) or (grads and backward is None):
                     known = False
@@ -805,8 +844,9 @@ class KFAC(Curvature):
             for job in jobs:
                 job.path_hint = hint
         if getattr(self, "_count_flops", False):                 # bench.py: what the launch plan executes
-            self._last_flops = sum(ops.kfac_plan_flops(jobs))
+            self._last_flops = sum(ops.kfac_plan_flops(jobs)) + sum(ops.kfac_group_plan_flops(group_jobs))
         ops.kfac_accumulate(jobs, events=getattr(self, "_timing_events", None))
+        ops.kfac_accumulate_groups(group_jobs)
 
     def restart_accumulation(self) -> None:
         """The next `update()` overwrites the factors of every layer instead of adding to them (the tensors, their
@@ -821,36 +861,100 @@ class KFAC(Curvature):
         """`check=False` (keyword-only extension): skip the read-back of the status words - the call's only host
         synchronisation - and leave them for `check_invert()`; a HIP-graph capture of the step needs that."""
         assert self.state, "State dict is empty. Did you call 'update' prior to this?"
-        factors, adds, muls = [], [], []
+        factors, adds, muls, prev = [], [], [], []
         gindex = self._global_index()
+        stacked, where = {}, []
         for position, (layer, value) in enumerate(self.state.items()):
             # layer index = position among the selected layers in modules() order (== enumerate(state)
             # of the reference, curvatures.py:360, when every layer is owned)
-            n, s = self._hyper(add, multiply, gindex.get(layer, position), max(len(gindex), len(self.state)))
-            for factor in value:
-                factors.append(factor)
-                adds.append(n)
-                muls.append(s)
+            index = gindex.get(layer, position)
+            n, s = self._hyper(add, multiply, index, max(len(gindex), len(self.state)))
+            old = self.inv_state.get(layer, (None, None))
+            for side, factor in enumerate(value):
+                if factor.dim() == 3:
+                    # grouped layer: one descriptor per group slice, written in place into the stacked inverse
+                    out = old[side]
+                    if out is None or out.shape != factor.shape or out.device != factor.device:
+                        out = torch.empty_like(factor)
+                    stacked[(layer, side)] = out
+                    for g in range(factor.shape[0]):
+                        factors.append(factor[g])
+                        prev.append(out[g])
+                        adds.append(n)
+                        muls.append(s)
+                        where.append((layer, index, side, g))
+                else:
+                    factors.append(factor)
+                    prev.append(old[side])
+                    adds.append(n)
+                    muls.append(s)
+                    where.append((layer, index, side, None))
         # outputs of the previous call are overwritten in place (stable addresses keep the cached launch
         # plan of sample_and_replace valid); RuntimeError if a damped factor is not positive definite
-        prev = [t for layer in self.state.keys() for t in self.inv_state.get(layer, (None, None))]
-        chols = ops.chol_inv_lower(factors, adds, muls, check=check, outs=prev)
+        self._invert_where = where if stacked else None
+        try:
+            chols = ops.chol_inv_lower(factors, adds, muls, check=check, outs=prev)
+        except RuntimeError as exc:
+            if stacked:
+                self._raise_not_pd(ops.chol_inv_lower.last_info, exc)
+            raise
         self._invert_info = chols.info
-        for index, layer in enumerate(self.state.keys()):
-            self.inv_state[layer] = (chols[2 * index], chols[2 * index + 1])
+        pos = 0
+        for layer, value in self.state.items():
+            pair = []
+            for side, factor in enumerate(value):
+                if factor.dim() == 3:
+                    pair.append(stacked[(layer, side)])
+                    pos += factor.shape[0]
+                else:
+                    pair.append(chols[pos])
+                    pos += 1
+            self.inv_state[layer] = tuple(pair)
+
+    def _raise_not_pd(self, info: Tensor, cause: Exception):
+        """Re-raise a failed inversion of a model with grouped layers, naming the layer and group of each bad factor."""
+        host = info.cpu()
+        names = {mod: name for name, mod in self.model.named_modules()}
+        bad = []
+        for i in torch.nonzero(host).flatten().tolist():
+            if int(host[i]) < 0:
+                raise cause
+            layer, index, side, g = self._invert_where[i]
+            what = f"layer {index} ({names.get(layer, layer.__class__.__name__)}) factor {'AG'[side]}"
+            bad.append(what if g is None else f"{what} group {g}")
+        raise RuntimeError("cholesky: damped factor(s) not positive-definite: " + "; ".join(bad)) from cause
 
     def check_invert(self) -> None:
         """Raise ``RuntimeError`` if the last ``invert(check=False)`` (or the last replay of a graph that contains it)
         met a damped factor that is not positive definite (curvatures.py:377-383 raises at that point)."""
         info = getattr(self, "_invert_info", None)
         if info is not None:
-            ops.check_chol_info(info)
+            try:
+                ops.check_chol_info(info)
+            except RuntimeError as exc:
+                if getattr(self, "_invert_where", None):
+                    self._raise_not_pd(info, exc)
+                raise
 
     def sample(self, layer: Module, z: Optional[Tensor] = None) -> Tensor:
         """(L_A z L_G^T)^T -> (m, n) (curvatures.py:387-392); `z` (n, m) may be supplied for parity tests."""
         assert self.inv_state, "Inverse state dict is empty. Did you call 'invert' prior to this?"
         first, second = self.inv_state[layer]
-        n, m = first.size(0), second.size(0)
+        n, m = first.size(-1), second.size(-1)
+        if first.dim() == 3:
+            # grouped layer: z (G, n, m); row block g of the (C_out, n) result is (L_A[g] z[g] L_G[g]^T)^T
+            G = first.shape[0]
+            if z is None:
+                z = self._randn(G, n, m, device=first.device)
+            if tuple(z.shape) != (G, n, m):
+                raise RuntimeError(f"KFAC.sample: noise of a grouped layer must be ({G}, {n}, {m})")
+            tmp = torch.empty(G, m, n, dtype=torch.float32, device=first.device)
+            out = torch.empty(G * m, n, dtype=torch.float32, device=first.device)
+            blocks = out.view(G, m, n)
+            pairs = _pairs(first, second)
+            ops.gemm_batched([ops.Gemm(lg, z[g].t(), tmp[g], tri=ops.TRI_A_LOWER) for g, (_, lg) in enumerate(pairs)])
+            ops.gemm_batched([ops.Gemm(tmp[g], la.t(), blocks[g], tri=ops.TRI_B_UPPER) for g, (la, _) in enumerate(pairs)])
+            return out
         if z is None:
             z = self._randn(n, m, device=first.device)
         tmp = torch.empty(m, n, dtype=torch.float32, device=first.device)
@@ -878,27 +982,33 @@ class KFAC(Curvature):
             flat, pos = None, 0
             if noise is None and owned:        # one generator launch for the whole model
                 dev = self.inv_state[owned[0][1]][0].device
-                total = sum(self.inv_state[l][0].size(0) * self.inv_state[l][1].size(0) for _, l in owned)
+                total = sum(self.inv_state[l][0].numel() // self.inv_state[l][0].size(-1) * self.inv_state[l][1].size(-1)
+                            for _, l in owned)
                 flat = torch.empty(total, dtype=torch.float32, device=dev)
             for _, layer in owned:
                 first, second = self.inv_state[layer]
-                n, m = first.size(0), second.size(0)
+                n, m = first.size(-1), second.size(-1)
+                G = first.shape[0] if first.dim() == 3 else 1
                 if noise is not None:
                     z = noise[layer]
                 else:
-                    z = flat[pos:pos + n * m].view(n, m)
-                    pos += n * m
-                tmp = torch.empty(m, n, dtype=torch.float32, device=first.device)
-                stage1.append(ops.Gemm(second, z.t(), tmp, tri=ops.TRI_A_LOWER))
+                    z = flat[pos:pos + G * n * m].view(*((G,) if first.dim() == 3 else ()), n, m)
+                    pos += G * n * m
                 n0 = n - int(layer.bias is not None)
-                w = layer.weight.data.view(m, n0)
-                w_mean = self.model_state_of(layer, 'weight').view(m, n0)
-                la_t = first.t()
-                stage2.append(ops.Gemm(tmp, la_t[:, :n0], w, epilogue=ops.EPI_ADD_E, E=w_mean, tri=ops.TRI_B_UPPER))
-                if layer.bias is not None:
-                    b = layer.bias.data.view(m, 1)
-                    b_mean = self.model_state_of(layer, 'bias').view(m, 1)
-                    stage2.append(ops.Gemm(tmp, la_t[:, n0:], b, epilogue=ops.EPI_ADD_E, E=b_mean))
+                # grouped layer: group g owns weight rows [g m, (g + 1) m) - one pair of products per group
+                ws = layer.weight.data.view(G, m, n0)
+                w_means = self.model_state_of(layer, 'weight').view(G, m, n0)
+                zs = z if G > 1 else [z]
+                for g, (la, lg) in enumerate(_pairs(first, second)):
+                    tmp = torch.empty(m, n, dtype=torch.float32, device=first.device)
+                    stage1.append(ops.Gemm(lg, zs[g].t(), tmp, tri=ops.TRI_A_LOWER))
+                    la_t = la.t()
+                    stage2.append(ops.Gemm(tmp, la_t[:, :n0], ws[g], epilogue=ops.EPI_ADD_E, E=w_means[g],
+                                           tri=ops.TRI_B_UPPER))
+                    if layer.bias is not None:
+                        b = layer.bias.data.view(G, m, 1)[g]
+                        b_mean = self.model_state_of(layer, 'bias').view(G, m, 1)[g]
+                        stage2.append(ops.Gemm(tmp, la_t[:, n0:], b, epilogue=ops.EPI_ADD_E, E=b_mean))
             # largest products first: the tail of each launch is then made of the short tiles
             stage1.sort(key=lambda j: -(j.A.shape[0] * j.A.shape[1] * j.B.shape[1]))
             stage2.sort(key=lambda j: -(j.A.shape[0] * j.A.shape[1] * j.B.shape[1]))
@@ -937,37 +1047,44 @@ class KFAC(Curvature):
         if plan is None:
             cache.clear()                                    # one bank's worth of buffers at a time
             dev = self.inv_state[owned[0][1]][0].device
-            total = sum(self.inv_state[l][0].size(0) * self.inv_state[l][1].size(0) for _, l in owned)
+            total = sum(self.inv_state[l][0].numel() // self.inv_state[l][0].size(-1) * self.inv_state[l][1].size(-1)
+                        for _, l in owned)
             flat = torch.empty(S * total, dtype=torch.float32, device=dev) if noise is None else None
             stage_a, stage_b, weights, biases, keep = [], [], {}, {}, []
             pos = 0
             for _, layer in owned:
                 first, second = self.inv_state[layer]
-                n, m = first.size(0), second.size(0)
+                n, m = first.size(-1), second.size(-1)
+                grouped = first.dim() == 3
+                G = first.shape[0] if grouped else 1
+                shape = (S, G, n, m) if grouped else (S, n, m)
                 if noise is not None:
                     z = noise[layer]
-                    if tuple(z.shape) != (S, n, m):
-                        raise RuntimeError(f"sample_many: noise of a layer must be ({S}, {n}, {m})")
-                    zt = z.transpose(1, 2).contiguous().view(S * m, n)          # rows (s, j): z_s^T
+                    if tuple(z.shape) != shape:
+                        raise RuntimeError(f"sample_many: noise of a layer must be {shape}")
+                    z = z.view(S, G, n, m)
+                    zts = [z[:, g].transpose(1, 2).contiguous().view(S * m, n) for g in range(G)]   # rows (s, j): z_s^T
                 else:
-                    zt = flat[pos:pos + S * n * m].view(S * m, n)                 # iid: drawn directly as z_s^T
-                    pos += S * n * m
-                V = torch.empty(n, S * m, dtype=torch.float32, device=dev)
-                stage_a.append(ops.Gemm(first, zt.t(), V, tri=ops.TRI_A_LOWER))     # V = L_A [z_1 | ... | z_S]
+                    zts = list(flat[pos:pos + S * G * n * m].view(G, S * m, n))       # iid: drawn directly as z_s^T
+                    pos += S * G * n * m
                 has_bias = layer.bias is not None
                 n0 = n - int(has_bias)
-                wb = torch.empty(S, m, n0, dtype=torch.float32, device=dev)
-                bb = torch.empty(S, m, dtype=torch.float32, device=dev) if has_bias else None
-                w_mean = self.model_state_of(layer, 'weight').view(m, n0)
-                b_mean = self.model_state_of(layer, 'bias').view(m, 1) if has_bias else None
-                for k in range(S):
-                    Vs_t = V[:, k * m:(k + 1) * m].t()                            # (m, n) view of V_s^T: K-contiguous columns
-                    stage_b.append(ops.Gemm(second, Vs_t[:, :n0], wb[k], epilogue=ops.EPI_ADD_E, E=w_mean, tri=ops.TRI_A_LOWER))
-                    if has_bias:
-                        stage_b.append(ops.Gemm(second, Vs_t[:, n0:], bb[k].view(m, 1), epilogue=ops.EPI_ADD_E, E=b_mean,
-                                                tri=ops.TRI_A_LOWER))
+                wb = torch.empty(S, G * m, n0, dtype=torch.float32, device=dev)
+                bb = torch.empty(S, G * m, dtype=torch.float32, device=dev) if has_bias else None
+                w_mean = self.model_state_of(layer, 'weight').view(G, m, n0)
+                b_mean = self.model_state_of(layer, 'bias').view(G, m, 1) if has_bias else None
+                for g, ((la, lg), zt) in enumerate(zip(_pairs(first, second), zts)):
+                    V = torch.empty(n, S * m, dtype=torch.float32, device=dev)
+                    stage_a.append(ops.Gemm(la, zt.t(), V, tri=ops.TRI_A_LOWER))     # V = L_A [z_1 | ... | z_S]
+                    for k in range(S):
+                        Vs_t = V[:, k * m:(k + 1) * m].t()                        # (m, n) view of V_s^T: K-contiguous columns
+                        stage_b.append(ops.Gemm(lg, Vs_t[:, :n0], wb[k].view(G, m, n0)[g], epilogue=ops.EPI_ADD_E,
+                                                E=w_mean[g], tri=ops.TRI_A_LOWER))
+                        if has_bias:
+                            stage_b.append(ops.Gemm(lg, Vs_t[:, n0:], bb[k].view(G, m, 1)[g], epilogue=ops.EPI_ADD_E,
+                                                    E=b_mean[g], tri=ops.TRI_A_LOWER))
+                    keep += [zt, V]
                 weights[layer], biases[layer] = wb, bb
-                keep += [zt, V]
             stage_a.sort(key=lambda j: -(j.A.shape[0] * j.A.shape[1] * j.B.shape[1]))
             stage_b.sort(key=lambda j: -(j.A.shape[0] * j.A.shape[1] * j.B.shape[1]))
             plan = (flat, ops.GemmPlan(stage_a), ops.GemmPlan(stage_b), SampleBank(S, weights, biases), keep)
@@ -1054,6 +1171,7 @@ class EFB(Curvature):
     def __init__(self, model: Union[Module, Sequential], factors: Dict[Module, Tensor],
                  layer_types: Union[List[str], str] = None, *, shard=None, eigvecs=None):
         super().__init__(model, layer_types, shard=shard)
+        _reject_grouped(self, "EFB")
         if eigvecs is None:
             from .utils import get_eigenvectors
             if shard is not None:
@@ -1268,6 +1386,7 @@ class INF(Curvature):
                  factors: Dict[Module, Tensor], lambdas: Dict[Module, Tensor],
                  layer_types: Union[List[str], str] = None, *, shard=None, eigvecs=None):
         super().__init__(model, layer_types, shard=shard)
+        _reject_grouped(self, "INF")
         assert diags.keys() == factors.keys() == lambdas.keys()
         if shard is not None:
             mine = {l for _, l in self._owned()}

@@ -1,4 +1,5 @@
-"""Plain ``torch.nn`` definitions of the benchmark networks (LeNet-5, ImageNet ResNet-18 / ResNet-50, DenseNet-121 / 161).
+"""Plain ``torch.nn`` definitions of the benchmark networks (LeNet-5, ImageNet ResNet-18 / ResNet-50, DenseNet-121 / 161,
+and the grouped-convolution networks MobileNetV2 / ResNeXt-50 32x4d).
 
 torchvision is not available on the target image, and the estimators select layers by class NAME
 (``Conv2d`` / ``Linear``; curvature/curvatures.py:121, :298), so these are ordinary torch modules with
@@ -100,6 +101,121 @@ def resnet18(num_classes: int = 1000) -> ResNet:
 
 def resnet50(num_classes: int = 1000) -> ResNet:
     return ResNet((3, 4, 6, 3), bottleneck=True, num_classes=num_classes)
+
+
+class _GroupedBottleneck(nn.Module):
+    """ResNeXt bottleneck (torchvision's Bottleneck with groups / width_per_group): 1x1, grouped 3x3 (stride here), 1x1."""
+
+    def __init__(self, cin: int, planes: int, stride: int, groups: int, base_width: int):
+        super().__init__()
+        width = int(planes * (base_width / 64.0)) * groups
+        cout = planes * 4
+        self.conv1, self.bn1 = _conv(cin, width, 1), nn.BatchNorm2d(width)
+        self.conv2 = nn.Conv2d(width, width, 3, stride=stride, padding=1, groups=groups, bias=False)
+        self.bn2 = nn.BatchNorm2d(width)
+        self.conv3, self.bn3 = _conv(width, cout, 1), nn.BatchNorm2d(cout)
+        self.relu = nn.ReLU(inplace=True)
+        self.downsample = None
+        if stride != 1 or cin != cout:
+            self.downsample = nn.Sequential(_conv(cin, cout, 1, stride), nn.BatchNorm2d(cout))
+
+    def forward(self, x):
+        identity = x if self.downsample is None else self.downsample(x)
+        out = self.relu(self.bn1(self.conv1(x)))
+        out = self.relu(self.bn2(self.conv2(out)))
+        out = self.bn3(self.conv3(out))
+        return self.relu(out + identity)
+
+
+class ResNeXt(nn.Module):
+    """ImageNet ResNeXt with torchvision's module registration order (grouped 3x3 convolutions in every unit)."""
+
+    def __init__(self, depths: Sequence[int], groups: int, width_per_group: int, num_classes: int = 1000):
+        super().__init__()
+        self.conv1 = nn.Conv2d(3, 64, 7, stride=2, padding=3, bias=False)
+        self.bn1 = nn.BatchNorm2d(64)
+        self.relu = nn.ReLU(inplace=True)
+        self.maxpool = nn.MaxPool2d(3, stride=2, padding=1)
+        cin = 64
+        for stage, (depth, planes) in enumerate(zip(depths, (64, 128, 256, 512))):
+            units = []
+            for u in range(depth):
+                units.append(_GroupedBottleneck(cin, planes, 2 if (u == 0 and stage > 0) else 1, groups, width_per_group))
+                cin = planes * 4
+            setattr(self, f"layer{stage + 1}", nn.Sequential(*units))
+        self.avgpool = nn.AdaptiveAvgPool2d((1, 1))
+        self.fc = nn.Linear(cin, num_classes)
+        for mod in self.modules():
+            if isinstance(mod, nn.Conv2d):
+                nn.init.kaiming_normal_(mod.weight, mode="fan_out", nonlinearity="relu")
+            elif isinstance(mod, nn.BatchNorm2d):
+                nn.init.constant_(mod.weight, 1)
+                nn.init.constant_(mod.bias, 0)
+
+    def forward(self, x):
+        x = self.maxpool(self.relu(self.bn1(self.conv1(x))))
+        x = self.layer4(self.layer3(self.layer2(self.layer1(x))))
+        return self.fc(self.avgpool(x).flatten(1))
+
+
+def resnext50_32x4d(num_classes: int = 1000) -> ResNeXt:
+    return ResNeXt((3, 4, 6, 3), groups=32, width_per_group=4, num_classes=num_classes)
+
+
+def _conv_bn_relu(cin: int, cout: int, k: int, stride: int = 1, groups: int = 1) -> nn.Sequential:
+    return nn.Sequential(nn.Conv2d(cin, cout, k, stride, (k - 1) // 2, groups=groups, bias=False), nn.BatchNorm2d(cout),
+                         nn.ReLU6(inplace=True))
+
+
+class _InvertedResidual(nn.Module):
+    """MobileNetV2 unit (torchvision's InvertedResidual): 1x1 expansion (t != 1), depthwise 3x3, linear 1x1."""
+
+    def __init__(self, cin: int, cout: int, stride: int, expand: int):
+        super().__init__()
+        hidden = cin * expand
+        self.use_res_connect = stride == 1 and cin == cout
+        layers = [_conv_bn_relu(cin, hidden, 1)] if expand != 1 else []
+        layers += [_conv_bn_relu(hidden, hidden, 3, stride, groups=hidden),
+                   nn.Conv2d(hidden, cout, 1, bias=False), nn.BatchNorm2d(cout)]
+        self.conv = nn.Sequential(*layers)
+
+    def forward(self, x):
+        return x + self.conv(x) if self.use_res_connect else self.conv(x)
+
+
+class MobileNetV2(nn.Module):
+    """MobileNetV2 (width 1.0) with torchvision's registration order: 17 depthwise 3x3 convolutions."""
+
+    def __init__(self, num_classes: int = 1000):
+        super().__init__()
+        settings = [(1, 16, 1, 1), (6, 24, 2, 2), (6, 32, 3, 2), (6, 64, 4, 2), (6, 96, 3, 1), (6, 160, 3, 2), (6, 320, 1, 1)]
+        features = [_conv_bn_relu(3, 32, 3, 2)]
+        cin = 32
+        for t, c, n, s in settings:
+            for i in range(n):
+                features.append(_InvertedResidual(cin, c, s if i == 0 else 1, t))
+                cin = c
+        features.append(_conv_bn_relu(cin, 1280, 1))
+        self.features = nn.Sequential(*features)
+        self.classifier = nn.Sequential(nn.Dropout(0.2), nn.Linear(1280, num_classes))
+        for mod in self.modules():
+            if isinstance(mod, nn.Conv2d):
+                nn.init.kaiming_normal_(mod.weight, mode="fan_out")
+            elif isinstance(mod, nn.BatchNorm2d):
+                nn.init.ones_(mod.weight)
+                nn.init.zeros_(mod.bias)
+            elif isinstance(mod, nn.Linear):
+                nn.init.normal_(mod.weight, 0, 0.01)
+                nn.init.zeros_(mod.bias)
+
+    def forward(self, x):
+        x = self.features(x)
+        x = nn.functional.adaptive_avg_pool2d(x, (1, 1)).flatten(1)
+        return self.classifier(x)
+
+
+def mobilenet_v2(num_classes: int = 1000) -> MobileNetV2:
+    return MobileNetV2(num_classes)
 
 
 class _DenseUnit(nn.Module):

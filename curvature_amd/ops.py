@@ -185,6 +185,71 @@ def kfac_accumulate(jobs: Sequence[FactorJob], events=None) -> None:
     _lib.check(rc, "curv_kfac_accumulate")
 
 
+class GroupFactorJob:
+    """The stacked Kronecker factors of a grouped convolution: dst[g] (+)= scale * unfold(src_g) unfold(src_g)^T, src_g
+    the g-th of `groups` equal channel slices of src (curv_kfac_group_accumulate)."""
+    __slots__ = ("src", "dst", "groups", "kernel", "stride", "padding", "has_bias", "scale", "first")
+
+    def __init__(self, src, dst, groups, kernel=(1, 1), stride=(1, 1), padding=(0, 0), has_bias=False, scale=1.0,
+                 first=False):
+        self.src, self.dst, self.groups = src, dst, int(groups)
+        self.kernel, self.stride, self.padding = tuple(kernel), tuple(stride), tuple(padding)
+        self.has_bias, self.scale, self.first = bool(has_bias), float(scale), bool(first)
+
+
+def _group_descs(jobs: Sequence[GroupFactorJob], check_tensors: bool = True):
+    arr = (_lib.curv_group_factor_desc * len(jobs))()
+    for d, j in zip(arr, jobs):
+        if check_tensors:
+            _require_gpu(j.src, j.dst)
+            if j.src.dim() != 4:
+                raise RuntimeError("grouped factor source must be (N,C,H,W)")
+        N, C, H, W = j.src.shape if check_tensors else j.src
+        if check_tensors:
+            dim = C // j.groups * j.kernel[0] * j.kernel[1] + int(j.has_bias)
+            if C % j.groups or tuple(j.dst.shape) != (j.groups, dim, dim):
+                raise RuntimeError(f"grouped factor destination must be ({j.groups},{dim},{dim}), got {tuple(j.dst.shape)}")
+            d.src, d.dst = j.src.data_ptr(), j.dst.data_ptr()
+        d.N, d.C, d.H, d.W, d.groups = int(N), int(C), int(H), int(W), j.groups
+        d.kh, d.kw = j.kernel
+        d.sh, d.sw = j.stride
+        d.ph, d.pw = j.padding
+        d.has_bias, d.first, d.scale = int(j.has_bias), int(j.first), j.scale
+    return arr
+
+
+def kfac_group_plan_flops(jobs: Sequence[GroupFactorJob]) -> List[int]:
+    """Multiply-add FLOPs (2 per multiply-add) the grouped build executes for each job (curv_kfac_group_plan_flops, host
+    only).  `job.src` may be a tensor or just its (N, C, H, W) shape."""
+    if not jobs:
+        return []
+    arr = _group_descs(jobs, check_tensors=all(isinstance(j.src, torch.Tensor) for j in jobs))
+    out = (ctypes.c_longlong * len(jobs))()
+    _lib.check(_lib.lib().curv_kfac_group_plan_flops(arr, len(jobs), out), "curv_kfac_group_plan_flops")
+    return [int(v) for v in out]
+
+
+def kfac_accumulate_groups(jobs: Sequence[GroupFactorJob], events=None) -> None:
+    """Factor build of grouped convolutions (curv_kfac_group_accumulate): a Gram launch per kernel class and one reduce
+    launch per batch of factors, on the current stream.  Scratch from `workspace` (so CURV_DEBUG_POISON covers it).
+    `events` = (start, stop) ``torch.cuda.Event``s (enable_timing) are recorded around the whole build."""
+    if not jobs:
+        return
+    n = len(jobs)
+    arr = _group_descs(jobs)
+    L = _lib.lib()
+    need = L.curv_kfac_group_workspace_bytes(arr, n)
+    if need == 0:
+        _lib.check(_lib.ERR_INVALID, "curv_kfac_group_workspace_bytes")
+    ws = workspace(need, jobs[0].src.device, "kfac_groups")
+    if events is not None:
+        events[0].record()
+    _lib.check(L.curv_kfac_group_accumulate(_lib.stream_ptr(), arr, n, ws.data_ptr(), ws.numel()),
+               "curv_kfac_group_accumulate")
+    if events is not None:
+        events[1].record()
+
+
 def rsqrt_affine(value: torch.Tensor, add: float, multiply: float, out: Optional[torch.Tensor] = None):
     _require_gpu(value, out)
     if out is None:

@@ -52,13 +52,19 @@ def rank_cost(dims: Sequence[Sequence[float]], estimator: str = "kfac", rank: in
     (ResNet layers at rank 100: 3400-4200), ~7.5e-14 s per (a b)^3, again bounded below by the largest one's chain."""
     if not dims:
         return 0.0
+    # a grouped convolution's entry carries its group count fifth: (n_g, m_g, K, build flops of all groups, G); its
+    # sampling and inversion cost is the sum over its G Kronecker pairs
+    reps = [d[4] if len(d) > 4 else 1 for d in dims]
+    count = sum(reps)
     flops = sum(d[3] if len(d) > 3 else (d[0] * (d[0] + 1.0) + d[1] * (d[1] + 1.0)) * d[2] for d in dims)
     build = 0.25e-3 + 0.035e-3 * min(len(dims), 10) + flops / 100e12
-    sample = 0.2e-3 + sum(2.0 * (d[0] * d[0] * d[1] + d[0] * d[1] * d[1]) for d in dims) / 200e12 + 2e-6 * len(dims)
-    chain = max(max(d[0], d[1]) for d in dims) / 64.0 * (34.5e-6 if 2 * len(dims) <= 64 else 40e-6)
+    sample = 0.2e-3 + sum(r * 2.0 * (d[0] * d[0] * d[1] + d[0] * d[1] * d[1]) for d, r in zip(dims, reps)) / 200e12 \
+        + 2e-6 * count
+    chain = max(max(d[0], d[1]) for d in dims) / 64.0 * (34.5e-6 if 2 * count <= 64 else 40e-6)
     # (the triangular inverse runs in fp32 off the chain, the far updates through LDS-DMA: 6.45 ms for the 108 ResNet-50
     # factors, 2.48 ms for one 4608^2)
-    invert = 0.2e-3 + 0.7 * chain + sum((2.0 / 3.0) * (d[0] ** 3 + d[1] ** 3) for d in dims) / 75e12 + 6e-6 * len(dims)
+    invert = 0.2e-3 + 0.7 * chain + sum(r * (2.0 / 3.0) * (d[0] ** 3 + d[1] ** 3) for d, r in zip(dims, reps)) / 75e12 \
+        + 6e-6 * count
     total = build + invert + sample
     if estimator in ("efb", "inf"):
         n3 = sum(float(d[0]) ** 3 + float(d[1]) ** 3 for d in dims)
@@ -81,6 +87,8 @@ def layer_geometry(layer, x_shape: Sequence[int], g_shape: Sequence[int]):
         (kh, kw), (sh, sw), (ph, pw) = layer.kernel_size, layer.stride, layer.padding
         a = dict(N=N, C=C, H=H, W=W, kh=kh, kw=kw, sh=sh, sw=sw, ph=ph, pw=pw, has_bias=bias)
         g = dict(N=g_shape[0], C=g_shape[1], H=g_shape[2], W=g_shape[3], kh=1, kw=1, sh=1, sw=1, ph=0, pw=0, has_bias=0)
+        if getattr(layer, "groups", 1) > 1:               # curv_group_factor_desc fields: C stays the total count
+            a["groups"] = g["groups"] = int(layer.groups)
     else:
         rows = 1
         for v in x_shape[:-1]:
@@ -99,6 +107,24 @@ def kfac_build_flops(geometries: Sequence[dict]) -> List[int]:
     n = len(geometries)
     if n == 0:
         return []
+    grouped = [i for i, d in enumerate(geometries) if d.get("groups", 1) > 1]
+    if grouped:                                           # grouped convolutions: curv_kfac_group_plan_flops
+        garr = (_lib.curv_group_factor_desc * len(grouped))()
+        for i, a in zip(grouped, garr):
+            for k, v in geometries[i].items():
+                setattr(a, k, int(v))
+            a.scale = 1.0
+        gout = (ctypes.c_longlong * len(grouped))()
+        _lib.check(_lib.lib().curv_kfac_group_plan_flops(garr, len(grouped), gout), "curv_kfac_group_plan_flops")
+        in_grouped = set(grouped)
+        rest = [i for i in range(n) if i not in in_grouped]
+        plain = kfac_build_flops([geometries[i] for i in rest])
+        out = [0] * n
+        for i, v in zip(grouped, gout):
+            out[i] = int(v)
+        for i, v in zip(rest, plain):
+            out[i] = v
+        return out
     arr = (_lib.curv_factor_desc * n)()
     for d, a in zip(geometries, arr):
         for k, v in d.items():
@@ -121,13 +147,17 @@ def layer_dims(layers, shapes) -> List[tuple]:
     dims = []
     for i, layer in enumerate(layers):
         a, g = geoms[2 * i], geoms[2 * i + 1]
-        n = a["C"] * a["kh"] * a["kw"] + a["has_bias"]
+        G = a.get("groups", 1)
+        n = a["C"] // G * a["kh"] * a["kw"] + a["has_bias"]
         if layer.__class__.__name__ == "Conv2d":
             (kh, kw), (sh, sw), (ph, pw) = layer.kernel_size, layer.stride, layer.padding
             K = a["N"] * ((a["H"] + 2 * ph - kh) // sh + 1) * ((a["W"] + 2 * pw - kw) // sw + 1)
         else:
             K = a["N"]
-        dims.append((n, g["C"], K, float(flops[2 * i] + flops[2 * i + 1])))
+        if G > 1:
+            dims.append((n, g["C"] // G, K, float(flops[2 * i] + flops[2 * i + 1]), G))
+        else:
+            dims.append((n, g["C"], K, float(flops[2 * i] + flops[2 * i + 1])))
     return dims
 
 

@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define CURV_ABI_VERSION 10
+#define CURV_ABI_VERSION 11
 
 #define CURV_OK 0
 #define CURV_ERR_NOT_PD 1
@@ -68,8 +68,8 @@ int curv_init_streams(void);
  *   Linear           : src = (N,C) viewed as (N,C,1,1); A: scale = 1/N, G: scale = N
  * `dst` is the (dim x dim) fp32 factor, dim = C*kh*kw + has_bias.  `first` != 0 overwrites dst
  * (the reference's `self.state[layer] = [...]` at :350), 0 accumulates (`+=` at :347-348).
- * The result is exactly symmetric.  Dilation and groups are not representable: the reference
- * ignores them (:329), callers must reject such layers.
+ * The result is exactly symmetric.  Dilation is not representable (the reference ignores it, :329): callers must
+ * reject such layers.  Grouped convolutions have a build of their own, curv_kfac_group_accumulate below.
  * ---------------------------------------------------------------------------------------------- */
 typedef struct curv_factor_desc {
   const float* src;
@@ -128,6 +128,48 @@ int curv_kfac_plan_info(const curv_factor_desc* descs, int n_factors, long long*
  * returns. */
 int curv_kfac_accumulate(void* stream, const curv_factor_desc* descs, int n_factors, void* workspace,
                          size_t workspace_bytes);
+
+/* ------------------------------------------------------------------------------------------------
+ * KFAC factor build of a GROUPED convolution (ABI 11, csrc/group_factor.hip): one Kronecker pair per group.
+ *
+ * A Conv2d with `groups` = G is G independent convolutions on channel slices; its block-diagonal KFAC stacks G
+ * factors: dst is a contiguous (G, n_g, n_g) fp32 tensor, n_g = cg kh kw + has_bias with cg = C / G, and
+ *   dst[g] (+)= scale * X_g X_g^T
+ * where X_g is the implicit im2col (rows (c, kh, kw), columns (n, oh, ow)) of input-channel slice [g cg, (g + 1) cg)
+ * of `src` (N, C, H, W) - C is the TOTAL channel count - plus the row of ones when `has_bias`: exactly what
+ * curv_kfac_accumulate computes for a Conv2d(cg, ., kernel, stride, padding) fed that slice.  The G side is the same
+ * entry with kh = kw = 1, stride 1, padding 0, src = grad_output (N, C_out, Ho, Wo), has_bias = 0.
+ * `scale`, `first`: as for curv_factor_desc.  Dilation is not representable.
+ * Deterministic: fixed-order sums, no atomics, and every launch parameter of a factor follows from its own geometry,
+ * so its bits do not depend on the other factors of the call.  Never reads outside `src`; enqueues on `stream` only
+ * and never waits on the host (graph capture works).
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct curv_group_factor_desc {
+  const float* src;
+  float* dst;
+  int32_t N, C, H, W;
+  int32_t groups, kh, kw, sh, sw, ph, pw;
+  int32_t has_bias;
+  int32_t first;
+  float scale;
+} curv_group_factor_desc;
+
+/* Device scratch needed by curv_kfac_group_accumulate for these factors (bytes); 0 with the error text set for an
+ * invalid geometry.  Host only: src / dst are not read. */
+size_t curv_kfac_group_workspace_bytes(const curv_group_factor_desc* descs, int n_factors);
+
+/* Host only: the multiply-add FLOPs (2 per multiply-add) the plan executes per factor, written to out[0 .. n_factors)
+ * (sharding cost model, tools).  Narrow groups (cg kh kw <= 16): (P (P + 1) / 2 + P) K G x 2 with P = cg kh kw and
+ * K = N Ho Wo; wide groups: the sum over the groups of what curv_kfac_plan_info reports for each group's own factor. */
+int curv_kfac_group_plan_flops(const curv_group_factor_desc* descs, int n_factors, long long* out);
+
+/* The build.  Narrow groups: a Gram pass per patch size (one thread holds the group's whole lower triangle) over slices
+ * of output pixels, then one reduce pass that sums the slices in order, adds the bias row and
+ * corner, scales, writes or adds dst and mirrors the upper triangle.  Wide groups (cg kh kw > 16): a group-major copy
+ * of src in the workspace, then one curv_kfac_accumulate call per factor with one descriptor per group (its plan
+ * depends on that factor alone).  The workspace must be 256-byte aligned.  `descs` is a host array. */
+int curv_kfac_group_accumulate(void* stream, const curv_group_factor_desc* descs, int n_factors, void* workspace,
+                               size_t workspace_bytes);
 
 /* Same, recording HIP events (from curv_event_create) on `stream` around EVERYTHING the call enqueues behind the
  * descriptor-table uploads (padding / pre-tiling passes, the MFMA kernels, the k-slice reductions, the 3x3 assembly), so
