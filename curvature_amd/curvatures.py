@@ -684,6 +684,18 @@ def _reject_grouped(est, what: str) -> None:
                                       "supported; select other layer types or use KFAC")
 
 
+def _factor_source(t: Tensor, groups: int) -> Tensor:
+    """A recorded activation / gradient as the factor build takes it: contiguous; float32 or (ordinary layers)
+    bfloat16 / float16.  A grouped layer's half-precision side becomes a float32 copy on the device: the grouped build
+    (curv_kfac_group_accumulate) has no half-precision form."""
+    t = t.detach()
+    if t.dtype not in (torch.float32, torch.bfloat16, torch.float16):
+        raise RuntimeError(f"KFAC.update expects float32, bfloat16 or float16 activations and gradients, got {t.dtype}")
+    if groups > 1 and t.dtype != torch.float32:
+        return t.float().contiguous()
+    return t.contiguous()
+
+
 def _pairs(first: Tensor, second: Tensor):
     """(L_A, L_G) of a layer as per-group lists of 2-D views: one pair for an ordinary layer, G for a grouped one."""
     if first.dim() == 3:
@@ -738,15 +750,28 @@ class KFAC(Curvature):
     def _save_output(self, module, grad_output):
         self.record[module][1] = grad_output         # raw; the reference stores grad * N (curvatures.py:310)
 
-    def update(self, batch_size: int = None, *, inputs: bool = True, grads: bool = True, input_weight: float = 1.0):
+    def update(self, batch_size: int = None, *, inputs: bool = True, grads: bool = True, input_weight: float = 1.0,
+               grad_scale: float = 1.0):
         """A += X X^T / (N L), G += (N g)(N g)^T / (N L) for every selected layer: one grouped launch.
 
         The keyword-only arguments extend the reference's ``update(batch_size)`` (curvatures.py:312) for
         Monte-Carlo Fisher loops that run several backward passes per forward pass
         (``curvature_amd.factors.compute_factors``): the A side depends only on the layer inputs, so it is
         built once per forward with ``input_weight`` = number of backward passes (``inputs=False`` for the
-        others), instead of adding the same matrix again and again."""
-        jobs, group_jobs = [], []
+        others), instead of adding the same matrix again and again.
+
+        Mixed precision: each side is routed by the dtype of its recorded tensor.  float32 goes to the fp32 build;
+        bfloat16 / float16 (a model run under ``torch.autocast``) to the half-precision MFMA build
+        (``ops.kfac_accumulate_half``), which computes the same factor as the fp32 build of the upcast tensor up to
+        the order of the sums.  A grouped convolution's half-precision side is copied to float32 on the device and
+        built by the grouped fp32 kernels (not on the half-precision kernel).  Any other dtype raises RuntimeError.
+        ``grad_scale``: the loss scale of a ``torch.cuda.amp.GradScaler`` whose scaled loss produced the recorded
+        gradients; the G side is divided by ``grad_scale ** 2``.  The caller skips ``update()`` on the steps the scaler
+        skips (non-finite gradients)."""
+        jobs, group_jobs, half_jobs = [], [], []
+        if not grad_scale > 0:
+            raise ValueError(f"KFAC.update: grad_scale must be positive, got {grad_scale}")
+        g_div = float(grad_scale) ** 2
         fresh = getattr(self, "_fresh", None)
         if fresh is None:
             fresh = self._fresh = set()              # factors allocated here that nothing has written yet
@@ -756,17 +781,11 @@ class KFAC(Curvature):
                 raise RuntimeError("KFAC.update: no recorded forward/backward pass for a selected layer")
             has_bias = layer.bias is not None
             x = g = None
-            if forward is not None:
-                x = forward.detach()
-                if x.dtype != torch.float32:
-                    raise RuntimeError("KFAC.update expects float32 activations and gradients")
-                x = x.contiguous()
-            if backward is not None:
-                g = backward.detach()
-                if g.dtype != torch.float32:
-                    raise RuntimeError("KFAC.update expects float32 activations and gradients")
-                g = g.contiguous()
             groups = _groups_of(layer)
+            if forward is not None:
+                x = _factor_source(forward, groups)
+            if backward is not None:
+                g = _factor_source(backward, groups)
             if layer.__class__.__name__ == 'Conv2d':
                 kernel, stride, padding = layer.kernel_size, layer.stride, layer.padding
                 C, m = layer.in_channels // groups, layer.out_channels // groups
@@ -806,16 +825,24 @@ class KFAC(Curvature):
                 if grads:
                     first = (layer, 1) in fresh
                     fresh.discard((layer, 1))
-                    group_jobs.append(ops.GroupFactorJob(g, G, groups, (1, 1), (1, 1), (0, 0), False, float(N) / L, first))
+                    group_jobs.append(ops.GroupFactorJob(g, G, groups, (1, 1), (1, 1), (0, 0), False,
+                                                         float(N) / L / g_div, first))
                 continue
             if inputs:
                 first = (layer, 0) in fresh
                 fresh.discard((layer, 0))
-                jobs.append(ops.FactorJob(x, A, kernel, stride, padding, has_bias, float(input_weight) / (N * L), first))
+                if x.dtype == torch.float32:
+                    jobs.append(ops.FactorJob(x, A, kernel, stride, padding, has_bias, float(input_weight) / (N * L), first))
+                else:
+                    half_jobs.append(ops.HalfFactorJob(x, A, kernel, stride, padding, has_bias,
+                                                       float(input_weight) / (N * L), first))
             if grads:
                 first = (layer, 1) in fresh
                 fresh.discard((layer, 1))
-                jobs.append(ops.FactorJob(g, G, (1, 1), (1, 1), (0, 0), False, float(N) / L, first))
+                if g.dtype == torch.float32:
+                    jobs.append(ops.FactorJob(g, G, (1, 1), (1, 1), (0, 0), False, float(N) / L / g_div, first))
+                else:
+                    half_jobs.append(ops.HalfFactorJob(g, G, (1, 1), (1, 1), (0, 0), False, float(N) / L / g_div, first))
         if self.shard is not None and self.shard.world > 1:
             # the launch form is a property of the MODEL, not of this rank's share: a share under the small-launch threshold
             # would otherwise sum its factors in another order than the unsharded run (which is over it)
@@ -829,24 +856,29 @@ class KFAC(Curvature):
                 if (inputs and forward is None) or (grads and backward is None):
                     known = False
                     break
+                # half-precision sides are built by curv_kfac16_accumulate, whose plans are per factor
+                fwd32 = inputs and forward.dtype == torch.float32
+                bwd32 = grads and backward.dtype == torch.float32
                 if layer.__class__.__name__ == 'Conv2d':
-                    if inputs:
+                    if fwd32:
                         geoms.append((*forward.shape, layer.kernel_size, layer.stride, layer.padding, layer.bias is not None))
-                    if grads:
+                    if bwd32:
                         geoms.append((*backward.shape, (1, 1), (1, 1), (0, 0), False))
                 else:
-                    if inputs:
+                    if fwd32:
                         geoms.append((forward.numel() // forward.shape[-1], forward.shape[-1], 1, 1, (1, 1), (1, 1), (0, 0),
                                       layer.bias is not None))
-                    if grads:
+                    if bwd32:
                         geoms.append((backward.numel() // backward.shape[-1], backward.shape[-1], 1, 1, (1, 1), (1, 1), (0, 0), False))
             hint = ops.kfac_path_for(geoms) if known else _lib.PATH_GROUPED
             for job in jobs:
                 job.path_hint = hint
         if getattr(self, "_count_flops", False):                 # bench.py: what the launch plan executes
-            self._last_flops = sum(ops.kfac_plan_flops(jobs)) + sum(ops.kfac_group_plan_flops(group_jobs))
+            self._last_flops = sum(ops.kfac_plan_flops(jobs)) + sum(ops.kfac_group_plan_flops(group_jobs)) + \
+                sum(ops.kfac_half_plan_flops(half_jobs))
         ops.kfac_accumulate(jobs, events=getattr(self, "_timing_events", None))
         ops.kfac_accumulate_groups(group_jobs)
+        ops.kfac_accumulate_half(half_jobs)
 
     def restart_accumulation(self) -> None:
         """The next `update()` overwrites the factors of every layer instead of adding to them (the tensors, their

@@ -8,6 +8,7 @@ here (``share_inputs=True``, KFAC only) A is built once per forward pass with we
 other draws update G only - the same accumulated factors (to fp32 rounding) for about half the factor-build
 work.  SURVEY.md section 8(f), rank 1.
 """
+import contextlib
 from types import SimpleNamespace
 from typing import Any, Callable, Iterable, Optional, Union
 
@@ -38,12 +39,16 @@ def compute_factors(args: Any,
                     epochs: Optional[int] = None,
                     device=None,
                     share_inputs: bool = True,
-                    label_sampler: Optional[Callable] = None):
+                    label_sampler: Optional[Callable] = None,
+                    autocast: Optional[torch.dtype] = None):
     """``compute_factors(args, model, data, factors=None)`` of the reference (scripts/factors.py:33-62).
 
     `args` may be the reference's argparse namespace or ``None`` with the keyword arguments.  `data` yields
     ``(images, labels)`` (the dataset labels are ignored, as in the reference).  `label_sampler(logits,
-    batch_index, sample_index)` replaces ``Categorical(logits).sample()`` (parity tests)."""
+    batch_index, sample_index)` replaces ``Categorical(logits).sample()`` (parity tests).  `autocast`
+    (``torch.bfloat16`` / ``torch.float16``): the forward pass and the loss run under ``torch.autocast('cuda',
+    dtype=autocast)``, so KFAC records half-precision activations and gradients (built on the bf16 / fp16 MFMA,
+    ``KFAC.update``); the label distribution is formed from the logits in float32."""
     a = _as_args(args, estimator=estimator, samples=samples, epochs=epochs, device=device)
     dev = a.device if a.device is not None else next(model.parameters()).device
     model.train()
@@ -55,13 +60,18 @@ def compute_factors(args: Any,
         est = est_base(model)
     shared = share_inputs and isinstance(est, curv.KFAC) and a.samples > 1
 
+    def amp():
+        return torch.autocast('cuda', dtype=autocast) if autocast is not None else contextlib.nullcontext()
+
     for _ in range(a.epochs):
         for batch, (images, _labels) in enumerate(data):
-            logits = model(images.to(dev, non_blocking=True))
-            dist = torch.distributions.Categorical(logits=logits)
+            with amp():
+                logits = model(images.to(dev, non_blocking=True))
+            dist = torch.distributions.Categorical(logits=logits if logits.dtype == torch.float32 else logits.float())
             for sample in range(a.samples):
                 labels = dist.sample() if label_sampler is None else label_sampler(logits, batch, sample)
-                loss = criterion(logits, labels)
+                with amp():
+                    loss = criterion(logits, labels)
                 model.zero_grad()
                 loss.backward(retain_graph=True)
                 if not shared:

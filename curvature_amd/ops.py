@@ -185,6 +185,86 @@ def kfac_accumulate(jobs: Sequence[FactorJob], events=None) -> None:
     _lib.check(rc, "curv_kfac_accumulate")
 
 
+_HALF_DTYPES = {torch.bfloat16: _lib.DTYPE_BF16, torch.float16: _lib.DTYPE_F16}
+
+
+class HalfFactorJob:
+    """A Kronecker-factor accumulation from a bf16 / fp16 source (what autocast hands the hooks) into an fp32 factor:
+    dst (+)= scale * unfold(src) unfold(src)^T, built on the bf16 / fp16 MFMA with fp32 accumulation
+    (curv_kfac16_accumulate).  Same fields as `FactorJob`; there is no path hint: a factor's plan is its own.
+    `src` may also be just its shape plus ``dtype`` (plan queries)."""
+    __slots__ = ("src", "dst", "kernel", "stride", "padding", "has_bias", "scale", "first", "dtype")
+
+    def __init__(self, src, dst, kernel=(1, 1), stride=(1, 1), padding=(0, 0), has_bias=False, scale=1.0,
+                 first=False, dtype=None):
+        self.src, self.dst = src, dst
+        self.kernel, self.stride, self.padding = tuple(kernel), tuple(stride), tuple(padding)
+        self.has_bias, self.scale, self.first = bool(has_bias), float(scale), bool(first)
+        self.dtype = src.dtype if isinstance(src, torch.Tensor) else dtype
+
+
+def _half_descs(jobs: Sequence[HalfFactorJob], check_tensors: bool = True):
+    arr = (_lib.curv_factor16_desc * len(jobs))()
+    for d, j in zip(arr, jobs):
+        if j.dtype not in _HALF_DTYPES:
+            raise RuntimeError(f"half-precision factor source must be bfloat16 or float16, got {j.dtype}")
+        shape = tuple(j.src.shape) if isinstance(j.src, torch.Tensor) else tuple(j.src)
+        if len(shape) == 4:
+            N, C, H, W = shape
+        elif len(shape) == 2:
+            (N, C), H, W = shape, 1, 1
+        else:
+            raise RuntimeError("factor source must be (N,C,H,W) or (N,C)")
+        if check_tensors:
+            if not (j.src.is_cuda and j.dst.is_cuda):
+                raise RuntimeError("curvature_amd runs on MI355X only: got a CPU tensor (no CPU fallback)")
+            if not j.src.is_contiguous():
+                raise RuntimeError("curvature_amd expects contiguous tensors")
+            _require_gpu(j.dst)
+            dim = C * j.kernel[0] * j.kernel[1] + int(j.has_bias)
+            if tuple(j.dst.shape) != (dim, dim):
+                raise RuntimeError(f"factor destination must be ({dim},{dim}), got {tuple(j.dst.shape)}")
+            d.src, d.dst = j.src.data_ptr(), j.dst.data_ptr()
+        d.N, d.C, d.H, d.W = int(N), int(C), int(H), int(W)
+        d.kh, d.kw = j.kernel
+        d.sh, d.sw = j.stride
+        d.ph, d.pw = j.padding
+        d.has_bias, d.first, d.scale = int(j.has_bias), int(j.first), j.scale
+        d.dtype = _HALF_DTYPES[j.dtype]
+    return arr
+
+
+def kfac_half_plan_flops(jobs: Sequence[HalfFactorJob]) -> List[int]:
+    """FLOPs (2 per multiply-add) the half-precision build executes for each job (curv_kfac16_plan_flops, host only):
+    every 128 x 128 tile on and above the diagonal over K padded to 16."""
+    if not jobs:
+        return []
+    arr = _half_descs(jobs, check_tensors=all(isinstance(j.src, torch.Tensor) for j in jobs))
+    out = (ctypes.c_longlong * len(jobs))()
+    _lib.check(_lib.lib().curv_kfac16_plan_flops(arr, len(jobs), out), "curv_kfac16_plan_flops")
+    return [int(v) for v in out]
+
+
+def kfac_accumulate_half(jobs: Sequence[HalfFactorJob], events=None) -> None:
+    """Factor build from bf16 / fp16 sources (curv_kfac16_accumulate): a pack, an MFMA and a reduce launch per batch of
+    factors, on the current stream.  Scratch from `workspace` (so CURV_DEBUG_POISON covers it).  `events` = (start,
+    stop) ``torch.cuda.Event``s (enable_timing) are recorded around the whole build."""
+    if not jobs:
+        return
+    n = len(jobs)
+    arr = _half_descs(jobs)
+    L = _lib.lib()
+    need = L.curv_kfac16_workspace_bytes(arr, n)
+    if need == 0:
+        _lib.check(_lib.ERR_INVALID, "curv_kfac16_workspace_bytes")
+    ws = workspace(need, jobs[0].src.device, "kfac_half")
+    if events is not None:
+        events[0].record()
+    _lib.check(L.curv_kfac16_accumulate(_lib.stream_ptr(), arr, n, ws.data_ptr(), ws.numel()), "curv_kfac16_accumulate")
+    if events is not None:
+        events[1].record()
+
+
 class GroupFactorJob:
     """The stacked Kronecker factors of a grouped convolution: dst[g] (+)= scale * unfold(src_g) unfold(src_g)^T, src_g
     the g-th of `groups` equal channel slices of src (curv_kfac_group_accumulate)."""

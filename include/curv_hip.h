@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define CURV_ABI_VERSION 11
+#define CURV_ABI_VERSION 12
 
 #define CURV_OK 0
 #define CURV_ERR_NOT_PD 1
@@ -170,6 +170,47 @@ int curv_kfac_group_plan_flops(const curv_group_factor_desc* descs, int n_factor
  * depends on that factor alone).  The workspace must be 256-byte aligned.  `descs` is a host array. */
 int curv_kfac_group_accumulate(void* stream, const curv_group_factor_desc* descs, int n_factors, void* workspace,
                                size_t workspace_bytes);
+
+/* ------------------------------------------------------------------------------------------------
+ * KFAC factor build from bf16 / fp16 sources (ABI 12, csrc/kfac_half.hip): what torch.autocast hands the hooks.
+ *
+ * Semantics are exactly those of curv_factor_desc: dst (+)= scale * X X^T with X the implicit im2col of `src` (rows
+ * (c, kh, kw), columns (n, oh, ow)) plus the row of ones when `has_bias`; `first` != 0 overwrites dst.  `src` is a
+ * contiguous (N, C, H, W) or (N, C) tensor of `dtype` (CURV_DTYPE_BF16 / CURV_DTYPE_F16), `dst` the fp32 dim x dim
+ * factor.  A bf16 x bf16 or fp16 x fp16 product is exact in fp32, so the v_mfma_f32_32x32x16_bf16 / _f16 build with fp32
+ * accumulation computes what the fp32 build computes on the upcast source, up to the order of the sums.
+ * Each factor's X is packed into the workspace (K-contiguous rows, zero padded to 128 rows and 16 columns), every
+ * 128 x 128 tile on or above the diagonal of every K slice is one MFMA work item writing an fp32 slab, and a fixed-order
+ * reduce scales, writes or adds dst and its mirror.  The result is exactly symmetric and bitwise reproducible; the plan
+ * of a factor follows from its own descriptor, so its bits never depend on the other factors of the call (no path hint).
+ * Never reads outside `src`; enqueues on `stream` only, never waits on the host and allocates nothing (graph capture
+ * works).  An empty call is a no-op.  Dilation and groups are not representable.
+ * ---------------------------------------------------------------------------------------------- */
+#define CURV_DTYPE_BF16 1
+#define CURV_DTYPE_F16 2
+typedef struct curv_factor16_desc {
+  const void* src;
+  float* dst;
+  int32_t N, C, H, W;
+  int32_t kh, kw, sh, sw, ph, pw;
+  int32_t has_bias;
+  int32_t first;
+  float scale;
+  int32_t dtype;
+} curv_factor16_desc;
+
+/* Device scratch needed by curv_kfac16_accumulate for these factors (bytes: the packed X of each factor and its slabs);
+ * 0 with the error text set for an invalid geometry or an unknown dtype.  Host only: src / dst are not read. */
+size_t curv_kfac16_workspace_bytes(const curv_factor16_desc* descs, int n_factors);
+
+/* Host only: the FLOPs (2 per multiply-add) the plan executes per factor, written to out[0 .. n_factors):
+ * 2 x 128^2 x (tiles on and above the diagonal) x K padded to 16 - at least dim (dim + 1) K. */
+int curv_kfac16_plan_flops(const curv_factor16_desc* descs, int n_factors, long long* out);
+
+/* The build: a pack, an MFMA and a reduce launch per batch of up to 16 factors of one dtype.  The workspace must be
+ * 256-byte aligned.  `descs` is a host array; it may be reused as soon as the call returns. */
+int curv_kfac16_accumulate(void* stream, const curv_factor16_desc* descs, int n_factors, void* workspace,
+                           size_t workspace_bytes);
 
 /* Same, recording HIP events (from curv_event_create) on `stream` around EVERYTHING the call enqueues behind the
  * descriptor-table uploads (padding / pre-tiling passes, the MFMA kernels, the k-slice reductions, the 3x3 assembly), so
