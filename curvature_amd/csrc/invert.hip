@@ -585,19 +585,25 @@ outer_update_dma_kernel(const InvDev* __restrict__ t, int nf, int k0, int kend, 
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), wm = wave >> 1, wn = wave & 1;
   const int r16 = lane & 15, kq = lane >> 4;
   const bool same = i == j;
-  const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)d.W, 0, (unsigned)((long long)np * np * 8), 0x00020000);
+  // one descriptor per operand, based at its block row (64-bit pointer arithmetic): the offsets below stay inside one
+  // NB x np panel, so they fit 32 bits at any width (a descriptor of the whole matrix needs np^2 * 8 < 2^31: np < 16384)
+  const unsigned panel_b = (unsigned)((long long)NB * np * 8);
+  const __amdgpu_buffer_rsrc_t rs_a =
+      __builtin_amdgcn_make_buffer_rsrc((void*)(d.W + (long long)i * NB * np), 0, panel_b, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rs_b =
+      __builtin_amdgcn_make_buffer_rsrc((void*)(d.W + (long long)j * NB * np), 0, panel_b, 0x00020000);
   // DMA lane geometry: piece p (8 rows x 128 B) of an operand = rows 8 p ..; this wave moves pieces `wave` and `wave + 4`
   // (32 rows apart: the same swizzle key)
   const int drow = 8 * wave + (lane >> 3);
   const int voff = (drow * np) * 8 + (((lane & 7) ^ ((drow >> 1) & 7)) << 4);
-  const int soff_a = (i * NB * np) * 8, soff_b = (j * NB * np) * 8, half_b = 32 * np * 8;
+  const int half_b = 32 * np * 8;
   auto issue = [&](int ke, unsigned buf) {
     const int kb = ke * 8;
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_void*)(lds + buf + wave * 1024), 16, voff, soff_a + kb, 0, 0);
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_void*)(lds + buf + (wave + 4) * 1024), 16, voff, soff_a + half_b + kb, 0, 0);
+    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_a, (lds_void*)(lds + buf + wave * 1024), 16, voff, kb, 0, 0);
+    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_a, (lds_void*)(lds + buf + (wave + 4) * 1024), 16, voff, half_b + kb, 0, 0);
     if (!same) {
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_void*)(lds + 2 * TILE_B + buf + wave * 1024), 16, voff, soff_b + kb, 0, 0);
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_void*)(lds + 2 * TILE_B + buf + (wave + 4) * 1024), 16, voff, soff_b + half_b + kb, 0, 0);
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_b, (lds_void*)(lds + 2 * TILE_B + buf + wave * 1024), 16, voff, kb, 0, 0);
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_b, (lds_void*)(lds + 2 * TILE_B + buf + (wave + 4) * 1024), 16, voff, half_b + kb, 0, 0);
     }
   };
   // operand addresses: block m (16 rows), half h: row * 128 + ((kq + 4 h) ^ key) * 16
@@ -2213,6 +2219,11 @@ static int chol_sweep(hipStream_t stream, std::vector<InvDev>& tab, void* worksp
 static int chol_inv_lower_impl(void* stream_, const curv_inv_desc* descs, int n_factors, int* info,
                                void* workspace, size_t workspace_bytes, const EarlyStatus* early);
 
+// Widest factor a sweep takes.  Element offsets into the work matrices are 64-bit everywhere; what stays 32-bit is the
+// per-factor tile count P^2 (launch enumeration, signed int: P < 46341) and the in-panel byte offsets of the far update's
+// descriptors (NB np 8 < 2^31).  2^21 keeps both with room to spare.
+constexpr int INV_MAX_N = 1 << 21;
+
 extern "C" int curv_chol_inv_lower(void* stream_, const curv_inv_desc* descs, int n_factors, int* info,
                                    void* workspace, size_t workspace_bytes) {
   return chol_inv_lower_impl(stream_, descs, n_factors, info, workspace, workspace_bytes, nullptr);
@@ -2234,6 +2245,7 @@ static int chol_inv_lower_impl(void* stream_, const curv_inv_desc* descs, int n_
   for (int i = 0; i < n_factors; ++i) {
     const curv_inv_desc& s = descs[i];
     CURV_REQUIRE(s.n > 0, "curv_chol_inv_lower: factor %d: empty", i);
+    CURV_REQUIRE(s.n <= INV_MAX_N, "curv_chol_inv_lower: factor %d: %d wide, the sweep takes at most %d", i, s.n, INV_MAX_N);
     CURV_REQUIRE(s.F != nullptr && s.L != nullptr, "curv_chol_inv_lower: factor %d: null pointer", i);
     CURV_REQUIRE(s.multiply >= 0.0 && s.add >= 0.0, "curv_chol_inv_lower: factor %d: negative hyper-parameter", i);
     InvDev& d = tab[i];
@@ -2265,6 +2277,8 @@ extern "C" int curv_chol_factor_inverse(void* stream_, const curv_cholinv_desc* 
   std::vector<InvDev> tab(n_mats);
   for (int i = 0; i < n_mats; ++i) {
     const curv_cholinv_desc& s = descs[i];
+    CURV_REQUIRE(s.n <= INV_MAX_N, "curv_chol_factor_inverse: matrix %d: %d wide, the sweep takes at most %d", i, s.n,
+                 INV_MAX_N);
     CURV_REQUIRE(s.n > 0 && s.M != nullptr && s.X != nullptr, "curv_chol_factor_inverse: matrix %d invalid", i);
     InvDev& d = tab[i];
     memset(&d, 0, sizeof(d));

@@ -217,7 +217,9 @@ __device__ __forceinline__ void syrk_body(const FactorDev& d, const int local, f
   //   address = base + soffset (SGPR: channel plane, advanced by SALU per slot) + voffset (VGPR: the
   //   lane's position inside a plane, constant across the channels it walks),
   // and a lane that holds padding, or lies outside a ragged chunk, carries voffset = OOB: the range
-  // check returns 0 for it, so halo zeros cost no instruction and no read ever leaves the tensor.
+  // check returns 0 for it, so halo zeros cost no instruction.  The channel plane travels in soffset, which LLVM does not
+  // document as covered by the check: a last panel that ends past C may fetch planes behind the tensor's last sample -
+  // values of any kind, which land only in patch rows past the factor's edge.
   // A slot is therefore ~2 instructions on either side (s_add + buffer_load, v_add + ds_write); the
   // wave issues one instruction every ~4 cycles, so this count is what the staging phase costs.
   constexpr int OOB = (int)0x80000000;

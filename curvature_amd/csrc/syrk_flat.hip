@@ -74,9 +74,11 @@ bool syrk_flat_eligible(const FactorDev& f, const void* src) {
   // flattened per-pixel factor (1x1, stride 1, no padding: H = 1, W = pixels per (sample, channel) row), no bias row, and
   // the whole tensor addressable by one buffer descriptor with 31-bit byte offsets (bit 31 of a lane's offset marks "no
   // fetch": flat_body).  The last tile row / column of a factor
-  // may be ragged (DenseNet-121 / 161: 64 + 32 k / 96 + 48 k channels; any multiple of 16 from 96 on): the panel rows behind the factor's edge are the next sample's first
-  // channels (zeros behind the tensor's end: the descriptor's range check) - finite values whose products land in tile rows
-  // and columns that neither epilogue stores (direct_store_block masks them, syrk_reduce_kernel does not read them)
+  // may be ragged (DenseNet-121 / 161: 64 + 32 k / 96 + 48 k channels; any multiple of 16 from 96 on): the DMA pieces of
+  // panel rows behind the factor's edge are skipped (flat_body: a piece is 16 rows), and the stale LDS rows in their place
+  // land in tile rows and columns that neither epilogue stores (direct_store_block masks them, syrk_reduce_kernel does
+  // not read them).  The range check does not stand in for this: a panel's row offset travels in soffset, which LLVM
+  // does not document as covered by it
   static const int ragged = getenv("CURV_FLAT_RAGGED") ? atoi(getenv("CURV_FLAT_RAGGED")) : 1;
   if (!(f.compact && f.H == 1 && f.kh == 1 && f.kw == 1 && f.sh == 1 && f.sw == 1 && f.ph == 0 && f.pw == 0)) return false;
   if (f.has_bias || f.dim < (ragged ? 96 : flat::TM) || f.dim % (ragged ? 16 : flat::TM) != 0) return false;
@@ -169,9 +171,16 @@ __device__ __forceinline__ void flat_body(const FactorDev& d, int local, float* 
     gi -= w ? gps : 0;
     voff_l += w ? wrap_b : SLOTS * 16;
   };
+  // a piece covers RPP rows of one panel, and a factor's dim is a multiple of RPP (syrk_flat_eligible): the pieces behind
+  // the edge of a ragged last tile row / column are skipped whole (wave-uniform), so that no panel row past the factor -
+  // for the last sample: past the tensor - is fetched; what LDS holds in their place reaches only tile rows and columns
+  // that neither epilogue stores
+  bool in_dim[NP];
+#pragma unroll
+  for (int i = 0; i < NP; ++i) in_dim[i] = ((i / PIECES) ? j0 : i0) + RPP * wave + 4 * RPP * (i % PIECES) < d.dim;
   auto piece = [&](int i, int voff, unsigned buf) {        // piece i = (panel i / PIECES, row group i % PIECES)
     const int p = i / PIECES, slot = i % PIECES;
-    if (p < N_PANELS) {
+    if (p < N_PANELS && in_dim[i]) {
       const unsigned lbase = (p ? 2u * PANEL_B : 0u) + buf + (unsigned)(RPP * wave + 4 * RPP * slot) * ROW_B;
       __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_void*)(lds + lbase), 16, voff,
                                                soff[p] + slot * 4 * RPP * pitch * 4 + (slot * 4 * RPP >= 64 ? hadj[p] : 0), 0, 0);
@@ -216,11 +225,12 @@ __device__ __forceinline__ void flat_body(const FactorDev& d, int local, float* 
         const bool gone = SLOTS * t + 2 * j + h >= g_tot;  // the whole group lies behind the K range
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
+          // both sides: behind the end of the stream's last row the fetched bytes lie past the tensor, and the row travels
+          // in soffset, which LLVM does not document as covered by the descriptor's range check - 0 x NaN must not reach
+          // the factor, whatever the hardware fetched there
           const bool k = 4 * rr[j] + e >= W || gone;
           xa0[e] = k ? 0.0f : xa0[e]; xa1[e] = k ? 0.0f : xa1[e];
-          // the B side only where LDS may hold anything (behind the stream's end nothing was fetched); behind a row's end
-          // it holds the next row's pixels, whose products with the A side's zeros vanish
-          xb0[e] = gone ? 0.0f : xb0[e]; xb1[e] = gone ? 0.0f : xb1[e];
+          xb0[e] = k ? 0.0f : xb0[e]; xb1[e] = k ? 0.0f : xb1[e];
         }
       }
     };

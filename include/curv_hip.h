@@ -125,7 +125,10 @@ int curv_kfac_plan_info(const curv_factor_desc* descs, int n_factors, long long*
  * padding pass and an assembly pass when such 3x3 factors are present and an unfold pass for the strided ones).  A launch that is small as a whole (LeNet scale: at most 2 GFLOP) takes a two-launch build of its own
  * instead (32 x 32 blocks x K slices gathered straight from the tensors, then a reduce pass; CURV_KFAC_SMALL=0 in the
  * environment keeps such a launch on the grouped kernels).  `descs` is a host array; it may be reused as soon as the call
- * returns. */
+ * returns.  A factor depends on nothing outside its `src`: the memory around a source may hold any bit pattern, NaN
+ * included (every kernel form is tested on sources fenced by NaN).  Two staging forms may still FETCH a few bytes past the
+ * end of `src` and discard them: the LDS-DMA kernel for flattened factors in the last 16-byte group of a source whose rows
+ * are not a multiple of 4 pixels, and the implicit-im2col kernel in the channel planes of a last panel that ends past C. */
 int curv_kfac_accumulate(void* stream, const curv_factor_desc* descs, int n_factors, void* workspace,
                          size_t workspace_bytes);
 
@@ -250,6 +253,7 @@ typedef struct curv_inv_desc {
 } curv_inv_desc;
 
 size_t curv_chol_inv_workspace_bytes(const curv_inv_desc* descs, int n_factors);
+/* A factor may be up to 2^21 wide (wider: CURV_ERR_INVALID); the work matrices are addressed with 64-bit offsets. */
 int curv_chol_inv_lower(void* stream, const curv_inv_desc* descs, int n_factors, int* info, void* workspace,
                         size_t workspace_bytes);
 /* The same call with an EARLY verdict for a host that must raise on "not positive definite" before it goes on (the

@@ -235,3 +235,25 @@ def test_two_estimators_tapping_one_attention_module_leave_f_linear_alone():
     for k in (k1, k2):
         for layer in k._layers():
             assert k.record[layer][0] is not None and k.record[layer][1] is not None
+
+
+def test_cholesky_sweep_width_limit_raises_on_the_host():
+    """curv_chol_inv_lower / curv_chol_factor_inverse refuse factors wider than 2^21 before touching the device, and the
+    workspace query of a 25089-wide factor (VGG-16 fc6: work matrices above 2^32 bytes) does not wrap."""
+    import ctypes
+    from curvature_amd import _lib
+    L = _lib.lib()
+    info = ctypes.c_int(0)
+    for n, rc in ((1 << 21) + 1, _lib.ERR_INVALID), (1 << 30, _lib.ERR_INVALID):
+        arr = (_lib.curv_inv_desc * 1)()
+        arr[0].n, arr[0].add, arr[0].multiply = n, 1.0, 1.0          # F, L null: the width is checked first
+        assert L.curv_chol_inv_lower(None, arr, 1, ctypes.byref(info), None, 0) == rc
+        assert b"at most 2097152" in L.curv_last_error()
+        carr = (_lib.curv_cholinv_desc * 1)()
+        carr[0].n = n
+        assert L.curv_chol_factor_inverse(None, carr, 1, ctypes.byref(info), None, 0) == rc
+        assert b"at most 2097152" in L.curv_last_error()
+    arr = (_lib.curv_inv_desc * 1)()
+    arr[0].n = 25089
+    np_ = 393 * 64
+    assert L.curv_chol_inv_workspace_bytes(arr, 1) >= 2 * np_ * np_ * 8 + 3 * np_ * np_ * 4 > 2 ** 34

@@ -181,3 +181,55 @@ def test_launch_form_of_the_unsharded_model_is_decided_by_the_library():
         d.N, d.C, d.H, d.W, d.kh, d.kw, d.sh, d.sw, d.has_bias, d.path_hint = 4, 16, 1, 1, 1, 1, 1, 1, 1, _lib.PATH_SMALL
     assert _lib.lib().curv_kfac_path_for(arr, 98) == _lib.PATH_GROUPED
     assert ops.kfac_path_for([]) == _lib.PATH_GROUPED
+
+
+# factors around the 32-bit limits of the build: dim^2 * 4 bytes crosses 2^31 between 23170 and 23171 (the direct
+# epilogue addresses the factor through one buffer descriptor with 31-bit offsets) and 2^32 at 32768 (where
+# direct_dst's (unsigned) dim * dim * 4 wraps to 0)
+# (the flattened-factor kernel takes widths of 16 k only)
+WIDE = [("linear", d) for d in (23168, 23170, 23171, 23184, 32752, 32767, 32768, 32769, 32784)] + \
+       [("flat", d) for d in (23168, 23184, 32752, 32768, 32784)]
+
+
+@pytest.mark.parametrize("kind,dim", WIDE)
+def test_wide_factor_plan_keeps_32bit_forms_in_range(kind, dim):
+    if kind == "linear":
+        d = dict(N=32, C=dim - 1, H=1, W=1, kh=1, kw=1, sh=1, sw=1, ph=0, pw=0, has_bias=1)      # (Linear: bias row)
+    else:
+        d = dict(N=2, C=dim, H=7, W=7, kh=1, kw=1, sh=1, sw=1, ph=0, pw=0, has_bias=0)           # 1x1 conv, 49 pixels
+    p = plan([d])[0]
+    assert p["dim"] == dim
+    if kind == "flat":
+        assert p["dma"] == 1                                # source far below 2^31 bytes: the LDS-DMA kernel
+    if dim * dim * 4 >= 2 ** 31:
+        assert p["direct"] == 0                             # 31-bit epilogue offsets: k-sliced through the reduce pass
+        assert p["nsub"] == p["ntiles"] * (p["TM"] // 64) ** 2
+    # the small build addresses a factor with 32-bit element indices and takes 2 GFLOP at most
+    geo = (d["N"], d["C"], d["H"], d["W"], (1, 1), (1, 1), (0, 0), bool(d["has_bias"]))
+    from curvature_amd import ops
+    assert ops.kfac_path_for([geo]) == _lib.PATH_GROUPED
+
+
+def _path_forced_small(d):
+    arr = (_lib.curv_factor_desc * 1)()
+    for k, v in d.items():
+        setattr(arr[0], k, v)
+    arr[0].scale, arr[0].first, arr[0].path_hint = 1.0, 1, _lib.PATH_SMALL
+    return _lib.lib().curv_kfac_path_for(arr, 1)
+
+
+def test_small_build_refuses_factors_beyond_31bit_indices_when_forced():
+    """A layer-sharded rank passes the unsharded model's launch form as a hint, which lifts the small build's flop gate:
+    its 31-bit element index (dim^2 < 2^31) must still hold."""
+    base = dict(N=1, H=1, W=1, kh=1, kw=1, sh=1, sw=1, ph=0, pw=0, has_bias=0)
+    assert _path_forced_small(dict(base, C=4096)) == _lib.PATH_SMALL        # the hint does lift the flop gate
+    for C in (46341, 50000, 65536):
+        assert _path_forced_small(dict(base, C=C)) == _lib.PATH_GROUPED
+
+
+@pytest.mark.parametrize("W,flat", [(65535, True), (65536, False)])
+def test_flat_kernel_needs_a_source_below_2gib(W, flat):
+    """The flattened-factor kernel reads its source through one descriptor with 31-bit offsets (bit 31 marks "no fetch")."""
+    d = dict(N=64, C=128, H=1, W=W, kh=1, kw=1, sh=1, sw=1, ph=0, pw=0, has_bias=0)
+    assert (64 * 128 * W * 4 < 2 ** 31 - 4096) == flat
+    assert (plan([d])[0]["dma"] == 1) == flat

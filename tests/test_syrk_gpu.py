@@ -1,6 +1,9 @@
 """Parity of the grouped implicit-im2col SYRK kernel (curv_kfac_accumulate) with the oracle's
 F.unfold + mm restatement of curvature/curvatures.py:329-350.  Tolerance: 1e-4 relative Frobenius
 (north_star); the kernel is exact-fp32 MFMA so the observed error is ~1e-6."""
+import functools
+import math
+
 import pytest
 import torch
 
@@ -9,6 +12,25 @@ from conftest import rel_fro
 pytestmark = pytest.mark.gpu
 
 TOL = 1e-4
+
+FENCE = 4096              # NaN floats in front of a fenced source
+FENCE_AFTER = 1 << 18     # and behind it (1 MiB: more than any staging form fetches past a source's end)
+OFFSETS = (0, 1)          # a source's start: on a 16-byte boundary, and 4 bytes past one (storage_offset % 4 == 1)
+
+
+def fenced(shape, offset, device="cuda:0"):
+    """A contiguous NaN-filled view of `shape` inside a NaN-filled buffer, `offset` floats past a 16-byte boundary (a
+    narrowed batch such as x[1:] starts like that).  A kernel that lets anything outside its source reach the result
+    puts NaN into it."""
+    n = math.prod(shape)
+    buf = torch.full((FENCE + offset + n + FENCE_AFTER,), float("nan"), device=device)
+    view = buf[FENCE + offset:FENCE + offset + n].view(shape)
+    assert view.is_contiguous() and view.data_ptr() % 16 == 4 * offset
+    return view
+
+
+def fenced_copy(t, offset):
+    return fenced(tuple(t.shape), offset).copy_(t)
 
 
 @pytest.fixture(autouse=True, params=["grouped", "small"])
@@ -20,7 +42,7 @@ def build_path(request, monkeypatch):
     return request.param
 
 
-# (N, C, H, W, kernel, stride, padding, bias)
+# (N, C, H, W, kernel, stride, padding, bias[, Cout: width of the G side, 37 if not given])
 CONV_CASES = [
     (3, 1, 28, 28, 5, 1, 2, True),      # LeNet conv1
     (3, 6, 14, 14, 5, 1, 0, True),      # LeNet conv2
@@ -73,6 +95,13 @@ CONV_CASES = [
     # exactly 64 channels, flattened (a pair-tile form of the LDS-DMA kernel was built and measured slower, LAB_NOTEBOOK R6)
     (5, 64, 9, 9, 1, 1, 0, False),      # odd sample count, 81 pixels per row
     (3, 64, 7, 7, 1, 1, 0, False),      # 49 pixels
+    # G sides on the LDS-DMA kernel too (Cout >= 96, a multiple of 16): ResNet-50 layer4's 1x1 convolutions at 7 x 7 (the
+    # last group of every (sample, channel) row holds one pixel), a 3x3 beside them, and a 64-pixel image (no row end
+    # inside a group)
+    (8, 512, 7, 7, 1, 1, 0, False, 2048),   # layer4.x.conv3: 512 -> 2048
+    (8, 2048, 7, 7, 1, 1, 0, False, 512),   # layer4.x.conv1: 2048 -> 512
+    (8, 512, 7, 7, 3, 1, 1, False, 256),    # layer4.x.conv2-like, G at 256
+    (8, 128, 8, 8, 1, 1, 0, False, 256),    # Ho * Wo % 4 == 0 on both sides
 ]
 
 
@@ -81,41 +110,61 @@ def _oracle():
     return o
 
 
-@pytest.mark.parametrize("case", CONV_CASES)
-def test_conv_factors(gpu, case):
-    from curvature_amd import ops
-    o = _oracle()
-    N, C, H, W, k, s, p, bias = case
+def _unpack(case):
+    N, C, H, W, k, s, p, bias = case[:8]
+    Cout = case[8] if len(case) > 8 else 37
     k2 = (k, k) if isinstance(k, int) else k
     s2 = (s, s) if isinstance(s, int) else s
     p2 = (p, p) if isinstance(p, int) else p
-    torch.manual_seed(1234)
-    x = torch.relu(torch.randn(N, C, H, W))
     Ho = (H + 2 * p2[0] - k2[0]) // s2[0] + 1
     Wo = (W + 2 * p2[1] - k2[1]) // s2[1] + 1
-    Cout = 37
+    return N, C, H, W, k2, s2, p2, bool(bias), Cout, Ho, Wo
+
+
+@functools.lru_cache(maxsize=None)
+def _conv_inputs(case):
+    """(x, g, A_ref, G_ref) of a case: the fp64 oracle runs once per case, whatever the offsets and build paths."""
+    o = _oracle()
+    N, C, H, W, k2, s2, p2, bias, Cout, Ho, Wo = _unpack(case)
+    torch.manual_seed(1234)
+    x = torch.relu(torch.randn(N, C, H, W))
     g = torch.randn(N, Cout, Ho, Wo) / N
     A_ref, G_ref = o.kfac_factors(x.double(), g.double(), k2, s2, p2, bias)
+    return x, g, A_ref, G_ref
+
+
+def _conv_jobs(case, xg, gg, gpu):
+    from curvature_amd import ops
+    N, C, H, W, k2, s2, p2, bias, Cout, Ho, Wo = _unpack(case)
     n = C * k2[0] * k2[1] + int(bias)
     A = torch.full((n, n), float("nan"), device=gpu)
     G = torch.full((Cout, Cout), float("nan"), device=gpu)
-    xg, gg = x.to(gpu), g.to(gpu)
     L = Ho * Wo
-    jobs = [ops.FactorJob(xg, A, k2, s2, p2, bias, 1.0 / (N * L), True),
+    return [ops.FactorJob(xg, A, k2, s2, p2, bias, 1.0 / (N * L), True),
             ops.FactorJob(gg, G, (1, 1), (1, 1), (0, 0), False, N / L, True)]
-    ops.kfac_accumulate(jobs)
-    torch.cuda.synchronize()
-    assert torch.isfinite(A).all() and torch.isfinite(G).all()
-    assert rel_fro(A, A_ref) < TOL, rel_fro(A, A_ref)
-    assert rel_fro(G, G_ref) < TOL, rel_fro(G, G_ref)
-    assert torch.equal(A, A.t()) and torch.equal(G, G.t())       # exactly symmetric
-    # accumulate a second batch (the reference's `+=`, curvatures.py:347-348)
-    for j in jobs:
-        j.first = False
-    ops.kfac_accumulate(jobs)
-    torch.cuda.synchronize()
-    assert rel_fro(A, 2 * A_ref) < TOL
-    assert rel_fro(G, 2 * G_ref) < TOL
+
+
+@pytest.mark.parametrize("case", CONV_CASES)
+def test_conv_factors(gpu, case):
+    """Sources fenced by NaN (nothing outside them may reach a factor), at a 16-byte-aligned start and 4 bytes past one."""
+    from curvature_amd import ops
+    x, g, A_ref, G_ref = _conv_inputs(case)
+    for offset in OFFSETS:
+        jobs = _conv_jobs(case, fenced_copy(x, offset), fenced_copy(g, offset), gpu)
+        A, G = jobs[0].dst, jobs[1].dst
+        ops.kfac_accumulate(jobs)
+        torch.cuda.synchronize()
+        assert torch.isfinite(A).all() and torch.isfinite(G).all(), offset
+        assert rel_fro(A, A_ref) < TOL, (offset, rel_fro(A, A_ref))
+        assert rel_fro(G, G_ref) < TOL, (offset, rel_fro(G, G_ref))
+        assert torch.equal(A, A.t()) and torch.equal(G, G.t())       # exactly symmetric
+        # accumulate a second batch (the reference's `+=`, curvatures.py:347-348)
+        for j in jobs:
+            j.first = False
+        ops.kfac_accumulate(jobs)
+        torch.cuda.synchronize()
+        assert rel_fro(A, 2 * A_ref) < TOL, offset
+        assert rel_fro(G, 2 * G_ref) < TOL, offset
 
 
 @pytest.mark.parametrize("N,C,Cout,bias", [(100, 400, 120, True), (7, 84, 10, True), (32, 513, 1000, False), (1, 5, 3, True)])
@@ -126,13 +175,97 @@ def test_linear_factors(gpu, N, C, Cout, bias):
     x = torch.randn(N, C)
     g = torch.randn(N, Cout) / N
     A_ref, G_ref = o.kfac_factors(x.double(), g.double(), has_bias=bias)
-    A = torch.empty(C + bias, C + bias, device=gpu)
-    G = torch.empty(Cout, Cout, device=gpu)
-    ops.kfac_accumulate([ops.FactorJob(x.to(gpu), A, has_bias=bias, scale=1.0 / N, first=True),
-                         ops.FactorJob(g.to(gpu), G, scale=float(N), first=True)])
-    torch.cuda.synchronize()
-    assert rel_fro(A, A_ref) < TOL, rel_fro(A, A_ref)
-    assert rel_fro(G, G_ref) < TOL, rel_fro(G, G_ref)
+    for offset in OFFSETS:
+        A = torch.empty(C + bias, C + bias, device=gpu)
+        G = torch.empty(Cout, Cout, device=gpu)
+        ops.kfac_accumulate([ops.FactorJob(fenced_copy(x, offset), A, has_bias=bias, scale=1.0 / N, first=True),
+                             ops.FactorJob(fenced_copy(g, offset), G, scale=float(N), first=True)])
+        torch.cuda.synchronize()
+        assert torch.isfinite(A).all() and torch.isfinite(G).all(), offset
+        assert rel_fro(A, A_ref) < TOL, (offset, rel_fro(A, A_ref))
+        assert rel_fro(G, G_ref) < TOL, (offset, rel_fro(G, G_ref))
+
+
+def _plan_rows(jobs):
+    """curv_kfac_plan_info of a job list: one dict per job (fields named as in test_plan_host.py)."""
+    import ctypes
+    from curvature_amd import _lib, ops
+    names = ("dim Ho Wo NS R Wc nchunks RS PS SS nch ntiles cpi nslices nitems base TM vec4 cshift nsub direct rshift "
+             "pre dma flops").split()
+    assert len(names) == ops.PLAN_INFO_FIELDS
+    arr = ops._factor_descs(jobs)
+    out = (ctypes.c_longlong * (ops.PLAN_INFO_FIELDS * len(jobs)))()
+    _lib.check(_lib.lib().curv_kfac_plan_info(arr, len(jobs), out), "curv_kfac_plan_info")
+    return [dict(zip(names, out[ops.PLAN_INFO_FIELDS * i:ops.PLAN_INFO_FIELDS * (i + 1)])) for i in range(len(jobs))]
+
+
+def test_fenced_cases_reach_every_kernel(gpu, build_path):
+    """The fenced cases above cover every kernel form of the fp32 factor build, as the planner routes them today (plan
+    fields 17 float4 staging, 22 pre-tiled LDS-DMA, 23 flat LDS-DMA / shifted correlations; the launch form from
+    kfac_path_for).  A planner change that moves a case off its kernel fails here instead of silently ending the
+    coverage of that kernel."""
+    from curvature_amd import _lib, ops
+    seen = set()
+    for case in CONV_CASES:
+        N, C, H, W, k2, s2, p2, bias, Cout, Ho, Wo = _unpack(case)
+        geoms = [(N, C, H, W, k2, s2, p2, bias), (N, Cout, Ho, Wo, (1, 1), (1, 1), (0, 0), False)]
+        if ops.kfac_path_for(geoms) == _lib.PATH_SMALL:
+            seen.add("small")
+        for offset in OFFSETS:
+            xg, gg = fenced((N, C, H, W), offset), fenced((N, Cout, Ho, Wo), offset)
+            for (geo_n, geo_c, geo_hw, geo_k, geo_s), p in zip(
+                    [(N, C, H * W, k2, s2), (N, Cout, Ho * Wo, (1, 1), (1, 1))], _plan_rows(_conv_jobs(case, xg, gg, gpu))):
+                one_by_one = geo_k == (1, 1)
+                if p["dma"] == 2:
+                    seen.add("corr C=64" if C == 64 else "corr C%128" if C % 128 == 0 else "corr other")
+                elif p["dma"] == 1 and not one_by_one:
+                    seen.add("kxk unfolded")
+                elif p["dma"] == 1 and geo_s != (1, 1):
+                    seen.add("strided 1x1 unfolded")
+                elif p["dma"] == 1:
+                    seen.add("flat W%4==0" if geo_hw % 4 == 0 else "flat W%4!=0")
+                    if p["dim"] % 128:
+                        seen.add("flat ragged dim")
+                elif p["pre"]:
+                    seen.add("pre-tiled")
+                elif p["dma"] == 0:
+                    seen.add("im2col float4" if p["vec4"] else "im2col")
+    want = {"im2col float4", "im2col", "pre-tiled", "flat W%4==0", "flat W%4!=0", "flat ragged dim", "corr C%128",
+            "corr C=64", "strided 1x1 unfolded"}
+    if build_path == "small":
+        want.add("small")
+    assert want <= seen, sorted(want - seen)
+
+
+def test_resnet50_layer4_one_by_one_fenced(gpu, build_path):
+    """KFAC.update() at ResNet-50 layer4.x.conv1 / conv3 (1x1, 2048 -> 512 and 512 -> 2048, 7 x 7, N = 8): every factor
+    of this geometry - A of both, G of both - is flattened with 49 pixels per row, so the last 4-pixel group of each row
+    straddles its end; the records end right before NaN.  Against an fp64 reference computed with plain torch."""
+    from curvature_amd.curvatures import KFAC
+    N, L = 8, 49
+    conv1 = torch.nn.Conv2d(2048, 512, 1, bias=False)
+    conv3 = torch.nn.Conv2d(512, 2048, 1, bias=False)
+    model = torch.nn.Sequential(conv1, conv3).to(gpu)
+    torch.manual_seed(21)
+    data = {layer: (torch.relu(torch.randn(N, layer.in_channels, 7, 7)), torch.randn(N, layer.out_channels, 7, 7) / N)
+            for layer in (conv1, conv3)}
+    refs = {}
+    for layer, (x, g) in data.items():
+        X = x.to(gpu, torch.float64).reshape(N, -1, L)
+        Gs = g.to(gpu, torch.float64).reshape(N, -1, L)
+        refs[layer] = (torch.einsum("ncl,ndl->cd", X, X) / (N * L), torch.einsum("ncl,ndl->cd", Gs, Gs) * N / L)
+    for offset in OFFSETS:
+        kfac = KFAC(model)
+        for layer, (x, g) in data.items():
+            kfac.record[layer] = [fenced_copy(x, offset), fenced_copy(g, offset)]
+        kfac.update(batch_size=N)
+        torch.cuda.synchronize()
+        for layer in (conv1, conv3):
+            A, G = kfac.state[layer]
+            RA, RG = refs[layer]
+            assert torch.isfinite(A).all() and torch.isfinite(G).all(), (offset, tuple(A.shape))
+            assert rel_fro(A, RA) < TOL and rel_fro(G, RG) < TOL, (offset, rel_fro(A, RA), rel_fro(G, RG))
+            assert torch.equal(A, A.t()) and torch.equal(G, G.t())
 
 
 def test_many_k_slices(gpu):
