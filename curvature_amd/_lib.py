@@ -13,7 +13,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc")
 INCLUDE = os.path.normpath(os.path.join(_HERE, "..", "include"))
 LIB_PATH = os.path.join(CSRC, "libcurv_hip.so")
-SOURCES = ["api.cpp", "collective.cpp", "elementwise.hip", "syrk.hip", "syrk_flat.hip", "syrk_corr.hip", "syrk_pre.hip", "syrk_small.hip", "group_factor.hip", "kfac_half.hip", "invert.hip", "gemm.hip", "inf.hip", "eigh.hip", "eigh_lowrank.hip"]
+SOURCES = ["api.cpp", "collective.cpp", "elementwise.hip", "syrk.hip", "syrk_flat.hip", "syrk_corr.hip", "syrk_pre.hip", "syrk_small.hip", "group_factor.hip", "kfac_half.hip", "convt_factor.hip", "invert.hip", "gemm.hip", "inf.hip", "eigh.hip", "eigh_lowrank.hip"]
 HIPCC_FLAGS = ["-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC", "-shared", "-Wall",
                "-Wno-unused-function", "-ldl"]
 
@@ -132,6 +132,17 @@ class curv_group_factor_desc(ctypes.Structure):
     ]
 
 
+class curv_convt_factor_desc(ctypes.Structure):
+    """Mirror of ``curv_convt_factor_desc`` in include/curv_hip.h."""
+    _fields_ = [
+        ("src", ctypes.c_void_p), ("dst", ctypes.c_void_p),
+        ("N", ctypes.c_int32), ("C", ctypes.c_int32), ("H", ctypes.c_int32), ("W", ctypes.c_int32),
+        ("kh", ctypes.c_int32), ("kw", ctypes.c_int32), ("sh", ctypes.c_int32), ("sw", ctypes.c_int32),
+        ("ph", ctypes.c_int32), ("pw", ctypes.c_int32), ("Ho", ctypes.c_int32), ("Wo", ctypes.c_int32),
+        ("has_bias", ctypes.c_int32), ("first", ctypes.c_int32), ("scale", ctypes.c_float),
+    ]
+
+
 class curv_factor16_desc(ctypes.Structure):
     """Mirror of ``curv_factor16_desc`` in include/curv_hip.h."""
     _fields_ = [
@@ -219,6 +230,9 @@ SIGNATURES = {
     "curv_kfac16_workspace_bytes": (_sz, [ctypes.POINTER(curv_factor16_desc), _i]),
     "curv_kfac16_plan_flops": (_i, [ctypes.POINTER(curv_factor16_desc), _i, ctypes.POINTER(ctypes.c_longlong)]),
     "curv_kfac16_accumulate": (_i, [_vp, ctypes.POINTER(curv_factor16_desc), _i, _vp, _sz]),
+    "curv_kfac_convt_workspace_bytes": (_sz, [ctypes.POINTER(curv_convt_factor_desc), _i]),
+    "curv_kfac_convt_plan_flops": (_i, [ctypes.POINTER(curv_convt_factor_desc), _i, ctypes.POINTER(ctypes.c_longlong)]),
+    "curv_kfac_convt_accumulate": (_i, [_vp, ctypes.POINTER(curv_convt_factor_desc), _i, _vp, _sz]),
     "curv_event_create": (_vp, []),
     "curv_event_destroy": (None, [_vp]),
     "curv_event_elapsed_ms": (_i, [_vp, _vp, ctypes.POINTER(ctypes.c_float)]),
@@ -266,6 +280,7 @@ DTYPE_BF16, DTYPE_F16 = 1, 2         # CURV_DTYPE_* (curv_factor16_desc.dtype)
 KFAC_TABLE_RESIDENT = 1             # CURV_KFAC_TABLE_RESIDENT
 PATH_AUTO, PATH_SMALL, PATH_GROUPED = 0, 1, 2     # CURV_PATH_* (curv_factor_desc.path_hint)
 SMALL_MAX_FLOP = 2.0e9              # CURV_SMALL_MAX_FLOP
+CONVT_MAX_PHASES = 64               # CURV_CONVT_MAX_PHASES
 GEMM_TABLE_RESIDENT = 1             # CURV_GEMM_TABLE_RESIDENT
 ERR_NOT_PD, ERR_INVALID, ERR_WORKSPACE, ERR_HIP, ERR_NOT_CONVERGED = 1, 2, 3, 4, 5     # CURV_ERR_* of the header
 

@@ -27,6 +27,51 @@ from torch.nn import Module, Sequential
 from . import _lib, ops
 
 SUPPORTED_LAYERS = ['Linear', 'Conv2d', 'MultiheadAttention']
+# selectable by name but not part of the default selection (which stays what the reference selects)
+OPTIONAL_LAYERS = ['ConvTranspose2d']
+# layer classes whose parameters are a weight matrix (Wm) and an optional bias
+_MATRIX_LAYERS = ('Linear', 'Conv2d', 'ConvTranspose2d')
+
+
+def _is_convt(layer) -> bool:
+    return layer.__class__.__name__ == 'ConvTranspose2d'
+
+
+def _check_convt(layer) -> None:
+    """What the transposed-convolution estimators represent: groups 1, dilation 1, integer padding."""
+    if layer.groups != 1:
+        raise NotImplementedError("ConvTranspose2d with groups > 1 is not supported")
+    if tuple(layer.dilation) != (1, 1):
+        raise NotImplementedError("dilated ConvTranspose2d is not supported")
+    if not all(isinstance(p, int) for p in layer.padding):
+        raise NotImplementedError("ConvTranspose2d with string padding is not supported")
+
+
+def _wm(layer, t: Tensor) -> Tensor:
+    """A tensor shaped like `layer.weight` as the layer matrix Wm (out, in*kh*kw): a view for Linear / Conv2d, a
+    contiguous copy of ``t.permute(1, 0, 2, 3)`` for ConvTranspose2d (whose weight is (in, out, kh, kw))."""
+    if _is_convt(layer):
+        return t.transpose(0, 1).reshape(t.shape[1], -1)
+    return t.reshape(t.shape[0], -1)
+
+
+def _wm_rows(layer) -> int:
+    """Rows of the layer matrix Wm: output features / channels."""
+    return layer.weight.shape[1] if _is_convt(layer) else layer.weight.shape[0]
+
+
+def _tap_views(layer, t: Tensor):
+    """[(columns, view)]: 2-D views of `t` (shaped like `layer.weight`) that together hold the weight columns of Wm,
+    `columns` = the matching slice of Wm's columns.  One view for Linear / Conv2d; one per kernel tap (a, b) for
+    ConvTranspose2d: Wm[:, ci kh kw + a kw + b] = weight[ci, :, a, b], a (out, in) view with strides (kh kw, out kh kw).
+    A product that writes these views writes Wm through the permutation, with no copy pass."""
+    if not _is_convt(layer):
+        return [(slice(None), t.view(t.shape[0], -1))]
+    cin, cout = t.shape[0], t.shape[1]
+    khw = t.numel() // (cin * cout)
+    n0 = cin * khw
+    v = t.view(cin, cout, khw)
+    return [(slice(k, n0, khw), v[:, :, k].t()) for k in range(khw)]
 
 
 def _is_scalar(x) -> bool:
@@ -160,7 +205,11 @@ class Curvature(ABC):
         else:
             raise TypeError
         for _type in self.layer_types:
-            assert _type in SUPPORTED_LAYERS
+            assert _type in SUPPORTED_LAYERS or _type in OPTIONAL_LAYERS
+        if 'ConvTranspose2d' in self.layer_types:
+            for layer in model.modules():
+                if _is_convt(layer):
+                    _check_convt(layer)
         self.state = dict()
         self.inv_state = dict()
         # optional layer sharding across ranks (curvature_amd.sharding.Shard); None = own every layer.
@@ -192,7 +241,7 @@ class Curvature(ABC):
         for layer in self.model.modules():
             name = layer.__class__.__name__
             if name in self.layer_types:
-                if name in ('Linear', 'Conv2d'):
+                if name in _MATRIX_LAYERS:
                     out.append(layer)
                 elif name == 'MultiheadAttention' and self._mha_as_projections:
                     out.extend(AttentionProjection.of(layer))
@@ -225,7 +274,7 @@ class Curvature(ABC):
             name = layer.__class__.__name__
             if name not in self.layer_types:
                 continue
-            if name in ('Linear', 'Conv2d'):
+            if name in _MATRIX_LAYERS:
                 order.append(layer)
             elif name == 'MultiheadAttention' and self._mha_as_projections:
                 order.extend(AttentionProjection.of(layer))
@@ -416,12 +465,24 @@ class Curvature(ABC):
         self._reload_mean(skip=params)
         self._allgather_sampled()
 
+    @staticmethod
+    def _replace_layer(sample: Tensor, layer) -> None:
+        """`_replace` of an (out, in*kh*kw [+1]) sample in Wm order; a ConvTranspose2d weight takes it permuted."""
+        if not _is_convt(layer):
+            Curvature._replace(sample, layer.weight, layer.bias)
+            return
+        if layer.bias is not None:
+            layer.bias.data.add_(sample[:, -1])
+            sample = sample[:, :-1]
+        w = layer.weight
+        layer.weight.data.add_(sample.reshape(w.shape[1], w.shape[0], *w.shape[2:]).transpose(0, 1))
+
     def sample_and_replace(self):
         """Reset to the mean weights, then add one posterior sample per selected layer (curvatures.py:117-129)."""
         self._reload_mean()
         for _, layer in self._owned():
             _sample = self.sample(layer)
-            self._replace(_sample, layer.weight, layer.bias)
+            self._replace_layer(_sample, layer)
         self._allgather_sampled()
 
 
@@ -447,7 +508,7 @@ class Diagonal(Curvature):
         fresh = {}
         if new:
             self._state_flat, views = _arena(
-                [(l.weight.shape[0], l.weight.numel() // l.weight.shape[0] + int(l.bias is not None)) for l in new],
+                [(_wm_rows(l), l.weight.numel() // _wm_rows(l) + int(l.bias is not None)) for l in new],
                 new[0].weight.device)
             fresh = dict(zip(new, views))
         keys, items = [], []
@@ -455,11 +516,12 @@ class Diagonal(Curvature):
             name = layer.__class__.__name__
             if name not in self.layer_types:
                 continue
-            if name in ('Linear', 'Conv2d'):
+            if name in _MATRIX_LAYERS:
                 if layer in owned:
                     bias_grad = layer.bias.grad.contiguous() if layer.bias is not None else None
                     keys.append(layer)
-                    items.append((layer.weight.grad.contiguous(), bias_grad, fresh.get(layer, self.state.get(layer)),
+                    # state in Wm layout (out, in*kh*kw [+1]); a ConvTranspose2d gradient is permuted into it
+                    items.append((_wm(layer, layer.weight.grad).contiguous(), bias_grad, fresh.get(layer, self.state.get(layer)),
                                   True if layer in fresh else None))
             elif name == 'MultiheadAttention':
                 for key, weight, bias in (('attn_in', layer.in_proj_weight, layer.in_proj_bias),
@@ -553,8 +615,11 @@ class Diagonal(Curvature):
                     w = layer.weight.data
                     if not w.is_contiguous():
                         raise RuntimeError("Diagonal.sample_and_replace: parameters must be contiguous")
-                    jobs.append(ops.Gemm(ones_r[:m], ones_c[:, :n0], w.view(m, n0), epilogue=ops.EPI_MUL_E_ADD_F,
-                                         E=z[:, :n0], F=self.model_state_of(layer, 'weight').view(m, n0)))
+                    zw = z[:, :n0]
+                    for (cols, wv), (_, fv) in zip(_tap_views(layer, w),
+                                                   _tap_views(layer, self.model_state_of(layer, 'weight'))):
+                        jobs.append(ops.Gemm(ones_r[:m], ones_c[:, :wv.shape[1]], wv, epilogue=ops.EPI_MUL_E_ADD_F,
+                                             E=zw[:, cols], F=fv))
                     if layer.bias is not None:
                         jobs.append(ops.Gemm(ones_r[:m], ones_c[:, :1], layer.bias.data.view(m, 1),
                                              epilogue=ops.EPI_MUL_E_ADD_F, E=z[:, n0:],
@@ -592,6 +657,11 @@ class BlockDiagonal(Curvature):
       (out, -1) for every layer type - identical for Linear, and what ``_replace`` consumes for Conv2d.
     O(P^2) memory per layer: meant for small layers, like the reference's.  MultiheadAttention is not supported
     (the reference's branch, :220-239, concatenates a 2-D gradient with a 1-D bias and raises)."""
+
+    def __init__(self, model: Union[Module, Sequential], layer_types: Union[List[str], str] = None, *, shard=None):
+        super().__init__(model, layer_types, shard=shard)
+        if any(_is_convt(l) for l in self._layers()):
+            raise NotImplementedError("BlockDiagonal: ConvTranspose2d layers are not supported")
 
     def update(self, batch_size: int):
         jobs = []
@@ -684,14 +754,15 @@ def _reject_grouped(est, what: str) -> None:
                                       "supported; select other layer types or use KFAC")
 
 
-def _factor_source(t: Tensor, groups: int) -> Tensor:
+def _factor_source(t: Tensor, groups: int, fp32: bool = False) -> Tensor:
     """A recorded activation / gradient as the factor build takes it: contiguous; float32 or (ordinary layers)
     bfloat16 / float16.  A grouped layer's half-precision side becomes a float32 copy on the device: the grouped build
-    (curv_kfac_group_accumulate) has no half-precision form."""
+    (curv_kfac_group_accumulate) has no half-precision form; neither has the transposed-convolution A-side build
+    (`fp32`)."""
     t = t.detach()
     if t.dtype not in (torch.float32, torch.bfloat16, torch.float16):
         raise RuntimeError(f"KFAC.update expects float32, bfloat16 or float16 activations and gradients, got {t.dtype}")
-    if groups > 1 and t.dtype != torch.float32:
+    if (groups > 1 or fp32) and t.dtype != torch.float32:
         return t.float().contiguous()
     return t.contiguous()
 
@@ -731,6 +802,13 @@ class KFAC(Curvature):
                     self.record[layer] = [None, None]
                     self.hooks.append(layer.register_forward_pre_hook(self._save_input))
                     self.hooks.append(layer.register_forward_hook(self._hook_output))
+                elif name == 'ConvTranspose2d':
+                    # Wm = weight.permute(1, 0, 2, 3).reshape(out, -1) [| bias]; A from the phase-split build
+                    # (curv_kfac_convt_accumulate), G a 1x1 factor of grad_output as for Conv2d
+                    _check_convt(layer)
+                    self.record[layer] = [None, None]
+                    self.hooks.append(layer.register_forward_pre_hook(self._save_input))
+                    self.hooks.append(layer.register_forward_hook(self._hook_output))
                 elif name == 'MultiheadAttention':
                     # the two projections as Linear-like layers (extension: curvatures.py:303-304 raises here); their
                     # inputs / output gradients are tapped off the F.linear calls of the attention forward
@@ -744,6 +822,9 @@ class KFAC(Curvature):
         self.record[module][0] = input[0]            # by reference, like curvatures.py:307
 
     def _hook_output(self, module, input, output):
+        if _is_convt(module):
+            # the output size carries the effective output_padding (layer(x, output_size=...) changes it)
+            self.__dict__.setdefault("_out_size", {})[module] = tuple(output.shape[-2:])
         if output.requires_grad:
             output.register_hook(lambda grad, module=module: self._save_output(module, grad))
 
@@ -768,7 +849,7 @@ class KFAC(Curvature):
         ``grad_scale``: the loss scale of a ``torch.cuda.amp.GradScaler`` whose scaled loss produced the recorded
         gradients; the G side is divided by ``grad_scale ** 2``.  The caller skips ``update()`` on the steps the scaler
         skips (non-finite gradients)."""
-        jobs, group_jobs, half_jobs = [], [], []
+        jobs, group_jobs, half_jobs, convt_jobs = [], [], [], []
         if not grad_scale > 0:
             raise ValueError(f"KFAC.update: grad_scale must be positive, got {grad_scale}")
         g_div = float(grad_scale) ** 2
@@ -782,11 +863,25 @@ class KFAC(Curvature):
             has_bias = layer.bias is not None
             x = g = None
             groups = _groups_of(layer)
+            convt = _is_convt(layer)
             if forward is not None:
-                x = _factor_source(forward, groups)
+                x = _factor_source(forward, groups, fp32=convt)
             if backward is not None:
                 g = _factor_source(backward, groups)
-            if layer.__class__.__name__ == 'Conv2d':
+            if convt:
+                kernel, stride, padding = layer.kernel_size, layer.stride, layer.padding
+                C, m = layer.in_channels, layer.out_channels
+                N = (x if x is not None else g).shape[0]
+                if g is not None:
+                    out_size = tuple(g.shape[2:])
+                elif layer in self.__dict__.get("_out_size", {}):
+                    out_size = self._out_size[layer]
+                else:                                        # records that did not pass this estimator's hooks
+                    out_size = tuple((x.shape[2 + d] - 1) * stride[d] - 2 * padding[d] + kernel[d] +
+                                     layer.output_padding[d] for d in range(2))
+                L = out_size[0] * out_size[1]
+                n = C * kernel[0] * kernel[1] + int(has_bias)
+            elif layer.__class__.__name__ == 'Conv2d':
                 kernel, stride, padding = layer.kernel_size, layer.stride, layer.padding
                 C, m = layer.in_channels // groups, layer.out_channels // groups
                 N = (x if x is not None else g).shape[0]
@@ -828,7 +923,14 @@ class KFAC(Curvature):
                     group_jobs.append(ops.GroupFactorJob(g, G, groups, (1, 1), (1, 1), (0, 0), False,
                                                          float(N) / L / g_div, first))
                 continue
-            if inputs:
+            if inputs and convt:
+                first = (layer, 0) in fresh
+                fresh.discard((layer, 0))
+                if x.dim() != 4:
+                    raise RuntimeError("KFAC.update: ConvTranspose2d inputs must be (N, C, H, W)")
+                convt_jobs.append(ops.ConvTFactorJob(x, A, kernel, stride, padding, out_size, has_bias,
+                                                     float(input_weight) / (N * L), first))
+            elif inputs:
                 first = (layer, 0) in fresh
                 fresh.discard((layer, 0))
                 if x.dtype == torch.float32:
@@ -859,7 +961,10 @@ class KFAC(Curvature):
                 # half-precision sides are built by curv_kfac16_accumulate, whose plans are per factor
                 fwd32 = inputs and forward.dtype == torch.float32
                 bwd32 = grads and backward.dtype == torch.float32
-                if layer.__class__.__name__ == 'Conv2d':
+                if _is_convt(layer):                             # A side: curv_kfac_convt_accumulate, per factor
+                    if bwd32:
+                        geoms.append((*backward.shape, (1, 1), (1, 1), (0, 0), False))
+                elif layer.__class__.__name__ == 'Conv2d':
                     if fwd32:
                         geoms.append((*forward.shape, layer.kernel_size, layer.stride, layer.padding, layer.bias is not None))
                     if bwd32:
@@ -875,10 +980,11 @@ class KFAC(Curvature):
                 job.path_hint = hint
         if getattr(self, "_count_flops", False):                 # bench.py: what the launch plan executes
             self._last_flops = sum(ops.kfac_plan_flops(jobs)) + sum(ops.kfac_group_plan_flops(group_jobs)) + \
-                sum(ops.kfac_half_plan_flops(half_jobs))
+                sum(ops.kfac_half_plan_flops(half_jobs)) + sum(ops.kfac_convt_plan_flops(convt_jobs))
         ops.kfac_accumulate(jobs, events=getattr(self, "_timing_events", None))
         ops.kfac_accumulate_groups(group_jobs)
         ops.kfac_accumulate_half(half_jobs)
+        ops.kfac_accumulate_convt(convt_jobs)
 
     def restart_accumulation(self) -> None:
         """The next `update()` overwrites the factors of every layer instead of adding to them (the tensors, their
@@ -1027,10 +1133,25 @@ class KFAC(Curvature):
                     z = flat[pos:pos + G * n * m].view(*((G,) if first.dim() == 3 else ()), n, m)
                     pos += G * n * m
                 n0 = n - int(layer.bias is not None)
+                zs = z if G > 1 else [z]
+                if _is_convt(layer):
+                    # Wm's columns land in the (in, out, kh, kw) weight one kernel tap at a time: a strided (out, in)
+                    # view per tap, so the epilogue writes through the permutation (L_A^T's column slices are no longer
+                    # triangular: these products run dense)
+                    la, lg = first, second
+                    tmp = torch.empty(m, n, dtype=torch.float32, device=first.device)
+                    stage1.append(ops.Gemm(lg, z.t(), tmp, tri=ops.TRI_A_LOWER))
+                    la_t = la.t()
+                    for (cols, wv), (_, mv) in zip(_tap_views(layer, layer.weight.data),
+                                                   _tap_views(layer, self.model_state_of(layer, 'weight'))):
+                        stage2.append(ops.Gemm(tmp, la_t[:, :n0][:, cols], wv, epilogue=ops.EPI_ADD_E, E=mv))
+                    if layer.bias is not None:
+                        stage2.append(ops.Gemm(tmp, la_t[:, n0:], layer.bias.data.view(m, 1), epilogue=ops.EPI_ADD_E,
+                                               E=self.model_state_of(layer, 'bias').view(m, 1)))
+                    continue
                 # grouped layer: group g owns weight rows [g m, (g + 1) m) - one pair of products per group
                 ws = layer.weight.data.view(G, m, n0)
                 w_means = self.model_state_of(layer, 'weight').view(G, m, n0)
-                zs = z if G > 1 else [z]
                 for g, (la, lg) in enumerate(_pairs(first, second)):
                     tmp = torch.empty(m, n, dtype=torch.float32, device=first.device)
                     stage1.append(ops.Gemm(lg, zs[g].t(), tmp, tri=ops.TRI_A_LOWER))
@@ -1101,17 +1222,25 @@ class KFAC(Curvature):
                     pos += S * G * n * m
                 has_bias = layer.bias is not None
                 n0 = n - int(has_bias)
-                wb = torch.empty(S, G * m, n0, dtype=torch.float32, device=dev)
+                convt = _is_convt(layer)
+                # a ConvTranspose2d's bank holds its sets in the weight's own (in, out, kh, kw) layout
+                wb = torch.empty(S, *(layer.weight.shape if convt else (G * m, n0)), dtype=torch.float32, device=dev)
                 bb = torch.empty(S, G * m, dtype=torch.float32, device=dev) if has_bias else None
-                w_mean = self.model_state_of(layer, 'weight').view(G, m, n0)
+                w_mean = self.model_state_of(layer, 'weight').view(G, m, n0) if not convt else None
                 b_mean = self.model_state_of(layer, 'bias').view(G, m, 1) if has_bias else None
                 for g, ((la, lg), zt) in enumerate(zip(_pairs(first, second), zts)):
                     V = torch.empty(n, S * m, dtype=torch.float32, device=dev)
                     stage_a.append(ops.Gemm(la, zt.t(), V, tri=ops.TRI_A_LOWER))     # V = L_A [z_1 | ... | z_S]
                     for k in range(S):
                         Vs_t = V[:, k * m:(k + 1) * m].t()                        # (m, n) view of V_s^T: K-contiguous columns
-                        stage_b.append(ops.Gemm(lg, Vs_t[:, :n0], wb[k].view(G, m, n0)[g], epilogue=ops.EPI_ADD_E,
-                                                E=w_mean[g], tri=ops.TRI_A_LOWER))
+                        if convt:                                                  # one product per kernel tap
+                            for (cols, wv), (_, mv) in zip(_tap_views(layer, wb[k]),
+                                                           _tap_views(layer, self.model_state_of(layer, 'weight'))):
+                                stage_b.append(ops.Gemm(lg, Vs_t[:, :n0][:, cols], wv, epilogue=ops.EPI_ADD_E, E=mv,
+                                                        tri=ops.TRI_A_LOWER))
+                        else:
+                            stage_b.append(ops.Gemm(lg, Vs_t[:, :n0], wb[k].view(G, m, n0)[g], epilogue=ops.EPI_ADD_E,
+                                                    E=w_mean[g], tri=ops.TRI_A_LOWER))
                         if has_bias:
                             stage_b.append(ops.Gemm(lg, Vs_t[:, n0:], bb[k].view(G, m, 1)[g], epilogue=ops.EPI_ADD_E,
                                                     E=b_mean[g], tri=ops.TRI_A_LOWER))
@@ -1226,7 +1355,8 @@ class EFB(Curvature):
             gw = layer.weight.grad
             if gw is None:
                 raise RuntimeError("EFB.update: a selected layer has no gradient (call backward() first)")
-            grads.append((gw.contiguous(), layer.bias.grad if layer.bias is not None else None))
+            # Wm layout (out, in*kh*kw): a ConvTranspose2d gradient is permuted into it
+            grads.append((_wm(layer, gw).contiguous(), layer.bias.grad if layer.bias is not None else None))
         dev = grads[0][0].device
         missing = [k for k, layer in enumerate(layers) if layer not in self.state]
         if missing:
@@ -1367,10 +1497,10 @@ class EFB(Curvature):
                 pt = tmp.view(-1).view(n, m)
                 stage1.append(ops.Gemm(first, zt.t(), pt))
                 n0 = n - int(layer.bias is not None)
-                w = layer.weight.data.view(m, n0)
-                w_mean = self.model_state_of(layer, 'weight').view(m, n0)
                 p = pt.t()                                                          # (m, n) view of P
-                stage2.append(ops.Gemm(second, p[:, :n0], w, epilogue=ops.EPI_ADD_E, E=w_mean))
+                for (cols, w), (_, w_mean) in zip(_tap_views(layer, layer.weight.data),
+                                                  _tap_views(layer, self.model_state_of(layer, 'weight'))):
+                    stage2.append(ops.Gemm(second, p[:, :n0][:, cols], w, epilogue=ops.EPI_ADD_E, E=w_mean))
                 if layer.bias is not None:
                     b = layer.bias.data.view(m, 1)
                     b_mean = self.model_state_of(layer, 'bias').view(m, 1)
@@ -1671,9 +1801,9 @@ class INF(Curvature):
                 # weight seen through transposed strides, the last row to the bias (curvatures.py:67-82, 536)
                 n0 = n - int(layer.bias is not None)
                 Yv = Y_l.view(n, m)
-                w_t = layer.weight.data.view(m, n0).t()
-                stages[4].append(ops.Gemm(ua[:n0], t2.t(), w_t, alpha=-1.0, beta=1.0, epilogue=ops.EPI_MUL_E_ADD_F,
-                                          E=r2[:n0], F=Yv[:n0]))
+                for rows, w in _tap_views(layer, layer.weight.data):             # (ConvTranspose2d: one per tap)
+                    stages[4].append(ops.Gemm(ua[:n0][rows], t2.t(), w.t(), alpha=-1.0, beta=1.0,
+                                              epilogue=ops.EPI_MUL_E_ADD_F, E=r2[:n0][rows], F=Yv[:n0][rows]))
                 if layer.bias is not None:
                     stages[4].append(ops.Gemm(ua[n0:], t2.t(), layer.bias.data.view(1, m), alpha=-1.0, beta=1.0,
                                               epilogue=ops.EPI_MUL_E_ADD_F, E=r2[n0:], F=Yv[n0:]))

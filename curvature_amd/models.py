@@ -1,5 +1,6 @@
 """Plain ``torch.nn`` definitions of the benchmark networks (LeNet-5, ImageNet ResNet-18 / ResNet-50, DenseNet-121 / 161,
-and the grouped-convolution networks MobileNetV2 / ResNeXt-50 32x4d).
+the grouped-convolution networks MobileNetV2 / ResNeXt-50 32x4d, and the upsampling networks DCGAN generator / U-Net
+with ``ConvTranspose2d`` layers).
 
 torchvision is not available on the target image, and the estimators select layers by class NAME
 (``Conv2d`` / ``Linear``; curvature/curvatures.py:121, :298), so these are ordinary torch modules with
@@ -272,6 +273,52 @@ def densenet121(num_classes: int = 1000) -> DenseNet:
 
 def densenet161(num_classes: int = 1000) -> DenseNet:
     return DenseNet(48, (6, 12, 36, 24), 96, num_classes=num_classes)
+
+
+def dcgan_generator(nz: int = 100, ngf: int = 64, nc: int = 3) -> nn.Sequential:
+    """DCGAN generator (Radford et al. 2016): a (N, nz, 1, 1) latent to an (N, nc, 64, 64) image.  The first layer is a
+    ConvTranspose2d(kernel 4, stride 1, padding 0) on the 1x1 latent, the other four are (kernel 4, stride 2, padding 1)
+    upsamplings; no biases, BatchNorm + ReLU between them, tanh at the end."""
+    layers = [nn.ConvTranspose2d(nz, ngf * 8, 4, 1, 0, bias=False), nn.BatchNorm2d(ngf * 8), nn.ReLU(True)]
+    c = ngf * 8
+    for _ in range(3):
+        layers += [nn.ConvTranspose2d(c, c // 2, 4, 2, 1, bias=False), nn.BatchNorm2d(c // 2), nn.ReLU(True)]
+        c //= 2
+    layers += [nn.ConvTranspose2d(c, nc, 4, 2, 1, bias=False), nn.Tanh()]
+    return nn.Sequential(*layers)
+
+
+def _double_conv(cin: int, cout: int) -> nn.Sequential:
+    return nn.Sequential(nn.Conv2d(cin, cout, 3, padding=1, bias=False), nn.BatchNorm2d(cout), nn.ReLU(inplace=True),
+                         nn.Conv2d(cout, cout, 3, padding=1, bias=False), nn.BatchNorm2d(cout), nn.ReLU(inplace=True))
+
+
+class UNet(nn.Module):
+    """U-Net (Ronneberger et al. 2015) with padded convolutions: four 2x2 max-pool downsamplings, four
+    ConvTranspose2d(C, C/2, kernel 2, stride 2) upsamplings (biased), skip concatenations, 1x1 classifier."""
+
+    def __init__(self, in_channels: int = 3, num_classes: int = 2, width: int = 64):
+        super().__init__()
+        w = [width * 2 ** i for i in range(5)]
+        self.inc = _double_conv(in_channels, w[0])
+        self.down = nn.ModuleList([_double_conv(w[i], w[i + 1]) for i in range(4)])
+        self.pool = nn.MaxPool2d(2)
+        self.up = nn.ModuleList([nn.ConvTranspose2d(w[i + 1], w[i], 2, stride=2) for i in reversed(range(4))])
+        self.dec = nn.ModuleList([_double_conv(2 * w[i], w[i]) for i in reversed(range(4))])
+        self.outc = nn.Conv2d(w[0], num_classes, 1)
+
+    def forward(self, x):
+        skips = [self.inc(x)]
+        for down in self.down:
+            skips.append(down(self.pool(skips[-1])))
+        y = skips.pop()
+        for up, dec in zip(self.up, self.dec):
+            y = dec(torch.cat([skips.pop(), up(y)], dim=1))
+        return self.outc(y)
+
+
+def unet(in_channels: int = 3, num_classes: int = 2, width: int = 64) -> UNet:
+    return UNet(in_channels, num_classes, width)
 
 
 def layer_table(model: nn.Module, input_chw: Tuple[int, int, int]) -> List[dict]:

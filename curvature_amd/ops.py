@@ -330,6 +330,74 @@ def kfac_accumulate_groups(jobs: Sequence[GroupFactorJob], events=None) -> None:
         events[1].record()
 
 
+class ConvTFactorJob:
+    """The A factor of a ConvTranspose2d (curv_kfac_convt_accumulate): dst (+)= scale * sum_o a(o) a(o)^T over the output
+    pixels, a(o) the layer's patch in Wm = weight.permute(1, 0, 2, 3).reshape(Cout, -1) order [+ 1].  `out_size` = (Ho, Wo)
+    of the layer's output (it carries the effective output_padding).  `src` may also be just its (N, C, H, W) shape (plan
+    queries)."""
+    __slots__ = ("src", "dst", "kernel", "stride", "padding", "out_size", "has_bias", "scale", "first")
+
+    def __init__(self, src, dst, kernel, stride, padding, out_size, has_bias=False, scale=1.0, first=False):
+        self.src, self.dst = src, dst
+        self.kernel, self.stride, self.padding = tuple(kernel), tuple(stride), tuple(padding)
+        self.out_size = tuple(int(v) for v in out_size)
+        self.has_bias, self.scale, self.first = bool(has_bias), float(scale), bool(first)
+
+
+def _convt_descs(jobs: Sequence[ConvTFactorJob], check_tensors: bool = True):
+    arr = (_lib.curv_convt_factor_desc * len(jobs))()
+    for d, j in zip(arr, jobs):
+        if check_tensors:
+            _require_gpu(j.src, j.dst)
+            if j.src.dim() != 4 or j.src.dtype != torch.float32 or not j.src.is_contiguous():
+                raise RuntimeError("transposed-convolution factor source must be a contiguous float32 (N,C,H,W) tensor")
+        N, C, H, W = j.src.shape if check_tensors else j.src
+        if check_tensors:
+            dim = C * j.kernel[0] * j.kernel[1] + int(j.has_bias)
+            if tuple(j.dst.shape) != (dim, dim):
+                raise RuntimeError(f"factor destination must be ({dim},{dim}), got {tuple(j.dst.shape)}")
+            d.src, d.dst = j.src.data_ptr(), j.dst.data_ptr()
+        d.N, d.C, d.H, d.W = int(N), int(C), int(H), int(W)
+        d.kh, d.kw = j.kernel
+        d.sh, d.sw = j.stride
+        d.ph, d.pw = j.padding
+        d.Ho, d.Wo = j.out_size
+        d.has_bias, d.first, d.scale = int(j.has_bias), int(j.first), j.scale
+    return arr
+
+
+def kfac_convt_plan_flops(jobs: Sequence[ConvTFactorJob]) -> List[int]:
+    """Multiply-add FLOPs (2 per multiply-add) the transposed-convolution build executes for each job: the sum over the
+    phase Grams it runs (curv_kfac_convt_plan_flops, host only).  `job.src` may be a tensor or its (N, C, H, W) shape."""
+    if not jobs:
+        return []
+    arr = _convt_descs(jobs, check_tensors=all(isinstance(j.src, torch.Tensor) for j in jobs))
+    out = (ctypes.c_longlong * len(jobs))()
+    _lib.check(_lib.lib().curv_kfac_convt_plan_flops(arr, len(jobs), out), "curv_kfac_convt_plan_flops")
+    return [int(v) for v in out]
+
+
+def kfac_accumulate_convt(jobs: Sequence[ConvTFactorJob], events=None) -> None:
+    """A-factor build of transposed convolutions (curv_kfac_convt_accumulate) on the current stream: per factor the window
+    copies of its phases, one fp32 MFMA build of the phase Grams and one assembly launch.  Scratch from `workspace` (so
+    CURV_DEBUG_POISON covers it).  `events` = (start, stop) ``torch.cuda.Event``s are recorded around the whole build."""
+    if not jobs:
+        return
+    n = len(jobs)
+    arr = _convt_descs(jobs)
+    L = _lib.lib()
+    need = L.curv_kfac_convt_workspace_bytes(arr, n)
+    if need == 0:
+        _lib.check(_lib.ERR_INVALID, "curv_kfac_convt_workspace_bytes")
+    ws = workspace(need, jobs[0].src.device, "kfac_convt")
+    if events is not None:
+        events[0].record()
+    _lib.check(L.curv_kfac_convt_accumulate(_lib.stream_ptr(), arr, n, ws.data_ptr(), ws.numel()),
+               "curv_kfac_convt_accumulate")
+    if events is not None:
+        events[1].record()
+
+
 def rsqrt_affine(value: torch.Tensor, add: float, multiply: float, out: Optional[torch.Tensor] = None):
     _require_gpu(value, out)
     if out is None:

@@ -82,7 +82,13 @@ def layer_geometry(layer, x_shape: Sequence[int], g_shape: Sequence[int]):
     """The two factor geometries (A side, G side) of a Linear / Conv2d layer as dicts of curv_factor_desc fields, from
     the shapes of its recorded input and grad_output."""
     bias = int(layer.bias is not None)
-    if layer.__class__.__name__ == "Conv2d":
+    if layer.__class__.__name__ == "ConvTranspose2d":        # A: curv_convt_factor_desc fields (convt=1 marks them)
+        N, C, H, W = x_shape
+        (kh, kw), (sh, sw), (ph, pw) = layer.kernel_size, layer.stride, layer.padding
+        a = dict(N=N, C=C, H=H, W=W, kh=kh, kw=kw, sh=sh, sw=sw, ph=ph, pw=pw, Ho=g_shape[2], Wo=g_shape[3],
+                 has_bias=bias, convt=1)
+        g = dict(N=g_shape[0], C=g_shape[1], H=g_shape[2], W=g_shape[3], kh=1, kw=1, sh=1, sw=1, ph=0, pw=0, has_bias=0)
+    elif layer.__class__.__name__ == "Conv2d":
         N, C, H, W = x_shape
         (kh, kw), (sh, sw), (ph, pw) = layer.kernel_size, layer.stride, layer.padding
         a = dict(N=N, C=C, H=H, W=W, kh=kh, kw=kw, sh=sh, sw=sw, ph=ph, pw=pw, has_bias=bias)
@@ -107,6 +113,25 @@ def kfac_build_flops(geometries: Sequence[dict]) -> List[int]:
     n = len(geometries)
     if n == 0:
         return []
+    convt = [i for i, d in enumerate(geometries) if d.get("convt", 0)]
+    if convt:                                             # transposed convolutions: curv_kfac_convt_plan_flops
+        carr = (_lib.curv_convt_factor_desc * len(convt))()
+        for i, a in zip(convt, carr):
+            for k, v in geometries[i].items():
+                if k != "convt":
+                    setattr(a, k, int(v))
+            a.scale = 1.0
+        cout = (ctypes.c_longlong * len(convt))()
+        _lib.check(_lib.lib().curv_kfac_convt_plan_flops(carr, len(convt), cout), "curv_kfac_convt_plan_flops")
+        in_convt = set(convt)
+        rest = [i for i in range(n) if i not in in_convt]
+        other = kfac_build_flops([geometries[i] for i in rest])
+        out = [0] * n
+        for i, v in zip(convt, cout):
+            out[i] = int(v)
+        for i, v in zip(rest, other):
+            out[i] = v
+        return out
     grouped = [i for i, d in enumerate(geometries) if d.get("groups", 1) > 1]
     if grouped:                                           # grouped convolutions: curv_kfac_group_plan_flops
         garr = (_lib.curv_group_factor_desc * len(grouped))()
@@ -149,7 +174,9 @@ def layer_dims(layers, shapes) -> List[tuple]:
         a, g = geoms[2 * i], geoms[2 * i + 1]
         G = a.get("groups", 1)
         n = a["C"] // G * a["kh"] * a["kw"] + a["has_bias"]
-        if layer.__class__.__name__ == "Conv2d":
+        if layer.__class__.__name__ == "ConvTranspose2d":
+            K = a["N"] * a["Ho"] * a["Wo"]
+        elif layer.__class__.__name__ == "Conv2d":
             (kh, kw), (sh, sw), (ph, pw) = layer.kernel_size, layer.stride, layer.padding
             K = a["N"] * ((a["H"] + 2 * ph - kh) // sh + 1) * ((a["W"] + 2 * pw - kw) // sw + 1)
         else:

@@ -215,6 +215,51 @@ int curv_kfac16_plan_flops(const curv_factor16_desc* descs, int n_factors, long 
 int curv_kfac16_accumulate(void* stream, const curv_factor16_desc* descs, int n_factors, void* workspace,
                            size_t workspace_bytes);
 
+/* ------------------------------------------------------------------------------------------------
+ * KFAC A-factor build of a ConvTranspose2d (csrc/convt_factor.hip; groups 1, dilation 1):
+ *   dst (+)= scale * sum_o a(o) a(o)^T
+ * over the N Ho Wo output pixels o, with a(o)[ci kh kw + a kw + b] = src[n, ci, (oh + ph - a) / sh, (ow + pw - b) / sw]
+ * where both quotients are whole numbers inside the input and 0 otherwise, plus a trailing 1 when `has_bias`.  This is
+ * the layer matrix Wm = weight.permute(1, 0, 2, 3).reshape(Cout, -1) [| bias] of the layer: dim = C kh kw + has_bias.
+ * `src` is the contiguous fp32 (N, C, H, W) layer input; Ho, Wo the spatial size of the layer's OUTPUT (it carries the
+ * effective output_padding: (H - 1) sh - 2 ph + kh <= Ho < that + sh).  `scale`, `first` as for curv_factor_desc; the
+ * G side of such a layer is an ordinary 1x1 factor of grad_output (curv_kfac_accumulate / curv_kfac16_accumulate).
+ *
+ * Output pixels split into sh sw phases by ((oh + ph) mod sh, (ow + pw) mod sw); phase r sees only the taps = r
+ * (mod stride), as a stride-1 correlation of the original input.  So A is a sum of phase Grams on disjoint tap sets: every
+ * entry between taps of different residues is exactly 0.0.  Each phase is built by curv_kfac_accumulate (one call per
+ * factor, so its bits depend on its own geometry only): straight from `src` when the phase is a symmetrically padded
+ * correlation of it (every phase of kernel == stride, padding 0, the single phase of stride 1; equal phases are built
+ * once), otherwise from a zero-bordered window copy of `src` in the workspace.  An assembly pass scatters the phase Grams
+ * to their taps, writes exact zeros elsewhere, sets the bias corner to N Ho Wo, scales, writes or adds dst and mirrors
+ * it: the result is exactly symmetric.  sh sw <= CURV_CONVT_MAX_PHASES.
+ * Never reads outside `src`; deterministic; enqueues on `stream` only, never waits on the host and allocates nothing
+ * (graph capture works).  An empty call is a no-op; invalid geometry returns CURV_ERR_INVALID with text.
+ * ---------------------------------------------------------------------------------------------- */
+#define CURV_CONVT_MAX_PHASES 64
+typedef struct curv_convt_factor_desc {
+  const float* src;
+  float* dst;
+  int32_t N, C, H, W;
+  int32_t kh, kw, sh, sw, ph, pw;
+  int32_t Ho, Wo;
+  int32_t has_bias;
+  int32_t first;
+  float scale;
+} curv_convt_factor_desc;
+
+/* Device scratch needed by curv_kfac_convt_accumulate for these factors (bytes; 0 with error text for invalid geometry). */
+size_t curv_kfac_convt_workspace_bytes(const curv_convt_factor_desc* descs, int n_factors);
+
+/* Host-only: multiply-add flops (2 per multiply-add) the build executes per factor: the sum of what curv_kfac_plan_info
+ * reports for the phase Grams it runs (a dense im2col build of the same factor executes dim (dim + 1) N Ho Wo). */
+int curv_kfac_convt_plan_flops(const curv_convt_factor_desc* descs, int n_factors, long long* out);
+
+/* The build of all factors, one after another on `stream`.  `workspace`: curv_kfac_convt_workspace_bytes, 256-byte
+ * aligned.  `descs` is a host array; it may be reused as soon as the call returns. */
+int curv_kfac_convt_accumulate(void* stream, const curv_convt_factor_desc* descs, int n_factors, void* workspace,
+                               size_t workspace_bytes);
+
 /* Same, recording HIP events (from curv_event_create) on `stream` around EVERYTHING the call enqueues behind the
  * descriptor-table uploads (padding / pre-tiling passes, the MFMA kernels, the k-slice reductions, the 3x3 assembly), so
  * that a benchmark can time the whole build without a profiler. */
