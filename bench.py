@@ -12,6 +12,12 @@ ImageNet ResNet-50 (54 layers, N = 32, synthetic 3x224x224 inputs). With N > 1 G
 ranks (disjoint layer groups, replicated forward/backward, one RCCL all-gather of the sampled weights per step):
 total work is fixed, so scaling is "strong". Rank 0 prints ONE JSON line; see DESIGN.md section "Measurement" for
 every field.
+
+A plain run does only what that line's headline needs: set-up, warm-up, the timed steps, --dump-outputs and the line.
+`--full` adds the legs that run after the timed region (several minutes on one GPU): the CPU baseline, BASELINE.json's
+other configurations, the stream-population probes and the CPU oracle's other configurations:
+
+    python bench.py --gpus 1 --steps 5 --warmup 2 --full
 """
 import argparse
 import copy
@@ -141,7 +147,7 @@ def cpu_baseline(batch_full, seed, budget_s=75.0):
 
 def cpu_baseline_subprocess(batch_full, timeout_s=300):
     """Run the CPU leg in a child process with a hard time limit (a torch CPU op cannot be interrupted from inside),
-    so that the default `python bench.py` always finishes within minutes.  The child never touches the GPU."""
+    so that `python bench.py --full` always finishes within minutes.  The child never touches the GPU."""
     import subprocess
     cmd = [sys.executable, os.path.abspath(__file__), "--cpu-baseline-only", "--batch", str(batch_full)]
     try:
@@ -694,6 +700,8 @@ def spawn_ranks(args) -> int:
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={args.gpus}",
            "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__),
            "--gpus", str(args.gpus), "--steps", str(args.steps), "--warmup", str(args.warmup), "--batch", str(args.batch)]
+    if args.full:
+        cmd.append("--full")
     if args.no_cpu_baseline:
         cmd.append("--no-cpu-baseline")
     if args.no_other_configs:
@@ -711,9 +719,12 @@ def main():
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--batch", type=int, default=32)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region, also run the CPU baseline (`cpu_baseline`) and the legs for "
+                         "BASELINE.json's configs 2, 3 and 5 (`other_configs`); single GPU only, several minutes")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU legs")
     ap.add_argument("--no-other-configs", action="store_true",
-                    help="skip the untimed-region legs for BASELINE.json's configs 2, 3 and 5 (`other_configs`)")
+                    help="with --full: skip the untimed-region legs for BASELINE.json's configs 2, 3 and 5 (`other_configs`)")
     ap.add_argument("--cpu-baseline-only", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--cpu-other-only", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
@@ -954,9 +965,9 @@ def main():
             out["ranks"] = rank_phases
         if dumped is not None:
             out["outputs_dumped"] = dumped
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline_subprocess(args.batch)
-        if world == 1 and not args.no_other_configs:
+        if world == 1 and args.full and not args.no_other_configs:
             # BASELINE.json's configs 2, 3 and 5: after the timed region, never inside it
             try:
                 other = other_configs_gpu(dev, model, kfac, args.batch)

@@ -81,6 +81,22 @@ def test_dump_outputs_is_passed_to_the_ranks(monkeypatch, tmp_path):
     assert tail[tail.index("--dump-outputs") + 1] == str(tmp_path / "out")
 
 
+@pytest.mark.parametrize("full", [False, True])
+def test_full_is_passed_to_the_ranks_only_when_asked(monkeypatch, full):
+    bench = load_bench()
+    import subprocess
+    seen = {}
+    monkeypatch.setattr(subprocess, "call", lambda cmd, env=None, **kw: seen.setdefault("cmd", list(cmd)) and 0)
+    monkeypatch.setattr(bench.torch.cuda, "device_count", lambda: 2)
+    for var in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
+        monkeypatch.delenv(var, raising=False)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "2"] + (["--full"] if full else []))
+    with pytest.raises(SystemExit):
+        bench.main()
+    tail = seen["cmd"][seen["cmd"].index(os.path.join(ROOT, "bench.py")) + 1:]
+    assert ("--full" in tail) == full
+
+
 def test_zero_steps_is_refused(monkeypatch):
     bench = load_bench()
     monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "0"])
