@@ -18,7 +18,6 @@
 #include "common.h"
 
 #include <algorithm>
-#include <cstdlib>
 #include <numeric>
 #include <vector>
 
@@ -30,15 +29,7 @@ constexpr double LOWRANK_GRAM_PIVOT = 1e-13;   // relative pivot of the Gram mat
 constexpr double LOWRANK_RESIDUAL = 3e-6;      // ||F - P F P|| / ||F|| the projection must reach (the iteration's own bar above 1024: 5e-6)
 constexpr int LR_BLOCKS = 1024;                // partial sums of the squared norms (summed in a fixed order)
 
-static double lowrank_probe() {
-  const char* e = getenv("CURV_EIGH_PROBE");
-  return e ? atof(e) : LOWRANK_PROBE;
-}
-static bool lowrank_enabled() {
-  const char* e = getenv("CURV_EIGH_LOWRANK");
-  return !(e && e[0] == '0' && e[1] == 0);
-}
-static int probe_columns(int n) { return (int)(n * lowrank_probe()) / 64 * 64; }
+static int probe_columns(int n) { return (int)(n * LOWRANK_PROBE) / 64 * 64; }
 
 // S = (F + F^T) / 2 in fp64, and the block's share of sum S^2
 __global__ void __launch_bounds__(256) lr_sym_f32_kernel(const float* __restrict__ F, double* __restrict__ S, int n,
@@ -210,7 +201,6 @@ static LowRankShared lowrank_shared(const std::vector<LowRank>& ms) {
 
 static std::vector<LowRank> lowrank_candidates(const curv_eigh_desc* descs, int n_mats) {
   std::vector<LowRank> ms;
-  if (!lowrank_enabled()) return ms;
   for (int i = 0; i < n_mats; ++i) {
     if (descs[i].n < LOWRANK_MIN_N) continue;
     LowRank q;

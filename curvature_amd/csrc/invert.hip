@@ -458,7 +458,6 @@ __device__ __forceinline__ void outer_update_body(const InvDev* __restrict__ t, 
                                                   int strip, int n_items, double* __restrict__ As, double* __restrict__ Bs) {
   bool trailing;
   int i, j, f, local;
-  const bool s_only = strip == 2;            // far launch of the S tiles alone (the trailing tiles went to outer_update_dma_kernel)
   if (strip == 1) {
     // strip: block columns / rows [lo, hi)
     if (!locate(t, nf, blockIdx.x, [kend, lo, hi](const InvDev& d) { return (int)strip_tiles(d.P, kend, lo, hi, s_in_sweep(d)); }, f, local))
@@ -478,35 +477,24 @@ __device__ __forceinline__ void outer_update_body(const InvDev* __restrict__ t, 
     }
   } else {
     const int row0 = lo;
-    // far part: everything from block row / column lo on.  XCD grouping: workgroups with equal blockIdx % 8 share an XCD; give each XCD whole super-blocks
+    // far part (strip == 2): the S tiles from block row lo on - the trailing tiles go to outer_update_dma_kernel.  XCD
+    // grouping: workgroups with equal blockIdx % 8 share an XCD; give each XCD whole super-blocks
     int item;
     {
       const int bid = blockIdx.x, xcd = bid & 7, jj = bid >> 3;
       item = ((jj / (SB * SB)) * 8 + xcd) * (SB * SB) + (jj % (SB * SB));
     }
     if (item >= n_items) return;
-    if (!locate(t, nf, item, [kend, row0, s_only](const InvDev& d) {
-          const int all = (int)outer_tiles(d.P, kend, row0, s_in_sweep(d));
-          return s_only ? all - (int)outer_tiles(d.P, kend, row0, false) : all; }, f, local)) return;
+    if (!locate(t, nf, item, [kend, row0](const InvDev& d) {
+          return (int)(outer_tiles(d.P, kend, row0, s_in_sweep(d)) - outer_tiles(d.P, kend, row0, false)); }, f, local)) return;
     const int r = t[f].P - row0;
-    const int nsb = (r + SB - 1) / SB;
-    const int n_trail_sb = nsb * (nsb + 1) / 2;
-    const int sb = local / (SB * SB) + (s_only ? n_trail_sb : 0), in = local % (SB * SB);
+    const int s2 = local / (SB * SB), in = local % (SB * SB);
     const int di = in / SB, dj = in - di * SB;
-    if (sb < n_trail_sb) {
-      int a = 0, tl = sb;
-      while (tl > a) { tl -= a + 1; ++a; }
-      const int ri = a * SB + di, rj = tl * SB + dj;          // relative to row0
-      if (ri >= r || rj > ri) return;
-      trailing = true; i = row0 + ri; j = row0 + rj;
-    } else {
-      const int s2 = sb - n_trail_sb;
-      const int ncb = (kend + SB - 1) / SB;
-      const int a = s2 / ncb, cb = s2 - a * ncb;
-      const int ri = a * SB + di; j = cb * SB + dj;
-      if (ri >= r || j >= kend) return;
-      trailing = false; i = row0 + ri;
-    }
+    const int ncb = (kend + SB - 1) / SB;
+    const int a = s2 / ncb, cb = s2 - a * ncb;
+    const int ri = a * SB + di; j = cb * SB + dj;
+    if (ri >= r || j >= kend) return;
+    trailing = false; i = row0 + ri;
   }
   const InvDev& d = t[f];
   const int np = d.np;
@@ -529,9 +517,7 @@ __device__ __forceinline__ void outer_update_body(const InvDev* __restrict__ t, 
 __global__ void __launch_bounds__(INV_THREADS, 3)
 outer_update_kernel(const InvDev* __restrict__ t, int nf, int k0, int kend, int lo, int hi, int strip, int n_items) {
   __shared__ double As[NB * OPA], Bs[NB * OPA > OKS * LDA ? NB * OPA : OKS * LDA];
-  if (!strip) KT_BEGIN(254)
   outer_update_body<2>(t, nf, k0, kend, lo, hi, strip, n_items, As, Bs);
-  if (!strip) KT_END(255)
 }
 // ------------------------------------------------------------------------------------------------
 // The far update of KFAC.invert's sweeps (trailing tiles only: their inverse is accumulated elsewhere, in fp32) with
@@ -1668,16 +1654,13 @@ static int stream_set(StreamSet** out) {
   CURV_HIP_CHECK(hipGetDevice(&dev));
   for (auto& e : cache) if (e.first == dev) { *out = &e.second; return CURV_OK; }
   StreamSet s;
-  int plo = 0, phi = 0;
-  CURV_HIP_CHECK(hipDeviceGetStreamPriorityRange(&plo, &phi));
-  // the large group's chain of short launches is the critical path of the sweep: highest priority
-  static const int aux_prio = getenv("CURV_AUX_PRIO") ? atoi(getenv("CURV_AUX_PRIO")) : 1;
-  CURV_HIP_CHECK(hipEventCreateWithFlags(&s.ev_fork, hipEventDisableTiming));
-  CURV_HIP_CHECK(hipEventCreateWithFlags(&s.ev_join, hipEventDisableTiming));
-  // the far updates are throughput work: lowest priority, so that the latency-critical chain launches of
-  // the other streams get workgroup slots first
+  // the large group's chain of short launches is the critical path of the sweep: highest priority; the far updates are
+  // throughput work: lowest priority, so that the latency-critical chain launches of the other streams get workgroup
+  // slots first
   int prio_low = 0, prio_high = 0;
   CURV_HIP_CHECK(hipDeviceGetStreamPriorityRange(&prio_low, &prio_high));
+  CURV_HIP_CHECK(hipEventCreateWithFlags(&s.ev_fork, hipEventDisableTiming));
+  CURV_HIP_CHECK(hipEventCreateWithFlags(&s.ev_join, hipEventDisableTiming));
   CURV_HIP_CHECK(hipEventCreateWithFlags(&s.ev_join2, hipEventDisableTiming));
   for (int g = 0; g < 2; ++g) CURV_HIP_CHECK(hipEventCreateWithFlags(&s.ev_chain[g], hipEventDisableTiming));
   // The far updates fill every workgroup slot they can get (4 per CU), and a retiring far workgroup frees
@@ -1707,26 +1690,9 @@ static int stream_set(StreamSet** out) {
     CURV_HIP_CHECK(hipStreamCreateWithPriority(out, hipStreamNonBlocking, prio_low));
     return CURV_OK;
   };
-  // Test hook (CURV_STREAM_ORDER; tests/test_invert_gpu.py, tools/stream_sensitivity.py, LAB_NOTEBOOK R5.6): creation order of
-  // the set's streams with dummies between them: a = large chain, m = small chain, 0 / 1 = far-update streams, x / p / h / l =
-  // unused CU-masked / plain / high-priority / low-priority stream (the dummies live as long as the process)
-  if (const char* order = getenv("CURV_STREAM_ORDER")) {
-    for (const char* c = order; *c; ++c) {
-      hipStream_t dummy = nullptr;
-      switch (*c) {
-        case 'a': CURV_HIP_CHECK(hipStreamCreateWithPriority(&s.aux, hipStreamNonBlocking, phi)); break;
-        case 'm': CURV_HIP_CHECK(hipStreamCreateWithFlags(&s.masked, hipStreamNonBlocking)); break;
-        case '0': { const int rc = wide_stream(&s.side[0].stream); if (rc != CURV_OK) return rc; } break;
-        case '1': { const int rc = wide_stream(&s.side[1].stream); if (rc != CURV_OK) return rc; } break;
-        case 'x': { const int rc = wide_stream(&dummy); if (rc != CURV_OK) return rc; } break;
-        case 'p': CURV_HIP_CHECK(hipStreamCreateWithFlags(&dummy, hipStreamNonBlocking)); break;
-        case 'h': CURV_HIP_CHECK(hipStreamCreateWithPriority(&dummy, hipStreamNonBlocking, phi)); break;
-        case 'l': CURV_HIP_CHECK(hipStreamCreateWithPriority(&dummy, hipStreamNonBlocking, plo)); break;
-        default: break;
-      }
-    }
-  }
-  if (s.aux == nullptr) CURV_HIP_CHECK(hipStreamCreateWithPriority(&s.aux, hipStreamNonBlocking, aux_prio ? phi : plo));
+  // Creation order aux, masked, side[0], side[1]: it decides which hardware queue, and so which pipe of the command
+  // processor, each stream gets (see await_verdict; LAB_NOTEBOOK R5.6).
+  CURV_HIP_CHECK(hipStreamCreateWithPriority(&s.aux, hipStreamNonBlocking, prio_high));
   // The small group's chain: a plain stream.  Measured alternatives (round 5, ResNet-50 factors): CU-masked like the far
   // updates' streams (the reserved CUs then belong to the large group's chain alone) 7.5 -> 8.5 ms -
   // the small group's own chain starves beside the far updates; on the LOW priority level (the runtime keeps a pool of
@@ -1734,9 +1700,9 @@ static int stream_set(StreamSet** out) {
   // no effect on the creation-order sensitivity, 6.9 / 6.9 / 11.0 ms for none / three streams after / three before the
   // set, as with a normal stream.  What the four busy streams of a sweep need is four different hardware pipes; a
   // fifth busy stream of any kind (CU-masked, low priority, shared between the groups) costs 4-5 ms.
-  if (s.masked == nullptr) CURV_HIP_CHECK(hipStreamCreateWithFlags(&s.masked, hipStreamNonBlocking));
+  CURV_HIP_CHECK(hipStreamCreateWithFlags(&s.masked, hipStreamNonBlocking));
   for (int g = 0; g < 2; ++g) {
-    if (s.side[g].stream == nullptr) { const int rc = wide_stream(&s.side[g].stream); if (rc != CURV_OK) return rc; }
+    { const int rc = wide_stream(&s.side[g].stream); if (rc != CURV_OK) return rc; }
     for (int i = 0; i < 2; ++i) {
       CURV_HIP_CHECK(hipEventCreateWithFlags(&s.side[g].ev_main[i], hipEventDisableTiming));
       CURV_HIP_CHECK(hipEventCreateWithFlags(&s.side[g].ev_side[i], hipEventDisableTiming));
@@ -1796,10 +1762,7 @@ extern "C" size_t curv_chol_inv_workspace_bytes(const curv_inv_desc* descs, int 
 // second group of a whole-model inversion started when the first one's last panels ran, whatever event it waited for;
 // tools/trace_buckets.py), so a group that is to start beside another one must be enqueued beside it.
 // block columns per outer panel (GroupSweep::begin has the measurements)
-static int sweep_nbo(bool latency_bound) {
-  static const int nbo_env = getenv("CURV_NBO") ? atoi(getenv("CURV_NBO")) : 0;
-  return latency_bound ? 4 : (nbo_env > 0 ? nbo_env : 6);
-}
+static int sweep_nbo(bool latency_bound) { return latency_bound ? 4 : 6; }
 struct GroupSweep {
   hipStream_t stream;
   SideStream* side;
@@ -1853,11 +1816,10 @@ struct GroupSweep {
     // then the near part of the outer update (the block columns / rows the NEXT chain touches); the rest of
     // the outer update goes to a second stream and overlaps the following chains (see below).
     // launches narrower than the GPU take the 1024-thread form of the tile kernels (see tile_product_k32)
-    static const long long wide_near = getenv("CURV_WIDE_NEAR") ? atoll(getenv("CURV_WIDE_NEAR")) : 512;
-    static const long long wide_prod = getenv("CURV_WIDE_PROD") ? atoll(getenv("CURV_WIDE_PROD")) : 256;
+    constexpr long long WIDE_NEAR = 512, WIDE_PROD = 256;
     // ... and below this many jobs the quarter form of the panel product (panel_product_quarter_kernel)
-    static const long long quarter_prod_env = getenv("CURV_QUARTER_PROD") ? atoll(getenv("CURV_QUARTER_PROD")) : 512;
-    quarter_prod = latency_bound ? quarter_prod_env : 0;
+    constexpr long long QUARTER_PROD = 512;
+    quarter_prod = latency_bound ? QUARTER_PROD : 0;
     // A call with few factors (a layer-sharded rank, a single large factor) is bound by the latency of its chain: the block
     // square of a panel then goes into one launch whose workgroups hand tiles to each other (chol_square_kernel), and the
     // panel product takes the quarter form.  A whole model on one GPU gains nothing from them (round 3: 8.40 ms with the
@@ -1901,7 +1863,7 @@ struct GroupSweep {
       if (jobs <= quarter_prod)
         hipExtLaunchKernelGGL(panel_product_quarter_kernel, dim3((unsigned)(cdivll(jobs, 8) * 32)), dim3(INV_THREADS), 0, st,
                               nullptr, done, 0, tb, n_factors, k0, kend);
-      else if (jobs <= wide_prod)
+      else if (jobs <= WIDE_PROD)
         hipExtLaunchKernelGGL(panel_product_wide_kernel, dim3((unsigned)jobs), dim3(1024), 0, st, nullptr, done, 0, tb, n_factors,
                               k0, kend);
       else
@@ -1916,10 +1878,9 @@ struct GroupSweep {
       inv_jobs += xrow_tiles(d.P, s_kind(d), k0, kend);
       inv_tiles += supd_tiles(d.P, s_kind(d), kend);
     }
-    static const int ext_events = getenv("CURV_EXT_EVENTS") ? atoi(getenv("CURV_EXT_EVENTS")) : 1;
     bool fork_recorded = false;           // ev_main rides on the panel product's completion
     if (prod_tiles > 0) {   // rows below the square (right-hand side mode: and the columns of Zm): one triangular product each
-      fork_recorded = ext_events != 0 && !capturing;
+      fork_recorded = !capturing;
       const int rc = launch_product(stream, prod_tiles, fork_recorded ? side->ev_main[panel & 1] : nullptr);
       if (rc != CURV_OK) return rc;
     }
@@ -1929,11 +1890,9 @@ struct GroupSweep {
     // "mid" strip so that a far update has two chain periods before anything waits for it was measured
     // 2-4 % slower: the far updates are throughput-bound, not waited for.)
     long long near_tiles = 0, far_tiles = 0;
-    bool any_s_part = false;
     for (const InvDev& d : tab) {
       near_tiles += strip_tiles(d.P, kend, kend, row0, s_in_sweep(d));
       far_tiles += outer_tiles(d.P, kend, row0, s_in_sweep(d));
-      any_s_part = any_s_part || s_in_sweep(d);
     }
     hipStream_t inv_st = side->stream;
     // (Measured and removed, LAB_NOTEBOOK R5.3 / R5.7: the near update on the side stream in front of the far update -
@@ -1941,26 +1900,19 @@ struct GroupSweep {
     // its own - every additional busy hardware queue costs far more than it brings, 7.5 -> 11.1 ms.)
     const bool inv_work = inv_jobs > 0 || inv_tiles > 0;
     const bool side_work = far_tiles > 0 || inv_work;
-    // fork: the side stream's work needs this panel's chain.  CURV_FORK_AFTER_NEAR=1 forks BEHIND the near update (a far
-    // update launched beside it takes every CU but the reserved ones and the near update then runs in rounds on those: one
-    // 4608^2 40 -> 14 us per panel) - measured neutral: the side stream's work moves 25 us later and lands on the next panel
-    // product instead (17 -> 45 us); one 4608^2 2.63 vs 2.66 ms, whole model 6.87 vs 6.84 ms over six pairs
-    static const int fork_late_env = getenv("CURV_FORK_AFTER_NEAR") ? atoi(getenv("CURV_FORK_AFTER_NEAR")) : 0;
-    const bool fork_late = fork_late_env != 0;
-    auto fork = [&]() -> int {
-      if (side_work) {
-        if (!fork_recorded || fork_late) CURV_HIP_CHECK(hipEventRecord(side->ev_main[panel & 1], stream));
-        CURV_HIP_CHECK(hipStreamWaitEvent(side->stream, side->ev_main[panel & 1], 0));
-      }
-      return CURV_OK;
-    };
-    if (!fork_late) { const int rc = fork(); if (rc != CURV_OK) return rc; }
+    // fork: the side stream's work needs this panel's chain.  (Forking BEHIND the near update instead was measured
+    // neutral: the side stream's work moves 25 us later and lands on the next panel product; one 4608^2 2.63 vs 2.66 ms,
+    // whole model 6.87 vs 6.84 ms over six pairs.)
+    if (side_work) {
+      if (!fork_recorded) CURV_HIP_CHECK(hipEventRecord(side->ev_main[panel & 1], stream));
+      CURV_HIP_CHECK(hipStreamWaitEvent(side->stream, side->ev_main[panel & 1], 0));
+    }
     if (near_tiles > 0) {
       if (far_pending) {                         // join: the previous far part wrote the tiles updated here
         CURV_HIP_CHECK(hipStreamWaitEvent(stream, side->ev_side[(panel + 1) & 1], 0));
       }
       far_pending = false;
-      if (near_tiles <= wide_near)
+      if (near_tiles <= WIDE_NEAR)
         hipLaunchKernelGGL(outer_update_wide_kernel, dim3((unsigned)near_tiles), dim3(1024), 0, stream, table, n_factors,
                            k0, kend, kend, row0, 1, (int)near_tiles);
       else
@@ -1968,37 +1920,27 @@ struct GroupSweep {
                            kend, kend, row0, 1, (int)near_tiles);
       CURV_LAUNCH_CHECK();
     }
-    if (fork_late) { const int rc = fork(); if (rc != CURV_OK) return rc; }
     if (far_tiles > 0) {
-      const long long grid = cdivll(far_tiles, 8 * SB * SB) * 8 * SB * SB;
-      const bool ride = ext_events != 0 && !capturing;
+      const bool ride = !capturing;
       const InvDev* tb = table;
-      // trailing tiles only (KFAC.invert: the inverse is accumulated in fp32 off the chain): the LDS-DMA form
-      static const int far_dma = getenv("CURV_FAR_DMA") ? atoi(getenv("CURV_FAR_DMA")) : 1;
-      if (far_dma && !any_s_part)
-        hipExtLaunchKernelGGL(outer_update_dma_kernel, dim3((unsigned)grid), dim3(INV_THREADS), 0, side->stream, nullptr,
-                              ride ? side->ev_side[panel & 1] : nullptr, 0, tb, n_factors, k0, kend, row0, (int)far_tiles);
-      else if (far_dma) {
-        // a sweep that accumulates its inverse itself (curv_chol_factor_inverse, INF's fp64 chain): the trailing tiles on the
-        // LDS-DMA form, the S tiles (B operand as [k][col]) on the register-staged one, one launch each
-        long long trail = 0;
-        for (const InvDev& d : tab) trail += outer_tiles(d.P, kend, row0, false);
-        const long long s_tiles = far_tiles - trail;
-        if (trail > 0) {
-          const long long g1 = cdivll(trail, 8 * SB * SB) * 8 * SB * SB;
-          hipExtLaunchKernelGGL(outer_update_dma_kernel, dim3((unsigned)g1), dim3(INV_THREADS), 0, side->stream, nullptr,
-                                (ride && s_tiles == 0) ? side->ev_side[panel & 1] : nullptr, 0, tb, n_factors, k0, kend, row0, (int)trail);
-          CURV_LAUNCH_CHECK();
-        }
-        if (s_tiles > 0) {
-          const long long g2 = cdivll(s_tiles, 8 * SB * SB) * 8 * SB * SB;
-          hipExtLaunchKernelGGL(outer_update_kernel, dim3((unsigned)g2), dim3(INV_THREADS), 0, side->stream, nullptr,
-                                ride ? side->ev_side[panel & 1] : nullptr, 0, tb, n_factors, k0, kend, row0, 0, 2, (int)s_tiles);
-        }
-      } else
-        hipExtLaunchKernelGGL(outer_update_kernel, dim3((unsigned)grid), dim3(INV_THREADS), 0, side->stream, nullptr,
-                              ride ? side->ev_side[panel & 1] : nullptr, 0, tb, n_factors, k0, kend, row0, 0, 0, (int)far_tiles);
-      CURV_LAUNCH_CHECK();
+      // the trailing tiles on the LDS-DMA form; the S tiles (B operand as [k][col]) of a sweep that accumulates its
+      // inverse itself (curv_chol_factor_inverse, INF's fp64 chain) on the register-staged one.  KFAC.invert's sweeps
+      // accumulate the inverse in fp32 off the chain: no S tiles, one launch.
+      long long trail = 0;
+      for (const InvDev& d : tab) trail += outer_tiles(d.P, kend, row0, false);
+      const long long s_tiles = far_tiles - trail;
+      if (trail > 0) {
+        const long long g1 = cdivll(trail, 8 * SB * SB) * 8 * SB * SB;
+        hipExtLaunchKernelGGL(outer_update_dma_kernel, dim3((unsigned)g1), dim3(INV_THREADS), 0, side->stream, nullptr,
+                              (ride && s_tiles == 0) ? side->ev_side[panel & 1] : nullptr, 0, tb, n_factors, k0, kend, row0, (int)trail);
+        CURV_LAUNCH_CHECK();
+      }
+      if (s_tiles > 0) {
+        const long long g2 = cdivll(s_tiles, 8 * SB * SB) * 8 * SB * SB;
+        hipExtLaunchKernelGGL(outer_update_kernel, dim3((unsigned)g2), dim3(INV_THREADS), 0, side->stream, nullptr,
+                              ride ? side->ev_side[panel & 1] : nullptr, 0, tb, n_factors, k0, kend, row0, 0, 2, (int)s_tiles);
+        CURV_LAUNCH_CHECK();
+      }
       if (!ride) CURV_HIP_CHECK(hipEventRecord(side->ev_side[panel & 1], side->stream));
       far_pending = true;
     }
@@ -2069,8 +2011,7 @@ struct EarlyStatus { int* host; const int* dev; size_t bytes; hipEvent_t ev; };
 // only (6.9 / 6.8 / 10.9 -> 6.8 / 6.8 / 7.3 ms for none / three streams after / three before the set).  The plain entry
 // point (no host wait: graph capture, check=False) joins at once and keeps the sensitivity.
 static int await_verdict(const EarlyStatus* early) {
-  static const int late_join = getenv("CURV_LATE_JOIN") ? atoi(getenv("CURV_LATE_JOIN")) : 1;
-  if (early != nullptr && late_join) CURV_HIP_CHECK(hipEventSynchronize(early->ev));
+  if (early != nullptr) CURV_HIP_CHECK(hipEventSynchronize(early->ev));
   return CURV_OK;
 }
 
@@ -2102,9 +2043,6 @@ static int chol_sweep(hipStream_t stream, std::vector<InvDev>& tab, void* worksp
   // a chain-bound call is swept as ONE group: the square kernel gives every factor its own workgroups, so the small
   // factors do not widen the large one's chain launches, and half the launches, events and waits remain (the host needs
   // 0.5 ms to enqueue the two sweeps of an 18-factor shard whose kernels take 0.6 ms)
-  static const int one_group_env = getenv("CURV_ONE_GROUP") ? atoi(getenv("CURV_ONE_GROUP")) : 1;
-  static const int force_one = getenv("CURV_FORCE_ONE_GROUP") ? atoi(getenv("CURV_FORCE_ONE_GROUP")) : 0;
-  const bool one_group = (latency_bound && one_group_env != 0) || force_one != 0;
   for (InvDev& d : tab) {
     d.W = reinterpret_cast<double*>(p); p += (size_t)d.np * d.np * sizeof(double);
     d.X = reinterpret_cast<double*>(p); p += (size_t)d.np * d.np * sizeof(double);
@@ -2114,7 +2052,7 @@ static int chol_sweep(hipStream_t stream, std::vector<InvDev>& tab, void* worksp
       d.X32 = reinterpret_cast<float*>(p); p += (size_t)d.np * d.np * sizeof(float);
       d.S32 = reinterpret_cast<float*>(p); p += (size_t)d.np * d.np * sizeof(float);
     }
-    (d.P > split || one_group ? big : small).push_back(d);
+    (d.P > split || latency_bound ? big : small).push_back(d);
   }
   StreamSet* ss = nullptr;
   { const int rc = stream_set(&ss); if (rc != CURV_OK) return rc; }
@@ -2164,24 +2102,20 @@ static int chol_sweep(hipStream_t stream, std::vector<InvDev>& tab, void* worksp
   // The large group is bound by its far updates in its first panels and by its chain in its last ones (the far
   // work shrinks with (P^2 - k^2), the chain does not): the small group starts when the large one has done
   // `start_panel` panels, so that its throughput work fills the large group's chain-bound tail.
-  static const int start_frac = getenv("CURV_SMALL_START") ? atoi(getenv("CURV_SMALL_START")) : 30;  // percent of the panels
+  constexpr int START_FRAC = 30;               // percent of the panels
   // (ResNet-50: 0 -> 9.25 ms, 20 -> 9.2, 30 -> 9.0, 40 -> 9.2, 50 -> 9.5)
   const int n_panels = cdiv(Pmax, sweep_nbo(latency_bound));
   long long far0 = 0;                          // far tiles of the large group's first panel
   for (const InvDev& d : big) far0 += outer_tiles(d.P, 4, 8, s_in_sweep(d));
   // only a far-bound large group has such a tail to fill (a chain step is ~54 us, a far tile ~0.04 us of the
   // whole GPU): with [2048 | 1024, 512, 256] the delay costs 8 %
-  const int start_panel = far0 >= 5000 ? std::min(n_panels - 1, n_panels * start_frac / 100) : 0;
+  const int start_panel = far0 >= 5000 ? std::min(n_panels - 1, n_panels * START_FRAC / 100) : 0;
   // (the chain-bound forms for the large group of a whole model: 6.7-7.0 vs 6.7-6.8 ms, LAB_NOTEBOOK R5.3 - not kept)
   // The two sweeps are enqueued panel by panel, the small group's panel t - start_panel behind the large group's panel t:
   // the event the small group's stream waits for (the large group has done `start_panel` panels) is then the large
   // group's stream TAIL at the moment of the wait, which is what hipStreamWaitEvent effectively waits for.
   GroupSweep gb(ss->aux, &ss->side[0], big, table0, flags0, latency_bound);
-  // CURV_SMALL_ONE_STREAM=1: the small group's far updates and fp32 inverse on its chain's stream (three busy streams)
-  static const int small_one = getenv("CURV_SMALL_ONE_STREAM") ? atoi(getenv("CURV_SMALL_ONE_STREAM")) : 0;
-  SideStream side_small = ss->side[1];
-  if (small_one) side_small.stream = ss->masked;
-  GroupSweep gs(ss->masked, small_one ? &side_small : &ss->side[1], small, table1, flags1, latency_bound);
+  GroupSweep gs(ss->masked, &ss->side[1], small, table1, flags1, latency_bound);
   int rc = gb.begin();
   if (rc != CURV_OK) return rc;
   bool small_started = false;

@@ -1127,10 +1127,9 @@ static int build_plan(const curv_factor_desc* descs, int n, Plan& plan) {
       // percent of the matrix pipe and kept it resident - holding half of their CUs' registers - for 5 ms beside the LDS-DMA
       // kernel; the implicit-im2col kernel gathers every MFMA operand from the LDS image by 4-byte reads between scalar
       // branches (0.60 of the pipe, round 6: 1.24 ms for what the LDS-DMA kernel does in 0.9).
-      static const int sub_on = getenv("CURV_FLAT_SUB") ? atoi(getenv("CURV_FLAT_SUB")) : 1;
       FactorDev g = f;
       g.C = f.rows; g.H = 1; g.W = f.Ho * f.Wo; g.kh = g.kw = g.sh = g.sw = 1; g.ph = g.pw = 0; g.compact = 1;
-      if (sub_on && (long long)f.Ho * f.Wo < (1LL << 30) && (long long)f.N * f.rows * f.Ho * f.Wo < (1LL << 29) &&
+      if ((long long)f.Ho * f.Wo < (1LL << 30) && (long long)f.N * f.rows * f.Ho * f.Wo < (1LL << 29) &&
           syrk_flat_eligible(g, reinterpret_cast<const void*>(16))) {
         f.sub = 1;
         f.C = g.C; f.H = 1; f.W = g.W; f.Ho = 1; f.Wo = g.W;

@@ -24,7 +24,6 @@
 //     of peak, 32 at two 0.57-0.60 - continues.  The same change made gemm_nt_kernel, whose tiles have short K ranges,
 //     slower: 1.45 -> 1.55 ms per sample, so that kernel keeps its 32-wide stages).
 // Work items, slabs and the wave roles on diagonal tiles are those of syrk.hip; syrk_reduce_kernel sums the slabs.
-#include <cstdlib>
 #include <cstring>
 #include <algorithm>
 #include <vector>
@@ -79,9 +78,8 @@ bool syrk_flat_eligible(const FactorDev& f, const void* src) {
   // land in tile rows and columns that neither epilogue stores (direct_store_block masks them, syrk_reduce_kernel does
   // not read them).  The range check does not stand in for this: a panel's row offset travels in soffset, which LLVM
   // does not document as covered by it
-  static const int ragged = getenv("CURV_FLAT_RAGGED") ? atoi(getenv("CURV_FLAT_RAGGED")) : 1;
   if (!(f.compact && f.H == 1 && f.kh == 1 && f.kw == 1 && f.sh == 1 && f.sw == 1 && f.ph == 0 && f.pw == 0)) return false;
-  if (f.has_bias || f.dim < (ragged ? 96 : flat::TM) || f.dim % (ragged ? 16 : flat::TM) != 0) return false;
+  if (f.has_bias || f.dim < 96 || f.dim % 16 != 0) return false;
   if (f.W < 8) return false;
   if ((long long)f.N * f.C * f.W * 4 >= (1LL << 31) - 4096) return false;
   return (reinterpret_cast<uintptr_t>(src) & 3) == 0;

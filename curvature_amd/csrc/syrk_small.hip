@@ -14,7 +14,6 @@
 // blocks go to slabs; syrk_small_reduce_kernel sums a block's slices in a fixed order (bit-reproducible), scales, adds
 // into the factor and writes the mirror block.
 #include <algorithm>
-#include <cstdlib>
 #include <vector>
 
 #include "syrk_plan.h"
@@ -230,8 +229,6 @@ constexpr int SMALL_MAX_SLICES = 64;     // the reduce pass walks a block's slic
 struct SmallPlan { std::vector<SmallDev> f; long long wgs = 0, red_wgs = 0, slab_floats = 0; };
 
 static bool small_plan(const curv_factor_desc* descs, int n, SmallPlan& plan) {
-  const char* env = getenv("CURV_KFAC_SMALL");
-  if (env != nullptr && atoi(env) == 0) return false;
   if (n <= 0 || n > 4 * SMALL_CHUNK) return false;
   // the caller may have decided for the whole (unsharded) model: a rank's share must not switch forms on its own size
   bool forced = n > 0;

@@ -481,7 +481,7 @@ def chol_inv_lower(factors: Sequence[torch.Tensor], adds: Sequence[float], multi
     L = _lib.lib()
     need = L.curv_chol_inv_workspace_bytes(arr, n)
     ws = workspace(need, dev, "invert")
-    early = check and not torch.cuda.is_current_stream_capturing() and os.environ.get("CURV_EARLY_STATUS", "1") != "0"
+    early = check and not torch.cuda.is_current_stream_capturing()
     if early:
         # the verdict travels to pinned host memory BEFORE the finalize passes (curv_chol_inv_lower_status): the host
         # waits for that copy only, and what it does next - raising, or preparing the sampler's launches - runs in the
@@ -912,7 +912,7 @@ def eigh(mats: Sequence[torch.Tensor], with_values: bool = False, max_sweeps: in
     # Wide, numerically rank-deficient matrices (a KFAC factor with fewer samples than rows) are projected onto their range
     # inside the library (csrc/eigh_lowrank.hip: only the k x k projected problem is iterated on); the others - and every
     # matrix that turns out not to be rank-deficient - take the block-Jacobi iteration on the whole matrix.  `_project=False`
-    # (or CURV_EIGH_LOWRANK=0 in the environment) asks for the plain iteration.
+    # asks for the plain iteration.
     n = len(mats)
     arr = (curv_eigh_desc * n)()
     vecs, vals = [], []

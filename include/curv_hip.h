@@ -123,8 +123,8 @@ int curv_kfac_plan_info(const curv_factor_desc* descs, int n_factors, long long*
  * implicit-im2col kernel, the LDS-DMA kernel for flattened factors, for the shifted correlations of 3x3 / stride 1 /
  * padding 1 factors and for the unfolded copies of stride-2 3x3 / strided 1x1 ones, one reduce launch for each, plus a
  * padding pass and an assembly pass when such 3x3 factors are present and an unfold pass for the strided ones).  A launch that is small as a whole (LeNet scale: at most 2 GFLOP) takes a two-launch build of its own
- * instead (32 x 32 blocks x K slices gathered straight from the tensors, then a reduce pass; CURV_KFAC_SMALL=0 in the
- * environment keeps such a launch on the grouped kernels).  `descs` is a host array; it may be reused as soon as the call
+ * instead (32 x 32 blocks x K slices gathered straight from the tensors, then a reduce pass; path_hint = CURV_PATH_GROUPED
+ * keeps such a launch on the grouped kernels).  `descs` is a host array; it may be reused as soon as the call
  * returns.  A factor depends on nothing outside its `src`: the memory around a source may hold any bit pattern, NaN
  * included (every kernel form is tested on sources fenced by NaN).  Two staging forms may still FETCH a few bytes past the
  * end of `src` and discard them: the LDS-DMA kernel for flattened factors in the last 16-byte group of a source whose rows
@@ -501,8 +501,8 @@ int curv_syevd(void* stream, const curv_eigh_desc* descs, int n_mats, void* work
  * finder, rank from a pivoted Cholesky of its Gram matrix, Cholesky-QR, the iteration on the k x k projected matrix only, an
  * orthonormal basis of the complement for the zero eigenvalues; accepted iff ||F - P F P|| <= 3e-6 ||F||, otherwise the matrix
  * takes the iteration on the whole matrix like all others.  Same outputs, same order.  The workspace size above includes
- * what the projection needs (about 1.2 GB per 4608-wide matrix).  CURV_EIGH_LOWRANK=0 in the environment, an explicit
- * max_sweeps or an explicit tol select the plain iteration.
+ * what the projection needs (about 1.2 GB per 4608-wide matrix).  An explicit max_sweeps or an explicit tol selects the
+ * plain iteration.
  * curv_syevd_ex: the same call; `ranks` (optional host array, n_mats ints) receives per matrix the rank k of the projected
  * problem, or 0 for a matrix that went through the plain iteration. */
 int curv_syevd_ex(void* stream, const curv_eigh_desc* descs, int n_mats, void* workspace, size_t workspace_bytes,

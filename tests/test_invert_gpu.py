@@ -99,11 +99,12 @@ def test_not_positive_definite_raises(gpu):
 
 
 @pytest.mark.parametrize("count", [3, 80])
-def test_early_verdict_equals_the_status_words(gpu, count, monkeypatch):
+def test_early_verdict_equals_the_status_words(gpu, count):
     """`curv_chol_inv_lower_status`: the status words copied to pinned host memory before the finalize passes are the
     words the device holds when the call is complete, for a chain-bound call (3 factors: one group) and a whole-model call
     (80: two groups on two streams) with failing factors among them; the inverse factors are bit-identical to the plain
-    call's, and the failure is reported for the same factors with the same pivots."""
+    call's (`check=False`, then `check_chol_info`), and the failure is reported for the same factors with the same
+    pivots."""
     from curvature_amd import ops
     torch.manual_seed(count)
     sizes = ([70, 300, 1100] * 27)[:count]
@@ -113,23 +114,22 @@ def test_early_verdict_equals_the_status_words(gpu, count, monkeypatch):
         Fs.append((X @ X.t() / n).contiguous())
     adds, muls = [0.5] * count, [1.0] * count
     good = [t.clone() for t in ops.chol_inv_lower(Fs, adds, muls)]
-    monkeypatch.setenv("CURV_EARLY_STATUS", "0")
-    plain = ops.chol_inv_lower(Fs, adds, muls)
+    plain = ops.chol_inv_lower(Fs, adds, muls, check=False)
+    ops.check_chol_info(plain.info)
     assert all(torch.equal(a, b) for a, b in zip(good, plain))
-    monkeypatch.delenv("CURV_EARLY_STATUS")
     bad = [1, count - 1]
     for b in bad:
         Fs[b] = Fs[b].clone()
         Fs[b][5, 5] = -3.0                         # pivot 6 fails (no damping can save it at add = 0.5)
     messages = []
-    for switch in ("1", "0"):
-        monkeypatch.setenv("CURV_EARLY_STATUS", switch)
-        with pytest.raises(RuntimeError) as err:
-            ops.chol_inv_lower(Fs, adds, muls)
-        messages.append(str(err.value))
-    assert messages[0] == messages[1] and str(bad) in messages[0].replace(" ", "").replace(",", ", ")
-    monkeypatch.delenv("CURV_EARLY_STATUS")
+    with pytest.raises(RuntimeError) as err:
+        ops.chol_inv_lower(Fs, adds, muls)
+    messages.append(str(err.value))
     outs = ops.chol_inv_lower(Fs, adds, muls, check=False)
+    with pytest.raises(RuntimeError) as err:
+        ops.check_chol_info(outs.info)
+    messages.append(str(err.value))
+    assert messages[0] == messages[1] and str(bad) in messages[0].replace(" ", "").replace(",", ", ")
     words = outs.info.cpu()
     assert sorted(torch.nonzero(words).flatten().tolist()) == bad
     for k in range(count):
@@ -192,15 +192,10 @@ def test_same_result_whatever_the_stream_layout(gpu, tmp_path):
         "filler = [torch.eye(8, device='cuda') * (i + 1.0) for i in range(70)]\n"
         "Ls += list(ops.chol_inv_lower(Fs + filler, [1.0] * 74, [1000.0] * 74))[:4]\n"
         f"torch.save([L.cpu() for L in Ls], {str(tmp_path / 'out.pt')!r})\n")
-    # ... nor may any of the sweep's other orchestration switches: plain event records instead of events riding on the
-    # launches, the caller's stream joining at once, the set's streams created in another order (the large chain's queue on
-    # the caller's pipe), the small group on one stream
-    for extra in ({"CURV_FREE_CUS": "0"}, {"CURV_EXT_EVENTS": "0", "CURV_LATE_JOIN": "0"}, {"CURV_STREAM_ORDER": "xm01a"},
-                  {"CURV_SMALL_ONE_STREAM": "1", "CURV_FORK_AFTER_NEAR": "1"}):
-        subprocess.run([sys.executable, str(script)], check=True, env=dict(os.environ, **extra), timeout=300)
-        there = torch.load(tmp_path / "out.pt")
-        for a, b in zip(here, there):
-            assert torch.equal(a, b), extra
+    subprocess.run([sys.executable, str(script)], check=True, env=dict(os.environ, CURV_FREE_CUS="0"), timeout=300)
+    there = torch.load(tmp_path / "out.pt")
+    for a, b in zip(here, there):
+        assert torch.equal(a, b)
 
 
 def test_chain_bound_and_throughput_forms_agree(gpu):

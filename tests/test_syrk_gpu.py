@@ -35,10 +35,20 @@ def fenced_copy(t, offset):
 
 @pytest.fixture(autouse=True, params=["grouped", "small"])
 def build_path(request, monkeypatch):
-    """Every case of this file runs twice: through the grouped build of syrk.hip (what a model that fills the GPU gets)
-    and with the two-launch small-model build of syrk_small.hip allowed (what most of these geometries - a handful of
-    samples - are routed to by default; cases above its size limit take the grouped path in both runs)."""
-    monkeypatch.setenv("CURV_KFAC_SMALL", "0" if request.param == "grouped" else "1")
+    """Every case of this file runs twice: through the grouped build of syrk.hip (what a model that fills the GPU gets:
+    every descriptor carries path_hint = PATH_GROUPED, KFAC.update's included) and with the two-launch small-model build
+    of syrk_small.hip allowed (what most of these geometries - a handful of samples - are routed to by default; cases
+    above its size limit take the grouped path in both runs)."""
+    if request.param == "grouped":
+        from curvature_amd import _lib, ops
+        descs = ops._factor_descs
+
+        def grouped(*args, **kwargs):
+            arr = descs(*args, **kwargs)
+            for d in arr:
+                d.path_hint = _lib.PATH_GROUPED
+            return arr
+        monkeypatch.setattr(ops, "_factor_descs", grouped)
     return request.param
 
 

@@ -1,6 +1,6 @@
 #!/bin/bash
 # same-box A/B of an environment switch of the library: bench.py's headline run with and without it, interleaved
-#   gpurun -- 'bash tools/ab_env.sh 3 CURV_BIG_FAR=1000000000'
+#   bash tools/ab_env.sh 3 CURV_FREE_CUS=0
 ROUNDS=$1; shift
 for r in $(seq 1 $ROUNDS); do
   for setting in "" "$@"; do

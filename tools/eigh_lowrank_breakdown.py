@@ -33,6 +33,5 @@ print(f"three 4608: {timed(lambda: ops.eigh(big)):.0f} ms (low-rank {ops.eigh.la
 print(f"one 4608: {timed(lambda: ops.eigh(big[:1])):.0f} ms")
 rest = [m for m in mats if m.shape[0] != 4608]
 print(f"the other 105: {timed(lambda: ops.eigh(rest)):.0f} ms (low-rank {ops.eigh.last_lowrank})")
-os.environ["CURV_EIGH_LOWRANK"] = "0"
-print(f"one 4608, iteration on the whole matrix: {timed(lambda: ops.eigh(big[:1])):.0f} ms")
-print(f"all 108, iteration on the whole matrices: {timed(lambda: ops.eigh(mats)):.0f} ms")
+print(f"one 4608, iteration on the whole matrix: {timed(lambda: ops.eigh(big[:1], _project=False)):.0f} ms")
+print(f"all 108, iteration on the whole matrices: {timed(lambda: ops.eigh(mats, _project=False)):.0f} ms")

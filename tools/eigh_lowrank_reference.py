@@ -44,7 +44,7 @@ def eigh_lowrank(mats: Sequence[torch.Tensor], index: Sequence[int]) -> dict:
         Sd = (Fd + Fd.t()) * 0.5
         S.append(Sd)
         nS2.append((Sd * Sd).sum())
-        r = int(n * float(os.environ.get("CURV_EIGH_PROBE", LOWRANK_PROBE))) // 64 * 64
+        r = int(n * LOWRANK_PROBE) // 64 * 64
         r_of.append(r)
         om = randn((n, r), dev, 0x5EED0000 + n, 0).double()
         jobs.append(Gemm64(Sd, om))

@@ -64,8 +64,8 @@ def main():
     big = 1 << 62
     kt = lambda s_, e_: ((big - t[s_] - t0) / 100.0 if t[s_] else float("nan"), (t[e_] - t0) / 100.0 if t[e_] else float("nan"))
     print("launches of this panel, first workgroup in -> last workgroup out (us after the square kernel's start): "
-          "panel product %.1f -> %.1f | near update %.1f -> %.1f | far update %.1f -> %.1f | next panel's square kernel starts %.1f"
-          % (kt(236, 237) + kt(252, 253) + kt(254, 255) + (us(t[238]),)))
+          "panel product %.1f -> %.1f | near update %.1f -> %.1f | next panel's square kernel starts %.1f"
+          % (kt(236, 237) + kt(252, 253) + (us(t[238]),)))
 
 
 if __name__ == "__main__":
