@@ -754,19 +754,6 @@ def _reject_grouped(est, what: str) -> None:
                                       "supported; select other layer types or use KFAC")
 
 
-def _factor_source(t: Tensor, groups: int, fp32: bool = False) -> Tensor:
-    """A recorded activation / gradient as the factor build takes it: contiguous; float32 or (ordinary layers)
-    bfloat16 / float16.  A grouped layer's half-precision side becomes a float32 copy on the device: the grouped build
-    (curv_kfac_group_accumulate) has no half-precision form; neither has the transposed-convolution A-side build
-    (`fp32`)."""
-    t = t.detach()
-    if t.dtype not in (torch.float32, torch.bfloat16, torch.float16):
-        raise RuntimeError(f"KFAC.update expects float32, bfloat16 or float16 activations and gradients, got {t.dtype}")
-    if (groups > 1 or fp32) and t.dtype != torch.float32:
-        return t.float().contiguous()
-    return t.contiguous()
-
-
 def _pairs(first: Tensor, second: Tensor):
     """(L_A, L_G) of a layer as per-group lists of 2-D views: one pair for an ordinary layer, G for a grouped one."""
     if first.dim() == 3:
@@ -788,6 +775,9 @@ class KFAC(Curvature):
         super().__init__(model, layer_types, shard=shard)
         self.hooks = list()
         self.record = dict()
+        self._fresh = set()                          # (layer, side) of factors that nothing has written yet
+        self._out_size = dict()                      # ConvTranspose2d layer -> (Ho, Wo) its last forward produced
+        self._path_hints = dict()                    # sharded update(): recorded shapes -> launch form of the whole model
         for layer in model.modules():
             name = layer.__class__.__name__
             if name in self.layer_types:
@@ -824,7 +814,7 @@ class KFAC(Curvature):
     def _hook_output(self, module, input, output):
         if _is_convt(module):
             # the output size carries the effective output_padding (layer(x, output_size=...) changes it)
-            self.__dict__.setdefault("_out_size", {})[module] = tuple(output.shape[-2:])
+            self._out_size[module] = tuple(output.shape[-2:])
         if output.requires_grad:
             output.register_hook(lambda grad, module=module: self._save_output(module, grad))
 
@@ -850,132 +840,46 @@ class KFAC(Curvature):
         gradients; the G side is divided by ``grad_scale ** 2``.  The caller skips ``update()`` on the steps the scaler
         skips (non-finite gradients)."""
         jobs, group_jobs, half_jobs, convt_jobs = [], [], [], []
+        launch = {ops.FactorJob: jobs, ops.GroupFactorJob: group_jobs, ops.HalfFactorJob: half_jobs,
+                  ops.ConvTFactorJob: convt_jobs}
         if not grad_scale > 0:
             raise ValueError(f"KFAC.update: grad_scale must be positive, got {grad_scale}")
         g_div = float(grad_scale) ** 2
-        fresh = getattr(self, "_fresh", None)
-        if fresh is None:
-            fresh = self._fresh = set()              # factors allocated here that nothing has written yet
         for _, layer in self._owned():
             forward, backward = self.record[layer]
             if (inputs and forward is None) or (grads and backward is None):
                 raise RuntimeError("KFAC.update: no recorded forward/backward pass for a selected layer")
-            has_bias = layer.bias is not None
-            x = g = None
-            groups = _groups_of(layer)
-            convt = _is_convt(layer)
-            if forward is not None:
-                x = _factor_source(forward, groups, fp32=convt)
-            if backward is not None:
-                g = _factor_source(backward, groups)
-            if convt:
-                kernel, stride, padding = layer.kernel_size, layer.stride, layer.padding
-                C, m = layer.in_channels, layer.out_channels
-                N = (x if x is not None else g).shape[0]
-                if g is not None:
-                    out_size = tuple(g.shape[2:])
-                elif layer in self.__dict__.get("_out_size", {}):
-                    out_size = self._out_size[layer]
-                else:                                        # records that did not pass this estimator's hooks
-                    out_size = tuple((x.shape[2 + d] - 1) * stride[d] - 2 * padding[d] + kernel[d] +
-                                     layer.output_padding[d] for d in range(2))
-                L = out_size[0] * out_size[1]
-                n = C * kernel[0] * kernel[1] + int(has_bias)
-            elif layer.__class__.__name__ == 'Conv2d':
-                kernel, stride, padding = layer.kernel_size, layer.stride, layer.padding
-                C, m = layer.in_channels // groups, layer.out_channels // groups
-                N = (x if x is not None else g).shape[0]
-                if g is not None:
-                    L = g.shape[2] * g.shape[3]
-                else:
-                    L = ((x.shape[2] + 2 * padding[0] - kernel[0]) // stride[0] + 1) * \
-                        ((x.shape[3] + 2 * padding[1] - kernel[1]) // stride[1] + 1)
-                n = C * kernel[0] * kernel[1] + int(has_bias)
-            else:
-                if x is not None and x.dim() != 2:      # (N, *, in) inputs: flatten the leading dims
-                    x = x.reshape(-1, x.shape[-1])
-                if g is not None and g.dim() != 2:
-                    g = g.reshape(-1, g.shape[-1])
-                N = (x if x is not None else g).shape[0]
-                C, m = layer.in_features, layer.out_features
-                kernel, stride, padding, L = (1, 1), (1, 1), (0, 0), 1
-                n = C + int(has_bias)
-            dev = (x if x is not None else g).device
+            sides = ops.factor_jobs(layer, forward, backward, self._out_size.get(layer))
+            N, L = sides.N, sides.L
             if layer not in self.state:
                 # a side that is not written by this call must start from zero, not from garbage
                 alloc = torch.empty if (inputs and grads) else torch.zeros
-                lead = (groups,) if groups > 1 else ()
-                self.state[layer] = [alloc(*lead, n, n, dtype=torch.float32, device=dev),
-                                     alloc(*lead, m, m, dtype=torch.float32, device=dev)]
+                dev = (sides.a or sides.g).src.device
+                lead = (sides.groups,) if sides.groups > 1 else ()   # a grouped layer: one Kronecker pair per group
+                self.state[layer] = [alloc(*lead, sides.n, sides.n, dtype=torch.float32, device=dev),
+                                     alloc(*lead, sides.m, sides.m, dtype=torch.float32, device=dev)]
                 if inputs and grads:
-                    fresh.update(((layer, 0), (layer, 1)))
+                    self._fresh.update(((layer, 0), (layer, 1)))
             A, G = self.state[layer]
-            if groups > 1:
-                # one Kronecker pair per group (curv_kfac_group_accumulate); same scales as an ordinary layer
-                if inputs:
-                    first = (layer, 0) in fresh
-                    fresh.discard((layer, 0))
-                    group_jobs.append(ops.GroupFactorJob(x, A, groups, kernel, stride, padding, has_bias,
-                                                         float(input_weight) / (N * L), first))
-                if grads:
-                    first = (layer, 1) in fresh
-                    fresh.discard((layer, 1))
-                    group_jobs.append(ops.GroupFactorJob(g, G, groups, (1, 1), (1, 1), (0, 0), False,
-                                                         float(N) / L / g_div, first))
-                continue
-            if inputs and convt:
-                first = (layer, 0) in fresh
-                fresh.discard((layer, 0))
-                if x.dim() != 4:
-                    raise RuntimeError("KFAC.update: ConvTranspose2d inputs must be (N, C, H, W)")
-                convt_jobs.append(ops.ConvTFactorJob(x, A, kernel, stride, padding, out_size, has_bias,
-                                                     float(input_weight) / (N * L), first))
-            elif inputs:
-                first = (layer, 0) in fresh
-                fresh.discard((layer, 0))
-                if x.dtype == torch.float32:
-                    jobs.append(ops.FactorJob(x, A, kernel, stride, padding, has_bias, float(input_weight) / (N * L), first))
-                else:
-                    half_jobs.append(ops.HalfFactorJob(x, A, kernel, stride, padding, has_bias,
-                                                       float(input_weight) / (N * L), first))
+            if inputs:
+                job = sides.a
+                job.dst, job.scale, job.first = A, float(input_weight) / (N * L), self._take_fresh(layer, 0)
+                launch[type(job)].append(job)
             if grads:
-                first = (layer, 1) in fresh
-                fresh.discard((layer, 1))
-                if g.dtype == torch.float32:
-                    jobs.append(ops.FactorJob(g, G, (1, 1), (1, 1), (0, 0), False, float(N) / L / g_div, first))
-                else:
-                    half_jobs.append(ops.HalfFactorJob(g, G, (1, 1), (1, 1), (0, 0), False, float(N) / L / g_div, first))
+                job = sides.g                            # same scales for every kind of layer
+                job.dst, job.scale, job.first = G, float(N) / L / g_div, self._take_fresh(layer, 1)
+                launch[type(job)].append(job)
         if self.shard is not None and self.shard.world > 1:
             # the launch form is a property of the MODEL, not of this rank's share: a share under the small-launch threshold
-            # would otherwise sum its factors in another order than the unsharded run (which is over it)
-            # (decided by the library itself - curv_kfac_path_for evaluates every gate of the small form, not only the
-            # flops - on the geometry of ALL selected layers: the hooks record every layer on every rank)
-            geoms, known = [], True
-            for layer in self._layers():
-                if _groups_of(layer) > 1:                        # built by curv_kfac_group_accumulate
-                    continue
-                forward, backward = self.record[layer]
-                if (inputs and forward is None) or (grads and backward is None):
-                    known = False
-                    break
-                # half-precision sides are built by curv_kfac16_accumulate, whose plans are per factor
-                fwd32 = inputs and forward.dtype == torch.float32
-                bwd32 = grads and backward.dtype == torch.float32
-                if _is_convt(layer):                             # A side: curv_kfac_convt_accumulate, per factor
-                    if bwd32:
-                        geoms.append((*backward.shape, (1, 1), (1, 1), (0, 0), False))
-                elif layer.__class__.__name__ == 'Conv2d':
-                    if fwd32:
-                        geoms.append((*forward.shape, layer.kernel_size, layer.stride, layer.padding, layer.bias is not None))
-                    if bwd32:
-                        geoms.append((*backward.shape, (1, 1), (1, 1), (0, 0), False))
-                else:
-                    if fwd32:
-                        geoms.append((forward.numel() // forward.shape[-1], forward.shape[-1], 1, 1, (1, 1), (1, 1), (0, 0),
-                                      layer.bias is not None))
-                    if bwd32:
-                        geoms.append((backward.numel() // backward.shape[-1], backward.shape[-1], 1, 1, (1, 1), (1, 1), (0, 0), False))
-            hint = ops.kfac_path_for(geoms) if known else _lib.PATH_GROUPED
+            # would otherwise sum its factors in another order than the unsharded run (which is over it).  It follows
+            # from the recorded shapes and dtypes of ALL selected layers (the hooks record every layer on every rank),
+            # so it is worked out once per set of them
+            records = [(layer, *(t if t is None else ops.ShapeOnly(t.shape, t.dtype) for t in self.record[layer]))
+                       for layer in self._layers()]
+            key = (inputs, grads, tuple(r[1:] for r in records))
+            hint = self._path_hints.get(key)
+            if hint is None:
+                hint = self._path_hints[key] = self._unsharded_path(records, inputs, grads)
             for job in jobs:
                 job.path_hint = hint
         if getattr(self, "_count_flops", False):                 # bench.py: what the launch plan executes
@@ -986,14 +890,32 @@ class KFAC(Curvature):
         ops.kfac_accumulate_half(half_jobs)
         ops.kfac_accumulate_convt(convt_jobs)
 
+    def _unsharded_path(self, records, inputs: bool, grads: bool) -> int:
+        """The launch form of the fp32 factor build of an unsharded update() on `records` = [(layer, input, grad_output)]
+        (`ops.ShapeOnly`s): decided by the library itself (curv_kfac_path_for evaluates every gate of the small form, not
+        only the flops) for the sides that come back as `FactorJob`.  Grouped, half-precision and transposed-convolution
+        A sides are built by launches of their own, whose plans are per factor."""
+        model_jobs = []
+        for layer, forward, backward in records:
+            if (inputs and forward is None) or (grads and backward is None):
+                return _lib.PATH_GROUPED
+            sides = ops.factor_jobs(layer, forward, backward, self._out_size.get(layer))
+            model_jobs += [job for job, wanted in ((sides.a, inputs), (sides.g, grads))
+                           if wanted and isinstance(job, ops.FactorJob)]
+        return ops.kfac_path_for(model_jobs)
+
+    def _take_fresh(self, layer, side: int) -> bool:
+        """True once for a factor that nothing has written yet: its next build overwrites instead of adding."""
+        if (layer, side) in self._fresh:
+            self._fresh.discard((layer, side))
+            return True
+        return False
+
     def restart_accumulation(self) -> None:
         """The next `update()` overwrites the factors of every layer instead of adding to them (the tensors, their
         addresses and the launch plans built on them stay).  Extension of the reference API: its only way to start
         over is a new estimator."""
-        fresh = getattr(self, "_fresh", None)
-        if fresh is None:
-            fresh = self._fresh = set()
-        fresh.update((layer, side) for layer in self.state for side in (0, 1))
+        self._fresh.update((layer, side) for layer in self.state for side in (0, 1))
 
     def invert(self, add: Union[float, list, tuple] = 0., multiply: Union[float, list, tuple] = 1., *, check: bool = True):
         """`check=False` (keyword-only extension): skip the read-back of the status words - the call's only host

@@ -5,9 +5,10 @@ Every wrapper requires CUDA(=HIP) fp32 contiguous tensors and raises ``RuntimeEr
 there is no CPU fallback.
 """
 import ctypes
+import math
 import os
 import threading
-from typing import List, Optional, Sequence
+from typing import List, NamedTuple, Optional, Sequence
 
 import torch
 
@@ -84,7 +85,8 @@ _kfac_last = {}                        # thread ident -> the "kfac" workspace it
 
 
 class FactorJob:
-    """One Kronecker-factor accumulation: dst (+)= scale * unfold(src) unfold(src)^T."""
+    """One Kronecker-factor accumulation: dst (+)= scale * unfold(src) unfold(src)^T.  `src` may also be just its shape
+    (plan queries)."""
     __slots__ = ("src", "dst", "kernel", "stride", "padding", "has_bias", "scale", "first", "path_hint")
 
     def __init__(self, src, dst, kernel=(1, 1), stride=(1, 1), padding=(0, 0), has_bias=False,
@@ -102,22 +104,25 @@ def small_path_flop(dim: int, K: int) -> float:
     return 2.0 * 1024.0 * (nb * (nb + 1) // 2) * float(K)
 
 
-def _factor_descs(jobs: Sequence[FactorJob]):
+def _factor_descs(jobs: Sequence[FactorJob], check_tensors: bool = True):
     n = len(jobs)
     arr = (curv_factor_desc * n)()
     for d, j in zip(arr, jobs):
-        _require_gpu(j.src, j.dst)
-        if j.src.dim() == 4:
-            N, C, H, W = j.src.shape
-        elif j.src.dim() == 2:
-            (N, C), H, W = j.src.shape, 1, 1
+        if check_tensors:
+            _require_gpu(j.src, j.dst)
+        shape = tuple(j.src.shape) if check_tensors else tuple(j.src)
+        if len(shape) == 4:
+            N, C, H, W = shape
+        elif len(shape) == 2:
+            (N, C), H, W = shape, 1, 1
         else:
             raise RuntimeError("factor source must be (N,C,H,W) or (N,C)")
-        dim = C * j.kernel[0] * j.kernel[1] + int(j.has_bias)
-        if tuple(j.dst.shape) != (dim, dim):
-            raise RuntimeError(f"factor destination must be ({dim},{dim}), got {tuple(j.dst.shape)}")
-        d.src, d.dst = j.src.data_ptr(), j.dst.data_ptr()
-        d.N, d.C, d.H, d.W = N, C, H, W
+        if check_tensors:
+            dim = C * j.kernel[0] * j.kernel[1] + int(j.has_bias)
+            if tuple(j.dst.shape) != (dim, dim):
+                raise RuntimeError(f"factor destination must be ({dim},{dim}), got {tuple(j.dst.shape)}")
+            d.src, d.dst = j.src.data_ptr(), j.dst.data_ptr()
+        d.N, d.C, d.H, d.W = int(N), int(C), int(H), int(W)
         d.kh, d.kw = j.kernel
         d.sh, d.sw = j.stride
         d.ph, d.pw = j.padding
@@ -126,22 +131,16 @@ def _factor_descs(jobs: Sequence[FactorJob]):
     return arr
 
 
-def kfac_path_for(geometries) -> int:
+def kfac_path_for(factors) -> int:
     """The launch form (``_lib.PATH_SMALL`` / ``_lib.PATH_GROUPED``) a factor build of exactly these factors takes on its
     own, decided by the library (curv_kfac_path_for: flops, factor count, slice length, workgroup count).
-    `geometries`: one ``(N, C, H, W, kernel, stride, padding, has_bias)`` per factor of the UNSHARDED model; host only."""
-    geometries = list(geometries)
-    n = len(geometries)
-    if n == 0:
+    `factors`: the fp32 factors of the UNSHARDED model, each a `FactorJob` (its `src` may be just a shape) or a tuple
+    ``(N, C, H, W, kernel, stride, padding, has_bias)``; host only."""
+    jobs = [f if isinstance(f, FactorJob) else FactorJob(f[:4], None, *f[4:]) for f in factors]
+    if not jobs:
         return _lib.PATH_GROUPED
-    arr = (curv_factor_desc * n)()
-    for d, (N, C, H, W, kernel, stride, padding, has_bias) in zip(arr, geometries):
-        d.N, d.C, d.H, d.W = int(N), int(C), int(H), int(W)
-        d.kh, d.kw = kernel
-        d.sh, d.sw = stride
-        d.ph, d.pw = padding
-        d.has_bias, d.first, d.scale, d.path_hint = int(has_bias), 1, 1.0, 0
-    return int(_lib.lib().curv_kfac_path_for(arr, n))
+    arr = _factor_descs(jobs, check_tensors=all(isinstance(j.src, torch.Tensor) for j in jobs))
+    return int(_lib.lib().curv_kfac_path_for(arr, len(jobs)))
 
 
 PLAN_INFO_FIELDS = 25                 # CURV_PLAN_INFO_FIELDS
@@ -149,10 +148,11 @@ PLAN_INFO_FIELDS = 25                 # CURV_PLAN_INFO_FIELDS
 
 def kfac_plan_flops(jobs: Sequence[FactorJob]) -> List[int]:
     """Multiply-add FLOPs the launch plan executes for each job (curv_kfac_plan_info, last field): dim (dim + 1) K for
-    a symmetric product; the sum over its 29 shifted correlations for a 3x3 / stride 1 / pad 1 factor."""
+    a symmetric product; the sum over its 29 shifted correlations for a 3x3 / stride 1 / pad 1 factor.  `job.src` may
+    be a tensor or just its shape (host only)."""
     if not jobs:
         return []
-    arr = _factor_descs(jobs)
+    arr = _factor_descs(jobs, check_tensors=all(isinstance(j.src, torch.Tensor) for j in jobs))
     out = (ctypes.c_longlong * (PLAN_INFO_FIELDS * len(jobs)))()
     _lib.check(_lib.lib().curv_kfac_plan_info(arr, len(jobs), out), "curv_kfac_plan_info")
     return [int(out[PLAN_INFO_FIELDS * i + PLAN_INFO_FIELDS - 1]) for i in range(len(jobs))]
@@ -396,6 +396,108 @@ def kfac_accumulate_convt(jobs: Sequence[ConvTFactorJob], events=None) -> None:
                "curv_kfac_convt_accumulate")
     if events is not None:
         events[1].record()
+
+
+class LayerJobs(NamedTuple):
+    """The two factor builds of one layer (`factor_jobs`): `a` / `g` the job of the A / G side (None without a source),
+    `n` / `m` the widths of A / G (of one group's, for a grouped layer), `N` samples of `L` positions each."""
+    a: object
+    g: object
+    n: int
+    m: int
+    N: int
+    L: int
+    groups: int
+
+    @property
+    def K(self) -> int:
+        """Columns summed over by either side."""
+        return self.N * self.L
+
+
+class ShapeOnly(NamedTuple):
+    """Stand-in for a recorded tensor where `factor_jobs` is asked for a plan only: its shape and dtype."""
+    shape: tuple
+    dtype: torch.dtype = torch.float32
+
+
+def _factor_source(t, fp32: bool, flatten: bool):
+    """A recorded activation / gradient as the factor build takes it: contiguous; float32 or (ordinary layers)
+    bfloat16 / float16.  A grouped layer's half-precision side becomes a float32 copy on the device: the grouped build
+    (curv_kfac_group_accumulate) has no half-precision form; neither has the transposed-convolution A-side build
+    (`fp32`).  `flatten`: the (N, *, in) input of a Linear layer as (rows, in).  A `ShapeOnly` stays one."""
+    if t is None:
+        return None
+    if t.dtype not in (torch.float32, torch.bfloat16, torch.float16):
+        raise RuntimeError(f"KFAC.update expects float32, bfloat16 or float16 activations and gradients, got {t.dtype}")
+    if isinstance(t, ShapeOnly):
+        shape = tuple(t.shape)
+        if flatten and len(shape) != 2:
+            shape = (math.prod(shape[:-1]), shape[-1])
+        return ShapeOnly(shape, torch.float32 if fp32 else t.dtype)
+    t = t.detach()
+    if fp32 and t.dtype != torch.float32:
+        t = t.float()
+    t = t.contiguous()
+    if flatten and t.dim() != 2:
+        t = t.reshape(-1, t.shape[-1])
+    return t
+
+
+def factor_jobs(layer, x, g, out_size=None) -> LayerJobs:
+    """Which build each side of a selected layer goes to, and with which geometry: the one place that knows the layer
+    kinds (Linear and attention projections, Conv2d, grouped Conv2d, ConvTranspose2d) and the dtype routing.
+
+    `x` / `g`: the recorded input / grad_output (either may be None: that side gets no job) or `ShapeOnly`
+    stand-ins (the jobs' `src` is then a shape: plan queries).  Each side is routed by its dtype: float32 to `FactorJob`,
+    bfloat16 / float16 to `HalfFactorJob`; both sides of a grouped convolution to `GroupFactorJob` and the A side of a
+    transposed convolution to `ConvTFactorJob`, as float32.  `out_size`: the output size a ConvTranspose2d forward was
+    seen to produce (it carries the effective output_padding), used when there is no `g` to read it from.  The jobs come
+    without `dst`, `scale` and `first`."""
+    kind = layer.__class__.__name__
+    conv, convt = kind in ('Conv2d', 'ConvTranspose2d'), kind == 'ConvTranspose2d'
+    groups = int(layer.groups) if kind == 'Conv2d' else 1
+    has_bias = layer.bias is not None
+    x = _factor_source(x, fp32=groups > 1 or convt, flatten=not conv)
+    g = _factor_source(g, fp32=groups > 1, flatten=not conv)
+    if x is None and g is None:
+        raise RuntimeError("KFAC.update: no recorded forward/backward pass for a selected layer")
+    if conv:
+        kernel, stride, padding = layer.kernel_size, layer.stride, layer.padding
+        C, m = layer.in_channels // groups, layer.out_channels // groups
+        if convt and x is not None and len(x.shape) != 4:
+            raise RuntimeError("KFAC.update: ConvTranspose2d inputs must be (N, C, H, W)")
+        if g is not None:
+            out_size = tuple(g.shape[2:])
+        elif not convt:
+            out_size = tuple((x.shape[2 + d] + 2 * padding[d] - kernel[d]) // stride[d] + 1 for d in range(2))
+        elif out_size is None:                           # records that did not pass the estimator's hooks
+            out_size = tuple((x.shape[2 + d] - 1) * stride[d] - 2 * padding[d] + kernel[d] +
+                             layer.output_padding[d] for d in range(2))
+    else:
+        C, m = layer.in_features, layer.out_features
+        kernel, stride, padding, out_size = (1, 1), (1, 1), (0, 0), (1, 1)
+    a_job = g_job = None
+    if x is not None:
+        src = x.shape if isinstance(x, ShapeOnly) else x
+        if groups > 1:
+            a_job = GroupFactorJob(src, None, groups, kernel, stride, padding, has_bias)
+        elif convt:
+            a_job = ConvTFactorJob(src, None, kernel, stride, padding, out_size, has_bias)
+        elif x.dtype == torch.float32:
+            a_job = FactorJob(src, None, kernel, stride, padding, has_bias)
+        else:
+            a_job = HalfFactorJob(src, None, kernel, stride, padding, has_bias, dtype=x.dtype)
+    if g is not None:
+        src = g.shape if isinstance(g, ShapeOnly) else g
+        if groups > 1:
+            g_job = GroupFactorJob(src, None, groups)
+        elif g.dtype == torch.float32:
+            g_job = FactorJob(src, None)
+        else:
+            g_job = HalfFactorJob(src, None, dtype=g.dtype)
+    return LayerJobs(a_job, g_job, C * kernel[0] * kernel[1] + int(has_bias), m,
+                     (x if x is not None else g).shape[0], out_size[0] * out_size[1], groups)
 
 
 def rsqrt_affine(value: torch.Tensor, add: float, multiply: float, out: Optional[torch.Tensor] = None):

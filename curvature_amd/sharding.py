@@ -33,7 +33,7 @@ def lpt_partition(costs: Sequence[float], world: int) -> List[int]:
 
 def rank_cost(dims: Sequence[Sequence[float]], estimator: str = "kfac", rank: int = 100) -> float:
     """Estimated step time (s) of a rank that owns the layers `dims` = [(n, m, K, build_flops), ...] (`build_flops`:
-    what the factor build executes for the layer, from the library's own launch plan - `kfac_build_flops`; when it is
+    what the factor build executes for the layer, from the library's own launch plan - `layer_dims`; when it is
     missing the symmetric products (n (n + 1) + m (m + 1)) K are assumed).
 
     Not additive: the factors of a rank are inverted in one batched sweep, so the serial chains of 64-column steps
@@ -78,114 +78,20 @@ def rank_cost(dims: Sequence[Sequence[float]], estimator: str = "kfac", rank: in
     return total
 
 
-def layer_geometry(layer, x_shape: Sequence[int], g_shape: Sequence[int]):
-    """The two factor geometries (A side, G side) of a Linear / Conv2d layer as dicts of curv_factor_desc fields, from
-    the shapes of its recorded input and grad_output."""
-    bias = int(layer.bias is not None)
-    if layer.__class__.__name__ == "ConvTranspose2d":        # A: curv_convt_factor_desc fields (convt=1 marks them)
-        N, C, H, W = x_shape
-        (kh, kw), (sh, sw), (ph, pw) = layer.kernel_size, layer.stride, layer.padding
-        a = dict(N=N, C=C, H=H, W=W, kh=kh, kw=kw, sh=sh, sw=sw, ph=ph, pw=pw, Ho=g_shape[2], Wo=g_shape[3],
-                 has_bias=bias, convt=1)
-        g = dict(N=g_shape[0], C=g_shape[1], H=g_shape[2], W=g_shape[3], kh=1, kw=1, sh=1, sw=1, ph=0, pw=0, has_bias=0)
-    elif layer.__class__.__name__ == "Conv2d":
-        N, C, H, W = x_shape
-        (kh, kw), (sh, sw), (ph, pw) = layer.kernel_size, layer.stride, layer.padding
-        a = dict(N=N, C=C, H=H, W=W, kh=kh, kw=kw, sh=sh, sw=sw, ph=ph, pw=pw, has_bias=bias)
-        g = dict(N=g_shape[0], C=g_shape[1], H=g_shape[2], W=g_shape[3], kh=1, kw=1, sh=1, sw=1, ph=0, pw=0, has_bias=0)
-        if getattr(layer, "groups", 1) > 1:               # curv_group_factor_desc fields: C stays the total count
-            a["groups"] = g["groups"] = int(layer.groups)
-    else:
-        rows = 1
-        for v in x_shape[:-1]:
-            rows *= int(v)
-        a = dict(N=rows, C=x_shape[-1], H=1, W=1, kh=1, kw=1, sh=1, sw=1, ph=0, pw=0, has_bias=bias)
-        g = dict(N=rows, C=g_shape[-1], H=1, W=1, kh=1, kw=1, sh=1, sw=1, ph=0, pw=0, has_bias=0)
-    return a, g
-
-
-def kfac_build_flops(geometries: Sequence[dict]) -> List[int]:
-    """Multiply-add flops the library's launch plan executes for each factor geometry (curv_kfac_plan_info, host
-    only - no GPU needed): dim (dim + 1) K for a symmetric product, the sum over its 29 shifted correlations for a 3x3 /
-    stride 1 / padding 1 factor.  The partition asks the planner instead of re-stating its eligibility rules."""
-    import ctypes
-    from . import _lib
-    n = len(geometries)
-    if n == 0:
-        return []
-    convt = [i for i, d in enumerate(geometries) if d.get("convt", 0)]
-    if convt:                                             # transposed convolutions: curv_kfac_convt_plan_flops
-        carr = (_lib.curv_convt_factor_desc * len(convt))()
-        for i, a in zip(convt, carr):
-            for k, v in geometries[i].items():
-                if k != "convt":
-                    setattr(a, k, int(v))
-            a.scale = 1.0
-        cout = (ctypes.c_longlong * len(convt))()
-        _lib.check(_lib.lib().curv_kfac_convt_plan_flops(carr, len(convt), cout), "curv_kfac_convt_plan_flops")
-        in_convt = set(convt)
-        rest = [i for i in range(n) if i not in in_convt]
-        other = kfac_build_flops([geometries[i] for i in rest])
-        out = [0] * n
-        for i, v in zip(convt, cout):
-            out[i] = int(v)
-        for i, v in zip(rest, other):
-            out[i] = v
-        return out
-    grouped = [i for i, d in enumerate(geometries) if d.get("groups", 1) > 1]
-    if grouped:                                           # grouped convolutions: curv_kfac_group_plan_flops
-        garr = (_lib.curv_group_factor_desc * len(grouped))()
-        for i, a in zip(grouped, garr):
-            for k, v in geometries[i].items():
-                setattr(a, k, int(v))
-            a.scale = 1.0
-        gout = (ctypes.c_longlong * len(grouped))()
-        _lib.check(_lib.lib().curv_kfac_group_plan_flops(garr, len(grouped), gout), "curv_kfac_group_plan_flops")
-        in_grouped = set(grouped)
-        rest = [i for i in range(n) if i not in in_grouped]
-        plain = kfac_build_flops([geometries[i] for i in rest])
-        out = [0] * n
-        for i, v in zip(grouped, gout):
-            out[i] = int(v)
-        for i, v in zip(rest, plain):
-            out[i] = v
-        return out
-    arr = (_lib.curv_factor_desc * n)()
-    for d, a in zip(geometries, arr):
-        for k, v in d.items():
-            setattr(a, k, int(v))
-        a.scale = 1.0
-    fields = 25                                           # CURV_PLAN_INFO_FIELDS
-    out = (ctypes.c_longlong * (fields * n))()
-    _lib.check(_lib.lib().curv_kfac_plan_info(arr, n, out), "curv_kfac_plan_info")
-    return [int(out[fields * i + fields - 1]) for i in range(n)]
-
-
 def layer_dims(layers, shapes) -> List[tuple]:
-    """[(n, m, K, build flops)] per layer for `partition_layers` / `make_layer_shard`; `shapes[layer]` = (input
-    shape, grad_output shape) of one batch."""
-    geoms = []
-    for layer in layers:
-        a, g = layer_geometry(layer, *shapes[layer])
-        geoms += [a, g]
-    flops = kfac_build_flops(geoms)
-    dims = []
-    for i, layer in enumerate(layers):
-        a, g = geoms[2 * i], geoms[2 * i + 1]
-        G = a.get("groups", 1)
-        n = a["C"] // G * a["kh"] * a["kw"] + a["has_bias"]
-        if layer.__class__.__name__ == "ConvTranspose2d":
-            K = a["N"] * a["Ho"] * a["Wo"]
-        elif layer.__class__.__name__ == "Conv2d":
-            (kh, kw), (sh, sw), (ph, pw) = layer.kernel_size, layer.stride, layer.padding
-            K = a["N"] * ((a["H"] + 2 * ph - kh) // sh + 1) * ((a["W"] + 2 * pw - kw) // sw + 1)
-        else:
-            K = a["N"]
-        if G > 1:
-            dims.append((n, g["C"] // G, K, float(flops[2 * i] + flops[2 * i + 1]), G))
-        else:
-            dims.append((n, g["C"], K, float(flops[2 * i] + flops[2 * i + 1])))
-    return dims
+    """[(n, m, K, build flops)] per layer for `partition_layers` / `make_layer_shard` (a grouped convolution's entry
+    carries its group count fifth); `shapes[layer]` = (input shape, grad_output shape) of one batch, taken as float32.
+    The build flops are what the library's launch plans execute for the layer's two factors (host only - no GPU
+    needed): the partition asks the planner instead of re-stating its eligibility rules."""
+    from . import ops
+    sides = [ops.factor_jobs(layer, *map(ops.ShapeOnly, shapes[layer])) for layer in layers]
+    flops = {}
+    for cls, plan_flops in ((ops.FactorJob, ops.kfac_plan_flops), (ops.GroupFactorJob, ops.kfac_group_plan_flops),
+                            (ops.ConvTFactorJob, ops.kfac_convt_plan_flops)):
+        batch = [job for s in sides for job in (s.a, s.g) if type(job) is cls]
+        flops.update(zip(map(id, batch), plan_flops(batch)))
+    return [(s.n, s.m, s.K, float(flops[id(s.a)] + flops[id(s.g)])) + ((s.groups,) if s.groups > 1 else ())
+            for s in sides]
 
 
 def partition_layers(dims: Sequence[Sequence[int]], world: int, estimator: str = "kfac", rank: int = 100) -> List[int]:

@@ -57,7 +57,7 @@ def test_host_queries():
     K = 2 * 9 * 9
     assert out[0] == 2 * (9 * 10 // 2 + 9) * K * 16              # depthwise: whole triangle + patch sums per thread
     # wide groups: what the ordinary build executes for each group's own convolution
-    one = sharding.kfac_build_flops([dict(N=2, C=32, H=9, W=9, kh=3, kw=3, sh=1, sw=1, ph=1, pw=1, has_bias=1)])[0]
+    one = ops.kfac_plan_flops([ops.FactorJob((2, 32, 9, 9), None, (3, 3), (1, 1), (1, 1), True)])[0]
     assert out[1] == 2 * one > 0
     assert L.curv_kfac_group_accumulate(None, arr, 0, None, 0) == 0   # empty batch is a no-op
     # the Python helper takes shapes as well as tensors
