@@ -16,9 +16,10 @@ All arithmetic runs in ``libcurv_hip.so`` (hand-written HIP for gfx950) through 
 no CPU fallback: CPU models raise ``RuntimeError``.
 """
 import copy
+import math
 import numbers
 from abc import ABC, abstractmethod
-from typing import Any, Dict, List, Optional, Sequence, Union
+from typing import Any, Dict, List, NamedTuple, Optional, Sequence, Union
 
 import torch
 from torch import Tensor
@@ -60,18 +61,97 @@ def _wm_rows(layer) -> int:
     return layer.weight.shape[1] if _is_convt(layer) else layer.weight.shape[0]
 
 
-def _tap_views(layer, t: Tensor):
-    """[(columns, view)]: 2-D views of `t` (shaped like `layer.weight`) that together hold the weight columns of Wm,
-    `columns` = the matching slice of Wm's columns.  One view for Linear / Conv2d; one per kernel tap (a, b) for
-    ConvTranspose2d: Wm[:, ci kh kw + a kw + b] = weight[ci, :, a, b], a (out, in) view with strides (kh kw, out kh kw).
-    A product that writes these views writes Wm through the permutation, with no copy pass."""
-    if not _is_convt(layer):
-        return [(slice(None), t.view(t.shape[0], -1))]
-    cin, cout = t.shape[0], t.shape[1]
-    khw = t.numel() // (cin * cout)
-    n0 = cin * khw
-    v = t.view(cin, cout, khw)
-    return [(slice(k, n0, khw), v[:, :, k].t()) for k in range(khw)]
+class _Slot(NamedTuple):
+    """One piece of a layer's parameters as a block of columns of its [W | b] matrix (`_slots`)."""
+    cols: slice       # the columns of Wm this piece holds
+    view: Tensor      # (rows, len(cols)) view into the parameter storage
+    lead: bool        # Wm's leading columns stored as they are: only there a slice of a triangular factor stays triangular
+
+
+def _slots(layer, weight: Tensor, bias: Optional[Tensor]) -> List[_Slot]:
+    """Where the columns of the layer matrix [W | b] (Wm order: (out, in*kh*kw [+1]), the bias last) live in `weight` (shaped
+    like `layer.weight`) and `bias` (or None): slots that cover the columns exactly once, in the order the samplers launch
+    them.  One slot for the weight of a Linear / Conv2d; one per kernel tap (a, b) for a ConvTranspose2d:
+    Wm[:, ci kh kw + a kw + b] = weight[ci, :, a, b], an (out, in) view with strides (kh kw, out kh kw); the bias, if any,
+    is the last slot, an (out, 1) view.  A product that writes these views writes Wm through the permutation, with no copy
+    pass.  The same map serves the live parameters, their means in `model_state` and one set of a `SampleBank`.  A grouped
+    layer takes row blocks of the views: group g owns rows [g m, (g + 1) m)."""
+    if _is_convt(layer):
+        cin, cout = weight.shape[0], weight.shape[1]
+        khw = weight.numel() // (cin * cout)
+        n0 = cin * khw
+        v = weight.view(cin, cout, khw)
+        out = [_Slot(slice(k, n0, khw), v[:, :, k].t(), False) for k in range(khw)]
+    else:
+        w = weight.view(weight.shape[0], -1)
+        n0 = w.shape[1]
+        out = [_Slot(slice(0, n0), w, True)]
+    if bias is not None:
+        out.append(_Slot(slice(n0, n0 + 1), bias.view(-1, 1), False))
+    return out
+
+
+def _live_slots(layer) -> List[_Slot]:
+    """`_slots` of the layer's own parameters (what the fused samplers write)."""
+    weight, bias = layer._parameters['weight'], layer._parameters['bias']
+    return _slots(layer, weight.data, bias.data if bias is not None else None)
+
+
+def _bank_buffers(layer, count: int, device):
+    """(weights, biases or None): buffers for `count` fp32 parameter sets of the layer, set k to be addressed through
+    `_slots(layer, weights[k], biases[k])`.  A ConvTranspose2d's sets are held in the weight's own (in, out, kh, kw)
+    layout, every other layer's as (out, in*kh*kw)."""
+    w = layer.weight
+    shape = w.shape if _is_convt(layer) else (w.shape[0], w.numel() // w.shape[0])
+    weights = torch.empty(count, *shape, dtype=torch.float32, device=device)
+    if layer.bias is None:
+        return weights, None
+    return weights, torch.empty(count, _wm_rows(layer), dtype=torch.float32, device=device)
+
+
+def _largest_first(stage: list) -> None:
+    """Sort the products of one launch by M K N, largest first (stable): the tail of the launch is then made of the short
+    tiles."""
+    stage.sort(key=lambda j: -(j.A.shape[0] * j.A.shape[1] * j.B.shape[1]))
+
+
+def _run_of(tensors: Sequence[Tensor]) -> Optional[Tensor]:
+    """The flat view over `tensors` if they are contiguous fp32 tensors that lie back to back, in this order, inside ONE
+    allocation (an elementwise step over all of them is then one launch); None otherwise."""
+    if not tensors:
+        return None
+    pos = tensors[0].data_ptr()
+    for t in tensors:
+        if not t.is_contiguous() or t.dtype != torch.float32 or t.data_ptr() != pos:
+            return None
+        pos += 4 * t.numel()
+    head, total = tensors[0], (pos - tensors[0].data_ptr()) // 4
+    if head.untyped_storage().nbytes() < 4 * (head.storage_offset() + total):
+        return None
+    return torch.as_strided(head.reshape(-1), (total,), (1,))
+
+
+class _Arena:
+    """One flat fp32 buffer and one view per shape, laid out back to back: whole-model elementwise steps (noise scaling,
+    scalar-hyper-parameter inverts) then take ONE launch over `flat` instead of one per layer.  `flat` has at least one
+    element, also when there are no views (a layer-sharded rank can own nothing)."""
+
+    def __init__(self, shapes: Sequence[Sequence[int]], device, zero: bool = False):
+        sizes = [math.prod(map(int, shape)) for shape in shapes]
+        self.total = sum(sizes)
+        self.flat = (torch.zeros if zero else torch.empty)(max(self.total, 1), dtype=torch.float32, device=device)
+        self.views, pos = [], 0
+        for shape, count in zip(shapes, sizes):
+            self.views.append(self.flat[pos:pos + count].view(*shape))
+            pos += count
+
+    def is_whole(self, tensors: Sequence[Tensor]) -> bool:
+        """True if `tensors` are this arena's views, all of them, in order, back to back: one launch over `flat` then
+        does what a loop over `tensors` does.  (Checked by address: contiguous fp32 tensors that tile `flat` from its first
+        to its last element.)  False for an empty list, also on an arena without views: there is nothing to launch, the
+        per-layer loop of the caller is the empty one."""
+        run = _run_of(tensors)
+        return run is not None and run.data_ptr() == self.flat.data_ptr() and run.numel() == self.total
 
 
 def _is_scalar(x) -> bool:
@@ -190,6 +270,9 @@ class Curvature(ABC):
     # KFAC / EFB / INF: every selected MultiheadAttention module contributes its two projections as layers of their own
     # (`AttentionProjection`), an extension of the reference (which raises for them)
     _mha_as_projections = False
+    # the `_Arena`s this estimator allocated for its `state` / `inv_state` tensors (None until then): Diagonal and EFB
+    # keep the first two, INF the other three (its corrections D, Lambda_lr and r)
+    _state_arena = _inv_arena = _corr_arena = _lam_arena = _r_arena = None
 
     def __init__(self, model: Union[Module, Sequential], layer_types: Union[List[str], str] = None, *,
                  shard=None):
@@ -393,6 +476,22 @@ class Curvature(ABC):
                             self._state_keys[(proj, pname)] = proj.state_key(prefix, pname)
         return self.model_state[self._state_keys[(layer, name)]]
 
+    def _mean_slots(self, layer) -> List[_Slot]:
+        """`_slots` of the layer's mean (MAP) parameters inside ``model_state``."""
+        return _slots(layer, self.model_state_of(layer, 'weight'),
+                      self.model_state_of(layer, 'bias') if layer.bias is not None else None)
+
+    def _param_ptrs(self, layers, means: bool = True):
+        """(params, their addresses, the addresses of their means) of `layers`: the weight and, where there is one, the
+        bias of each.  The address tuples are parts of the samplers' plan keys (plain ints: `evaluate._drop_plans_for`
+        searches them); built by C-level loops, this runs in front of every sample of a BNN loop.  `means=False`: a
+        sampler that does not read the means leaves their addresses out."""
+        ptr = Tensor.data_ptr
+        params = [p for l in layers for p in (l._parameters['weight'], l._parameters['bias']) if p is not None]
+        mean = [self.model_state_of(l, nm) for l in layers for nm in ('weight', 'bias')
+                if l._parameters[nm] is not None] if means else ()
+        return params, tuple(map(ptr, params)), tuple(map(ptr, mean))
+
     @staticmethod
     def _replace(sample: Tensor, weight: Tensor, bias: Tensor = None):
         """weight += sample[:, :-1], bias += sample[:, -1] (curvatures.py:67-82)."""
@@ -426,7 +525,7 @@ class Curvature(ABC):
         # selected nn.MultiheadAttention modules (string keys, outside `_layers()`); left out, `replace_from` would reset
         # them to their means
         for mha in (self._attention() if self._supports_mha else []):
-            owned += [_InProjection.of(mha), mha.out_proj]
+            owned += AttentionProjection.of(mha)
         weights = {l: torch.empty(S, *l.weight.shape, dtype=l.weight.dtype, device=l.weight.device) for l in owned}
         biases = {l: (torch.empty(S, *l.bias.shape, dtype=l.bias.dtype, device=l.bias.device) if l.bias is not None else None)
                   for l in owned}
@@ -453,29 +552,18 @@ class Curvature(ABC):
         key = (index, tuple(map(Tensor.data_ptr, params)))
         plan = plans.get(key)
         if plan is None:
-            dsts, srcs = [], []
-            for layer in layers:
-                dsts.append(layer.weight.data)
-                srcs.append(bank.weights[layer][index].view(layer.weight.shape))
-                if layer.bias is not None:
-                    dsts.append(layer.bias.data)
-                    srcs.append(bank.biases[layer][index])
-            plan = plans[key] = ops.CopyPlan(dsts, srcs)
+            sets = [t[index] for l in layers for t in (bank.weights[l], bank.biases[l]) if t is not None]   # like `params`
+            plan = plans[key] = ops.CopyPlan([p.data for p in params], [t.view(p.shape) for p, t in zip(params, sets)])
         plan.run()
         self._reload_mean(skip=params)
         self._allgather_sampled()
 
     @staticmethod
     def _replace_layer(sample: Tensor, layer) -> None:
-        """`_replace` of an (out, in*kh*kw [+1]) sample in Wm order; a ConvTranspose2d weight takes it permuted."""
-        if not _is_convt(layer):
-            Curvature._replace(sample, layer.weight, layer.bias)
-            return
-        if layer.bias is not None:
-            layer.bias.data.add_(sample[:, -1])
-            sample = sample[:, :-1]
-        w = layer.weight
-        layer.weight.data.add_(sample.reshape(w.shape[1], w.shape[0], *w.shape[2:]).transpose(0, 1))
+        """`_replace` of an (out, in*kh*kw [+1]) sample in Wm order, for every kind of layer (a ConvTranspose2d weight
+        takes it permuted)."""
+        for slot in _live_slots(layer):
+            slot.view.add_(sample[:, slot.cols])
 
     def sample_and_replace(self):
         """Reset to the mean weights, then add one posterior sample per selected layer (curvatures.py:117-129)."""
@@ -507,10 +595,10 @@ class Diagonal(Curvature):
         new = [l for _, l in self._owned() if l not in self.state and l.weight.grad is not None]
         fresh = {}
         if new:
-            self._state_flat, views = _arena(
+            self._state_arena = _Arena(
                 [(_wm_rows(l), l.weight.numel() // _wm_rows(l) + int(l.bias is not None)) for l in new],
                 new[0].weight.device)
-            fresh = dict(zip(new, views))
+            fresh = dict(zip(new, self._state_arena.views))
         keys, items = [], []
         for layer in self.model.modules():
             name = layer.__class__.__name__
@@ -549,18 +637,20 @@ class Diagonal(Curvature):
         arena = {}
         fresh = [l for l in self.state if l not in self.inv_state and not isinstance(l, str)]
         if fresh:
-            self._inv_flat, views = _arena([tuple(self.state[l].shape) for l in fresh], self.state[fresh[0]].device)
-            arena = dict(zip(fresh, views))
+            self._inv_arena = _Arena([tuple(self.state[l].shape) for l in fresh], self.state[fresh[0]].device)
+            arena = dict(zip(fresh, self._inv_arena.views))
         plain = [l for l in self.state if not isinstance(l, str)]
-        state_flat, inv_flat = getattr(self, "_state_flat", None), getattr(self, "_inv_flat", None)
+        states, invs = self._state_arena, self._inv_arena
+        # (the last condition is not implied by the others: the inverse arena was shaped after whatever `state` held at
+        # the first inversion, and `state` may have been rebuilt since)
         whole = _is_scalar(add) and _is_scalar(multiply) and len(plain) == len(self.state) and \
-            _is_arena(state_flat, [self.state[l] for l in plain]) and \
-            _is_arena(inv_flat, [self.inv_state.get(l, arena.get(l)) for l in plain]) and \
-            state_flat.numel() == inv_flat.numel() == sum(self.state[l].numel() for l in plain)
+            states is not None and states.is_whole([self.state[l] for l in plain]) and \
+            invs is not None and invs.is_whole([self.inv_state.get(l, arena.get(l)) for l in plain]) and \
+            states.total == invs.total
         if whole:      # one pair of hyper-parameters, both dicts whole arenas (no attention entries): one launch
             for l in plain:
                 self.inv_state.setdefault(l, arena.get(l))
-            ops.rsqrt_affine(state_flat, float(add), float(multiply), out=inv_flat)
+            ops.rsqrt_affine(states.flat, float(add), float(multiply), out=invs.flat)
             return
         for position, (layer, value) in enumerate(self.state.items()):
             # Diagonal uses lists when both are list/tuple (curvatures.py:183); same outcome as _hyper.
@@ -593,46 +683,33 @@ class Diagonal(Curvature):
         [W | b] split straight onto the parameters (a K = 1 product with the `MUL_E_ADD_F` epilogue)."""
         assert self.inv_state, "Inverse state dict is empty. Did you call 'invert' prior to this?"
         layers = [l for _, l in self._owned() if l in self.inv_state]
-        self._reload_mean(skip=[p for l in layers for p in (l.weight, l.bias) if p is not None])
+        params, param_ptrs, mean_ptrs = self._param_ptrs(layers)
+        self._reload_mean(skip=params)
         if layers:
-            key = (tuple(self.inv_state[l].data_ptr() for l in layers),
-                   tuple(p.data_ptr() for l in layers for p in (l.weight, l.bias) if p is not None),
-                   tuple(self.model_state_of(l, nm).data_ptr() for l in layers for nm in ('weight', 'bias')
-                         if getattr(l, nm) is not None))
+            key = (tuple(map(Tensor.data_ptr, [self.inv_state[l] for l in layers])), param_ptrs, mean_ptrs)
             plan = self._sample_plans().get(key)
             if plan is None:
-                dev = self.inv_state[layers[0]].device
-                zflat, zs = _arena([tuple(self.inv_state[l].shape) for l in layers], dev)
-                rows = max(self.inv_state[l].shape[0] for l in layers)
-                cols = max(self.inv_state[l].shape[1] for l in layers)
-                ones_r = torch.ones(rows, 1, dtype=torch.float32, device=dev)
-                ones_c = torch.ones(1, cols, dtype=torch.float32, device=dev)
-                scale, jobs = [], []
-                for layer, z in zip(layers, zs):
-                    m, n = z.shape
-                    n0 = n - int(layer.bias is not None)
-                    scale.append((z, self.inv_state[layer]))
-                    w = layer.weight.data
-                    if not w.is_contiguous():
+                invs = [self.inv_state[l] for l in layers]
+                dev = invs[0].device
+                noise = _Arena([tuple(inv.shape) for inv in invs], dev)
+                ones_r = torch.ones(max(inv.shape[0] for inv in invs), 1, dtype=torch.float32, device=dev)
+                ones_c = torch.ones(1, max(inv.shape[1] for inv in invs), dtype=torch.float32, device=dev)
+                jobs = []
+                for layer, z in zip(layers, noise.views):
+                    if not layer.weight.data.is_contiguous():
                         raise RuntimeError("Diagonal.sample_and_replace: parameters must be contiguous")
-                    zw = z[:, :n0]
-                    for (cols, wv), (_, fv) in zip(_tap_views(layer, w),
-                                                   _tap_views(layer, self.model_state_of(layer, 'weight'))):
-                        jobs.append(ops.Gemm(ones_r[:m], ones_c[:, :wv.shape[1]], wv, epilogue=ops.EPI_MUL_E_ADD_F,
-                                             E=zw[:, cols], F=fv))
-                    if layer.bias is not None:
-                        jobs.append(ops.Gemm(ones_r[:m], ones_c[:, :1], layer.bias.data.view(m, 1),
-                                             epilogue=ops.EPI_MUL_E_ADD_F, E=z[:, n0:],
-                                             F=self.model_state_of(layer, 'bias').view(m, 1)))
-                inv_flat = getattr(self, "_inv_flat", None)
-                whole = _is_arena(inv_flat, [self.inv_state[l] for l in layers]) and \
-                    sum(self.inv_state[l].numel() for l in layers) == zflat.numel()
-                plan = (key, zflat, scale, ops.GemmPlan(jobs), inv_flat if whole else None)
+                    for live, mean in zip(_live_slots(layer), self._mean_slots(layer)):
+                        jobs.append(ops.Gemm(ones_r[:z.shape[0]], ones_c[:, :live.view.shape[1]], live.view,
+                                             epilogue=ops.EPI_MUL_E_ADD_F, E=z[:, live.cols], F=mean.view))
+                # z and inv_state are shaped alike: one launch scales the noise when inv_state is invert()'s whole arena
+                whole = self._inv_arena is not None and self._inv_arena.is_whole(invs)
+                plan = (key, noise.flat, list(zip(noise.views, invs)), ops.GemmPlan(jobs),
+                        self._inv_arena.flat if whole else None)
                 self._keep_plan(key, plan)
             _, zflat, scale, gemms, inv_flat = plan
             self._randn(zflat.numel(), device=zflat.device, out=zflat)
             if inv_flat is not None:                               # z *= inv_state: one launch over the arena
-                ops.mul(zflat, inv_flat[:zflat.numel()], out=zflat)
+                ops.mul(zflat, inv_flat, out=zflat)
             else:
                 for z, inv in scale:
                     ops.mul(z, inv, out=z)
@@ -721,20 +798,21 @@ class BlockDiagonal(Curvature):
             pos = 0
             for _, layer in owned:
                 inv = self.inv_state[layer]
-                P, n_w = inv.shape[0], layer.weight.numel()
+                P = inv.shape[0]
                 z = flat[pos:pos + P].view(1, P)
                 pos += P
-                w = layer.weight.data
-                if not w.is_contiguous():
-                    raise RuntimeError("BlockDiagonal.sample_and_replace: parameters must be contiguous")
-                jobs.append(ops.Gemm(z, inv[:, :n_w], w.view(1, n_w), epilogue=ops.EPI_ADD_E,
-                                     E=self.model_state_of(layer, 'weight').view(1, n_w)))
-                skip.append(w)
-                if layer.bias is not None:
-                    b = layer.bias.data
-                    jobs.append(ops.Gemm(z, inv[:, n_w:], b.view(1, P - n_w), epilogue=ops.EPI_ADD_E,
-                                         E=self.model_state_of(layer, 'bias').view(1, P - n_w)))
-                    skip.append(b)
+                col = 0
+                for name in ('weight', 'bias'):                       # g's order: the weight, flat, then the bias
+                    if layer._parameters[name] is None:
+                        continue
+                    p = layer._parameters[name].data
+                    if not p.is_contiguous():
+                        raise RuntimeError("BlockDiagonal.sample_and_replace: parameters must be contiguous")
+                    k = p.numel()
+                    jobs.append(ops.Gemm(z, inv[:, col:col + k], p.view(1, k), epilogue=ops.EPI_ADD_E,
+                                         E=self.model_state_of(layer, name).view(1, k)))
+                    skip.append(p)
+                    col += k
         self._reload_mean(skip=skip)
         ops.gemm_batched(jobs)
         self._allgather_sampled()
@@ -1029,13 +1107,12 @@ class KFAC(Curvature):
         assert self.inv_state, "Inverse state dict is empty. Did you call 'invert' prior to this?"
         owned = self._owned()
         ptr = Tensor.data_ptr
-        params = [p for _, l in owned for p in (l._parameters['weight'], l._parameters['bias']) if p is not None]
+        params, param_ptrs, mean_ptrs = self._param_ptrs([l for _, l in owned])
         # The two GEMM launches are described once and replayed while the tensors involved stay where they
         # are (invert() rewrites inv_state in place): per call only the noise is drawn.
         inv_state = self.inv_state
-        means = [self.model_state_of(l, nm) for _, l in owned for nm in ('weight', 'bias') if l._parameters[nm] is not None]
-        key = (noise is None, tuple(map(ptr, [t for _, l in owned for t in inv_state[l]])), tuple(map(ptr, params)),
-               tuple(map(ptr, means)), tuple(map(ptr, noise.values())) if noise is not None else ())
+        key = (noise is None, tuple(map(ptr, [t for _, l in owned for t in inv_state[l]])), param_ptrs, mean_ptrs,
+               tuple(map(ptr, noise.values())) if noise is not None else ())
         plan = self._sample_plans().get(key)
         if plan is None:
             stage1, stage2 = [], []
@@ -1054,39 +1131,21 @@ class KFAC(Curvature):
                 else:
                     z = flat[pos:pos + G * n * m].view(*((G,) if first.dim() == 3 else ()), n, m)
                     pos += G * n * m
-                n0 = n - int(layer.bias is not None)
                 zs = z if G > 1 else [z]
-                if _is_convt(layer):
-                    # Wm's columns land in the (in, out, kh, kw) weight one kernel tap at a time: a strided (out, in)
-                    # view per tap, so the epilogue writes through the permutation (L_A^T's column slices are no longer
-                    # triangular: these products run dense)
-                    la, lg = first, second
-                    tmp = torch.empty(m, n, dtype=torch.float32, device=first.device)
-                    stage1.append(ops.Gemm(lg, z.t(), tmp, tri=ops.TRI_A_LOWER))
-                    la_t = la.t()
-                    for (cols, wv), (_, mv) in zip(_tap_views(layer, layer.weight.data),
-                                                   _tap_views(layer, self.model_state_of(layer, 'weight'))):
-                        stage2.append(ops.Gemm(tmp, la_t[:, :n0][:, cols], wv, epilogue=ops.EPI_ADD_E, E=mv))
-                    if layer.bias is not None:
-                        stage2.append(ops.Gemm(tmp, la_t[:, n0:], layer.bias.data.view(m, 1), epilogue=ops.EPI_ADD_E,
-                                               E=self.model_state_of(layer, 'bias').view(m, 1)))
-                    continue
-                # grouped layer: group g owns weight rows [g m, (g + 1) m) - one pair of products per group
-                ws = layer.weight.data.view(G, m, n0)
-                w_means = self.model_state_of(layer, 'weight').view(G, m, n0)
+                slots = list(zip(_live_slots(layer), self._mean_slots(layer)))
+                # grouped layer: group g owns the rows [g m, (g + 1) m) of every slot - one pair of products per group
                 for g, (la, lg) in enumerate(_pairs(first, second)):
+                    rows = slice(g * m, (g + 1) * m)
                     tmp = torch.empty(m, n, dtype=torch.float32, device=first.device)
                     stage1.append(ops.Gemm(lg, zs[g].t(), tmp, tri=ops.TRI_A_LOWER))
                     la_t = la.t()
-                    stage2.append(ops.Gemm(tmp, la_t[:, :n0], ws[g], epilogue=ops.EPI_ADD_E, E=w_means[g],
-                                           tri=ops.TRI_B_UPPER))
-                    if layer.bias is not None:
-                        b = layer.bias.data.view(G, m, 1)[g]
-                        b_mean = self.model_state_of(layer, 'bias').view(G, m, 1)[g]
-                        stage2.append(ops.Gemm(tmp, la_t[:, n0:], b, epilogue=ops.EPI_ADD_E, E=b_mean))
-            # largest products first: the tail of each launch is then made of the short tiles
-            stage1.sort(key=lambda j: -(j.A.shape[0] * j.A.shape[1] * j.B.shape[1]))
-            stage2.sort(key=lambda j: -(j.A.shape[0] * j.A.shape[1] * j.B.shape[1]))
+                    for live, mean in slots:
+                        # one product per slot, its epilogue writing through the slot's strides.  Only the leading columns
+                        # of L_A^T are still upper triangular: a kernel tap's column slice and the bias column run dense
+                        stage2.append(ops.Gemm(tmp, la_t[:, live.cols], live.view[rows], epilogue=ops.EPI_ADD_E,
+                                               E=mean.view[rows], tri=ops.TRI_B_UPPER if live.lead else ops.TRI_NONE))
+            _largest_first(stage1)
+            _largest_first(stage2)
             plan = (key, flat, ops.GemmPlan(stage1), ops.GemmPlan(stage2))
             self._keep_plan(key, plan)
         if plan[1] is not None:
@@ -1142,34 +1201,22 @@ class KFAC(Curvature):
                 else:
                     zts = list(flat[pos:pos + S * G * n * m].view(G, S * m, n))       # iid: drawn directly as z_s^T
                     pos += S * G * n * m
-                has_bias = layer.bias is not None
-                n0 = n - int(has_bias)
-                convt = _is_convt(layer)
-                # a ConvTranspose2d's bank holds its sets in the weight's own (in, out, kh, kw) layout
-                wb = torch.empty(S, *(layer.weight.shape if convt else (G * m, n0)), dtype=torch.float32, device=dev)
-                bb = torch.empty(S, G * m, dtype=torch.float32, device=dev) if has_bias else None
-                w_mean = self.model_state_of(layer, 'weight').view(G, m, n0) if not convt else None
-                b_mean = self.model_state_of(layer, 'bias').view(G, m, 1) if has_bias else None
+                wb, bb = _bank_buffers(layer, S, dev)
+                sets = [_slots(layer, wb[k], bb[k] if bb is not None else None) for k in range(S)]
+                means = self._mean_slots(layer)
                 for g, ((la, lg), zt) in enumerate(zip(_pairs(first, second), zts)):
+                    rows = slice(g * m, (g + 1) * m)                              # of group g, as in sample_and_replace
                     V = torch.empty(n, S * m, dtype=torch.float32, device=dev)
                     stage_a.append(ops.Gemm(la, zt.t(), V, tri=ops.TRI_A_LOWER))     # V = L_A [z_1 | ... | z_S]
                     for k in range(S):
                         Vs_t = V[:, k * m:(k + 1) * m].t()                        # (m, n) view of V_s^T: K-contiguous columns
-                        if convt:                                                  # one product per kernel tap
-                            for (cols, wv), (_, mv) in zip(_tap_views(layer, wb[k]),
-                                                           _tap_views(layer, self.model_state_of(layer, 'weight'))):
-                                stage_b.append(ops.Gemm(lg, Vs_t[:, :n0][:, cols], wv, epilogue=ops.EPI_ADD_E, E=mv,
-                                                        tri=ops.TRI_A_LOWER))
-                        else:
-                            stage_b.append(ops.Gemm(lg, Vs_t[:, :n0], wb[k].view(G, m, n0)[g], epilogue=ops.EPI_ADD_E,
-                                                    E=w_mean[g], tri=ops.TRI_A_LOWER))
-                        if has_bias:
-                            stage_b.append(ops.Gemm(lg, Vs_t[:, n0:], bb[k].view(G, m, 1)[g], epilogue=ops.EPI_ADD_E,
-                                                    E=b_mean[g], tri=ops.TRI_A_LOWER))
+                        for slot, mean in zip(sets[k], means):
+                            stage_b.append(ops.Gemm(lg, Vs_t[:, slot.cols], slot.view[rows], epilogue=ops.EPI_ADD_E,
+                                                    E=mean.view[rows], tri=ops.TRI_A_LOWER))
                     keep += [zt, V]
                 weights[layer], biases[layer] = wb, bb
-            stage_a.sort(key=lambda j: -(j.A.shape[0] * j.A.shape[1] * j.B.shape[1]))
-            stage_b.sort(key=lambda j: -(j.A.shape[0] * j.A.shape[1] * j.B.shape[1]))
+            _largest_first(stage_a)
+            _largest_first(stage_b)
             plan = (flat, ops.GemmPlan(stage_a), ops.GemmPlan(stage_b), SampleBank(S, weights, biases), keep)
             cache[key] = plan
         if plan[0] is not None:
@@ -1179,27 +1226,6 @@ class KFAC(Curvature):
         return plan[3]
 
 
-class _InProjection:
-    """``in_proj_weight`` / ``in_proj_bias`` of an nn.MultiheadAttention presented as a layer with ``weight`` / ``bias``
-    (a `SampleBank` key; one object per module, so the key is stable)."""
-
-    def __init__(self, mha: Module):
-        self.mha = mha
-
-    @classmethod
-    def of(cls, mha: Module) -> "_InProjection":
-        if "_curv_in_projection" not in mha.__dict__:
-            mha.__dict__["_curv_in_projection"] = cls(mha)
-        return mha.__dict__["_curv_in_projection"]
-
-    weight = property(lambda self: self.mha.in_proj_weight)
-    bias = property(lambda self: self.mha.in_proj_bias)
-
-    @property
-    def _parameters(self):
-        return {'weight': self.mha.in_proj_weight, 'bias': self.mha.in_proj_bias}
-
-
 class SampleBank:
     """`count` sampled parameter sets of an estimator's own layers (`KFAC.sample_many`): ``weights[layer]`` is
     (count, out, in[*kh*kw]) and ``biases[layer]`` (count, out) or None, each entry ``mean + sample``.  The buffers belong
@@ -1207,36 +1233,6 @@ class SampleBank:
 
     def __init__(self, count: int, weights: Dict[Module, Tensor], biases: Dict[Module, Optional[Tensor]]):
         self.count, self.weights, self.biases = count, weights, biases
-
-
-def _arena(shapes: Sequence[Sequence[int]], device, zero: bool = False):
-    """One flat fp32 buffer and one view per shape, laid out back to back: whole-model elementwise steps
-    (noise scaling, scalar-hyper-parameter inverts) then take ONE launch over the flat buffer instead of one
-    per layer."""
-    sizes = []
-    for shape in shapes:
-        count = 1
-        for d in shape:
-            count *= int(d)
-        sizes.append(count)
-    flat = (torch.zeros if zero else torch.empty)(max(sum(sizes), 1), dtype=torch.float32, device=device)
-    views, pos = [], 0
-    for shape, count in zip(shapes, sizes):
-        views.append(flat[pos:pos + count].view(*shape))
-        pos += count
-    return flat, views
-
-
-def _is_arena(flat: Optional[Tensor], tensors: Sequence[Tensor]) -> bool:
-    """True if `tensors` are exactly the consecutive contiguous views `_arena` handed out for `flat`."""
-    if flat is None:
-        return False
-    pos = flat.data_ptr()
-    for t in tensors:
-        if not t.is_contiguous() or t.dtype != torch.float32 or t.data_ptr() != pos:
-            return False
-        pos += 4 * t.numel()
-    return pos <= flat.data_ptr() + 4 * flat.numel()
 
 
 class EFB(Curvature):
@@ -1283,9 +1279,9 @@ class EFB(Curvature):
         missing = [k for k, layer in enumerate(layers) if layer not in self.state]
         if missing:
             # Lambda of all (new) layers in one zeroed arena: every update is then the same accumulate launch pair
-            self._state_flat, views = _arena([(grads[k][0].shape[0], grads[k][0].numel() // grads[k][0].shape[0] +
-                                               int(grads[k][1] is not None)) for k in missing], dev, zero=True)
-            for k, v in zip(missing, views):
+            self._state_arena = _Arena([(grads[k][0].shape[0], grads[k][0].numel() // grads[k][0].shape[0] +
+                                         int(grads[k][1] is not None)) for k in missing], dev, zero=True)
+            for k, v in zip(missing, self._state_arena.views):
                 self.state[layers[k]] = v
         # The launch plan is keyed by what it writes and by the eigenvectors only.  The gradients are staged into an arena the
         # plan owns with one batched copy per call: after zero_grad(set_to_none=True) every backward pass allocates new
@@ -1295,14 +1291,14 @@ class EFB(Curvature):
         plan = getattr(self, "_update_plan", None)
         if plan is None or plan[0] != key:
             stage1, stage2, staged = [], [], []
-            _, tmps = _arena([tuple(self.state[l].shape) for l in layers], dev)
+            tmps = _Arena([tuple(self.state[l].shape) for l in layers], dev).views
             shapes = []
             for layer, (gw, gb) in zip(layers, grads):
                 m = gw.shape[0]
                 shapes.append((m, gw.numel() // m))
                 if gb is not None:
                     shapes.append((m, 1))
-            _, views = _arena(shapes, dev)
+            views = _Arena(shapes, dev).views
             vi = 0
             for layer, (gw, gb), tmp in zip(layers, grads, tmps):
                 n0 = gw.numel() // gw.shape[0]
@@ -1358,17 +1354,17 @@ class EFB(Curvature):
         values = [self.state[l] for l in layers]
         prev = [self.inv_state.get(l) for l in layers]
         if not (all(p is not None and p.shape == v.shape for p, v in zip(prev, values))
-                and _is_arena(getattr(self, "_inv_flat", None), prev)):
+                and self._inv_arena is not None and self._inv_arena.is_whole(prev)):
             # inverse state of all layers in one arena, overwritten in place by later calls (stable addresses
             # keep the sampler's launch plan valid; the noise scaling is one launch over the flat buffer)
-            self._inv_flat, views = _arena([tuple(v.shape) for v in values], values[0].device)
-            for layer, v in zip(layers, views):
+            self._inv_arena = _Arena([tuple(v.shape) for v in values], values[0].device)
+            for layer, v in zip(layers, self._inv_arena.views):
                 self.inv_state[layer] = v
-        state_flat = getattr(self, "_state_flat", None)
-        if _is_scalar(add) and _is_scalar(multiply) and _is_arena(state_flat, values) and \
-                sum(v.numel() for v in values) == self._inv_flat.numel() == state_flat.numel():
-            # one pair of hyper-parameters for every layer and both dicts are whole arenas: one launch
-            ops.rsqrt_affine(state_flat, float(add), float(multiply), out=self._inv_flat)
+        states = self._state_arena
+        if _is_scalar(add) and _is_scalar(multiply) and states is not None and states.is_whole(values):
+            # one pair of hyper-parameters for every layer and both dicts are whole arenas (inv_state is one, shaped like
+            # `values`, after the block above): one launch
+            ops.rsqrt_affine(states.flat, float(add), float(multiply), out=self._inv_arena.flat)
             return
         for position, (layer, value) in enumerate(zip(layers, values)):
             n, s = self._hyper(add, multiply, gindex.get(layer, position), max(len(gindex), len(layers)))
@@ -1396,20 +1392,20 @@ class EFB(Curvature):
         are described once and replayed while the tensors involved stay where they are."""
         assert self.inv_state, "Inverse state dict is empty. Did you call 'invert' prior to this?"
         layers = self._mine()
-        self._reload_mean(skip=[p for l in layers for p in (l.weight, l.bias) if p is not None])
+        params, param_ptrs, mean_ptrs = self._param_ptrs(layers)
+        self._reload_mean(skip=params)
         if not layers:
             self._allgather_sampled()
             return
-        key = (noise is None, tuple(t.data_ptr() for l in layers for t in (*self.eigvecs[l], self.inv_state[l])),
-               tuple(p.data_ptr() for l in layers for p in (l.weight, l.bias) if p is not None),
-               tuple(self.model_state_of(l, nm).data_ptr() for l in layers for nm in ('weight', 'bias')
-                     if getattr(l, nm) is not None))
+        key = (noise is None, tuple(map(Tensor.data_ptr, [t for l in layers for t in (*self.eigvecs[l], self.inv_state[l])])),
+               param_ptrs, mean_ptrs)
         plan = self._sample_plans().get(key)
         if plan is None:
-            dev = self.inv_state[layers[0]].device
-            shapes = [tuple(self.inv_state[l].shape) for l in layers]               # (m, n)
-            zflat, zts = _arena(shapes, dev)
-            _, tmps = _arena(shapes, dev)
+            invs = [self.inv_state[l] for l in layers]
+            shapes = [tuple(inv.shape) for inv in invs]                             # (m, n)
+            zs = _Arena(shapes, invs[0].device)
+            zflat, zts = zs.flat, zs.views
+            tmps = _Arena(shapes, invs[0].device).views
             stage1, stage2 = [], []
             for layer, zt, tmp in zip(layers, zts, tmps):
                 first, second = self.eigvecs[layer]
@@ -1418,28 +1414,21 @@ class EFB(Curvature):
                 # contiguous along the summation index - the form the LDS-DMA GEMM kernel takes), no transposed copies
                 pt = tmp.view(-1).view(n, m)
                 stage1.append(ops.Gemm(first, zt.t(), pt))
-                n0 = n - int(layer.bias is not None)
                 p = pt.t()                                                          # (m, n) view of P
-                for (cols, w), (_, w_mean) in zip(_tap_views(layer, layer.weight.data),
-                                                  _tap_views(layer, self.model_state_of(layer, 'weight'))):
-                    stage2.append(ops.Gemm(second, p[:, :n0][:, cols], w, epilogue=ops.EPI_ADD_E, E=w_mean))
-                if layer.bias is not None:
-                    b = layer.bias.data.view(m, 1)
-                    b_mean = self.model_state_of(layer, 'bias').view(m, 1)
-                    stage2.append(ops.Gemm(second, p[:, n0:], b, epilogue=ops.EPI_ADD_E, E=b_mean))
-            stage1.sort(key=lambda j: -(j.A.shape[0] * j.A.shape[1] * j.B.shape[1]))
-            stage2.sort(key=lambda j: -(j.A.shape[0] * j.A.shape[1] * j.B.shape[1]))
-            inv_flat = getattr(self, "_inv_flat", None)
-            whole = _is_arena(inv_flat, [self.inv_state[l] for l in layers]) and \
-                sum(self.inv_state[l].numel() for l in layers) == zflat.numel()
-            plan = (key, zflat, zts, ops.GemmPlan(stage1), ops.GemmPlan(stage2), inv_flat if whole else None)
+                for live, mean in zip(_live_slots(layer), self._mean_slots(layer)):
+                    stage2.append(ops.Gemm(second, p[:, live.cols], live.view, epilogue=ops.EPI_ADD_E, E=mean.view))
+            _largest_first(stage1)
+            _largest_first(stage2)
+            # zt and inv_state are shaped alike: one launch scales the noise when inv_state is invert()'s whole arena
+            whole = self._inv_arena is not None and self._inv_arena.is_whole(invs)
+            plan = (key, zflat, zts, ops.GemmPlan(stage1), ops.GemmPlan(stage2), self._inv_arena.flat if whole else None)
             self._keep_plan(key, plan)
         _, zflat, zts, plan1, plan2, inv_flat = plan
         if noise is None:
             # z^T of the reference drawn directly in (m, n) layout: the transpose of iid noise is iid noise
             self._randn(zflat.numel(), device=zflat.device, out=zflat)
             if inv_flat is not None:
-                ops.mul(zflat, inv_flat[:zflat.numel()], out=zflat)                 # one launch for the model
+                ops.mul(zflat, inv_flat, out=zflat)                                 # one launch for the model
             else:
                 for layer, zt in zip(layers, zts):
                     ops.mul(zt, self.inv_state[layer], out=zt)
@@ -1502,8 +1491,12 @@ class INF(Curvature):
             n, m = self.eigvecs[layer][0].shape[0], self.eigvecs[layer][1].shape[0]
             a, b = (picked[layer][0].numel(), picked[layer][1].numel()) if layer in picked else (n, m)
             shapes.append((n, m, a, b))
-        self._corr_flat, corrs = _arena([(n, m) for n, m, _, _ in shapes], dev) if layers else (None, [])
-        self._lam_flat, lams = _arena([(a * b,) for _, _, a, b in shapes], dev) if layers else (None, [])
+        self._corr_arena = self._lam_arena = None
+        corrs = lams = ()
+        if layers:
+            self._corr_arena = _Arena([(n, m) for n, m, _, _ in shapes], dev)
+            self._lam_arena = _Arena([(a * b,) for _, _, a, b in shapes], dev)
+            corrs, lams = self._corr_arena.views, self._lam_arena.views
         for layer, corr, lam in zip(layers, corrs, lams):
             xxt_eigvecs, ggt_eigvecs = self.eigvecs[layer]
             n, m = xxt_eigvecs.shape[0], ggt_eigvecs.shape[0]
@@ -1537,22 +1530,23 @@ class INF(Curvature):
         gindex = self._global_index()
         # r of all layers in one arena, overwritten in place by later calls (stable addresses for the sampler's plan)
         rs = [self.inv_state[l][2] for l in layers] if len(self.inv_state) == len(layers) else []
-        if not rs or not _is_arena(getattr(self, "_r_flat", None), rs) or \
+        if self._r_arena is None or not self._r_arena.is_whole(rs) or \
                 any(r.numel() != self.state[l][3].numel() for r, l in zip(rs, layers)):
-            self._r_flat, rs = _arena([(self.state[l][3].numel(),) for l in layers], self.state[layers[0]][3].device)
+            self._r_arena = _Arena([(self.state[l][3].numel(),) for l in layers], self.state[layers[0]][3].device)
+            rs = self._r_arena.views
         hypers = [self._hyper(add, multiply, gindex.get(layer, position), max(len(gindex), len(layers)))
                   for position, layer in enumerate(layers)]
+        corrs, lams = self._corr_arena, self._lam_arena
+        # (the r of the layers are a whole arena, each as long as its layer's D, after the block above: as long as `corrs`)
         one_pair = len(set(hypers)) == 1 and \
-            _is_arena(getattr(self, "_corr_flat", None), [self.state[l][3] for l in layers]) and \
-            _is_arena(getattr(self, "_lam_flat", None), [self.state[l][2] for l in layers]) and \
-            self._corr_flat.numel() == self._r_flat.numel() == sum(self.state[l][3].numel() for l in layers) and \
-            self._lam_flat.numel() == sum(self.state[l][2].numel() for l in layers)
+            corrs is not None and corrs.is_whole([self.state[l][3] for l in layers]) and \
+            lams is not None and lams.is_whole([self.state[l][2] for l in layers])
         if one_pair:
             # the three elementwise steps of :521-530 over the arenas of update(): three launches for the whole model
             n, s = hypers[0]
-            ops.clamp_min0_(self._corr_flat)                             # in place on `state`, like :523
-            reg_flat = ops.sqrt_scale(self._lam_flat, s)
-            ops.rsqrt_affine(self._corr_flat, n, s, out=self._r_flat)
+            ops.clamp_min0_(corrs.flat)                                  # in place on `state`, like :523
+            reg_flat = ops.sqrt_scale(lams.flat, s)
+            ops.rsqrt_affine(corrs.flat, n, s, out=self._r_arena.flat)
             pos = 0
             for layer, r in zip(layers, rs):
                 lr_frst_eigvecs, lr_scnd_eigvecs, lr_lambda, _ = self.state[layer]
@@ -1605,13 +1599,9 @@ class INF(Curvature):
         # (measured on ResNet-50's stem: 1.7e-3; with fp64: at the level of the fp32 inputs)
         first, parts = [], []
         # r**2 in fp64: one launch for the model when the r of its layers lie back to back (invert()'s arena)
-        rs = [reg[3] for reg in regs]
-        r2_flat = None
-        if len(rs) > 1 and all(t.is_contiguous() and t.dtype == torch.float32 for t in rs) and \
-                all(rs[k + 1].data_ptr() == rs[k].data_ptr() + 4 * rs[k].numel() for k in range(len(rs) - 1)):
-            total = sum(t.numel() for t in rs)
-            if rs[0].untyped_storage().nbytes() >= 4 * (rs[0].storage_offset() + total):      # ... inside ONE allocation
-                r2_flat = ops.square_f64(torch.as_strided(rs[0].reshape(-1), (total,), (1,)))
+        # (bare tensors here, no arena to ask: the tensor-level check `_Arena.is_whole` is built on)
+        r_run = _run_of([reg[3] for reg in regs]) if len(regs) > 1 else None
+        r2_flat = ops.square_f64(r_run) if r_run is not None else None
         pos = 0
         for ua, ug, sigma, r in regs:
             (n, a), (m, b) = ua.shape, ug.shape
@@ -1698,19 +1688,19 @@ class INF(Curvature):
         if not layers:
             self._allgather_sampled()
             return
-        key = (tuple(t.data_ptr() for l in layers for t in self.inv_state[l]),
-               tuple(p.data_ptr() for l in layers for p in (l.weight, l.bias) if p is not None))
+        # (no mean addresses: the last product accumulates onto the parameters, which _reload_mean has just reset)
+        key = (tuple(map(Tensor.data_ptr, [t for l in layers for t in self.inv_state[l]])), self._param_ptrs(layers, means=False)[1])
         plan = self._sample_plans().get(key)
         if plan is None:
             dev = self.inv_state[layers[0]][0].device
             dims = [(self.inv_state[l][0].shape, self.inv_state[l][1].shape) for l in layers]
-            xflat, Xs = _arena([(n * m,) for (n, _), (m, _) in dims], dev)
-            yflat, Ys = _arena([(n * m,) for (n, _), (m, _) in dims], dev)
-            r2flat, r2s = _arena([(n, m) for (n, _), (m, _) in dims], dev)
+            vecs = [(n * m,) for (n, _), (m, _) in dims]
+            xs, ys, r2 = _Arena(vecs, dev), _Arena(vecs, dev), _Arena([(n, m) for (n, _), (m, _) in dims], dev)
+            xflat, Xs, yflat, Ys, r2flat, r2s = xs.flat, xs.views, ys.flat, ys.views, r2.flat, r2.views
             small = []
             for (n, a), (m, b) in dims:
                 small += [(b, n), (a, b), (a * b, 1), (m, a)]
-            _, sm = _arena(small, dev)
+            sm = _Arena(small, dev).views
             stages = [[], [], [], [], []]
             for k, (layer, ((n, a), (m, b)), Y_l, r2) in enumerate(zip(layers, dims, Ys, r2s)):
                 ua, ug, r, P = self.inv_state[layer]
@@ -1721,18 +1711,19 @@ class INF(Curvature):
                 stages[3].append(ops.Gemm(ug, qx.view(b, a), t2))                    # U_G unvec(Qx): (m, a)
                 # (Y_l - r^2 * (U_A t2^T)) as an (n, m) matrix is the transposed sample: rows < n0 go to the
                 # weight seen through transposed strides, the last row to the bias (curvatures.py:67-82, 536)
-                n0 = n - int(layer.bias is not None)
                 Yv = Y_l.view(n, m)
-                for rows, w in _tap_views(layer, layer.weight.data):             # (ConvTranspose2d: one per tap)
-                    stages[4].append(ops.Gemm(ua[:n0][rows], t2.t(), w.t(), alpha=-1.0, beta=1.0,
-                                              epilogue=ops.EPI_MUL_E_ADD_F, E=r2[:n0][rows], F=Yv[:n0][rows]))
-                if layer.bias is not None:
-                    stages[4].append(ops.Gemm(ua[n0:], t2.t(), layer.bias.data.view(1, m), alpha=-1.0, beta=1.0,
-                                              epilogue=ops.EPI_MUL_E_ADD_F, E=r2[n0:], F=Yv[n0:]))
-            r_whole = _is_arena(getattr(self, "_r_flat", None), [self.inv_state[l][2] for l in layers]) and \
-                sum(self.inv_state[l][2].numel() for l in layers) == xflat.numel()
+                for slot in _live_slots(layer):
+                    # the slot's columns of Wm are rows here; a single column (the bias) is written as the plain row it is,
+                    # strides (m, 1) rather than the (1, 1) of the transposed (m, 1) view
+                    dst = slot.view.t()
+                    if dst.shape[0] == 1:
+                        dst = dst.reshape(1, m)
+                    stages[4].append(ops.Gemm(ua[slot.cols], t2.t(), dst, alpha=-1.0, beta=1.0,
+                                              epilogue=ops.EPI_MUL_E_ADD_F, E=r2[slot.cols], F=Yv[slot.cols]))
+            # X, Y_l and r are as long as each other: one launch each over the model when r is invert()'s whole arena
+            r_whole = self._r_arena is not None and self._r_arena.is_whole([self.inv_state[l][2] for l in layers])
             plan = (key, xflat, Xs, yflat, Ys, r2flat, r2s, [ops.GemmPlan(st) for st in stages],
-                    self._r_flat if r_whole else None, [None])         # (last: the inversion whose r**2 `r2flat` holds)
+                    self._r_arena.flat if r_whole else None, [None])   # (last: the inversion whose r**2 `r2flat` holds)
             self._keep_plan(key, plan)
         _, xflat, Xs, yflat, Ys, r2flat, r2s, gemms, r_flat, r2_of = plan
         if noise is None:
@@ -1740,10 +1731,9 @@ class INF(Curvature):
         else:
             ops.CopyPlan(Xs, [noise[l].reshape(-1).contiguous() for l in layers]).run()
         if r_flat is not None:                                  # Y_l = r * X and r^2 for the whole model
-            rf = r_flat[:xflat.numel()]
-            ops.mul(rf, xflat, out=yflat)
+            ops.mul(r_flat, xflat, out=yflat)
             if r2_of[0] != getattr(self, "_r_version", 0):       # r changes with invert() only: r^2 once per inversion
-                ops.mul(rf, rf, out=r2flat)
+                ops.mul(r_flat, r_flat, out=r2flat)
                 r2_of[0] = getattr(self, "_r_version", 0)
         else:
             for layer, X, Y_l, r2 in zip(layers, Xs, Ys, r2s):
