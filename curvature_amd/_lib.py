@@ -13,7 +13,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc")
 INCLUDE = os.path.normpath(os.path.join(_HERE, "..", "include"))
 LIB_PATH = os.path.join(CSRC, "libcurv_hip.so")
-SOURCES = ["api.cpp", "collective.cpp", "elementwise.hip", "syrk.hip", "syrk_flat.hip", "syrk_corr.hip", "syrk_pre.hip", "syrk_small.hip", "group_factor.hip", "kfac_half.hip", "convt_factor.hip", "invert.hip", "gemm.hip", "inf.hip", "eigh.hip", "eigh_lowrank.hip"]
+SOURCES = ["api.cpp", "collective.cpp", "elementwise.hip", "syrk.hip", "syrk_flat.hip", "syrk_corr.hip", "syrk_pre.hip", "syrk_small.hip", "group_factor.hip", "kfac_half.hip", "convt_factor.hip", "persample.hip", "invert.hip", "gemm.hip", "inf.hip", "eigh.hip", "eigh_lowrank.hip"]
 HIPCC_FLAGS = ["-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC", "-shared", "-Wall",
                "-Wno-unused-function", "-ldl"]
 
@@ -191,6 +191,21 @@ class curv_sq_desc(ctypes.Structure):
                 ("reserved", ctypes.c_int32)]
 
 
+class curv_persample_desc(ctypes.Structure):
+    """Mirror of ``curv_persample_desc`` in include/curv_hip.h."""
+    _fields_ = [("A", ctypes.c_void_p), ("B", ctypes.c_void_p), ("C", ctypes.c_void_p)] + \
+               [(k, ctypes.c_longlong) for k in ("a_ns", "a_rs", "b_ns", "b_rs", "c_rs")] + \
+               [("S", ctypes.c_int32), ("M", ctypes.c_int32), ("Nc", ctypes.c_int32), ("L", ctypes.c_int32),
+                ("first", ctypes.c_int32), ("alpha", ctypes.c_float)]
+
+
+class curv_persample_pack_desc(ctypes.Structure):
+    """Mirror of ``curv_persample_pack_desc`` in include/curv_hip.h."""
+    _fields_ = [("src", ctypes.c_void_p), ("dst", ctypes.c_void_p)] + \
+               [(k, ctypes.c_int32) for k in ("N", "C", "H", "W", "kh", "kw", "sh", "sw", "ph", "pw", "has_bias",
+                                              "channels_last", "rows_outer", "Lp")]
+
+
 class curv_copy_desc(ctypes.Structure):
     _fields_ = [("dst", ctypes.c_void_p), ("src", ctypes.c_void_p), ("bytes", ctypes.c_ulonglong)]
 
@@ -268,6 +283,10 @@ SIGNATURES = {
     "curv_rsqrt_affine": (_i, [_vp, _vp, _d, _d, _vp, _ll]),
     "curv_sq_accumulate": (_i, [_vp, _vp, _vp, _i, _i, _d, _vp, _i]),
     "curv_sq_accumulate_batched": (_i, [_vp, ctypes.POINTER(curv_sq_desc), _i, _d]),
+    "curv_persample_workspace_bytes": (_sz, [ctypes.POINTER(curv_persample_desc), _i]),
+    "curv_persample_plan_flops": (_i, [ctypes.POINTER(curv_persample_desc), _i, ctypes.POINTER(ctypes.c_longlong)]),
+    "curv_persample_sq_accumulate": (_i, [_vp, ctypes.POINTER(curv_persample_desc), _i, _vp, _sz]),
+    "curv_persample_pack": (_i, [_vp, ctypes.POINTER(curv_persample_pack_desc), _i]),
     "curv_clamp_min0": (_i, [_vp, _vp, _ll]),
     "curv_sqrt_scale": (_i, [_vp, _vp, _d, _vp, _ll]),
     "curv_mul": (_i, [_vp, _vp, _vp, _vp, _ll]),

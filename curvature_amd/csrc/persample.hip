@@ -1,0 +1,534 @@
+// Exact per-sample Fisher products (curv_persample_sq_accumulate / curv_persample_pack, include/curv_hip.h):
+//   C[i][j] (+)= alpha * sum_{n < S} ( sum_{l < L} A[n a_ns + i a_rs + l] * B[n b_ns + j b_rs + l] )**2
+// For a layer with grad_output g_n (m x L) and unfolded input X_n (n_in x L) the inner sum is P_n = g_n X_n^T, the
+// sample's share of [W.grad | b.grad]; the sum of its squares is the Fisher diagonal (Diagonal) and, on operands rotated
+// into the Kronecker eigenbasis, EFB's eigenvalue correction.  P_n is never written: a 128 x 128 tile of it lives in the
+// MFMA accumulators for the length of one sample, is squared and added into a second accumulator set at the sample's end
+// and starts the next sample from zero.
+//
+// Three launches per batch of up to 16 products:
+//   1. (curv_persample_pack, a call of its own) X of a layer into caller scratch wherever the source cannot be read in
+//      place: the unfold of a convolution input (rows (c, kh, kw)), the transpose of a Linear input (N, T, D), or a plain
+//      copy; plus the ones row of a biased layer; every row padded with zeros to Lp columns by the pack itself.
+//   2. product: one workgroup per item = (product, 128 x 128 output tile, range of samples); 2 x 2 waves of 64 x 64, each
+//      2 x 2 v_mfma_f32_32x32x2_f32 blocks.  Staging is the NT GEMM's (gemm_nt.h): both 128-row panels of a stage of 32 l
+//      values arrive by LDS-DMA into a double-buffered, XOR-swizzled image and come back with ds_read_b128.  The stages of
+//      all samples of the item form ONE sequence (the prefetch runs across sample boundaries); the last stage of a sample
+//      whose L is no multiple of 32 zeroes the l values at or behind L in the operand registers, so what lies behind a row
+//      in memory (the next row, the next sample, NaN) never enters a product.  64 + 64 accumulators per lane, two
+//      workgroups per CU (registers and 64 KiB of LDS each).  A product whose smaller side has at most 64 rows runs on
+//      64 x 128 tiles with that side as the A panel (2 x 1 blocks per wave, the transposed tile when the side is Nc):
+//      half the MFMAs of a half-empty 128 x 128 tile.  Each item writes its fp32 slab.
+//   3. reduce: one thread per entry of C sums the slabs of its tile in slice order, scales, writes or adds.
+// The split of a product into sample ranges follows from its own sizes only, every item and reduce thread reads only its
+// own product's operands and slabs, and all sums run in a fixed order without atomics: a product's bits are the same
+// alone, in a whole-model call and on a sharded rank.  No host synchronisation, no device allocation; tables travel as
+// kernel arguments.
+#include "common.h"
+
+#include <algorithm>
+#include <vector>
+
+namespace curv {
+namespace {
+
+constexpr int PS_THREADS = 256;
+constexpr int PS_TM = 128;                     // tile rows / columns
+constexpr int PS_KC = 32;                      // l values per stage
+constexpr int PS_ROW_B = PS_KC * 4;            // 128 B per image row
+constexpr int PS_SLOTS = PS_KC / 4;            // 16-byte slots per row
+constexpr int PS_STEPS = PS_KC / 8;            // groups of 4 MFMA k-steps per lane half
+constexpr int PS_RPP = 1024 / PS_ROW_B;        // rows per 1 KiB wave-instruction
+constexpr int PS_PIECES = PS_TM / PS_RPP / 4;  // DMA pieces per wave and panel
+constexpr int PS_PANEL_B = PS_TM * PS_ROW_B;   // 16 KiB per panel per buffer
+constexpr int PS_NP = 2 * PS_PIECES;
+constexpr int PS_PPS = (PS_NP + PS_STEPS / 2 - 1) / (PS_STEPS / 2);
+static_assert(PS_PPS <= 4, "at most one DMA piece per MFMA group");
+constexpr int PS_BATCH = 16;                   // products per launch (tables as kernel arguments)
+constexpr int PS_ITEMS_TARGET = 512;           // a product is cut into sample ranges until it has about this many items ...
+constexpr int PS_STAGES_MIN = 64;              // ... of at least 64 stages
+constexpr long long PS_BYTES_MAX = 1LL << 31;  // operand extents: 32-bit buffer offsets
+
+typedef __attribute__((address_space(1))) float gfl;
+typedef __attribute__((address_space(3))) void lds_void;
+typedef __attribute__((address_space(3))) char lds_char;
+
+struct PsProduct {
+  const float* A;
+  const float* B;
+  float* C;
+  float* slabs;
+  long long a_ns, a_rs, b_ns, b_rs, c_rs;
+  int S, M, Nc, L;             // as the product kernel sees them: A and B have changed places when `swap`
+  int tiles_n, tiles;          // output tiles: tiles = tiles_m tiles_n
+  int spi, slices;             // samples per item, sample ranges
+  int half, swap;              // 64 x 128 tiles (M <= 64); the kernel computes the transposed tile (C is Nc x M)
+  int first;
+  float alpha;
+  unsigned a_bytes, b_bytes;
+  long long base;              // first item / reduce block of this product in the launch
+};
+
+struct PsBatch {
+  PsProduct p[PS_BATCH];
+  int count;
+};
+
+struct Plan {
+  int tiles_m, tiles_n, tiles, sps, spi, slices, half, swap;
+  long long a_bytes, b_bytes;
+  size_t slab_bytes;
+  long long flops;
+};
+
+bool plan_of(const curv_persample_desc& d, int index, Plan* p) {
+  if (d.S < 1 || d.M < 1 || d.Nc < 1 || d.L < 1) {
+    set_error("curv_persample: item %d: invalid sizes (S %d M %d Nc %d L %d)", index, d.S, d.M, d.Nc, d.L);
+    return false;
+  }
+  if ((d.M > 1 && d.a_rs < d.L) || (d.Nc > 1 && d.b_rs < d.L) || d.a_rs < 0 || d.b_rs < 0 || d.a_ns < 0 || d.b_ns < 0 ||
+      d.c_rs < d.Nc) {
+    set_error("curv_persample: item %d: invalid strides (a_rs %lld b_rs %lld below L %d, or c_rs %lld below Nc %d, or "
+              "negative)", index, d.a_rs, d.b_rs, d.L, d.c_rs, d.Nc);
+    return false;
+  }
+  p->a_bytes = ((long long)(d.S - 1) * d.a_ns + (long long)(d.M - 1) * d.a_rs + d.L) * 4;
+  p->b_bytes = ((long long)(d.S - 1) * d.b_ns + (long long)(d.Nc - 1) * d.b_rs + d.L) * 4;
+  // voffset + soffset of the LDS-DMA reach at most 16 stages' worth behind the operand's end
+  if (p->a_bytes >= PS_BYTES_MAX - 4096 || p->b_bytes >= PS_BYTES_MAX - 4096) {
+    set_error("curv_persample: item %d: operand too large for 32-bit offsets (%lld / %lld bytes, below %lld)", index,
+              p->a_bytes, p->b_bytes, PS_BYTES_MAX - 4096);
+    return false;
+  }
+  // a side of at most 64 rows takes 64 x 128 tiles, as the A side of the kernel (the transposed tile when it is Nc)
+  p->half = std::min(d.M, d.Nc) <= PS_TM / 2;
+  p->swap = p->half && d.M > PS_TM / 2;
+  p->tiles_m = p->half ? 1 : cdiv(d.M, PS_TM);
+  p->tiles_n = cdiv(p->swap ? d.M : d.Nc, PS_TM);
+  const long long tiles = (long long)p->tiles_m * p->tiles_n;
+  if (tiles > (1 << 24)) {
+    set_error("curv_persample: item %d: too many output tiles (%lld)", index, tiles);
+    return false;
+  }
+  p->tiles = (int)tiles;
+  p->sps = cdiv(d.L, PS_KC);
+  // the split follows from the product's own sizes only
+  const int want = std::max(1, cdiv(PS_ITEMS_TARGET, p->tiles));
+  const int spi_min = cdiv(PS_STAGES_MIN, p->sps);
+  p->spi = std::min(d.S, std::max(cdiv(d.S, want), spi_min));
+  p->slices = cdiv(d.S, p->spi);
+  const int tile_rows = p->half ? PS_TM / 2 : PS_TM;
+  p->slab_bytes = align_up((size_t)p->slices * p->tiles * tile_rows * PS_TM * sizeof(float), 256);
+  p->flops = 2LL * p->tiles * tile_rows * PS_TM * (long long)d.S * p->sps * PS_KC;
+  return true;
+}
+
+__device__ inline int find_product(const PsBatch& b, long long at) {
+  int f = 0;
+  for (int i = 1; i < b.count; ++i)
+    if (at >= b.p[i].base) f = i;
+  return f;
+}
+
+// Product: one workgroup per item = (tile * slices + slice) of one product.  Full tiles (128 x 128): wave (wm, wn) computes
+// rows 64 wm .. + 64 of the A panel against rows 64 wn .. + 64 of the B panel, 2 x 2 MFMA blocks.  Half tiles (64 x 128, a
+// product whose A side has at most 64 rows): every wave takes all 64 A rows against B rows 32 wave .. + 32, 2 x 1 blocks -
+// half the MFMAs per stage instead of a half-empty tile.  C/D map of a 32x32 block: column = lane & 31, row = (reg & 3) +
+// 8 (reg >> 2) + 4 (lane >> 5).
+template <bool HALF>
+__device__ __forceinline__ void ps_product_tile(const PsProduct& d, int local, lds_char* lds) {
+  constexpr int BN = HALF ? 1 : 2;                         // MFMA blocks per wave along the B side
+  constexpr int TA = HALF ? PS_TM / 2 : PS_TM;             // A rows per tile
+  constexpr int PA = TA / PS_RPP / 4;                      // DMA pieces per wave: A panel, then the B panel's
+  constexpr int NP = PA + PS_PIECES;
+  const int slice = local % d.slices, tile = local / d.slices;
+  const int tm = tile / d.tiles_n, tn = tile - tm * d.tiles_n;
+  const int i0 = tm * TA, j0 = tn * PS_TM, M = d.M, N = d.Nc, L = d.L;
+  const int s0 = slice * d.spi, s1 = min(s0 + d.spi, d.S);
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int r32 = lane & 31, h = lane >> 5;
+  const int row_a = HALF ? 0 : 64 * (wave >> 1), row_b = HALF ? 32 * wave : 64 * (wave & 1);
+  const int sps = (L + PS_KC - 1) / PS_KC;
+  const int n_stages = (s1 - s0) * sps;
+
+  // DMA lane geometry (gemm_nt.h): piece `slot` of this wave covers panel rows 32 slot + 8 wave + (lane >> 3); the lane's
+  // 16-byte group is XOR-swizzled by (row >> 1) & 7 on the source side
+  const int rsub = PS_RPP * wave + (lane >> 3);
+  const int g_lane = (lane & (PS_SLOTS - 1)) ^ ((rsub >> 1) & (PS_SLOTS - 1));
+  int voff_a[PA], voff_b[PS_PIECES];
+  // rows beyond the matrix are clamped to its last row (their results are never stored)
+#pragma unroll
+  for (int p = 0; p < PA; ++p)
+    voff_a[p] = (int)(((long long)min(i0 + 4 * PS_RPP * p + rsub, M - 1) * d.a_rs + 4 * g_lane) * 4);
+#pragma unroll
+  for (int p = 0; p < PS_PIECES; ++p)
+    voff_b[p] = (int)(((long long)min(j0 + 4 * PS_RPP * p + rsub, N - 1) * d.b_rs + 4 * g_lane) * 4);
+  const __amdgpu_buffer_rsrc_t rsa = __builtin_amdgcn_make_buffer_rsrc((void*)d.A, 0, d.a_bytes, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rsb = __builtin_amdgcn_make_buffer_rsrc((void*)d.B, 0, d.b_bytes, 0x00020000);
+
+  unsigned addr_a[2][PS_STEPS], addr_b[BN][PS_STEPS];
+#pragma unroll
+  for (int o = 0; o < 2 + BN; ++o) {
+    const int R = (o < 2 ? row_a : row_b) + (o & 1) * 32 + r32;
+    const unsigned pbase = (o < 2) ? 0u : 2u * PS_PANEL_B;
+    const int rkey = (R >> 1) & (PS_SLOTS - 1);
+#pragma unroll
+    for (int j = 0; j < PS_STEPS; ++j) {
+      const unsigned at = pbase + R * PS_ROW_B + (((2 * j + h) ^ rkey) << 4);
+      if (o < 2) addr_a[o][j] = at;
+      else addr_b[o - 2][j] = at;
+    }
+  }
+  f32x16 c[2][BN], q[2][BN];       // P_n of the running sample; the sum of P_n**2 over the finished samples
+#pragma unroll
+  for (int m = 0; m < 2; ++m)
+#pragma unroll
+    for (int nb = 0; nb < BN; ++nb) { c[m][nb] = 0.0f; q[m][nb] = 0.0f; }
+
+  // A lane whose 16-byte group lies at or behind L - or any lane behind the item's last stage - carries an out-of-range
+  // voffset (the descriptor's range check drops the fetch)
+  constexpr int OOB = (int)0x80000000;
+  auto issue = [&](int i, bool live, unsigned soff_a, unsigned soff_b, unsigned nbuf) {
+    const bool b_side = i >= PA;
+    const int slot = b_side ? i - PA : i;
+    const unsigned lbase = (b_side ? 2u * PS_PANEL_B : 0u) + nbuf + (unsigned)(PS_RPP * wave + 4 * PS_RPP * slot) * PS_ROW_B;
+    if (!b_side)
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(rsa, (lds_void*)(lds + lbase), 16, live ? voff_a[slot] : OOB, soff_a, 0, 0);
+    else
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(rsb, (lds_void*)(lds + lbase), 16, live ? voff_b[slot] : OOB, soff_b, 0, 0);
+  };
+  int n = s0, kk = 0;                                       // sample and first l of the running stage
+  if (n_stages > 0) {
+    const bool live = 4 * g_lane < L;
+    const unsigned sa = (unsigned)((long long)n * d.a_ns * 4), sb = (unsigned)((long long)n * d.b_ns * 4);
+#pragma unroll
+    for (int i = 0; i < NP; ++i) issue(i, live, sa, sb, 0u);
+  }
+  for (int t = 0; t < n_stages; ++t) {
+    __builtin_amdgcn_s_waitcnt(0x0f70);        // vmcnt(0): this wave's DMA of stage t has landed
+    __syncthreads();
+    int kn = kk + PS_KC, nn = n;
+    const bool sample_ends = kn >= L;
+    if (sample_ends) { kn = 0; ++nn; }
+    const bool live_n = t + 1 < n_stages && kn + 4 * g_lane < L;
+    const unsigned sa = (unsigned)(((long long)nn * d.a_ns + kn) * 4), sb = (unsigned)(((long long)nn * d.b_ns + kn) * 4);
+    const unsigned buf = (unsigned)(t & 1) * PS_PANEL_B, nbuf = PS_PANEL_B - buf;
+    const bool tail_stage = kk + PS_KC > L;    // (the last stage of a sample whose L is no multiple of the stage)
+    auto rd = [&](unsigned at) { return *reinterpret_cast<const __attribute__((address_space(3))) f32x4*>(lds + at + buf); };
+    f32x4 a[2], b[BN];
+#pragma unroll
+    for (int m = 0; m < 2; ++m) a[m] = rd(addr_a[m][0]);
+#pragma unroll
+    for (int nb = 0; nb < BN; ++nb) b[nb] = rd(addr_b[nb][0]);
+#pragma unroll
+    for (int j = 0; j < PS_STEPS; ++j) {
+      if (tail_stage) {
+        asm volatile("; l tail" ::: "memory");             // keeps this a branch around a VALU-only block
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const bool gone = kk + 4 * (2 * j + h) + e >= L;
+#pragma unroll
+          for (int m = 0; m < 2; ++m) a[m][e] = gone ? 0.0f : a[m][e];
+#pragma unroll
+          for (int nb = 0; nb < BN; ++nb) b[nb][e] = gone ? 0.0f : b[nb][e];
+        }
+      }
+      f32x4 na[2], nb_[BN];
+      if (j + 1 < PS_STEPS) {
+#pragma unroll
+        for (int m = 0; m < 2; ++m) na[m] = rd(addr_a[m][j + 1]);
+#pragma unroll
+        for (int nb = 0; nb < BN; ++nb) nb_[nb] = rd(addr_b[nb][j + 1]);
+      }
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+#pragma unroll
+        for (int m = 0; m < 2; ++m)
+#pragma unroll
+          for (int nb = 0; nb < BN; ++nb) c[m][nb] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[m][e], b[nb][e], c[m][nb], 0, 0, 0);
+        if (e < PS_PPS && PS_PPS * j + e < NP) issue(PS_PPS * j + e, live_n, sa, sb, nbuf);   // one piece behind a group of MFMAs
+      }
+      if (j + 1 < PS_STEPS) {
+#pragma unroll
+        for (int m = 0; m < 2; ++m) a[m] = na[m];
+#pragma unroll
+        for (int nb = 0; nb < BN; ++nb) b[nb] = nb_[nb];
+      }
+    }
+    if (sample_ends) {
+      // the sample boundary: square the tile of P_n, add it to the running sum, start the next sample from zero
+#pragma unroll
+      for (int m = 0; m < 2; ++m)
+#pragma unroll
+        for (int nb = 0; nb < BN; ++nb) {
+          q[m][nb] += c[m][nb] * c[m][nb];
+          c[m][nb] = 0.0f;
+        }
+    }
+    n = nn;
+    kk = kn;
+  }
+
+  // raw partial tile, row-major TA x 128, to this item's slab (every entry is written)
+  gfl* slab = (gfl*)d.slabs + (long long)local * (TA * PS_TM);
+#pragma unroll
+  for (int m = 0; m < 2; ++m)
+#pragma unroll
+    for (int nb = 0; nb < BN; ++nb) {
+      const int col = row_b + 32 * nb + r32;
+#pragma unroll
+      for (int reg = 0; reg < 16; ++reg) {
+        const int r = row_a + 32 * m + (reg & 3) + 8 * (reg >> 2) + 4 * h;
+        slab[r * PS_TM + col] = q[m][nb][reg];
+      }
+    }
+}
+
+__global__ void __launch_bounds__(PS_THREADS, 2) ps_product_kernel(const PsBatch batch) {
+  __shared__ __attribute__((aligned(1024))) char smem[4 * PS_PANEL_B];   // [buffer][A panel, B panel] as gemm_nt.h
+  const PsProduct& d = batch.p[find_product(batch, blockIdx.x)];
+  const int local = (int)(blockIdx.x - d.base);
+  if (d.half) ps_product_tile<true>(d, local, (lds_char*)smem);
+  else ps_product_tile<false>(d, local, (lds_char*)smem);
+}
+
+// Reduce: one thread per entry (i, j) of C; it sums the slab entries of its tile in slice order, scales, writes or adds.
+// Blocks of a product: ceil(M Nc / 256).
+__global__ void __launch_bounds__(PS_THREADS) ps_reduce_kernel(const PsBatch batch) {
+  const PsProduct& d = batch.p[find_product(batch, blockIdx.x)];
+  const int rows = d.swap ? d.Nc : d.M, cols = d.swap ? d.M : d.Nc;            // of C
+  const long long idx = (blockIdx.x - d.base) * PS_THREADS + threadIdx.x;
+  if (idx >= (long long)rows * cols) return;
+  const int i = (int)(idx / cols), j = (int)(idx - (long long)i * cols);
+  const int ik = d.swap ? j : i, jk = d.swap ? i : j;                           // in the tile the kernel computed
+  const int ta = d.half ? PS_TM / 2 : PS_TM;
+  const int tm = ik / ta, tn = jk / PS_TM;
+  const long long tile = (long long)tm * d.tiles_n + tn, slab = (long long)ta * PS_TM;
+  const float* s = d.slabs + tile * d.slices * slab + (ik - tm * ta) * PS_TM + (jk - tn * PS_TM);
+  float v = 0.f;
+#pragma unroll 8
+  for (int sl = 0; sl < d.slices; ++sl) v += s[sl * slab];                      // loads independent, adds in slice order
+  v *= d.alpha;
+  float* out = d.C + (long long)i * d.c_rs + j;
+  *out = d.first ? v : *out + v;
+}
+
+// ------------------------------------------------------------------------------------------------ pack
+struct PsPack {
+  const float* src;
+  float* dst;
+  int N, C, H, W, kh, kw, sh, sw, ph, pw, Ho, Wo;
+  int rows;                   // C kh kw (the ones row, if any, is row `rows`)
+  int R;                      // rows + has_bias
+  int L, Lp;
+  int has_bias, channels_last, rows_outer;
+  long long base;             // first thread of this layer in the launch
+};
+
+struct PsPackBatch {
+  PsPack p[PS_BATCH];
+  int count;
+};
+
+bool pack_plan_of(const curv_persample_pack_desc& d, int index, PsPack* out) {
+  if (d.N < 1 || d.C < 1 || d.H < 1 || d.W < 1 || d.kh < 1 || d.kw < 1 || d.sh < 1 || d.sw < 1 || d.ph < 0 || d.pw < 0) {
+    set_error("curv_persample_pack: item %d: invalid geometry (N %d C %d H %d W %d kernel %dx%d stride %dx%d padding %dx%d)",
+              index, d.N, d.C, d.H, d.W, d.kh, d.kw, d.sh, d.sw, d.ph, d.pw);
+    return false;
+  }
+  if (d.H + 2 * d.ph < d.kh || d.W + 2 * d.pw < d.kw) {
+    set_error("curv_persample_pack: item %d: empty output (kernel %dx%d larger than the padded %dx%d input)", index, d.kh,
+              d.kw, d.H + 2 * d.ph, d.W + 2 * d.pw);
+    return false;
+  }
+  PsPack P;
+  P.src = d.src; P.dst = d.dst;
+  P.N = d.N; P.C = d.C; P.H = d.H; P.W = d.W;
+  P.kh = d.kh; P.kw = d.kw; P.sh = d.sh; P.sw = d.sw; P.ph = d.ph; P.pw = d.pw;
+  P.Ho = (d.H + 2 * d.ph - d.kh) / d.sh + 1;
+  P.Wo = (d.W + 2 * d.pw - d.kw) / d.sw + 1;
+  const long long rows = (long long)d.C * d.kh * d.kw, L = (long long)P.Ho * P.Wo;
+  if (rows > (1 << 24) || L > (1 << 24) || (long long)d.N * d.C * d.H * d.W >= (1LL << 40) ||
+      (long long)d.C * d.H * d.W >= (1LL << 31) || (long long)d.N * (rows + 1) * (d.Lp / 4 + 1) >= (1LL << 31)) {
+    set_error("curv_persample_pack: item %d: too large (%lld rows, %lld positions)", index, rows, L);
+    return false;
+  }
+  P.rows = (int)rows;
+  P.has_bias = d.has_bias ? 1 : 0;
+  P.R = P.rows + P.has_bias;
+  P.L = (int)L;
+  P.Lp = d.Lp;
+  if (d.Lp < P.L || (d.Lp & 3)) {
+    set_error("curv_persample_pack: item %d: Lp %d must be a multiple of 4 and at least L = %d", index, d.Lp, P.L);
+    return false;
+  }
+  P.channels_last = d.channels_last ? 1 : 0;
+  P.rows_outer = d.rows_outer ? 1 : 0;
+  P.base = 0;
+  *out = P;
+  return true;
+}
+
+// Pack: one thread per 4 consecutive columns of one row of one sample (one 16-byte store); padding columns are written
+// as zeros, a masked gather reads src[0] and drops it.
+__global__ void __launch_bounds__(PS_THREADS) ps_pack_kernel(const PsPackBatch batch) {
+  const long long t = (long long)blockIdx.x * PS_THREADS + threadIdx.x;
+  int f = 0;
+  for (int i = 1; i < batch.count; ++i)
+    if (t >= batch.p[i].base) f = i;
+  const PsPack& F = batch.p[f];
+  // 32-bit index arithmetic from here on (a layer has fewer than 2^31 threads and a sample fewer than 2^31 values:
+  // pack_plan_of): the 64-bit divisions cost more than the copy
+  const unsigned gpr = F.Lp / 4, R = F.R;
+  if (t - F.base >= (long long)F.N * R * gpr) return;
+  const unsigned local = (unsigned)(t - F.base);
+  const unsigned row = local / gpr;                        // n R + r
+  const int k0 = (int)(local - row * gpr) * 4;
+  const int n = (int)(row / R), r = (int)(row - (unsigned)n * R);
+  float v[4];
+  if (r < F.rows) {
+    const unsigned khw = F.kh * F.kw;
+    const int c = (int)((unsigned)r / khw), q = r - c * (int)khw;
+    const int a = (int)((unsigned)q / (unsigned)F.kw), b = q - a * F.kw;
+    int oh = (int)((unsigned)k0 / (unsigned)F.Wo), ow = k0 - oh * F.Wo;
+    const float* plane = F.src + (F.channels_last ? (long long)n * F.H * F.W * F.C + c
+                                                  : ((long long)n * F.C + c) * F.H * F.W);
+    const int step = F.channels_last ? F.C : 1;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const int ih = oh * F.sh - F.ph + a, iw = ow * F.sw - F.pw + b;
+      const bool ok = k0 + e < F.L && (unsigned)ih < (unsigned)F.H && (unsigned)iw < (unsigned)F.W;
+      const float x = ok ? plane[(ih * F.W + iw) * step] : F.src[0];        // a masked gather reads src[0]
+      v[e] = ok ? x : 0.0f;
+      if (++ow == F.Wo) { ow = 0; ++oh; }
+    }
+  } else {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) v[e] = k0 + e < F.L ? 1.0f : 0.0f;      // the ones row of a biased layer
+  }
+  const long long out = F.rows_outer ? ((long long)r * F.N + n) * F.Lp + k0 : (long long)row * F.Lp + k0;
+  *reinterpret_cast<float4*>(F.dst + out) = make_float4(v[0], v[1], v[2], v[3]);
+}
+
+bool plans_of(const curv_persample_desc* descs, int n, Plan* plans, size_t* total) {
+  *total = 0;
+  for (int i = 0; i < n; ++i) {
+    if (!plan_of(descs[i], i, &plans[i])) return false;
+    *total += plans[i].slab_bytes;
+  }
+  return true;
+}
+
+}  // namespace
+}  // namespace curv
+
+using namespace curv;
+
+extern "C" size_t curv_persample_workspace_bytes(const curv_persample_desc* descs, int n) {
+  if (n <= 0) return 0;
+  if (!descs) {
+    set_error("curv_persample_workspace_bytes: null descriptors");
+    return 0;
+  }
+  std::vector<Plan> plans(n);
+  size_t total;
+  if (!plans_of(descs, n, plans.data(), &total)) return 0;
+  return total;
+}
+
+extern "C" int curv_persample_plan_flops(const curv_persample_desc* descs, int n, long long* out) {
+  if (n <= 0) return CURV_OK;
+  CURV_REQUIRE(descs && out, "curv_persample_plan_flops: null argument");
+  for (int i = 0; i < n; ++i) {
+    Plan p;
+    if (!plan_of(descs[i], i, &p)) return CURV_ERR_INVALID;
+    out[i] = p.flops;
+  }
+  return CURV_OK;
+}
+
+extern "C" int curv_persample_sq_accumulate(void* stream_, const curv_persample_desc* descs, int n, void* workspace,
+                                            size_t workspace_bytes) {
+  if (n <= 0) return CURV_OK;
+  CURV_REQUIRE(descs != nullptr, "curv_persample_sq_accumulate: null descriptors");
+  hipStream_t stream = (hipStream_t)stream_;
+  std::vector<Plan> plans(n);
+  size_t total;
+  if (!plans_of(descs, n, plans.data(), &total)) return CURV_ERR_INVALID;
+  for (int i = 0; i < n; ++i)
+    CURV_REQUIRE(descs[i].A && descs[i].B && descs[i].C, "curv_persample_sq_accumulate: item %d: null operand", i);
+  if (!workspace || workspace_bytes < total || (reinterpret_cast<uintptr_t>(workspace) & 255)) {
+    set_error("curv_persample_sq_accumulate: workspace too small (%zu < %zu bytes) or not 256-byte aligned",
+              workspace_bytes, total);
+    return CURV_ERR_WORKSPACE;
+  }
+  size_t at = 0;
+  for (int first = 0; first < n; first += PS_BATCH) {
+    const int count = std::min(PS_BATCH, n - first);
+    PsBatch items, blocks;
+    items.count = blocks.count = count;
+    long long n_items = 0, n_blocks = 0;
+    for (int k = 0; k < count; ++k) {
+      const curv_persample_desc& d = descs[first + k];
+      const Plan& p = plans[first + k];
+      PsProduct P;
+      P.A = d.A; P.B = d.B; P.C = d.C;
+      P.slabs = (float*)((char*)workspace + at);
+      at += p.slab_bytes;
+      P.a_ns = d.a_ns; P.a_rs = d.a_rs; P.b_ns = d.b_ns; P.b_rs = d.b_rs; P.c_rs = d.c_rs;
+      P.S = d.S; P.M = d.M; P.Nc = d.Nc; P.L = d.L;
+      P.a_bytes = (unsigned)p.a_bytes; P.b_bytes = (unsigned)p.b_bytes;
+      if (p.swap) {
+        std::swap(P.A, P.B); std::swap(P.a_ns, P.b_ns); std::swap(P.a_rs, P.b_rs); std::swap(P.M, P.Nc);
+        std::swap(P.a_bytes, P.b_bytes);
+      }
+      P.tiles_n = p.tiles_n; P.tiles = p.tiles; P.spi = p.spi; P.slices = p.slices;
+      P.half = p.half; P.swap = p.swap;
+      P.first = d.first ? 1 : 0; P.alpha = d.alpha;
+      P.base = n_items;
+      items.p[k] = P;
+      P.base = n_blocks;
+      blocks.p[k] = P;
+      n_items += (long long)p.tiles * p.slices;
+      n_blocks += cdivll((long long)d.M * d.Nc, PS_THREADS);
+    }
+    for (int k = count; k < PS_BATCH; ++k) { items.p[k] = items.p[0]; blocks.p[k] = blocks.p[0]; }
+    CURV_REQUIRE(n_items < (1LL << 31) && n_blocks < (1LL << 31), "curv_persample_sq_accumulate: too many workgroups (%lld, %lld)",
+                 n_items, n_blocks);
+    hipLaunchKernelGGL(ps_product_kernel, dim3((unsigned)n_items), dim3(PS_THREADS), 0, stream, items);
+    CURV_LAUNCH_CHECK();
+    hipLaunchKernelGGL(ps_reduce_kernel, dim3((unsigned)n_blocks), dim3(PS_THREADS), 0, stream, blocks);
+    CURV_LAUNCH_CHECK();
+  }
+  return CURV_OK;
+}
+
+extern "C" int curv_persample_pack(void* stream_, const curv_persample_pack_desc* descs, int n) {
+  if (n <= 0) return CURV_OK;
+  CURV_REQUIRE(descs != nullptr, "curv_persample_pack: null descriptors");
+  hipStream_t stream = (hipStream_t)stream_;
+  std::vector<PsPack> packs(n);
+  for (int i = 0; i < n; ++i) {
+    if (!pack_plan_of(descs[i], i, &packs[i])) return CURV_ERR_INVALID;
+    CURV_REQUIRE(descs[i].src && descs[i].dst && (reinterpret_cast<uintptr_t>(descs[i].dst) & 15) == 0,
+                 "curv_persample_pack: item %d: null src or dst, or dst not 16-byte aligned", i);
+  }
+  for (int first = 0; first < n; first += PS_BATCH) {
+    const int count = std::min(PS_BATCH, n - first);
+    PsPackBatch b;
+    b.count = count;
+    long long threads = 0;
+    for (int k = 0; k < count; ++k) {
+      b.p[k] = packs[first + k];
+      b.p[k].base = threads;
+      threads += (long long)b.p[k].N * b.p[k].R * (b.p[k].Lp / 4);
+    }
+    for (int k = count; k < PS_BATCH; ++k) b.p[k] = b.p[0];
+    const long long blocks = cdivll(threads, PS_THREADS);
+    CURV_REQUIRE(blocks < (1LL << 31), "curv_persample_pack: too many workgroups (%lld)", blocks);
+    hipLaunchKernelGGL(ps_pack_kernel, dim3((unsigned)blocks), dim3(PS_THREADS), 0, stream, b);
+    CURV_LAUNCH_CHECK();
+  }
+  return CURV_OK;
+}

@@ -492,6 +492,80 @@ class Curvature(ABC):
                 if l._parameters[nm] is not None] if means else ()
         return params, tuple(map(ptr, params)), tuple(map(ptr, mean))
 
+    # ------------------------------------------------------------------ recording hooks (KFAC; per-sample Diagonal / EFB)
+    def _record_layer(self, layer) -> None:
+        """Record `layer`'s input (by reference) and raw grad_output into ``self.record[layer]`` at every pass."""
+        self.record[layer] = [None, None]
+        self.hooks.append(layer.register_forward_pre_hook(self._save_input))
+        self.hooks.append(layer.register_forward_hook(self._hook_output))
+
+    def _save_input(self, module, input):
+        self.record[module][0] = input[0]            # by reference, like curvatures.py:307
+
+    def _hook_output(self, module, input, output):
+        if _is_convt(module):
+            # the output size carries the effective output_padding (layer(x, output_size=...) changes it)
+            self._out_size[module] = tuple(output.shape[-2:])
+        if output.requires_grad:
+            output.register_hook(lambda grad, module=module: self._save_output(module, grad))
+
+    def _save_output(self, module, grad_output):
+        self.record[module][1] = grad_output         # raw; the reference stores grad * N (curvatures.py:310)
+
+    def _record_per_sample(self, what: str) -> None:
+        """``per_sample=True`` of Diagonal / EFB: check that every selected layer has a per-sample form and register
+        KFAC's recording hooks on it."""
+        self.hooks = list()
+        self.record = dict()
+        names = {mod: name for name, mod in self.model.named_modules()}
+        for layer in self.model.modules():
+            kind = layer.__class__.__name__
+            if kind not in self.layer_types:
+                continue
+            why = None
+            if kind == 'Conv2d':
+                if int(layer.groups) != 1:
+                    why = f"grouped convolution (groups={layer.groups})"
+                elif tuple(layer.dilation) != (1, 1):
+                    why = "dilated convolution"
+                elif not all(isinstance(p, int) for p in layer.padding):
+                    why = "string padding mode"
+            elif kind != 'Linear':
+                why = kind
+            if why is not None:
+                raise NotImplementedError(f"{what}(per_sample=True): layer '{names.get(layer, '?')}' is not supported ({why}); "
+                                          "select other layer types or use per_sample=False")
+            self._record_layer(layer)
+
+    def _per_sample_operands(self, what: str, layers, **layout):
+        """The per-sample operands of `layers` from their records, packed where they cannot be read in place:
+        [(sides, g tensor, x tensor)] with `sides` the `ops.PerSampleSides` whose strides address the two tensors.  A missing
+        record raises like KFAC's; CPU records raise RuntimeError (no fallback).  The packed copies live in shared scratch:
+        they are valid until the next per-sample update on this stream."""
+        sides = []
+        for layer in layers:
+            forward, backward = self.record[layer]
+            if forward is None or backward is None:
+                raise RuntimeError(f"{what}.update: no recorded forward/backward pass for a selected layer")
+            for t in (forward, backward):
+                if t.dtype != torch.float32:
+                    raise RuntimeError(f"{what}.update(per_sample=True) expects float32 records, got {t.dtype}")
+                if not t.is_cuda:
+                    raise RuntimeError("curvature_amd runs on MI355X only: got a CPU tensor (no CPU fallback)")
+            sides.append(ops.per_sample_operands(layer, forward, backward, **layout))
+        flat = [op for s in sides for op in (s.g, s.x)]
+        bufs = ops.per_sample_scratch([op.floats for op in flat], flat[0].src.device)
+        packed = [(op, buf) for op, buf in zip(flat, bufs) if op.pack is not None]
+        ops.per_sample_pack([op for op, _ in packed], [buf for _, buf in packed])
+        tensors = [buf if op.pack is not None else op.src for op, buf in zip(flat, bufs)]
+        return [(s, tensors[2 * k], tensors[2 * k + 1]) for k, s in enumerate(sides)]
+
+    @staticmethod
+    def _per_sample_job(sides, g, x, dst, alpha: float, first: bool):
+        """dst (+)= alpha * sum_n (g_n x_n^T)**2 for operands laid out as `sides` says."""
+        return ops.PerSampleJob(g, x, dst, sides.N, sides.m, sides.n, sides.L, sides.g.ns, sides.g.rs, sides.x.ns,
+                                sides.x.rs, alpha=alpha, first=first)
+
     @staticmethod
     def _replace(sample: Tensor, weight: Tensor, bias: Tensor = None):
         """weight += sample[:, :-1], bias += sample[:, -1] (curvatures.py:67-82)."""
@@ -586,7 +660,42 @@ class Diagonal(Curvature):
 
     _supports_mha = True
 
+    def __init__(self, model: Union[Module, Sequential], layer_types: Union[List[str], str] = None, *, shard=None,
+                 per_sample: bool = False):
+        """`per_sample` (keyword-only extension, default off: nothing changes): the exact Fisher diagonal at any batch
+        size.  ``update(batch_size)`` then accumulates ``batch_size * sum_n P_n**2`` with P_n = g_n X_n^T the share of
+        sample n (index of the leading dimension) in [W.grad | b.grad], from the layer inputs and raw grad_outputs that
+        KFAC's hooks record, instead of ``batch_size * (sum_n P_n)**2`` from ``.grad`` - the two agree at batch size 1.
+        The P_n are those of the BATCH pass: a BatchNorm layer in training mode couples the samples of a batch, and the
+        per-sample quantities are defined from that pass's records, not from N separate passes.  Linear and Conv2d
+        (groups 1, dilation 1, integer padding) with float32 records; any other selected layer raises
+        NotImplementedError here."""
+        super().__init__(model, layer_types, shard=shard)
+        self.per_sample = bool(per_sample)
+        if self.per_sample:
+            self._record_per_sample("Diagonal")
+
+    def _update_per_sample(self, batch_size):
+        layers = [l for _, l in self._owned()]
+        if not layers:
+            return
+        operands = self._per_sample_operands("Diagonal", layers)
+        new = [(l, s) for l, (s, _, _) in zip(layers, operands) if l not in self.state]
+        fresh = {}
+        if new:
+            self._state_arena = _Arena([(s.m, s.n) for _, s in new], operands[0][1].device)
+            fresh = {l: v for (l, _), v in zip(new, self._state_arena.views)}
+        jobs = []
+        for layer, (sides, g, x) in zip(layers, operands):
+            dst = fresh.get(layer, self.state.get(layer))
+            jobs.append(self._per_sample_job(sides, g, x, dst, float(batch_size), layer in fresh))
+        ops.per_sample_sq_accumulate(jobs)                 # one product per layer, all layers in one call
+        for layer, job in zip(layers, jobs):
+            self.state[layer] = job.C
+
     def update(self, batch_size: int):
+        if self.per_sample:
+            return self._update_per_sample(batch_size)
         # one pass over modules() so that `state` gets the reference's insertion order (curvatures.py:149-174),
         # which is the order per-layer hyper-parameter lists are indexed by
         owned = {l for _, l in self._owned()}
@@ -867,16 +976,12 @@ class KFAC(Curvature):
                     # reference ignores `groups` and then fails in _replace): state[layer] = [A, G] stacked (G, n, n)
                     if name == 'Conv2d' and not all(isinstance(p, int) for p in layer.padding):
                         raise NotImplementedError("KFAC: string padding modes are not supported")
-                    self.record[layer] = [None, None]
-                    self.hooks.append(layer.register_forward_pre_hook(self._save_input))
-                    self.hooks.append(layer.register_forward_hook(self._hook_output))
+                    self._record_layer(layer)
                 elif name == 'ConvTranspose2d':
                     # Wm = weight.permute(1, 0, 2, 3).reshape(out, -1) [| bias]; A from the phase-split build
                     # (curv_kfac_convt_accumulate), G a 1x1 factor of grad_output as for Conv2d
                     _check_convt(layer)
-                    self.record[layer] = [None, None]
-                    self.hooks.append(layer.register_forward_pre_hook(self._save_input))
-                    self.hooks.append(layer.register_forward_hook(self._hook_output))
+                    self._record_layer(layer)
                 elif name == 'MultiheadAttention':
                     # the two projections as Linear-like layers (extension: curvatures.py:303-304 raises here); their
                     # inputs / output gradients are tapped off the F.linear calls of the attention forward
@@ -885,19 +990,6 @@ class KFAC(Curvature):
                         self.record[proj] = [None, None]
                     self.hooks.append(layer.register_forward_pre_hook(tap.install))
                     self.hooks.append(layer.register_forward_hook(tap.remove, always_call=True))
-
-    def _save_input(self, module, input):
-        self.record[module][0] = input[0]            # by reference, like curvatures.py:307
-
-    def _hook_output(self, module, input, output):
-        if _is_convt(module):
-            # the output size carries the effective output_padding (layer(x, output_size=...) changes it)
-            self._out_size[module] = tuple(output.shape[-2:])
-        if output.requires_grad:
-            output.register_hook(lambda grad, module=module: self._save_output(module, grad))
-
-    def _save_output(self, module, grad_output):
-        self.record[module][1] = grad_output         # raw; the reference stores grad * N (curvatures.py:310)
 
     def update(self, batch_size: int = None, *, inputs: bool = True, grads: bool = True, input_weight: float = 1.0,
                grad_scale: float = 1.0):
@@ -1248,8 +1340,16 @@ class EFB(Curvature):
     _mha_as_projections = True
 
     def __init__(self, model: Union[Module, Sequential], factors: Dict[Module, Tensor],
-                 layer_types: Union[List[str], str] = None, *, shard=None, eigvecs=None):
+                 layer_types: Union[List[str], str] = None, *, shard=None, eigvecs=None, per_sample: bool = False):
+        """`per_sample` (keyword-only, default off: nothing changes): ``update(batch_size)`` accumulates the exact
+        ``batch_size * sum_n (U_G^T P_n U_A)**2`` into `state` and ``batch_size * sum_n P_n**2`` into `diags`, with
+        P_n = g_n X_n^T the share of sample n in [W.grad | b.grad], from recorded layer inputs and grad_outputs (see
+        `Diagonal`; the P_n are those of the batch pass, also under a training-mode BatchNorm) instead of squaring the
+        batch gradient.  The two agree at batch size 1."""
         super().__init__(model, layer_types, shard=shard)
+        self.per_sample = bool(per_sample)
+        if self.per_sample:
+            self._record_per_sample("EFB")
         _reject_grouped(self, "EFB")
         if eigvecs is None:
             from .utils import get_eigenvectors
@@ -1264,7 +1364,38 @@ class EFB(Curvature):
         """Owned layers that have eigenvectors, in ``modules()`` order."""
         return [l for _, l in self._owned() if l in self.eigvecs]
 
+    def _update_per_sample(self, batch_size):
+        layers = self._mine()
+        if not layers:
+            return
+        # both operands of every layer packed as ONE (rows, N Lp) matrix: a rotation is one product per layer,
+        #   T = U_G^T g (m x N Lp),  Y = U_A^T X (n x N Lp),  then  Lambda += batch_size * sum_n (T_n Y_n^T)**2
+        operands = self._per_sample_operands("EFB", layers, rows_outer=True, in_place=False)
+        dev = operands[0][1].device
+        missing = [(l, s) for l, (s, _, _) in zip(layers, operands) if l not in self.state]
+        if missing:
+            self._state_arena = _Arena([(s.m, s.n) for _, s in missing], dev, zero=True)
+            for (l, _), v in zip(missing, self._state_arena.views):
+                self.state[l] = v
+        rotated = [torch.empty(t.numel(), dtype=torch.float32, device=dev) for _, g, x in operands for t in (g, x)]
+        gemms, jobs = [], []
+        for k, (layer, (sides, g, x)) in enumerate(zip(layers, operands)):
+            U_At, U_Gt = self._eigvecs_t(layer)
+            T, Y = rotated[2 * k], rotated[2 * k + 1]
+            cols = sides.N * sides.g.Lp
+            gemms.append(ops.Gemm(U_Gt, g.view(sides.m, cols), T.view(sides.m, cols)))
+            gemms.append(ops.Gemm(U_At, x.view(sides.n, cols), Y.view(sides.n, cols)))
+            jobs.append(self._per_sample_job(sides, T, Y, self.state[layer], float(batch_size), False))
+            first = layer not in self.diags
+            if first:
+                self.diags[layer] = torch.empty(sides.m, sides.n, dtype=torch.float32, device=dev)
+            jobs.append(self._per_sample_job(sides, g, x, self.diags[layer], float(batch_size), first))
+        ops.gemm_batched(gemms)
+        ops.per_sample_sq_accumulate(jobs)
+
     def update(self, batch_size: int):
+        if self.per_sample:
+            return self._update_per_sample(batch_size)
         layers = self._mine()
         if not layers:
             return

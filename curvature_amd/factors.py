@@ -40,7 +40,8 @@ def compute_factors(args: Any,
                     device=None,
                     share_inputs: bool = True,
                     label_sampler: Optional[Callable] = None,
-                    autocast: Optional[torch.dtype] = None):
+                    autocast: Optional[torch.dtype] = None,
+                    per_sample: bool = False):
     """``compute_factors(args, model, data, factors=None)`` of the reference (scripts/factors.py:33-62).
 
     `args` may be the reference's argparse namespace or ``None`` with the keyword arguments.  `data` yields
@@ -48,16 +49,21 @@ def compute_factors(args: Any,
     batch_index, sample_index)` replaces ``Categorical(logits).sample()`` (parity tests).  `autocast`
     (``torch.bfloat16`` / ``torch.float16``): the forward pass and the loss run under ``torch.autocast('cuda',
     dtype=autocast)``, so KFAC records half-precision activations and gradients (built on the bf16 / fp16 MFMA,
-    ``KFAC.update``); the label distribution is formed from the logits in float32."""
+    ``KFAC.update``); the label distribution is formed from the logits in float32.  `per_sample`: passed to `Diagonal` /
+    `EFB` (the exact per-sample Fisher at any batch size); other estimators have no such form (ValueError)."""
     a = _as_args(args, estimator=estimator, samples=samples, epochs=epochs, device=device)
     dev = a.device if a.device is not None else next(model.parameters()).device
     model.train()
     criterion = torch.nn.CrossEntropyLoss().to(dev)
-    est_base = getattr(curv, a.estimator.upper())
+    # 'diag' / 'diagonal' select Diagonal (the reference's lookup by upper-cased name, scripts/factors.py:40, has none)
+    est_base = curv.Diagonal if a.estimator in ('diag', 'diagonal') else getattr(curv, a.estimator.upper())
+    if per_sample and not issubclass(est_base, (curv.Diagonal, curv.EFB)):
+        raise ValueError(f"compute_factors: per_sample applies to the Diagonal and EFB estimators, not '{a.estimator}'")
+    extra = {"per_sample": True} if per_sample else {}
     if a.estimator == 'efb':
-        est = est_base(model, factors)
+        est = est_base(model, factors, **extra)
     else:
-        est = est_base(model)
+        est = est_base(model, **extra)
     shared = share_inputs and isinstance(est, curv.KFAC) and a.samples > 1
 
     def amp():

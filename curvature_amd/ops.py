@@ -500,6 +500,178 @@ def factor_jobs(layer, x, g, out_size=None) -> LayerJobs:
                      (x if x is not None else g).shape[0], out_size[0] * out_size[1], groups)
 
 
+class PerSampleOperand(NamedTuple):
+    """One side of P_n = g_n X_n^T as `per_sample_sq_accumulate` reads it: `rows` rows of `L` values per sample, sample
+    `n` row `r` at ``ns * n + rs * r`` floats.  `pack` is None where the record `src` is read in place, otherwise the
+    geometry ``(N, C, H, W, kernel, stride, padding, has_bias, channels_last)`` of the copy `per_sample_pack` writes
+    (`floats` of scratch, rows of `Lp` values with a zero tail, `rows_outer`: (rows, N, Lp) instead of (N, rows, Lp))."""
+    src: object
+    rows: int
+    L: int
+    Lp: int
+    ns: int
+    rs: int
+    pack: Optional[tuple]
+    rows_outer: bool
+    floats: int
+
+
+class PerSampleSides(NamedTuple):
+    """`per_sample_operands` of one layer: the `g` (m rows) and `x` (n rows, ones row included) operands of `N` samples."""
+    g: PerSampleOperand
+    x: PerSampleOperand
+    n: int
+    m: int
+    N: int
+    L: int
+
+
+def _per_sample_operand(src, geometry, in_place: bool, rows_outer: bool) -> PerSampleOperand:
+    N, C, H, W, kernel, stride, padding, has_bias, channels_last = geometry
+    L = ((H + 2 * padding[0] - kernel[0]) // stride[0] + 1) * ((W + 2 * padding[1] - kernel[1]) // stride[1] + 1)
+    rows = C * kernel[0] * kernel[1] + int(has_bias)
+    if in_place:
+        return PerSampleOperand(src, rows, L, L, rows * L, L, None, False, 0)
+    Lp = (L + 3) // 4 * 4
+    ns, rs = (Lp, N * Lp) if rows_outer else (rows * Lp, Lp)
+    return PerSampleOperand(src, rows, L, Lp, ns, rs, geometry, rows_outer, N * rows * Lp)
+
+
+def per_sample_operands(layer, x, g, rows_outer: bool = False, in_place: bool = True) -> PerSampleSides:
+    """The step from a layer's records `(x, g)` to the operands of its per-sample gradients P_n = g_n X_n^T (sample = index
+    of the leading dimension, as in `KFAC.update`), on the geometry of `factor_jobs`.
+
+    Conv2d (groups 1, dilation 1): g_n = grad_output[n] as (m, Ho Wo), X_n = unfold(x[n]) [+ ones row].  Linear:
+    g_n = grad_output[n]^T (m, T), X_n = x[n]^T [+ ones row] (D [+ 1], T) with T the product of the middle dimensions
+    (1 for an (N, D) input).  An operand is read in place where the record already is that matrix, rows contiguous and a
+    whole number of 16-byte groups long (grad_output of a convolution; the input of a bias-free 1x1 / stride-1 one);
+    everything else names the pack that writes it.  `rows_outer` / ``in_place=False``: every operand packed as one
+    (rows, N Lp) matrix (EFB rotates it with one product).  float32 records only."""
+    for t in (x, g):
+        if t.dtype != torch.float32:
+            raise RuntimeError(f"per-sample update expects float32 records, got {t.dtype}")
+    sides = factor_jobs(layer, ShapeOnly(tuple(x.shape)), ShapeOnly(tuple(g.shape)))
+    if sides.groups != 1 or not isinstance(sides.a, FactorJob):
+        raise NotImplementedError(f"per-sample update: unsupported layer {layer.__class__.__name__}")
+    x, g = x.detach().contiguous(), g.detach().contiguous()
+    N = int(x.shape[0])
+    has_bias = sides.a.has_bias
+    if layer.__class__.__name__ == 'Conv2d':
+        _, C, H, W = x.shape
+        _, m, Ho, Wo = g.shape
+        geo_x = (N, C, H, W, sides.a.kernel, sides.a.stride, sides.a.padding, has_bias, False)
+        geo_g = (N, m, Ho, Wo, (1, 1), (1, 1), (0, 0), False, False)
+        whole = in_place and (Ho * Wo) % 4 == 0
+        plain = sides.a.kernel == (1, 1) and sides.a.stride == (1, 1) and sides.a.padding == (0, 0) and not has_bias
+        x_op = _per_sample_operand(x, geo_x, whole and plain, rows_outer)
+        g_op = _per_sample_operand(g, geo_g, whole, rows_outer)
+    else:
+        T = math.prod(x.shape[1:-1])
+        geo_x = (N, int(x.shape[-1]), T, 1, (1, 1), (1, 1), (0, 0), has_bias, True)
+        geo_g = (N, int(g.shape[-1]), T, 1, (1, 1), (1, 1), (0, 0), False, True)
+        x_op = _per_sample_operand(x, geo_x, False, rows_outer)
+        g_op = _per_sample_operand(g, geo_g, False, rows_outer)
+    if g_op.L != x_op.L or g_op.rows != sides.m or x_op.rows != sides.n or g.shape[0] != N:
+        raise RuntimeError(f"per-sample update: records of {layer.__class__.__name__} do not match the layer "
+                           f"(input {tuple(x.shape)}, grad_output {tuple(g.shape)})")
+    return PerSampleSides(g_op, x_op, sides.n, sides.m, N, x_op.L)
+
+
+def per_sample_pack(operands: Sequence[PerSampleOperand], dsts: Sequence[torch.Tensor]) -> None:
+    """curv_persample_pack: the packed copy of every operand into its `dst` (a float32 GPU buffer of `floats` values, 16-byte
+    aligned), all layers in one call."""
+    if not operands:
+        return
+    arr = (_lib.curv_persample_pack_desc * len(operands))()
+    for d, op, dst in zip(arr, operands, dsts):
+        _require_gpu(op.src, dst)
+        if dst.numel() < op.floats:
+            raise RuntimeError("per_sample_pack: destination too small")
+        N, C, H, W, kernel, stride, padding, has_bias, channels_last = op.pack
+        d.src, d.dst = op.src.data_ptr(), dst.data_ptr()
+        d.N, d.C, d.H, d.W = N, C, H, W
+        d.kh, d.kw = kernel
+        d.sh, d.sw = stride
+        d.ph, d.pw = padding
+        d.has_bias, d.channels_last, d.rows_outer, d.Lp = int(has_bias), int(channels_last), int(op.rows_outer), op.Lp
+    _lib.check(_lib.lib().curv_persample_pack(_lib.stream_ptr(), arr, len(operands)), "curv_persample_pack")
+
+
+class PerSampleJob:
+    """C (+)= alpha * sum_n (A_n B_n^T)**2 over `S` samples: A_n is (M, L) at ``A + n a_ns`` with row stride `a_rs`, B_n
+    (Nc, L) likewise, C an (M, Nc) view with unit column stride.  `first`: overwrite C.  A / B may also be `None` with
+    explicit sizes (plan queries)."""
+    __slots__ = ("A", "B", "C", "S", "M", "Nc", "L", "a_ns", "a_rs", "b_ns", "b_rs", "alpha", "first")
+
+    def __init__(self, A, B, C, S, M, Nc, L, a_ns, a_rs, b_ns, b_rs, alpha=1.0, first=False):
+        self.A, self.B, self.C = A, B, C
+        self.S, self.M, self.Nc, self.L = int(S), int(M), int(Nc), int(L)
+        self.a_ns, self.a_rs, self.b_ns, self.b_rs = int(a_ns), int(a_rs), int(b_ns), int(b_rs)
+        self.alpha, self.first = float(alpha), bool(first)
+
+
+def _per_sample_descs(jobs: Sequence[PerSampleJob], check_tensors: bool = True):
+    arr = (_lib.curv_persample_desc * len(jobs))()
+    for d, j in zip(arr, jobs):
+        d.S, d.M, d.Nc, d.L = j.S, j.M, j.Nc, j.L
+        d.a_ns, d.a_rs, d.b_ns, d.b_rs = j.a_ns, j.a_rs, j.b_ns, j.b_rs
+        d.alpha, d.first = j.alpha, int(j.first)
+        d.c_rs = j.Nc
+        if check_tensors:
+            for t in (j.A, j.B, j.C):
+                if not t.is_cuda:
+                    raise RuntimeError("curvature_amd runs on MI355X only: got a CPU tensor (no CPU fallback)")
+                if t.dtype != torch.float32:
+                    raise RuntimeError(f"curvature_amd expects float32 tensors, got {t.dtype}")
+            if j.C.dim() != 2 or tuple(j.C.shape) != (j.M, j.Nc) or j.C.stride(1) != 1:
+                raise RuntimeError(f"per_sample_sq_accumulate: destination must be an ({j.M},{j.Nc}) view with unit "
+                                   f"column stride, got {tuple(j.C.shape)}")
+            a_need = (j.S - 1) * j.a_ns + (j.M - 1) * j.a_rs + j.L
+            b_need = (j.S - 1) * j.b_ns + (j.Nc - 1) * j.b_rs + j.L
+            if j.A.numel() < a_need or j.B.numel() < b_need:
+                raise RuntimeError("per_sample_sq_accumulate: an operand is smaller than its sizes and strides say")
+            d.A, d.B, d.C, d.c_rs = j.A.data_ptr(), j.B.data_ptr(), j.C.data_ptr(), j.C.stride(0)
+    return arr
+
+
+def per_sample_plan_flops(jobs: Sequence[PerSampleJob]) -> List[int]:
+    """Multiply-add FLOPs (2 per multiply-add) the plan executes per job (curv_persample_plan_flops, host only)."""
+    if not jobs:
+        return []
+    arr = _per_sample_descs(jobs, check_tensors=False)
+    out = (ctypes.c_longlong * len(jobs))()
+    _lib.check(_lib.lib().curv_persample_plan_flops(arr, len(jobs), out), "curv_persample_plan_flops")
+    return [int(v) for v in out]
+
+
+def per_sample_sq_accumulate(jobs: Sequence[PerSampleJob]) -> None:
+    """curv_persample_sq_accumulate over any number of products, on the current stream; slabs from `workspace`."""
+    if not jobs:
+        return
+    n = len(jobs)
+    arr = _per_sample_descs(jobs)
+    L = _lib.lib()
+    need = L.curv_persample_workspace_bytes(arr, n)
+    if need == 0:
+        _lib.check(_lib.ERR_INVALID, "curv_persample_workspace_bytes")
+    ws = workspace(need, jobs[0].C.device, "persample")
+    _lib.check(L.curv_persample_sq_accumulate(_lib.stream_ptr(), arr, n, ws.data_ptr(), ws.numel()),
+               "curv_persample_sq_accumulate")
+
+
+def per_sample_scratch(floats: Sequence[int], device) -> List[torch.Tensor]:
+    """One float32 buffer of each given size (0: None), carved 256-byte aligned out of the "persample_x" workspace: the
+    packed operands of one `update()`; valid until the next call."""
+    offs, at = [], 0
+    for f in floats:
+        offs.append(at)
+        at += (int(f) * 4 + 255) // 256 * 256
+    if at == 0:
+        return [None] * len(offs)
+    ws = workspace(at, device, "persample_x")
+    return [ws[o:o + int(f) * 4].view(torch.float32) if f else None for o, f in zip(offs, floats)]
+
+
 def rsqrt_affine(value: torch.Tensor, add: float, multiply: float, out: Optional[torch.Tensor] = None):
     _require_gpu(value, out)
     if out is None:

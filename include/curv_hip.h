@@ -452,6 +452,71 @@ typedef struct curv_sq_desc {
   int32_t first, reserved;
 } curv_sq_desc;
 int curv_sq_accumulate_batched(void* stream, const curv_sq_desc* descs, int n, double batch_size);
+
+/* ------------------------------------------------------------------------------------------------
+ * Exact per-sample Fisher for Diagonal and EFB at any batch size (csrc/persample.hip).
+ *
+ * curvatures.py:152 (Diagonal) and :427-434 (EFB) square the BATCH gradient [W.grad | b.grad] = sum_n P_n, with
+ * P_n = g_n X_n^T the share of sample n (g_n: the layer's grad_output of the sample as m x L, X_n: its unfolded input
+ * [+ ones row] as n_in x L).  That is the Fisher diagonal only at batch size 1.  These entry points compute the sum of
+ * the squares of the P_n themselves,
+ *     C[i][j] (+)= alpha * sum_{n < S} ( sum_{l < L} A[n*a_ns + i*a_rs + l] * B[n*b_ns + j*b_rs + l] )**2
+ * without ever writing a P_n: Diagonal's state with A = g, B = X; EFB's with A = U_G^T g, B = U_A^T X.
+ *
+ * A is S segments of M x L, B is S segments of Nc x L, both contiguous along l; segment strides (a_ns, b_ns) and row
+ * strides (a_rs, b_rs) are free (in floats; a row stride may be below L only for a single row, a segment stride may be
+ * 0), so grad_output (N, m, Ho*Wo) and the input of a 1x1 / stride-1 convolution (N, C, H*W) are read in place, as is
+ * a packed copy in (N, rows, Lp) or (rows, N, Lp) order.  C is M x Nc with row stride c_rs >= Nc; `first` != 0
+ * overwrites it.  fp32 MFMA with fp32 accumulation; deterministic (fixed-order sums, no atomics); the plan of an item
+ * follows from its own sizes only, so its bits do not depend on the other items of the call.  Enqueues on `stream`
+ * only, never waits on the host, allocates nothing (graph capture works).  An empty call is a no-op.
+ * l values at or behind L never enter a product (memory there may hold anything, NaN included), but the staging
+ * fetches whole 16-byte groups: where L is no multiple of 4 it may FETCH up to 12 bytes behind the end of an operand and
+ * discard them.  Pack such operands (below) when the bytes behind them may be unmapped.  Operand extents stay below
+ * 2^31 bytes (CURV_ERR_INVALID otherwise).
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct curv_persample_desc {
+  const float* A;
+  const float* B;
+  float* C;
+  long long a_ns, a_rs, b_ns, b_rs, c_rs;
+  int32_t S, M, Nc, L;
+  int32_t first;
+  float alpha;
+} curv_persample_desc;
+
+/* Device scratch needed by curv_persample_sq_accumulate for these items (bytes: one fp32 slab per output tile and range
+ * of samples); 0 with the error text set (naming the item) for invalid sizes.  Host only. */
+size_t curv_persample_workspace_bytes(const curv_persample_desc* descs, int n);
+/* Host only: the multiply-add FLOPs (2 per multiply-add) the plan executes per item, written to out[0 .. n): whole
+ * 128 x 128 tiles (64 x 128 where min(M, Nc) <= 64) over L padded to stages of 32 - at least the algorithmic
+ * 2 S M Nc L. */
+int curv_persample_plan_flops(const curv_persample_desc* descs, int n, long long* out);
+/* The products: an MFMA and a reduce launch per batch of up to 16 items.  The workspace must be 256-byte aligned.
+ * `descs` is a host array; it may be reused as soon as the call returns. */
+int curv_persample_sq_accumulate(void* stream, const curv_persample_desc* descs, int n, void* workspace,
+                                 size_t workspace_bytes);
+
+/* X of a layer, l-contiguous, into caller scratch `dst` - wherever the source cannot be read in place:
+ *   dst[(n*R + r)*Lp + l]   (rows_outer = 0)   or   dst[(r*N + n)*Lp + l]   (rows_outer != 0: one R x (N Lp) matrix)
+ * for r < R = C*kh*kw + has_bias, l < Lp, with L = Ho*Wo: row r = (c, a, b) is the implicit im2col of `src` (the
+ * reference's F.unfold, curvatures.py:329-330), the last row the ones of a biased layer (:333-335), and every l in
+ * [L, Lp) is written as 0 by the pack itself.  `src` is (N, C, H, W), or with channels_last != 0 (N, H, W, C): the
+ * (N, T, D) input of a Linear layer is C = D, H = T, W = 1, i.e. the transpose to D rows of T.  kh = kw = 1, stride 1,
+ * padding 0 is a plain copy with a zero tail (grad_output with L = 196 or 49).  Lp >= L, a multiple of 4; dst 16-byte
+ * aligned.  Never reads outside `src` (a masked gather reads src[0] and drops it).  Invalid geometry (kh = 0, sh = 0, an
+ * empty output) returns CURV_ERR_INVALID with the item named.  An empty call is a no-op. */
+typedef struct curv_persample_pack_desc {
+  const float* src;
+  float* dst;
+  int32_t N, C, H, W;
+  int32_t kh, kw, sh, sw, ph, pw;
+  int32_t has_bias;
+  int32_t channels_last;
+  int32_t rows_outer;
+  int32_t Lp;
+} curv_persample_pack_desc;
+int curv_persample_pack(void* stream, const curv_persample_pack_desc* descs, int n);
 /* v = max(v, 0) in place      curvatures.py:523 */
 int curv_clamp_min0(void* stream, float* v, long long count);
 /* out = sqrt(s*v)             curvatures.py:525 */
