@@ -109,50 +109,31 @@ def build(force: bool = False, verbose: bool = False) -> str:
     return LIB_PATH
 
 
+# What the convolution descriptors of include/curv_hip.h name alike, in the order they declare it
+_ENDS = [("src", ctypes.c_void_p), ("dst", ctypes.c_void_p)]
+_SOURCE = [(k, ctypes.c_int32) for k in ("N", "C", "H", "W")]
+_WINDOW = [(k, ctypes.c_int32) for k in ("kh", "kw", "sh", "sw", "ph", "pw")]
+_ENTRY = [("has_bias", ctypes.c_int32), ("first", ctypes.c_int32), ("scale", ctypes.c_float)]
+
+
 class curv_factor_desc(ctypes.Structure):
     """Mirror of ``curv_factor_desc`` in include/curv_hip.h."""
-    _fields_ = [
-        ("src", ctypes.c_void_p), ("dst", ctypes.c_void_p),
-        ("N", ctypes.c_int32), ("C", ctypes.c_int32), ("H", ctypes.c_int32), ("W", ctypes.c_int32),
-        ("kh", ctypes.c_int32), ("kw", ctypes.c_int32), ("sh", ctypes.c_int32), ("sw", ctypes.c_int32),
-        ("ph", ctypes.c_int32), ("pw", ctypes.c_int32),
-        ("has_bias", ctypes.c_int32), ("first", ctypes.c_int32),
-        ("scale", ctypes.c_float), ("path_hint", ctypes.c_int32),
-    ]
+    _fields_ = _ENDS + _SOURCE + _WINDOW + _ENTRY + [("path_hint", ctypes.c_int32)]
 
 
 class curv_group_factor_desc(ctypes.Structure):
     """Mirror of ``curv_group_factor_desc`` in include/curv_hip.h."""
-    _fields_ = [
-        ("src", ctypes.c_void_p), ("dst", ctypes.c_void_p),
-        ("N", ctypes.c_int32), ("C", ctypes.c_int32), ("H", ctypes.c_int32), ("W", ctypes.c_int32),
-        ("groups", ctypes.c_int32), ("kh", ctypes.c_int32), ("kw", ctypes.c_int32), ("sh", ctypes.c_int32),
-        ("sw", ctypes.c_int32), ("ph", ctypes.c_int32), ("pw", ctypes.c_int32),
-        ("has_bias", ctypes.c_int32), ("first", ctypes.c_int32), ("scale", ctypes.c_float),
-    ]
+    _fields_ = _ENDS + _SOURCE + [("groups", ctypes.c_int32)] + _WINDOW + _ENTRY
 
 
 class curv_convt_factor_desc(ctypes.Structure):
     """Mirror of ``curv_convt_factor_desc`` in include/curv_hip.h."""
-    _fields_ = [
-        ("src", ctypes.c_void_p), ("dst", ctypes.c_void_p),
-        ("N", ctypes.c_int32), ("C", ctypes.c_int32), ("H", ctypes.c_int32), ("W", ctypes.c_int32),
-        ("kh", ctypes.c_int32), ("kw", ctypes.c_int32), ("sh", ctypes.c_int32), ("sw", ctypes.c_int32),
-        ("ph", ctypes.c_int32), ("pw", ctypes.c_int32), ("Ho", ctypes.c_int32), ("Wo", ctypes.c_int32),
-        ("has_bias", ctypes.c_int32), ("first", ctypes.c_int32), ("scale", ctypes.c_float),
-    ]
+    _fields_ = _ENDS + _SOURCE + _WINDOW + [("Ho", ctypes.c_int32), ("Wo", ctypes.c_int32)] + _ENTRY
 
 
 class curv_factor16_desc(ctypes.Structure):
     """Mirror of ``curv_factor16_desc`` in include/curv_hip.h."""
-    _fields_ = [
-        ("src", ctypes.c_void_p), ("dst", ctypes.c_void_p),
-        ("N", ctypes.c_int32), ("C", ctypes.c_int32), ("H", ctypes.c_int32), ("W", ctypes.c_int32),
-        ("kh", ctypes.c_int32), ("kw", ctypes.c_int32), ("sh", ctypes.c_int32), ("sw", ctypes.c_int32),
-        ("ph", ctypes.c_int32), ("pw", ctypes.c_int32),
-        ("has_bias", ctypes.c_int32), ("first", ctypes.c_int32),
-        ("scale", ctypes.c_float), ("dtype", ctypes.c_int32),
-    ]
+    _fields_ = _ENDS + _SOURCE + _WINDOW + _ENTRY + [("dtype", ctypes.c_int32)]
 
 
 class curv_inv_desc(ctypes.Structure):
@@ -201,9 +182,8 @@ class curv_persample_desc(ctypes.Structure):
 
 class curv_persample_pack_desc(ctypes.Structure):
     """Mirror of ``curv_persample_pack_desc`` in include/curv_hip.h."""
-    _fields_ = [("src", ctypes.c_void_p), ("dst", ctypes.c_void_p)] + \
-               [(k, ctypes.c_int32) for k in ("N", "C", "H", "W", "kh", "kw", "sh", "sw", "ph", "pw", "has_bias",
-                                              "channels_last", "rows_outer", "Lp")]
+    _fields_ = _ENDS + _SOURCE + _WINDOW + \
+               [(k, ctypes.c_int32) for k in ("has_bias", "channels_last", "rows_outer", "Lp")]
 
 
 class curv_copy_desc(ctypes.Structure):

@@ -21,10 +21,7 @@
 // Against a dense im2col of the zero-stuffed input (dim^2 N Ho Wo multiply-adds), the phase Grams execute about
 // 1 / (sh sw)^2 of the products: each has 1 / (sh sw) of the rows and 1 / (sh sw) of the pixels.
 // Every launch goes on the caller's stream; nothing waits on the host or allocates, so the call can be captured.
-#include "common.h"
-
-#include <algorithm>
-#include <vector>
+#include "side_build.h"
 
 namespace curv {
 namespace {
@@ -102,12 +99,8 @@ void phase_descs(const curv_convt_factor_desc& d, const Plan& p, const float* sr
 }
 
 bool plan_of(const curv_convt_factor_desc& d, int index, Plan* p) {
-  if (d.N < 1 || d.C < 1 || d.H < 1 || d.W < 1 || d.kh < 1 || d.kw < 1 || d.sh < 1 || d.sw < 1 || d.ph < 0 ||
-      d.pw < 0) {
-    set_error("curv_kfac_convt: factor %d: invalid geometry (N %d C %d H %d W %d kernel %dx%d stride %dx%d padding %dx%d)",
-              index, d.N, d.C, d.H, d.W, d.kh, d.kw, d.sh, d.sw, d.ph, d.pw);
-    return false;
-  }
+  side::ConvGeom g;                      // the source side only: the output size is the caller's
+  if (!side::source_geom_of(d, "curv_kfac_convt", "factor", index, &g)) return false;
   const long long ho_min = (long long)(d.H - 1) * d.sh - 2LL * d.ph + d.kh;
   const long long wo_min = (long long)(d.W - 1) * d.sw - 2LL * d.pw + d.kw;
   if (ho_min < 1 || wo_min < 1 || d.Ho < ho_min || d.Ho >= ho_min + d.sh || d.Wo < wo_min || d.Wo >= wo_min + d.sw) {
@@ -122,7 +115,7 @@ bool plan_of(const curv_convt_factor_desc& d, int index, Plan* p) {
   }
   const long long n = (long long)d.C * d.kh * d.kw + (d.has_bias ? 1 : 0);
   const long long K = (long long)d.N * d.Ho * d.Wo;
-  if (n > (1LL << 20) || K >= (1LL << 31) || (long long)d.N * d.C * d.H * d.W >= (1LL << 40)) {
+  if (n > (1LL << 20) || K >= (1LL << 31)) {
     set_error("curv_kfac_convt: factor %d: too large (dim %lld, %lld output pixels)", index, n, K);
     return false;
   }
@@ -333,60 +326,37 @@ Layout layout_of(const std::vector<Plan>& plans) {
   return L;
 }
 
-bool plans_of(const curv_convt_factor_desc* descs, int n_factors, std::vector<Plan>* plans) {
-  plans->resize(n_factors);
-  for (int i = 0; i < n_factors; ++i)
-    if (!plan_of(descs[i], i, &(*plans)[i])) return false;
-  return true;
-}
-
 }  // namespace
 }  // namespace curv
 
 using namespace curv;
 
 extern "C" size_t curv_kfac_convt_workspace_bytes(const curv_convt_factor_desc* descs, int n_factors) {
-  if (n_factors <= 0) return 0;
-  if (!descs) {
-    set_error("curv_kfac_convt_workspace_bytes: null descriptors");
-    return 0;
-  }
-  std::vector<Plan> plans;
-  if (!plans_of(descs, n_factors, &plans)) return 0;
-  return std::max(layout_of(plans).total, CT_ALIGN);
+  // never 0 for valid descriptors: 0 reports an error
+  return side::workspace_bytes("curv_kfac_convt_workspace_bytes", descs, n_factors, plan_of,
+                               [](const std::vector<Plan>& plans) { return std::max(layout_of(plans).total, CT_ALIGN); });
 }
 
 extern "C" int curv_kfac_convt_plan_flops(const curv_convt_factor_desc* descs, int n_factors, long long* out) {
-  if (n_factors <= 0) return CURV_OK;
-  CURV_REQUIRE(descs && out, "curv_kfac_convt_plan_flops: null argument");
-  for (int i = 0; i < n_factors; ++i) {
-    Plan p;
-    if (!plan_of(descs[i], i, &p)) return CURV_ERR_INVALID;
-    out[i] = p.flops;
-  }
-  return CURV_OK;
+  return side::plan_flops("curv_kfac_convt_plan_flops", descs, n_factors, out, plan_of);
 }
 
 extern "C" int curv_kfac_convt_accumulate(void* stream_, const curv_convt_factor_desc* descs, int n_factors,
                                           void* workspace, size_t workspace_bytes) {
+  const char* const name = "curv_kfac_convt_accumulate";
   if (n_factors <= 0) return CURV_OK;
-  CURV_REQUIRE(descs != nullptr, "curv_kfac_convt_accumulate: null descriptors");
   hipStream_t stream = (hipStream_t)stream_;
   std::vector<Plan> plans;
-  if (!plans_of(descs, n_factors, &plans)) return CURV_ERR_INVALID;
-  for (int i = 0; i < n_factors; ++i)
-    CURV_REQUIRE(descs[i].src && descs[i].dst, "curv_kfac_convt_accumulate: factor %d: null src or dst", i);
+  if (!side::plans_of(name, descs, n_factors, plan_of, &plans)) return CURV_ERR_INVALID;
   const Layout L = layout_of(plans);
-  if (!workspace || workspace_bytes < L.total || (reinterpret_cast<uintptr_t>(workspace) & (CT_ALIGN - 1))) {
-    set_error("curv_kfac_convt_accumulate: workspace too small (%zu < %zu bytes) or not %zu-byte aligned",
-              workspace_bytes, L.total, CT_ALIGN);
-    return CURV_ERR_WORKSPACE;
-  }
+  int rc = side::require_src_dst(name, descs, n_factors);
+  if (rc == CURV_OK) rc = side::require_workspace(name, workspace, workspace_bytes, L.total, CT_ALIGN);
+  if (rc != CURV_OK) return rc;
   char* slabs = (char*)workspace;
   char* win = slabs + L.slabs;
   void* build_ws = win + L.wins;
   for (int i = 0; i < n_factors; ++i) {
-    const int rc = build_one(stream, descs[i], plans[i], slabs, win, build_ws, L.build);
+    rc = build_one(stream, descs[i], plans[i], slabs, win, build_ws, L.build);
     if (rc != CURV_OK) return rc;
   }
   return CURV_OK;

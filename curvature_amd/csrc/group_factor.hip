@@ -18,10 +18,7 @@
 //     depends on this factor's geometry alone.  One pass over the tensor buys the existing kernels' fp32 MFMA rate.
 // Every launch goes on the caller's stream and nothing waits on the host, so the call can be captured into a graph.
 // Narrow factor tables travel as kernel arguments (batches of GRP_BATCH factors): no descriptor upload.
-#include "common.h"
-
-#include <algorithm>
-#include <vector>
+#include "side_build.h"
 
 namespace curv {
 namespace {
@@ -43,14 +40,11 @@ struct GrpFactor {
   int K;                      // output pixels N Ho Wo
   int S;                      // slices
   int E;                      // partials per (group, slice)
-  int wg_base;                // first workgroup of this factor in the launch
+  int base;                   // first workgroup of this factor in the launch
   int step_n, step_oh, step_ow;   // GRP_THREADS pixels = step_n Ho Wo + step_oh Wo + step_ow
 };
 
-struct GrpBatch {
-  GrpFactor f[GRP_BATCH];
-  int count;
-};
+typedef side::ArgBatch<GrpFactor, GRP_BATCH> GrpBatch;
 
 struct Plan {
   int P, n, Ho, Wo, K, S, E;
@@ -77,23 +71,17 @@ void wide_descs(const curv_group_factor_desc& d, const Plan& p, const float* cop
 }
 
 bool plan_of(const curv_group_factor_desc& d, int index, Plan* p) {
-  if (d.N < 1 || d.C < 1 || d.H < 1 || d.W < 1 || d.groups < 1 || d.kh < 1 || d.kw < 1 || d.sh < 1 || d.sw < 1 ||
-      d.ph < 0 || d.pw < 0 || d.C % d.groups != 0) {
-    set_error("curv_kfac_group: factor %d: invalid geometry (N %d C %d H %d W %d groups %d kernel %dx%d stride %dx%d "
-              "padding %dx%d; C must be a multiple of groups)", index, d.N, d.C, d.H, d.W, d.groups, d.kh, d.kw, d.sh,
-              d.sw, d.ph, d.pw);
+  side::ConvGeom g;
+  if (!side::conv_geom_of(d, "curv_kfac_group", "factor", index, &g)) return false;
+  if (d.groups < 1 || d.C % d.groups != 0) {
+    set_error("curv_kfac_group: factor %d: C %d must be a multiple of groups %d", index, d.C, d.groups);
     return false;
   }
-  p->Ho = (d.H + 2 * d.ph - d.kh) / d.sh + 1;
-  p->Wo = (d.W + 2 * d.pw - d.kw) / d.sw + 1;
-  if (d.H + 2 * d.ph < d.kh || d.W + 2 * d.pw < d.kw || p->Ho < 1 || p->Wo < 1) {
-    set_error("curv_kfac_group: factor %d: kernel %dx%d larger than the padded %dx%d input", index, d.kh, d.kw,
-              d.H + 2 * d.ph, d.W + 2 * d.pw);
-    return false;
-  }
+  p->Ho = g.Ho;
+  p->Wo = g.Wo;
   long long K = (long long)d.N * p->Ho * p->Wo;
   long long P = (long long)(d.C / d.groups) * d.kh * d.kw;
-  if (K >= (1LL << 30) || P > 8192 || (long long)d.N * d.C * d.H * d.W >= (1LL << 40)) {
+  if (K >= (1LL << 30) || P > 8192) {
     set_error("curv_kfac_group: factor %d: too large (%lld output pixels, %lld patch rows)", index, K, P);
     return false;
   }
@@ -131,13 +119,6 @@ __device__ inline float wave_sum(float x) {
 #pragma unroll
   for (int off = 32; off >= 1; off >>= 1) x += __shfl_xor(x, off, 64);
   return x;
-}
-
-__device__ inline int find_factor(const GrpBatch& b, int block) {
-  int f = 0;
-  for (int i = 1; i < b.count; ++i)
-    if (block >= b.f[i].wg_base) f = i;
-  return f;
 }
 
 // Sums `acc` over the workgroup (butterfly in each wave, then the four waves in order) into out[0 .. E).
@@ -202,9 +183,9 @@ __global__ void __launch_bounds__(GRP_THREADS) group_gram_narrow_kernel(const Gr
   constexpr int T = P * (P + 1) / 2;
   constexpr int E = T + P;
   __shared__ float red[4][E];
-  const int fi = find_factor(batch, blockIdx.x);
-  const GrpFactor& F = batch.f[fi];
-  const int b = blockIdx.x - F.wg_base;
+  const int fi = side::owner_of(batch, (int)blockIdx.x);
+  const GrpFactor& F = batch.e[fi];
+  const int b = blockIdx.x - F.base;
   const int g = b / F.S, s = b - g * F.S;
   long long off[P];
   int ra[P], rb[P];
@@ -245,11 +226,11 @@ __global__ void __launch_bounds__(GRP_THREADS) group_major_copy_kernel(const flo
 // One thread per (group, entry of the n x n square); entries above the diagonal idle.  Workgroups of a factor:
 // G x ceil(n^2 / GRP_THREADS).
 __global__ void __launch_bounds__(GRP_THREADS) group_reduce_kernel(const GrpBatch batch) {
-  const int fi = find_factor(batch, blockIdx.x);
-  const GrpFactor& F = batch.f[fi];
+  const int fi = side::owner_of(batch, (int)blockIdx.x);
+  const GrpFactor& F = batch.e[fi];
   const int n = F.n, P = F.P, S = F.S;
   const int chunks = (n * n + GRP_THREADS - 1) / GRP_THREADS;
-  const int b = blockIdx.x - F.wg_base;
+  const int b = blockIdx.x - F.base;
   const int g = b / chunks;
   const int idx = (b - g * chunks) * GRP_THREADS + (int)threadIdx.x;
   if (idx >= n * n) return;
@@ -295,7 +276,7 @@ GrpFactor factor_of(const curv_group_factor_desc& d, const Plan& p, float* part)
   F.N = d.N; F.C = d.C; F.H = d.H; F.W = d.W; F.G = d.groups; F.cg = d.C / d.groups;
   F.kh = d.kh; F.kw = d.kw; F.sh = d.sh; F.sw = d.sw; F.ph = d.ph; F.pw = d.pw; F.Ho = p.Ho; F.Wo = p.Wo;
   F.P = p.P; F.n = p.n; F.has_bias = d.has_bias ? 1 : 0; F.first = d.first ? 1 : 0; F.scale = d.scale;
-  F.K = p.K; F.S = p.S; F.E = p.E; F.wg_base = 0;
+  F.K = p.K; F.S = p.S; F.E = p.E; F.base = 0;
   const int HoWo = p.Ho * p.Wo;
   F.step_n = GRP_THREADS / HoWo;
   const int rem = GRP_THREADS - F.step_n * HoWo;
@@ -308,29 +289,21 @@ GrpFactor factor_of(const curv_group_factor_desc& d, const Plan& p, float* part)
 // reduce pass (kind 1).
 int launch_batches(hipStream_t stream, const curv_group_factor_desc* descs, const Plan* plans, float* const* parts,
                    const int* idx, int count, int kind, int narrow_P) {
-  for (int at = 0; at < count; at += GRP_BATCH) {
-    GrpBatch b;
-    b.count = 0;
-    long long blocks = 0;
-    for (int k = at; k < count && k < at + GRP_BATCH; ++k) {
-      const int i = idx[k];
-      GrpFactor F = factor_of(descs[i], plans[i], parts[i]);
-      F.wg_base = (int)blocks;
-      blocks += blocks_of(descs[i], plans[i], kind);
-      b.f[b.count++] = F;
-    }
-    for (int k = b.count; k < GRP_BATCH; ++k) b.f[k] = b.f[0];
-    if (blocks >= (1LL << 31)) {
-      set_error("curv_kfac_group_accumulate: too many workgroups (%lld)", blocks);
-      return CURV_ERR_INVALID;
-    }
-    if (kind == 1)
-      hipLaunchKernelGGL(group_reduce_kernel, dim3((unsigned)blocks), dim3(GRP_THREADS), 0, stream, b);
-    else
-      kNarrow[narrow_P](stream, b, (int)blocks);
-    CURV_LAUNCH_CHECK();
-  }
-  return CURV_OK;
+  return side::for_arg_batches<GrpFactor, GRP_BATCH, 1>(
+      count, "curv_kfac_group_accumulate",
+      [&](int k, GrpFactor* F, long long* blocks) {
+        *F = factor_of(descs[idx[k]], plans[idx[k]], parts[idx[k]]);
+        blocks[0] = blocks_of(descs[idx[k]], plans[idx[k]], kind);
+      },
+      [](int, long long blocks) { return blocks; },
+      [&](const GrpBatch* b, const long long*, const unsigned* grid) {
+        if (kind == 1)
+          hipLaunchKernelGGL(group_reduce_kernel, dim3(grid[0]), dim3(GRP_THREADS), 0, stream, b[0]);
+        else
+          kNarrow[narrow_P](stream, b[0], (int)grid[0]);
+        CURV_LAUNCH_CHECK();
+        return CURV_OK;
+      });
 }
 
 // Wide factor: group-major copy into `copy`, then the ordinary build, one descriptor per group.
@@ -349,24 +322,18 @@ int build_wide(hipStream_t stream, const curv_group_factor_desc& d, const Plan& 
   return curv_kfac_accumulate(stream, sub.data(), d.groups, build_ws, build_bytes);
 }
 
-bool plans_of(const curv_group_factor_desc* descs, int n_factors, Plan* plans) {
-  for (int i = 0; i < n_factors; ++i)
-    if (!plan_of(descs[i], i, &plans[i])) return false;
-  return true;
-}
-
 // Scratch layout: the narrow factors' slice partials one after another, then ONE copy region and ONE build region that
 // the wide factors use in turn (their calls are ordered on the stream).
 struct Layout {
   size_t parts, copy, build, total;
 };
 
-Layout layout_of(const Plan* plans, int n_factors) {
+Layout layout_of(const std::vector<Plan>& plans) {
   Layout L{0, 0, 0, 0};
-  for (int i = 0; i < n_factors; ++i) {
-    L.parts += plans[i].part_bytes;
-    L.copy = std::max(L.copy, plans[i].copy_bytes);
-    L.build = std::max(L.build, align_up(plans[i].build_bytes, 256));
+  for (const Plan& p : plans) {
+    L.parts += p.part_bytes;
+    L.copy = std::max(L.copy, p.copy_bytes);
+    L.build = std::max(L.build, align_up(p.build_bytes, 256));
   }
   L.total = L.parts + L.copy + L.build;
   return L;
@@ -378,44 +345,27 @@ Layout layout_of(const Plan* plans, int n_factors) {
 using namespace curv;
 
 extern "C" size_t curv_kfac_group_workspace_bytes(const curv_group_factor_desc* descs, int n_factors) {
-  if (n_factors <= 0) return 0;
-  if (!descs) {
-    set_error("curv_kfac_group_workspace_bytes: null descriptors");
-    return 0;
-  }
-  std::vector<Plan> plans(n_factors);
-  if (!plans_of(descs, n_factors, plans.data())) return 0;
-  return layout_of(plans.data(), n_factors).total;
+  return side::workspace_bytes("curv_kfac_group_workspace_bytes", descs, n_factors, plan_of,
+                               [](const std::vector<Plan>& plans) { return layout_of(plans).total; });
 }
 
 extern "C" int curv_kfac_group_plan_flops(const curv_group_factor_desc* descs, int n_factors, long long* out) {
-  if (n_factors <= 0) return CURV_OK;
-  CURV_REQUIRE(descs && out, "curv_kfac_group_plan_flops: null argument");
-  for (int i = 0; i < n_factors; ++i) {
-    Plan p;
-    if (!plan_of(descs[i], i, &p)) return CURV_ERR_INVALID;
-    out[i] = p.flops;
-  }
-  return CURV_OK;
+  return side::plan_flops("curv_kfac_group_plan_flops", descs, n_factors, out, plan_of);
 }
 
 extern "C" int curv_kfac_group_accumulate(void* stream_, const curv_group_factor_desc* descs, int n_factors,
                                           void* workspace, size_t workspace_bytes) {
+  const char* const name = "curv_kfac_group_accumulate";
   if (n_factors <= 0) return CURV_OK;
-  CURV_REQUIRE(descs != nullptr, "curv_kfac_group_accumulate: null descriptors");
   hipStream_t stream = (hipStream_t)stream_;
-  std::vector<Plan> plans(n_factors);
+  std::vector<Plan> plans;
+  if (!side::plans_of(name, descs, n_factors, plan_of, &plans)) return CURV_ERR_INVALID;
+  const Layout L = layout_of(plans);
+  int rc = side::require_src_dst(name, descs, n_factors);
+  if (rc == CURV_OK) rc = side::require_workspace(name, workspace, workspace_bytes, L.total, GRP_SLOT_ALIGN);
+  if (rc != CURV_OK) return rc;
   std::vector<float*> parts(n_factors, nullptr);
   std::vector<int> idx(n_factors);
-  if (!plans_of(descs, n_factors, plans.data())) return CURV_ERR_INVALID;
-  for (int i = 0; i < n_factors; ++i)
-    CURV_REQUIRE(descs[i].src && descs[i].dst, "curv_kfac_group_accumulate: factor %d: null src or dst", i);
-  const Layout L = layout_of(plans.data(), n_factors);
-  if (!workspace || workspace_bytes < L.total || (reinterpret_cast<uintptr_t>(workspace) & (GRP_SLOT_ALIGN - 1))) {
-    set_error("curv_kfac_group_accumulate: workspace too small (%zu < %zu bytes) or not %zu-byte aligned",
-              workspace_bytes, L.total, GRP_SLOT_ALIGN);
-    return CURV_ERR_WORKSPACE;
-  }
   size_t at = 0;
   for (int i = 0; i < n_factors; ++i) {
     parts[i] = (float*)((char*)workspace + at);
@@ -423,19 +373,18 @@ extern "C" int curv_kfac_group_accumulate(void* stream_, const curv_group_factor
   }
   float* copy = (float*)((char*)workspace + L.parts);
   void* build_ws = (char*)workspace + L.parts + L.copy;
-  int rc = CURV_OK;
   // narrow: Gram passes (one class per patch size), then one reduce pass over all of them
   for (int P = 1; P <= GRP_NARROW_MAX && rc == CURV_OK; ++P) {
     int count = 0;
     for (int i = 0; i < n_factors; ++i)
       if (plans[i].narrow && plans[i].P == P) idx[count++] = i;
-    if (count) rc = launch_batches(stream, descs, plans.data(), parts.data(), idx.data(), count, 0, P);
+    rc = launch_batches(stream, descs, plans.data(), parts.data(), idx.data(), count, 0, P);
   }
   if (rc != CURV_OK) return rc;
   int count = 0;
   for (int i = 0; i < n_factors; ++i)
     if (plans[i].narrow) idx[count++] = i;
-  if (count) rc = launch_batches(stream, descs, plans.data(), parts.data(), idx.data(), count, 1, 0);
+  rc = launch_batches(stream, descs, plans.data(), parts.data(), idx.data(), count, 1, 0);
   // wide: one group-major copy and one ordinary build per factor, sharing the copy and build regions
   for (int i = 0; i < n_factors && rc == CURV_OK; ++i)
     if (!plans[i].narrow) rc = build_wide(stream, descs[i], plans[i], copy, build_ws, L.build);

@@ -20,10 +20,7 @@
 // The slicing and tiling of a factor follow from its own geometry, and every item and reduce thread reads only its own
 // factor's image and slabs: a factor's bits do not depend on the other factors of the call.  No atomics, no host
 // synchronisation, no device allocation (graph capture works).  Factor tables travel as kernel arguments.
-#include "common.h"
-
-#include <algorithm>
-#include <vector>
+#include "side_build.h"
 
 namespace curv {
 namespace {
@@ -62,13 +59,10 @@ struct H16Factor {
   int copy_rows;              // pack rows are plain 16-byte copies of the source (see h16_pack_kernel)
   float scale;
   unsigned short one;         // 1.0 in the source dtype
-  long long base;             // first thread group / item / reduce block of this factor in the launch
+  long long base;             // first pack thread / item / reduce block of this factor in the launch
 };
 
-struct H16Batch {
-  H16Factor f[H16_BATCH];
-  int count;
-};
+typedef side::ArgBatch<H16Factor, H16_BATCH> H16Batch;
 
 struct Plan {
   int Ho, Wo, rows, dim, P, T, K, Kp, stages, spi, S;
@@ -77,26 +71,17 @@ struct Plan {
 };
 
 bool plan_of(const curv_factor16_desc& d, int index, Plan* p) {
-  if (d.N < 1 || d.C < 1 || d.H < 1 || d.W < 1 || d.kh < 1 || d.kw < 1 || d.sh < 1 || d.sw < 1 || d.ph < 0 ||
-      d.pw < 0) {
-    set_error("curv_kfac16: factor %d: invalid geometry (N %d C %d H %d W %d kernel %dx%d stride %dx%d padding %dx%d)",
-              index, d.N, d.C, d.H, d.W, d.kh, d.kw, d.sh, d.sw, d.ph, d.pw);
-    return false;
-  }
+  side::ConvGeom g;
+  if (!side::conv_geom_of(d, "curv_kfac16", "factor", index, &g)) return false;
   if (d.dtype != CURV_DTYPE_BF16 && d.dtype != CURV_DTYPE_F16) {
     set_error("curv_kfac16: factor %d: unknown dtype %d (CURV_DTYPE_BF16 = 1, CURV_DTYPE_F16 = 2)", index, d.dtype);
     return false;
   }
-  if (d.H + 2 * d.ph < d.kh || d.W + 2 * d.pw < d.kw) {
-    set_error("curv_kfac16: factor %d: kernel %dx%d larger than the padded %dx%d input", index, d.kh, d.kw,
-              d.H + 2 * d.ph, d.W + 2 * d.pw);
-    return false;
-  }
-  p->Ho = (d.H + 2 * d.ph - d.kh) / d.sh + 1;
-  p->Wo = (d.W + 2 * d.pw - d.kw) / d.sw + 1;
+  p->Ho = g.Ho;
+  p->Wo = g.Wo;
   const long long K = (long long)d.N * p->Ho * p->Wo;
   const long long rows = (long long)d.C * d.kh * d.kw;
-  if (K > H16_K_MAX || rows > 65536 || (long long)d.N * d.C * d.H * d.W >= (1LL << 40)) {
+  if (K > H16_K_MAX || rows > 65536) {
     set_error("curv_kfac16: factor %d: too large (%lld columns, at most %lld; %lld rows, at most 65536)", index, K,
               H16_K_MAX, rows);
     return false;
@@ -118,17 +103,10 @@ bool plan_of(const curv_factor16_desc& d, int index, Plan* p) {
   return true;
 }
 
-__device__ inline int find_factor(const H16Batch& b, long long at) {
-  int f = 0;
-  for (int i = 1; i < b.count; ++i)
-    if (at >= b.f[i].base) f = i;
-  return f;
-}
-
 // Pack: one thread per 8 consecutive columns of one image row (one 16-byte store); threads of a factor R x Kp / 8.
 __global__ void __launch_bounds__(H16_THREADS) h16_pack_kernel(const H16Batch batch) {
   const long long t = (long long)blockIdx.x * H16_THREADS + threadIdx.x;
-  const H16Factor& F = batch.f[find_factor(batch, t)];
+  const H16Factor& F = batch.e[side::owner_of(batch, t)];
   const long long local = t - F.base;
   const int groups_per_row = F.Kp / H16_PACK_PER_THREAD;
   if (local >= (long long)F.P * H16_TM * groups_per_row) return;
@@ -206,7 +184,7 @@ __global__ void __launch_bounds__(H16_THREADS, 3) h16_syrk_kernel(const H16Batch
     item = ((j >> 5) * 8 + xcd) * 32 + (j & 31);
   }
   if (item >= items) return;
-  const H16Factor& F = batch.f[find_factor(batch, item)];
+  const H16Factor& F = batch.e[side::owner_of(batch, item)];
   const int local = (int)(item - F.base);
   const int slice = local / F.T;
   int tile = local - slice * F.T, ti = 0;
@@ -303,7 +281,7 @@ __global__ void __launch_bounds__(H16_THREADS, 3) h16_syrk_kernel(const H16Batch
 // Reduce: one thread per entry (r, c) of dst; it sums, in slice order, the slab entries of the upper-triangle position
 // (i, j) = (min, max), so dst[r][c] and dst[c][r] get the same bits.  Blocks of a factor: ceil(dim^2 / 256).
 __global__ void __launch_bounds__(H16_THREADS) h16_reduce_kernel(const H16Batch batch) {
-  const H16Factor& F = batch.f[find_factor(batch, blockIdx.x)];
+  const H16Factor& F = batch.e[side::owner_of(batch, (long long)blockIdx.x)];
   const long long idx = (blockIdx.x - F.base) * H16_THREADS + threadIdx.x;
   const int dim = F.dim;
   if (idx >= (long long)dim * dim) return;
@@ -346,49 +324,39 @@ long long units_of(const Plan& p, int kind) {
   return cdivll((long long)p.dim * p.dim, H16_THREADS);
 }
 
+// One pass over the factors `idx` (all of one dtype) in batches of H16_BATCH.
 int launch_pass(hipStream_t stream, const curv_factor16_desc* descs, const Plan* plans, char* const* regions,
                 const int* idx, int count, int kind) {
-  for (int at = 0; at < count; at += H16_BATCH) {
-    H16Batch b;
-    b.count = 0;
-    long long units = 0;
-    for (int k = at; k < count && k < at + H16_BATCH; ++k) {
-      const int i = idx[k];
-      H16Factor F = factor_of(descs[i], plans[i], regions[i]);
-      F.base = units;
-      units += units_of(plans[i], kind);
-      b.f[b.count++] = F;
-    }
-    for (int k = b.count; k < H16_BATCH; ++k) b.f[k] = b.f[0];
-    const long long blocks = kind == 0 ? cdivll(units, H16_THREADS) : kind == 1 ? cdivll(units, 256) * 256 : units;
-    if (blocks >= (1LL << 31)) {
-      set_error("curv_kfac16_accumulate: too many workgroups (%lld)", blocks);
-      return CURV_ERR_INVALID;
-    }
-    if (kind == 0) {
-      hipLaunchKernelGGL(h16_pack_kernel, dim3((unsigned)blocks), dim3(H16_THREADS), 0, stream, b);
-    } else if (kind == 1) {
-      if (descs[idx[at]].dtype == CURV_DTYPE_BF16)
-        hipLaunchKernelGGL(h16_syrk_kernel<CURV_DTYPE_BF16>, dim3((unsigned)blocks), dim3(H16_THREADS), 0, stream, b,
-                           units);
-      else
-        hipLaunchKernelGGL(h16_syrk_kernel<CURV_DTYPE_F16>, dim3((unsigned)blocks), dim3(H16_THREADS), 0, stream, b,
-                           units);
-    } else {
-      hipLaunchKernelGGL(h16_reduce_kernel, dim3((unsigned)blocks), dim3(H16_THREADS), 0, stream, b);
-    }
-    CURV_LAUNCH_CHECK();
-  }
-  return CURV_OK;
+  return side::for_arg_batches<H16Factor, H16_BATCH, 1>(
+      count, "curv_kfac16_accumulate",
+      [&](int k, H16Factor* F, long long* units) {
+        *F = factor_of(descs[idx[k]], plans[idx[k]], regions[idx[k]]);
+        units[0] = units_of(plans[idx[k]], kind);
+      },
+      [&](int, long long units) {
+        return kind == 0 ? cdivll(units, H16_THREADS) : kind == 1 ? cdivll(units, 256) * 256 : units;
+      },
+      [&](const H16Batch* b, const long long* units, const unsigned* grid) {
+        if (kind == 0)
+          hipLaunchKernelGGL(h16_pack_kernel, dim3(grid[0]), dim3(H16_THREADS), 0, stream, b[0]);
+        else if (kind == 1 && descs[idx[0]].dtype == CURV_DTYPE_BF16)
+          hipLaunchKernelGGL(h16_syrk_kernel<CURV_DTYPE_BF16>, dim3(grid[0]), dim3(H16_THREADS), 0, stream, b[0], units[0]);
+        else if (kind == 1)
+          hipLaunchKernelGGL(h16_syrk_kernel<CURV_DTYPE_F16>, dim3(grid[0]), dim3(H16_THREADS), 0, stream, b[0], units[0]);
+        else
+          hipLaunchKernelGGL(h16_reduce_kernel, dim3(grid[0]), dim3(H16_THREADS), 0, stream, b[0]);
+        CURV_LAUNCH_CHECK();
+        return CURV_OK;
+      });
 }
 
-bool plans_of(const curv_factor16_desc* descs, int n_factors, Plan* plans, size_t* total) {
-  *total = 0;
-  for (int i = 0; i < n_factors; ++i) {
-    if (!plan_of(descs[i], i, &plans[i])) return false;
-    *total += plans[i].img_bytes + align_up(plans[i].slab_bytes, 256);
-  }
-  return true;
+// Every factor has a region of its own: image, then slabs.
+size_t region_bytes(const Plan& p) { return p.img_bytes + align_up(p.slab_bytes, 256); }
+
+size_t bytes_of(const std::vector<Plan>& plans) {
+  size_t total = 0;
+  for (const Plan& p : plans) total += region_bytes(p);
+  return total;
 }
 
 }  // namespace
@@ -397,48 +365,28 @@ bool plans_of(const curv_factor16_desc* descs, int n_factors, Plan* plans, size_
 using namespace curv;
 
 extern "C" size_t curv_kfac16_workspace_bytes(const curv_factor16_desc* descs, int n_factors) {
-  if (n_factors <= 0) return 0;
-  if (!descs) {
-    set_error("curv_kfac16_workspace_bytes: null descriptors");
-    return 0;
-  }
-  std::vector<Plan> plans(n_factors);
-  size_t total;
-  if (!plans_of(descs, n_factors, plans.data(), &total)) return 0;
-  return total;
+  return side::workspace_bytes("curv_kfac16_workspace_bytes", descs, n_factors, plan_of, bytes_of);
 }
 
 extern "C" int curv_kfac16_plan_flops(const curv_factor16_desc* descs, int n_factors, long long* out) {
-  if (n_factors <= 0) return CURV_OK;
-  CURV_REQUIRE(descs && out, "curv_kfac16_plan_flops: null argument");
-  for (int i = 0; i < n_factors; ++i) {
-    Plan p;
-    if (!plan_of(descs[i], i, &p)) return CURV_ERR_INVALID;
-    out[i] = p.flops;
-  }
-  return CURV_OK;
+  return side::plan_flops("curv_kfac16_plan_flops", descs, n_factors, out, plan_of);
 }
 
 extern "C" int curv_kfac16_accumulate(void* stream_, const curv_factor16_desc* descs, int n_factors, void* workspace,
                                       size_t workspace_bytes) {
+  const char* const name = "curv_kfac16_accumulate";
   if (n_factors <= 0) return CURV_OK;
-  CURV_REQUIRE(descs != nullptr, "curv_kfac16_accumulate: null descriptors");
   hipStream_t stream = (hipStream_t)stream_;
-  std::vector<Plan> plans(n_factors);
-  size_t total;
-  if (!plans_of(descs, n_factors, plans.data(), &total)) return CURV_ERR_INVALID;
-  for (int i = 0; i < n_factors; ++i)
-    CURV_REQUIRE(descs[i].src && descs[i].dst, "curv_kfac16_accumulate: factor %d: null src or dst", i);
-  if (!workspace || workspace_bytes < total || (reinterpret_cast<uintptr_t>(workspace) & 255)) {
-    set_error("curv_kfac16_accumulate: workspace too small (%zu < %zu bytes) or not 256-byte aligned", workspace_bytes,
-              total);
-    return CURV_ERR_WORKSPACE;
-  }
+  std::vector<Plan> plans;
+  if (!side::plans_of(name, descs, n_factors, plan_of, &plans)) return CURV_ERR_INVALID;
+  int rc = side::require_src_dst(name, descs, n_factors);
+  if (rc == CURV_OK) rc = side::require_workspace(name, workspace, workspace_bytes, bytes_of(plans), 256);
+  if (rc != CURV_OK) return rc;
   std::vector<char*> regions(n_factors);
   size_t at = 0;
   for (int i = 0; i < n_factors; ++i) {
     regions[i] = (char*)workspace + at;
-    at += plans[i].img_bytes + align_up(plans[i].slab_bytes, 256);
+    at += region_bytes(plans[i]);
   }
   // SYRK batches hold one dtype; pack and reduce take the same batches
   std::vector<int> idx;
@@ -450,9 +398,8 @@ extern "C" int curv_kfac16_accumulate(void* stream_, const curv_factor16_desc* d
     return d.dtype == CURV_DTYPE_BF16;
   });
   for (int kind = 0; kind < 3; ++kind) {
-    int rc = CURV_OK;
-    if (split) rc = launch_pass(stream, descs, plans.data(), regions.data(), idx.data(), split, kind);
-    if (rc == CURV_OK && split < n_factors)
+    rc = launch_pass(stream, descs, plans.data(), regions.data(), idx.data(), split, kind);
+    if (rc == CURV_OK)
       rc = launch_pass(stream, descs, plans.data(), regions.data(), idx.data() + split, n_factors - split, kind);
     if (rc != CURV_OK) return rc;
   }

@@ -24,34 +24,19 @@
 // own product's operands and slabs, and all sums run in a fixed order without atomics: a product's bits are the same
 // alone, in a whole-model call and on a sharded rank.  No host synchronisation, no device allocation; tables travel as
 // kernel arguments.
-#include "common.h"
-
-#include <algorithm>
-#include <vector>
+#include "gemm_nt.h"
+#include "side_build.h"
 
 namespace curv {
 namespace {
 
 constexpr int PS_THREADS = 256;
-constexpr int PS_TM = 128;                     // tile rows / columns
-constexpr int PS_KC = 32;                      // l values per stage
-constexpr int PS_ROW_B = PS_KC * 4;            // 128 B per image row
-constexpr int PS_SLOTS = PS_KC / 4;            // 16-byte slots per row
-constexpr int PS_STEPS = PS_KC / 8;            // groups of 4 MFMA k-steps per lane half
-constexpr int PS_RPP = 1024 / PS_ROW_B;        // rows per 1 KiB wave-instruction
-constexpr int PS_PIECES = PS_TM / PS_RPP / 4;  // DMA pieces per wave and panel
-constexpr int PS_PANEL_B = PS_TM * PS_ROW_B;   // 16 KiB per panel per buffer
-constexpr int PS_NP = 2 * PS_PIECES;
-constexpr int PS_PPS = (PS_NP + PS_STEPS / 2 - 1) / (PS_STEPS / 2);
-static_assert(PS_PPS <= 4, "at most one DMA piece per MFMA group");
+constexpr int PS_TM = nt::TM;                  // tile rows / columns; the stage constants are nt:: (gemm_nt.h)
+static_assert(nt::KC == 32, "lane geometry and swizzle key below are those of stages of 32 l values");
 constexpr int PS_BATCH = 16;                   // products per launch (tables as kernel arguments)
 constexpr int PS_ITEMS_TARGET = 512;           // a product is cut into sample ranges until it has about this many items ...
 constexpr int PS_STAGES_MIN = 64;              // ... of at least 64 stages
 constexpr long long PS_BYTES_MAX = 1LL << 31;  // operand extents: 32-bit buffer offsets
-
-typedef __attribute__((address_space(1))) float gfl;
-typedef __attribute__((address_space(3))) void lds_void;
-typedef __attribute__((address_space(3))) char lds_char;
 
 struct PsProduct {
   const float* A;
@@ -69,10 +54,7 @@ struct PsProduct {
   long long base;              // first item / reduce block of this product in the launch
 };
 
-struct PsBatch {
-  PsProduct p[PS_BATCH];
-  int count;
-};
+typedef side::ArgBatch<PsProduct, PS_BATCH> PsBatch;
 
 struct Plan {
   int tiles_m, tiles_n, tiles, sps, spi, slices, half, swap;
@@ -111,7 +93,7 @@ bool plan_of(const curv_persample_desc& d, int index, Plan* p) {
     return false;
   }
   p->tiles = (int)tiles;
-  p->sps = cdiv(d.L, PS_KC);
+  p->sps = cdiv(d.L, nt::KC);
   // the split follows from the product's own sizes only
   const int want = std::max(1, cdiv(PS_ITEMS_TARGET, p->tiles));
   const int spi_min = cdiv(PS_STAGES_MIN, p->sps);
@@ -119,15 +101,8 @@ bool plan_of(const curv_persample_desc& d, int index, Plan* p) {
   p->slices = cdiv(d.S, p->spi);
   const int tile_rows = p->half ? PS_TM / 2 : PS_TM;
   p->slab_bytes = align_up((size_t)p->slices * p->tiles * tile_rows * PS_TM * sizeof(float), 256);
-  p->flops = 2LL * p->tiles * tile_rows * PS_TM * (long long)d.S * p->sps * PS_KC;
+  p->flops = 2LL * p->tiles * tile_rows * PS_TM * (long long)d.S * p->sps * nt::KC;
   return true;
-}
-
-__device__ inline int find_product(const PsBatch& b, long long at) {
-  int f = 0;
-  for (int i = 1; i < b.count; ++i)
-    if (at >= b.p[i].base) f = i;
-  return f;
 }
 
 // Product: one workgroup per item = (tile * slices + slice) of one product.  Full tiles (128 x 128): wave (wm, wn) computes
@@ -136,11 +111,11 @@ __device__ inline int find_product(const PsBatch& b, long long at) {
 // half the MFMAs per stage instead of a half-empty tile.  C/D map of a 32x32 block: column = lane & 31, row = (reg & 3) +
 // 8 (reg >> 2) + 4 (lane >> 5).
 template <bool HALF>
-__device__ __forceinline__ void ps_product_tile(const PsProduct& d, int local, lds_char* lds) {
+__device__ __forceinline__ void ps_product_tile(const PsProduct& d, int local, lds_char_t* lds) {
   constexpr int BN = HALF ? 1 : 2;                         // MFMA blocks per wave along the B side
   constexpr int TA = HALF ? PS_TM / 2 : PS_TM;             // A rows per tile
-  constexpr int PA = TA / PS_RPP / 4;                      // DMA pieces per wave: A panel, then the B panel's
-  constexpr int NP = PA + PS_PIECES;
+  constexpr int PA = TA / nt::RPP / 4;                     // DMA pieces per wave: A panel, then the B panel's
+  constexpr int NP = PA + nt::PIECES;
   const int slice = local % d.slices, tile = local / d.slices;
   const int tm = tile / d.tiles_n, tn = tile - tm * d.tiles_n;
   const int i0 = tm * TA, j0 = tn * PS_TM, M = d.M, N = d.Nc, L = d.L;
@@ -149,33 +124,33 @@ __device__ __forceinline__ void ps_product_tile(const PsProduct& d, int local, l
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int r32 = lane & 31, h = lane >> 5;
   const int row_a = HALF ? 0 : 64 * (wave >> 1), row_b = HALF ? 32 * wave : 64 * (wave & 1);
-  const int sps = (L + PS_KC - 1) / PS_KC;
+  const int sps = (L + nt::KC - 1) / nt::KC;
   const int n_stages = (s1 - s0) * sps;
 
   // DMA lane geometry (gemm_nt.h): piece `slot` of this wave covers panel rows 32 slot + 8 wave + (lane >> 3); the lane's
   // 16-byte group is XOR-swizzled by (row >> 1) & 7 on the source side
-  const int rsub = PS_RPP * wave + (lane >> 3);
-  const int g_lane = (lane & (PS_SLOTS - 1)) ^ ((rsub >> 1) & (PS_SLOTS - 1));
-  int voff_a[PA], voff_b[PS_PIECES];
+  const int rsub = nt::RPP * wave + (lane >> 3);
+  const int g_lane = (lane & (nt::SLOTS - 1)) ^ ((rsub >> 1) & (nt::SLOTS - 1));
+  int voff_a[PA], voff_b[nt::PIECES];
   // rows beyond the matrix are clamped to its last row (their results are never stored)
 #pragma unroll
   for (int p = 0; p < PA; ++p)
-    voff_a[p] = (int)(((long long)min(i0 + 4 * PS_RPP * p + rsub, M - 1) * d.a_rs + 4 * g_lane) * 4);
+    voff_a[p] = (int)(((long long)min(i0 + 4 * nt::RPP * p + rsub, M - 1) * d.a_rs + 4 * g_lane) * 4);
 #pragma unroll
-  for (int p = 0; p < PS_PIECES; ++p)
-    voff_b[p] = (int)(((long long)min(j0 + 4 * PS_RPP * p + rsub, N - 1) * d.b_rs + 4 * g_lane) * 4);
+  for (int p = 0; p < nt::PIECES; ++p)
+    voff_b[p] = (int)(((long long)min(j0 + 4 * nt::RPP * p + rsub, N - 1) * d.b_rs + 4 * g_lane) * 4);
   const __amdgpu_buffer_rsrc_t rsa = __builtin_amdgcn_make_buffer_rsrc((void*)d.A, 0, d.a_bytes, 0x00020000);
   const __amdgpu_buffer_rsrc_t rsb = __builtin_amdgcn_make_buffer_rsrc((void*)d.B, 0, d.b_bytes, 0x00020000);
 
-  unsigned addr_a[2][PS_STEPS], addr_b[BN][PS_STEPS];
+  unsigned addr_a[2][nt::STEPS], addr_b[BN][nt::STEPS];
 #pragma unroll
   for (int o = 0; o < 2 + BN; ++o) {
     const int R = (o < 2 ? row_a : row_b) + (o & 1) * 32 + r32;
-    const unsigned pbase = (o < 2) ? 0u : 2u * PS_PANEL_B;
-    const int rkey = (R >> 1) & (PS_SLOTS - 1);
+    const unsigned pbase = (o < 2) ? 0u : 2u * nt::PANEL_B;
+    const int rkey = (R >> 1) & (nt::SLOTS - 1);
 #pragma unroll
-    for (int j = 0; j < PS_STEPS; ++j) {
-      const unsigned at = pbase + R * PS_ROW_B + (((2 * j + h) ^ rkey) << 4);
+    for (int j = 0; j < nt::STEPS; ++j) {
+      const unsigned at = pbase + R * nt::ROW_B + (((2 * j + h) ^ rkey) << 4);
       if (o < 2) addr_a[o][j] = at;
       else addr_b[o - 2][j] = at;
     }
@@ -192,11 +167,11 @@ __device__ __forceinline__ void ps_product_tile(const PsProduct& d, int local, l
   auto issue = [&](int i, bool live, unsigned soff_a, unsigned soff_b, unsigned nbuf) {
     const bool b_side = i >= PA;
     const int slot = b_side ? i - PA : i;
-    const unsigned lbase = (b_side ? 2u * PS_PANEL_B : 0u) + nbuf + (unsigned)(PS_RPP * wave + 4 * PS_RPP * slot) * PS_ROW_B;
+    const unsigned lbase = (b_side ? 2u * nt::PANEL_B : 0u) + nbuf + (unsigned)(nt::RPP * wave + 4 * nt::RPP * slot) * nt::ROW_B;
     if (!b_side)
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rsa, (lds_void*)(lds + lbase), 16, live ? voff_a[slot] : OOB, soff_a, 0, 0);
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(rsa, (lds_void_t*)(lds + lbase), 16, live ? voff_a[slot] : OOB, soff_a, 0, 0);
     else
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rsb, (lds_void*)(lds + lbase), 16, live ? voff_b[slot] : OOB, soff_b, 0, 0);
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(rsb, (lds_void_t*)(lds + lbase), 16, live ? voff_b[slot] : OOB, soff_b, 0, 0);
   };
   int n = s0, kk = 0;                                       // sample and first l of the running stage
   if (n_stages > 0) {
@@ -208,13 +183,13 @@ __device__ __forceinline__ void ps_product_tile(const PsProduct& d, int local, l
   for (int t = 0; t < n_stages; ++t) {
     __builtin_amdgcn_s_waitcnt(0x0f70);        // vmcnt(0): this wave's DMA of stage t has landed
     __syncthreads();
-    int kn = kk + PS_KC, nn = n;
+    int kn = kk + nt::KC, nn = n;
     const bool sample_ends = kn >= L;
     if (sample_ends) { kn = 0; ++nn; }
     const bool live_n = t + 1 < n_stages && kn + 4 * g_lane < L;
     const unsigned sa = (unsigned)(((long long)nn * d.a_ns + kn) * 4), sb = (unsigned)(((long long)nn * d.b_ns + kn) * 4);
-    const unsigned buf = (unsigned)(t & 1) * PS_PANEL_B, nbuf = PS_PANEL_B - buf;
-    const bool tail_stage = kk + PS_KC > L;    // (the last stage of a sample whose L is no multiple of the stage)
+    const unsigned buf = (unsigned)(t & 1) * nt::PANEL_B, nbuf = nt::PANEL_B - buf;
+    const bool tail_stage = kk + nt::KC > L;    // (the last stage of a sample whose L is no multiple of the stage)
     auto rd = [&](unsigned at) { return *reinterpret_cast<const __attribute__((address_space(3))) f32x4*>(lds + at + buf); };
     f32x4 a[2], b[BN];
 #pragma unroll
@@ -222,7 +197,7 @@ __device__ __forceinline__ void ps_product_tile(const PsProduct& d, int local, l
 #pragma unroll
     for (int nb = 0; nb < BN; ++nb) b[nb] = rd(addr_b[nb][0]);
 #pragma unroll
-    for (int j = 0; j < PS_STEPS; ++j) {
+    for (int j = 0; j < nt::STEPS; ++j) {
       if (tail_stage) {
         asm volatile("; l tail" ::: "memory");             // keeps this a branch around a VALU-only block
 #pragma unroll
@@ -235,7 +210,7 @@ __device__ __forceinline__ void ps_product_tile(const PsProduct& d, int local, l
         }
       }
       f32x4 na[2], nb_[BN];
-      if (j + 1 < PS_STEPS) {
+      if (j + 1 < nt::STEPS) {
 #pragma unroll
         for (int m = 0; m < 2; ++m) na[m] = rd(addr_a[m][j + 1]);
 #pragma unroll
@@ -247,9 +222,9 @@ __device__ __forceinline__ void ps_product_tile(const PsProduct& d, int local, l
         for (int m = 0; m < 2; ++m)
 #pragma unroll
           for (int nb = 0; nb < BN; ++nb) c[m][nb] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[m][e], b[nb][e], c[m][nb], 0, 0, 0);
-        if (e < PS_PPS && PS_PPS * j + e < NP) issue(PS_PPS * j + e, live_n, sa, sb, nbuf);   // one piece behind a group of MFMAs
+        if (e < nt::PPS && nt::PPS * j + e < NP) issue(nt::PPS * j + e, live_n, sa, sb, nbuf);   // one piece behind a group of MFMAs
       }
-      if (j + 1 < PS_STEPS) {
+      if (j + 1 < nt::STEPS) {
 #pragma unroll
         for (int m = 0; m < 2; ++m) a[m] = na[m];
 #pragma unroll
@@ -286,17 +261,17 @@ __device__ __forceinline__ void ps_product_tile(const PsProduct& d, int local, l
 }
 
 __global__ void __launch_bounds__(PS_THREADS, 2) ps_product_kernel(const PsBatch batch) {
-  __shared__ __attribute__((aligned(1024))) char smem[4 * PS_PANEL_B];   // [buffer][A panel, B panel] as gemm_nt.h
-  const PsProduct& d = batch.p[find_product(batch, blockIdx.x)];
+  __shared__ __attribute__((aligned(1024))) char smem[4 * nt::PANEL_B];   // [buffer][A panel, B panel] as gemm_nt.h
+  const PsProduct& d = batch.e[side::owner_of(batch, (long long)blockIdx.x)];
   const int local = (int)(blockIdx.x - d.base);
-  if (d.half) ps_product_tile<true>(d, local, (lds_char*)smem);
-  else ps_product_tile<false>(d, local, (lds_char*)smem);
+  if (d.half) ps_product_tile<true>(d, local, (lds_char_t*)smem);
+  else ps_product_tile<false>(d, local, (lds_char_t*)smem);
 }
 
 // Reduce: one thread per entry (i, j) of C; it sums the slab entries of its tile in slice order, scales, writes or adds.
 // Blocks of a product: ceil(M Nc / 256).
 __global__ void __launch_bounds__(PS_THREADS) ps_reduce_kernel(const PsBatch batch) {
-  const PsProduct& d = batch.p[find_product(batch, blockIdx.x)];
+  const PsProduct& d = batch.e[side::owner_of(batch, (long long)blockIdx.x)];
   const int rows = d.swap ? d.Nc : d.M, cols = d.swap ? d.M : d.Nc;            // of C
   const long long idx = (blockIdx.x - d.base) * PS_THREADS + threadIdx.x;
   if (idx >= (long long)rows * cols) return;
@@ -326,31 +301,17 @@ struct PsPack {
   long long base;             // first thread of this layer in the launch
 };
 
-struct PsPackBatch {
-  PsPack p[PS_BATCH];
-  int count;
-};
+typedef side::ArgBatch<PsPack, PS_BATCH> PsPackBatch;
 
 bool pack_plan_of(const curv_persample_pack_desc& d, int index, PsPack* out) {
-  if (d.N < 1 || d.C < 1 || d.H < 1 || d.W < 1 || d.kh < 1 || d.kw < 1 || d.sh < 1 || d.sw < 1 || d.ph < 0 || d.pw < 0) {
-    set_error("curv_persample_pack: item %d: invalid geometry (N %d C %d H %d W %d kernel %dx%d stride %dx%d padding %dx%d)",
-              index, d.N, d.C, d.H, d.W, d.kh, d.kw, d.sh, d.sw, d.ph, d.pw);
-    return false;
-  }
-  if (d.H + 2 * d.ph < d.kh || d.W + 2 * d.pw < d.kw) {
-    set_error("curv_persample_pack: item %d: empty output (kernel %dx%d larger than the padded %dx%d input)", index, d.kh,
-              d.kw, d.H + 2 * d.ph, d.W + 2 * d.pw);
-    return false;
-  }
+  side::ConvGeom g;
+  if (!side::conv_geom_of(d, "curv_persample_pack", "item", index, &g)) return false;
   PsPack P;
   P.src = d.src; P.dst = d.dst;
-  P.N = d.N; P.C = d.C; P.H = d.H; P.W = d.W;
-  P.kh = d.kh; P.kw = d.kw; P.sh = d.sh; P.sw = d.sw; P.ph = d.ph; P.pw = d.pw;
-  P.Ho = (d.H + 2 * d.ph - d.kh) / d.sh + 1;
-  P.Wo = (d.W + 2 * d.pw - d.kw) / d.sw + 1;
+  P.N = g.N; P.C = g.C; P.H = g.H; P.W = g.W;
+  P.kh = g.kh; P.kw = g.kw; P.sh = g.sh; P.sw = g.sw; P.ph = g.ph; P.pw = g.pw; P.Ho = g.Ho; P.Wo = g.Wo;
   const long long rows = (long long)d.C * d.kh * d.kw, L = (long long)P.Ho * P.Wo;
-  if (rows > (1 << 24) || L > (1 << 24) || (long long)d.N * d.C * d.H * d.W >= (1LL << 40) ||
-      (long long)d.C * d.H * d.W >= (1LL << 31) || (long long)d.N * (rows + 1) * (d.Lp / 4 + 1) >= (1LL << 31)) {
+  if (rows > (1 << 24) || L > (1 << 24) || (long long)d.C * d.H * d.W >= (1LL << 31) || (long long)d.N * (rows + 1) * (d.Lp / 4 + 1) >= (1LL << 31)) {
     set_error("curv_persample_pack: item %d: too large (%lld rows, %lld positions)", index, rows, L);
     return false;
   }
@@ -374,10 +335,10 @@ bool pack_plan_of(const curv_persample_pack_desc& d, int index, PsPack* out) {
 // as zeros, a masked gather reads src[0] and drops it.
 __global__ void __launch_bounds__(PS_THREADS) ps_pack_kernel(const PsPackBatch batch) {
   const long long t = (long long)blockIdx.x * PS_THREADS + threadIdx.x;
-  int f = 0;
+  int f = 0;                                               // (side::owner_of, spelled out: the call compiles differently)
   for (int i = 1; i < batch.count; ++i)
-    if (t >= batch.p[i].base) f = i;
-  const PsPack& F = batch.p[f];
+    if (t >= batch.e[i].base) f = i;
+  const PsPack& F = batch.e[f];
   // 32-bit index arithmetic from here on (a layer has fewer than 2^31 threads and a sample fewer than 2^31 values:
   // pack_plan_of): the 64-bit divisions cost more than the copy
   const unsigned gpr = F.Lp / 4, R = F.R;
@@ -411,13 +372,29 @@ __global__ void __launch_bounds__(PS_THREADS) ps_pack_kernel(const PsPackBatch b
   *reinterpret_cast<float4*>(F.dst + out) = make_float4(v[0], v[1], v[2], v[3]);
 }
 
-bool plans_of(const curv_persample_desc* descs, int n, Plan* plans, size_t* total) {
-  *total = 0;
-  for (int i = 0; i < n; ++i) {
-    if (!plan_of(descs[i], i, &plans[i])) return false;
-    *total += plans[i].slab_bytes;
+size_t bytes_of(const std::vector<Plan>& plans) {
+  size_t total = 0;
+  for (const Plan& p : plans) total += p.slab_bytes;
+  return total;
+}
+
+// The product of `d` as the kernels see it, its slabs at `slabs`.
+PsProduct product_of(const curv_persample_desc& d, const Plan& p, float* slabs) {
+  PsProduct P;
+  P.A = d.A; P.B = d.B; P.C = d.C;
+  P.slabs = slabs;
+  P.a_ns = d.a_ns; P.a_rs = d.a_rs; P.b_ns = d.b_ns; P.b_rs = d.b_rs; P.c_rs = d.c_rs;
+  P.S = d.S; P.M = d.M; P.Nc = d.Nc; P.L = d.L;
+  P.a_bytes = (unsigned)p.a_bytes; P.b_bytes = (unsigned)p.b_bytes;
+  if (p.swap) {
+    std::swap(P.A, P.B); std::swap(P.a_ns, P.b_ns); std::swap(P.a_rs, P.b_rs); std::swap(P.M, P.Nc);
+    std::swap(P.a_bytes, P.b_bytes);
   }
-  return true;
+  P.tiles_n = p.tiles_n; P.tiles = p.tiles; P.spi = p.spi; P.slices = p.slices;
+  P.half = p.half; P.swap = p.swap;
+  P.first = d.first ? 1 : 0; P.alpha = d.alpha;
+  P.base = 0;
+  return P;
 }
 
 }  // namespace
@@ -426,109 +403,64 @@ bool plans_of(const curv_persample_desc* descs, int n, Plan* plans, size_t* tota
 using namespace curv;
 
 extern "C" size_t curv_persample_workspace_bytes(const curv_persample_desc* descs, int n) {
-  if (n <= 0) return 0;
-  if (!descs) {
-    set_error("curv_persample_workspace_bytes: null descriptors");
-    return 0;
-  }
-  std::vector<Plan> plans(n);
-  size_t total;
-  if (!plans_of(descs, n, plans.data(), &total)) return 0;
-  return total;
+  return side::workspace_bytes("curv_persample_workspace_bytes", descs, n, plan_of, bytes_of);
 }
 
 extern "C" int curv_persample_plan_flops(const curv_persample_desc* descs, int n, long long* out) {
-  if (n <= 0) return CURV_OK;
-  CURV_REQUIRE(descs && out, "curv_persample_plan_flops: null argument");
-  for (int i = 0; i < n; ++i) {
-    Plan p;
-    if (!plan_of(descs[i], i, &p)) return CURV_ERR_INVALID;
-    out[i] = p.flops;
-  }
-  return CURV_OK;
+  return side::plan_flops("curv_persample_plan_flops", descs, n, out, plan_of);
 }
 
 extern "C" int curv_persample_sq_accumulate(void* stream_, const curv_persample_desc* descs, int n, void* workspace,
                                             size_t workspace_bytes) {
+  const char* const name = "curv_persample_sq_accumulate";
   if (n <= 0) return CURV_OK;
-  CURV_REQUIRE(descs != nullptr, "curv_persample_sq_accumulate: null descriptors");
   hipStream_t stream = (hipStream_t)stream_;
-  std::vector<Plan> plans(n);
-  size_t total;
-  if (!plans_of(descs, n, plans.data(), &total)) return CURV_ERR_INVALID;
-  for (int i = 0; i < n; ++i)
-    CURV_REQUIRE(descs[i].A && descs[i].B && descs[i].C, "curv_persample_sq_accumulate: item %d: null operand", i);
-  if (!workspace || workspace_bytes < total || (reinterpret_cast<uintptr_t>(workspace) & 255)) {
-    set_error("curv_persample_sq_accumulate: workspace too small (%zu < %zu bytes) or not 256-byte aligned",
-              workspace_bytes, total);
-    return CURV_ERR_WORKSPACE;
-  }
+  std::vector<Plan> plans;
+  if (!side::plans_of(name, descs, n, plan_of, &plans)) return CURV_ERR_INVALID;
+  for (int i = 0; i < n; ++i) CURV_REQUIRE(descs[i].A && descs[i].B && descs[i].C, "%s: item %d: null operand", name, i);
+  const int rc = side::require_workspace(name, workspace, workspace_bytes, bytes_of(plans), 256);
+  if (rc != CURV_OK) return rc;
   size_t at = 0;
-  for (int first = 0; first < n; first += PS_BATCH) {
-    const int count = std::min(PS_BATCH, n - first);
-    PsBatch items, blocks;
-    items.count = blocks.count = count;
-    long long n_items = 0, n_blocks = 0;
-    for (int k = 0; k < count; ++k) {
-      const curv_persample_desc& d = descs[first + k];
-      const Plan& p = plans[first + k];
-      PsProduct P;
-      P.A = d.A; P.B = d.B; P.C = d.C;
-      P.slabs = (float*)((char*)workspace + at);
-      at += p.slab_bytes;
-      P.a_ns = d.a_ns; P.a_rs = d.a_rs; P.b_ns = d.b_ns; P.b_rs = d.b_rs; P.c_rs = d.c_rs;
-      P.S = d.S; P.M = d.M; P.Nc = d.Nc; P.L = d.L;
-      P.a_bytes = (unsigned)p.a_bytes; P.b_bytes = (unsigned)p.b_bytes;
-      if (p.swap) {
-        std::swap(P.A, P.B); std::swap(P.a_ns, P.b_ns); std::swap(P.a_rs, P.b_rs); std::swap(P.M, P.Nc);
-        std::swap(P.a_bytes, P.b_bytes);
-      }
-      P.tiles_n = p.tiles_n; P.tiles = p.tiles; P.spi = p.spi; P.slices = p.slices;
-      P.half = p.half; P.swap = p.swap;
-      P.first = d.first ? 1 : 0; P.alpha = d.alpha;
-      P.base = n_items;
-      items.p[k] = P;
-      P.base = n_blocks;
-      blocks.p[k] = P;
-      n_items += (long long)p.tiles * p.slices;
-      n_blocks += cdivll((long long)d.M * d.Nc, PS_THREADS);
-    }
-    for (int k = count; k < PS_BATCH; ++k) { items.p[k] = items.p[0]; blocks.p[k] = blocks.p[0]; }
-    CURV_REQUIRE(n_items < (1LL << 31) && n_blocks < (1LL << 31), "curv_persample_sq_accumulate: too many workgroups (%lld, %lld)",
-                 n_items, n_blocks);
-    hipLaunchKernelGGL(ps_product_kernel, dim3((unsigned)n_items), dim3(PS_THREADS), 0, stream, items);
-    CURV_LAUNCH_CHECK();
-    hipLaunchKernelGGL(ps_reduce_kernel, dim3((unsigned)n_blocks), dim3(PS_THREADS), 0, stream, blocks);
-    CURV_LAUNCH_CHECK();
-  }
-  return CURV_OK;
+  // one walk, two launches: lane 0 counts the items of the product launch, lane 1 the blocks of the reduce launch
+  return side::for_arg_batches<PsProduct, PS_BATCH, 2>(
+      n, name,
+      [&](int i, PsProduct* P, long long* units) {
+        *P = product_of(descs[i], plans[i], (float*)((char*)workspace + at));
+        at += plans[i].slab_bytes;
+        units[0] = (long long)plans[i].tiles * plans[i].slices;
+        units[1] = cdivll((long long)descs[i].M * descs[i].Nc, PS_THREADS);
+      },
+      [](int, long long units) { return units; },
+      [&](const PsBatch* b, const long long*, const unsigned* grid) {
+        hipLaunchKernelGGL(ps_product_kernel, dim3(grid[0]), dim3(PS_THREADS), 0, stream, b[0]);
+        CURV_LAUNCH_CHECK();
+        hipLaunchKernelGGL(ps_reduce_kernel, dim3(grid[1]), dim3(PS_THREADS), 0, stream, b[1]);
+        CURV_LAUNCH_CHECK();
+        return CURV_OK;
+      });
 }
 
 extern "C" int curv_persample_pack(void* stream_, const curv_persample_pack_desc* descs, int n) {
+  const char* const name = "curv_persample_pack";
   if (n <= 0) return CURV_OK;
-  CURV_REQUIRE(descs != nullptr, "curv_persample_pack: null descriptors");
+  CURV_REQUIRE(descs != nullptr, "%s: null descriptors", name);
   hipStream_t stream = (hipStream_t)stream_;
   std::vector<PsPack> packs(n);
   for (int i = 0; i < n; ++i) {
     if (!pack_plan_of(descs[i], i, &packs[i])) return CURV_ERR_INVALID;
     CURV_REQUIRE(descs[i].src && descs[i].dst && (reinterpret_cast<uintptr_t>(descs[i].dst) & 15) == 0,
-                 "curv_persample_pack: item %d: null src or dst, or dst not 16-byte aligned", i);
+                 "%s: item %d: null src or dst, or dst not 16-byte aligned", name, i);
   }
-  for (int first = 0; first < n; first += PS_BATCH) {
-    const int count = std::min(PS_BATCH, n - first);
-    PsPackBatch b;
-    b.count = count;
-    long long threads = 0;
-    for (int k = 0; k < count; ++k) {
-      b.p[k] = packs[first + k];
-      b.p[k].base = threads;
-      threads += (long long)b.p[k].N * b.p[k].R * (b.p[k].Lp / 4);
-    }
-    for (int k = count; k < PS_BATCH; ++k) b.p[k] = b.p[0];
-    const long long blocks = cdivll(threads, PS_THREADS);
-    CURV_REQUIRE(blocks < (1LL << 31), "curv_persample_pack: too many workgroups (%lld)", blocks);
-    hipLaunchKernelGGL(ps_pack_kernel, dim3((unsigned)blocks), dim3(PS_THREADS), 0, stream, b);
-    CURV_LAUNCH_CHECK();
-  }
-  return CURV_OK;
+  return side::for_arg_batches<PsPack, PS_BATCH, 1>(
+      n, name,
+      [&](int i, PsPack* P, long long* threads) {
+        *P = packs[i];
+        threads[0] = (long long)P->N * P->R * (P->Lp / 4);
+      },
+      [](int, long long threads) { return cdivll(threads, PS_THREADS); },
+      [&](const PsPackBatch* b, const long long*, const unsigned* grid) {
+        hipLaunchKernelGGL(ps_pack_kernel, dim3(grid[0]), dim3(PS_THREADS), 0, stream, b[0]);
+        CURV_LAUNCH_CHECK();
+        return CURV_OK;
+      });
 }

@@ -84,16 +84,25 @@ def release_workspaces() -> None:
 _kfac_last = {}                        # thread ident -> the "kfac" workspace its last curv_kfac_accumulate call used
 
 
-class FactorJob:
-    """One Kronecker-factor accumulation: dst (+)= scale * unfold(src) unfold(src)^T.  `src` may also be just its shape
-    (plan queries)."""
-    __slots__ = ("src", "dst", "kernel", "stride", "padding", "has_bias", "scale", "first", "path_hint")
+class _ConvJob:
+    """What the four factor jobs share: source and destination, the convolution geometry, and how the product enters the
+    destination.  Every subclass adds one field of its own."""
+    __slots__ = ("src", "dst", "kernel", "stride", "padding", "has_bias", "scale", "first")
 
-    def __init__(self, src, dst, kernel=(1, 1), stride=(1, 1), padding=(0, 0), has_bias=False,
-                 scale=1.0, first=False, path_hint=0):
+    def _set(self, src, dst, kernel, stride, padding, has_bias, scale, first):
         self.src, self.dst = src, dst
         self.kernel, self.stride, self.padding = tuple(kernel), tuple(stride), tuple(padding)
         self.has_bias, self.scale, self.first = bool(has_bias), float(scale), bool(first)
+
+
+class FactorJob(_ConvJob):
+    """One Kronecker-factor accumulation: dst (+)= scale * unfold(src) unfold(src)^T.  `src` may also be just its shape
+    (plan queries)."""
+    __slots__ = ("path_hint",)
+
+    def __init__(self, src, dst, kernel=(1, 1), stride=(1, 1), padding=(0, 0), has_bias=False,
+                 scale=1.0, first=False, path_hint=0):
+        self._set(src, dst, kernel, stride, padding, has_bias, scale, first)
         self.path_hint = int(path_hint)            # _lib.PATH_*: which launch form the UNSHARDED model takes
 
 
@@ -104,29 +113,68 @@ def small_path_flop(dim: int, K: int) -> float:
     return 2.0 * 1024.0 * (nb * (nb + 1) // 2) * float(K)
 
 
+def _set_geometry(d, shape, kernel, stride, padding, has_bias) -> None:
+    """The geometry fields every convolution descriptor names alike."""
+    d.N, d.C, d.H, d.W = map(int, shape)
+    d.kh, d.kw = kernel
+    d.sh, d.sw = stride
+    d.ph, d.pw = padding
+    d.has_bias = int(has_bias)
+
+
+def _fill_desc(d, j, check_tensors: bool, flat_ok: bool = False, groups: Optional[int] = None,
+               source: str = "factor source must be (N,C,H,W) or (N,C)") -> None:
+    """Descriptor `d` of any factor build from job `j`: the source as (N, C, H, W) (`flat_ok`: an (N, C) one as
+    (N, C, 1, 1)), geometry, `has_bias`, `first`, `scale`; with `check_tensors` also the destination shape, (dim, dim) or
+    (groups, dim, dim), and the two addresses.  The caller checks the tensors themselves and adds its own field."""
+    shape = tuple(j.src.shape) if isinstance(j.src, torch.Tensor) else tuple(j.src)
+    if flat_ok and len(shape) == 2:
+        shape += (1, 1)
+    if len(shape) != 4:
+        raise RuntimeError(source)
+    if check_tensors:
+        dim = shape[1] // (groups or 1) * j.kernel[0] * j.kernel[1] + int(j.has_bias)
+        want = (dim, dim) if groups is None else (groups, dim, dim)
+        if shape[1] % (groups or 1) or tuple(j.dst.shape) != want:
+            raise RuntimeError(f"{'factor' if groups is None else 'grouped factor'} destination must be "
+                               f"({','.join(map(str, want))}), got {tuple(j.dst.shape)}")
+        d.src, d.dst = j.src.data_ptr(), j.dst.data_ptr()
+    _set_geometry(d, shape, j.kernel, j.stride, j.padding, j.has_bias)
+    d.first, d.scale = int(j.first), j.scale
+
+
+def _all_tensors(jobs) -> bool:
+    return all(isinstance(j.src, torch.Tensor) for j in jobs)
+
+
+def _plan_flops(name: str, arr, n: int) -> List[int]:
+    """``<name>(arr, n, out)``: one FLOP count per descriptor."""
+    out = (ctypes.c_longlong * n)()
+    _lib.check(getattr(_lib.lib(), name)(arr, n, out), name)
+    return [int(v) for v in out]
+
+
+def _run_build(bytes_name: str, name: str, arr, n: int, device, tag: str, events=None) -> None:
+    """A side build on the current stream: ``<bytes_name>(arr, n)`` bytes of scratch (0: the library refused the
+    descriptors) from `workspace(tag)`, then ``<name>``; `events` = (start, stop) ``torch.cuda.Event``s around it."""
+    L = _lib.lib()
+    need = getattr(L, bytes_name)(arr, n)
+    if need == 0:
+        _lib.check(_lib.ERR_INVALID, bytes_name)
+    ws = workspace(need, device, tag)
+    if events is not None:
+        events[0].record()
+    _lib.check(getattr(L, name)(_lib.stream_ptr(), arr, n, ws.data_ptr(), ws.numel()), name)
+    if events is not None:
+        events[1].record()
+
+
 def _factor_descs(jobs: Sequence[FactorJob], check_tensors: bool = True):
-    n = len(jobs)
-    arr = (curv_factor_desc * n)()
+    arr = (curv_factor_desc * len(jobs))()
     for d, j in zip(arr, jobs):
         if check_tensors:
             _require_gpu(j.src, j.dst)
-        shape = tuple(j.src.shape) if check_tensors else tuple(j.src)
-        if len(shape) == 4:
-            N, C, H, W = shape
-        elif len(shape) == 2:
-            (N, C), H, W = shape, 1, 1
-        else:
-            raise RuntimeError("factor source must be (N,C,H,W) or (N,C)")
-        if check_tensors:
-            dim = C * j.kernel[0] * j.kernel[1] + int(j.has_bias)
-            if tuple(j.dst.shape) != (dim, dim):
-                raise RuntimeError(f"factor destination must be ({dim},{dim}), got {tuple(j.dst.shape)}")
-            d.src, d.dst = j.src.data_ptr(), j.dst.data_ptr()
-        d.N, d.C, d.H, d.W = int(N), int(C), int(H), int(W)
-        d.kh, d.kw = j.kernel
-        d.sh, d.sw = j.stride
-        d.ph, d.pw = j.padding
-        d.has_bias, d.first, d.scale = int(j.has_bias), int(j.first), j.scale
+        _fill_desc(d, j, check_tensors, flat_ok=True)
         d.path_hint = getattr(j, "path_hint", 0)
     return arr
 
@@ -139,7 +187,7 @@ def kfac_path_for(factors) -> int:
     jobs = [f if isinstance(f, FactorJob) else FactorJob(f[:4], None, *f[4:]) for f in factors]
     if not jobs:
         return _lib.PATH_GROUPED
-    arr = _factor_descs(jobs, check_tensors=all(isinstance(j.src, torch.Tensor) for j in jobs))
+    arr = _factor_descs(jobs, check_tensors=_all_tensors(jobs))
     return int(_lib.lib().curv_kfac_path_for(arr, len(jobs)))
 
 
@@ -152,7 +200,7 @@ def kfac_plan_flops(jobs: Sequence[FactorJob]) -> List[int]:
     be a tensor or just its shape (host only)."""
     if not jobs:
         return []
-    arr = _factor_descs(jobs, check_tensors=all(isinstance(j.src, torch.Tensor) for j in jobs))
+    arr = _factor_descs(jobs, check_tensors=_all_tensors(jobs))
     out = (ctypes.c_longlong * (PLAN_INFO_FIELDS * len(jobs)))()
     _lib.check(_lib.lib().curv_kfac_plan_info(arr, len(jobs), out), "curv_kfac_plan_info")
     return [int(out[PLAN_INFO_FIELDS * i + PLAN_INFO_FIELDS - 1]) for i in range(len(jobs))]
@@ -170,7 +218,7 @@ def kfac_accumulate(jobs: Sequence[FactorJob], events=None) -> None:
     L = _lib.lib()
     need = L.curv_kfac_workspace_bytes(arr, n)
     if need == 0:
-        _lib.check(2, "curv_kfac_workspace_bytes")
+        _lib.check(_lib.ERR_INVALID, "curv_kfac_workspace_bytes")
     ws = workspace(need, jobs[0].src.device, "kfac")
     # the "kfac" workspaces are written by this function only: if this thread's previous call used this very buffer,
     # its head still holds the descriptor table of that call and unchanged argument blocks need no second upload
@@ -188,18 +236,16 @@ def kfac_accumulate(jobs: Sequence[FactorJob], events=None) -> None:
 _HALF_DTYPES = {torch.bfloat16: _lib.DTYPE_BF16, torch.float16: _lib.DTYPE_F16}
 
 
-class HalfFactorJob:
+class HalfFactorJob(_ConvJob):
     """A Kronecker-factor accumulation from a bf16 / fp16 source (what autocast hands the hooks) into an fp32 factor:
     dst (+)= scale * unfold(src) unfold(src)^T, built on the bf16 / fp16 MFMA with fp32 accumulation
     (curv_kfac16_accumulate).  Same fields as `FactorJob`; there is no path hint: a factor's plan is its own.
     `src` may also be just its shape plus ``dtype`` (plan queries)."""
-    __slots__ = ("src", "dst", "kernel", "stride", "padding", "has_bias", "scale", "first", "dtype")
+    __slots__ = ("dtype",)
 
     def __init__(self, src, dst, kernel=(1, 1), stride=(1, 1), padding=(0, 0), has_bias=False, scale=1.0,
                  first=False, dtype=None):
-        self.src, self.dst = src, dst
-        self.kernel, self.stride, self.padding = tuple(kernel), tuple(stride), tuple(padding)
-        self.has_bias, self.scale, self.first = bool(has_bias), float(scale), bool(first)
+        self._set(src, dst, kernel, stride, padding, has_bias, scale, first)
         self.dtype = src.dtype if isinstance(src, torch.Tensor) else dtype
 
 
@@ -208,28 +254,15 @@ def _half_descs(jobs: Sequence[HalfFactorJob], check_tensors: bool = True):
     for d, j in zip(arr, jobs):
         if j.dtype not in _HALF_DTYPES:
             raise RuntimeError(f"half-precision factor source must be bfloat16 or float16, got {j.dtype}")
-        shape = tuple(j.src.shape) if isinstance(j.src, torch.Tensor) else tuple(j.src)
-        if len(shape) == 4:
-            N, C, H, W = shape
-        elif len(shape) == 2:
-            (N, C), H, W = shape, 1, 1
-        else:
-            raise RuntimeError("factor source must be (N,C,H,W) or (N,C)")
         if check_tensors:
+            if len(j.src.shape) not in (2, 4):
+                raise RuntimeError("factor source must be (N,C,H,W) or (N,C)")
             if not (j.src.is_cuda and j.dst.is_cuda):
                 raise RuntimeError("curvature_amd runs on MI355X only: got a CPU tensor (no CPU fallback)")
             if not j.src.is_contiguous():
                 raise RuntimeError("curvature_amd expects contiguous tensors")
             _require_gpu(j.dst)
-            dim = C * j.kernel[0] * j.kernel[1] + int(j.has_bias)
-            if tuple(j.dst.shape) != (dim, dim):
-                raise RuntimeError(f"factor destination must be ({dim},{dim}), got {tuple(j.dst.shape)}")
-            d.src, d.dst = j.src.data_ptr(), j.dst.data_ptr()
-        d.N, d.C, d.H, d.W = int(N), int(C), int(H), int(W)
-        d.kh, d.kw = j.kernel
-        d.sh, d.sw = j.stride
-        d.ph, d.pw = j.padding
-        d.has_bias, d.first, d.scale = int(j.has_bias), int(j.first), j.scale
+        _fill_desc(d, j, check_tensors, flat_ok=True)
         d.dtype = _HALF_DTYPES[j.dtype]
     return arr
 
@@ -239,10 +272,7 @@ def kfac_half_plan_flops(jobs: Sequence[HalfFactorJob]) -> List[int]:
     every 128 x 128 tile on and above the diagonal over K padded to 16."""
     if not jobs:
         return []
-    arr = _half_descs(jobs, check_tensors=all(isinstance(j.src, torch.Tensor) for j in jobs))
-    out = (ctypes.c_longlong * len(jobs))()
-    _lib.check(_lib.lib().curv_kfac16_plan_flops(arr, len(jobs), out), "curv_kfac16_plan_flops")
-    return [int(v) for v in out]
+    return _plan_flops("curv_kfac16_plan_flops", _half_descs(jobs, check_tensors=_all_tensors(jobs)), len(jobs))
 
 
 def kfac_accumulate_half(jobs: Sequence[HalfFactorJob], events=None) -> None:
@@ -251,30 +281,19 @@ def kfac_accumulate_half(jobs: Sequence[HalfFactorJob], events=None) -> None:
     stop) ``torch.cuda.Event``s (enable_timing) are recorded around the whole build."""
     if not jobs:
         return
-    n = len(jobs)
-    arr = _half_descs(jobs)
-    L = _lib.lib()
-    need = L.curv_kfac16_workspace_bytes(arr, n)
-    if need == 0:
-        _lib.check(_lib.ERR_INVALID, "curv_kfac16_workspace_bytes")
-    ws = workspace(need, jobs[0].src.device, "kfac_half")
-    if events is not None:
-        events[0].record()
-    _lib.check(L.curv_kfac16_accumulate(_lib.stream_ptr(), arr, n, ws.data_ptr(), ws.numel()), "curv_kfac16_accumulate")
-    if events is not None:
-        events[1].record()
+    _run_build("curv_kfac16_workspace_bytes", "curv_kfac16_accumulate", _half_descs(jobs), len(jobs),
+               jobs[0].src.device, "kfac_half", events)
 
 
-class GroupFactorJob:
+class GroupFactorJob(_ConvJob):
     """The stacked Kronecker factors of a grouped convolution: dst[g] (+)= scale * unfold(src_g) unfold(src_g)^T, src_g
     the g-th of `groups` equal channel slices of src (curv_kfac_group_accumulate)."""
-    __slots__ = ("src", "dst", "groups", "kernel", "stride", "padding", "has_bias", "scale", "first")
+    __slots__ = ("groups",)
 
     def __init__(self, src, dst, groups, kernel=(1, 1), stride=(1, 1), padding=(0, 0), has_bias=False, scale=1.0,
                  first=False):
-        self.src, self.dst, self.groups = src, dst, int(groups)
-        self.kernel, self.stride, self.padding = tuple(kernel), tuple(stride), tuple(padding)
-        self.has_bias, self.scale, self.first = bool(has_bias), float(scale), bool(first)
+        self._set(src, dst, kernel, stride, padding, has_bias, scale, first)
+        self.groups = int(groups)
 
 
 def _group_descs(jobs: Sequence[GroupFactorJob], check_tensors: bool = True):
@@ -282,19 +301,8 @@ def _group_descs(jobs: Sequence[GroupFactorJob], check_tensors: bool = True):
     for d, j in zip(arr, jobs):
         if check_tensors:
             _require_gpu(j.src, j.dst)
-            if j.src.dim() != 4:
-                raise RuntimeError("grouped factor source must be (N,C,H,W)")
-        N, C, H, W = j.src.shape if check_tensors else j.src
-        if check_tensors:
-            dim = C // j.groups * j.kernel[0] * j.kernel[1] + int(j.has_bias)
-            if C % j.groups or tuple(j.dst.shape) != (j.groups, dim, dim):
-                raise RuntimeError(f"grouped factor destination must be ({j.groups},{dim},{dim}), got {tuple(j.dst.shape)}")
-            d.src, d.dst = j.src.data_ptr(), j.dst.data_ptr()
-        d.N, d.C, d.H, d.W, d.groups = int(N), int(C), int(H), int(W), j.groups
-        d.kh, d.kw = j.kernel
-        d.sh, d.sw = j.stride
-        d.ph, d.pw = j.padding
-        d.has_bias, d.first, d.scale = int(j.has_bias), int(j.first), j.scale
+        _fill_desc(d, j, check_tensors, groups=j.groups, source="grouped factor source must be (N,C,H,W)")
+        d.groups = j.groups
     return arr
 
 
@@ -303,10 +311,7 @@ def kfac_group_plan_flops(jobs: Sequence[GroupFactorJob]) -> List[int]:
     only).  `job.src` may be a tensor or just its (N, C, H, W) shape."""
     if not jobs:
         return []
-    arr = _group_descs(jobs, check_tensors=all(isinstance(j.src, torch.Tensor) for j in jobs))
-    out = (ctypes.c_longlong * len(jobs))()
-    _lib.check(_lib.lib().curv_kfac_group_plan_flops(arr, len(jobs), out), "curv_kfac_group_plan_flops")
-    return [int(v) for v in out]
+    return _plan_flops("curv_kfac_group_plan_flops", _group_descs(jobs, check_tensors=_all_tensors(jobs)), len(jobs))
 
 
 def kfac_accumulate_groups(jobs: Sequence[GroupFactorJob], events=None) -> None:
@@ -315,33 +320,20 @@ def kfac_accumulate_groups(jobs: Sequence[GroupFactorJob], events=None) -> None:
     `events` = (start, stop) ``torch.cuda.Event``s (enable_timing) are recorded around the whole build."""
     if not jobs:
         return
-    n = len(jobs)
-    arr = _group_descs(jobs)
-    L = _lib.lib()
-    need = L.curv_kfac_group_workspace_bytes(arr, n)
-    if need == 0:
-        _lib.check(_lib.ERR_INVALID, "curv_kfac_group_workspace_bytes")
-    ws = workspace(need, jobs[0].src.device, "kfac_groups")
-    if events is not None:
-        events[0].record()
-    _lib.check(L.curv_kfac_group_accumulate(_lib.stream_ptr(), arr, n, ws.data_ptr(), ws.numel()),
-               "curv_kfac_group_accumulate")
-    if events is not None:
-        events[1].record()
+    _run_build("curv_kfac_group_workspace_bytes", "curv_kfac_group_accumulate", _group_descs(jobs), len(jobs),
+               jobs[0].src.device, "kfac_groups", events)
 
 
-class ConvTFactorJob:
+class ConvTFactorJob(_ConvJob):
     """The A factor of a ConvTranspose2d (curv_kfac_convt_accumulate): dst (+)= scale * sum_o a(o) a(o)^T over the output
     pixels, a(o) the layer's patch in Wm = weight.permute(1, 0, 2, 3).reshape(Cout, -1) order [+ 1].  `out_size` = (Ho, Wo)
     of the layer's output (it carries the effective output_padding).  `src` may also be just its (N, C, H, W) shape (plan
     queries)."""
-    __slots__ = ("src", "dst", "kernel", "stride", "padding", "out_size", "has_bias", "scale", "first")
+    __slots__ = ("out_size",)
 
     def __init__(self, src, dst, kernel, stride, padding, out_size, has_bias=False, scale=1.0, first=False):
-        self.src, self.dst = src, dst
-        self.kernel, self.stride, self.padding = tuple(kernel), tuple(stride), tuple(padding)
+        self._set(src, dst, kernel, stride, padding, has_bias, scale, first)
         self.out_size = tuple(int(v) for v in out_size)
-        self.has_bias, self.scale, self.first = bool(has_bias), float(scale), bool(first)
 
 
 def _convt_descs(jobs: Sequence[ConvTFactorJob], check_tensors: bool = True):
@@ -349,20 +341,9 @@ def _convt_descs(jobs: Sequence[ConvTFactorJob], check_tensors: bool = True):
     for d, j in zip(arr, jobs):
         if check_tensors:
             _require_gpu(j.src, j.dst)
-            if j.src.dim() != 4 or j.src.dtype != torch.float32 or not j.src.is_contiguous():
-                raise RuntimeError("transposed-convolution factor source must be a contiguous float32 (N,C,H,W) tensor")
-        N, C, H, W = j.src.shape if check_tensors else j.src
-        if check_tensors:
-            dim = C * j.kernel[0] * j.kernel[1] + int(j.has_bias)
-            if tuple(j.dst.shape) != (dim, dim):
-                raise RuntimeError(f"factor destination must be ({dim},{dim}), got {tuple(j.dst.shape)}")
-            d.src, d.dst = j.src.data_ptr(), j.dst.data_ptr()
-        d.N, d.C, d.H, d.W = int(N), int(C), int(H), int(W)
-        d.kh, d.kw = j.kernel
-        d.sh, d.sw = j.stride
-        d.ph, d.pw = j.padding
+        _fill_desc(d, j, check_tensors,
+                   source="transposed-convolution factor source must be a contiguous float32 (N,C,H,W) tensor")
         d.Ho, d.Wo = j.out_size
-        d.has_bias, d.first, d.scale = int(j.has_bias), int(j.first), j.scale
     return arr
 
 
@@ -371,10 +352,7 @@ def kfac_convt_plan_flops(jobs: Sequence[ConvTFactorJob]) -> List[int]:
     phase Grams it runs (curv_kfac_convt_plan_flops, host only).  `job.src` may be a tensor or its (N, C, H, W) shape."""
     if not jobs:
         return []
-    arr = _convt_descs(jobs, check_tensors=all(isinstance(j.src, torch.Tensor) for j in jobs))
-    out = (ctypes.c_longlong * len(jobs))()
-    _lib.check(_lib.lib().curv_kfac_convt_plan_flops(arr, len(jobs), out), "curv_kfac_convt_plan_flops")
-    return [int(v) for v in out]
+    return _plan_flops("curv_kfac_convt_plan_flops", _convt_descs(jobs, check_tensors=_all_tensors(jobs)), len(jobs))
 
 
 def kfac_accumulate_convt(jobs: Sequence[ConvTFactorJob], events=None) -> None:
@@ -383,19 +361,8 @@ def kfac_accumulate_convt(jobs: Sequence[ConvTFactorJob], events=None) -> None:
     CURV_DEBUG_POISON covers it).  `events` = (start, stop) ``torch.cuda.Event``s are recorded around the whole build."""
     if not jobs:
         return
-    n = len(jobs)
-    arr = _convt_descs(jobs)
-    L = _lib.lib()
-    need = L.curv_kfac_convt_workspace_bytes(arr, n)
-    if need == 0:
-        _lib.check(_lib.ERR_INVALID, "curv_kfac_convt_workspace_bytes")
-    ws = workspace(need, jobs[0].src.device, "kfac_convt")
-    if events is not None:
-        events[0].record()
-    _lib.check(L.curv_kfac_convt_accumulate(_lib.stream_ptr(), arr, n, ws.data_ptr(), ws.numel()),
-               "curv_kfac_convt_accumulate")
-    if events is not None:
-        events[1].record()
+    _run_build("curv_kfac_convt_workspace_bytes", "curv_kfac_convt_accumulate", _convt_descs(jobs), len(jobs),
+               jobs[0].src.device, "kfac_convt", events)
 
 
 class LayerJobs(NamedTuple):
@@ -587,13 +554,9 @@ def per_sample_pack(operands: Sequence[PerSampleOperand], dsts: Sequence[torch.T
         _require_gpu(op.src, dst)
         if dst.numel() < op.floats:
             raise RuntimeError("per_sample_pack: destination too small")
-        N, C, H, W, kernel, stride, padding, has_bias, channels_last = op.pack
         d.src, d.dst = op.src.data_ptr(), dst.data_ptr()
-        d.N, d.C, d.H, d.W = N, C, H, W
-        d.kh, d.kw = kernel
-        d.sh, d.sw = stride
-        d.ph, d.pw = padding
-        d.has_bias, d.channels_last, d.rows_outer, d.Lp = int(has_bias), int(channels_last), int(op.rows_outer), op.Lp
+        _set_geometry(d, op.pack[:4], *op.pack[4:8])
+        d.channels_last, d.rows_outer, d.Lp = int(op.pack[8]), int(op.rows_outer), op.Lp
     _lib.check(_lib.lib().curv_persample_pack(_lib.stream_ptr(), arr, len(operands)), "curv_persample_pack")
 
 
@@ -638,25 +601,15 @@ def per_sample_plan_flops(jobs: Sequence[PerSampleJob]) -> List[int]:
     """Multiply-add FLOPs (2 per multiply-add) the plan executes per job (curv_persample_plan_flops, host only)."""
     if not jobs:
         return []
-    arr = _per_sample_descs(jobs, check_tensors=False)
-    out = (ctypes.c_longlong * len(jobs))()
-    _lib.check(_lib.lib().curv_persample_plan_flops(arr, len(jobs), out), "curv_persample_plan_flops")
-    return [int(v) for v in out]
+    return _plan_flops("curv_persample_plan_flops", _per_sample_descs(jobs, check_tensors=False), len(jobs))
 
 
 def per_sample_sq_accumulate(jobs: Sequence[PerSampleJob]) -> None:
     """curv_persample_sq_accumulate over any number of products, on the current stream; slabs from `workspace`."""
     if not jobs:
         return
-    n = len(jobs)
-    arr = _per_sample_descs(jobs)
-    L = _lib.lib()
-    need = L.curv_persample_workspace_bytes(arr, n)
-    if need == 0:
-        _lib.check(_lib.ERR_INVALID, "curv_persample_workspace_bytes")
-    ws = workspace(need, jobs[0].C.device, "persample")
-    _lib.check(L.curv_persample_sq_accumulate(_lib.stream_ptr(), arr, n, ws.data_ptr(), ws.numel()),
-               "curv_persample_sq_accumulate")
+    _run_build("curv_persample_workspace_bytes", "curv_persample_sq_accumulate", _per_sample_descs(jobs), len(jobs),
+               jobs[0].C.device, "persample")
 
 
 def per_sample_scratch(floats: Sequence[int], device) -> List[torch.Tensor]:
