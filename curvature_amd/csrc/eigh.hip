@@ -21,7 +21,7 @@
 // The 64x64 sub-problems are solved in fp64 in both phases (their cost is LDS latency, not arithmetic).
 // Eigenvalues are returned ascending with the eigenvectors as columns, like the reference's symeig;
 // signs and the basis inside degenerate clusters are arbitrary there as here.
-#include "common.h"
+#include "kernarg.h"
 #include "mma64.h"
 
 #include <algorithm>
@@ -807,16 +807,7 @@ eigh_gather_kernel(const EighDev* __restrict__ t, int nf, const int* __restrict_
   }
 }
 
-constexpr int EIG_UPLOAD_CHUNK = 24;
-struct EighChunk { EighDev f[EIG_UPLOAD_CHUNK]; };
-static_assert(sizeof(EighChunk) <= 3840, "kernel argument block must stay below 4 KB");
-
-__global__ void __launch_bounds__(256) eigh_upload_kernel(EighDev* __restrict__ table, EighChunk chunk, int count) {
-  const int words = count * (int)(sizeof(EighDev) / 4);
-  const int* in = reinterpret_cast<const int*>(&chunk);
-  int* out = reinterpret_cast<int*>(table);
-  for (int w = threadIdx.x; w < words; w += blockDim.x) out[w] = in[w];
-}
+constexpr int EIG_UPLOAD_CHUNK = 24;      // rows per launch of the table upload (upload_table, kernarg.h)
 
 struct EighLayout {
   size_t table, norms, flags, perm, total;
@@ -940,14 +931,8 @@ int curv::syevd_jacobi(hipStream_t stream, const curv_eigh_desc* descs, int n_ma
     const long long Pg = cdiv(s.n, NB);
     gather_tiles += Pg * Pg;
   }
-  for (int b = 0; b < n_mats; b += EIG_UPLOAD_CHUNK) {
-    EighChunk chunk;
-    const int count = std::min(EIG_UPLOAD_CHUNK, n_mats - b);
-    memset(&chunk, 0, sizeof(chunk));
-    memcpy(chunk.f, tab.data() + b, (size_t)count * sizeof(EighDev));
-    hipLaunchKernelGGL(eigh_upload_kernel, dim3(1), dim3(256), 0, stream, table + b, chunk, count);
-    CURV_LAUNCH_CHECK();
-  }
+  int rcu = upload_table<EIG_UPLOAD_CHUNK>(stream, table, tab.data(), n_mats);
+  if (rcu != CURV_OK) return rcu;
   CURV_HIP_CHECK(hipMemsetAsync(flags, 0, (size_t)n_mats * 2 * sizeof(int), stream));
   CURV_HIP_CHECK(hipMemsetAsync(norms, 0, L.norms, stream));      // includes every matrix's scale (0 = no test yet)
   std::vector<int> host_flags(2 * n_mats);
@@ -1077,14 +1062,8 @@ int curv::syevd_jacobi(hipStream_t stream, const curv_eigh_desc* descs, int n_ma
     if (rcg != CURV_OK) return rcg;
     // the rotations of phase B accumulate onto V' (T3): swap the roles of the two buffers in the device table
     for (int i = 0; i < n_mats; ++i) std::swap(tab[i].V, tab[i].T3);
-    for (int b = 0; b < n_mats; b += EIG_UPLOAD_CHUNK) {
-      EighChunk chunk;
-      const int count = std::min(EIG_UPLOAD_CHUNK, n_mats - b);
-      memset(&chunk, 0, sizeof(chunk));
-      memcpy(chunk.f, tab.data() + b, (size_t)count * sizeof(EighDev));
-      hipLaunchKernelGGL(eigh_upload_kernel, dim3(1), dim3(256), 0, stream, table + b, chunk, count);
-      CURV_LAUNCH_CHECK();
-    }
+    rcu = upload_table<EIG_UPLOAD_CHUNK>(stream, table, tab.data(), n_mats);
+    if (rcu != CURV_OK) return rcu;
     hipLaunchKernelGGL(eigh_mirror_kernel, dim3((unsigned)prep_tiles), dim3(EIG_THREADS), 0, stream, table, n_mats, 0);
     CURV_LAUNCH_CHECK();
     hipLaunchKernelGGL(eigh_resume_kernel, dim3((unsigned)cdiv(n_mats, 64)), dim3(64), 0, stream, table, n_mats);

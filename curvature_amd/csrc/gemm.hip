@@ -10,7 +10,7 @@
 //   INF           the small dense products of update / pre_sampler / sampler   :487-600
 // One launch covers any number of independent products (one per layer): the work list is
 // (descriptor, 64x64 output tile), decoded on the device from the descriptor table.
-#include "common.h"
+#include "kernarg.h"
 #include "gemm_nt.h"
 
 #include <algorithm>
@@ -553,22 +553,9 @@ gemm_f64_macro_kernel(const Gemm64Table tab, int n_desc) {
       }
 }
 
+// rows per launch of the two table uploads (upload_table, kernarg.h): tile order, descriptor table
 constexpr int ORDER_UPLOAD_CHUNK = 944;
-struct OrderChunk { int v[ORDER_UPLOAD_CHUNK]; };
-__global__ void __launch_bounds__(256) order_upload_kernel(int* __restrict__ dst, OrderChunk chunk, int count) {
-  for (int w = threadIdx.x; w < count; w += blockDim.x) dst[w] = chunk.v[w];
-}
-
 constexpr int GEMM_UPLOAD_CHUNK = 17;
-struct GemmChunk { GemmDev f[GEMM_UPLOAD_CHUNK]; };
-static_assert(sizeof(GemmChunk) <= 3840, "kernel argument block must stay below 4 KB");
-
-__global__ void __launch_bounds__(256) gemm_upload_kernel(GemmDev* __restrict__ table, GemmChunk chunk, int count) {
-  const int words = count * (int)(sizeof(GemmDev) / 4);
-  const int* in = reinterpret_cast<const int*>(&chunk);
-  int* out = reinterpret_cast<int*>(table);
-  for (int w = threadIdx.x; w < words; w += blockDim.x) out[w] = in[w];
-}
 
 // ------------------------------------------------------------------------------------------------
 // Standard normal noise: Philox4x32-10 counter-based generator + Box-Muller, 4 values per counter.
@@ -800,13 +787,9 @@ static int gemm_batched_impl(void* stream_, const curv_gemm_desc* descs, int n_d
   all.insert(all.end(), tab_v.begin(), tab_v.end());
   // CURV_GEMM_TABLE_RESIDENT: the caller replays the very same descriptor array into a workspace nobody else has
   // written since the previous call - the device table is still there
-  for (int b = 0; b < n + n_nt + n_v && !(flags & CURV_GEMM_TABLE_RESIDENT); b += GEMM_UPLOAD_CHUNK) {
-    GemmChunk chunk;
-    const int count = std::min(GEMM_UPLOAD_CHUNK, n + n_nt + n_v - b);
-    memset(&chunk, 0, sizeof(chunk));
-    memcpy(chunk.f, all.data() + b, (size_t)count * sizeof(GemmDev));
-    hipLaunchKernelGGL(gemm_upload_kernel, dim3(1), dim3(256), 0, stream, table + b, chunk, count);
-    CURV_LAUNCH_CHECK();
+  if (!(flags & CURV_GEMM_TABLE_RESIDENT)) {
+    const int rcu = upload_table<GEMM_UPLOAD_CHUNK>(stream, table, all.data(), n + n_nt + n_v);
+    if (rcu != CURV_OK) return rcu;
   }
   float* slabs = reinterpret_cast<float*>(reinterpret_cast<char*>(workspace) + curv_gemm_workspace_bytes(n_desc));
   // a full launch (several tiles per workgroup slot, no K slicing): its tiles in descending K order, in the space the
@@ -831,13 +814,10 @@ static int gemm_batched_impl(void* stream_, const curv_gemm_desc* descs, int n_d
         }
       }
       std::stable_sort(keyed.begin(), keyed.end(), [](const std::pair<int, int>& a, const std::pair<int, int>& b) { return a.first > b.first; });
-      for (size_t b = 0; b < keyed.size(); b += ORDER_UPLOAD_CHUNK) {
-        OrderChunk chunk;
-        const int count = (int)std::min<size_t>(ORDER_UPLOAD_CHUNK, keyed.size() - b);
-        for (int k = 0; k < count; ++k) chunk.v[k] = keyed[b + k].second;
-        hipLaunchKernelGGL(order_upload_kernel, dim3(1), dim3(256), 0, stream, dev_order + b, chunk, count);
-        CURV_LAUNCH_CHECK();
-      }
+      std::vector<int> host_order(keyed.size());
+      for (size_t k = 0; k < keyed.size(); ++k) host_order[k] = keyed[k].second;
+      const int rcu = upload_table<ORDER_UPLOAD_CHUNK>(stream, dev_order, host_order.data(), (int)host_order.size());
+      if (rcu != CURV_OK) return rcu;
     }
   }
   if (n_nt > 0) {

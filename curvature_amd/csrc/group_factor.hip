@@ -44,7 +44,7 @@ struct GrpFactor {
   int step_n, step_oh, step_ow;   // GRP_THREADS pixels = step_n Ho Wo + step_oh Wo + step_ow
 };
 
-typedef side::ArgBatch<GrpFactor, GRP_BATCH> GrpBatch;
+typedef ArgBatch<GrpFactor, GRP_BATCH> GrpBatch;
 
 struct Plan {
   int P, n, Ho, Wo, K, S, E;
@@ -183,7 +183,7 @@ __global__ void __launch_bounds__(GRP_THREADS) group_gram_narrow_kernel(const Gr
   constexpr int T = P * (P + 1) / 2;
   constexpr int E = T + P;
   __shared__ float red[4][E];
-  const int fi = side::owner_of(batch, (int)blockIdx.x);
+  const int fi = owner_of(batch, (int)blockIdx.x);
   const GrpFactor& F = batch.e[fi];
   const int b = blockIdx.x - F.base;
   const int g = b / F.S, s = b - g * F.S;
@@ -226,7 +226,7 @@ __global__ void __launch_bounds__(GRP_THREADS) group_major_copy_kernel(const flo
 // One thread per (group, entry of the n x n square); entries above the diagonal idle.  Workgroups of a factor:
 // G x ceil(n^2 / GRP_THREADS).
 __global__ void __launch_bounds__(GRP_THREADS) group_reduce_kernel(const GrpBatch batch) {
-  const int fi = side::owner_of(batch, (int)blockIdx.x);
+  const int fi = owner_of(batch, (int)blockIdx.x);
   const GrpFactor& F = batch.e[fi];
   const int n = F.n, P = F.P, S = F.S;
   const int chunks = (n * n + GRP_THREADS - 1) / GRP_THREADS;
@@ -289,7 +289,7 @@ GrpFactor factor_of(const curv_group_factor_desc& d, const Plan& p, float* part)
 // reduce pass (kind 1).
 int launch_batches(hipStream_t stream, const curv_group_factor_desc* descs, const Plan* plans, float* const* parts,
                    const int* idx, int count, int kind, int narrow_P) {
-  return side::for_arg_batches<GrpFactor, GRP_BATCH, 1>(
+  return for_arg_batches<GrpFactor, GRP_BATCH, 1>(
       count, "curv_kfac_group_accumulate",
       [&](int k, GrpFactor* F, long long* blocks) {
         *F = factor_of(descs[idx[k]], plans[idx[k]], parts[idx[k]]);

@@ -26,7 +26,7 @@
 // Matrices are padded to a multiple of 64 with an identity tail, so no kernel needs bounds checks.
 // "Not positive definite" is reported through a per-factor device info word (0 = ok).
 #include <type_traits>
-#include "common.h"
+#include "kernarg.h"
 #include "mma64.h"
 #include <hip/hip_ext.h>
 
@@ -1599,16 +1599,7 @@ inv_finalize_kernel(const InvDev* __restrict__ t, int nf, int sq) {   // sq: edg
   }
 }
 
-constexpr int INV_UPLOAD_CHUNK = 28;
-struct InvChunk { InvDev f[INV_UPLOAD_CHUNK]; };
-static_assert(sizeof(InvChunk) <= 3840, "kernel argument block must stay below 4 KB");
-
-__global__ void __launch_bounds__(256) inv_upload_kernel(InvDev* __restrict__ table, InvChunk chunk, int count) {
-  const int words = count * (int)(sizeof(InvDev) / 4);
-  const int* in = reinterpret_cast<const int*>(&chunk);
-  int* out = reinterpret_cast<int*>(table);
-  for (int w = threadIdx.x; w < words; w += blockDim.x) out[w] = in[w];
-}
+constexpr int INV_UPLOAD_CHUNK = 28;      // rows per launch of the table upload (upload_table, kernarg.h)
 
 static size_t inv_table_bytes(int n) { return align_up((size_t)std::max(n, 1) * sizeof(InvDev), 256); }
 static size_t inv_flags_bytes(int n) { return align_up((size_t)std::max(n, 1) * SQ_FLAGS * sizeof(int), 256); }
@@ -1791,14 +1782,8 @@ struct GroupSweep {
       prep_tiles += (long long)d.P * (d.P + 1) / 2;
       fin_tiles += (long long)d.P * d.P;
     }
-    for (int b = 0; b < n_factors; b += INV_UPLOAD_CHUNK) {
-      InvChunk chunk;
-      const int count = std::min(INV_UPLOAD_CHUNK, n_factors - b);
-      memset(&chunk, 0, sizeof(chunk));
-      memcpy(chunk.f, tab.data() + b, (size_t)count * sizeof(InvDev));
-      hipLaunchKernelGGL(inv_upload_kernel, dim3(1), dim3(256), 0, stream, table + b, chunk, count);
-      CURV_LAUNCH_CHECK();
-    }
+    const int rcu = upload_table<INV_UPLOAD_CHUNK>(stream, table, tab.data(), n_factors);
+    if (rcu != CURV_OK) return rcu;
     hipLaunchKernelGGL(inv_prepare_kernel, dim3((unsigned)prep_tiles), dim3(INV_THREADS), 0, stream, table, n_factors, flags);
     CURV_LAUNCH_CHECK();
     // outer panel: 4 block columns = 256 for the chain-bound forms (the square kernel is built for 4); 6 = 384 for the

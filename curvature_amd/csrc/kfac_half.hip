@@ -62,7 +62,7 @@ struct H16Factor {
   long long base;             // first pack thread / item / reduce block of this factor in the launch
 };
 
-typedef side::ArgBatch<H16Factor, H16_BATCH> H16Batch;
+typedef ArgBatch<H16Factor, H16_BATCH> H16Batch;
 
 struct Plan {
   int Ho, Wo, rows, dim, P, T, K, Kp, stages, spi, S;
@@ -106,7 +106,7 @@ bool plan_of(const curv_factor16_desc& d, int index, Plan* p) {
 // Pack: one thread per 8 consecutive columns of one image row (one 16-byte store); threads of a factor R x Kp / 8.
 __global__ void __launch_bounds__(H16_THREADS) h16_pack_kernel(const H16Batch batch) {
   const long long t = (long long)blockIdx.x * H16_THREADS + threadIdx.x;
-  const H16Factor& F = batch.e[side::owner_of(batch, t)];
+  const H16Factor& F = batch.e[owner_of(batch, t)];
   const long long local = t - F.base;
   const int groups_per_row = F.Kp / H16_PACK_PER_THREAD;
   if (local >= (long long)F.P * H16_TM * groups_per_row) return;
@@ -184,7 +184,7 @@ __global__ void __launch_bounds__(H16_THREADS, 3) h16_syrk_kernel(const H16Batch
     item = ((j >> 5) * 8 + xcd) * 32 + (j & 31);
   }
   if (item >= items) return;
-  const H16Factor& F = batch.e[side::owner_of(batch, item)];
+  const H16Factor& F = batch.e[owner_of(batch, item)];
   const int local = (int)(item - F.base);
   const int slice = local / F.T;
   int tile = local - slice * F.T, ti = 0;
@@ -281,7 +281,7 @@ __global__ void __launch_bounds__(H16_THREADS, 3) h16_syrk_kernel(const H16Batch
 // Reduce: one thread per entry (r, c) of dst; it sums, in slice order, the slab entries of the upper-triangle position
 // (i, j) = (min, max), so dst[r][c] and dst[c][r] get the same bits.  Blocks of a factor: ceil(dim^2 / 256).
 __global__ void __launch_bounds__(H16_THREADS) h16_reduce_kernel(const H16Batch batch) {
-  const H16Factor& F = batch.e[side::owner_of(batch, (long long)blockIdx.x)];
+  const H16Factor& F = batch.e[owner_of(batch, (long long)blockIdx.x)];
   const long long idx = (blockIdx.x - F.base) * H16_THREADS + threadIdx.x;
   const int dim = F.dim;
   if (idx >= (long long)dim * dim) return;
@@ -327,7 +327,7 @@ long long units_of(const Plan& p, int kind) {
 // One pass over the factors `idx` (all of one dtype) in batches of H16_BATCH.
 int launch_pass(hipStream_t stream, const curv_factor16_desc* descs, const Plan* plans, char* const* regions,
                 const int* idx, int count, int kind) {
-  return side::for_arg_batches<H16Factor, H16_BATCH, 1>(
+  return for_arg_batches<H16Factor, H16_BATCH, 1>(
       count, "curv_kfac16_accumulate",
       [&](int k, H16Factor* F, long long* units) {
         *F = factor_of(descs[idx[k]], plans[idx[k]], regions[idx[k]]);

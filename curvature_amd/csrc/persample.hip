@@ -54,7 +54,7 @@ struct PsProduct {
   long long base;              // first item / reduce block of this product in the launch
 };
 
-typedef side::ArgBatch<PsProduct, PS_BATCH> PsBatch;
+typedef ArgBatch<PsProduct, PS_BATCH> PsBatch;
 
 struct Plan {
   int tiles_m, tiles_n, tiles, sps, spi, slices, half, swap;
@@ -262,7 +262,7 @@ __device__ __forceinline__ void ps_product_tile(const PsProduct& d, int local, l
 
 __global__ void __launch_bounds__(PS_THREADS, 2) ps_product_kernel(const PsBatch batch) {
   __shared__ __attribute__((aligned(1024))) char smem[4 * nt::PANEL_B];   // [buffer][A panel, B panel] as gemm_nt.h
-  const PsProduct& d = batch.e[side::owner_of(batch, (long long)blockIdx.x)];
+  const PsProduct& d = batch.e[owner_of(batch, (long long)blockIdx.x)];
   const int local = (int)(blockIdx.x - d.base);
   if (d.half) ps_product_tile<true>(d, local, (lds_char_t*)smem);
   else ps_product_tile<false>(d, local, (lds_char_t*)smem);
@@ -271,7 +271,7 @@ __global__ void __launch_bounds__(PS_THREADS, 2) ps_product_kernel(const PsBatch
 // Reduce: one thread per entry (i, j) of C; it sums the slab entries of its tile in slice order, scales, writes or adds.
 // Blocks of a product: ceil(M Nc / 256).
 __global__ void __launch_bounds__(PS_THREADS) ps_reduce_kernel(const PsBatch batch) {
-  const PsProduct& d = batch.e[side::owner_of(batch, (long long)blockIdx.x)];
+  const PsProduct& d = batch.e[owner_of(batch, (long long)blockIdx.x)];
   const int rows = d.swap ? d.Nc : d.M, cols = d.swap ? d.M : d.Nc;            // of C
   const long long idx = (blockIdx.x - d.base) * PS_THREADS + threadIdx.x;
   if (idx >= (long long)rows * cols) return;
@@ -301,7 +301,7 @@ struct PsPack {
   long long base;             // first thread of this layer in the launch
 };
 
-typedef side::ArgBatch<PsPack, PS_BATCH> PsPackBatch;
+typedef ArgBatch<PsPack, PS_BATCH> PsPackBatch;
 
 bool pack_plan_of(const curv_persample_pack_desc& d, int index, PsPack* out) {
   side::ConvGeom g;
@@ -335,7 +335,7 @@ bool pack_plan_of(const curv_persample_pack_desc& d, int index, PsPack* out) {
 // as zeros, a masked gather reads src[0] and drops it.
 __global__ void __launch_bounds__(PS_THREADS) ps_pack_kernel(const PsPackBatch batch) {
   const long long t = (long long)blockIdx.x * PS_THREADS + threadIdx.x;
-  int f = 0;                                               // (side::owner_of, spelled out: the call compiles differently)
+  int f = 0;                                               // (owner_of, spelled out: the call compiles differently)
   for (int i = 1; i < batch.count; ++i)
     if (t >= batch.e[i].base) f = i;
   const PsPack& F = batch.e[f];
@@ -422,7 +422,7 @@ extern "C" int curv_persample_sq_accumulate(void* stream_, const curv_persample_
   if (rc != CURV_OK) return rc;
   size_t at = 0;
   // one walk, two launches: lane 0 counts the items of the product launch, lane 1 the blocks of the reduce launch
-  return side::for_arg_batches<PsProduct, PS_BATCH, 2>(
+  return for_arg_batches<PsProduct, PS_BATCH, 2>(
       n, name,
       [&](int i, PsProduct* P, long long* units) {
         *P = product_of(descs[i], plans[i], (float*)((char*)workspace + at));
@@ -451,7 +451,7 @@ extern "C" int curv_persample_pack(void* stream_, const curv_persample_pack_desc
     CURV_REQUIRE(descs[i].src && descs[i].dst && (reinterpret_cast<uintptr_t>(descs[i].dst) & 15) == 0,
                  "%s: item %d: null src or dst, or dst not 16-byte aligned", name, i);
   }
-  return side::for_arg_batches<PsPack, PS_BATCH, 1>(
+  return for_arg_batches<PsPack, PS_BATCH, 1>(
       n, name,
       [&](int i, PsPack* P, long long* threads) {
         *P = packs[i];

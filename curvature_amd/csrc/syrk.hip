@@ -30,7 +30,7 @@
 //     v_mfma_f32_32x32x2_f32 blocks and skips the redundant lower-left block on the diagonal;
 //   * partial tiles go to fp32 slabs and a second kernel sums the k-slices in a fixed order, applies
 //     the scale and adds into the factor and its mirror image: deterministic, exactly symmetric.
-#include "common.h"
+#include "side_build.h"
 #include "syrk_plan.h"
 
 #include <algorithm>
@@ -854,21 +854,9 @@ syrk_reduce_kernel(const FactorDev* __restrict__ descs, int n_factors, const flo
   }
 }
 
-// The descriptor table travels as kernel arguments (copied by the runtime at launch time), so the
-// call is fully asynchronous and needs neither pinned staging memory nor a stream synchronisation.
+// The descriptor table travels as kernel arguments (upload_table, kernarg.h), 13 rows per launch; the first launch
+// also zeroes the pad behind the table: the dummy load target of masked staging slots.
 constexpr int UPLOAD_CHUNK = 13;
-constexpr int ZERO_PAD_FLOATS = 64;    // dummy load target of masked staging slots
-struct TableChunk { FactorDev f[UPLOAD_CHUNK]; };
-static_assert(sizeof(TableChunk) <= 3840, "kernel argument block must stay below 4 KB");
-
-__global__ void __launch_bounds__(256)
-upload_table_kernel(FactorDev* __restrict__ table, TableChunk chunk, int count, float* __restrict__ zeros) {
-  const int words = count * (int)(sizeof(FactorDev) / 4);
-  const int* in = reinterpret_cast<const int*>(&chunk);
-  int* out = reinterpret_cast<int*>(table);
-  for (int w = threadIdx.x; w < words; w += blockDim.x) out[w] = in[w];
-  if (zeros != nullptr && threadIdx.x < ZERO_PAD_FLOATS) zeros[threadIdx.x] = 0.0f;
-}
 
 // ---------------------------------------------------------------------------------------------
 // Host-side planning
@@ -1066,16 +1054,17 @@ static int build_plan(const curv_factor_desc* descs, int n, Plan& plan) {
   std::vector<double> chunk_cost(n);   // MFMA CU-cycles of one (tile, chunk)
   std::vector<double> chunk_px(n, 1.0); // k values (samples x output pixels) of one chunk
   double total_cost = 0.0;
+  std::vector<side::ConvGeom> geom(n);
+  for (int i = 0; i < n; ++i)
+    if (!side::conv_geom_of(descs[i], "curv_kfac", "factor", i, &geom[i])) return CURV_ERR_INVALID;
   {
     // size of the launch in MFMA CU-cycles (64 x 64 x k = 32 k), before any chunk is planned
     double estimate = 0.0;
     for (int i = 0; i < n; ++i) {
       const curv_factor_desc& s = descs[i];
-      if (s.N <= 0 || s.C <= 0 || s.kh <= 0 || s.kw <= 0 || s.sh <= 0 || s.sw <= 0) continue;   // rejected below
       const double dim = (double)s.C * s.kh * s.kw + (s.has_bias ? 1 : 0);
       const double blocks = std::ceil(dim / 64.0);
-      const double ho = (s.H + 2.0 * s.ph - s.kh) / s.sh + 1, wo = (s.W + 2.0 * s.pw - s.kw) / s.sw + 1;
-      estimate += 32.0 * blocks * (blocks + 1) / 2 * s.N * std::max(ho, 1.0) * std::max(wo, 1.0);
+      estimate += 32.0 * blocks * (blocks + 1) / 2 * s.N * geom[i].Ho * geom[i].Wo;
     }
     g_chunk_px_cap = estimate < 512.0 * 16.0 * CURV_ITEM_FLOOR ? CURV_SMALL_CHUNK_PX : 4096;
   }
@@ -1083,16 +1072,11 @@ static int build_plan(const curv_factor_desc* descs, int n, Plan& plan) {
     const curv_factor_desc& s = descs[i];
     FactorDev& f = plan.f[i];
     memset(&f, 0, sizeof(f));
-    CURV_REQUIRE(s.N > 0 && s.C > 0 && s.H > 0 && s.W > 0, "curv_kfac: factor %d: empty source", i);
-    CURV_REQUIRE(s.kh > 0 && s.kw > 0 && s.sh > 0 && s.sw > 0 && s.ph >= 0 && s.pw >= 0,
-                 "curv_kfac: factor %d: bad kernel geometry", i);
     CURV_REQUIRE(s.src != nullptr && s.dst != nullptr, "curv_kfac: factor %d: null pointer", i);
     f.src = s.src; f.dst = s.dst;
     f.N = s.N; f.C = s.C; f.H = s.H; f.W = s.W;
     f.kh = s.kh; f.kw = s.kw; f.sh = s.sh; f.sw = s.sw; f.ph = s.ph; f.pw = s.pw;
-    CURV_REQUIRE(s.H + 2 * s.ph >= s.kh && s.W + 2 * s.pw >= s.kw, "curv_kfac: factor %d: kernel larger than input", i);
-    f.Ho = (s.H + 2 * s.ph - s.kh) / s.sh + 1;
-    f.Wo = (s.W + 2 * s.pw - s.kw) / s.sw + 1;
+    f.Ho = geom[i].Ho; f.Wo = geom[i].Wo;
     f.khkw = s.kh * s.kw;
     f.compact = (s.kh == 1 && s.kw == 1) ? 1 : 0;
     bool flattened = false;
@@ -1476,21 +1460,20 @@ static int kfac_accumulate_impl(void* stream_, const curv_factor_desc* descs, in
     memset(&none, 0xff, sizeof(none));
     shadow.rows.resize(n_table, none);
   }
-  for (int b = 0; b < n_table; b += UPLOAD_CHUNK) {
-    TableChunk chunk;
-    const int count = std::min(UPLOAD_CHUNK, n_table - b);
-    memset(&chunk, 0, sizeof(chunk));
-    for (int k = 0; k < count; ++k) {
-      chunk.f[k] = plan.f[all[b + k]];
-      if (chunk.f[k].pre || chunk.f[k].sub) chunk.f[k].src = area + chunk.f[k].xq_off;   // the kernel stages from the pre-tiled / compact copy
-      chunk.f[k].xq_off = 0;
-    }
-    if (resident && memcmp(&shadow.rows[b], chunk.f, (size_t)count * sizeof(FactorDev)) == 0) continue;
-    memcpy(&shadow.rows[b], chunk.f, (size_t)count * sizeof(FactorDev));
-    hipLaunchKernelGGL(upload_table_kernel, dim3(1), dim3(256), 0, stream, table + b, chunk, count,
-                       b == 0 ? zeros : nullptr);
-    CURV_LAUNCH_CHECK();
+  std::vector<FactorDev> rows(n_table);
+  for (int k = 0; k < n_table; ++k) {
+    rows[k] = plan.f[all[k]];
+    if (rows[k].pre || rows[k].sub) rows[k].src = area + rows[k].xq_off;   // the kernel stages from the pre-tiled / compact copy
+    rows[k].xq_off = 0;
   }
+  // a block that the device still holds is skipped; the shadow takes every block that goes out
+  rc = upload_table<UPLOAD_CHUNK>(stream, table, rows.data(), n_table, zeros, [&](int b, int count) {
+    const size_t bytes = (size_t)count * sizeof(FactorDev);
+    if (resident && memcmp(&shadow.rows[b], &rows[b], bytes) == 0) return true;
+    memcpy(&shadow.rows[b], &rows[b], bytes);
+    return false;
+  });
+  if (rc != CURV_OK) return rc;
   const int n0 = (int)plan.order[0].size(), n1 = (int)plan.order[1].size(), n2 = (int)plan.order[2].size();
   if (ev_start) CURV_HIP_CHECK(hipEventRecord((hipEvent_t)ev_start, stream));
   // launch order on the caller's stream: padding pass, pre-tiling pass, pre-tiled patch kernel, LDS-DMA kernel; the

@@ -29,6 +29,7 @@
 #include <cstring>
 #include <vector>
 
+#include "kernarg.h"
 #include "syrk_plan.h"
 
 namespace curv {
@@ -57,14 +58,13 @@ struct CorrDev {
   int comp_at[CORR_COMPONENTS];
   int first;
   float scale;
-  long long prep_base;       // first workgroup of this layer in the prep grid
-  int tile_base;             // first workgroup of this layer in the assembly grid
+  int base;                  // first workgroup of this layer in the launch (prep or assembly)
   unsigned g_magic, h_magic, c_magic;       // ceil(2^32 / d) for W / G, H, C
   int G, pad_;               // source floats per access of the padding pass (4 / 2 / 1)
 };
 constexpr int CORR_CHUNK = 13;
-struct CorrChunk { CorrDev l[CORR_CHUNK]; };
-static_assert(sizeof(CorrChunk) <= 3840, "kernel argument block must stay below 4 KB");
+typedef ArgBatch<CorrDev, CORR_CHUNK> CorrBatch;
+static_assert(sizeof(CorrBatch) <= 3840, "kernel argument block must stay below 4 KB");
 
 typedef __attribute__((address_space(1))) float gfl;
 
@@ -183,14 +183,11 @@ __device__ __forceinline__ void corr_prep_body(const CorrDev& d, long long g_fir
     }
   }
 }
-__global__ void __launch_bounds__(256) corr_prep_kernel(CorrChunk chunk, int count, long long total) {
-  (void)total;
-  int l = 0;
-  while (l + 1 < count && chunk.l[l + 1].prep_base <= (long long)blockIdx.x) ++l;
-  const CorrDev& d = chunk.l[l];
+__global__ void __launch_bounds__(256) corr_prep_kernel(const CorrBatch batch) {
+  const CorrDev& d = batch.e[owner_of_early_exit(batch, (int)blockIdx.x)];
   const int G = d.G;
   const long long groups = (long long)d.N * d.C * d.H * (d.W / G);
-  const long long g0 = ((long long)blockIdx.x - d.prep_base) * PREP_SEG;
+  const long long g0 = ((long long)blockIdx.x - d.base) * PREP_SEG;
   const int cnt = (int)min((long long)PREP_SEG, groups - g0);
   if (G == 4) corr_prep_body<4>(d, g0, cnt);
   else if (G == 2) corr_prep_body<2>(d, g0, cnt);
@@ -200,18 +197,16 @@ __global__ void __launch_bounds__(256) corr_prep_kernel(CorrChunk chunk, int cou
 
 // dst tile (OUT x OUT) of channel tile (cb, cb2): rows (c, p), columns (c', q).  p >= q reads the components at
 // [c][c'], p < q is the transposed block (q, p) and reads them at [c'][c] (the mirrored channel tile).
-__global__ void __launch_bounds__(256) corr_assemble_kernel(CorrChunk chunk, int count) {
+__global__ void __launch_bounds__(256) corr_assemble_kernel(const CorrBatch batch) {
   using namespace corr;
   __shared__ float ta[29][CT][CT + 1];        // components at channel tile (cb, cb2)
   __shared__ float tb[29][CT][CT + 1];        // ... at (cb2, cb)
-  int l = 0;
-  while (l + 1 < count && chunk.l[l + 1].tile_base <= (int)blockIdx.x) ++l;
-  const CorrDev& d = chunk.l[l];
+  const CorrDev& d = batch.e[owner_of_early_exit(batch, (int)blockIdx.x)];
   const int C = d.C, nct = C / CT;
   // Workgroups b, b + 8, b + 16, b + 24 share an XCD (and its L2); they take four NEIGHBOURING tiles of a row of channel
   // tiles, whose 8-float component rows are the four quarters of one 128-byte line (one tile per workgroup in launch
   // order fetched every such line four times, each time on another XCD)
-  int t = blockIdx.x - d.tile_base;
+  int t = blockIdx.x - d.base;
   if (t < ((nct * nct) & ~31)) { const int w = t & 31; t = (t & ~31) + ((w & 7) << 2) + (w >> 3); }
   const int cb = t / nct, cb2 = t - cb * nct;
   {
@@ -490,41 +485,37 @@ static void fill_dev(const CorrLayer& L, const FactorDev& user, float* area, Cor
 
 int launch_corr_prep(hipStream_t stream, const std::vector<CorrLayer>& layers, const std::vector<FactorDev>& f,
                      float* area) {
-  for (size_t b = 0; b < layers.size(); b += CORR_CHUNK) {
-    CorrChunk chunk;
-    memset(&chunk, 0, sizeof(chunk));
-    const int count = (int)std::min<size_t>(CORR_CHUNK, layers.size() - b);
-    long long total = 0;
-    for (int k = 0; k < count; ++k) {
-      const CorrLayer& L = layers[b + k];
-      fill_dev(L, f[L.user], area, chunk.l[k]);
-      chunk.l[k].prep_base = total;
-      total += ((long long)L.N * L.C * L.H * (L.W / chunk.l[k].G) + PREP_SEG - 1) / PREP_SEG;
-    }
-    CURV_REQUIRE(total < (1LL << 31), "curv_kfac: too many padding segments");
-    hipLaunchKernelGGL(corr_prep_kernel, dim3((unsigned)total), dim3(256), 0, stream, chunk, count, total);
-    CURV_LAUNCH_CHECK();
-  }
-  return CURV_OK;
+  return for_arg_batches<CorrDev, CORR_CHUNK, 1>(
+      (int)layers.size(), "curv_kfac: padding pass",
+      [&](int k, CorrDev* d, long long* segs) {
+        const CorrLayer& L = layers[k];
+        fill_dev(L, f[L.user], area, *d);
+        segs[0] = cdivll((long long)L.N * L.C * L.H * (L.W / d->G), PREP_SEG);
+      },
+      [](int, long long segs) { return segs; },
+      [&](const CorrBatch* b, const long long*, const unsigned* grid) {
+        hipLaunchKernelGGL(corr_prep_kernel, dim3(grid[0]), dim3(256), 0, stream, b[0]);
+        CURV_LAUNCH_CHECK();
+        return CURV_OK;
+      });
 }
 
 int launch_corr_assemble(hipStream_t stream, const std::vector<CorrLayer>& layers, const std::vector<FactorDev>& f,
                          float* area) {
-  for (size_t b = 0; b < layers.size(); b += CORR_CHUNK) {
-    CorrChunk chunk;
-    memset(&chunk, 0, sizeof(chunk));
-    const int count = (int)std::min<size_t>(CORR_CHUNK, layers.size() - b);
-    int tiles = 0;
-    for (int k = 0; k < count; ++k) {
-      const CorrLayer& L = layers[b + k];
-      fill_dev(L, f[L.user], area, chunk.l[k]);
-      chunk.l[k].tile_base = tiles;
-      tiles += (L.C / corr::CT) * (L.C / corr::CT);
-    }
-    hipLaunchKernelGGL(corr_assemble_kernel, dim3(tiles), dim3(256), 0, stream, chunk, count);
-    CURV_LAUNCH_CHECK();
-  }
-  return CURV_OK;
+  // (the walk's 2^31 limit cannot be met: a layer has (C / CT)^2 tiles and a batch 13 layers)
+  return for_arg_batches<CorrDev, CORR_CHUNK, 1>(
+      (int)layers.size(), "curv_kfac: assembly pass",
+      [&](int k, CorrDev* d, long long* tiles) {
+        const CorrLayer& L = layers[k];
+        fill_dev(L, f[L.user], area, *d);
+        tiles[0] = (long long)(L.C / corr::CT) * (L.C / corr::CT);
+      },
+      [](int, long long tiles) { return tiles; },
+      [&](const CorrBatch* b, const long long*, const unsigned* grid) {
+        hipLaunchKernelGGL(corr_assemble_kernel, dim3(grid[0]), dim3(256), 0, stream, b[0]);
+        CURV_LAUNCH_CHECK();
+        return CURV_OK;
+      });
 }
 
 }  // namespace curv

@@ -27,6 +27,7 @@
 #include <cstring>
 #include <algorithm>
 #include <vector>
+#include "side_build.h"
 #include "syrk_plan.h"
 
 namespace curv {
@@ -314,7 +315,7 @@ struct SubDev {
   const float* src;
   float* out;
   int C, H, W, kh, kw, sh, sw, ph, pw, Ho, Wo;
-  int wg_base;           // first workgroup of this factor in the grid
+  int base;              // first workgroup of this factor in the grid
   unsigned words;        // N * C kh kw * Ho * Wo (< 2^29: syrk_flat_eligible)
   unsigned m_wo, m_ho, m_rows, m_kk, m_kw;     // ceil(2^32 / d) for Wo, Ho, C kh kw, kh kw, kw
 };
@@ -327,15 +328,13 @@ __device__ __forceinline__ unsigned sub_div(unsigned x, unsigned d, unsigned mag
 static unsigned sub_magic(int d) { return d <= 1 ? 0u : (unsigned)(((1ull << 32) + (unsigned)d - 1) / (unsigned)d); }
 constexpr int SUB_CHUNK = 16;
 constexpr int SUB_SEG = 2048;  // output words per workgroup: 8 per thread, stores coalesced
-struct SubChunk { SubDev f[SUB_CHUNK]; };
-static_assert(sizeof(SubChunk) <= 3840, "kernel argument block must stay below 4 KB");
+typedef ArgBatch<SubDev, SUB_CHUNK> SubBatch;
+static_assert(sizeof(SubBatch) <= 3840, "kernel argument block must stay below 4 KB");
 
-__global__ void __launch_bounds__(256) unfold_prep_kernel(SubChunk chunk, int count) {
-  int l = 0;
-  while (l + 1 < count && chunk.f[l + 1].wg_base <= (int)blockIdx.x) ++l;
-  const SubDev& d = chunk.f[l];
+__global__ void __launch_bounds__(256) unfold_prep_kernel(const SubBatch batch) {
+  const SubDev& d = batch.e[owner_of_early_exit(batch, (int)blockIdx.x)];
   const unsigned Wo = d.Wo, Ho = d.Ho, kk = d.kh * d.kw, rows = d.C * kk;
-  const unsigned e0 = (blockIdx.x - d.wg_base) * SUB_SEG;
+  const unsigned e0 = (blockIdx.x - d.base) * SUB_SEG;
   const gfloat_t* src = (const gfloat_t*)d.src;
   gfloat_t* out = (gfloat_t*)d.out;
   // eight elements per thread, all eight loads issued before the first store (the nine rows of a channel read the same
@@ -365,34 +364,37 @@ __global__ void __launch_bounds__(256) unfold_prep_kernel(SubChunk chunk, int co
 }
 
 int launch_sub_prep(hipStream_t stream, const std::vector<FactorDev>& f, int n_user, const curv_factor_desc* descs, float* area) {
-  std::vector<int> which;
-  for (int i = 0; i < n_user; ++i) if (f[i].sub) which.push_back(i);
-  for (size_t b = 0; b < which.size(); b += SUB_CHUNK) {
-    SubChunk chunk;
-    memset(&chunk, 0, sizeof(chunk));
-    const int count = (int)std::min<size_t>(SUB_CHUNK, which.size() - b);
-    long long wgs = 0;
-    for (int k = 0; k < count; ++k) {
-      const int i = which[b + k];
-      const curv_factor_desc& s = descs[i];
-      SubDev& d = chunk.f[k];
-      d.src = s.src;
-      d.out = area + f[i].xq_off;
-      d.C = s.C; d.H = s.H; d.W = s.W; d.kh = s.kh; d.kw = s.kw; d.sh = s.sh; d.sw = s.sw; d.ph = s.ph; d.pw = s.pw;
-      d.Ho = (s.H + 2 * s.ph - s.kh) / s.sh + 1; d.Wo = (s.W + 2 * s.pw - s.kw) / s.sw + 1;
-      const long long words = (long long)s.N * s.C * s.kh * s.kw * d.Ho * d.Wo;
-      CURV_REQUIRE(words < (1LL << 31), "curv_kfac: unfolded source too large");
-      d.words = (unsigned)words;
-      d.m_wo = sub_magic(d.Wo); d.m_ho = sub_magic(d.Ho); d.m_rows = sub_magic(s.C * s.kh * s.kw);
-      d.m_kk = sub_magic(s.kh * s.kw); d.m_kw = sub_magic(s.kw);
-      d.wg_base = (int)wgs;
-      wgs += cdivll(words, SUB_SEG);
-      CURV_REQUIRE(wgs < (1LL << 31), "curv_kfac: unfolded sources too large for one pass");
-    }
-    hipLaunchKernelGGL(unfold_prep_kernel, dim3((unsigned)wgs), dim3(256), 0, stream, chunk, count);
-    CURV_LAUNCH_CHECK();
+  std::vector<SubDev> subs;
+  for (int i = 0; i < n_user; ++i) {
+    if (!f[i].sub) continue;
+    const curv_factor_desc& s = descs[i];
+    side::ConvGeom g;
+    if (!side::conv_geom_of(s, "curv_kfac", "factor", i, &g)) return CURV_ERR_INVALID;
+    SubDev d;
+    memset(&d, 0, sizeof(d));
+    d.src = s.src;
+    d.out = area + f[i].xq_off;
+    d.C = s.C; d.H = s.H; d.W = s.W; d.kh = s.kh; d.kw = s.kw; d.sh = s.sh; d.sw = s.sw; d.ph = s.ph; d.pw = s.pw;
+    d.Ho = g.Ho; d.Wo = g.Wo;
+    const long long words = (long long)s.N * s.C * s.kh * s.kw * d.Ho * d.Wo;
+    CURV_REQUIRE(words < (1LL << 31), "curv_kfac: unfolded source too large");
+    d.words = (unsigned)words;
+    d.m_wo = sub_magic(d.Wo); d.m_ho = sub_magic(d.Ho); d.m_rows = sub_magic(s.C * s.kh * s.kw);
+    d.m_kk = sub_magic(s.kh * s.kw); d.m_kw = sub_magic(s.kw);
+    subs.push_back(d);
   }
-  return CURV_OK;
+  return for_arg_batches<SubDev, SUB_CHUNK, 1>(
+      (int)subs.size(), "curv_kfac: unfolding pass",
+      [&](int k, SubDev* d, long long* wgs) {
+        *d = subs[k];
+        wgs[0] = cdivll(d->words, SUB_SEG);
+      },
+      [](int, long long wgs) { return wgs; },
+      [&](const SubBatch* b, const long long*, const unsigned* grid) {
+        hipLaunchKernelGGL(unfold_prep_kernel, dim3(grid[0]), dim3(256), 0, stream, b[0]);
+        CURV_LAUNCH_CHECK();
+        return CURV_OK;
+      });
 }
 
 int launch_syrk_flat(hipStream_t stream, const FactorDev* table, int n_factors, int n_items, float* slabs) {

@@ -16,6 +16,7 @@
 #include <cstring>
 #include <vector>
 
+#include "kernarg.h"
 #include "syrk_plan.h"
 
 namespace curv {
@@ -31,14 +32,14 @@ struct PreDev {
   unsigned ps_magic;          // ceil(2^32 / PS): r / PS for r < 2^16
   unsigned c_magic, ns_magic, rg_magic;   // ceil(2^32 / d) for C, NS, n_rg (quotients of numbers whose product with d < 2^32)
   int n_planes;               // chunks * NS * C
-  int seg_base;               // first workgroup (= SEG-word segment of the copy) of this factor in the grid
+  int base;                   // first workgroup (= SEG-word segment of the copy) of this factor in the grid
   int pad;
   long long words;            // n_planes * PS
 };
 constexpr int PRE_CHUNK = 32;
 constexpr int SEG = 4096;     // output words per workgroup: 16 per thread, coalesced
-struct PreChunk { PreDev f[PRE_CHUNK]; };
-static_assert(sizeof(PreChunk) <= 3840, "kernel argument block must stay below 4 KB");
+typedef ArgBatch<PreDev, PRE_CHUNK> PreBatch;
+static_assert(sizeof(PreBatch) <= 3840, "kernel argument block must stay below 4 KB");
 
 typedef __attribute__((address_space(1))) float gfl_t;
 
@@ -47,11 +48,9 @@ static unsigned magic_of(int d) { return (unsigned)(((1ull << 32) + (unsigned)d 
 
 // one workgroup per SEG consecutive words of a factor's copy: the plane of the segment's first word comes from one
 // exact division per workgroup, everything after it from 32-bit multiply-high arithmetic on small offsets
-__global__ void __launch_bounds__(256) patch_prep_kernel(PreChunk chunk, int count) {
-  int l = 0;
-  while (l + 1 < count && chunk.f[l + 1].seg_base <= (int)blockIdx.x) ++l;
-  const PreDev& d = chunk.f[l];
-  const long long w0 = (long long)(blockIdx.x - d.seg_base) * SEG;
+__global__ void __launch_bounds__(256) patch_prep_kernel(const PreBatch batch) {
+  const PreDev& d = batch.e[owner_of_early_exit(batch, (int)blockIdx.x)];
+  const long long w0 = (long long)(blockIdx.x - d.base) * SEG;
   const int PS = d.PS, RS = d.RS, C = d.C, H = d.H, W = d.W, NS = d.NS, n_rg = d.n_rg;
   const int plane0 = (int)(w0 / PS);
   const int r0 = (int)(w0 - (long long)plane0 * PS);
@@ -101,36 +100,36 @@ long long syrk_pre_floats(const FactorDev& f) {
 }
 
 int launch_patch_prep(hipStream_t stream, const std::vector<FactorDev>& f, const std::vector<int>& which, float* area) {
-  for (size_t b = 0; b < which.size(); b += PRE_CHUNK) {
-    PreChunk chunk;
-    memset(&chunk, 0, sizeof(chunk));
-    const int count = (int)std::min<size_t>(PRE_CHUNK, which.size() - b);
-    long long segs = 0;
-    for (int k = 0; k < count; ++k) {
-      const FactorDev& v = f[which[b + k]];
-      PreDev& d = chunk.f[k];
-      d.src = v.src;
-      d.xq = area + v.xq_off;
-      d.N = v.N; d.C = v.C; d.H = v.H; d.W = v.W;
-      d.NS = v.NS; d.R = v.R; d.n_rg = v.n_rg;
-      d.sh = v.sh; d.ph = v.ph; d.pw = v.pw;
-      d.rows_in = (v.R - 1) * v.sh + v.kh;
-      d.RS = v.RS; d.PS = v.PS;
-      d.rs_magic = magic_of(v.RS);
-      d.ps_magic = magic_of(v.PS);
-      d.c_magic = magic_of(v.C); d.ns_magic = magic_of(v.NS); d.rg_magic = magic_of(v.n_rg);
-      CURV_REQUIRE((long long)v.n_chunks * v.NS * v.C * v.C < (1LL << 32), "curv_kfac: pre-tiled copy has too many planes");
-      d.n_planes = v.n_chunks * v.NS * v.C;
-      d.words = (long long)d.n_planes * v.PS;
-      d.seg_base = (int)segs;
-      d.pad = v.nch * v.PS + 64;
-      segs += (d.words + SEG - 1) / SEG;
-      CURV_REQUIRE(segs < (1LL << 31), "curv_kfac: too many patch segments");
-    }
-    hipLaunchKernelGGL(patch_prep_kernel, dim3((unsigned)segs), dim3(256), 0, stream, chunk, count);
-    CURV_LAUNCH_CHECK();
-  }
-  return CURV_OK;
+  for (int i : which)
+    CURV_REQUIRE((long long)f[i].n_chunks * f[i].NS * f[i].C * f[i].C < (1LL << 32), "curv_kfac: pre-tiled copy has too many planes");
+  return for_arg_batches<PreDev, PRE_CHUNK, 1>(
+      (int)which.size(), "curv_kfac: pre-tiling pass",
+      [&](int k, PreDev* out, long long* segs) {
+        const FactorDev& v = f[which[k]];
+        PreDev d;
+        memset(&d, 0, sizeof(d));
+        d.src = v.src;
+        d.xq = area + v.xq_off;
+        d.N = v.N; d.C = v.C; d.H = v.H; d.W = v.W;
+        d.NS = v.NS; d.R = v.R; d.n_rg = v.n_rg;
+        d.sh = v.sh; d.ph = v.ph; d.pw = v.pw;
+        d.rows_in = (v.R - 1) * v.sh + v.kh;
+        d.RS = v.RS; d.PS = v.PS;
+        d.rs_magic = magic_of(v.RS);
+        d.ps_magic = magic_of(v.PS);
+        d.c_magic = magic_of(v.C); d.ns_magic = magic_of(v.NS); d.rg_magic = magic_of(v.n_rg);
+        d.n_planes = v.n_chunks * v.NS * v.C;
+        d.words = (long long)d.n_planes * v.PS;
+        d.pad = v.nch * v.PS + 64;
+        *out = d;
+        segs[0] = (d.words + SEG - 1) / SEG;
+      },
+      [](int, long long segs) { return segs; },
+      [&](const PreBatch* b, const long long*, const unsigned* grid) {
+        hipLaunchKernelGGL(patch_prep_kernel, dim3(grid[0]), dim3(256), 0, stream, b[0]);
+        CURV_LAUNCH_CHECK();
+        return CURV_OK;
+      });
 }
 
 }  // namespace curv

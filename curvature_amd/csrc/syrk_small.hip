@@ -16,6 +16,7 @@
 #include <algorithm>
 #include <vector>
 
+#include "side_build.h"
 #include "syrk_plan.h"
 
 namespace curv {
@@ -27,12 +28,12 @@ struct SmallDev {
   int rows, dim, has_bias, first;
   float scale;
   int nb, n_pairs, n_slices, kslice, K;
-  int wg_base, red_base;
+  int base;                              // first workgroup of this factor in the launch (build or reduce)
   long long slab_base;                   // floats
 };
 constexpr int SMALL_CHUNK = 24;
-struct SmallChunk { SmallDev f[SMALL_CHUNK]; };
-static_assert(sizeof(SmallChunk) <= 3840, "kernel argument block must stay below 4 KB");
+typedef ArgBatch<SmallDev, SMALL_CHUNK> SmallBatch;
+static_assert(sizeof(SmallBatch) <= 3840, "kernel argument block must stay below 4 KB");
 
 typedef __attribute__((address_space(1))) float gfl;
 
@@ -60,13 +61,11 @@ constexpr int SMALL_MAX_KSLICE = 2048;   // k values of a slice: the pixel table
 constexpr int SMALL_WAVES = 8;           // waves per workgroup: they split the slice's K range (16 accumulator registers / 8)
 
 __global__ void __launch_bounds__(64 * SMALL_WAVES)
-syrk_small_kernel(SmallChunk chunk, int count, float* __restrict__ slabs) {
+syrk_small_kernel(const SmallBatch batch, float* __restrict__ slabs) {
   __shared__ float part[SMALL_WAVES][16][64];
   __shared__ int2 ktab[SMALL_MAX_KSLICE];
-  int f = 0;
-  while (f + 1 < count && chunk.f[f + 1].wg_base <= (int)blockIdx.x) ++f;
-  const SmallDev& d = chunk.f[f];
-  const int local = blockIdx.x - d.wg_base;
+  const SmallDev& d = batch.e[owner_of_early_exit(batch, (int)blockIdx.x)];
+  const int local = blockIdx.x - d.base;
   const int pair = local / d.n_slices, slice = local - pair * d.n_slices;
   int bi, bj;
   small_pair(d.nb, pair, bi, bj);
@@ -158,12 +157,10 @@ syrk_small_kernel(SmallChunk chunk, int count, float* __restrict__ slabs) {
 // per element in flight (a slab written by another XCD is a 2 us round trip: summing 64 slices eight at a time took 15 us);
 // the four partial sums meet in LDS and are added in group order, so the result is a fixed function of the slabs.
 __global__ void __launch_bounds__(1024)
-syrk_small_reduce_kernel(SmallChunk chunk, int count, const float* __restrict__ slabs) {
+syrk_small_reduce_kernel(const SmallBatch batch, const float* __restrict__ slabs) {
   __shared__ float partial[3][1024];
-  int f = 0;
-  while (f + 1 < count && chunk.f[f + 1].red_base <= (int)blockIdx.x) ++f;
-  const SmallDev& d = chunk.f[f];
-  const int pair = blockIdx.x - d.red_base;
+  const SmallDev& d = batch.e[owner_of_early_exit(batch, (int)blockIdx.x)];
+  const int pair = blockIdx.x - d.base;
   int bi, bj;
   small_pair(d.nb, pair, bi, bj);
   const int dim = d.dim, n_slices = d.n_slices;
@@ -242,14 +239,12 @@ static bool small_plan(const curv_factor_desc* descs, int n, SmallPlan& plan) {
     const curv_factor_desc& s = descs[i];
     SmallDev& d = plan.f[i];
     memset(&d, 0, sizeof(d));
-    if (s.N <= 0 || s.C <= 0 || s.H <= 0 || s.W <= 0 || s.kh <= 0 || s.kw <= 0 || s.sh <= 0 || s.sw <= 0 || s.ph < 0 || s.pw < 0)
-      return false;                                                       // (the grouped path reports the error)
-    if (s.H + 2 * s.ph < s.kh || s.W + 2 * s.pw < s.kw) return false;
+    side::ConvGeom g;
+    if (side::conv_geom_fault(s, &g)) return false;                       // (the grouped path reports the error)
     if ((long long)s.N * s.C * s.H * s.W >= (1LL << 31) || s.H >= (1 << 15) || s.W >= (1 << 15)) return false;   // (pixel table packs y sh, x sw in 16 bits)
     d.src = s.src; d.dst = s.dst;
     d.N = s.N; d.C = s.C; d.H = s.H; d.W = s.W; d.kh = s.kh; d.kw = s.kw; d.sh = s.sh; d.sw = s.sw; d.ph = s.ph; d.pw = s.pw;
-    d.Ho = (s.H + 2 * s.ph - s.kh) / s.sh + 1;
-    d.Wo = (s.W + 2 * s.pw - s.kw) / s.sw + 1;
+    d.Ho = g.Ho; d.Wo = g.Wo;
     d.rows = s.C * s.kh * s.kw;
     d.has_bias = s.has_bias ? 1 : 0;
     d.dim = d.rows + d.has_bias;
@@ -273,8 +268,6 @@ static bool small_plan(const curv_factor_desc* descs, int n, SmallPlan& plan) {
     d.kslice = (cdiv(d.K, d.n_slices) + 7) & ~7;
     if (d.kslice > SMALL_MAX_KSLICE) return false;            // a factor this long is not a small launch's
     d.n_slices = cdiv(d.K, d.kslice);
-    d.wg_base = (int)plan.wgs;
-    d.red_base = (int)plan.red_wgs;
     d.slab_base = plan.slab_floats;
     plan.wgs += (long long)d.n_pairs * d.n_slices;
     plan.red_wgs += d.n_pairs;
@@ -311,23 +304,24 @@ int kfac_accumulate_small(hipStream_t stream, const curv_factor_desc* descs, int
     CURV_REQUIRE(descs[i].src != nullptr && descs[i].dst != nullptr, "curv_kfac: factor %d: null pointer", i);
   float* slabs = reinterpret_cast<float*>(workspace);
   if (ev_start) CURV_HIP_CHECK(hipEventRecord((hipEvent_t)ev_start, stream));
-  for (int b = 0; b < n; b += SMALL_CHUNK) {
-    SmallChunk chunk;
-    memset(&chunk, 0, sizeof(chunk));
-    const int count = std::min(SMALL_CHUNK, n - b);
-    long long wgs = 0, red = 0;
-    for (int k = 0; k < count; ++k) {
-      chunk.f[k] = plan.f[b + k];
-      chunk.f[k].wg_base = (int)wgs;
-      chunk.f[k].red_base = (int)red;
-      wgs += (long long)chunk.f[k].n_pairs * chunk.f[k].n_slices;
-      red += chunk.f[k].n_pairs;
-    }
-    hipLaunchKernelGGL(syrk_small_kernel, dim3((unsigned)wgs), dim3(64 * SMALL_WAVES), 0, stream, chunk, count, slabs);
-    CURV_LAUNCH_CHECK();
-    hipLaunchKernelGGL(syrk_small_reduce_kernel, dim3((unsigned)red), dim3(1024), 0, stream, chunk, count, (const float*)slabs);
-    CURV_LAUNCH_CHECK();
-  }
+  // one walk, two launches: lane 0 counts the workgroups of the build, lane 1 those of the reduce pass (the walk's
+  // 2^31 limit cannot be met: small_plan keeps a launch below 2^24 workgroups)
+  const int rc = for_arg_batches<SmallDev, SMALL_CHUNK, 2>(
+      n, "curv_kfac",
+      [&](int i, SmallDev* d, long long* wgs) {
+        *d = plan.f[i];
+        wgs[0] = (long long)d->n_pairs * d->n_slices;
+        wgs[1] = d->n_pairs;
+      },
+      [](int, long long wgs) { return wgs; },
+      [&](const SmallBatch* b, const long long*, const unsigned* grid) {
+        hipLaunchKernelGGL(syrk_small_kernel, dim3(grid[0]), dim3(64 * SMALL_WAVES), 0, stream, b[0], slabs);
+        CURV_LAUNCH_CHECK();
+        hipLaunchKernelGGL(syrk_small_reduce_kernel, dim3(grid[1]), dim3(1024), 0, stream, b[1], (const float*)slabs);
+        CURV_LAUNCH_CHECK();
+        return CURV_OK;
+      });
+  if (rc != CURV_OK) return rc;
   if (ev_stop) CURV_HIP_CHECK(hipEventRecord((hipEvent_t)ev_stop, stream));
   return CURV_OK;
 }

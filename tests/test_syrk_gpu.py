@@ -395,7 +395,7 @@ def _linear_jobs(ops, gpu, count, seed):
 def test_resident_table_survives_a_shorter_table_in_between(gpu):
     """Round-3 advisor: the library's host shadow of the resident descriptor table only ever grew, so a call with a
     SHORTER table (whose zero pad / slabs overwrite the tail rows of the longer one on the device) left stale shadow
-    rows behind and the next long call skipped their upload.  40 factors (three 14-row argument blocks), a 6-factor call
+    rows behind and the next long call skipped their upload.  40 factors (rows in argument blocks of 13), a 6-factor call
     on the same workspace in between, then the 40 again: bit-identical to the first result."""
     from curvature_amd import ops
     jobs = _linear_jobs(ops, gpu, 40, 11)
