@@ -180,6 +180,14 @@ class curv_persample_desc(ctypes.Structure):
                 ("first", ctypes.c_int32), ("alpha", ctypes.c_float)]
 
 
+class curv_persample_quad_desc(ctypes.Structure):
+    """Mirror of ``curv_persample_quad_desc`` in include/curv_hip.h."""
+    _fields_ = [("A", ctypes.c_void_p), ("B", ctypes.c_void_p), ("W", ctypes.c_void_p), ("out", ctypes.c_void_p)] + \
+               [(k, ctypes.c_longlong) for k in ("a_ns", "a_rs", "b_ns", "b_rs", "w_rs", "o_stride")] + \
+               [("S", ctypes.c_int32), ("M", ctypes.c_int32), ("Nc", ctypes.c_int32), ("L", ctypes.c_int32),
+                ("first", ctypes.c_int32), ("alpha", ctypes.c_float)]
+
+
 class curv_persample_pack_desc(ctypes.Structure):
     """Mirror of ``curv_persample_pack_desc`` in include/curv_hip.h."""
     _fields_ = _ENDS + _SOURCE + _WINDOW + \
@@ -267,6 +275,9 @@ SIGNATURES = {
     "curv_persample_plan_flops": (_i, [ctypes.POINTER(curv_persample_desc), _i, ctypes.POINTER(ctypes.c_longlong)]),
     "curv_persample_sq_accumulate": (_i, [_vp, ctypes.POINTER(curv_persample_desc), _i, _vp, _sz]),
     "curv_persample_pack": (_i, [_vp, ctypes.POINTER(curv_persample_pack_desc), _i]),
+    "curv_persample_quad_workspace_bytes": (_sz, [ctypes.POINTER(curv_persample_quad_desc), _i]),
+    "curv_persample_quad_plan_flops": (_i, [ctypes.POINTER(curv_persample_quad_desc), _i, ctypes.POINTER(ctypes.c_longlong)]),
+    "curv_persample_quad_reduce": (_i, [_vp, ctypes.POINTER(curv_persample_quad_desc), _i, _vp, _sz]),
     "curv_clamp_min0": (_i, [_vp, _vp, _ll]),
     "curv_sqrt_scale": (_i, [_vp, _vp, _d, _vp, _ll]),
     "curv_mul": (_i, [_vp, _vp, _vp, _vp, _ll]),

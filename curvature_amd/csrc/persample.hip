@@ -24,6 +24,12 @@
 // own product's operands and slabs, and all sums run in a fixed order without atomics: a product's bits are the same
 // alone, in a whole-model call and on a sharded rank.  No host synchronisation, no device allocation; tables travel as
 // kernel arguments.
+//
+// The other reduction of the same products (curv_persample_quad_reduce): over the entries, per sample,
+//   out[n] (+)= alpha * sum_ij W[i][j] * P_n[i][j]**2
+// - the variance of a network output under a Laplace posterior (curvatures.py: functional_variance).  Same items, same
+// staging; the product launch leaves one float per (tile, sample) instead of a slab (see ps_product_tile), the reduce
+// launch sums a sample's tiles in tile order.
 #include "gemm_nt.h"
 #include "side_build.h"
 
@@ -56,6 +62,28 @@ struct PsProduct {
 
 typedef ArgBatch<PsProduct, PS_BATCH> PsBatch;
 
+// A product of curv_persample_quad_reduce: the same operands and tiling; instead of C and slabs the weights W (entry
+// (i, j) of the tile the kernel computes at W[i w_is + j w_js]: the strides change places with the operands when `swap`),
+// the fp32 `partial`[tile][sample] and the S outputs.
+struct PsQuad {
+  const float* A;
+  const float* B;
+  const float* W;              // may be null: all ones
+  float* out;
+  float* partial;
+  long long a_ns, a_rs, b_ns, b_rs, w_is, w_js, o_stride;
+  int S, M, Nc, L;
+  int tiles_n, tiles;
+  int spi, slices;
+  int half, swap;
+  int first;
+  float alpha;
+  unsigned a_bytes, b_bytes;
+  long long base;              // first item / reduce block of this product in the launch
+};
+
+typedef ArgBatch<PsQuad, PS_BATCH> PsQuadBatch;
+
 struct Plan {
   int tiles_m, tiles_n, tiles, sps, spi, slices, half, swap;
   long long a_bytes, b_bytes;
@@ -63,22 +91,24 @@ struct Plan {
   long long flops;
 };
 
-bool plan_of(const curv_persample_desc& d, int index, Plan* p) {
+// Sizes, operand strides and extents, tiling and sample ranges: what both kinds of product (C per entry, out per sample)
+// share.  `who` names the entry points in the error text.
+template <typename Desc>
+bool tiling_of(const Desc& d, const char* who, int index, Plan* p) {
   if (d.S < 1 || d.M < 1 || d.Nc < 1 || d.L < 1) {
-    set_error("curv_persample: item %d: invalid sizes (S %d M %d Nc %d L %d)", index, d.S, d.M, d.Nc, d.L);
+    set_error("%s: item %d: invalid sizes (S %d M %d Nc %d L %d)", who, index, d.S, d.M, d.Nc, d.L);
     return false;
   }
-  if ((d.M > 1 && d.a_rs < d.L) || (d.Nc > 1 && d.b_rs < d.L) || d.a_rs < 0 || d.b_rs < 0 || d.a_ns < 0 || d.b_ns < 0 ||
-      d.c_rs < d.Nc) {
-    set_error("curv_persample: item %d: invalid strides (a_rs %lld b_rs %lld below L %d, or c_rs %lld below Nc %d, or "
-              "negative)", index, d.a_rs, d.b_rs, d.L, d.c_rs, d.Nc);
+  if ((d.M > 1 && d.a_rs < d.L) || (d.Nc > 1 && d.b_rs < d.L) || d.a_rs < 0 || d.b_rs < 0 || d.a_ns < 0 || d.b_ns < 0) {
+    set_error("%s: item %d: invalid strides (a_rs %lld b_rs %lld below L %d, or negative)", who, index, d.a_rs, d.b_rs,
+              d.L);
     return false;
   }
   p->a_bytes = ((long long)(d.S - 1) * d.a_ns + (long long)(d.M - 1) * d.a_rs + d.L) * 4;
   p->b_bytes = ((long long)(d.S - 1) * d.b_ns + (long long)(d.Nc - 1) * d.b_rs + d.L) * 4;
   // voffset + soffset of the LDS-DMA reach at most 16 stages' worth behind the operand's end
   if (p->a_bytes >= PS_BYTES_MAX - 4096 || p->b_bytes >= PS_BYTES_MAX - 4096) {
-    set_error("curv_persample: item %d: operand too large for 32-bit offsets (%lld / %lld bytes, below %lld)", index,
+    set_error("%s: item %d: operand too large for 32-bit offsets (%lld / %lld bytes, below %lld)", who, index,
               p->a_bytes, p->b_bytes, PS_BYTES_MAX - 4096);
     return false;
   }
@@ -89,7 +119,7 @@ bool plan_of(const curv_persample_desc& d, int index, Plan* p) {
   p->tiles_n = cdiv(p->swap ? d.M : d.Nc, PS_TM);
   const long long tiles = (long long)p->tiles_m * p->tiles_n;
   if (tiles > (1 << 24)) {
-    set_error("curv_persample: item %d: too many output tiles (%lld)", index, tiles);
+    set_error("%s: item %d: too many output tiles (%lld)", who, index, tiles);
     return false;
   }
   p->tiles = (int)tiles;
@@ -100,8 +130,36 @@ bool plan_of(const curv_persample_desc& d, int index, Plan* p) {
   p->spi = std::min(d.S, std::max(cdiv(d.S, want), spi_min));
   p->slices = cdiv(d.S, p->spi);
   const int tile_rows = p->half ? PS_TM / 2 : PS_TM;
-  p->slab_bytes = align_up((size_t)p->slices * p->tiles * tile_rows * PS_TM * sizeof(float), 256);
   p->flops = 2LL * p->tiles * tile_rows * PS_TM * (long long)d.S * p->sps * nt::KC;
+  return true;
+}
+
+bool plan_of(const curv_persample_desc& d, int index, Plan* p) {
+  if (!tiling_of(d, "curv_persample", index, p)) return false;
+  if (d.c_rs < d.Nc) {
+    set_error("curv_persample: item %d: invalid strides (c_rs %lld below Nc %d)", index, d.c_rs, d.Nc);
+    return false;
+  }
+  const int tile_rows = p->half ? PS_TM / 2 : PS_TM;
+  p->slab_bytes = align_up((size_t)p->slices * p->tiles * tile_rows * PS_TM * sizeof(float), 256);
+  return true;
+}
+
+// (`slab_bytes`: the partials, one float per output tile and sample)
+bool quad_plan_of(const curv_persample_quad_desc& d, int index, Plan* p) {
+  if (!tiling_of(d, "curv_persample_quad", index, p)) return false;
+  // every staged row starts on a 16-byte boundary: the only form the library's own operands take and the only one tested
+  if (((d.a_ns | d.a_rs | d.b_ns | d.b_rs) & 3) != 0) {
+    set_error("curv_persample_quad: item %d: operand strides must be multiples of 4 floats (a_ns %lld a_rs %lld b_ns %lld "
+              "b_rs %lld)", index, d.a_ns, d.a_rs, d.b_ns, d.b_rs);
+    return false;
+  }
+  if ((d.W != nullptr && d.w_rs < d.Nc) || d.o_stride < 1) {
+    set_error("curv_persample_quad: item %d: invalid strides (w_rs %lld below Nc %d, or o_stride %lld below 1)", index,
+              d.w_rs, d.Nc, d.o_stride);
+    return false;
+  }
+  p->slab_bytes = align_up((size_t)p->tiles * d.S * sizeof(float), 256);
   return true;
 }
 
@@ -110,8 +168,19 @@ bool plan_of(const curv_persample_desc& d, int index, Plan* p) {
 // product whose A side has at most 64 rows): every wave takes all 64 A rows against B rows 32 wave .. + 32, 2 x 1 blocks -
 // half the MFMAs per stage instead of a half-empty tile.  C/D map of a 32x32 block: column = lane & 31, row = (reg & 3) +
 // 8 (reg >> 2) + 4 (lane >> 5).
-template <bool HALF>
-__device__ __forceinline__ void ps_product_tile(const PsProduct& d, int local, lds_char_t* lds) {
+//
+// What becomes of P_n at the end of a sample is the MODE.  PS_SQ (d a PsProduct): P_n**2 is added per entry into a second
+// accumulator set, which goes to the item's slab.  PS_QUAD_W / PS_QUAD_ONES (d a PsQuad): sum_ij W_ij P_n[i][j]**2 over the
+// tile - the second register set holds the lane's share of the W tile instead, loaded once per item, with zeros for the
+// rows and columns at or beyond M / Nc (W is not read for them); without W nothing is held and those entries are masked
+// by their index.  The lane sums its 64 entries, the wave reduces by butterfly, lane 0 of each wave leaves the wave's sum
+// in red[sample parity][wave], and behind the next barrier (the next stage's, or one after the last stage) thread 0 adds
+// the four in wave order and writes partial[tile][sample]: no barrier of its own, fixed order, no atomics.  The parity
+// keeps the waves that run ahead into the next sample's end off the four values thread 0 is still reading.
+enum { PS_SQ = 0, PS_QUAD_W = 1, PS_QUAD_ONES = 2 };
+
+template <bool HALF, int MODE, typename Product>
+__device__ __forceinline__ void ps_product_tile(const Product& d, int local, lds_char_t* lds, float* red) {
   constexpr int BN = HALF ? 1 : 2;                         // MFMA blocks per wave along the B side
   constexpr int TA = HALF ? PS_TM / 2 : PS_TM;             // A rows per tile
   constexpr int PA = TA / nt::RPP / 4;                     // DMA pieces per wave: A panel, then the B panel's
@@ -132,7 +201,8 @@ __device__ __forceinline__ void ps_product_tile(const PsProduct& d, int local, l
   const int rsub = nt::RPP * wave + (lane >> 3);
   const int g_lane = (lane & (nt::SLOTS - 1)) ^ ((rsub >> 1) & (nt::SLOTS - 1));
   int voff_a[PA], voff_b[nt::PIECES];
-  // rows beyond the matrix are clamped to its last row (their results are never stored)
+  // rows beyond the matrix are clamped to its last row (their results are never stored, and the PS_QUAD modes leave them
+  // out of the sums)
 #pragma unroll
   for (int p = 0; p < PA; ++p)
     voff_a[p] = (int)(((long long)min(i0 + 4 * nt::RPP * p + rsub, M - 1) * d.a_rs + 4 * g_lane) * 4);
@@ -155,11 +225,38 @@ __device__ __forceinline__ void ps_product_tile(const PsProduct& d, int local, l
       else addr_b[o - 2][j] = at;
     }
   }
-  f32x16 c[2][BN], q[2][BN];       // P_n of the running sample; the sum of P_n**2 over the finished samples
+  f32x16 c[2][BN], q[2][BN];       // P_n of the running sample; the sum of P_n**2 over the finished samples (PS_QUAD_W: W)
 #pragma unroll
   for (int m = 0; m < 2; ++m)
 #pragma unroll
     for (int nb = 0; nb < BN; ++nb) { c[m][nb] = 0.0f; q[m][nb] = 0.0f; }
+  // entry (m, nb, reg) of this lane is row i0 + row_a + 4 h + roff(m, reg), column j0 + row_b + 32 nb + r32 of the product
+  auto roff = [](int m, int reg) { return 32 * m + (reg & 3) + 8 * (reg >> 2); };
+  const int rows_left = M - (i0 + row_a + 4 * h);            // the entry is inside the product iff roff < rows_left ...
+  bool col_in[BN];                                           // ... and col_in[nb]
+#pragma unroll
+  for (int nb = 0; nb < BN; ++nb) col_in[nb] = j0 + row_b + 32 * nb + r32 < N;
+  if constexpr (MODE == PS_QUAD_W) {
+#pragma unroll
+    for (int m = 0; m < 2; ++m)
+#pragma unroll
+      for (int nb = 0; nb < BN; ++nb)
+#pragma unroll
+        for (int reg = 0; reg < 16; ++reg) {
+          const long long at = (long long)(i0 + row_a + 4 * h + roff(m, reg)) * d.w_is + (long long)(j0 + row_b + 32 * nb + r32) * d.w_js;
+          if (roff(m, reg) < rows_left && col_in[nb]) q[m][nb][reg] = d.W[at];
+        }
+  }
+  int flush = -1;                                            // the sample whose four wave sums wait in `red`
+  auto flush_sample = [&]() {
+    if constexpr (MODE != PS_SQ) {
+      if (flush >= 0 && tid == 0) {
+        const float* r = red + 4 * (flush & 1);
+        d.partial[(long long)tile * d.S + flush] = ((r[0] + r[1]) + r[2]) + r[3];
+      }
+      flush = -1;
+    }
+  };
 
   // A lane whose 16-byte group lies at or behind L - or any lane behind the item's last stage - carries an out-of-range
   // voffset (the descriptor's range check drops the fetch)
@@ -183,6 +280,7 @@ __device__ __forceinline__ void ps_product_tile(const PsProduct& d, int local, l
   for (int t = 0; t < n_stages; ++t) {
     __builtin_amdgcn_s_waitcnt(0x0f70);        // vmcnt(0): this wave's DMA of stage t has landed
     __syncthreads();
+    if constexpr (MODE != PS_SQ) flush_sample();
     int kn = kk + nt::KC, nn = n;
     const bool sample_ends = kn >= L;
     if (sample_ends) { kn = 0; ++nn; }
@@ -233,39 +331,94 @@ __device__ __forceinline__ void ps_product_tile(const PsProduct& d, int local, l
     }
     if (sample_ends) {
       // the sample boundary: square the tile of P_n, add it to the running sum, start the next sample from zero
+      if constexpr (MODE == PS_SQ) {
 #pragma unroll
-      for (int m = 0; m < 2; ++m)
+        for (int m = 0; m < 2; ++m)
 #pragma unroll
-        for (int nb = 0; nb < BN; ++nb) {
-          q[m][nb] += c[m][nb] * c[m][nb];
-          c[m][nb] = 0.0f;
-        }
+          for (int nb = 0; nb < BN; ++nb) {
+            q[m][nb] += c[m][nb] * c[m][nb];
+            c[m][nb] = 0.0f;
+          }
+      } else {
+        // ... or sum its (weighted) squares over the tile, this lane's 64 entries first
+        float v = 0.0f;
+#pragma unroll
+        for (int m = 0; m < 2; ++m)
+#pragma unroll
+          for (int nb = 0; nb < BN; ++nb) {
+#pragma unroll
+            for (int reg = 0; reg < 16; ++reg) {
+              const float p = c[m][nb][reg];
+              if constexpr (MODE == PS_QUAD_W) v += q[m][nb][reg] * p * p;
+              else v += (roff(m, reg) < rows_left && col_in[nb]) ? p * p : 0.0f;
+            }
+            c[m][nb] = 0.0f;
+          }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+        if (lane == 0) red[4 * (n & 1) + wave] = v;
+        flush = n;
+      }
     }
     n = nn;
     kk = kn;
   }
 
-  // raw partial tile, row-major TA x 128, to this item's slab (every entry is written)
-  gfl* slab = (gfl*)d.slabs + (long long)local * (TA * PS_TM);
+  if constexpr (MODE == PS_SQ) {
+    // raw partial tile, row-major TA x 128, to this item's slab (every entry is written)
+    gfl* slab = (gfl*)d.slabs + (long long)local * (TA * PS_TM);
 #pragma unroll
-  for (int m = 0; m < 2; ++m)
+    for (int m = 0; m < 2; ++m)
 #pragma unroll
-    for (int nb = 0; nb < BN; ++nb) {
-      const int col = row_b + 32 * nb + r32;
+      for (int nb = 0; nb < BN; ++nb) {
+        const int col = row_b + 32 * nb + r32;
 #pragma unroll
-      for (int reg = 0; reg < 16; ++reg) {
-        const int r = row_a + 32 * m + (reg & 3) + 8 * (reg >> 2) + 4 * h;
-        slab[r * PS_TM + col] = q[m][nb][reg];
+        for (int reg = 0; reg < 16; ++reg) {
+          const int r = row_a + 32 * m + (reg & 3) + 8 * (reg >> 2) + 4 * h;
+          slab[r * PS_TM + col] = q[m][nb][reg];
+        }
       }
-    }
+  } else {
+    __syncthreads();                 // the wave sums of the item's last sample
+    flush_sample();
+  }
 }
 
 __global__ void __launch_bounds__(PS_THREADS, 2) ps_product_kernel(const PsBatch batch) {
   __shared__ __attribute__((aligned(1024))) char smem[4 * nt::PANEL_B];   // [buffer][A panel, B panel] as gemm_nt.h
   const PsProduct& d = batch.e[owner_of(batch, (long long)blockIdx.x)];
   const int local = (int)(blockIdx.x - d.base);
-  if (d.half) ps_product_tile<true>(d, local, (lds_char_t*)smem);
-  else ps_product_tile<false>(d, local, (lds_char_t*)smem);
+  if (d.half) ps_product_tile<true, PS_SQ>(d, local, (lds_char_t*)smem, nullptr);
+  else ps_product_tile<false, PS_SQ>(d, local, (lds_char_t*)smem, nullptr);
+}
+
+// The same items for curv_persample_quad_reduce: partial[tile][sample] instead of a slab.
+__global__ void __launch_bounds__(PS_THREADS, 2) ps_quad_product_kernel(const PsQuadBatch batch) {
+  __shared__ __attribute__((aligned(1024))) char smem[4 * nt::PANEL_B];
+  __shared__ float red[8];                                                  // [sample parity][wave]
+  const PsQuad& d = batch.e[owner_of(batch, (long long)blockIdx.x)];
+  const int local = (int)(blockIdx.x - d.base);
+  if (d.half) {
+    if (d.W) ps_product_tile<true, PS_QUAD_W>(d, local, (lds_char_t*)smem, red);
+    else ps_product_tile<true, PS_QUAD_ONES>(d, local, (lds_char_t*)smem, red);
+  } else {
+    if (d.W) ps_product_tile<false, PS_QUAD_W>(d, local, (lds_char_t*)smem, red);
+    else ps_product_tile<false, PS_QUAD_ONES>(d, local, (lds_char_t*)smem, red);
+  }
+}
+
+// Reduce: one thread per sample sums the partials of its product in tile order, scales, writes or adds.  Blocks of a
+// product: ceil(S / 256).
+__global__ void __launch_bounds__(PS_THREADS) ps_quad_reduce_kernel(const PsQuadBatch batch) {
+  const PsQuad& d = batch.e[owner_of(batch, (long long)blockIdx.x)];
+  const long long s = (blockIdx.x - d.base) * PS_THREADS + threadIdx.x;
+  if (s >= d.S) return;
+  float v = 0.f;
+#pragma unroll 8
+  for (int t = 0; t < d.tiles; ++t) v += d.partial[(long long)t * d.S + s];
+  v *= d.alpha;
+  float* out = d.out + s * d.o_stride;
+  *out = d.first ? v : *out + v;
 }
 
 // Reduce: one thread per entry (i, j) of C; it sums the slab entries of its tile in slice order, scales, writes or adds.
@@ -397,6 +550,26 @@ PsProduct product_of(const curv_persample_desc& d, const Plan& p, float* slabs) 
   return P;
 }
 
+// The same for curv_persample_quad_reduce, its partials at `partial`.
+PsQuad quad_of(const curv_persample_quad_desc& d, const Plan& p, float* partial) {
+  PsQuad P;
+  P.A = d.A; P.B = d.B; P.W = d.W; P.out = d.out;
+  P.partial = partial;
+  P.a_ns = d.a_ns; P.a_rs = d.a_rs; P.b_ns = d.b_ns; P.b_rs = d.b_rs;
+  P.w_is = d.w_rs; P.w_js = 1; P.o_stride = d.o_stride;
+  P.S = d.S; P.M = d.M; P.Nc = d.Nc; P.L = d.L;
+  P.a_bytes = (unsigned)p.a_bytes; P.b_bytes = (unsigned)p.b_bytes;
+  if (p.swap) {
+    std::swap(P.A, P.B); std::swap(P.a_ns, P.b_ns); std::swap(P.a_rs, P.b_rs); std::swap(P.M, P.Nc);
+    std::swap(P.a_bytes, P.b_bytes); std::swap(P.w_is, P.w_js);
+  }
+  P.tiles_n = p.tiles_n; P.tiles = p.tiles; P.spi = p.spi; P.slices = p.slices;
+  P.half = p.half; P.swap = p.swap;
+  P.first = d.first ? 1 : 0; P.alpha = d.alpha;
+  P.base = 0;
+  return P;
+}
+
 }  // namespace
 }  // namespace curv
 
@@ -435,6 +608,48 @@ extern "C" int curv_persample_sq_accumulate(void* stream_, const curv_persample_
         hipLaunchKernelGGL(ps_product_kernel, dim3(grid[0]), dim3(PS_THREADS), 0, stream, b[0]);
         CURV_LAUNCH_CHECK();
         hipLaunchKernelGGL(ps_reduce_kernel, dim3(grid[1]), dim3(PS_THREADS), 0, stream, b[1]);
+        CURV_LAUNCH_CHECK();
+        return CURV_OK;
+      });
+}
+
+extern "C" size_t curv_persample_quad_workspace_bytes(const curv_persample_quad_desc* descs, int n) {
+  return side::workspace_bytes("curv_persample_quad_workspace_bytes", descs, n, quad_plan_of, bytes_of);
+}
+
+extern "C" int curv_persample_quad_plan_flops(const curv_persample_quad_desc* descs, int n, long long* out) {
+  return side::plan_flops("curv_persample_quad_plan_flops", descs, n, out, quad_plan_of);
+}
+
+extern "C" int curv_persample_quad_reduce(void* stream_, const curv_persample_quad_desc* descs, int n, void* workspace,
+                                          size_t workspace_bytes) {
+  const char* const name = "curv_persample_quad_reduce";
+  if (n <= 0) return CURV_OK;
+  hipStream_t stream = (hipStream_t)stream_;
+  std::vector<Plan> plans;
+  if (!side::plans_of(name, descs, n, quad_plan_of, &plans)) return CURV_ERR_INVALID;
+  for (int i = 0; i < n; ++i) {
+    CURV_REQUIRE(descs[i].A && descs[i].B && descs[i].out, "%s: item %d: null operand", name, i);
+    CURV_REQUIRE(((reinterpret_cast<uintptr_t>(descs[i].A) | reinterpret_cast<uintptr_t>(descs[i].B)) & 15) == 0,
+                 "%s: item %d: A and B must be 16-byte aligned", name, i);
+  }
+  const int rc = side::require_workspace(name, workspace, workspace_bytes, bytes_of(plans), 256);
+  if (rc != CURV_OK) return rc;
+  size_t at = 0;
+  // one walk, two launches, as curv_persample_sq_accumulate: the items of the product launch, the blocks of the reduce
+  return for_arg_batches<PsQuad, PS_BATCH, 2>(
+      n, name,
+      [&](int i, PsQuad* P, long long* units) {
+        *P = quad_of(descs[i], plans[i], (float*)((char*)workspace + at));
+        at += plans[i].slab_bytes;
+        units[0] = (long long)plans[i].tiles * plans[i].slices;
+        units[1] = cdivll(descs[i].S, PS_THREADS);
+      },
+      [](int, long long units) { return units; },
+      [&](const PsQuadBatch* b, const long long*, const unsigned* grid) {
+        hipLaunchKernelGGL(ps_quad_product_kernel, dim3(grid[0]), dim3(PS_THREADS), 0, stream, b[0]);
+        CURV_LAUNCH_CHECK();
+        hipLaunchKernelGGL(ps_quad_reduce_kernel, dim3(grid[1]), dim3(PS_THREADS), 0, stream, b[1]);
         CURV_LAUNCH_CHECK();
         return CURV_OK;
       });

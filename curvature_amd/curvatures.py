@@ -512,12 +512,11 @@ class Curvature(ABC):
     def _save_output(self, module, grad_output):
         self.record[module][1] = grad_output         # raw; the reference stores grad * N (curvatures.py:310)
 
-    def _record_per_sample(self, what: str) -> None:
-        """``per_sample=True`` of Diagonal / EFB: check that every selected layer has a per-sample form and register
-        KFAC's recording hooks on it."""
-        self.hooks = list()
-        self.record = dict()
+    def _per_sample_layers(self, what: str, advice: str) -> List[Module]:
+        """The selected layers, in ``modules()`` order, after checking that every one has a per-sample form P_n = g_n X_n^T:
+        Linear, and Conv2d with groups 1, dilation 1 and integer padding.  Any other raises NotImplementedError naming it."""
         names = {mod: name for name, mod in self.model.named_modules()}
+        layers = []
         for layer in self.model.modules():
             kind = layer.__class__.__name__
             if kind not in self.layer_types:
@@ -533,15 +532,24 @@ class Curvature(ABC):
             elif kind != 'Linear':
                 why = kind
             if why is not None:
-                raise NotImplementedError(f"{what}(per_sample=True): layer '{names.get(layer, '?')}' is not supported ({why}); "
-                                          "select other layer types or use per_sample=False")
+                raise NotImplementedError(f"{what}: layer '{names.get(layer, '?')}' is not supported ({why}); {advice}")
+            layers.append(layer)
+        return layers
+
+    def _record_per_sample(self, what: str) -> None:
+        """``per_sample=True`` of Diagonal / EFB: check that every selected layer has a per-sample form and register
+        KFAC's recording hooks on it."""
+        self.hooks = list()
+        self.record = dict()
+        for layer in self._per_sample_layers(f"{what}(per_sample=True)", "select other layer types or use per_sample=False"):
             self._record_layer(layer)
 
-    def _per_sample_operands(self, what: str, layers, **layout):
+    def _per_sample_operands(self, what: str, layers, x_side: bool = True, **layout):
         """The per-sample operands of `layers` from their records, packed where they cannot be read in place:
         [(sides, g tensor, x tensor)] with `sides` the `ops.PerSampleSides` whose strides address the two tensors.  A missing
         record raises like KFAC's; CPU records raise RuntimeError (no fallback).  The packed copies live in shared scratch:
-        they are valid until the next per-sample update on this stream."""
+        they are valid until the next per-sample update on this stream.  ``x_side=False``: only the g side is packed (the x
+        tensor comes back as None), into scratch of its own, so that the x side of the call before stays valid."""
         sides = []
         for layer in layers:
             forward, backward = self.record[layer]
@@ -553,11 +561,14 @@ class Curvature(ABC):
                 if not t.is_cuda:
                     raise RuntimeError("curvature_amd runs on MI355X only: got a CPU tensor (no CPU fallback)")
             sides.append(ops.per_sample_operands(layer, forward, backward, **layout))
-        flat = [op for s in sides for op in (s.g, s.x)]
-        bufs = ops.per_sample_scratch([op.floats for op in flat], flat[0].src.device)
+        flat = [op for s in sides for op in ((s.g, s.x) if x_side else (s.g,))]
+        bufs = ops.per_sample_scratch([op.floats for op in flat], flat[0].src.device,
+                                      "persample_x" if x_side else "persample_g")
         packed = [(op, buf) for op, buf in zip(flat, bufs) if op.pack is not None]
         ops.per_sample_pack([op for op, _ in packed], [buf for _, buf in packed])
         tensors = [buf if op.pack is not None else op.src for op, buf in zip(flat, bufs)]
+        if not x_side:
+            return [(s, tensors[k], None) for k, s in enumerate(sides)]
         return [(s, tensors[2 * k], tensors[2 * k + 1]) for k, s in enumerate(sides)]
 
     @staticmethod
@@ -565,6 +576,84 @@ class Curvature(ABC):
         """dst (+)= alpha * sum_n (g_n x_n^T)**2 for operands laid out as `sides` says."""
         return ops.PerSampleJob(g, x, dst, sides.N, sides.m, sides.n, sides.L, sides.g.ns, sides.g.rs, sides.x.ns,
                                 sides.x.rs, alpha=alpha, first=first)
+
+    # ------------------------------------------------------------------ linearised (GLM) predictive
+    def functional_variance(self, out: Tensor, *, first: bool = True, inputs: bool = True) -> Tensor:
+        """The variance of a network output under the posterior this estimator samples from, linearised in the weights:
+        with P_n the Jacobian of the output for sample n with respect to a layer's [W | b], adds ``sum_layers v_layer[n]``
+        into ``out[n]`` (overwrites it when `first`), v_layer[n] the variance of ``<P_n, sample(layer)>``:
+
+            KFAC      ||L_G^T P_n L_A||_F**2
+            Diagonal  sum_ij inv_ij**2 P_n[i, j]**2
+            EFB       sum_ij inv_ij**2 (U_G^T P_n U_A)[i, j]**2
+
+        P_n = g_n X_n^T comes from the current records: the layer inputs of the last forward pass and the raw grad_outputs
+        of the last backward pass, which the caller ran on ``output[:, c].sum()`` for the output c in question (in ``eval()``
+        mode, so that the samples of the batch are independent; `evaluate.glm_predictive` drives this).  No weights are
+        sampled and no P_n is written (`ops.per_sample_quad_reduce`).  `out`: a length-N float32 GPU view of any stride (a
+        column of an (N, classes) matrix).  ``inputs=False`` reuses the X side of the previous call - rotated into the
+        posterior's basis once per forward pass, not once per output - like ``KFAC.update(inputs=False)``; it raises
+        RuntimeError unless the recorded inputs are the very tensors of that call, and nothing else may have used the
+        per-sample scratch in between.  The kept X side (the unfolded inputs of every layer) stays on the estimator as
+        ``_variance_inputs`` until the next ``inputs=True`` call replaces it; `evaluate.glm_predictive` drops it.  Linear and Conv2d (groups 1, dilation 1, integer padding) with
+        float32 GPU records; other selected layers raise NotImplementedError, as does a layer-sharded estimator.
+        Implemented by KFAC, Diagonal and EFB.  No counterpart in the reference, which has the Monte-Carlo predictive only."""
+        raise NotImplementedError(f"{type(self).__name__}.functional_variance: no linearised predictive for this estimator "
+                                  "(KFAC, Diagonal and EFB have one)")
+
+    def _functional_variance(self, what: str, out: Tensor, first: bool, inputs: bool, basis, weights) -> Tensor:
+        """`functional_variance` of the three estimators.  ``basis(layer)`` = (R_G, R_A), the rotations T = R_G g and
+        Y = R_A X of the packed (rows, N Lp) operands, or `basis` None (no rotation: the operands are read where they are);
+        ``weights(layer)`` = the (m, n) tensor whose square weighs the entries, or `weights` None (all ones)."""
+        assert self.inv_state, "Inverse state dict is empty. Did you call 'invert' prior to this?"
+        if self.shard is not None and self.shard.world > 1:
+            raise NotImplementedError(f"{what}.functional_variance: layer-sharded estimators are not supported")
+        if getattr(self, "record", None) is None:
+            raise RuntimeError(f"{what}.functional_variance: no recording hooks (construct with per_sample=True, or go "
+                               "through evaluate.glm_predictive)")
+        layers = self._per_sample_layers(f"{what}.functional_variance", "select other layer types")
+        layers = [l for l in layers if l in self.inv_state]
+        assert layers, "Inverse state dict holds none of the selected layers"
+        layout = dict(rows_outer=True, in_place=False) if basis is not None else {}
+        operands = self._per_sample_operands(what, layers, x_side=inputs, **layout)
+        dev, N = operands[0][1].device, operands[0][0].N
+        if out.dim() != 1 or out.shape[0] != N or out.dtype != torch.float32 or not out.is_cuda:
+            raise RuntimeError(f"{what}.functional_variance: out must be a float32 GPU view of length {N}, got "
+                               f"{tuple(out.shape)} {out.dtype} on {out.device}")
+        # the kept X side belongs to the recorded inputs themselves (tensor and version), not just to their shapes
+        key = tuple((l, id(self.record[l][0]), self.record[l][0]._version, s.n, s.N, s.L, s.x.ns, s.x.rs)
+                    for l, (s, _, _) in zip(layers, operands))
+        if inputs:
+            self._variance_inputs = None                       # (the X side of other records goes first)
+            # what depends on the forward pass and the posterior only: X (rotated) and the squared weights
+            xs = [x for _, _, x in operands]
+            if basis is not None:
+                xs = [torch.empty(x.numel(), dtype=torch.float32, device=dev) for x in xs]
+                ops.gemm_batched([ops.Gemm(basis(l)[1], x.view(s.n, -1), y.view(s.n, -1))
+                                  for l, (s, _, x), y in zip(layers, operands, xs)])
+            ws = [None] * len(layers)
+            if weights is not None:
+                ws = [ops.mul(weights(l), weights(l)) for l in layers]
+            self._variance_inputs = (key, xs, ws)
+        kept = getattr(self, "_variance_inputs", None)
+        if kept is None or kept[0] != key:
+            raise RuntimeError(f"{what}.functional_variance(inputs=False): no call with inputs=True on these recorded inputs "
+                               "before (a new forward pass needs inputs=True once)")
+        _, xs, ws = kept
+        gs = [g for _, g, _ in operands]
+        if basis is not None:
+            gs = [torch.empty(g.numel(), dtype=torch.float32, device=dev) for g in gs]
+            ops.gemm_batched([ops.Gemm(basis(l)[0], g.view(s.m, -1), t.view(s.m, -1))
+                              for l, (s, g, _), t in zip(layers, operands, gs)])
+        # every layer into its own row, the rows summed in layer order by one product with a row of ones: the result does
+        # not depend on how the layers are grouped into launches
+        rows = torch.empty(len(layers), N, dtype=torch.float32, device=dev)
+        ops.per_sample_quad_reduce([ops.PerSampleQuadJob(g, x, w, rows[k], s.N, s.m, s.n, s.L, s.g.ns, s.g.rs, s.x.ns, s.x.rs,
+                                                         first=True)
+                                    for k, ((s, _, _), g, x, w) in enumerate(zip(operands, gs, xs, ws))])
+        ones = torch.ones(1, len(layers), dtype=torch.float32, device=dev)
+        ops.gemm_batched([ops.Gemm(ones, rows, out.unsqueeze(0), beta=0.0 if first else 1.0)])
+        return out
 
     @staticmethod
     def _replace(sample: Tensor, weight: Tensor, bias: Tensor = None):
@@ -777,6 +866,9 @@ class Diagonal(Curvature):
         if prev is not None and prev.shape == like.shape and prev.device == like.device and prev.is_contiguous():
             return prev
         return None
+
+    def functional_variance(self, out: Tensor, *, first: bool = True, inputs: bool = True) -> Tensor:
+        return self._functional_variance("Diagonal", out, first, inputs, None, lambda layer: self.inv_state[layer])
 
     def sample(self, layer: Union[Module, str], z: Optional[Tensor] = None) -> Tensor:
         assert self.inv_state, "Inverse state dict is empty. Did you call 'invert' prior to this?"
@@ -1166,6 +1258,11 @@ class KFAC(Curvature):
                     self._raise_not_pd(info, exc)
                 raise
 
+    def functional_variance(self, out: Tensor, *, first: bool = True, inputs: bool = True) -> Tensor:
+        # sample = L_G Z L_A^T: T = L_G^T g, Y = L_A^T X
+        return self._functional_variance("KFAC", out, first, inputs,
+                                         lambda layer: tuple(f.t() for f in reversed(self.inv_state[layer])), None)
+
     def sample(self, layer: Module, z: Optional[Tensor] = None) -> Tensor:
         """(L_A z L_G^T)^T -> (m, n) (curvatures.py:387-392); `z` (n, m) may be supplied for parity tests."""
         assert self.inv_state, "Inverse state dict is empty. Did you call 'invert' prior to this?"
@@ -1500,6 +1597,11 @@ class EFB(Curvature):
         for position, (layer, value) in enumerate(zip(layers, values)):
             n, s = self._hyper(add, multiply, gindex.get(layer, position), max(len(gindex), len(layers)))
             ops.rsqrt_affine(value, n, s, out=self.inv_state[layer])
+
+    def functional_variance(self, out: Tensor, *, first: bool = True, inputs: bool = True) -> Tensor:
+        # sample = U_G (Z * inv) U_A^T: T = U_G^T g, Y = U_A^T X, as `_update_per_sample`
+        return self._functional_variance("EFB", out, first, inputs, lambda layer: self._eigvecs_t(layer)[::-1],
+                                         lambda layer: self.inv_state[layer])
 
     def sample(self, layer: Module, z: Optional[Tensor] = None) -> Tensor:
         """(U_A (z * inv^T) U_G^T)^T = U_G (z^T * inv) U_A^T -> (m, n) (curvatures.py:453-460)."""

@@ -19,6 +19,7 @@ thread that enqueues the sample, and a tiny model pays for re-pointing its state
 the serial loop, and the pipelined one is switched on only for a layer-sharded estimator, where it takes the
 all-gather of the sampled parameters (a wait on the other ranks, not local work) off the forward stream.
 """
+import math
 from typing import Iterable, List, Tuple
 
 import torch
@@ -164,3 +165,51 @@ def eval_bnn(model: torch.nn.Module, dataset: Iterable, estimator, samples: int 
             _drop_plans_for(estimator, sets.sets[1])
         mean_predictions = mean_predictions / samples
     return mean_predictions.cpu().numpy(), labels.numpy()
+
+
+def glm_predictive(model: torch.nn.Module, estimator, images: torch.Tensor, outputs=None):
+    """The linearised-Laplace (GLM) predictive of one batch: ``(logits, variance, probs)``, each (N, classes).
+
+    ``variance[n, c]`` is the closed-form variance of output c for input n under the posterior `estimator` samples from,
+    with the network linearised in its weights at their mean (`Curvature.functional_variance`: KFAC, Diagonal, EFB);
+    ``probs = softmax(logits / sqrt(1 + pi / 8 * variance))`` is the probit approximation of the expected softmax.  No
+    weights are sampled: one forward pass, then for every output c in `outputs` (default: all; the variance of the
+    others stays 0) one backward pass of ``logits[:, c].sum()`` and one `functional_variance` call - the side of it that
+    depends on the layer inputs only is worked out for the first output and reused for the others.
+
+    The model is put into ``eval()`` mode, which makes the samples of the batch independent under BatchNorm: the
+    gradient of ``sum_n f_c(x_n)`` then splits into the per-sample Jacobians the variance is made of.  A Diagonal / EFB
+    built without ``per_sample=True`` gets the recording hooks for the length of the call.  The parameters and their
+    ``.grad`` are left as they were found (the backward passes are `torch.autograd.grad` calls on the parameters that
+    require grad; a selected layer they do not reach raises RuntimeError).  GPU only (RuntimeError for a CPU model: no fallback)."""
+    first_param = next(model.parameters())
+    if not first_param.is_cuda or not images.is_cuda:
+        raise RuntimeError("curvature_amd runs on MI355X only: glm_predictive got a CPU model or batch (no CPU fallback)")
+    model.eval()
+    borrowed = getattr(estimator, "record", None) is None
+    params = [p for p in model.parameters() if p.requires_grad]
+    try:
+        if borrowed:
+            estimator._record_per_sample(type(estimator).__name__)
+        logits = model(images)
+        if logits.dim() != 2:
+            raise RuntimeError(f"glm_predictive: the model must return (N, classes) logits, got {tuple(logits.shape)}")
+        classes = list(range(logits.shape[1])) if outputs is None else [int(c) for c in outputs]
+        variance = torch.zeros(logits.shape, dtype=torch.float32, device=logits.device)
+        for k, c in enumerate(classes):
+            # (torch.autograd.grad fills the recording hooks like backward(), and touches no .grad.  A selected layer the
+            # pass does not reach - frozen parameters behind inputs that need no grad - records nothing: its stale
+            # grad_output is cleared first, so that `functional_variance` raises instead of using it)
+            for pair in estimator.record.values():
+                pair[1] = None
+            torch.autograd.grad(logits[:, c].sum(), params, retain_graph=True, allow_unused=True)
+            estimator.functional_variance(variance[:, c], inputs=k == 0)
+    finally:
+        if borrowed:
+            for hook in estimator.hooks:
+                hook.remove()
+            del estimator.hooks, estimator.record
+        estimator.__dict__.pop("_variance_inputs", None)       # the X side of this batch
+    logits = logits.detach()
+    probs = torch.softmax(logits.float() / torch.sqrt(1.0 + (math.pi / 8.0) * variance), dim=1)
+    return logits, variance, probs

@@ -612,16 +612,75 @@ def per_sample_sq_accumulate(jobs: Sequence[PerSampleJob]) -> None:
                jobs[0].C.device, "persample")
 
 
-def per_sample_scratch(floats: Sequence[int], device) -> List[torch.Tensor]:
-    """One float32 buffer of each given size (0: None), carved 256-byte aligned out of the "persample_x" workspace: the
-    packed operands of one `update()`; valid until the next call."""
+class PerSampleQuadJob:
+    """out[n] (+)= alpha * sum_ij W[i, j] * (A_n B_n^T)[i, j]**2 for `S` samples: A, B and their sizes and strides as in
+    `PerSampleJob`; `W` an (M, Nc) view with unit column stride or None (all ones); `out` a length-S float32 view of any
+    stride (a column of an (N, classes) matrix).  `first`: overwrite out.  A / B / out may also be `None` with explicit
+    sizes (plan queries)."""
+    __slots__ = ("A", "B", "W", "out", "S", "M", "Nc", "L", "a_ns", "a_rs", "b_ns", "b_rs", "alpha", "first")
+
+    def __init__(self, A, B, W, out, S, M, Nc, L, a_ns, a_rs, b_ns, b_rs, alpha=1.0, first=False):
+        self.A, self.B, self.W, self.out = A, B, W, out
+        self.S, self.M, self.Nc, self.L = int(S), int(M), int(Nc), int(L)
+        self.a_ns, self.a_rs, self.b_ns, self.b_rs = int(a_ns), int(a_rs), int(b_ns), int(b_rs)
+        self.alpha, self.first = float(alpha), bool(first)
+
+
+def _per_sample_quad_descs(jobs: Sequence[PerSampleQuadJob], check_tensors: bool = True):
+    arr = (_lib.curv_persample_quad_desc * len(jobs))()
+    for d, j in zip(arr, jobs):
+        d.S, d.M, d.Nc, d.L = j.S, j.M, j.Nc, j.L
+        d.a_ns, d.a_rs, d.b_ns, d.b_rs = j.a_ns, j.a_rs, j.b_ns, j.b_rs
+        d.alpha, d.first = j.alpha, int(j.first)
+        d.w_rs, d.o_stride = j.Nc, 1
+        if check_tensors:
+            for t in (j.A, j.B, j.out) + (() if j.W is None else (j.W,)):
+                if not t.is_cuda:
+                    raise RuntimeError("curvature_amd runs on MI355X only: got a CPU tensor (no CPU fallback)")
+                if t.dtype != torch.float32:
+                    raise RuntimeError(f"curvature_amd expects float32 tensors, got {t.dtype}")
+            if j.W is not None:
+                if j.W.dim() != 2 or tuple(j.W.shape) != (j.M, j.Nc) or j.W.stride(1) != 1:
+                    raise RuntimeError(f"per_sample_quad_reduce: weights must be an ({j.M},{j.Nc}) view with unit column "
+                                       f"stride, got {tuple(j.W.shape)}")
+                d.W, d.w_rs = j.W.data_ptr(), j.W.stride(0)
+            if j.out.dim() != 1 or j.out.shape[0] != j.S or (j.S > 1 and j.out.stride(0) < 1):
+                raise RuntimeError(f"per_sample_quad_reduce: destination must be a length-{j.S} view with a positive "
+                                   f"stride, got {tuple(j.out.shape)}")
+            a_need = (j.S - 1) * j.a_ns + (j.M - 1) * j.a_rs + j.L
+            b_need = (j.S - 1) * j.b_ns + (j.Nc - 1) * j.b_rs + j.L
+            if j.A.numel() < a_need or j.B.numel() < b_need:
+                raise RuntimeError("per_sample_quad_reduce: an operand is smaller than its sizes and strides say")
+            d.A, d.B, d.out = j.A.data_ptr(), j.B.data_ptr(), j.out.data_ptr()
+            d.o_stride = max(j.out.stride(0), 1)
+    return arr
+
+
+def per_sample_quad_plan_flops(jobs: Sequence[PerSampleQuadJob]) -> List[int]:
+    """Multiply-add FLOPs (2 per multiply-add) the plan executes per job (curv_persample_quad_plan_flops, host only)."""
+    if not jobs:
+        return []
+    return _plan_flops("curv_persample_quad_plan_flops", _per_sample_quad_descs(jobs, check_tensors=False), len(jobs))
+
+
+def per_sample_quad_reduce(jobs: Sequence[PerSampleQuadJob]) -> None:
+    """curv_persample_quad_reduce over any number of products, on the current stream; partials from `workspace`."""
+    if not jobs:
+        return
+    _run_build("curv_persample_quad_workspace_bytes", "curv_persample_quad_reduce", _per_sample_quad_descs(jobs),
+               len(jobs), jobs[0].out.device, "persample")
+
+
+def per_sample_scratch(floats: Sequence[int], device, tag: str = "persample_x") -> List[torch.Tensor]:
+    """One float32 buffer of each given size (0: None), carved 256-byte aligned out of the `tag` workspace: the
+    packed operands of one `update()`; valid until the next call with that tag."""
     offs, at = [], 0
     for f in floats:
         offs.append(at)
         at += (int(f) * 4 + 255) // 256 * 256
     if at == 0:
         return [None] * len(offs)
-    ws = workspace(at, device, "persample_x")
+    ws = workspace(at, device, tag)
     return [ws[o:o + int(f) * 4].view(torch.float32) if f else None for o, f in zip(offs, floats)]
 
 

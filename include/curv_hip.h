@@ -517,6 +517,48 @@ typedef struct curv_persample_pack_desc {
   int32_t Lp;
 } curv_persample_pack_desc;
 int curv_persample_pack(void* stream, const curv_persample_pack_desc* descs, int n);
+
+/* ------------------------------------------------------------------------------------------------
+ * Linearised Laplace (GLM) predictive: the other reduction of the per-sample products (csrc/persample.hip) - over the
+ * entries of P_n = A_n B_n^T, per sample:
+ *     out[s*o_stride] (+)= alpha * sum_{i < M, j < Nc} W[i*w_rs + j] * ( sum_{l < L} A[s*a_ns + i*a_rs + l] * B[s*b_ns + j*b_rs + l] )**2
+ * With A = the layer's grad_output g_n when sum_n f_c(x_n) is back-propagated and B = X_n, P_n is the Jacobian of
+ * output c for sample s with respect to [W | b], and the sum is the layer's share of the variance of f_c(x_s) under the
+ * posterior an estimator samples from (no reference counterpart: the reference only offers the Monte-Carlo predictive):
+ *     KFAC      sample L_G Z L_A^T              A = L_G^T g,  B = L_A^T X,  W = NULL
+ *     Diagonal  sample Z * inv                  A = g,        B = X,        W = inv**2
+ *     EFB       sample U_G (Z * inv) U_A^T      A = U_G^T g,  B = U_A^T X,  W = inv**2
+ * A, B, S, M, Nc, L and the four operand strides are those of curv_persample_desc, with the same rules (operand
+ * extents below 2^31 bytes, l values at or behind L never enter a product, whole 16-byte groups are fetched) and one
+ * more: A and B are 16-byte aligned and a_ns, a_rs, b_ns, b_rs are multiples of 4 floats, so that every row starts on
+ * a 16-byte boundary (CURV_ERR_INVALID otherwise) - what curv_persample_pack writes and what an operand read in place
+ * with L % 4 == 0 has.  W is
+ * M x Nc with row stride w_rs >= Nc, or NULL for all ones; it is never read outside its M x Nc entries.  out is S values
+ * o_stride >= 1 floats apart (a column of an (N, classes) matrix); `first` != 0 overwrites them.  fp32 MFMA, fp32 sums
+ * in a fixed order (lane, wave, workgroup, then tiles in tile order), no atomics; the plan of an item follows from its
+ * own sizes only, so its bits do not depend on the other items of the call.  Enqueues on `stream` only, never waits on
+ * the host, allocates nothing.  An empty call is a no-op; invalid sizes or strides return CURV_ERR_INVALID with the
+ * item named.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct curv_persample_quad_desc {
+  const float* A;
+  const float* B;
+  const float* W;          /* may be NULL */
+  float* out;
+  long long a_ns, a_rs, b_ns, b_rs, w_rs, o_stride;
+  int32_t S, M, Nc, L;
+  int32_t first;
+  float alpha;
+} curv_persample_quad_desc;
+/* Device scratch for these items (bytes: one float per output tile and sample); 0 with the error text set (naming the
+ * item) for invalid sizes.  Host only. */
+size_t curv_persample_quad_workspace_bytes(const curv_persample_quad_desc* descs, int n);
+/* Host only: the multiply-add FLOPs the plan executes per item (as curv_persample_plan_flops: at least 2 S M Nc L). */
+int curv_persample_quad_plan_flops(const curv_persample_quad_desc* descs, int n, long long* out);
+/* An MFMA and a reduce launch per batch of up to 16 items.  The workspace must be 256-byte aligned.  `descs` is a host
+ * array; it may be reused as soon as the call returns. */
+int curv_persample_quad_reduce(void* stream, const curv_persample_quad_desc* descs, int n, void* workspace,
+                               size_t workspace_bytes);
 /* v = max(v, 0) in place      curvatures.py:523 */
 int curv_clamp_min0(void* stream, float* v, long long count);
 /* out = sqrt(s*v)             curvatures.py:525 */
