@@ -1,5 +1,5 @@
-// The 128 x 128 NT tile product of the fp32 GEMMs (gemm.hip: samplers, EFB) as a header, because the inversion sweep
-// (invert.hip: the fp32 accumulation of the triangular inverse) runs its rank-K updates through the same tile code.
+// The 128 x 128 NT tile product of the fp32 GEMMs (gemm.hip: samplers, EFB) as a header, because the per-sample products
+// (persample.hip: the exact Fisher and the linearised predictive) stage their panels with the same constants and swizzle.
 #pragma once
 #include "common.h"
 

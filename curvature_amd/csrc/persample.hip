@@ -44,12 +44,11 @@ constexpr int PS_ITEMS_TARGET = 512;           // a product is cut into sample r
 constexpr int PS_STAGES_MIN = 64;              // ... of at least 64 stages
 constexpr long long PS_BYTES_MAX = 1LL << 31;  // operand extents: 32-bit buffer offsets
 
-struct PsProduct {
+// What both kinds of product share: the operands and their tiling, as operands_of fills them.
+struct PsOperands {
   const float* A;
   const float* B;
-  float* C;
-  float* slabs;
-  long long a_ns, a_rs, b_ns, b_rs, c_rs;
+  long long a_ns, a_rs, b_ns, b_rs;
   int S, M, Nc, L;             // as the product kernel sees them: A and B have changed places when `swap`
   int tiles_n, tiles;          // output tiles: tiles = tiles_m tiles_n
   int spi, slices;             // samples per item, sample ranges
@@ -60,26 +59,22 @@ struct PsProduct {
   long long base;              // first item / reduce block of this product in the launch
 };
 
+struct PsProduct : PsOperands {
+  float* C;
+  float* slabs;
+  long long c_rs;
+};
+
 typedef ArgBatch<PsProduct, PS_BATCH> PsBatch;
 
-// A product of curv_persample_quad_reduce: the same operands and tiling; instead of C and slabs the weights W (entry
-// (i, j) of the tile the kernel computes at W[i w_is + j w_js]: the strides change places with the operands when `swap`),
-// the fp32 `partial`[tile][sample] and the S outputs.
-struct PsQuad {
-  const float* A;
-  const float* B;
+// A product of curv_persample_quad_reduce: instead of C and slabs the weights W (entry (i, j) of the tile the kernel
+// computes at W[i w_is + j w_js]: the strides change places with the operands when `swap`), the fp32
+// `partial`[tile][sample] and the S outputs.
+struct PsQuad : PsOperands {
   const float* W;              // may be null: all ones
   float* out;
   float* partial;
-  long long a_ns, a_rs, b_ns, b_rs, w_is, w_js, o_stride;
-  int S, M, Nc, L;
-  int tiles_n, tiles;
-  int spi, slices;
-  int half, swap;
-  int first;
-  float alpha;
-  unsigned a_bytes, b_bytes;
-  long long base;              // first item / reduce block of this product in the launch
+  long long w_is, w_js, o_stride;
 };
 
 typedef ArgBatch<PsQuad, PS_BATCH> PsQuadBatch;
@@ -455,6 +450,8 @@ struct PsPack {
 };
 
 typedef ArgBatch<PsPack, PS_BATCH> PsPackBatch;
+static_assert(sizeof(PsBatch) <= 3840 && sizeof(PsQuadBatch) <= 3840 && sizeof(PsPackBatch) <= 3840,
+              "kernel argument block must stay below 4 KB");
 
 bool pack_plan_of(const curv_persample_pack_desc& d, int index, PsPack* out) {
   side::ConvGeom g;
@@ -531,12 +528,13 @@ size_t bytes_of(const std::vector<Plan>& plans) {
   return total;
 }
 
-// The product of `d` as the kernels see it, its slabs at `slabs`.
-PsProduct product_of(const curv_persample_desc& d, const Plan& p, float* slabs) {
-  PsProduct P;
-  P.A = d.A; P.B = d.B; P.C = d.C;
-  P.slabs = slabs;
-  P.a_ns = d.a_ns; P.a_rs = d.a_rs; P.b_ns = d.b_ns; P.b_rs = d.b_rs; P.c_rs = d.c_rs;
+// A Product (PsProduct / PsQuad) with the operands of `d` as the kernels see them; its own fields are the caller's.  The
+// one place where A and B change places.
+template <typename Product, typename Desc>
+Product operands_of(const Desc& d, const Plan& p) {
+  Product P;
+  P.A = d.A; P.B = d.B;
+  P.a_ns = d.a_ns; P.a_rs = d.a_rs; P.b_ns = d.b_ns; P.b_rs = d.b_rs;
   P.S = d.S; P.M = d.M; P.Nc = d.Nc; P.L = d.L;
   P.a_bytes = (unsigned)p.a_bytes; P.b_bytes = (unsigned)p.b_bytes;
   if (p.swap) {
@@ -550,24 +548,57 @@ PsProduct product_of(const curv_persample_desc& d, const Plan& p, float* slabs) 
   return P;
 }
 
+// The product of `d`, its slabs at `slabs`.
+PsProduct product_of(const curv_persample_desc& d, const Plan& p, float* slabs) {
+  PsProduct P = operands_of<PsProduct>(d, p);
+  P.C = d.C; P.slabs = slabs; P.c_rs = d.c_rs;
+  return P;
+}
+
 // The same for curv_persample_quad_reduce, its partials at `partial`.
 PsQuad quad_of(const curv_persample_quad_desc& d, const Plan& p, float* partial) {
-  PsQuad P;
-  P.A = d.A; P.B = d.B; P.W = d.W; P.out = d.out;
-  P.partial = partial;
-  P.a_ns = d.a_ns; P.a_rs = d.a_rs; P.b_ns = d.b_ns; P.b_rs = d.b_rs;
-  P.w_is = d.w_rs; P.w_js = 1; P.o_stride = d.o_stride;
-  P.S = d.S; P.M = d.M; P.Nc = d.Nc; P.L = d.L;
-  P.a_bytes = (unsigned)p.a_bytes; P.b_bytes = (unsigned)p.b_bytes;
-  if (p.swap) {
-    std::swap(P.A, P.B); std::swap(P.a_ns, P.b_ns); std::swap(P.a_rs, P.b_rs); std::swap(P.M, P.Nc);
-    std::swap(P.a_bytes, P.b_bytes); std::swap(P.w_is, P.w_js);
-  }
-  P.tiles_n = p.tiles_n; P.tiles = p.tiles; P.spi = p.spi; P.slices = p.slices;
-  P.half = p.half; P.swap = p.swap;
-  P.first = d.first ? 1 : 0; P.alpha = d.alpha;
-  P.base = 0;
+  PsQuad P = operands_of<PsQuad>(d, p);
+  P.W = d.W; P.out = d.out; P.partial = partial; P.o_stride = d.o_stride;
+  P.w_is = d.w_rs; P.w_js = 1;
+  if (p.swap) std::swap(P.w_is, P.w_js);
   return P;
+}
+
+// The body of both accumulate entry points: plans, check(name, desc, index) of every descriptor's operands, workspace,
+// then one walk and two launches per batch - lane 0 counts the items of the product launch, lane 1 the blocks of the
+// reduce launch, reduce_units(desc) of them per product.  make = product_of / quad_of.
+template <typename Product, typename Desc, typename Check, typename Units>
+int run_products(const char* name, void* stream_, const Desc* descs, int n, void* workspace, size_t workspace_bytes,
+                 bool (*plan)(const Desc&, int, Plan*), Check check, Product (*make)(const Desc&, const Plan&, float*),
+                 Units reduce_units, void (*product_kernel)(ArgBatch<Product, PS_BATCH>),
+                 void (*reduce_kernel)(ArgBatch<Product, PS_BATCH>)) {
+  if (n <= 0) return CURV_OK;
+  hipStream_t stream = (hipStream_t)stream_;
+  std::vector<Plan> plans;
+  if (!side::plans_of(name, descs, n, plan, &plans)) return CURV_ERR_INVALID;
+  for (int i = 0; i < n; ++i) {
+    const int rc = check(name, descs[i], i);
+    if (rc != CURV_OK) return rc;
+  }
+  const int rc = side::require_workspace(name, workspace, workspace_bytes, bytes_of(plans), 256);
+  if (rc != CURV_OK) return rc;
+  size_t at = 0;
+  return for_arg_batches<Product, PS_BATCH, 2>(
+      n, name,
+      [&](int i, Product* P, long long* units) {
+        *P = make(descs[i], plans[i], (float*)((char*)workspace + at));
+        at += plans[i].slab_bytes;
+        units[0] = (long long)plans[i].tiles * plans[i].slices;
+        units[1] = reduce_units(descs[i]);
+      },
+      [](int, long long units) { return units; },
+      [&](const ArgBatch<Product, PS_BATCH>* b, const long long*, const unsigned* grid) {
+        hipLaunchKernelGGL(product_kernel, dim3(grid[0]), dim3(PS_THREADS), 0, stream, b[0]);
+        CURV_LAUNCH_CHECK();
+        hipLaunchKernelGGL(reduce_kernel, dim3(grid[1]), dim3(PS_THREADS), 0, stream, b[1]);
+        CURV_LAUNCH_CHECK();
+        return CURV_OK;
+      });
 }
 
 }  // namespace
@@ -585,32 +616,14 @@ extern "C" int curv_persample_plan_flops(const curv_persample_desc* descs, int n
 
 extern "C" int curv_persample_sq_accumulate(void* stream_, const curv_persample_desc* descs, int n, void* workspace,
                                             size_t workspace_bytes) {
-  const char* const name = "curv_persample_sq_accumulate";
-  if (n <= 0) return CURV_OK;
-  hipStream_t stream = (hipStream_t)stream_;
-  std::vector<Plan> plans;
-  if (!side::plans_of(name, descs, n, plan_of, &plans)) return CURV_ERR_INVALID;
-  for (int i = 0; i < n; ++i) CURV_REQUIRE(descs[i].A && descs[i].B && descs[i].C, "%s: item %d: null operand", name, i);
-  const int rc = side::require_workspace(name, workspace, workspace_bytes, bytes_of(plans), 256);
-  if (rc != CURV_OK) return rc;
-  size_t at = 0;
-  // one walk, two launches: lane 0 counts the items of the product launch, lane 1 the blocks of the reduce launch
-  return for_arg_batches<PsProduct, PS_BATCH, 2>(
-      n, name,
-      [&](int i, PsProduct* P, long long* units) {
-        *P = product_of(descs[i], plans[i], (float*)((char*)workspace + at));
-        at += plans[i].slab_bytes;
-        units[0] = (long long)plans[i].tiles * plans[i].slices;
-        units[1] = cdivll((long long)descs[i].M * descs[i].Nc, PS_THREADS);
-      },
-      [](int, long long units) { return units; },
-      [&](const PsBatch* b, const long long*, const unsigned* grid) {
-        hipLaunchKernelGGL(ps_product_kernel, dim3(grid[0]), dim3(PS_THREADS), 0, stream, b[0]);
-        CURV_LAUNCH_CHECK();
-        hipLaunchKernelGGL(ps_reduce_kernel, dim3(grid[1]), dim3(PS_THREADS), 0, stream, b[1]);
-        CURV_LAUNCH_CHECK();
+  return run_products(
+      "curv_persample_sq_accumulate", stream_, descs, n, workspace, workspace_bytes, plan_of,
+      [](const char* name, const curv_persample_desc& d, int i) -> int {
+        CURV_REQUIRE(d.A && d.B && d.C, "%s: item %d: null operand", name, i);
         return CURV_OK;
-      });
+      },
+      product_of, [](const curv_persample_desc& d) { return cdivll((long long)d.M * d.Nc, PS_THREADS); },
+      ps_product_kernel, ps_reduce_kernel);
 }
 
 extern "C" size_t curv_persample_quad_workspace_bytes(const curv_persample_quad_desc* descs, int n) {
@@ -623,36 +636,16 @@ extern "C" int curv_persample_quad_plan_flops(const curv_persample_quad_desc* de
 
 extern "C" int curv_persample_quad_reduce(void* stream_, const curv_persample_quad_desc* descs, int n, void* workspace,
                                           size_t workspace_bytes) {
-  const char* const name = "curv_persample_quad_reduce";
-  if (n <= 0) return CURV_OK;
-  hipStream_t stream = (hipStream_t)stream_;
-  std::vector<Plan> plans;
-  if (!side::plans_of(name, descs, n, quad_plan_of, &plans)) return CURV_ERR_INVALID;
-  for (int i = 0; i < n; ++i) {
-    CURV_REQUIRE(descs[i].A && descs[i].B && descs[i].out, "%s: item %d: null operand", name, i);
-    CURV_REQUIRE(((reinterpret_cast<uintptr_t>(descs[i].A) | reinterpret_cast<uintptr_t>(descs[i].B)) & 15) == 0,
-                 "%s: item %d: A and B must be 16-byte aligned", name, i);
-  }
-  const int rc = side::require_workspace(name, workspace, workspace_bytes, bytes_of(plans), 256);
-  if (rc != CURV_OK) return rc;
-  size_t at = 0;
-  // one walk, two launches, as curv_persample_sq_accumulate: the items of the product launch, the blocks of the reduce
-  return for_arg_batches<PsQuad, PS_BATCH, 2>(
-      n, name,
-      [&](int i, PsQuad* P, long long* units) {
-        *P = quad_of(descs[i], plans[i], (float*)((char*)workspace + at));
-        at += plans[i].slab_bytes;
-        units[0] = (long long)plans[i].tiles * plans[i].slices;
-        units[1] = cdivll(descs[i].S, PS_THREADS);
-      },
-      [](int, long long units) { return units; },
-      [&](const PsQuadBatch* b, const long long*, const unsigned* grid) {
-        hipLaunchKernelGGL(ps_quad_product_kernel, dim3(grid[0]), dim3(PS_THREADS), 0, stream, b[0]);
-        CURV_LAUNCH_CHECK();
-        hipLaunchKernelGGL(ps_quad_reduce_kernel, dim3(grid[1]), dim3(PS_THREADS), 0, stream, b[1]);
-        CURV_LAUNCH_CHECK();
+  return run_products(
+      "curv_persample_quad_reduce", stream_, descs, n, workspace, workspace_bytes, quad_plan_of,
+      [](const char* name, const curv_persample_quad_desc& d, int i) -> int {
+        CURV_REQUIRE(d.A && d.B && d.out, "%s: item %d: null operand", name, i);
+        CURV_REQUIRE(((reinterpret_cast<uintptr_t>(d.A) | reinterpret_cast<uintptr_t>(d.B)) & 15) == 0,
+                     "%s: item %d: A and B must be 16-byte aligned", name, i);
         return CURV_OK;
-      });
+      },
+      quad_of, [](const curv_persample_quad_desc& d) { return cdivll(d.S, PS_THREADS); },
+      ps_quad_product_kernel, ps_quad_reduce_kernel);
 }
 
 extern "C" int curv_persample_pack(void* stream_, const curv_persample_pack_desc* descs, int n) {

@@ -572,10 +572,12 @@ class Curvature(ABC):
         return [(s, tensors[2 * k], tensors[2 * k + 1]) for k, s in enumerate(sides)]
 
     @staticmethod
-    def _per_sample_job(sides, g, x, dst, alpha: float, first: bool):
-        """dst (+)= alpha * sum_n (g_n x_n^T)**2 for operands laid out as `sides` says."""
-        return ops.PerSampleJob(g, x, dst, sides.N, sides.m, sides.n, sides.L, sides.g.ns, sides.g.rs, sides.x.ns,
-                                sides.x.rs, alpha=alpha, first=first)
+    def _rotated(sides) -> List[Tensor]:
+        """R t for every (R, t, rows) of `sides`, t an operand packed as one (rows, N Lp) matrix: fresh buffers of t's
+        size, all products in one call."""
+        out = [torch.empty(t.numel(), dtype=torch.float32, device=t.device) for _, t, _ in sides]
+        ops.gemm_batched([ops.Gemm(R, t.view(rows, -1), y.view(rows, -1)) for (R, t, rows), y in zip(sides, out)])
+        return out
 
     # ------------------------------------------------------------------ linearised (GLM) predictive
     def functional_variance(self, out: Tensor, *, first: bool = True, inputs: bool = True) -> Tensor:
@@ -628,9 +630,7 @@ class Curvature(ABC):
             # what depends on the forward pass and the posterior only: X (rotated) and the squared weights
             xs = [x for _, _, x in operands]
             if basis is not None:
-                xs = [torch.empty(x.numel(), dtype=torch.float32, device=dev) for x in xs]
-                ops.gemm_batched([ops.Gemm(basis(l)[1], x.view(s.n, -1), y.view(s.n, -1))
-                                  for l, (s, _, x), y in zip(layers, operands, xs)])
+                xs = self._rotated([(basis(l)[1], x, s.n) for l, (s, _, x) in zip(layers, operands)])
             ws = [None] * len(layers)
             if weights is not None:
                 ws = [ops.mul(weights(l), weights(l)) for l in layers]
@@ -642,14 +642,11 @@ class Curvature(ABC):
         _, xs, ws = kept
         gs = [g for _, g, _ in operands]
         if basis is not None:
-            gs = [torch.empty(g.numel(), dtype=torch.float32, device=dev) for g in gs]
-            ops.gemm_batched([ops.Gemm(basis(l)[0], g.view(s.m, -1), t.view(s.m, -1))
-                              for l, (s, g, _), t in zip(layers, operands, gs)])
+            gs = self._rotated([(basis(l)[0], g, s.m) for l, (s, g, _) in zip(layers, operands)])
         # every layer into its own row, the rows summed in layer order by one product with a row of ones: the result does
         # not depend on how the layers are grouped into launches
         rows = torch.empty(len(layers), N, dtype=torch.float32, device=dev)
-        ops.per_sample_quad_reduce([ops.PerSampleQuadJob(g, x, w, rows[k], s.N, s.m, s.n, s.L, s.g.ns, s.g.rs, s.x.ns, s.x.rs,
-                                                         first=True)
+        ops.per_sample_quad_reduce([ops.PerSampleQuadJob.of(s, g, x, w, rows[k], first=True)
                                     for k, ((s, _, _), g, x, w) in enumerate(zip(operands, gs, xs, ws))])
         ones = torch.ones(1, len(layers), dtype=torch.float32, device=dev)
         ops.gemm_batched([ops.Gemm(ones, rows, out.unsqueeze(0), beta=0.0 if first else 1.0)])
@@ -777,7 +774,7 @@ class Diagonal(Curvature):
         jobs = []
         for layer, (sides, g, x) in zip(layers, operands):
             dst = fresh.get(layer, self.state.get(layer))
-            jobs.append(self._per_sample_job(sides, g, x, dst, float(batch_size), layer in fresh))
+            jobs.append(ops.PerSampleJob.of(sides, g, x, dst, alpha=batch_size, first=layer in fresh))
         ops.per_sample_sq_accumulate(jobs)                 # one product per layer, all layers in one call
         for layer, job in zip(layers, jobs):
             self.state[layer] = job.C
@@ -1474,20 +1471,18 @@ class EFB(Curvature):
             self._state_arena = _Arena([(s.m, s.n) for _, s in missing], dev, zero=True)
             for (l, _), v in zip(missing, self._state_arena.views):
                 self.state[l] = v
-        rotated = [torch.empty(t.numel(), dtype=torch.float32, device=dev) for _, g, x in operands for t in (g, x)]
-        gemms, jobs = [], []
-        for k, (layer, (sides, g, x)) in enumerate(zip(layers, operands)):
+        rotations = []
+        for layer, (sides, g, x) in zip(layers, operands):
             U_At, U_Gt = self._eigvecs_t(layer)
-            T, Y = rotated[2 * k], rotated[2 * k + 1]
-            cols = sides.N * sides.g.Lp
-            gemms.append(ops.Gemm(U_Gt, g.view(sides.m, cols), T.view(sides.m, cols)))
-            gemms.append(ops.Gemm(U_At, x.view(sides.n, cols), Y.view(sides.n, cols)))
-            jobs.append(self._per_sample_job(sides, T, Y, self.state[layer], float(batch_size), False))
+            rotations += [(U_Gt, g, sides.m), (U_At, x, sides.n)]
+        rotated = self._rotated(rotations)
+        jobs = []
+        for k, (layer, (sides, g, x)) in enumerate(zip(layers, operands)):
+            jobs.append(ops.PerSampleJob.of(sides, rotated[2 * k], rotated[2 * k + 1], self.state[layer], alpha=batch_size))
             first = layer not in self.diags
             if first:
                 self.diags[layer] = torch.empty(sides.m, sides.n, dtype=torch.float32, device=dev)
-            jobs.append(self._per_sample_job(sides, g, x, self.diags[layer], float(batch_size), first))
-        ops.gemm_batched(gemms)
+            jobs.append(ops.PerSampleJob.of(sides, g, x, self.diags[layer], alpha=batch_size, first=first))
         ops.per_sample_sq_accumulate(jobs)
 
     def update(self, batch_size: int):

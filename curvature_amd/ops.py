@@ -560,40 +560,67 @@ def per_sample_pack(operands: Sequence[PerSampleOperand], dsts: Sequence[torch.T
     _lib.check(_lib.lib().curv_persample_pack(_lib.stream_ptr(), arr, len(operands)), "curv_persample_pack")
 
 
-class PerSampleJob:
-    """C (+)= alpha * sum_n (A_n B_n^T)**2 over `S` samples: A_n is (M, L) at ``A + n a_ns`` with row stride `a_rs`, B_n
-    (Nc, L) likewise, C an (M, Nc) view with unit column stride.  `first`: overwrite C.  A / B may also be `None` with
-    explicit sizes (plan queries)."""
-    __slots__ = ("A", "B", "C", "S", "M", "Nc", "L", "a_ns", "a_rs", "b_ns", "b_rs", "alpha", "first")
+class _PerSampleProduct:
+    """What `PerSampleJob` and `PerSampleQuadJob` share: the operands A_n (M, L) at ``A + n a_ns`` with row stride `a_rs` and
+    B_n (Nc, L) likewise, for `S` samples, and `alpha` / `first`."""
+    __slots__ = ("A", "B", "S", "M", "Nc", "L", "a_ns", "a_rs", "b_ns", "b_rs", "alpha", "first")
 
-    def __init__(self, A, B, C, S, M, Nc, L, a_ns, a_rs, b_ns, b_rs, alpha=1.0, first=False):
-        self.A, self.B, self.C = A, B, C
+    def _set_operands(self, A, B, S, M, Nc, L, a_ns, a_rs, b_ns, b_rs, alpha, first):
+        self.A, self.B = A, B
         self.S, self.M, self.Nc, self.L = int(S), int(M), int(Nc), int(L)
         self.a_ns, self.a_rs, self.b_ns, self.b_rs = int(a_ns), int(a_rs), int(b_ns), int(b_rs)
         self.alpha, self.first = float(alpha), bool(first)
+
+    @classmethod
+    def of(cls, sides: PerSampleSides, A, B, *own, alpha=1.0, first=False):
+        """The job on a layer's `per_sample_operands`: A the g side, B the x side, `own` the remaining tensors of the
+        constructor (C; W, out)."""
+        return cls(A, B, *own, sides.N, sides.m, sides.n, sides.L, sides.g.ns, sides.g.rs, sides.x.ns, sides.x.rs,
+                   alpha=alpha, first=first)
+
+
+class PerSampleJob(_PerSampleProduct):
+    """C (+)= alpha * sum_n (A_n B_n^T)**2 over `S` samples: A_n is (M, L) at ``A + n a_ns`` with row stride `a_rs`, B_n
+    (Nc, L) likewise, C an (M, Nc) view with unit column stride.  `first`: overwrite C.  A / B may also be `None` with
+    explicit sizes (plan queries)."""
+    __slots__ = ("C",)
+
+    def __init__(self, A, B, C, S, M, Nc, L, a_ns, a_rs, b_ns, b_rs, alpha=1.0, first=False):
+        self.C = C
+        self._set_operands(A, B, S, M, Nc, L, a_ns, a_rs, b_ns, b_rs, alpha, first)
+
+
+def _fill_per_sample(d, j: _PerSampleProduct, name: str, tensors) -> None:
+    """The shared fields of job `j` into descriptor `d`; with `tensors` (the job's own, behind A and B, None among them
+    skipped; None: a plan query) also the device / dtype checks, the extent check of A and B under `name`, and their
+    addresses."""
+    d.S, d.M, d.Nc, d.L = j.S, j.M, j.Nc, j.L
+    d.a_ns, d.a_rs, d.b_ns, d.b_rs = j.a_ns, j.a_rs, j.b_ns, j.b_rs
+    d.alpha, d.first = j.alpha, int(j.first)
+    if tensors is None:
+        return
+    for t in (j.A, j.B) + tuple(t for t in tensors if t is not None):
+        if not t.is_cuda:
+            raise RuntimeError("curvature_amd runs on MI355X only: got a CPU tensor (no CPU fallback)")
+        if t.dtype != torch.float32:
+            raise RuntimeError(f"curvature_amd expects float32 tensors, got {t.dtype}")
+    a_need = (j.S - 1) * j.a_ns + (j.M - 1) * j.a_rs + j.L
+    b_need = (j.S - 1) * j.b_ns + (j.Nc - 1) * j.b_rs + j.L
+    if j.A.numel() < a_need or j.B.numel() < b_need:
+        raise RuntimeError(f"{name}: an operand is smaller than its sizes and strides say")
+    d.A, d.B = j.A.data_ptr(), j.B.data_ptr()
 
 
 def _per_sample_descs(jobs: Sequence[PerSampleJob], check_tensors: bool = True):
     arr = (_lib.curv_persample_desc * len(jobs))()
     for d, j in zip(arr, jobs):
-        d.S, d.M, d.Nc, d.L = j.S, j.M, j.Nc, j.L
-        d.a_ns, d.a_rs, d.b_ns, d.b_rs = j.a_ns, j.a_rs, j.b_ns, j.b_rs
-        d.alpha, d.first = j.alpha, int(j.first)
+        _fill_per_sample(d, j, "per_sample_sq_accumulate", (j.C,) if check_tensors else None)
         d.c_rs = j.Nc
         if check_tensors:
-            for t in (j.A, j.B, j.C):
-                if not t.is_cuda:
-                    raise RuntimeError("curvature_amd runs on MI355X only: got a CPU tensor (no CPU fallback)")
-                if t.dtype != torch.float32:
-                    raise RuntimeError(f"curvature_amd expects float32 tensors, got {t.dtype}")
             if j.C.dim() != 2 or tuple(j.C.shape) != (j.M, j.Nc) or j.C.stride(1) != 1:
                 raise RuntimeError(f"per_sample_sq_accumulate: destination must be an ({j.M},{j.Nc}) view with unit "
                                    f"column stride, got {tuple(j.C.shape)}")
-            a_need = (j.S - 1) * j.a_ns + (j.M - 1) * j.a_rs + j.L
-            b_need = (j.S - 1) * j.b_ns + (j.Nc - 1) * j.b_rs + j.L
-            if j.A.numel() < a_need or j.B.numel() < b_need:
-                raise RuntimeError("per_sample_sq_accumulate: an operand is smaller than its sizes and strides say")
-            d.A, d.B, d.C, d.c_rs = j.A.data_ptr(), j.B.data_ptr(), j.C.data_ptr(), j.C.stride(0)
+            d.C, d.c_rs = j.C.data_ptr(), j.C.stride(0)
     return arr
 
 
@@ -612,33 +639,24 @@ def per_sample_sq_accumulate(jobs: Sequence[PerSampleJob]) -> None:
                jobs[0].C.device, "persample")
 
 
-class PerSampleQuadJob:
+class PerSampleQuadJob(_PerSampleProduct):
     """out[n] (+)= alpha * sum_ij W[i, j] * (A_n B_n^T)[i, j]**2 for `S` samples: A, B and their sizes and strides as in
     `PerSampleJob`; `W` an (M, Nc) view with unit column stride or None (all ones); `out` a length-S float32 view of any
     stride (a column of an (N, classes) matrix).  `first`: overwrite out.  A / B / out may also be `None` with explicit
     sizes (plan queries)."""
-    __slots__ = ("A", "B", "W", "out", "S", "M", "Nc", "L", "a_ns", "a_rs", "b_ns", "b_rs", "alpha", "first")
+    __slots__ = ("W", "out")
 
     def __init__(self, A, B, W, out, S, M, Nc, L, a_ns, a_rs, b_ns, b_rs, alpha=1.0, first=False):
-        self.A, self.B, self.W, self.out = A, B, W, out
-        self.S, self.M, self.Nc, self.L = int(S), int(M), int(Nc), int(L)
-        self.a_ns, self.a_rs, self.b_ns, self.b_rs = int(a_ns), int(a_rs), int(b_ns), int(b_rs)
-        self.alpha, self.first = float(alpha), bool(first)
+        self.W, self.out = W, out
+        self._set_operands(A, B, S, M, Nc, L, a_ns, a_rs, b_ns, b_rs, alpha, first)
 
 
 def _per_sample_quad_descs(jobs: Sequence[PerSampleQuadJob], check_tensors: bool = True):
     arr = (_lib.curv_persample_quad_desc * len(jobs))()
     for d, j in zip(arr, jobs):
-        d.S, d.M, d.Nc, d.L = j.S, j.M, j.Nc, j.L
-        d.a_ns, d.a_rs, d.b_ns, d.b_rs = j.a_ns, j.a_rs, j.b_ns, j.b_rs
-        d.alpha, d.first = j.alpha, int(j.first)
+        _fill_per_sample(d, j, "per_sample_quad_reduce", (j.out, j.W) if check_tensors else None)
         d.w_rs, d.o_stride = j.Nc, 1
         if check_tensors:
-            for t in (j.A, j.B, j.out) + (() if j.W is None else (j.W,)):
-                if not t.is_cuda:
-                    raise RuntimeError("curvature_amd runs on MI355X only: got a CPU tensor (no CPU fallback)")
-                if t.dtype != torch.float32:
-                    raise RuntimeError(f"curvature_amd expects float32 tensors, got {t.dtype}")
             if j.W is not None:
                 if j.W.dim() != 2 or tuple(j.W.shape) != (j.M, j.Nc) or j.W.stride(1) != 1:
                     raise RuntimeError(f"per_sample_quad_reduce: weights must be an ({j.M},{j.Nc}) view with unit column "
@@ -647,12 +665,7 @@ def _per_sample_quad_descs(jobs: Sequence[PerSampleQuadJob], check_tensors: bool
             if j.out.dim() != 1 or j.out.shape[0] != j.S or (j.S > 1 and j.out.stride(0) < 1):
                 raise RuntimeError(f"per_sample_quad_reduce: destination must be a length-{j.S} view with a positive "
                                    f"stride, got {tuple(j.out.shape)}")
-            a_need = (j.S - 1) * j.a_ns + (j.M - 1) * j.a_rs + j.L
-            b_need = (j.S - 1) * j.b_ns + (j.Nc - 1) * j.b_rs + j.L
-            if j.A.numel() < a_need or j.B.numel() < b_need:
-                raise RuntimeError("per_sample_quad_reduce: an operand is smaller than its sizes and strides say")
-            d.A, d.B, d.out = j.A.data_ptr(), j.B.data_ptr(), j.out.data_ptr()
-            d.o_stride = max(j.out.stride(0), 1)
+            d.out, d.o_stride = j.out.data_ptr(), max(j.out.stride(0), 1)
     return arr
 
 

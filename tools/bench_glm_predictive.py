@@ -113,7 +113,7 @@ def quad_jobs(kind, est, layers, out_rows):
             g, x = t, y
         else:
             g, x, w = g.clone(), x.clone(), est.inv_state[layer].square()
-        jobs.append(ops.PerSampleQuadJob(g, x, w, out_rows[k], s.N, s.m, s.n, s.L, s.g.ns, s.g.rs, s.x.ns, s.x.rs, first=True))
+        jobs.append(ops.PerSampleQuadJob.of(s, g, x, w, out_rows[k], first=True))
     return jobs
 
 

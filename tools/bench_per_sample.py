@@ -53,7 +53,7 @@ def layer_class(layer):
 def flops_of(layer, record):
     """(algorithmic, executed) multiply-add flops of the layer's per-sample product."""
     s = ops.per_sample_operands(layer, *record)
-    job = ops.PerSampleJob(None, None, None, s.N, s.m, s.n, s.L, s.g.ns, s.g.rs, s.x.ns, s.x.rs)
+    job = ops.PerSampleJob.of(s, None, None, None)
     return 2 * s.N * s.m * s.n * s.L, ops.per_sample_plan_flops([job])[0]
 
 
