@@ -30,6 +30,12 @@
 // - the variance of a network output under a Laplace posterior (curvatures.py: functional_variance).  Same items, same
 // staging; the product launch leaves one float per (tile, sample) instead of a slab (see ps_product_tile), the reduce
 // launch sums a sample's tiles in tile order.
+//
+// The third (curv_persample_cov_reduce): a Gram over K <= 16 outputs, per sample,
+//   out[n][c][c'] (+)= alpha * sum_ij W[i][j] * P_{n,c}[i][j] * P_{n,c'}[i][j],   P_{n,c} = A_{c,n} B_n^T
+// - the joint covariance of the network outputs (curvatures.py: functional_covariance).  A kernel of its own
+// (ps_cov_tile) on the same staging: tiles of 8 rows i x 128 columns j of all outputs, so that a lane holds every output
+// of its entries and the Gram is lane-local; the B rows of a stage are staged once for all outputs.
 #include "gemm_nt.h"
 #include "side_build.h"
 
@@ -79,12 +85,39 @@ struct PsQuad : PsOperands {
 
 typedef ArgBatch<PsQuad, PS_BATCH> PsQuadBatch;
 
+// A product of curv_persample_cov_reduce: K operands A_c (output c at A + c a_cs) against one B.  Output tiles are
+// COV_TI rows i x 128 columns j of ALL outputs (see ps_cov_tile); `half` and `swap` are 0.  partial[tile][sample][pair],
+// pair = (c, c') with c <= c' in row-major order of the upper triangle.
+constexpr int COV_TI = 8;                      // rows i per output tile
+constexpr int COV_K_MAX = CURV_PERSAMPLE_COV_MAX_OUTPUTS;
+constexpr int COV_PAIRS_MAX = COV_K_MAX * (COV_K_MAX + 1) / 2;
+static_assert(COV_K_MAX == 16, "ps_cov_product_kernel instantiates 1 .. 4 groups of four outputs");
+
+struct PsCov : PsOperands {
+  const float* W;              // may be null: all ones
+  float* out;
+  float* partial;
+  long long a_cs, w_rs, o_ns, o_rs;
+  int K, pairs;
+};
+
+typedef ArgBatch<PsCov, PS_BATCH> PsCovBatch;
+
 struct Plan {
   int tiles_m, tiles_n, tiles, sps, spi, slices, half, swap;
   long long a_bytes, b_bytes;
   size_t slab_bytes;
   long long flops;
 };
+
+// The sample ranges of a product of `p->tiles` output tiles: it follows from the product's own sizes only.
+void split_samples(Plan* p, int S, int L) {
+  p->sps = cdiv(L, nt::KC);
+  const int want = std::max(1, cdiv(PS_ITEMS_TARGET, p->tiles));
+  const int spi_min = cdiv(PS_STAGES_MIN, p->sps);
+  p->spi = std::min(S, std::max(cdiv(S, want), spi_min));
+  p->slices = cdiv(S, p->spi);
+}
 
 // Sizes, operand strides and extents, tiling and sample ranges: what both kinds of product (C per entry, out per sample)
 // share.  `who` names the entry points in the error text.
@@ -118,12 +151,7 @@ bool tiling_of(const Desc& d, const char* who, int index, Plan* p) {
     return false;
   }
   p->tiles = (int)tiles;
-  p->sps = cdiv(d.L, nt::KC);
-  // the split follows from the product's own sizes only
-  const int want = std::max(1, cdiv(PS_ITEMS_TARGET, p->tiles));
-  const int spi_min = cdiv(PS_STAGES_MIN, p->sps);
-  p->spi = std::min(d.S, std::max(cdiv(d.S, want), spi_min));
-  p->slices = cdiv(d.S, p->spi);
+  split_samples(p, d.S, d.L);
   const int tile_rows = p->half ? PS_TM / 2 : PS_TM;
   p->flops = 2LL * p->tiles * tile_rows * PS_TM * (long long)d.S * p->sps * nt::KC;
   return true;
@@ -155,6 +183,47 @@ bool quad_plan_of(const curv_persample_quad_desc& d, int index, Plan* p) {
     return false;
   }
   p->slab_bytes = align_up((size_t)p->tiles * d.S * sizeof(float), 256);
+  return true;
+}
+
+// (`slab_bytes`: the partials, K (K + 1) / 2 floats per output tile and sample; the tiling is ps_cov_tile's)
+bool cov_plan_of(const curv_persample_cov_desc& d, int index, Plan* p) {
+  const char* const who = "curv_persample_cov";
+  if (d.K < 1 || d.K > COV_K_MAX) {
+    set_error("%s: item %d: K %d outside 1 .. %d", who, index, d.K, COV_K_MAX);
+    return false;
+  }
+  if (!tiling_of(d, who, index, p)) return false;
+  if (((d.a_cs | d.a_ns | d.a_rs | d.b_ns | d.b_rs) & 3) != 0 || d.a_cs < 0) {
+    set_error("%s: item %d: operand strides must be multiples of 4 floats (a_cs %lld a_ns %lld a_rs %lld b_ns %lld b_rs "
+              "%lld), a_cs not negative", who, index, d.a_cs, d.a_ns, d.a_rs, d.b_ns, d.b_rs);
+    return false;
+  }
+  if (d.a_cs >= PS_BYTES_MAX) p->a_bytes = PS_BYTES_MAX;
+  else p->a_bytes += (long long)(d.K - 1) * d.a_cs * 4;
+  if (p->a_bytes >= PS_BYTES_MAX - 4096) {
+    set_error("%s: item %d: operand too large for 32-bit offsets (%lld bytes over %d outputs, below %lld)", who, index,
+              p->a_bytes, d.K, PS_BYTES_MAX - 4096);
+    return false;
+  }
+  if ((d.W != nullptr && d.w_rs < d.Nc) || d.o_rs < d.K || d.o_ns < (long long)d.K * d.o_rs) {
+    set_error("%s: item %d: invalid strides (w_rs %lld below Nc %d, o_rs %lld below K %d, or o_ns %lld below K o_rs)", who,
+              index, d.w_rs, d.Nc, d.o_rs, d.K, d.o_ns);
+    return false;
+  }
+  p->half = p->swap = 0;
+  p->tiles_m = cdiv(d.M, COV_TI);
+  p->tiles_n = cdiv(d.Nc, PS_TM);
+  const long long tiles = (long long)p->tiles_m * p->tiles_n;
+  if (tiles > (1 << 24)) {
+    set_error("%s: item %d: too many output tiles (%lld)", who, index, tiles);
+    return false;
+  }
+  p->tiles = (int)tiles;
+  split_samples(p, d.S, d.L);
+  const int groups = cdiv(d.K, 4), pairs = d.K * (d.K + 1) / 2;
+  p->flops = 2LL * p->tiles * (4 * groups * COV_TI) * PS_TM * (long long)d.S * p->sps * nt::KC;
+  p->slab_bytes = align_up((size_t)p->tiles * d.S * pairs * sizeof(float), 256);
   return true;
 }
 
@@ -416,6 +485,240 @@ __global__ void __launch_bounds__(PS_THREADS) ps_quad_reduce_kernel(const PsQuad
   *out = d.first ? v : *out + v;
 }
 
+// ------------------------------------------------------------------------------------------------ joint covariance
+// The third reduction of the same products (curv_persample_cov_reduce): a Gram over K outputs, per sample,
+//   out[s][c][c'] (+)= alpha * sum_ij W[i][j] * P_{s,c}[i][j] * P_{s,c'}[i][j],   P_{s,c} = A_{c,s} B_s^T.
+// Item = (product, tile of COV_TI = 8 rows i x 128 columns j, range of samples).  The A panel of a stage holds the 8 rows
+// of ALL outputs, as rows (group of four outputs, i, output in the group): panel row 32 m + 4 i + c is row i0 + i of
+// output 4 m + c (the DMA's voffset is per row, so the order costs nothing); the B panel is K9's 128 rows, staged once
+// per stage and used against every output.  Wave w takes all 32 KG A rows (KG = ceil(K / 4) MFMA blocks) against B rows
+// 32 w .. + 32.  With the 32x32 C/D map (row = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5)) register `reg` of block m is
+// output 4 m + (reg & 3) of row i0 + 2 (reg >> 2) + (lane >> 5), column j0 + 32 w + (lane & 31): a lane holds every
+// output of its four (i, j) in its own registers, and the Gram over outputs is lane-local - for each pair c <= c' four
+// multiply-adds, with the lane's four weights (W, or 1; 0 for i >= M or j >= Nc, where W is not read) folded into the
+// first factor.  Outputs c >= K of the last group and rows beyond M are staged from a clamped (valid) row and never
+// counted.
+//
+// At a sample's end every pair is summed over the wave by DPP: four row steps (quad_perm, quad_perm, row_half_mirror,
+// row_mirror), then row_bcast:15 and row_bcast:31, i.e. six VALU instructions and no LDS traffic per value, where the
+// butterfly of K9 costs six ds_bpermute round trips (up to 136 values per sample make that the larger part of a sample of
+// two stages) and a transposing pass through LDS would need 34 KiB per wave beside the panels.  Lane 63 leaves the wave's
+// sum in red[sample parity][wave][pair]; behind the next barrier thread `pair` adds the four in wave order and writes
+// partial[tile][sample][pair] (K9's hand-over, K (K + 1) / 2 threads wide): fixed order, no atomics.
+template <int CTRL, int ROW_MASK>
+__device__ __forceinline__ float ps_dpp(float v) {
+  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, ROW_MASK, 0xf, false));
+}
+
+// The sum of `v` over the wave, in lane 63 (a lane outside a step's row mask adds the 0 of `old`).
+__device__ __forceinline__ float ps_wave_sum_dpp(float v) {
+  v += ps_dpp<0xB1, 0xf>(v);       // quad_perm [1, 0, 3, 2]
+  v += ps_dpp<0x4E, 0xf>(v);       // quad_perm [2, 3, 0, 1]
+  v += ps_dpp<0x141, 0xf>(v);      // row_half_mirror
+  v += ps_dpp<0x140, 0xf>(v);      // row_mirror: every lane holds the sum of its row of 16
+  v += ps_dpp<0x142, 0xa>(v);      // row_bcast:15 into rows 1 and 3
+  v += ps_dpp<0x143, 0xc>(v);      // row_bcast:31 into rows 2 and 3
+  return v;
+}
+
+template <int KG>
+__device__ __forceinline__ void ps_cov_tile(const PsCov& d, int local, lds_char_t* lds, float* red) {
+  constexpr int NP = KG + nt::PIECES;                      // DMA pieces per wave: KG of the A panel, then the B panel's
+  const int slice = local % d.slices, tile = local / d.slices;
+  const int tm = tile / d.tiles_n, tn = tile - tm * d.tiles_n;
+  const int i0 = tm * COV_TI, j0 = tn * PS_TM, M = d.M, N = d.Nc, L = d.L, K = d.K;
+  const int s0 = slice * d.spi, s1 = min(s0 + d.spi, d.S);
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int r32 = lane & 31, h = lane >> 5;
+  const int sps = (L + nt::KC - 1) / nt::KC;
+  const int n_stages = (s1 - s0) * sps;
+
+  // DMA lane geometry as ps_product_tile; piece m of the A panel is group m: row rsub of it is output 4 m + (rsub & 3)
+  // of row i0 + (rsub >> 2), both clamped to the last valid one
+  const int rsub = nt::RPP * wave + (lane >> 3);
+  const int g_lane = (lane & (nt::SLOTS - 1)) ^ ((rsub >> 1) & (nt::SLOTS - 1));
+  int voff_a[KG], voff_b[nt::PIECES];
+#pragma unroll
+  for (int p = 0; p < KG; ++p)
+    voff_a[p] = (int)(((long long)min(4 * p + (rsub & 3), K - 1) * d.a_cs + (long long)min(i0 + (rsub >> 2), M - 1) * d.a_rs +
+                       4 * g_lane) * 4);
+#pragma unroll
+  for (int p = 0; p < nt::PIECES; ++p)
+    voff_b[p] = (int)(((long long)min(j0 + 4 * nt::RPP * p + rsub, N - 1) * d.b_rs + 4 * g_lane) * 4);
+  const __amdgpu_buffer_rsrc_t rsa = __builtin_amdgcn_make_buffer_rsrc((void*)d.A, 0, d.a_bytes, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rsb = __builtin_amdgcn_make_buffer_rsrc((void*)d.B, 0, d.b_bytes, 0x00020000);
+
+  unsigned addr_a[KG][nt::STEPS], addr_b[nt::STEPS];
+#pragma unroll
+  for (int o = 0; o <= KG; ++o) {
+    const int R = (o < KG ? 32 * o : 32 * wave) + r32;
+    const unsigned pbase = (o < KG) ? 0u : 2u * nt::PANEL_B;
+    const int rkey = (R >> 1) & (nt::SLOTS - 1);
+#pragma unroll
+    for (int j = 0; j < nt::STEPS; ++j) {
+      const unsigned at = pbase + R * nt::ROW_B + (((2 * j + h) ^ rkey) << 4);
+      if (o < KG) addr_a[o][j] = at;
+      else addr_b[j] = at;
+    }
+  }
+  f32x16 c[KG];                    // P_{n,c} of the running sample: c[m][4 q + cl] = output 4 m + cl, row i0 + 2 q + h
+#pragma unroll
+  for (int m = 0; m < KG; ++m) c[m] = 0.0f;
+  float wq[4];                     // the weights of the lane's four entries (row i0 + 2 q + h, column `col`)
+  {
+    const int col = j0 + 32 * wave + r32;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const int i = i0 + 2 * q + h;
+      const bool in = i < M && col < N;
+      wq[q] = in ? 1.0f : 0.0f;
+      if (in && d.W) wq[q] = d.W[(long long)i * d.w_rs + col];
+    }
+  }
+  int flush = -1;                  // the sample whose wave sums wait in `red`
+  auto flush_sample = [&]() {
+    if (flush >= 0 && tid < d.pairs) {
+      const float* r = red + 4 * COV_PAIRS_MAX * (flush & 1) + tid;
+      d.partial[((long long)tile * d.S + flush) * d.pairs + tid] =
+          ((r[0] + r[COV_PAIRS_MAX]) + r[2 * COV_PAIRS_MAX]) + r[3 * COV_PAIRS_MAX];
+    }
+    flush = -1;
+  };
+
+  constexpr int OOB = (int)0x80000000;
+  auto issue = [&](int i, bool live, unsigned soff_a, unsigned soff_b, unsigned nbuf) {
+    const bool b_side = i >= KG;
+    const int slot = b_side ? i - KG : i;
+    const unsigned lbase = (b_side ? 2u * nt::PANEL_B : 0u) + nbuf + (unsigned)(nt::RPP * wave + 4 * nt::RPP * slot) * nt::ROW_B;
+    if (!b_side)
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(rsa, (lds_void_t*)(lds + lbase), 16, live ? voff_a[slot] : OOB, soff_a, 0, 0);
+    else
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(rsb, (lds_void_t*)(lds + lbase), 16, live ? voff_b[slot] : OOB, soff_b, 0, 0);
+  };
+  int n = s0, kk = 0;                                       // sample and first l of the running stage
+  if (n_stages > 0) {
+    const bool live = 4 * g_lane < L;
+    const unsigned sa = (unsigned)((long long)n * d.a_ns * 4), sb = (unsigned)((long long)n * d.b_ns * 4);
+#pragma unroll
+    for (int i = 0; i < NP; ++i) issue(i, live, sa, sb, 0u);
+  }
+  for (int t = 0; t < n_stages; ++t) {
+    __builtin_amdgcn_s_waitcnt(0x0f70);        // vmcnt(0): this wave's DMA of stage t has landed
+    __syncthreads();
+    flush_sample();
+    int kn = kk + nt::KC, nn = n;
+    const bool sample_ends = kn >= L;
+    if (sample_ends) { kn = 0; ++nn; }
+    const bool live_n = t + 1 < n_stages && kn + 4 * g_lane < L;
+    const unsigned sa = (unsigned)(((long long)nn * d.a_ns + kn) * 4), sb = (unsigned)(((long long)nn * d.b_ns + kn) * 4);
+    const unsigned buf = (unsigned)(t & 1) * nt::PANEL_B, nbuf = nt::PANEL_B - buf;
+    const bool tail_stage = kk + nt::KC > L;    // (the last stage of a sample whose L is no multiple of the stage)
+    auto rd = [&](unsigned at) { return *reinterpret_cast<const __attribute__((address_space(3))) f32x4*>(lds + at + buf); };
+    f32x4 a[KG], b;
+#pragma unroll
+    for (int m = 0; m < KG; ++m) a[m] = rd(addr_a[m][0]);
+    b = rd(addr_b[0]);
+#pragma unroll
+    for (int j = 0; j < nt::STEPS; ++j) {
+      if (tail_stage) {
+        asm volatile("; l tail" ::: "memory");             // keeps this a branch around a VALU-only block
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const bool gone = kk + 4 * (2 * j + h) + e >= L;
+#pragma unroll
+          for (int m = 0; m < KG; ++m) a[m][e] = gone ? 0.0f : a[m][e];
+          b[e] = gone ? 0.0f : b[e];
+        }
+      }
+      f32x4 na[KG], nb;
+      if (j + 1 < nt::STEPS) {
+#pragma unroll
+        for (int m = 0; m < KG; ++m) na[m] = rd(addr_a[m][j + 1]);
+        nb = rd(addr_b[j + 1]);
+      }
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+#pragma unroll
+        for (int m = 0; m < KG; ++m) c[m] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[m][e], b[e], c[m], 0, 0, 0);
+        if (4 * j + e < NP) issue(4 * j + e, live_n, sa, sb, nbuf);   // one piece behind a group of MFMAs
+      }
+      if (j + 1 < nt::STEPS) {
+#pragma unroll
+        for (int m = 0; m < KG; ++m) a[m] = na[m];
+        b = nb;
+      }
+    }
+    if (sample_ends) {
+      // the sample boundary: the weighted Gram of the lane's entries over the outputs, pair by pair, summed over the wave
+      float* r = red + 4 * COV_PAIRS_MAX * (n & 1) + COV_PAIRS_MAX * wave;
+      int pair = 0;
+#pragma unroll
+      for (int ca = 0; ca < 4 * KG; ++ca) {
+        if (ca < K) {
+          float ta[4];
+#pragma unroll
+          for (int q = 0; q < 4; ++q) ta[q] = wq[q] * c[ca >> 2][4 * q + (ca & 3)];
+#pragma unroll
+          for (int cb = ca; cb < 4 * KG; ++cb) {
+            if (cb < K) {
+              float v = ta[0] * c[cb >> 2][cb & 3];
+#pragma unroll
+              for (int q = 1; q < 4; ++q) v = __builtin_fmaf(ta[q], c[cb >> 2][4 * q + (cb & 3)], v);
+              v = ps_wave_sum_dpp(v);
+              if (lane == 63) r[pair] = v;
+              ++pair;
+            }
+          }
+        }
+      }
+#pragma unroll
+      for (int m = 0; m < KG; ++m) c[m] = 0.0f;
+      flush = n;
+    }
+    n = nn;
+    kk = kn;
+  }
+  __syncthreads();                   // the wave sums of the item's last sample
+  flush_sample();
+}
+
+__global__ void __launch_bounds__(PS_THREADS, 2) ps_cov_product_kernel(const PsCovBatch batch) {
+  __shared__ __attribute__((aligned(1024))) char smem[4 * nt::PANEL_B];
+  __shared__ float red[2 * 4 * COV_PAIRS_MAX];                             // [sample parity][wave][pair]
+  const PsCov& d = batch.e[owner_of(batch, (long long)blockIdx.x)];
+  const int local = (int)(blockIdx.x - d.base);
+  switch ((d.K + 3) >> 2) {
+    case 1: ps_cov_tile<1>(d, local, (lds_char_t*)smem, red); break;
+    case 2: ps_cov_tile<2>(d, local, (lds_char_t*)smem, red); break;
+    case 3: ps_cov_tile<3>(d, local, (lds_char_t*)smem, red); break;
+    default: ps_cov_tile<4>(d, local, (lds_char_t*)smem, red); break;
+  }
+}
+
+// Reduce: one thread per (sample, pair c <= c') sums the partials of its product in tile order, scales, writes or adds,
+// and stores the one value at [c][c'] and [c'][c].  Blocks of a product: ceil(S K (K + 1) / 2 / 256).
+__global__ void __launch_bounds__(PS_THREADS) ps_cov_reduce_kernel(const PsCovBatch batch) {
+  const PsCov& d = batch.e[owner_of(batch, (long long)blockIdx.x)];
+  const long long idx = (blockIdx.x - d.base) * PS_THREADS + threadIdx.x;
+  if (idx >= (long long)d.S * d.pairs) return;
+  const long long s = idx / d.pairs;
+  const int pair = (int)(idx - s * d.pairs);
+  int ca = 0, left = pair;
+  while (left >= d.K - ca) { left -= d.K - ca; ++ca; }
+  const int cb = ca + left;
+  const long long step = (long long)d.S * d.pairs;
+  const float* p = d.partial + idx;
+  float v = 0.f;
+#pragma unroll 8
+  for (int t = 0; t < d.tiles; ++t) v += p[t * step];
+  v *= d.alpha;
+  float* out = d.out + s * d.o_ns;
+  if (!d.first) v = out[ca * d.o_rs + cb] + v;
+  out[ca * d.o_rs + cb] = v;
+  out[cb * d.o_rs + ca] = v;
+}
+
 // Reduce: one thread per entry (i, j) of C; it sums the slab entries of its tile in slice order, scales, writes or adds.
 // Blocks of a product: ceil(M Nc / 256).
 __global__ void __launch_bounds__(PS_THREADS) ps_reduce_kernel(const PsBatch batch) {
@@ -450,7 +753,8 @@ struct PsPack {
 };
 
 typedef ArgBatch<PsPack, PS_BATCH> PsPackBatch;
-static_assert(sizeof(PsBatch) <= 3840 && sizeof(PsQuadBatch) <= 3840 && sizeof(PsPackBatch) <= 3840,
+static_assert(sizeof(PsBatch) <= 3840 && sizeof(PsQuadBatch) <= 3840 && sizeof(PsPackBatch) <= 3840 &&
+                  sizeof(PsCovBatch) <= 3840,
               "kernel argument block must stay below 4 KB");
 
 bool pack_plan_of(const curv_persample_pack_desc& d, int index, PsPack* out) {
@@ -564,9 +868,18 @@ PsQuad quad_of(const curv_persample_quad_desc& d, const Plan& p, float* partial)
   return P;
 }
 
-// The body of both accumulate entry points: plans, check(name, desc, index) of every descriptor's operands, workspace,
+// The same for curv_persample_cov_reduce.
+PsCov cov_of(const curv_persample_cov_desc& d, const Plan& p, float* partial) {
+  PsCov P = operands_of<PsCov>(d, p);
+  P.W = d.W; P.out = d.out; P.partial = partial;
+  P.a_cs = d.a_cs; P.w_rs = d.w_rs; P.o_ns = d.o_ns; P.o_rs = d.o_rs;
+  P.K = d.K; P.pairs = d.K * (d.K + 1) / 2;
+  return P;
+}
+
+// The body of the accumulate entry points: plans, check(name, desc, index) of every descriptor's operands, workspace,
 // then one walk and two launches per batch - lane 0 counts the items of the product launch, lane 1 the blocks of the
-// reduce launch, reduce_units(desc) of them per product.  make = product_of / quad_of.
+// reduce launch, reduce_units(desc) of them per product.  make = product_of / quad_of / cov_of.
 template <typename Product, typename Desc, typename Check, typename Units>
 int run_products(const char* name, void* stream_, const Desc* descs, int n, void* workspace, size_t workspace_bytes,
                  bool (*plan)(const Desc&, int, Plan*), Check check, Product (*make)(const Desc&, const Plan&, float*),
@@ -646,6 +959,28 @@ extern "C" int curv_persample_quad_reduce(void* stream_, const curv_persample_qu
       },
       quad_of, [](const curv_persample_quad_desc& d) { return cdivll(d.S, PS_THREADS); },
       ps_quad_product_kernel, ps_quad_reduce_kernel);
+}
+
+extern "C" size_t curv_persample_cov_workspace_bytes(const curv_persample_cov_desc* descs, int n) {
+  return side::workspace_bytes("curv_persample_cov_workspace_bytes", descs, n, cov_plan_of, bytes_of);
+}
+
+extern "C" int curv_persample_cov_plan_flops(const curv_persample_cov_desc* descs, int n, long long* out) {
+  return side::plan_flops("curv_persample_cov_plan_flops", descs, n, out, cov_plan_of);
+}
+
+extern "C" int curv_persample_cov_reduce(void* stream_, const curv_persample_cov_desc* descs, int n, void* workspace,
+                                         size_t workspace_bytes) {
+  return run_products(
+      "curv_persample_cov_reduce", stream_, descs, n, workspace, workspace_bytes, cov_plan_of,
+      [](const char* name, const curv_persample_cov_desc& d, int i) -> int {
+        CURV_REQUIRE(d.A && d.B && d.out, "%s: item %d: null operand", name, i);
+        CURV_REQUIRE(((reinterpret_cast<uintptr_t>(d.A) | reinterpret_cast<uintptr_t>(d.B)) & 15) == 0,
+                     "%s: item %d: A and B must be 16-byte aligned", name, i);
+        return CURV_OK;
+      },
+      cov_of, [](const curv_persample_cov_desc& d) { return cdivll((long long)d.S * (d.K * (d.K + 1) / 2), PS_THREADS); },
+      ps_cov_product_kernel, ps_cov_reduce_kernel);
 }
 
 extern "C" int curv_persample_pack(void* stream_, const curv_persample_pack_desc* descs, int n) {

@@ -572,10 +572,11 @@ class Curvature(ABC):
         return [(s, tensors[2 * k], tensors[2 * k + 1]) for k, s in enumerate(sides)]
 
     @staticmethod
-    def _rotated(sides) -> List[Tensor]:
-        """R t for every (R, t, rows) of `sides`, t an operand packed as one (rows, N Lp) matrix: fresh buffers of t's
-        size, all products in one call."""
-        out = [torch.empty(t.numel(), dtype=torch.float32, device=t.device) for _, t, _ in sides]
+    def _rotated(sides, out: List[Tensor] = None) -> List[Tensor]:
+        """R t for every (R, t, rows) of `sides`, t an operand packed as one (rows, N Lp) matrix: into `out`, or fresh
+        buffers of t's size; all products in one call."""
+        if out is None:
+            out = [torch.empty(t.numel(), dtype=torch.float32, device=t.device) for _, t, _ in sides]
         ops.gemm_batched([ops.Gemm(R, t.view(rows, -1), y.view(rows, -1)) for (R, t, rows), y in zip(sides, out)])
         return out
 
@@ -603,38 +604,54 @@ class Curvature(ABC):
         raise NotImplementedError(f"{type(self).__name__}.functional_variance: no linearised predictive for this estimator "
                                   "(KFAC, Diagonal and EFB have one)")
 
-    def _functional_variance(self, what: str, out: Tensor, first: bool, inputs: bool, basis, weights) -> Tensor:
-        """`functional_variance` of the three estimators.  ``basis(layer)`` = (R_G, R_A), the rotations T = R_G g and
-        Y = R_A X of the packed (rows, N Lp) operands, or `basis` None (no rotation: the operands are read where they are);
-        ``weights(layer)`` = the (m, n) tensor whose square weighs the entries, or `weights` None (all ones)."""
+    def _predictive_operands(self, what: str, call: str, inputs: bool, basis, weights, kept: str, check=None):
+        """What both reductions of the linearised predictive (`_functional_variance`, `_stage_output`) start from: the
+        checks, the selected layers that have an inverse state, their per-sample operands from the current records (the
+        g side only unless `inputs`), and the key that ties a kept X side to the recorded inputs themselves (tensor and
+        version), not just to their shapes.  With `inputs`, attribute `kept` is dropped first (the X side of other records
+        goes before the new one is made) and what depends on the forward pass and the posterior only is worked out: X
+        (rotated) and the squared weights; ``check(operands)`` runs before any of that (the caller's test of its own
+        arguments against the batch).  Returns (layers, operands, key, (xs, ws) or None)."""
         assert self.inv_state, "Inverse state dict is empty. Did you call 'invert' prior to this?"
         if self.shard is not None and self.shard.world > 1:
-            raise NotImplementedError(f"{what}.functional_variance: layer-sharded estimators are not supported")
+            raise NotImplementedError(f"{what}.{call}: layer-sharded estimators are not supported")
         if getattr(self, "record", None) is None:
-            raise RuntimeError(f"{what}.functional_variance: no recording hooks (construct with per_sample=True, or go "
+            raise RuntimeError(f"{what}.{call}: no recording hooks (construct with per_sample=True, or go "
                                "through evaluate.glm_predictive)")
-        layers = self._per_sample_layers(f"{what}.functional_variance", "select other layer types")
+        layers = self._per_sample_layers(f"{what}.{call}", "select other layer types")
         layers = [l for l in layers if l in self.inv_state]
         assert layers, "Inverse state dict holds none of the selected layers"
         layout = dict(rows_outer=True, in_place=False) if basis is not None else {}
         operands = self._per_sample_operands(what, layers, x_side=inputs, **layout)
-        dev, N = operands[0][1].device, operands[0][0].N
-        if out.dim() != 1 or out.shape[0] != N or out.dtype != torch.float32 or not out.is_cuda:
-            raise RuntimeError(f"{what}.functional_variance: out must be a float32 GPU view of length {N}, got "
-                               f"{tuple(out.shape)} {out.dtype} on {out.device}")
-        # the kept X side belongs to the recorded inputs themselves (tensor and version), not just to their shapes
+        if check is not None:
+            check(operands)
         key = tuple((l, id(self.record[l][0]), self.record[l][0]._version, s.n, s.N, s.L, s.x.ns, s.x.rs)
                     for l, (s, _, _) in zip(layers, operands))
-        if inputs:
-            self._variance_inputs = None                       # (the X side of other records goes first)
-            # what depends on the forward pass and the posterior only: X (rotated) and the squared weights
-            xs = [x for _, _, x in operands]
-            if basis is not None:
-                xs = self._rotated([(basis(l)[1], x, s.n) for l, (s, _, x) in zip(layers, operands)])
-            ws = [None] * len(layers)
-            if weights is not None:
-                ws = [ops.mul(weights(l), weights(l)) for l in layers]
-            self._variance_inputs = (key, xs, ws)
+        if not inputs:
+            return layers, operands, key, None
+        setattr(self, kept, None)
+        xs = [x for _, _, x in operands]
+        if basis is not None:
+            xs = self._rotated([(basis(l)[1], x, s.n) for l, (s, _, x) in zip(layers, operands)])
+        ws = [None] * len(layers)
+        if weights is not None:
+            ws = [ops.mul(weights(l), weights(l)) for l in layers]
+        return layers, operands, key, (xs, ws)
+
+    def _functional_variance(self, what: str, out: Tensor, first: bool, inputs: bool, basis, weights) -> Tensor:
+        """`functional_variance` of the three estimators.  ``basis(layer)`` = (R_G, R_A), the rotations T = R_G g and
+        Y = R_A X of the packed (rows, N Lp) operands, or `basis` None (no rotation: the operands are read where they are);
+        ``weights(layer)`` = the (m, n) tensor whose square weighs the entries, or `weights` None (all ones)."""
+        def check(operands):
+            N = operands[0][0].N
+            if out.dim() != 1 or out.shape[0] != N or out.dtype != torch.float32 or not out.is_cuda:
+                raise RuntimeError(f"{what}.functional_variance: out must be a float32 GPU view of length {N}, got "
+                                   f"{tuple(out.shape)} {out.dtype} on {out.device}")
+        layers, operands, key, x_side = self._predictive_operands(what, "functional_variance", inputs, basis, weights,
+                                                                   "_variance_inputs", check)
+        dev, N = operands[0][1].device, operands[0][0].N
+        if x_side is not None:
+            self._variance_inputs = (key,) + x_side
         kept = getattr(self, "_variance_inputs", None)
         if kept is None or kept[0] != key:
             raise RuntimeError(f"{what}.functional_variance(inputs=False): no call with inputs=True on these recorded inputs "
@@ -650,6 +667,90 @@ class Curvature(ABC):
                                     for k, ((s, _, _), g, x, w) in enumerate(zip(operands, gs, xs, ws))])
         ones = torch.ones(1, len(layers), dtype=torch.float32, device=dev)
         ops.gemm_batched([ops.Gemm(ones, rows, out.unsqueeze(0), beta=0.0 if first else 1.0)])
+        return out
+
+    # ------------------------------------------------------------------ joint covariance of the outputs
+    def stage_output(self, slot: int, count: int, *, inputs: bool = False) -> None:
+        """One output of `functional_covariance`: the caller has just back-propagated ``output[:, c].sum()`` (in ``eval()``
+        mode, as for `functional_variance`); the g side of every layer from the current records - packed, and rotated by
+        L_G^T (KFAC) or U_G^T (EFB) - goes into slot `slot` of a stack of `count` slots (scratch of its own: `count` x the
+        packed g side of the model).  ``inputs=True``, once per forward pass and before the other slots: also the X side
+        and the squared weights, exactly as ``functional_variance(inputs=True)`` works them out, and a fresh stack (no slot
+        staged).  The stack and the X side stay on the estimator as ``_covariance_outputs`` until the next ``inputs=True``
+        call replaces them (`evaluate.glm_predictive_joint` drops them); nothing else may use the per-sample scratch in
+        between.  RuntimeError without ``inputs=True`` on these very recorded inputs (tensor and version) and `count`
+        before.  Layers, records and estimators as for `functional_variance`."""
+        raise NotImplementedError(f"{type(self).__name__}.stage_output: no linearised predictive for this estimator "
+                                  "(KFAC, Diagonal and EFB have one)")
+
+    def functional_covariance(self, out: Tensor, *, first: bool = True) -> Tensor:
+        """The joint covariance of the `count` staged outputs (`stage_output`) under the posterior this estimator samples
+        from, linearised in the weights: adds ``sum_layers <T(P_{n,c}), T(P_{n,c'})>`` into ``out[n, c, c']`` (overwrites
+        it when `first`), with P_{n,c} the Jacobian of output c for sample n with respect to a layer's [W | b] and T the
+        map whose squared norm `functional_variance` sums (L_G^T P L_A, inv * P, inv * (U_G^T P U_A)).  `out`: a contiguous
+        (N, count, count) float32 GPU tensor; both triangles are written and are bit-for-bit symmetric; its diagonal is
+        what `functional_variance` gives for each output.  One pass over the products (`ops.per_sample_cov_reduce`): the X
+        side of a layer is staged once for all outputs, no P is written.  RuntimeError if a slot has not been staged since
+        the last ``stage_output(inputs=True)`` or the recorded inputs are no longer those tensors.  At most
+        `ops.PERSAMPLE_COV_MAX_OUTPUTS` outputs.  Implemented by KFAC, Diagonal and EFB."""
+        raise NotImplementedError(f"{type(self).__name__}.functional_covariance: no linearised predictive for this "
+                                  "estimator (KFAC, Diagonal and EFB have one)")
+
+    def _stage_output(self, what: str, slot: int, count: int, inputs: bool, basis, weights) -> None:
+        """`stage_output` of the three estimators; `basis` and `weights` as in `_functional_variance`."""
+        slot, count = int(slot), int(count)
+        if not 1 <= count <= ops.PERSAMPLE_COV_MAX_OUTPUTS or not 0 <= slot < count:
+            raise ValueError(f"{what}.stage_output: slot {slot} of {count} (at most {ops.PERSAMPLE_COV_MAX_OUTPUTS} outputs)")
+        layers, operands, key, x_side = self._predictive_operands(what, "stage_output", inputs, basis, weights,
+                                                                   "_covariance_outputs")
+        if x_side is not None:
+            # a slot is what one output's g side takes: its packed copy, or the record itself where that is read in place
+            sizes = [s.g.floats or s.N * s.g.ns for s, _, _ in operands]
+            stack = ops.per_sample_scratch([count * f for f in sizes], operands[0][1].device, "persample_cov_g")
+            self._covariance_outputs = dict(key=key, count=count, xs=x_side[0], ws=x_side[1], sizes=sizes, stack=stack,
+                                            sides=[s for s, _, _ in operands], staged=set(),
+                                            inputs=[self.record[l][0] for l in layers])
+        kept = getattr(self, "_covariance_outputs", None)
+        if kept is None or kept["key"] != key or kept["count"] != count:
+            raise RuntimeError(f"{what}.stage_output(inputs=False): no call with inputs=True on these recorded inputs and "
+                               f"{count} outputs before (a new forward pass needs inputs=True once)")
+        slots = [t[slot * f:(slot + 1) * f] for t, f in zip(kept["stack"], kept["sizes"])]
+        if basis is not None:
+            self._rotated([(basis(l)[0], g, s.m) for l, (s, g, _) in zip(layers, operands)], slots)
+        else:
+            ops.CopyPlan(slots, [g.reshape(-1)[:f] for (_, g, _), f in zip(operands, kept["sizes"])]).run()
+        kept["staged"].add(slot)
+
+    def _functional_covariance(self, what: str, out: Tensor, first: bool, basis, weights) -> Tensor:
+        """`functional_covariance` of the three estimators (`basis` and `weights` went into the staged operands: they only
+        say here that the estimator has them)."""
+        kept = getattr(self, "_covariance_outputs", None)
+        if kept is None:
+            raise RuntimeError(f"{what}.functional_covariance: no output staged (stage_output(inputs=True) first)")
+        record = getattr(self, "record", None) or {}
+        layers = [k[0] for k in kept["key"]]
+        for (layer, _, version, *_), x in zip(kept["key"], kept["inputs"]):
+            now = record.get(layer, (None, None))[0]
+            if now is not x or now._version != version:
+                raise RuntimeError(f"{what}.functional_covariance: the recorded inputs are no longer those of "
+                                   "stage_output(inputs=True) (a new forward pass needs its outputs staged again)")
+        count, missing = kept["count"], sorted(set(range(kept["count"])) - kept["staged"])
+        if missing:
+            raise RuntimeError(f"{what}.functional_covariance: output slots {missing} of {count} have not been staged since "
+                               "the last stage_output(inputs=True)")
+        sides = kept["sides"]
+        N, dev = sides[0].N, kept["stack"][0].device
+        if tuple(out.shape) != (N, count, count) or out.dtype != torch.float32 or not out.is_cuda or not out.is_contiguous():
+            raise RuntimeError(f"{what}.functional_covariance: out must be a contiguous float32 GPU tensor of shape "
+                               f"({N}, {count}, {count}), got {tuple(out.shape)} {out.dtype} on {out.device}")
+        # every layer into its own (N, count, count) row, the rows summed in layer order by the ones-row product of
+        # `_functional_variance`: the result does not depend on how the layers are grouped into launches
+        rows = torch.empty(len(layers), N, count, count, dtype=torch.float32, device=dev)
+        ops.per_sample_cov_reduce([ops.PerSampleCovJob.of(s, g, x, w, rows[k], count, f, first=True)
+                                   for k, (s, g, x, w, f) in enumerate(zip(sides, kept["stack"], kept["xs"], kept["ws"],
+                                                                           kept["sizes"]))])
+        ones = torch.ones(1, len(layers), dtype=torch.float32, device=dev)
+        ops.gemm_batched([ops.Gemm(ones, rows.view(len(layers), -1), out.view(1, -1), beta=0.0 if first else 1.0)])
         return out
 
     @staticmethod
@@ -864,8 +965,20 @@ class Diagonal(Curvature):
             return prev
         return None
 
+    def _predictive_terms(self):
+        return "Diagonal", None, lambda layer: self.inv_state[layer]
+
     def functional_variance(self, out: Tensor, *, first: bool = True, inputs: bool = True) -> Tensor:
-        return self._functional_variance("Diagonal", out, first, inputs, None, lambda layer: self.inv_state[layer])
+        what, basis, weights = self._predictive_terms()
+        return self._functional_variance(what, out, first, inputs, basis, weights)
+
+    def stage_output(self, slot: int, count: int, *, inputs: bool = False) -> None:
+        what, basis, weights = self._predictive_terms()
+        self._stage_output(what, slot, count, inputs, basis, weights)
+
+    def functional_covariance(self, out: Tensor, *, first: bool = True) -> Tensor:
+        what, basis, weights = self._predictive_terms()
+        return self._functional_covariance(what, out, first, basis, weights)
 
     def sample(self, layer: Union[Module, str], z: Optional[Tensor] = None) -> Tensor:
         assert self.inv_state, "Inverse state dict is empty. Did you call 'invert' prior to this?"
@@ -1255,10 +1368,21 @@ class KFAC(Curvature):
                     self._raise_not_pd(info, exc)
                 raise
 
-    def functional_variance(self, out: Tensor, *, first: bool = True, inputs: bool = True) -> Tensor:
+    def _predictive_terms(self):
         # sample = L_G Z L_A^T: T = L_G^T g, Y = L_A^T X
-        return self._functional_variance("KFAC", out, first, inputs,
-                                         lambda layer: tuple(f.t() for f in reversed(self.inv_state[layer])), None)
+        return "KFAC", lambda layer: tuple(f.t() for f in reversed(self.inv_state[layer])), None
+
+    def functional_variance(self, out: Tensor, *, first: bool = True, inputs: bool = True) -> Tensor:
+        what, basis, weights = self._predictive_terms()
+        return self._functional_variance(what, out, first, inputs, basis, weights)
+
+    def stage_output(self, slot: int, count: int, *, inputs: bool = False) -> None:
+        what, basis, weights = self._predictive_terms()
+        self._stage_output(what, slot, count, inputs, basis, weights)
+
+    def functional_covariance(self, out: Tensor, *, first: bool = True) -> Tensor:
+        what, basis, weights = self._predictive_terms()
+        return self._functional_covariance(what, out, first, basis, weights)
 
     def sample(self, layer: Module, z: Optional[Tensor] = None) -> Tensor:
         """(L_A z L_G^T)^T -> (m, n) (curvatures.py:387-392); `z` (n, m) may be supplied for parity tests."""
@@ -1593,10 +1717,21 @@ class EFB(Curvature):
             n, s = self._hyper(add, multiply, gindex.get(layer, position), max(len(gindex), len(layers)))
             ops.rsqrt_affine(value, n, s, out=self.inv_state[layer])
 
-    def functional_variance(self, out: Tensor, *, first: bool = True, inputs: bool = True) -> Tensor:
+    def _predictive_terms(self):
         # sample = U_G (Z * inv) U_A^T: T = U_G^T g, Y = U_A^T X, as `_update_per_sample`
-        return self._functional_variance("EFB", out, first, inputs, lambda layer: self._eigvecs_t(layer)[::-1],
-                                         lambda layer: self.inv_state[layer])
+        return "EFB", lambda layer: self._eigvecs_t(layer)[::-1], lambda layer: self.inv_state[layer]
+
+    def functional_variance(self, out: Tensor, *, first: bool = True, inputs: bool = True) -> Tensor:
+        what, basis, weights = self._predictive_terms()
+        return self._functional_variance(what, out, first, inputs, basis, weights)
+
+    def stage_output(self, slot: int, count: int, *, inputs: bool = False) -> None:
+        what, basis, weights = self._predictive_terms()
+        self._stage_output(what, slot, count, inputs, basis, weights)
+
+    def functional_covariance(self, out: Tensor, *, first: bool = True) -> Tensor:
+        what, basis, weights = self._predictive_terms()
+        return self._functional_covariance(what, out, first, basis, weights)
 
     def sample(self, layer: Module, z: Optional[Tensor] = None) -> Tensor:
         """(U_A (z * inv^T) U_G^T)^T = U_G (z^T * inv) U_A^T -> (m, n) (curvatures.py:453-460)."""

@@ -19,6 +19,7 @@ thread that enqueues the sample, and a tiny model pays for re-pointing its state
 the serial loop, and the pipelined one is switched on only for a layer-sharded estimator, where it takes the
 all-gather of the sampled parameters (a wait on the other ranks, not local work) off the forward stream.
 """
+import contextlib
 import math
 from typing import Iterable, List, Tuple
 
@@ -167,6 +168,47 @@ def eval_bnn(model: torch.nn.Module, dataset: Iterable, estimator, samples: int 
     return mean_predictions.cpu().numpy(), labels.numpy()
 
 
+@contextlib.contextmanager
+def _linearised(what: str, model: torch.nn.Module, estimator, images: torch.Tensor):
+    """What `glm_predictive` and `glm_predictive_joint` do around their reductions: the model goes into ``eval()`` mode, an
+    estimator without recording hooks borrows them for the length of the block, one forward pass.  Yields
+    ``(logits, backward)``; ``backward(c)`` back-propagates ``logits[:, c].sum()`` into the records with
+    `torch.autograd.grad` on the parameters that require grad (no ``.grad`` is touched).  On the way out the borrowed hooks
+    are removed and what the estimator kept of this batch (``_variance_inputs``, ``_covariance_outputs``) is dropped."""
+    first_param = next(model.parameters())
+    if not first_param.is_cuda or not images.is_cuda:
+        raise RuntimeError(f"curvature_amd runs on MI355X only: {what} got a CPU model or batch (no CPU fallback)")
+    model.eval()
+    borrowed = getattr(estimator, "record", None) is None
+    params = [p for p in model.parameters() if p.requires_grad]
+    try:
+        if borrowed:
+            estimator._record_per_sample(type(estimator).__name__)
+        logits = model(images)
+        if logits.dim() != 2:
+            raise RuntimeError(f"{what}: the model must return (N, classes) logits, got {tuple(logits.shape)}")
+
+        def backward(c: int) -> None:
+            # (torch.autograd.grad fills the recording hooks like backward(), and touches no .grad.  A selected layer the
+            # pass does not reach - frozen parameters behind inputs that need no grad - records nothing: its stale
+            # grad_output is cleared first, so that the reduction raises instead of using it)
+            for pair in estimator.record.values():
+                pair[1] = None
+            torch.autograd.grad(logits[:, c].sum(), params, retain_graph=True, allow_unused=True)
+        yield logits, backward
+    finally:
+        if borrowed:
+            for hook in estimator.hooks:
+                hook.remove()
+            del estimator.hooks, estimator.record
+        estimator.__dict__.pop("_variance_inputs", None)       # the X side of this batch
+        estimator.__dict__.pop("_covariance_outputs", None)    # ... and the stack of its outputs' g sides
+
+
+def _probit(logits: torch.Tensor, variance: torch.Tensor) -> torch.Tensor:
+    return torch.softmax(logits.float() / torch.sqrt(1.0 + (math.pi / 8.0) * variance), dim=1)
+
+
 def glm_predictive(model: torch.nn.Module, estimator, images: torch.Tensor, outputs=None):
     """The linearised-Laplace (GLM) predictive of one batch: ``(logits, variance, probs)``, each (N, classes).
 
@@ -181,35 +223,43 @@ def glm_predictive(model: torch.nn.Module, estimator, images: torch.Tensor, outp
     gradient of ``sum_n f_c(x_n)`` then splits into the per-sample Jacobians the variance is made of.  A Diagonal / EFB
     built without ``per_sample=True`` gets the recording hooks for the length of the call.  The parameters and their
     ``.grad`` are left as they were found (the backward passes are `torch.autograd.grad` calls on the parameters that
-    require grad; a selected layer they do not reach raises RuntimeError).  GPU only (RuntimeError for a CPU model: no fallback)."""
-    first_param = next(model.parameters())
-    if not first_param.is_cuda or not images.is_cuda:
-        raise RuntimeError("curvature_amd runs on MI355X only: glm_predictive got a CPU model or batch (no CPU fallback)")
-    model.eval()
-    borrowed = getattr(estimator, "record", None) is None
-    params = [p for p in model.parameters() if p.requires_grad]
-    try:
-        if borrowed:
-            estimator._record_per_sample(type(estimator).__name__)
-        logits = model(images)
-        if logits.dim() != 2:
-            raise RuntimeError(f"glm_predictive: the model must return (N, classes) logits, got {tuple(logits.shape)}")
+    require grad; a selected layer they do not reach raises RuntimeError).  GPU only (RuntimeError for a CPU model: no fallback).
+    `glm_predictive_joint` gives the covariance between the outputs as well."""
+    with _linearised("glm_predictive", model, estimator, images) as (logits, backward):
         classes = list(range(logits.shape[1])) if outputs is None else [int(c) for c in outputs]
         variance = torch.zeros(logits.shape, dtype=torch.float32, device=logits.device)
         for k, c in enumerate(classes):
-            # (torch.autograd.grad fills the recording hooks like backward(), and touches no .grad.  A selected layer the
-            # pass does not reach - frozen parameters behind inputs that need no grad - records nothing: its stale
-            # grad_output is cleared first, so that `functional_variance` raises instead of using it)
-            for pair in estimator.record.values():
-                pair[1] = None
-            torch.autograd.grad(logits[:, c].sum(), params, retain_graph=True, allow_unused=True)
+            backward(c)
             estimator.functional_variance(variance[:, c], inputs=k == 0)
-    finally:
-        if borrowed:
-            for hook in estimator.hooks:
-                hook.remove()
-            del estimator.hooks, estimator.record
-        estimator.__dict__.pop("_variance_inputs", None)       # the X side of this batch
     logits = logits.detach()
-    probs = torch.softmax(logits.float() / torch.sqrt(1.0 + (math.pi / 8.0) * variance), dim=1)
-    return logits, variance, probs
+    return logits, variance, _probit(logits, variance)
+
+
+def glm_predictive_joint(model: torch.nn.Module, estimator, images: torch.Tensor, outputs=None):
+    """`glm_predictive` with the joint covariance of the outputs: ``(logits, covariance, probs)``.
+
+    ``covariance[n]`` is the K x K covariance matrix of the outputs `outputs` (in that order; default: all classes) for
+    input n under the linearised posterior - the logits share every weight below the head, so they are not independent;
+    the covariance is what sampling logits, a multi-output regression head or ``Var(f_c - f_c')`` need.  Its diagonal is
+    `glm_predictive`'s variance.  ``probs`` is the same probit softmax on that diagonal (the variance of an output that
+    is not selected is 0).  One forward pass, per output one backward pass and one `Curvature.stage_output`, then one
+    `Curvature.functional_covariance`: a single pass over the per-sample products in which the input side of every layer
+    is staged once for all outputs.  At most `ops.PERSAMPLE_COV_MAX_OUTPUTS` (16) distinct outputs per call: ValueError
+    otherwise (raised after the forward pass, when the class count is known) - pass ``outputs=``, for instance the top-k
+    classes.  Model mode, hooks, parameters and ``.grad`` as in `glm_predictive`.  GPU only."""
+    with _linearised("glm_predictive_joint", model, estimator, images) as (logits, backward):
+        classes = list(range(logits.shape[1])) if outputs is None else [int(c) for c in outputs]
+        K = len(classes)
+        if not 1 <= K <= ops.PERSAMPLE_COV_MAX_OUTPUTS or len(set(classes)) != K:
+            raise ValueError(f"glm_predictive_joint: {K} outputs ({len(set(classes))} distinct); the joint covariance takes "
+                             f"1 to {ops.PERSAMPLE_COV_MAX_OUTPUTS} distinct outputs per call: pass outputs= (for instance "
+                             "the top-k classes)")
+        covariance = torch.empty(logits.shape[0], K, K, dtype=torch.float32, device=logits.device)
+        for k, c in enumerate(classes):
+            backward(c)
+            estimator.stage_output(k, K, inputs=k == 0)
+        estimator.functional_covariance(covariance)
+    logits = logits.detach()
+    variance = torch.zeros(logits.shape, dtype=torch.float32, device=logits.device)
+    variance[:, classes] = torch.diagonal(covariance, dim1=1, dim2=2)
+    return logits, covariance, _probit(logits, variance)

@@ -561,7 +561,7 @@ def per_sample_pack(operands: Sequence[PerSampleOperand], dsts: Sequence[torch.T
 
 
 class _PerSampleProduct:
-    """What `PerSampleJob` and `PerSampleQuadJob` share: the operands A_n (M, L) at ``A + n a_ns`` with row stride `a_rs` and
+    """What `PerSampleJob`, `PerSampleQuadJob` and `PerSampleCovJob` share: the operands A_n (M, L) at ``A + n a_ns`` with row stride `a_rs` and
     B_n (Nc, L) likewise, for `S` samples, and `alpha` / `first`."""
     __slots__ = ("A", "B", "S", "M", "Nc", "L", "a_ns", "a_rs", "b_ns", "b_rs", "alpha", "first")
 
@@ -574,7 +574,7 @@ class _PerSampleProduct:
     @classmethod
     def of(cls, sides: PerSampleSides, A, B, *own, alpha=1.0, first=False):
         """The job on a layer's `per_sample_operands`: A the g side, B the x side, `own` the remaining tensors of the
-        constructor (C; W, out)."""
+        constructor (C; W, out; W, out, K, a_cs)."""
         return cls(A, B, *own, sides.N, sides.m, sides.n, sides.L, sides.g.ns, sides.g.rs, sides.x.ns, sides.x.rs,
                    alpha=alpha, first=first)
 
@@ -681,6 +681,60 @@ def per_sample_quad_reduce(jobs: Sequence[PerSampleQuadJob]) -> None:
     if not jobs:
         return
     _run_build("curv_persample_quad_workspace_bytes", "curv_persample_quad_reduce", _per_sample_quad_descs(jobs),
+               len(jobs), jobs[0].out.device, "persample")
+
+
+PERSAMPLE_COV_MAX_OUTPUTS = _lib.PERSAMPLE_COV_MAX_OUTPUTS
+
+
+class PerSampleCovJob(_PerSampleProduct):
+    """out[n, c, c'] (+)= alpha * sum_ij W[i, j] * (A_{c,n} B_n^T)[i, j] * (A_{c',n} B_n^T)[i, j] for `S` samples and `K`
+    outputs (at most `PERSAMPLE_COV_MAX_OUTPUTS`): output c of A at ``A + c a_cs``, otherwise A, B, W and their sizes
+    and strides as in `PerSampleQuadJob`; `out` an (S, K, K) float32 view with unit last stride (any other strides the
+    library allows).  `first`: overwrite out.  A / B / out may also be `None` with explicit sizes (plan queries)."""
+    __slots__ = ("W", "out", "K", "a_cs")
+
+    def __init__(self, A, B, W, out, K, a_cs, S, M, Nc, L, a_ns, a_rs, b_ns, b_rs, alpha=1.0, first=False):
+        self.W, self.out, self.K, self.a_cs = W, out, int(K), int(a_cs)
+        self._set_operands(A, B, S, M, Nc, L, a_ns, a_rs, b_ns, b_rs, alpha, first)
+
+
+def _per_sample_cov_descs(jobs: Sequence[PerSampleCovJob], check_tensors: bool = True):
+    arr = (_lib.curv_persample_cov_desc * len(jobs))()
+    for d, j in zip(arr, jobs):
+        _fill_per_sample(d, j, "per_sample_cov_reduce", (j.out, j.W) if check_tensors else None)
+        d.K, d.a_cs = j.K, j.a_cs
+        d.w_rs, d.o_rs, d.o_ns = j.Nc, j.K, j.K * j.K
+        if check_tensors:
+            if j.A.numel() < (j.K - 1) * j.a_cs + (j.S - 1) * j.a_ns + (j.M - 1) * j.a_rs + j.L:
+                raise RuntimeError("per_sample_cov_reduce: an operand is smaller than its sizes and strides say")
+            if j.W is not None:
+                if j.W.dim() != 2 or tuple(j.W.shape) != (j.M, j.Nc) or j.W.stride(1) != 1:
+                    raise RuntimeError(f"per_sample_cov_reduce: weights must be an ({j.M},{j.Nc}) view with unit column "
+                                       f"stride, got {tuple(j.W.shape)}")
+                d.W, d.w_rs = j.W.data_ptr(), j.W.stride(0)
+            if j.out.dim() != 3 or tuple(j.out.shape) != (j.S, j.K, j.K) or (j.K > 1 and j.out.stride(2) != 1):
+                raise RuntimeError(f"per_sample_cov_reduce: destination must be an ({j.S},{j.K},{j.K}) view with unit "
+                                   f"last stride, got {tuple(j.out.shape)}")
+            # (the stride of a dimension of size 1 says nothing: take the smallest the library allows)
+            d.o_rs = j.out.stride(1) if j.K > 1 else j.K
+            d.o_ns = j.out.stride(0) if j.S > 1 else j.K * d.o_rs
+            d.out = j.out.data_ptr()
+    return arr
+
+
+def per_sample_cov_plan_flops(jobs: Sequence[PerSampleCovJob]) -> List[int]:
+    """Multiply-add FLOPs (2 per multiply-add) the plan executes per job (curv_persample_cov_plan_flops, host only)."""
+    if not jobs:
+        return []
+    return _plan_flops("curv_persample_cov_plan_flops", _per_sample_cov_descs(jobs, check_tensors=False), len(jobs))
+
+
+def per_sample_cov_reduce(jobs: Sequence[PerSampleCovJob]) -> None:
+    """curv_persample_cov_reduce over any number of products, on the current stream; partials from `workspace`."""
+    if not jobs:
+        return
+    _run_build("curv_persample_cov_workspace_bytes", "curv_persample_cov_reduce", _per_sample_cov_descs(jobs),
                len(jobs), jobs[0].out.device, "persample")
 
 

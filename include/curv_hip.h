@@ -559,6 +559,46 @@ int curv_persample_quad_plan_flops(const curv_persample_quad_desc* descs, int n,
  * array; it may be reused as soon as the call returns. */
 int curv_persample_quad_reduce(void* stream, const curv_persample_quad_desc* descs, int n, void* workspace,
                                size_t workspace_bytes);
+
+/* ------------------------------------------------------------------------------------------------
+ * Joint output covariance of the linearised Laplace predictive: the third reduction of the per-sample products
+ * (csrc/persample.hip) - a Gram over K outputs, per sample:
+ *     out[s*o_ns + c*o_rs + c'] (+)= alpha * sum_{i < M, j < Nc} W[i*w_rs + j] * P_{s,c}[i][j] * P_{s,c'}[i][j]
+ *     P_{s,c}[i][j] = sum_{l < L} A[c*a_cs + s*a_ns + i*a_rs + l] * B[s*b_ns + j*b_rs + l]          for c, c' < K
+ * With A_c the (rotated) grad_output of the layer when sum_n f_c(x_n) is back-propagated and B, W as in the table of
+ * curv_persample_quad_reduce, out[s] is the layer's share of the covariance of the outputs f_c(x_s) under the posterior;
+ * its diagonal is what K calls of curv_persample_quad_reduce give.  The B rows of a stage are staged once and used
+ * against all K outputs.  1 <= K <= CURV_PERSAMPLE_COV_MAX_OUTPUTS.  The rules of curv_persample_quad_desc hold: A and B
+ * 16-byte aligned; a_cs (>= 0), a_ns, a_rs, b_ns, b_rs multiples of 4 floats; operand extents (all K outputs of A) below
+ * 2^31 bytes; l values at or behind L never enter a product; W is M x Nc with row stride w_rs >= Nc or NULL for all ones
+ * and is never read outside its entries.  out is S blocks of K x K, o_rs >= K, o_ns >= K*o_rs; `first` != 0 overwrites
+ * the K x K entries (nothing between them is touched).  One value per pair c <= c' is computed and stored at [c][c'] and
+ * [c'][c]: both triangles are written and are bit-for-bit symmetric.  fp32 MFMA, fp32 sums in a fixed order (lane, wave
+ * by DPP, workgroup, then tiles in tile order), no atomics; the plan of an item follows from its own sizes only, so its
+ * bits do not depend on the other items of the call.  Enqueues on `stream` only, never waits on the host, allocates
+ * nothing.  An empty call is a no-op; invalid sizes or strides return CURV_ERR_INVALID with the item named.
+ * ---------------------------------------------------------------------------------------------- */
+#define CURV_PERSAMPLE_COV_MAX_OUTPUTS 16
+typedef struct curv_persample_cov_desc {
+  const float* A;
+  const float* B;
+  const float* W;          /* may be NULL */
+  float* out;
+  long long a_cs, a_ns, a_rs, b_ns, b_rs, w_rs, o_ns, o_rs;
+  int32_t S, K, M, Nc, L;
+  int32_t first;
+  float alpha;
+} curv_persample_cov_desc;
+/* Device scratch for these items (bytes: K (K + 1) / 2 floats per output tile of 8 x 128 and sample); 0 with the error
+ * text set (naming the item) for invalid input.  Host only. */
+size_t curv_persample_cov_workspace_bytes(const curv_persample_cov_desc* descs, int n);
+/* Host only: the multiply-add FLOPs the plan executes per item: whole tiles, K padded to a multiple of 4, L to stages of
+ * 32 - at least the algorithmic 2 S K M Nc L. */
+int curv_persample_cov_plan_flops(const curv_persample_cov_desc* descs, int n, long long* out);
+/* An MFMA and a reduce launch per batch of up to 16 items.  The workspace must be 256-byte aligned.  `descs` is a host
+ * array; it may be reused as soon as the call returns. */
+int curv_persample_cov_reduce(void* stream, const curv_persample_cov_desc* descs, int n, void* workspace,
+                              size_t workspace_bytes);
 /* v = max(v, 0) in place      curvatures.py:523 */
 int curv_clamp_min0(void* stream, float* v, long long count);
 /* out = sqrt(s*v)             curvatures.py:525 */
