@@ -13,7 +13,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc")
 INCLUDE = os.path.normpath(os.path.join(_HERE, "..", "include"))
 LIB_PATH = os.path.join(CSRC, "libcurv_hip.so")
-SOURCES = ["api.cpp", "collective.cpp", "elementwise.hip", "syrk.hip", "syrk_flat.hip", "syrk_corr.hip", "syrk_pre.hip", "syrk_small.hip", "group_factor.hip", "kfac_half.hip", "convt_factor.hip", "persample.hip", "invert.hip", "gemm.hip", "inf.hip", "eigh.hip", "eigh_lowrank.hip"]
+SOURCES = ["api.cpp", "collective.cpp", "elementwise.hip", "syrk.hip", "syrk_flat.hip", "syrk_corr.hip", "syrk_pre.hip", "syrk_small.hip", "group_factor.hip", "kfac_half.hip", "convt_factor.hip", "persample.hip", "logit_mc.hip", "invert.hip", "gemm.hip", "inf.hip", "eigh.hip", "eigh_lowrank.hip"]
 HIPCC_FLAGS = ["-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC", "-shared", "-Wall",
                "-Wno-unused-function", "-ldl"]
 
@@ -195,6 +195,14 @@ class curv_persample_cov_desc(ctypes.Structure):
                [(k, ctypes.c_int32) for k in ("S", "K", "M", "Nc", "L", "first")] + [("alpha", ctypes.c_float)]
 
 
+class curv_logit_mc_desc(ctypes.Structure):
+    """Mirror of ``curv_logit_mc_desc`` in include/curv_hip.h."""
+    _fields_ = [(k, ctypes.c_void_p) for k in ("cov", "mu", "rest", "Z", "probs", "probs_rest", "draws", "info")] + \
+               [(k, ctypes.c_longlong) for k in ("o_ns", "o_rs", "mu_ns", "z_ns", "z_ss")] + \
+               [("seed", ctypes.c_ulonglong), ("offset", ctypes.c_ulonglong)] + \
+               [(k, ctypes.c_int32) for k in ("N", "K", "S", "reserved")]
+
+
 class curv_persample_pack_desc(ctypes.Structure):
     """Mirror of ``curv_persample_pack_desc`` in include/curv_hip.h."""
     _fields_ = _ENDS + _SOURCE + _WINDOW + \
@@ -288,6 +296,9 @@ SIGNATURES = {
     "curv_persample_cov_workspace_bytes": (_sz, [ctypes.POINTER(curv_persample_cov_desc), _i]),
     "curv_persample_cov_plan_flops": (_i, [ctypes.POINTER(curv_persample_cov_desc), _i, ctypes.POINTER(ctypes.c_longlong)]),
     "curv_persample_cov_reduce": (_i, [_vp, ctypes.POINTER(curv_persample_cov_desc), _i, _vp, _sz]),
+    "curv_logit_mc_workspace_bytes": (_sz, [ctypes.POINTER(curv_logit_mc_desc), _i]),
+    "curv_logit_mc_plan_flops": (_i, [ctypes.POINTER(curv_logit_mc_desc), _i, ctypes.POINTER(ctypes.c_longlong)]),
+    "curv_logit_mc": (_i, [_vp, ctypes.POINTER(curv_logit_mc_desc), _i, _vp, _sz]),
     "curv_clamp_min0": (_i, [_vp, _vp, _ll]),
     "curv_sqrt_scale": (_i, [_vp, _vp, _d, _vp, _ll]),
     "curv_mul": (_i, [_vp, _vp, _vp, _vp, _ll]),

@@ -12,6 +12,7 @@
 // (descriptor, 64x64 output tile), decoded on the device from the descriptor table.
 #include "kernarg.h"
 #include "gemm_nt.h"
+#include "philox.h"
 
 #include <algorithm>
 #include <vector>
@@ -558,18 +559,8 @@ constexpr int ORDER_UPLOAD_CHUNK = 944;
 constexpr int GEMM_UPLOAD_CHUNK = 17;
 
 // ------------------------------------------------------------------------------------------------
-// Standard normal noise: Philox4x32-10 counter-based generator + Box-Muller, 4 values per counter.
+// Standard normal noise: Philox4x32-10 counter-based generator + Box-Muller, 4 values per counter (philox.h).
 // ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ void philox_round(unsigned (&c)[4], unsigned k0, unsigned k1) {
-  const unsigned long long p0 = 0xD2511F53ull * c[0];
-  const unsigned long long p1 = 0xCD9E8D57ull * c[2];
-  const unsigned n0 = (unsigned)(p1 >> 32) ^ c[1] ^ k0;
-  const unsigned n1 = (unsigned)p1;
-  const unsigned n2 = (unsigned)(p0 >> 32) ^ c[3] ^ k1;
-  const unsigned n3 = (unsigned)p0;
-  c[0] = n0; c[1] = n1; c[2] = n2; c[3] = n3;
-}
-
 __global__ void __launch_bounds__(256)
 randn_kernel(float* __restrict__ out, long long count, unsigned long long seed, unsigned long long offset,
              const unsigned long long* __restrict__ counter) {
@@ -577,26 +568,8 @@ randn_kernel(float* __restrict__ out, long long count, unsigned long long seed, 
   const long long nquad = (count + 3) >> 2;
   const long long stride = (long long)gridDim.x * blockDim.x;
   for (long long q = (long long)blockIdx.x * blockDim.x + threadIdx.x; q < nquad; q += stride) {
-    const unsigned long long ctr = offset + (unsigned long long)q;
-    unsigned c[4] = {(unsigned)ctr, (unsigned)(ctr >> 32), 0u, 0u};
-    unsigned k0 = (unsigned)seed, k1 = (unsigned)(seed >> 32);
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-      philox_round(c, k0, k1);
-      k0 += 0x9E3779B9u;
-      k1 += 0xBB67AE85u;
-    }
     float z[4];
-#pragma unroll
-    for (int p = 0; p < 2; ++p) {
-      const float u1 = ((float)(c[2 * p] >> 8) + 1.0f) * (1.0f / 16777216.0f);      // (0, 1]
-      const float u2 = (float)(c[2 * p + 1] >> 8) * (1.0f / 16777216.0f);           // [0, 1)
-      const float r = sqrtf(-2.0f * logf(u1));
-      float sn, cs;
-      sincosf(6.283185307179586f * u2, &sn, &cs);
-      z[2 * p] = r * cs;
-      z[2 * p + 1] = r * sn;
-    }
+    philox_normal4(seed, offset + (unsigned long long)q, z);
 #pragma unroll
     for (int e = 0; e < 4; ++e)
       if (4 * q + e < count) out[4 * q + e] = z[e];

@@ -38,6 +38,7 @@
 // of its entries and the Gram is lane-local; the B rows of a stage are staged once for all outputs.
 #include "gemm_nt.h"
 #include "side_build.h"
+#include "wave_sum.h"
 
 namespace curv {
 namespace {
@@ -505,22 +506,7 @@ __global__ void __launch_bounds__(PS_THREADS) ps_quad_reduce_kernel(const PsQuad
 // two stages) and a transposing pass through LDS would need 34 KiB per wave beside the panels.  Lane 63 leaves the wave's
 // sum in red[sample parity][wave][pair]; behind the next barrier thread `pair` adds the four in wave order and writes
 // partial[tile][sample][pair] (K9's hand-over, K (K + 1) / 2 threads wide): fixed order, no atomics.
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ float ps_dpp(float v) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, ROW_MASK, 0xf, false));
-}
-
-// The sum of `v` over the wave, in lane 63 (a lane outside a step's row mask adds the 0 of `old`).
-__device__ __forceinline__ float ps_wave_sum_dpp(float v) {
-  v += ps_dpp<0xB1, 0xf>(v);       // quad_perm [1, 0, 3, 2]
-  v += ps_dpp<0x4E, 0xf>(v);       // quad_perm [2, 3, 0, 1]
-  v += ps_dpp<0x141, 0xf>(v);      // row_half_mirror
-  v += ps_dpp<0x140, 0xf>(v);      // row_mirror: every lane holds the sum of its row of 16
-  v += ps_dpp<0x142, 0xa>(v);      // row_bcast:15 into rows 1 and 3
-  v += ps_dpp<0x143, 0xc>(v);      // row_bcast:31 into rows 2 and 3
-  return v;
-}
-
+// (wave_sum_dpp: wave_sum.h)
 template <int KG>
 __device__ __forceinline__ void ps_cov_tile(const PsCov& d, int local, lds_char_t* lds, float* red) {
   constexpr int NP = KG + nt::PIECES;                      // DMA pieces per wave: KG of the A panel, then the B panel's
@@ -665,7 +651,7 @@ __device__ __forceinline__ void ps_cov_tile(const PsCov& d, int local, lds_char_
               float v = ta[0] * c[cb >> 2][cb & 3];
 #pragma unroll
               for (int q = 1; q < 4; ++q) v = __builtin_fmaf(ta[q], c[cb >> 2][4 * q + (cb & 3)], v);
-              v = ps_wave_sum_dpp(v);
+              v = wave_sum_dpp(v);
               if (lane == 63) r[pair] = v;
               ++pair;
             }

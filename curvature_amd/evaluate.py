@@ -235,23 +235,14 @@ def glm_predictive(model: torch.nn.Module, estimator, images: torch.Tensor, outp
     return logits, variance, _probit(logits, variance)
 
 
-def glm_predictive_joint(model: torch.nn.Module, estimator, images: torch.Tensor, outputs=None):
-    """`glm_predictive` with the joint covariance of the outputs: ``(logits, covariance, probs)``.
-
-    ``covariance[n]`` is the K x K covariance matrix of the outputs `outputs` (in that order; default: all classes) for
-    input n under the linearised posterior - the logits share every weight below the head, so they are not independent;
-    the covariance is what sampling logits, a multi-output regression head or ``Var(f_c - f_c')`` need.  Its diagonal is
-    `glm_predictive`'s variance.  ``probs`` is the same probit softmax on that diagonal (the variance of an output that
-    is not selected is 0).  One forward pass, per output one backward pass and one `Curvature.stage_output`, then one
-    `Curvature.functional_covariance`: a single pass over the per-sample products in which the input side of every layer
-    is staged once for all outputs.  At most `ops.PERSAMPLE_COV_MAX_OUTPUTS` (16) distinct outputs per call: ValueError
-    otherwise (raised after the forward pass, when the class count is known) - pass ``outputs=``, for instance the top-k
-    classes.  Model mode, hooks, parameters and ``.grad`` as in `glm_predictive`.  GPU only."""
-    with _linearised("glm_predictive_joint", model, estimator, images) as (logits, backward):
+def _joint_covariance(what: str, model: torch.nn.Module, estimator, images: torch.Tensor, outputs):
+    """What `glm_predictive_joint` and `glm_predictive_mc` share: ``(logits, covariance, classes)`` from one forward pass,
+    one backward pass and one `Curvature.stage_output` per selected output, and one `Curvature.functional_covariance`."""
+    with _linearised(what, model, estimator, images) as (logits, backward):
         classes = list(range(logits.shape[1])) if outputs is None else [int(c) for c in outputs]
         K = len(classes)
         if not 1 <= K <= ops.PERSAMPLE_COV_MAX_OUTPUTS or len(set(classes)) != K:
-            raise ValueError(f"glm_predictive_joint: {K} outputs ({len(set(classes))} distinct); the joint covariance takes "
+            raise ValueError(f"{what}: {K} outputs ({len(set(classes))} distinct); the joint covariance takes "
                              f"1 to {ops.PERSAMPLE_COV_MAX_OUTPUTS} distinct outputs per call: pass outputs= (for instance "
                              "the top-k classes)")
         covariance = torch.empty(logits.shape[0], K, K, dtype=torch.float32, device=logits.device)
@@ -259,7 +250,114 @@ def glm_predictive_joint(model: torch.nn.Module, estimator, images: torch.Tensor
             backward(c)
             estimator.stage_output(k, K, inputs=k == 0)
         estimator.functional_covariance(covariance)
-    logits = logits.detach()
+    return logits.detach(), covariance, classes
+
+
+def glm_predictive_joint(model: torch.nn.Module, estimator, images: torch.Tensor, outputs=None):
+    """`glm_predictive` with the joint covariance of the outputs: ``(logits, covariance, probs)``.
+
+    ``covariance[n]`` is the K x K covariance matrix of the outputs `outputs` (in that order; default: all classes) for
+    input n under the linearised posterior - the logits share every weight below the head, so they are not independent;
+    the covariance is what sampling logits, a multi-output regression head or ``Var(f_c - f_c')`` need.  Its diagonal is
+    `glm_predictive`'s variance.  ``probs`` is the same probit softmax on that diagonal (the variance of an output that
+    is not selected is 0); `glm_predictive_mc` gives the expected softmax under the whole covariance.  One forward pass,
+    per output one backward pass and one `Curvature.stage_output`, then one
+    `Curvature.functional_covariance`: a single pass over the per-sample products in which the input side of every layer
+    is staged once for all outputs.  At most `ops.PERSAMPLE_COV_MAX_OUTPUTS` (16) distinct outputs per call: ValueError
+    otherwise (raised after the forward pass, when the class count is known) - pass ``outputs=``, for instance the top-k
+    classes.  Model mode, hooks, parameters and ``.grad`` as in `glm_predictive`.  GPU only."""
+    logits, covariance, classes = _joint_covariance("glm_predictive_joint", model, estimator, images, outputs)
     variance = torch.zeros(logits.shape, dtype=torch.float32, device=logits.device)
     variance[:, classes] = torch.diagonal(covariance, dim1=1, dim2=2)
     return logits, covariance, _probit(logits, variance)
+
+
+def mc_softmax(logits: torch.Tensor, covariance: torch.Tensor, classes, samples: int, noise=None, seed: int = 0,
+               offset: int = 0, return_draws: bool = False, what: str = "mc_softmax"):
+    """``E softmax(f)`` for ``f[:, classes] ~ N(logits[:, classes], covariance)`` and the other logits held fixed, by
+    `samples` draws in one `ops.logit_mc` call: ``(probs, draws)`` with `probs` (N, all classes) and `draws` the
+    (N, samples, K) logit draws or None.  The selected columns are the kernel's means; an unselected class c gets the mass
+    left over, ``probs_rest[n] * exp(logits[n, c] - rest[n])`` with ``rest = logsumexp`` of the unselected logits, so rows
+    sum to 1.  `noise`: explicit (N, samples, K) standard-normal z; otherwise the library's Philox stream at `seed`,
+    `offset` (``N * samples * ceil(K / 4)`` counters).  A covariance with a negative Cholesky pivot raises RuntimeError
+    naming the input (one host read of the status words, after the kernel); columns dropped because the covariance is
+    singular are no error."""
+    N, C = logits.shape
+    K = len(classes)
+    dev = logits.device
+    chosen = set(classes)
+    others = [c for c in range(C) if c not in chosen]
+    logits = logits.float()
+    mu = logits[:, classes].contiguous()
+    rest = torch.logsumexp(logits[:, others], dim=1) if others else None
+    selected = torch.empty(N, K, dtype=torch.float32, device=dev)
+    left = torch.empty(N, dtype=torch.float32, device=dev)
+    info = torch.empty(N, dtype=torch.int32, device=dev)
+    draws = torch.empty(N, samples, K, dtype=torch.float32, device=dev) if return_draws else None
+    ops.logit_mc([ops.LogitMCJob(covariance, mu, samples, rest=rest, noise=noise, probs=selected, probs_rest=left,
+                                 draws=draws, info=info, seed=seed, offset=offset)])
+    status = info.cpu()
+    if bool((status < 0).any()):
+        n = int(torch.nonzero(status < 0)[0])
+        raise RuntimeError(f"{what}: the covariance of input {n} is not positive semi-definite (Cholesky pivot "
+                           f"{-int(status[n]) - 1} is negative)")
+    probs = torch.empty(N, C, dtype=torch.float32, device=dev)
+    probs[:, classes] = selected
+    if others:
+        probs[:, others] = left[:, None] * torch.exp(logits[:, others] - rest[:, None])
+    return probs, draws
+
+
+def glm_predictive_mc(model: torch.nn.Module, estimator, images: torch.Tensor, outputs=None, samples: int = 256,
+                      noise=None, return_draws: bool = False):
+    """The GLM predictive by Monte Carlo over the joint logit covariance: ``(logits, covariance, probs)``, plus `draws`
+    (N, samples, K) with ``return_draws=True``.
+
+    `logits` and `covariance` are `glm_predictive_joint`'s (same passes, same bits).  ``probs`` (N, classes) is the mean
+    over `samples` draws ``f ~ N(logits[:, outputs], covariance)`` of the softmax over all classes, the logits that are not
+    selected held at their values (their variance is 0 by the convention of the covariance): the expectation the probit
+    softmax of `glm_predictive` approximates from the diagonal alone, here with the correlations between the logits.  One
+    fused kernel (`ops.logit_mc`): a Cholesky factor per input, the draws, their softmax and the mean, without an
+    (N, samples, K) tensor unless `draws` is asked for.  `noise`: explicit (N, samples, K) float32 GPU z, mirroring
+    ``KFAC.sample(layer, z)``; otherwise the draws come from the estimator's own noise stream (`noise_seed` pins them,
+    `noise_offset` advances by ``N * samples * ceil(K / 4)``, so successive calls are independent).  A covariance that is
+    singular is fine (`Curvature.functional_covariance` gives one whenever there are more outputs than the Jacobians'
+    rank); one that is not positive semi-definite raises RuntimeError naming the input.  GPU only."""
+    samples = int(samples)
+    if samples < 1:
+        raise ValueError(f"glm_predictive_mc: samples must be at least 1, got {samples}")
+    logits, covariance, classes = _joint_covariance("glm_predictive_mc", model, estimator, images, outputs)
+    seed = offset = 0
+    if noise is None:
+        if getattr(estimator, "_noise_counter", None) is not None:
+            raise RuntimeError("glm_predictive_mc: the noise position is kept on the host only; switch the estimator's "
+                               "device noise counter off (use_device_noise_counter(False)) or pass noise=")
+        seed, offset = estimator._seed(), estimator.noise_offset
+        estimator.noise_offset += logits.shape[0] * samples * ((len(classes) + 3) // 4)
+    probs, draws = mc_softmax(logits, covariance, classes, samples, noise=noise, seed=seed, offset=offset,
+                              return_draws=return_draws, what="glm_predictive_mc")
+    return (logits, covariance, probs, draws) if return_draws else (logits, covariance, probs)
+
+
+def eval_glm(model: torch.nn.Module, dataset: Iterable, estimator, predictive: str = "probit", outputs=None,
+             samples: int = 256, device=None):
+    """The GLM predictive over `dataset`: ``(predictions, labels)`` as numpy arrays, the counterpart of `eval_bnn` without
+    weight samples.  ``predictive="probit"`` goes through `glm_predictive`, ``"mc"`` through `glm_predictive_mc` with
+    `samples` draws per input from the estimator's noise stream; `outputs` as there.  The probabilities stay on the device
+    and cross to the host once at the end."""
+    if predictive not in ("probit", "mc"):
+        raise ValueError(f"eval_glm: predictive must be 'probit' or 'mc', got {predictive!r}")
+    if device is None:
+        device = next(model.parameters()).device
+    probs, labels_all = [], []
+    for images, labels in dataset:
+        images = images.to(device, non_blocking=True)
+        if predictive == "probit":
+            probs.append(glm_predictive(model, estimator, images, outputs=outputs)[2])
+        else:
+            probs.append(glm_predictive_mc(model, estimator, images, outputs=outputs, samples=samples)[2])
+        if labels is not None:
+            labels_all.append(labels.cpu() if isinstance(labels, torch.Tensor) else torch.as_tensor(labels))
+    predictions = torch.cat(probs) if probs else torch.empty(0, device=device)
+    labels = torch.cat(labels_all) if labels_all else torch.empty(0, dtype=torch.long)
+    return predictions.cpu().numpy(), labels.numpy()

@@ -738,6 +738,91 @@ def per_sample_cov_reduce(jobs: Sequence[PerSampleCovJob]) -> None:
                len(jobs), jobs[0].out.device, "persample")
 
 
+class LogitMCJob:
+    """probs[n, c] = mean over `S` draws of softmax([f, rest[n]])[c] with f = mu[n] + L_n z, L_n L_n^T = cov[n]
+    (curv_logit_mc): `cov` an (N, K, K) float32 view with unit last stride (what `per_sample_cov_reduce` writes; only the
+    lower triangles are read), `mu` an (N, K) view with unit last stride, `rest` (N,) - the log-sum-exp of the logits that
+    are not selected - or None, `noise` an (N, S, K) view of explicit z with unit last stride or None (then the library's
+    Philox stream at `seed`, `offset`; the call consumes ``N * S * ceil(K / 4)`` counters).  Outputs, contiguous, any of
+    them None but not all: `probs` (N, K), `probs_rest` (N,), `draws` (N, S, K), `info` (N,) int32 - the number of dropped
+    Cholesky columns, or -(j + 1) for a negative pivot j.  Every tensor may also be None with explicit `N`, `K` (plan
+    queries)."""
+    __slots__ = ("cov", "mu", "rest", "noise", "probs", "probs_rest", "draws", "info", "N", "K", "S", "seed", "offset")
+
+    def __init__(self, cov, mu, S, rest=None, noise=None, probs=None, probs_rest=None, draws=None, info=None,
+                 seed: int = 0, offset: int = 0, N: Optional[int] = None, K: Optional[int] = None):
+        self.cov, self.mu, self.rest, self.noise = cov, mu, rest, noise
+        self.probs, self.probs_rest, self.draws, self.info = probs, probs_rest, draws, info
+        self.N = int(cov.shape[0] if N is None else N)
+        self.K = int(cov.shape[-1] if K is None else K)
+        self.S, self.seed, self.offset = int(S), int(seed), int(offset)
+
+
+def _logit_mc_descs(jobs: Sequence[LogitMCJob], check_tensors: bool = True):
+    name = "logit_mc"
+    arr = (_lib.curv_logit_mc_desc * len(jobs))()
+    for d, j in zip(arr, jobs):
+        N, K, S = j.N, j.K, j.S
+        d.N, d.K, d.S = N, K, S
+        d.o_rs, d.o_ns, d.mu_ns = K, K * K, K
+        d.seed, d.offset = j.seed & (2 ** 64 - 1), j.offset & (2 ** 64 - 1)
+        if not check_tensors:
+            d.probs = 256                # (an item without outputs is refused; the host queries never read the address)
+            continue
+        floats = (j.cov, j.mu, j.rest, j.noise, j.probs, j.probs_rest, j.draws)
+        for t in floats + (j.info,):
+            if t is not None and not t.is_cuda:
+                raise RuntimeError("curvature_amd runs on MI355X only: got a CPU tensor (no CPU fallback)")
+        for t in floats:
+            if t is not None and t.dtype != torch.float32:
+                raise RuntimeError(f"curvature_amd expects float32 tensors, got {t.dtype}")
+        if j.cov.dim() != 3 or tuple(j.cov.shape) != (N, K, K) or (K > 1 and j.cov.stride(2) != 1):
+            raise RuntimeError(f"{name}: cov must be an ({N},{K},{K}) view with unit last stride, got {tuple(j.cov.shape)}")
+        if j.mu.dim() != 2 or tuple(j.mu.shape) != (N, K) or (K > 1 and j.mu.stride(1) != 1):
+            raise RuntimeError(f"{name}: mu must be an ({N},{K}) view with unit last stride, got {tuple(j.mu.shape)}")
+        # (the stride of a dimension of size 1 says nothing: take the smallest the library allows)
+        d.o_rs = j.cov.stride(1) if K > 1 else K
+        d.o_ns = j.cov.stride(0) if N > 1 else K * d.o_rs
+        d.mu_ns = j.mu.stride(0) if N > 1 else K
+        d.cov, d.mu = j.cov.data_ptr(), j.mu.data_ptr()
+        if j.noise is not None:
+            if j.noise.dim() != 3 or tuple(j.noise.shape) != (N, S, K) or (K > 1 and j.noise.stride(2) != 1):
+                raise RuntimeError(f"{name}: noise must be an ({N},{S},{K}) view with unit last stride, got "
+                                   f"{tuple(j.noise.shape)}")
+            d.z_ss = j.noise.stride(1) if S > 1 else K
+            d.z_ns = j.noise.stride(0) if N > 1 else (S - 1) * d.z_ss + K
+            d.Z = j.noise.data_ptr()
+        for what, t, shape in (("rest", j.rest, (N,)), ("probs", j.probs, (N, K)), ("probs_rest", j.probs_rest, (N,)),
+                               ("draws", j.draws, (N, S, K)), ("info", j.info, (N,))):
+            if t is None:
+                continue
+            if tuple(t.shape) != shape or not t.is_contiguous() or (what == "info" and t.dtype != torch.int32):
+                raise RuntimeError(f"{name}: {what} must be a contiguous {shape} tensor"
+                                   f"{' of int32' if what == 'info' else ''}, got {tuple(t.shape)} {t.dtype}")
+            setattr(d, what, t.data_ptr())
+    return arr
+
+
+def logit_mc_plan_flops(jobs: Sequence[LogitMCJob]) -> List[int]:
+    """Multiply-add FLOPs (2 per multiply-add) of the draws the plan executes per job (curv_logit_mc_plan_flops, host
+    only)."""
+    if not jobs:
+        return []
+    return _plan_flops("curv_logit_mc_plan_flops", _logit_mc_descs(jobs, check_tensors=False), len(jobs))
+
+
+def logit_mc(jobs: Sequence[LogitMCJob]) -> None:
+    """curv_logit_mc over any number of items, on the current stream; the partial sums of items whose draws are cut into
+    chunks from `workspace` (an item of one chunk per input needs none)."""
+    if not jobs:
+        return
+    L, arr, n = _lib.lib(), _logit_mc_descs(jobs), len(jobs)
+    need = L.curv_logit_mc_workspace_bytes(arr, n)       # 0: nothing needed - or refused, which the call itself reports
+    ws = workspace(need, jobs[0].cov.device, "persample") if need else None
+    _lib.check(L.curv_logit_mc(_lib.stream_ptr(), arr, n, ws.data_ptr() if need else None, ws.numel() if need else 0),
+               "curv_logit_mc")
+
+
 def per_sample_scratch(floats: Sequence[int], device, tag: str = "persample_x") -> List[torch.Tensor]:
     """One float32 buffer of each given size (0: None), carved 256-byte aligned out of the `tag` workspace: the
     packed operands of one `update()`; valid until the next call with that tag."""

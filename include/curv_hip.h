@@ -599,6 +599,71 @@ int curv_persample_cov_plan_flops(const curv_persample_cov_desc* descs, int n, l
  * array; it may be reused as soon as the call returns. */
 int curv_persample_cov_reduce(void* stream, const curv_persample_cov_desc* descs, int n, void* workspace,
                               size_t workspace_bytes);
+
+/* ------------------------------------------------------------------------------------------------
+ * Monte-Carlo softmax of the linearised Laplace predictive from the joint logit covariance (csrc/logit_mc.hip): for
+ * each of N inputs, with Sigma_n the K x K covariance curv_persample_cov_reduce wrote and mu_n the K selected logits,
+ *     f_s = mu_n + L_n z_s  (s < S, z_s ~ N(0, I)),   L_n L_n^T = Sigma_n,   lse_s = logsumexp(f_s, rest[n])
+ *     probs[n*K + c] = (1/S) sum_s exp(f_s[c] - lse_s)        probs_rest[n] = (1/S) sum_s exp(rest[n] - lse_s)
+ * i.e. E softmax(f) under f ~ N(mu_n, Sigma_n) - the predictive the covariance exists for (the logits share every weight
+ * below the head, so they are not independent) - in one kernel that reads Sigma and the logits once and writes (N, K);
+ * the (N, S, K) draws stay in registers unless `draws` asks for them.  1 <= K <= CURV_PERSAMPLE_COV_MAX_OUTPUTS.
+ *
+ * Inputs.  cov: N blocks of K x K with strides o_ns >= K o_rs, o_rs >= K (the layout curv_persample_cov_reduce writes);
+ * only the lower triangle c' <= c is read, nothing between or above the entries.  mu: K floats per input, mu_ns >= K
+ * apart.  rest: N floats or NULL; rest[n] is the log-sum-exp of the logits of the classes that are NOT selected - they are
+ * constants, their variance being 0 under the convention of curv_persample_cov_reduce; NULL (or -inf) means every class is
+ * selected, and probs_rest is then 0.  Z: explicit standard-normal noise, z_s[c] at Z[n*z_ns + s*z_ss + c] (z_ss >= K,
+ * z_ns >= (S - 1) z_ss + K), or NULL: the draws then come from the generator of curv_randn keyed by `seed` - with
+ * Kq = ceil(K / 4), draw s of input n takes the counters offset + (n S + s) Kq + q, q < Kq, and value e of counter q is
+ * z_s[4 q + e]: exactly the numbers curv_randn(seed, offset) writes into an (N, S, 4 Kq) buffer, so a call with Z = NULL
+ * has the bits of a call with that buffer as Z.  The position of the stream is the host-side `offset` only (the caller
+ * advances it by N S Kq); a device-side counter as in curv_randn_counter is not offered.
+ *
+ * Outputs, each may be NULL but not all: probs (N x K, contiguous), probs_rest (N), draws (N x S x K, contiguous: the
+ * f_s themselves), info (N status words).
+ *
+ * Factorisation.  L_n is the lower Cholesky factor, computed in fp64 from the fp32 entries and kept in fp32.  Sigma_n is
+ * positive SEMI-definite and often singular, so a tiny or negative pivot is no error: with
+ * thr = 16 * 2^-23 * max_c Sigma_cc, a pivot d_j <= thr makes column j of L exact zeros.  info[n] = the number of dropped
+ * columns (0 for a definite block); if a pivot lies below -thr the block is not a covariance: info[n] = -(j + 1) for the
+ * first such j, and the column is dropped all the same, so finite input never gives a non-finite output.
+ *
+ * Plan.  The draws of an input are cut into chunks of max(256, 256 ceil(ceil(S / ceil(1024 / N)) / 256)) draws, one
+ * workgroup each, so that few inputs still fill the chip; with more than one chunk the partial sums (K + 1 floats per
+ * input and chunk) go to the caller's workspace and a second launch adds them in chunk order.  An item whose inputs have
+ * one chunk needs no workspace: curv_logit_mc_workspace_bytes is then 0 WITHOUT an error text, and `workspace` may be
+ * NULL.  The plan of an item follows from its own N, K and S only.
+ *
+ * The rules of the library: fp32 sums in a fixed order (lane, wave by DPP, workgroup, then chunks in chunk order), no
+ * atomics, so the bits of an item do not depend on the other items of the call nor on the run.  Enqueues on `stream`
+ * only, never waits on the host, allocates nothing.  An empty call is a no-op; invalid sizes or strides (K outside
+ * 1 .. 16, o_rs < K, o_ns < K o_rs, mu_ns < K, bad Z strides, N or S below 1, S above 2^30, N S above 2^40, every
+ * output NULL) return CURV_ERR_INVALID with the item named.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct curv_logit_mc_desc {
+  const float* cov;
+  const float* mu;
+  const float* rest;       /* may be NULL */
+  const float* Z;          /* may be NULL */
+  float* probs;            /* may be NULL */
+  float* probs_rest;       /* may be NULL */
+  float* draws;            /* may be NULL */
+  int32_t* info;           /* may be NULL */
+  long long o_ns, o_rs, mu_ns, z_ns, z_ss;
+  unsigned long long seed, offset;
+  int32_t N, K, S;
+  int32_t reserved;
+} curv_logit_mc_desc;
+/* Device scratch for these items (bytes: see Plan; 256-byte aligned per item); 0 with the error text set (naming the
+ * item) for invalid input - and 0 without one where no item needs scratch.  Host only. */
+size_t curv_logit_mc_workspace_bytes(const curv_logit_mc_desc* descs, int n);
+/* Host only: the multiply-add FLOPs of f = mu + L z the plan executes per item: whole quads of every row of L,
+ * 2 N S 8 Kq (Kq + 1) - at least the algorithmic 2 N S K (K + 1) / 2. */
+int curv_logit_mc_plan_flops(const curv_logit_mc_desc* descs, int n, long long* out);
+/* One launch per batch of up to 16 items, a second where an item has chunks.  The workspace must be 256-byte aligned.
+ * `descs` is a host array; it may be reused as soon as the call returns. */
+int curv_logit_mc(void* stream, const curv_logit_mc_desc* descs, int n, void* workspace, size_t workspace_bytes);
 /* v = max(v, 0) in place      curvatures.py:523 */
 int curv_clamp_min0(void* stream, float* v, long long count);
 /* out = sqrt(s*v)             curvatures.py:525 */
