@@ -11,11 +11,10 @@
 //      place: the unfold of a convolution input (rows (c, kh, kw)), the transpose of a Linear input (N, T, D), or a plain
 //      copy; plus the ones row of a biased layer; every row padded with zeros to Lp columns by the pack itself.
 //   2. product: one workgroup per item = (product, 128 x 128 output tile, range of samples); 2 x 2 waves of 64 x 64, each
-//      2 x 2 v_mfma_f32_32x32x2_f32 blocks.  Staging is the NT GEMM's (gemm_nt.h): both 128-row panels of a stage of 32 l
-//      values arrive by LDS-DMA into a double-buffered, XOR-swizzled image and come back with ds_read_b128.  The stages of
-//      all samples of the item form ONE sequence (the prefetch runs across sample boundaries); the last stage of a sample
-//      whose L is no multiple of 32 zeroes the l values at or behind L in the operand registers, so what lies behind a row
-//      in memory (the next row, the next sample, NaN) never enters a product.  64 + 64 accumulators per lane, two
+//      2 x 2 v_mfma_f32_32x32x2_f32 blocks, on the stage engine (nt_stage.h), a stage being 32 l values of one sample.
+//      The stages of all samples of the item form ONE sequence (ps_walk_samples: the prefetch runs across sample
+//      boundaries); the last stage of a sample whose L is no multiple of 32 is the engine's tail stage, so what lies behind
+//      a row in memory (the next row, the next sample, NaN) never enters a product.  64 + 64 accumulators per lane, two
 //      workgroups per CU (registers and 64 KiB of LDS each).  A product whose smaller side has at most 64 rows runs on
 //      64 x 128 tiles with that side as the A panel (2 x 1 blocks per wave, the transposed tile when the side is Nc):
 //      half the MFMAs of a half-empty 128 x 128 tile.  Each item writes its fp32 slab.
@@ -34,9 +33,9 @@
 // The third (curv_persample_cov_reduce): a Gram over K <= 16 outputs, per sample,
 //   out[n][c][c'] (+)= alpha * sum_ij W[i][j] * P_{n,c}[i][j] * P_{n,c'}[i][j],   P_{n,c} = A_{c,n} B_n^T
 // - the joint covariance of the network outputs (curvatures.py: functional_covariance).  A kernel of its own
-// (ps_cov_tile) on the same staging: tiles of 8 rows i x 128 columns j of all outputs, so that a lane holds every output
+// (ps_cov_tile) on the same engine and walk: tiles of 8 rows i x 128 columns j of all outputs, so that a lane holds every output
 // of its entries and the Gram is lane-local; the B rows of a stage are staged once for all outputs.
-#include "gemm_nt.h"
+#include "nt_stage.h"
 #include "side_build.h"
 #include "wave_sum.h"
 
@@ -44,8 +43,7 @@ namespace curv {
 namespace {
 
 constexpr int PS_THREADS = 256;
-constexpr int PS_TM = nt::TM;                  // tile rows / columns; the stage constants are nt:: (gemm_nt.h)
-static_assert(nt::KC == 32, "lane geometry and swizzle key below are those of stages of 32 l values");
+constexpr int PS_TM = nt::TM;                  // tile rows / columns; the stage constants are nt:: (nt_stage.h)
 constexpr int PS_BATCH = 16;                   // products per launch (tables as kernel arguments)
 constexpr int PS_ITEMS_TARGET = 512;           // a product is cut into sample ranges until it has about this many items ...
 constexpr int PS_STAGES_MIN = 64;              // ... of at least 64 stages
@@ -244,52 +242,82 @@ bool cov_plan_of(const curv_persample_cov_desc& d, int index, Plan* p) {
 // keeps the waves that run ahead into the next sample's end off the four values thread 0 is still reading.
 enum { PS_SQ = 0, PS_QUAD_W = 1, PS_QUAD_ONES = 2 };
 
+// An item of a product launch: its output tile and its range of samples.
+struct PsItem {
+  int tile, tm, tn, slice;
+};
+__device__ __forceinline__ PsItem ps_item_of(const PsOperands& d, int local) {
+  PsItem it;
+  it.slice = local % d.slices;
+  it.tile = local / d.slices;
+  it.tm = it.tile / d.tiles_n;
+  it.tn = it.tile - it.tm * d.tiles_n;
+  return it;
+}
+
+// The walk over the stages of an item's samples, which all three product tiles share: the stages of samples
+// [slice spi, ...) form ONE sequence on the stage engine (nt_stage.h; the prefetch runs across sample boundaries), a
+// stage being 32 l values of one sample; the last stage of a sample whose L is no multiple of 32 is the engine's tail
+// stage.  The client has filled dma.voff_a / voff_b (the sample and l of a stage travel as soffsets) and brings the
+// accumulators c[NA][NB] (not reset here) and two hooks: sample_end(n) right behind the last stage of sample n - P_n is
+// complete in c - and flush(n) behind the next barrier after it, the next stage's.  Returns the sample whose flush is
+// still due (the item's last), or -1.
+template <int NA, int NB, int PA, typename SampleEnd, typename Flush>
+__device__ __forceinline__ int ps_walk_samples(const PsOperands& d, int slice, const nt::Dma<PA>& dma,
+                                               const unsigned (&addr_a)[NA][nt::STEPS],
+                                               const unsigned (&addr_b)[NB][nt::STEPS], f32x16 (&c)[NA][NB], int h,
+                                               SampleEnd sample_end, Flush flush) {
+  const int L = d.L, s0 = slice * d.spi, s1 = min(s0 + d.spi, d.S);
+  const int n_stages = (s1 - s0) * ((L + nt::KC - 1) / nt::KC);
+  int n = s0, kk = 0;                                       // sample and first l of the running stage
+  int pending = -1;                                         // the sample whose flush is due
+  if (n_stages > 0)
+    dma.issue_first(dma.live(0, L), (unsigned)((long long)n * d.a_ns * 4), (unsigned)((long long)n * d.b_ns * 4));
+  for (int t = 0; t < n_stages; ++t) {
+    nt::stage_landed();
+    if (pending >= 0) flush(pending);
+    pending = -1;
+    int kn = kk + nt::KC, nn = n;
+    const bool sample_ends = kn >= L;
+    if (sample_ends) { kn = 0; ++nn; }
+    const bool live_n = t + 1 < n_stages && dma.live(kn, L);
+    const unsigned sa = (unsigned)(((long long)nn * d.a_ns + kn) * 4), sb = (unsigned)(((long long)nn * d.b_ns + kn) * 4);
+    nt::stage<NA, NB, PA + nt::PIECES>(c, addr_a, addr_b, dma.lds, t, L - kk, h,
+                                       [&](int i, unsigned nbuf) { dma.issue(i, live_n, sa, sb, nbuf); });
+    if (sample_ends) {
+      sample_end(n);
+      pending = n;
+    }
+    n = nn;
+    kk = kn;
+  }
+  return pending;
+}
+
 template <bool HALF, int MODE, typename Product>
 __device__ __forceinline__ void ps_product_tile(const Product& d, int local, lds_char_t* lds, float* red) {
   constexpr int BN = HALF ? 1 : 2;                         // MFMA blocks per wave along the B side
   constexpr int TA = HALF ? PS_TM / 2 : PS_TM;             // A rows per tile
-  constexpr int PA = TA / nt::RPP / 4;                     // DMA pieces per wave: A panel, then the B panel's
-  constexpr int NP = PA + nt::PIECES;
-  const int slice = local % d.slices, tile = local / d.slices;
-  const int tm = tile / d.tiles_n, tn = tile - tm * d.tiles_n;
-  const int i0 = tm * TA, j0 = tn * PS_TM, M = d.M, N = d.Nc, L = d.L;
-  const int s0 = slice * d.spi, s1 = min(s0 + d.spi, d.S);
+  constexpr int PA = TA / nt::RPP / 4;                     // DMA pieces per wave of the A panel
+  const PsItem it = ps_item_of(d, local);
+  const int i0 = it.tm * TA, j0 = it.tn * PS_TM, M = d.M, N = d.Nc;
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int r32 = lane & 31, h = lane >> 5;
   const int row_a = HALF ? 0 : 64 * (wave >> 1), row_b = HALF ? 32 * wave : 64 * (wave & 1);
-  const int sps = (L + nt::KC - 1) / nt::KC;
-  const int n_stages = (s1 - s0) * sps;
 
-  // DMA lane geometry (gemm_nt.h): piece `slot` of this wave covers panel rows 32 slot + 8 wave + (lane >> 3); the lane's
-  // 16-byte group is XOR-swizzled by (row >> 1) & 7 on the source side
-  const int rsub = nt::RPP * wave + (lane >> 3);
-  const int g_lane = (lane & (nt::SLOTS - 1)) ^ ((rsub >> 1) & (nt::SLOTS - 1));
-  int voff_a[PA], voff_b[nt::PIECES];
   // rows beyond the matrix are clamped to its last row (their results are never stored, and the PS_QUAD modes leave them
   // out of the sums)
+  nt::Dma<PA> dma(d.A, d.a_bytes, d.B, d.b_bytes, lds, wave, lane);
 #pragma unroll
-  for (int p = 0; p < PA; ++p)
-    voff_a[p] = (int)(((long long)min(i0 + 4 * nt::RPP * p + rsub, M - 1) * d.a_rs + 4 * g_lane) * 4);
+  for (int p = 0; p < PA; ++p) dma.voff_a[p] = dma.row_voff(i0, p, M, d.a_rs);
 #pragma unroll
-  for (int p = 0; p < nt::PIECES; ++p)
-    voff_b[p] = (int)(((long long)min(j0 + 4 * nt::RPP * p + rsub, N - 1) * d.b_rs + 4 * g_lane) * 4);
-  const __amdgpu_buffer_rsrc_t rsa = __builtin_amdgcn_make_buffer_rsrc((void*)d.A, 0, d.a_bytes, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rsb = __builtin_amdgcn_make_buffer_rsrc((void*)d.B, 0, d.b_bytes, 0x00020000);
-
+  for (int p = 0; p < nt::PIECES; ++p) dma.voff_b[p] = dma.row_voff(j0, p, N, d.b_rs);
   unsigned addr_a[2][nt::STEPS], addr_b[BN][nt::STEPS];
 #pragma unroll
-  for (int o = 0; o < 2 + BN; ++o) {
-    const int R = (o < 2 ? row_a : row_b) + (o & 1) * 32 + r32;
-    const unsigned pbase = (o < 2) ? 0u : 2u * nt::PANEL_B;
-    const int rkey = (R >> 1) & (nt::SLOTS - 1);
+  for (int m = 0; m < 2; ++m) nt::read_addrs(addr_a[m], row_a + 32 * m + r32, false, h);
 #pragma unroll
-    for (int j = 0; j < nt::STEPS; ++j) {
-      const unsigned at = pbase + R * nt::ROW_B + (((2 * j + h) ^ rkey) << 4);
-      if (o < 2) addr_a[o][j] = at;
-      else addr_b[o - 2][j] = at;
-    }
-  }
+  for (int nb = 0; nb < BN; ++nb) nt::read_addrs(addr_b[nb], row_b + 32 * nb + r32, true, h);
   f32x16 c[2][BN], q[2][BN];       // P_n of the running sample; the sum of P_n**2 over the finished samples (PS_QUAD_W: W)
 #pragma unroll
   for (int m = 0; m < 2; ++m)
@@ -312,124 +340,19 @@ __device__ __forceinline__ void ps_product_tile(const Product& d, int local, lds
           if (roff(m, reg) < rows_left && col_in[nb]) q[m][nb][reg] = d.W[at];
         }
   }
-  int flush = -1;                                            // the sample whose four wave sums wait in `red`
-  auto flush_sample = [&]() {
-    if constexpr (MODE != PS_SQ) {
-      if (flush >= 0 && tid == 0) {
-        const float* r = red + 4 * (flush & 1);
-        d.partial[(long long)tile * d.S + flush] = ((r[0] + r[1]) + r[2]) + r[3];
-      }
-      flush = -1;
-    }
-  };
-
-  // A lane whose 16-byte group lies at or behind L - or any lane behind the item's last stage - carries an out-of-range
-  // voffset (the descriptor's range check drops the fetch)
-  constexpr int OOB = (int)0x80000000;
-  auto issue = [&](int i, bool live, unsigned soff_a, unsigned soff_b, unsigned nbuf) {
-    const bool b_side = i >= PA;
-    const int slot = b_side ? i - PA : i;
-    const unsigned lbase = (b_side ? 2u * nt::PANEL_B : 0u) + nbuf + (unsigned)(nt::RPP * wave + 4 * nt::RPP * slot) * nt::ROW_B;
-    if (!b_side)
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rsa, (lds_void_t*)(lds + lbase), 16, live ? voff_a[slot] : OOB, soff_a, 0, 0);
-    else
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rsb, (lds_void_t*)(lds + lbase), 16, live ? voff_b[slot] : OOB, soff_b, 0, 0);
-  };
-  int n = s0, kk = 0;                                       // sample and first l of the running stage
-  if (n_stages > 0) {
-    const bool live = 4 * g_lane < L;
-    const unsigned sa = (unsigned)((long long)n * d.a_ns * 4), sb = (unsigned)((long long)n * d.b_ns * 4);
-#pragma unroll
-    for (int i = 0; i < NP; ++i) issue(i, live, sa, sb, 0u);
-  }
-  for (int t = 0; t < n_stages; ++t) {
-    __builtin_amdgcn_s_waitcnt(0x0f70);        // vmcnt(0): this wave's DMA of stage t has landed
-    __syncthreads();
-    if constexpr (MODE != PS_SQ) flush_sample();
-    int kn = kk + nt::KC, nn = n;
-    const bool sample_ends = kn >= L;
-    if (sample_ends) { kn = 0; ++nn; }
-    const bool live_n = t + 1 < n_stages && kn + 4 * g_lane < L;
-    const unsigned sa = (unsigned)(((long long)nn * d.a_ns + kn) * 4), sb = (unsigned)(((long long)nn * d.b_ns + kn) * 4);
-    const unsigned buf = (unsigned)(t & 1) * nt::PANEL_B, nbuf = nt::PANEL_B - buf;
-    const bool tail_stage = kk + nt::KC > L;    // (the last stage of a sample whose L is no multiple of the stage)
-    auto rd = [&](unsigned at) { return *reinterpret_cast<const __attribute__((address_space(3))) f32x4*>(lds + at + buf); };
-    f32x4 a[2], b[BN];
-#pragma unroll
-    for (int m = 0; m < 2; ++m) a[m] = rd(addr_a[m][0]);
-#pragma unroll
-    for (int nb = 0; nb < BN; ++nb) b[nb] = rd(addr_b[nb][0]);
-#pragma unroll
-    for (int j = 0; j < nt::STEPS; ++j) {
-      if (tail_stage) {
-        asm volatile("; l tail" ::: "memory");             // keeps this a branch around a VALU-only block
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const bool gone = kk + 4 * (2 * j + h) + e >= L;
-#pragma unroll
-          for (int m = 0; m < 2; ++m) a[m][e] = gone ? 0.0f : a[m][e];
-#pragma unroll
-          for (int nb = 0; nb < BN; ++nb) b[nb][e] = gone ? 0.0f : b[nb][e];
-        }
-      }
-      f32x4 na[2], nb_[BN];
-      if (j + 1 < nt::STEPS) {
-#pragma unroll
-        for (int m = 0; m < 2; ++m) na[m] = rd(addr_a[m][j + 1]);
-#pragma unroll
-        for (int nb = 0; nb < BN; ++nb) nb_[nb] = rd(addr_b[nb][j + 1]);
-      }
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-#pragma unroll
-        for (int m = 0; m < 2; ++m)
-#pragma unroll
-          for (int nb = 0; nb < BN; ++nb) c[m][nb] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[m][e], b[nb][e], c[m][nb], 0, 0, 0);
-        if (e < nt::PPS && nt::PPS * j + e < NP) issue(nt::PPS * j + e, live_n, sa, sb, nbuf);   // one piece behind a group of MFMAs
-      }
-      if (j + 1 < nt::STEPS) {
-#pragma unroll
-        for (int m = 0; m < 2; ++m) a[m] = na[m];
-#pragma unroll
-        for (int nb = 0; nb < BN; ++nb) b[nb] = nb_[nb];
-      }
-    }
-    if (sample_ends) {
-      // the sample boundary: square the tile of P_n, add it to the running sum, start the next sample from zero
-      if constexpr (MODE == PS_SQ) {
-#pragma unroll
-        for (int m = 0; m < 2; ++m)
-#pragma unroll
-          for (int nb = 0; nb < BN; ++nb) {
-            q[m][nb] += c[m][nb] * c[m][nb];
-            c[m][nb] = 0.0f;
-          }
-      } else {
-        // ... or sum its (weighted) squares over the tile, this lane's 64 entries first
-        float v = 0.0f;
-#pragma unroll
-        for (int m = 0; m < 2; ++m)
-#pragma unroll
-          for (int nb = 0; nb < BN; ++nb) {
-#pragma unroll
-            for (int reg = 0; reg < 16; ++reg) {
-              const float p = c[m][nb][reg];
-              if constexpr (MODE == PS_QUAD_W) v += q[m][nb][reg] * p * p;
-              else v += (roff(m, reg) < rows_left && col_in[nb]) ? p * p : 0.0f;
-            }
-            c[m][nb] = 0.0f;
-          }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-        if (lane == 0) red[4 * (n & 1) + wave] = v;
-        flush = n;
-      }
-    }
-    n = nn;
-    kk = kn;
-  }
 
   if constexpr (MODE == PS_SQ) {
+    // the sample boundary: square the tile of P_n, add it to the running sum, start the next sample from zero
+    auto sample_end = [&](int) {
+#pragma unroll
+      for (int m = 0; m < 2; ++m)
+#pragma unroll
+        for (int nb = 0; nb < BN; ++nb) {
+          q[m][nb] += c[m][nb] * c[m][nb];
+          c[m][nb] = 0.0f;
+        }
+    };
+    ps_walk_samples(d, it.slice, dma, addr_a, addr_b, c, h, sample_end, [](int) {});
     // raw partial tile, row-major TA x 128, to this item's slab (every entry is written)
     gfl* slab = (gfl*)d.slabs + (long long)local * (TA * PS_TM);
 #pragma unroll
@@ -444,13 +367,39 @@ __device__ __forceinline__ void ps_product_tile(const Product& d, int local, lds
         }
       }
   } else {
+    auto flush = [&](int n) {
+      if (tid == 0) {
+        const float* r = red + 4 * (n & 1);
+        d.partial[(long long)it.tile * d.S + n] = ((r[0] + r[1]) + r[2]) + r[3];
+      }
+    };
+    // the sample boundary: sum the (weighted) squares of P_n over the tile, this lane's 64 entries first
+    auto sample_end = [&](int n) {
+      float v = 0.0f;
+#pragma unroll
+      for (int m = 0; m < 2; ++m)
+#pragma unroll
+        for (int nb = 0; nb < BN; ++nb) {
+#pragma unroll
+          for (int reg = 0; reg < 16; ++reg) {
+            const float p = c[m][nb][reg];
+            if constexpr (MODE == PS_QUAD_W) v += q[m][nb][reg] * p * p;
+            else v += (roff(m, reg) < rows_left && col_in[nb]) ? p * p : 0.0f;
+          }
+          c[m][nb] = 0.0f;
+        }
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+      if (lane == 0) red[4 * (n & 1) + wave] = v;
+    };
+    const int last = ps_walk_samples(d, it.slice, dma, addr_a, addr_b, c, h, sample_end, flush);
     __syncthreads();                 // the wave sums of the item's last sample
-    flush_sample();
+    if (last >= 0) flush(last);
   }
 }
 
 __global__ void __launch_bounds__(PS_THREADS, 2) ps_product_kernel(const PsBatch batch) {
-  __shared__ __attribute__((aligned(1024))) char smem[4 * nt::PANEL_B];   // [buffer][A panel, B panel] as gemm_nt.h
+  __shared__ __attribute__((aligned(1024))) char smem[nt::LDS_B];
   const PsProduct& d = batch.e[owner_of(batch, (long long)blockIdx.x)];
   const int local = (int)(blockIdx.x - d.base);
   if (d.half) ps_product_tile<true, PS_SQ>(d, local, (lds_char_t*)smem, nullptr);
@@ -459,7 +408,7 @@ __global__ void __launch_bounds__(PS_THREADS, 2) ps_product_kernel(const PsBatch
 
 // The same items for curv_persample_quad_reduce: partial[tile][sample] instead of a slab.
 __global__ void __launch_bounds__(PS_THREADS, 2) ps_quad_product_kernel(const PsQuadBatch batch) {
-  __shared__ __attribute__((aligned(1024))) char smem[4 * nt::PANEL_B];
+  __shared__ __attribute__((aligned(1024))) char smem[nt::LDS_B];
   __shared__ float red[8];                                                  // [sample parity][wave]
   const PsQuad& d = batch.e[owner_of(batch, (long long)blockIdx.x)];
   const int local = (int)(blockIdx.x - d.base);
@@ -509,48 +458,29 @@ __global__ void __launch_bounds__(PS_THREADS) ps_quad_reduce_kernel(const PsQuad
 // (wave_sum_dpp: wave_sum.h)
 template <int KG>
 __device__ __forceinline__ void ps_cov_tile(const PsCov& d, int local, lds_char_t* lds, float* red) {
-  constexpr int NP = KG + nt::PIECES;                      // DMA pieces per wave: KG of the A panel, then the B panel's
-  const int slice = local % d.slices, tile = local / d.slices;
-  const int tm = tile / d.tiles_n, tn = tile - tm * d.tiles_n;
-  const int i0 = tm * COV_TI, j0 = tn * PS_TM, M = d.M, N = d.Nc, L = d.L, K = d.K;
-  const int s0 = slice * d.spi, s1 = min(s0 + d.spi, d.S);
+  const PsItem it = ps_item_of(d, local);
+  const int i0 = it.tm * COV_TI, j0 = it.tn * PS_TM, M = d.M, N = d.Nc, K = d.K;
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int r32 = lane & 31, h = lane >> 5;
-  const int sps = (L + nt::KC - 1) / nt::KC;
-  const int n_stages = (s1 - s0) * sps;
 
-  // DMA lane geometry as ps_product_tile; piece m of the A panel is group m: row rsub of it is output 4 m + (rsub & 3)
-  // of row i0 + (rsub >> 2), both clamped to the last valid one
-  const int rsub = nt::RPP * wave + (lane >> 3);
-  const int g_lane = (lane & (nt::SLOTS - 1)) ^ ((rsub >> 1) & (nt::SLOTS - 1));
-  int voff_a[KG], voff_b[nt::PIECES];
+  // piece m of the A panel is group m: row rsub of it is output 4 m + (rsub & 3) of row i0 + (rsub >> 2), both clamped
+  // to the last valid one
+  nt::Dma<KG> dma(d.A, d.a_bytes, d.B, d.b_bytes, lds, wave, lane);
 #pragma unroll
   for (int p = 0; p < KG; ++p)
-    voff_a[p] = (int)(((long long)min(4 * p + (rsub & 3), K - 1) * d.a_cs + (long long)min(i0 + (rsub >> 2), M - 1) * d.a_rs +
-                       4 * g_lane) * 4);
+    dma.voff_a[p] = (int)(((long long)min(4 * p + (dma.rsub & 3), K - 1) * d.a_cs +
+                           (long long)min(i0 + (dma.rsub >> 2), M - 1) * d.a_rs + 4 * dma.g_lane) * 4);
 #pragma unroll
-  for (int p = 0; p < nt::PIECES; ++p)
-    voff_b[p] = (int)(((long long)min(j0 + 4 * nt::RPP * p + rsub, N - 1) * d.b_rs + 4 * g_lane) * 4);
-  const __amdgpu_buffer_rsrc_t rsa = __builtin_amdgcn_make_buffer_rsrc((void*)d.A, 0, d.a_bytes, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rsb = __builtin_amdgcn_make_buffer_rsrc((void*)d.B, 0, d.b_bytes, 0x00020000);
-
-  unsigned addr_a[KG][nt::STEPS], addr_b[nt::STEPS];
+  for (int p = 0; p < nt::PIECES; ++p) dma.voff_b[p] = dma.row_voff(j0, p, N, d.b_rs);
+  unsigned addr_a[KG][nt::STEPS], addr_b[1][nt::STEPS];
+  f32x16 c[KG][1];                 // P_{n,c} of the running sample: c[m][0][4 q + cl] = output 4 m + cl, row i0 + 2 q + h
 #pragma unroll
-  for (int o = 0; o <= KG; ++o) {
-    const int R = (o < KG ? 32 * o : 32 * wave) + r32;
-    const unsigned pbase = (o < KG) ? 0u : 2u * nt::PANEL_B;
-    const int rkey = (R >> 1) & (nt::SLOTS - 1);
-#pragma unroll
-    for (int j = 0; j < nt::STEPS; ++j) {
-      const unsigned at = pbase + R * nt::ROW_B + (((2 * j + h) ^ rkey) << 4);
-      if (o < KG) addr_a[o][j] = at;
-      else addr_b[j] = at;
-    }
+  for (int m = 0; m < KG; ++m) {
+    nt::read_addrs(addr_a[m], 32 * m + r32, false, h);
+    c[m][0] = 0.0f;
   }
-  f32x16 c[KG];                    // P_{n,c} of the running sample: c[m][4 q + cl] = output 4 m + cl, row i0 + 2 q + h
-#pragma unroll
-  for (int m = 0; m < KG; ++m) c[m] = 0.0f;
+  nt::read_addrs(addr_b[0], 32 * wave + r32, true, h);
   float wq[4];                     // the weights of the lane's four entries (row i0 + 2 q + h, column `col`)
   {
     const int col = j0 + 32 * wave + r32;
@@ -562,115 +492,46 @@ __device__ __forceinline__ void ps_cov_tile(const PsCov& d, int local, lds_char_
       if (in && d.W) wq[q] = d.W[(long long)i * d.w_rs + col];
     }
   }
-  int flush = -1;                  // the sample whose wave sums wait in `red`
-  auto flush_sample = [&]() {
-    if (flush >= 0 && tid < d.pairs) {
-      const float* r = red + 4 * COV_PAIRS_MAX * (flush & 1) + tid;
-      d.partial[((long long)tile * d.S + flush) * d.pairs + tid] =
+  auto flush = [&](int n) {
+    if (tid < d.pairs) {
+      const float* r = red + 4 * COV_PAIRS_MAX * (n & 1) + tid;
+      d.partial[((long long)it.tile * d.S + n) * d.pairs + tid] =
           ((r[0] + r[COV_PAIRS_MAX]) + r[2 * COV_PAIRS_MAX]) + r[3 * COV_PAIRS_MAX];
     }
-    flush = -1;
   };
-
-  constexpr int OOB = (int)0x80000000;
-  auto issue = [&](int i, bool live, unsigned soff_a, unsigned soff_b, unsigned nbuf) {
-    const bool b_side = i >= KG;
-    const int slot = b_side ? i - KG : i;
-    const unsigned lbase = (b_side ? 2u * nt::PANEL_B : 0u) + nbuf + (unsigned)(nt::RPP * wave + 4 * nt::RPP * slot) * nt::ROW_B;
-    if (!b_side)
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rsa, (lds_void_t*)(lds + lbase), 16, live ? voff_a[slot] : OOB, soff_a, 0, 0);
-    else
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rsb, (lds_void_t*)(lds + lbase), 16, live ? voff_b[slot] : OOB, soff_b, 0, 0);
-  };
-  int n = s0, kk = 0;                                       // sample and first l of the running stage
-  if (n_stages > 0) {
-    const bool live = 4 * g_lane < L;
-    const unsigned sa = (unsigned)((long long)n * d.a_ns * 4), sb = (unsigned)((long long)n * d.b_ns * 4);
+  // the sample boundary: the weighted Gram of the lane's entries over the outputs, pair by pair, summed over the wave
+  auto sample_end = [&](int n) {
+    float* r = red + 4 * COV_PAIRS_MAX * (n & 1) + COV_PAIRS_MAX * wave;
+    int pair = 0;
 #pragma unroll
-    for (int i = 0; i < NP; ++i) issue(i, live, sa, sb, 0u);
-  }
-  for (int t = 0; t < n_stages; ++t) {
-    __builtin_amdgcn_s_waitcnt(0x0f70);        // vmcnt(0): this wave's DMA of stage t has landed
-    __syncthreads();
-    flush_sample();
-    int kn = kk + nt::KC, nn = n;
-    const bool sample_ends = kn >= L;
-    if (sample_ends) { kn = 0; ++nn; }
-    const bool live_n = t + 1 < n_stages && kn + 4 * g_lane < L;
-    const unsigned sa = (unsigned)(((long long)nn * d.a_ns + kn) * 4), sb = (unsigned)(((long long)nn * d.b_ns + kn) * 4);
-    const unsigned buf = (unsigned)(t & 1) * nt::PANEL_B, nbuf = nt::PANEL_B - buf;
-    const bool tail_stage = kk + nt::KC > L;    // (the last stage of a sample whose L is no multiple of the stage)
-    auto rd = [&](unsigned at) { return *reinterpret_cast<const __attribute__((address_space(3))) f32x4*>(lds + at + buf); };
-    f32x4 a[KG], b;
+    for (int ca = 0; ca < 4 * KG; ++ca) {
+      if (ca < K) {
+        float ta[4];
 #pragma unroll
-    for (int m = 0; m < KG; ++m) a[m] = rd(addr_a[m][0]);
-    b = rd(addr_b[0]);
+        for (int q = 0; q < 4; ++q) ta[q] = wq[q] * c[ca >> 2][0][4 * q + (ca & 3)];
 #pragma unroll
-    for (int j = 0; j < nt::STEPS; ++j) {
-      if (tail_stage) {
-        asm volatile("; l tail" ::: "memory");             // keeps this a branch around a VALU-only block
+        for (int cb = ca; cb < 4 * KG; ++cb) {
+          if (cb < K) {
+            float v = ta[0] * c[cb >> 2][0][cb & 3];
 #pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const bool gone = kk + 4 * (2 * j + h) + e >= L;
-#pragma unroll
-          for (int m = 0; m < KG; ++m) a[m][e] = gone ? 0.0f : a[m][e];
-          b[e] = gone ? 0.0f : b[e];
-        }
-      }
-      f32x4 na[KG], nb;
-      if (j + 1 < nt::STEPS) {
-#pragma unroll
-        for (int m = 0; m < KG; ++m) na[m] = rd(addr_a[m][j + 1]);
-        nb = rd(addr_b[j + 1]);
-      }
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-#pragma unroll
-        for (int m = 0; m < KG; ++m) c[m] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[m][e], b[e], c[m], 0, 0, 0);
-        if (4 * j + e < NP) issue(4 * j + e, live_n, sa, sb, nbuf);   // one piece behind a group of MFMAs
-      }
-      if (j + 1 < nt::STEPS) {
-#pragma unroll
-        for (int m = 0; m < KG; ++m) a[m] = na[m];
-        b = nb;
-      }
-    }
-    if (sample_ends) {
-      // the sample boundary: the weighted Gram of the lane's entries over the outputs, pair by pair, summed over the wave
-      float* r = red + 4 * COV_PAIRS_MAX * (n & 1) + COV_PAIRS_MAX * wave;
-      int pair = 0;
-#pragma unroll
-      for (int ca = 0; ca < 4 * KG; ++ca) {
-        if (ca < K) {
-          float ta[4];
-#pragma unroll
-          for (int q = 0; q < 4; ++q) ta[q] = wq[q] * c[ca >> 2][4 * q + (ca & 3)];
-#pragma unroll
-          for (int cb = ca; cb < 4 * KG; ++cb) {
-            if (cb < K) {
-              float v = ta[0] * c[cb >> 2][cb & 3];
-#pragma unroll
-              for (int q = 1; q < 4; ++q) v = __builtin_fmaf(ta[q], c[cb >> 2][4 * q + (cb & 3)], v);
-              v = wave_sum_dpp(v);
-              if (lane == 63) r[pair] = v;
-              ++pair;
-            }
+            for (int q = 1; q < 4; ++q) v = __builtin_fmaf(ta[q], c[cb >> 2][0][4 * q + (cb & 3)], v);
+            v = wave_sum_dpp(v);
+            if (lane == 63) r[pair] = v;
+            ++pair;
           }
         }
       }
-#pragma unroll
-      for (int m = 0; m < KG; ++m) c[m] = 0.0f;
-      flush = n;
     }
-    n = nn;
-    kk = kn;
-  }
+#pragma unroll
+    for (int m = 0; m < KG; ++m) c[m][0] = 0.0f;
+  };
+  const int last = ps_walk_samples(d, it.slice, dma, addr_a, addr_b, c, h, sample_end, flush);
   __syncthreads();                   // the wave sums of the item's last sample
-  flush_sample();
+  if (last >= 0) flush(last);
 }
 
 __global__ void __launch_bounds__(PS_THREADS, 2) ps_cov_product_kernel(const PsCovBatch batch) {
-  __shared__ __attribute__((aligned(1024))) char smem[4 * nt::PANEL_B];
+  __shared__ __attribute__((aligned(1024))) char smem[nt::LDS_B];
   __shared__ float red[2 * 4 * COV_PAIRS_MAX];                             // [sample parity][wave][pair]
   const PsCov& d = batch.e[owner_of(batch, (long long)blockIdx.x)];
   const int local = (int)(blockIdx.x - d.base);
