@@ -188,6 +188,14 @@ class curv_persample_quad_desc(ctypes.Structure):
                 ("first", ctypes.c_int32), ("alpha", ctypes.c_float)]
 
 
+class curv_persample_grid_desc(ctypes.Structure):
+    """Mirror of ``curv_persample_grid_desc`` in include/curv_hip.h (`shift` and `gain` are host arrays of H floats)."""
+    _fields_ = [(k, ctypes.c_void_p) for k in ("A", "B", "u", "v", "V", "out")] + \
+               [("shift", ctypes.POINTER(ctypes.c_float)), ("gain", ctypes.POINTER(ctypes.c_float))] + \
+               [(k, ctypes.c_longlong) for k in ("a_ns", "a_rs", "b_ns", "b_rs", "v_rs", "o_stride", "o_hs")] + \
+               [(k, ctypes.c_int32) for k in ("S", "M", "Nc", "L", "H", "first")]
+
+
 class curv_persample_cov_desc(ctypes.Structure):
     """Mirror of ``curv_persample_cov_desc`` in include/curv_hip.h."""
     _fields_ = [("A", ctypes.c_void_p), ("B", ctypes.c_void_p), ("W", ctypes.c_void_p), ("out", ctypes.c_void_p)] + \
@@ -293,6 +301,9 @@ SIGNATURES = {
     "curv_persample_quad_workspace_bytes": (_sz, [ctypes.POINTER(curv_persample_quad_desc), _i]),
     "curv_persample_quad_plan_flops": (_i, [ctypes.POINTER(curv_persample_quad_desc), _i, ctypes.POINTER(ctypes.c_longlong)]),
     "curv_persample_quad_reduce": (_i, [_vp, ctypes.POINTER(curv_persample_quad_desc), _i, _vp, _sz]),
+    "curv_persample_quad_grid_workspace_bytes": (_sz, [ctypes.POINTER(curv_persample_grid_desc), _i]),
+    "curv_persample_quad_grid_plan_flops": (_i, [ctypes.POINTER(curv_persample_grid_desc), _i, ctypes.POINTER(ctypes.c_longlong)]),
+    "curv_persample_quad_grid_reduce": (_i, [_vp, ctypes.POINTER(curv_persample_grid_desc), _i, _vp, _sz]),
     "curv_persample_cov_workspace_bytes": (_sz, [ctypes.POINTER(curv_persample_cov_desc), _i]),
     "curv_persample_cov_plan_flops": (_i, [ctypes.POINTER(curv_persample_cov_desc), _i, ctypes.POINTER(ctypes.c_longlong)]),
     "curv_persample_cov_reduce": (_i, [_vp, ctypes.POINTER(curv_persample_cov_desc), _i, _vp, _sz]),
@@ -313,6 +324,7 @@ PATH_AUTO, PATH_SMALL, PATH_GROUPED = 0, 1, 2     # CURV_PATH_* (curv_factor_des
 SMALL_MAX_FLOP = 2.0e9              # CURV_SMALL_MAX_FLOP
 CONVT_MAX_PHASES = 64               # CURV_CONVT_MAX_PHASES
 PERSAMPLE_COV_MAX_OUTPUTS = 16      # CURV_PERSAMPLE_COV_MAX_OUTPUTS
+PERSAMPLE_GRID_MAX = 16             # CURV_PERSAMPLE_GRID_MAX
 GEMM_TABLE_RESIDENT = 1             # CURV_GEMM_TABLE_RESIDENT
 ERR_NOT_PD, ERR_INVALID, ERR_WORKSPACE, ERR_HIP, ERR_NOT_CONVERGED = 1, 2, 3, 4, 5     # CURV_ERR_* of the header
 

@@ -30,6 +30,12 @@
 // staging; the product launch leaves one float per (tile, sample) instead of a slab (see ps_product_tile), the reduce
 // launch sums a sample's tiles in tile order.
 //
+// The same reduction for H <= 16 damping pairs at once (curv_persample_quad_grid_reduce): per sample and grid point,
+//   out[h][n] (+)= gain[h] * sum_ij w_h(i, j) * P_n[i][j]**2,   w_h = 1 / ((u_i + shift_h)(v_j + shift_h))  or  1 / (V_ij + shift_h)
+// - in the posterior's eigenbasis the damping (add, multiply) enters the variance only through these weights (curvatures.py:
+// functional_variance_grid).  Two more modes of ps_product_tile: P_n**2 is formed once per sample and
+// summed against the weights of one grid point after the other; partial[tile][sample][h].
+//
 // The third (curv_persample_cov_reduce): a Gram over K <= 16 outputs, per sample,
 //   out[n][c][c'] (+)= alpha * sum_ij W[i][j] * P_{n,c}[i][j] * P_{n,c'}[i][j],   P_{n,c} = A_{c,n} B_n^T
 // - the joint covariance of the network outputs (curvatures.py: functional_covariance).  A kernel of its own
@@ -83,6 +89,26 @@ struct PsQuad : PsOperands {
 };
 
 typedef ArgBatch<PsQuad, PS_BATCH> PsQuadBatch;
+
+// A product of curv_persample_quad_grid_reduce: H grid points, each with its `shift` and `gain` (by value: the tables of
+// the call travel with the kernel arguments), and the weights' source - the eigenvalues u (rows of the tile the kernel
+// computes) and v (columns), or the dense V (entry (i, j) at V[i v_is + j v_js]); u / v and the V strides change places
+// with the operands when `swap`.  partial[tile][sample][h].  Eight products per launch: the record is 320 bytes.
+constexpr int GRID_MAX = CURV_PERSAMPLE_GRID_MAX;
+constexpr int PS_GRID_BATCH = 8;
+
+struct PsGrid : PsOperands {
+  const float* u;              // separable form (V null)
+  const float* v;
+  const float* V;              // dense form (u, v null)
+  float* out;
+  float* partial;
+  long long v_is, v_js, o_stride, o_hs;
+  int H;
+  float shift[GRID_MAX], gain[GRID_MAX];
+};
+
+typedef ArgBatch<PsGrid, PS_GRID_BATCH> PsGridBatch;
 
 // A product of curv_persample_cov_reduce: K operands A_c (output c at A + c a_cs) against one B.  Output tiles are
 // COV_TI rows i x 128 columns j of ALL outputs (see ps_cov_tile); `half` and `swap` are 0.  partial[tile][sample][pair],
@@ -185,6 +211,38 @@ bool quad_plan_of(const curv_persample_quad_desc& d, int index, Plan* p) {
   return true;
 }
 
+// (`slab_bytes`: the partials, H floats per output tile and sample; tiling and FLOPs are those of quad_plan_of)
+bool grid_plan_of(const curv_persample_grid_desc& d, int index, Plan* p) {
+  const char* const who = "curv_persample_quad_grid";
+  if (d.H < 1 || d.H > GRID_MAX) {
+    set_error("%s: item %d: H %d outside 1 .. %d", who, index, d.H, GRID_MAX);
+    return false;
+  }
+  if (!d.shift || !d.gain) {
+    set_error("%s: item %d: null shift or gain (host arrays of H floats)", who, index);
+    return false;
+  }
+  for (int h = 0; h < d.H; ++h)
+    if (!(d.shift[h] > 0.0f) || !std::isfinite(d.shift[h]) || !std::isfinite(d.gain[h])) {
+      set_error("%s: item %d: grid point %d: shift %g must be finite and > 0, gain %g finite", who, index, h,
+                (double)d.shift[h], (double)d.gain[h]);
+      return false;
+    }
+  if (!tiling_of(d, who, index, p)) return false;
+  if (((d.a_ns | d.a_rs | d.b_ns | d.b_rs) & 3) != 0) {
+    set_error("%s: item %d: operand strides must be multiples of 4 floats (a_ns %lld a_rs %lld b_ns %lld b_rs %lld)", who,
+              index, d.a_ns, d.a_rs, d.b_ns, d.b_rs);
+    return false;
+  }
+  if ((d.V != nullptr && d.v_rs < d.Nc) || d.o_stride < 1 || (d.H > 1 && d.o_hs < 1)) {
+    set_error("%s: item %d: invalid strides (v_rs %lld below Nc %d, o_stride %lld or o_hs %lld below 1)", who, index,
+              d.v_rs, d.Nc, d.o_stride, d.o_hs);
+    return false;
+  }
+  p->slab_bytes = align_up((size_t)p->tiles * d.S * d.H * sizeof(float), 256);
+  return true;
+}
+
 // (`slab_bytes`: the partials, K (K + 1) / 2 floats per output tile and sample; the tiling is ps_cov_tile's)
 bool cov_plan_of(const curv_persample_cov_desc& d, int index, Plan* p) {
   const char* const who = "curv_persample_cov";
@@ -240,7 +298,15 @@ bool cov_plan_of(const curv_persample_cov_desc& d, int index, Plan* p) {
 // in red[sample parity][wave], and behind the next barrier (the next stage's, or one after the last stage) thread 0 adds
 // the four in wave order and writes partial[tile][sample]: no barrier of its own, fixed order, no atomics.  The parity
 // keeps the waves that run ahead into the next sample's end off the four values thread 0 is still reading.
-enum { PS_SQ = 0, PS_QUAD_W = 1, PS_QUAD_ONES = 2 };
+// PS_GRID_SEP / PS_GRID_DENSE (d a PsGrid): the same sum for H grid points in turn, w_h = 1 / ((u_i + shift_h)(v_j +
+// shift_h)) or 1 / (V_ij + shift_h).  The second register set holds what the weights are made of, loaded once per item:
+// the lane's 32 u values (its rows) and, beside it, its 2 (half tiles: 1) v values, or its share of the V tile - with
+// +inf for rows and columns at or beyond M / Nc (not read), whose weight is then 1 / inf = 0.  At the sample's end the
+// lane squares its accumulators in place, once, and for h = 0 .. H - 1 (a loop that is not unrolled: one h is live at a
+// time) divides, sums - 34 divisions per h in the separable form, 64 in the dense one - and reduces over the wave by DPP
+// (wave_sum.h); lane 63 leaves red[sample parity][wave][h], thread h adds the four behind the next barrier and writes
+// partial[tile][sample][h].  Grid point h sees shift[h] only: its bits do not depend on the other grid points.
+enum { PS_SQ = 0, PS_QUAD_W = 1, PS_QUAD_ONES = 2, PS_GRID_SEP = 3, PS_GRID_DENSE = 4 };
 
 // An item of a product launch: its output tile and its range of samples.
 struct PsItem {
@@ -340,6 +406,27 @@ __device__ __forceinline__ void ps_product_tile(const Product& d, int local, lds
           if (roff(m, reg) < rows_left && col_in[nb]) q[m][nb][reg] = d.W[at];
         }
   }
+  float vcol[BN];                                            // PS_GRID_SEP: v of the lane's columns (u is in q[m][0])
+  if constexpr (MODE == PS_GRID_SEP) {
+#pragma unroll
+    for (int m = 0; m < 2; ++m)
+#pragma unroll
+      for (int reg = 0; reg < 16; ++reg)
+        q[m][0][reg] = roff(m, reg) < rows_left ? d.u[i0 + row_a + 4 * h + roff(m, reg)] : __builtin_inff();
+#pragma unroll
+    for (int nb = 0; nb < BN; ++nb) vcol[nb] = col_in[nb] ? d.v[j0 + row_b + 32 * nb + r32] : __builtin_inff();
+  }
+  if constexpr (MODE == PS_GRID_DENSE) {
+#pragma unroll
+    for (int m = 0; m < 2; ++m)
+#pragma unroll
+      for (int nb = 0; nb < BN; ++nb)
+#pragma unroll
+        for (int reg = 0; reg < 16; ++reg) {
+          const long long at = (long long)(i0 + row_a + 4 * h + roff(m, reg)) * d.v_is + (long long)(j0 + row_b + 32 * nb + r32) * d.v_js;
+          q[m][nb][reg] = (roff(m, reg) < rows_left && col_in[nb]) ? d.V[at] : __builtin_inff();
+        }
+  }
 
   if constexpr (MODE == PS_SQ) {
     // the sample boundary: square the tile of P_n, add it to the running sum, start the next sample from zero
@@ -366,6 +453,61 @@ __device__ __forceinline__ void ps_product_tile(const Product& d, int local, lds
           slab[r * PS_TM + col] = q[m][nb][reg];
         }
       }
+  } else if constexpr (MODE == PS_GRID_SEP || MODE == PS_GRID_DENSE) {
+    const int H = d.H;
+    auto flush = [&](int n) {
+      if (tid < H) {
+        const float* r = red + 4 * GRID_MAX * (n & 1) + tid;
+        d.partial[((long long)it.tile * d.S + n) * H + tid] = ((r[0] + r[GRID_MAX]) + r[2 * GRID_MAX]) + r[3 * GRID_MAX];
+      }
+    };
+    // the sample boundary: P_n**2 in place, then the weighted sum over the tile for one grid point after the other
+    auto sample_end = [&](int n) {
+#pragma unroll
+      for (int m = 0; m < 2; ++m)
+#pragma unroll
+        for (int nb = 0; nb < BN; ++nb) c[m][nb] = c[m][nb] * c[m][nb];
+      float* r = red + 4 * GRID_MAX * (n & 1) + GRID_MAX * wave;
+#pragma unroll 1
+      for (int g = 0; g < H; ++g) {
+        const float sh = d.shift[g];
+        float v = 0.0f;
+        if constexpr (MODE == PS_GRID_SEP) {
+          float acc[BN];                                       // per column: sum_i P_ij**2 / (u_i + shift)
+#pragma unroll
+          for (int nb = 0; nb < BN; ++nb) acc[nb] = 0.0f;
+#pragma unroll
+          for (int m = 0; m < 2; ++m)
+#pragma unroll
+            for (int reg = 0; reg < 16; ++reg) {
+              const float ru = 1.0f / (q[m][0][reg] + sh);
+#pragma unroll
+              for (int nb = 0; nb < BN; ++nb) acc[nb] = __builtin_fmaf(ru, c[m][nb][reg], acc[nb]);
+            }
+#pragma unroll
+          for (int nb = 0; nb < BN; ++nb) v = __builtin_fmaf(1.0f / (vcol[nb] + sh), acc[nb], v);
+        } else {
+#pragma unroll
+          for (int m = 0; m < 2; ++m)
+#pragma unroll
+            for (int nb = 0; nb < BN; ++nb) {
+              float acc = 0.0f;                                // one chain per MFMA block, the blocks added in order
+#pragma unroll
+              for (int reg = 0; reg < 16; ++reg) acc = __builtin_fmaf(1.0f / (q[m][nb][reg] + sh), c[m][nb][reg], acc);
+              v += acc;
+            }
+        }
+        v = wave_sum_dpp(v);
+        if (lane == 63) r[g] = v;
+      }
+#pragma unroll
+      for (int m = 0; m < 2; ++m)
+#pragma unroll
+        for (int nb = 0; nb < BN; ++nb) c[m][nb] = 0.0f;
+    };
+    const int last = ps_walk_samples(d, it.slice, dma, addr_a, addr_b, c, h, sample_end, flush);
+    __syncthreads();                 // the wave sums of the item's last sample
+    if (last >= 0) flush(last);
   } else {
     auto flush = [&](int n) {
       if (tid == 0) {
@@ -432,6 +574,39 @@ __global__ void __launch_bounds__(PS_THREADS) ps_quad_reduce_kernel(const PsQuad
   for (int t = 0; t < d.tiles; ++t) v += d.partial[(long long)t * d.S + s];
   v *= d.alpha;
   float* out = d.out + s * d.o_stride;
+  *out = d.first ? v : *out + v;
+}
+
+// The same items for curv_persample_quad_grid_reduce: partial[tile][sample][h].
+__global__ void __launch_bounds__(PS_THREADS, 2) ps_grid_product_kernel(const PsGridBatch batch) {
+  __shared__ __attribute__((aligned(1024))) char smem[nt::LDS_B];
+  __shared__ float red[2 * 4 * GRID_MAX];                                   // [sample parity][wave][h]
+  const PsGrid& d = batch.e[owner_of(batch, (long long)blockIdx.x)];
+  const int local = (int)(blockIdx.x - d.base);
+  if (d.half) {
+    if (d.V) ps_product_tile<true, PS_GRID_DENSE>(d, local, (lds_char_t*)smem, red);
+    else ps_product_tile<true, PS_GRID_SEP>(d, local, (lds_char_t*)smem, red);
+  } else {
+    if (d.V) ps_product_tile<false, PS_GRID_DENSE>(d, local, (lds_char_t*)smem, red);
+    else ps_product_tile<false, PS_GRID_SEP>(d, local, (lds_char_t*)smem, red);
+  }
+}
+
+// Reduce: one thread per (sample, h) sums the partials of its product in tile order, applies gain[h], writes or adds.
+// Blocks of a product: ceil(S H / 256).
+__global__ void __launch_bounds__(PS_THREADS) ps_grid_reduce_kernel(const PsGridBatch batch) {
+  const PsGrid& d = batch.e[owner_of(batch, (long long)blockIdx.x)];
+  const long long idx = (blockIdx.x - d.base) * PS_THREADS + threadIdx.x;
+  const long long step = (long long)d.S * d.H;
+  if (idx >= step) return;
+  const long long s = idx / d.H;
+  const int g = (int)(idx - s * d.H);
+  const float* p = d.partial + idx;
+  float v = 0.f;
+#pragma unroll 8
+  for (int t = 0; t < d.tiles; ++t) v += p[t * step];
+  v *= d.gain[g];
+  float* out = d.out + g * d.o_hs + s * d.o_stride;
   *out = d.first ? v : *out + v;
 }
 
@@ -601,7 +776,7 @@ struct PsPack {
 
 typedef ArgBatch<PsPack, PS_BATCH> PsPackBatch;
 static_assert(sizeof(PsBatch) <= 3840 && sizeof(PsQuadBatch) <= 3840 && sizeof(PsPackBatch) <= 3840 &&
-                  sizeof(PsCovBatch) <= 3840,
+                  sizeof(PsCovBatch) <= 3840 && sizeof(PsGridBatch) <= 3840,
               "kernel argument block must stay below 4 KB");
 
 bool pack_plan_of(const curv_persample_pack_desc& d, int index, PsPack* out) {
@@ -680,7 +855,11 @@ size_t bytes_of(const std::vector<Plan>& plans) {
 }
 
 // A Product (PsProduct / PsQuad) with the operands of `d` as the kernels see them; its own fields are the caller's.  The
-// one place where A and B change places.
+// one place where A and B change places.  (curv_persample_grid_desc has no alpha: its scale is gain[h].)
+inline float alpha_of(const curv_persample_grid_desc&) { return 1.0f; }
+template <typename Desc>
+float alpha_of(const Desc& d) { return d.alpha; }
+
 template <typename Product, typename Desc>
 Product operands_of(const Desc& d, const Plan& p) {
   Product P;
@@ -694,7 +873,7 @@ Product operands_of(const Desc& d, const Plan& p) {
   }
   P.tiles_n = p.tiles_n; P.tiles = p.tiles; P.spi = p.spi; P.slices = p.slices;
   P.half = p.half; P.swap = p.swap;
-  P.first = d.first ? 1 : 0; P.alpha = d.alpha;
+  P.first = d.first ? 1 : 0; P.alpha = alpha_of(d);
   P.base = 0;
   return P;
 }
@@ -724,14 +903,30 @@ PsCov cov_of(const curv_persample_cov_desc& d, const Plan& p, float* partial) {
   return P;
 }
 
+// The same for curv_persample_quad_grid_reduce: the grid's tables by value; u and v (the rows and columns of the product)
+// and the strides of V change places with the operands.
+PsGrid grid_of(const curv_persample_grid_desc& d, const Plan& p, float* partial) {
+  PsGrid P = operands_of<PsGrid>(d, p);
+  P.u = d.u; P.v = d.v; P.V = d.V; P.out = d.out; P.partial = partial;
+  P.o_stride = d.o_stride; P.o_hs = d.o_hs; P.H = d.H;
+  P.v_is = d.v_rs; P.v_js = 1;
+  if (p.swap) { std::swap(P.u, P.v); std::swap(P.v_is, P.v_js); }
+  for (int h = 0; h < GRID_MAX; ++h) {
+    P.shift[h] = d.shift[std::min(h, d.H - 1)];
+    P.gain[h] = d.gain[std::min(h, d.H - 1)];
+  }
+  return P;
+}
+
 // The body of the accumulate entry points: plans, check(name, desc, index) of every descriptor's operands, workspace,
 // then one walk and two launches per batch - lane 0 counts the items of the product launch, lane 1 the blocks of the
-// reduce launch, reduce_units(desc) of them per product.  make = product_of / quad_of / cov_of.
-template <typename Product, typename Desc, typename Check, typename Units>
+// reduce launch, reduce_units(desc) of them per product.  make = product_of / quad_of / cov_of / grid_of; BATCH products
+// per launch (the kernels' argument type says how many).
+template <typename Product, int BATCH, typename Desc, typename Check, typename Units>
 int run_products(const char* name, void* stream_, const Desc* descs, int n, void* workspace, size_t workspace_bytes,
                  bool (*plan)(const Desc&, int, Plan*), Check check, Product (*make)(const Desc&, const Plan&, float*),
-                 Units reduce_units, void (*product_kernel)(ArgBatch<Product, PS_BATCH>),
-                 void (*reduce_kernel)(ArgBatch<Product, PS_BATCH>)) {
+                 Units reduce_units, void (*product_kernel)(ArgBatch<Product, BATCH>),
+                 void (*reduce_kernel)(ArgBatch<Product, BATCH>)) {
   if (n <= 0) return CURV_OK;
   hipStream_t stream = (hipStream_t)stream_;
   std::vector<Plan> plans;
@@ -743,7 +938,7 @@ int run_products(const char* name, void* stream_, const Desc* descs, int n, void
   const int rc = side::require_workspace(name, workspace, workspace_bytes, bytes_of(plans), 256);
   if (rc != CURV_OK) return rc;
   size_t at = 0;
-  return for_arg_batches<Product, PS_BATCH, 2>(
+  return for_arg_batches<Product, BATCH, 2>(
       n, name,
       [&](int i, Product* P, long long* units) {
         *P = make(descs[i], plans[i], (float*)((char*)workspace + at));
@@ -752,7 +947,7 @@ int run_products(const char* name, void* stream_, const Desc* descs, int n, void
         units[1] = reduce_units(descs[i]);
       },
       [](int, long long units) { return units; },
-      [&](const ArgBatch<Product, PS_BATCH>* b, const long long*, const unsigned* grid) {
+      [&](const ArgBatch<Product, BATCH>* b, const long long*, const unsigned* grid) {
         hipLaunchKernelGGL(product_kernel, dim3(grid[0]), dim3(PS_THREADS), 0, stream, b[0]);
         CURV_LAUNCH_CHECK();
         hipLaunchKernelGGL(reduce_kernel, dim3(grid[1]), dim3(PS_THREADS), 0, stream, b[1]);
@@ -806,6 +1001,30 @@ extern "C" int curv_persample_quad_reduce(void* stream_, const curv_persample_qu
       },
       quad_of, [](const curv_persample_quad_desc& d) { return cdivll(d.S, PS_THREADS); },
       ps_quad_product_kernel, ps_quad_reduce_kernel);
+}
+
+extern "C" size_t curv_persample_quad_grid_workspace_bytes(const curv_persample_grid_desc* descs, int n) {
+  return side::workspace_bytes("curv_persample_quad_grid_workspace_bytes", descs, n, grid_plan_of, bytes_of);
+}
+
+extern "C" int curv_persample_quad_grid_plan_flops(const curv_persample_grid_desc* descs, int n, long long* out) {
+  return side::plan_flops("curv_persample_quad_grid_plan_flops", descs, n, out, grid_plan_of);
+}
+
+extern "C" int curv_persample_quad_grid_reduce(void* stream_, const curv_persample_grid_desc* descs, int n, void* workspace,
+                                               size_t workspace_bytes) {
+  return run_products(
+      "curv_persample_quad_grid_reduce", stream_, descs, n, workspace, workspace_bytes, grid_plan_of,
+      [](const char* name, const curv_persample_grid_desc& d, int i) -> int {
+        CURV_REQUIRE(d.A && d.B && d.out, "%s: item %d: null operand", name, i);
+        CURV_REQUIRE(((reinterpret_cast<uintptr_t>(d.A) | reinterpret_cast<uintptr_t>(d.B)) & 15) == 0,
+                     "%s: item %d: A and B must be 16-byte aligned", name, i);
+        CURV_REQUIRE(d.V ? (!d.u && !d.v) : (d.u && d.v),
+                     "%s: item %d: the weights are either u and v (separable) or V (dense)", name, i);
+        return CURV_OK;
+      },
+      grid_of, [](const curv_persample_grid_desc& d) { return cdivll((long long)d.S * d.H, PS_THREADS); },
+      ps_grid_product_kernel, ps_grid_reduce_kernel);
 }
 
 extern "C" size_t curv_persample_cov_workspace_bytes(const curv_persample_cov_desc* descs, int n) {

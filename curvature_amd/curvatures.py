@@ -604,23 +604,29 @@ class Curvature(ABC):
         raise NotImplementedError(f"{type(self).__name__}.functional_variance: no linearised predictive for this estimator "
                                   "(KFAC, Diagonal and EFB have one)")
 
-    def _predictive_operands(self, what: str, call: str, inputs: bool, basis, weights, kept: str, check=None):
-        """What both reductions of the linearised predictive (`_functional_variance`, `_stage_output`) start from: the
-        checks, the selected layers that have an inverse state, their per-sample operands from the current records (the
+    def _predictive_operands(self, what: str, call: str, inputs: bool, basis, weights, kept: str, check=None,
+                             select: str = "inv_state"):
+        """What the reductions of the linearised predictive (`_functional_variance`, `_stage_output`,
+        `_functional_variance_grid`) start from: the checks, the selected layers that have an inverse state (`select`:
+        the dict that says so - the grid needs `state` only), their per-sample operands from the current records (the
         g side only unless `inputs`), and the key that ties a kept X side to the recorded inputs themselves (tensor and
         version), not just to their shapes.  With `inputs`, attribute `kept` is dropped first (the X side of other records
         goes before the new one is made) and what depends on the forward pass and the posterior only is worked out: X
         (rotated) and the squared weights; ``check(operands)`` runs before any of that (the caller's test of its own
         arguments against the batch).  Returns (layers, operands, key, (xs, ws) or None)."""
-        assert self.inv_state, "Inverse state dict is empty. Did you call 'invert' prior to this?"
+        have = getattr(self, select)
+        if select == "inv_state":
+            assert have, "Inverse state dict is empty. Did you call 'invert' prior to this?"
+        else:
+            assert have, "State dict is empty. Did you call 'update' prior to this?"
         if self.shard is not None and self.shard.world > 1:
             raise NotImplementedError(f"{what}.{call}: layer-sharded estimators are not supported")
         if getattr(self, "record", None) is None:
             raise RuntimeError(f"{what}.{call}: no recording hooks (construct with per_sample=True, or go "
                                "through evaluate.glm_predictive)")
         layers = self._per_sample_layers(f"{what}.{call}", "select other layer types")
-        layers = [l for l in layers if l in self.inv_state]
-        assert layers, "Inverse state dict holds none of the selected layers"
+        layers = [l for l in layers if l in have]
+        assert layers, f"{select} holds none of the selected layers"
         layout = dict(rows_outer=True, in_place=False) if basis is not None else {}
         operands = self._per_sample_operands(what, layers, x_side=inputs, **layout)
         if check is not None:
@@ -667,6 +673,88 @@ class Curvature(ABC):
                                     for k, ((s, _, _), g, x, w) in enumerate(zip(operands, gs, xs, ws))])
         ones = torch.ones(1, len(layers), dtype=torch.float32, device=dev)
         ops.gemm_batched([ops.Gemm(ones, rows, out.unsqueeze(0), beta=0.0 if first else 1.0)])
+        return out
+
+    # ------------------------------------------------------------------ the variance over a grid of damping pairs
+    def functional_variance_grid(self, out: Tensor, hypers, *, first: bool = True, inputs: bool = True) -> Tensor:
+        """`functional_variance` for a whole list of damping pairs at once, without an inversion: row h of `out` receives
+        (`first`: is overwritten with) what ``invert(*hypers[h])`` followed by `functional_variance` would give.  In the
+        posterior's eigenbasis the damping enters a layer's share only through the weights of the squared entries of
+        Q_n = U_G^T P_n U_A (Diagonal: P_n itself), with rho = add / multiply:
+
+            KFAC      (1 / multiply) sum_ij Q_ij**2 / ((lambda_G,i + sqrt(rho)) (lambda_A,j + sqrt(rho)))
+            Diagonal  (1 / multiply) sum_ij P_ij**2 / (state_ij + rho)
+            EFB       (1 / multiply) sum_ij Q_ij**2 / (state_ij + rho)
+
+        so one backward pass, one rotation and one pass over the per-sample products per output serve every pair
+        (`ops.per_sample_quad_grid_reduce`).  `hypers`: a sequence of ``(add, multiply)``, each a pair of scalars or a pair of
+        per-layer lists, resolved per layer exactly as `invert` resolves them; every value finite and > 0 (ValueError naming
+        the pair).  `out`: a contiguous ``(len(hypers), N)`` float32 GPU tensor.  More than `ops.PERSAMPLE_GRID_MAX` pairs
+        run as chunks of that many over the same operands.  Needs `state` only, not `inv_state`; KFAC needs
+        `KFAC.decompose()` after its last `update()`.  Records, layers, ``inputs=False`` (the kept X side is
+        ``_variance_grid_inputs``; `evaluate.glm_predictive_grid` drops it) and the refusal of a layer-sharded estimator as
+        for `functional_variance`.  Implemented by KFAC, Diagonal and EFB."""
+        raise NotImplementedError(f"{type(self).__name__}.functional_variance_grid: no linearised predictive for this "
+                                  "estimator (KFAC, Diagonal and EFB have one)")
+
+    def _grid_points(self, what: str, hypers, separable: bool):
+        """`hypers` checked and resolved: for every selected layer index the lists ``shift[h]`` (rho, or sqrt(rho) for the
+        separable weights) and ``gain[h]`` = 1 / multiply, as a function ``(layer) -> (shifts, gains)``."""
+        hypers = list(hypers)
+        if not hypers:
+            raise ValueError(f"{what}.functional_variance_grid: no damping pairs")
+        for h, pair in enumerate(hypers):
+            if not isinstance(pair, (tuple, list)) or len(pair) != 2:
+                raise ValueError(f"{what}.functional_variance_grid: pair {h} is not an (add, multiply) pair: {pair!r}")
+            for value in pair:
+                values = [value] if _is_scalar(value) else list(value)
+                if not values or not all(math.isfinite(float(x)) and float(x) > 0 for x in values):
+                    raise ValueError(f"{what}.functional_variance_grid: pair {h} {tuple(pair)!r}: add and multiply must "
+                                     "be finite and > 0")
+        gindex = self._global_index()
+
+        def points(layer):
+            resolved = [self._hyper(add, multiply, gindex[layer], len(gindex)) for add, multiply in hypers]
+            rhos = [n / s for n, s in resolved]
+            return [math.sqrt(r) for r in rhos] if separable else rhos, [1.0 / s for _, s in resolved]
+        return hypers, points
+
+    def _functional_variance_grid(self, what: str, out: Tensor, hypers, points, first: bool, inputs: bool, basis,
+                                  spectrum) -> Tensor:
+        """`functional_variance_grid` of the three estimators, on the checked `hypers` and the ``points(layer)`` of
+        `_grid_points`.  `basis` as in `_functional_variance`; ``spectrum(layer)`` =
+        (u, v, None) - the eigenvalues of the G and the A side: separable weights - or (None, None, V): dense ones."""
+        def check(operands):
+            N = operands[0][0].N
+            if tuple(out.shape) != (len(hypers), N) or out.dtype != torch.float32 or not out.is_cuda or \
+                    not out.is_contiguous():
+                raise RuntimeError(f"{what}.functional_variance_grid: out must be a contiguous float32 GPU tensor of shape "
+                                   f"({len(hypers)}, {N}), got {tuple(out.shape)} {out.dtype} on {out.device}")
+        layers, operands, key, x_side = self._predictive_operands(what, "functional_variance_grid", inputs, basis, None,
+                                                                   "_variance_grid_inputs", check, select="state")
+        dev, N = operands[0][1].device, operands[0][0].N
+        if x_side is not None:
+            self._variance_grid_inputs = (key, x_side[0])
+        kept = getattr(self, "_variance_grid_inputs", None)
+        if kept is None or kept[0] != key:
+            raise RuntimeError(f"{what}.functional_variance_grid(inputs=False): no call with inputs=True on these recorded "
+                               "inputs before (a new forward pass needs inputs=True once)")
+        xs = kept[1]
+        gs = [g for _, g, _ in operands]
+        if basis is not None:
+            gs = self._rotated([(basis(l)[0], g, s.m) for l, (s, g, _) in zip(layers, operands)])
+        tables = [points(l) for l in layers]
+        ones = torch.ones(1, len(layers), dtype=torch.float32, device=dev)
+        # chunks of PERSAMPLE_GRID_MAX pairs over the same operands; every layer into its own (pairs, N) block, the blocks
+        # summed in layer order by the ones-row product of `_functional_variance`
+        for h0 in range(0, len(hypers), ops.PERSAMPLE_GRID_MAX):
+            h1 = min(h0 + ops.PERSAMPLE_GRID_MAX, len(hypers))
+            rows = torch.empty(len(layers), h1 - h0, N, dtype=torch.float32, device=dev)
+            ops.per_sample_quad_grid_reduce([
+                ops.PerSampleGridJob.of(s, g, x, *spectrum(l), rows[k], shifts[h0:h1], gains[h0:h1], first=True)
+                for k, (l, (s, _, _), g, x, (shifts, gains)) in enumerate(zip(layers, operands, gs, xs, tables))])
+            ops.gemm_batched([ops.Gemm(ones, rows.view(len(layers), -1), out[h0:h1].view(1, -1),
+                                       beta=0.0 if first else 1.0)])
         return out
 
     # ------------------------------------------------------------------ joint covariance of the outputs
@@ -968,6 +1056,12 @@ class Diagonal(Curvature):
     def _predictive_terms(self):
         return "Diagonal", None, lambda layer: self.inv_state[layer]
 
+    def functional_variance_grid(self, out: Tensor, hypers, *, first: bool = True, inputs: bool = True) -> Tensor:
+        # inv**2 = 1 / (s state + n) = (1 / s) / (state + n / s)
+        hypers, points = self._grid_points("Diagonal", hypers, separable=False)
+        return self._functional_variance_grid("Diagonal", out, hypers, points, first, inputs, None,
+                                              lambda layer: (None, None, self.state[layer]))
+
     def functional_variance(self, out: Tensor, *, first: bool = True, inputs: bool = True) -> Tensor:
         what, basis, weights = self._predictive_terms()
         return self._functional_variance(what, out, first, inputs, basis, weights)
@@ -1211,6 +1305,7 @@ class KFAC(Curvature):
         ``grad_scale``: the loss scale of a ``torch.cuda.amp.GradScaler`` whose scaled loss produced the recorded
         gradients; the G side is divided by ``grad_scale ** 2``.  The caller skips ``update()`` on the steps the scaler
         skips (non-finite gradients)."""
+        self._decomposition = None                   # (of the factors as they were: `decompose`)
         jobs, group_jobs, half_jobs, convt_jobs = [], [], [], []
         launch = {ops.FactorJob: jobs, ops.GroupFactorJob: group_jobs, ops.HalfFactorJob: half_jobs,
                   ops.ConvTFactorJob: convt_jobs}
@@ -1288,6 +1383,7 @@ class KFAC(Curvature):
         addresses and the launch plans built on them stay).  Extension of the reference API: its only way to start
         over is a new estimator."""
         self._fresh.update((layer, side) for layer in self.state for side in (0, 1))
+        self._decomposition = None
 
     def invert(self, add: Union[float, list, tuple] = 0., multiply: Union[float, list, tuple] = 1., *, check: bool = True):
         """`check=False` (keyword-only extension): skip the read-back of the status words - the call's only host
@@ -1371,6 +1467,32 @@ class KFAC(Curvature):
     def _predictive_terms(self):
         # sample = L_G Z L_A^T: T = L_G^T g, Y = L_A^T X
         return "KFAC", lambda layer: tuple(f.t() for f in reversed(self.inv_state[layer])), None
+
+    def decompose(self) -> None:
+        """The eigendecompositions F = U diag(lambda) U^T of the accumulated factors of every owned layer, in one batched
+        `ops.eigh`: what `functional_variance_grid` needs instead of an inversion.  Kept per layer as
+        ``(U_G^T, U_A^T, lambda_G, lambda_A)``, the eigenvalues clamped at 0 (a factor is positive semi-definite; the
+        iteration may leave -1e-9); `update()` and `restart_accumulation()` drop it.  Grouped layers (stacked factors)
+        have no per-sample form and are left out."""
+        assert self.state, "State dict is empty. Did you call 'update' prior to this?"
+        layers = [l for l, (A, G) in self.state.items() if A.dim() == 2 and G.dim() == 2]
+        vecs, vals = ops.eigh([f for l in layers for f in self.state[l]], with_values=True) if layers else ([], [])
+        self._decomposition = {}
+        for k, layer in enumerate(layers):
+            (U_A, U_G), (lam_A, lam_G) = vecs[2 * k:2 * k + 2], vals[2 * k:2 * k + 2]
+            self._decomposition[layer] = (U_G.t().contiguous(), U_A.t().contiguous(), ops.clamp_min0_(lam_G),
+                                          ops.clamp_min0_(lam_A))
+
+    def functional_variance_grid(self, out: Tensor, hypers, *, first: bool = True, inputs: bool = True) -> Tensor:
+        # L L^T = (sqrt(s) F + sqrt(n) I)^-1 = U diag(1 / (sqrt(s) (lambda + sqrt(n / s)))) U^T on both sides: the two
+        # 1 / sqrt(s) make the gain 1 / s, and the shift of both spectra is sqrt(n / s)
+        hypers, points = self._grid_points("KFAC", hypers, separable=True)
+        kept = getattr(self, "_decomposition", None)
+        if kept is None:
+            raise RuntimeError("KFAC.functional_variance_grid: no eigendecomposition of the current factors: call "
+                               "decompose() after the last update()")
+        return self._functional_variance_grid("KFAC", out, hypers, points, first, inputs, lambda layer: kept[layer][:2],
+                                              lambda layer: (kept[layer][2], kept[layer][3], None))
 
     def functional_variance(self, out: Tensor, *, first: bool = True, inputs: bool = True) -> Tensor:
         what, basis, weights = self._predictive_terms()
@@ -1720,6 +1842,12 @@ class EFB(Curvature):
     def _predictive_terms(self):
         # sample = U_G (Z * inv) U_A^T: T = U_G^T g, Y = U_A^T X, as `_update_per_sample`
         return "EFB", lambda layer: self._eigvecs_t(layer)[::-1], lambda layer: self.inv_state[layer]
+
+    def functional_variance_grid(self, out: Tensor, hypers, *, first: bool = True, inputs: bool = True) -> Tensor:
+        hypers, points = self._grid_points("EFB", hypers, separable=False)
+        return self._functional_variance_grid("EFB", out, hypers, points, first, inputs,
+                                              lambda layer: self._eigvecs_t(layer)[::-1],
+                                              lambda layer: (None, None, self.state[layer]))
 
     def functional_variance(self, out: Tensor, *, first: bool = True, inputs: bool = True) -> Tensor:
         what, basis, weights = self._predictive_terms()

@@ -174,7 +174,8 @@ def _linearised(what: str, model: torch.nn.Module, estimator, images: torch.Tens
     estimator without recording hooks borrows them for the length of the block, one forward pass.  Yields
     ``(logits, backward)``; ``backward(c)`` back-propagates ``logits[:, c].sum()`` into the records with
     `torch.autograd.grad` on the parameters that require grad (no ``.grad`` is touched).  On the way out the borrowed hooks
-    are removed and what the estimator kept of this batch (``_variance_inputs``, ``_covariance_outputs``) is dropped."""
+    are removed and what the estimator kept of this batch (``_variance_inputs``, ``_covariance_outputs``,
+    ``_variance_grid_inputs``) is dropped."""
     first_param = next(model.parameters())
     if not first_param.is_cuda or not images.is_cuda:
         raise RuntimeError(f"curvature_amd runs on MI355X only: {what} got a CPU model or batch (no CPU fallback)")
@@ -203,10 +204,11 @@ def _linearised(what: str, model: torch.nn.Module, estimator, images: torch.Tens
             del estimator.hooks, estimator.record
         estimator.__dict__.pop("_variance_inputs", None)       # the X side of this batch
         estimator.__dict__.pop("_covariance_outputs", None)    # ... and the stack of its outputs' g sides
+        estimator.__dict__.pop("_variance_grid_inputs", None)  # ... and the X side `functional_variance_grid` kept
 
 
 def _probit(logits: torch.Tensor, variance: torch.Tensor) -> torch.Tensor:
-    return torch.softmax(logits.float() / torch.sqrt(1.0 + (math.pi / 8.0) * variance), dim=1)
+    return torch.softmax(logits.float() / torch.sqrt(1.0 + (math.pi / 8.0) * variance), dim=-1)
 
 
 def glm_predictive(model: torch.nn.Module, estimator, images: torch.Tensor, outputs=None):
@@ -233,6 +235,54 @@ def glm_predictive(model: torch.nn.Module, estimator, images: torch.Tensor, outp
             estimator.functional_variance(variance[:, c], inputs=k == 0)
     logits = logits.detach()
     return logits, variance, _probit(logits, variance)
+
+
+def glm_predictive_grid(model: torch.nn.Module, estimator, images: torch.Tensor, hypers, outputs=None):
+    """`glm_predictive` for a whole list of damping pairs ``hypers = [(add, multiply), ...]`` at once, without an
+    inversion: ``(logits, variance, probs)`` with `logits` (N, classes) and `variance`, `probs` of shape
+    ``(len(hypers), N, classes)`` - slice h is what ``estimator.invert(*hypers[h])`` followed by `glm_predictive` gives.
+    One forward pass and per output one backward pass and one `Curvature.functional_variance_grid` call serve every
+    pair (KFAC: after `KFAC.decompose()`); the estimator's `inv_state` is neither needed nor touched.  `outputs`, model
+    mode, hooks, parameters and ``.grad`` as in `glm_predictive`.  GPU only."""
+    hypers = list(hypers)
+    with _linearised("glm_predictive_grid", model, estimator, images) as (logits, backward):
+        classes = list(range(logits.shape[1])) if outputs is None else [int(c) for c in outputs]
+        N, C = logits.shape
+        variance = torch.zeros(len(hypers), N, C, dtype=torch.float32, device=logits.device)
+        column = torch.empty(len(hypers), N, dtype=torch.float32, device=logits.device)
+        for k, c in enumerate(classes):
+            backward(c)
+            estimator.functional_variance_grid(column, hypers, inputs=k == 0)
+            variance[:, :, c] = column
+    logits = logits.detach()
+    return logits, variance, _probit(logits, variance)         # (N, classes) against (H, N, classes)
+
+
+def tune_glm(model: torch.nn.Module, dataset: Iterable, estimator, hypers, outputs=None):
+    """The damping pair of ``hypers = [(add, multiply), ...]`` under which the probit GLM predictive explains the labelled
+    `dataset` best - the search the reference's ``scripts/hyper.py`` does with one inversion and one evaluation per
+    candidate, here one `glm_predictive_grid` per batch for all of them.  Returns ``dict(nll=(H,), accuracy=(H,),
+    best=int)``: `nll` the mean negative log-likelihood of the probit probabilities at the labels, `accuracy` the share
+    of inputs whose most probable class is the label (both float64 CPU tensors, accumulated on the device and read
+    once), `best` the argmin of `nll` (the first on a tie).  Nothing is called on the estimator afterwards: the caller
+    goes on with ``estimator.invert(*hypers[best])``."""
+    hypers = list(hypers)
+    device = next(model.parameters()).device
+    nll = torch.zeros(len(hypers), dtype=torch.float64, device=device)
+    hits = torch.zeros(len(hypers), dtype=torch.float64, device=device)
+    count = 0
+    for images, labels in dataset:
+        images = images.to(device, non_blocking=True)
+        labels = torch.as_tensor(labels).to(device, non_blocking=True).long()
+        probs = glm_predictive_grid(model, estimator, images, hypers, outputs=outputs)[2]
+        index = labels.view(1, -1, 1).expand(len(hypers), -1, 1)
+        nll -= torch.log(probs.gather(2, index).squeeze(2).double()).sum(1)
+        hits += (probs.argmax(2) == labels.view(1, -1)).double().sum(1)
+        count += int(labels.numel())
+    if count == 0:
+        raise ValueError("tune_glm: the dataset is empty")
+    nll, accuracy = (nll / count).cpu(), (hits / count).cpu()
+    return dict(nll=nll, accuracy=accuracy, best=int(torch.argmin(nll)))
 
 
 def _joint_covariance(what: str, model: torch.nn.Module, estimator, images: torch.Tensor, outputs):

@@ -561,7 +561,7 @@ def per_sample_pack(operands: Sequence[PerSampleOperand], dsts: Sequence[torch.T
 
 
 class _PerSampleProduct:
-    """What `PerSampleJob`, `PerSampleQuadJob` and `PerSampleCovJob` share: the operands A_n (M, L) at ``A + n a_ns`` with row stride `a_rs` and
+    """What `PerSampleJob`, `PerSampleQuadJob`, `PerSampleGridJob` and `PerSampleCovJob` share: the operands A_n (M, L) at ``A + n a_ns`` with row stride `a_rs` and
     B_n (Nc, L) likewise, for `S` samples, and `alpha` / `first`."""
     __slots__ = ("A", "B", "S", "M", "Nc", "L", "a_ns", "a_rs", "b_ns", "b_rs", "alpha", "first")
 
@@ -574,7 +574,7 @@ class _PerSampleProduct:
     @classmethod
     def of(cls, sides: PerSampleSides, A, B, *own, alpha=1.0, first=False):
         """The job on a layer's `per_sample_operands`: A the g side, B the x side, `own` the remaining tensors of the
-        constructor (C; W, out; W, out, K, a_cs)."""
+        constructor (C; W, out; u, v, V, out, shift, gain; W, out, K, a_cs)."""
         return cls(A, B, *own, sides.N, sides.m, sides.n, sides.L, sides.g.ns, sides.g.rs, sides.x.ns, sides.x.rs,
                    alpha=alpha, first=first)
 
@@ -590,15 +590,23 @@ class PerSampleJob(_PerSampleProduct):
         self._set_operands(A, B, S, M, Nc, L, a_ns, a_rs, b_ns, b_rs, alpha, first)
 
 
+def _fill_per_sample_sizes(d, j: _PerSampleProduct) -> None:
+    d.S, d.M, d.Nc, d.L = j.S, j.M, j.Nc, j.L
+    d.a_ns, d.a_rs, d.b_ns, d.b_rs = j.a_ns, j.a_rs, j.b_ns, j.b_rs
+    d.first = int(j.first)
+
+
 def _fill_per_sample(d, j: _PerSampleProduct, name: str, tensors) -> None:
     """The shared fields of job `j` into descriptor `d`; with `tensors` (the job's own, behind A and B, None among them
     skipped; None: a plan query) also the device / dtype checks, the extent check of A and B under `name`, and their
     addresses."""
-    d.S, d.M, d.Nc, d.L = j.S, j.M, j.Nc, j.L
-    d.a_ns, d.a_rs, d.b_ns, d.b_rs = j.a_ns, j.a_rs, j.b_ns, j.b_rs
-    d.alpha, d.first = j.alpha, int(j.first)
-    if tensors is None:
-        return
+    _fill_per_sample_sizes(d, j)
+    d.alpha = j.alpha
+    if tensors is not None:
+        _check_per_sample_tensors(d, j, name, tensors)
+
+
+def _check_per_sample_tensors(d, j: _PerSampleProduct, name: str, tensors) -> None:
     for t in (j.A, j.B) + tuple(t for t in tensors if t is not None):
         if not t.is_cuda:
             raise RuntimeError("curvature_amd runs on MI355X only: got a CPU tensor (no CPU fallback)")
@@ -681,6 +689,87 @@ def per_sample_quad_reduce(jobs: Sequence[PerSampleQuadJob]) -> None:
     if not jobs:
         return
     _run_build("curv_persample_quad_workspace_bytes", "curv_persample_quad_reduce", _per_sample_quad_descs(jobs),
+               len(jobs), jobs[0].out.device, "persample")
+
+
+PERSAMPLE_GRID_MAX = _lib.PERSAMPLE_GRID_MAX
+
+
+class PerSampleGridJob(_PerSampleProduct):
+    """out[h, n] (+)= gain[h] * sum_ij w_h[i, j] * (A_n B_n^T)[i, j]**2 for `S` samples and the H grid points
+    ``(shift[h], gain[h])`` (at most `PERSAMPLE_GRID_MAX`): A, B and their sizes and strides as in `PerSampleQuadJob`.
+    The weights are separable, ``w_h[i, j] = 1 / ((u[i] + shift[h]) (v[j] + shift[h]))`` with `u` (M,) and `v` (Nc,)
+    contiguous, or dense, ``w_h[i, j] = 1 / (V[i, j] + shift[h])`` with `V` an (M, Nc) view with unit column stride: give
+    `u` and `v`, or `V`, and None for the other.  `shift` (finite, > 0) and `gain` (finite) are sequences of H Python
+    floats; they travel with the kernel arguments.  `out` an (H, S) float32 view with positive strides.  `first`:
+    overwrite out.  There is no `alpha`.  A / B / out and the weights may also be `None` with explicit sizes (plan
+    queries)."""
+    __slots__ = ("u", "v", "V", "out", "shift", "gain")
+
+    def __init__(self, A, B, u, v, V, out, shift, gain, S, M, Nc, L, a_ns, a_rs, b_ns, b_rs, alpha=1.0, first=False):
+        self.u, self.v, self.V, self.out = u, v, V, out
+        self.shift, self.gain = [float(x) for x in shift], [float(x) for x in gain]
+        if float(alpha) != 1.0:
+            raise ValueError("PerSampleGridJob has no alpha: the scale of grid point h is gain[h]")
+        self._set_operands(A, B, S, M, Nc, L, a_ns, a_rs, b_ns, b_rs, 1.0, first)
+
+
+def _per_sample_grid_descs(jobs: Sequence[PerSampleGridJob], check_tensors: bool = True):
+    name = "per_sample_quad_grid_reduce"
+    arr = (_lib.curv_persample_grid_desc * len(jobs))()
+    keep = []                                        # the host tables the descriptors point to
+    for d, j in zip(arr, jobs):
+        H = len(j.shift)
+        if not 1 <= H <= PERSAMPLE_GRID_MAX or len(j.gain) != H:
+            raise ValueError(f"{name}: {H} shifts and {len(j.gain)} gains; a job takes 1 to {PERSAMPLE_GRID_MAX} grid "
+                             "points, as many gains as shifts")
+        for h, (s, g) in enumerate(zip(j.shift, j.gain)):
+            if not (s > 0 and math.isfinite(s) and math.isfinite(g)):
+                raise ValueError(f"{name}: grid point {h}: shift {s} must be finite and > 0, gain {g} finite")
+        _fill_per_sample_sizes(d, j)
+        d.H = H
+        tables = ((ctypes.c_float * H)(*j.shift), (ctypes.c_float * H)(*j.gain))
+        keep.append(tables)
+        d.shift, d.gain = ctypes.cast(tables[0], ctypes.POINTER(ctypes.c_float)), ctypes.cast(tables[1], ctypes.POINTER(ctypes.c_float))
+        d.v_rs, d.o_stride, d.o_hs = j.Nc, 1, j.S
+        if not check_tensors:
+            continue
+        separable = j.V is None
+        if (j.u is None) != (j.v is None) or separable == (j.u is None):
+            raise RuntimeError(f"{name}: give the weights as u and v (separable) or as V (dense), not both")
+        _check_per_sample_tensors(d, j, name, (j.out, j.u, j.v, j.V))
+        if separable:
+            for what, t, rows in (("u", j.u, j.M), ("v", j.v, j.Nc)):
+                if t.dim() != 1 or t.shape[0] != rows or not t.is_contiguous():
+                    raise RuntimeError(f"{name}: {what} must be a contiguous vector of {rows} values, got {tuple(t.shape)}")
+            d.u, d.v = j.u.data_ptr(), j.v.data_ptr()
+        else:
+            if j.V.dim() != 2 or tuple(j.V.shape) != (j.M, j.Nc) or j.V.stride(1) != 1:
+                raise RuntimeError(f"{name}: V must be an ({j.M},{j.Nc}) view with unit column stride, got "
+                                   f"{tuple(j.V.shape)}")
+            d.V, d.v_rs = j.V.data_ptr(), j.V.stride(0)
+        if j.out.dim() != 2 or tuple(j.out.shape) != (H, j.S) or (j.S > 1 and j.out.stride(1) < 1) or \
+                (H > 1 and j.out.stride(0) < 1):
+            raise RuntimeError(f"{name}: destination must be an ({H},{j.S}) view with positive strides, got "
+                               f"{tuple(j.out.shape)}")
+        d.out, d.o_stride, d.o_hs = j.out.data_ptr(), max(j.out.stride(1), 1), max(j.out.stride(0), 1)
+    arr._tables = keep
+    return arr
+
+
+def per_sample_quad_grid_plan_flops(jobs: Sequence[PerSampleGridJob]) -> List[int]:
+    """Multiply-add FLOPs (2 per multiply-add) of the MFMA products the plan executes per job
+    (curv_persample_quad_grid_plan_flops, host only): those of `per_sample_quad_plan_flops`, whatever H."""
+    if not jobs:
+        return []
+    return _plan_flops("curv_persample_quad_grid_plan_flops", _per_sample_grid_descs(jobs, check_tensors=False), len(jobs))
+
+
+def per_sample_quad_grid_reduce(jobs: Sequence[PerSampleGridJob]) -> None:
+    """curv_persample_quad_grid_reduce over any number of products, on the current stream; partials from `workspace`."""
+    if not jobs:
+        return
+    _run_build("curv_persample_quad_grid_workspace_bytes", "curv_persample_quad_grid_reduce", _per_sample_grid_descs(jobs),
                len(jobs), jobs[0].out.device, "persample")
 
 

@@ -561,6 +561,57 @@ int curv_persample_quad_reduce(void* stream, const curv_persample_quad_desc* des
                                size_t workspace_bytes);
 
 /* ------------------------------------------------------------------------------------------------
+ * The same reduction for a whole grid of damping pairs (add, multiply) in one pass over the products
+ * (csrc/persample.hip; DESIGN.md "K12"): for h < H, per sample,
+ *     out[h*o_hs + s*o_stride] (+)= gain[h] * sum_{i < M, j < Nc} w_h(i,j) * ( sum_{l < L} A_s[i][l] * B_s[j][l] )**2
+ *     separable (u and v given, V NULL):   w_h(i,j) = 1 / ((u[i] + shift[h]) * (v[j] + shift[h]))     u: M floats, v: Nc floats
+ *     dense     (V given, u and v NULL):   w_h(i,j) = 1 / (V[i*v_rs + j] + shift[h])                  V: M x Nc, v_rs >= Nc
+ * With the operands in the posterior's eigenbasis the damping enters the variance only through these weights, with
+ * rho = add / multiply and gain = 1 / multiply:
+ *     KFAC      A = U_G^T g,  B = U_A^T X,  u = eig(G), v = eig(A),  shift = sqrt(rho)
+ *     Diagonal  A = g,        B = X,        V = state,               shift = rho
+ *     EFB       A = U_G^T g,  B = U_A^T X,  V = state,               shift = rho
+ * so one call gives what H calls of curv_persample_quad_reduce behind H inversions give.  1 <= H <=
+ * CURV_PERSAMPLE_GRID_MAX.  `shift` and `gain` are HOST arrays of H floats; they are copied into the kernel arguments
+ * during the call.  Every shift must be finite and > 0, every gain finite; u, v and V are expected to be >= 0 (an
+ * entry + shift of 0 divides by zero).  A, B, S, M, Nc, L and the four operand strides follow the rules of
+ * curv_persample_quad_desc: A and B 16-byte aligned, strides multiples of 4 floats, extents below 2^31 bytes, no
+ * l >= L enters a product.  u, v and V are never read outside their M / Nc / M x Nc entries.  out is H rows of S values,
+ * o_stride >= 1 floats between samples and o_hs >= 1 floats between grid points (H > 1); `first` != 0 overwrites them,
+ * nothing between them is touched.  There is no alpha: gain[h] is the scale.
+ * The weights are formed with IEEE (correctly rounded) divisions.  fp32 MFMA, fp32 sums in a fixed order (lane, wave
+ * by DPP, workgroup, then tiles in tile order), no atomics; the plan of an item follows from its own sizes only and
+ * grid point h is computed from shift[h] and gain[h] alone, so row h has the same bits whatever other grid points or
+ * items share the call.  Enqueues on `stream` only, never waits on the host, allocates nothing.  An empty call is a
+ * no-op; invalid sizes, strides, H, shift or gain return CURV_ERR_INVALID with the item named.
+ * ---------------------------------------------------------------------------------------------- */
+#define CURV_PERSAMPLE_GRID_MAX 16
+typedef struct curv_persample_grid_desc {
+  const float* A;
+  const float* B;
+  const float* u;          /* separable form: M eigenvalues of the A side ... */
+  const float* v;          /* ... and Nc of the B side */
+  const float* V;          /* dense form: M x Nc */
+  float* out;
+  const float* shift;      /* host, H floats */
+  const float* gain;       /* host, H floats */
+  long long a_ns, a_rs, b_ns, b_rs, v_rs, o_stride, o_hs;
+  int32_t S, M, Nc, L;
+  int32_t H;
+  int32_t first;
+} curv_persample_grid_desc;
+/* Device scratch for these items (bytes: H floats per output tile and sample); 0 with the error text set (naming the
+ * item) for invalid input.  Host only. */
+size_t curv_persample_quad_grid_workspace_bytes(const curv_persample_grid_desc* descs, int n);
+/* Host only: the multiply-add FLOPs of the MFMA products the plan executes per item (those of
+ * curv_persample_quad_plan_flops: they do not depend on H; the H weighted sums at a sample's end are not counted). */
+int curv_persample_quad_grid_plan_flops(const curv_persample_grid_desc* descs, int n, long long* out);
+/* An MFMA and a reduce launch per batch of up to 8 items.  The workspace must be 256-byte aligned.  `descs`, `shift`
+ * and `gain` are host arrays; they may be reused as soon as the call returns. */
+int curv_persample_quad_grid_reduce(void* stream, const curv_persample_grid_desc* descs, int n, void* workspace,
+                                    size_t workspace_bytes);
+
+/* ------------------------------------------------------------------------------------------------
  * Joint output covariance of the linearised Laplace predictive: the third reduction of the per-sample products
  * (csrc/persample.hip) - a Gram over K outputs, per sample:
  *     out[s*o_ns + c*o_rs + c'] (+)= alpha * sum_{i < M, j < Nc} W[i*w_rs + j] * P_{s,c}[i][j] * P_{s,c'}[i][j]
