@@ -26,6 +26,7 @@ from torch import Tensor
 from torch.nn import Module, Sequential
 
 from . import _lib, ops
+from .predictive import LinearisedPredictive, PredictiveTerms
 
 SUPPORTED_LAYERS = ['Linear', 'Conv2d', 'MultiheadAttention']
 # selectable by name but not part of the default selection (which stays what the reference selects)
@@ -378,6 +379,8 @@ class Curvature(ABC):
                 owners.append(0)
             self.shard.allgather_params(entries, owners)
 
+    _is_scalar = staticmethod(_is_scalar)
+
     @staticmethod
     def _hyper(add, multiply, index: int, count: int):
         """(n, s) of layer `index`: lists only when BOTH are non-scalars (curvatures.py:361-365)."""
@@ -580,7 +583,7 @@ class Curvature(ABC):
         ops.gemm_batched([ops.Gemm(R, t.view(rows, -1), y.view(rows, -1)) for (R, t, rows), y in zip(sides, out)])
         return out
 
-    # ------------------------------------------------------------------ linearised (GLM) predictive
+    # ------------------------------------------------------------------ linearised (GLM) predictive: the API (predictive.py)
     def functional_variance(self, out: Tensor, *, first: bool = True, inputs: bool = True) -> Tensor:
         """The variance of a network output under the posterior this estimator samples from, linearised in the weights:
         with P_n the Jacobian of the output for sample n with respect to a layer's [W | b], adds ``sum_layers v_layer[n]``
@@ -597,85 +600,14 @@ class Curvature(ABC):
         column of an (N, classes) matrix).  ``inputs=False`` reuses the X side of the previous call - rotated into the
         posterior's basis once per forward pass, not once per output - like ``KFAC.update(inputs=False)``; it raises
         RuntimeError unless the recorded inputs are the very tensors of that call, and nothing else may have used the
-        per-sample scratch in between.  The kept X side (the unfolded inputs of every layer) stays on the estimator as
-        ``_variance_inputs`` until the next ``inputs=True`` call replaces it; `evaluate.glm_predictive` drops it.  Linear and Conv2d (groups 1, dilation 1, integer padding) with
+        per-sample scratch in between.  The kept X side (the unfolded inputs of every layer) stays on the estimator (entry
+        ``"variance"`` of ``_predictive_kept``) until the next ``inputs=True`` call replaces it or `drop_predictive_state`
+        drops it, as `evaluate.glm_predictive` does.  Linear and Conv2d (groups 1, dilation 1, integer padding) with
         float32 GPU records; other selected layers raise NotImplementedError, as does a layer-sharded estimator.
         Implemented by KFAC, Diagonal and EFB.  No counterpart in the reference, which has the Monte-Carlo predictive only."""
         raise NotImplementedError(f"{type(self).__name__}.functional_variance: no linearised predictive for this estimator "
                                   "(KFAC, Diagonal and EFB have one)")
 
-    def _predictive_operands(self, what: str, call: str, inputs: bool, basis, weights, kept: str, check=None,
-                             select: str = "inv_state"):
-        """What the reductions of the linearised predictive (`_functional_variance`, `_stage_output`,
-        `_functional_variance_grid`) start from: the checks, the selected layers that have an inverse state (`select`:
-        the dict that says so - the grid needs `state` only), their per-sample operands from the current records (the
-        g side only unless `inputs`), and the key that ties a kept X side to the recorded inputs themselves (tensor and
-        version), not just to their shapes.  With `inputs`, attribute `kept` is dropped first (the X side of other records
-        goes before the new one is made) and what depends on the forward pass and the posterior only is worked out: X
-        (rotated) and the squared weights; ``check(operands)`` runs before any of that (the caller's test of its own
-        arguments against the batch).  Returns (layers, operands, key, (xs, ws) or None)."""
-        have = getattr(self, select)
-        if select == "inv_state":
-            assert have, "Inverse state dict is empty. Did you call 'invert' prior to this?"
-        else:
-            assert have, "State dict is empty. Did you call 'update' prior to this?"
-        if self.shard is not None and self.shard.world > 1:
-            raise NotImplementedError(f"{what}.{call}: layer-sharded estimators are not supported")
-        if getattr(self, "record", None) is None:
-            raise RuntimeError(f"{what}.{call}: no recording hooks (construct with per_sample=True, or go "
-                               "through evaluate.glm_predictive)")
-        layers = self._per_sample_layers(f"{what}.{call}", "select other layer types")
-        layers = [l for l in layers if l in have]
-        assert layers, f"{select} holds none of the selected layers"
-        layout = dict(rows_outer=True, in_place=False) if basis is not None else {}
-        operands = self._per_sample_operands(what, layers, x_side=inputs, **layout)
-        if check is not None:
-            check(operands)
-        key = tuple((l, id(self.record[l][0]), self.record[l][0]._version, s.n, s.N, s.L, s.x.ns, s.x.rs)
-                    for l, (s, _, _) in zip(layers, operands))
-        if not inputs:
-            return layers, operands, key, None
-        setattr(self, kept, None)
-        xs = [x for _, _, x in operands]
-        if basis is not None:
-            xs = self._rotated([(basis(l)[1], x, s.n) for l, (s, _, x) in zip(layers, operands)])
-        ws = [None] * len(layers)
-        if weights is not None:
-            ws = [ops.mul(weights(l), weights(l)) for l in layers]
-        return layers, operands, key, (xs, ws)
-
-    def _functional_variance(self, what: str, out: Tensor, first: bool, inputs: bool, basis, weights) -> Tensor:
-        """`functional_variance` of the three estimators.  ``basis(layer)`` = (R_G, R_A), the rotations T = R_G g and
-        Y = R_A X of the packed (rows, N Lp) operands, or `basis` None (no rotation: the operands are read where they are);
-        ``weights(layer)`` = the (m, n) tensor whose square weighs the entries, or `weights` None (all ones)."""
-        def check(operands):
-            N = operands[0][0].N
-            if out.dim() != 1 or out.shape[0] != N or out.dtype != torch.float32 or not out.is_cuda:
-                raise RuntimeError(f"{what}.functional_variance: out must be a float32 GPU view of length {N}, got "
-                                   f"{tuple(out.shape)} {out.dtype} on {out.device}")
-        layers, operands, key, x_side = self._predictive_operands(what, "functional_variance", inputs, basis, weights,
-                                                                   "_variance_inputs", check)
-        dev, N = operands[0][1].device, operands[0][0].N
-        if x_side is not None:
-            self._variance_inputs = (key,) + x_side
-        kept = getattr(self, "_variance_inputs", None)
-        if kept is None or kept[0] != key:
-            raise RuntimeError(f"{what}.functional_variance(inputs=False): no call with inputs=True on these recorded inputs "
-                               "before (a new forward pass needs inputs=True once)")
-        _, xs, ws = kept
-        gs = [g for _, g, _ in operands]
-        if basis is not None:
-            gs = self._rotated([(basis(l)[0], g, s.m) for l, (s, g, _) in zip(layers, operands)])
-        # every layer into its own row, the rows summed in layer order by one product with a row of ones: the result does
-        # not depend on how the layers are grouped into launches
-        rows = torch.empty(len(layers), N, dtype=torch.float32, device=dev)
-        ops.per_sample_quad_reduce([ops.PerSampleQuadJob.of(s, g, x, w, rows[k], first=True)
-                                    for k, ((s, _, _), g, x, w) in enumerate(zip(operands, gs, xs, ws))])
-        ones = torch.ones(1, len(layers), dtype=torch.float32, device=dev)
-        ops.gemm_batched([ops.Gemm(ones, rows, out.unsqueeze(0), beta=0.0 if first else 1.0)])
-        return out
-
-    # ------------------------------------------------------------------ the variance over a grid of damping pairs
     def functional_variance_grid(self, out: Tensor, hypers, *, first: bool = True, inputs: bool = True) -> Tensor:
         """`functional_variance` for a whole list of damping pairs at once, without an inversion: row h of `out` receives
         (`first`: is overwritten with) what ``invert(*hypers[h])`` followed by `functional_variance` would give.  In the
@@ -691,82 +623,21 @@ class Curvature(ABC):
         per-layer lists, resolved per layer exactly as `invert` resolves them; every value finite and > 0 (ValueError naming
         the pair).  `out`: a contiguous ``(len(hypers), N)`` float32 GPU tensor.  More than `ops.PERSAMPLE_GRID_MAX` pairs
         run as chunks of that many over the same operands.  Needs `state` only, not `inv_state`; KFAC needs
-        `KFAC.decompose()` after its last `update()`.  Records, layers, ``inputs=False`` (the kept X side is
-        ``_variance_grid_inputs``; `evaluate.glm_predictive_grid` drops it) and the refusal of a layer-sharded estimator as
-        for `functional_variance`.  Implemented by KFAC, Diagonal and EFB."""
+        `KFAC.decompose()` after its last `update()`.  Records, layers, ``inputs=False`` (the kept X side is entry
+        ``"grid"`` of ``_predictive_kept``; `evaluate.glm_predictive_grid` drops it) and the refusal of a layer-sharded
+        estimator as for `functional_variance`.  Implemented by KFAC, Diagonal and EFB."""
         raise NotImplementedError(f"{type(self).__name__}.functional_variance_grid: no linearised predictive for this "
                                   "estimator (KFAC, Diagonal and EFB have one)")
 
-    def _grid_points(self, what: str, hypers, separable: bool):
-        """`hypers` checked and resolved: for every selected layer index the lists ``shift[h]`` (rho, or sqrt(rho) for the
-        separable weights) and ``gain[h]`` = 1 / multiply, as a function ``(layer) -> (shifts, gains)``."""
-        hypers = list(hypers)
-        if not hypers:
-            raise ValueError(f"{what}.functional_variance_grid: no damping pairs")
-        for h, pair in enumerate(hypers):
-            if not isinstance(pair, (tuple, list)) or len(pair) != 2:
-                raise ValueError(f"{what}.functional_variance_grid: pair {h} is not an (add, multiply) pair: {pair!r}")
-            for value in pair:
-                values = [value] if _is_scalar(value) else list(value)
-                if not values or not all(math.isfinite(float(x)) and float(x) > 0 for x in values):
-                    raise ValueError(f"{what}.functional_variance_grid: pair {h} {tuple(pair)!r}: add and multiply must "
-                                     "be finite and > 0")
-        gindex = self._global_index()
-
-        def points(layer):
-            resolved = [self._hyper(add, multiply, gindex[layer], len(gindex)) for add, multiply in hypers]
-            rhos = [n / s for n, s in resolved]
-            return [math.sqrt(r) for r in rhos] if separable else rhos, [1.0 / s for _, s in resolved]
-        return hypers, points
-
-    def _functional_variance_grid(self, what: str, out: Tensor, hypers, points, first: bool, inputs: bool, basis,
-                                  spectrum) -> Tensor:
-        """`functional_variance_grid` of the three estimators, on the checked `hypers` and the ``points(layer)`` of
-        `_grid_points`.  `basis` as in `_functional_variance`; ``spectrum(layer)`` =
-        (u, v, None) - the eigenvalues of the G and the A side: separable weights - or (None, None, V): dense ones."""
-        def check(operands):
-            N = operands[0][0].N
-            if tuple(out.shape) != (len(hypers), N) or out.dtype != torch.float32 or not out.is_cuda or \
-                    not out.is_contiguous():
-                raise RuntimeError(f"{what}.functional_variance_grid: out must be a contiguous float32 GPU tensor of shape "
-                                   f"({len(hypers)}, {N}), got {tuple(out.shape)} {out.dtype} on {out.device}")
-        layers, operands, key, x_side = self._predictive_operands(what, "functional_variance_grid", inputs, basis, None,
-                                                                   "_variance_grid_inputs", check, select="state")
-        dev, N = operands[0][1].device, operands[0][0].N
-        if x_side is not None:
-            self._variance_grid_inputs = (key, x_side[0])
-        kept = getattr(self, "_variance_grid_inputs", None)
-        if kept is None or kept[0] != key:
-            raise RuntimeError(f"{what}.functional_variance_grid(inputs=False): no call with inputs=True on these recorded "
-                               "inputs before (a new forward pass needs inputs=True once)")
-        xs = kept[1]
-        gs = [g for _, g, _ in operands]
-        if basis is not None:
-            gs = self._rotated([(basis(l)[0], g, s.m) for l, (s, g, _) in zip(layers, operands)])
-        tables = [points(l) for l in layers]
-        ones = torch.ones(1, len(layers), dtype=torch.float32, device=dev)
-        # chunks of PERSAMPLE_GRID_MAX pairs over the same operands; every layer into its own (pairs, N) block, the blocks
-        # summed in layer order by the ones-row product of `_functional_variance`
-        for h0 in range(0, len(hypers), ops.PERSAMPLE_GRID_MAX):
-            h1 = min(h0 + ops.PERSAMPLE_GRID_MAX, len(hypers))
-            rows = torch.empty(len(layers), h1 - h0, N, dtype=torch.float32, device=dev)
-            ops.per_sample_quad_grid_reduce([
-                ops.PerSampleGridJob.of(s, g, x, *spectrum(l), rows[k], shifts[h0:h1], gains[h0:h1], first=True)
-                for k, (l, (s, _, _), g, x, (shifts, gains)) in enumerate(zip(layers, operands, gs, xs, tables))])
-            ops.gemm_batched([ops.Gemm(ones, rows.view(len(layers), -1), out[h0:h1].view(1, -1),
-                                       beta=0.0 if first else 1.0)])
-        return out
-
-    # ------------------------------------------------------------------ joint covariance of the outputs
     def stage_output(self, slot: int, count: int, *, inputs: bool = False) -> None:
         """One output of `functional_covariance`: the caller has just back-propagated ``output[:, c].sum()`` (in ``eval()``
         mode, as for `functional_variance`); the g side of every layer from the current records - packed, and rotated by
         L_G^T (KFAC) or U_G^T (EFB) - goes into slot `slot` of a stack of `count` slots (scratch of its own: `count` x the
         packed g side of the model).  ``inputs=True``, once per forward pass and before the other slots: also the X side
         and the squared weights, exactly as ``functional_variance(inputs=True)`` works them out, and a fresh stack (no slot
-        staged).  The stack and the X side stay on the estimator as ``_covariance_outputs`` until the next ``inputs=True``
-        call replaces them (`evaluate.glm_predictive_joint` drops them); nothing else may use the per-sample scratch in
-        between.  RuntimeError without ``inputs=True`` on these very recorded inputs (tensor and version) and `count`
+        staged).  The stack and the X side stay on the estimator (entry ``"covariance"`` of ``_predictive_kept``) until the
+        next ``inputs=True`` call replaces them (`evaluate.glm_predictive_joint` drops them); nothing else may use the
+        per-sample scratch in between.  RuntimeError without ``inputs=True`` on these very recorded inputs (tensor and version) and `count`
         before.  Layers, records and estimators as for `functional_variance`."""
         raise NotImplementedError(f"{type(self).__name__}.stage_output: no linearised predictive for this estimator "
                                   "(KFAC, Diagonal and EFB have one)")
@@ -784,62 +655,10 @@ class Curvature(ABC):
         raise NotImplementedError(f"{type(self).__name__}.functional_covariance: no linearised predictive for this "
                                   "estimator (KFAC, Diagonal and EFB have one)")
 
-    def _stage_output(self, what: str, slot: int, count: int, inputs: bool, basis, weights) -> None:
-        """`stage_output` of the three estimators; `basis` and `weights` as in `_functional_variance`."""
-        slot, count = int(slot), int(count)
-        if not 1 <= count <= ops.PERSAMPLE_COV_MAX_OUTPUTS or not 0 <= slot < count:
-            raise ValueError(f"{what}.stage_output: slot {slot} of {count} (at most {ops.PERSAMPLE_COV_MAX_OUTPUTS} outputs)")
-        layers, operands, key, x_side = self._predictive_operands(what, "stage_output", inputs, basis, weights,
-                                                                   "_covariance_outputs")
-        if x_side is not None:
-            # a slot is what one output's g side takes: its packed copy, or the record itself where that is read in place
-            sizes = [s.g.floats or s.N * s.g.ns for s, _, _ in operands]
-            stack = ops.per_sample_scratch([count * f for f in sizes], operands[0][1].device, "persample_cov_g")
-            self._covariance_outputs = dict(key=key, count=count, xs=x_side[0], ws=x_side[1], sizes=sizes, stack=stack,
-                                            sides=[s for s, _, _ in operands], staged=set(),
-                                            inputs=[self.record[l][0] for l in layers])
-        kept = getattr(self, "_covariance_outputs", None)
-        if kept is None or kept["key"] != key or kept["count"] != count:
-            raise RuntimeError(f"{what}.stage_output(inputs=False): no call with inputs=True on these recorded inputs and "
-                               f"{count} outputs before (a new forward pass needs inputs=True once)")
-        slots = [t[slot * f:(slot + 1) * f] for t, f in zip(kept["stack"], kept["sizes"])]
-        if basis is not None:
-            self._rotated([(basis(l)[0], g, s.m) for l, (s, g, _) in zip(layers, operands)], slots)
-        else:
-            ops.CopyPlan(slots, [g.reshape(-1)[:f] for (_, g, _), f in zip(operands, kept["sizes"])]).run()
-        kept["staged"].add(slot)
-
-    def _functional_covariance(self, what: str, out: Tensor, first: bool, basis, weights) -> Tensor:
-        """`functional_covariance` of the three estimators (`basis` and `weights` went into the staged operands: they only
-        say here that the estimator has them)."""
-        kept = getattr(self, "_covariance_outputs", None)
-        if kept is None:
-            raise RuntimeError(f"{what}.functional_covariance: no output staged (stage_output(inputs=True) first)")
-        record = getattr(self, "record", None) or {}
-        layers = [k[0] for k in kept["key"]]
-        for (layer, _, version, *_), x in zip(kept["key"], kept["inputs"]):
-            now = record.get(layer, (None, None))[0]
-            if now is not x or now._version != version:
-                raise RuntimeError(f"{what}.functional_covariance: the recorded inputs are no longer those of "
-                                   "stage_output(inputs=True) (a new forward pass needs its outputs staged again)")
-        count, missing = kept["count"], sorted(set(range(kept["count"])) - kept["staged"])
-        if missing:
-            raise RuntimeError(f"{what}.functional_covariance: output slots {missing} of {count} have not been staged since "
-                               "the last stage_output(inputs=True)")
-        sides = kept["sides"]
-        N, dev = sides[0].N, kept["stack"][0].device
-        if tuple(out.shape) != (N, count, count) or out.dtype != torch.float32 or not out.is_cuda or not out.is_contiguous():
-            raise RuntimeError(f"{what}.functional_covariance: out must be a contiguous float32 GPU tensor of shape "
-                               f"({N}, {count}, {count}), got {tuple(out.shape)} {out.dtype} on {out.device}")
-        # every layer into its own (N, count, count) row, the rows summed in layer order by the ones-row product of
-        # `_functional_variance`: the result does not depend on how the layers are grouped into launches
-        rows = torch.empty(len(layers), N, count, count, dtype=torch.float32, device=dev)
-        ops.per_sample_cov_reduce([ops.PerSampleCovJob.of(s, g, x, w, rows[k], count, f, first=True)
-                                   for k, (s, g, x, w, f) in enumerate(zip(sides, kept["stack"], kept["xs"], kept["ws"],
-                                                                           kept["sizes"]))])
-        ones = torch.ones(1, len(layers), dtype=torch.float32, device=dev)
-        ops.gemm_batched([ops.Gemm(ones, rows.view(len(layers), -1), out.view(1, -1), beta=0.0 if first else 1.0)])
-        return out
+    def drop_predictive_state(self) -> None:
+        """Forget what the four methods above kept of the last forward pass for their next call (the X sides, the stack of
+        staged outputs: ``_predictive_kept``).  Nothing to do for an estimator that keeps nothing."""
+        self.__dict__.pop("_predictive_kept", None)
 
     @staticmethod
     def _replace(sample: Tensor, weight: Tensor, bias: Tensor = None):
@@ -923,7 +742,7 @@ class Curvature(ABC):
         self._allgather_sampled()
 
 
-class Diagonal(Curvature):
+class Diagonal(LinearisedPredictive, Curvature):
     """Diagonal Fisher: state += grad**2 * batch_size (curvatures.py:132-193).
 
     ``nn.MultiheadAttention`` modules are handled as in the reference (:159-174, 125-129): their input and
@@ -1053,26 +872,10 @@ class Diagonal(Curvature):
             return prev
         return None
 
-    def _predictive_terms(self):
-        return "Diagonal", None, lambda layer: self.inv_state[layer]
-
-    def functional_variance_grid(self, out: Tensor, hypers, *, first: bool = True, inputs: bool = True) -> Tensor:
-        # inv**2 = 1 / (s state + n) = (1 / s) / (state + n / s)
-        hypers, points = self._grid_points("Diagonal", hypers, separable=False)
-        return self._functional_variance_grid("Diagonal", out, hypers, points, first, inputs, None,
-                                              lambda layer: (None, None, self.state[layer]))
-
-    def functional_variance(self, out: Tensor, *, first: bool = True, inputs: bool = True) -> Tensor:
-        what, basis, weights = self._predictive_terms()
-        return self._functional_variance(what, out, first, inputs, basis, weights)
-
-    def stage_output(self, slot: int, count: int, *, inputs: bool = False) -> None:
-        what, basis, weights = self._predictive_terms()
-        self._stage_output(what, slot, count, inputs, basis, weights)
-
-    def functional_covariance(self, out: Tensor, *, first: bool = True) -> Tensor:
-        what, basis, weights = self._predictive_terms()
-        return self._functional_covariance(what, out, first, basis, weights)
+    def _predictive_terms(self) -> PredictiveTerms:
+        # grid: inv**2 = 1 / (s state + n) = (1 / s) / (state + n / s)
+        return PredictiveTerms("Diagonal", basis=None, weights=lambda layer: self.inv_state[layer], grid_basis=None,
+                               spectrum=lambda layer: (None, None, self.state[layer]), separable=False)
 
     def sample(self, layer: Union[Module, str], z: Optional[Tensor] = None) -> Tensor:
         assert self.inv_state, "Inverse state dict is empty. Did you call 'invert' prior to this?"
@@ -1244,7 +1047,7 @@ def _pairs(first: Tensor, second: Tensor):
     return [(first, second)]
 
 
-class KFAC(Curvature):
+class KFAC(LinearisedPredictive, Curvature):
     """Kronecker-factored Fisher (curvatures.py:264-392).
 
     ``state[layer] = [A, G]`` (fp32, exactly symmetric), ``inv_state[layer] = (L_A, L_G)`` with
@@ -1464,9 +1267,16 @@ class KFAC(Curvature):
                     self._raise_not_pd(info, exc)
                 raise
 
-    def _predictive_terms(self):
-        # sample = L_G Z L_A^T: T = L_G^T g, Y = L_A^T X
-        return "KFAC", lambda layer: tuple(f.t() for f in reversed(self.inv_state[layer])), None
+    def _predictive_terms(self) -> PredictiveTerms:
+        # sample = L_G Z L_A^T: T = L_G^T g, Y = L_A^T X.  Grid:
+        # L L^T = (sqrt(s) F + sqrt(n) I)^-1 = U diag(1 / (sqrt(s) (lambda + sqrt(n / s)))) U^T on both sides: the two
+        # 1 / sqrt(s) make the gain 1 / s, and the shift of both spectra is sqrt(n / s)
+        kept = getattr(self, "_decomposition", None)
+        return PredictiveTerms(
+            "KFAC", basis=lambda layer: tuple(f.t() for f in reversed(self.inv_state[layer])), weights=None,
+            grid_basis=lambda layer: kept[layer][:2], spectrum=lambda layer: (kept[layer][2], kept[layer][3], None),
+            separable=True, grid_missing=None if kept is not None else
+            "no eigendecomposition of the current factors: call decompose() after the last update()")
 
     def decompose(self) -> None:
         """The eigendecompositions F = U diag(lambda) U^T of the accumulated factors of every owned layer, in one batched
@@ -1482,29 +1292,6 @@ class KFAC(Curvature):
             (U_A, U_G), (lam_A, lam_G) = vecs[2 * k:2 * k + 2], vals[2 * k:2 * k + 2]
             self._decomposition[layer] = (U_G.t().contiguous(), U_A.t().contiguous(), ops.clamp_min0_(lam_G),
                                           ops.clamp_min0_(lam_A))
-
-    def functional_variance_grid(self, out: Tensor, hypers, *, first: bool = True, inputs: bool = True) -> Tensor:
-        # L L^T = (sqrt(s) F + sqrt(n) I)^-1 = U diag(1 / (sqrt(s) (lambda + sqrt(n / s)))) U^T on both sides: the two
-        # 1 / sqrt(s) make the gain 1 / s, and the shift of both spectra is sqrt(n / s)
-        hypers, points = self._grid_points("KFAC", hypers, separable=True)
-        kept = getattr(self, "_decomposition", None)
-        if kept is None:
-            raise RuntimeError("KFAC.functional_variance_grid: no eigendecomposition of the current factors: call "
-                               "decompose() after the last update()")
-        return self._functional_variance_grid("KFAC", out, hypers, points, first, inputs, lambda layer: kept[layer][:2],
-                                              lambda layer: (kept[layer][2], kept[layer][3], None))
-
-    def functional_variance(self, out: Tensor, *, first: bool = True, inputs: bool = True) -> Tensor:
-        what, basis, weights = self._predictive_terms()
-        return self._functional_variance(what, out, first, inputs, basis, weights)
-
-    def stage_output(self, slot: int, count: int, *, inputs: bool = False) -> None:
-        what, basis, weights = self._predictive_terms()
-        self._stage_output(what, slot, count, inputs, basis, weights)
-
-    def functional_covariance(self, out: Tensor, *, first: bool = True) -> Tensor:
-        what, basis, weights = self._predictive_terms()
-        return self._functional_covariance(what, out, first, basis, weights)
 
     def sample(self, layer: Module, z: Optional[Tensor] = None) -> Tensor:
         """(L_A z L_G^T)^T -> (m, n) (curvatures.py:387-392); `z` (n, m) may be supplied for parity tests."""
@@ -1667,7 +1454,7 @@ class SampleBank:
         self.count, self.weights, self.biases = count, weights, biases
 
 
-class EFB(Curvature):
+class EFB(LinearisedPredictive, Curvature):
     """Eigenvalue-corrected Kronecker factorisation (curvatures.py:395-460).
 
     ``state[layer]`` = Lambda (m, n) accumulating (U_G^T grad U_A)**2, ``diags[layer]`` the diagonal Fisher
@@ -1839,27 +1626,11 @@ class EFB(Curvature):
             n, s = self._hyper(add, multiply, gindex.get(layer, position), max(len(gindex), len(layers)))
             ops.rsqrt_affine(value, n, s, out=self.inv_state[layer])
 
-    def _predictive_terms(self):
+    def _predictive_terms(self) -> PredictiveTerms:
         # sample = U_G (Z * inv) U_A^T: T = U_G^T g, Y = U_A^T X, as `_update_per_sample`
-        return "EFB", lambda layer: self._eigvecs_t(layer)[::-1], lambda layer: self.inv_state[layer]
-
-    def functional_variance_grid(self, out: Tensor, hypers, *, first: bool = True, inputs: bool = True) -> Tensor:
-        hypers, points = self._grid_points("EFB", hypers, separable=False)
-        return self._functional_variance_grid("EFB", out, hypers, points, first, inputs,
-                                              lambda layer: self._eigvecs_t(layer)[::-1],
-                                              lambda layer: (None, None, self.state[layer]))
-
-    def functional_variance(self, out: Tensor, *, first: bool = True, inputs: bool = True) -> Tensor:
-        what, basis, weights = self._predictive_terms()
-        return self._functional_variance(what, out, first, inputs, basis, weights)
-
-    def stage_output(self, slot: int, count: int, *, inputs: bool = False) -> None:
-        what, basis, weights = self._predictive_terms()
-        self._stage_output(what, slot, count, inputs, basis, weights)
-
-    def functional_covariance(self, out: Tensor, *, first: bool = True) -> Tensor:
-        what, basis, weights = self._predictive_terms()
-        return self._functional_covariance(what, out, first, basis, weights)
+        basis = lambda layer: self._eigvecs_t(layer)[::-1]     # noqa: E731
+        return PredictiveTerms("EFB", basis=basis, weights=lambda layer: self.inv_state[layer], grid_basis=basis,
+                               spectrum=lambda layer: (None, None, self.state[layer]), separable=False)
 
     def sample(self, layer: Module, z: Optional[Tensor] = None) -> Tensor:
         """(U_A (z * inv^T) U_G^T)^T = U_G (z^T * inv) U_A^T -> (m, n) (curvatures.py:453-460)."""

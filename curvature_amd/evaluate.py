@@ -169,13 +169,13 @@ def eval_bnn(model: torch.nn.Module, dataset: Iterable, estimator, samples: int 
 
 
 @contextlib.contextmanager
-def _linearised(what: str, model: torch.nn.Module, estimator, images: torch.Tensor):
+def _linearised(what: str, model: torch.nn.Module, estimator, images: torch.Tensor, outputs=None):
     """What `glm_predictive` and `glm_predictive_joint` do around their reductions: the model goes into ``eval()`` mode, an
     estimator without recording hooks borrows them for the length of the block, one forward pass.  Yields
-    ``(logits, backward)``; ``backward(c)`` back-propagates ``logits[:, c].sum()`` into the records with
-    `torch.autograd.grad` on the parameters that require grad (no ``.grad`` is touched).  On the way out the borrowed hooks
-    are removed and what the estimator kept of this batch (``_variance_inputs``, ``_covariance_outputs``,
-    ``_variance_grid_inputs``) is dropped."""
+    ``(logits, classes, backward)``: `classes` the selected `outputs` (default: all), and ``backward(c)`` back-propagates
+    ``logits[:, c].sum()`` into the records with `torch.autograd.grad` on the parameters that require grad (no ``.grad`` is
+    touched).  On the way out the borrowed hooks are removed and what the estimator kept of this batch is dropped
+    (`drop_predictive_state`)."""
     first_param = next(model.parameters())
     if not first_param.is_cuda or not images.is_cuda:
         raise RuntimeError(f"curvature_amd runs on MI355X only: {what} got a CPU model or batch (no CPU fallback)")
@@ -196,15 +196,14 @@ def _linearised(what: str, model: torch.nn.Module, estimator, images: torch.Tens
             for pair in estimator.record.values():
                 pair[1] = None
             torch.autograd.grad(logits[:, c].sum(), params, retain_graph=True, allow_unused=True)
-        yield logits, backward
+        classes = list(range(logits.shape[1])) if outputs is None else [int(c) for c in outputs]
+        yield logits, classes, backward
     finally:
         if borrowed:
             for hook in estimator.hooks:
                 hook.remove()
             del estimator.hooks, estimator.record
-        estimator.__dict__.pop("_variance_inputs", None)       # the X side of this batch
-        estimator.__dict__.pop("_covariance_outputs", None)    # ... and the stack of its outputs' g sides
-        estimator.__dict__.pop("_variance_grid_inputs", None)  # ... and the X side `functional_variance_grid` kept
+        estimator.drop_predictive_state()                      # the X sides of this batch, the stack of its g sides
 
 
 def _probit(logits: torch.Tensor, variance: torch.Tensor) -> torch.Tensor:
@@ -227,8 +226,7 @@ def glm_predictive(model: torch.nn.Module, estimator, images: torch.Tensor, outp
     ``.grad`` are left as they were found (the backward passes are `torch.autograd.grad` calls on the parameters that
     require grad; a selected layer they do not reach raises RuntimeError).  GPU only (RuntimeError for a CPU model: no fallback).
     `glm_predictive_joint` gives the covariance between the outputs as well."""
-    with _linearised("glm_predictive", model, estimator, images) as (logits, backward):
-        classes = list(range(logits.shape[1])) if outputs is None else [int(c) for c in outputs]
+    with _linearised("glm_predictive", model, estimator, images, outputs) as (logits, classes, backward):
         variance = torch.zeros(logits.shape, dtype=torch.float32, device=logits.device)
         for k, c in enumerate(classes):
             backward(c)
@@ -245,8 +243,7 @@ def glm_predictive_grid(model: torch.nn.Module, estimator, images: torch.Tensor,
     pair (KFAC: after `KFAC.decompose()`); the estimator's `inv_state` is neither needed nor touched.  `outputs`, model
     mode, hooks, parameters and ``.grad`` as in `glm_predictive`.  GPU only."""
     hypers = list(hypers)
-    with _linearised("glm_predictive_grid", model, estimator, images) as (logits, backward):
-        classes = list(range(logits.shape[1])) if outputs is None else [int(c) for c in outputs]
+    with _linearised("glm_predictive_grid", model, estimator, images, outputs) as (logits, classes, backward):
         N, C = logits.shape
         variance = torch.zeros(len(hypers), N, C, dtype=torch.float32, device=logits.device)
         column = torch.empty(len(hypers), N, dtype=torch.float32, device=logits.device)
@@ -288,8 +285,7 @@ def tune_glm(model: torch.nn.Module, dataset: Iterable, estimator, hypers, outpu
 def _joint_covariance(what: str, model: torch.nn.Module, estimator, images: torch.Tensor, outputs):
     """What `glm_predictive_joint` and `glm_predictive_mc` share: ``(logits, covariance, classes)`` from one forward pass,
     one backward pass and one `Curvature.stage_output` per selected output, and one `Curvature.functional_covariance`."""
-    with _linearised(what, model, estimator, images) as (logits, backward):
-        classes = list(range(logits.shape[1])) if outputs is None else [int(c) for c in outputs]
+    with _linearised(what, model, estimator, images, outputs) as (logits, classes, backward):
         K = len(classes)
         if not 1 <= K <= ops.PERSAMPLE_COV_MAX_OUTPUTS or len(set(classes)) != K:
             raise ValueError(f"{what}: {K} outputs ({len(set(classes))} distinct); the joint covariance takes "

@@ -1,0 +1,227 @@
+"""The linearised (GLM) predictive of KFAC, Diagonal and EFB: `functional_variance`, `functional_variance_grid`,
+`stage_output` and `functional_covariance` once, for every estimator that describes itself by a `PredictiveTerms`.
+
+`Curvature` documents the four methods (and refuses them for the estimators that have no linearised predictive);
+`LinearisedPredictive` goes in front of it in the bases of the three that do.  What a call keeps for the next
+``inputs=False`` call lives in one dict on the estimator, ``_predictive_kept``, with at most the entries ``"variance"``,
+``"grid"`` and ``"covariance"``: each reduction replaces its own entry only, `Curvature.drop_predictive_state` drops them all.
+"""
+import math
+from typing import Callable, List, NamedTuple, Optional
+
+import torch
+from torch import Tensor
+
+from . import ops
+
+
+class PredictiveTerms(NamedTuple):
+    """What an estimator says about itself.  `name` goes into the messages.  ``basis(layer)`` = (R_G, R_A), the rotations
+    T = R_G g and Y = R_A X of the packed (rows, N Lp) operands, or `basis` None (no rotation: the operands are read where
+    they are); ``weights(layer)`` = the (m, n) tensor whose square weighs the entries, or `weights` None (all ones).  The
+    grid has a basis of its own and ``spectrum(layer)`` = (u, v, None) - the eigenvalues of the G and the A side:
+    `separable` weights - or (None, None, V): dense ones; `grid_missing`: why the grid cannot run yet, if it cannot."""
+    name: str
+    basis: Optional[Callable]
+    weights: Optional[Callable]
+    grid_basis: Optional[Callable]
+    spectrum: Callable
+    separable: bool
+    grid_missing: Optional[str] = None
+
+
+class LinearisedPredictive:
+    """The four reductions of `Curvature`'s linearised predictive (documented there) for an estimator whose
+    ``_predictive_terms()`` gives its `PredictiveTerms`, with `Curvature`'s recording hooks and `state` / `inv_state`."""
+
+    def _kept(self) -> dict:
+        return self.__dict__.setdefault("_predictive_kept", {})
+
+    # ------------------------------------------------------------------ the shared steps
+    def _predictive_operands(self, what: str, call: str, inputs: bool, rotated: bool, check=None,
+                             select: str = "inv_state"):
+        """What every reduction starts from: the checks, the selected layers that have an inverse state (`select`: the
+        dict that says so - the grid needs `state` only), their per-sample operands from the current records (the g side
+        only unless `inputs`; packed for a rotation if `rotated`), and the key that ties a kept X side to the recorded
+        inputs themselves (tensor and version), not just to their shapes.  ``check(operands)`` runs last (the caller's
+        test of its own arguments against the batch).  Returns (layers, operands, key)."""
+        have = getattr(self, select)
+        assert have, ("Inverse state dict is empty. Did you call 'invert' prior to this?" if select == "inv_state" else
+                      "State dict is empty. Did you call 'update' prior to this?")
+        if self.shard is not None and self.shard.world > 1:
+            raise NotImplementedError(f"{what}.{call}: layer-sharded estimators are not supported")
+        if getattr(self, "record", None) is None:
+            raise RuntimeError(f"{what}.{call}: no recording hooks (construct with per_sample=True, or go "
+                               "through evaluate.glm_predictive)")
+        layers = self._per_sample_layers(f"{what}.{call}", "select other layer types")
+        layers = [l for l in layers if l in have]
+        assert layers, f"{select} holds none of the selected layers"
+        layout = dict(rows_outer=True, in_place=False) if rotated else {}
+        operands = self._per_sample_operands(what, layers, x_side=inputs, **layout)
+        if check is not None:
+            check(operands)
+        key = tuple((l, id(self.record[l][0]), self.record[l][0]._version, s.n, s.N, s.L, s.x.ns, s.x.rs)
+                    for l, (s, _, _) in zip(layers, operands))
+        return layers, operands, key
+
+    def _x_side(self, entry: str, layers, operands, basis, weights):
+        """What depends on the forward pass and the posterior only: X (rotated) and the squared weights.  Entry `entry` of
+        the kept state is dropped first: the X side of other records goes before the new one is made."""
+        self._kept().pop(entry, None)
+        xs = [x for _, _, x in operands] if basis is None else \
+            self._rotated([(basis(l)[1], x, s.n) for l, (s, _, x) in zip(layers, operands)])
+        return xs, [None if weights is None else ops.mul(weights(l), weights(l)) for l in layers]
+
+    def _kept_entry(self, what: str, call: str, entry: str, key, count: Optional[int] = None) -> dict:
+        """Entry `entry` of the kept state, if a call with ``inputs=True`` made it on these very recorded inputs (and for
+        `count` outputs); RuntimeError otherwise."""
+        kept = self._kept().get(entry)
+        if kept is None or kept["key"] != key or (count is not None and kept["count"] != count):
+            outputs = "" if count is None else f" and {count} outputs"
+            raise RuntimeError(f"{what}.{call}(inputs=False): no call with inputs=True on these recorded inputs{outputs} "
+                               "before (a new forward pass needs inputs=True once)")
+        return kept
+
+    def _g_side(self, layers, operands, basis, out: List[Tensor] = None) -> List[Tensor]:
+        """The g side of every layer, rotated by the G half of `basis` (into `out`, or fresh buffers) if there is one."""
+        if basis is None:
+            return [g for _, g, _ in operands]
+        return self._rotated([(basis(l)[0], g, s.m) for l, (s, g, _) in zip(layers, operands)], out)
+
+    @staticmethod
+    def _sum_layers(rows: Tensor, out: Tensor, first: bool) -> None:
+        """``out (+)= sum_k rows[k]``, `out` a (1, row size) view: the per-layer rows summed in layer order by one product
+        with a row of ones, so that the result does not depend on how the layers are grouped into launches."""
+        ones = torch.ones(1, rows.shape[0], dtype=torch.float32, device=rows.device)
+        ops.gemm_batched([ops.Gemm(ones, rows.view(rows.shape[0], -1), out, beta=0.0 if first else 1.0)])
+
+    # ------------------------------------------------------------------ the variance of one output
+    def functional_variance(self, out: Tensor, *, first: bool = True, inputs: bool = True) -> Tensor:
+        """`Curvature.functional_variance`."""
+        what, basis, weights, *_ = self._predictive_terms()
+
+        def check(operands):
+            N = operands[0][0].N
+            if out.dim() != 1 or out.shape[0] != N or out.dtype != torch.float32 or not out.is_cuda:
+                raise RuntimeError(f"{what}.functional_variance: out must be a float32 GPU view of length {N}, got "
+                                   f"{tuple(out.shape)} {out.dtype} on {out.device}")
+        layers, operands, key = self._predictive_operands(what, "functional_variance", inputs, basis is not None, check)
+        if inputs:
+            xs, ws = self._x_side("variance", layers, operands, basis, weights)
+            self._kept()["variance"] = dict(key=key, xs=xs, ws=ws)
+        kept = self._kept_entry(what, "functional_variance", "variance", key)
+        gs = self._g_side(layers, operands, basis)
+        rows = torch.empty(len(layers), operands[0][0].N, dtype=torch.float32, device=operands[0][1].device)
+        ops.per_sample_quad_reduce([ops.PerSampleQuadJob.of(s, g, x, w, rows[k], first=True)
+                                    for k, ((s, _, _), g, x, w) in enumerate(zip(operands, gs, kept["xs"], kept["ws"]))])
+        self._sum_layers(rows, out.unsqueeze(0), first)
+        return out
+
+    # ------------------------------------------------------------------ the variance over a grid of damping pairs
+    def _grid_points(self, what: str, hypers, separable: bool):
+        """`hypers` checked and resolved: for every selected layer index the lists ``shift[h]`` (rho, or sqrt(rho) for the
+        separable weights) and ``gain[h]`` = 1 / multiply, as a function ``(layer) -> (shifts, gains)``."""
+        hypers = list(hypers)
+        if not hypers:
+            raise ValueError(f"{what}.functional_variance_grid: no damping pairs")
+        for h, pair in enumerate(hypers):
+            if not isinstance(pair, (tuple, list)) or len(pair) != 2:
+                raise ValueError(f"{what}.functional_variance_grid: pair {h} is not an (add, multiply) pair: {pair!r}")
+            for value in pair:
+                values = [value] if self._is_scalar(value) else list(value)
+                if not values or not all(math.isfinite(float(x)) and float(x) > 0 for x in values):
+                    raise ValueError(f"{what}.functional_variance_grid: pair {h} {tuple(pair)!r}: add and multiply must "
+                                     "be finite and > 0")
+        gindex = self._global_index()
+
+        def points(layer):
+            resolved = [self._hyper(add, multiply, gindex[layer], len(gindex)) for add, multiply in hypers]
+            rhos = [n / s for n, s in resolved]
+            return [math.sqrt(r) for r in rhos] if separable else rhos, [1.0 / s for _, s in resolved]
+        return hypers, points
+
+    def functional_variance_grid(self, out: Tensor, hypers, *, first: bool = True, inputs: bool = True) -> Tensor:
+        """`Curvature.functional_variance_grid`."""
+        terms = self._predictive_terms()
+        what, basis, spectrum = terms.name, terms.grid_basis, terms.spectrum
+        hypers, points = self._grid_points(what, hypers, terms.separable)
+        if terms.grid_missing is not None:
+            raise RuntimeError(f"{what}.functional_variance_grid: {terms.grid_missing}")
+
+        def check(operands):
+            N = operands[0][0].N
+            if tuple(out.shape) != (len(hypers), N) or out.dtype != torch.float32 or not out.is_cuda or \
+                    not out.is_contiguous():
+                raise RuntimeError(f"{what}.functional_variance_grid: out must be a contiguous float32 GPU tensor of shape "
+                                   f"({len(hypers)}, {N}), got {tuple(out.shape)} {out.dtype} on {out.device}")
+        layers, operands, key = self._predictive_operands(what, "functional_variance_grid", inputs, basis is not None,
+                                                          check, select="state")
+        if inputs:
+            xs, _ = self._x_side("grid", layers, operands, basis, None)
+            self._kept()["grid"] = dict(key=key, xs=xs)
+        xs = self._kept_entry(what, "functional_variance_grid", "grid", key)["xs"]
+        gs = self._g_side(layers, operands, basis)
+        tables = [points(l) for l in layers]
+        N, dev = operands[0][0].N, operands[0][1].device
+        # chunks of PERSAMPLE_GRID_MAX pairs over the same operands; every layer into its own (pairs, N) block
+        for h0 in range(0, len(hypers), ops.PERSAMPLE_GRID_MAX):
+            h1 = min(h0 + ops.PERSAMPLE_GRID_MAX, len(hypers))
+            rows = torch.empty(len(layers), h1 - h0, N, dtype=torch.float32, device=dev)
+            ops.per_sample_quad_grid_reduce([
+                ops.PerSampleGridJob.of(s, g, x, *spectrum(l), rows[k], shifts[h0:h1], gains[h0:h1], first=True)
+                for k, (l, (s, _, _), g, x, (shifts, gains)) in enumerate(zip(layers, operands, gs, xs, tables))])
+            self._sum_layers(rows, out[h0:h1].view(1, -1), first)
+        return out
+
+    # ------------------------------------------------------------------ joint covariance of the outputs
+    def stage_output(self, slot: int, count: int, *, inputs: bool = False) -> None:
+        """`Curvature.stage_output`."""
+        what, basis, weights, *_ = self._predictive_terms()
+        slot, count = int(slot), int(count)
+        if not 1 <= count <= ops.PERSAMPLE_COV_MAX_OUTPUTS or not 0 <= slot < count:
+            raise ValueError(f"{what}.stage_output: slot {slot} of {count} (at most {ops.PERSAMPLE_COV_MAX_OUTPUTS} outputs)")
+        layers, operands, key = self._predictive_operands(what, "stage_output", inputs, basis is not None)
+        if inputs:
+            xs, ws = self._x_side("covariance", layers, operands, basis, weights)
+            # a slot is what one output's g side takes: its packed copy, or the record itself where that is read in place
+            sizes = [s.g.floats or s.N * s.g.ns for s, _, _ in operands]
+            stack = ops.per_sample_scratch([count * f for f in sizes], operands[0][1].device, "persample_cov_g")
+            self._kept()["covariance"] = dict(key=key, count=count, xs=xs, ws=ws, sizes=sizes, stack=stack,
+                                              sides=[s for s, _, _ in operands], staged=set(),
+                                              inputs=[self.record[l][0] for l in layers])
+        kept = self._kept_entry(what, "stage_output", "covariance", key, count)
+        slots = [t[slot * f:(slot + 1) * f] for t, f in zip(kept["stack"], kept["sizes"])]
+        if basis is not None:
+            self._g_side(layers, operands, basis, slots)
+        else:
+            ops.CopyPlan(slots, [g.reshape(-1)[:f] for (_, g, _), f in zip(operands, kept["sizes"])]).run()
+        kept["staged"].add(slot)
+
+    def functional_covariance(self, out: Tensor, *, first: bool = True) -> Tensor:
+        """`Curvature.functional_covariance` (basis and weights went into the staged operands)."""
+        what = self._predictive_terms().name
+        kept = self._kept().get("covariance")
+        if kept is None:
+            raise RuntimeError(f"{what}.functional_covariance: no output staged (stage_output(inputs=True) first)")
+        record = getattr(self, "record", None) or {}
+        for (layer, _, version, *_), x in zip(kept["key"], kept["inputs"]):
+            now = record.get(layer, (None, None))[0]
+            if now is not x or now._version != version:
+                raise RuntimeError(f"{what}.functional_covariance: the recorded inputs are no longer those of "
+                                   "stage_output(inputs=True) (a new forward pass needs its outputs staged again)")
+        count, missing = kept["count"], sorted(set(range(kept["count"])) - kept["staged"])
+        if missing:
+            raise RuntimeError(f"{what}.functional_covariance: output slots {missing} of {count} have not been staged since "
+                               "the last stage_output(inputs=True)")
+        sides = kept["sides"]
+        N, dev = sides[0].N, kept["stack"][0].device
+        if tuple(out.shape) != (N, count, count) or out.dtype != torch.float32 or not out.is_cuda or not out.is_contiguous():
+            raise RuntimeError(f"{what}.functional_covariance: out must be a contiguous float32 GPU tensor of shape "
+                               f"({N}, {count}, {count}), got {tuple(out.shape)} {out.dtype} on {out.device}")
+        # every layer into its own (N, count, count) row
+        rows = torch.empty(len(sides), N, count, count, dtype=torch.float32, device=dev)
+        ops.per_sample_cov_reduce([ops.PerSampleCovJob.of(s, g, x, w, rows[k], count, f, first=True)
+                                   for k, (s, g, x, w, f) in enumerate(zip(sides, kept["stack"], kept["xs"], kept["ws"],
+                                                                           kept["sizes"]))])
+        self._sum_layers(rows, out.view(1, -1), first)
+        return out

@@ -301,7 +301,7 @@ def test_lenet_against_float64(gpu, kind):
     for p, (value, grad, grad_value) in zip(model.parameters(), before):
         assert torch.equal(p.detach(), value) and p.grad is grad and torch.equal(p.grad, grad_value)
     assert hasattr(est, "hooks") == hooked                                     # borrowed hooks are gone again
-    assert not hasattr(est, "_covariance_outputs") and not hasattr(est, "_variance_inputs")
+    assert not getattr(est, "_predictive_kept", None)
     assert not model.training
     _, variance_after, probs_after = glm_predictive(model, est, x)             # the variance path is what it was
     assert torch.equal(variance_after, variance) and torch.equal(probs_after, probs_before)
@@ -394,4 +394,4 @@ def test_unstaged_slots_and_stale_inputs_are_refused(gpu):
         with pytest.raises(RuntimeError, match="recorded inputs"):
             est.functional_covariance(out)
     finally:
-        est.__dict__.pop("_covariance_outputs", None)
+        est.drop_predictive_state()

@@ -330,7 +330,7 @@ def test_lenet_grid_against_float64_and_against_invert(gpu, kind):
     for p, (value, grad, grad_value) in zip(model.parameters(), before):
         assert torch.equal(p.detach(), value) and p.grad is grad and torch.equal(p.grad, grad_value)
     assert hasattr(est, "hooks") == hooked                                     # borrowed hooks are gone again
-    assert not hasattr(est, "_variance_grid_inputs")                           # ... and so is the kept X side
+    assert not getattr(est, "_predictive_kept", None)                          # ... and so is the kept X side
     assert not model.training
 
     worst = 0.0
@@ -414,7 +414,7 @@ def test_input_side_reuse(gpu, kind):
         with pytest.raises(RuntimeError, match="shape"):
             est.functional_variance_grid(torch.empty(len(HYPERS) + 1, N_LENET, device=gpu), HYPERS)
     finally:
-        est.__dict__.pop("_variance_grid_inputs", None)
+        est.drop_predictive_state()
         if borrowed:
             for hook in est.hooks:
                 hook.remove()

@@ -347,7 +347,7 @@ def test_glm_predictive_mc(gpu, kind):
 
     # left as glm_predictive_joint leaves it
     assert hasattr(est, "hooks") == had_hooks
-    assert "_variance_inputs" not in est.__dict__ and "_covariance_outputs" not in est.__dict__
+    assert not est.__dict__.get("_predictive_kept")
     for p, before, grad in zip(model.parameters(), params, grads):
         assert torch.equal(p.detach(), before)
         assert (p.grad is None) == (grad is None) and (grad is None or torch.equal(p.grad, grad))

@@ -107,7 +107,8 @@ def plan_of(est, model, x, classes, params):
     logits = model(x)
     torch.autograd.grad(logits[:, classes[0]].sum(), params)
     est.stage_output(0, len(classes), inputs=True)
-    kept = est.__dict__.pop("_covariance_outputs")
+    kept = est._predictive_kept["covariance"]
+    est.drop_predictive_state()
     jobs = [ops.PerSampleCovJob.of(s, None, None, None, None, len(classes), f) for s, f in zip(kept["sides"], kept["sizes"])]
     return sum(ops.per_sample_cov_plan_flops(jobs)), sum(2 * j.S * j.K * j.M * j.Nc * j.L for j in jobs)
 

@@ -63,22 +63,19 @@ def kernel_jobs(kind, est, model, x, c, params):
     tensors alive)."""
     logits = model(x)
     torch.autograd.grad(logits[:, c].sum(), params)
-    basis = (lambda l: est._decomposition[l][:2]) if kind == "kfac" else None
-    layers, operands, _, (xs, _) = est._predictive_operands(kind, "bench", True, basis, None, "_variance_grid_inputs",
-                                                            select="state")
-    gs = [g for _, g, _ in operands]
-    if basis is not None:
-        gs = est._rotated([(basis(l)[0], g, s.m) for l, (s, g, _) in zip(layers, operands)])
+    terms = est._predictive_terms()
+    basis = terms.grid_basis
+    layers, operands, _ = est._predictive_operands(kind, "bench", True, basis is not None, select="state")
+    xs, _ = est._x_side("grid", layers, operands, basis, None)
+    gs = est._g_side(layers, operands, basis)
     N, dev = operands[0][0].N, gs[0].device
     shifts, gains = [0.03 * 1.5 ** h for h in range(16)], [1.0 / (1 + h) for h in range(16)]
     grid_rows = torch.empty(len(layers), 16, N, device=dev)
     quad_rows = torch.empty(len(layers), N, device=dev)
     grid, quad, keep = [], [], [gs, xs, grid_rows, quad_rows]
     for k, (l, (s, _, _), g, xk) in enumerate(zip(layers, operands, gs, xs)):
-        if kind == "kfac":
-            weights, W = (est._decomposition[l][2], est._decomposition[l][3], None), None
-        else:
-            weights, W = (None, None, est.state[l]), 1.0 / (est.state[l] + shifts[0])
+        weights = terms.spectrum(l)
+        W = None if terms.separable else 1.0 / (est.state[l] + shifts[0])
         keep.append(W)
         grid.append(ops.PerSampleGridJob.of(s, g, xk, *weights, grid_rows[k], shifts, gains, first=True))
         quad.append(ops.PerSampleQuadJob.of(s, g, xk, W, quad_rows[k], first=True))
@@ -104,7 +101,7 @@ def run(name, model, x, labels, outputs, reps):
         rows.append(row)
         print(json.dumps(row), flush=True)
         del grid, quad, keep
-        est.__dict__.pop("_variance_grid_inputs", None)
+        est.drop_predictive_state()
 
         # (b) a validation batch, 16 pairs
         def loop():

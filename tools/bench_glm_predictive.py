@@ -48,12 +48,15 @@ def timed(fn, reps):
 
 
 def estimators(model, x, labels):
-    """KFAC and Diagonal of `model` after one update on (x, labels) and an inversion."""
+    """KFAC and Diagonal of `model` after one update on (x, labels), in train() mode (see bench_glm_covariance.py), and
+    an inversion."""
     kfac, diag = KFAC(model), Diagonal(model, per_sample=True)
+    model.train()
     model.zero_grad()
     F.cross_entropy(model(x), labels).backward()
     kfac.update(x.shape[0])
     diag.update(x.shape[0])
+    model.eval()
     kfac.invert(add=1.0, multiply=1000.0)
     diag.invert(add=1.0, multiply=1000.0)
     return {"kfac": kfac, "diagonal": diag}
@@ -135,7 +138,7 @@ def run_resnet(N, reps, dev):
         row["first_output_ms"] = timed(lambda: est.functional_variance(out, inputs=True), reps)
         row["next_output_ms"] = timed(lambda: est.functional_variance(out, inputs=False), reps)
         mine = out.clone()
-        del est._variance_inputs
+        est.drop_predictive_state()
         jobs = quad_jobs(kind, est, layers, torch.empty(len(layers), N, device=dev))
         algo = sum(2 * j.S * j.M * j.Nc * j.L for j in jobs)
         executed = sum(ops.per_sample_quad_plan_flops(jobs))
