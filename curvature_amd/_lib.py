@@ -217,6 +217,12 @@ class curv_persample_pack_desc(ctypes.Structure):
                [(k, ctypes.c_int32) for k in ("has_bias", "channels_last", "rows_outer", "Lp")]
 
 
+class curv_persample_pack_ex_desc(ctypes.Structure):
+    """Mirror of ``curv_persample_pack_ex_desc`` in include/curv_hip.h."""
+    _fields_ = _ENDS + [(k, ctypes.c_longlong) for k in ("s_n", "s_c", "s_h", "s_w", "src_elems")] + _SOURCE + _WINDOW + \
+               [(k, ctypes.c_int32) for k in ("Ho", "Wo", "has_bias", "dtype", "transposed", "rows_outer", "Lp", "reserved")]
+
+
 class curv_copy_desc(ctypes.Structure):
     _fields_ = [("dst", ctypes.c_void_p), ("src", ctypes.c_void_p), ("bytes", ctypes.c_ulonglong)]
 
@@ -298,6 +304,7 @@ SIGNATURES = {
     "curv_persample_plan_flops": (_i, [ctypes.POINTER(curv_persample_desc), _i, ctypes.POINTER(ctypes.c_longlong)]),
     "curv_persample_sq_accumulate": (_i, [_vp, ctypes.POINTER(curv_persample_desc), _i, _vp, _sz]),
     "curv_persample_pack": (_i, [_vp, ctypes.POINTER(curv_persample_pack_desc), _i]),
+    "curv_persample_pack_ex": (_i, [_vp, ctypes.POINTER(curv_persample_pack_ex_desc), _i]),
     "curv_persample_quad_workspace_bytes": (_sz, [ctypes.POINTER(curv_persample_quad_desc), _i]),
     "curv_persample_quad_plan_flops": (_i, [ctypes.POINTER(curv_persample_quad_desc), _i, ctypes.POINTER(ctypes.c_longlong)]),
     "curv_persample_quad_reduce": (_i, [_vp, ctypes.POINTER(curv_persample_quad_desc), _i, _vp, _sz]),
@@ -318,7 +325,7 @@ SIGNATURES = {
 
 
 ABI_VERSION = 12                     # CURV_ABI_VERSION of include/curv_hip.h
-DTYPE_BF16, DTYPE_F16 = 1, 2         # CURV_DTYPE_* (curv_factor16_desc.dtype)
+DTYPE_F32, DTYPE_BF16, DTYPE_F16 = 0, 1, 2     # CURV_DTYPE_* (curv_factor16_desc.dtype; curv_persample_pack_ex_desc.dtype)
 KFAC_TABLE_RESIDENT = 1             # CURV_KFAC_TABLE_RESIDENT
 PATH_AUTO, PATH_SMALL, PATH_GROUPED = 0, 1, 2     # CURV_PATH_* (curv_factor_desc.path_hint)
 SMALL_MAX_FLOP = 2.0e9              # CURV_SMALL_MAX_FLOP

@@ -848,6 +848,194 @@ __global__ void __launch_bounds__(PS_THREADS) ps_pack_kernel(const PsPackBatch b
   *reinterpret_cast<float4*>(F.dst + out) = make_float4(v[0], v[1], v[2], v[3]);
 }
 
+// ------------------------------------------------------------------------------------------------ general pack
+// curv_persample_pack_ex: the same destination from a source of fp32, bf16 or fp16 values addressed through element
+// strides, and the transposed gather of a ConvTranspose2d input.  ps_pack_kernel above stays as it is (what it packs
+// keeps its bits and its time); this kernel takes what it cannot express.
+struct PsPackEx {
+  const void* src;
+  float* dst;
+  unsigned s_n, s_c, s_h, s_w;  // source strides in elements (the whole source holds fewer than 2^31 bytes: pack_ex_plan_of)
+  int N, C, H, W, kh, kw, sh, sw, ph, pw, Ho, Wo;
+  int rows, R, L, Lp;
+  int has_bias, transposed, rows_outer;
+  int vec;                      // rows are plain runs of the source, every group of four aligned: one vector load each
+  long long base;               // first thread of this item in the launch
+};
+
+typedef ArgBatch<PsPackEx, PS_BATCH> PsPackExBatch;
+static_assert(sizeof(PsPackExBatch) <= 3840, "kernel argument block must stay below 4 KB");
+
+int pack_ex_elem_bytes(int dtype) {
+  return dtype == CURV_DTYPE_F32 ? 4 : (dtype == CURV_DTYPE_BF16 || dtype == CURV_DTYPE_F16) ? 2 : 0;
+}
+
+bool pack_ex_plan_of(const curv_persample_pack_ex_desc& d, int index, PsPackEx* out) {
+  const char* const who = "curv_persample_pack_ex";
+  const int esize = pack_ex_elem_bytes(d.dtype);
+  if (esize == 0) {
+    set_error("%s: item %d: unknown dtype %d (CURV_DTYPE_F32, CURV_DTYPE_BF16 or CURV_DTYPE_F16)", who, index, d.dtype);
+    return false;
+  }
+  if (!d.src || !d.dst) {
+    set_error("%s: item %d: null src or dst", who, index);
+    return false;
+  }
+  if (reinterpret_cast<uintptr_t>(d.dst) & 15) {
+    set_error("%s: item %d: dst is not 16-byte aligned", who, index);
+    return false;
+  }
+  if (reinterpret_cast<uintptr_t>(d.src) % (uintptr_t)esize) {
+    set_error("%s: item %d: src is not aligned to its %d-byte elements", who, index, esize);
+    return false;
+  }
+  side::ConvGeom g;
+  if (d.transposed) {
+    if (!side::source_geom_of(d, who, "item", index, &g)) return false;
+    // the sizes `output_size` allows: output_padding in [0, stride)
+    const long long lo_h = (long long)(d.H - 1) * d.sh - 2LL * d.ph + d.kh, lo_w = (long long)(d.W - 1) * d.sw - 2LL * d.pw + d.kw;
+    if (d.Ho < 1 || d.Wo < 1 || d.Ho < lo_h || d.Ho > lo_h + d.sh - 1 || d.Wo < lo_w || d.Wo > lo_w + d.sw - 1) {
+      set_error("%s: item %d: transposed output %dx%d outside [%lld, %lld] x [%lld, %lld] (H %d W %d kernel %dx%d stride "
+                "%dx%d padding %dx%d)", who, index, d.Ho, d.Wo, lo_h, lo_h + d.sh - 1, lo_w, lo_w + d.sw - 1, d.H, d.W,
+                d.kh, d.kw, d.sh, d.sw, d.ph, d.pw);
+      return false;
+    }
+    g.Ho = d.Ho; g.Wo = d.Wo;
+  } else if (!side::conv_geom_of(d, who, "item", index, &g)) {
+    return false;
+  }
+  PsPackEx P;
+  P.src = d.src; P.dst = d.dst;
+  P.N = g.N; P.C = g.C; P.H = g.H; P.W = g.W;
+  P.kh = g.kh; P.kw = g.kw; P.sh = g.sh; P.sw = g.sw; P.ph = g.ph; P.pw = g.pw; P.Ho = g.Ho; P.Wo = g.Wo;
+  const long long rows = (long long)d.C * d.kh * d.kw, L = (long long)P.Ho * P.Wo;
+  if (rows > (1 << 24) || L > (1 << 24) || (long long)d.N * (rows + 1) * (d.Lp / 4 + 1) >= (1LL << 31)) {
+    set_error("%s: item %d: too large (%lld rows, %lld positions)", who, index, rows, L);
+    return false;
+  }
+  if (d.Lp < L || (d.Lp & 3)) {
+    set_error("%s: item %d: Lp %d must be a multiple of 4 and at least L = %lld", who, index, d.Lp, L);
+    return false;
+  }
+  if (d.s_n < 0 || d.s_c < 0 || d.s_h < 0 || d.s_w < 0 || d.src_elems < 1 ||
+      d.src_elems * esize >= PS_BYTES_MAX) {
+    set_error("%s: item %d: negative stride, or source extent %lld elements outside [1, 2^31 bytes)", who, index,
+              d.src_elems);
+    return false;
+  }
+  // the largest addressed offset, dimension by dimension (a stride at or beyond the extent is refused before it is multiplied)
+  const long long limit = d.src_elems;
+  long long last = 0;
+  const long long dims[4] = {d.N, d.C, d.H, d.W}, strides[4] = {d.s_n, d.s_c, d.s_h, d.s_w};
+  for (int k = 0; k < 4; ++k) {
+    if (dims[k] > 1 && strides[k] >= limit) last = limit;
+    else last += (dims[k] - 1) * strides[k];
+    if (last >= limit) {
+      set_error("%s: item %d: the source extent (%lld elements) is smaller than the largest offset its sizes and strides "
+                "address (N %d C %d H %d W %d, strides %lld %lld %lld %lld)", who, index, limit, d.N, d.C, d.H, d.W, d.s_n,
+                d.s_c, d.s_h, d.s_w);
+      return false;
+    }
+  }
+  P.s_n = (unsigned)(d.N > 1 ? d.s_n : 0); P.s_c = (unsigned)(d.C > 1 ? d.s_c : 0);
+  P.s_h = (unsigned)(d.H > 1 ? d.s_h : 0); P.s_w = (unsigned)(d.W > 1 ? d.s_w : 0);
+  P.rows = (int)rows;
+  P.has_bias = d.has_bias ? 1 : 0;
+  P.R = P.rows + P.has_bias;
+  P.L = (int)L;
+  P.Lp = d.Lp;
+  P.transposed = d.transposed ? 1 : 0;
+  P.rows_outer = d.rows_outer ? 1 : 0;
+  // the vector path: a row is the run of H W source values behind (n, c), and every group of four of it starts on a
+  // 4-element boundary - decided here, per item, from the pointer and the strides, so that the kernel's branch is uniform
+  const bool plain = !P.transposed && d.kh == 1 && d.kw == 1 && d.sh == 1 && d.sw == 1 && d.ph == 0 && d.pw == 0;
+  const bool run = (d.W == 1 || d.s_w == 1) && (d.H == 1 || d.s_h == d.W);
+  const bool aligned = (reinterpret_cast<uintptr_t>(d.src) % (4 * (uintptr_t)esize)) == 0 && (d.N == 1 || d.s_n % 4 == 0) &&
+                       (d.C == 1 || d.s_c % 4 == 0);
+  P.vec = plain && run && aligned;
+  P.base = 0;
+  *out = P;
+  return true;
+}
+
+// The source types: a bf16 value is its bit pattern (the upper half of the fp32 one), fp16 converts exactly.
+struct ps_bf16 { unsigned short bits; };
+__device__ __forceinline__ float ps_up(float x) { return x; }
+__device__ __forceinline__ float ps_up(ps_bf16 x) { return __uint_as_float((unsigned)x.bits << 16); }
+__device__ __forceinline__ float ps_up(_Float16 x) { return (float)x; }
+template <typename T>
+struct alignas(4 * sizeof(T)) PsQuad4 { T v[4]; };
+
+// One thread per 4 consecutive columns of one row of one sample (one 16-byte store), as ps_pack_kernel; a masked or
+// padded element reads src[0] and drops it.  32-bit index arithmetic for the same reason as there.
+template <typename T>
+__global__ void __launch_bounds__(PS_THREADS) ps_pack_ex_kernel(const PsPackExBatch batch) {
+  const long long t = (long long)blockIdx.x * PS_THREADS + threadIdx.x;
+  const PsPackEx& F = batch.e[owner_of(batch, t)];
+  const unsigned gpr = F.Lp / 4, R = F.R;
+  if (t - F.base >= (long long)F.N * R * gpr) return;
+  const unsigned local = (unsigned)(t - F.base);
+  const unsigned row = local / gpr;                        // n R + r
+  const int k0 = (int)(local - row * gpr) * 4;
+  const unsigned n = row / R;
+  const int r = (int)(row - n * R);
+  const T* src = reinterpret_cast<const T*>(F.src);
+  float v[4];
+  if (r >= F.rows) {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) v[e] = k0 + e < F.L ? 1.0f : 0.0f;      // the ones row of a biased layer
+  } else if (F.vec && k0 + 4 <= F.L) {                                    // (1 x 1: r is the channel)
+    const PsQuad4<T> q = *reinterpret_cast<const PsQuad4<T>*>(src + (n * F.s_n + (unsigned)r * F.s_c + (unsigned)k0));
+#pragma unroll
+    for (int e = 0; e < 4; ++e) v[e] = ps_up(q.v[e]);
+  } else {
+    const unsigned khw = F.kh * F.kw;
+    const int c = (int)((unsigned)r / khw), q = r - c * (int)khw;
+    const int a = (int)((unsigned)q / (unsigned)F.kw), b = q - a * F.kw;
+    int oh = (int)((unsigned)k0 / (unsigned)F.Wo), ow = k0 - oh * F.Wo;
+    const unsigned plane = n * F.s_n + (unsigned)c * F.s_c;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      bool ok = k0 + e < F.L;
+      unsigned ih, iw;
+      if (F.transposed) {
+        // x[n, c, (oh + ph - a) / sh, (ow + pw - b) / sw] where both are whole and inside; no division of a negative
+        const int th = oh + F.ph - a, tw = ow + F.pw - b;
+        ok = ok && th >= 0 && tw >= 0;
+        const unsigned uh = ok ? (unsigned)th : 0u, uw = ok ? (unsigned)tw : 0u;
+        ih = uh / (unsigned)F.sh;
+        iw = uw / (unsigned)F.sw;
+        ok = ok && ih * (unsigned)F.sh == uh && iw * (unsigned)F.sw == uw;
+      } else {
+        ih = (unsigned)(oh * F.sh - F.ph + a);
+        iw = (unsigned)(ow * F.sw - F.pw + b);
+      }
+      ok = ok && ih < (unsigned)F.H && iw < (unsigned)F.W;
+      const float x = ps_up(src[ok ? plane + ih * F.s_h + iw * F.s_w : 0u]);  // a masked gather reads src[0]
+      v[e] = ok ? x : 0.0f;
+      if (++ow == F.Wo) { ow = 0; ++oh; }
+    }
+  }
+  const long long out = F.rows_outer ? ((long long)r * F.N + n) * F.Lp + k0 : (long long)row * F.Lp + k0;
+  *reinterpret_cast<float4*>(F.dst + out) = make_float4(v[0], v[1], v[2], v[3]);
+}
+
+template <typename T>
+int launch_pack_ex(hipStream_t stream, const std::vector<PsPackEx>& packs, const char* name) {
+  return for_arg_batches<PsPackEx, PS_BATCH, 1>(
+      (int)packs.size(), name,
+      [&](int i, PsPackEx* P, long long* threads) {
+        *P = packs[i];
+        threads[0] = (long long)P->N * P->R * (P->Lp / 4);
+      },
+      [](int, long long threads) { return cdivll(threads, PS_THREADS); },
+      [&](const PsPackExBatch* b, const long long*, const unsigned* grid) {
+        hipLaunchKernelGGL(ps_pack_ex_kernel<T>, dim3(grid[0]), dim3(PS_THREADS), 0, stream, b[0]);
+        CURV_LAUNCH_CHECK();
+        return CURV_OK;
+      });
+}
+
 size_t bytes_of(const std::vector<Plan>& plans) {
   size_t total = 0;
   for (const Plan& p : plans) total += p.slab_bytes;
@@ -1072,4 +1260,22 @@ extern "C" int curv_persample_pack(void* stream_, const curv_persample_pack_desc
         CURV_LAUNCH_CHECK();
         return CURV_OK;
       });
+}
+
+extern "C" int curv_persample_pack_ex(void* stream_, const curv_persample_pack_ex_desc* descs, int n) {
+  const char* const name = "curv_persample_pack_ex";
+  if (n <= 0) return CURV_OK;
+  CURV_REQUIRE(descs != nullptr, "%s: null descriptors", name);
+  hipStream_t stream = (hipStream_t)stream_;
+  // every item is planned before anything is launched; the items of one source type share their launches, in call order
+  std::vector<PsPackEx> packs[3];
+  for (int i = 0; i < n; ++i) {
+    PsPackEx P;
+    if (!pack_ex_plan_of(descs[i], i, &P)) return CURV_ERR_INVALID;
+    packs[descs[i].dtype].push_back(P);
+  }
+  int rc = launch_pack_ex<float>(stream, packs[CURV_DTYPE_F32], name);
+  if (rc == CURV_OK) rc = launch_pack_ex<ps_bf16>(stream, packs[CURV_DTYPE_BF16], name);
+  if (rc == CURV_OK) rc = launch_pack_ex<_Float16>(stream, packs[CURV_DTYPE_F16], name);
+  return rc;
 }

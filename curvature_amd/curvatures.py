@@ -517,21 +517,27 @@ class Curvature(ABC):
 
     def _per_sample_layers(self, what: str, advice: str) -> List[Module]:
         """The selected layers, in ``modules()`` order, after checking that every one has a per-sample form P_n = g_n X_n^T:
-        Linear, and Conv2d with groups 1, dilation 1 and integer padding.  Any other raises NotImplementedError naming it."""
+        Linear, and Conv2d with groups 1, dilation 1 and integer padding; with `ops.widen_per_sample` also ConvTranspose2d
+        under the same restrictions and, for the estimators that treat a MultiheadAttention module as its two projections
+        (KFAC, EFB), those two `AttentionProjection`s.  Any other raises NotImplementedError naming it."""
         names = {mod: name for name, mod in self.model.named_modules()}
+        wide = ops.per_sample_is_wide()
         layers = []
         for layer in self.model.modules():
             kind = layer.__class__.__name__
             if kind not in self.layer_types:
                 continue
             why = None
-            if kind == 'Conv2d':
+            if kind == 'Conv2d' or (kind == 'ConvTranspose2d' and wide):
                 if int(layer.groups) != 1:
                     why = f"grouped convolution (groups={layer.groups})"
                 elif tuple(layer.dilation) != (1, 1):
                     why = "dilated convolution"
                 elif not all(isinstance(p, int) for p in layer.padding):
                     why = "string padding mode"
+            elif kind == 'MultiheadAttention' and self._mha_as_projections and wide:
+                layers.extend(AttentionProjection.of(layer))
+                continue
             elif kind != 'Linear':
                 why = kind
             if why is not None:
@@ -541,29 +547,52 @@ class Curvature(ABC):
 
     def _record_per_sample(self, what: str) -> None:
         """``per_sample=True`` of Diagonal / EFB: check that every selected layer has a per-sample form and register
-        KFAC's recording hooks on it."""
+        KFAC's recording hooks on it (for the projections of an attention module: its tap on F.linear)."""
         self.hooks = list()
         self.record = dict()
+        self._out_size = dict()
         for layer in self._per_sample_layers(f"{what}(per_sample=True)", "select other layer types or use per_sample=False"):
-            self._record_layer(layer)
+            if not isinstance(layer, AttentionProjection):
+                self._record_layer(layer)
+                continue
+            self.record[layer] = [None, None]
+            if layer.kind == 'attn_in':                      # once per module
+                tap = _LinearTap(self, layer.module)
+                self.hooks.append(layer.module.register_forward_pre_hook(tap.install))
+                self.hooks.append(layer.module.register_forward_hook(tap.remove, always_call=True))
 
     def _per_sample_operands(self, what: str, layers, x_side: bool = True, **layout):
         """The per-sample operands of `layers` from their records, packed where they cannot be read in place:
         [(sides, g tensor, x tensor)] with `sides` the `ops.PerSampleSides` whose strides address the two tensors.  A missing
-        record raises like KFAC's; CPU records raise RuntimeError (no fallback).  The packed copies live in shared scratch:
-        they are valid until the next per-sample update on this stream.  ``x_side=False``: only the g side is packed (the x
-        tensor comes back as None), into scratch of its own, so that the x side of the call before stays valid."""
+        record raises like KFAC's; CPU records raise RuntimeError (no fallback), as do records whose dtype the line does
+        not take (`ops.per_sample_dtype_fault`).  The packed copies live in shared
+        scratch: they are valid until the next per-sample update on this stream.  ``x_side=False``: only the g side is
+        packed (the x tensor comes back as None), into scratch of its own, so that the x side of the call before stays
+        valid."""
         sides = []
         for layer in layers:
             forward, backward = self.record[layer]
             if forward is None or backward is None:
                 raise RuntimeError(f"{what}.update: no recorded forward/backward pass for a selected layer")
             for t in (forward, backward):
-                if t.dtype != torch.float32:
-                    raise RuntimeError(f"{what}.update(per_sample=True) expects float32 records, got {t.dtype}")
+                fault = ops.per_sample_dtype_fault(f"{what}.update(per_sample=True)", t)
+                if fault:
+                    raise RuntimeError(fault)
                 if not t.is_cuda:
                     raise RuntimeError("curvature_amd runs on MI355X only: got a CPU tensor (no CPU fallback)")
-            sides.append(ops.per_sample_operands(layer, forward, backward, **layout))
+            extra = {}
+            if isinstance(layer, AttentionProjection) and layer.kind == 'attn_out':
+                # its record is (T N, E): the batch size is that of the module's input projection, recorded as (T, N, E)
+                first = self.record.get(AttentionProjection.of(layer.module)[0], (None, None))[0]
+                if first is None:
+                    raise RuntimeError(f"{what}: the output projection of an attention module takes its batch size from "
+                                       "the module's input projection, which has no record (select MultiheadAttention as "
+                                       "a whole)")
+                if first.dim() != 3:
+                    raise RuntimeError(f"{what}: unbatched (T, E) attention input is not supported (the input projection "
+                                       f"recorded {tuple(first.shape)}); pass a batch of one")
+                extra["samples"] = int(first.shape[1])
+            sides.append(ops.per_sample_operands(layer, forward, backward, **layout, **extra))
         flat = [op for s in sides for op in ((s.g, s.x) if x_side else (s.g,))]
         bufs = ops.per_sample_scratch([op.floats for op in flat], flat[0].src.device,
                                       "persample_x" if x_side else "persample_g")
@@ -603,7 +632,9 @@ class Curvature(ABC):
         per-sample scratch in between.  The kept X side (the unfolded inputs of every layer) stays on the estimator (entry
         ``"variance"`` of ``_predictive_kept``) until the next ``inputs=True`` call replaces it or `drop_predictive_state`
         drops it, as `evaluate.glm_predictive` does.  Linear and Conv2d (groups 1, dilation 1, integer padding) with
-        float32 GPU records; other selected layers raise NotImplementedError, as does a layer-sharded estimator.
+        float32 GPU records; with `ops.widen_per_sample` also ConvTranspose2d, for KFAC and EFB the two projections of a
+        MultiheadAttention module, and bfloat16 / float16 records (a model run under ``torch.autocast``: the pack upcasts
+        them, all sums are float32).  Other selected layers raise NotImplementedError, as does a layer-sharded estimator.
         Implemented by KFAC, Diagonal and EFB.  No counterpart in the reference, which has the Monte-Carlo predictive only."""
         raise NotImplementedError(f"{type(self).__name__}.functional_variance: no linearised predictive for this estimator "
                                   "(KFAC, Diagonal and EFB have one)")
@@ -763,7 +794,8 @@ class Diagonal(LinearisedPredictive, Curvature):
         The P_n are those of the BATCH pass: a BatchNorm layer in training mode couples the samples of a batch, and the
         per-sample quantities are defined from that pass's records, not from N separate passes.  Linear and Conv2d
         (groups 1, dilation 1, integer padding) with float32 records; any other selected layer raises
-        NotImplementedError here."""
+        NotImplementedError here.  `ops.widen_per_sample` adds ConvTranspose2d and bfloat16 / float16 records
+        (MultiheadAttention stays refused: the state for it here is not one matrix per projection)."""
         super().__init__(model, layer_types, shard=shard)
         self.per_sample = bool(per_sample)
         if self.per_sample:
@@ -1472,7 +1504,8 @@ class EFB(LinearisedPredictive, Curvature):
         ``batch_size * sum_n (U_G^T P_n U_A)**2`` into `state` and ``batch_size * sum_n P_n**2`` into `diags`, with
         P_n = g_n X_n^T the share of sample n in [W.grad | b.grad], from recorded layer inputs and grad_outputs (see
         `Diagonal`; the P_n are those of the batch pass, also under a training-mode BatchNorm) instead of squaring the
-        batch gradient.  The two agree at batch size 1."""
+        batch gradient.  The two agree at batch size 1.  Layers and record dtypes as for `Diagonal`; with
+        `ops.widen_per_sample` also the two projections of a selected MultiheadAttention module."""
         super().__init__(model, layer_types, shard=shard)
         self.per_sample = bool(per_sample)
         if self.per_sample:

@@ -175,7 +175,10 @@ def _linearised(what: str, model: torch.nn.Module, estimator, images: torch.Tens
     ``(logits, classes, backward)``: `classes` the selected `outputs` (default: all), and ``backward(c)`` back-propagates
     ``logits[:, c].sum()`` into the records with `torch.autograd.grad` on the parameters that require grad (no ``.grad`` is
     touched).  On the way out the borrowed hooks are removed and what the estimator kept of this batch is dropped
-    (`drop_predictive_state`)."""
+    (`drop_predictive_state`).  Mixed precision is the caller's (with `ops.widen_per_sample`): a call wrapped in
+    ``torch.autocast`` records bfloat16 / float16 tensors and may yield half-precision `logits`; the drivers do not enter
+    autocast themselves, and everything they allocate or return beside `logits` (`variance`, `covariance`, `probs`) is
+    float32 - `_probit` and `mc_softmax` work on ``logits.float()``."""
     first_param = next(model.parameters())
     if not first_param.is_cuda or not images.is_cuda:
         raise RuntimeError(f"curvature_amd runs on MI355X only: {what} got a CPU model or batch (no CPU fallback)")

@@ -467,18 +467,50 @@ def factor_jobs(layer, x, g, out_size=None) -> LayerJobs:
                      (x if x is not None else g).shape[0], out_size[0] * out_size[1], groups)
 
 
+class PackSource(NamedTuple):
+    """Where `per_sample_pack` reads an operand: the source seen as ``(N, C, H, W)`` with element `strides`
+    ``(s_n, s_c, s_h, s_w)`` (the tensor itself gives the address, the dtype and the extent), the window, and `out_size`
+    ``(Ho, Wo)`` for the transposed gather of a ConvTranspose2d input (None: the forward im2col).  `channels_last`: False /
+    True where the strides are those of a contiguous (N, C, H, W) / (N, H, W, C) tensor - the two sources
+    curv_persample_pack knows - and None for any other view."""
+    shape: tuple
+    kernel: tuple
+    stride: tuple
+    padding: tuple
+    has_bias: bool
+    strides: tuple
+    out_size: Optional[tuple]
+    channels_last: Optional[bool]
+
+
+def _pack_source(shape, strides, kernel=(1, 1), stride=(1, 1), padding=(0, 0), has_bias=False, out_size=None,
+                 tokens: bool = False) -> PackSource:
+    """`tokens`: a source that is both layouts at once (one token per sample) counts as (N, H, W, C), as the input of a
+    Linear layer always has."""
+    shape, strides = tuple(map(int, shape)), tuple(map(int, strides))
+    N, C, H, W = shape
+
+    def same(want):                                    # (the stride of a dimension of size 1 addresses nothing)
+        return all(d == 1 or s == w for d, s, w in zip(shape, strides, want))
+    forms = [(False, (C * H * W, H * W, W, 1)), (True, (H * W * C, 1, W * C, C))]
+    form = next((f for f, want in (forms[::-1] if tokens else forms) if same(want)), None)
+    return PackSource(shape, tuple(kernel), tuple(stride), tuple(padding), bool(has_bias), strides,
+                      None if out_size is None else tuple(map(int, out_size)), form)
+
+
 class PerSampleOperand(NamedTuple):
     """One side of P_n = g_n X_n^T as `per_sample_sq_accumulate` reads it: `rows` rows of `L` values per sample, sample
     `n` row `r` at ``ns * n + rs * r`` floats.  `pack` is None where the record `src` is read in place, otherwise the
-    geometry ``(N, C, H, W, kernel, stride, padding, has_bias, channels_last)`` of the copy `per_sample_pack` writes
-    (`floats` of scratch, rows of `Lp` values with a zero tail, `rows_outer`: (rows, N, Lp) instead of (N, rows, Lp))."""
+    `PackSource` of the copy `per_sample_pack` writes (`floats` of scratch, rows of `Lp` values with a zero tail,
+    `rows_outer`: (rows, N, Lp) instead of (N, rows, Lp)); `src` is then float32, bfloat16 or float16 and may be any view
+    with non-negative strides."""
     src: object
     rows: int
     L: int
     Lp: int
     ns: int
     rs: int
-    pack: Optional[tuple]
+    pack: Optional[PackSource]
     rows_outer: bool
     floats: int
 
@@ -493,71 +525,186 @@ class PerSampleSides(NamedTuple):
     L: int
 
 
-def _per_sample_operand(src, geometry, in_place: bool, rows_outer: bool) -> PerSampleOperand:
-    N, C, H, W, kernel, stride, padding, has_bias, channels_last = geometry
-    L = ((H + 2 * padding[0] - kernel[0]) // stride[0] + 1) * ((W + 2 * padding[1] - kernel[1]) // stride[1] + 1)
-    rows = C * kernel[0] * kernel[1] + int(has_bias)
-    if in_place:
+# The wider per-sample line is opt-in: with it off - the default - the per-sample selection, its refusals
+# and their messages are exactly what they were.
+_WIDE = False
+
+
+def widen_per_sample(enable: bool = True) -> bool:
+    """Switch the wider per-sample line on or off for the process; returns what it was.  On: `per_sample_operands`, the
+    exact Fisher of Diagonal / EFB (``per_sample=True``) and the linearised predictive take bfloat16 / float16 records
+    (a model run under ``torch.autocast``; each side by its own dtype), ConvTranspose2d layers and, for KFAC and EFB, the
+    two projections of a MultiheadAttention module.  Off: float32 records of Linear and Conv2d only; the others raise."""
+    global _WIDE
+    was, _WIDE = _WIDE, bool(enable)
+    return was
+
+
+def per_sample_is_wide() -> bool:
+    return _WIDE
+
+
+def per_sample_dtype_fault(what: str, t) -> Optional[str]:
+    """Why the record `t` cannot enter the per-sample line (None: it can): float32 always; bfloat16 / float16 with
+    `widen_per_sample`; nothing else."""
+    if t.dtype == torch.float32 or (_WIDE and t.dtype in _PACK_DTYPES):
+        return None
+    if t.dtype in _PACK_DTYPES:
+        return f"{what} expects float32 records, got {t.dtype} (ops.widen_per_sample() admits bfloat16 / float16)"
+    return f"{what} expects float32" + (", bfloat16 or float16" if _WIDE else "") + f" records, got {t.dtype}"
+
+
+_PACK_DTYPES = {torch.float32: _lib.DTYPE_F32, torch.bfloat16: _lib.DTYPE_BF16, torch.float16: _lib.DTYPE_F16}
+
+
+def _per_sample_operand(src, geometry: PackSource, in_place: bool, rows_outer: bool) -> PerSampleOperand:
+    """`in_place` is the caller's wish; it holds only for a float32 source that is that very matrix in memory."""
+    (N, C, H, W), kernel, stride, padding = geometry.shape, geometry.kernel, geometry.stride, geometry.padding
+    if geometry.out_size is not None:
+        L = geometry.out_size[0] * geometry.out_size[1]
+    else:
+        L = ((H + 2 * padding[0] - kernel[0]) // stride[0] + 1) * ((W + 2 * padding[1] - kernel[1]) // stride[1] + 1)
+    rows = C * kernel[0] * kernel[1] + int(geometry.has_bias)
+    if in_place and src.dtype == torch.float32 and geometry.channels_last is False:
         return PerSampleOperand(src, rows, L, L, rows * L, L, None, False, 0)
     Lp = (L + 3) // 4 * 4
     ns, rs = (Lp, N * Lp) if rows_outer else (rows * Lp, Lp)
     return PerSampleOperand(src, rows, L, Lp, ns, rs, geometry, rows_outer, N * rows * Lp)
 
 
-def per_sample_operands(layer, x, g, rows_outer: bool = False, in_place: bool = True) -> PerSampleSides:
-    """The step from a layer's records `(x, g)` to the operands of its per-sample gradients P_n = g_n X_n^T (sample = index
-    of the leading dimension, as in `KFAC.update`), on the geometry of `factor_jobs`.
+def _token_major(what: str, t, N: Optional[int]):
+    """The record of an attention projection as (T, N, E): the attention forward hands F.linear a (T, N, E) tensor
+    (input projection) or (T N, E) rows t N + n (output projection, `N` from the module's input projection)."""
+    if t.dim() == 3:
+        return t
+    if t.dim() == 2 and N is not None and N >= 1 and t.shape[0] % N == 0:
+        return t.view(t.shape[0] // N, N, t.shape[1]) if t.is_contiguous() else t.reshape(t.shape[0] // N, N, t.shape[1])
+    if t.dim() == 2 and N is None:
+        raise RuntimeError(f"per-sample update: {what}: unbatched (T, E) attention input is not supported (the record "
+                           f"{tuple(t.shape)} has no sample dimension); pass a batch of one")
+    raise RuntimeError(f"per-sample update: {what}: record {tuple(t.shape)} does not fit {N} samples")
 
-    Conv2d (groups 1, dilation 1): g_n = grad_output[n] as (m, Ho Wo), X_n = unfold(x[n]) [+ ones row].  Linear:
-    g_n = grad_output[n]^T (m, T), X_n = x[n]^T [+ ones row] (D [+ 1], T) with T the product of the middle dimensions
-    (1 for an (N, D) input).  An operand is read in place where the record already is that matrix, rows contiguous and a
-    whole number of 16-byte groups long (grad_output of a convolution; the input of a bias-free 1x1 / stride-1 one);
-    everything else names the pack that writes it.  `rows_outer` / ``in_place=False``: every operand packed as one
-    (rows, N Lp) matrix (EFB rotates it with one product).  float32 records only."""
+
+def per_sample_operands(layer, x, g, rows_outer: bool = False, in_place: bool = True,
+                        samples: Optional[int] = None) -> PerSampleSides:
+    """The step from a layer's records `(x, g)` to the operands of its per-sample gradients P_n = g_n X_n^T, on the
+    geometry of `factor_jobs`.
+
+    Conv2d (groups 1, dilation 1): g_n = grad_output[n] as (m, Ho Wo), X_n = unfold(x[n]) [+ ones row].  ConvTranspose2d
+    (groups 1, dilation 1): g_n likewise, X_n the transposed gather (row (ci, a, b) at (oh, ow) is
+    x[n, ci, (oh + ph - a) / sh, (ow + pw - b) / sw] where that is a whole position inside the input, else 0) - the column
+    order of Wm; the output size is grad_output's.  Linear: g_n = grad_output[n]^T (m, T), X_n = x[n]^T [+ ones row] (D [+ 1], T)
+    with T the product of the middle dimensions (1 for an (N, D) input).  The sample is the leading index, as in
+    `KFAC.update` - except for an `AttentionProjection` (curvatures.py), whose records are token-major: (T, N, E), or
+    (T N, E) for the output projection with `samples` = N; they are read through strides, not transposed.  An operand is
+    read in place where the record already is that matrix in float32, rows contiguous and a whole number of 16-byte groups
+    long (grad_output of a convolution; the input of a bias-free 1x1 / stride-1 one); everything else names the pack that
+    writes it.  `rows_outer` / ``in_place=False``: every operand packed as one (rows, N Lp) matrix (EFB rotates it with
+    one product).  float32 records; with `widen_per_sample` each side float32, bfloat16 or float16 by its own dtype (an
+    autocast ResNet-50 has a float32 stem input and a bfloat16 grad_output): a half side is always packed - the pack
+    upcasts it - and never read in place.  Any other dtype raises RuntimeError.  Views are not copied: the pack reads
+    them through their strides."""
     for t in (x, g):
-        if t.dtype != torch.float32:
-            raise RuntimeError(f"per-sample update expects float32 records, got {t.dtype}")
+        fault = per_sample_dtype_fault("per-sample update", t)
+        if fault:
+            raise RuntimeError(fault)
+    kind = layer.__class__.__name__
+    x, g = x.detach(), g.detach()
+    if kind == 'AttentionProjection':
+        what = f"attention projection '{layer.kind}'"
+        x, g = _token_major(what, x, samples), _token_major(what, g, samples)
+        if x.shape[:2] != g.shape[:2]:
+            raise RuntimeError(f"per-sample update: {what}: records do not match (input {tuple(x.shape)}, grad_output "
+                               f"{tuple(g.shape)})")
     sides = factor_jobs(layer, ShapeOnly(tuple(x.shape)), ShapeOnly(tuple(g.shape)))
-    if sides.groups != 1 or not isinstance(sides.a, FactorJob):
-        raise NotImplementedError(f"per-sample update: unsupported layer {layer.__class__.__name__}")
-    x, g = x.detach().contiguous(), g.detach().contiguous()
-    N = int(x.shape[0])
+    if sides.groups != 1 or not isinstance(sides.a, (FactorJob, ConvTFactorJob)):
+        raise NotImplementedError(f"per-sample update: unsupported layer {kind}")
     has_bias = sides.a.has_bias
-    if layer.__class__.__name__ == 'Conv2d':
-        _, C, H, W = x.shape
-        _, m, Ho, Wo = g.shape
-        geo_x = (N, C, H, W, sides.a.kernel, sides.a.stride, sides.a.padding, has_bias, False)
-        geo_g = (N, m, Ho, Wo, (1, 1), (1, 1), (0, 0), False, False)
+    if kind in ('Conv2d', 'ConvTranspose2d'):
+        if x.dim() != 4 or g.dim() != 4:
+            raise RuntimeError(f"per-sample update: records of {kind} must be (N, C, H, W), got {tuple(x.shape)} and "
+                               f"{tuple(g.shape)}")
+        N, Ng = int(x.shape[0]), int(g.shape[0])
+        Ho, Wo = map(int, g.shape[2:])
+        geo_x = _pack_source(x.shape, x.stride(), sides.a.kernel, sides.a.stride, sides.a.padding, has_bias,
+                             (Ho, Wo) if kind == 'ConvTranspose2d' else None)
+        geo_g = _pack_source(g.shape, g.stride())
         whole = in_place and (Ho * Wo) % 4 == 0
-        plain = sides.a.kernel == (1, 1) and sides.a.stride == (1, 1) and sides.a.padding == (0, 0) and not has_bias
+        plain = kind == 'Conv2d' and sides.a.kernel == (1, 1) and sides.a.stride == (1, 1) and \
+            sides.a.padding == (0, 0) and not has_bias
         x_op = _per_sample_operand(x, geo_x, whole and plain, rows_outer)
         g_op = _per_sample_operand(g, geo_g, whole, rows_outer)
     else:
-        T = math.prod(x.shape[1:-1])
-        geo_x = (N, int(x.shape[-1]), T, 1, (1, 1), (1, 1), (0, 0), has_bias, True)
-        geo_g = (N, int(g.shape[-1]), T, 1, (1, 1), (1, 1), (0, 0), False, True)
-        x_op = _per_sample_operand(x, geo_x, False, rows_outer)
-        g_op = _per_sample_operand(g, geo_g, False, rows_outer)
-    if g_op.L != x_op.L or g_op.rows != sides.m or x_op.rows != sides.n or g.shape[0] != N:
-        raise RuntimeError(f"per-sample update: records of {layer.__class__.__name__} do not match the layer "
+        if kind == 'AttentionProjection':                  # (T, N, E): the sample is the middle index
+            N = Ng = int(x.shape[1])
+            views = [(t, (N, int(t.shape[2]), int(t.shape[0]), 1), (t.stride(1), t.stride(2), t.stride(0), 1)) for t in (x, g)]
+        else:                                              # (N, *, D) as (N, T, D): X_n = x[n]^T
+            N, Ng = int(x.shape[0]), int(g.shape[0])
+            T = math.prod(x.shape[1:-1])
+            x, g = x.reshape(N, T, x.shape[-1]), g.reshape(int(g.shape[0]), -1, g.shape[-1])
+            views = [(t, (int(t.shape[0]), int(t.shape[2]), int(t.shape[1]), 1), (t.stride(0), t.stride(2), t.stride(1), 1))
+                     for t in (x, g)]
+        (x, shape_x, strides_x), (g, shape_g, strides_g) = views
+        x_op = _per_sample_operand(x, _pack_source(shape_x, strides_x, has_bias=has_bias, tokens=True), False, rows_outer)
+        g_op = _per_sample_operand(g, _pack_source(shape_g, strides_g, tokens=True), False, rows_outer)
+    if g_op.L != x_op.L or g_op.rows != sides.m or x_op.rows != sides.n or Ng != N:
+        raise RuntimeError(f"per-sample update: records of {kind} do not match the layer "
                            f"(input {tuple(x.shape)}, grad_output {tuple(g.shape)})")
     return PerSampleSides(g_op, x_op, sides.n, sides.m, N, x_op.L)
 
 
-def per_sample_pack(operands: Sequence[PerSampleOperand], dsts: Sequence[torch.Tensor]) -> None:
-    """curv_persample_pack: the packed copy of every operand into its `dst` (a float32 GPU buffer of `floats` values, 16-byte
-    aligned), all layers in one call."""
-    if not operands:
+def _pack_entry(op: PerSampleOperand) -> str:
+    """The entry point that packs `op`: curv_persample_pack for what it can express (a float32 source, contiguous as
+    (N, C, H, W) or (N, H, W, C), forward window) - those calls stay the launches they were - and curv_persample_pack_ex
+    for everything else (half precision, strided views, the transposed gather)."""
+    plain = op.src.dtype == torch.float32 and op.pack.out_size is None and op.pack.channels_last is not None
+    return "curv_persample_pack" if plain else "curv_persample_pack_ex"
+
+
+def _source_extent(t: torch.Tensor) -> int:
+    """Elements from `t`'s first one to the end of its storage."""
+    return t.untyped_storage().nbytes() // t.element_size() - t.storage_offset()
+
+
+def _fill_pack(d, op: PerSampleOperand, dst: torch.Tensor, general: bool) -> None:
+    """Descriptor `d` (curv_persample_pack_desc, or curv_persample_pack_ex_desc when `general`) of `op` into `dst`: the
+    one place that fills either."""
+    geo = op.pack
+    d.src, d.dst = op.src.data_ptr(), dst.data_ptr()
+    _set_geometry(d, geo.shape, geo.kernel, geo.stride, geo.padding, geo.has_bias)
+    d.rows_outer, d.Lp = int(op.rows_outer), op.Lp
+    if not general:
+        d.channels_last = int(geo.channels_last)
         return
-    arr = (_lib.curv_persample_pack_desc * len(operands))()
-    for d, op, dst in zip(arr, operands, dsts):
-        _require_gpu(op.src, dst)
+    d.s_n, d.s_c, d.s_h, d.s_w = geo.strides
+    d.src_elems = _source_extent(op.src)
+    d.dtype = _PACK_DTYPES[op.src.dtype]
+    d.transposed = int(geo.out_size is not None)
+    if geo.out_size is not None:
+        d.Ho, d.Wo = geo.out_size
+
+
+def per_sample_pack(operands: Sequence[PerSampleOperand], dsts: Sequence[torch.Tensor]) -> None:
+    """The packed float32 copy of every operand into its `dst` (a float32 GPU buffer of `floats` values, 16-byte aligned),
+    all layers in at most one call of each entry point (`_pack_entry`)."""
+    routed = {"curv_persample_pack": [], "curv_persample_pack_ex": []}
+    for op, dst in zip(operands, dsts):
+        _require_gpu(dst)
+        if not op.src.is_cuda:
+            raise RuntimeError("curvature_amd runs on MI355X only: got a CPU tensor (no CPU fallback)")
+        if op.src.dtype not in _PACK_DTYPES:
+            raise RuntimeError(f"per_sample_pack expects float32, bfloat16 or float16 sources, got {op.src.dtype}")
         if dst.numel() < op.floats:
             raise RuntimeError("per_sample_pack: destination too small")
-        d.src, d.dst = op.src.data_ptr(), dst.data_ptr()
-        _set_geometry(d, op.pack[:4], *op.pack[4:8])
-        d.channels_last, d.rows_outer, d.Lp = int(op.pack[8]), int(op.rows_outer), op.Lp
-    _lib.check(_lib.lib().curv_persample_pack(_lib.stream_ptr(), arr, len(operands)), "curv_persample_pack")
+        routed[_pack_entry(op)].append((op, dst))
+    for name, items in routed.items():
+        if not items:
+            continue
+        general = name == "curv_persample_pack_ex"
+        arr = ((_lib.curv_persample_pack_ex_desc if general else _lib.curv_persample_pack_desc) * len(items))()
+        for d, (op, dst) in zip(arr, items):
+            _fill_pack(d, op, dst, general)
+        _lib.check(getattr(_lib.lib(), name)(_lib.stream_ptr(), arr, len(items)), name)
 
 
 class _PerSampleProduct:

@@ -189,6 +189,7 @@ int curv_kfac_group_accumulate(void* stream, const curv_group_factor_desc* descs
  * Never reads outside `src`; enqueues on `stream` only, never waits on the host and allocates nothing (graph capture
  * works).  An empty call is a no-op.  Dilation and groups are not representable.
  * ---------------------------------------------------------------------------------------------- */
+#define CURV_DTYPE_F32 0   /* (curv_persample_pack_ex only: curv_kfac16_accumulate builds half-precision factors) */
 #define CURV_DTYPE_BF16 1
 #define CURV_DTYPE_F16 2
 typedef struct curv_factor16_desc {
@@ -517,6 +518,45 @@ typedef struct curv_persample_pack_desc {
   int32_t Lp;
 } curv_persample_pack_desc;
 int curv_persample_pack(void* stream, const curv_persample_pack_desc* descs, int n);
+
+/* The general form of curv_persample_pack: the same destination (layout, ones row, zero tail, fp32, dst 16-byte aligned,
+ * Lp a multiple of 4) from a source that the entry point above cannot express.
+ *   dtype       CURV_DTYPE_F32, CURV_DTYPE_BF16 or CURV_DTYPE_F16: half values are upcast by the pack (bf16 is its bit
+ *               pattern shifted up 16 bits, fp16 the exact conversion: inf, NaN, -0 and subnormals survive).  A product
+ *               of two bf16 or two fp16 values is exact in fp32, so the fp32 products on the upcast copy compute what a
+ *               half-precision kernel with fp32 accumulation would.
+ *   s_n .. s_w  source strides in ELEMENTS: element (n, c, h, w) is src[n*s_n + c*s_c + h*s_h + w*s_w].  (N, C, H, W) is
+ *               (CHW, HW, W, 1); the (N, T, D) input of a Linear layer is C = D, H = T, W = 1 with (TD, 1, D, -); the
+ *               (T, N, E) record of an attention projection is C = E, H = T, W = 1 with (E, 1, NE, -).  Not negative.
+ *   src_elems   the extent of the source in elements: the largest addressed offset must lie inside it, and it must
+ *               hold fewer than 2^31 bytes.  Nothing outside it is read (a masked or padded element reads src[0]).
+ *   transposed  != 0: X of a ConvTranspose2d with output Ho x Wo (given; within the range output_size allows,
+ *               [(H-1)s - 2p + k, (H-1)s - 2p + k + s - 1]): row r = (ci, a, b) at l = (oh, ow) is
+ *               x[n, ci, (oh + ph - a)/sh, (ow + pw - b)/sw] where both divisions are exact and the result lies inside
+ *               H x W, 0 elsewhere - the column order of Wm = weight.permute(1, 0, 2, 3).reshape(Cout, -1).  L = Ho*Wo.
+ *               == 0: the forward im2col of curv_persample_pack; Ho and Wo are not read.
+ * A 1x1 / stride-1 / padding-0 item whose rows are plain runs of the source, with the pointer and the sample and channel
+ * strides multiples of four elements, is read with one 8- or 16-byte load per four values; everything else gathers per
+ * element.  One launch per 16 items of one dtype; an item's bits do not depend on the other items of the call.  Every item
+ * is checked before anything is launched: invalid geometry, an unknown dtype, a transposed output size outside its range,
+ * Lp, the element limits of curv_persample_pack and a source extent smaller than the largest offset return
+ * CURV_ERR_INVALID with the item named.  An empty call is a no-op. */
+typedef struct curv_persample_pack_ex_desc {
+  const void* src;
+  float* dst;
+  long long s_n, s_c, s_h, s_w;
+  long long src_elems;
+  int32_t N, C, H, W;
+  int32_t kh, kw, sh, sw, ph, pw;
+  int32_t Ho, Wo;
+  int32_t has_bias;
+  int32_t dtype;
+  int32_t transposed;
+  int32_t rows_outer;
+  int32_t Lp;
+  int32_t reserved;
+} curv_persample_pack_ex_desc;
+int curv_persample_pack_ex(void* stream, const curv_persample_pack_ex_desc* descs, int n);
 
 /* ------------------------------------------------------------------------------------------------
  * Linearised Laplace (GLM) predictive: the other reduction of the per-sample products (csrc/persample.hip) - over the
