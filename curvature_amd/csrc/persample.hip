@@ -1,4 +1,4 @@
-// Exact per-sample Fisher products (curv_persample_sq_accumulate / curv_persample_pack, include/curv_hip.h):
+// Exact per-sample Fisher products (curv_persample_sq_accumulate / curv_persample_pack_ex, include/curv_hip.h):
 //   C[i][j] (+)= alpha * sum_{n < S} ( sum_{l < L} A[n a_ns + i a_rs + l] * B[n b_ns + j b_rs + l] )**2
 // For a layer with grad_output g_n (m x L) and unfolded input X_n (n_in x L) the inner sum is P_n = g_n X_n^T, the
 // sample's share of [W.grad | b.grad]; the sum of its squares is the Fisher diagonal (Diagonal) and, on operands rotated
@@ -7,7 +7,7 @@
 // and starts the next sample from zero.
 //
 // Three launches per batch of up to 16 products:
-//   1. (curv_persample_pack, a call of its own) X of a layer into caller scratch wherever the source cannot be read in
+//   1. (curv_persample_pack_ex, a call of its own) X of a layer into caller scratch wherever the source cannot be read in
 //      place: the unfold of a convolution input (rows (c, kh, kw)), the transpose of a Linear input (N, T, D), or a plain
 //      copy; plus the ones row of a biased layer; every row padded with zeros to Lp columns by the pack itself.
 //   2. product: one workgroup per item = (product, 128 x 128 output tile, range of samples); 2 x 2 waves of 64 x 64, each
@@ -44,6 +44,8 @@
 #include "nt_stage.h"
 #include "side_build.h"
 #include "wave_sum.h"
+
+#include <climits>
 
 namespace curv {
 namespace {
@@ -763,15 +765,21 @@ __global__ void __launch_bounds__(PS_THREADS) ps_reduce_kernel(const PsBatch bat
 }
 
 // ------------------------------------------------------------------------------------------------ pack
+// curv_persample_pack_ex (and curv_persample_pack, its fp32-contiguous spelling): X_n or g_n as K-contiguous fp32 rows,
+// from a source of fp32, bf16 or fp16 values addressed through element strides; forward im2col or the transposed gather
+// of a ConvTranspose2d input.
 struct PsPack {
-  const float* src;
+  const void* src;
   float* dst;
+  long long s_n;                // sample stride in elements: the sample base is formed in 64 bits, once per thread
+  unsigned s_c, s_h, s_w;       // strides inside a sample, in elements (a sample spans fewer than 2^31: pack_plan_of)
   int N, C, H, W, kh, kw, sh, sw, ph, pw, Ho, Wo;
-  int rows;                   // C kh kw (the ones row, if any, is row `rows`)
-  int R;                      // rows + has_bias
+  int rows;                     // C kh kw (the ones row, if any, is row `rows`)
+  int R;                        // rows + has_bias
   int L, Lp;
-  int has_bias, channels_last, rows_outer;
-  long long base;             // first thread of this layer in the launch
+  int has_bias, transposed, rows_outer;
+  int vec;                      // rows are plain runs of the source, every group of four aligned: one vector load each
+  long long base;               // first thread of this item in the launch
 };
 
 typedef ArgBatch<PsPack, PS_BATCH> PsPackBatch;
@@ -779,114 +787,19 @@ static_assert(sizeof(PsBatch) <= 3840 && sizeof(PsQuadBatch) <= 3840 && sizeof(P
                   sizeof(PsCovBatch) <= 3840 && sizeof(PsGridBatch) <= 3840,
               "kernel argument block must stay below 4 KB");
 
-bool pack_plan_of(const curv_persample_pack_desc& d, int index, PsPack* out) {
-  side::ConvGeom g;
-  if (!side::conv_geom_of(d, "curv_persample_pack", "item", index, &g)) return false;
-  PsPack P;
-  P.src = d.src; P.dst = d.dst;
-  P.N = g.N; P.C = g.C; P.H = g.H; P.W = g.W;
-  P.kh = g.kh; P.kw = g.kw; P.sh = g.sh; P.sw = g.sw; P.ph = g.ph; P.pw = g.pw; P.Ho = g.Ho; P.Wo = g.Wo;
-  const long long rows = (long long)d.C * d.kh * d.kw, L = (long long)P.Ho * P.Wo;
-  if (rows > (1 << 24) || L > (1 << 24) || (long long)d.C * d.H * d.W >= (1LL << 31) || (long long)d.N * (rows + 1) * (d.Lp / 4 + 1) >= (1LL << 31)) {
-    set_error("curv_persample_pack: item %d: too large (%lld rows, %lld positions)", index, rows, L);
-    return false;
-  }
-  P.rows = (int)rows;
-  P.has_bias = d.has_bias ? 1 : 0;
-  P.R = P.rows + P.has_bias;
-  P.L = (int)L;
-  P.Lp = d.Lp;
-  if (d.Lp < P.L || (d.Lp & 3)) {
-    set_error("curv_persample_pack: item %d: Lp %d must be a multiple of 4 and at least L = %d", index, d.Lp, P.L);
-    return false;
-  }
-  P.channels_last = d.channels_last ? 1 : 0;
-  P.rows_outer = d.rows_outer ? 1 : 0;
-  P.base = 0;
-  *out = P;
-  return true;
-}
-
-// Pack: one thread per 4 consecutive columns of one row of one sample (one 16-byte store); padding columns are written
-// as zeros, a masked gather reads src[0] and drops it.
-__global__ void __launch_bounds__(PS_THREADS) ps_pack_kernel(const PsPackBatch batch) {
-  const long long t = (long long)blockIdx.x * PS_THREADS + threadIdx.x;
-  int f = 0;                                               // (owner_of, spelled out: the call compiles differently)
-  for (int i = 1; i < batch.count; ++i)
-    if (t >= batch.e[i].base) f = i;
-  const PsPack& F = batch.e[f];
-  // 32-bit index arithmetic from here on (a layer has fewer than 2^31 threads and a sample fewer than 2^31 values:
-  // pack_plan_of): the 64-bit divisions cost more than the copy
-  const unsigned gpr = F.Lp / 4, R = F.R;
-  if (t - F.base >= (long long)F.N * R * gpr) return;
-  const unsigned local = (unsigned)(t - F.base);
-  const unsigned row = local / gpr;                        // n R + r
-  const int k0 = (int)(local - row * gpr) * 4;
-  const int n = (int)(row / R), r = (int)(row - (unsigned)n * R);
-  float v[4];
-  if (r < F.rows) {
-    const unsigned khw = F.kh * F.kw;
-    const int c = (int)((unsigned)r / khw), q = r - c * (int)khw;
-    const int a = (int)((unsigned)q / (unsigned)F.kw), b = q - a * F.kw;
-    int oh = (int)((unsigned)k0 / (unsigned)F.Wo), ow = k0 - oh * F.Wo;
-    const float* plane = F.src + (F.channels_last ? (long long)n * F.H * F.W * F.C + c
-                                                  : ((long long)n * F.C + c) * F.H * F.W);
-    const int step = F.channels_last ? F.C : 1;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const int ih = oh * F.sh - F.ph + a, iw = ow * F.sw - F.pw + b;
-      const bool ok = k0 + e < F.L && (unsigned)ih < (unsigned)F.H && (unsigned)iw < (unsigned)F.W;
-      const float x = ok ? plane[(ih * F.W + iw) * step] : F.src[0];        // a masked gather reads src[0]
-      v[e] = ok ? x : 0.0f;
-      if (++ow == F.Wo) { ow = 0; ++oh; }
-    }
-  } else {
-#pragma unroll
-    for (int e = 0; e < 4; ++e) v[e] = k0 + e < F.L ? 1.0f : 0.0f;      // the ones row of a biased layer
-  }
-  const long long out = F.rows_outer ? ((long long)r * F.N + n) * F.Lp + k0 : (long long)row * F.Lp + k0;
-  *reinterpret_cast<float4*>(F.dst + out) = make_float4(v[0], v[1], v[2], v[3]);
-}
-
-// ------------------------------------------------------------------------------------------------ general pack
-// curv_persample_pack_ex: the same destination from a source of fp32, bf16 or fp16 values addressed through element
-// strides, and the transposed gather of a ConvTranspose2d input.  ps_pack_kernel above stays as it is (what it packs
-// keeps its bits and its time); this kernel takes what it cannot express.
-struct PsPackEx {
-  const void* src;
-  float* dst;
-  unsigned s_n, s_c, s_h, s_w;  // source strides in elements (the whole source holds fewer than 2^31 bytes: pack_ex_plan_of)
-  int N, C, H, W, kh, kw, sh, sw, ph, pw, Ho, Wo;
-  int rows, R, L, Lp;
-  int has_bias, transposed, rows_outer;
-  int vec;                      // rows are plain runs of the source, every group of four aligned: one vector load each
-  long long base;               // first thread of this item in the launch
-};
-
-typedef ArgBatch<PsPackEx, PS_BATCH> PsPackExBatch;
-static_assert(sizeof(PsPackExBatch) <= 3840, "kernel argument block must stay below 4 KB");
-
-int pack_ex_elem_bytes(int dtype) {
+int pack_elem_bytes(int dtype) {
   return dtype == CURV_DTYPE_F32 ? 4 : (dtype == CURV_DTYPE_BF16 || dtype == CURV_DTYPE_F16) ? 2 : 0;
 }
 
-bool pack_ex_plan_of(const curv_persample_pack_ex_desc& d, int index, PsPackEx* out) {
-  const char* const who = "curv_persample_pack_ex";
-  const int esize = pack_ex_elem_bytes(d.dtype);
+// Item `index` of a call of `who` as the kernel reads it, or false with the error text set.  One order of checks for
+// both entry points, that of curv_persample_pack: sizes first, addresses after them, so that a call with null pointers
+// learns whether its geometry would be taken.  `pointers`: the one message a caller has for a null src or dst and a
+// misaligned dst (curv_persample_pack), in place of one message each.
+bool pack_plan_of(const curv_persample_pack_ex_desc& d, int index, const char* who, PsPack* out,
+                  const char* pointers = nullptr) {
+  const int esize = pack_elem_bytes(d.dtype);
   if (esize == 0) {
     set_error("%s: item %d: unknown dtype %d (CURV_DTYPE_F32, CURV_DTYPE_BF16 or CURV_DTYPE_F16)", who, index, d.dtype);
-    return false;
-  }
-  if (!d.src || !d.dst) {
-    set_error("%s: item %d: null src or dst", who, index);
-    return false;
-  }
-  if (reinterpret_cast<uintptr_t>(d.dst) & 15) {
-    set_error("%s: item %d: dst is not 16-byte aligned", who, index);
-    return false;
-  }
-  if (reinterpret_cast<uintptr_t>(d.src) % (uintptr_t)esize) {
-    set_error("%s: item %d: src is not aligned to its %d-byte elements", who, index, esize);
     return false;
   }
   side::ConvGeom g;
@@ -904,12 +817,23 @@ bool pack_ex_plan_of(const curv_persample_pack_ex_desc& d, int index, PsPackEx* 
   } else if (!side::conv_geom_of(d, who, "item", index, &g)) {
     return false;
   }
-  PsPackEx P;
+  if (d.s_n < 0 || d.s_c < 0 || d.s_h < 0 || d.s_w < 0 || d.src_elems < 1) {
+    set_error("%s: item %d: negative stride, or source extent %lld elements below 1", who, index, d.src_elems);
+    return false;
+  }
+  PsPack P;
   P.src = d.src; P.dst = d.dst;
   P.N = g.N; P.C = g.C; P.H = g.H; P.W = g.W;
   P.kh = g.kh; P.kw = g.kw; P.sh = g.sh; P.sw = g.sw; P.ph = g.ph; P.pw = g.pw; P.Ho = g.Ho; P.Wo = g.Wo;
   const long long rows = (long long)d.C * d.kh * d.kw, L = (long long)P.Ho * P.Wo;
-  if (rows > (1 << 24) || L > (1 << 24) || (long long)d.N * (rows + 1) * (d.Lp / 4 + 1) >= (1LL << 31)) {
+  // what one sample spans, (C-1) s_c + (H-1) s_h + (W-1) s_w, stays below 2^31 elements: offsets inside a sample are
+  // 32-bit (a stride of 2^31 or more is refused before it is multiplied)
+  const long long dims[4] = {d.N, d.C, d.H, d.W}, strides[4] = {d.s_n, d.s_c, d.s_h, d.s_w};
+  const long long span_max = 1LL << 31;
+  long long span = 0;
+  for (int k = 1; k < 4 && span < span_max; ++k)
+    span = dims[k] > 1 && strides[k] >= span_max ? span_max : span + (dims[k] - 1) * strides[k];
+  if (rows > (1 << 24) || L > (1 << 24) || span >= span_max || (long long)d.N * (rows + 1) * (d.Lp / 4 + 1) >= (1LL << 31)) {
     set_error("%s: item %d: too large (%lld rows, %lld positions)", who, index, rows, L);
     return false;
   }
@@ -917,27 +841,30 @@ bool pack_ex_plan_of(const curv_persample_pack_ex_desc& d, int index, PsPackEx* 
     set_error("%s: item %d: Lp %d must be a multiple of 4 and at least L = %lld", who, index, d.Lp, L);
     return false;
   }
-  if (d.s_n < 0 || d.s_c < 0 || d.s_h < 0 || d.s_w < 0 || d.src_elems < 1 ||
-      d.src_elems * esize >= PS_BYTES_MAX) {
-    set_error("%s: item %d: negative stride, or source extent %lld elements outside [1, 2^31 bytes)", who, index,
-              d.src_elems);
+  if (pointers && (!d.src || !d.dst || (reinterpret_cast<uintptr_t>(d.dst) & 15))) {
+    set_error("%s: item %d: %s", who, index, pointers);
     return false;
   }
-  // the largest addressed offset, dimension by dimension (a stride at or beyond the extent is refused before it is multiplied)
-  const long long limit = d.src_elems;
-  long long last = 0;
-  const long long dims[4] = {d.N, d.C, d.H, d.W}, strides[4] = {d.s_n, d.s_c, d.s_h, d.s_w};
-  for (int k = 0; k < 4; ++k) {
-    if (dims[k] > 1 && strides[k] >= limit) last = limit;
-    else last += (dims[k] - 1) * strides[k];
-    if (last >= limit) {
-      set_error("%s: item %d: the source extent (%lld elements) is smaller than the largest offset its sizes and strides "
-                "address (N %d C %d H %d W %d, strides %lld %lld %lld %lld)", who, index, limit, d.N, d.C, d.H, d.W, d.s_n,
-                d.s_c, d.s_h, d.s_w);
-      return false;
-    }
+  if (!d.src || !d.dst) {
+    set_error("%s: item %d: null src or dst", who, index);
+    return false;
   }
-  P.s_n = (unsigned)(d.N > 1 ? d.s_n : 0); P.s_c = (unsigned)(d.C > 1 ? d.s_c : 0);
+  if (reinterpret_cast<uintptr_t>(d.dst) & 15) {
+    set_error("%s: item %d: dst is not 16-byte aligned", who, index);
+    return false;
+  }
+  if (reinterpret_cast<uintptr_t>(d.src) % (uintptr_t)esize) {
+    set_error("%s: item %d: src is not aligned to its %d-byte elements", who, index, esize);
+    return false;
+  }
+  // the largest addressed offset, span + (N-1) s_n, lies inside the extent (by a division: the product may not fit)
+  if (span >= d.src_elems || (d.N > 1 && d.s_n > (d.src_elems - 1 - span) / (d.N - 1))) {
+    set_error("%s: item %d: the source extent (%lld elements) is smaller than the largest offset its sizes and strides "
+              "address (N %d C %d H %d W %d, strides %lld %lld %lld %lld)", who, index, d.src_elems, d.N, d.C, d.H, d.W,
+              d.s_n, d.s_c, d.s_h, d.s_w);
+    return false;
+  }
+  P.s_n = d.N > 1 ? d.s_n : 0; P.s_c = (unsigned)(d.C > 1 ? d.s_c : 0);
   P.s_h = (unsigned)(d.H > 1 ? d.s_h : 0); P.s_w = (unsigned)(d.W > 1 ? d.s_w : 0);
   P.rows = (int)rows;
   P.has_bias = d.has_bias ? 1 : 0;
@@ -966,12 +893,15 @@ __device__ __forceinline__ float ps_up(_Float16 x) { return (float)x; }
 template <typename T>
 struct alignas(4 * sizeof(T)) PsQuad4 { T v[4]; };
 
-// One thread per 4 consecutive columns of one row of one sample (one 16-byte store), as ps_pack_kernel; a masked or
-// padded element reads src[0] and drops it.  32-bit index arithmetic for the same reason as there.
-template <typename T>
-__global__ void __launch_bounds__(PS_THREADS) ps_pack_ex_kernel(const PsPackExBatch batch) {
+// Pack: one thread per 4 consecutive columns of one row of one sample (one 16-byte store); padding columns are written
+// as zeros, a masked or padded element reads element 0 of the source and drops it.  32-bit index arithmetic after the
+// sample base (an item has fewer than 2^31 threads and a sample spans fewer than 2^31 elements: pack_plan_of): the
+// 64-bit divisions cost more than the copy.  TRANSPOSED: the launch may hold items of the transposed gather (its two
+// divisions per element stay out of the code of a launch that holds none: the forward unfolds of a ResNet).
+template <typename T, bool TRANSPOSED>
+__global__ void __launch_bounds__(PS_THREADS) ps_pack_kernel(const PsPackBatch batch) {
   const long long t = (long long)blockIdx.x * PS_THREADS + threadIdx.x;
-  const PsPackEx& F = batch.e[owner_of(batch, t)];
+  const PsPack& F = batch.e[owner_of(batch, t)];
   const unsigned gpr = F.Lp / 4, R = F.R;
   if (t - F.base >= (long long)F.N * R * gpr) return;
   const unsigned local = (unsigned)(t - F.base);
@@ -979,41 +909,51 @@ __global__ void __launch_bounds__(PS_THREADS) ps_pack_ex_kernel(const PsPackExBa
   const int k0 = (int)(local - row * gpr) * 4;
   const unsigned n = row / R;
   const int r = (int)(row - n * R);
-  const T* src = reinterpret_cast<const T*>(F.src);
+  const T* first = reinterpret_cast<const T*>(F.src);
+  const T* sample = first + (long long)n * F.s_n;
   float v[4];
   if (r >= F.rows) {
 #pragma unroll
     for (int e = 0; e < 4; ++e) v[e] = k0 + e < F.L ? 1.0f : 0.0f;      // the ones row of a biased layer
   } else if (F.vec && k0 + 4 <= F.L) {                                    // (1 x 1: r is the channel)
-    const PsQuad4<T> q = *reinterpret_cast<const PsQuad4<T>*>(src + (n * F.s_n + (unsigned)r * F.s_c + (unsigned)k0));
+    const PsQuad4<T> q = *reinterpret_cast<const PsQuad4<T>*>(sample + ((unsigned)r * F.s_c + (unsigned)k0));
 #pragma unroll
     for (int e = 0; e < 4; ++e) v[e] = ps_up(q.v[e]);
   } else {
-    const unsigned khw = F.kh * F.kw;
+    // every field the four elements read is held in a register first: a field read inside the loop is a load from the
+    // argument block with a wait of its own, and the four gathers would no longer be in flight together
+    const unsigned khw = F.kh * F.kw, kw = F.kw, H = F.H, W = F.W, s_h = F.s_h, s_w = F.s_w;
+    const int L = F.L, Wo = F.Wo, sh = F.sh, sw = F.sw, ph = F.ph, pw = F.pw;
+    const bool transposed = TRANSPOSED && F.transposed;
     const int c = (int)((unsigned)r / khw), q = r - c * (int)khw;
-    const int a = (int)((unsigned)q / (unsigned)F.kw), b = q - a * F.kw;
-    int oh = (int)((unsigned)k0 / (unsigned)F.Wo), ow = k0 - oh * F.Wo;
-    const unsigned plane = n * F.s_n + (unsigned)c * F.s_c;
+    const int a = (int)((unsigned)q / kw), b = q - a * (int)kw;
+    int oh = (int)((unsigned)k0 / (unsigned)Wo), ow = k0 - oh * Wo;
+    const T* plane = sample + (unsigned)c * F.s_c;
+    const T* at[4];
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
-      bool ok = k0 + e < F.L;
+      bool ok = k0 + e < L;
       unsigned ih, iw;
-      if (F.transposed) {
+      if (transposed) {
         // x[n, c, (oh + ph - a) / sh, (ow + pw - b) / sw] where both are whole and inside; no division of a negative
-        const int th = oh + F.ph - a, tw = ow + F.pw - b;
-        ok = ok && th >= 0 && tw >= 0;
+        const int th = oh + ph - a, tw = ow + pw - b;
+        ok = ok & (th >= 0) & (tw >= 0);
         const unsigned uh = ok ? (unsigned)th : 0u, uw = ok ? (unsigned)tw : 0u;
-        ih = uh / (unsigned)F.sh;
-        iw = uw / (unsigned)F.sw;
-        ok = ok && ih * (unsigned)F.sh == uh && iw * (unsigned)F.sw == uw;
+        ih = uh / (unsigned)sh;
+        iw = uw / (unsigned)sw;
+        ok = ok & (ih * (unsigned)sh == uh) & (iw * (unsigned)sw == uw);
       } else {
-        ih = (unsigned)(oh * F.sh - F.ph + a);
-        iw = (unsigned)(ow * F.sw - F.pw + b);
+        ih = (unsigned)(oh * sh - ph + a);
+        iw = (unsigned)(ow * sw - pw + b);
       }
-      ok = ok && ih < (unsigned)F.H && iw < (unsigned)F.W;
-      const float x = ps_up(src[ok ? plane + ih * F.s_h + iw * F.s_w : 0u]);  // a masked gather reads src[0]
-      v[e] = ok ? x : 0.0f;
-      if (++ow == F.Wo) { ow = 0; ++oh; }
+      ok = ok & (ih < H) & (iw < W);
+      at[e] = ok ? plane + (ih * s_h + iw * s_w) : nullptr;
+      if (++ow == Wo) { ow = 0; ++oh; }
+    }
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const float x = ps_up(*(at[e] ? at[e] : first));                    // a masked gather reads element 0 and drops it
+      v[e] = at[e] ? x : 0.0f;
     }
   }
   const long long out = F.rows_outer ? ((long long)r * F.N + n) * F.Lp + k0 : (long long)row * F.Lp + k0;
@@ -1021,19 +961,37 @@ __global__ void __launch_bounds__(PS_THREADS) ps_pack_ex_kernel(const PsPackExBa
 }
 
 template <typename T>
-int launch_pack_ex(hipStream_t stream, const std::vector<PsPackEx>& packs, const char* name) {
-  return for_arg_batches<PsPackEx, PS_BATCH, 1>(
-      (int)packs.size(), name,
-      [&](int i, PsPackEx* P, long long* threads) {
+int launch_pack(hipStream_t stream, const std::vector<PsPack>& packs, const char* who) {
+  return for_arg_batches<PsPack, PS_BATCH, 1>(
+      (int)packs.size(), who,
+      [&](int i, PsPack* P, long long* threads) {
         *P = packs[i];
         threads[0] = (long long)P->N * P->R * (P->Lp / 4);
       },
       [](int, long long threads) { return cdivll(threads, PS_THREADS); },
-      [&](const PsPackExBatch* b, const long long*, const unsigned* grid) {
-        hipLaunchKernelGGL(ps_pack_ex_kernel<T>, dim3(grid[0]), dim3(PS_THREADS), 0, stream, b[0]);
+      [&](const PsPackBatch* b, const long long*, const unsigned* grid) {
+        const bool transposed = std::any_of(b[0].e, b[0].e + b[0].count, [](const PsPack& P) { return P.transposed != 0; });
+        void (*kernel)(PsPackBatch) = ps_pack_kernel<T, false>;
+        if (transposed) kernel = ps_pack_kernel<T, true>;
+        hipLaunchKernelGGL(kernel, dim3(grid[0]), dim3(PS_THREADS), 0, stream, b[0]);
         CURV_LAUNCH_CHECK();
         return CURV_OK;
       });
+}
+
+// Every item is planned before anything is launched; the items of one source type share their launches, in call order.
+int pack_items(hipStream_t stream, const curv_persample_pack_ex_desc* descs, int n, const char* who,
+               const char* pointers = nullptr) {
+  std::vector<PsPack> packs[3];
+  for (int i = 0; i < n; ++i) {
+    PsPack P;
+    if (!pack_plan_of(descs[i], i, who, &P, pointers)) return CURV_ERR_INVALID;
+    packs[descs[i].dtype].push_back(P);
+  }
+  int rc = launch_pack<float>(stream, packs[CURV_DTYPE_F32], who);
+  if (rc == CURV_OK) rc = launch_pack<ps_bf16>(stream, packs[CURV_DTYPE_BF16], who);
+  if (rc == CURV_OK) rc = launch_pack<_Float16>(stream, packs[CURV_DTYPE_F16], who);
+  return rc;
 }
 
 size_t bytes_of(const std::vector<Plan>& plans) {
@@ -1237,45 +1195,34 @@ extern "C" int curv_persample_cov_reduce(void* stream_, const curv_persample_cov
       ps_cov_product_kernel, ps_cov_reduce_kernel);
 }
 
+// The fp32-contiguous spelling of curv_persample_pack_ex: (N, C, H, W), or (N, H, W, C) with channels_last.
 extern "C" int curv_persample_pack(void* stream_, const curv_persample_pack_desc* descs, int n) {
   const char* const name = "curv_persample_pack";
   if (n <= 0) return CURV_OK;
   CURV_REQUIRE(descs != nullptr, "%s: null descriptors", name);
-  hipStream_t stream = (hipStream_t)stream_;
-  std::vector<PsPack> packs(n);
+  // (sizes that a geometry check refuses may be anything: they count as 0 here, and a product saturates)
+  auto times = [](long long a, int b) { return b <= 0 ? 0 : a > LLONG_MAX / b ? LLONG_MAX : a * b; };
+  std::vector<curv_persample_pack_ex_desc> items(n);
   for (int i = 0; i < n; ++i) {
-    if (!pack_plan_of(descs[i], i, &packs[i])) return CURV_ERR_INVALID;
-    CURV_REQUIRE(descs[i].src && descs[i].dst && (reinterpret_cast<uintptr_t>(descs[i].dst) & 15) == 0,
-                 "%s: item %d: null src or dst, or dst not 16-byte aligned", name, i);
+    const curv_persample_pack_desc& d = descs[i];
+    curv_persample_pack_ex_desc& e = items[i];
+    e = curv_persample_pack_ex_desc{};
+    e.src = d.src; e.dst = d.dst;
+    e.N = d.N; e.C = d.C; e.H = d.H; e.W = d.W;
+    e.kh = d.kh; e.kw = d.kw; e.sh = d.sh; e.sw = d.sw; e.ph = d.ph; e.pw = d.pw;
+    e.has_bias = d.has_bias; e.rows_outer = d.rows_outer; e.Lp = d.Lp;
+    e.dtype = CURV_DTYPE_F32;
+    const long long hw = times(d.H, d.W), wc = times(d.W, d.C), chw = times(hw, d.C);
+    if (d.channels_last) { e.s_n = chw; e.s_c = 1; e.s_h = wc; e.s_w = d.C; }
+    else { e.s_n = chw; e.s_c = hw; e.s_h = d.W; e.s_w = 1; }
+    e.src_elems = times(chw, d.N);
   }
-  return for_arg_batches<PsPack, PS_BATCH, 1>(
-      n, name,
-      [&](int i, PsPack* P, long long* threads) {
-        *P = packs[i];
-        threads[0] = (long long)P->N * P->R * (P->Lp / 4);
-      },
-      [](int, long long threads) { return cdivll(threads, PS_THREADS); },
-      [&](const PsPackBatch* b, const long long*, const unsigned* grid) {
-        hipLaunchKernelGGL(ps_pack_kernel, dim3(grid[0]), dim3(PS_THREADS), 0, stream, b[0]);
-        CURV_LAUNCH_CHECK();
-        return CURV_OK;
-      });
+  return pack_items((hipStream_t)stream_, items.data(), n, name, "null src or dst, or dst not 16-byte aligned");
 }
 
 extern "C" int curv_persample_pack_ex(void* stream_, const curv_persample_pack_ex_desc* descs, int n) {
   const char* const name = "curv_persample_pack_ex";
   if (n <= 0) return CURV_OK;
   CURV_REQUIRE(descs != nullptr, "%s: null descriptors", name);
-  hipStream_t stream = (hipStream_t)stream_;
-  // every item is planned before anything is launched; the items of one source type share their launches, in call order
-  std::vector<PsPackEx> packs[3];
-  for (int i = 0; i < n; ++i) {
-    PsPackEx P;
-    if (!pack_ex_plan_of(descs[i], i, &P)) return CURV_ERR_INVALID;
-    packs[descs[i].dtype].push_back(P);
-  }
-  int rc = launch_pack_ex<float>(stream, packs[CURV_DTYPE_F32], name);
-  if (rc == CURV_OK) rc = launch_pack_ex<ps_bf16>(stream, packs[CURV_DTYPE_BF16], name);
-  if (rc == CURV_OK) rc = launch_pack_ex<_Float16>(stream, packs[CURV_DTYPE_F16], name);
-  return rc;
+  return pack_items((hipStream_t)stream_, descs, n, name);
 }

@@ -470,9 +470,7 @@ def factor_jobs(layer, x, g, out_size=None) -> LayerJobs:
 class PackSource(NamedTuple):
     """Where `per_sample_pack` reads an operand: the source seen as ``(N, C, H, W)`` with element `strides`
     ``(s_n, s_c, s_h, s_w)`` (the tensor itself gives the address, the dtype and the extent), the window, and `out_size`
-    ``(Ho, Wo)`` for the transposed gather of a ConvTranspose2d input (None: the forward im2col).  `channels_last`: False /
-    True where the strides are those of a contiguous (N, C, H, W) / (N, H, W, C) tensor - the two sources
-    curv_persample_pack knows - and None for any other view."""
+    ``(Ho, Wo)`` for the transposed gather of a ConvTranspose2d input (None: the forward im2col)."""
     shape: tuple
     kernel: tuple
     stride: tuple
@@ -480,22 +478,17 @@ class PackSource(NamedTuple):
     has_bias: bool
     strides: tuple
     out_size: Optional[tuple]
-    channels_last: Optional[bool]
 
 
-def _pack_source(shape, strides, kernel=(1, 1), stride=(1, 1), padding=(0, 0), has_bias=False, out_size=None,
-                 tokens: bool = False) -> PackSource:
-    """`tokens`: a source that is both layouts at once (one token per sample) counts as (N, H, W, C), as the input of a
-    Linear layer always has."""
-    shape, strides = tuple(map(int, shape)), tuple(map(int, strides))
-    N, C, H, W = shape
+def _pack_source(shape, strides, kernel=(1, 1), stride=(1, 1), padding=(0, 0), has_bias=False, out_size=None) -> PackSource:
+    return PackSource(tuple(map(int, shape)), tuple(kernel), tuple(stride), tuple(padding), bool(has_bias),
+                      tuple(map(int, strides)), None if out_size is None else tuple(map(int, out_size)))
 
-    def same(want):                                    # (the stride of a dimension of size 1 addresses nothing)
-        return all(d == 1 or s == w for d, s, w in zip(shape, strides, want))
-    forms = [(False, (C * H * W, H * W, W, 1)), (True, (H * W * C, 1, W * C, C))]
-    form = next((f for f, want in (forms[::-1] if tokens else forms) if same(want)), None)
-    return PackSource(shape, tuple(kernel), tuple(stride), tuple(padding), bool(has_bias), strides,
-                      None if out_size is None else tuple(map(int, out_size)), form)
+
+def _is_contiguous_nchw(geometry: PackSource) -> bool:
+    """The strides are those of a contiguous (N, C, H, W) tensor (the stride of a dimension of size 1 addresses nothing)."""
+    N, C, H, W = geometry.shape
+    return all(d == 1 or s == w for d, s, w in zip(geometry.shape, geometry.strides, (C * H * W, H * W, W, 1)))
 
 
 class PerSampleOperand(NamedTuple):
@@ -565,7 +558,7 @@ def _per_sample_operand(src, geometry: PackSource, in_place: bool, rows_outer: b
     else:
         L = ((H + 2 * padding[0] - kernel[0]) // stride[0] + 1) * ((W + 2 * padding[1] - kernel[1]) // stride[1] + 1)
     rows = C * kernel[0] * kernel[1] + int(geometry.has_bias)
-    if in_place and src.dtype == torch.float32 and geometry.channels_last is False:
+    if in_place and src.dtype == torch.float32 and _is_contiguous_nchw(geometry):
         return PerSampleOperand(src, rows, L, L, rows * L, L, None, False, 0)
     Lp = (L + 3) // 4 * 4
     ns, rs = (Lp, N * Lp) if rows_outer else (rows * Lp, Lp)
@@ -645,20 +638,12 @@ def per_sample_operands(layer, x, g, rows_outer: bool = False, in_place: bool = 
             views = [(t, (int(t.shape[0]), int(t.shape[2]), int(t.shape[1]), 1), (t.stride(0), t.stride(2), t.stride(1), 1))
                      for t in (x, g)]
         (x, shape_x, strides_x), (g, shape_g, strides_g) = views
-        x_op = _per_sample_operand(x, _pack_source(shape_x, strides_x, has_bias=has_bias, tokens=True), False, rows_outer)
-        g_op = _per_sample_operand(g, _pack_source(shape_g, strides_g, tokens=True), False, rows_outer)
+        x_op = _per_sample_operand(x, _pack_source(shape_x, strides_x, has_bias=has_bias), False, rows_outer)
+        g_op = _per_sample_operand(g, _pack_source(shape_g, strides_g), False, rows_outer)
     if g_op.L != x_op.L or g_op.rows != sides.m or x_op.rows != sides.n or Ng != N:
         raise RuntimeError(f"per-sample update: records of {kind} do not match the layer "
                            f"(input {tuple(x.shape)}, grad_output {tuple(g.shape)})")
     return PerSampleSides(g_op, x_op, sides.n, sides.m, N, x_op.L)
-
-
-def _pack_entry(op: PerSampleOperand) -> str:
-    """The entry point that packs `op`: curv_persample_pack for what it can express (a float32 source, contiguous as
-    (N, C, H, W) or (N, H, W, C), forward window) - those calls stay the launches they were - and curv_persample_pack_ex
-    for everything else (half precision, strided views, the transposed gather)."""
-    plain = op.src.dtype == torch.float32 and op.pack.out_size is None and op.pack.channels_last is not None
-    return "curv_persample_pack" if plain else "curv_persample_pack_ex"
 
 
 def _source_extent(t: torch.Tensor) -> int:
@@ -666,16 +651,12 @@ def _source_extent(t: torch.Tensor) -> int:
     return t.untyped_storage().nbytes() // t.element_size() - t.storage_offset()
 
 
-def _fill_pack(d, op: PerSampleOperand, dst: torch.Tensor, general: bool) -> None:
-    """Descriptor `d` (curv_persample_pack_desc, or curv_persample_pack_ex_desc when `general`) of `op` into `dst`: the
-    one place that fills either."""
+def _fill_pack(d, op: PerSampleOperand, dst: torch.Tensor) -> None:
+    """The curv_persample_pack_ex_desc `d` of `op` into `dst`."""
     geo = op.pack
     d.src, d.dst = op.src.data_ptr(), dst.data_ptr()
     _set_geometry(d, geo.shape, geo.kernel, geo.stride, geo.padding, geo.has_bias)
     d.rows_outer, d.Lp = int(op.rows_outer), op.Lp
-    if not general:
-        d.channels_last = int(geo.channels_last)
-        return
     d.s_n, d.s_c, d.s_h, d.s_w = geo.strides
     d.src_elems = _source_extent(op.src)
     d.dtype = _PACK_DTYPES[op.src.dtype]
@@ -686,9 +667,11 @@ def _fill_pack(d, op: PerSampleOperand, dst: torch.Tensor, general: bool) -> Non
 
 def per_sample_pack(operands: Sequence[PerSampleOperand], dsts: Sequence[torch.Tensor]) -> None:
     """The packed float32 copy of every operand into its `dst` (a float32 GPU buffer of `floats` values, 16-byte aligned),
-    all layers in at most one call of each entry point (`_pack_entry`)."""
-    routed = {"curv_persample_pack": [], "curv_persample_pack_ex": []}
-    for op, dst in zip(operands, dsts):
+    all layers in one call of curv_persample_pack_ex."""
+    if len(dsts) != len(operands):
+        raise RuntimeError(f"per_sample_pack: {len(operands)} operands, {len(dsts)} destinations")
+    arr = (_lib.curv_persample_pack_ex_desc * len(operands))()
+    for d, op, dst in zip(arr, operands, dsts):
         _require_gpu(dst)
         if not op.src.is_cuda:
             raise RuntimeError("curvature_amd runs on MI355X only: got a CPU tensor (no CPU fallback)")
@@ -696,15 +679,9 @@ def per_sample_pack(operands: Sequence[PerSampleOperand], dsts: Sequence[torch.T
             raise RuntimeError(f"per_sample_pack expects float32, bfloat16 or float16 sources, got {op.src.dtype}")
         if dst.numel() < op.floats:
             raise RuntimeError("per_sample_pack: destination too small")
-        routed[_pack_entry(op)].append((op, dst))
-    for name, items in routed.items():
-        if not items:
-            continue
-        general = name == "curv_persample_pack_ex"
-        arr = ((_lib.curv_persample_pack_ex_desc if general else _lib.curv_persample_pack_desc) * len(items))()
-        for d, (op, dst) in zip(arr, items):
-            _fill_pack(d, op, dst, general)
-        _lib.check(getattr(_lib.lib(), name)(_lib.stream_ptr(), arr, len(items)), name)
+        _fill_pack(d, op, dst)
+    if operands:
+        _lib.check(_lib.lib().curv_persample_pack_ex(_lib.stream_ptr(), arr, len(arr)), "curv_persample_pack_ex")
 
 
 class _PerSampleProduct:

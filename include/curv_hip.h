@@ -498,7 +498,11 @@ int curv_persample_plan_flops(const curv_persample_desc* descs, int n, long long
 int curv_persample_sq_accumulate(void* stream, const curv_persample_desc* descs, int n, void* workspace,
                                  size_t workspace_bytes);
 
-/* X of a layer, l-contiguous, into caller scratch `dst` - wherever the source cannot be read in place:
+/* The fp32-contiguous spelling of curv_persample_pack_ex below (an adapter over the same planner and kernel: float32,
+ * transposed = 0, strides (CHW, HW, W, 1) or with channels_last (HWC, 1, WC, C), src_elems = N*C*H*W; refusals read
+ * "curv_persample_pack: item <i>: ..."; beside the messages it always had, a src that is not 4-byte aligned is now
+ * refused, "src is not aligned to its 4-byte elements").  X of a layer, l-contiguous, into caller scratch `dst` - wherever the source
+ * cannot be read in place:
  *   dst[(n*R + r)*Lp + l]   (rows_outer = 0)   or   dst[(r*N + n)*Lp + l]   (rows_outer != 0: one R x (N Lp) matrix)
  * for r < R = C*kh*kw + has_bias, l < Lp, with L = Ho*Wo: row r = (c, a, b) is the implicit im2col of `src` (the
  * reference's F.unfold, curvatures.py:329-330), the last row the ones of a biased layer (:333-335), and every l in
@@ -520,7 +524,7 @@ typedef struct curv_persample_pack_desc {
 int curv_persample_pack(void* stream, const curv_persample_pack_desc* descs, int n);
 
 /* The general form of curv_persample_pack: the same destination (layout, ones row, zero tail, fp32, dst 16-byte aligned,
- * Lp a multiple of 4) from a source that the entry point above cannot express.
+ * Lp a multiple of 4) from a source of three dtypes, read through strides, forward or transposed.
  *   dtype       CURV_DTYPE_F32, CURV_DTYPE_BF16 or CURV_DTYPE_F16: half values are upcast by the pack (bf16 is its bit
  *               pattern shifted up 16 bits, fp16 the exact conversion: inf, NaN, -0 and subnormals survive).  A product
  *               of two bf16 or two fp16 values is exact in fp32, so the fp32 products on the upcast copy compute what a
@@ -528,8 +532,9 @@ int curv_persample_pack(void* stream, const curv_persample_pack_desc* descs, int
  *   s_n .. s_w  source strides in ELEMENTS: element (n, c, h, w) is src[n*s_n + c*s_c + h*s_h + w*s_w].  (N, C, H, W) is
  *               (CHW, HW, W, 1); the (N, T, D) input of a Linear layer is C = D, H = T, W = 1 with (TD, 1, D, -); the
  *               (T, N, E) record of an attention projection is C = E, H = T, W = 1 with (E, 1, NE, -).  Not negative.
- *   src_elems   the extent of the source in elements: the largest addressed offset must lie inside it, and it must
- *               hold fewer than 2^31 bytes.  Nothing outside it is read (a masked or padded element reads src[0]).
+ *   src_elems   the extent of the source in elements: the largest addressed offset must lie inside it.  It may be of
+ *               any size (s_n is used in 64 bits), but what one sample spans, (C-1)*s_c + (H-1)*s_h + (W-1)*s_w, must be
+ *               below 2^31 elements.  Nothing outside it is read (a masked or padded element reads src[0]).
  *   transposed  != 0: X of a ConvTranspose2d with output Ho x Wo (given; within the range output_size allows,
  *               [(H-1)s - 2p + k, (H-1)s - 2p + k + s - 1]): row r = (ci, a, b) at l = (oh, ow) is
  *               x[n, ci, (oh + ph - a)/sh, (ow + pw - b)/sw] where both divisions are exact and the result lies inside
@@ -539,7 +544,7 @@ int curv_persample_pack(void* stream, const curv_persample_pack_desc* descs, int
  * strides multiples of four elements, is read with one 8- or 16-byte load per four values; everything else gathers per
  * element.  One launch per 16 items of one dtype; an item's bits do not depend on the other items of the call.  Every item
  * is checked before anything is launched: invalid geometry, an unknown dtype, a transposed output size outside its range,
- * Lp, the element limits of curv_persample_pack and a source extent smaller than the largest offset return
+ * Lp, the element limits ("too large") and a source extent smaller than the largest offset return
  * CURV_ERR_INVALID with the item named.  An empty call is a no-op. */
 typedef struct curv_persample_pack_ex_desc {
   const void* src;

@@ -130,7 +130,8 @@ def test_operands_geometry():
     assert (s.g.ns, s.g.rs) == (52, 2 * 52) and (s.x.ns, s.x.rs) == (52, 2 * 52)
     lin = torch.nn.Linear(5, 3)
     s = ops.per_sample_operands(lin, torch.zeros(4, 7, 5), torch.zeros(4, 7, 3))
-    assert (s.N, s.m, s.n, s.L) == (4, 3, 6, 7) and s.x.pack[-1] and s.g.pack[-1]          # channels-last transposes
+    assert (s.N, s.m, s.n, s.L) == (4, 3, 6, 7)
+    assert s.x.pack.strides == (35, 1, 5, 1) and s.g.pack.strides == (21, 1, 3, 1)          # channels-last transposes
     s = ops.per_sample_operands(lin, torch.zeros(4, 5), torch.zeros(4, 3))
     assert (s.N, s.m, s.n, s.L) == (4, 3, 6, 1)
     with pytest.raises(RuntimeError, match="float16"):
@@ -194,7 +195,14 @@ def pack_desc(**kw):
 def test_invalid_pack_geometry_is_refused(bad):
     L = _lib.lib()
     assert L.curv_persample_pack(None, pack_desc(**bad), 1) == _lib.ERR_INVALID
-    assert b"item 0" in L.curv_last_error()
+    assert b"item 0" in L.curv_last_error() and b"null" not in L.curv_last_error()     # the geometry, not the addresses
+
+
+def test_a_sample_of_2_to_the_32_values_is_too_large():
+    big = pack_desc(N=1, C=1 << 16, H=1 << 8, W=1 << 8, kh=1, kw=1, ph=0, pw=0, Lp=1 << 16)
+    L = _lib.lib()
+    assert L.curv_persample_pack(None, big, 1) == _lib.ERR_INVALID
+    assert b"curv_persample_pack: item 0: too large" in L.curv_last_error()
 
 
 def test_compute_factors_accepts_per_sample():

@@ -1,6 +1,6 @@
 """The per-sample operand step for half-precision records, ConvTranspose2d and attention projections, without a GPU:
-the ABI of curv_persample_pack_ex, what `ops.per_sample_operands` makes of each kind of record (sizes, strides, scratch
-and the entry point that packs it), the shapes the attention tap records, and the refusals that stay.  The wider line is
+the ABI of curv_persample_pack_ex, what `ops.per_sample_operands` makes of each kind of record (sizes, strides and
+scratch), the descriptor `ops._fill_pack` writes, the shapes the attention tap records, and the refusals that stay.  The wider line is
 opt-in (`ops.widen_per_sample`): every test here runs with it on, except the one that checks what off means."""
 import ctypes
 import os
@@ -15,7 +15,6 @@ from curvature_amd import _lib, ops
 from curvature_amd.curvatures import EFB, KFAC, AttentionProjection, Diagonal
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-OLD, NEW = "curv_persample_pack", "curv_persample_pack_ex"
 
 
 @pytest.fixture(autouse=True)
@@ -33,9 +32,9 @@ def geometry(op):
 def test_pack_ex_is_declared_bound_and_additive():
     header = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "curv_hip.h")).read(), flags=re.S)
     assert re.search(r"\bint\s+curv_persample_pack_ex\s*\(", header)
-    assert NEW in _lib.SIGNATURES and OLD in _lib.SIGNATURES
+    assert "curv_persample_pack_ex" in _lib.SIGNATURES and "curv_persample_pack" in _lib.SIGNATURES
     handle = _lib.lib()
-    assert hasattr(handle, NEW)
+    assert hasattr(handle, "curv_persample_pack_ex")
     assert handle.curv_version() == 12 == _lib.ABI_VERSION
     assert (_lib.DTYPE_F32, _lib.DTYPE_BF16, _lib.DTYPE_F16) == (0, 1, 2)
     assert handle.curv_persample_pack_ex(None, None, 0) == 0                  # an empty call is a no-op
@@ -58,7 +57,7 @@ def test_descriptor_sizes_match_the_header(tmp_path):
 
 # ------------------------------------------------------------------------------------------------ operands
 def test_conv2d_fp32_is_what_it_was():
-    """The values the parent commit gives (hard-coded), and the old entry point for every packed operand."""
+    """The values of the float32 line before it was widened (hard-coded)."""
     conv = torch.nn.Conv2d(8, 16, 1, bias=False)
     s = ops.per_sample_operands(conv, torch.zeros(2, 8, 4, 4), torch.zeros(2, 16, 4, 4))
     assert (s.N, s.m, s.n, s.L) == (2, 16, 8, 16)
@@ -69,21 +68,20 @@ def test_conv2d_fp32_is_what_it_was():
     assert (s.N, s.m, s.n, s.L) == (2, 16, 73, 49)
     assert geometry(s.g) == (16, 49, 52, 16 * 52, 52, 2 * 16 * 52)
     assert geometry(s.x) == (73, 49, 52, 73 * 52, 52, 2 * 73 * 52)
-    assert ops._pack_entry(s.g) == OLD and ops._pack_entry(s.x) == OLD
+    assert s.g.pack.strides == (16 * 49, 49, 7, 1) and s.x.pack.strides == (8 * 49, 49, 7, 1)
     s = ops.per_sample_operands(conv, torch.zeros(2, 8, 7, 7), torch.zeros(2, 16, 7, 7), rows_outer=True, in_place=False)
     assert geometry(s.g) == (16, 49, 52, 52, 104, 2 * 16 * 52) and geometry(s.x) == (73, 49, 52, 52, 104, 2 * 73 * 52)
-    assert ops._pack_entry(s.g) == OLD and ops._pack_entry(s.x) == OLD
     lin = torch.nn.Linear(5, 3)
     s = ops.per_sample_operands(lin, torch.zeros(4, 7, 5), torch.zeros(4, 7, 3))
     assert (s.N, s.m, s.n, s.L) == (4, 3, 6, 7)
     assert geometry(s.x) == (6, 7, 8, 48, 8, 4 * 6 * 8) and geometry(s.g) == (3, 7, 8, 24, 8, 4 * 3 * 8)
-    assert ops._pack_entry(s.g) == OLD and ops._pack_entry(s.x) == OLD and s.x.pack.channels_last is True
+    assert s.x.pack.strides == (7 * 5, 1, 5, 1) and s.g.pack.strides == (7 * 3, 1, 3, 1)     # (N, H, W, C): (HWC, 1, WC, C)
     s = ops.per_sample_operands(lin, torch.zeros(4, 5), torch.zeros(4, 3))
     assert (s.N, s.m, s.n, s.L) == (4, 3, 6, 1) and geometry(s.x) == (6, 1, 4, 24, 4, 4 * 6 * 4)
-    assert ops._pack_entry(s.x) == OLD and s.x.pack.channels_last is True and s.g.pack.channels_last is True
+    assert s.x.pack.strides == (5, 1, 5, 1) and s.g.pack.strides == (3, 1, 3, 1)              # (N, H, W, C) with H = W = 1
     s = ops.per_sample_operands(lin, torch.zeros(4, 5), torch.zeros(4, 3))
     assert (s.N, s.m, s.n, s.L) == (4, 3, 6, 1) and geometry(s.x) == (6, 1, 4, 24, 4, 4 * 6 * 4)
-    assert ops._pack_entry(s.x) == OLD and s.x.pack.channels_last is True and s.g.pack.channels_last is True
+    assert s.x.pack.strides == (5, 1, 5, 1) and s.g.pack.strides == (3, 1, 3, 1)              # (N, H, W, C) with H = W = 1
 
 
 @pytest.mark.parametrize("half", [torch.bfloat16, torch.float16])
@@ -93,9 +91,8 @@ def test_a_half_side_is_packed_where_fp32_is_read_in_place(half):
     s = ops.per_sample_operands(conv, x, g.to(half))                          # the stem of an autocast model
     assert s.x.pack is None and geometry(s.x) == (8, 16, 16, 128, 16, 0)
     assert s.g.pack is not None and geometry(s.g) == (16, 16, 16, 256, 16, 2 * 16 * 16) and s.g.src.dtype == half
-    assert ops._pack_entry(s.g) == NEW
     s = ops.per_sample_operands(conv, x.to(half), g)
-    assert s.g.pack is None and s.x.pack is not None and ops._pack_entry(s.x) == NEW
+    assert s.g.pack is None and s.x.pack is not None and s.x.src.dtype == half
     assert geometry(s.x) == (8, 16, 16, 128, 16, 2 * 8 * 16)
 
 
@@ -104,9 +101,41 @@ def test_views_are_not_copied():
     x = torch.zeros(2, 4, 4, 8).permute(0, 3, 1, 2)                           # channels-last memory
     g = torch.zeros(2, 16, 4, 8)[:, :, :, ::2]
     s = ops.per_sample_operands(conv, x, g)
-    assert s.x.src.data_ptr() == x.data_ptr() and s.x.pack.strides == (128, 1, 32, 8) and ops._pack_entry(s.x) == OLD
-    assert s.g.src.data_ptr() == g.data_ptr() and s.g.pack.strides == (512, 32, 8, 2) and ops._pack_entry(s.g) == NEW
-    assert s.g.pack.channels_last is None and geometry(s.g) == (16, 16, 16, 256, 16, 512)
+    assert s.x.src.data_ptr() == x.data_ptr() and s.x.pack.strides == (128, 1, 32, 8)   # (HWC, 1, WC, C)
+    assert s.g.src.data_ptr() == g.data_ptr() and s.g.pack.strides == (512, 32, 8, 2)  # neither layout's
+    assert geometry(s.g) == (16, 16, 16, 256, 16, 512)
+
+
+def filled(op):
+    """Every field of the curv_persample_pack_ex_desc `ops._fill_pack` writes for `op`, but the two addresses."""
+    d = _lib.curv_persample_pack_ex_desc()
+    dst = torch.zeros(op.floats)
+    ops._fill_pack(d, op, dst)
+    assert (d.src, d.dst) == (op.src.data_ptr(), dst.data_ptr()) and d.reserved == 0
+    return dict(shape=(d.N, d.C, d.H, d.W), strides=(d.s_n, d.s_c, d.s_h, d.s_w), src_elems=d.src_elems, dtype=d.dtype,
+                window=(d.kh, d.kw, d.sh, d.sw, d.ph, d.pw), has_bias=d.has_bias, transposed=d.transposed,
+                out=(d.Ho, d.Wo), Lp=d.Lp, rows_outer=d.rows_outer)
+
+
+def test_fill_pack_writes_every_field():
+    conv = torch.nn.Conv2d(8, 16, 3, padding=1)
+    s = ops.per_sample_operands(conv, torch.zeros(2, 8, 7, 7), torch.zeros(2, 16, 7, 7))
+    assert filled(s.x) == dict(shape=(2, 8, 7, 7), strides=(392, 49, 7, 1), src_elems=784, dtype=_lib.DTYPE_F32,
+                               window=(3, 3, 1, 1, 1, 1), has_bias=1, transposed=0, out=(0, 0), Lp=52, rows_outer=0)
+    lin = torch.nn.Linear(5, 3)
+    s = ops.per_sample_operands(lin, torch.zeros(4, 7, 5), torch.zeros(4, 7, 3), rows_outer=True, in_place=False)
+    assert filled(s.x) == dict(shape=(4, 5, 7, 1), strides=(35, 1, 5, 1), src_elems=140, dtype=_lib.DTYPE_F32,
+                               window=(1, 1, 1, 1, 0, 0), has_bias=1, transposed=0, out=(0, 0), Lp=8, rows_outer=1)
+    conv = torch.nn.Conv2d(8, 16, 1, bias=False)
+    whole = torch.zeros(3, 16, 4, 4, dtype=torch.bfloat16)
+    s = ops.per_sample_operands(conv, torch.zeros(2, 8, 4, 4), whole[1:])     # a view: the extent counts from its start
+    assert filled(s.g) == dict(shape=(2, 16, 4, 4), strides=(256, 16, 4, 1), src_elems=512, dtype=_lib.DTYPE_BF16,
+                               window=(1, 1, 1, 1, 0, 0), has_bias=0, transposed=0, out=(0, 0), Lp=16, rows_outer=0)
+    convt = torch.nn.ConvTranspose2d(4, 3, 4, 2, 1)
+    x = torch.zeros(2, 4, 5, 6)
+    s = ops.per_sample_operands(convt, x, torch.zeros_like(convt(x)))
+    assert filled(s.x) == dict(shape=(2, 4, 5, 6), strides=(120, 30, 6, 1), src_elems=240, dtype=_lib.DTYPE_F32,
+                               window=(4, 4, 2, 2, 1, 1), has_bias=1, transposed=1, out=(10, 12), Lp=120, rows_outer=0)
 
 
 CONVT = {
@@ -131,9 +160,9 @@ def test_conv_transpose_operands(name):
     assert (s.N, s.m, s.n, s.L) == (2, 3, 4 * kh * kw + 1, L) and L % 4 == 0
     assert s.g.pack is None and geometry(s.g) == (3, L, L, 3 * L, L, 0)       # fp32, whole 16-byte groups: in place
     assert geometry(s.x) == (s.n, L, L, s.n * L, L, 2 * s.n * L)
-    assert s.x.pack.out_size == (Ho, Wo) and ops._pack_entry(s.x) == NEW
+    assert s.x.pack.out_size == (Ho, Wo)
     s = ops.per_sample_operands(layer, x, g.bfloat16(), rows_outer=True, in_place=False)
-    assert geometry(s.g) == (3, L, L, L, 2 * L, 2 * 3 * L) and ops._pack_entry(s.g) == NEW
+    assert geometry(s.g) == (3, L, L, L, 2 * L, 2 * 3 * L) and s.g.src.dtype == torch.bfloat16
     assert geometry(s.x) == (s.n, L, L, L, 2 * L, 2 * s.n * L)
 
 
@@ -146,7 +175,7 @@ def test_attention_projection_operands():
     assert geometry(s.x) == (E + 1, T, 8, 9 * 8, 8, N * 9 * 8) and geometry(s.g) == (3 * E, T, 8, 24 * 8, 8, N * 24 * 8)
     assert s.x.pack.shape == (N, E, T, 1) and s.x.pack.strides[:3] == (E, 1, N * E)        # the sample is the middle index
     assert s.g.pack.shape == (N, 3 * E, T, 1) and s.g.pack.strides[:3] == (3 * E, 1, N * 3 * E)
-    assert s.x.src.data_ptr() == x.data_ptr() and ops._pack_entry(s.x) == NEW and ops._pack_entry(s.g) == NEW
+    assert s.x.src.data_ptr() == x.data_ptr()
     x2, g2 = torch.zeros(T * N, E), torch.zeros(T * N, E)
     s = ops.per_sample_operands(proj_out, x2, g2, samples=N)
     assert (s.N, s.m, s.n, s.L) == (N, E, E + 1, T)

@@ -532,40 +532,58 @@ def test_off_by_default(gpu):
 
 # ------------------------------------------------------------------------------------------------ 4. unchanged ground
 def test_fp32_lenet_is_bit_identical_through_the_general_pack(gpu, monkeypatch):
-    """The old entry point is still the default for what it can express, and the general kernel's forward fp32 path
-    writes the same bits: LeNet-5 `Diagonal(per_sample=True).update` and `glm_predictive`, default route against every
-    operand forced to curv_persample_pack_ex."""
+    """One route: LeNet-5 `Diagonal(per_sample=True).update`, `invert` and `glm_predictive` call curv_persample_pack_ex
+    once per `ops.per_sample_pack` and never curv_persample_pack - whose adapter writes the same bits for every packed
+    operand of the model."""
     from curvature_amd import _lib, models, ops
     from curvature_amd.curvatures import Diagonal
     from curvature_amd.evaluate import glm_predictive
     torch.manual_seed(0)
     model = models.lenet5().to(gpu)
     x, labels = torch.randn(8, 1, 28, 28, device=gpu), torch.randint(0, 10, (8,), device=gpu)
-    calls = {"curv_persample_pack": 0, "curv_persample_pack_ex": 0}
+    calls = {"curv_persample_pack": 0, "curv_persample_pack_ex": 0, "per_sample_pack": 0}
     handle = _lib.lib()
-    for name in calls:
+    direct = handle.curv_persample_pack
+    for name in ("curv_persample_pack", "curv_persample_pack_ex"):
         def counted(*args, _name=name, _original=getattr(handle, name)):
             calls[_name] += 1
             return _original(*args)
         monkeypatch.setattr(handle, name, counted, raising=False)
+    layouts, original = [], ops.per_sample_pack
 
-    def run():
-        est = Diagonal(model, per_sample=True)
-        model.zero_grad()
-        F.cross_entropy(model(x), labels).backward()
-        est.update(8)
-        est.invert(add=0.5, multiply=2.0)
-        _, variance, probs = glm_predictive(model, est, x, outputs=[0, 7])
-        for hook in est.hooks:
-            hook.remove()
-        return [est.state[l].clone() for l in est.state], variance, probs
-    states, variance, probs = run()
-    assert calls["curv_persample_pack"] > 0 and calls["curv_persample_pack_ex"] == 0
-    before = dict(calls)
-    monkeypatch.setattr(ops, "_pack_entry", lambda op: "curv_persample_pack_ex")
-    states_ex, variance_ex, probs_ex = run()
-    assert calls["curv_persample_pack"] == before["curv_persample_pack"]
-    assert calls["curv_persample_pack_ex"] == before["curv_persample_pack"]   # call for call
-    for a, b in zip(states, states_ex):
-        assert torch.equal(a, b)
-    assert torch.equal(variance, variance_ex) and torch.equal(probs, probs_ex)
+    def through_the_adapter(op):
+        """`op` packed by curv_persample_pack itself, and whether its source is (N, H, W, C)."""
+        geo = op.pack
+        N, C, H, W = geo.shape
+        nhwc = geo.strides[1] == 1 and (C > 1 or H * W == 1)
+        assert op.src.dtype == torch.float32 and geo.out_size is None
+        assert all(d == 1 or s == w for d, s, w in
+                   zip(geo.shape, geo.strides, (H * W * C, 1, W * C, C) if nhwc else (C * H * W, H * W, W, 1)))
+        arr = (_lib.curv_persample_pack_desc * 1)()
+        d = arr[0]
+        dst = torch.full((op.floats,), float("nan"), device=gpu)
+        d.src, d.dst = op.src.data_ptr(), dst.data_ptr()
+        d.N, d.C, d.H, d.W = geo.shape
+        (d.kh, d.kw), (d.sh, d.sw), (d.ph, d.pw) = geo.kernel, geo.stride, geo.padding
+        d.has_bias, d.channels_last, d.rows_outer, d.Lp = int(geo.has_bias), int(nhwc), int(op.rows_outer), op.Lp
+        assert direct(_lib.stream_ptr(), arr, 1) == 0, handle.curv_last_error()
+        return dst, nhwc
+
+    def recorded(operands, dsts):
+        calls["per_sample_pack"] += bool(operands)             # (an empty call makes no library call)
+        original(operands, dsts)
+        for op, wrote in zip(operands, dsts):
+            again, nhwc = through_the_adapter(op)
+            assert torch.equal(again.view(torch.int32), wrote[:op.floats].view(torch.int32))
+            layouts.append(nhwc)
+    monkeypatch.setattr(ops, "per_sample_pack", recorded)
+    est = Diagonal(model, per_sample=True)
+    F.cross_entropy(model(x), labels).backward()
+    est.update(8)
+    est.invert(add=0.5, multiply=2.0)
+    glm_predictive(model, est, x, outputs=[0, 7])
+    for hook in est.hooks:
+        hook.remove()
+    assert calls["per_sample_pack"] >= 2 and calls["curv_persample_pack_ex"] == calls["per_sample_pack"]
+    assert calls["curv_persample_pack"] == 0
+    assert layouts.count(True) >= 6 and layouts.count(False) >= 2            # three Linear layers, two Conv2d inputs

@@ -168,8 +168,8 @@ def test_forward_geometries_bit_for_bit(gpu, case, dtype, rows_outer, bias):
     want = item.expected()
     assert not bool(torch.isnan(want).any())
     assert same_bits(got, want)
-    if dtype == "bf16" and old_form is not None:
-        # the upcast copy through the OLD entry point: the same bits
+    if dtype in ("bf16", "fp32") and old_form is not None:
+        # the (upcast) contiguous copy through curv_persample_pack, the fp32-contiguous spelling: the same bits
         copy = view.float().contiguous(memory_format=torch.channels_last if old_form else torch.contiguous_format)
         assert same_bits(got, pack_old(copy, item, gpu, old_form))
 
@@ -232,6 +232,28 @@ def test_half_special_values_survive(gpu, dtype, lead):
     assert int(nan.sum()) == 1 and torch.equal(torch.isnan(got), nan)         # NaN compared as NaN
     assert same_bits(got[~nan], want[~nan])                                   # -0.0, subnormals and inf by their bits
     assert float(want[7]) != 0.0 and bool(torch.signbit(got[2]))
+
+
+@pytest.mark.parametrize("lead", [64, 65], ids=["vector", "gather"])
+def test_sample_base_is_formed_in_64_bits(gpu, lead):
+    """fp16, N = 3 samples of (2, 4, 4) values 2^31 + 8 elements apart in a buffer that is never filled: sample 1 lies
+    where a signed 32-bit product wraps, sample 2 (at 2^32 + 16) where an unsigned one does.  Elements 0 and 16, where a
+    wrapped product lands, hold NaNs (as values of sample 0), and NaNs follow sample 0."""
+    free, _ = torch.cuda.mem_get_info()
+    if free < 10 << 30:
+        pytest.skip(f"an 8 GiB source needs 10 GiB of free device memory, {free >> 20} MiB are free")
+    s_n = (1 << 31) + 8
+    buf = torch.empty(lead + 2 * s_n + 32, dtype=torch.float16, device=gpu)
+    view = buf[lead:].as_strided((3, 2, 4, 4), (s_n, 16, 4, 1))
+    values = ((torch.arange(96) - 40) * 0.25).half().view(3, 2, 4, 4)         # distinct, exact in fp16
+    values[0, 0, 0, 0] = values[0, 1, 0, 0] = float("nan")                    # elements 0 and 16
+    for n in range(3):                                                        # only the three samples are written
+        view[n].copy_(values[n])
+    buf[lead + 32:lead + 96] = float("nan")
+    rc, (got,) = pack_ex([Item(view)], gpu)
+    assert rc == 0, _lib.lib().curv_last_error()
+    want = values.float().reshape(-1)
+    assert int(torch.isnan(want).sum()) == 2 and same_bits(got, want)         # the upcast NaNs by their bits as well
 
 
 def test_alone_and_in_a_batch_of_twenty(gpu):

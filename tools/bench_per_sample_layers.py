@@ -5,9 +5,10 @@
 
 HIP events around `update()`, median of `--reps` calls after two warm-up calls (as tools/bench_per_sample.py).
 
-  half   ResNet-50, N = 32, 224 x 224, bf16 autocast.  `update()` on the recorded bf16 / fp32 tensors (the general pack
-         upcasts them) against the route there was before it: `.float()` copies of the same records, made inside the
-         timed region, through the fp32 path (curv_persample_pack, in-place reads).  `--runs` alternated runs of each.
+  half   ResNet-50, N = 32, 224 x 224, bf16 autocast.  `update()` on the recorded bf16 / fp32 tensors (the pack upcasts
+         them) against the route there was before half records were taken: `.float()` copies of the same records, made
+         inside the timed region, then the float32 instantiation of the same pack and in-place reads.  `--runs`
+         alternated runs of each.
          The split of pack against product comes from a kernel trace of this script with ``--part half``.
   convt  every ConvTranspose2d of the DCGAN generator (N = 64) and of the U-Net (N = 8, 256 x 256), one layer per call,
          against torch doing what a user would write: zero-stuff, `F.unfold`, `bmm`, square, sum.  Beside the time the
