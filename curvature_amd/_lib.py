@@ -13,7 +13,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc")
 INCLUDE = os.path.normpath(os.path.join(_HERE, "..", "include"))
 LIB_PATH = os.path.join(CSRC, "libcurv_hip.so")
-SOURCES = ["api.cpp", "collective.cpp", "elementwise.hip", "syrk.hip", "syrk_flat.hip", "syrk_corr.hip", "syrk_pre.hip", "syrk_small.hip", "group_factor.hip", "kfac_half.hip", "convt_factor.hip", "persample.hip", "logit_mc.hip", "invert.hip", "gemm.hip", "inf.hip", "eigh.hip", "eigh_lowrank.hip"]
+SOURCES = ["api.cpp", "collective.cpp", "elementwise.hip", "syrk.hip", "syrk_flat.hip", "syrk_corr.hip", "syrk_pre.hip", "syrk_small.hip", "group_factor.hip", "kfac_half.hip", "convt_factor.hip", "persample.hip", "persample_dw.hip", "logit_mc.hip", "invert.hip", "gemm.hip", "inf.hip", "eigh.hip", "eigh_lowrank.hip"]
 HIPCC_FLAGS = ["-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC", "-shared", "-Wall",
                "-Wno-unused-function", "-ldl"]
 
@@ -223,6 +223,18 @@ class curv_persample_pack_ex_desc(ctypes.Structure):
                [(k, ctypes.c_int32) for k in ("Ho", "Wo", "has_bias", "dtype", "transposed", "rows_outer", "Lp", "reserved")]
 
 
+class curv_persample_dw_desc(ctypes.Structure):
+    """Mirror of ``curv_persample_dw_desc`` in include/curv_hip.h."""
+    _fields_ = [("x", ctypes.c_void_p), ("g", ctypes.c_void_p)] + \
+               [(k, ctypes.c_longlong) for k in ("x_sn", "x_sc", "x_sh", "x_sw", "x_elems",
+                                                 "g_sn", "g_sc", "g_sh", "g_sw", "g_elems")] + _SOURCE + _WINDOW + \
+               [(k, ctypes.c_int32) for k in ("Ho", "Wo", "has_bias", "first")] + [("alpha", ctypes.c_float),
+                                                                                   ("reserved", ctypes.c_int32)] + \
+               [("dst", ctypes.c_void_p), ("c_rs", ctypes.c_longlong)] + \
+               [(k, ctypes.c_void_p) for k in ("T", "Wt", "s", "out")] + \
+               [(k, ctypes.c_longlong) for k in ("t_cs", "t_rs", "w_rs", "o_stride")]
+
+
 class curv_copy_desc(ctypes.Structure):
     _fields_ = [("dst", ctypes.c_void_p), ("src", ctypes.c_void_p), ("bytes", ctypes.c_ulonglong)]
 
@@ -314,6 +326,11 @@ SIGNATURES = {
     "curv_persample_cov_workspace_bytes": (_sz, [ctypes.POINTER(curv_persample_cov_desc), _i]),
     "curv_persample_cov_plan_flops": (_i, [ctypes.POINTER(curv_persample_cov_desc), _i, ctypes.POINTER(ctypes.c_longlong)]),
     "curv_persample_cov_reduce": (_i, [_vp, ctypes.POINTER(curv_persample_cov_desc), _i, _vp, _sz]),
+    "curv_persample_dw_workspace_bytes": (_sz, [ctypes.POINTER(curv_persample_dw_desc), _i]),
+    "curv_persample_dw_plan_info": (_i, [ctypes.POINTER(curv_persample_dw_desc), _i, ctypes.POINTER(ctypes.c_longlong),
+                                        ctypes.POINTER(ctypes.c_longlong)]),
+    "curv_persample_dw_sq_accumulate": (_i, [_vp, ctypes.POINTER(curv_persample_dw_desc), _i, _vp, _sz]),
+    "curv_persample_dw_quad_reduce": (_i, [_vp, ctypes.POINTER(curv_persample_dw_desc), _i, _vp, _sz]),
     "curv_logit_mc_workspace_bytes": (_sz, [ctypes.POINTER(curv_logit_mc_desc), _i]),
     "curv_logit_mc_plan_flops": (_i, [ctypes.POINTER(curv_logit_mc_desc), _i, ctypes.POINTER(ctypes.c_longlong)]),
     "curv_logit_mc": (_i, [_vp, ctypes.POINTER(curv_logit_mc_desc), _i, _vp, _sz]),

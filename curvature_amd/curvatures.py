@@ -496,6 +496,8 @@ class Curvature(ABC):
         return params, tuple(map(ptr, params)), tuple(map(ptr, mean))
 
     # ------------------------------------------------------------------ recording hooks (KFAC; per-sample Diagonal / EFB)
+    _per_sample_groups = False       # Diagonal, KFAC: grouped convolutions have a per-sample form (ops.admit_grouped_per_sample)
+
     def _record_layer(self, layer) -> None:
         """Record `layer`'s input (by reference) and raw grad_output into ``self.record[layer]`` at every pass."""
         self.record[layer] = [None, None]
@@ -515,13 +517,16 @@ class Curvature(ABC):
     def _save_output(self, module, grad_output):
         self.record[module][1] = grad_output         # raw; the reference stores grad * N (curvatures.py:310)
 
-    def _per_sample_layers(self, what: str, advice: str) -> List[Module]:
+    def _per_sample_layers(self, what: str, advice: str, grouped: bool = False) -> List[Module]:
         """The selected layers, in ``modules()`` order, after checking that every one has a per-sample form P_n = g_n X_n^T:
         Linear, and Conv2d with groups 1, dilation 1 and integer padding; with `ops.widen_per_sample` also ConvTranspose2d
         under the same restrictions and, for the estimators that treat a MultiheadAttention module as its two projections
-        (KFAC, EFB), those two `AttentionProjection`s.  Any other raises NotImplementedError naming it."""
+        (KFAC, EFB), those two `AttentionProjection`s.  Any other raises NotImplementedError naming it.  `grouped`: the
+        caller takes grouped Conv2d layers (`ops.per_sample_route`: as group slices or by the depthwise kernel); they
+        pass only with `ops.admit_grouped_per_sample` on, and a caller that does not take them then says who does."""
         names = {mod: name for name, mod in self.model.named_modules()}
         wide = ops.per_sample_is_wide()
+        groups_on = ops.per_sample_admits_groups()
         layers = []
         for layer in self.model.modules():
             kind = layer.__class__.__name__
@@ -529,8 +534,10 @@ class Curvature(ABC):
                 continue
             why = None
             if kind == 'Conv2d' or (kind == 'ConvTranspose2d' and wide):
-                if int(layer.groups) != 1:
+                if int(layer.groups) != 1 and not (grouped and groups_on and kind == 'Conv2d'):
                     why = f"grouped convolution (groups={layer.groups})"
+                    if groups_on and kind == 'Conv2d':
+                        why += "; Diagonal(per_sample=True) and functional_variance take it"
                 elif tuple(layer.dilation) != (1, 1):
                     why = "dilated convolution"
                 elif not all(isinstance(p, int) for p in layer.padding):
@@ -551,7 +558,8 @@ class Curvature(ABC):
         self.hooks = list()
         self.record = dict()
         self._out_size = dict()
-        for layer in self._per_sample_layers(f"{what}(per_sample=True)", "select other layer types or use per_sample=False"):
+        for layer in self._per_sample_layers(f"{what}(per_sample=True)", "select other layer types or use per_sample=False",
+                                             grouped=self._per_sample_groups):
             if not isinstance(layer, AttentionProjection):
                 self._record_layer(layer)
                 continue
@@ -560,6 +568,23 @@ class Curvature(ABC):
                 tap = _LinearTap(self, layer.module)
                 self.hooks.append(layer.module.register_forward_pre_hook(tap.install))
                 self.hooks.append(layer.module.register_forward_hook(tap.remove, always_call=True))
+
+    def _records_of(self, what: str, layer):
+        """(input, grad_output) recorded for `layer` - for an `ops.GroupSlice`, or a grouped layer itself, those of the
+        grouped layer, which must be float32 (RuntimeError naming the layer and the dtype otherwise)."""
+        module = layer.layer if isinstance(layer, ops.GroupSlice) else layer
+        forward, backward = self.record[module]
+        if forward is None or backward is None:
+            raise RuntimeError(f"{what}.update: no recorded forward/backward pass for a selected layer")
+        if _groups_of(module) > 1:
+            name = next((f"'{name}'" for name, mod in self.model.named_modules() if mod is module), repr(module))
+            for t in (forward, backward):
+                fault = ops.grouped_dtype_fault(name, t)
+                if fault:
+                    raise RuntimeError(fault)
+                if not t.is_cuda:
+                    raise RuntimeError("curvature_amd runs on MI355X only: got a CPU tensor (no CPU fallback)")
+        return forward, backward
 
     def _per_sample_operands(self, what: str, layers, x_side: bool = True, **layout):
         """The per-sample operands of `layers` from their records, packed where they cannot be read in place:
@@ -571,9 +596,7 @@ class Curvature(ABC):
         valid."""
         sides = []
         for layer in layers:
-            forward, backward = self.record[layer]
-            if forward is None or backward is None:
-                raise RuntimeError(f"{what}.update: no recorded forward/backward pass for a selected layer")
+            forward, backward = self._records_of(what, layer)
             for t in (forward, backward):
                 fault = ops.per_sample_dtype_fault(f"{what}.update(per_sample=True)", t)
                 if fault:
@@ -634,7 +657,10 @@ class Curvature(ABC):
         drops it, as `evaluate.glm_predictive` does.  Linear and Conv2d (groups 1, dilation 1, integer padding) with
         float32 GPU records; with `ops.widen_per_sample` also ConvTranspose2d, for KFAC and EFB the two projections of a
         MultiheadAttention module, and bfloat16 / float16 records (a model run under ``torch.autocast``: the pack upcasts
-        them, all sums are float32).  Other selected layers raise NotImplementedError, as does a layer-sharded estimator.
+        them, all sums are float32).  With `ops.admit_grouped_per_sample`, for KFAC and Diagonal, also Conv2d with
+        ``groups > 1`` (float32 records): one product per group on channel slices of the records, or the direct kernel of
+        csrc/persample_dw.hip for a depthwise layer, which keeps no X side - its recorded input is read again
+        (`ops.per_sample_route`).  Other selected layers raise NotImplementedError, as does a layer-sharded estimator.
         Implemented by KFAC, Diagonal and EFB.  No counterpart in the reference, which has the Monte-Carlo predictive only."""
         raise NotImplementedError(f"{type(self).__name__}.functional_variance: no linearised predictive for this estimator "
                                   "(KFAC, Diagonal and EFB have one)")
@@ -784,6 +810,7 @@ class Diagonal(LinearisedPredictive, Curvature):
     stream, so sampling them everywhere would leave the ranks with different attention weights)."""
 
     _supports_mha = True
+    _per_sample_groups = True
 
     def __init__(self, model: Union[Module, Sequential], layer_types: Union[List[str], str] = None, *, shard=None,
                  per_sample: bool = False):
@@ -795,7 +822,8 @@ class Diagonal(LinearisedPredictive, Curvature):
         per-sample quantities are defined from that pass's records, not from N separate passes.  Linear and Conv2d
         (groups 1, dilation 1, integer padding) with float32 records; any other selected layer raises
         NotImplementedError here.  `ops.widen_per_sample` adds ConvTranspose2d and bfloat16 / float16 records
-        (MultiheadAttention stays refused: the state for it here is not one matrix per projection)."""
+        (MultiheadAttention stays refused: the state for it here is not one matrix per projection);
+        `ops.admit_grouped_per_sample` adds Conv2d with ``groups > 1`` (float32 records; `ops.per_sample_route`)."""
         super().__init__(model, layer_types, shard=shard)
         self.per_sample = bool(per_sample)
         if self.per_sample:
@@ -805,19 +833,29 @@ class Diagonal(LinearisedPredictive, Curvature):
         layers = [l for _, l in self._owned()]
         if not layers:
             return
-        operands = self._per_sample_operands("Diagonal", layers)
-        new = [(l, s) for l, (s, _, _) in zip(layers, operands) if l not in self.state]
+        # a grouped layer (ops.admit_grouped_per_sample) enters as its group slices - products of their own into row
+        # blocks of the layer's state - or, a true depthwise one, through the direct kernel
+        direct = [l for l in layers if ops.per_sample_route(l) == "depthwise"]
+        items = ops.per_sample_items([l for l in layers if l not in direct])
+        operands = self._per_sample_operands("Diagonal", items) if items else []
+        records = {l: self._records_of("Diagonal", l) for l in direct}
+        device = operands[0][1].device if operands else records[direct[0]][0].device
+        new = [l for l in layers if l not in self.state]
         fresh = {}
         if new:
-            self._state_arena = _Arena([(s.m, s.n) for _, s in new], operands[0][1].device)
-            fresh = {l: v for (l, _), v in zip(new, self._state_arena.views)}
+            self._state_arena = _Arena([(_wm_rows(l), l.weight.numel() // _wm_rows(l) + int(l.bias is not None))
+                                        for l in new], device)
+            fresh = dict(zip(new, self._state_arena.views))
+        state = {l: fresh.get(l, self.state.get(l)) for l in layers}
         jobs = []
-        for layer, (sides, g, x) in zip(layers, operands):
-            dst = fresh.get(layer, self.state.get(layer))
+        for item, (sides, g, x) in zip(items, operands):
+            layer, dst = (item.layer, state[item.layer][item.rows]) if isinstance(item, ops.GroupSlice) else (item, state[item])
             jobs.append(ops.PerSampleJob.of(sides, g, x, dst, alpha=batch_size, first=layer in fresh))
-        ops.per_sample_sq_accumulate(jobs)                 # one product per layer, all layers in one call
-        for layer, job in zip(layers, jobs):
-            self.state[layer] = job.C
+        ops.per_sample_sq_accumulate(jobs)                 # one product per layer or slice, all in one call
+        ops.per_sample_dw_sq_accumulate([ops.PerSampleDwJob.of(l, *records[l], dst=state[l], alpha=batch_size,
+                                                               first=l in fresh) for l in direct])
+        for layer in layers:
+            self.state[layer] = state[layer]
 
     def update(self, batch_size: int):
         if self.per_sample:
@@ -906,8 +944,11 @@ class Diagonal(LinearisedPredictive, Curvature):
 
     def _predictive_terms(self) -> PredictiveTerms:
         # grid: inv**2 = 1 / (s state + n) = (1 / s) / (state + n / s)
-        return PredictiveTerms("Diagonal", basis=None, weights=lambda layer: self.inv_state[layer], grid_basis=None,
-                               spectrum=lambda layer: (None, None, self.state[layer]), separable=False)
+        def weights(layer):                                # (a group slice: its row block of the layer's matrix)
+            return self.inv_state[layer.layer][layer.rows] if isinstance(layer, ops.GroupSlice) else self.inv_state[layer]
+        return PredictiveTerms("Diagonal", basis=None, weights=weights, grid_basis=None,
+                               spectrum=lambda layer: (None, None, self.state[layer]), separable=False,
+                               direct=lambda layer: (None, self.inv_state[layer], None))
 
     def sample(self, layer: Union[Module, str], z: Optional[Tensor] = None) -> Tensor:
         assert self.inv_state, "Inverse state dict is empty. Did you call 'invert' prior to this?"
@@ -1088,6 +1129,7 @@ class KFAC(LinearisedPredictive, Curvature):
     factor N is folded into the scale of the G-side SYRK, which saves one pass over every gradient."""
 
     _mha_as_projections = True
+    _per_sample_groups = True
 
     def __init__(self, model: Union[Module, Sequential], layer_types: Union[List[str], str] = None, *, shard=None):
         super().__init__(model, layer_types, shard=shard)
@@ -1304,11 +1346,17 @@ class KFAC(LinearisedPredictive, Curvature):
         # L L^T = (sqrt(s) F + sqrt(n) I)^-1 = U diag(1 / (sqrt(s) (lambda + sqrt(n / s)))) U^T on both sides: the two
         # 1 / sqrt(s) make the gain 1 / s, and the shift of both spectra is sqrt(n / s)
         kept = getattr(self, "_decomposition", None)
+        def basis(layer):                                  # (a group slice: its pair of the stacked inverse factors)
+            if isinstance(layer, ops.GroupSlice):
+                return tuple(f[layer.g].t() for f in reversed(self.inv_state[layer.layer]))
+            return tuple(f.t() for f in reversed(self.inv_state[layer]))
         return PredictiveTerms(
-            "KFAC", basis=lambda layer: tuple(f.t() for f in reversed(self.inv_state[layer])), weights=None,
+            "KFAC", basis=basis, weights=None,
             grid_basis=lambda layer: kept[layer][:2], spectrum=lambda layer: (kept[layer][2], kept[layer][3], None),
             separable=True, grid_missing=None if kept is not None else
-            "no eigendecomposition of the current factors: call decompose() after the last update()")
+            "no eigendecomposition of the current factors: call decompose() after the last update()",
+            # depthwise (one output channel per group): T = L_A stacked (C, n_g, n_g), s = L_G stacked (C, 1, 1), in place
+            direct=lambda layer: (self.inv_state[layer][0], None, self.inv_state[layer][1]))
 
     def decompose(self) -> None:
         """The eigendecompositions F = U diag(lambda) U^T of the accumulated factors of every owned layer, in one batched

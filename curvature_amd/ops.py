@@ -547,6 +547,74 @@ def per_sample_dtype_fault(what: str, t) -> Optional[str]:
     return f"{what} expects float32" + (", bfloat16 or float16" if _WIDE else "") + f" records, got {t.dtype}"
 
 
+# Grouped and depthwise convolutions in the per-sample line are opt-in as well, by a switch of their own:
+# with it off - the default - selection, refusals and messages are exactly what they were, whatever `widen_per_sample` says.
+_GROUPS = False
+
+
+def admit_grouped_per_sample(enable: bool = True) -> bool:
+    """Switch grouped convolutions in the per-sample line on or off for the process; returns what it was.  On:
+    ``Diagonal(per_sample=True)`` and the `functional_variance` of Diagonal and KFAC take a Conv2d with ``groups > 1``
+    (dilation 1, integer padding, float32 records) by the route `per_sample_route` names.  Off: such a layer raises.
+    Independent of `widen_per_sample`."""
+    global _GROUPS
+    was, _GROUPS = _GROUPS, bool(enable)
+    return was
+
+
+def per_sample_admits_groups() -> bool:
+    return _GROUPS
+
+
+DW_MAX_TAPS = 49                       # kernel taps up to which a depthwise layer takes the direct kernel
+
+
+def per_sample_route(layer) -> str:
+    """How the per-sample products of `layer` are formed (host only; the one place that decides it): ``"whole"`` - one
+    product P_n = g_n X_n^T (every layer but a grouped Conv2d); ``"depthwise"`` - the direct kernel of
+    csrc/persample_dw.hip (in_channels == out_channels == groups, at most `DW_MAX_TAPS` kernel taps); ``"slices"`` - one
+    product per group on channel slices of the records (`GroupSlice`: every other grouped Conv2d)."""
+    if layer.__class__.__name__ != 'Conv2d' or int(layer.groups) == 1:
+        return "whole"
+    if layer.in_channels == layer.out_channels == int(layer.groups) and \
+            layer.kernel_size[0] * layer.kernel_size[1] <= DW_MAX_TAPS:
+        return "depthwise"
+    return "slices"
+
+
+class GroupSlice(NamedTuple):
+    """Group `g` of a grouped Conv2d `layer` as a layer of its own in the per-sample line (a pseudo-layer like
+    `AttentionProjection`; hashable, equal by (layer, g)): the convolution of the input channels
+    [g c_g, (g + 1) c_g) to the output channels [g m_g, (g + 1) m_g), rows [g m_g, (g + 1) m_g) of the layer matrix."""
+    layer: object
+    g: int
+
+    @property
+    def rows(self) -> slice:
+        m = self.layer.out_channels // int(self.layer.groups)
+        return slice(self.g * m, (self.g + 1) * m)
+
+    @staticmethod
+    def of(layer) -> list:
+        return [GroupSlice(layer, g) for g in range(int(layer.groups))]
+
+
+def per_sample_items(layers) -> list:
+    """`layers` with every grouped layer of the ``"slices"`` route replaced by its `GroupSlice`s, in group order."""
+    out = []
+    for layer in layers:
+        out.extend(GroupSlice.of(layer) if per_sample_route(layer) == "slices" else [layer])
+    return out
+
+
+def grouped_dtype_fault(name: str, t) -> Optional[str]:
+    """Why the record `t` of the grouped layer `name` cannot enter the per-sample line (None: it can): float32 only,
+    whatever `widen_per_sample` says."""
+    if t.dtype == torch.float32:
+        return None
+    return f"per-sample update: grouped convolution {name} expects float32 records, got {t.dtype}"
+
+
 _PACK_DTYPES = {torch.float32: _lib.DTYPE_F32, torch.bfloat16: _lib.DTYPE_BF16, torch.float16: _lib.DTYPE_F16}
 
 
@@ -596,7 +664,12 @@ def per_sample_operands(layer, x, g, rows_outer: bool = False, in_place: bool = 
     one product).  float32 records; with `widen_per_sample` each side float32, bfloat16 or float16 by its own dtype (an
     autocast ResNet-50 has a float32 stem input and a bfloat16 grad_output): a half side is always packed - the pack
     upcasts it - and never read in place.  Any other dtype raises RuntimeError.  Views are not copied: the pack reads
-    them through their strides."""
+    them through their strides.  A grouped Conv2d itself raises NotImplementedError; with `admit_grouped_per_sample` one
+    group of it, a `GroupSlice`, is a layer here (`_slice_operands`)."""
+    if isinstance(layer, GroupSlice):
+        if not _GROUPS:
+            raise NotImplementedError("per-sample update: unsupported layer GroupSlice")
+        return _slice_operands(layer, x.detach(), g.detach(), rows_outer, in_place)
     for t in (x, g):
         fault = per_sample_dtype_fault("per-sample update", t)
         if fault:
@@ -642,6 +715,52 @@ def per_sample_operands(layer, x, g, rows_outer: bool = False, in_place: bool = 
         g_op = _per_sample_operand(g, _pack_source(shape_g, strides_g), False, rows_outer)
     if g_op.L != x_op.L or g_op.rows != sides.m or x_op.rows != sides.n or Ng != N:
         raise RuntimeError(f"per-sample update: records of {kind} do not match the layer "
+                           f"(input {tuple(x.shape)}, grad_output {tuple(g.shape)})")
+    return PerSampleSides(g_op, x_op, sides.n, sides.m, N, x_op.L)
+
+
+def _slice_operands(item: GroupSlice, x, g, rows_outer: bool, in_place: bool) -> PerSampleSides:
+    """`per_sample_operands` of one group of a grouped Conv2d (`admit_grouped_per_sample`): the geometry of `factor_jobs`
+    with C = c_g and m = m_g on the channel slices of the two records, which are neither copied nor made contiguous.
+    The g side ``grad_output[:, g m_g:(g + 1) m_g]`` is read in place under the rule of every layer (float32 - the only dtype
+    a grouped layer takes -, the record contiguous, L % 4 == 0: the slice then starts on a 16-byte boundary), with the
+    record's own sample stride; otherwise the pack reads the view through its strides.  The x side is the view
+    ``x[:, g c_g:(g + 1) c_g]``: packed (its ones row written per slice), or read in place for a bias-free 1x1 / stride-1
+    layer.  An operand read in place has as `src` the flat run from the slice's first element to the record's end."""
+    layer, k = item.layer, int(item.g)
+    for t in (x, g):
+        fault = grouped_dtype_fault(repr(item), t)
+        if fault:
+            raise RuntimeError(fault)
+    if x.dim() != 4 or g.dim() != 4:
+        raise RuntimeError(f"per-sample update: records of Conv2d must be (N, C, H, W), got {tuple(x.shape)} and "
+                           f"{tuple(g.shape)}")
+    sides = factor_jobs(layer, ShapeOnly(tuple(x.shape)), ShapeOnly(tuple(g.shape)))
+    if not 0 <= k < sides.groups or x.shape[1] != layer.in_channels or g.shape[1] != layer.out_channels:
+        raise RuntimeError(f"per-sample update: records of {item!r} do not match the layer (input {tuple(x.shape)}, "
+                           f"grad_output {tuple(g.shape)})")
+    a, has_bias = sides.a, sides.a.has_bias
+    c_g, m_g = layer.in_channels // sides.groups, sides.m
+    N, Ng = int(x.shape[0]), int(g.shape[0])
+    Ho, Wo = map(int, g.shape[2:])
+    xv, gv = x[:, k * c_g:(k + 1) * c_g], g[:, k * m_g:(k + 1) * m_g]
+    geo_x = _pack_source(xv.shape, x.stride(), a.kernel, a.stride, a.padding, has_bias)
+    geo_g = _pack_source(gv.shape, g.stride())
+    whole = in_place and (Ho * Wo) % 4 == 0
+    plain = a.kernel == (1, 1) and a.stride == (1, 1) and a.padding == (0, 0) and not has_bias
+
+    def operand(record, view, geometry, wish):
+        op = _per_sample_operand(view, geometry, False, rows_outer)
+        full = _pack_source(record.shape, record.stride())
+        if not (wish and _is_contiguous_nchw(full)):
+            return op
+        plane = int(record.shape[2]) * int(record.shape[3])
+        flat = record.reshape(-1)[view.storage_offset() - record.storage_offset():]           # (a view: it is contiguous)
+        return PerSampleOperand(flat, op.rows, op.L, op.L, int(record.shape[1]) * plane, plane, None, False, 0)
+    x_op = operand(x, xv, geo_x, whole and plain)
+    g_op = operand(g, gv, geo_g, whole)
+    if g_op.L != x_op.L or g_op.rows != sides.m or x_op.rows != sides.n or Ng != N:
+        raise RuntimeError(f"per-sample update: records of {item!r} do not match the layer "
                            f"(input {tuple(x.shape)}, grad_output {tuple(g.shape)})")
     return PerSampleSides(g_op, x_op, sides.n, sides.m, N, x_op.L)
 
@@ -1034,6 +1153,112 @@ def logit_mc(jobs: Sequence[LogitMCJob]) -> None:
     ws = workspace(need, jobs[0].cov.device, "persample") if need else None
     _lib.check(L.curv_logit_mc(_lib.stream_ptr(), arr, n, ws.data_ptr() if need else None, ws.numel() if need else 0),
                "curv_logit_mc")
+
+
+class PerSampleDwJob:
+    """The per-sample products of a true depthwise convolution (csrc/persample_dw.hip): `x` the (N, C, H, W) input and `g`
+    the (N, C, Ho, Wo) grad_output, float32 GPU tensors of any strides (not negative), with the layer's `kernel`, `stride`,
+    `padding` and `has_bias`; n_g = kh kw + has_bias.  For `per_sample_dw_sq_accumulate`: `dst` a (C, n_g) view with unit
+    column stride.  For `per_sample_dw_quad_reduce`: `out` a length-N view of positive stride, `T` (C, n_g, n_g) with unit
+    last stride, `W` (C, n_g) with unit column stride and `s` C values (any shape, contiguous), each or all None (identity,
+    ones, ones).  `alpha`, `first` as in `PerSampleJob`.  `x` / `g` may also be shapes (plan queries)."""
+    __slots__ = ("x", "g", "kernel", "stride", "padding", "has_bias", "dst", "out", "T", "W", "s", "alpha", "first")
+
+    def __init__(self, x, g, kernel, stride=(1, 1), padding=(0, 0), has_bias=False, dst=None, out=None, T=None, W=None,
+                 s=None, alpha=1.0, first=False):
+        self.x, self.g = x, g
+        self.kernel, self.stride, self.padding = tuple(map(int, kernel)), tuple(map(int, stride)), tuple(map(int, padding))
+        self.has_bias, self.dst, self.out, self.T, self.W, self.s = bool(has_bias), dst, out, T, W, s
+        self.alpha, self.first = float(alpha), bool(first)
+
+    @classmethod
+    def of(cls, layer, x, g, **own):
+        """The job of a depthwise Conv2d `layer` on its records."""
+        return cls(x.detach(), g.detach(), layer.kernel_size, layer.stride, layer.padding, layer.bias is not None, **own)
+
+
+def _per_sample_dw_descs(jobs: Sequence[PerSampleDwJob], name: str, reduction: Optional[str]):
+    """`reduction`: "sq", "quad" or None (a plan query: geometry only, `x` / `g` may be shapes)."""
+    arr = (_lib.curv_persample_dw_desc * len(jobs))()
+    for d, j in zip(arr, jobs):
+        xs, gs = (tuple(t.shape) if isinstance(t, torch.Tensor) else tuple(t) for t in (j.x, j.g))
+        if len(xs) != 4 or len(gs) != 4 or xs[:2] != gs[:2]:
+            raise RuntimeError(f"{name}: records must be (N, C, H, W) and (N, C, Ho, Wo), got {xs} and {gs}")
+        _set_geometry(d, xs, j.kernel, j.stride, j.padding, j.has_bias)
+        d.Ho, d.Wo = gs[2:]
+        d.first, d.alpha = int(j.first), j.alpha
+        for side, t, shape in (("x", j.x, xs), ("g", j.g, gs)):
+            if isinstance(t, torch.Tensor):
+                strides, elems = t.stride(), _source_extent(t)
+            else:
+                strides, elems = (math.prod(shape[1:]), shape[2] * shape[3], shape[3], 1), math.prod(shape)
+            for k, v in zip(("sn", "sc", "sh", "sw"), strides):
+                setattr(d, f"{side}_{k}", int(v))
+            setattr(d, f"{side}_elems", int(elems))
+        if reduction is None:
+            continue
+        C, n_g = xs[1], j.kernel[0] * j.kernel[1] + int(j.has_bias)
+        own = (j.dst,) if reduction == "sq" else (j.out, j.T, j.W, j.s)
+        for t in (j.x, j.g) + tuple(t for t in own if t is not None):
+            if not isinstance(t, torch.Tensor) or not t.is_cuda:
+                raise RuntimeError("curvature_amd runs on MI355X only: got a CPU tensor (no CPU fallback)")
+            if t.dtype != torch.float32:
+                raise RuntimeError(f"curvature_amd expects float32 tensors, got {t.dtype}")
+        d.x, d.g = j.x.data_ptr(), j.g.data_ptr()
+        if reduction == "sq":
+            if j.dst is None or j.dst.dim() != 2 or tuple(j.dst.shape) != (C, n_g) or j.dst.stride(1) != 1:
+                raise RuntimeError(f"{name}: destination must be a ({C},{n_g}) view with unit column stride, got "
+                                   f"{None if j.dst is None else tuple(j.dst.shape)}")
+            d.dst, d.c_rs = j.dst.data_ptr(), j.dst.stride(0) if C > 1 else n_g
+            continue
+        if j.out is None or j.out.dim() != 1 or j.out.shape[0] != xs[0] or (xs[0] > 1 and j.out.stride(0) < 1):
+            raise RuntimeError(f"{name}: destination must be a length-{xs[0]} view with a positive stride, got "
+                               f"{None if j.out is None else tuple(j.out.shape)}")
+        d.out, d.o_stride = j.out.data_ptr(), max(j.out.stride(0), 1)
+        if j.T is not None:
+            if tuple(j.T.shape) != (C, n_g, n_g) or (n_g > 1 and j.T.stride(2) != 1):
+                raise RuntimeError(f"{name}: T must be a ({C},{n_g},{n_g}) view with unit last stride, got {tuple(j.T.shape)}")
+            d.T, d.t_cs, d.t_rs = j.T.data_ptr(), j.T.stride(0) if C > 1 else n_g * n_g, j.T.stride(1) if n_g > 1 else n_g
+        if j.W is not None:
+            if tuple(j.W.shape) != (C, n_g) or (n_g > 1 and j.W.stride(1) != 1):
+                raise RuntimeError(f"{name}: W must be a ({C},{n_g}) view with unit column stride, got {tuple(j.W.shape)}")
+            d.Wt, d.w_rs = j.W.data_ptr(), j.W.stride(0) if C > 1 else n_g
+        if j.s is not None:
+            if j.s.numel() != C or not j.s.is_contiguous():
+                raise RuntimeError(f"{name}: s must hold {C} contiguous values, got {tuple(j.s.shape)}")
+            d.s = j.s.data_ptr()
+    return arr
+
+
+def per_sample_dw_plan_info(jobs: Sequence[PerSampleDwJob]):
+    """(flops, bytes) per job (curv_persample_dw_plan_info, host only): the FLOPs of the plane products, 2 N C Ho Wo n_g,
+    and the bytes the algorithm needs, 4 N C (H W + Ho Wo).  `x` / `g` of a job may be shapes."""
+    if not jobs:
+        return [], []
+    n = len(jobs)
+    arr = _per_sample_dw_descs(jobs, "per_sample_dw_plan_info", None)
+    flops, nbytes = (ctypes.c_longlong * n)(), (ctypes.c_longlong * n)()
+    _lib.check(_lib.lib().curv_persample_dw_plan_info(arr, n, flops, nbytes), "curv_persample_dw_plan_info")
+    return [int(v) for v in flops], [int(v) for v in nbytes]
+
+
+def per_sample_dw_sq_accumulate(jobs: Sequence[PerSampleDwJob]) -> None:
+    """``dst[c, j] (+)= alpha sum_n p[n, c, j]**2`` for every job (curv_persample_dw_sq_accumulate), on the current stream;
+    the products p from `workspace`."""
+    if not jobs:
+        return
+    _run_build("curv_persample_dw_workspace_bytes", "curv_persample_dw_sq_accumulate",
+               _per_sample_dw_descs(jobs, "per_sample_dw_sq_accumulate", "sq"), len(jobs), jobs[0].dst.device, "persample_dw")
+
+
+def per_sample_dw_quad_reduce(jobs: Sequence[PerSampleDwJob]) -> None:
+    """``out[n] (+)= alpha sum_c s[c]**2 sum_j W[c, j] (sum_i T[c, i, j] p[n, c, i])**2`` for every job
+    (curv_persample_dw_quad_reduce), on the current stream; the products p from `workspace`."""
+    if not jobs:
+        return
+    _run_build("curv_persample_dw_workspace_bytes", "curv_persample_dw_quad_reduce",
+               _per_sample_dw_descs(jobs, "per_sample_dw_quad_reduce", "quad"), len(jobs), jobs[0].out.device,
+               "persample_dw")
 
 
 def per_sample_scratch(floats: Sequence[int], device, tag: str = "persample_x") -> List[torch.Tensor]:

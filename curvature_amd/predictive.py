@@ -28,6 +28,8 @@ class PredictiveTerms(NamedTuple):
     spectrum: Callable
     separable: bool
     grid_missing: Optional[str] = None
+    direct: Optional[Callable] = None          # ``direct(layer)`` = (T, w, s) of a depthwise layer for `ops.PerSampleDwJob`
+                                               # (w not yet squared; each may be None)
 
 
 class LinearisedPredictive:
@@ -39,12 +41,15 @@ class LinearisedPredictive:
 
     # ------------------------------------------------------------------ the shared steps
     def _predictive_operands(self, what: str, call: str, inputs: bool, rotated: bool, check=None,
-                             select: str = "inv_state"):
+                             select: str = "inv_state", grouped: bool = False):
         """What every reduction starts from: the checks, the selected layers that have an inverse state (`select`: the
         dict that says so - the grid needs `state` only), their per-sample operands from the current records (the g side
         only unless `inputs`; packed for a rotation if `rotated`), and the key that ties a kept X side to the recorded
-        inputs themselves (tensor and version), not just to their shapes.  ``check(operands)`` runs last (the caller's
-        test of its own arguments against the batch).  Returns (layers, operands, key)."""
+        inputs themselves (tensor and version), not just to their shapes.  ``check(N)`` runs last (the caller's
+        test of its own arguments against the batch of N samples).  `grouped`: the caller takes grouped convolutions
+        (`ops.admit_grouped_per_sample`): their group slices stand among the layers as `ops.GroupSlice` items, and the
+        true depthwise ones come back apart, with their records.  Returns (layers, operands, key, direct), `direct` a list
+        of (layer, input, grad_output)."""
         have = getattr(self, select)
         assert have, ("Inverse state dict is empty. Did you call 'invert' prior to this?" if select == "inv_state" else
                       "State dict is empty. Did you call 'update' prior to this?")
@@ -53,16 +58,21 @@ class LinearisedPredictive:
         if getattr(self, "record", None) is None:
             raise RuntimeError(f"{what}.{call}: no recording hooks (construct with per_sample=True, or go "
                                "through evaluate.glm_predictive)")
-        layers = self._per_sample_layers(f"{what}.{call}", "select other layer types")
+        layers = self._per_sample_layers(f"{what}.{call}", "select other layer types", grouped=grouped)
         layers = [l for l in layers if l in have]
         assert layers, f"{select} holds none of the selected layers"
+        direct = [l for l in layers if ops.per_sample_route(l) == "depthwise"]
+        direct = [(l, *self._records_of(what, l)) for l in direct]
+        layers = ops.per_sample_items([l for l in layers if ops.per_sample_route(l) != "depthwise"])
         layout = dict(rows_outer=True, in_place=False) if rotated else {}
-        operands = self._per_sample_operands(what, layers, x_side=inputs, **layout)
+        operands = self._per_sample_operands(what, layers, x_side=inputs, **layout) if layers else []
         if check is not None:
-            check(operands)
-        key = tuple((l, id(self.record[l][0]), self.record[l][0]._version, s.n, s.N, s.L, s.x.ns, s.x.rs)
-                    for l, (s, _, _) in zip(layers, operands))
-        return layers, operands, key
+            check(operands[0][0].N if operands else int(direct[0][1].shape[0]))
+        inputs_of = [self.record[l.layer if isinstance(l, ops.GroupSlice) else l][0] for l in layers]
+        key = tuple((l, id(x), x._version, s.n, s.N, s.L, s.x.ns, s.x.rs)
+                    for l, x, (s, _, _) in zip(layers, inputs_of, operands)) + \
+            tuple((l, id(x), x._version, tuple(x.shape), tuple(x.stride())) for l, x, _ in direct)
+        return layers, operands, key, direct
 
     def _x_side(self, entry: str, layers, operands, basis, weights):
         """What depends on the forward pass and the posterior only: X (rotated) and the squared weights.  Entry `entry` of
@@ -100,20 +110,25 @@ class LinearisedPredictive:
         """`Curvature.functional_variance`."""
         what, basis, weights, *_ = self._predictive_terms()
 
-        def check(operands):
-            N = operands[0][0].N
+        def check(N):
             if out.dim() != 1 or out.shape[0] != N or out.dtype != torch.float32 or not out.is_cuda:
                 raise RuntimeError(f"{what}.functional_variance: out must be a float32 GPU view of length {N}, got "
                                    f"{tuple(out.shape)} {out.dtype} on {out.device}")
-        layers, operands, key = self._predictive_operands(what, "functional_variance", inputs, basis is not None, check)
+        layers, operands, key, direct = self._predictive_operands(what, "functional_variance", inputs, basis is not None,
+                                                                  check, grouped=True)
         if inputs:
             xs, ws = self._x_side("variance", layers, operands, basis, weights)
-            self._kept()["variance"] = dict(key=key, xs=xs, ws=ws)
+            # a depthwise layer has no packed X to keep: its recorded input is read again; (T, w**2, s) is what it keeps
+            terms = [self._predictive_terms().direct(l) for l, _, _ in direct]
+            terms = [(T, None if w is None else ops.mul(w, w), s) for T, w, s in terms]
+            self._kept()["variance"] = dict(key=key, xs=xs, ws=ws, direct=terms)
         kept = self._kept_entry(what, "functional_variance", "variance", key)
         gs = self._g_side(layers, operands, basis)
-        rows = torch.empty(len(layers), operands[0][0].N, dtype=torch.float32, device=operands[0][1].device)
+        rows = torch.empty(len(layers) + len(direct), out.shape[0], dtype=torch.float32, device=out.device)
         ops.per_sample_quad_reduce([ops.PerSampleQuadJob.of(s, g, x, w, rows[k], first=True)
                                     for k, ((s, _, _), g, x, w) in enumerate(zip(operands, gs, kept["xs"], kept["ws"]))])
+        ops.per_sample_dw_quad_reduce([ops.PerSampleDwJob.of(l, x, g, out=rows[len(layers) + k], T=T, W=w, s=s, first=True)
+                                       for k, ((l, x, g), (T, w, s)) in enumerate(zip(direct, kept["direct"]))])
         self._sum_layers(rows, out.unsqueeze(0), first)
         return out
 
@@ -148,14 +163,13 @@ class LinearisedPredictive:
         if terms.grid_missing is not None:
             raise RuntimeError(f"{what}.functional_variance_grid: {terms.grid_missing}")
 
-        def check(operands):
-            N = operands[0][0].N
+        def check(N):
             if tuple(out.shape) != (len(hypers), N) or out.dtype != torch.float32 or not out.is_cuda or \
                     not out.is_contiguous():
                 raise RuntimeError(f"{what}.functional_variance_grid: out must be a contiguous float32 GPU tensor of shape "
                                    f"({len(hypers)}, {N}), got {tuple(out.shape)} {out.dtype} on {out.device}")
-        layers, operands, key = self._predictive_operands(what, "functional_variance_grid", inputs, basis is not None,
-                                                          check, select="state")
+        layers, operands, key, _ = self._predictive_operands(what, "functional_variance_grid", inputs, basis is not None,
+                                                             check, select="state")
         if inputs:
             xs, _ = self._x_side("grid", layers, operands, basis, None)
             self._kept()["grid"] = dict(key=key, xs=xs)
@@ -180,7 +194,7 @@ class LinearisedPredictive:
         slot, count = int(slot), int(count)
         if not 1 <= count <= ops.PERSAMPLE_COV_MAX_OUTPUTS or not 0 <= slot < count:
             raise ValueError(f"{what}.stage_output: slot {slot} of {count} (at most {ops.PERSAMPLE_COV_MAX_OUTPUTS} outputs)")
-        layers, operands, key = self._predictive_operands(what, "stage_output", inputs, basis is not None)
+        layers, operands, key, _ = self._predictive_operands(what, "stage_output", inputs, basis is not None)
         if inputs:
             xs, ws = self._x_side("covariance", layers, operands, basis, weights)
             # a slot is what one output's g side takes: its packed copy, or the record itself where that is read in place

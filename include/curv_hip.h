@@ -564,6 +564,63 @@ typedef struct curv_persample_pack_ex_desc {
 int curv_persample_pack_ex(void* stream, const curv_persample_pack_ex_desc* descs, int n);
 
 /* ------------------------------------------------------------------------------------------------
+ * Per-sample products of true depthwise convolutions (in_channels == out_channels == groups; csrc/persample_dw.hip,
+ * DESIGN.md "K14").  Channel c owns row c of [W | b], a 1 x n_g row with n_g = kh*kw + has_bias, and its per-sample
+ * gradient is a correlation of two planes, not a matrix product:
+ *     p[n, c, a*kw + b] = sum_{oh, ow} g[n, c, oh, ow] * x[n, c, oh*sh + a - ph, ow*sw + b - pw]     (taps outside H x W: 0)
+ *     p[n, c, kh*kw]    = sum_{oh, ow} g[n, c, oh, ow]                                               (has_bias != 0)
+ * Phase 1 writes p (N*C*n_g floats per item) to the workspace, phase 2 reduces it:
+ *     curv_persample_dw_sq_accumulate:  dst[c*c_rs + j]  (+)= alpha * sum_n p[n,c,j]**2
+ *     curv_persample_dw_quad_reduce:    out[n*o_stride]  (+)= alpha * sum_c s[c]**2 * sum_j W[c*w_rs + j] *
+ *                                                              ( sum_i T[c*t_cs + i*t_rs + j] * p[n,c,i] )**2
+ * T, W and s may each be NULL: the identity, all ones, all ones.  Diagonal: W = inv**2; KFAC: T = L_A stacked
+ * (C, n_g, n_g), s = L_G stacked (C, 1, 1) - with one output channel per group ||L_G^T P L_A||_F**2 = l_G**2 ||p L_A||**2.
+ *
+ * One descriptor serves both entry points (each reads its own destination fields).  x is (N, C, H, W) and g is
+ * (N, C, Ho, Wo), float32, each read through four strides in ELEMENTS (not negative; any layout, channels_last included)
+ * inside an extent x_elems / g_elems counted from the pointer: nothing outside the extents is read (a masked tap reads
+ * x[0] of its plane and drops it).  Ho, Wo must be the output size of the geometry; kh*kw <= 49; what one sample spans
+ * stays below 2^31 elements.  Plain fp32 VALU arithmetic (the work is HBM-bound), no atomics, sums in a fixed order
+ * (lane, wave, workgroup, then planes / samples / channels in index order); how a plane is split among waves follows
+ * from its own sizes only, so an item's bits do not depend on the other items of the call.  Up to 16 items per launch.
+ * Enqueues on `stream` only, never waits on the host, allocates nothing.  An empty call is a no-op; invalid geometry,
+ * strides or extents return CURV_ERR_INVALID with the item named, before anything is launched.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct curv_persample_dw_desc {
+  const float* x;
+  const float* g;
+  long long x_sn, x_sc, x_sh, x_sw, x_elems;
+  long long g_sn, g_sc, g_sh, g_sw, g_elems;
+  int32_t N, C, H, W;
+  int32_t kh, kw, sh, sw, ph, pw;
+  int32_t Ho, Wo;
+  int32_t has_bias;
+  int32_t first;
+  float alpha;
+  int32_t reserved;
+  /* curv_persample_dw_sq_accumulate */
+  float* dst;              /* (C, n_g) with row stride c_rs >= n_g */
+  long long c_rs;
+  /* curv_persample_dw_quad_reduce */
+  const float* T;          /* may be NULL */
+  const float* Wt;         /* the weights W of the formula; may be NULL */
+  const float* s;          /* may be NULL */
+  float* out;
+  long long t_cs, t_rs, w_rs, o_stride;
+} curv_persample_dw_desc;
+/* Device scratch for these items (bytes: p of every item, 256-byte aligned each); 0 with the error text set (naming the
+ * item) for invalid geometry.  Host only; the pointers are not read. */
+size_t curv_persample_dw_workspace_bytes(const curv_persample_dw_desc* descs, int n);
+/* Host only: per item the FLOPs of phase 1 (2 N C Ho Wo n_g) into flops[0 .. n) and the bytes the algorithm needs,
+ * 4 N C (H W + Ho Wo), into bytes[0 .. n); either array may be NULL. */
+int curv_persample_dw_plan_info(const curv_persample_dw_desc* descs, int n, long long* flops, long long* bytes);
+/* The workspace must be 256-byte aligned.  `descs` is a host array; it may be reused as soon as the call returns. */
+int curv_persample_dw_sq_accumulate(void* stream, const curv_persample_dw_desc* descs, int n, void* workspace,
+                                    size_t workspace_bytes);
+int curv_persample_dw_quad_reduce(void* stream, const curv_persample_dw_desc* descs, int n, void* workspace,
+                                  size_t workspace_bytes);
+
+/* ------------------------------------------------------------------------------------------------
  * Linearised Laplace (GLM) predictive: the other reduction of the per-sample products (csrc/persample.hip) - over the
  * entries of P_n = A_n B_n^T, per sample:
  *     out[s*o_stride] (+)= alpha * sum_{i < M, j < Nc} W[i*w_rs + j] * ( sum_{l < L} A[s*a_ns + i*a_rs + l] * B[s*b_ns + j*b_rs + l] )**2
