@@ -307,6 +307,7 @@ SIGNATURES = {
     "curv_gemm_workspace_bytes_for": (_sz, [ctypes.POINTER(curv_gemm_desc), _i]),
     "curv_gemm_batched": (_i, [_vp, ctypes.POINTER(curv_gemm_desc), _i, _vp, _sz]),
     "curv_gemm_batched_ex": (_i, [_vp, ctypes.POINTER(curv_gemm_desc), _i, _vp, _sz, ctypes.c_uint]),
+    "curv_gemm_plan_info": (_i, [ctypes.POINTER(curv_gemm_desc), _i, _sz, ctypes.POINTER(ctypes.c_longlong)]),
     "curv_randn": (_i, [_vp, _vp, _ll, ctypes.c_ulonglong, ctypes.c_ulonglong]),
     "curv_randn_counter": (_i, [_vp, _vp, ctypes.c_longlong, ctypes.c_ulonglong, _vp]),
     "curv_rsqrt_affine": (_i, [_vp, _vp, _d, _d, _vp, _ll]),
@@ -350,6 +351,7 @@ CONVT_MAX_PHASES = 64               # CURV_CONVT_MAX_PHASES
 PERSAMPLE_COV_MAX_OUTPUTS = 16      # CURV_PERSAMPLE_COV_MAX_OUTPUTS
 PERSAMPLE_GRID_MAX = 16             # CURV_PERSAMPLE_GRID_MAX
 GEMM_TABLE_RESIDENT = 1             # CURV_GEMM_TABLE_RESIDENT
+GEMM_PLAN_FIELDS = 8                # CURV_GEMM_PLAN_FIELDS
 ERR_NOT_PD, ERR_INVALID, ERR_WORKSPACE, ERR_HIP, ERR_NOT_CONVERGED = 1, 2, 3, 4, 5     # CURV_ERR_* of the header
 
 

@@ -667,19 +667,30 @@ extern "C" size_t curv_gemm_workspace_bytes_for(const curv_gemm_desc* descs, int
   return total;
 }
 
-static int gemm_batched_impl(void* stream_, const curv_gemm_desc* descs, int n_desc, void* workspace,
-                             size_t workspace_bytes, unsigned flags) {
-  hipStream_t stream = (hipStream_t)stream_;
-  if (n_desc == 0) return CURV_OK;
+// What one call launches: the descriptors sorted into their work lists, and the sizes of the launches.  Built by
+// gemm_classify alone: curv_gemm_batched launches from it, curv_gemm_plan_info reports it.
+struct GemmWork {
+  std::vector<GemmDev> tab, tab_nt, tab_v;      // work lists: the general (or small) kernel, the NT / LDS-DMA kernel, thin products
+  long long tiles = 0;                          // workgroups of gemm_f32_kernel, or of gemm_nt_small_kernel when `small`
+  long long tiles_nt = 0;                       // items (tile x slice) of gemm_nt_kernel
+  long long red_tiles = 0;                      // workgroups of gemm_nt_reduce_kernel
+  long long gemv_wgs = 0;                       // workgroups of gemv_rows_kernel
+  bool small = false;                           // `tab` goes to gemm_nt_small_kernel
+  bool ordered = false;                         // gemm_nt_kernel walks its tiles through the K-sorted order list
+};
+
+// Validates the descriptors of one call and sorts them into `w` (n_desc > 0).
+static int gemm_classify(const curv_gemm_desc* descs, int n_desc, size_t workspace_bytes, GemmWork& w) {
   CURV_REQUIRE(descs != nullptr, "curv_gemm_batched: null descriptor array");
-  if (workspace == nullptr || workspace_bytes < curv_gemm_workspace_bytes(n_desc)) {
+  if (workspace_bytes < curv_gemm_workspace_bytes(n_desc)) {
     set_error("curv_gemm_batched: workspace too small");
     return CURV_ERR_WORKSPACE;
   }
-  std::vector<GemmDev> tab, tab_nt, tab_v;      // work lists: the general kernel, the NT / LDS-DMA kernel, thin products
+  std::vector<GemmDev>&tab = w.tab, &tab_nt = w.tab_nt, &tab_v = w.tab_v;
   tab.reserve(n_desc);
-  long long tiles = 0, tiles_nt = 0, red_tiles = 0, slab_floats = 0, gemv_wgs = 0;
-  const bool small = small_launch(descs, n_desc);      // everything goes to gemm_nt_small_kernel (work list `tab`)
+  long long &tiles = w.tiles, &tiles_nt = w.tiles_nt, &red_tiles = w.red_tiles, &gemv_wgs = w.gemv_wgs;
+  long long slab_floats = 0;
+  const bool small = w.small = small_launch(descs, n_desc);      // everything goes to gemm_nt_small_kernel (work list `tab`)
   // K slicing needs the slab area behind the table: only with a workspace sized by curv_gemm_workspace_bytes_for
   const bool underfilled = nt_tiles_of(descs, n_desc) < NT_SPLIT_BELOW_TILES;
   const bool may_split = underfilled && workspace_bytes >= curv_gemm_workspace_bytes_for(descs, n_desc);
@@ -752,6 +763,22 @@ static int gemm_batched_impl(void* stream_, const curv_gemm_desc* descs, int n_d
     CURV_REQUIRE(tiles < (1LL << 30), "curv_gemm_batched: too many tiles");
     tab.push_back(d);
   }
+  // a full launch (several tiles per workgroup slot, no K slicing) walks its tiles in descending K order; the list
+  // lies in the space the slabs of an underfilled launch would take
+  w.ordered = tab_nt.size() > 1 && !underfilled && workspace_bytes >= curv_gemm_workspace_bytes_for(descs, n_desc);
+  return CURV_OK;
+}
+
+static int gemm_batched_impl(void* stream_, const curv_gemm_desc* descs, int n_desc, void* workspace,
+                             size_t workspace_bytes, unsigned flags) {
+  hipStream_t stream = (hipStream_t)stream_;
+  if (n_desc == 0) return CURV_OK;
+  GemmWork w;
+  const int rcw = gemm_classify(descs, n_desc, workspace != nullptr ? workspace_bytes : 0, w);
+  if (rcw != CURV_OK) return rcw;
+  const std::vector<GemmDev>&tab = w.tab, &tab_nt = w.tab_nt, &tab_v = w.tab_v;
+  const long long tiles = w.tiles, tiles_nt = w.tiles_nt, red_tiles = w.red_tiles, gemv_wgs = w.gemv_wgs;
+  const bool small = w.small;
   if (tab.empty() && tab_nt.empty() && tab_v.empty()) return CURV_OK;
   GemmDev* table = reinterpret_cast<GemmDev*>(workspace);
   const int n = (int)tab.size(), n_nt = (int)tab_nt.size(), n_v = (int)tab_v.size();
@@ -765,10 +792,8 @@ static int gemm_batched_impl(void* stream_, const curv_gemm_desc* descs, int n_d
     if (rcu != CURV_OK) return rcu;
   }
   float* slabs = reinterpret_cast<float*>(reinterpret_cast<char*>(workspace) + curv_gemm_workspace_bytes(n_desc));
-  // a full launch (several tiles per workgroup slot, no K slicing): its tiles in descending K order, in the space the
-  // slabs of an underfilled launch would take
   const int* order = nullptr;
-  if (n_nt > 1 && !underfilled && workspace_bytes >= curv_gemm_workspace_bytes_for(descs, n_desc)) {
+  if (w.ordered) {
     int* dev_order = reinterpret_cast<int*>(slabs);
     order = dev_order;
     if (!(flags & CURV_GEMM_TABLE_RESIDENT)) {
@@ -812,6 +837,27 @@ static int gemm_batched_impl(void* stream_, const curv_gemm_desc* descs, int n_d
     hipLaunchKernelGGL(gemv_rows_kernel, dim3((unsigned)gemv_wgs), dim3(256), 0, stream, table + n + n_nt, n_v);
     CURV_LAUNCH_CHECK();
   }
+  return CURV_OK;
+}
+
+extern "C" int curv_gemm_plan_info(const curv_gemm_desc* descs, int n_desc, size_t workspace_bytes, long long* out) {
+  if (n_desc == 0) {
+    if (out != nullptr) std::fill(out, out + CURV_GEMM_PLAN_FIELDS, 0LL);
+    return CURV_OK;
+  }
+  CURV_REQUIRE(n_desc > 0 && out != nullptr, "curv_gemm_plan_info: bad arguments");
+  GemmWork w;
+  const int rc = gemm_classify(descs, n_desc, workspace_bytes, w);
+  if (rc != CURV_OK) return rc;
+  std::fill(out, out + CURV_GEMM_PLAN_FIELDS, 0LL);
+  for (const GemmDev& d : w.tab)
+    if (!w.small) out[d.tm == 128 ? 1 : 0] += (long long)cdiv(d.M, d.tm) * d.tiles_n;
+  out[2] = w.tiles_nt;
+  for (const GemmDev& d : w.tab_nt) out[3] += d.n_slices > 1;
+  out[4] = w.red_tiles;
+  out[5] = w.small ? w.tiles : 0;
+  out[6] = w.gemv_wgs;
+  out[7] = w.ordered ? w.tiles_nt : 0;
   return CURV_OK;
 }
 

@@ -1479,6 +1479,24 @@ def gemm_batched(jobs: Sequence[Gemm]) -> None:
     GemmPlan(jobs).run()
 
 
+GEMM_PLAN_KEYS = ("tiles64", "tiles128", "nt_items", "split_products", "reduce_wgs", "small_blocks", "gemv_wgs",
+                  "order_entries")
+
+
+def gemm_plan_info(jobs, workspace_bytes: Optional[int] = None) -> dict:
+    """What `gemm_batched(jobs)` would launch (curv_gemm_plan_info; host only): work items per kernel under the keys of
+    GEMM_PLAN_KEYS.  `jobs`: a list of Gemm, or a ctypes array of curv_gemm_desc.  `workspace_bytes`: the size GemmPlan
+    allocates unless given."""
+    descs = jobs if isinstance(jobs, ctypes.Array) else (_gemm_descs(jobs) if len(jobs) else None)
+    n = len(jobs)
+    L = _lib.lib()
+    if workspace_bytes is None:
+        workspace_bytes = max(int(L.curv_gemm_workspace_bytes_for(descs, n)), 256) if n else 0
+    out = (ctypes.c_longlong * _lib.GEMM_PLAN_FIELDS)()
+    _lib.check(L.curv_gemm_plan_info(descs, n, int(workspace_bytes), out), "curv_gemm_plan_info")
+    return dict(zip(GEMM_PLAN_KEYS, (int(v) for v in out)))
+
+
 class GemmPlan:
     """A fixed list of products: descriptors are built once, `run()` only enqueues (one launch).  The
     operand tensors are kept alive by the plan; their contents may change between runs."""

@@ -390,6 +390,15 @@ int curv_gemm_batched(void* stream, const curv_gemm_desc* descs, int n_desc, voi
 #define CURV_GEMM_TABLE_RESIDENT 1u
 int curv_gemm_batched_ex(void* stream, const curv_gemm_desc* descs, int n_desc, void* workspace,
                          size_t workspace_bytes, unsigned flags);
+/* Host only: what curv_gemm_batched would launch for these descriptors on a workspace of this many bytes; no pointer is
+ * dereferenced and nothing runs on the device.  It goes through the launch's own validation and classification, so it
+ * returns the launch's refusals with their messages.  out[0 .. CURV_GEMM_PLAN_FIELDS):
+ *   0  64 x 64 tiles of the general kernel            4  workgroups of the reduce launch (tiles of split products)
+ *   1  128 x 128 tiles of the general kernel          5  32 x 32 blocks of the small-launch kernel
+ *   2  items of the NT kernel (tiles x K slices)      6  workgroups of the one-column (gemv) kernel
+ *   3  K-sliced products                              7  entries of the K-sorted tile order list (0: not used) */
+#define CURV_GEMM_PLAN_FIELDS 8
+int curv_gemm_plan_info(const curv_gemm_desc* descs, int n_desc, size_t workspace_bytes, long long* out);
 
 /* fp64 variant (alpha/beta only) for the ill-conditioned products of INF.pre_sampler.  `tri`: triangular operands -
  * entries outside the triangle are neither read nor multiplied (they must be zero in memory where a tile straddles the
