@@ -235,6 +235,33 @@ class curv_persample_dw_desc(ctypes.Structure):
                [(k, ctypes.c_longlong) for k in ("t_cs", "t_rs", "w_rs", "o_stride")]
 
 
+_DW_RECORD = [("x", ctypes.c_void_p), ("g", ctypes.c_void_p)] + \
+             [(k, ctypes.c_longlong) for k in ("x_sn", "x_sc", "x_sh", "x_sw", "x_elems",
+                                               "g_sn", "g_sc", "g_sh", "g_sw", "g_elems")] + _SOURCE + _WINDOW + \
+             [(k, ctypes.c_int32) for k in ("Ho", "Wo", "has_bias")]
+
+
+class curv_persample_dw_project_desc(ctypes.Structure):
+    """Mirror of ``curv_persample_dw_project_desc`` in include/curv_hip.h."""
+    _fields_ = _DW_RECORD + [("reserved", ctypes.c_int32)] + [(k, ctypes.c_void_p) for k in ("T", "Wt", "s", "y")] + \
+               [(k, ctypes.c_longlong) for k in ("t_cs", "t_rs", "w_rs", "y_ns")]
+
+
+class curv_persample_dw_grid_desc(ctypes.Structure):
+    """Mirror of ``curv_persample_dw_grid_desc`` in include/curv_hip.h (`shift` and `gain` are host arrays of Hn floats)."""
+    _fields_ = _DW_RECORD + [("first", ctypes.c_int32)] + [(k, ctypes.c_void_p) for k in ("T", "u", "v", "V", "out")] + \
+               [("shift", ctypes.POINTER(ctypes.c_float)), ("gain", ctypes.POINTER(ctypes.c_float))] + \
+               [(k, ctypes.c_longlong) for k in ("t_cs", "t_rs", "v_rs", "o_stride", "o_hs")] + \
+               [("Hn", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
+class curv_persample_gram_desc(ctypes.Structure):
+    """Mirror of ``curv_persample_gram_desc`` in include/curv_hip.h."""
+    _fields_ = [("Y", ctypes.c_void_p), ("out", ctypes.c_void_p)] + \
+               [(k, ctypes.c_longlong) for k in ("y_ks", "y_ns", "o_ns", "o_rs")] + \
+               [(k, ctypes.c_int32) for k in ("N", "K", "E", "first")] + [("alpha", ctypes.c_float), ("reserved", ctypes.c_int32)]
+
+
 class curv_copy_desc(ctypes.Structure):
     _fields_ = [("dst", ctypes.c_void_p), ("src", ctypes.c_void_p), ("bytes", ctypes.c_ulonglong)]
 
@@ -332,6 +359,15 @@ SIGNATURES = {
                                         ctypes.POINTER(ctypes.c_longlong)]),
     "curv_persample_dw_sq_accumulate": (_i, [_vp, ctypes.POINTER(curv_persample_dw_desc), _i, _vp, _sz]),
     "curv_persample_dw_quad_reduce": (_i, [_vp, ctypes.POINTER(curv_persample_dw_desc), _i, _vp, _sz]),
+    "curv_persample_dw_project_workspace_bytes": (_sz, [ctypes.POINTER(curv_persample_dw_project_desc), _i]),
+    "curv_persample_dw_project_plan_info": (_i, [ctypes.POINTER(curv_persample_dw_project_desc), _i,
+                                                ctypes.POINTER(ctypes.c_longlong), ctypes.POINTER(ctypes.c_longlong)]),
+    "curv_persample_dw_project": (_i, [_vp, ctypes.POINTER(curv_persample_dw_project_desc), _i, _vp, _sz]),
+    "curv_persample_dw_quad_grid_workspace_bytes": (_sz, [ctypes.POINTER(curv_persample_dw_grid_desc), _i]),
+    "curv_persample_dw_quad_grid_plan_info": (_i, [ctypes.POINTER(curv_persample_dw_grid_desc), _i,
+                                                  ctypes.POINTER(ctypes.c_longlong), ctypes.POINTER(ctypes.c_longlong)]),
+    "curv_persample_dw_quad_grid_reduce": (_i, [_vp, ctypes.POINTER(curv_persample_dw_grid_desc), _i, _vp, _sz]),
+    "curv_persample_gram_reduce": (_i, [_vp, ctypes.POINTER(curv_persample_gram_desc), _i]),
     "curv_logit_mc_workspace_bytes": (_sz, [ctypes.POINTER(curv_logit_mc_desc), _i]),
     "curv_logit_mc_plan_flops": (_i, [ctypes.POINTER(curv_logit_mc_desc), _i, ctypes.POINTER(ctypes.c_longlong)]),
     "curv_logit_mc": (_i, [_vp, ctypes.POINTER(curv_logit_mc_desc), _i, _vp, _sz]),

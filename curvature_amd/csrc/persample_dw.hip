@@ -1,5 +1,6 @@
 // Per-sample products of true depthwise convolutions (curv_persample_dw_sq_accumulate / curv_persample_dw_quad_reduce,
-// include/curv_hip.h; DESIGN.md "K14").
+// include/curv_hip.h; DESIGN.md "K14"; curv_persample_dw_project / curv_persample_dw_quad_grid_reduce and the Gram of
+// staged rows, curv_persample_gram_reduce: DESIGN.md "K15").
 //
 // A depthwise layer (in_channels == out_channels == groups) has one 1 x (kh kw [+ 1]) row of [W | b] per channel.  Its
 // per-sample gradient is no matrix product but a correlation of two planes,
@@ -16,7 +17,8 @@
 //      accumulator).  Sums in a fixed order: lane, wave (DPP), the waves of the workgroup in order.  No atomics.
 //   2. one small kernel per reduction: ps_dw_sq_kernel (one thread per (c, j), the samples in order) or
 //      ps_dw_quad_kernel (one workgroup per sample: the T / W / s form per channel, a thread's channels in order, then
-//      lane, wave, workgroup).
+//      lane, wave, workgroup), ps_dw_project_kernel (one thread per value written) or ps_dw_grid_kernel (as the quad
+//      kernel, one chain per grid point).
 // How a plane is split follows from its own sizes only, so an item's bits do not depend on the other items of a call.
 #include "kernarg.h"
 #include "side_build.h"
@@ -72,7 +74,48 @@ struct DwQuad {
 };
 typedef ArgBatch<DwQuad, DW_BATCH> DwQuadBatch;
 
-static_assert(sizeof(DwBatch) <= 3840 && sizeof(DwSqBatch) <= 3840 && sizeof(DwQuadBatch) <= 3840,
+struct DwProject {
+  const float* p;
+  const float* T;
+  const float* W;
+  const float* s;
+  float* y;
+  long long t_cs, t_rs, w_rs, y_ns;
+  int Cn, n_g;
+  long long per;                      // N C n_g: the item's threads
+  long long base;                     // first thread
+};
+typedef ArgBatch<DwProject, DW_BATCH> DwProjectBatch;
+
+constexpr int DW_GRID_MAX = CURV_PERSAMPLE_GRID_MAX;
+constexpr int DW_GRID_BATCH = 8;      // items per launch of the grid reduction: an item carries its 2 x 16 grid values
+struct DwGrid {
+  const float* p;
+  const float* T;
+  const float* u;
+  const float* v;                     // separable: v (C, n_g); dense (u null): V (C, n_g)
+  float* out;
+  long long t_cs, t_rs, v_rs, o_stride, o_hs;
+  int Cn, n_g, H, first;
+  float shift[DW_GRID_MAX], gain[DW_GRID_MAX];
+  long long base;                     // first workgroup (= sample)
+};
+typedef ArgBatch<DwGrid, DW_GRID_BATCH> DwGridBatch;
+
+constexpr int GRAM_MAX_K = CURV_PERSAMPLE_COV_MAX_OUTPUTS;
+constexpr int GRAM_MAX_PAIRS = GRAM_MAX_K * (GRAM_MAX_K + 1) / 2;
+struct GramItem {
+  const float* Y;
+  float* out;
+  long long y_ks, y_ns, o_ns, o_rs;
+  int K, E, first;
+  float alpha;
+  long long base;                     // first workgroup (= sample)
+};
+typedef ArgBatch<GramItem, DW_BATCH> GramBatch;
+
+static_assert(sizeof(DwBatch) <= 3840 && sizeof(DwSqBatch) <= 3840 && sizeof(DwQuadBatch) <= 3840 &&
+              sizeof(DwProjectBatch) <= 3840 && sizeof(DwGridBatch) <= 3840 && sizeof(GramBatch) <= 3840,
               "kernel argument block must stay below 4 KB");
 
 // ------------------------------------------------------------------------------------------------ phase 1
@@ -320,6 +363,130 @@ __global__ void __launch_bounds__(DW_THREADS) ps_dw_quad_kernel(const DwQuadBatc
   }
 }
 
+// y[n y_ns + c n_g + j] = s[c] W[c w_rs + j] sum_i T[c t_cs + i t_rs + j] p[n, c, i]: one thread per (n, c, j), the i in
+// order; neighbouring threads read neighbouring j of T.
+__global__ void __launch_bounds__(DW_THREADS) ps_dw_project_kernel(const DwProjectBatch batch) {
+  const long long t = (long long)blockIdx.x * DW_THREADS + threadIdx.x;
+  const DwProject& F = batch.e[owner_of(batch, t)];
+  const long long at = t - F.base;
+  if (at >= F.per) return;
+  const int n_g = F.n_g, row = F.Cn * n_g;
+  const long long n = at / row;
+  const int cj = (int)(at - n * row), c = cj / n_g, j = cj - c * n_g;
+  const float* __restrict__ p = F.p + (n * F.Cn + c) * n_g;
+  float y;
+  if (F.T) {
+    const float* __restrict__ T = F.T + (long long)c * F.t_cs + j;
+    y = 0.0f;
+    for (int i = 0; i < n_g; ++i) y = fmaf(T[(long long)i * F.t_rs], p[i], y);
+  } else {
+    y = p[j];
+  }
+  if (F.W) y *= F.W[(long long)c * F.w_rs + j];
+  if (F.s) y *= F.s[c];
+  F.y[n * F.y_ns + cj] = y;
+}
+
+// out[h o_hs + n o_stride] (+)= gain[h] sum_c sum_j w_h(c, j) (sum_i T[c t_cs + i t_rs + j] p[n, c, i])**2: one workgroup
+// per sample; a thread takes the channels c = thread, thread + 256, ... and their j in order, one chain per grid point,
+// then lane, wave, workgroup.  Grid point h sees shift[h] and gain[h] only.
+__global__ void __launch_bounds__(DW_THREADS) ps_dw_grid_kernel(const DwGridBatch batch) {
+  __shared__ float lds[DW_WAVES][DW_GRID_MAX];
+  const DwGrid& F = batch.e[owner_of(batch, (long long)blockIdx.x)];
+  const int n = (int)((long long)blockIdx.x - F.base);
+  const int n_g = F.n_g, H = F.H;
+  float acc[DW_GRID_MAX];
+#pragma unroll
+  for (int h = 0; h < DW_GRID_MAX; ++h) acc[h] = 0.0f;
+  for (int c = threadIdx.x; c < F.Cn; c += DW_THREADS) {
+    const float* __restrict__ p = F.p + ((long long)n * F.Cn + c) * n_g;
+    const float* __restrict__ T = F.T ? F.T + (long long)c * F.t_cs : nullptr;
+    const float* __restrict__ v = F.v + (long long)c * F.v_rs;
+    const float uc = F.u ? F.u[c] : 0.0f;
+    for (int j = 0; j < n_g; ++j) {
+      float y;
+      if (T) {
+        y = 0.0f;
+        for (int i = 0; i < n_g; ++i) y = fmaf(T[(long long)i * F.t_rs + j], p[i], y);
+      } else {
+        y = p[j];
+      }
+      const float y2 = y * y, vj = v[j];
+#pragma unroll
+      for (int h = 0; h < DW_GRID_MAX; ++h)
+        if (h < H) {
+          const float sh = F.shift[h];
+          const float w = F.u ? 1.0f / ((uc + sh) * (vj + sh)) : 1.0f / (vj + sh);
+          acc[h] = fmaf(w, y2, acc[h]);
+        }
+    }
+  }
+#pragma unroll
+  for (int h = 0; h < DW_GRID_MAX; ++h) {
+    const float v = wave_sum_dpp(acc[h]);
+    if ((threadIdx.x & 63) == 63) lds[threadIdx.x >> 6][h] = v;
+  }
+  __syncthreads();
+  if ((int)threadIdx.x < H) {
+    const int h = threadIdx.x;
+    float v = lds[0][h];
+#pragma unroll
+    for (int w = 1; w < DW_WAVES; ++w) v += lds[w][h];
+    float* out = F.out + ((long long)h * F.o_hs + (long long)n * F.o_stride);
+    *out = F.first ? F.gain[h] * v : *out + F.gain[h] * v;
+  }
+}
+
+// out[n o_ns + k o_rs + k'] (+)= alpha sum_e Y[k y_ks + n y_ns + e] Y[k' y_ks + n y_ns + e]: one workgroup per sample; a
+// thread takes e = thread, thread + 256, ... in order with one chain per pair k <= k' in registers (KT: the compiled-in
+// number of outputs, K <= KT; the outputs from K on read as 0), then lane, wave, workgroup.  One value per pair goes to
+// both triangles.
+template <int KT>
+__global__ void __launch_bounds__(DW_THREADS) ps_gram_kernel(const GramBatch batch) {
+  constexpr int PAIRS = KT * (KT + 1) / 2;
+  __shared__ float lds[DW_WAVES][PAIRS];
+  const GramItem& F = batch.e[owner_of(batch, (long long)blockIdx.x)];
+  const int n = (int)((long long)blockIdx.x - F.base);
+  const int K = F.K, E = F.E;
+  const float* __restrict__ Y = F.Y + (long long)n * F.y_ns;
+  float acc[PAIRS];
+#pragma unroll
+  for (int q = 0; q < PAIRS; ++q) acc[q] = 0.0f;
+  for (int e = threadIdx.x; e < E; e += DW_THREADS) {
+    float y[KT];
+#pragma unroll
+    for (int k = 0; k < KT; ++k) y[k] = k < K ? Y[(long long)k * F.y_ks + e] : 0.0f;
+    int q = 0;
+#pragma unroll
+    for (int k = 0; k < KT; ++k)
+#pragma unroll
+      for (int l = k; l < KT; ++l, ++q) acc[q] = fmaf(y[k], y[l], acc[q]);
+  }
+#pragma unroll
+  for (int q = 0; q < PAIRS; ++q) {
+    const float v = wave_sum_dpp(acc[q]);
+    if ((threadIdx.x & 63) == 63) lds[threadIdx.x >> 6][q] = v;
+  }
+  __syncthreads();
+  if ((int)threadIdx.x < PAIRS) {
+    int k = 0, at = threadIdx.x;                       // pair `thread` of the KT-wide triangle is (k, l)
+    while (at >= KT - k) { at -= KT - k; ++k; }
+    const int l = k + at;
+    if (l < K) {
+      float v = lds[0][threadIdx.x];
+#pragma unroll
+      for (int w = 1; w < DW_WAVES; ++w) v += lds[w][threadIdx.x];
+      v *= F.alpha;
+      float* o = F.out + (long long)n * F.o_ns;
+      float* upper = o + ((long long)k * F.o_rs + l);
+      float* lower = o + ((long long)l * F.o_rs + k);
+      const float r = F.first ? v : *upper + v;
+      *upper = r;
+      *lower = r;
+    }
+  }
+}
+
 // ------------------------------------------------------------------------------------------------ host
 // The largest offset (in elements) an (N, C, H, W) view with these strides addresses, or -1 if what one sample spans does
 // not fit 31 bits.
@@ -336,8 +503,10 @@ long long dw_span(const long long dims[4], const long long strides[4], long long
 }
 
 // Item `index` as phase 1 reads it (without `p` and `base`), or false with the error text set.  `pointers`: also the
-// records' addresses (the host-only queries do not need them).
-bool dw_item_of(const curv_persample_dw_desc& d, int index, const char* who, bool pointers, DwItem* out) {
+// records' addresses (the host-only queries do not need them).  `Desc`: any descriptor with the record, geometry and
+// extent fields of curv_persample_dw_desc.
+template <typename Desc>
+bool dw_item_of(const Desc& d, int index, const char* who, bool pointers, DwItem* out) {
   side::ConvGeom geo;
   if (!side::conv_geom_of(d, who, "item", index, &geo)) return false;
   if (d.Ho != geo.Ho || d.Wo != geo.Wo) {
@@ -442,7 +611,8 @@ DwKernel dw_kernel_of(DwVariant v) {
 }
 
 // Every item planned (nothing is launched before all are), `p` carved out of the workspace in call order.
-int dw_plan(const char* name, const curv_persample_dw_desc* descs, int n, void* workspace, size_t workspace_bytes,
+template <typename Desc>
+int dw_plan(const char* name, const Desc* descs, int n, void* workspace, size_t workspace_bytes,
             std::vector<DwItem>* items) {
   CURV_REQUIRE(descs, "%s: null descriptors", name);
   items->resize(n);
@@ -593,4 +763,238 @@ extern "C" int curv_persample_dw_quad_reduce(void* stream_, const curv_persample
         CURV_LAUNCH_CHECK();
         return CURV_OK;
       });
+}
+
+// ------------------------------------------------------------------------------------------------ K15: project, grid, Gram
+namespace curv {
+namespace {
+
+// The fields of item `index` behind its records, or false with the error text set.
+bool dw_project_ok(const curv_persample_dw_project_desc& d, int index, const char* who, const DwItem& F, bool pointers) {
+  const long long row = (long long)F.C * F.n_g;
+  if (row >= (1LL << 31)) {
+    set_error("%s: item %d: too large (%lld values per sample)", who, index, row);
+    return false;
+  }
+  if (d.y_ns < row && d.N > 1) {
+    set_error("%s: item %d: y_ns %lld below C n_g = %lld", who, index, d.y_ns, row);
+    return false;
+  }
+  if ((d.T && (d.t_rs < 0 || d.t_cs < 0)) || (d.Wt && d.w_rs < 0)) {
+    set_error("%s: item %d: negative stride of T or W", who, index);
+    return false;
+  }
+  if (pointers && !d.y) {
+    set_error("%s: item %d: null destination", who, index);
+    return false;
+  }
+  return true;
+}
+
+bool dw_grid_ok(const curv_persample_dw_grid_desc& d, int index, const char* who, const DwItem&, bool pointers) {
+  if (d.Hn < 1 || d.Hn > DW_GRID_MAX || !d.shift || !d.gain) {
+    set_error("%s: item %d: H %d (1 to %d grid points, with their shift and gain)", who, index, d.Hn, DW_GRID_MAX);
+    return false;
+  }
+  for (int h = 0; h < d.Hn; ++h)
+    if (!(d.shift[h] > 0.0f) || !std::isfinite(d.shift[h]) || !std::isfinite(d.gain[h])) {
+      set_error("%s: item %d: grid point %d: shift %g must be finite and > 0, gain %g finite", who, index, h,
+                (double)d.shift[h], (double)d.gain[h]);
+      return false;
+    }
+  if ((d.T && (d.t_rs < 0 || d.t_cs < 0)) || d.v_rs < 0) {
+    set_error("%s: item %d: negative stride of T or of the weights", who, index);
+    return false;
+  }
+  if ((d.o_stride < 1 && d.N > 1) || (d.o_hs < 1 && d.Hn > 1)) {
+    set_error("%s: item %d: o_stride %lld or o_hs %lld below 1", who, index, d.o_stride, d.o_hs);
+    return false;
+  }
+  if (!pointers) return true;
+  const bool separable = d.u != nullptr;
+  if (!d.out || (separable ? (!d.v || d.V) : (!d.V || d.v))) {
+    set_error("%s: item %d: null destination, or weights given neither as u and v (separable) nor as V (dense)", who, index);
+    return false;
+  }
+  return true;
+}
+
+template <typename Desc, typename Check>
+size_t dw_workspace_bytes_of(const char* name, const Desc* descs, int n, Check check) {
+  if (n <= 0) return 0;
+  if (!descs) {
+    set_error("%s: null descriptors", name);
+    return 0;
+  }
+  size_t need = 0;
+  for (int i = 0; i < n; ++i) {
+    DwItem F;
+    if (!dw_item_of(descs[i], i, name, false, &F) || !check(descs[i], i, name, F, false)) return 0;
+    need += dw_p_bytes(F);
+  }
+  return need;
+}
+
+// Per item the FLOPs of phase 1 and of the reduction behind it (`after(F, d)`), and the bytes the algorithm needs.
+template <typename Desc, typename Check, typename After>
+int dw_plan_info_of(const char* name, const Desc* descs, int n, long long* flops, long long* bytes, Check check, After after) {
+  if (n <= 0) return CURV_OK;
+  CURV_REQUIRE(descs && (flops || bytes), "%s: null argument", name);
+  for (int i = 0; i < n; ++i) {
+    DwItem F;
+    if (!dw_item_of(descs[i], i, name, false, &F) || !check(descs[i], i, name, F, false)) return CURV_ERR_INVALID;
+    const long long planes = (long long)F.N * F.C, L = (long long)F.Ho * F.Wo;
+    long long extra_flops = 0, extra_bytes = 0;
+    after(F, descs[i], &extra_flops, &extra_bytes);
+    if (flops) flops[i] = 2 * planes * L * F.n_g + extra_flops;
+    if (bytes) bytes[i] = 4 * planes * ((long long)F.H * F.W + L) + extra_bytes;
+  }
+  return CURV_OK;
+}
+
+void dw_project_cost(const DwItem& F, const curv_persample_dw_project_desc& d, long long* flops, long long* bytes) {
+  const long long values = (long long)F.N * F.C * F.n_g;
+  *flops = d.T ? 2 * values * F.n_g : 0;
+  *bytes = 4 * values;                                                     // y written once
+}
+
+void dw_grid_cost(const DwItem& F, const curv_persample_dw_grid_desc& d, long long* flops, long long* bytes) {
+  const long long values = (long long)F.N * F.C * F.n_g;
+  *flops = (d.T ? 2 * values * F.n_g : 0) + 2 * values * d.Hn;
+  *bytes = 0;
+}
+
+}  // namespace
+}  // namespace curv
+
+extern "C" size_t curv_persample_dw_project_workspace_bytes(const curv_persample_dw_project_desc* descs, int n) {
+  return dw_workspace_bytes_of("curv_persample_dw_project_workspace_bytes", descs, n, dw_project_ok);
+}
+
+extern "C" int curv_persample_dw_project_plan_info(const curv_persample_dw_project_desc* descs, int n, long long* flops,
+                                                   long long* bytes) {
+  return dw_plan_info_of("curv_persample_dw_project_plan_info", descs, n, flops, bytes, dw_project_ok, dw_project_cost);
+}
+
+extern "C" size_t curv_persample_dw_quad_grid_workspace_bytes(const curv_persample_dw_grid_desc* descs, int n) {
+  return dw_workspace_bytes_of("curv_persample_dw_quad_grid_workspace_bytes", descs, n, dw_grid_ok);
+}
+
+extern "C" int curv_persample_dw_quad_grid_plan_info(const curv_persample_dw_grid_desc* descs, int n, long long* flops,
+                                                     long long* bytes) {
+  return dw_plan_info_of("curv_persample_dw_quad_grid_plan_info", descs, n, flops, bytes, dw_grid_ok, dw_grid_cost);
+}
+
+extern "C" int curv_persample_dw_project(void* stream_, const curv_persample_dw_project_desc* descs, int n, void* workspace,
+                                         size_t workspace_bytes) {
+  const char* const name = "curv_persample_dw_project";
+  if (n <= 0) return CURV_OK;
+  hipStream_t stream = (hipStream_t)stream_;
+  std::vector<DwItem> items;
+  int rc = dw_plan(name, descs, n, workspace, workspace_bytes, &items);
+  if (rc != CURV_OK) return rc;
+  for (int i = 0; i < n; ++i)
+    if (!dw_project_ok(descs[i], i, name, items[i], true)) return CURV_ERR_INVALID;
+  rc = dw_products(name, stream, items);
+  if (rc != CURV_OK) return rc;
+  return for_arg_batches<DwProject, DW_BATCH, 1>(
+      n, name,
+      [&](int i, DwProject* P, long long* threads) {
+        const DwItem& F = items[i];
+        const curv_persample_dw_project_desc& d = descs[i];
+        P->p = F.p; P->T = d.T; P->W = d.Wt; P->s = d.s; P->y = d.y;
+        P->t_cs = d.t_cs; P->t_rs = d.t_rs; P->w_rs = d.w_rs; P->y_ns = F.N > 1 ? d.y_ns : 0;
+        P->Cn = F.C; P->n_g = F.n_g; P->per = (long long)F.N * F.C * F.n_g;
+        threads[0] = (long long)align_up((size_t)P->per, DW_THREADS);      // an item's threads fill whole workgroups
+      },
+      [](int, long long threads) { return threads / DW_THREADS; },
+      [&](const DwProjectBatch* b, const long long*, const unsigned* grid) {
+        hipLaunchKernelGGL(ps_dw_project_kernel, dim3(grid[0]), dim3(DW_THREADS), 0, stream, b[0]);
+        CURV_LAUNCH_CHECK();
+        return CURV_OK;
+      });
+}
+
+extern "C" int curv_persample_dw_quad_grid_reduce(void* stream_, const curv_persample_dw_grid_desc* descs, int n,
+                                                  void* workspace, size_t workspace_bytes) {
+  const char* const name = "curv_persample_dw_quad_grid_reduce";
+  if (n <= 0) return CURV_OK;
+  hipStream_t stream = (hipStream_t)stream_;
+  std::vector<DwItem> items;
+  int rc = dw_plan(name, descs, n, workspace, workspace_bytes, &items);
+  if (rc != CURV_OK) return rc;
+  for (int i = 0; i < n; ++i)
+    if (!dw_grid_ok(descs[i], i, name, items[i], true)) return CURV_ERR_INVALID;
+  rc = dw_products(name, stream, items);
+  if (rc != CURV_OK) return rc;
+  return for_arg_batches<DwGrid, DW_GRID_BATCH, 1>(
+      n, name,
+      [&](int i, DwGrid* Q, long long* blocks) {
+        const DwItem& F = items[i];
+        const curv_persample_dw_grid_desc& d = descs[i];
+        Q->p = F.p; Q->T = d.T; Q->u = d.u; Q->v = d.u ? d.v : d.V; Q->out = d.out;
+        Q->t_cs = d.t_cs; Q->t_rs = d.t_rs; Q->v_rs = d.v_rs; Q->o_stride = d.o_stride; Q->o_hs = d.o_hs;
+        Q->Cn = F.C; Q->n_g = F.n_g; Q->H = d.Hn; Q->first = d.first ? 1 : 0;
+        for (int h = 0; h < DW_GRID_MAX; ++h) {                            // (the slots from H on repeat the last point)
+          Q->shift[h] = d.shift[std::min(h, d.Hn - 1)];
+          Q->gain[h] = d.gain[std::min(h, d.Hn - 1)];
+        }
+        blocks[0] = F.N;
+      },
+      [](int, long long blocks) { return blocks; },
+      [&](const DwGridBatch* b, const long long*, const unsigned* grid) {
+        hipLaunchKernelGGL(ps_dw_grid_kernel, dim3(grid[0]), dim3(DW_THREADS), 0, stream, b[0]);
+        CURV_LAUNCH_CHECK();
+        return CURV_OK;
+      });
+}
+
+extern "C" int curv_persample_gram_reduce(void* stream_, const curv_persample_gram_desc* descs, int n) {
+  const char* const name = "curv_persample_gram_reduce";
+  if (n <= 0) return CURV_OK;
+  hipStream_t stream = (hipStream_t)stream_;
+  CURV_REQUIRE(descs, "%s: null descriptors", name);
+  for (int i = 0; i < n; ++i) {
+    const curv_persample_gram_desc& d = descs[i];
+    CURV_REQUIRE(d.K >= 1 && d.K <= GRAM_MAX_K, "%s: item %d: K %d (1 to %d outputs)", name, i, d.K, GRAM_MAX_K);
+    CURV_REQUIRE(d.N >= 1 && d.E >= 1, "%s: item %d: invalid sizes (N %d, E %d)", name, i, d.N, d.E);
+    CURV_REQUIRE(d.y_ks >= 0 && d.y_ns >= 0, "%s: item %d: negative stride of Y", name, i);
+    CURV_REQUIRE(d.o_rs >= d.K && (d.N == 1 || d.o_ns >= d.K * d.o_rs), "%s: item %d: o_rs %lld below K = %d or o_ns %lld "
+                 "below K o_rs", name, i, d.o_rs, d.K, d.o_ns);
+    CURV_REQUIRE(d.Y && d.out, "%s: item %d: null operand or destination", name, i);
+    CURV_REQUIRE(((reinterpret_cast<uintptr_t>(d.Y) | reinterpret_cast<uintptr_t>(d.out)) & 3) == 0,
+                 "%s: item %d: an address is not aligned to its 4-byte elements", name, i);
+  }
+  // the items of one compiled-in width share their launches, in call order
+  const int widths[] = {1, 4, 8, 16};
+  for (int KT : widths) {
+    std::vector<int> same;
+    for (int i = 0; i < n; ++i) {
+      int kt = 1;
+      while (kt < descs[i].K) kt = kt == 1 ? 4 : 2 * kt;
+      if (kt == KT) same.push_back(i);
+    }
+    const int rc = for_arg_batches<GramItem, DW_BATCH, 1>(
+        (int)same.size(), name,
+        [&](int k, GramItem* G, long long* blocks) {
+          const curv_persample_gram_desc& d = descs[same[k]];
+          G->Y = d.Y; G->out = d.out;
+          G->y_ks = d.K > 1 ? d.y_ks : 0; G->y_ns = d.N > 1 ? d.y_ns : 0; G->o_ns = d.N > 1 ? d.o_ns : 0; G->o_rs = d.o_rs;
+          G->K = d.K; G->E = d.E; G->first = d.first ? 1 : 0; G->alpha = d.alpha;
+          blocks[0] = d.N;
+        },
+        [](int, long long blocks) { return blocks; },
+        [&](const GramBatch* b, const long long*, const unsigned* grid) {
+          switch (KT) {
+            case 1: hipLaunchKernelGGL(ps_gram_kernel<1>, dim3(grid[0]), dim3(DW_THREADS), 0, stream, b[0]); break;
+            case 4: hipLaunchKernelGGL(ps_gram_kernel<4>, dim3(grid[0]), dim3(DW_THREADS), 0, stream, b[0]); break;
+            case 8: hipLaunchKernelGGL(ps_gram_kernel<8>, dim3(grid[0]), dim3(DW_THREADS), 0, stream, b[0]); break;
+            default: hipLaunchKernelGGL(ps_gram_kernel<16>, dim3(grid[0]), dim3(DW_THREADS), 0, stream, b[0]); break;
+          }
+          CURV_LAUNCH_CHECK();
+          return CURV_OK;
+        });
+    if (rc != CURV_OK) return rc;
+  }
+  return CURV_OK;
 }

@@ -523,7 +523,8 @@ class Curvature(ABC):
         under the same restrictions and, for the estimators that treat a MultiheadAttention module as its two projections
         (KFAC, EFB), those two `AttentionProjection`s.  Any other raises NotImplementedError naming it.  `grouped`: the
         caller takes grouped Conv2d layers (`ops.per_sample_route`: as group slices or by the depthwise kernel); they
-        pass only with `ops.admit_grouped_per_sample` on, and a caller that does not take them then says who does."""
+        pass only with `ops.admit_grouped_per_sample` on, and a caller that does not take them then says who does
+        (`stage_output` and `functional_variance_grid` take them with `ops.admit_grouped_joint` on as well)."""
         names = {mod: name for name, mod in self.model.named_modules()}
         wide = ops.per_sample_is_wide()
         groups_on = ops.per_sample_admits_groups()
@@ -537,7 +538,9 @@ class Curvature(ABC):
                 if int(layer.groups) != 1 and not (grouped and groups_on and kind == 'Conv2d'):
                     why = f"grouped convolution (groups={layer.groups})"
                     if groups_on and kind == 'Conv2d':
-                        why += "; Diagonal(per_sample=True) and functional_variance take it"
+                        why += "; Diagonal(per_sample=True) and the linearised predictive of KFAC and Diagonal take it" \
+                            if ops.per_sample_admits_grouped_joint() else \
+                            "; Diagonal(per_sample=True) and functional_variance take it"
                 elif tuple(layer.dilation) != (1, 1):
                     why = "dilated convolution"
                 elif not all(isinstance(p, int) for p in layer.padding):
@@ -682,7 +685,9 @@ class Curvature(ABC):
         run as chunks of that many over the same operands.  Needs `state` only, not `inv_state`; KFAC needs
         `KFAC.decompose()` after its last `update()`.  Records, layers, ``inputs=False`` (the kept X side is entry
         ``"grid"`` of ``_predictive_kept``; `evaluate.glm_predictive_grid` drops it) and the refusal of a layer-sharded
-        estimator as for `functional_variance`.  Implemented by KFAC, Diagonal and EFB."""
+        estimator as for `functional_variance` - except that a grouped Conv2d needs `ops.admit_grouped_joint` beside
+        `ops.admit_grouped_per_sample` (KFAC, Diagonal): its group slices then are layers with their group's spectra, and a
+        depthwise layer takes `ops.per_sample_dw_quad_grid_reduce` on its records.  Implemented by KFAC, Diagonal and EFB."""
         raise NotImplementedError(f"{type(self).__name__}.functional_variance_grid: no linearised predictive for this "
                                   "estimator (KFAC, Diagonal and EFB have one)")
 
@@ -695,7 +700,11 @@ class Curvature(ABC):
         staged).  The stack and the X side stay on the estimator (entry ``"covariance"`` of ``_predictive_kept``) until the
         next ``inputs=True`` call replaces them (`evaluate.glm_predictive_joint` drops them); nothing else may use the
         per-sample scratch in between.  RuntimeError without ``inputs=True`` on these very recorded inputs (tensor and version) and `count`
-        before.  Layers, records and estimators as for `functional_variance`."""
+        before.  Layers, records and estimators as for `functional_variance` - except that a grouped Conv2d needs
+        `ops.admit_grouped_joint` beside `ops.admit_grouped_per_sample` (KFAC, Diagonal).  Its group slices then are layers
+        (those that read the record in place share one copy of it per slot); a depthwise layer has no g side to stage:
+        its transformed products ``s w (T^T p)`` (`ops.per_sample_dw_project`) go into slot `slot` of a (count, N, C n_g)
+        stack kept beside the others, and nothing of its X is kept."""
         raise NotImplementedError(f"{type(self).__name__}.stage_output: no linearised predictive for this estimator "
                                   "(KFAC, Diagonal and EFB have one)")
 
@@ -706,7 +715,8 @@ class Curvature(ABC):
         map whose squared norm `functional_variance` sums (L_G^T P L_A, inv * P, inv * (U_G^T P U_A)).  `out`: a contiguous
         (N, count, count) float32 GPU tensor; both triangles are written and are bit-for-bit symmetric; its diagonal is
         what `functional_variance` gives for each output.  One pass over the products (`ops.per_sample_cov_reduce`): the X
-        side of a layer is staged once for all outputs, no P is written.  RuntimeError if a slot has not been staged since
+        side of a layer is staged once for all outputs, no P is written (a depthwise layer: the Gram of its staged rows,
+        `ops.per_sample_gram_reduce`).  RuntimeError if a slot has not been staged since
         the last ``stage_output(inputs=True)`` or the recorded inputs are no longer those tensors.  At most
         `ops.PERSAMPLE_COV_MAX_OUTPUTS` outputs.  Implemented by KFAC, Diagonal and EFB."""
         raise NotImplementedError(f"{type(self).__name__}.functional_covariance: no linearised predictive for this "
@@ -946,9 +956,11 @@ class Diagonal(LinearisedPredictive, Curvature):
         # grid: inv**2 = 1 / (s state + n) = (1 / s) / (state + n / s)
         def weights(layer):                                # (a group slice: its row block of the layer's matrix)
             return self.inv_state[layer.layer][layer.rows] if isinstance(layer, ops.GroupSlice) else self.inv_state[layer]
-        return PredictiveTerms("Diagonal", basis=None, weights=weights, grid_basis=None,
-                               spectrum=lambda layer: (None, None, self.state[layer]), separable=False,
-                               direct=lambda layer: (None, self.inv_state[layer], None))
+        def spectrum(layer):
+            return None, None, self.state[layer.layer][layer.rows] if isinstance(layer, ops.GroupSlice) else self.state[layer]
+        return PredictiveTerms("Diagonal", basis=None, weights=weights, grid_basis=None, spectrum=spectrum, separable=False,
+                               direct=lambda layer: (None, self.inv_state[layer], None),
+                               direct_grid=lambda layer: (None, None, None, self.state[layer]))
 
     def sample(self, layer: Union[Module, str], z: Optional[Tensor] = None) -> Tensor:
         assert self.inv_state, "Inverse state dict is empty. Did you call 'invert' prior to this?"
@@ -1350,28 +1362,57 @@ class KFAC(LinearisedPredictive, Curvature):
             if isinstance(layer, ops.GroupSlice):
                 return tuple(f[layer.g].t() for f in reversed(self.inv_state[layer.layer]))
             return tuple(f.t() for f in reversed(self.inv_state[layer]))
+        def eigen(layer):                                  # (a group slice: its group of the stacked decomposition)
+            if isinstance(layer, ops.GroupSlice):
+                return tuple(t[layer.g] for t in kept[layer.layer][:4])
+            return kept[layer]
         return PredictiveTerms(
             "KFAC", basis=basis, weights=None,
-            grid_basis=lambda layer: kept[layer][:2], spectrum=lambda layer: (kept[layer][2], kept[layer][3], None),
+            grid_basis=lambda layer: eigen(layer)[:2], spectrum=lambda layer: (eigen(layer)[2], eigen(layer)[3], None),
             separable=True, grid_missing=None if kept is not None else
             "no eigendecomposition of the current factors: call decompose() after the last update()",
             # depthwise (one output channel per group): T = L_A stacked (C, n_g, n_g), s = L_G stacked (C, 1, 1), in place
-            direct=lambda layer: (self.inv_state[layer][0], None, self.inv_state[layer][1]))
+            direct=lambda layer: (self.inv_state[layer][0], None, self.inv_state[layer][1]),
+            # its grid: T = U_A stacked, u = the 1 x 1 G factors (their own eigenvalues), v = eig(A) (C, n_g)
+            direct_grid=lambda layer: (kept[layer][4], kept[layer][2].view(-1), kept[layer][3], None))
 
     def decompose(self) -> None:
         """The eigendecompositions F = U diag(lambda) U^T of the accumulated factors of every owned layer, in one batched
         `ops.eigh`: what `functional_variance_grid` needs instead of an inversion.  Kept per layer as
         ``(U_G^T, U_A^T, lambda_G, lambda_A)``, the eigenvalues clamped at 0 (a factor is positive semi-definite; the
         iteration may leave -1e-9); `update()` and `restart_accumulation()` drop it.  Grouped layers (stacked factors)
-        have no per-sample form and are left out."""
+        are left out - unless `ops.admit_grouped_per_sample` and `ops.admit_grouped_joint` are both on: then the per-group
+        matrices go into the same `ops.eigh` call (a 1 x 1 factor is its own eigenvalue and does not) and the result stays
+        stacked, ``(U_G^T (G, m, m), U_A^T (G, n, n), lambda_G (G, m), lambda_A (G, n))``, for a depthwise layer
+        (`ops.per_sample_route`) with U_A (G, n, n) itself as a fifth entry, which its grid job reads."""
         assert self.state, "State dict is empty. Did you call 'update' prior to this?"
-        layers = [l for l, (A, G) in self.state.items() if A.dim() == 2 and G.dim() == 2]
-        vecs, vals = ops.eigh([f for l in layers for f in self.state[l]], with_values=True) if layers else ([], [])
+        stacked = ops.per_sample_admits_groups() and ops.per_sample_admits_grouped_joint()
+        layers = [l for l, (A, G) in self.state.items() if (A.dim() == 2 and G.dim() == 2) or
+                  (stacked and A.dim() == 3 and G.dim() == 3)]
+
+        def solved(F):                                     # the 2-D matrices of a factor that go to the solver
+            return [F] if F.dim() == 2 else [f for f in F if f.shape[-1] > 1]
+        mats = [f for l in layers for F in self.state[l] for f in solved(F)]
+        vecs, vals = ops.eigh(mats, with_values=True) if mats else ([], [])
         self._decomposition = {}
-        for k, layer in enumerate(layers):
-            (U_A, U_G), (lam_A, lam_G) = vecs[2 * k:2 * k + 2], vals[2 * k:2 * k + 2]
-            self._decomposition[layer] = (U_G.t().contiguous(), U_A.t().contiguous(), ops.clamp_min0_(lam_G),
-                                          ops.clamp_min0_(lam_A))
+        at = 0
+        for layer in layers:
+            sides = []                                     # (U, lambda) of the A and of the G side
+            for F in self.state[layer]:
+                count = len(solved(F))
+                U, lam = vecs[at:at + count], vals[at:at + count]
+                at += count
+                if F.dim() == 2:
+                    sides.append((U[0], ops.clamp_min0_(lam[0])))
+                elif count:
+                    sides.append((torch.stack(U), ops.clamp_min0_(torch.stack(lam))))
+                else:
+                    sides.append((torch.ones_like(F), ops.clamp_min0_(F.reshape(F.shape[0], 1).clone())))
+            (U_A, lam_A), (U_G, lam_G) = sides
+            kept = (U_G.transpose(-1, -2).contiguous(), U_A.transpose(-1, -2).contiguous(), lam_G, lam_A)
+            if U_A.dim() == 3 and ops.per_sample_route(layer) == "depthwise":
+                kept += (U_A,)
+            self._decomposition[layer] = kept
 
     def sample(self, layer: Module, z: Optional[Tensor] = None) -> Tensor:
         """(L_A z L_G^T)^T -> (m, n) (curvatures.py:387-392); `z` (n, m) may be supplied for parity tests."""

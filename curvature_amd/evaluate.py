@@ -244,7 +244,8 @@ def glm_predictive_grid(model: torch.nn.Module, estimator, images: torch.Tensor,
     ``(len(hypers), N, classes)`` - slice h is what ``estimator.invert(*hypers[h])`` followed by `glm_predictive` gives.
     One forward pass and per output one backward pass and one `Curvature.functional_variance_grid` call serve every
     pair (KFAC: after `KFAC.decompose()`); the estimator's `inv_state` is neither needed nor touched.  `outputs`, model
-    mode, hooks, parameters and ``.grad`` as in `glm_predictive`.  GPU only."""
+    mode, hooks, parameters and ``.grad`` as in `glm_predictive`.  A grouped Conv2d needs `ops.admit_grouped_joint`
+    beside `ops.admit_grouped_per_sample` (KFAC, Diagonal; `tune_glm` goes through here).  GPU only."""
     hypers = list(hypers)
     with _linearised("glm_predictive_grid", model, estimator, images, outputs) as (logits, classes, backward):
         N, C = logits.shape
@@ -314,7 +315,9 @@ def glm_predictive_joint(model: torch.nn.Module, estimator, images: torch.Tensor
     `Curvature.functional_covariance`: a single pass over the per-sample products in which the input side of every layer
     is staged once for all outputs.  At most `ops.PERSAMPLE_COV_MAX_OUTPUTS` (16) distinct outputs per call: ValueError
     otherwise (raised after the forward pass, when the class count is known) - pass ``outputs=``, for instance the top-k
-    classes.  Model mode, hooks, parameters and ``.grad`` as in `glm_predictive`.  GPU only."""
+    classes.  Model mode, hooks, parameters and ``.grad`` as in `glm_predictive`.  A grouped Conv2d needs
+    `ops.admit_grouped_joint` beside `ops.admit_grouped_per_sample` (KFAC, Diagonal; `glm_predictive_mc` and
+    ``eval_glm(predictive="mc")`` go through the same passes).  GPU only."""
     logits, covariance, classes = _joint_covariance("glm_predictive_joint", model, estimator, images, outputs)
     variance = torch.zeros(logits.shape, dtype=torch.float32, device=logits.device)
     variance[:, classes] = torch.diagonal(covariance, dim1=1, dim2=2)

@@ -556,7 +556,9 @@ def admit_grouped_per_sample(enable: bool = True) -> bool:
     """Switch grouped convolutions in the per-sample line on or off for the process; returns what it was.  On:
     ``Diagonal(per_sample=True)`` and the `functional_variance` of Diagonal and KFAC take a Conv2d with ``groups > 1``
     (dilation 1, integer padding, float32 records) by the route `per_sample_route` names.  Off: such a layer raises.
-    Independent of `widen_per_sample`."""
+    Independent of `widen_per_sample`.  The other linearised predictives (`stage_output` / `functional_covariance`,
+    `functional_variance_grid`) take such a layer with `admit_grouped_joint` on as well; EFB, INF and
+    ``ConvTranspose2d(groups > 1)`` refuse it either way."""
     global _GROUPS
     was, _GROUPS = _GROUPS, bool(enable)
     return was
@@ -564,6 +566,24 @@ def admit_grouped_per_sample(enable: bool = True) -> bool:
 
 def per_sample_admits_groups() -> bool:
     return _GROUPS
+
+
+# The joint covariance and the damping grid of grouped convolutions have a switch of their own again: off -
+# the default - `stage_output`, `functional_variance_grid` and `KFAC.decompose` are exactly what they were.
+_GROUPS_JOINT = False
+
+
+def admit_grouped_joint(enable: bool = True) -> bool:
+    """Switch grouped convolutions in `stage_output` / `functional_covariance`, `functional_variance_grid` and
+    `KFAC.decompose` on or off for the process; returns what it was.  It has an effect only while
+    `admit_grouped_per_sample` is on as well: alone it admits nothing."""
+    global _GROUPS_JOINT
+    was, _GROUPS_JOINT = _GROUPS_JOINT, bool(enable)
+    return was
+
+
+def per_sample_admits_grouped_joint() -> bool:
+    return _GROUPS_JOINT
 
 
 DW_MAX_TAPS = 49                       # kernel taps up to which a depthwise layer takes the direct kernel
@@ -1177,34 +1197,54 @@ class PerSampleDwJob:
         return cls(x.detach(), g.detach(), layer.kernel_size, layer.stride, layer.padding, layer.bias is not None, **own)
 
 
+def _fill_dw_record(d, j, name: str):
+    """The record, geometry and extent fields every curv_persample_dw_*_desc has, from job `j` (`x` / `g` tensors or, for a
+    plan query, shapes); returns the two shapes."""
+    xs, gs = (tuple(t.shape) if isinstance(t, torch.Tensor) else tuple(t) for t in (j.x, j.g))
+    if len(xs) != 4 or len(gs) != 4 or xs[:2] != gs[:2]:
+        raise RuntimeError(f"{name}: records must be (N, C, H, W) and (N, C, Ho, Wo), got {xs} and {gs}")
+    _set_geometry(d, xs, j.kernel, j.stride, j.padding, j.has_bias)
+    d.Ho, d.Wo = gs[2:]
+    for side, t, shape in (("x", j.x, xs), ("g", j.g, gs)):
+        if isinstance(t, torch.Tensor):
+            strides, elems = t.stride(), _source_extent(t)
+        else:
+            strides, elems = (math.prod(shape[1:]), shape[2] * shape[3], shape[3], 1), math.prod(shape)
+        for k, v in zip(("sn", "sc", "sh", "sw"), strides):
+            setattr(d, f"{side}_{k}", int(v))
+        setattr(d, f"{side}_elems", int(elems))
+    return xs, gs
+
+
+def _fill_dw_pointers(d, j, own) -> None:
+    """The device / dtype checks of the records and of the job's `own` tensors (None among them skipped), and the records'
+    addresses."""
+    for t in (j.x, j.g) + tuple(t for t in own if t is not None):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise RuntimeError("curvature_amd runs on MI355X only: got a CPU tensor (no CPU fallback)")
+        if t.dtype != torch.float32:
+            raise RuntimeError(f"curvature_amd expects float32 tensors, got {t.dtype}")
+    d.x, d.g = j.x.data_ptr(), j.g.data_ptr()
+
+
+def _dw_transform(d, j, name: str, C: int, n_g: int) -> None:
+    """`T` (C, n_g, n_g) of job `j` into descriptor `d`, if it has one."""
+    if j.T is not None:
+        if tuple(j.T.shape) != (C, n_g, n_g) or (n_g > 1 and j.T.stride(2) != 1):
+            raise RuntimeError(f"{name}: T must be a ({C},{n_g},{n_g}) view with unit last stride, got {tuple(j.T.shape)}")
+        d.T, d.t_cs, d.t_rs = j.T.data_ptr(), j.T.stride(0) if C > 1 else n_g * n_g, j.T.stride(1) if n_g > 1 else n_g
+
+
 def _per_sample_dw_descs(jobs: Sequence[PerSampleDwJob], name: str, reduction: Optional[str]):
     """`reduction`: "sq", "quad" or None (a plan query: geometry only, `x` / `g` may be shapes)."""
     arr = (_lib.curv_persample_dw_desc * len(jobs))()
     for d, j in zip(arr, jobs):
-        xs, gs = (tuple(t.shape) if isinstance(t, torch.Tensor) else tuple(t) for t in (j.x, j.g))
-        if len(xs) != 4 or len(gs) != 4 or xs[:2] != gs[:2]:
-            raise RuntimeError(f"{name}: records must be (N, C, H, W) and (N, C, Ho, Wo), got {xs} and {gs}")
-        _set_geometry(d, xs, j.kernel, j.stride, j.padding, j.has_bias)
-        d.Ho, d.Wo = gs[2:]
+        xs, gs = _fill_dw_record(d, j, name)
         d.first, d.alpha = int(j.first), j.alpha
-        for side, t, shape in (("x", j.x, xs), ("g", j.g, gs)):
-            if isinstance(t, torch.Tensor):
-                strides, elems = t.stride(), _source_extent(t)
-            else:
-                strides, elems = (math.prod(shape[1:]), shape[2] * shape[3], shape[3], 1), math.prod(shape)
-            for k, v in zip(("sn", "sc", "sh", "sw"), strides):
-                setattr(d, f"{side}_{k}", int(v))
-            setattr(d, f"{side}_elems", int(elems))
         if reduction is None:
             continue
         C, n_g = xs[1], j.kernel[0] * j.kernel[1] + int(j.has_bias)
-        own = (j.dst,) if reduction == "sq" else (j.out, j.T, j.W, j.s)
-        for t in (j.x, j.g) + tuple(t for t in own if t is not None):
-            if not isinstance(t, torch.Tensor) or not t.is_cuda:
-                raise RuntimeError("curvature_amd runs on MI355X only: got a CPU tensor (no CPU fallback)")
-            if t.dtype != torch.float32:
-                raise RuntimeError(f"curvature_amd expects float32 tensors, got {t.dtype}")
-        d.x, d.g = j.x.data_ptr(), j.g.data_ptr()
+        _fill_dw_pointers(d, j, (j.dst,) if reduction == "sq" else (j.out, j.T, j.W, j.s))
         if reduction == "sq":
             if j.dst is None or j.dst.dim() != 2 or tuple(j.dst.shape) != (C, n_g) or j.dst.stride(1) != 1:
                 raise RuntimeError(f"{name}: destination must be a ({C},{n_g}) view with unit column stride, got "
@@ -1215,10 +1255,7 @@ def _per_sample_dw_descs(jobs: Sequence[PerSampleDwJob], name: str, reduction: O
             raise RuntimeError(f"{name}: destination must be a length-{xs[0]} view with a positive stride, got "
                                f"{None if j.out is None else tuple(j.out.shape)}")
         d.out, d.o_stride = j.out.data_ptr(), max(j.out.stride(0), 1)
-        if j.T is not None:
-            if tuple(j.T.shape) != (C, n_g, n_g) or (n_g > 1 and j.T.stride(2) != 1):
-                raise RuntimeError(f"{name}: T must be a ({C},{n_g},{n_g}) view with unit last stride, got {tuple(j.T.shape)}")
-            d.T, d.t_cs, d.t_rs = j.T.data_ptr(), j.T.stride(0) if C > 1 else n_g * n_g, j.T.stride(1) if n_g > 1 else n_g
+        _dw_transform(d, j, name, C, n_g)
         if j.W is not None:
             if tuple(j.W.shape) != (C, n_g) or (n_g > 1 and j.W.stride(1) != 1):
                 raise RuntimeError(f"{name}: W must be a ({C},{n_g}) view with unit column stride, got {tuple(j.W.shape)}")
@@ -1259,6 +1296,188 @@ def per_sample_dw_quad_reduce(jobs: Sequence[PerSampleDwJob]) -> None:
     _run_build("curv_persample_dw_workspace_bytes", "curv_persample_dw_quad_reduce",
                _per_sample_dw_descs(jobs, "per_sample_dw_quad_reduce", "quad"), len(jobs), jobs[0].out.device,
                "persample_dw")
+
+
+class PerSampleDwProjectJob(PerSampleDwJob):
+    """``y[n, c n_g + j] = s[c] W[c, j] sum_i T[c, i, j] p[n, c, i]`` of a depthwise layer (`per_sample_dw_project`): records
+    and geometry as in `PerSampleDwJob`, `T`, `W` (not squared) and `s` likewise, each or all None; `y` an (N, C n_g) float32
+    view with unit last stride (a slot of a staged stack).  `x` / `g` may also be shapes (plan queries)."""
+    __slots__ = ("y",)
+
+    def __init__(self, x, g, kernel, stride=(1, 1), padding=(0, 0), has_bias=False, y=None, T=None, W=None, s=None):
+        super().__init__(x, g, kernel, stride, padding, has_bias, T=T, W=W, s=s)
+        self.y = y
+
+
+class PerSampleDwGridJob(PerSampleDwJob):
+    """``out[h, n] (+)= gain[h] sum_cj w_h[c, j] (sum_i T[c, i, j] p[n, c, i])**2`` of a depthwise layer for the H grid points
+    ``(shift[h], gain[h])`` (`per_sample_dw_quad_grid_reduce`; at most `PERSAMPLE_GRID_MAX`): records, geometry and `T` as
+    in `PerSampleDwJob`.  The weights are separable, ``w_h[c, j] = 1 / ((u[c] + shift[h]) (v[c, j] + shift[h]))`` with `u` C
+    contiguous values and `v` a (C, n_g) view with unit column stride, or dense, ``w_h[c, j] = 1 / (V[c, j] + shift[h])``
+    with `V` such a view: give `u` and `v`, or `V`.  `shift` (finite, > 0) and `gain` (finite) are sequences of H Python
+    floats; `out` an (H, N) float32 view with positive strides.  There is no `alpha`.  `x` / `g` may also be shapes
+    (plan queries)."""
+    __slots__ = ("u", "v", "V", "shift", "gain")
+
+    def __init__(self, x, g, kernel, stride=(1, 1), padding=(0, 0), has_bias=False, out=None, T=None, u=None, v=None, V=None,
+                 shift=(), gain=(), first=False):
+        super().__init__(x, g, kernel, stride, padding, has_bias, out=out, T=T, first=first)
+        self.u, self.v, self.V = u, v, V
+        self.shift, self.gain = [float(x) for x in shift], [float(x) for x in gain]
+
+
+def _per_sample_dw_project_descs(jobs: Sequence[PerSampleDwProjectJob], name: str, check_tensors: bool = True):
+    arr = (_lib.curv_persample_dw_project_desc * len(jobs))()
+    for d, j in zip(arr, jobs):
+        xs, _ = _fill_dw_record(d, j, name)
+        N, C, n_g = xs[0], xs[1], j.kernel[0] * j.kernel[1] + int(j.has_bias)
+        d.y_ns = C * n_g
+        if not check_tensors:
+            continue
+        _fill_dw_pointers(d, j, (j.y, j.T, j.W, j.s))
+        if j.y is None or j.y.dim() != 2 or tuple(j.y.shape) != (N, C * n_g) or (C * n_g > 1 and j.y.stride(1) != 1) or \
+                (N > 1 and j.y.stride(0) < C * n_g):
+            raise RuntimeError(f"{name}: destination must be an ({N},{C * n_g}) view with unit last stride and rows that do "
+                               f"not overlap, got {None if j.y is None else tuple(j.y.shape)}")
+        d.y, d.y_ns = j.y.data_ptr(), j.y.stride(0) if N > 1 else C * n_g
+        _dw_transform(d, j, name, C, n_g)
+        if j.W is not None:
+            if tuple(j.W.shape) != (C, n_g) or (n_g > 1 and j.W.stride(1) != 1):
+                raise RuntimeError(f"{name}: W must be a ({C},{n_g}) view with unit column stride, got {tuple(j.W.shape)}")
+            d.Wt, d.w_rs = j.W.data_ptr(), j.W.stride(0) if C > 1 else n_g
+        if j.s is not None:
+            if j.s.numel() != C or not j.s.is_contiguous():
+                raise RuntimeError(f"{name}: s must hold {C} contiguous values, got {tuple(j.s.shape)}")
+            d.s = j.s.data_ptr()
+    return arr
+
+
+def _per_sample_dw_grid_descs(jobs: Sequence[PerSampleDwGridJob], name: str, check_tensors: bool = True):
+    arr = (_lib.curv_persample_dw_grid_desc * len(jobs))()
+    keep = []                                        # the host tables the descriptors point to
+    for d, j in zip(arr, jobs):
+        H = len(j.shift)
+        if not 1 <= H <= PERSAMPLE_GRID_MAX or len(j.gain) != H:
+            raise ValueError(f"{name}: {H} shifts and {len(j.gain)} gains; a job takes 1 to {PERSAMPLE_GRID_MAX} grid "
+                             "points, as many gains as shifts")
+        for h, (s, g) in enumerate(zip(j.shift, j.gain)):
+            if not (s > 0 and math.isfinite(s) and math.isfinite(g)):
+                raise ValueError(f"{name}: grid point {h}: shift {s} must be finite and > 0, gain {g} finite")
+        xs, _ = _fill_dw_record(d, j, name)
+        N, C, n_g = xs[0], xs[1], j.kernel[0] * j.kernel[1] + int(j.has_bias)
+        d.Hn, d.first = H, int(j.first)
+        tables = ((ctypes.c_float * H)(*j.shift), (ctypes.c_float * H)(*j.gain))
+        keep.append(tables)
+        d.shift, d.gain = ctypes.cast(tables[0], ctypes.POINTER(ctypes.c_float)), ctypes.cast(tables[1], ctypes.POINTER(ctypes.c_float))
+        d.v_rs, d.o_stride, d.o_hs = n_g, 1, N
+        if not check_tensors:
+            continue
+        separable = j.V is None
+        if (j.u is None) != (j.v is None) or separable == (j.u is None):
+            raise RuntimeError(f"{name}: give the weights as u and v (separable) or as V (dense), not both")
+        _fill_dw_pointers(d, j, (j.out, j.T, j.u, j.v, j.V))
+        _dw_transform(d, j, name, C, n_g)
+        table = j.v if separable else j.V
+        if tuple(table.shape) != (C, n_g) or (n_g > 1 and table.stride(1) != 1):
+            raise RuntimeError(f"{name}: {'v' if separable else 'V'} must be a ({C},{n_g}) view with unit column stride, got "
+                               f"{tuple(table.shape)}")
+        d.v_rs = table.stride(0) if C > 1 else n_g
+        if separable:
+            if j.u.numel() != C or not j.u.is_contiguous():
+                raise RuntimeError(f"{name}: u must hold {C} contiguous values, got {tuple(j.u.shape)}")
+            d.u, d.v = j.u.data_ptr(), j.v.data_ptr()
+        else:
+            d.V = j.V.data_ptr()
+        if j.out is None or j.out.dim() != 2 or tuple(j.out.shape) != (H, N) or (N > 1 and j.out.stride(1) < 1) or \
+                (H > 1 and j.out.stride(0) < 1):
+            raise RuntimeError(f"{name}: destination must be an ({H},{N}) view with positive strides, got "
+                               f"{None if j.out is None else tuple(j.out.shape)}")
+        d.out, d.o_stride, d.o_hs = j.out.data_ptr(), max(j.out.stride(1), 1), max(j.out.stride(0), 1)
+    arr._tables = keep
+    return arr
+
+
+def _dw_plan_info(symbol: str, arr, n: int):
+    flops, nbytes = (ctypes.c_longlong * n)(), (ctypes.c_longlong * n)()
+    _lib.check(getattr(_lib.lib(), symbol)(arr, n, flops, nbytes), symbol)
+    return [int(v) for v in flops], [int(v) for v in nbytes]
+
+
+def per_sample_dw_project_plan_info(jobs: Sequence[PerSampleDwProjectJob]):
+    """(flops, bytes) per job (curv_persample_dw_project_plan_info, host only): those of `per_sample_dw_plan_info` plus the
+    transform by T and the N C n_g values written."""
+    if not jobs:
+        return [], []
+    return _dw_plan_info("curv_persample_dw_project_plan_info",
+                         _per_sample_dw_project_descs(jobs, "per_sample_dw_project_plan_info", False), len(jobs))
+
+
+def per_sample_dw_quad_grid_plan_info(jobs: Sequence[PerSampleDwGridJob]):
+    """(flops, bytes) per job (curv_persample_dw_quad_grid_plan_info, host only): those of `per_sample_dw_plan_info` plus the
+    transform by T and the H weighted sums."""
+    if not jobs:
+        return [], []
+    return _dw_plan_info("curv_persample_dw_quad_grid_plan_info",
+                         _per_sample_dw_grid_descs(jobs, "per_sample_dw_quad_grid_plan_info", False), len(jobs))
+
+
+def per_sample_dw_project(jobs: Sequence[PerSampleDwProjectJob]) -> None:
+    """``y[n, c n_g + j] = s[c] W[c, j] sum_i T[c, i, j] p[n, c, i]`` for every job (curv_persample_dw_project), on the
+    current stream; the products p from `workspace`."""
+    if not jobs:
+        return
+    _run_build("curv_persample_dw_project_workspace_bytes", "curv_persample_dw_project",
+               _per_sample_dw_project_descs(jobs, "per_sample_dw_project"), len(jobs), jobs[0].y.device, "persample_dw")
+
+
+def per_sample_dw_quad_grid_reduce(jobs: Sequence[PerSampleDwGridJob]) -> None:
+    """``out[h, n] (+)= gain[h] sum_cj w_h[c, j] (sum_i T[c, i, j] p[n, c, i])**2`` for every job
+    (curv_persample_dw_quad_grid_reduce), on the current stream; the products p from `workspace`."""
+    if not jobs:
+        return
+    _run_build("curv_persample_dw_quad_grid_workspace_bytes", "curv_persample_dw_quad_grid_reduce",
+               _per_sample_dw_grid_descs(jobs, "per_sample_dw_quad_grid_reduce"), len(jobs), jobs[0].out.device,
+               "persample_dw")
+
+
+class PerSampleGramJob:
+    """``out[n, k, k'] (+)= alpha sum_e Y[k, n, e] Y[k', n, e]`` (`per_sample_gram_reduce`): `Y` a (K, N, E) float32 view with
+    unit last stride (K at most `PERSAMPLE_COV_MAX_OUTPUTS`; a staged stack of `per_sample_dw_project` rows), `out` an
+    (N, K, K) view with unit last stride, as `PerSampleCovJob` takes it.  `first`: overwrite out."""
+    __slots__ = ("Y", "out", "alpha", "first")
+
+    def __init__(self, Y, out, alpha=1.0, first=False):
+        self.Y, self.out, self.alpha, self.first = Y, out, float(alpha), bool(first)
+
+
+def per_sample_gram_reduce(jobs: Sequence[PerSampleGramJob]) -> None:
+    """curv_persample_gram_reduce over any number of jobs, on the current stream (no workspace).  The jobs of a call must
+    not share destinations."""
+    if not jobs:
+        return
+    name = "per_sample_gram_reduce"
+    arr = (_lib.curv_persample_gram_desc * len(jobs))()
+    for d, j in zip(arr, jobs):
+        for t in (j.Y, j.out):
+            if not t.is_cuda:
+                raise RuntimeError("curvature_amd runs on MI355X only: got a CPU tensor (no CPU fallback)")
+            if t.dtype != torch.float32:
+                raise RuntimeError(f"curvature_amd expects float32 tensors, got {t.dtype}")
+        if j.Y.dim() != 3 or not 1 <= j.Y.shape[0] <= PERSAMPLE_COV_MAX_OUTPUTS or j.Y.shape[2] < 1 or \
+                (j.Y.shape[2] > 1 and j.Y.stride(2) != 1) or min(j.Y.stride()) < 0:
+            raise RuntimeError(f"{name}: Y must be a (K, N, E) view with unit last stride, 1 <= K <= "
+                               f"{PERSAMPLE_COV_MAX_OUTPUTS}, got {tuple(j.Y.shape)}")
+        K, N, E = map(int, j.Y.shape)
+        if j.out.dim() != 3 or tuple(j.out.shape) != (N, K, K) or (K > 1 and j.out.stride(2) != 1):
+            raise RuntimeError(f"{name}: destination must be an ({N},{K},{K}) view with unit last stride, got "
+                               f"{tuple(j.out.shape)}")
+        d.Y, d.out, d.N, d.K, d.E = j.Y.data_ptr(), j.out.data_ptr(), N, K, E
+        d.y_ks, d.y_ns = j.Y.stride(0) if K > 1 else 0, j.Y.stride(1) if N > 1 else 0
+        # (the stride of a dimension of size 1 says nothing: take the smallest the library allows)
+        d.o_rs = j.out.stride(1) if K > 1 else K
+        d.o_ns = j.out.stride(0) if N > 1 else K * d.o_rs
+        d.first, d.alpha = int(j.first), j.alpha
+    _lib.check(_lib.lib().curv_persample_gram_reduce(_lib.stream_ptr(), arr, len(arr)), "curv_persample_gram_reduce")
 
 
 def per_sample_scratch(floats: Sequence[int], device, tag: str = "persample_x") -> List[torch.Tensor]:

@@ -30,6 +30,13 @@ class PredictiveTerms(NamedTuple):
     grid_missing: Optional[str] = None
     direct: Optional[Callable] = None          # ``direct(layer)`` = (T, w, s) of a depthwise layer for `ops.PerSampleDwJob`
                                                # (w not yet squared; each may be None)
+    direct_grid: Optional[Callable] = None     # ``direct_grid(layer)`` = (T, u, v, V) of a depthwise layer for
+                                               # `ops.PerSampleDwGridJob`: separable (u, v) or dense (V) grid weights
+
+
+def _module_of(layer):
+    """The module whose records and hyperparameters an item of the per-sample line has: a group slice's grouped layer."""
+    return layer.layer if isinstance(layer, ops.GroupSlice) else layer
 
 
 class LinearisedPredictive:
@@ -68,7 +75,7 @@ class LinearisedPredictive:
         operands = self._per_sample_operands(what, layers, x_side=inputs, **layout) if layers else []
         if check is not None:
             check(operands[0][0].N if operands else int(direct[0][1].shape[0]))
-        inputs_of = [self.record[l.layer if isinstance(l, ops.GroupSlice) else l][0] for l in layers]
+        inputs_of = [self.record[_module_of(l)][0] for l in layers]
         key = tuple((l, id(x), x._version, s.n, s.N, s.L, s.x.ns, s.x.rs)
                     for l, x, (s, _, _) in zip(layers, inputs_of, operands)) + \
             tuple((l, id(x), x._version, tuple(x.shape), tuple(x.stride())) for l, x, _ in direct)
@@ -168,22 +175,29 @@ class LinearisedPredictive:
                     not out.is_contiguous():
                 raise RuntimeError(f"{what}.functional_variance_grid: out must be a contiguous float32 GPU tensor of shape "
                                    f"({len(hypers)}, {N}), got {tuple(out.shape)} {out.dtype} on {out.device}")
-        layers, operands, key, _ = self._predictive_operands(what, "functional_variance_grid", inputs, basis is not None,
-                                                             check, select="state")
+        layers, operands, key, direct = self._predictive_operands(what, "functional_variance_grid", inputs,
+                                                                  basis is not None, check, select="state",
+                                                                  grouped=ops.per_sample_admits_grouped_joint())
         if inputs:
             xs, _ = self._x_side("grid", layers, operands, basis, None)
             self._kept()["grid"] = dict(key=key, xs=xs)
         xs = self._kept_entry(what, "functional_variance_grid", "grid", key)["xs"]
         gs = self._g_side(layers, operands, basis)
-        tables = [points(l) for l in layers]
-        N, dev = operands[0][0].N, operands[0][1].device
+        tables = [points(_module_of(l)) for l in layers]
+        # a depthwise layer: one grid job on its records, with the grid terms of its stacked factors
+        direct = [(l, x, g, terms.direct_grid(l), points(l)) for l, x, g in direct]
+        N, dev = out.shape[1], out.device
         # chunks of PERSAMPLE_GRID_MAX pairs over the same operands; every layer into its own (pairs, N) block
         for h0 in range(0, len(hypers), ops.PERSAMPLE_GRID_MAX):
             h1 = min(h0 + ops.PERSAMPLE_GRID_MAX, len(hypers))
-            rows = torch.empty(len(layers), h1 - h0, N, dtype=torch.float32, device=dev)
+            rows = torch.empty(len(layers) + len(direct), h1 - h0, N, dtype=torch.float32, device=dev)
             ops.per_sample_quad_grid_reduce([
                 ops.PerSampleGridJob.of(s, g, x, *spectrum(l), rows[k], shifts[h0:h1], gains[h0:h1], first=True)
                 for k, (l, (s, _, _), g, x, (shifts, gains)) in enumerate(zip(layers, operands, gs, xs, tables))])
+            ops.per_sample_dw_quad_grid_reduce([
+                ops.PerSampleDwGridJob.of(l, x, g, out=rows[len(layers) + k], T=T, u=u, v=v, V=V, shift=shifts[h0:h1],
+                                          gain=gains[h0:h1], first=True)
+                for k, (l, x, g, (T, u, v, V), (shifts, gains)) in enumerate(direct)])
             self._sum_layers(rows, out[h0:h1].view(1, -1), first)
         return out
 
@@ -194,21 +208,48 @@ class LinearisedPredictive:
         slot, count = int(slot), int(count)
         if not 1 <= count <= ops.PERSAMPLE_COV_MAX_OUTPUTS or not 0 <= slot < count:
             raise ValueError(f"{what}.stage_output: slot {slot} of {count} (at most {ops.PERSAMPLE_COV_MAX_OUTPUTS} outputs)")
-        layers, operands, key, _ = self._predictive_operands(what, "stage_output", inputs, basis is not None)
+        layers, operands, key, direct = self._predictive_operands(what, "stage_output", inputs, basis is not None,
+                                                                  grouped=ops.per_sample_admits_grouped_joint())
         if inputs:
             xs, ws = self._x_side("covariance", layers, operands, basis, weights)
-            # a slot is what one output's g side takes: its packed copy, or the record itself where that is read in place
-            sizes = [s.g.floats or s.N * s.g.ns for s, _, _ in operands]
-            stack = ops.per_sample_scratch([count * f for f in sizes], operands[0][1].device, "persample_cov_g")
-            self._kept()["covariance"] = dict(key=key, count=count, xs=xs, ws=ws, sizes=sizes, stack=stack,
-                                              sides=[s for s, _, _ in operands], staged=set(),
-                                              inputs=[self.record[l][0] for l in layers])
+            # a slot is what one output's g side takes: its packed copy, or the record itself where that is read in place.
+            # The slices of a grouped layer that read its record in place share one copy of it per slot and are views into
+            # it: `place` = (buffer, offset) of every item, `whole` = the grouped layer a shared buffer copies
+            sizes, place, whole, shared = [], [], {}, {}
+            for l, (s, _, _) in zip(layers, operands):
+                if isinstance(l, ops.GroupSlice) and not s.g.floats:
+                    if l.layer not in shared:
+                        shared[l.layer] = len(sizes)
+                        whole[len(sizes)] = l.layer
+                        sizes.append(self.record[l.layer][1].numel())
+                    place.append((shared[l.layer], l.rows.start * s.g.rs))
+                else:
+                    place.append((len(sizes), 0))
+                    sizes.append(s.g.floats or s.N * s.g.ns)
+            N = operands[0][0].N if operands else int(direct[0][1].shape[0])
+            dev = operands[0][1].device if operands else direct[0][1].device
+            stack = ops.per_sample_scratch([count * f for f in sizes], dev, "persample_cov_g") if sizes else []
+            # a depthwise layer keeps nothing of X: (T, w, s) and, per slot, the N rows its transformed products take
+            terms = [self._predictive_terms().direct(l) for l, _, _ in direct]
+            projected = [torch.empty(count, N, l.out_channels * (l.kernel_size[0] * l.kernel_size[1] + int(l.bias is not None)),
+                                     dtype=torch.float32, device=dev) for l, _, _ in direct]
+            self._kept()["covariance"] = dict(key=key, count=count, xs=xs, ws=ws, sizes=sizes, stack=stack, place=place,
+                                              whole=whole, sides=[s for s, _, _ in operands], staged=set(),
+                                              direct=terms, projected=projected, N=N, device=dev,
+                                              inputs=[self.record[_module_of(l)][0] for l in layers] +
+                                                     [x for _, x, _ in direct])
         kept = self._kept_entry(what, "stage_output", "covariance", key, count)
         slots = [t[slot * f:(slot + 1) * f] for t, f in zip(kept["stack"], kept["sizes"])]
         if basis is not None:
-            self._g_side(layers, operands, basis, slots)
+            self._g_side(layers, operands, basis, [slots[b][at:] for b, at in kept["place"]])
         else:
-            ops.CopyPlan(slots, [g.reshape(-1)[:f] for (_, g, _), f in zip(operands, kept["sizes"])]).run()
+            sources = [None] * len(slots)
+            for (b, _), (_, g, _) in zip(kept["place"], operands):
+                sources[b] = self.record[kept["whole"][b]][1].detach().reshape(-1) if b in kept["whole"] else \
+                    g.reshape(-1)[:kept["sizes"][b]]
+            ops.CopyPlan(slots, sources).run()
+        ops.per_sample_dw_project([ops.PerSampleDwProjectJob.of(l, x, g, y=y[slot], T=T, W=w, s=s)
+                                   for (l, x, g), (T, w, s), y in zip(direct, kept["direct"], kept["projected"])])
         kept["staged"].add(slot)
 
     def functional_covariance(self, out: Tensor, *, first: bool = True) -> Tensor:
@@ -219,7 +260,7 @@ class LinearisedPredictive:
             raise RuntimeError(f"{what}.functional_covariance: no output staged (stage_output(inputs=True) first)")
         record = getattr(self, "record", None) or {}
         for (layer, _, version, *_), x in zip(kept["key"], kept["inputs"]):
-            now = record.get(layer, (None, None))[0]
+            now = record.get(_module_of(layer), (None, None))[0]
             if now is not x or now._version != version:
                 raise RuntimeError(f"{what}.functional_covariance: the recorded inputs are no longer those of "
                                    "stage_output(inputs=True) (a new forward pass needs its outputs staged again)")
@@ -227,15 +268,16 @@ class LinearisedPredictive:
         if missing:
             raise RuntimeError(f"{what}.functional_covariance: output slots {missing} of {count} have not been staged since "
                                "the last stage_output(inputs=True)")
-        sides = kept["sides"]
-        N, dev = sides[0].N, kept["stack"][0].device
+        sides, N, dev = kept["sides"], kept["N"], kept["device"]
         if tuple(out.shape) != (N, count, count) or out.dtype != torch.float32 or not out.is_cuda or not out.is_contiguous():
             raise RuntimeError(f"{what}.functional_covariance: out must be a contiguous float32 GPU tensor of shape "
                                f"({N}, {count}, {count}), got {tuple(out.shape)} {out.dtype} on {out.device}")
-        # every layer into its own (N, count, count) row
-        rows = torch.empty(len(sides), N, count, count, dtype=torch.float32, device=dev)
-        ops.per_sample_cov_reduce([ops.PerSampleCovJob.of(s, g, x, w, rows[k], count, f, first=True)
-                                   for k, (s, g, x, w, f) in enumerate(zip(sides, kept["stack"], kept["xs"], kept["ws"],
-                                                                           kept["sizes"]))])
+        # every layer (a group slice, a depthwise layer) into its own (N, count, count) row
+        rows = torch.empty(len(sides) + len(kept["projected"]), N, count, count, dtype=torch.float32, device=dev)
+        ops.per_sample_cov_reduce([ops.PerSampleCovJob.of(s, kept["stack"][b][at:], x, w, rows[k], count, kept["sizes"][b],
+                                                          first=True)
+                                   for k, (s, (b, at), x, w) in enumerate(zip(sides, kept["place"], kept["xs"], kept["ws"]))])
+        ops.per_sample_gram_reduce([ops.PerSampleGramJob(y, rows[len(sides) + k], first=True)
+                                    for k, y in enumerate(kept["projected"])])
         self._sum_layers(rows, out.view(1, -1), first)
         return out

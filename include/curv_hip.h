@@ -630,6 +630,98 @@ int curv_persample_dw_quad_reduce(void* stream, const curv_persample_dw_desc* de
                                   size_t workspace_bytes);
 
 /* ------------------------------------------------------------------------------------------------
+ * The other reductions of a depthwise layer's products (csrc/persample_dw.hip, DESIGN.md "K15"): what the joint output
+ * covariance and the damping grid of the linearised predictive need.  Phase 1 is that of the entry points above, so an
+ * item's products p have the same bits; the descriptors below carry the record, geometry and extent fields of
+ * curv_persample_dw_desc under the same names and rules.  T, the weights and s are each optional (identity, ones, ones).
+ *     curv_persample_dw_project:           y[n*y_ns + c*n_g + j] = s[c] * W[c*w_rs + j] * sum_i T[c*t_cs + i*t_rs + j] * p[n,c,i]
+ *     curv_persample_dw_quad_grid_reduce:  out[h*o_hs + n*o_stride] (+)= gain[h] * sum_c sum_j w_h(c,j) *
+ *                                                                      ( sum_i T[c*t_cs + i*t_rs + j] * p[n,c,i] )**2
+ *         separable (u and v given, V NULL):  w_h(c,j) = 1 / ((u[c] + shift[h]) * (v[c*v_rs + j] + shift[h]))
+ *         dense     (V given, u and v NULL):  w_h(c,j) = 1 / (V[c*v_rs + j] + shift[h])
+ * project: W is the unsquared weight (Diagonal: W = inv; KFAC: T = L_A stacked, s = L_G stacked); y holds N rows of
+ * C*n_g values, y_ns >= C*n_g floats apart, and nothing between the rows is touched.  The variance of
+ * curv_persample_dw_quad_reduce is sum_e y[n][e]**2; the covariance of K outputs is the Gram of their K rows
+ * (curv_persample_gram_reduce).
+ * grid: the contract of curv_persample_quad_grid_reduce - 1 <= H <= CURV_PERSAMPLE_GRID_MAX; `shift` and `gain` are HOST
+ * arrays of H floats, copied into the kernel arguments during the call; every shift finite and > 0, every gain finite;
+ * IEEE divisions; no alpha; grid point h is computed from shift[h] and gain[h] alone, so row h has the same bits
+ * whatever other grid points or items share the call.  KFAC: T = U_A stacked (C, n_g, n_g), u = the 1 x 1 G factors (C),
+ * v = eig(A) (C, n_g), shift = sqrt(rho); Diagonal: T NULL, V = state, shift = rho.  Up to 8 items per launch of the
+ * reduction.
+ * Both: fp32 sums in a fixed order (thread, lane, wave by DPP, workgroup), no atomics, an item's plan follows from its
+ * own sizes only; the workspace (256-byte aligned) holds the p of every item and every word read from it was written by
+ * the same call.  Work goes on `stream` only, nothing is allocated, the host never waits.  An empty call is a no-op;
+ * invalid input returns CURV_ERR_INVALID with the item named, before anything is launched.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct curv_persample_dw_project_desc {
+  const float* x;
+  const float* g;
+  long long x_sn, x_sc, x_sh, x_sw, x_elems;
+  long long g_sn, g_sc, g_sh, g_sw, g_elems;
+  int32_t N, C, H, W;
+  int32_t kh, kw, sh, sw, ph, pw;
+  int32_t Ho, Wo;
+  int32_t has_bias;
+  int32_t reserved;
+  const float* T;          /* may be NULL */
+  const float* Wt;         /* the weights W of the formula; may be NULL */
+  const float* s;          /* may be NULL */
+  float* y;
+  long long t_cs, t_rs, w_rs, y_ns;
+} curv_persample_dw_project_desc;
+typedef struct curv_persample_dw_grid_desc {
+  const float* x;
+  const float* g;
+  long long x_sn, x_sc, x_sh, x_sw, x_elems;
+  long long g_sn, g_sc, g_sh, g_sw, g_elems;
+  int32_t N, C, H, W;
+  int32_t kh, kw, sh, sw, ph, pw;
+  int32_t Ho, Wo;
+  int32_t has_bias;
+  int32_t first;
+  const float* T;          /* may be NULL */
+  const float* u;          /* separable form: C values ... */
+  const float* v;          /* ... and (C, n_g) with row stride v_rs */
+  const float* V;          /* dense form: (C, n_g) with row stride v_rs */
+  float* out;
+  const float* shift;      /* host, Hn floats */
+  const float* gain;       /* host, Hn floats */
+  long long t_cs, t_rs, v_rs, o_stride, o_hs;
+  int32_t Hn;              /* the H of the formula: grid points (H names the input height above) */
+  int32_t reserved;
+} curv_persample_dw_grid_desc;
+/* Host only, as curv_persample_dw_workspace_bytes and curv_persample_dw_plan_info (the FLOPs include those of the
+ * transform and, for the grid, of the Hn weighted sums; the bytes of project include y). */
+size_t curv_persample_dw_project_workspace_bytes(const curv_persample_dw_project_desc* descs, int n);
+int curv_persample_dw_project_plan_info(const curv_persample_dw_project_desc* descs, int n, long long* flops, long long* bytes);
+size_t curv_persample_dw_quad_grid_workspace_bytes(const curv_persample_dw_grid_desc* descs, int n);
+int curv_persample_dw_quad_grid_plan_info(const curv_persample_dw_grid_desc* descs, int n, long long* flops, long long* bytes);
+int curv_persample_dw_project(void* stream, const curv_persample_dw_project_desc* descs, int n, void* workspace,
+                              size_t workspace_bytes);
+int curv_persample_dw_quad_grid_reduce(void* stream, const curv_persample_dw_grid_desc* descs, int n, void* workspace,
+                                       size_t workspace_bytes);
+
+/* Per-sample Gram of K staged vectors (csrc/persample_dw.hip; no phase 1, no geometry, no workspace):
+ *     out[n*o_ns + k*o_rs + k'] (+)= alpha * sum_{e < E} Y[k*y_ks + n*y_ns + e] * Y[k'*y_ks + n*y_ns + e]      k, k' < K
+ * 1 <= K <= CURV_PERSAMPLE_COV_MAX_OUTPUTS (defined below: 16).  The output layout and `first` are those of
+ * curv_persample_cov_reduce: o_rs >= K, o_ns >= K*o_rs, nothing between the K x K entries is touched; one value per pair
+ * k <= k' is computed and stored at both places, so the result is bit-for-bit symmetric.  One workgroup per sample, the
+ * pair sums in registers; fp32 sums in a fixed order (thread, lane, wave by DPP, workgroup), no atomics.  The items of
+ * a call must not share destinations.  Work goes on `stream` only.  An empty call is a no-op; invalid sizes or strides
+ * return CURV_ERR_INVALID with the item named, before anything is launched. */
+typedef struct curv_persample_gram_desc {
+  const float* Y;
+  float* out;
+  long long y_ks, y_ns, o_ns, o_rs;
+  int32_t N, K, E;
+  int32_t first;
+  float alpha;
+  int32_t reserved;
+} curv_persample_gram_desc;
+int curv_persample_gram_reduce(void* stream, const curv_persample_gram_desc* descs, int n);
+
+/* ------------------------------------------------------------------------------------------------
  * Linearised Laplace (GLM) predictive: the other reduction of the per-sample products (csrc/persample.hip) - over the
  * entries of P_n = A_n B_n^T, per sample:
  *     out[s*o_stride] (+)= alpha * sum_{i < M, j < Nc} W[i*w_rs + j] * ( sum_{l < L} A[s*a_ns + i*a_rs + l] * B[s*b_ns + j*b_rs + l] )**2
