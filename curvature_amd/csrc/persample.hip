@@ -766,14 +766,15 @@ __global__ void __launch_bounds__(PS_THREADS) ps_reduce_kernel(const PsBatch bat
 
 // ------------------------------------------------------------------------------------------------ pack
 // curv_persample_pack_ex (and curv_persample_pack, its fp32-contiguous spelling): X_n or g_n as K-contiguous fp32 rows,
-// from a source of fp32, bf16 or fp16 values addressed through element strides; forward im2col or the transposed gather
-// of a ConvTranspose2d input.
+// from a source of fp32, bf16 or fp16 values addressed through element strides; forward im2col (with a dilation: the
+// `reserved` word of the descriptor) or the transposed gather of a ConvTranspose2d input.
 struct PsPack {
   const void* src;
   float* dst;
   long long s_n;                // sample stride in elements: the sample base is formed in 64 bits, once per thread
   unsigned s_c, s_h, s_w;       // strides inside a sample, in elements (a sample spans fewer than 2^31: pack_plan_of)
   int N, C, H, W, kh, kw, sh, sw, ph, pw, Ho, Wo;
+  int dh, dw;                   // dilation of the forward im2col (1, 1 for a transposed item)
   int rows;                     // C kh kw (the ones row, if any, is row `rows`)
   int R;                        // rows + has_bias
   int L, Lp;
@@ -803,7 +804,13 @@ bool pack_plan_of(const curv_persample_pack_ex_desc& d, int index, const char* w
     return false;
   }
   side::ConvGeom g;
+  // the dilation rides in `reserved` (a half of 0 is 1): 0, what callers wrote before there was one, is dilation 1
+  const int dh = std::max(d.reserved & 0xffff, 1), dw = std::max((d.reserved >> 16) & 0xffff, 1);
   if (d.transposed) {
+    if (dh != 1 || dw != 1) {
+      set_error("%s: item %d: dilation %dx%d with the transposed gather", who, index, dh, dw);
+      return false;
+    }
     if (!side::source_geom_of(d, who, "item", index, &g)) return false;
     // the sizes `output_size` allows: output_padding in [0, stride)
     const long long lo_h = (long long)(d.H - 1) * d.sh - 2LL * d.ph + d.kh, lo_w = (long long)(d.W - 1) * d.sw - 2LL * d.pw + d.kw;
@@ -814,8 +821,20 @@ bool pack_plan_of(const curv_persample_pack_ex_desc& d, int index, const char* w
       return false;
     }
     g.Ho = d.Ho; g.Wo = d.Wo;
-  } else if (!side::conv_geom_of(d, who, "item", index, &g)) {
-    return false;
+  } else if (dh == 1 && dw == 1) {
+    if (!side::conv_geom_of(d, who, "item", index, &g)) return false;
+  } else {
+    // the output of the dilated window: the geometry check of a kernel of (k - 1) d + 1 taps a side
+    curv_persample_pack_ex_desc e = d;
+    const long long eh = (long long)(d.kh - 1) * dh + 1, ew = (long long)(d.kw - 1) * dw + 1;
+    const bool taps = d.kh >= 1 && d.kw >= 1 && eh < (1LL << 31) && ew < (1LL << 31);
+    e.kh = taps ? (int)eh : 0; e.kw = taps ? (int)ew : 0;
+    if (const char* fault = side::conv_geom_fault(e, &g)) {
+      set_error("%s: item %d: %s (N %d C %d H %d W %d kernel %dx%d dilation %dx%d stride %dx%d padding %dx%d)", who, index,
+                fault, d.N, d.C, d.H, d.W, d.kh, d.kw, dh, dw, d.sh, d.sw, d.ph, d.pw);
+      return false;
+    }
+    g.kh = d.kh; g.kw = d.kw;
   }
   if (d.s_n < 0 || d.s_c < 0 || d.s_h < 0 || d.s_w < 0 || d.src_elems < 1) {
     set_error("%s: item %d: negative stride, or source extent %lld elements below 1", who, index, d.src_elems);
@@ -825,6 +844,7 @@ bool pack_plan_of(const curv_persample_pack_ex_desc& d, int index, const char* w
   P.src = d.src; P.dst = d.dst;
   P.N = g.N; P.C = g.C; P.H = g.H; P.W = g.W;
   P.kh = g.kh; P.kw = g.kw; P.sh = g.sh; P.sw = g.sw; P.ph = g.ph; P.pw = g.pw; P.Ho = g.Ho; P.Wo = g.Wo;
+  P.dh = dh; P.dw = dw;
   const long long rows = (long long)d.C * d.kh * d.kw, L = (long long)P.Ho * P.Wo;
   // what one sample spans, (C-1) s_c + (H-1) s_h + (W-1) s_w, stays below 2^31 elements: offsets inside a sample are
   // 32-bit (a stride of 2^31 or more is refused before it is multiplied)
@@ -927,6 +947,7 @@ __global__ void __launch_bounds__(PS_THREADS) ps_pack_kernel(const PsPackBatch b
     const bool transposed = TRANSPOSED && F.transposed;
     const int c = (int)((unsigned)r / khw), q = r - c * (int)khw;
     const int a = (int)((unsigned)q / kw), b = q - a * (int)kw;
+    const int ta = a * F.dh, tb = b * F.dw;                               // the tap's offset in the forward window
     int oh = (int)((unsigned)k0 / (unsigned)Wo), ow = k0 - oh * Wo;
     const T* plane = sample + (unsigned)c * F.s_c;
     const T* at[4];
@@ -943,8 +964,8 @@ __global__ void __launch_bounds__(PS_THREADS) ps_pack_kernel(const PsPackBatch b
         iw = uw / (unsigned)sw;
         ok = ok & (ih * (unsigned)sh == uh) & (iw * (unsigned)sw == uw);
       } else {
-        ih = (unsigned)(oh * sh - ph + a);
-        iw = (unsigned)(ow * sw - pw + b);
+        ih = (unsigned)(oh * sh - ph + ta);
+        iw = (unsigned)(ow * sw - pw + tb);
       }
       ok = ok & (ih < H) & (iw < W);
       at[e] = ok ? plane + (ih * s_h + iw * s_w) : nullptr;

@@ -49,6 +49,24 @@ def _check_convt(layer) -> None:
         raise NotImplementedError("ConvTranspose2d with string padding is not supported")
 
 
+def _check_dilated(model, layer) -> None:
+    """What the A-factor build of a dilated Conv2d represents (`ops.admit_dilated`; curv_kfac_dilated_accumulate): groups 1,
+    integer padding, stride 1 and a padding that is a multiple of the dilation - the residue classes of the input grid are
+    then undilated convolutions of their own."""
+    name = next((f"'{n}'" for n, mod in model.named_modules() if mod is layer), repr(layer))
+    if int(layer.groups) != 1:
+        raise NotImplementedError(f"KFAC: dilated convolution {name} has groups={layer.groups}; dilation with groups > 1 is "
+                                  "not supported")
+    if not all(isinstance(p, int) for p in layer.padding):
+        raise NotImplementedError(f"KFAC: dilated convolution {name}: string padding modes are not supported")
+    if tuple(layer.stride) != (1, 1) or any(p % d for p, d in zip(layer.padding, layer.dilation)):
+        raise NotImplementedError(
+            f"KFAC: dilated convolution {name} (stride {tuple(layer.stride)}, padding {tuple(layer.padding)}, dilation "
+            f"{tuple(layer.dilation)}): the A-factor build needs stride 1 and a padding that is a multiple of the dilation; "
+            "the per-sample line (Diagonal(per_sample=True), the linearised predictive of Diagonal) does not have this "
+            "restriction")
+
+
 def _wm(layer, t: Tensor) -> Tensor:
     """A tensor shaped like `layer.weight` as the layer matrix Wm (out, in*kh*kw): a view for Linear / Conv2d, a
     contiguous copy of ``t.permute(1, 0, 2, 3)`` for ConvTranspose2d (whose weight is (in, out, kh, kw))."""
@@ -519,8 +537,8 @@ class Curvature(ABC):
 
     def _per_sample_layers(self, what: str, advice: str, grouped: bool = False) -> List[Module]:
         """The selected layers, in ``modules()`` order, after checking that every one has a per-sample form P_n = g_n X_n^T:
-        Linear, and Conv2d with groups 1, dilation 1 and integer padding; with `ops.widen_per_sample` also ConvTranspose2d
-        under the same restrictions and, for the estimators that treat a MultiheadAttention module as its two projections
+        Linear, and Conv2d with groups 1, dilation 1 (any dilation with `ops.admit_dilated`) and integer padding; with
+        `ops.widen_per_sample` also ConvTranspose2d with groups 1, dilation 1 and integer padding and, for the estimators that treat a MultiheadAttention module as its two projections
         (KFAC, EFB), those two `AttentionProjection`s.  Any other raises NotImplementedError naming it.  `grouped`: the
         caller takes grouped Conv2d layers (`ops.per_sample_route`: as group slices or by the depthwise kernel); they
         pass only with `ops.admit_grouped_per_sample` on, and a caller that does not take them then says who does
@@ -535,13 +553,16 @@ class Curvature(ABC):
                 continue
             why = None
             if kind == 'Conv2d' or (kind == 'ConvTranspose2d' and wide):
-                if int(layer.groups) != 1 and not (grouped and groups_on and kind == 'Conv2d'):
+                if int(layer.groups) != 1 and tuple(layer.dilation) != (1, 1) and kind == 'Conv2d' and \
+                        ops.dilated_admitted():
+                    why = f"dilated convolution with groups={layer.groups}: ops.admit_dilated covers groups 1 only"
+                elif int(layer.groups) != 1 and not (grouped and groups_on and kind == 'Conv2d'):
                     why = f"grouped convolution (groups={layer.groups})"
                     if groups_on and kind == 'Conv2d':
                         why += "; Diagonal(per_sample=True) and the linearised predictive of KFAC and Diagonal take it" \
                             if ops.per_sample_admits_grouped_joint() else \
                             "; Diagonal(per_sample=True) and functional_variance take it"
-                elif tuple(layer.dilation) != (1, 1):
+                elif tuple(layer.dilation) != (1, 1) and not (kind == 'Conv2d' and ops.dilated_admitted()):
                     why = "dilated convolution"
                 elif not all(isinstance(p, int) for p in layer.padding):
                     why = "string padding mode"
@@ -1156,7 +1177,9 @@ class KFAC(LinearisedPredictive, Curvature):
                 if name in ('Linear', 'Conv2d'):
                     if name == 'Conv2d' and tuple(layer.dilation) != (1, 1):
                         # the reference silently ignores it (curvatures.py:329)
-                        raise NotImplementedError("KFAC: dilated convolutions are not supported")
+                        if not ops.dilated_admitted():
+                            raise NotImplementedError("KFAC: dilated convolutions are not supported")
+                        _check_dilated(model, layer)
                     # grouped convolutions (groups > 1): block-diagonal KFAC, one Kronecker pair per group (the
                     # reference ignores `groups` and then fails in _replace): state[layer] = [A, G] stacked (G, n, n)
                     if name == 'Conv2d' and not all(isinstance(p, int) for p in layer.padding):
@@ -1195,9 +1218,9 @@ class KFAC(LinearisedPredictive, Curvature):
         gradients; the G side is divided by ``grad_scale ** 2``.  The caller skips ``update()`` on the steps the scaler
         skips (non-finite gradients)."""
         self._decomposition = None                   # (of the factors as they were: `decompose`)
-        jobs, group_jobs, half_jobs, convt_jobs = [], [], [], []
+        jobs, group_jobs, half_jobs, convt_jobs, dilated_jobs = [], [], [], [], []
         launch = {ops.FactorJob: jobs, ops.GroupFactorJob: group_jobs, ops.HalfFactorJob: half_jobs,
-                  ops.ConvTFactorJob: convt_jobs}
+                  ops.ConvTFactorJob: convt_jobs, ops.DilatedFactorJob: dilated_jobs}
         if not grad_scale > 0:
             raise ValueError(f"KFAC.update: grad_scale must be positive, got {grad_scale}")
         g_div = float(grad_scale) ** 2
@@ -1240,17 +1263,19 @@ class KFAC(LinearisedPredictive, Curvature):
                 job.path_hint = hint
         if getattr(self, "_count_flops", False):                 # bench.py: what the launch plan executes
             self._last_flops = sum(ops.kfac_plan_flops(jobs)) + sum(ops.kfac_group_plan_flops(group_jobs)) + \
-                sum(ops.kfac_half_plan_flops(half_jobs)) + sum(ops.kfac_convt_plan_flops(convt_jobs))
+                sum(ops.kfac_half_plan_flops(half_jobs)) + sum(ops.kfac_convt_plan_flops(convt_jobs)) + \
+                sum(ops.kfac_dilated_plan_flops(dilated_jobs))
         ops.kfac_accumulate(jobs, events=getattr(self, "_timing_events", None))
         ops.kfac_accumulate_groups(group_jobs)
         ops.kfac_accumulate_half(half_jobs)
         ops.kfac_accumulate_convt(convt_jobs)
+        ops.kfac_accumulate_dilated(dilated_jobs)
 
     def _unsharded_path(self, records, inputs: bool, grads: bool) -> int:
         """The launch form of the fp32 factor build of an unsharded update() on `records` = [(layer, input, grad_output)]
         (`ops.ShapeOnly`s): decided by the library itself (curv_kfac_path_for evaluates every gate of the small form, not
-        only the flops) for the sides that come back as `FactorJob`.  Grouped, half-precision and transposed-convolution
-        A sides are built by launches of their own, whose plans are per factor."""
+        only the flops) for the sides that come back as `FactorJob`.  Grouped, half-precision, transposed-convolution and
+        dilated A sides are built by launches of their own, whose plans are per factor."""
         model_jobs = []
         for layer, forward, backward in records:
             if (inputs and forward is None) or (grads and backward is None):

@@ -85,7 +85,7 @@ _kfac_last = {}                        # thread ident -> the "kfac" workspace it
 
 
 class _ConvJob:
-    """What the four factor jobs share: source and destination, the convolution geometry, and how the product enters the
+    """What the five factor jobs share: source and destination, the convolution geometry, and how the product enters the
     destination.  Every subclass adds one field of its own."""
     __slots__ = ("src", "dst", "kernel", "stride", "padding", "has_bias", "scale", "first")
 
@@ -365,6 +365,67 @@ def kfac_accumulate_convt(jobs: Sequence[ConvTFactorJob], events=None) -> None:
                jobs[0].src.device, "kfac_convt", events)
 
 
+class DilatedFactorJob(_ConvJob):
+    """The A factor of a dilated Conv2d (curv_kfac_dilated_accumulate): dst (+)= scale * X X^T with X =
+    F.unfold(src, kernel, dilation, padding, stride 1) [+ ones row], built as the sum of the plain factors of the residue
+    classes ``src[:, :, rh::dh, rw::dw]``.  Stride 1 and a padding that is a multiple of the dilation (the library refuses
+    anything else).  `src` may also be just its (N, C, H, W) shape (plan queries)."""
+    __slots__ = ("dilation",)
+
+    def __init__(self, src, dst, kernel, stride, padding, dilation, has_bias=False, scale=1.0, first=False):
+        self._set(src, dst, kernel, stride, padding, has_bias, scale, first)
+        self.dilation = tuple(int(v) for v in dilation)
+
+
+def _dilated_descs(jobs: Sequence[DilatedFactorJob], check_tensors: bool = True):
+    arr = (_lib.curv_dilated_factor_desc * len(jobs))()
+    for d, j in zip(arr, jobs):
+        if check_tensors:
+            _require_gpu(j.src, j.dst)
+        _fill_desc(d, j, check_tensors, source="dilated-convolution factor source must be a contiguous float32 (N,C,H,W) tensor")
+        d.dh, d.dw = j.dilation
+    return arr
+
+
+def kfac_dilated_plan_flops(jobs: Sequence[DilatedFactorJob]) -> List[int]:
+    """Multiply-add FLOPs (2 per multiply-add) the dilated build executes for each job: the sum over the plain builds of
+    its class stacks (curv_kfac_dilated_plan_flops, host only).  `job.src` may be a tensor or its (N, C, H, W) shape."""
+    if not jobs:
+        return []
+    return _plan_flops("curv_kfac_dilated_plan_flops", _dilated_descs(jobs, check_tensors=_all_tensors(jobs)), len(jobs))
+
+
+def kfac_accumulate_dilated(jobs: Sequence[DilatedFactorJob], events=None) -> None:
+    """A-factor build of dilated convolutions (curv_kfac_dilated_accumulate) on the current stream: per factor one gather
+    pass that writes the residue-class sub-images, then one fp32 MFMA build per size group (at most four).  Scratch from
+    `workspace` (so CURV_DEBUG_POISON covers it).  `events` = (start, stop) ``torch.cuda.Event``s are recorded around the
+    whole build."""
+    if not jobs:
+        return
+    _run_build("curv_kfac_dilated_workspace_bytes", "curv_kfac_dilated_accumulate", _dilated_descs(jobs), len(jobs),
+               jobs[0].src.device, "kfac_dilated", events)
+
+
+# Dilated convolutions (DESIGN.md K16) are opt-in: with the switch off - the default - every selection, refusal and message
+# is exactly what it was.
+_DILATED = False
+
+
+def admit_dilated(enable: bool = True) -> bool:
+    """Switch dilated convolutions on or off for the process; returns what it was.  On: `factor_jobs` routes the A side
+    of a groups-1 Conv2d with a dilation other than (1, 1) to `DilatedFactorJob`, KFAC (and with it EFB and INF) records
+    such a layer - stride 1, padding a multiple of the dilation - and the per-sample line (``per_sample=True``, the
+    linearised predictives) takes it with any stride and integer padding.  Off: such a layer raises where it did.
+    Dilation with ``groups > 1``, string padding and dilated ConvTranspose2d are refused either way."""
+    global _DILATED
+    was, _DILATED = _DILATED, bool(enable)
+    return was
+
+
+def dilated_admitted() -> bool:
+    return _DILATED
+
+
 class LayerJobs(NamedTuple):
     """The two factor builds of one layer (`factor_jobs`): `a` / `g` the job of the A / G side (None without a source),
     `n` / `m` the widths of A / G (of one group's, for a grouped layer), `N` samples of `L` positions each."""
@@ -418,14 +479,18 @@ def factor_jobs(layer, x, g, out_size=None) -> LayerJobs:
     `x` / `g`: the recorded input / grad_output (either may be None: that side gets no job) or `ShapeOnly`
     stand-ins (the jobs' `src` is then a shape: plan queries).  Each side is routed by its dtype: float32 to `FactorJob`,
     bfloat16 / float16 to `HalfFactorJob`; both sides of a grouped convolution to `GroupFactorJob` and the A side of a
-    transposed convolution to `ConvTFactorJob`, as float32.  `out_size`: the output size a ConvTranspose2d forward was
+    transposed convolution to `ConvTFactorJob`, as float32; with `admit_dilated` the A side of a dilated groups-1 Conv2d
+    to `DilatedFactorJob`, as float32 too (without it the dilation is not looked at, as before).  `out_size`: the output size a ConvTranspose2d forward was
     seen to produce (it carries the effective output_padding), used when there is no `g` to read it from.  The jobs come
     without `dst`, `scale` and `first`."""
     kind = layer.__class__.__name__
     conv, convt = kind in ('Conv2d', 'ConvTranspose2d'), kind == 'ConvTranspose2d'
     groups = int(layer.groups) if kind == 'Conv2d' else 1
     has_bias = layer.bias is not None
-    x = _factor_source(x, fp32=groups > 1 or convt, flatten=not conv)
+    dilation = tuple(layer.dilation) if _DILATED and kind == 'Conv2d' else (1, 1)
+    if dilation != (1, 1) and groups > 1:
+        raise NotImplementedError(f"dilated convolution with groups > 1 (groups={groups}) is not supported")
+    x = _factor_source(x, fp32=groups > 1 or convt or dilation != (1, 1), flatten=not conv)
     g = _factor_source(g, fp32=groups > 1, flatten=not conv)
     if x is None and g is None:
         raise RuntimeError("KFAC.update: no recorded forward/backward pass for a selected layer")
@@ -437,7 +502,8 @@ def factor_jobs(layer, x, g, out_size=None) -> LayerJobs:
         if g is not None:
             out_size = tuple(g.shape[2:])
         elif not convt:
-            out_size = tuple((x.shape[2 + d] + 2 * padding[d] - kernel[d]) // stride[d] + 1 for d in range(2))
+            out_size = tuple((x.shape[2 + d] + 2 * padding[d] - dilation[d] * (kernel[d] - 1) - 1) // stride[d] + 1
+                             for d in range(2))
         elif out_size is None:                           # records that did not pass the estimator's hooks
             out_size = tuple((x.shape[2 + d] - 1) * stride[d] - 2 * padding[d] + kernel[d] +
                              layer.output_padding[d] for d in range(2))
@@ -451,6 +517,8 @@ def factor_jobs(layer, x, g, out_size=None) -> LayerJobs:
             a_job = GroupFactorJob(src, None, groups, kernel, stride, padding, has_bias)
         elif convt:
             a_job = ConvTFactorJob(src, None, kernel, stride, padding, out_size, has_bias)
+        elif dilation != (1, 1):
+            a_job = DilatedFactorJob(src, None, kernel, stride, padding, dilation, has_bias)
         elif x.dtype == torch.float32:
             a_job = FactorJob(src, None, kernel, stride, padding, has_bias)
         else:
@@ -470,7 +538,7 @@ def factor_jobs(layer, x, g, out_size=None) -> LayerJobs:
 class PackSource(NamedTuple):
     """Where `per_sample_pack` reads an operand: the source seen as ``(N, C, H, W)`` with element `strides`
     ``(s_n, s_c, s_h, s_w)`` (the tensor itself gives the address, the dtype and the extent), the window, and `out_size`
-    ``(Ho, Wo)`` for the transposed gather of a ConvTranspose2d input (None: the forward im2col)."""
+    ``(Ho, Wo)`` for the transposed gather of a ConvTranspose2d input (None: the forward im2col, with `dilation`)."""
     shape: tuple
     kernel: tuple
     stride: tuple
@@ -478,11 +546,14 @@ class PackSource(NamedTuple):
     has_bias: bool
     strides: tuple
     out_size: Optional[tuple]
+    dilation: tuple = (1, 1)
 
 
-def _pack_source(shape, strides, kernel=(1, 1), stride=(1, 1), padding=(0, 0), has_bias=False, out_size=None) -> PackSource:
+def _pack_source(shape, strides, kernel=(1, 1), stride=(1, 1), padding=(0, 0), has_bias=False, out_size=None,
+                 dilation=(1, 1)) -> PackSource:
     return PackSource(tuple(map(int, shape)), tuple(kernel), tuple(stride), tuple(padding), bool(has_bias),
-                      tuple(map(int, strides)), None if out_size is None else tuple(map(int, out_size)))
+                      tuple(map(int, strides)), None if out_size is None else tuple(map(int, out_size)),
+                      tuple(map(int, dilation)))
 
 
 def _is_contiguous_nchw(geometry: PackSource) -> bool:
@@ -644,7 +715,9 @@ def _per_sample_operand(src, geometry: PackSource, in_place: bool, rows_outer: b
     if geometry.out_size is not None:
         L = geometry.out_size[0] * geometry.out_size[1]
     else:
-        L = ((H + 2 * padding[0] - kernel[0]) // stride[0] + 1) * ((W + 2 * padding[1] - kernel[1]) // stride[1] + 1)
+        dh, dw = geometry.dilation
+        L = ((H + 2 * padding[0] - dh * (kernel[0] - 1) - 1) // stride[0] + 1) * \
+            ((W + 2 * padding[1] - dw * (kernel[1] - 1) - 1) // stride[1] + 1)
     rows = C * kernel[0] * kernel[1] + int(geometry.has_bias)
     if in_place and src.dtype == torch.float32 and _is_contiguous_nchw(geometry):
         return PerSampleOperand(src, rows, L, L, rows * L, L, None, False, 0)
@@ -671,7 +744,8 @@ def per_sample_operands(layer, x, g, rows_outer: bool = False, in_place: bool = 
     """The step from a layer's records `(x, g)` to the operands of its per-sample gradients P_n = g_n X_n^T, on the
     geometry of `factor_jobs`.
 
-    Conv2d (groups 1, dilation 1): g_n = grad_output[n] as (m, Ho Wo), X_n = unfold(x[n]) [+ ones row].  ConvTranspose2d
+    Conv2d (groups 1; dilation 1, or any with `admit_dilated`): g_n = grad_output[n] as (m, Ho Wo), X_n = unfold(x[n])
+    [+ ones row].  ConvTranspose2d
     (groups 1, dilation 1): g_n likewise, X_n the transposed gather (row (ci, a, b) at (oh, ow) is
     x[n, ci, (oh + ph - a) / sh, (ow + pw - b) / sw] where that is a whole position inside the input, else 0) - the column
     order of Wm; the output size is grad_output's.  Linear: g_n = grad_output[n]^T (m, T), X_n = x[n]^T [+ ones row] (D [+ 1], T)
@@ -703,7 +777,7 @@ def per_sample_operands(layer, x, g, rows_outer: bool = False, in_place: bool = 
             raise RuntimeError(f"per-sample update: {what}: records do not match (input {tuple(x.shape)}, grad_output "
                                f"{tuple(g.shape)})")
     sides = factor_jobs(layer, ShapeOnly(tuple(x.shape)), ShapeOnly(tuple(g.shape)))
-    if sides.groups != 1 or not isinstance(sides.a, (FactorJob, ConvTFactorJob)):
+    if sides.groups != 1 or not isinstance(sides.a, (FactorJob, ConvTFactorJob, DilatedFactorJob)):
         raise NotImplementedError(f"per-sample update: unsupported layer {kind}")
     has_bias = sides.a.has_bias
     if kind in ('Conv2d', 'ConvTranspose2d'):
@@ -713,7 +787,7 @@ def per_sample_operands(layer, x, g, rows_outer: bool = False, in_place: bool = 
         N, Ng = int(x.shape[0]), int(g.shape[0])
         Ho, Wo = map(int, g.shape[2:])
         geo_x = _pack_source(x.shape, x.stride(), sides.a.kernel, sides.a.stride, sides.a.padding, has_bias,
-                             (Ho, Wo) if kind == 'ConvTranspose2d' else None)
+                             (Ho, Wo) if kind == 'ConvTranspose2d' else None, getattr(sides.a, "dilation", (1, 1)))
         geo_g = _pack_source(g.shape, g.stride())
         whole = in_place and (Ho * Wo) % 4 == 0
         plain = kind == 'Conv2d' and sides.a.kernel == (1, 1) and sides.a.stride == (1, 1) and \
@@ -800,6 +874,10 @@ def _fill_pack(d, op: PerSampleOperand, dst: torch.Tensor) -> None:
     d.src_elems = _source_extent(op.src)
     d.dtype = _PACK_DTYPES[op.src.dtype]
     d.transposed = int(geo.out_size is not None)
+    if geo.dilation != (1, 1):                         # dh | dw << 16 in `reserved`; 0 is dilation 1
+        if not all(1 <= v < 1 << 16 for v in geo.dilation):
+            raise RuntimeError(f"per_sample_pack: dilation {geo.dilation} outside [1, 65535]")
+        d.reserved = geo.dilation[0] | geo.dilation[1] << 16
     if geo.out_size is not None:
         d.Ho, d.Wo = geo.out_size
 

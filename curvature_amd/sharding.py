@@ -87,7 +87,8 @@ def layer_dims(layers, shapes) -> List[tuple]:
     sides = [ops.factor_jobs(layer, *map(ops.ShapeOnly, shapes[layer])) for layer in layers]
     flops = {}
     for cls, plan_flops in ((ops.FactorJob, ops.kfac_plan_flops), (ops.GroupFactorJob, ops.kfac_group_plan_flops),
-                            (ops.ConvTFactorJob, ops.kfac_convt_plan_flops)):
+                            (ops.ConvTFactorJob, ops.kfac_convt_plan_flops),
+                            (ops.DilatedFactorJob, ops.kfac_dilated_plan_flops)):
         batch = [job for s in sides for job in (s.a, s.g) if type(job) is cls]
         flops.update(zip(map(id, batch), plan_flops(batch)))
     return [(s.n, s.m, s.K, float(flops[id(s.a)] + flops[id(s.g)])) + ((s.groups,) if s.groups > 1 else ())

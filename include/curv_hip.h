@@ -68,8 +68,9 @@ int curv_init_streams(void);
  *   Linear           : src = (N,C) viewed as (N,C,1,1); A: scale = 1/N, G: scale = N
  * `dst` is the (dim x dim) fp32 factor, dim = C*kh*kw + has_bias.  `first` != 0 overwrites dst
  * (the reference's `self.state[layer] = [...]` at :350), 0 accumulates (`+=` at :347-348).
- * The result is exactly symmetric.  Dilation is not representable (the reference ignores it, :329): callers must
- * reject such layers.  Grouped convolutions have a build of their own, curv_kfac_group_accumulate below.
+ * The result is exactly symmetric.  Dilation is not representable here (the reference ignores it, :329): the A factor of
+ * a dilated convolution is built by curv_kfac_dilated_accumulate below.  Grouped convolutions have a build of their own,
+ * curv_kfac_group_accumulate below.
  * ---------------------------------------------------------------------------------------------- */
 typedef struct curv_factor_desc {
   const float* src;
@@ -260,6 +261,51 @@ int curv_kfac_convt_plan_flops(const curv_convt_factor_desc* descs, int n_factor
  * aligned.  `descs` is a host array; it may be reused as soon as the call returns. */
 int curv_kfac_convt_accumulate(void* stream, const curv_convt_factor_desc* descs, int n_factors, void* workspace,
                                size_t workspace_bytes);
+
+/* ------------------------------------------------------------------------------------------------
+ * KFAC A-factor build of a DILATED Conv2d (csrc/dilated_factor.hip; groups 1, stride 1, padding a multiple of the dilation):
+ *   dst (+)= scale * X X^T,  X the im2col of `src` with dilation: row (c, a, b) at column (n, oh, ow) is
+ *   src[n, c, oh - ph + a dh, ow - pw + b dw] (0 outside the input), plus the row of ones when `has_bias` -
+ * F.unfold(src, kernel, dilation, padding, stride 1), which the reference does not compute (it drops the dilation, :329).
+ * The descriptor has the fields of curv_factor_desc (without the path hint: a factor's plan is its own) plus dh, dw.
+ *
+ * All taps of an output pixel lie in one residue class of the input grid modulo (dh, dw), so X is the union over the dh dw
+ * classes of the undilated im2col (same kernel, stride 1, padding (ph / dh, pw / dw)) of the sub-images
+ * src[:, :, rh::dh, rw::dw], and the factor the sum of their plain factors.  A gather pass reads `src` once and writes the
+ * sub-images into the workspace, the classes of equal size stacked as one (count N, C, Hg, Wg) tensor - at most 2 x 2 sizes,
+ * one when dh | H and dw | W; curv_kfac_accumulate then runs once per size group, in sequence on `stream`.  A class with an
+ * empty sub-image (dilation larger than the image) adds scale * N * (its output pixels) to the bias corner and nothing
+ * else.  With dh = dw = 1 the call is curv_kfac_accumulate on `src` itself (any stride and padding, no copy, the same bits).
+ * The result is exactly symmetric; sums run in a fixed order without atomics; a factor's launch plan follows from its own
+ * geometry, so its bits do not depend on the other factors of the call.  Never reads outside `src`; enqueues on `stream`
+ * only, never waits on the host and allocates nothing (graph capture works).  An empty call is a no-op.
+ * CURV_ERR_INVALID with the factor named, before anything is launched: dh or dw below 1; with a dilation above 1 a stride
+ * other than 1, ph % dh != 0 or pw % dw != 0, a dilated kernel (k - 1) d + 1 larger than the padded input; and the size
+ * limits of the plain build, applied to the class stacks.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct curv_dilated_factor_desc {
+  const float* src;
+  float* dst;
+  int32_t N, C, H, W;
+  int32_t kh, kw, sh, sw, ph, pw;
+  int32_t has_bias;
+  int32_t first;
+  float scale;
+  int32_t dh, dw;
+} curv_dilated_factor_desc;
+
+/* Device scratch needed by curv_kfac_dilated_accumulate for these factors (bytes): the SUM over the factors of the scratch
+ * each needs alone (its class stacks plus the scratch of its plain builds); 0 with error text for invalid geometry. */
+size_t curv_kfac_dilated_workspace_bytes(const curv_dilated_factor_desc* descs, int n_factors);
+
+/* Host-only: multiply-add flops (2 per multiply-add) the build executes per factor: the sum of what curv_kfac_plan_info
+ * reports for the plain builds of its class stacks (dh = dw = 1: for the factor itself). */
+int curv_kfac_dilated_plan_flops(const curv_dilated_factor_desc* descs, int n_factors, long long* out);
+
+/* The build of all factors, one after another on `stream`.  `workspace`: curv_kfac_dilated_workspace_bytes, 256-byte
+ * aligned.  `descs` is a host array; it may be reused as soon as the call returns. */
+int curv_kfac_dilated_accumulate(void* stream, const curv_dilated_factor_desc* descs, int n_factors, void* workspace,
+                                 size_t workspace_bytes);
 
 /* Same, recording HIP events (from curv_event_create) on `stream` around EVERYTHING the call enqueues behind the
  * descriptor-table uploads (padding / pre-tiling passes, the MFMA kernels, the k-slice reductions, the 3x3 assembly), so
@@ -549,6 +595,11 @@ int curv_persample_pack(void* stream, const curv_persample_pack_desc* descs, int
  *               x[n, ci, (oh + ph - a)/sh, (ow + pw - b)/sw] where both divisions are exact and the result lies inside
  *               H x W, 0 elsewhere - the column order of Wm = weight.permute(1, 0, 2, 3).reshape(Cout, -1).  L = Ho*Wo.
  *               == 0: the forward im2col of curv_persample_pack; Ho and Wo are not read.
+ *   reserved    the DILATION of the forward im2col: dh in the low and dw in the high 16 bits, a half of 0 standing for 1 - so
+ *               0, what every caller wrote so far, is dilation 1 and the layout is unchanged (no second entry point).  Row
+ *               (c, a, b) at l = (oh, ow) is x[n, c, oh sh - ph + a dh, ow sw - pw + b dw], and L follows from the dilated
+ *               output size, (H + 2 ph - (kh - 1) dh - 1) / sh + 1 (w alike); any stride and any padding.  A transposed
+ *               item with a dilation other than 1 is refused.
  * A 1x1 / stride-1 / padding-0 item whose rows are plain runs of the source, with the pointer and the sample and channel
  * strides multiples of four elements, is read with one 8- or 16-byte load per four values; everything else gathers per
  * element.  One launch per 16 items of one dtype; an item's bits do not depend on the other items of the call.  Every item
