@@ -13,7 +13,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc")
 INCLUDE = os.path.normpath(os.path.join(_HERE, "..", "include"))
 LIB_PATH = os.path.join(CSRC, "libcurv_hip.so")
-SOURCES = ["api.cpp", "collective.cpp", "elementwise.hip", "syrk.hip", "syrk_flat.hip", "syrk_corr.hip", "syrk_pre.hip", "syrk_small.hip", "group_factor.hip", "kfac_half.hip", "convt_factor.hip", "dilated_factor.hip", "persample.hip", "persample_dw.hip", "logit_mc.hip", "invert.hip", "gemm.hip", "inf.hip", "eigh.hip", "eigh_lowrank.hip"]
+SOURCES = ["api.cpp", "collective.cpp", "elementwise.hip", "syrk.hip", "syrk_flat.hip", "syrk_corr.hip", "syrk_pre.hip", "syrk_small.hip", "group_factor.hip", "kfac_half.hip", "convt_factor.hip", "dilated_factor.hip", "reduce_factor.hip", "persample.hip", "persample_dw.hip", "logit_mc.hip", "invert.hip", "gemm.hip", "inf.hip", "eigh.hip", "eigh_lowrank.hip"]
 HIPCC_FLAGS = ["-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC", "-shared", "-Wall",
                "-Wno-unused-function", "-ldl"]
 
@@ -134,6 +134,11 @@ class curv_convt_factor_desc(ctypes.Structure):
 class curv_dilated_factor_desc(ctypes.Structure):
     """Mirror of ``curv_dilated_factor_desc`` in include/curv_hip.h."""
     _fields_ = _ENDS + _SOURCE + _WINDOW + _ENTRY + [("dh", ctypes.c_int32), ("dw", ctypes.c_int32)]
+
+
+class curv_reduce_factor_desc(ctypes.Structure):
+    """Mirror of ``curv_reduce_factor_desc`` in include/curv_hip.h."""
+    _fields_ = _ENDS + _SOURCE + _WINDOW + _ENTRY + [(k, ctypes.c_int32) for k in ("dtype", "form", "mean", "T", "E")]
 
 
 class curv_factor16_desc(ctypes.Structure):
@@ -312,6 +317,9 @@ SIGNATURES = {
     "curv_kfac_dilated_workspace_bytes": (_sz, [ctypes.POINTER(curv_dilated_factor_desc), _i]),
     "curv_kfac_dilated_plan_flops": (_i, [ctypes.POINTER(curv_dilated_factor_desc), _i, ctypes.POINTER(ctypes.c_longlong)]),
     "curv_kfac_dilated_accumulate": (_i, [_vp, ctypes.POINTER(curv_dilated_factor_desc), _i, _vp, _sz]),
+    "curv_kfac_reduce_workspace_bytes": (_sz, [ctypes.POINTER(curv_reduce_factor_desc), _i]),
+    "curv_kfac_reduce_plan_flops": (_i, [ctypes.POINTER(curv_reduce_factor_desc), _i, ctypes.POINTER(ctypes.c_longlong)]),
+    "curv_kfac_reduce_accumulate": (_i, [_vp, ctypes.POINTER(curv_reduce_factor_desc), _i, _vp, _sz]),
     "curv_event_create": (_vp, []),
     "curv_event_destroy": (None, [_vp]),
     "curv_event_elapsed_ms": (_i, [_vp, _vp, ctypes.POINTER(ctypes.c_float)]),
@@ -390,6 +398,7 @@ ABI_VERSION = 12                     # CURV_ABI_VERSION of include/curv_hip.h
 DTYPE_F32, DTYPE_BF16, DTYPE_F16 = 0, 1, 2     # CURV_DTYPE_* (curv_factor16_desc.dtype; curv_persample_pack_ex_desc.dtype)
 KFAC_TABLE_RESIDENT = 1             # CURV_KFAC_TABLE_RESIDENT
 PATH_AUTO, PATH_SMALL, PATH_GROUPED = 0, 1, 2     # CURV_PATH_* (curv_factor_desc.path_hint)
+REDUCE_PLANE, REDUCE_TOKEN = 0, 1    # CURV_REDUCE_* (curv_reduce_factor_desc.form)
 SMALL_MAX_FLOP = 2.0e9              # CURV_SMALL_MAX_FLOP
 CONVT_MAX_PHASES = 64               # CURV_CONVT_MAX_PHASES
 PERSAMPLE_COV_MAX_OUTPUTS = 16      # CURV_PERSAMPLE_COV_MAX_OUTPUTS

@@ -80,6 +80,27 @@ def _wm_rows(layer) -> int:
     return layer.weight.shape[1] if _is_convt(layer) else layer.weight.shape[0]
 
 
+def _check_reduce(model, layer) -> None:
+    """The layers ``KFAC(approximation="reduce")`` takes: Linear and Conv2d with groups 1 and dilation 1 (the reduce pass
+    of curv_kfac_reduce_accumulate has no grouped or dilated form, whatever `ops.admit_dilated` says; string padding is
+    refused as for expand)."""
+    kind = layer.__class__.__name__
+    why = None
+    if kind == 'Conv2d':
+        if layer.groups != 1:
+            why = f"a grouped convolution (groups={layer.groups})"
+        elif tuple(layer.dilation) != (1, 1):
+            why = f"a dilated convolution (dilation {tuple(layer.dilation)})"
+    elif kind == 'ConvTranspose2d':
+        why = "a transposed convolution"
+    elif kind == 'MultiheadAttention':
+        why = "an attention layer (its records are (T, N, E), with the batch second)"
+    if why is not None:
+        name = next((f"'{n}'" for n, mod in model.named_modules() if mod is layer), repr(layer))
+        raise NotImplementedError(f'KFAC(approximation="reduce"): layer {name} is {why}, which the '
+                                  f'reduce build does not take; approximation="expand" takes it')
+
+
 class _Slot(NamedTuple):
     """One piece of a layer's parameters as a block of columns of its [W | b] matrix (`_slots`)."""
     cols: slice       # the columns of Wm this piece holds
@@ -1159,13 +1180,27 @@ class KFAC(LinearisedPredictive, Curvature):
     ``state[layer] = [A, G]`` (fp32, exactly symmetric), ``inv_state[layer] = (L_A, L_G)`` with
     L = chol_lower((sqrt(s) F + sqrt(n) I)^-1).  ``record[layer] = [input, grad_output]``: unlike the
     reference the recorded grad_output is NOT pre-multiplied by the batch size (curvatures.py:310); the
-    factor N is folded into the scale of the G-side SYRK, which saves one pass over every gradient."""
+    factor N is folded into the scale of the G-side SYRK, which saves one pass over every gradient.
+
+    ``approximation`` (keyword-only extension) says how a layer that applies its weight at L positions per sample (the
+    output pixels of a Conv2d, the tokens of a Linear on (N, *, in) inputs) enters the factors.  ``"expand"``, the default
+    and the reference's form: all N L positions are columns of both Grams.  ``"reduce"`` (KFAC-reduce, Eschenhagen et al.,
+    NeurIPS 2023): the positions are reduced first, x_n = mean_l x_{n,l} (the ones entry of a biased layer
+    stays 1) and g_n = sum_l g_{n,l}, and A (+)= input_weight / N sum_n x_n x_n^T, G (+)= N / grad_scale^2 sum_n g_n g_n^T;
+    for L = 1 both forms coincide.  The shapes of ``state`` / ``inv_state`` are the same, so everything downstream
+    (``invert``, ``decompose``, the samplers, EFB, INF, the linearised predictives) takes either.  A reduce factor has
+    rank at most the number of SAMPLES accumulated into it (an expand factor: positions): accumulate it over many batches
+    and invert with ``add > 0``.  ``"reduce"`` takes Linear and Conv2d with groups 1, dilation 1 and integer padding."""
 
     _mha_as_projections = True
     _per_sample_groups = True
 
-    def __init__(self, model: Union[Module, Sequential], layer_types: Union[List[str], str] = None, *, shard=None):
+    def __init__(self, model: Union[Module, Sequential], layer_types: Union[List[str], str] = None, *, shard=None,
+                 approximation: str = "expand"):
+        if approximation not in ("expand", "reduce"):
+            raise ValueError(f'KFAC: approximation must be "expand" or "reduce", got {approximation!r}')
         super().__init__(model, layer_types, shard=shard)
+        self.approximation = approximation
         self.hooks = list()
         self.record = dict()
         self._fresh = set()                          # (layer, side) of factors that nothing has written yet
@@ -1174,6 +1209,8 @@ class KFAC(LinearisedPredictive, Curvature):
         for layer in model.modules():
             name = layer.__class__.__name__
             if name in self.layer_types:
+                if approximation == "reduce":
+                    _check_reduce(model, layer)
                 if name in ('Linear', 'Conv2d'):
                     if name == 'Conv2d' and tuple(layer.dilation) != (1, 1):
                         # the reference silently ignores it (curvatures.py:329)
@@ -1201,7 +1238,8 @@ class KFAC(LinearisedPredictive, Curvature):
 
     def update(self, batch_size: int = None, *, inputs: bool = True, grads: bool = True, input_weight: float = 1.0,
                grad_scale: float = 1.0):
-        """A += X X^T / (N L), G += (N g)(N g)^T / (N L) for every selected layer: one grouped launch.
+        """A += X X^T / (N L), G += (N g)(N g)^T / (N L) for every selected layer: one grouped launch.  (With
+        ``approximation="reduce"``: the position-reduced rows, N columns and L = 1 in these scales - the class docstring.)
 
         The keyword-only arguments extend the reference's ``update(batch_size)`` (curvatures.py:312) for
         Monte-Carlo Fisher loops that run several backward passes per forward pass
@@ -1218,9 +1256,9 @@ class KFAC(LinearisedPredictive, Curvature):
         gradients; the G side is divided by ``grad_scale ** 2``.  The caller skips ``update()`` on the steps the scaler
         skips (non-finite gradients)."""
         self._decomposition = None                   # (of the factors as they were: `decompose`)
-        jobs, group_jobs, half_jobs, convt_jobs, dilated_jobs = [], [], [], [], []
+        jobs, group_jobs, half_jobs, convt_jobs, dilated_jobs, reduce_jobs = [], [], [], [], [], []
         launch = {ops.FactorJob: jobs, ops.GroupFactorJob: group_jobs, ops.HalfFactorJob: half_jobs,
-                  ops.ConvTFactorJob: convt_jobs, ops.DilatedFactorJob: dilated_jobs}
+                  ops.ConvTFactorJob: convt_jobs, ops.DilatedFactorJob: dilated_jobs, ops.ReduceFactorJob: reduce_jobs}
         if not grad_scale > 0:
             raise ValueError(f"KFAC.update: grad_scale must be positive, got {grad_scale}")
         g_div = float(grad_scale) ** 2
@@ -1228,8 +1266,10 @@ class KFAC(LinearisedPredictive, Curvature):
             forward, backward = self.record[layer]
             if (inputs and forward is None) or (grads and backward is None):
                 raise RuntimeError("KFAC.update: no recorded forward/backward pass for a selected layer")
-            sides = ops.factor_jobs(layer, forward, backward, self._out_size.get(layer))
+            sides = ops.factor_jobs(layer, forward, backward, self._out_size.get(layer), self.approximation)
             N, L = sides.N, sides.L
+            if self.approximation == "reduce":
+                L = 1                                    # the positions are reduced before the Gram: N columns, not N L
             if layer not in self.state:
                 # a side that is not written by this call must start from zero, not from garbage
                 alloc = torch.empty if (inputs and grads) else torch.zeros
@@ -1264,23 +1304,24 @@ class KFAC(LinearisedPredictive, Curvature):
         if getattr(self, "_count_flops", False):                 # bench.py: what the launch plan executes
             self._last_flops = sum(ops.kfac_plan_flops(jobs)) + sum(ops.kfac_group_plan_flops(group_jobs)) + \
                 sum(ops.kfac_half_plan_flops(half_jobs)) + sum(ops.kfac_convt_plan_flops(convt_jobs)) + \
-                sum(ops.kfac_dilated_plan_flops(dilated_jobs))
+                sum(ops.kfac_dilated_plan_flops(dilated_jobs)) + sum(ops.kfac_reduce_plan_flops(reduce_jobs))
         ops.kfac_accumulate(jobs, events=getattr(self, "_timing_events", None))
         ops.kfac_accumulate_groups(group_jobs)
         ops.kfac_accumulate_half(half_jobs)
         ops.kfac_accumulate_convt(convt_jobs)
         ops.kfac_accumulate_dilated(dilated_jobs)
+        ops.kfac_accumulate_reduce(reduce_jobs)
 
     def _unsharded_path(self, records, inputs: bool, grads: bool) -> int:
         """The launch form of the fp32 factor build of an unsharded update() on `records` = [(layer, input, grad_output)]
         (`ops.ShapeOnly`s): decided by the library itself (curv_kfac_path_for evaluates every gate of the small form, not
-        only the flops) for the sides that come back as `FactorJob`.  Grouped, half-precision, transposed-convolution and
-        dilated A sides are built by launches of their own, whose plans are per factor."""
+        only the flops) for the sides that come back as `FactorJob`.  Grouped, half-precision, transposed-convolution,
+        dilated A sides and reduce factors are built by launches of their own, whose plans are per factor."""
         model_jobs = []
         for layer, forward, backward in records:
             if (inputs and forward is None) or (grads and backward is None):
                 return _lib.PATH_GROUPED
-            sides = ops.factor_jobs(layer, forward, backward, self._out_size.get(layer))
+            sides = ops.factor_jobs(layer, forward, backward, self._out_size.get(layer), self.approximation)
             model_jobs += [job for job, wanted in ((sides.a, inputs), (sides.g, grads))
                            if wanted and isinstance(job, ops.FactorJob)]
         return ops.kfac_path_for(model_jobs)

@@ -85,7 +85,7 @@ _kfac_last = {}                        # thread ident -> the "kfac" workspace it
 
 
 class _ConvJob:
-    """What the five factor jobs share: source and destination, the convolution geometry, and how the product enters the
+    """What the factor jobs share: source and destination, the convolution geometry, and how the product enters the
     destination.  Every subclass adds one field of its own."""
     __slots__ = ("src", "dst", "kernel", "stride", "padding", "has_bias", "scale", "first")
 
@@ -406,6 +406,69 @@ def kfac_accumulate_dilated(jobs: Sequence[DilatedFactorJob], events=None) -> No
                jobs[0].src.device, "kfac_dilated", events)
 
 
+class ReduceFactorJob(_ConvJob):
+    """One KFAC-reduce factor (curv_kfac_reduce_accumulate): dst (+)= scale * R R^T with R the (N, dim)
+    per-sample rows [+ ones column].  `form` = ``_lib.REDUCE_PLANE``: `src` is (N, C, H, W) and a row the mean (`mean`) or
+    sum over the output pixels of the im2col columns of the window; ``_lib.REDUCE_TOKEN``: `src` is (N, T, E) and a row the
+    mean or sum over T.  `src` is float32, bfloat16 or float16 (the rows and the build are float32); it may also be just
+    its shape, with `dtype` (plan queries)."""
+    __slots__ = ("form", "mean", "dtype")
+
+    def __init__(self, src, dst, kernel=(1, 1), stride=(1, 1), padding=(0, 0), has_bias=False, scale=1.0, first=False,
+                 form=_lib.REDUCE_PLANE, mean=True, dtype=None):
+        self._set(src, dst, kernel, stride, padding, has_bias, scale, first)
+        self.form, self.mean = int(form), bool(mean)
+        self.dtype = src.dtype if isinstance(src, torch.Tensor) else (dtype or torch.float32)
+
+
+def _reduce_descs(jobs: Sequence[ReduceFactorJob], check_tensors: bool = True):
+    arr = (_lib.curv_reduce_factor_desc * len(jobs))()
+    for d, j in zip(arr, jobs):
+        if j.dtype not in _PACK_DTYPES:
+            raise RuntimeError(f"reduce factor source must be float32, bfloat16 or float16, got {j.dtype}")
+        shape = tuple(int(v) for v in j.src.shape) if isinstance(j.src, torch.Tensor) else tuple(int(v) for v in j.src)
+        token = j.form == _lib.REDUCE_TOKEN
+        if len(shape) != (3 if token else 4):
+            raise RuntimeError("reduce factor source must be (N,T,E)" if token else "reduce factor source must be (N,C,H,W)")
+        if token:
+            d.N, d.T, d.E = shape
+            d.has_bias = int(j.has_bias)
+            dim = shape[2] + int(j.has_bias)
+        else:
+            _set_geometry(d, shape, j.kernel, j.stride, j.padding, j.has_bias)
+            dim = shape[1] * j.kernel[0] * j.kernel[1] + int(j.has_bias)
+        if check_tensors:
+            if not (j.src.is_cuda and j.dst.is_cuda):
+                raise RuntimeError("curvature_amd runs on MI355X only: got a CPU tensor (no CPU fallback)")
+            if not j.src.is_contiguous():
+                raise RuntimeError("curvature_amd expects contiguous tensors")
+            _require_gpu(j.dst)
+            if tuple(j.dst.shape) != (dim, dim):
+                raise RuntimeError(f"factor destination must be ({dim},{dim}), got {tuple(j.dst.shape)}")
+            d.src, d.dst = j.src.data_ptr(), j.dst.data_ptr()
+        d.first, d.scale = int(j.first), j.scale
+        d.dtype, d.form, d.mean = _PACK_DTYPES[j.dtype], j.form, int(j.mean)
+    return arr
+
+
+def kfac_reduce_plan_flops(jobs: Sequence[ReduceFactorJob]) -> List[int]:
+    """What the reduce build executes for each job (curv_kfac_reduce_plan_flops, host only): the additions of the reduce
+    pass plus the multiply-add FLOPs of the flat build of its (N, dim) rows.  `job.src` may be a tensor or its shape."""
+    if not jobs:
+        return []
+    return _plan_flops("curv_kfac_reduce_plan_flops", _reduce_descs(jobs, check_tensors=_all_tensors(jobs)), len(jobs))
+
+
+def kfac_accumulate_reduce(jobs: Sequence[ReduceFactorJob], events=None) -> None:
+    """KFAC-reduce factor build (curv_kfac_reduce_accumulate) on the current stream: per factor one streaming pass that
+    writes the per-sample rows, then one fp32 build of their Gram.  Scratch from `workspace` (so CURV_DEBUG_POISON covers
+    it).  `events` = (start, stop) ``torch.cuda.Event``s are recorded around the whole build."""
+    if not jobs:
+        return
+    _run_build("curv_kfac_reduce_workspace_bytes", "curv_kfac_reduce_accumulate", _reduce_descs(jobs), len(jobs),
+               jobs[0].src.device, "kfac_reduce", events)
+
+
 # Dilated convolutions (DESIGN.md K16) are opt-in: with the switch off - the default - every selection, refusal and message
 # is exactly what it was.
 _DILATED = False
@@ -472,9 +535,61 @@ def _factor_source(t, fp32: bool, flatten: bool):
     return t
 
 
-def factor_jobs(layer, x, g, out_size=None) -> LayerJobs:
+def _reduce_jobs(layer, x, g) -> LayerJobs:
+    """`factor_jobs` for ``approximation="reduce"``: a Linear layer on 2-D records has one position per
+    sample, where both forms coincide - today's jobs; a Linear layer on (N, *, in) records gets token-form jobs with N the
+    first dimension and L the product of the middle ones; a Conv2d (groups 1, dilation 1, integer padding) gets plane-form
+    jobs, also when L = 1.  Either dtype goes to the same job: the reduce pass upcasts."""
+    kind = layer.__class__.__name__
+    if x is None and g is None:
+        raise RuntimeError("KFAC.update: no recorded forward/backward pass for a selected layer")
+    has_bias = getattr(layer, "bias", None) is not None
+    if kind == 'Linear':
+        if len((x if x is not None else g).shape) == 2:
+            return factor_jobs(layer, x, g)
+        jobs = []
+        for t, bias, mean in ((x, has_bias, True), (g, False, False)):
+            t = _factor_source(t, fp32=False, flatten=False)
+            if t is None:
+                jobs.append(None)
+                continue
+            if len(t.shape) < 3:
+                raise RuntimeError("KFAC.update: the records of a Linear layer must both be (N, in) or both (N, *, in)")
+            N, L, E = t.shape[0], math.prod(t.shape[1:-1]), t.shape[-1]
+            src = (N, L, E) if isinstance(t, ShapeOnly) else t.reshape(N, L, E)
+            jobs.append(ReduceFactorJob(src, None, has_bias=bias, form=_lib.REDUCE_TOKEN, mean=mean, dtype=t.dtype))
+        return LayerJobs(jobs[0], jobs[1], layer.in_features + int(has_bias), layer.out_features, N, L, 1)
+    if kind != 'Conv2d':
+        raise NotImplementedError(f'approximation="reduce" does not take a {kind} layer; approximation="expand" does')
+    if int(layer.groups) != 1 or tuple(layer.dilation) != (1, 1) or not all(isinstance(p, int) for p in layer.padding):
+        raise NotImplementedError(f'approximation="reduce" takes a Conv2d with groups 1, dilation 1 and integer padding, '
+                                  f'got groups={layer.groups}, dilation={tuple(layer.dilation)}, padding={layer.padding}; '
+                                  f'approximation="expand" takes grouped and dilated layers')
+    x = _factor_source(x, fp32=False, flatten=False)
+    g = _factor_source(g, fp32=False, flatten=False)
+    for t in (x, g):
+        if t is not None and len(t.shape) != 4:
+            raise RuntimeError("KFAC.update: Conv2d records must be (N, C, H, W)")
+    kernel, stride, padding = layer.kernel_size, layer.stride, layer.padding
+    if g is not None:
+        out_size = tuple(g.shape[2:])
+    else:
+        out_size = tuple((x.shape[2 + d] + 2 * padding[d] - kernel[d]) // stride[d] + 1 for d in range(2))
+    a_job = g_job = None
+    if x is not None:
+        a_job = ReduceFactorJob(tuple(x.shape) if isinstance(x, ShapeOnly) else x, None, kernel, stride, padding, has_bias,
+                                mean=True, dtype=x.dtype)
+    if g is not None:
+        g_job = ReduceFactorJob(tuple(g.shape) if isinstance(g, ShapeOnly) else g, None, mean=False, dtype=g.dtype)
+    return LayerJobs(a_job, g_job, layer.in_channels * kernel[0] * kernel[1] + int(has_bias), layer.out_channels,
+                     (x if x is not None else g).shape[0], out_size[0] * out_size[1], 1)
+
+
+def factor_jobs(layer, x, g, out_size=None, approximation="expand") -> LayerJobs:
     """Which build each side of a selected layer goes to, and with which geometry: the one place that knows the layer
     kinds (Linear and attention projections, Conv2d, grouped Conv2d, ConvTranspose2d) and the dtype routing.
+    `approximation`: "expand" (every position of a weight-sharing layer is a column of the Gram: what follows) or "reduce"
+    (the positions are reduced first: `ReduceFactorJob`s, see `_reduce_jobs`).
 
     `x` / `g`: the recorded input / grad_output (either may be None: that side gets no job) or `ShapeOnly`
     stand-ins (the jobs' `src` is then a shape: plan queries).  Each side is routed by its dtype: float32 to `FactorJob`,
@@ -483,6 +598,10 @@ def factor_jobs(layer, x, g, out_size=None) -> LayerJobs:
     to `DilatedFactorJob`, as float32 too (without it the dilation is not looked at, as before).  `out_size`: the output size a ConvTranspose2d forward was
     seen to produce (it carries the effective output_padding), used when there is no `g` to read it from.  The jobs come
     without `dst`, `scale` and `first`."""
+    if approximation == "reduce":
+        return _reduce_jobs(layer, x, g)
+    if approximation != "expand":
+        raise ValueError(f'approximation must be "expand" or "reduce", got {approximation!r}')
     kind = layer.__class__.__name__
     conv, convt = kind in ('Conv2d', 'ConvTranspose2d'), kind == 'ConvTranspose2d'
     groups = int(layer.groups) if kind == 'Conv2d' else 1

@@ -78,17 +78,19 @@ def rank_cost(dims: Sequence[Sequence[float]], estimator: str = "kfac", rank: in
     return total
 
 
-def layer_dims(layers, shapes) -> List[tuple]:
+def layer_dims(layers, shapes, approximation: str = "expand") -> List[tuple]:
     """[(n, m, K, build flops)] per layer for `partition_layers` / `make_layer_shard` (a grouped convolution's entry
     carries its group count fifth); `shapes[layer]` = (input shape, grad_output shape) of one batch, taken as float32.
     The build flops are what the library's launch plans execute for the layer's two factors (host only - no GPU
-    needed): the partition asks the planner instead of re-stating its eligibility rules."""
+    needed): the partition asks the planner instead of re-stating its eligibility rules.  `approximation`: that of the
+    estimator (``KFAC(approximation=...)``); a reduce layer is priced by `ops.kfac_reduce_plan_flops`."""
     from . import ops
-    sides = [ops.factor_jobs(layer, *map(ops.ShapeOnly, shapes[layer])) for layer in layers]
+    sides = [ops.factor_jobs(layer, *map(ops.ShapeOnly, shapes[layer]), approximation=approximation) for layer in layers]
     flops = {}
     for cls, plan_flops in ((ops.FactorJob, ops.kfac_plan_flops), (ops.GroupFactorJob, ops.kfac_group_plan_flops),
                             (ops.ConvTFactorJob, ops.kfac_convt_plan_flops),
-                            (ops.DilatedFactorJob, ops.kfac_dilated_plan_flops)):
+                            (ops.DilatedFactorJob, ops.kfac_dilated_plan_flops),
+                            (ops.ReduceFactorJob, ops.kfac_reduce_plan_flops)):
         batch = [job for s in sides for job in (s.a, s.g) if type(job) is cls]
         flops.update(zip(map(id, batch), plan_flops(batch)))
     return [(s.n, s.m, s.K, float(flops[id(s.a)] + flops[id(s.g)])) + ((s.groups,) if s.groups > 1 else ())

@@ -307,6 +307,58 @@ int curv_kfac_dilated_plan_flops(const curv_dilated_factor_desc* descs, int n_fa
 int curv_kfac_dilated_accumulate(void* stream, const curv_dilated_factor_desc* descs, int n_factors, void* workspace,
                                  size_t workspace_bytes);
 
+/* ------------------------------------------------------------------------------------------------
+ * KFAC-reduce factor build (csrc/reduce_factor.hip): the shared positions of a weight-sharing layer are reduced first and
+ * the Gram runs over the N samples only (Eschenhagen et al., NeurIPS 2023):
+ *   dst (+)= scale * R R^T,  R the (N, dim) matrix of per-sample rows [plus the column of ones when `has_bias`].
+ * `form` = CURV_REDUCE_PLANE: `src` is a contiguous (N, C, H, W) tensor of `dtype`, dim = C kh kw and
+ *   row[n, (c, a, b)] = m * sum over the Ho x Wo output pixels (oh, ow) of xpad[n, c, oh sh + a - ph, ow sw + b - pw],
+ * the row mean (m = 1 / (Ho Wo), `mean` = 1) or row sum (m = 1, `mean` = 0) of F.unfold(src, kernel, padding, stride) over
+ * its columns, without the im2col matrix: the padding adds zeros, a tap that sees padding only gives 0.  The A side of a
+ * Conv2d is this with `mean` = 1, its G side the grad_output with kh = kw = 1, stride 1, padding 0 and `mean` = 0.
+ * `form` = CURV_REDUCE_TOKEN: `src` is a contiguous (N, T, E) tensor, dim = E and row[n, e] = m * sum_t src[n, t, e] with
+ * m = 1 / T or 1 (C, H, W and the window are not read): the two sides of a Linear layer applied to T tokens per sample.
+ * `dtype`: CURV_DTYPE_F32, CURV_DTYPE_BF16 or CURV_DTYPE_F16; half values are upcast exactly and summed in fp32.
+ *
+ * Per factor: one reduce pass reads `src` once and writes the rows (fp32, contiguous, 256-byte aligned) into the workspace,
+ * then ONE curv_kfac_accumulate call builds the factor from them as an (N, dim) flat source (CURV_PATH_AUTO; `has_bias`,
+ * `scale`, `first` passed through).  No float atomics: every row entry is summed by one workgroup in an order that follows
+ * from the factor's own geometry, so the result is bitwise reproducible and independent of the other factors of the call;
+ * it is exactly symmetric.  Never reads outside `src`; enqueues on `stream` only, never waits on the host and allocates
+ * nothing (graph capture works).  An empty call is a no-op.
+ * CURV_ERR_INVALID with the factor named, before anything is launched: unknown dtype or form; sizes below 1, a stride below
+ * 1 or a negative padding; a kernel larger than the padded input (no output pixel); dim above 2^20; 2^31 or more planes
+ * (N C) or token rows (N T); a window wider than 4096 taps; and whatever curv_kfac_accumulate refuses for the row matrix.
+ * ---------------------------------------------------------------------------------------------- */
+#define CURV_REDUCE_PLANE 0
+#define CURV_REDUCE_TOKEN 1
+typedef struct curv_reduce_factor_desc {
+  const void* src;
+  float* dst;
+  int32_t N, C, H, W;
+  int32_t kh, kw, sh, sw, ph, pw;
+  int32_t has_bias;
+  int32_t first;
+  float scale;
+  int32_t dtype;           /* CURV_DTYPE_* */
+  int32_t form;            /* CURV_REDUCE_* */
+  int32_t mean;            /* 1: the row is divided by the number of positions, 0: it is their sum */
+  int32_t T, E;            /* token form: positions per sample, features */
+} curv_reduce_factor_desc;
+
+/* Device scratch needed by curv_kfac_reduce_accumulate for these factors (bytes): the SUM over the factors of the rows of
+ * each plus the scratch of its build; 0 with error text for an invalid descriptor.  Host only: src / dst are not read. */
+size_t curv_kfac_reduce_workspace_bytes(const curv_reduce_factor_desc* descs, int n_factors);
+
+/* Host-only: per factor the additions of the reduce pass (plane form N C (H W kw + H kh kw), token form N T E) plus the
+ * multiply-add flops curv_kfac_plan_info reports for the build of its row matrix. */
+int curv_kfac_reduce_plan_flops(const curv_reduce_factor_desc* descs, int n_factors, long long* out);
+
+/* The build of all factors, one after another on `stream`.  `workspace`: curv_kfac_reduce_workspace_bytes, 256-byte
+ * aligned.  `descs` is a host array; it may be reused as soon as the call returns. */
+int curv_kfac_reduce_accumulate(void* stream, const curv_reduce_factor_desc* descs, int n_factors, void* workspace,
+                                size_t workspace_bytes);
+
 /* Same, recording HIP events (from curv_event_create) on `stream` around EVERYTHING the call enqueues behind the
  * descriptor-table uploads (padding / pre-tiling passes, the MFMA kernels, the k-slice reductions, the 3x3 assembly), so
  * that a benchmark can time the whole build without a profiler. */
