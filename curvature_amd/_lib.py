@@ -13,7 +13,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc")
 INCLUDE = os.path.normpath(os.path.join(_HERE, "..", "include"))
 LIB_PATH = os.path.join(CSRC, "libcurv_hip.so")
-SOURCES = ["api.cpp", "collective.cpp", "elementwise.hip", "syrk.hip", "syrk_flat.hip", "syrk_corr.hip", "syrk_pre.hip", "syrk_small.hip", "group_factor.hip", "kfac_half.hip", "convt_factor.hip", "dilated_factor.hip", "reduce_factor.hip", "persample.hip", "persample_dw.hip", "logit_mc.hip", "invert.hip", "gemm.hip", "inf.hip", "eigh.hip", "eigh_lowrank.hip"]
+SOURCES = ["api.cpp", "collective.cpp", "elementwise.hip", "syrk.hip", "syrk_flat.hip", "syrk_corr.hip", "syrk_pre.hip", "syrk_small.hip", "group_factor.hip", "kfac_half.hip", "convt_factor.hip", "dilated_factor.hip", "conv3d_factor.hip", "reduce_factor.hip", "persample.hip", "persample_dw.hip", "logit_mc.hip", "invert.hip", "gemm.hip", "inf.hip", "eigh.hip", "eigh_lowrank.hip"]
 HIPCC_FLAGS = ["-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC", "-shared", "-Wall",
                "-Wno-unused-function", "-ldl"]
 
@@ -134,6 +134,12 @@ class curv_convt_factor_desc(ctypes.Structure):
 class curv_dilated_factor_desc(ctypes.Structure):
     """Mirror of ``curv_dilated_factor_desc`` in include/curv_hip.h."""
     _fields_ = _ENDS + _SOURCE + _WINDOW + _ENTRY + [("dh", ctypes.c_int32), ("dw", ctypes.c_int32)]
+
+
+class curv_conv3d_factor_desc(ctypes.Structure):
+    """Mirror of ``curv_conv3d_factor_desc`` in include/curv_hip.h."""
+    _fields_ = _ENDS + [(k, ctypes.c_int32) for k in ("N", "C", "D", "H", "W", "kd", "kh", "kw", "sd", "sh", "sw", "pd", "ph",
+                                                     "pw")] + _ENTRY
 
 
 class curv_reduce_factor_desc(ctypes.Structure):
@@ -317,6 +323,9 @@ SIGNATURES = {
     "curv_kfac_dilated_workspace_bytes": (_sz, [ctypes.POINTER(curv_dilated_factor_desc), _i]),
     "curv_kfac_dilated_plan_flops": (_i, [ctypes.POINTER(curv_dilated_factor_desc), _i, ctypes.POINTER(ctypes.c_longlong)]),
     "curv_kfac_dilated_accumulate": (_i, [_vp, ctypes.POINTER(curv_dilated_factor_desc), _i, _vp, _sz]),
+    "curv_kfac_conv3d_workspace_bytes": (_sz, [ctypes.POINTER(curv_conv3d_factor_desc), _i]),
+    "curv_kfac_conv3d_plan_flops": (_i, [ctypes.POINTER(curv_conv3d_factor_desc), _i, ctypes.POINTER(ctypes.c_longlong)]),
+    "curv_kfac_conv3d_accumulate": (_i, [_vp, ctypes.POINTER(curv_conv3d_factor_desc), _i, _vp, _sz]),
     "curv_kfac_reduce_workspace_bytes": (_sz, [ctypes.POINTER(curv_reduce_factor_desc), _i]),
     "curv_kfac_reduce_plan_flops": (_i, [ctypes.POINTER(curv_reduce_factor_desc), _i, ctypes.POINTER(ctypes.c_longlong)]),
     "curv_kfac_reduce_accumulate": (_i, [_vp, ctypes.POINTER(curv_reduce_factor_desc), _i, _vp, _sz]),

@@ -32,7 +32,9 @@ SUPPORTED_LAYERS = ['Linear', 'Conv2d', 'MultiheadAttention']
 # selectable by name but not part of the default selection (which stays what the reference selects)
 OPTIONAL_LAYERS = ['ConvTranspose2d']
 # layer classes whose parameters are a weight matrix (Wm) and an optional bias
-_MATRIX_LAYERS = ('Linear', 'Conv2d', 'ConvTranspose2d')
+_MATRIX_LAYERS = ('Linear', 'Conv2d', 'ConvTranspose2d', 'Conv1d', 'Conv3d')
+# selectable by name only while `ops.admit_conv_nd` is on
+_ND_LAYERS = ('Conv1d', 'Conv3d')
 
 
 def _is_convt(layer) -> bool:
@@ -49,6 +51,31 @@ def _check_convt(layer) -> None:
         raise NotImplementedError("ConvTranspose2d with string padding is not supported")
 
 
+def _layer_name(model, layer) -> str:
+    """The layer's `named_modules()` name in quotes (its repr if the model does not hold it)."""
+    return next((f"'{n}'" for n, mod in model.named_modules() if mod is layer), repr(layer))
+
+
+def _check_conv_nd(model, layer) -> None:
+    """What the estimators represent of a selected Conv1d / Conv3d (`ops.admit_conv_nd`): groups 1, integer zero padding,
+    no dilation - except a Conv1d with `ops.admit_dilated` on, which is the dilated Conv2d of its (N, C, 1, L) view."""
+    kind, name = layer.__class__.__name__, _layer_name(model, layer)
+    why = None
+    if int(layer.groups) != 1:
+        why = f"has groups={layer.groups}; grouped {kind} layers are not supported"
+    elif isinstance(layer.padding, str):
+        why = f"has string padding ({layer.padding!r}); string padding modes are not supported"
+    elif layer.padding_mode != 'zeros':
+        why = f"has padding_mode={layer.padding_mode!r}; only zero padding is supported"
+    elif any(d != 1 for d in layer.dilation):
+        if kind == 'Conv3d':
+            why = f"is dilated (dilation {tuple(layer.dilation)}); dilated Conv3d layers are not supported"
+        elif not ops.dilated_admitted():
+            why = f"is dilated (dilation {tuple(layer.dilation)}); ops.admit_dilated() admits a dilated Conv1d"
+    if why is not None:
+        raise NotImplementedError(f"{kind} layer {name} {why}")
+
+
 def _check_dilated(model, layer) -> None:
     """What the A-factor build of a dilated Conv2d represents (`ops.admit_dilated`; curv_kfac_dilated_accumulate): groups 1,
     integer padding, stride 1 and a padding that is a multiple of the dilation - the residue classes of the input grid are
@@ -59,7 +86,7 @@ def _check_dilated(model, layer) -> None:
                                   "not supported")
     if not all(isinstance(p, int) for p in layer.padding):
         raise NotImplementedError(f"KFAC: dilated convolution {name}: string padding modes are not supported")
-    if tuple(layer.stride) != (1, 1) or any(p % d for p, d in zip(layer.padding, layer.dilation)):
+    if any(s != 1 for s in layer.stride) or any(p % d for p, d in zip(layer.padding, layer.dilation)):
         raise NotImplementedError(
             f"KFAC: dilated convolution {name} (stride {tuple(layer.stride)}, padding {tuple(layer.padding)}, dilation "
             f"{tuple(layer.dilation)}): the A-factor build needs stride 1 and a padding that is a multiple of the dilation; "
@@ -91,6 +118,11 @@ def _check_reduce(model, layer) -> None:
             why = f"a grouped convolution (groups={layer.groups})"
         elif tuple(layer.dilation) != (1, 1):
             why = f"a dilated convolution (dilation {tuple(layer.dilation)})"
+    elif kind == 'Conv1d':                               # (groups 1 and zero padding: `_check_conv_nd`)
+        if any(d != 1 for d in layer.dilation):
+            why = f"a dilated convolution (dilation {tuple(layer.dilation)})"
+    elif kind == 'Conv3d':
+        why = "a 3-D convolution (the reduce pass has no depth window)"
     elif kind == 'ConvTranspose2d':
         why = "a transposed convolution"
     elif kind == 'MultiheadAttention':
@@ -328,11 +360,16 @@ class Curvature(ABC):
         else:
             raise TypeError
         for _type in self.layer_types:
-            assert _type in SUPPORTED_LAYERS or _type in OPTIONAL_LAYERS
+            assert _type in SUPPORTED_LAYERS or _type in OPTIONAL_LAYERS or \
+                (ops.conv_nd_admitted() and _type in _ND_LAYERS)
         if 'ConvTranspose2d' in self.layer_types:
             for layer in model.modules():
                 if _is_convt(layer):
                     _check_convt(layer)
+        if any(_type in _ND_LAYERS for _type in self.layer_types):
+            for layer in model.modules():
+                if layer.__class__.__name__ in _ND_LAYERS and layer.__class__.__name__ in self.layer_types:
+                    _check_conv_nd(model, layer)
         self.state = dict()
         self.inv_state = dict()
         # optional layer sharding across ranks (curvature_amd.sharding.Shard); None = own every layer.
@@ -573,7 +610,13 @@ class Curvature(ABC):
             if kind not in self.layer_types:
                 continue
             why = None
-            if kind == 'Conv2d' or (kind == 'ConvTranspose2d' and wide):
+            if kind == 'Conv3d':
+                why = "a 3-D convolution: a sample's product sums over the output depths, which the per-sample kernels " \
+                      "would square one by one; KFAC, Diagonal, EFB and INF with the weight samplers take it"
+            elif kind == 'Conv1d':                           # groups 1, zero padding (`_check_conv_nd`): as a Conv2d
+                if any(d != 1 for d in layer.dilation) and not ops.dilated_admitted():
+                    why = "dilated convolution"
+            elif kind == 'Conv2d' or (kind == 'ConvTranspose2d' and wide):
                 if int(layer.groups) != 1 and tuple(layer.dilation) != (1, 1) and kind == 'Conv2d' and \
                         ops.dilated_admitted():
                     why = f"dilated convolution with groups={layer.groups}: ops.admit_dilated covers groups 1 only"
@@ -1222,6 +1265,13 @@ class KFAC(LinearisedPredictive, Curvature):
                     if name == 'Conv2d' and not all(isinstance(p, int) for p in layer.padding):
                         raise NotImplementedError("KFAC: string padding modes are not supported")
                     self._record_layer(layer)
+                elif name in _ND_LAYERS:
+                    # `_check_conv_nd` has passed; a Conv1d is the Conv2d of its (N, C, 1, L) view, a dilated one (with
+                    # `ops.admit_dilated`) under the rule of the class split; a Conv3d builds A from its depth-unfolded
+                    # stack (curv_kfac_conv3d_accumulate), G as a 1x1 factor of grad_output
+                    if any(d != 1 for d in layer.dilation):
+                        _check_dilated(model, layer)
+                    self._record_layer(layer)
                 elif name == 'ConvTranspose2d':
                     # Wm = weight.permute(1, 0, 2, 3).reshape(out, -1) [| bias]; A from the phase-split build
                     # (curv_kfac_convt_accumulate), G a 1x1 factor of grad_output as for Conv2d
@@ -1256,9 +1306,10 @@ class KFAC(LinearisedPredictive, Curvature):
         gradients; the G side is divided by ``grad_scale ** 2``.  The caller skips ``update()`` on the steps the scaler
         skips (non-finite gradients)."""
         self._decomposition = None                   # (of the factors as they were: `decompose`)
-        jobs, group_jobs, half_jobs, convt_jobs, dilated_jobs, reduce_jobs = [], [], [], [], [], []
+        jobs, group_jobs, half_jobs, convt_jobs, dilated_jobs, reduce_jobs, conv3d_jobs = [], [], [], [], [], [], []
         launch = {ops.FactorJob: jobs, ops.GroupFactorJob: group_jobs, ops.HalfFactorJob: half_jobs,
-                  ops.ConvTFactorJob: convt_jobs, ops.DilatedFactorJob: dilated_jobs, ops.ReduceFactorJob: reduce_jobs}
+                  ops.ConvTFactorJob: convt_jobs, ops.DilatedFactorJob: dilated_jobs, ops.ReduceFactorJob: reduce_jobs,
+                  ops.Conv3dFactorJob: conv3d_jobs}
         if not grad_scale > 0:
             raise ValueError(f"KFAC.update: grad_scale must be positive, got {grad_scale}")
         g_div = float(grad_scale) ** 2
@@ -1304,13 +1355,15 @@ class KFAC(LinearisedPredictive, Curvature):
         if getattr(self, "_count_flops", False):                 # bench.py: what the launch plan executes
             self._last_flops = sum(ops.kfac_plan_flops(jobs)) + sum(ops.kfac_group_plan_flops(group_jobs)) + \
                 sum(ops.kfac_half_plan_flops(half_jobs)) + sum(ops.kfac_convt_plan_flops(convt_jobs)) + \
-                sum(ops.kfac_dilated_plan_flops(dilated_jobs)) + sum(ops.kfac_reduce_plan_flops(reduce_jobs))
+                sum(ops.kfac_dilated_plan_flops(dilated_jobs)) + sum(ops.kfac_reduce_plan_flops(reduce_jobs)) + \
+                sum(ops.kfac_conv3d_plan_flops(conv3d_jobs))
         ops.kfac_accumulate(jobs, events=getattr(self, "_timing_events", None))
         ops.kfac_accumulate_groups(group_jobs)
         ops.kfac_accumulate_half(half_jobs)
         ops.kfac_accumulate_convt(convt_jobs)
         ops.kfac_accumulate_dilated(dilated_jobs)
         ops.kfac_accumulate_reduce(reduce_jobs)
+        ops.kfac_accumulate_conv3d(conv3d_jobs)
 
     def _unsharded_path(self, records, inputs: bool, grads: bool) -> int:
         """The launch form of the fp32 factor build of an unsharded update() on `records` = [(layer, input, grad_output)]

@@ -406,6 +406,64 @@ def kfac_accumulate_dilated(jobs: Sequence[DilatedFactorJob], events=None) -> No
                jobs[0].src.device, "kfac_dilated", events)
 
 
+class Conv3dFactorJob(_ConvJob):
+    """The A factor of a Conv3d (curv_kfac_conv3d_accumulate): dst (+)= scale * X X^T with X the 3-D im2col of
+    `src` (N, C, D, H, W) [+ ones row], rows in the order of ``weight.reshape(Cout, -1)``; built as the plain factor of the
+    depth-unfolded (N Do, C kd, H, W) stack.  `kernel`, `stride` and `padding` are (depth, height, width) triples; groups 1,
+    dilation 1.  `src` may also be just its (N, C, D, H, W) shape (plan queries)."""
+    __slots__ = ()
+
+    def __init__(self, src, dst, kernel, stride=(1, 1, 1), padding=(0, 0, 0), has_bias=False, scale=1.0, first=False):
+        self._set(src, dst, kernel, stride, padding, has_bias, scale, first)
+
+    @property
+    def stack_shape(self) -> tuple:
+        """(N Do, C kd, H, W): the stack the plain build runs on, with the 2-D window ``kernel[1:]`` etc."""
+        N, C, D, H, W = (int(v) for v in (self.src.shape if isinstance(self.src, torch.Tensor) else self.src))
+        Do = (D + 2 * self.padding[0] - self.kernel[0]) // self.stride[0] + 1
+        return (N * Do, C * self.kernel[0], H, W)
+
+
+def _conv3d_descs(jobs: Sequence[Conv3dFactorJob], check_tensors: bool = True):
+    arr = (_lib.curv_conv3d_factor_desc * len(jobs))()
+    for d, j in zip(arr, jobs):
+        if check_tensors:
+            _require_gpu(j.src, j.dst)
+        shape = tuple(j.src.shape) if isinstance(j.src, torch.Tensor) else tuple(j.src)
+        if len(shape) != 5 or not len(j.kernel) == len(j.stride) == len(j.padding) == 3:
+            raise RuntimeError("3-D convolution factor source must be a contiguous float32 (N,C,D,H,W) tensor, with "
+                               "(depth, height, width) kernel, stride and padding")
+        if check_tensors:
+            dim = shape[1] * math.prod(j.kernel) + int(j.has_bias)
+            if tuple(j.dst.shape) != (dim, dim):
+                raise RuntimeError(f"factor destination must be ({dim},{dim}), got {tuple(j.dst.shape)}")
+            d.src, d.dst = j.src.data_ptr(), j.dst.data_ptr()
+        d.N, d.C, d.D, d.H, d.W = map(int, shape)
+        d.kd, d.kh, d.kw = j.kernel
+        d.sd, d.sh, d.sw = j.stride
+        d.pd, d.ph, d.pw = j.padding
+        d.has_bias, d.first, d.scale = int(j.has_bias), int(j.first), j.scale
+    return arr
+
+
+def kfac_conv3d_plan_flops(jobs: Sequence[Conv3dFactorJob]) -> List[int]:
+    """Multiply-add FLOPs (2 per multiply-add) the Conv3d build executes for each job: those of the plain build of its
+    depth-unfolded stack (curv_kfac_conv3d_plan_flops, host only).  `job.src` may be a tensor or its (N, C, D, H, W) shape."""
+    if not jobs:
+        return []
+    return _plan_flops("curv_kfac_conv3d_plan_flops", _conv3d_descs(jobs, check_tensors=_all_tensors(jobs)), len(jobs))
+
+
+def kfac_accumulate_conv3d(jobs: Sequence[Conv3dFactorJob], events=None) -> None:
+    """A-factor build of 3-D convolutions (curv_kfac_conv3d_accumulate) on the current stream: per factor one gather pass
+    that writes the depth-unfolded stack, then one fp32 MFMA build of it.  Scratch from `workspace` (so CURV_DEBUG_POISON
+    covers it).  `events` = (start, stop) ``torch.cuda.Event``s are recorded around the whole build."""
+    if not jobs:
+        return
+    _run_build("curv_kfac_conv3d_workspace_bytes", "curv_kfac_conv3d_accumulate", _conv3d_descs(jobs), len(jobs),
+               jobs[0].src.device, "kfac_conv3d", events)
+
+
 class ReduceFactorJob(_ConvJob):
     """One KFAC-reduce factor (curv_kfac_reduce_accumulate): dst (+)= scale * R R^T with R the (N, dim)
     per-sample rows [+ ones column].  `form` = ``_lib.REDUCE_PLANE``: `src` is (N, C, H, W) and a row the mean (`mean`) or
@@ -489,6 +547,79 @@ def dilated_admitted() -> bool:
     return _DILATED
 
 
+# Conv1d and Conv3d are opt-in too: with the switch off - the default - every selection, refusal and message
+# is exactly what it was.
+_CONV_ND = False
+_ND_KINDS = ('Conv1d', 'Conv3d')
+
+
+def admit_conv_nd(enable: bool = True) -> bool:
+    """Switch Conv1d and Conv3d layers on or off for the process; returns what it was.  On: the estimators accept
+    ``'Conv1d'`` and ``'Conv3d'`` in `layer_types` by name (they never enter the default selection) and `factor_jobs` routes
+    them: a Conv1d as the Conv2d it is with a height of 1, the A side of a Conv3d to `Conv3dFactorJob`.  Groups 1, integer
+    zero padding; a Conv1d may be dilated with `admit_dilated` on, a Conv3d not.  The per-sample line takes a Conv1d, not
+    a Conv3d.  Off: both kinds are refused where they were."""
+    global _CONV_ND
+    was, _CONV_ND = _CONV_ND, bool(enable)
+    return was
+
+
+def conv_nd_admitted() -> bool:
+    return _CONV_ND
+
+
+class ConvView(NamedTuple):
+    """`conv_view` of a convolution layer: its 2-D window and its records as 4-D tensors."""
+    kernel: tuple
+    stride: tuple
+    padding: tuple
+    dilation: tuple
+    x: object
+    g: object
+    depth: Optional[tuple]
+
+
+def _reshaped(t, dims: int, shape_of):
+    """The record `t` (tensor, `ShapeOnly` or None) of `dims` dimensions with the shape `shape_of(its shape)`: a view where
+    the strides allow one.  A record of another rank is handed on as it is (the caller's own check names it)."""
+    if t is None or len(t.shape) != dims:
+        return t
+    shape = shape_of(tuple(int(v) for v in t.shape))
+    return ShapeOnly(shape, t.dtype) if isinstance(t, ShapeOnly) else t.reshape(shape)
+
+
+def conv_view(layer, x=None, g=None) -> ConvView:
+    """The 2-D geometry of a convolution layer and the 4-D views of its records (tensors, `ShapeOnly`s or None) - the one
+    place that knows how the convolution kinds map onto the (N, C, H, W) builds:
+    Conv2d / ConvTranspose2d: themselves.  Conv1d (`admit_conv_nd`): the Conv2d with H = 1 - kernel (1, k), stride (1, s),
+    padding (0, p), dilation (1, d), records (N, C, L) seen as (N, C, 1, L) (views: the strides of the record stay).
+    Conv3d (`admit_conv_nd`): the window (kh, kw) / (sh, sw) / (ph, pw) of the depth-unfolded stack, `depth` =
+    (kd, sd, pd); grad_output (N, Cout, Do, Ho, Wo) seen as (N, Cout, Do Ho, Wo), the input left as (N, C, D, H, W) - the
+    gather of curv_kfac_conv3d_accumulate reads it.  `dilation` is what the layer says (whether it is honoured is the
+    caller's business)."""
+    kind = layer.__class__.__name__
+    kernel, stride, padding, dilation = (tuple(v) if not isinstance(v, str) else v
+                                         for v in (layer.kernel_size, layer.stride, layer.padding, layer.dilation))
+    if kind not in _ND_KINDS:
+        return ConvView(kernel, stride, padding, dilation, x, g, None)
+    if not _CONV_ND:
+        raise NotImplementedError(f"{kind} layers are not supported (ops.admit_conv_nd() admits Conv1d and Conv3d)")
+    if int(layer.groups) != 1:
+        raise NotImplementedError(f"grouped {kind} (groups={layer.groups}) is not supported")
+    if isinstance(padding, str):
+        raise NotImplementedError(f"{kind} with string padding is not supported")
+    if layer.padding_mode != 'zeros':
+        raise NotImplementedError(f"{kind} with padding_mode={layer.padding_mode!r} is not supported")
+    if kind == 'Conv1d':
+        wide = lambda s: s[:2] + (1, s[2])
+        return ConvView((1,) + kernel, (1,) + stride, (0,) + padding, (1,) + dilation, _reshaped(x, 3, wide),
+                        _reshaped(g, 3, wide), None)
+    if dilation != (1, 1, 1):
+        raise NotImplementedError(f"dilated Conv3d (dilation {dilation}) is not supported")
+    return ConvView(kernel[1:], stride[1:], padding[1:], (1, 1), x,
+                    _reshaped(g, 5, lambda s: s[:2] + (s[2] * s[3], s[4])), (kernel[0], stride[0], padding[0]))
+
+
 class LayerJobs(NamedTuple):
     """The two factor builds of one layer (`factor_jobs`): `a` / `g` the job of the A / G side (None without a source),
     `n` / `m` the widths of A / G (of one group's, for a grouped layer), `N` samples of `L` positions each."""
@@ -559,18 +690,22 @@ def _reduce_jobs(layer, x, g) -> LayerJobs:
             src = (N, L, E) if isinstance(t, ShapeOnly) else t.reshape(N, L, E)
             jobs.append(ReduceFactorJob(src, None, has_bias=bias, form=_lib.REDUCE_TOKEN, mean=mean, dtype=t.dtype))
         return LayerJobs(jobs[0], jobs[1], layer.in_features + int(has_bias), layer.out_features, N, L, 1)
-    if kind != 'Conv2d':
+    if kind == 'Conv3d' and _CONV_ND:
+        raise NotImplementedError('approximation="reduce" does not take a 3-D convolution (Conv3d): the reduce pass has no '
+                                  'depth window; approximation="expand" takes it')
+    if kind != 'Conv2d' and not (kind == 'Conv1d' and _CONV_ND):
         raise NotImplementedError(f'approximation="reduce" does not take a {kind} layer; approximation="expand" does')
-    if int(layer.groups) != 1 or tuple(layer.dilation) != (1, 1) or not all(isinstance(p, int) for p in layer.padding):
-        raise NotImplementedError(f'approximation="reduce" takes a Conv2d with groups 1, dilation 1 and integer padding, '
+    if int(layer.groups) != 1 or any(d != 1 for d in layer.dilation) or not all(isinstance(p, int) for p in layer.padding):
+        raise NotImplementedError(f'approximation="reduce" takes a {kind} with groups 1, dilation 1 and integer padding, '
                                   f'got groups={layer.groups}, dilation={tuple(layer.dilation)}, padding={layer.padding}; '
                                   f'approximation="expand" takes grouped and dilated layers')
-    x = _factor_source(x, fp32=False, flatten=False)
-    g = _factor_source(g, fp32=False, flatten=False)
+    view = conv_view(layer, _factor_source(x, fp32=False, flatten=False), _factor_source(g, fp32=False, flatten=False))
+    x, g = view.x, view.g
     for t in (x, g):
         if t is not None and len(t.shape) != 4:
-            raise RuntimeError("KFAC.update: Conv2d records must be (N, C, H, W)")
-    kernel, stride, padding = layer.kernel_size, layer.stride, layer.padding
+            raise RuntimeError("KFAC.update: Conv2d records must be (N, C, H, W)" if kind == 'Conv2d' else
+                               "KFAC.update: Conv1d records must be (N, C, L)")
+    kernel, stride, padding = view.kernel, view.stride, view.padding
     if g is not None:
         out_size = tuple(g.shape[2:])
     else:
@@ -585,6 +720,29 @@ def _reduce_jobs(layer, x, g) -> LayerJobs:
                      (x if x is not None else g).shape[0], out_size[0] * out_size[1], 1)
 
 
+def _conv3d_jobs(layer, x, g, has_bias: bool) -> LayerJobs:
+    """`factor_jobs` of a Conv3d (`admit_conv_nd`; `x` float32, both contiguous): the A side to `Conv3dFactorJob` on the
+    (N, C, D, H, W) input; the G side a 1x1 factor of grad_output seen as (N, Cout, Do Ho, Wo), routed by its dtype.
+    L = Do Ho Wo, n = Cin kd kh kw [+ 1], m = Cout."""
+    kernel, stride, padding = (tuple(v) for v in (layer.kernel_size, layer.stride, layer.padding))
+    if x is not None and len(x.shape) != 5:
+        raise RuntimeError("KFAC.update: Conv3d inputs must be (N, C, D, H, W)")
+    if g is not None and len(g.shape) != 5:
+        raise RuntimeError("KFAC.update: Conv3d gradients must be (N, C, D, H, W)")
+    a_job = g_job = None
+    if x is not None:
+        a_job = Conv3dFactorJob(tuple(x.shape) if isinstance(x, ShapeOnly) else x, None, kernel, stride, padding, has_bias)
+    if g is not None:
+        L = math.prod(g.shape[2:])
+        g = conv_view(layer, None, g).g
+        src = g.shape if isinstance(g, ShapeOnly) else g
+        g_job = FactorJob(src, None) if g.dtype == torch.float32 else HalfFactorJob(src, None, dtype=g.dtype)
+    else:
+        L = math.prod((x.shape[2 + d] + 2 * padding[d] - kernel[d]) // stride[d] + 1 for d in range(3))
+    return LayerJobs(a_job, g_job, layer.in_channels * math.prod(kernel) + int(has_bias), layer.out_channels,
+                     (x if x is not None else g).shape[0], L, 1)
+
+
 def factor_jobs(layer, x, g, out_size=None, approximation="expand") -> LayerJobs:
     """Which build each side of a selected layer goes to, and with which geometry: the one place that knows the layer
     kinds (Linear and attention projections, Conv2d, grouped Conv2d, ConvTranspose2d) and the dtype routing.
@@ -595,7 +753,10 @@ def factor_jobs(layer, x, g, out_size=None, approximation="expand") -> LayerJobs
     stand-ins (the jobs' `src` is then a shape: plan queries).  Each side is routed by its dtype: float32 to `FactorJob`,
     bfloat16 / float16 to `HalfFactorJob`; both sides of a grouped convolution to `GroupFactorJob` and the A side of a
     transposed convolution to `ConvTFactorJob`, as float32; with `admit_dilated` the A side of a dilated groups-1 Conv2d
-    to `DilatedFactorJob`, as float32 too (without it the dilation is not looked at, as before).  `out_size`: the output size a ConvTranspose2d forward was
+    to `DilatedFactorJob`, as float32 too (without it the dilation is not looked at, as before).  With `admit_conv_nd` a
+    Conv1d (groups 1) is routed as the Conv2d of `conv_view` - its records seen as (N, C, 1, L) - and the A side of a Conv3d
+    goes to `Conv3dFactorJob`, as float32, its G side to the 1x1 job of grad_output seen as (N, Cout, Do Ho, Wo)
+    (`_conv3d_jobs`).  `out_size`: the output size a ConvTranspose2d forward was
     seen to produce (it carries the effective output_padding), used when there is no `g` to read it from.  The jobs come
     without `dst`, `scale` and `first`."""
     if approximation == "reduce":
@@ -603,18 +764,35 @@ def factor_jobs(layer, x, g, out_size=None, approximation="expand") -> LayerJobs
     if approximation != "expand":
         raise ValueError(f'approximation must be "expand" or "reduce", got {approximation!r}')
     kind = layer.__class__.__name__
-    conv, convt = kind in ('Conv2d', 'ConvTranspose2d'), kind == 'ConvTranspose2d'
+    nd = _CONV_ND and kind in _ND_KINDS                  # a Conv1d rides the Conv2d route through its (N, C, 1, L) view
+    conv, convt = kind in ('Conv2d', 'ConvTranspose2d') or nd, kind == 'ConvTranspose2d'
     groups = int(layer.groups) if kind == 'Conv2d' else 1
     has_bias = layer.bias is not None
     dilation = tuple(layer.dilation) if _DILATED and kind == 'Conv2d' else (1, 1)
+    depth = None
+    if nd:
+        view = conv_view(layer)                          # (refuses what neither kind can be: groups, string padding ...)
+        depth = view.depth                               # (kd, sd, pd) of a Conv3d
+        if view.dilation != (1, 1):
+            if not _DILATED:
+                raise NotImplementedError(f"dilated {kind} (dilation {tuple(layer.dilation)}) is not supported "
+                                          f"(ops.admit_dilated() admits a dilated Conv1d)")
+            dilation = view.dilation
     if dilation != (1, 1) and groups > 1:
         raise NotImplementedError(f"dilated convolution with groups > 1 (groups={groups}) is not supported")
-    x = _factor_source(x, fp32=groups > 1 or convt or dilation != (1, 1), flatten=not conv)
+    x = _factor_source(x, fp32=groups > 1 or convt or dilation != (1, 1) or depth is not None, flatten=not conv)
     g = _factor_source(g, fp32=groups > 1, flatten=not conv)
     if x is None and g is None:
         raise RuntimeError("KFAC.update: no recorded forward/backward pass for a selected layer")
+    if depth is not None:
+        return _conv3d_jobs(layer, x, g, has_bias)
     if conv:
         kernel, stride, padding = layer.kernel_size, layer.stride, layer.padding
+        if nd:                                           # the 2-D geometry and the (N, C, 1, L) views of a Conv1d
+            view = conv_view(layer, x, g)
+            kernel, stride, padding, x, g = view.kernel, view.stride, view.padding, view.x, view.g
+            if any(t is not None and len(t.shape) != 4 for t in (x, g)):
+                raise RuntimeError(f"KFAC.update: {kind} records must be (N, C, L)")
         C, m = layer.in_channels // groups, layer.out_channels // groups
         if convt and x is not None and len(x.shape) != 4:
             raise RuntimeError("KFAC.update: ConvTranspose2d inputs must be (N, C, H, W)")
@@ -899,7 +1077,13 @@ def per_sample_operands(layer, x, g, rows_outer: bool = False, in_place: bool = 
     if sides.groups != 1 or not isinstance(sides.a, (FactorJob, ConvTFactorJob, DilatedFactorJob)):
         raise NotImplementedError(f"per-sample update: unsupported layer {kind}")
     has_bias = sides.a.has_bias
-    if kind in ('Conv2d', 'ConvTranspose2d'):
+    if kind in ('Conv2d', 'ConvTranspose2d') or (_CONV_ND and kind == 'Conv1d'):
+        if kind == 'Conv1d':                               # read through its (N, C, 1, L) views: nothing is copied
+            if x.dim() != 3 or g.dim() != 3:
+                raise RuntimeError(f"per-sample update: records of Conv1d must be (N, C, L), got {tuple(x.shape)} and "
+                                   f"{tuple(g.shape)}")
+            view = conv_view(layer, x, g)
+            x, g = view.x, view.g
         if x.dim() != 4 or g.dim() != 4:
             raise RuntimeError(f"per-sample update: records of {kind} must be (N, C, H, W), got {tuple(x.shape)} and "
                                f"{tuple(g.shape)}")

@@ -90,6 +90,7 @@ def layer_dims(layers, shapes, approximation: str = "expand") -> List[tuple]:
     for cls, plan_flops in ((ops.FactorJob, ops.kfac_plan_flops), (ops.GroupFactorJob, ops.kfac_group_plan_flops),
                             (ops.ConvTFactorJob, ops.kfac_convt_plan_flops),
                             (ops.DilatedFactorJob, ops.kfac_dilated_plan_flops),
+                            (ops.Conv3dFactorJob, ops.kfac_conv3d_plan_flops),
                             (ops.ReduceFactorJob, ops.kfac_reduce_plan_flops)):
         batch = [job for s in sides for job in (s.a, s.g) if type(job) is cls]
         flops.update(zip(map(id, batch), plan_flops(batch)))

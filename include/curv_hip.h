@@ -308,6 +308,49 @@ int curv_kfac_dilated_accumulate(void* stream, const curv_dilated_factor_desc* d
                                  size_t workspace_bytes);
 
 /* ------------------------------------------------------------------------------------------------
+ * KFAC A-factor build of a Conv3d (csrc/conv3d_factor.hip; groups 1, dilation 1):
+ *   dst (+)= scale * X X^T,  X the 3-D im2col of `src` (N, C, D, H, W): row (c, a, b, e) at column (n, od, oh, ow) is
+ *   src[n, c, od sd - pd + a, oh sh - ph + b, ow sw - pw + e] (0 outside the input), plus the row of ones when `has_bias` -
+ * the rows in the order of weight.reshape(Cout, -1).  dim = C kd kh kw + has_bias.
+ *
+ * X is the 2-D im2col - kernel (kh, kw), stride (sh, sw), padding (ph, pw) - of the depth-unfolded stack
+ *   x'[(n Do + d), (c kd + a), h, w] = src[n, c, d sd + a - pd, h, w]   (0 where the depth index is outside [0, D)),
+ * Do = (D + 2 pd - kd) / sd + 1, column for column.  A gather pass reads `src` once and writes the contiguous
+ * (N Do, C kd, H, W) stack into the workspace, whole H W planes at a time (a source plane goes to at most ceil(kd / sd)
+ * places; the planes that are padding are written with zeros, the workspace is never assumed clean); curv_kfac_accumulate
+ * then runs once for the stack, with every fast path it has for C kd channels.  One call per factor: a factor's launch
+ * plan follows from its own geometry, so its bits do not depend on the other factors of the call; they are those of
+ * curv_kfac_accumulate on the stack.  The result is exactly symmetric; no atomics.  `src` may be only 4-byte aligned.
+ * Never reads outside `src`; enqueues on `stream` only, never waits on the host and allocates nothing (graph capture
+ * works).  An empty call is a no-op.
+ * CURV_ERR_INVALID with the factor named, before anything is launched: a size below 1, negative padding, a kernel larger
+ * than the padded input; 2^31 or more source planes, samples or channels of the stack, or floats in one plane or in one
+ * sample of the stack; and the limits of the plain build, applied to the stack (its text follows this build's).
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct curv_conv3d_factor_desc {
+  const float* src;
+  float* dst;
+  int32_t N, C, D, H, W;
+  int32_t kd, kh, kw, sd, sh, sw, pd, ph, pw;
+  int32_t has_bias;
+  int32_t first;
+  float scale;
+} curv_conv3d_factor_desc;
+
+/* Device scratch needed by curv_kfac_conv3d_accumulate for these factors (bytes): the SUM over the factors of the scratch
+ * each needs alone (its stack plus the scratch of its plain build); 0 with error text for invalid geometry. */
+size_t curv_kfac_conv3d_workspace_bytes(const curv_conv3d_factor_desc* descs, int n_factors);
+
+/* Host-only: multiply-add flops (2 per multiply-add) the build executes per factor: what curv_kfac_plan_info reports for
+ * the plain build of its stack. */
+int curv_kfac_conv3d_plan_flops(const curv_conv3d_factor_desc* descs, int n_factors, long long* out);
+
+/* The build of all factors, one after another on `stream`.  `workspace`: curv_kfac_conv3d_workspace_bytes, 256-byte
+ * aligned.  `descs` is a host array; it may be reused as soon as the call returns. */
+int curv_kfac_conv3d_accumulate(void* stream, const curv_conv3d_factor_desc* descs, int n_factors, void* workspace,
+                                size_t workspace_bytes);
+
+/* ------------------------------------------------------------------------------------------------
  * KFAC-reduce factor build (csrc/reduce_factor.hip): the shared positions of a weight-sharing layer are reduced first and
  * the Gram runs over the N samples only (Eschenhagen et al., NeurIPS 2023):
  *   dst (+)= scale * R R^T,  R the (N, dim) matrix of per-sample rows [plus the column of ones when `has_bias`].
