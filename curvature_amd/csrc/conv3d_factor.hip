@@ -28,7 +28,7 @@ struct Plan {
   int n;                      // dim
   int Do;                     // output depth
   long long P;                // H W: floats of a plane
-  size_t gather_bytes, build_bytes;
+  size_t stage_bytes, build_bytes;   // the stack; the scratch of its plain build
   long long flops;
 };
 
@@ -75,18 +75,16 @@ bool plan_of(const curv_conv3d_factor_desc& d, int index, Plan* p) {
   p->Do = (int)Do;
   p->P = P;
   p->n = (int)std::min<long long>(channels * d.kh * d.kw + (d.has_bias ? 1 : 0), lim - 1);
-  p->gather_bytes = align_up((size_t)(samples * channels * P) * sizeof(float), C3_ALIGN);
+  p->stage_bytes = align_up((size_t)(samples * channels * P) * sizeof(float), C3_ALIGN);
   const curv_factor_desc e = stack_desc(d, *p, reinterpret_cast<const char*>(C3_ALIGN));
-  long long info[CURV_PLAN_INFO_FIELDS];
-  const size_t need = curv_kfac_workspace_bytes(&e, 1);
-  if (need == 0 || curv_kfac_plan_info(&e, 1, info) != CURV_OK) {
+  size_t need;
+  if (!side::plain_plan(&e, 1, &need, &p->flops)) {
     const std::string why = curv_last_error();
     set_error("%s: factor %d: the plain build rejected the depth-unfolded stack (N %d C %d H %d W %d kernel %dx%d stride "
               "%dx%d padding %dx%d): %s", who, index, e.N, e.C, e.H, e.W, e.kh, e.kw, e.sh, e.sw, e.ph, e.pw, why.c_str());
     return false;
   }
   p->build_bytes = align_up(need, C3_ALIGN);
-  p->flops = info[CURV_PLAN_INFO_FIELDS - 1];
   return true;
 }
 
@@ -211,8 +209,7 @@ __global__ void __launch_bounds__(C3_THREADS) conv3d_gather_kernel(const GatherA
   }
 }
 
-int build_one(hipStream_t stream, const curv_conv3d_factor_desc& d, const Plan& p, char* stack, void* build_ws,
-              size_t build_bytes) {
+int build_one(hipStream_t stream, const curv_conv3d_factor_desc& d, const Plan& p, char* stack, void* build_ws) {
   GatherArgs A;
   A.src = d.src;
   A.dst = reinterpret_cast<float*>(stack);
@@ -240,11 +237,8 @@ int build_one(hipStream_t stream, const curv_conv3d_factor_desc& d, const Plan& 
   hipLaunchKernelGGL(conv3d_gather_kernel, dim3((unsigned)(copy_blocks + zero_blocks)), dim3(C3_THREADS), 0, stream, A);
   CURV_LAUNCH_CHECK();
   const curv_factor_desc e = stack_desc(d, p, stack);
-  return curv_kfac_accumulate(stream, &e, 1, build_ws, build_bytes);
+  return curv_kfac_accumulate(stream, &e, 1, build_ws, p.build_bytes);
 }
-
-// Scratch of one factor: its stack, then the scratch of its plain build.
-size_t bytes_of(const Plan& p) { return p.gather_bytes + std::max(p.build_bytes, C3_ALIGN); }
 
 }  // namespace
 }  // namespace curv
@@ -253,12 +247,7 @@ using namespace curv;
 
 extern "C" size_t curv_kfac_conv3d_workspace_bytes(const curv_conv3d_factor_desc* descs, int n_factors) {
   // the sum over the factors (every factor has scratch of its own); never 0 for valid descriptors: 0 reports an error
-  return side::workspace_bytes("curv_kfac_conv3d_workspace_bytes", descs, n_factors, plan_of,
-                               [](const std::vector<Plan>& plans) {
-                                 size_t total = 0;
-                                 for (const Plan& p : plans) total += bytes_of(p);
-                                 return total;
-                               });
+  return side::workspace_bytes("curv_kfac_conv3d_workspace_bytes", descs, n_factors, plan_of, side::staged_bytes<Plan>);
 }
 
 extern "C" int curv_kfac_conv3d_plan_flops(const curv_conv3d_factor_desc* descs, int n_factors, long long* out) {
@@ -267,22 +256,6 @@ extern "C" int curv_kfac_conv3d_plan_flops(const curv_conv3d_factor_desc* descs,
 
 extern "C" int curv_kfac_conv3d_accumulate(void* stream_, const curv_conv3d_factor_desc* descs, int n_factors,
                                            void* workspace, size_t workspace_bytes) {
-  const char* const name = "curv_kfac_conv3d_accumulate";
-  if (n_factors <= 0) return CURV_OK;
-  hipStream_t stream = (hipStream_t)stream_;
-  std::vector<Plan> plans;
-  if (!side::plans_of(name, descs, n_factors, plan_of, &plans)) return CURV_ERR_INVALID;
-  size_t total = 0;
-  for (const Plan& p : plans) total += bytes_of(p);
-  int rc = side::require_src_dst(name, descs, n_factors);
-  if (rc == CURV_OK) rc = side::require_workspace(name, workspace, workspace_bytes, total, C3_ALIGN);
-  if (rc != CURV_OK) return rc;
-  char* at = (char*)workspace;
-  for (int i = 0; i < n_factors; ++i) {
-    const Plan& p = plans[i];
-    rc = build_one(stream, descs[i], p, at, at + p.gather_bytes, std::max(p.build_bytes, C3_ALIGN));
-    if (rc != CURV_OK) return rc;
-    at += bytes_of(p);
-  }
-  return CURV_OK;
+  return side::staged_accumulate("curv_kfac_conv3d_accumulate", (hipStream_t)stream_, descs, n_factors, workspace,
+                                 workspace_bytes, C3_ALIGN, plan_of, build_one);
 }

@@ -169,19 +169,13 @@ bool plan_of(const curv_convt_factor_desc& d, int index, Plan* p) {
   const char* base = reinterpret_cast<const char*>(CT_ALIGN);
   for (int mis = 0; mis < 2; ++mis) {
     phase_descs(d, *p, reinterpret_cast<const float*>(base + 4 * mis), base, const_cast<char*>(base), &sub);
-    const size_t bytes = curv_kfac_workspace_bytes(sub.data(), (int)sub.size());
-    if (bytes == 0) {
+    size_t bytes;
+    if (!side::plain_plan(sub.data(), (int)sub.size(), &bytes, mis ? &p->flops : nullptr)) {   // (one plan query, not two)
       set_error("curv_kfac_convt: factor %d: the phase build rejected the geometry", index);
       return false;
     }
     p->build_bytes = std::max(p->build_bytes, bytes);
   }
-  std::vector<long long> info((size_t)CURV_PLAN_INFO_FIELDS * sub.size());
-  if (curv_kfac_plan_info(sub.data(), (int)sub.size(), info.data()) != CURV_OK) {
-    set_error("curv_kfac_convt: factor %d: the phase build rejected the geometry", index);
-    return false;
-  }
-  for (size_t s = 0; s < sub.size(); ++s) p->flops += info[(size_t)CURV_PLAN_INFO_FIELDS * s + CURV_PLAN_INFO_FIELDS - 1];
   return true;
 }
 

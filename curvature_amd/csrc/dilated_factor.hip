@@ -45,7 +45,7 @@ struct Plan {
   int nbh, nbw;               // classes below these have the larger size
   Group g[4];
   long long corner;           // N x output pixels of the classes with an empty sub-image
-  size_t gather_bytes, build_bytes;
+  size_t stage_bytes, build_bytes;   // the class stacks; the scratch of the plain builds (which run one after another)
   long long flops;
 };
 
@@ -71,16 +71,16 @@ curv_factor_desc group_desc(const curv_dilated_factor_desc& d, const Plan& p, in
 // Scratch and flops of the plain build of `e` alone; false (error text set, the plain build's own text behind it) where
 // the plain build refuses it: its size limits are this build's.
 bool plain_plan(const curv_factor_desc& e, int index, size_t* bytes, long long* flops) {
-  long long info[CURV_PLAN_INFO_FIELDS];
-  const size_t need = curv_kfac_workspace_bytes(&e, 1);
-  if (need == 0 || curv_kfac_plan_info(&e, 1, info) != CURV_OK) {
+  size_t need;
+  long long f;
+  if (!side::plain_plan(&e, 1, &need, &f)) {
     const std::string why = curv_last_error();
     set_error("curv_kfac_dilated: factor %d: the plain build rejected a class stack (N %d C %d H %d W %d kernel %dx%d "
               "padding %dx%d): %s", index, e.N, e.C, e.H, e.W, e.kh, e.kw, e.ph, e.pw, why.c_str());
     return false;
   }
   *bytes = std::max(*bytes, align_up(need, DL_ALIGN));
-  *flops += info[CURV_PLAN_INFO_FIELDS - 1];
+  *flops += f;
   return true;
 }
 
@@ -144,13 +144,14 @@ bool plan_of(const curv_dilated_factor_desc& d, int index, Plan* p) {
       continue;
     }
     g.built = true;
-    g.off = p->gather_bytes;
-    p->gather_bytes += align_up((size_t)d.N * g.count * d.C * g.Hg * g.Wg * sizeof(float), DL_ALIGN);
+    g.off = p->stage_bytes;
+    p->stage_bytes += align_up((size_t)d.N * g.count * d.C * g.Hg * g.Wg * sizeof(float), DL_ALIGN);
     const curv_factor_desc e = group_desc(d, *p, q, reinterpret_cast<const char*>(DL_ALIGN));
     if (!plain_plan(e, index, &p->build_bytes, &p->flops)) return false;
   }
   // (class (0, 0) has the larger size and output pixel (0, 0): the kernel fits, so group 0 is always built, and with it
   // the caller's `first` always has a build that honours it)
+  p->build_bytes = std::max(p->build_bytes, DL_ALIGN);
   return true;
 }
 
@@ -226,11 +227,10 @@ __global__ void dilated_corner_kernel(float* corner, float add) {
   if (threadIdx.x == 0) *corner += add;
 }
 
-int build_one(hipStream_t stream, const curv_dilated_factor_desc& d, const Plan& p, char* stacks, void* build_ws,
-              size_t build_bytes) {
+int build_one(hipStream_t stream, const curv_dilated_factor_desc& d, const Plan& p, char* stacks, void* build_ws) {
   if (p.plain) {
     const curv_factor_desc e = group_desc(d, p, 0, nullptr);
-    return curv_kfac_accumulate(stream, &e, 1, build_ws, build_bytes);
+    return curv_kfac_accumulate(stream, &e, 1, build_ws, p.build_bytes);
   }
   GatherArgs A;
   A.src = d.src;
@@ -260,7 +260,7 @@ int build_one(hipStream_t stream, const curv_dilated_factor_desc& d, const Plan&
     curv_factor_desc e = group_desc(d, p, q, stacks);
     e.first = first ? 1 : 0;
     first = false;
-    const int rc = curv_kfac_accumulate(stream, &e, 1, build_ws, build_bytes);
+    const int rc = curv_kfac_accumulate(stream, &e, 1, build_ws, p.build_bytes);
     if (rc != CURV_OK) return rc;
   }
   if (p.corner > 0 && d.has_bias) {
@@ -271,9 +271,6 @@ int build_one(hipStream_t stream, const curv_dilated_factor_desc& d, const Plan&
   return CURV_OK;
 }
 
-// Scratch of one factor: its class stacks, then the scratch of its plain builds (which run one after another).
-size_t bytes_of(const Plan& p) { return p.gather_bytes + std::max(p.build_bytes, DL_ALIGN); }
-
 }  // namespace
 }  // namespace curv
 
@@ -281,12 +278,7 @@ using namespace curv;
 
 extern "C" size_t curv_kfac_dilated_workspace_bytes(const curv_dilated_factor_desc* descs, int n_factors) {
   // the sum over the factors (every factor has scratch of its own); never 0 for valid descriptors: 0 reports an error
-  return side::workspace_bytes("curv_kfac_dilated_workspace_bytes", descs, n_factors, plan_of,
-                               [](const std::vector<Plan>& plans) {
-                                 size_t total = 0;
-                                 for (const Plan& p : plans) total += bytes_of(p);
-                                 return total;
-                               });
+  return side::workspace_bytes("curv_kfac_dilated_workspace_bytes", descs, n_factors, plan_of, side::staged_bytes<Plan>);
 }
 
 extern "C" int curv_kfac_dilated_plan_flops(const curv_dilated_factor_desc* descs, int n_factors, long long* out) {
@@ -295,22 +287,6 @@ extern "C" int curv_kfac_dilated_plan_flops(const curv_dilated_factor_desc* desc
 
 extern "C" int curv_kfac_dilated_accumulate(void* stream_, const curv_dilated_factor_desc* descs, int n_factors,
                                             void* workspace, size_t workspace_bytes) {
-  const char* const name = "curv_kfac_dilated_accumulate";
-  if (n_factors <= 0) return CURV_OK;
-  hipStream_t stream = (hipStream_t)stream_;
-  std::vector<Plan> plans;
-  if (!side::plans_of(name, descs, n_factors, plan_of, &plans)) return CURV_ERR_INVALID;
-  size_t total = 0;
-  for (const Plan& p : plans) total += bytes_of(p);
-  int rc = side::require_src_dst(name, descs, n_factors);
-  if (rc == CURV_OK) rc = side::require_workspace(name, workspace, workspace_bytes, total, DL_ALIGN);
-  if (rc != CURV_OK) return rc;
-  char* at = (char*)workspace;
-  for (int i = 0; i < n_factors; ++i) {
-    const Plan& p = plans[i];
-    rc = build_one(stream, descs[i], p, at, at + p.gather_bytes, std::max(p.build_bytes, DL_ALIGN));
-    if (rc != CURV_OK) return rc;
-    at += bytes_of(p);
-  }
-  return CURV_OK;
+  return side::staged_accumulate("curv_kfac_dilated_accumulate", (hipStream_t)stream_, descs, n_factors, workspace,
+                                 workspace_bytes, DL_ALIGN, plan_of, build_one);
 }

@@ -104,14 +104,10 @@ bool plan_of(const curv_group_factor_desc& d, int index, Plan* p) {
   // sources, which every 256-byte aligned slot has)
   std::vector<curv_factor_desc> sub;
   wide_descs(d, *p, reinterpret_cast<const float*>(GRP_SLOT_ALIGN), &sub);
-  p->build_bytes = curv_kfac_workspace_bytes(sub.data(), d.groups);
-  std::vector<long long> info((size_t)CURV_PLAN_INFO_FIELDS * d.groups);
-  if (p->build_bytes == 0 || curv_kfac_plan_info(sub.data(), d.groups, info.data()) != CURV_OK) {
+  if (!side::plain_plan(sub.data(), d.groups, &p->build_bytes, &p->flops)) {
     set_error("curv_kfac_group: factor %d: the per-group build rejected the geometry", index);
     return false;
   }
-  p->flops = 0;
-  for (int g = 0; g < d.groups; ++g) p->flops += info[(size_t)CURV_PLAN_INFO_FIELDS * g + CURV_PLAN_INFO_FIELDS - 1];
   return true;
 }
 

@@ -37,7 +37,7 @@ struct Plan {
   unsigned TR, segw;          // rows and columns of a piece (PP > 1: H and W)
   int Ho, Wo;
   float inv;                  // 1 / L or 1
-  size_t rows_bytes, build_bytes;
+  size_t stage_bytes, build_bytes;   // the rows; the scratch of their build
   long long flops;
 };
 
@@ -128,19 +128,19 @@ bool plan_of(const curv_reduce_factor_desc& d, int index, Plan* p) {
     return false;
   }
   p->inv = d.mean ? (float)(1.0 / (double)L) : 1.0f;
-  p->rows_bytes = align_up((size_t)d.N * p->dim * sizeof(float), RD_ALIGN);
+  p->stage_bytes = align_up((size_t)d.N * p->dim * sizeof(float), RD_ALIGN);
   // the build of the row matrix: its size limits are this build's
   const curv_factor_desc e = flat_desc(d, p->dim, reinterpret_cast<const float*>(RD_ALIGN));
-  long long info[CURV_PLAN_INFO_FIELDS];
-  const size_t need = curv_kfac_workspace_bytes(&e, 1);
-  if (need == 0 || curv_kfac_plan_info(&e, 1, info) != CURV_OK) {
+  size_t need;
+  long long flat;
+  if (!side::plain_plan(&e, 1, &need, &flat)) {
     const std::string why = curv_last_error();
     set_error("%s: factor %d: the flat build rejected the (N %d, dim %d) row matrix: %s", who, index, d.N, p->dim,
               why.c_str());
     return false;
   }
   p->build_bytes = align_up(need, RD_ALIGN);
-  p->flops = adds + info[CURV_PLAN_INFO_FIELDS - 1];
+  p->flops = adds + flat;
   return true;
 }
 
@@ -313,8 +313,8 @@ int launch_form(hipStream_t stream, int form, unsigned blocks, const ReduceArgs&
   return CURV_OK;
 }
 
-int build_one(hipStream_t stream, const curv_reduce_factor_desc& d, const Plan& p, float* rows, void* build_ws,
-              size_t build_bytes) {
+int build_one(hipStream_t stream, const curv_reduce_factor_desc& d, const Plan& p, char* stage, void* build_ws) {
+  float* rows = reinterpret_cast<float*>(stage);
   ReduceArgs A{};
   A.src = d.src;
   A.dst = rows;
@@ -333,16 +333,7 @@ int build_one(hipStream_t stream, const curv_reduce_factor_desc& d, const Plan& 
   else rc = launch_form<CURV_DTYPE_F16>(stream, d.form, blocks, A);
   if (rc != CURV_OK) return rc;
   const curv_factor_desc e = flat_desc(d, p.dim, rows);
-  return curv_kfac_accumulate(stream, &e, 1, build_ws, build_bytes);
-}
-
-// Scratch of one factor: its rows, then the scratch of its build.
-size_t bytes_of(const Plan& p) { return p.rows_bytes + p.build_bytes; }
-
-size_t total_bytes(const std::vector<Plan>& plans) {
-  size_t total = 0;
-  for (const Plan& p : plans) total += bytes_of(p);
-  return total;
+  return curv_kfac_accumulate(stream, &e, 1, build_ws, p.build_bytes);
 }
 
 }  // namespace
@@ -352,7 +343,7 @@ using namespace curv;
 
 extern "C" size_t curv_kfac_reduce_workspace_bytes(const curv_reduce_factor_desc* descs, int n_factors) {
   // the sum over the factors (every factor has scratch of its own); never 0 for valid descriptors: 0 reports an error
-  return side::workspace_bytes("curv_kfac_reduce_workspace_bytes", descs, n_factors, plan_of, total_bytes);
+  return side::workspace_bytes("curv_kfac_reduce_workspace_bytes", descs, n_factors, plan_of, side::staged_bytes<Plan>);
 }
 
 extern "C" int curv_kfac_reduce_plan_flops(const curv_reduce_factor_desc* descs, int n_factors, long long* out) {
@@ -361,20 +352,6 @@ extern "C" int curv_kfac_reduce_plan_flops(const curv_reduce_factor_desc* descs,
 
 extern "C" int curv_kfac_reduce_accumulate(void* stream_, const curv_reduce_factor_desc* descs, int n_factors,
                                            void* workspace, size_t workspace_bytes) {
-  const char* const name = "curv_kfac_reduce_accumulate";
-  if (n_factors <= 0) return CURV_OK;
-  hipStream_t stream = (hipStream_t)stream_;
-  std::vector<Plan> plans;
-  if (!side::plans_of(name, descs, n_factors, plan_of, &plans)) return CURV_ERR_INVALID;
-  int rc = side::require_src_dst(name, descs, n_factors);
-  if (rc == CURV_OK) rc = side::require_workspace(name, workspace, workspace_bytes, total_bytes(plans), RD_ALIGN);
-  if (rc != CURV_OK) return rc;
-  char* at = (char*)workspace;
-  for (int i = 0; i < n_factors; ++i) {
-    const Plan& p = plans[i];
-    rc = build_one(stream, descs[i], p, reinterpret_cast<float*>(at), at + p.rows_bytes, p.build_bytes);
-    if (rc != CURV_OK) return rc;
-    at += bytes_of(p);
-  }
-  return CURV_OK;
+  return side::staged_accumulate("curv_kfac_reduce_accumulate", (hipStream_t)stream_, descs, n_factors, workspace,
+                                 workspace_bytes, RD_ALIGN, plan_of, build_one);
 }

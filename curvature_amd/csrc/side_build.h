@@ -1,8 +1,9 @@
 // What the convolution factor builds share: the check of a convolution geometry (the main build of syrk.hip and
 // syrk_small.hip takes it too) and, for the side builds (kfac_half.hip, group_factor.hip, convt_factor.hip,
-// persample.hip), the bodies of the *_workspace_bytes / *_plan_flops / *_accumulate entry points.  Argument batches
-// live in kernarg.h.  A side build brings its own descriptor, `Plan`, `bool plan_of(const Desc&, int index, Plan*)`
-// with its own limits, its kernels and its workspace layout.
+// persample.hip), the bodies of the *_workspace_bytes / *_plan_flops / *_accumulate entry points; the query of the plain
+// build that the builds which end in curv_kfac_accumulate make (`plain_plan`), and the whole *_accumulate of the staged
+// ones (`staged_accumulate`).  Argument batches live in kernarg.h.  A side build brings its own descriptor, `Plan`,
+// `bool plan_of(const Desc&, int index, Plan*)` with its own limits, its kernels and its workspace layout.
 #pragma once
 #include "kernarg.h"
 
@@ -107,6 +108,50 @@ inline int require_workspace(const char* name, const void* workspace, size_t byt
     return CURV_ERR_WORKSPACE;
   }
   return CURV_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ the plain sub-build
+// What the plain build (curv_kfac_accumulate) needs for the `count` stand-in descriptors `sub` a side build hands it:
+// `*bytes` of scratch and, unless `flops` is null, `*flops` = the sum of its plan's executed flops.  false where it
+// refuses them: its text is in curv_last_error(), the caller words its own message.
+inline bool plain_plan(const curv_factor_desc* sub, int count, size_t* bytes, long long* flops) {
+  *bytes = curv_kfac_workspace_bytes(sub, count);
+  if (*bytes == 0) return false;
+  if (!flops) return true;
+  std::vector<long long> info((size_t)CURV_PLAN_INFO_FIELDS * count);
+  if (curv_kfac_plan_info(sub, count, info.data()) != CURV_OK) return false;
+  *flops = 0;
+  for (int i = 0; i < count; ++i) *flops += info[(size_t)CURV_PLAN_INFO_FIELDS * i + CURV_PLAN_INFO_FIELDS - 1];
+  return true;
+}
+
+// ------------------------------------------------------------------------------------------------ staged builds
+// A staged build (dilated_factor.hip, conv3d_factor.hip, reduce_factor.hip) writes, per factor, a stack or row matrix into
+// scratch and runs the plain build on it.  Its Plan names `stage_bytes` (the staging region) and `build_bytes` (the plain
+// build's scratch, never 0); the workspace is the SUM over the factors of the two, every factor's staging region followed
+// by its build region: no factor waits for another's scratch.
+template <typename Plan>
+size_t staged_bytes(const std::vector<Plan>& plans) {
+  size_t total = 0;
+  for (const Plan& p : plans) total += p.stage_bytes + p.build_bytes;
+  return total;
+}
+
+// *_accumulate of a staged build: build_one(stream, desc, plan, staging region, build region) for one factor after another.
+template <typename Desc, typename Plan, typename BuildOne>
+int staged_accumulate(const char* name, hipStream_t stream, const Desc* descs, int n, void* workspace, size_t bytes,
+                      size_t align, bool (*plan_of)(const Desc&, int, Plan*), BuildOne build_one) {
+  if (n <= 0) return CURV_OK;
+  std::vector<Plan> plans;
+  if (!plans_of(name, descs, n, plan_of, &plans)) return CURV_ERR_INVALID;
+  int rc = require_src_dst(name, descs, n);
+  if (rc == CURV_OK) rc = require_workspace(name, workspace, bytes, staged_bytes(plans), align);
+  char* at = (char*)workspace;
+  for (int i = 0; i < n && rc == CURV_OK; ++i) {
+    rc = build_one(stream, descs[i], plans[i], at, at + plans[i].stage_bytes);
+    at += plans[i].stage_bytes + plans[i].build_bytes;
+  }
+  return rc;
 }
 
 }  // namespace side

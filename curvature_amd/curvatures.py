@@ -1306,10 +1306,7 @@ class KFAC(LinearisedPredictive, Curvature):
         gradients; the G side is divided by ``grad_scale ** 2``.  The caller skips ``update()`` on the steps the scaler
         skips (non-finite gradients)."""
         self._decomposition = None                   # (of the factors as they were: `decompose`)
-        jobs, group_jobs, half_jobs, convt_jobs, dilated_jobs, reduce_jobs, conv3d_jobs = [], [], [], [], [], [], []
-        launch = {ops.FactorJob: jobs, ops.GroupFactorJob: group_jobs, ops.HalfFactorJob: half_jobs,
-                  ops.ConvTFactorJob: convt_jobs, ops.DilatedFactorJob: dilated_jobs, ops.ReduceFactorJob: reduce_jobs,
-                  ops.Conv3dFactorJob: conv3d_jobs}
+        jobs = []                                    # of every class: ops.accumulate_factors sorts them to their builds
         if not grad_scale > 0:
             raise ValueError(f"KFAC.update: grad_scale must be positive, got {grad_scale}")
         g_div = float(grad_scale) ** 2
@@ -1334,11 +1331,11 @@ class KFAC(LinearisedPredictive, Curvature):
             if inputs:
                 job = sides.a
                 job.dst, job.scale, job.first = A, float(input_weight) / (N * L), self._take_fresh(layer, 0)
-                launch[type(job)].append(job)
+                jobs.append(job)
             if grads:
                 job = sides.g                            # same scales for every kind of layer
                 job.dst, job.scale, job.first = G, float(N) / L / g_div, self._take_fresh(layer, 1)
-                launch[type(job)].append(job)
+                jobs.append(job)
         if self.shard is not None and self.shard.world > 1:
             # the launch form is a property of the MODEL, not of this rank's share: a share under the small-launch threshold
             # would otherwise sum its factors in another order than the unsharded run (which is over it).  It follows
@@ -1351,19 +1348,11 @@ class KFAC(LinearisedPredictive, Curvature):
             if hint is None:
                 hint = self._path_hints[key] = self._unsharded_path(records, inputs, grads)
             for job in jobs:
-                job.path_hint = hint
+                if type(job) is ops.FactorJob:
+                    job.path_hint = hint
         if getattr(self, "_count_flops", False):                 # bench.py: what the launch plan executes
-            self._last_flops = sum(ops.kfac_plan_flops(jobs)) + sum(ops.kfac_group_plan_flops(group_jobs)) + \
-                sum(ops.kfac_half_plan_flops(half_jobs)) + sum(ops.kfac_convt_plan_flops(convt_jobs)) + \
-                sum(ops.kfac_dilated_plan_flops(dilated_jobs)) + sum(ops.kfac_reduce_plan_flops(reduce_jobs)) + \
-                sum(ops.kfac_conv3d_plan_flops(conv3d_jobs))
-        ops.kfac_accumulate(jobs, events=getattr(self, "_timing_events", None))
-        ops.kfac_accumulate_groups(group_jobs)
-        ops.kfac_accumulate_half(half_jobs)
-        ops.kfac_accumulate_convt(convt_jobs)
-        ops.kfac_accumulate_dilated(dilated_jobs)
-        ops.kfac_accumulate_reduce(reduce_jobs)
-        ops.kfac_accumulate_conv3d(conv3d_jobs)
+            self._last_flops = sum(ops.factor_plan_flops(jobs))
+        ops.accumulate_factors(jobs, events=getattr(self, "_timing_events", None))
 
     def _unsharded_path(self, records, inputs: bool, grads: bool) -> int:
         """The launch form of the fp32 factor build of an unsharded update() on `records` = [(layer, input, grad_output)]

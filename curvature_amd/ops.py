@@ -7,6 +7,7 @@ there is no CPU fallback.
 import ctypes
 import math
 import os
+import sys
 import threading
 from typing import List, NamedTuple, Optional, Sequence
 
@@ -169,6 +170,23 @@ def _run_build(bytes_name: str, name: str, arr, n: int, device, tag: str, events
         events[1].record()
 
 
+def _side_plan_flops(cls, jobs) -> List[int]:
+    """``<symbol>_plan_flops`` of the `FACTOR_BUILDS` record of job class `cls`."""
+    if not jobs:
+        return []
+    build = _BUILD_OF[cls]
+    return _plan_flops(build.symbol + "_plan_flops", build.descs(jobs, check_tensors=_all_tensors(jobs)), len(jobs))
+
+
+def _side_accumulate(cls, jobs, events) -> None:
+    """``<symbol>_accumulate`` of the `FACTOR_BUILDS` record of job class `cls`, with scratch from ``workspace(tag)``."""
+    if not jobs:
+        return
+    build = _BUILD_OF[cls]
+    _run_build(build.symbol + "_workspace_bytes", build.symbol + "_accumulate", build.descs(jobs), len(jobs),
+               jobs[0].src.device, build.tag, events)
+
+
 def _factor_descs(jobs: Sequence[FactorJob], check_tensors: bool = True):
     arr = (curv_factor_desc * len(jobs))()
     for d, j in zip(arr, jobs):
@@ -270,19 +288,14 @@ def _half_descs(jobs: Sequence[HalfFactorJob], check_tensors: bool = True):
 def kfac_half_plan_flops(jobs: Sequence[HalfFactorJob]) -> List[int]:
     """FLOPs (2 per multiply-add) the half-precision build executes for each job (curv_kfac16_plan_flops, host only):
     every 128 x 128 tile on and above the diagonal over K padded to 16."""
-    if not jobs:
-        return []
-    return _plan_flops("curv_kfac16_plan_flops", _half_descs(jobs, check_tensors=_all_tensors(jobs)), len(jobs))
+    return _side_plan_flops(HalfFactorJob, jobs)
 
 
 def kfac_accumulate_half(jobs: Sequence[HalfFactorJob], events=None) -> None:
     """Factor build from bf16 / fp16 sources (curv_kfac16_accumulate): a pack, an MFMA and a reduce launch per batch of
     factors, on the current stream.  Scratch from `workspace` (so CURV_DEBUG_POISON covers it).  `events` = (start,
     stop) ``torch.cuda.Event``s (enable_timing) are recorded around the whole build."""
-    if not jobs:
-        return
-    _run_build("curv_kfac16_workspace_bytes", "curv_kfac16_accumulate", _half_descs(jobs), len(jobs),
-               jobs[0].src.device, "kfac_half", events)
+    _side_accumulate(HalfFactorJob, jobs, events)
 
 
 class GroupFactorJob(_ConvJob):
@@ -309,19 +322,14 @@ def _group_descs(jobs: Sequence[GroupFactorJob], check_tensors: bool = True):
 def kfac_group_plan_flops(jobs: Sequence[GroupFactorJob]) -> List[int]:
     """Multiply-add FLOPs (2 per multiply-add) the grouped build executes for each job (curv_kfac_group_plan_flops, host
     only).  `job.src` may be a tensor or just its (N, C, H, W) shape."""
-    if not jobs:
-        return []
-    return _plan_flops("curv_kfac_group_plan_flops", _group_descs(jobs, check_tensors=_all_tensors(jobs)), len(jobs))
+    return _side_plan_flops(GroupFactorJob, jobs)
 
 
 def kfac_accumulate_groups(jobs: Sequence[GroupFactorJob], events=None) -> None:
     """Factor build of grouped convolutions (curv_kfac_group_accumulate): a Gram launch per kernel class and one reduce
     launch per batch of factors, on the current stream.  Scratch from `workspace` (so CURV_DEBUG_POISON covers it).
     `events` = (start, stop) ``torch.cuda.Event``s (enable_timing) are recorded around the whole build."""
-    if not jobs:
-        return
-    _run_build("curv_kfac_group_workspace_bytes", "curv_kfac_group_accumulate", _group_descs(jobs), len(jobs),
-               jobs[0].src.device, "kfac_groups", events)
+    _side_accumulate(GroupFactorJob, jobs, events)
 
 
 class ConvTFactorJob(_ConvJob):
@@ -350,19 +358,14 @@ def _convt_descs(jobs: Sequence[ConvTFactorJob], check_tensors: bool = True):
 def kfac_convt_plan_flops(jobs: Sequence[ConvTFactorJob]) -> List[int]:
     """Multiply-add FLOPs (2 per multiply-add) the transposed-convolution build executes for each job: the sum over the
     phase Grams it runs (curv_kfac_convt_plan_flops, host only).  `job.src` may be a tensor or its (N, C, H, W) shape."""
-    if not jobs:
-        return []
-    return _plan_flops("curv_kfac_convt_plan_flops", _convt_descs(jobs, check_tensors=_all_tensors(jobs)), len(jobs))
+    return _side_plan_flops(ConvTFactorJob, jobs)
 
 
 def kfac_accumulate_convt(jobs: Sequence[ConvTFactorJob], events=None) -> None:
     """A-factor build of transposed convolutions (curv_kfac_convt_accumulate) on the current stream: per factor the window
     copies of its phases, one fp32 MFMA build of the phase Grams and one assembly launch.  Scratch from `workspace` (so
     CURV_DEBUG_POISON covers it).  `events` = (start, stop) ``torch.cuda.Event``s are recorded around the whole build."""
-    if not jobs:
-        return
-    _run_build("curv_kfac_convt_workspace_bytes", "curv_kfac_convt_accumulate", _convt_descs(jobs), len(jobs),
-               jobs[0].src.device, "kfac_convt", events)
+    _side_accumulate(ConvTFactorJob, jobs, events)
 
 
 class DilatedFactorJob(_ConvJob):
@@ -390,9 +393,7 @@ def _dilated_descs(jobs: Sequence[DilatedFactorJob], check_tensors: bool = True)
 def kfac_dilated_plan_flops(jobs: Sequence[DilatedFactorJob]) -> List[int]:
     """Multiply-add FLOPs (2 per multiply-add) the dilated build executes for each job: the sum over the plain builds of
     its class stacks (curv_kfac_dilated_plan_flops, host only).  `job.src` may be a tensor or its (N, C, H, W) shape."""
-    if not jobs:
-        return []
-    return _plan_flops("curv_kfac_dilated_plan_flops", _dilated_descs(jobs, check_tensors=_all_tensors(jobs)), len(jobs))
+    return _side_plan_flops(DilatedFactorJob, jobs)
 
 
 def kfac_accumulate_dilated(jobs: Sequence[DilatedFactorJob], events=None) -> None:
@@ -400,10 +401,7 @@ def kfac_accumulate_dilated(jobs: Sequence[DilatedFactorJob], events=None) -> No
     pass that writes the residue-class sub-images, then one fp32 MFMA build per size group (at most four).  Scratch from
     `workspace` (so CURV_DEBUG_POISON covers it).  `events` = (start, stop) ``torch.cuda.Event``s are recorded around the
     whole build."""
-    if not jobs:
-        return
-    _run_build("curv_kfac_dilated_workspace_bytes", "curv_kfac_dilated_accumulate", _dilated_descs(jobs), len(jobs),
-               jobs[0].src.device, "kfac_dilated", events)
+    _side_accumulate(DilatedFactorJob, jobs, events)
 
 
 class Conv3dFactorJob(_ConvJob):
@@ -449,19 +447,14 @@ def _conv3d_descs(jobs: Sequence[Conv3dFactorJob], check_tensors: bool = True):
 def kfac_conv3d_plan_flops(jobs: Sequence[Conv3dFactorJob]) -> List[int]:
     """Multiply-add FLOPs (2 per multiply-add) the Conv3d build executes for each job: those of the plain build of its
     depth-unfolded stack (curv_kfac_conv3d_plan_flops, host only).  `job.src` may be a tensor or its (N, C, D, H, W) shape."""
-    if not jobs:
-        return []
-    return _plan_flops("curv_kfac_conv3d_plan_flops", _conv3d_descs(jobs, check_tensors=_all_tensors(jobs)), len(jobs))
+    return _side_plan_flops(Conv3dFactorJob, jobs)
 
 
 def kfac_accumulate_conv3d(jobs: Sequence[Conv3dFactorJob], events=None) -> None:
     """A-factor build of 3-D convolutions (curv_kfac_conv3d_accumulate) on the current stream: per factor one gather pass
     that writes the depth-unfolded stack, then one fp32 MFMA build of it.  Scratch from `workspace` (so CURV_DEBUG_POISON
     covers it).  `events` = (start, stop) ``torch.cuda.Event``s are recorded around the whole build."""
-    if not jobs:
-        return
-    _run_build("curv_kfac_conv3d_workspace_bytes", "curv_kfac_conv3d_accumulate", _conv3d_descs(jobs), len(jobs),
-               jobs[0].src.device, "kfac_conv3d", events)
+    _side_accumulate(Conv3dFactorJob, jobs, events)
 
 
 class ReduceFactorJob(_ConvJob):
@@ -512,19 +505,73 @@ def _reduce_descs(jobs: Sequence[ReduceFactorJob], check_tensors: bool = True):
 def kfac_reduce_plan_flops(jobs: Sequence[ReduceFactorJob]) -> List[int]:
     """What the reduce build executes for each job (curv_kfac_reduce_plan_flops, host only): the additions of the reduce
     pass plus the multiply-add FLOPs of the flat build of its (N, dim) rows.  `job.src` may be a tensor or its shape."""
-    if not jobs:
-        return []
-    return _plan_flops("curv_kfac_reduce_plan_flops", _reduce_descs(jobs, check_tensors=_all_tensors(jobs)), len(jobs))
+    return _side_plan_flops(ReduceFactorJob, jobs)
 
 
 def kfac_accumulate_reduce(jobs: Sequence[ReduceFactorJob], events=None) -> None:
     """KFAC-reduce factor build (curv_kfac_reduce_accumulate) on the current stream: per factor one streaming pass that
     writes the per-sample rows, then one fp32 build of their Gram.  Scratch from `workspace` (so CURV_DEBUG_POISON covers
     it).  `events` = (start, stop) ``torch.cuda.Event``s are recorded around the whole build."""
-    if not jobs:
-        return
-    _run_build("curv_kfac_reduce_workspace_bytes", "curv_kfac_reduce_accumulate", _reduce_descs(jobs), len(jobs),
-               jobs[0].src.device, "kfac_reduce", events)
+    _side_accumulate(ReduceFactorJob, jobs, events)
+
+
+class FactorBuild(NamedTuple):
+    """One kind of factor build: the job class, its descriptor filler, the names of the `ops` functions that price and
+    build jobs of that class and, for the side builds, the library's symbol stem and the tag of their scratch."""
+    job: type
+    descs: object
+    plan_flops: str
+    accumulate: str
+    symbol: Optional[str] = None
+    tag: Optional[str] = None
+
+
+# Every kind of factor build, in launch order.  A new kind is a job class, its filler, its two named functions and a row
+# here: KFAC.update, sharding.layer_dims and the job tests read the kinds from this table.
+FACTOR_BUILDS = (
+    FactorBuild(FactorJob, _factor_descs, "kfac_plan_flops", "kfac_accumulate"),
+    FactorBuild(GroupFactorJob, _group_descs, "kfac_group_plan_flops", "kfac_accumulate_groups", "curv_kfac_group",
+                "kfac_groups"),
+    FactorBuild(HalfFactorJob, _half_descs, "kfac_half_plan_flops", "kfac_accumulate_half", "curv_kfac16", "kfac_half"),
+    FactorBuild(ConvTFactorJob, _convt_descs, "kfac_convt_plan_flops", "kfac_accumulate_convt", "curv_kfac_convt",
+                "kfac_convt"),
+    FactorBuild(DilatedFactorJob, _dilated_descs, "kfac_dilated_plan_flops", "kfac_accumulate_dilated",
+                "curv_kfac_dilated", "kfac_dilated"),
+    FactorBuild(ReduceFactorJob, _reduce_descs, "kfac_reduce_plan_flops", "kfac_accumulate_reduce", "curv_kfac_reduce",
+                "kfac_reduce"),
+    FactorBuild(Conv3dFactorJob, _conv3d_descs, "kfac_conv3d_plan_flops", "kfac_accumulate_conv3d", "curv_kfac_conv3d",
+                "kfac_conv3d"),
+)
+_BUILD_OF = {build.job: build for build in FACTOR_BUILDS}
+
+
+def _by_build(jobs) -> list:
+    """[(record, its jobs)] for every kind, in table order, a kind's jobs ([] where it has none) in input order."""
+    batches = {build.job: [] for build in FACTOR_BUILDS}
+    for job in jobs:
+        if type(job) not in batches:
+            raise TypeError(f"not a factor job: {type(job).__name__} (ops.FACTOR_BUILDS lists the job classes)")
+        batches[type(job)].append(job)
+    return [(_BUILD_OF[cls], batch) for cls, batch in batches.items()]
+
+
+def factor_plan_flops(jobs) -> List[int]:
+    """What the library executes for each of `jobs`, a list of factor jobs of any classes, in input order: the jobs of one
+    class are priced together by the class's named function (``ops.kfac_*_plan_flops``, looked up when called)."""
+    flops = {}
+    for build, batch in _by_build(jobs):
+        flops.update(zip(map(id, batch), getattr(sys.modules[__name__], build.plan_flops)(batch)))
+    return [flops[id(job)] for job in jobs]
+
+
+def accumulate_factors(jobs, events=None) -> None:
+    """Build `jobs`, a list of factor jobs of any classes: one call of the named build (``ops.kfac_accumulate*``, looked up
+    when called) per class, in table order, a class's jobs in input order.  A class without jobs is called with an empty
+    list, which launches nothing - as `KFAC.update` always called every build, so what stands in for a build sees every
+    update.  `events` go to the fp32 `FactorJob` build only.  TypeError, before any build is called, for a job of a class
+    the table does not list."""
+    for build, batch in _by_build(jobs):
+        getattr(sys.modules[__name__], build.accumulate)(batch, events=events if build.job is FactorJob else None)
 
 
 # Dilated convolutions (DESIGN.md K16) are opt-in: with the switch off - the default - every selection, refusal and message
@@ -666,6 +713,19 @@ def _factor_source(t, fp32: bool, flatten: bool):
     return t
 
 
+def _job_source(t):
+    """The `src` of a job for the record `t`: the tensor itself, or the shape of a `ShapeOnly`."""
+    return tuple(t.shape) if isinstance(t, ShapeOnly) else t
+
+
+def _conv_out_size(shape, kernel, stride, padding, dilation=None) -> tuple:
+    """The output size of a convolution over an (N, C, *spatial) input of `shape`: what a layer without a recorded
+    gradient takes its positions from."""
+    dilation = dilation or (1,) * len(kernel)
+    return tuple((shape[2 + d] + 2 * padding[d] - dilation[d] * (kernel[d] - 1) - 1) // stride[d] + 1
+                 for d in range(len(kernel)))
+
+
 def _reduce_jobs(layer, x, g) -> LayerJobs:
     """`factor_jobs` for ``approximation="reduce"``: a Linear layer on 2-D records has one position per
     sample, where both forms coincide - today's jobs; a Linear layer on (N, *, in) records gets token-form jobs with N the
@@ -706,16 +766,12 @@ def _reduce_jobs(layer, x, g) -> LayerJobs:
             raise RuntimeError("KFAC.update: Conv2d records must be (N, C, H, W)" if kind == 'Conv2d' else
                                "KFAC.update: Conv1d records must be (N, C, L)")
     kernel, stride, padding = view.kernel, view.stride, view.padding
-    if g is not None:
-        out_size = tuple(g.shape[2:])
-    else:
-        out_size = tuple((x.shape[2 + d] + 2 * padding[d] - kernel[d]) // stride[d] + 1 for d in range(2))
+    out_size = tuple(g.shape[2:]) if g is not None else _conv_out_size(x.shape, kernel, stride, padding)
     a_job = g_job = None
     if x is not None:
-        a_job = ReduceFactorJob(tuple(x.shape) if isinstance(x, ShapeOnly) else x, None, kernel, stride, padding, has_bias,
-                                mean=True, dtype=x.dtype)
+        a_job = ReduceFactorJob(_job_source(x), None, kernel, stride, padding, has_bias, mean=True, dtype=x.dtype)
     if g is not None:
-        g_job = ReduceFactorJob(tuple(g.shape) if isinstance(g, ShapeOnly) else g, None, mean=False, dtype=g.dtype)
+        g_job = ReduceFactorJob(_job_source(g), None, mean=False, dtype=g.dtype)
     return LayerJobs(a_job, g_job, layer.in_channels * kernel[0] * kernel[1] + int(has_bias), layer.out_channels,
                      (x if x is not None else g).shape[0], out_size[0] * out_size[1], 1)
 
@@ -731,14 +787,14 @@ def _conv3d_jobs(layer, x, g, has_bias: bool) -> LayerJobs:
         raise RuntimeError("KFAC.update: Conv3d gradients must be (N, C, D, H, W)")
     a_job = g_job = None
     if x is not None:
-        a_job = Conv3dFactorJob(tuple(x.shape) if isinstance(x, ShapeOnly) else x, None, kernel, stride, padding, has_bias)
+        a_job = Conv3dFactorJob(_job_source(x), None, kernel, stride, padding, has_bias)
     if g is not None:
         L = math.prod(g.shape[2:])
         g = conv_view(layer, None, g).g
-        src = g.shape if isinstance(g, ShapeOnly) else g
+        src = _job_source(g)
         g_job = FactorJob(src, None) if g.dtype == torch.float32 else HalfFactorJob(src, None, dtype=g.dtype)
     else:
-        L = math.prod((x.shape[2 + d] + 2 * padding[d] - kernel[d]) // stride[d] + 1 for d in range(3))
+        L = math.prod(_conv_out_size(x.shape, kernel, stride, padding))
     return LayerJobs(a_job, g_job, layer.in_channels * math.prod(kernel) + int(has_bias), layer.out_channels,
                      (x if x is not None else g).shape[0], L, 1)
 
@@ -799,8 +855,7 @@ def factor_jobs(layer, x, g, out_size=None, approximation="expand") -> LayerJobs
         if g is not None:
             out_size = tuple(g.shape[2:])
         elif not convt:
-            out_size = tuple((x.shape[2 + d] + 2 * padding[d] - dilation[d] * (kernel[d] - 1) - 1) // stride[d] + 1
-                             for d in range(2))
+            out_size = _conv_out_size(x.shape, kernel, stride, padding, dilation)
         elif out_size is None:                           # records that did not pass the estimator's hooks
             out_size = tuple((x.shape[2 + d] - 1) * stride[d] - 2 * padding[d] + kernel[d] +
                              layer.output_padding[d] for d in range(2))
@@ -809,7 +864,7 @@ def factor_jobs(layer, x, g, out_size=None, approximation="expand") -> LayerJobs
         kernel, stride, padding, out_size = (1, 1), (1, 1), (0, 0), (1, 1)
     a_job = g_job = None
     if x is not None:
-        src = x.shape if isinstance(x, ShapeOnly) else x
+        src = _job_source(x)
         if groups > 1:
             a_job = GroupFactorJob(src, None, groups, kernel, stride, padding, has_bias)
         elif convt:
@@ -821,7 +876,7 @@ def factor_jobs(layer, x, g, out_size=None, approximation="expand") -> LayerJobs
         else:
             a_job = HalfFactorJob(src, None, kernel, stride, padding, has_bias, dtype=x.dtype)
     if g is not None:
-        src = g.shape if isinstance(g, ShapeOnly) else g
+        src = _job_source(g)
         if groups > 1:
             g_job = GroupFactorJob(src, None, groups)
         elif g.dtype == torch.float32:

@@ -86,16 +86,8 @@ def layer_dims(layers, shapes, approximation: str = "expand") -> List[tuple]:
     estimator (``KFAC(approximation=...)``); a reduce layer is priced by `ops.kfac_reduce_plan_flops`."""
     from . import ops
     sides = [ops.factor_jobs(layer, *map(ops.ShapeOnly, shapes[layer]), approximation=approximation) for layer in layers]
-    flops = {}
-    for cls, plan_flops in ((ops.FactorJob, ops.kfac_plan_flops), (ops.GroupFactorJob, ops.kfac_group_plan_flops),
-                            (ops.ConvTFactorJob, ops.kfac_convt_plan_flops),
-                            (ops.DilatedFactorJob, ops.kfac_dilated_plan_flops),
-                            (ops.Conv3dFactorJob, ops.kfac_conv3d_plan_flops),
-                            (ops.ReduceFactorJob, ops.kfac_reduce_plan_flops)):
-        batch = [job for s in sides for job in (s.a, s.g) if type(job) is cls]
-        flops.update(zip(map(id, batch), plan_flops(batch)))
-    return [(s.n, s.m, s.K, float(flops[id(s.a)] + flops[id(s.g)])) + ((s.groups,) if s.groups > 1 else ())
-            for s in sides]
+    flops = iter(ops.factor_plan_flops([job for s in sides for job in (s.a, s.g)]))
+    return [(s.n, s.m, s.K, float(next(flops) + next(flops))) + ((s.groups,) if s.groups > 1 else ()) for s in sides]
 
 
 def partition_layers(dims: Sequence[Sequence[int]], world: int, estimator: str = "kfac", rank: int = 100) -> List[int]:

@@ -543,3 +543,83 @@ def test_gemm_small_launch_kernel(gpu):
     ops.gemm_batched(jobs)
     for a, j in zip(first, jobs):
         assert torch.equal(a, j.C)
+
+
+class EveryExpandKind(torch.nn.Module):
+    """One layer of every kind of expand factor build: plain, grouped, transposed, dilated, 3-D (on a depth of 3) and a
+    Linear that autocast feeds bfloat16 records.  (2, 3, 9, 9) -> 9x9 maps, 17x17 after the transposed convolution."""
+
+    def __init__(self):
+        super().__init__()
+        nn = torch.nn
+        self.conv = nn.Conv2d(3, 4, 3, padding=1)
+        self.gconv = nn.Conv2d(4, 8, 3, padding=1, groups=2)
+        self.up = nn.ConvTranspose2d(8, 2, 3, stride=2, padding=1)
+        self.dil = nn.Conv2d(2, 3, 3, padding=2, dilation=2)
+        self.c3 = nn.Conv3d(2, 3, (2, 3, 3), padding=(0, 1, 1))
+        self.fc = nn.Linear(3, 5)
+
+    def forward(self, x):
+        u = self.up(torch.relu(self.gconv(torch.relu(self.conv(x)))))             # (2, 2, 17, 17)
+        v = self.c3(torch.stack([u, torch.relu(u), -u], 2))                       # (2, 2, 3, 17, 17) -> (2, 3, 2, 17, 17)
+        z = self.dil(u).mean((2, 3)) + v.mean((2, 3, 4))
+        with torch.autocast("cuda", dtype=torch.bfloat16):
+            return self.fc(z.bfloat16())
+
+
+class ReduceKinds(torch.nn.Module):
+    """A Conv2d and a Linear on 36 tokens, for approximation="reduce"."""
+
+    def __init__(self):
+        super().__init__()
+        self.conv = torch.nn.Conv2d(3, 4, 3, padding=1)
+        self.fc = torch.nn.Linear(9, 2)
+
+    def forward(self, x):
+        return self.fc(self.conv(x).flatten(1, 2))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("net, types, approximation, kinds", [
+    (EveryExpandKind, ['Linear', 'Conv2d', 'ConvTranspose2d', 'Conv3d'], "expand",
+     {"FactorJob", "GroupFactorJob", "HalfFactorJob", "ConvTFactorJob", "DilatedFactorJob", "Conv3dFactorJob"}),
+    (ReduceKinds, ['Linear', 'Conv2d'], "reduce", {"ReduceFactorJob"})], ids=["expand", "reduce"])
+def test_update_builds_the_bits_of_the_named_builds(gpu, net, types, approximation, kinds):
+    """KFAC.update hands its jobs to ops.accumulate_factors; every factor it leaves has the bits of the layer's named
+    build called directly on the same records with the same scale and `first` - the jobs of a class in one call, as
+    update() launches them (the launch form of the fp32 build depends on the factors of the call).  No tolerance: the
+    dispatcher adds no arithmetic."""
+    from curvature_amd import ops
+    from curvature_amd.curvatures import KFAC
+    named = {ops.FactorJob: ops.kfac_accumulate, ops.GroupFactorJob: ops.kfac_accumulate_groups,
+             ops.HalfFactorJob: ops.kfac_accumulate_half, ops.ConvTFactorJob: ops.kfac_accumulate_convt,
+             ops.DilatedFactorJob: ops.kfac_accumulate_dilated, ops.Conv3dFactorJob: ops.kfac_accumulate_conv3d,
+             ops.ReduceFactorJob: ops.kfac_accumulate_reduce}
+    was = ops.admit_dilated(True), ops.admit_conv_nd(True)
+    try:
+        torch.manual_seed(0)
+        model = net().to(gpu)
+        est = KFAC(model, types, approximation=approximation)
+        model(torch.randn(2, 3, 9, 9, device=gpu)).float().square().mean().backward()
+        layers = est._layers()
+        want = {}
+        for first in (True, False):
+            est.update(2)
+            by_class = {}
+            for layer in layers:
+                sides = ops.factor_jobs(layer, *est.record[layer], est._out_size.get(layer), approximation)
+                L = 1 if approximation == "reduce" else sides.L
+                for side, job, scale in ((0, sides.a, 1.0 / (sides.N * L)), (1, sides.g, float(sides.N) / L)):
+                    if first:
+                        want[layer, side] = torch.full_like(est.state[layer][side], float("nan"))
+                    job.dst, job.scale, job.first = want[layer, side], scale, first
+                    by_class.setdefault(type(job), []).append(job)
+            assert {cls.__name__ for cls in by_class} == kinds
+            for cls, jobs in by_class.items():
+                named[cls](jobs)
+            for (layer, side), factor in want.items():
+                assert torch.isfinite(factor).all()
+                assert torch.equal(est.state[layer][side], factor), (layer, side, first)
+    finally:
+        ops.admit_dilated(was[0])
+        ops.admit_conv_nd(was[1])

@@ -1,6 +1,7 @@
-"""What KFAC.update hands the four factor builds, without a GPU: update() does no device work before it calls
-ops.kfac_accumulate / _groups / _half / _convt, so with those replaced by recorders it runs on CPU tensors.  The expected
-values below are written out by hand from the layer definitions and the update() contract (A: input_weight / (N L),
+"""What KFAC.update hands the factor builds, without a GPU: update() does no device work before ops.accumulate_factors
+calls the named build of every job class (ops.kfac_accumulate, _groups, _half, _convt, _dilated, _reduce, _conv3d - the
+rows of ops.FACTOR_BUILDS), so with every one of those replaced by a recorder it runs on CPU tensors.  The expected values
+below are written out by hand from the layer definitions and the update() contract (A: input_weight / (N L),
 G: N / L / grad_scale^2)."""
 import pytest
 import torch
@@ -9,7 +10,8 @@ import torch.nn as nn
 from curvature_amd import _lib, ops, sharding
 from curvature_amd.curvatures import KFAC
 
-BUILDS = ("kfac_accumulate", "kfac_accumulate_groups", "kfac_accumulate_half", "kfac_accumulate_convt")
+BUILDS = tuple(build.accumulate for build in ops.FACTOR_BUILDS)
+BUILD_OF = {build.job.__name__: build.accumulate for build in ops.FACTOR_BUILDS}
 TYPES = ['Linear', 'Conv2d', 'ConvTranspose2d', 'MultiheadAttention']
 F32, BF16 = torch.float32, torch.bfloat16
 
@@ -36,11 +38,18 @@ class Mixed(nn.Module):
 
 @pytest.fixture
 def calls(monkeypatch):
-    """Recorders in place of the four builds and around ops.kfac_path_for: {name: [argument of each call]}, and the
-    launch forms kfac_path_for answered under "form"."""
-    seen = {name: [] for name in BUILDS + ("kfac_path_for", "form")}
+    """Recorders in place of every build of ops.FACTOR_BUILDS and around ops.kfac_path_for: {name: [argument of each call]},
+    the names of the builds in the order they were called under "order", and the launch forms kfac_path_for answered
+    under "form"."""
+    seen = {name: [] for name in BUILDS + ("kfac_path_for", "form", "order")}
+
+    def recorder(name):
+        def record(jobs, events=None):
+            seen[name].append(list(jobs))
+            seen["order"].append(name)
+        return record
     for name in BUILDS:
-        monkeypatch.setattr(ops, name, lambda jobs, events=None, name=name: seen[name].append(list(jobs)))
+        monkeypatch.setattr(ops, name, recorder(name))
     path_for = ops.kfac_path_for
 
     def recorded_path_for(factors):
@@ -94,8 +103,6 @@ EXPECTED = [
     (("FactorJob", (4, 6), *ONE, True, None, None), (7, 7),
      ("FactorJob", (4, 6), *ONE, False, None, None), (6, 6), 4, 1),
 ]
-BUILD_OF = {"FactorJob": "kfac_accumulate", "GroupFactorJob": "kfac_accumulate_groups",
-            "HalfFactorJob": "kfac_accumulate_half", "ConvTFactorJob": "kfac_accumulate_convt"}
 
 
 def _check(launched, est, layers, sides, a_scale, g_scale, first, half=()):
@@ -226,3 +233,106 @@ def test_shard_path_hint_describes_the_unsharded_fp32_launch(calls, autocast, kw
     assert all(job.path_hint == calls["form"][0] for job in calls["kfac_accumulate"][-1])
     est.update(2, **kwargs)                                             # same records: same form
     assert all(job.path_hint == calls["form"][0] for job in calls["kfac_accumulate"][-1])
+
+
+class Kinds(nn.Module):
+    """The kinds Mixed does not hold: a dilated Conv2d (stride 1, padding = dilation), a Conv1d on one row of its output
+    and a Conv3d on the batch seen as one channel of depth 3.  With a (2, 3, 9, 9) batch every map stays 9 wide."""
+
+    def __init__(self):
+        super().__init__()
+        self.dil = nn.Conv2d(3, 4, 3, padding=2, dilation=2)
+        self.c1 = nn.Conv1d(4, 5, 3, padding=1)
+        self.c3 = nn.Conv3d(1, 3, (2, 3, 3), padding=(0, 1, 1), bias=False)
+
+    def forward(self, x):
+        z = self.c1(self.dil(x)[:, :, 0, :])                          # (2, 4, 9) -> (2, 5, 9)
+        return z.mean() + self.c3(x.unsqueeze(1)).mean()              # (2, 1, 3, 9, 9) -> (2, 3, 2, 9, 9)
+
+
+class Tokens(nn.Module):
+    """A Conv2d and a Linear fed 3-D records, for approximation="reduce": 36 tokens of 9 features from a (2, 3, 9, 9) batch."""
+
+    def __init__(self):
+        super().__init__()
+        self.conv = nn.Conv2d(3, 4, 3, padding=1)
+        self.fc = nn.Linear(9, 2)
+
+    def forward(self, x):
+        return self.fc(self.conv(x).flatten(1, 2))                    # (2, 36, 9) -> (2, 36, 2)
+
+
+# per build, in table order: (job class, layer, side, source shape, factor shape, scale) of every job, in launch order.
+# Kinds: L = 81 (dil), 9 (c1), 2 x 9 x 9 = 162 (c3); A: 1 / (N L), G: N / L.
+KINDS_EXPECTED = [
+    ("kfac_accumulate", [("FactorJob", "dil", 1, (2, 4, 9, 9), (4, 4), 2.0 / 81),
+                         ("FactorJob", "c1", 0, (2, 4, 1, 9), (13, 13), 1.0 / 18),
+                         ("FactorJob", "c1", 1, (2, 5, 1, 9), (5, 5), 2.0 / 9),
+                         ("FactorJob", "c3", 1, (2, 3, 18, 9), (3, 3), 2.0 / 162)]),
+    ("kfac_accumulate_dilated", [("DilatedFactorJob", "dil", 0, (2, 3, 9, 9), (28, 28), 1.0 / 162)]),
+    ("kfac_accumulate_conv3d", [("Conv3dFactorJob", "c3", 0, (2, 1, 3, 9, 9), (18, 18), 1.0 / 324)]),
+]
+# Tokens under "reduce": the positions are reduced first, so L = 1 in both scales: A 1 / N, G N.
+TOKENS_EXPECTED = [
+    ("kfac_accumulate_reduce", [("ReduceFactorJob", "conv", 0, (2, 3, 9, 9), (28, 28), 0.5),
+                                ("ReduceFactorJob", "conv", 1, (2, 4, 9, 9), (4, 4), 2.0),
+                                ("ReduceFactorJob", "fc", 0, (2, 36, 9), (10, 10), 0.5),
+                                ("ReduceFactorJob", "fc", 1, (2, 36, 2), (2, 2), 2.0)]),
+]
+
+
+def _price_by_shape(monkeypatch):
+    """The named plan_flops functions take CPU records: each prices stand-ins that carry the shapes (host only)."""
+    import copy
+    for build in ops.FACTOR_BUILDS:
+        def priced(jobs, real=getattr(ops, build.plan_flops)):
+            stand_ins = [copy.copy(j) for j in jobs]
+            for j in stand_ins:
+                j.src = _shape(j.src)
+            return real(stand_ins)
+        monkeypatch.setattr(ops, build.plan_flops, priced)
+
+
+@pytest.mark.parametrize("net, types, approximation, expected", [
+    (Kinds, ['Conv2d', 'Conv1d', 'Conv3d'], "expand", KINDS_EXPECTED),
+    (Tokens, ['Linear', 'Conv2d'], "reduce", TOKENS_EXPECTED)], ids=["expand", "reduce"])
+def test_every_other_kind_goes_through_the_table(calls, monkeypatch, net, types, approximation, expected):
+    _price_by_shape(monkeypatch)
+    was = ops.admit_dilated(True), ops.admit_conv_nd(True)
+    try:
+        torch.manual_seed(0)
+        model = net()
+        est = KFAC(model, types, approximation=approximation)
+        model(torch.randn(2, 3, 9, 9)).square().mean().backward()
+        est._count_flops = True
+        for first in (True, False):
+            calls["order"].clear()
+            est.update(2)
+            assert calls["order"] == list(BUILDS)                               # table order, one call per class
+            launched = _last(calls)
+            assert [name for name in BUILDS if launched[name]] == [name for name, _ in expected]
+            flops = 0
+            for name, jobs in expected:
+                assert len(launched[name]) == len(jobs)
+                for job, (cls, layer, side, src, dst, scale) in zip(launched[name], jobs):
+                    assert type(job).__name__ == cls and BUILD_OF[cls] == name
+                    assert _shape(job.src) == src and job.src.is_contiguous()
+                    assert job.dst is est.state[getattr(model, layer)][side] and tuple(job.dst.shape) == dst
+                    assert job.scale == scale
+                    assert job.first is first
+                build = [b for b in ops.FACTOR_BUILDS if b.accumulate == name][0]
+                flops += sum(getattr(ops, build.plan_flops)(launched[name]))
+            assert flops > 0 and est._last_flops == flops
+    finally:
+        ops.admit_dilated(was[0])
+        ops.admit_conv_nd(was[1])
+
+
+def test_accumulate_factors_refuses_what_is_not_a_job(calls):
+    job = ops.FactorJob((2, 3), None)
+    with pytest.raises(TypeError, match="object"):
+        ops.accumulate_factors([job, object()])
+    assert calls["order"] == []                                                 # refused before any build is called
+    assert ops.factor_plan_flops([]) == []
+    with pytest.raises(TypeError, match="str"):
+        ops.factor_plan_flops([job, "job"])
