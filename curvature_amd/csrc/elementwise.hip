@@ -16,9 +16,15 @@ static inline dim3 sweep_grid(long long count, int per_thread) {
   return dim3((unsigned)blocks);
 }
 
-// (s*v + n)^(-1/2) with the reference's rounding sequence: mul, add, reciprocal, sqrt (no fma contraction).
+// (s*v + n)^(-1/2) with the reference's rounding sequence: mul, add, reciprocal, sqrt, each correctly rounded on its own
+// (what reciprocal().sqrt() is in IEEE float32; tests/test_small_kernels_gpu.py holds it to bit equality).  Plain
+// operators with contraction switched off: the __fmul_rn / __fadd_rn intrinsics are plain operators too, which an fma may
+// still replace, and __fsqrt_rn is the hardware square root, good to 1 ulp only (one ulp off in a quarter of the
+// elements).  1.0f / x and sqrtf are correctly rounded under hipcc's default -fhip-fp32-correctly-rounded-divide-sqrt.
 __device__ __forceinline__ float rsq_aff(float s, float v, float n) {
-  return __fsqrt_rn(__frcp_rn(__fadd_rn(__fmul_rn(s, v), n)));
+#pragma clang fp contract(off)
+  const float x = s * v + n;
+  return sqrtf(1.0f / x);
 }
 
 // out[i] = (s * v[i] + n)^(-1/2)
@@ -113,10 +119,9 @@ sqrt_scale_kernel(const float* __restrict__ v, float s, float* __restrict__ out,
     out[j] = sqrtf(s * v[j]);
 }
 
-// out[i] = a[i] * b[i]
+// out[i] = a[i] * b[i]; out may be a or b, and a may be b (the samplers multiply in place): no __restrict__ here
 __global__ void __launch_bounds__(256)
-mul_kernel(const float* __restrict__ a, const float* __restrict__ b, float* __restrict__ out,
-           long long count) {
+mul_kernel(const float* a, const float* b, float* out, long long count) {
   const long long stride = (long long)gridDim.x * blockDim.x;
   for (long long j = (long long)blockIdx.x * blockDim.x + threadIdx.x; j < count; j += stride)
     out[j] = a[j] * b[j];

@@ -137,10 +137,11 @@ square_f64_kernel(const float* __restrict__ v, double* __restrict__ out, long lo
   }
 }
 
-// M[i][j] = (M[i][j] or src[i][j]) * dl[i] * dr[j]; src may be fp64 (P_c = diag(sigma) L_c diag(sigma))
+// M[i][j] = (M[i][j] or src[i][j]) * dl[i] * dr[j]; src may be fp64 (P_c = diag(sigma) L_c diag(sigma)).
+// dst may be src (the in-place form), so neither carries __restrict__.
 template <typename T>
 __global__ void __launch_bounds__(256)
-diag_scale_kernel(const T* __restrict__ src, float* __restrict__ dst, const float* __restrict__ dl,
+diag_scale_kernel(const T* src, float* dst, const float* __restrict__ dl,
                   const float* __restrict__ dr, int rows, int cols) {
   const long long total = (long long)rows * cols;
   const long long stride = (long long)gridDim.x * blockDim.x;
@@ -163,10 +164,12 @@ vtv_assemble_kernel(const T* __restrict__ V4, const float* __restrict__ sigma, i
   for (long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += stride) {
     const int x = (int)(e / ab), y = (int)(e - (long long)x * ab);
     const int i = x / b, j = x - i * b, k = y / b, l = y - k * b;
+    // sigma[x] sigma[y] is common to both terms: element (y, x) adds the same two entries of V4 in the other order, so
+    // the result is exactly symmetric (as w1 + w2 with w = sxy * V4[..] it was not once the compiler formed an fma)
     const T sxy = (T)sigma[x] * (T)sigma[y];
-    const T w1 = sxy * V4[(long long)(i * a + k) * ld4 + (j * b + l)];
-    const T w2 = sxy * V4[(long long)(k * a + i) * ld4 + (l * b + j)];
-    vtv[e] = (w1 + w2) * (T)0.5;
+    const T v1 = V4[(long long)(i * a + k) * ld4 + (j * b + l)];
+    const T v2 = V4[(long long)(k * a + i) * ld4 + (l * b + j)];
+    vtv[e] = sxy * ((v1 + v2) * (T)0.5);
   }
 }
 

@@ -1944,7 +1944,7 @@ def sq_accumulate(grad_w: torch.Tensor, grad_b: Optional[torch.Tensor], batch_si
     given (preallocated, uninitialised) state instead of adding to it; default: only when it is allocated here."""
     _require_gpu(grad_w, grad_b, state)
     rows = grad_w.shape[0]
-    cols_w = grad_w.numel() // rows
+    cols_w = math.prod(grad_w.shape[1:])
     if first is None:
         first = state is None
     if state is None:
@@ -1971,7 +1971,7 @@ def sq_accumulate_many(items, batch_size: float) -> List[torch.Tensor]:
         if not grad_w.is_contiguous() or (grad_b is not None and not grad_b.is_contiguous()):
             raise RuntimeError("sq_accumulate_many: gradients must be contiguous")
         rows = grad_w.shape[0]
-        cols_w = grad_w.numel() // rows
+        cols_w = math.prod(grad_w.shape[1:])           # not numel() // rows: a rows = 0 item is legal and skipped
         if first is None:
             first = state is None
         if state is None:
@@ -2374,6 +2374,10 @@ def inf_vtv_assemble(V4: torch.Tensor, sigma: torch.Tensor, a: int, b: int) -> t
     _require_gpu(sigma)
     if not V4.is_cuda or not V4.is_contiguous() or V4.dtype not in (torch.float32, torch.float64):
         raise RuntimeError("inf_vtv_assemble: bad V4")
+    if a <= 0 or b <= 0 or tuple(V4.shape) != (a * a, b * b):
+        raise RuntimeError(f"inf_vtv_assemble: V4 is {tuple(V4.shape)}, a = {a}, b = {b} need ({a * a}, {b * b})")
+    if sigma.numel() != a * b:
+        raise RuntimeError(f"inf_vtv_assemble: sigma has {sigma.numel()} elements, a * b = {a * b}")
     out = torch.empty(a * b, a * b, dtype=V4.dtype, device=V4.device)
     fn = _lib.lib().curv_inf_vtv_assemble_f64 if V4.dtype == torch.float64 else _lib.lib().curv_inf_vtv_assemble
     _lib.check(fn(_lib.stream_ptr(), V4.data_ptr(), sigma.data_ptr(), a, b, out.data_ptr()), "curv_inf_vtv_assemble")
@@ -2386,6 +2390,9 @@ def diag_scale(src: torch.Tensor, dl: torch.Tensor, dr: torch.Tensor, out: Optio
     if not src.is_cuda or not src.is_contiguous() or src.dtype not in (torch.float32, torch.float64):
         raise RuntimeError("diag_scale: bad source")
     _require_gpu(dl, dr)
+    if src.dim() != 2 or dl.numel() != src.shape[0] or dr.numel() != src.shape[1]:
+        raise RuntimeError(f"diag_scale: source {tuple(src.shape)} needs dl, dr of {src.shape[0]}, {src.shape[1]} "
+                           f"elements, got {dl.numel()}, {dr.numel()}")
     if out is None or out.shape != src.shape or out.dtype != torch.float32 or out.device != src.device \
             or not out.is_contiguous():
         out = torch.empty(src.shape, dtype=torch.float32, device=src.device)

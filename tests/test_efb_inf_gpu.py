@@ -142,7 +142,21 @@ def test_inf_select_exact_and_ties(gpu):
     lam = torch.zeros(12 * 8)
     lam[[5, 17, 40]] = torch.tensor([3.0, -2.0, 1.0])
     I, J = ops.inf_select(lam.to(gpu), 12, 8, 5)          # ties at |0|: exactly 5 elements selected, any 2 zeros
-    assert set([0, 2, 5]).issubset(set(I.tolist())) and len(I) <= 5 and len(J) <= 5
+    # the 93 zeros lie in every row and column, the winners' included: which two are taken shows in the lists only as a
+    # length between 3 (both beside a winner) and 5
+    assert set([0, 2, 5]).issubset(set(I.tolist())) and 3 <= len(I) <= 5
+    assert set([0, 1, 5]).issubset(set(J.tolist())) and 3 <= len(J) <= 5
+    # ties that do show: four values of 0.5 on rows and columns no winner uses, over strictly smaller distinct values;
+    # rank 5 takes the three winners and exactly two of them, so both lists are exactly 5 long
+    lam = 0.01 * torch.arange(1, 12 * 8 + 1, dtype=torch.float32) / (12 * 8)
+    lam[[5, 17, 40]] = torch.tensor([3.0, -2.0, 1.0])
+    tied = [7 * 8 + 2, 8 * 8 + 3, 9 * 8 + 4, 10 * 8 + 6]
+    lam[tied] = torch.tensor([0.5, -0.5, -0.5, 0.5])
+    I, J = ops.inf_select(lam.to(gpu), 12, 8, 5)
+    assert len(I) == 5 and len(J) == 5
+    column_of = {t // 8: t % 8 for t in tied}
+    extra_rows, extra_cols = set(I.tolist()) - {0, 2, 5}, set(J.tolist()) - {0, 1, 5}
+    assert extra_rows <= set(column_of) and {column_of[i] for i in extra_rows} == extra_cols
 
 
 def test_inf_invert_per_layer_hyperparameters_match_the_one_pair_path(gpu):
