@@ -204,6 +204,14 @@ class curv_persample_quad_desc(ctypes.Structure):
                 ("first", ctypes.c_int32), ("alpha", ctypes.c_float)]
 
 
+class curv_persample_project_desc(ctypes.Structure):
+    """Mirror of ``curv_persample_project_desc`` in include/curv_hip.h."""
+    _fields_ = [(k, ctypes.c_void_p) for k in ("A", "B", "W", "U", "Z")] + \
+               [(k, ctypes.c_longlong) for k in ("a_ns", "a_rs", "b_ns", "b_rs", "w_rs", "u_rs", "z_ns", "z_rs", "z_cs")] + \
+               [(k, ctypes.c_int32) for k in ("S", "M", "Nc", "L", "R", "first")] + \
+               [("alpha", ctypes.c_float), ("reserved", ctypes.c_int32)]
+
+
 class curv_persample_grid_desc(ctypes.Structure):
     """Mirror of ``curv_persample_grid_desc`` in include/curv_hip.h (`shift` and `gain` are host arrays of H floats)."""
     _fields_ = [(k, ctypes.c_void_p) for k in ("A", "B", "u", "v", "V", "out")] + \
@@ -373,6 +381,9 @@ SIGNATURES = {
     "curv_persample_quad_workspace_bytes": (_sz, [ctypes.POINTER(curv_persample_quad_desc), _i]),
     "curv_persample_quad_plan_flops": (_i, [ctypes.POINTER(curv_persample_quad_desc), _i, ctypes.POINTER(ctypes.c_longlong)]),
     "curv_persample_quad_reduce": (_i, [_vp, ctypes.POINTER(curv_persample_quad_desc), _i, _vp, _sz]),
+    "curv_persample_project_workspace_bytes": (_sz, [ctypes.POINTER(curv_persample_project_desc), _i]),
+    "curv_persample_project_plan_flops": (_i, [ctypes.POINTER(curv_persample_project_desc), _i, ctypes.POINTER(ctypes.c_longlong)]),
+    "curv_persample_project": (_i, [_vp, ctypes.POINTER(curv_persample_project_desc), _i, _vp, _sz]),
     "curv_persample_quad_grid_workspace_bytes": (_sz, [ctypes.POINTER(curv_persample_grid_desc), _i]),
     "curv_persample_quad_grid_plan_flops": (_i, [ctypes.POINTER(curv_persample_grid_desc), _i, ctypes.POINTER(ctypes.c_longlong)]),
     "curv_persample_quad_grid_reduce": (_i, [_vp, ctypes.POINTER(curv_persample_grid_desc), _i, _vp, _sz]),

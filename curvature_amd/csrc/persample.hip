@@ -41,6 +41,13 @@
 // - the joint covariance of the network outputs (curvatures.py: functional_covariance).  A kernel of its own
 // (ps_cov_tile) on the same engine and walk: tiles of 8 rows i x 128 columns j of all outputs, so that a lane holds every output
 // of its entries and the Gram is lane-local; the B rows of a stage are staged once for all outputs.
+//
+// The fourth (curv_persample_project): the weighted product projected from the left, per sample,
+//   Z[n][j][l] (+)= alpha * sum_i W[i][j] * P_n[i][j] * U[i][l],   l < R
+// - what INF's low-rank term needs of a layer's Jacobian (curvatures.py: INF): the posterior weighs the
+// entries in the parameter basis BEFORE the rotation into the Kronecker eigenbasis, so no rotation of the operands can
+// stand in for it.  One more mode of ps_product_tile: at a sample's end the accumulators, times W, are the A operand of
+// a second MFMA straight from the registers; neither P_n nor W o P_n is written.
 #include "nt_stage.h"
 #include "side_build.h"
 #include "wave_sum.h"
@@ -130,8 +137,23 @@ struct PsCov : PsOperands {
 
 typedef ArgBatch<PsCov, PS_BATCH> PsCovBatch;
 
+// A product of curv_persample_project: the weights W (M x Nc, as PsQuad's; never swapped), U (M x R, row stride u_rs), the
+// destination Z (entry (n, j, l) at Z[n z_ns + j z_rs + l z_cs]) and the fp32 `partial`[sample][part][Nc][R]: part = the
+// 64-row half of a row tile (half tiles: the one part there is), 2 tm + wave row.
+struct PsProject : PsOperands {
+  const float* W;
+  const float* U;
+  float* Z;
+  float* partial;
+  long long w_is, w_js, u_rs, z_ns, z_rs, z_cs;
+  int R, parts;
+};
+
+typedef ArgBatch<PsProject, PS_BATCH> PsProjectBatch;
+
 struct Plan {
   int tiles_m, tiles_n, tiles, sps, spi, slices, half, swap;
+  int parts;                                   // curv_persample_project: partial blocks per sample
   long long a_bytes, b_bytes;
   size_t slab_bytes;
   long long flops;
@@ -286,6 +308,54 @@ bool cov_plan_of(const curv_persample_cov_desc& d, int index, Plan* p) {
   return true;
 }
 
+// (`slab_bytes`: the partials, one Nc x R block per sample and 64-row part.)  This product never changes its operands'
+// places: W and U belong to the rows of A.  M <= 64 takes the half tile, anything else the full one, whatever Nc is.
+bool project_plan_of(const curv_persample_project_desc& d, int index, Plan* p) {
+  const char* const who = "curv_persample_project";
+  if (d.R < 1) {
+    set_error("%s: item %d: R %d below 1", who, index, d.R);
+    return false;
+  }
+  if (!tiling_of(d, who, index, p)) return false;
+  if (((d.a_ns | d.a_rs | d.b_ns | d.b_rs) & 3) != 0) {
+    set_error("%s: item %d: operand strides must be multiples of 4 floats (a_ns %lld a_rs %lld b_ns %lld b_rs %lld)", who,
+              index, d.a_ns, d.a_rs, d.b_ns, d.b_rs);
+    return false;
+  }
+  if (d.w_rs < d.Nc || d.u_rs < d.R || d.z_cs < 1 || d.z_rs < 1 || d.z_ns < 1) {
+    set_error("%s: item %d: invalid strides (w_rs %lld below Nc %d, u_rs %lld below R %d, or z_ns %lld z_rs %lld z_cs %lld "
+              "below 1)", who, index, d.w_rs, d.Nc, d.u_rs, d.R, d.z_ns, d.z_rs, d.z_cs);
+    return false;
+  }
+  // U and a partial block are addressed by 32-bit byte offsets that reach a tile's worth behind their last row
+  if (d.M > 1 && ((long long)d.M + PS_TM) * d.u_rs * 4 >= PS_BYTES_MAX) {
+    set_error("%s: item %d: U too large for 32-bit offsets ((M %d + %d) rows of u_rs %lld floats)", who, index, d.M, PS_TM,
+              d.u_rs);
+    return false;
+  }
+  if (((long long)d.Nc + PS_TM) * d.R * 4 >= PS_BYTES_MAX) {
+    set_error("%s: item %d: Nc x R block too large for 32-bit offsets (Nc %d R %d)", who, index, d.Nc, d.R);
+    return false;
+  }
+  p->half = d.M <= PS_TM / 2;
+  p->swap = 0;
+  p->tiles_m = p->half ? 1 : cdiv(d.M, PS_TM);
+  p->tiles_n = cdiv(d.Nc, PS_TM);
+  const long long tiles = (long long)p->tiles_m * p->tiles_n;
+  if (tiles > (1 << 24)) {
+    set_error("%s: item %d: too many output tiles (%lld)", who, index, tiles);
+    return false;
+  }
+  p->tiles = (int)tiles;
+  split_samples(p, d.S, d.L);
+  p->parts = p->half ? 1 : 2 * p->tiles_m;
+  const int tile_rows = p->half ? PS_TM / 2 : PS_TM;
+  // the products, and at every sample's end the second MFMA: tile_rows x 128 entries against ceil(R / 32) chunks of U
+  p->flops = 2LL * p->tiles * tile_rows * PS_TM * (long long)d.S * ((long long)p->sps * nt::KC + 32LL * cdiv(d.R, 32));
+  p->slab_bytes = align_up((size_t)d.S * p->parts * d.Nc * d.R * sizeof(float), 256);
+  return true;
+}
+
 // Product: one workgroup per item = (tile * slices + slice) of one product.  Full tiles (128 x 128): wave (wm, wn) computes
 // rows 64 wm .. + 64 of the A panel against rows 64 wn .. + 64 of the B panel, 2 x 2 MFMA blocks.  Half tiles (64 x 128, a
 // product whose A side has at most 64 rows): every wave takes all 64 A rows against B rows 32 wave .. + 32, 2 x 1 blocks -
@@ -308,7 +378,15 @@ bool cov_plan_of(const curv_persample_cov_desc& d, int index, Plan* p) {
 // time) divides, sums - 34 divisions per h in the separable form, 64 in the dense one - and reduces over the wave by DPP
 // (wave_sum.h); lane 63 leaves red[sample parity][wave][h], thread h adds the four behind the next barrier and writes
 // partial[tile][sample][h].  Grid point h sees shift[h] only: its bits do not depend on the other grid points.
-enum { PS_SQ = 0, PS_QUAD_W = 1, PS_QUAD_ONES = 2, PS_GRID_SEP = 3, PS_GRID_DENSE = 4 };
+// PS_PROJECT (d a PsProject): Z_n = (W o P_n)^T U.  The second register set holds W as in PS_QUAD_W.  At the sample's end
+// the lane multiplies its accumulators by W in place; what it then holds is, register by register, the A operand of
+// another v_mfma_f32_32x32x2_f32: lane (r32, h) has column r32 and row 4 h + roff(m, reg) of the block, and the MFMA
+// wants A[i = lane & 31][k = lane >> 5] - so with i = the column and the two k of step (m, reg) = the rows 4 h + roff(m,
+// reg), h = 0, 1, the 32 steps of a wave sum its 64 rows, the B operand of a step being U[row][32 lb + r32], read from
+// memory (zero, and not read, for rows at or beyond M and columns at or beyond R).  R is walked in chunks lb of 32
+// columns (a loop that is not unrolled): 16 BN registers of z per lane.  The result block (column j = 4 h + roff(reg),
+// l = 32 lb + r32) goes straight to the wave's partial block; no LDS, no barrier, no hand-over.
+enum { PS_SQ = 0, PS_QUAD_W = 1, PS_QUAD_ONES = 2, PS_GRID_SEP = 3, PS_GRID_DENSE = 4, PS_PROJECT = 5 };
 
 // An item of a product launch: its output tile and its range of samples.
 struct PsItem {
@@ -397,7 +475,7 @@ __device__ __forceinline__ void ps_product_tile(const Product& d, int local, lds
   bool col_in[BN];                                           // ... and col_in[nb]
 #pragma unroll
   for (int nb = 0; nb < BN; ++nb) col_in[nb] = j0 + row_b + 32 * nb + r32 < N;
-  if constexpr (MODE == PS_QUAD_W) {
+  if constexpr (MODE == PS_QUAD_W || MODE == PS_PROJECT) {
 #pragma unroll
     for (int m = 0; m < 2; ++m)
 #pragma unroll
@@ -455,6 +533,56 @@ __device__ __forceinline__ void ps_product_tile(const Product& d, int local, lds
           slab[r * PS_TM + col] = q[m][nb][reg];
         }
       }
+  } else if constexpr (MODE == PS_PROJECT) {
+    const int R = d.R, chunks = (R + 31) >> 5;
+    const int part = HALF ? 0 : 2 * it.tm + (wave >> 1);
+    // U and the partial block through buffer descriptors, the whole offset in the voffset (the range check does not see
+    // an soffset): rows at or beyond M (of U) and columns at or beyond Nc (of the block) fall behind the descriptor's
+    // extent - the load gives 0, the store is dropped - and a lane whose l is at or beyond R carries an out-of-range
+    // voffset, which the row offsets cannot bring back into range (project_plan_of bounds them)
+    constexpr int OOB = (int)0x80000000;
+    const unsigned u_bytes = (unsigned)(((long long)(M - 1) * d.u_rs + R) * 4), z_bytes = (unsigned)((long long)N * R * 4);
+    const __amdgpu_buffer_rsrc_t rsu = __builtin_amdgcn_make_buffer_rsrc((void*)d.U, 0, u_bytes, 0x00020000);
+    const int u_row = (int)d.u_rs * 4, z_row = R * 4;
+    const int u_lane = ((i0 + row_a + 4 * h) * (int)d.u_rs + r32) * 4, z_lane = ((j0 + row_b + 4 * h) * R + r32) * 4;
+    // the sample boundary: W o P_n in place, then its 64 rows against U, 32 columns of U at a time
+    auto sample_end = [&](int n) {
+#pragma unroll
+      for (int m = 0; m < 2; ++m)
+#pragma unroll
+        for (int nb = 0; nb < BN; ++nb) c[m][nb] = c[m][nb] * q[m][nb];
+      float* block = d.partial + ((long long)n * d.parts + part) * ((long long)N * R);
+      const __amdgpu_buffer_rsrc_t rsz = __builtin_amdgcn_make_buffer_rsrc((void*)block, 0, z_bytes, 0x00020000);
+#pragma unroll 1
+      for (int lb = 0; lb < chunks; ++lb) {
+        const bool l_in = 32 * lb + r32 < R;
+        const int u_at = l_in ? u_lane + 128 * lb : OOB, z_at = l_in ? z_lane + 128 * lb : OOB;
+        f32x16 z[BN];
+#pragma unroll
+        for (int nb = 0; nb < BN; ++nb) z[nb] = 0.0f;
+#pragma unroll
+        for (int m = 0; m < 2; ++m)
+#pragma unroll
+          for (int reg = 0; reg < 16; ++reg) {
+            const float u = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rsu, u_at + roff(m, reg) * u_row, 0, 0));
+#pragma unroll
+            for (int nb = 0; nb < BN; ++nb) z[nb] = __builtin_amdgcn_mfma_f32_32x32x2f32(c[m][nb][reg], u, z[nb], 0, 0, 0);
+          }
+#pragma unroll
+        for (int nb = 0; nb < BN; ++nb)
+#pragma unroll
+          for (int reg = 0; reg < 16; ++reg) {
+            const float v = z[nb][reg];          // (a bit cast of the vector element itself stores element 0 sixteen times)
+            __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), rsz,
+                                                  z_at + (32 * nb + roff(0, reg)) * z_row, 0, 0);
+          }
+      }
+#pragma unroll
+      for (int m = 0; m < 2; ++m)
+#pragma unroll
+        for (int nb = 0; nb < BN; ++nb) c[m][nb] = 0.0f;
+    };
+    ps_walk_samples(d, it.slice, dma, addr_a, addr_b, c, h, sample_end, [](int) {});
   } else if constexpr (MODE == PS_GRID_SEP || MODE == PS_GRID_DENSE) {
     const int H = d.H;
     auto flush = [&](int n) {
@@ -609,6 +737,33 @@ __global__ void __launch_bounds__(PS_THREADS) ps_grid_reduce_kernel(const PsGrid
   for (int t = 0; t < d.tiles; ++t) v += p[t * step];
   v *= d.gain[g];
   float* out = d.out + g * d.o_hs + s * d.o_stride;
+  *out = d.first ? v : *out + v;
+}
+
+// The same items for curv_persample_project: partial[sample][part][Nc][R] instead of a slab.
+__global__ void __launch_bounds__(PS_THREADS, 2) ps_project_product_kernel(const PsProjectBatch batch) {
+  __shared__ __attribute__((aligned(1024))) char smem[nt::LDS_B];
+  const PsProject& d = batch.e[owner_of(batch, (long long)blockIdx.x)];
+  const int local = (int)(blockIdx.x - d.base);
+  if (d.half) ps_product_tile<true, PS_PROJECT>(d, local, (lds_char_t*)smem, nullptr);
+  else ps_product_tile<false, PS_PROJECT>(d, local, (lds_char_t*)smem, nullptr);
+}
+
+// Reduce: one thread per entry (n, j, l) of Z sums the parts of its sample in part order (row tiles, the two wave rows
+// of each), scales, writes or adds.  Blocks of a product: ceil(S Nc R / 256).
+__global__ void __launch_bounds__(PS_THREADS) ps_project_reduce_kernel(const PsProjectBatch batch) {
+  const PsProject& d = batch.e[owner_of(batch, (long long)blockIdx.x)];
+  const long long idx = (blockIdx.x - d.base) * PS_THREADS + threadIdx.x;
+  const long long block = (long long)d.Nc * d.R;
+  if (idx >= d.S * block) return;
+  const long long s = idx / block, rem = idx - s * block;
+  const int j = (int)(rem / d.R), l = (int)(rem - (long long)j * d.R);
+  const float* p = d.partial + s * d.parts * block + rem;
+  float v = 0.f;
+#pragma unroll 4
+  for (int t = 0; t < d.parts; ++t) v += p[t * block];
+  v *= d.alpha;
+  float* out = d.Z + s * d.z_ns + j * d.z_rs + l * d.z_cs;
   *out = d.first ? v : *out + v;
 }
 
@@ -785,7 +940,7 @@ struct PsPack {
 
 typedef ArgBatch<PsPack, PS_BATCH> PsPackBatch;
 static_assert(sizeof(PsBatch) <= 3840 && sizeof(PsQuadBatch) <= 3840 && sizeof(PsPackBatch) <= 3840 &&
-                  sizeof(PsCovBatch) <= 3840 && sizeof(PsGridBatch) <= 3840,
+                  sizeof(PsCovBatch) <= 3840 && sizeof(PsGridBatch) <= 3840 && sizeof(PsProjectBatch) <= 3840,
               "kernel argument block must stay below 4 KB");
 
 int pack_elem_bytes(int dtype) {
@@ -1070,6 +1225,16 @@ PsCov cov_of(const curv_persample_cov_desc& d, const Plan& p, float* partial) {
   return P;
 }
 
+// The same for curv_persample_project (no swap: project_plan_of).
+PsProject project_of(const curv_persample_project_desc& d, const Plan& p, float* partial) {
+  PsProject P = operands_of<PsProject>(d, p);
+  P.W = d.W; P.U = d.U; P.Z = d.Z; P.partial = partial;
+  P.w_is = d.w_rs; P.w_js = 1; P.u_rs = d.M > 1 ? d.u_rs : d.R;      // (the stride of a single row says nothing)
+  P.z_ns = d.z_ns; P.z_rs = d.z_rs; P.z_cs = d.z_cs;
+  P.R = d.R; P.parts = p.parts;
+  return P;
+}
+
 // The same for curv_persample_quad_grid_reduce: the grid's tables by value; u and v (the rows and columns of the product)
 // and the strides of V change places with the operands.
 PsGrid grid_of(const curv_persample_grid_desc& d, const Plan& p, float* partial) {
@@ -1214,6 +1379,28 @@ extern "C" int curv_persample_cov_reduce(void* stream_, const curv_persample_cov
       },
       cov_of, [](const curv_persample_cov_desc& d) { return cdivll((long long)d.S * (d.K * (d.K + 1) / 2), PS_THREADS); },
       ps_cov_product_kernel, ps_cov_reduce_kernel);
+}
+
+extern "C" size_t curv_persample_project_workspace_bytes(const curv_persample_project_desc* descs, int n) {
+  return side::workspace_bytes("curv_persample_project_workspace_bytes", descs, n, project_plan_of, bytes_of);
+}
+
+extern "C" int curv_persample_project_plan_flops(const curv_persample_project_desc* descs, int n, long long* out) {
+  return side::plan_flops("curv_persample_project_plan_flops", descs, n, out, project_plan_of);
+}
+
+extern "C" int curv_persample_project(void* stream_, const curv_persample_project_desc* descs, int n, void* workspace,
+                                      size_t workspace_bytes) {
+  return run_products(
+      "curv_persample_project", stream_, descs, n, workspace, workspace_bytes, project_plan_of,
+      [](const char* name, const curv_persample_project_desc& d, int i) -> int {
+        CURV_REQUIRE(d.A && d.B && d.W && d.U && d.Z, "%s: item %d: null operand", name, i);
+        CURV_REQUIRE(((reinterpret_cast<uintptr_t>(d.A) | reinterpret_cast<uintptr_t>(d.B)) & 15) == 0,
+                     "%s: item %d: A and B must be 16-byte aligned", name, i);
+        return CURV_OK;
+      },
+      project_of, [](const curv_persample_project_desc& d) { return cdivll((long long)d.S * d.Nc * d.R, PS_THREADS); },
+      ps_project_product_kernel, ps_project_reduce_kernel);
 }
 
 // The fp32-contiguous spelling of curv_persample_pack_ex: (N, C, H, W), or (N, H, W, C) with channels_last.

@@ -749,7 +749,11 @@ class Curvature(ABC):
         ``groups > 1`` (float32 records): one product per group on channel slices of the records, or the direct kernel of
         csrc/persample_dw.hip for a depthwise layer, which keeps no X side - its recorded input is read again
         (`ops.per_sample_route`).  Other selected layers raise NotImplementedError, as does a layer-sharded estimator.
-        Implemented by KFAC, Diagonal and EFB.  No counterpart in the reference, which has the Monte-Carlo predictive only."""
+        Implemented by KFAC, Diagonal and EFB, and by INF with `ops.admit_inf_predictive` (see `INF`).  No counterpart in the
+        reference, which has the Monte-Carlo predictive only."""
+        opted = self._opt_in_predictive()
+        if opted is not None:
+            return opted.functional_variance(out, first=first, inputs=inputs)
         raise NotImplementedError(f"{type(self).__name__}.functional_variance: no linearised predictive for this estimator "
                                   "(KFAC, Diagonal and EFB have one)")
 
@@ -773,6 +777,9 @@ class Curvature(ABC):
         estimator as for `functional_variance` - except that a grouped Conv2d needs `ops.admit_grouped_joint` beside
         `ops.admit_grouped_per_sample` (KFAC, Diagonal): its group slices then are layers with their group's spectra, and a
         depthwise layer takes `ops.per_sample_dw_quad_grid_reduce` on its records.  Implemented by KFAC, Diagonal and EFB."""
+        opted = self._opt_in_predictive()
+        if opted is not None:
+            return opted.functional_variance_grid(out, hypers, first=first, inputs=inputs)
         raise NotImplementedError(f"{type(self).__name__}.functional_variance_grid: no linearised predictive for this "
                                   "estimator (KFAC, Diagonal and EFB have one)")
 
@@ -790,6 +797,9 @@ class Curvature(ABC):
         (those that read the record in place share one copy of it per slot); a depthwise layer has no g side to stage:
         its transformed products ``s w (T^T p)`` (`ops.per_sample_dw_project`) go into slot `slot` of a (count, N, C n_g)
         stack kept beside the others, and nothing of its X is kept."""
+        opted = self._opt_in_predictive()
+        if opted is not None:
+            return opted.stage_output(slot, count, inputs=inputs)
         raise NotImplementedError(f"{type(self).__name__}.stage_output: no linearised predictive for this estimator "
                                   "(KFAC, Diagonal and EFB have one)")
 
@@ -804,8 +814,17 @@ class Curvature(ABC):
         `ops.per_sample_gram_reduce`).  RuntimeError if a slot has not been staged since
         the last ``stage_output(inputs=True)`` or the recorded inputs are no longer those tensors.  At most
         `ops.PERSAMPLE_COV_MAX_OUTPUTS` outputs.  Implemented by KFAC, Diagonal and EFB."""
+        opted = self._opt_in_predictive()
+        if opted is not None:
+            return opted.functional_covariance(out, first=first)
         raise NotImplementedError(f"{type(self).__name__}.functional_covariance: no linearised predictive for this "
                                   "estimator (KFAC, Diagonal and EFB have one)")
+
+    def _opt_in_predictive(self):
+        """The object that answers the four methods above for an estimator whose linearised predictive is behind a switch
+        of `ops` (INF), or None: they then refuse.  Called on the class's method only - an estimator without any attribute
+        still gets the refusal."""
+        return None
 
     def drop_predictive_state(self) -> None:
         """Forget what the four methods above kept of the last forward pass for their next call (the X sides, the stack of
@@ -1943,7 +1962,22 @@ class INF(Curvature):
 
     Keyword-only extensions of the reference constructor: `shard` (only this rank's layers are decomposed,
     reduced, inverted and sampled; dicts coming from sharded estimators already hold just those) and `eigvecs`
-    (reuse e.g. ``efb.eigvecs`` instead of decomposing the same factors again, curvatures.py:403 vs :473)."""
+    (reuse e.g. ``efb.eigvecs`` instead of decomposing the same factors again, curvatures.py:403 vs :473).
+
+    The linearised predictive (`functional_variance`, `stage_output`, `functional_covariance`; opt-in:
+    `ops.admit_inf_predictive`) is that of the regularised precision `invert` stands for,
+
+        Pi = V diag(s lambda) V^T + diag(s corr + add),   V = kron(U_A, U_G),   r = (s corr + add)^(-1/2),
+
+    whose inverse is, by Woodbury with sigma = sqrt(s lambda), S = diag(sigma), vtv = V_s^T V_s as `vtv` forms it and
+    B = chol(vtv + I),  Pi^-1 = diag(r^2) - diag(r^2) V S (I + vtv)^-1 S V^T diag(r^2).  A layer's share of the variance of
+    an output with per-sample Jacobian P (n x m, index i m + j) is
+
+        sum_ij r2_ij P_ij^2 - ||F q||^2,   q = vec(U_A^T (R2 o P) U_G) in the order k b + l,   F = B^-1 S.
+
+    This is NOT the covariance of `sampler`: the pre-sampler P_c it shares with the reference uses B^-1 B^-T where
+    (B B^T)^-1 = B^-T B^-1 is needed, so the samples' covariance M M^T differs from Pi^-1 (4e-3 against entries of 1.4 on a
+    random layer with n, m, a, b = 5, 4, 3, 2; tests/test_inf_predictive.py records it).  The sampler is left as it is."""
 
     _mha_as_projections = True
 
@@ -2054,41 +2088,87 @@ class INF(Curvature):
         self._r_version = getattr(self, "_r_version", 0) + 1            # (the sampler's cached r**2 is stale)
         prev = [self.inv_state[l][3] if l in self.inv_state else None for l in layers]
         pre_samples = self.pre_sampler_many(regs, outs=prev)
-        for layer, (ua, ug, _, r), pre_sample in zip(layers, regs, pre_samples):
+        self._sigma = dict()                                             # sqrt(s lambda) per layer: the predictive's F = B^-1 S
+        for layer, (ua, ug, sigma, r), pre_sample in zip(layers, regs, pre_samples):
             self.inv_state[layer] = (ua, ug, r, pre_sample)
+            self._sigma[layer] = sigma
+
+    # ------------------------------------------------------------------ linearised (GLM) predictive (opt-in)
+    def _opt_in_predictive(self):
+        """`Curvature._opt_in_predictive`: with `ops.admit_inf_predictive` on, the four methods of the linearised predictive
+        run `LinearisedPredictive` on this estimator (`_INFPredictive`); off - the default - they are `Curvature`'s refusals,
+        reached before any attribute of the estimator is touched.  Per layer ``sum r2 P**2`` by
+        `ops.per_sample_quad_reduce` minus ``||F q||**2`` with q from `ops.per_sample_project` (the class docstring);
+        `stage_output` also writes the output's vectors ``F q_n`` into slot `slot` of a (count, N, a b) stack per layer, and
+        `functional_covariance` is `ops.per_sample_cov_reduce` with W = r**2 minus the Gram of those stacks.  Layers,
+        records and ``inputs=False`` as for EFB.  `functional_variance_grid` stays refused: a damping pair changes r and with
+        it V_s^T V_s, so every pair needs a factorisation of its own."""
+        return _INFPredictive(self) if ops.inf_predictive_admitted() else None
+
+    def _lowrank_terms(self) -> dict:
+        """``{layer: (U_A, U_G, F^T)}`` for the current inversion, F = B^-1 S with B = chol(vtv + I) and its columns in the
+        order l a + k (the order in which the projected products come out of their GEMM; `LinearisedPredictive._lowrank`).
+        Built at the first predictive call after an inversion (all layers together through the stages: `_vtv_many`, one
+        float64 factorisation sweep, one float64 product that scales and rounds to float32), kept with the predictive's
+        other state: `drop_predictive_state` drops it."""
+        state = self.__dict__.setdefault("_predictive_kept", {})
+        kept = state.get("lowrank")
+        if kept is not None and kept["version"] == self._r_version:
+            return kept["terms"]
+        layers = list(self.inv_state)
+        regs = [(self.inv_state[l][0], self.inv_state[l][1], self._sigma[l], self.inv_state[l][2]) for l in layers]
+        terms, infos = dict(), []
+        for group in self._scratch_groups(regs):
+            vtvs = self._vtv_many([regs[k] for k in group])
+            invB = ops.chol_factor_inverse(vtvs, [1.0] * len(vtvs), check=False)
+            infos.append(ops.chol_factor_inverse.last_info)
+            jobs = []
+            for k, inv in zip(group, invB):
+                ua, ug, sigma, _ = regs[k]
+                a, b = ua.shape[1], ug.shape[1]
+                # column l a + k of the result is column k b + l of B^-1 S: a permutation as the B operand, sigma in
+                # the permuted order as the column scale
+                order = torch.arange(a * b, device=ua.device).view(a, b).t().reshape(-1)
+                perm = torch.zeros(a * b, a * b, dtype=torch.float64, device=ua.device)
+                perm[order, torch.arange(a * b, device=ua.device)] = 1.0
+                F = torch.empty(a * b, a * b, dtype=torch.float32, device=ua.device)
+                jobs.append(ops.Gemm64(inv, perm, tri=ops.TRI64_A_LOWER, out32=F,
+                                       col_scale=ops.gather2d(sigma.view(a, b).t()).view(-1)))
+                terms[layers[k]] = (ua, ug, F.t())
+            ops.gemm_f64_batched(jobs)
+        ops.check_factor_inverse_info(torch.cat(infos))
+        state["lowrank"] = dict(version=self._r_version, terms=terms)
+        return terms
+
+    def _predictive_terms(self) -> PredictiveTerms:
+        def weights(layer):                                  # r (index i m + j) as the (m, n) matrix of the products' entries
+            ua, ug, r, _ = self.inv_state[layer]
+            return ops.gather2d(r.view(ua.shape[0], ug.shape[0]).t())
+        return PredictiveTerms("INF", basis=None, weights=weights, grid_basis=None, spectrum=None, separable=False,
+                               grid_missing="not supported", lowrank=lambda layer: self._lowrank_terms()[layer])
 
     RHS_SWEEP_ABOVE = 16        # layers per call from which T is built by the sweep's right-hand side mode (pre_sampler_many)
 
     @staticmethod
-    def pre_sampler_many(regs, outs: Optional[Sequence[Optional[Tensor]]] = None) -> List[Tensor]:
-        """`pre_sampler` for a list of (U_A_lr, U_G_lr, sigma, r) tuples, stage by stage.  `outs`: previous
-        P_c tensors, overwritten in place where the shape still fits."""
-        if not regs:
-            return []
-        # bound the float64 scratch of a batch (PA, M, V4, vtv, the two inverses, T, L_c per layer): layers are
-        # processed in groups of at most ~24 GB, far below the 288 GB of the device
+    def _scratch_groups(regs) -> List[List[int]]:
+        """The positions of `regs` in groups whose float64 scratch (PA, M, V4, vtv, the two inverses, T, L_c per layer)
+        stays below ~24 GB, far below the 288 GB of the device."""
         def scratch(reg):
             (n, a), (m, b) = reg[0].shape, reg[1].shape
             return 8.0 * (n * a * a / 2 + m * b * b / 2 + n * m + a * a * m / 2 + 6.0 * (a * b) ** 2)
-        if len(regs) > 1:
-            groups, cur, size = [], [], 0.0
-            for k, reg in enumerate(regs):
-                if cur and size + scratch(reg) > 24e9:
-                    groups.append(cur)
-                    cur, size = [], 0.0
-                cur.append(k)
-                size += scratch(reg)
-            groups.append(cur)
-            if len(groups) > 1:
-                res: List[Optional[Tensor]] = [None] * len(regs)
-                for g in groups:
-                    part = INF.pre_sampler_many([regs[k] for k in g], [outs[k] for k in g] if outs is not None else None)
-                    for k, t in zip(g, part):
-                        res[k] = t
-                return res
-        # V_s^T V_s in closed form, fp64 end to end: with strongly varying r (e.g. invert(1, 1000) on a ResNet) it is a
-        # badly conditioned weighted Gram matrix, and an fp32 evaluation caps P_c - and the samples - at ~1e-3
-        # (measured on ResNet-50's stem: 1.7e-3; with fp64: at the level of the fp32 inputs)
+        groups, cur, size = [], [], 0.0
+        for k, reg in enumerate(regs):
+            if cur and size + scratch(reg) > 24e9:
+                groups.append(cur)
+                cur, size = [], 0.0
+            cur.append(k)
+            size += scratch(reg)
+        groups.append(cur)
+        return groups
+
+    @staticmethod
+    def _vtv_many(regs) -> List[Tensor]:
+        """`vtv` for a list of (U_A_lr, U_G_lr, sigma, r) tuples, stage by stage, float64."""
         first, parts = [], []
         # r**2 in fp64: one launch for the model when the r of its layers lie back to back (invert()'s arena)
         # (bare tensors here, no arena to ask: the tensor-level check `_Arena.is_whole` is built on)
@@ -2106,8 +2186,28 @@ class INF(Curvature):
             parts.append((PG, sigma, a, b))
         Ms = ops.gemm_f64_batched(first)
         V4s = ops.gemm_f64_batched([ops.Gemm64(M, PG) for M, (PG, _, _, _) in zip(Ms, parts)])
-        vtvs = [ops.inf_vtv_assemble_sym(V4.contiguous(), sigma, a, b) for V4, (_, sigma, a, b) in zip(V4s, parts)]
-        del first, Ms, V4s, parts
+        return [ops.inf_vtv_assemble_sym(V4.contiguous(), sigma, a, b) for V4, (_, sigma, a, b) in zip(V4s, parts)]
+
+    @staticmethod
+    def pre_sampler_many(regs, outs: Optional[Sequence[Optional[Tensor]]] = None) -> List[Tensor]:
+        """`pre_sampler` for a list of (U_A_lr, U_G_lr, sigma, r) tuples, stage by stage.  `outs`: previous
+        P_c tensors, overwritten in place where the shape still fits."""
+        if not regs:
+            return []
+        # bound the float64 scratch of a batch: layers are processed in groups (`_scratch_groups`)
+        if len(regs) > 1:
+            groups = INF._scratch_groups(regs)
+            if len(groups) > 1:
+                res: List[Optional[Tensor]] = [None] * len(regs)
+                for g in groups:
+                    part = INF.pre_sampler_many([regs[k] for k in g], [outs[k] for k in g] if outs is not None else None)
+                    for k, t in zip(g, part):
+                        res[k] = t
+                return res
+        # V_s^T V_s in closed form, fp64 end to end: with strongly varying r (e.g. invert(1, 1000) on a ResNet) it is a
+        # badly conditioned weighted Gram matrix, and an fp32 evaluation caps P_c - and the samples - at ~1e-3
+        # (measured on ResNet-50's stem: 1.7e-3; with fp64: at the level of the fp32 inputs)
+        vtvs = INF._vtv_many(regs)
         # float64, lower triangular: A^-1 = chol(vtv)^-1, then T = (I - B^-1) A^-1 = A^-1 - chol(vtv + I)^-1 A^-1 by forward
         # substitution INSIDE the second sweep (`rhs`): no explicit B^-1, no product with it (a sixth of the call's flops).
         # The status words are read at the END of this function: a read-back here would leave the GPU idle while the
@@ -2260,3 +2360,23 @@ class INF(Curvature):
         ops.gemm_batched([ops.Gemm(frst_eigvecs, t2.t(), out, alpha=-1.0, epilogue=ops.EPI_MUL_E_ADD_F, E=r2,
                                    F=Y_l.view(n, m))])
         return out
+
+
+class _INFPredictive(LinearisedPredictive):
+    """`LinearisedPredictive` on an `INF` it does not derive from: INF's four methods stay `Curvature`'s own (refusals with
+    `ops.admit_inf_predictive` off), which hand over to an object of this class with the switch on
+    (`INF._opt_in_predictive`).  Everything the mixin asks of its estimator - state, records, hooks, `_predictive_terms`,
+    the kept state - is the INF's: nothing lives here but the reference."""
+
+    def __init__(self, inf: INF):
+        object.__setattr__(self, "_inf", inf)
+
+    def __getattr__(self, name):                   # (only what the mixin itself does not define)
+        return getattr(object.__getattribute__(self, "_inf"), name)
+
+    def _kept(self) -> dict:
+        return self._inf.__dict__.setdefault("_predictive_kept", {})
+
+    def functional_variance_grid(self, out: Tensor, hypers, *, first: bool = True, inputs: bool = True) -> Tensor:
+        raise NotImplementedError("INF.functional_variance_grid: a damping pair changes r and V_s^T V_s, so every pair needs "
+                                  "its own factorisation; call invert(add, multiply) and functional_variance per pair")

@@ -217,7 +217,8 @@ def glm_predictive(model: torch.nn.Module, estimator, images: torch.Tensor, outp
     """The linearised-Laplace (GLM) predictive of one batch: ``(logits, variance, probs)``, each (N, classes).
 
     ``variance[n, c]`` is the closed-form variance of output c for input n under the posterior `estimator` samples from,
-    with the network linearised in its weights at their mean (`Curvature.functional_variance`: KFAC, Diagonal, EFB);
+    with the network linearised in its weights at their mean (`Curvature.functional_variance`: KFAC, Diagonal, EFB; INF
+    with `ops.admit_inf_predictive`, for the posterior its regularised precision stands for - see `INF`);
     ``probs = softmax(logits / sqrt(1 + pi / 8 * variance))`` is the probit approximation of the expected softmax.  No
     weights are sampled: one forward pass, then for every output c in `outputs` (default: all; the variance of the
     others stays 0) one backward pass of ``logits[:, c].sum()`` and one `functional_variance` call - the side of it that
@@ -225,7 +226,7 @@ def glm_predictive(model: torch.nn.Module, estimator, images: torch.Tensor, outp
 
     The model is put into ``eval()`` mode, which makes the samples of the batch independent under BatchNorm: the
     gradient of ``sum_n f_c(x_n)`` then splits into the per-sample Jacobians the variance is made of.  A Diagonal / EFB
-    built without ``per_sample=True`` gets the recording hooks for the length of the call.  The parameters and their
+    built without ``per_sample=True``, or an INF, gets the recording hooks for the length of the call.  The parameters and their
     ``.grad`` are left as they were found (the backward passes are `torch.autograd.grad` calls on the parameters that
     require grad; a selected layer they do not reach raises RuntimeError).  GPU only (RuntimeError for a CPU model: no fallback).
     `glm_predictive_joint` gives the covariance between the outputs as well."""
@@ -317,7 +318,7 @@ def glm_predictive_joint(model: torch.nn.Module, estimator, images: torch.Tensor
     otherwise (raised after the forward pass, when the class count is known) - pass ``outputs=``, for instance the top-k
     classes.  Model mode, hooks, parameters and ``.grad`` as in `glm_predictive`.  A grouped Conv2d needs
     `ops.admit_grouped_joint` beside `ops.admit_grouped_per_sample` (KFAC, Diagonal; `glm_predictive_mc` and
-    ``eval_glm(predictive="mc")`` go through the same passes).  GPU only."""
+    ``eval_glm(predictive="mc")`` go through the same passes).  INF takes part with `ops.admit_inf_predictive`.  GPU only."""
     logits, covariance, classes = _joint_covariance("glm_predictive_joint", model, estimator, images, outputs)
     variance = torch.zeros(logits.shape, dtype=torch.float32, device=logits.device)
     variance[:, classes] = torch.diagonal(covariance, dim1=1, dim2=2)
@@ -374,7 +375,8 @@ def glm_predictive_mc(model: torch.nn.Module, estimator, images: torch.Tensor, o
     ``KFAC.sample(layer, z)``; otherwise the draws come from the estimator's own noise stream (`noise_seed` pins them,
     `noise_offset` advances by ``N * samples * ceil(K / 4)``, so successive calls are independent).  A covariance that is
     singular is fine (`Curvature.functional_covariance` gives one whenever there are more outputs than the Jacobians'
-    rank); one that is not positive semi-definite raises RuntimeError naming the input.  GPU only."""
+    rank); one that is not positive semi-definite raises RuntimeError naming the input.  Estimators as for
+    `glm_predictive_joint` (INF with `ops.admit_inf_predictive`).  GPU only."""
     samples = int(samples)
     if samples < 1:
         raise ValueError(f"glm_predictive_mc: samples must be at least 1, got {samples}")
@@ -395,8 +397,9 @@ def eval_glm(model: torch.nn.Module, dataset: Iterable, estimator, predictive: s
              samples: int = 256, device=None):
     """The GLM predictive over `dataset`: ``(predictions, labels)`` as numpy arrays, the counterpart of `eval_bnn` without
     weight samples.  ``predictive="probit"`` goes through `glm_predictive`, ``"mc"`` through `glm_predictive_mc` with
-    `samples` draws per input from the estimator's noise stream; `outputs` as there.  The probabilities stay on the device
-    and cross to the host once at the end."""
+    `samples` draws per input from the estimator's noise stream; `outputs` as there.  Every estimator with a linearised
+    predictive (KFAC, Diagonal, EFB; INF with `ops.admit_inf_predictive`).  The probabilities stay on the device and cross
+    to the host once at the end."""
     if predictive not in ("probit", "mc"):
         raise ValueError(f"eval_glm: predictive must be 'probit' or 'mc', got {predictive!r}")
     if device is None:

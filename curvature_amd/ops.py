@@ -1391,6 +1391,93 @@ def per_sample_quad_reduce(jobs: Sequence[PerSampleQuadJob]) -> None:
                len(jobs), jobs[0].out.device, "persample")
 
 
+class PerSampleProjectJob(_PerSampleProduct):
+    """Z[n, j, l] (+)= alpha * sum_i W[i, j] * (A_n B_n^T)[i, j] * U[i, l] for `S` samples (`per_sample_project`): A, B and
+    their sizes and strides as in `PerSampleQuadJob`; `W` an (M, Nc) view with unit column stride (required); `U` an
+    (M, R) view with unit column stride, any R; `Z` an (S, Nc, R) float32 view of any positive, non-overlapping strides
+    (a permuted buffer is fine).  `first`: overwrite Z.  A / B / W / U / Z may also be `None` with explicit sizes (plan
+    queries: `R` then says how many columns U has)."""
+    __slots__ = ("W", "U", "Z", "R")
+
+    def __init__(self, A, B, W, U, Z, S, M, Nc, L, a_ns, a_rs, b_ns, b_rs, alpha=1.0, first=False, R=None):
+        self.W, self.U, self.Z = W, U, Z
+        self.R = int(U.shape[1]) if U is not None and U.dim() == 2 else int(R or 0)
+        self._set_operands(A, B, S, M, Nc, L, a_ns, a_rs, b_ns, b_rs, alpha, first)
+
+
+def _per_sample_project_descs(jobs: Sequence[PerSampleProjectJob], check_tensors: bool = True):
+    name = "per_sample_project"
+    arr = (_lib.curv_persample_project_desc * len(jobs))()
+    for d, j in zip(arr, jobs):
+        _fill_per_sample(d, j, name, (j.W, j.U, j.Z) if check_tensors else None)
+        d.R = j.R
+        d.w_rs, d.u_rs, d.z_ns, d.z_rs, d.z_cs = j.Nc, max(j.R, 1), j.Nc * max(j.R, 1), max(j.R, 1), 1
+        if check_tensors:
+            if j.W.dim() != 2 or tuple(j.W.shape) != (j.M, j.Nc) or (j.Nc > 1 and j.W.stride(1) != 1):
+                raise RuntimeError(f"{name}: weights must be an ({j.M},{j.Nc}) view with unit column stride, got "
+                                   f"{tuple(j.W.shape)}")
+            if j.U.dim() != 2 or j.U.shape[0] != j.M or j.U.shape[1] < 1 or (j.R > 1 and j.U.stride(1) != 1) or \
+                    (j.M > 1 and j.U.stride(0) < j.R):
+                raise RuntimeError(f"{name}: U must be an ({j.M}, R) view with unit column stride and rows that do not "
+                                   f"overlap, got {tuple(j.U.shape)} with strides {tuple(j.U.stride())}")
+            if j.Z.dim() != 3 or tuple(j.Z.shape) != (j.S, j.Nc, j.R):
+                raise RuntimeError(f"{name}: destination must be an ({j.S},{j.Nc},{j.R}) view, got {tuple(j.Z.shape)}")
+            # (the stride of a dimension of size 1 says nothing: take 1)
+            zs = [max(int(st), 1) if size == 1 else int(st) for st, size in zip(j.Z.stride(), j.Z.shape)]
+            order = sorted(range(3), key=lambda k: zs[k])
+            live = [k for k in order if j.Z.shape[k] > 1]
+            if any(zs[k] < 1 for k in range(3)) or \
+                    any(zs[hi] < zs[lo] * j.Z.shape[lo] for lo, hi in zip(live, live[1:])):
+                raise RuntimeError(f"{name}: destination strides {tuple(j.Z.stride())} are not positive or overlap")
+            d.W, d.w_rs = j.W.data_ptr(), max(j.W.stride(0), j.Nc)
+            d.U, d.u_rs = j.U.data_ptr(), max(j.U.stride(0), j.R)
+            d.Z, (d.z_ns, d.z_rs, d.z_cs) = j.Z.data_ptr(), zs
+    return arr
+
+
+def per_sample_project_plan_flops(jobs: Sequence[PerSampleProjectJob]) -> List[int]:
+    """Multiply-add FLOPs (2 per multiply-add) the plan executes per job (curv_persample_project_plan_flops, host only):
+    those of the products plus those of the second MFMA at every sample's end."""
+    if not jobs:
+        return []
+    return _plan_flops("curv_persample_project_plan_flops", _per_sample_project_descs(jobs, check_tensors=False), len(jobs))
+
+
+def per_sample_project_workspace_bytes(jobs: Sequence[PerSampleProjectJob]) -> int:
+    """Bytes of scratch `per_sample_project` takes for these jobs (curv_persample_project_workspace_bytes, host only)."""
+    if not jobs:
+        return 0
+    return int(_lib.lib().curv_persample_project_workspace_bytes(_per_sample_project_descs(jobs, check_tensors=False),
+                                                                 len(jobs)))
+
+
+def per_sample_project(jobs: Sequence[PerSampleProjectJob]) -> None:
+    """curv_persample_project over any number of products, on the current stream; partials from `workspace`."""
+    if not jobs:
+        return
+    _run_build("curv_persample_project_workspace_bytes", "curv_persample_project", _per_sample_project_descs(jobs),
+               len(jobs), jobs[0].Z.device, "persample")
+
+
+# The linearised predictive of INF (DESIGN.md K19) is opt-in: with the switch off - the default - INF refuses the four
+# methods exactly as it did, with the same messages.
+_INF_PREDICTIVE = False
+
+
+def admit_inf_predictive(enable: bool = True) -> bool:
+    """Switch INF's linearised (GLM) predictive on or off for the process; returns what it was.  On: `INF` answers
+    `functional_variance`, `stage_output` and `functional_covariance` (and with them the `evaluate.glm_predictive*`
+    drivers) by `per_sample_project`; `functional_variance_grid` stays refused.  Off: the four raise NotImplementedError
+    where they did."""
+    global _INF_PREDICTIVE
+    was, _INF_PREDICTIVE = _INF_PREDICTIVE, bool(enable)
+    return was
+
+
+def inf_predictive_admitted() -> bool:
+    return _INF_PREDICTIVE
+
+
 PERSAMPLE_GRID_MAX = _lib.PERSAMPLE_GRID_MAX
 
 

@@ -1,10 +1,12 @@
-"""The linearised (GLM) predictive of KFAC, Diagonal and EFB: `functional_variance`, `functional_variance_grid`,
+"""The linearised (GLM) predictive of KFAC, Diagonal, EFB and INF: `functional_variance`, `functional_variance_grid`,
 `stage_output` and `functional_covariance` once, for every estimator that describes itself by a `PredictiveTerms`.
 
 `Curvature` documents the four methods (and refuses them for the estimators that have no linearised predictive);
-`LinearisedPredictive` goes in front of it in the bases of the three that do.  What a call keeps for the next
+`LinearisedPredictive` goes in front of it in the bases of KFAC, Diagonal and EFB; INF, whose predictive is behind a switch,
+hands over to a `LinearisedPredictive` that holds it by reference (`curvatures._INFPredictive`).  What a call keeps for the next
 ``inputs=False`` call lives in one dict on the estimator, ``_predictive_kept``, with at most the entries ``"variance"``,
-``"grid"`` and ``"covariance"``: each reduction replaces its own entry only, `Curvature.drop_predictive_state` drops them all.
+``"grid"``, ``"covariance"`` and (INF) ``"lowrank"``: each reduction replaces its own entry only,
+`Curvature.drop_predictive_state` drops them all.
 """
 import math
 from typing import Callable, List, NamedTuple, Optional
@@ -32,6 +34,8 @@ class PredictiveTerms(NamedTuple):
                                                # (w not yet squared; each may be None)
     direct_grid: Optional[Callable] = None     # ``direct_grid(layer)`` = (T, u, v, V) of a depthwise layer for
                                                # `ops.PerSampleDwGridJob`: separable (u, v) or dense (V) grid weights
+    lowrank: Optional[Callable] = None         # ``lowrank(layer)`` = (U_A, U_G, F^T): the posterior is diag(w**2) minus a
+                                               # low-rank part in the Kronecker eigenbasis (INF; `_lowrank`)
 
 
 def _module_of(layer):
@@ -112,10 +116,30 @@ class LinearisedPredictive:
         ones = torch.ones(1, rows.shape[0], dtype=torch.float32, device=rows.device)
         ops.gemm_batched([ops.Gemm(ones, rows.view(rows.shape[0], -1), out, beta=0.0 if first else 1.0)])
 
+    @staticmethod
+    def _lowrank(operands, gs, xs, ws, low, outs: List[Tensor]) -> None:
+        """The low-rank vectors of every layer into `outs` (each (N, a b)): ``outs[k][n] = F vec(U_A^T (W o P_n)^T U_G)``
+        with P_n = g_n X_n^T the (m, n) product, W = `ws` (m, n) and (U_A, U_G, F^T) = `low`.  The weights enter entry by
+        entry BEFORE the rotation, which no rotation of the operands can express: `ops.per_sample_project` gives
+        Z_n = (W o P_n)^T U_G without writing P_n, stored as (N, b, n) so that ONE product per layer, (N b, n) x U_A, rotates
+        all samples; its rows are the vectors q_n in the order l a + k, which the columns of F^T follow."""
+        project, rotate, scale = [], [], []
+        for (s, _, _), g, x, w, (ua, ug, ft), y in zip(operands, gs, xs, ws, low, outs):
+            a, b = ua.shape[1], ug.shape[1]
+            zt = torch.empty(s.N, b, s.n, dtype=torch.float32, device=y.device)
+            qt = torch.empty(s.N * b, a, dtype=torch.float32, device=y.device)
+            project.append(ops.PerSampleProjectJob.of(s, g, x, w, ug, zt.permute(0, 2, 1), first=True))
+            rotate.append(ops.Gemm(zt.view(s.N * b, s.n), ua, qt))
+            scale.append(ops.Gemm(qt.view(s.N, b * a), ft, y))
+        ops.per_sample_project(project)
+        ops.gemm_batched(rotate)
+        ops.gemm_batched(scale)
+
     # ------------------------------------------------------------------ the variance of one output
     def functional_variance(self, out: Tensor, *, first: bool = True, inputs: bool = True) -> Tensor:
         """`Curvature.functional_variance`."""
         what, basis, weights, *_ = self._predictive_terms()
+        lowrank = self._predictive_terms().lowrank
 
         def check(N):
             if out.dim() != 1 or out.shape[0] != N or out.dtype != torch.float32 or not out.is_cuda:
@@ -128,7 +152,8 @@ class LinearisedPredictive:
             # a depthwise layer has no packed X to keep: its recorded input is read again; (T, w**2, s) is what it keeps
             terms = [self._predictive_terms().direct(l) for l, _, _ in direct]
             terms = [(T, None if w is None else ops.mul(w, w), s) for T, w, s in terms]
-            self._kept()["variance"] = dict(key=key, xs=xs, ws=ws, direct=terms)
+            self._kept()["variance"] = dict(key=key, xs=xs, ws=ws, direct=terms,
+                                            low=None if lowrank is None else [lowrank(l) for l in layers])
         kept = self._kept_entry(what, "functional_variance", "variance", key)
         gs = self._g_side(layers, operands, basis)
         rows = torch.empty(len(layers) + len(direct), out.shape[0], dtype=torch.float32, device=out.device)
@@ -136,6 +161,12 @@ class LinearisedPredictive:
                                     for k, ((s, _, _), g, x, w) in enumerate(zip(operands, gs, kept["xs"], kept["ws"]))])
         ops.per_sample_dw_quad_reduce([ops.PerSampleDwJob.of(l, x, g, out=rows[len(layers) + k], T=T, W=w, s=s, first=True)
                                        for k, ((l, x, g), (T, w, s)) in enumerate(zip(direct, kept["direct"]))])
+        if kept["low"] is not None:
+            # minus the squared norm of every layer's low-rank vector, into the layer's row
+            ys = [torch.empty(out.shape[0], ft.shape[1], dtype=torch.float32, device=out.device) for _, _, ft in kept["low"]]
+            self._lowrank(operands, gs, kept["xs"], kept["ws"], kept["low"], ys)
+            ops.per_sample_gram_reduce([ops.PerSampleGramJob(y.unsqueeze(0), rows[k].view(-1, 1, 1), alpha=-1.0)
+                                        for k, y in enumerate(ys)])
         self._sum_layers(rows, out.unsqueeze(0), first)
         return out
 
@@ -205,6 +236,7 @@ class LinearisedPredictive:
     def stage_output(self, slot: int, count: int, *, inputs: bool = False) -> None:
         """`Curvature.stage_output`."""
         what, basis, weights, *_ = self._predictive_terms()
+        lowrank = self._predictive_terms().lowrank
         slot, count = int(slot), int(count)
         if not 1 <= count <= ops.PERSAMPLE_COV_MAX_OUTPUTS or not 0 <= slot < count:
             raise ValueError(f"{what}.stage_output: slot {slot} of {count} (at most {ops.PERSAMPLE_COV_MAX_OUTPUTS} outputs)")
@@ -236,6 +268,7 @@ class LinearisedPredictive:
             self._kept()["covariance"] = dict(key=key, count=count, xs=xs, ws=ws, sizes=sizes, stack=stack, place=place,
                                               whole=whole, sides=[s for s, _, _ in operands], staged=set(),
                                               direct=terms, projected=projected, N=N, device=dev,
+                                              low=None if lowrank is None else [lowrank(l) for l in layers],
                                               inputs=[self.record[_module_of(l)][0] for l in layers] +
                                                      [x for _, x, _ in direct])
         kept = self._kept_entry(what, "stage_output", "covariance", key, count)
@@ -250,6 +283,13 @@ class LinearisedPredictive:
             ops.CopyPlan(slots, sources).run()
         ops.per_sample_dw_project([ops.PerSampleDwProjectJob.of(l, x, g, y=y[slot], T=T, W=w, s=s)
                                    for (l, x, g), (T, w, s), y in zip(direct, kept["direct"], kept["projected"])])
+        if kept["low"] is not None:
+            # the output's low-rank vectors into slot `slot` of a (count, N, a b) stack per layer
+            if "lowstack" not in kept:
+                kept["lowstack"] = [torch.empty(count, kept["N"], ft.shape[1], dtype=torch.float32, device=kept["device"])
+                                    for _, _, ft in kept["low"]]
+            self._lowrank(operands, [g for _, g, _ in operands], kept["xs"], kept["ws"], kept["low"],
+                          [stack[slot] for stack in kept["lowstack"]])
         kept["staged"].add(slot)
 
     def functional_covariance(self, out: Tensor, *, first: bool = True) -> Tensor:
@@ -279,5 +319,7 @@ class LinearisedPredictive:
                                    for k, (s, (b, at), x, w) in enumerate(zip(sides, kept["place"], kept["xs"], kept["ws"]))])
         ops.per_sample_gram_reduce([ops.PerSampleGramJob(y, rows[len(sides) + k], first=True)
                                     for k, y in enumerate(kept["projected"])])
+        if kept["low"] is not None:
+            ops.per_sample_gram_reduce([ops.PerSampleGramJob(y, rows[k], alpha=-1.0) for k, y in enumerate(kept["lowstack"])])
         self._sum_layers(rows, out.view(1, -1), first)
         return out

@@ -910,6 +910,42 @@ int curv_persample_quad_reduce(void* stream, const curv_persample_quad_desc* des
                                size_t workspace_bytes);
 
 /* ------------------------------------------------------------------------------------------------
+ * The weighted per-sample product projected from the left (csrc/persample.hip; DESIGN.md "K19"), per sample:
+ *     Z[s*z_ns + j*z_rs + l*z_cs] (+)= alpha * sum_{i < M} W[i*w_rs + j] * P_s[i][j] * U[i*u_rs + l],    j < Nc, l < R
+ * with P_s = A_s B_s^T as above.  INF's posterior weighs the entries of the Jacobian in the parameter basis (W = r**2)
+ * before it rotates them into the Kronecker eigenbasis (U = U_G; the other rotation, by U_A, is a plain product on Z), so
+ * no rotation of the operands can stand in for this reduction.  At a sample's end the MFMA accumulators, times W, are
+ * the A operand of a second v_mfma_f32_32x32x2_f32 straight from the registers: neither P_s nor W o P_s is written.
+ * A, B, S, M, Nc, L, the operand strides and W (required here) follow the rules of curv_persample_quad_desc; U is M x R
+ * with row stride u_rs >= R, any R >= 1, read only inside its M x R entries; Z is addressed through three positive
+ * strides and nothing beside its S x Nc x R entries is touched.  A and B never change places in this plan: M <= 64 takes
+ * 64 x 128 tiles, any other M 128 x 128 ones.  fp32 MFMA, fp32 sums in a fixed order (the 64 rows of a wave by the MFMA,
+ * then a sample's row tiles and the two wave rows of each in order), no atomics; an item's plan follows from its own
+ * sizes only, so its bits do not depend on the other items of the call.  Enqueues on `stream` only.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct curv_persample_project_desc {
+  const float* A;
+  const float* B;
+  const float* W;
+  const float* U;
+  float* Z;
+  long long a_ns, a_rs, b_ns, b_rs, w_rs, u_rs, z_ns, z_rs, z_cs;
+  int32_t S, M, Nc, L, R;
+  int32_t first;
+  float alpha;
+  int32_t reserved;        /* 0 */
+} curv_persample_project_desc;
+/* Device scratch for these items (bytes: one Nc x R block per sample and 64-row part of M); 0 with the error text set
+ * for invalid sizes.  Host only. */
+size_t curv_persample_project_workspace_bytes(const curv_persample_project_desc* descs, int n);
+/* Host only: the multiply-add FLOPs the plan executes per item, those of the products plus those of the second MFMA
+ * (at least 2 S M Nc (L + R)). */
+int curv_persample_project_plan_flops(const curv_persample_project_desc* descs, int n, long long* out);
+/* An MFMA and a reduce launch per batch of up to 16 items.  The workspace must be 256-byte aligned. */
+int curv_persample_project(void* stream, const curv_persample_project_desc* descs, int n, void* workspace,
+                           size_t workspace_bytes);
+
+/* ------------------------------------------------------------------------------------------------
  * The same reduction for a whole grid of damping pairs (add, multiply) in one pass over the products
  * (csrc/persample.hip; DESIGN.md "K12"): for h < H, per sample,
  *     out[h*o_hs + s*o_stride] (+)= gain[h] * sum_{i < M, j < Nc} w_h(i,j) * ( sum_{l < L} A_s[i][l] * B_s[j][l] )**2
