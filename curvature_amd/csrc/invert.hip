@@ -71,7 +71,8 @@ struct InvDev {
   int n, np, P;
   float sqrt_s, sqrt_n;
   int reverse;          // 1: factor J M J and emit L = J X^T J (KFAC.invert); 0: plain M, emit X = chol(M)^-1
-  int f64_in;           // reverse == 0 only: F points to an fp64 matrix (INF's V_s^T V_s), damping added in fp64
+  int f64_in;           // reverse == 0 only: F points to an fp64 matrix (INF's V_s^T V_s), damping added in fp64 (add64)
+  int r_minus;          // right-hand side mode: emit R - Z instead of Z
   double* Xout;         // reverse == 0: (n x n) fp64 output, lower triangular
   // reverse == 0, right-hand side mode: emit Z = chol(M)^-1 R for a lower-triangular (n x n) fp64 R instead of the inverse
   // itself - INF.pre_sampler's B_c^-1 A_c^-1 without B_c^-1 and without the product (curvatures.py:566-570).  The forward
@@ -80,7 +81,7 @@ struct InvDev {
   // inverse X_sq of its block square - which is all of C^-1 that is formed (X holds the squares, nothing between them).
   const double* R;
   double* Zm;
-  int r_minus, pad_;    // emit R - Z instead of Z
+  double add64;         // f64_in: the damping as the caller gave it (sqrt_n holds it rounded to fp32, for fp32 input)
   // reverse == 1 (KFAC.invert): the triangular inverse outside the block squares is accumulated in fp32, off the chain
   // (supd32_kernel, xrows32_kernel): C32 = fp32 copy of the rows of C below each square (written by the panel product),
   // S32 = the running sums, X32 = the finished rows of C^-1 outside the squares (the squares themselves stay in X, fp64).
@@ -167,7 +168,7 @@ inv_prepare_kernel(const InvDev* __restrict__ t, int nf, int* __restrict__ flags
       double v;
       if (i < n && jj < n) {
         v = 0.5 * (M[(long long)i * n + jj] + M[(long long)jj * n + i]);
-        if (i == jj) v += (double)sn;
+        if (i == jj) v += d.add64;
       } else {
         v = (i == jj) ? 1.0 : 0.0;
       }
@@ -1600,6 +1601,7 @@ inv_finalize_kernel(const InvDev* __restrict__ t, int nf, int sq) {   // sq: edg
 }
 
 constexpr int INV_UPLOAD_CHUNK = 28;      // rows per launch of the table upload (upload_table, kernarg.h)
+static_assert(sizeof(InvDev) * INV_UPLOAD_CHUNK <= 3840, "a new InvDev field needs a hole in the row or a smaller chunk");
 
 static size_t inv_table_bytes(int n) { return align_up((size_t)std::max(n, 1) * sizeof(InvDev), 256); }
 static size_t inv_flags_bytes(int n) { return align_up((size_t)std::max(n, 1) * SQ_FLAGS * sizeof(int), 256); }
@@ -2206,7 +2208,8 @@ extern "C" int curv_chol_factor_inverse(void* stream_, const curv_cholinv_desc* 
     d.P = cdiv(s.n, NB); d.np = d.P * NB;
     d.info = info + i;
     d.sqrt_s = 1.0f;
-    d.sqrt_n = (float)s.diag_add;            // added in fp32 like the reference's `vtv + eye` (:567)
+    d.sqrt_n = (float)s.diag_add;            // fp32 input: added in fp32 like the reference's `vtv + eye` (:567)
+    d.add64 = s.diag_add;                    // fp64 input: added in fp64, unrounded
     d.reverse = 0;
     d.pivot_min = s.pivot_min > 0.0 ? s.pivot_min : 0.0;
     d.R = s.R;                               // (Zm: a third work matrix, placed by chol_sweep)

@@ -428,7 +428,10 @@ int curv_event_synchronize(void* event);                                /* block
  * torch's cholesky returns).  The damped matrix is formed in fp32 exactly as the reference does
  * (:368-375); the factorisation itself runs in fp64.  info[i] (device int32) is 0 on success and
  * 1 + the index of the failing pivot when factor i is not positive definite, in which case L holds
- * garbage: the caller raises the reference's RuntimeError (:380, scripts/hyper.py:141).
+ * garbage: the caller raises the reference's RuntimeError (:380, scripts/hyper.py:141).  The index
+ * counts in the order of the sweep, which factorises the index-REVERSED damped factor J (.) J: word w
+ * names row n - w of F (what LAPACK reports for J (.) J, not for the factor as given;
+ * tests/test_chol_factor_inverse_gpu.py).
  * ---------------------------------------------------------------------------------------------- */
 typedef struct curv_inv_desc {
   const float* F;
