@@ -247,6 +247,13 @@ class curv_persample_pack_ex_desc(ctypes.Structure):
                [(k, ctypes.c_int32) for k in ("Ho", "Wo", "has_bias", "dtype", "transposed", "rows_outer", "Lp", "reserved")]
 
 
+class curv_persample_pack3d_desc(ctypes.Structure):
+    """Mirror of ``curv_persample_pack3d_desc`` in include/curv_hip.h."""
+    _fields_ = _ENDS + [(k, ctypes.c_longlong) for k in ("s_n", "s_c", "s_d", "s_h", "s_w", "src_elems")] + \
+               [(k, ctypes.c_int32) for k in ("N", "C", "D", "H", "W", "kd", "kh", "kw", "sd", "sh", "sw", "pd", "ph", "pw",
+                                              "has_bias", "dtype", "rows_outer", "Lp", "reserved")]
+
+
 class curv_persample_dw_desc(ctypes.Structure):
     """Mirror of ``curv_persample_dw_desc`` in include/curv_hip.h."""
     _fields_ = [("x", ctypes.c_void_p), ("g", ctypes.c_void_p)] + \
@@ -378,6 +385,7 @@ SIGNATURES = {
     "curv_persample_sq_accumulate": (_i, [_vp, ctypes.POINTER(curv_persample_desc), _i, _vp, _sz]),
     "curv_persample_pack": (_i, [_vp, ctypes.POINTER(curv_persample_pack_desc), _i]),
     "curv_persample_pack_ex": (_i, [_vp, ctypes.POINTER(curv_persample_pack_ex_desc), _i]),
+    "curv_persample_pack3d": (_i, [_vp, ctypes.POINTER(curv_persample_pack3d_desc), _i]),
     "curv_persample_quad_workspace_bytes": (_sz, [ctypes.POINTER(curv_persample_quad_desc), _i]),
     "curv_persample_quad_plan_flops": (_i, [ctypes.POINTER(curv_persample_quad_desc), _i, ctypes.POINTER(ctypes.c_longlong)]),
     "curv_persample_quad_reduce": (_i, [_vp, ctypes.POINTER(curv_persample_quad_desc), _i, _vp, _sz]),

@@ -922,7 +922,8 @@ __global__ void __launch_bounds__(PS_THREADS) ps_reduce_kernel(const PsBatch bat
 // ------------------------------------------------------------------------------------------------ pack
 // curv_persample_pack_ex (and curv_persample_pack, its fp32-contiguous spelling): X_n or g_n as K-contiguous fp32 rows,
 // from a source of fp32, bf16 or fp16 values addressed through element strides; forward im2col (with a dilation: the
-// `reserved` word of the descriptor) or the transposed gather of a ConvTranspose2d input.
+// `reserved` word of the descriptor) or the transposed gather of a ConvTranspose2d input; curv_persample_pack3d: the 3-D
+// im2col of a Conv3d input, the same record with a depth window (a 2-D item is D = kd = sd = 1, pd = 0).
 struct PsPack {
   const void* src;
   float* dst;
@@ -930,12 +931,17 @@ struct PsPack {
   unsigned s_c, s_h, s_w;       // strides inside a sample, in elements (a sample spans fewer than 2^31: pack_plan_of)
   int N, C, H, W, kh, kw, sh, sw, ph, pw, Ho, Wo;
   int dh, dw;                   // dilation of the forward im2col (1, 1 for a transposed item)
-  int rows;                     // C kh kw (the ones row, if any, is row `rows`)
+  int rows;                     // C kd kh kw (the ones row, if any, is row `rows`)
   int R;                        // rows + has_bias
   int L, Lp;
   int has_bias, transposed, rows_outer;
   int vec;                      // rows are plain runs of the source, every group of four aligned: one vector load each
   long long base;               // first thread of this item in the launch
+  // the depth window, read by the DEPTH instantiations of the kernel only (behind everything else: the offsets of the
+  // fields the 2-D instantiations read are what they were)
+  unsigned s_d;
+  int D, kd, sd, pd, Do;
+  int depth;                    // the item has one: D, kd or pd differ from (1, 1, 0); it is launched with its like
 };
 
 typedef ArgBatch<PsPack, PS_BATCH> PsPackBatch;
@@ -947,21 +953,61 @@ int pack_elem_bytes(int dtype) {
   return dtype == CURV_DTYPE_F32 ? 4 : (dtype == CURV_DTYPE_BF16 || dtype == CURV_DTYPE_F16) ? 2 : 0;
 }
 
+// What the planner reads: the general 2-D descriptor with a depth window beside it.  The 2-D entry points hand over
+// D = kd = sd = 1, pd = 0, s_d = 0; `volume`: the item came through curv_persample_pack3d (its messages name the depth).
+struct PackItem : curv_persample_pack_ex_desc {
+  long long s_d;
+  int D, kd, sd, pd;
+  int volume;
+};
+
+PackItem pack_item_of(const curv_persample_pack_ex_desc& d) {
+  PackItem it;
+  static_cast<curv_persample_pack_ex_desc&>(it) = d;
+  it.s_d = 0; it.D = it.kd = it.sd = 1; it.pd = 0; it.volume = 0;
+  return it;
+}
+
+// What is wrong with the geometry of a 3-D item, nullptr if nothing: side::conv_geom_fault with a depth axis.  *Do:
+// the output depth.
+const char* volume_geom_fault(const PackItem& d, side::ConvGeom* g, int* Do) {
+  if (d.D < 1 || d.kd < 1 || d.sd < 1 || d.pd < 0) return "invalid geometry";
+  if (const char* fault = side::source_geom_fault(d, g)) return fault;
+  // (N C H W is below 2^40 by now; times D by a division: the product may not fit)
+  if ((long long)d.N * d.C * d.H * d.W >= ((1LL << 40) + d.D - 1) / d.D) return "too large (2^40 source elements or more)";
+  if ((long long)d.D + 2LL * d.pd < d.kd || (long long)d.H + 2LL * d.ph < d.kh || (long long)d.W + 2LL * d.pw < d.kw)
+    return "kernel larger than the padded input";
+  *Do = (int)(((long long)d.D + 2LL * d.pd - d.kd) / d.sd + 1);
+  g->Ho = (int)(((long long)d.H + 2LL * d.ph - d.kh) / d.sh + 1);
+  g->Wo = (int)(((long long)d.W + 2LL * d.pw - d.kw) / d.sw + 1);
+  return nullptr;
+}
+
 // Item `index` of a call of `who` as the kernel reads it, or false with the error text set.  One order of checks for
-// both entry points, that of curv_persample_pack: sizes first, addresses after them, so that a call with null pointers
+// every entry point, that of curv_persample_pack: sizes first, addresses after them, so that a call with null pointers
 // learns whether its geometry would be taken.  `pointers`: the one message a caller has for a null src or dst and a
 // misaligned dst (curv_persample_pack), in place of one message each.
-bool pack_plan_of(const curv_persample_pack_ex_desc& d, int index, const char* who, PsPack* out,
-                  const char* pointers = nullptr) {
+bool pack_plan_of(const PackItem& d, int index, const char* who, PsPack* out, const char* pointers = nullptr) {
   const int esize = pack_elem_bytes(d.dtype);
   if (esize == 0) {
     set_error("%s: item %d: unknown dtype %d (CURV_DTYPE_F32, CURV_DTYPE_BF16 or CURV_DTYPE_F16)", who, index, d.dtype);
     return false;
   }
   side::ConvGeom g;
+  int Do = 1;
   // the dilation rides in `reserved` (a half of 0 is 1): 0, what callers wrote before there was one, is dilation 1
   const int dh = std::max(d.reserved & 0xffff, 1), dw = std::max((d.reserved >> 16) & 0xffff, 1);
-  if (d.transposed) {
+  if (d.volume) {                                       // (no dilation and no transposed form: pack_item_of)
+    if (d.reserved != 0) {
+      set_error("%s: item %d: reserved is %d, must be 0", who, index, d.reserved);
+      return false;
+    }
+    if (const char* fault = volume_geom_fault(d, &g, &Do)) {
+      set_error("%s: item %d: %s (N %d C %d D %d H %d W %d kernel %dx%dx%d stride %dx%dx%d padding %dx%dx%d)", who, index,
+                fault, d.N, d.C, d.D, d.H, d.W, d.kd, d.kh, d.kw, d.sd, d.sh, d.sw, d.pd, d.ph, d.pw);
+      return false;
+    }
+  } else if (d.transposed) {
     if (dh != 1 || dw != 1) {
       set_error("%s: item %d: dilation %dx%d with the transposed gather", who, index, dh, dw);
       return false;
@@ -991,7 +1037,7 @@ bool pack_plan_of(const curv_persample_pack_ex_desc& d, int index, const char* w
     }
     g.kh = d.kh; g.kw = d.kw;
   }
-  if (d.s_n < 0 || d.s_c < 0 || d.s_h < 0 || d.s_w < 0 || d.src_elems < 1) {
+  if (d.s_n < 0 || d.s_c < 0 || d.s_d < 0 || d.s_h < 0 || d.s_w < 0 || d.src_elems < 1) {
     set_error("%s: item %d: negative stride, or source extent %lld elements below 1", who, index, d.src_elems);
     return false;
   }
@@ -1000,13 +1046,18 @@ bool pack_plan_of(const curv_persample_pack_ex_desc& d, int index, const char* w
   P.N = g.N; P.C = g.C; P.H = g.H; P.W = g.W;
   P.kh = g.kh; P.kw = g.kw; P.sh = g.sh; P.sw = g.sw; P.ph = g.ph; P.pw = g.pw; P.Ho = g.Ho; P.Wo = g.Wo;
   P.dh = dh; P.dw = dw;
-  const long long rows = (long long)d.C * d.kh * d.kw, L = (long long)P.Ho * P.Wo;
-  // what one sample spans, (C-1) s_c + (H-1) s_h + (W-1) s_w, stays below 2^31 elements: offsets inside a sample are
-  // 32-bit (a stride of 2^31 or more is refused before it is multiplied)
-  const long long dims[4] = {d.N, d.C, d.H, d.W}, strides[4] = {d.s_n, d.s_c, d.s_h, d.s_w};
+  P.D = d.D; P.kd = d.kd; P.sd = d.sd; P.pd = d.pd; P.Do = Do;
+  P.depth = d.D != 1 || d.kd != 1 || d.pd != 0;
+  // (the depth factors of a 3-D item enter only while the 2-D products are within their limit: nothing overflows)
+  long long rows = (long long)d.C * d.kh * d.kw, L = (long long)P.Ho * P.Wo;
+  if (rows <= (1 << 24)) rows *= d.kd;
+  if (L <= (1 << 24)) L *= Do;
+  // what one sample spans, (C-1) s_c + (D-1) s_d + (H-1) s_h + (W-1) s_w, stays below 2^31 elements: offsets inside a
+  // sample are 32-bit (a stride of 2^31 or more is refused before it is multiplied)
+  const long long dims[5] = {d.N, d.C, d.D, d.H, d.W}, strides[5] = {d.s_n, d.s_c, d.s_d, d.s_h, d.s_w};
   const long long span_max = 1LL << 31;
   long long span = 0;
-  for (int k = 1; k < 4 && span < span_max; ++k)
+  for (int k = 1; k < 5 && span < span_max; ++k)
     span = dims[k] > 1 && strides[k] >= span_max ? span_max : span + (dims[k] - 1) * strides[k];
   if (rows > (1 << 24) || L > (1 << 24) || span >= span_max || (long long)d.N * (rows + 1) * (d.Lp / 4 + 1) >= (1LL << 31)) {
     set_error("%s: item %d: too large (%lld rows, %lld positions)", who, index, rows, L);
@@ -1014,6 +1065,15 @@ bool pack_plan_of(const curv_persample_pack_ex_desc& d, int index, const char* w
   }
   if (d.Lp < L || (d.Lp & 3)) {
     set_error("%s: item %d: Lp %d must be a multiple of 4 and at least L = %lld", who, index, d.Lp, L);
+    return false;
+  }
+  // the largest addressed offset, span + (N-1) s_n, lies inside the extent (by a division: the product may not fit).  The
+  // 3-D form counts the extent among the sizes and checks it before the addresses; the 2-D forms keep their order
+  const bool short_extent = span >= d.src_elems || (d.N > 1 && d.s_n > (d.src_elems - 1 - span) / (d.N - 1));
+  if (short_extent && d.volume) {
+    set_error("%s: item %d: the source extent (%lld elements) is smaller than the largest offset its sizes and strides "
+              "address (N %d C %d D %d H %d W %d, strides %lld %lld %lld %lld %lld)", who, index, d.src_elems, d.N, d.C,
+              d.D, d.H, d.W, d.s_n, d.s_c, d.s_d, d.s_h, d.s_w);
     return false;
   }
   if (pointers && (!d.src || !d.dst || (reinterpret_cast<uintptr_t>(d.dst) & 15))) {
@@ -1032,8 +1092,7 @@ bool pack_plan_of(const curv_persample_pack_ex_desc& d, int index, const char* w
     set_error("%s: item %d: src is not aligned to its %d-byte elements", who, index, esize);
     return false;
   }
-  // the largest addressed offset, span + (N-1) s_n, lies inside the extent (by a division: the product may not fit)
-  if (span >= d.src_elems || (d.N > 1 && d.s_n > (d.src_elems - 1 - span) / (d.N - 1))) {
+  if (short_extent) {
     set_error("%s: item %d: the source extent (%lld elements) is smaller than the largest offset its sizes and strides "
               "address (N %d C %d H %d W %d, strides %lld %lld %lld %lld)", who, index, d.src_elems, d.N, d.C, d.H, d.W,
               d.s_n, d.s_c, d.s_h, d.s_w);
@@ -1041,6 +1100,7 @@ bool pack_plan_of(const curv_persample_pack_ex_desc& d, int index, const char* w
   }
   P.s_n = d.N > 1 ? d.s_n : 0; P.s_c = (unsigned)(d.C > 1 ? d.s_c : 0);
   P.s_h = (unsigned)(d.H > 1 ? d.s_h : 0); P.s_w = (unsigned)(d.W > 1 ? d.s_w : 0);
+  P.s_d = (unsigned)(d.D > 1 ? d.s_d : 0);
   P.rows = (int)rows;
   P.has_bias = d.has_bias ? 1 : 0;
   P.R = P.rows + P.has_bias;
@@ -1048,10 +1108,11 @@ bool pack_plan_of(const curv_persample_pack_ex_desc& d, int index, const char* w
   P.Lp = d.Lp;
   P.transposed = d.transposed ? 1 : 0;
   P.rows_outer = d.rows_outer ? 1 : 0;
-  // the vector path: a row is the run of H W source values behind (n, c), and every group of four of it starts on a
+  // the vector path: a row is the run of D H W source values behind (n, c), and every group of four of it starts on a
   // 4-element boundary - decided here, per item, from the pointer and the strides, so that the kernel's branch is uniform
-  const bool plain = !P.transposed && d.kh == 1 && d.kw == 1 && d.sh == 1 && d.sw == 1 && d.ph == 0 && d.pw == 0;
-  const bool run = (d.W == 1 || d.s_w == 1) && (d.H == 1 || d.s_h == d.W);
+  const bool plain = !P.transposed && d.kh == 1 && d.kw == 1 && d.sh == 1 && d.sw == 1 && d.ph == 0 && d.pw == 0 &&
+                     d.kd == 1 && d.sd == 1 && d.pd == 0;
+  const bool run = (d.W == 1 || d.s_w == 1) && (d.H == 1 || d.s_h == d.W) && (d.D == 1 || d.s_d == (long long)d.H * d.W);
   const bool aligned = (reinterpret_cast<uintptr_t>(d.src) % (4 * (uintptr_t)esize)) == 0 && (d.N == 1 || d.s_n % 4 == 0) &&
                        (d.C == 1 || d.s_c % 4 == 0);
   P.vec = plain && run && aligned;
@@ -1072,8 +1133,12 @@ struct alignas(4 * sizeof(T)) PsQuad4 { T v[4]; };
 // as zeros, a masked or padded element reads element 0 of the source and drops it.  32-bit index arithmetic after the
 // sample base (an item has fewer than 2^31 threads and a sample spans fewer than 2^31 elements: pack_plan_of): the
 // 64-bit divisions cost more than the copy.  TRANSPOSED: the launch may hold items of the transposed gather (its two
-// divisions per element stay out of the code of a launch that holds none: the forward unfolds of a ResNet).
-template <typename T, bool TRANSPOSED>
+// divisions per element stay out of the code of a launch that holds none: the forward unfolds of a ResNet).  DEPTH:
+// the items of the launch have a depth window (curv_persample_pack3d): l = (od, oh, ow) is decoded with two divisions and
+// the four elements walk with carries through ow and oh (with Wo = 1 or Ho Wo < 4 one thread crosses several depths); the
+// tap is (c, ad, a, b).  Items with a depth window are launched apart from the others (launch_pack), never transposed, so
+// a launch without one runs the code it ran before there was a depth.
+template <typename T, bool TRANSPOSED, bool DEPTH>
 __global__ void __launch_bounds__(PS_THREADS) ps_pack_kernel(const PsPackBatch batch) {
   const long long t = (long long)blockIdx.x * PS_THREADS + threadIdx.x;
   const PsPack& F = batch.e[owner_of(batch, t)];
@@ -1100,10 +1165,17 @@ __global__ void __launch_bounds__(PS_THREADS) ps_pack_kernel(const PsPackBatch b
     const unsigned khw = F.kh * F.kw, kw = F.kw, H = F.H, W = F.W, s_h = F.s_h, s_w = F.s_w;
     const int L = F.L, Wo = F.Wo, sh = F.sh, sw = F.sw, ph = F.ph, pw = F.pw;
     const bool transposed = TRANSPOSED && F.transposed;
-    const int c = (int)((unsigned)r / khw), q = r - c * (int)khw;
+    const unsigned taps = DEPTH ? (unsigned)F.kd * khw : khw;            // of one channel
+    const int c = (int)((unsigned)r / taps);
+    int q = r - c * (int)taps, ad = 0;
+    if (DEPTH) { ad = (int)((unsigned)q / khw); q -= ad * (int)khw; }
     const int a = (int)((unsigned)q / kw), b = q - a * (int)kw;
     const int ta = a * F.dh, tb = b * F.dw;                               // the tap's offset in the forward window
-    int oh = (int)((unsigned)k0 / (unsigned)Wo), ow = k0 - oh * Wo;
+    const unsigned D = F.D, s_d = F.s_d;
+    const int Ho = F.Ho, sd = F.sd, td = ad - F.pd;
+    int od = 0, rest = k0;
+    if (DEPTH) { od = (int)((unsigned)k0 / (unsigned)(Ho * Wo)); rest = k0 - od * Ho * Wo; }
+    int oh = (int)((unsigned)rest / (unsigned)Wo), ow = rest - oh * Wo;
     const T* plane = sample + (unsigned)c * F.s_c;
     const T* at[4];
 #pragma unroll
@@ -1123,8 +1195,18 @@ __global__ void __launch_bounds__(PS_THREADS) ps_pack_kernel(const PsPackBatch b
         iw = (unsigned)(ow * sw - pw + tb);
       }
       ok = ok & (ih < H) & (iw < W);
-      at[e] = ok ? plane + (ih * s_h + iw * s_w) : nullptr;
-      if (++ow == Wo) { ow = 0; ++oh; }
+      if constexpr (DEPTH) {
+        const unsigned id = (unsigned)(od * sd + td);
+        ok = ok & (id < D);
+        at[e] = ok ? plane + (id * s_d + ih * s_h + iw * s_w) : nullptr;
+        if (++ow == Wo) {
+          ow = 0;
+          if (++oh == Ho) { oh = 0; ++od; }
+        }
+      } else {
+        at[e] = ok ? plane + (ih * s_h + iw * s_w) : nullptr;
+        if (++ow == Wo) { ow = 0; ++oh; }
+      }
     }
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
@@ -1136,8 +1218,9 @@ __global__ void __launch_bounds__(PS_THREADS) ps_pack_kernel(const PsPackBatch b
   *reinterpret_cast<float4*>(F.dst + out) = make_float4(v[0], v[1], v[2], v[3]);
 }
 
+// `packs`: the items of one source type that have a depth window (`depth`), or those that have none.
 template <typename T>
-int launch_pack(hipStream_t stream, const std::vector<PsPack>& packs, const char* who) {
+int launch_pack(hipStream_t stream, const std::vector<PsPack>& packs, bool depth, const char* who) {
   return for_arg_batches<PsPack, PS_BATCH, 1>(
       (int)packs.size(), who,
       [&](int i, PsPack* P, long long* threads) {
@@ -1147,26 +1230,30 @@ int launch_pack(hipStream_t stream, const std::vector<PsPack>& packs, const char
       [](int, long long threads) { return cdivll(threads, PS_THREADS); },
       [&](const PsPackBatch* b, const long long*, const unsigned* grid) {
         const bool transposed = std::any_of(b[0].e, b[0].e + b[0].count, [](const PsPack& P) { return P.transposed != 0; });
-        void (*kernel)(PsPackBatch) = ps_pack_kernel<T, false>;
-        if (transposed) kernel = ps_pack_kernel<T, true>;
+        void (*kernel)(PsPackBatch) = ps_pack_kernel<T, false, false>;
+        if (transposed) kernel = ps_pack_kernel<T, true, false>;
+        if (depth) kernel = ps_pack_kernel<T, false, true>;               // (an item with a depth is never transposed)
         hipLaunchKernelGGL(kernel, dim3(grid[0]), dim3(PS_THREADS), 0, stream, b[0]);
         CURV_LAUNCH_CHECK();
         return CURV_OK;
       });
 }
 
-// Every item is planned before anything is launched; the items of one source type share their launches, in call order.
-int pack_items(hipStream_t stream, const curv_persample_pack_ex_desc* descs, int n, const char* who,
-               const char* pointers = nullptr) {
-  std::vector<PsPack> packs[3];
-  for (int i = 0; i < n; ++i) {
+// Every item is planned before anything is launched; the items of one source type share their launches, in call order -
+// those with a depth window apart from those without, which so run the instantiations they always ran.
+int pack_items(hipStream_t stream, const std::vector<PackItem>& items, const char* who, const char* pointers = nullptr) {
+  std::vector<PsPack> packs[2][3];
+  for (size_t i = 0; i < items.size(); ++i) {
     PsPack P;
-    if (!pack_plan_of(descs[i], i, who, &P, pointers)) return CURV_ERR_INVALID;
-    packs[descs[i].dtype].push_back(P);
+    if (!pack_plan_of(items[i], (int)i, who, &P, pointers)) return CURV_ERR_INVALID;
+    packs[P.depth][items[i].dtype].push_back(P);
   }
-  int rc = launch_pack<float>(stream, packs[CURV_DTYPE_F32], who);
-  if (rc == CURV_OK) rc = launch_pack<ps_bf16>(stream, packs[CURV_DTYPE_BF16], who);
-  if (rc == CURV_OK) rc = launch_pack<_Float16>(stream, packs[CURV_DTYPE_F16], who);
+  int rc = CURV_OK;
+  for (int depth = 0; depth < 2 && rc == CURV_OK; ++depth) {
+    rc = launch_pack<float>(stream, packs[depth][CURV_DTYPE_F32], depth != 0, who);
+    if (rc == CURV_OK) rc = launch_pack<ps_bf16>(stream, packs[depth][CURV_DTYPE_BF16], depth != 0, who);
+    if (rc == CURV_OK) rc = launch_pack<_Float16>(stream, packs[depth][CURV_DTYPE_F16], depth != 0, who);
+  }
   return rc;
 }
 
@@ -1410,11 +1497,11 @@ extern "C" int curv_persample_pack(void* stream_, const curv_persample_pack_desc
   CURV_REQUIRE(descs != nullptr, "%s: null descriptors", name);
   // (sizes that a geometry check refuses may be anything: they count as 0 here, and a product saturates)
   auto times = [](long long a, int b) { return b <= 0 ? 0 : a > LLONG_MAX / b ? LLONG_MAX : a * b; };
-  std::vector<curv_persample_pack_ex_desc> items(n);
+  std::vector<PackItem> items(n);
   for (int i = 0; i < n; ++i) {
     const curv_persample_pack_desc& d = descs[i];
-    curv_persample_pack_ex_desc& e = items[i];
-    e = curv_persample_pack_ex_desc{};
+    PackItem& e = items[i];
+    e = pack_item_of(curv_persample_pack_ex_desc{});
     e.src = d.src; e.dst = d.dst;
     e.N = d.N; e.C = d.C; e.H = d.H; e.W = d.W;
     e.kh = d.kh; e.kw = d.kw; e.sh = d.sh; e.sw = d.sw; e.ph = d.ph; e.pw = d.pw;
@@ -1425,12 +1512,34 @@ extern "C" int curv_persample_pack(void* stream_, const curv_persample_pack_desc
     else { e.s_n = chw; e.s_c = hw; e.s_h = d.W; e.s_w = 1; }
     e.src_elems = times(chw, d.N);
   }
-  return pack_items((hipStream_t)stream_, items.data(), n, name, "null src or dst, or dst not 16-byte aligned");
+  return pack_items((hipStream_t)stream_, items, name, "null src or dst, or dst not 16-byte aligned");
 }
 
 extern "C" int curv_persample_pack_ex(void* stream_, const curv_persample_pack_ex_desc* descs, int n) {
   const char* const name = "curv_persample_pack_ex";
   if (n <= 0) return CURV_OK;
   CURV_REQUIRE(descs != nullptr, "%s: null descriptors", name);
-  return pack_items((hipStream_t)stream_, descs, n, name);
+  std::vector<PackItem> items(n);
+  for (int i = 0; i < n; ++i) items[i] = pack_item_of(descs[i]);
+  return pack_items((hipStream_t)stream_, items, name);
+}
+
+// The 3-D im2col of a Conv3d input: the same planner and kernel with the depth window of the descriptor.
+extern "C" int curv_persample_pack3d(void* stream_, const curv_persample_pack3d_desc* descs, int n) {
+  const char* const name = "curv_persample_pack3d";
+  if (n <= 0) return CURV_OK;
+  CURV_REQUIRE(descs != nullptr, "%s: null descriptors", name);
+  std::vector<PackItem> items(n);
+  for (int i = 0; i < n; ++i) {
+    const curv_persample_pack3d_desc& d = descs[i];
+    PackItem& e = items[i];
+    e = pack_item_of(curv_persample_pack_ex_desc{});
+    e.src = d.src; e.dst = d.dst;
+    e.s_n = d.s_n; e.s_c = d.s_c; e.s_d = d.s_d; e.s_h = d.s_h; e.s_w = d.s_w; e.src_elems = d.src_elems;
+    e.N = d.N; e.C = d.C; e.D = d.D; e.H = d.H; e.W = d.W;
+    e.kd = d.kd; e.kh = d.kh; e.kw = d.kw; e.sd = d.sd; e.sh = d.sh; e.sw = d.sw; e.pd = d.pd; e.ph = d.ph; e.pw = d.pw;
+    e.has_bias = d.has_bias; e.dtype = d.dtype; e.rows_outer = d.rows_outer; e.Lp = d.Lp; e.reserved = d.reserved;
+    e.volume = 1;
+  }
+  return pack_items((hipStream_t)stream_, items, name);
 }

@@ -595,7 +595,8 @@ class Curvature(ABC):
 
     def _per_sample_layers(self, what: str, advice: str, grouped: bool = False) -> List[Module]:
         """The selected layers, in ``modules()`` order, after checking that every one has a per-sample form P_n = g_n X_n^T:
-        Linear, and Conv2d with groups 1, dilation 1 (any dilation with `ops.admit_dilated`) and integer padding; with
+        Linear, and Conv2d with groups 1, dilation 1 (any dilation with `ops.admit_dilated`) and integer padding; a Conv3d
+        (selectable with `ops.admit_conv_nd`) with `ops.admit_conv3d_per_sample`; with
         `ops.widen_per_sample` also ConvTranspose2d with groups 1, dilation 1 and integer padding and, for the estimators that treat a MultiheadAttention module as its two projections
         (KFAC, EFB), those two `AttentionProjection`s.  Any other raises NotImplementedError naming it.  `grouped`: the
         caller takes grouped Conv2d layers (`ops.per_sample_route`: as group slices or by the depthwise kernel); they
@@ -610,9 +611,10 @@ class Curvature(ABC):
             if kind not in self.layer_types:
                 continue
             why = None
-            if kind == 'Conv3d':
-                why = "a 3-D convolution: a sample's product sums over the output depths, which the per-sample kernels " \
-                      "would square one by one; KFAC, Diagonal, EFB and INF with the weight samplers take it"
+            if kind == 'Conv3d':                             # groups 1, zero padding, dilation 1 (`_check_conv_nd`)
+                if not ops.conv3d_per_sample_admitted():
+                    why = "a 3-D convolution: a sample's product sums over the output depths, which the per-sample " \
+                          "kernels would square one by one; KFAC, Diagonal, EFB and INF with the weight samplers take it"
             elif kind == 'Conv1d':                           # groups 1, zero padding (`_check_conv_nd`): as a Conv2d
                 if any(d != 1 for d in layer.dilation) and not ops.dilated_admitted():
                     why = "dilated convolution"

@@ -604,8 +604,8 @@ def admit_conv_nd(enable: bool = True) -> bool:
     """Switch Conv1d and Conv3d layers on or off for the process; returns what it was.  On: the estimators accept
     ``'Conv1d'`` and ``'Conv3d'`` in `layer_types` by name (they never enter the default selection) and `factor_jobs` routes
     them: a Conv1d as the Conv2d it is with a height of 1, the A side of a Conv3d to `Conv3dFactorJob`.  Groups 1, integer
-    zero padding; a Conv1d may be dilated with `admit_dilated` on, a Conv3d not.  The per-sample line takes a Conv1d, not
-    a Conv3d.  Off: both kinds are refused where they were."""
+    zero padding; a Conv1d may be dilated with `admit_dilated` on, a Conv3d not.  The per-sample line takes a Conv1d, and a
+    Conv3d only with `admit_conv3d_per_sample` on as well.  Off: both kinds are refused where they were."""
     global _CONV_ND
     was, _CONV_ND = _CONV_ND, bool(enable)
     return was
@@ -613,6 +613,28 @@ def admit_conv_nd(enable: bool = True) -> bool:
 
 def conv_nd_admitted() -> bool:
     return _CONV_ND
+
+
+# The per-sample line of a Conv3d has a switch of its own: with it off - the default - `admit_conv_nd`
+# admits what it admitted, and every refusal of a Conv3d in the per-sample line reads as it did.
+_CONV3D_PER_SAMPLE = False
+
+
+def admit_conv3d_per_sample(enable: bool = True) -> bool:
+    """Switch the per-sample line of Conv3d layers on or off for the process; returns what it was.  On, and with
+    `admit_conv_nd` on as well (alone it admits nothing: a Conv3d cannot be selected without that switch):
+    `per_sample_operands` takes a Conv3d - its X side the 3-D im2col of the (N, C, D, H, W) record, written per sample by
+    curv_persample_pack3d, its g side grad_output as (m, Do Ho Wo) - and with it ``Diagonal(per_sample=True)``,
+    ``EFB(per_sample=True)`` and the linearised predictives (`functional_variance`, `stage_output` /
+    `functional_covariance`, `functional_variance_grid`) do.  Groups 1, integer zero padding, dilation 1.  Off: a Conv3d
+    is refused there as before."""
+    global _CONV3D_PER_SAMPLE
+    was, _CONV3D_PER_SAMPLE = _CONV3D_PER_SAMPLE, bool(enable)
+    return was
+
+
+def conv3d_per_sample_admitted() -> bool:
+    return _CONV3D_PER_SAMPLE
 
 
 class ConvView(NamedTuple):
@@ -890,7 +912,9 @@ def factor_jobs(layer, x, g, out_size=None, approximation="expand") -> LayerJobs
 class PackSource(NamedTuple):
     """Where `per_sample_pack` reads an operand: the source seen as ``(N, C, H, W)`` with element `strides`
     ``(s_n, s_c, s_h, s_w)`` (the tensor itself gives the address, the dtype and the extent), the window, and `out_size`
-    ``(Ho, Wo)`` for the transposed gather of a ConvTranspose2d input (None: the forward im2col, with `dilation`)."""
+    ``(Ho, Wo)`` for the transposed gather of a ConvTranspose2d input (None: the forward im2col, with `dilation`).  The
+    record of a Conv3d (`admit_conv3d_per_sample`): `shape` ``(N, C, D, H, W)``, five `strides`, and `kernel`, `stride`
+    and `padding` as 3-tuples (depth first); `out_size` None and `dilation` (1, 1)."""
     shape: tuple
     kernel: tuple
     stride: tuple
@@ -909,9 +933,10 @@ def _pack_source(shape, strides, kernel=(1, 1), stride=(1, 1), padding=(0, 0), h
 
 
 def _is_contiguous_nchw(geometry: PackSource) -> bool:
-    """The strides are those of a contiguous (N, C, H, W) tensor (the stride of a dimension of size 1 addresses nothing)."""
-    N, C, H, W = geometry.shape
-    return all(d == 1 or s == w for d, s, w in zip(geometry.shape, geometry.strides, (C * H * W, H * W, W, 1)))
+    """The strides are those of a contiguous (N, C, H, W) - or (N, C, D, H, W) - tensor (the stride of a dimension of size 1
+    addresses nothing)."""
+    dense = [math.prod(geometry.shape[k + 1:]) for k in range(len(geometry.shape))]
+    return all(d == 1 or s == w for d, s, w in zip(geometry.shape, geometry.strides, dense))
 
 
 class PerSampleOperand(NamedTuple):
@@ -1063,14 +1088,15 @@ _PACK_DTYPES = {torch.float32: _lib.DTYPE_F32, torch.bfloat16: _lib.DTYPE_BF16, 
 
 def _per_sample_operand(src, geometry: PackSource, in_place: bool, rows_outer: bool) -> PerSampleOperand:
     """`in_place` is the caller's wish; it holds only for a float32 source that is that very matrix in memory."""
-    (N, C, H, W), kernel, stride, padding = geometry.shape, geometry.kernel, geometry.stride, geometry.padding
+    kernel, stride, padding = geometry.kernel, geometry.stride, geometry.padding
+    N, C = geometry.shape[:2]
     if geometry.out_size is not None:
         L = geometry.out_size[0] * geometry.out_size[1]
-    else:
-        dh, dw = geometry.dilation
-        L = ((H + 2 * padding[0] - dh * (kernel[0] - 1) - 1) // stride[0] + 1) * \
-            ((W + 2 * padding[1] - dw * (kernel[1] - 1) - 1) // stride[1] + 1)
-    rows = C * kernel[0] * kernel[1] + int(geometry.has_bias)
+    else:                                                  # every windowed axis: two of a 4-D record, three of a 5-D one
+        dilation = (1,) * (len(kernel) - 2) + tuple(geometry.dilation)
+        L = math.prod((size + 2 * p - d * (k - 1) - 1) // s + 1
+                      for size, k, s, p, d in zip(geometry.shape[2:], kernel, stride, padding, dilation))
+    rows = C * math.prod(kernel) + int(geometry.has_bias)
     if in_place and src.dtype == torch.float32 and _is_contiguous_nchw(geometry):
         return PerSampleOperand(src, rows, L, L, rows * L, L, None, False, 0)
     Lp = (L + 3) // 4 * 4
@@ -1101,7 +1127,11 @@ def per_sample_operands(layer, x, g, rows_outer: bool = False, in_place: bool = 
     (groups 1, dilation 1): g_n likewise, X_n the transposed gather (row (ci, a, b) at (oh, ow) is
     x[n, ci, (oh + ph - a) / sh, (ow + pw - b) / sw] where that is a whole position inside the input, else 0) - the column
     order of Wm; the output size is grad_output's.  Linear: g_n = grad_output[n]^T (m, T), X_n = x[n]^T [+ ones row] (D [+ 1], T)
-    with T the product of the middle dimensions (1 for an (N, D) input).  The sample is the leading index, as in
+    with T the product of the middle dimensions (1 for an (N, D) input).  Conv3d (`admit_conv_nd` and
+    `admit_conv3d_per_sample`; groups 1, dilation 1): g_n = grad_output[n] as (m, Do Ho Wo), X_n the 3-D im2col of x[n]
+    [+ ones row], rows in the order of ``weight.reshape(Cout, -1)``; the records are read through their five strides, in
+    place under the rule below (the input of a bias-free 1x1x1 / stride-1 one), and a side of 2^31 bytes or more raises
+    RuntimeError naming the largest batch that fits.  The sample is the leading index, as in
     `KFAC.update` - except for an `AttentionProjection` (curvatures.py), whose records are token-major: (T, N, E), or
     (T N, E) for the output projection with `samples` = N; they are read through strides, not transposed.  An operand is
     read in place where the record already is that matrix in float32, rows contiguous and a whole number of 16-byte groups
@@ -1128,11 +1158,34 @@ def per_sample_operands(layer, x, g, rows_outer: bool = False, in_place: bool = 
         if x.shape[:2] != g.shape[:2]:
             raise RuntimeError(f"per-sample update: {what}: records do not match (input {tuple(x.shape)}, grad_output "
                                f"{tuple(g.shape)})")
+    conv3d = kind == 'Conv3d' and _CONV_ND and _CONV3D_PER_SAMPLE
+    if conv3d and (x.dim() != 5 or g.dim() != 5):
+        raise RuntimeError(f"per-sample update: records of Conv3d must be (N, C, D, H, W), got {tuple(x.shape)} and "
+                           f"{tuple(g.shape)}")
     sides = factor_jobs(layer, ShapeOnly(tuple(x.shape)), ShapeOnly(tuple(g.shape)))
-    if sides.groups != 1 or not isinstance(sides.a, (FactorJob, ConvTFactorJob, DilatedFactorJob)):
+    if sides.groups != 1 or not isinstance(sides.a, (FactorJob, ConvTFactorJob, DilatedFactorJob) +
+                                           ((Conv3dFactorJob,) if conv3d else ())):
         raise NotImplementedError(f"per-sample update: unsupported layer {kind}")
     has_bias = sides.a.has_bias
-    if kind in ('Conv2d', 'ConvTranspose2d') or (_CONV_ND and kind == 'Conv1d'):
+    if conv3d:
+        # the records themselves, through their five strides (a channels_last_3d record or a channel slice is not copied):
+        # the X side is the 3-D im2col the pack writes per sample, the g side grad_output as (m, Do Ho Wo)
+        N, Ng = int(x.shape[0]), int(g.shape[0])
+        one, none = (1, 1, 1), (0, 0, 0)
+        geo_x = _pack_source(x.shape, x.stride(), sides.a.kernel, sides.a.stride, sides.a.padding, has_bias)
+        geo_g = _pack_source(g.shape, g.stride(), one, one, none)
+        whole = in_place and math.prod(g.shape[2:]) % 4 == 0
+        plain = (sides.a.kernel, sides.a.stride, sides.a.padding) == (one, one, none) and not has_bias
+        x_op = _per_sample_operand(x, geo_x, whole and plain, rows_outer)
+        g_op = _per_sample_operand(g, geo_g, whole, rows_outer)
+        for side, op in (("x", x_op), ("g", g_op)):
+            size = N * op.rows * op.Lp * 4                 # the product kernels address an operand in 31 bits
+            if size >= 1 << 31:
+                fits = ((1 << 31) - 1) // (op.rows * op.Lp * 4)
+                raise RuntimeError(f"per-sample update: the {side} operand of Conv3d is too large for the per-sample "
+                                   f"products: N {N} x rows {op.rows} x Lp {op.Lp} float32 values are {size} bytes, 2^31 or "
+                                   f"more; the largest batch that fits is {fits}")
+    elif kind in ('Conv2d', 'ConvTranspose2d') or (_CONV_ND and kind == 'Conv1d'):
         if kind == 'Conv1d':                               # read through its (N, C, 1, L) views: nothing is copied
             if x.dim() != 3 or g.dim() != 3:
                 raise RuntimeError(f"per-sample update: records of Conv1d must be (N, C, L), got {tuple(x.shape)} and "
@@ -1223,14 +1276,23 @@ def _source_extent(t: torch.Tensor) -> int:
 
 
 def _fill_pack(d, op: PerSampleOperand, dst: torch.Tensor) -> None:
-    """The curv_persample_pack_ex_desc `d` of `op` into `dst`."""
+    """The descriptor `d` of `op` into `dst`: a curv_persample_pack_ex_desc, or a curv_persample_pack3d_desc for an
+    operand with a 5-D source."""
     geo = op.pack
     d.src, d.dst = op.src.data_ptr(), dst.data_ptr()
-    _set_geometry(d, geo.shape, geo.kernel, geo.stride, geo.padding, geo.has_bias)
     d.rows_outer, d.Lp = int(op.rows_outer), op.Lp
-    d.s_n, d.s_c, d.s_h, d.s_w = geo.strides
     d.src_elems = _source_extent(op.src)
     d.dtype = _PACK_DTYPES[op.src.dtype]
+    if len(geo.shape) == 5:
+        d.N, d.C, d.D, d.H, d.W = geo.shape
+        d.kd, d.kh, d.kw = geo.kernel
+        d.sd, d.sh, d.sw = geo.stride
+        d.pd, d.ph, d.pw = geo.padding
+        d.has_bias = int(geo.has_bias)
+        d.s_n, d.s_c, d.s_d, d.s_h, d.s_w = geo.strides
+        return
+    _set_geometry(d, geo.shape, geo.kernel, geo.stride, geo.padding, geo.has_bias)
+    d.s_n, d.s_c, d.s_h, d.s_w = geo.strides
     d.transposed = int(geo.out_size is not None)
     if geo.dilation != (1, 1):                         # dh | dw << 16 in `reserved`; 0 is dilation 1
         if not all(1 <= v < 1 << 16 for v in geo.dilation):
@@ -1242,11 +1304,16 @@ def _fill_pack(d, op: PerSampleOperand, dst: torch.Tensor) -> None:
 
 def per_sample_pack(operands: Sequence[PerSampleOperand], dsts: Sequence[torch.Tensor]) -> None:
     """The packed float32 copy of every operand into its `dst` (a float32 GPU buffer of `floats` values, 16-byte aligned),
-    all layers in one call of curv_persample_pack_ex."""
+    all layers in one call of curv_persample_pack_ex - and one of curv_persample_pack3d for the operands with a 5-D source
+    (the records of a Conv3d), if there are any."""
     if len(dsts) != len(operands):
         raise RuntimeError(f"per_sample_pack: {len(operands)} operands, {len(dsts)} destinations")
-    arr = (_lib.curv_persample_pack_ex_desc * len(operands))()
-    for d, op, dst in zip(arr, operands, dsts):
+    deep = [len(op.pack.shape) == 5 for op in operands]
+    arr = (_lib.curv_persample_pack_ex_desc * deep.count(False))()
+    arr3 = (_lib.curv_persample_pack3d_desc * deep.count(True))()
+    flat, volume = iter(arr), iter(arr3)
+    for op, dst, is_deep in zip(operands, dsts, deep):
+        d = next(volume if is_deep else flat)
         _require_gpu(dst)
         if not op.src.is_cuda:
             raise RuntimeError("curvature_amd runs on MI355X only: got a CPU tensor (no CPU fallback)")
@@ -1255,8 +1322,10 @@ def per_sample_pack(operands: Sequence[PerSampleOperand], dsts: Sequence[torch.T
         if dst.numel() < op.floats:
             raise RuntimeError("per_sample_pack: destination too small")
         _fill_pack(d, op, dst)
-    if operands:
+    if len(arr):
         _lib.check(_lib.lib().curv_persample_pack_ex(_lib.stream_ptr(), arr, len(arr)), "curv_persample_pack_ex")
+    if len(arr3):
+        _lib.check(_lib.lib().curv_persample_pack3d(_lib.stream_ptr(), arr3, len(arr3)), "curv_persample_pack3d")
 
 
 class _PerSampleProduct:

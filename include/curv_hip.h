@@ -721,6 +721,41 @@ typedef struct curv_persample_pack_ex_desc {
 } curv_persample_pack_ex_desc;
 int curv_persample_pack_ex(void* stream, const curv_persample_pack_ex_desc* descs, int n);
 
+/* curv_persample_pack_ex with a depth window: X of a Conv3d, the 3-D im2col of a record, written per sample (the same
+ * planner and kernel; a 2-D item is D = kd = sd = 1, pd = 0).  The destination is that of curv_persample_pack_ex -
+ *   dst[(n*R + r)*Lp + l]   (rows_outer = 0)   or   dst[(r*N + n)*Lp + l]   (rows_outer != 0)
+ * fp32, dst 16-byte aligned, Lp a multiple of 4 - with R = C*kd*kh*kw + has_bias and L = Do*Ho*Wo: row r = (c, a, b, e) at
+ * l = (od, oh, ow) is x[n, c, od*sd - pd + a, oh*sh - ph + b, ow*sw - pw + e], 0 outside the input - the row order of
+ * weight.reshape(Cout, -1) -, the last row the ones of a biased layer for l < L, and every l in [L, Lp) is 0.  The source
+ * as in the 2-D form: `dtype` fp32 / bf16 / fp16, upcast exactly; element (n, c, d, h, w) is
+ * src[n*s_n + c*s_c + d*s_d + h*s_h + w*s_w] (strides in ELEMENTS, not negative; (N, C, D, H, W) contiguous is
+ * (CDHW, DHW, HW, W, 1), channels_last_3d (CDHW, 1, HWC, WC, C)); s_n is used in 64 bits, what one sample spans must be
+ * below 2^31 elements; nothing outside [src, src + src_elems) is read (a masked or padded element reads src[0] and drops
+ * it).  No dilation and no transposed form; `reserved` must be 0.  A 1x1x1 / stride-1 / padding-0 item whose rows are plain
+ * runs of the source (s_w == 1 or W == 1, s_h == W or H == 1, s_d == H*W or D == 1), with the pointer and the sample and
+ * channel strides multiples of four elements, is read with one 8- or 16-byte load per four values; everything else
+ * gathers per element.  Items with a depth window (D, kd or pd other than 1, 1, 0) are launched apart from those without,
+ * 16 of one dtype per launch; an item's bits do not depend on the other items of the call.  Every item is checked before
+ * anything is launched, sizes before addresses; CURV_ERR_INVALID with "curv_persample_pack3d: item <i>: ..." for an
+ * unknown dtype, a nonzero `reserved`, a size below 1, negative padding, a kernel larger than the padded input in any
+ * axis, a negative stride or an extent below 1, "too large" (more than 2^24 rows or positions, a sample span or a thread
+ * count of 2^31 or more), a bad Lp, a source extent smaller than the largest offset (a size here: it is checked before
+ * the addresses), a null or misaligned src or dst.  An empty call is a no-op. */
+typedef struct curv_persample_pack3d_desc {
+  const void* src;
+  float* dst;
+  long long s_n, s_c, s_d, s_h, s_w;
+  long long src_elems;
+  int32_t N, C, D, H, W;
+  int32_t kd, kh, kw, sd, sh, sw, pd, ph, pw;
+  int32_t has_bias;
+  int32_t dtype;
+  int32_t rows_outer;
+  int32_t Lp;
+  int32_t reserved;
+} curv_persample_pack3d_desc;
+int curv_persample_pack3d(void* stream, const curv_persample_pack3d_desc* descs, int n);
+
 /* ------------------------------------------------------------------------------------------------
  * Per-sample products of true depthwise convolutions (in_channels == out_channels == groups; csrc/persample_dw.hip,
  * DESIGN.md "K14").  Channel c owns row c of [W | b], a 1 x n_g row with n_g = kh*kw + has_bias, and its per-sample
