@@ -13,7 +13,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc")
 INCLUDE = os.path.normpath(os.path.join(_HERE, "..", "include"))
 LIB_PATH = os.path.join(CSRC, "libcurv_hip.so")
-SOURCES = ["api.cpp", "collective.cpp", "elementwise.hip", "syrk.hip", "syrk_flat.hip", "syrk_corr.hip", "syrk_pre.hip", "syrk_small.hip", "group_factor.hip", "kfac_half.hip", "convt_factor.hip", "dilated_factor.hip", "conv3d_factor.hip", "reduce_factor.hip", "persample.hip", "persample_dw.hip", "logit_mc.hip", "invert.hip", "gemm.hip", "inf.hip", "eigh.hip", "eigh_lowrank.hip"]
+SOURCES = ["api.cpp", "collective.cpp", "elementwise.hip", "syrk.hip", "syrk_flat.hip", "syrk_corr.hip", "syrk_pre.hip", "syrk_small.hip", "group_factor.hip", "kfac_half.hip", "convt_factor.hip", "dilated_factor.hip", "conv3d_factor.hip", "reduce_factor.hip", "persample.hip", "persample_dw.hip", "logit_mc.hip", "invert.hip", "gemm.hip", "inf.hip", "eigh.hip", "eigh_lowrank.hip", "logdet.hip"]
 HIPCC_FLAGS = ["-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC", "-shared", "-Wall",
                "-Wno-unused-function", "-ldl"]
 
@@ -302,6 +302,13 @@ class curv_eigh_desc(ctypes.Structure):
                 ("reserved", ctypes.c_int32)]
 
 
+class curv_logsum_desc(ctypes.Structure):
+    """Mirror of ``curv_logsum_desc`` in include/curv_hip.h."""
+    _fields_ = [("x", ctypes.c_void_p), ("dtype", ctypes.c_int32), ("mode", ctypes.c_int32), ("count", ctypes.c_int64),
+                ("stride", ctypes.c_int64), ("weight", ctypes.c_double), ("gain", ctypes.c_double * 16),
+                ("shift", ctypes.c_double * 16)]
+
+
 class curv_select_desc(ctypes.Structure):
     _fields_ = [("lambda_vec", ctypes.c_void_p), ("I", ctypes.c_void_p), ("J", ctypes.c_void_p),
                 ("counts", ctypes.c_void_p), ("n", ctypes.c_int32), ("m", ctypes.c_int32), ("rank", ctypes.c_int32),
@@ -419,6 +426,8 @@ SIGNATURES = {
     "curv_sqrt_scale": (_i, [_vp, _vp, _d, _vp, _ll]),
     "curv_mul": (_i, [_vp, _vp, _vp, _vp, _ll]),
     "curv_copy_batched": (_i, [_vp, ctypes.POINTER(curv_copy_desc), _i]),
+    "curv_logsum_workspace_bytes": (_sz, [ctypes.POINTER(curv_logsum_desc), _i, _i]),
+    "curv_logsum_grid": (_i, [_vp, ctypes.POINTER(curv_logsum_desc), _i, _i, _vp, _ll, _vp, _vp, _sz]),
 }
 
 
@@ -431,6 +440,9 @@ SMALL_MAX_FLOP = 2.0e9              # CURV_SMALL_MAX_FLOP
 CONVT_MAX_PHASES = 64               # CURV_CONVT_MAX_PHASES
 PERSAMPLE_COV_MAX_OUTPUTS = 16      # CURV_PERSAMPLE_COV_MAX_OUTPUTS
 PERSAMPLE_GRID_MAX = 16             # CURV_PERSAMPLE_GRID_MAX
+DTYPE_F64 = 3                       # CURV_DTYPE_F64 (curv_logsum_desc.dtype)
+LOGSUM_GRID_MAX, LOGSUM_CHUNK, LOGSUM_ROW_BYTES = 16, 4096, 304     # CURV_LOGSUM_*
+LOGSUM_LOG, LOGSUM_SQUARES = 0, 1    # CURV_LOGSUM_LOG / _SQUARES (curv_logsum_desc.mode)
 GEMM_TABLE_RESIDENT = 1             # CURV_GEMM_TABLE_RESIDENT
 GEMM_PLAN_FIELDS = 8                # CURV_GEMM_PLAN_FIELDS
 ERR_NOT_PD, ERR_INVALID, ERR_WORKSPACE, ERR_HIP, ERR_NOT_CONVERGED = 1, 2, 3, 4, 5     # CURV_ERR_* of the header

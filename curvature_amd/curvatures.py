@@ -833,6 +833,108 @@ class Curvature(ABC):
         staged outputs: ``_predictive_kept``).  Nothing to do for an estimator that keeps nothing."""
         self.__dict__.pop("_predictive_kept", None)
 
+    # ------------------------------------------------------------------ Laplace evidence (DESIGN.md K21)
+    def _evidence_pairs(self, method: str, hypers) -> list:
+        """`hypers` checked as `LinearisedPredictive._grid_points` checks them, before anything touches the device."""
+        what = f"{type(self).__name__}.{method}"
+        hypers = list(hypers)
+        if not hypers:
+            raise ValueError(f"{what}: no damping pairs")
+        for h, pair in enumerate(hypers):
+            if not isinstance(pair, (tuple, list)) or len(pair) != 2:
+                raise ValueError(f"{what}: pair {h} is not an (add, multiply) pair: {pair!r}")
+            for value in pair:
+                values = [value] if _is_scalar(value) else list(value)
+                if not values or not all(math.isfinite(float(x)) and float(x) > 0 for x in values):
+                    raise ValueError(f"{what}: pair {h} {tuple(pair)!r}: add and multiply must be finite and > 0")
+        return hypers
+
+    def _resolved(self, hypers) -> list:
+        """[(state key, [(n, s) of every pair])] for the entries of `state`, resolved as `invert` resolves them."""
+        gindex = self._global_index()
+        count = max(len(gindex), len(self.state))
+        return [(key, [self._hyper(add, multiply, gindex.get(key, position), count) for add, multiply in hypers])
+                for position, key in enumerate(self.state)]
+
+    def _spectrum_log_det(self, hypers, spectra):
+        """(rows, total) of `_log_det_parts` for Pi = s diag(x+) + n I in the basis `spectra[key]` holds the x of."""
+        segments = [ops.LogSumSegment.of(spectra[key], 1.0, [s for _, s in points], [n for n, _ in points])
+                    for key, points in self._resolved(hypers)]
+        return ops.logsum_grid(segments, len(hypers))
+
+    def _log_det_parts(self, hypers):
+        """(rows (L, H), total (H,)): float64 GPU tensors, log det Pi_l(n_lh, s_lh) per entry of `state` and their sum."""
+        raise NotImplementedError(f"{type(self).__name__}.log_det_grid: not implemented for this estimator")
+
+    def log_det_grid(self, hypers, *, per_layer: bool = False) -> Tensor:
+        """``sum_l log det Pi_l(n_l, s_l)`` of the regularised precision that ``invert(add, multiply)`` stands for, for every
+        pair of ``hypers = [(add, multiply), ...]`` at once and without an inversion: a float64 GPU tensor of shape (H,), or
+        (L, H) - one row per entry of `state`, in its order - with `per_layer`.  Each pair holds scalars or per-layer lists,
+        resolved per layer as `invert` resolves them; every value finite and > 0 (ValueError naming the pair).  With
+        x+ = max(x, 0), as `invert` and `decompose` clamp:
+
+            Diagonal, EFB   Pi = s diag(state+) + n I (EFB: in the U_A (x) U_G basis): sum_e log(s state[e]+ + n)
+            KFAC            the reference's factored damping, Pi = (sqrt(s) A + sqrt(n) I) (x) (sqrt(s) G + sqrt(n) I):
+                            dim(G) sum_i log(sqrt(s) lambda_A,i + sqrt(n)) + dim(A) sum_j log(sqrt(s) lambda_G,j + sqrt(n))
+                            from `decompose()` (needed after the last `update()`); stacked decompositions of grouped
+                            layers sum over their groups.  Because of the factored damping this is an approximation of the
+                            log-determinant under the prior N(0, I / n), exact where A or G is a multiple of I
+            BlockDiagonal   Pi = s F + n I: the eigenvalues of `state` by one batched `ops.eigh`, clamped at 0 and kept
+                            until the next `update()`, then as Diagonal
+            INF             Pi = V diag(s lambda) V^T + diag(s corr+ + n):
+                            sum_e log(s corr[e]+ + n) - 2 sum_k log diag(B^-1)_k, B = chol(vtv + I): one factorisation
+                            sweep per pair for all layers, on scratch - `state`, `inv_state` and what `invert` keeps for
+                            the sampler are untouched; needs neither `invert` nor `ops.admit_inf_predictive`
+
+        `multiply` is the data-set size in the reference's convention (the curvature is accumulated as a mean).  The whole
+        model goes through one `ops.logsum_grid` call per `ops.LOGSUM_GRID_MAX` pairs: one read of the float32 state,
+        float64 from the load on, a fixed summation order (the same bits for the same pair in any list).  Nothing in
+        `state` or `inv_state` is written.  On a layer-sharded estimator the result covers the owned layers: the caller
+        all-reduces."""
+        hypers = self._evidence_pairs("log_det_grid", hypers)
+        assert self.state, "State dict is empty. Did you call 'update' prior to this?"
+        rows, total = self._log_det_parts(hypers)
+        return rows if per_layer else total
+
+    def log_prior_grid(self, hypers) -> Tensor:
+        """The prior's share of the Laplace evidence for every pair of `hypers` (as for `log_det_grid`): a float64 GPU
+        tensor (H,) of ``-1/2 sum_l n_l ||theta_l||^2 + 1/2 sum_l P_l log n_l`` over the layers of `state`, theta_l the
+        MAP [W | b] of layer l - read from ``model_state`` (`_mean_slots`), so a model that currently holds a sample gives
+        the same value - and P_l its parameter count (the 2 pi terms cancel against the log-determinant's).  The squared
+        norms are one `ops.logsum_grid` call.  On a layer-sharded estimator the owned layers only: the caller all-reduces."""
+        hypers = self._evidence_pairs("log_prior_grid", hypers)
+        assert self.state, "State dict is empty. Did you call 'update' prior to this?"
+        resolved = self._resolved(hypers)
+        segments, first, biased, second, counts = [], [], [], [], []
+        for k, (key, _) in enumerate(resolved):
+            if isinstance(key, str):
+                raise NotImplementedError(f"{type(self).__name__}.log_prior_grid: the attention entry {key!r} of `state` has "
+                                          "no [W | b] matrix")
+            views = [slot.view for slot in self._mean_slots(key)]
+            if not all(v.is_contiguous() for v in views):
+                # (the tap views of a ConvTranspose2d: together they are its weight tensor, which is read whole)
+                views = [self.model_state_of(key, 'weight')] + \
+                    ([self.model_state_of(key, 'bias')] if key.bias is not None else [])
+            weight, rest = views[0], views[1:]
+            first.append(len(segments))
+            segments.append(ops.LogSumSegment.squares(weight))
+            if rest:
+                biased.append(k)
+                second.append(len(segments))
+                segments.append(ops.LogSumSegment.squares(rest[0]))
+            counts.append(sum(v.numel() for v in views))
+        out, _ = ops.logsum_grid(segments, 1)
+        dev = out.device
+        squares = out[torch.tensor(first, device=dev), 0]
+        if biased:
+            squares[torch.tensor(biased, device=dev)] += out[torch.tensor(second, device=dev), 0]
+        precisions = torch.tensor([[n for n, _ in points] for _, points in resolved], dtype=torch.float64, device=dev)
+        prior = torch.tensor([0.5 * math.fsum(P * math.log(points[h][0]) for P, (_, points) in zip(counts, resolved))
+                              for h in range(len(hypers))], dtype=torch.float64, device=dev)
+        for k in range(len(resolved)):             # layer by layer, elementwise in h: the same bits for a pair in any list
+            prior.addcmul_(precisions[k], squares[k], value=-0.5)
+        return prior
+
     @staticmethod
     def _replace(sample: Tensor, weight: Tensor, bias: Tensor = None):
         """weight += sample[:, :-1], bias += sample[:, -1] (curvatures.py:67-82)."""
@@ -1050,6 +1152,9 @@ class Diagonal(LinearisedPredictive, Curvature):
                 out = arena[layer]
             self.inv_state[layer] = ops.rsqrt_affine(value, n, s, out=out)
 
+    def _log_det_parts(self, hypers):
+        return self._spectrum_log_det(hypers, self.state)
+
     @staticmethod
     def _reuse(prev: Optional[Tensor], like: Tensor) -> Optional[Tensor]:
         """The previous inverse-state tensor if it can be overwritten in place (stable addresses keep cached
@@ -1151,6 +1256,14 @@ class BlockDiagonal(Curvature):
                 self.state[layer] = torch.empty(g.numel(), g.numel(), dtype=torch.float32, device=g.device)
             jobs.append(ops.FactorJob(g.view(1, -1), self.state[layer], scale=float(batch_size), first=first))
         ops.kfac_accumulate(jobs)
+        self._spectrum = None                        # (of the blocks as they were: `log_det_grid`)
+
+    def _log_det_parts(self, hypers):
+        kept = self.__dict__.get("_spectrum")
+        if kept is None or list(kept) != list(self.state):
+            _, values = ops.eigh(list(self.state.values()), with_values=True)
+            kept = self._spectrum = {layer: ops.clamp_min0_(w) for layer, w in zip(self.state, values)}
+        return self._spectrum_log_det(hypers, kept)
 
     def invert(self, add: Union[float, list, tuple] = 0., multiply: Union[float, list, tuple] = 1.):
         assert self.state, "State dict is empty. Did you call 'update' prior to this?"
@@ -1543,6 +1656,24 @@ class KFAC(LinearisedPredictive, Curvature):
                 kept += (U_A,)
             self._decomposition[layer] = kept
 
+    def _log_det_parts(self, hypers):
+        kept = getattr(self, "_decomposition", None)
+        if kept is None:
+            raise RuntimeError("KFAC.log_det_grid: no eigendecomposition of the current factors: call decompose() after the "
+                               "last update()")
+        left_out = [_layer_name(self.model, l) for l in self.state if l not in kept]
+        if left_out:
+            raise RuntimeError(f"KFAC.log_det_grid: decompose() left out the grouped layer(s) {', '.join(left_out)}: switch "
+                               "ops.admit_grouped_per_sample and ops.admit_grouped_joint on and call decompose() again")
+        segments = []
+        for layer, points in self._resolved(hypers):
+            lam_G, lam_A = kept[layer][2], kept[layer][3]           # (m,), (n,) - stacked: (G, m), (G, n), every group alike
+            gains, shifts = [math.sqrt(s) for _, s in points], [math.sqrt(n) for n, _ in points]
+            segments.append(ops.LogSumSegment.of(lam_A, lam_G.shape[-1], gains, shifts))
+            segments.append(ops.LogSumSegment.of(lam_G, lam_A.shape[-1], gains, shifts))
+        out, total = ops.logsum_grid(segments, len(hypers))
+        return out[0::2] + out[1::2], total
+
     def sample(self, layer: Module, z: Optional[Tensor] = None) -> Tensor:
         """(L_A z L_G^T)^T -> (m, n) (curvatures.py:387-392); `z` (n, m) may be supplied for parity tests."""
         assert self.inv_state, "Inverse state dict is empty. Did you call 'invert' prior to this?"
@@ -1877,6 +2008,9 @@ class EFB(LinearisedPredictive, Curvature):
             n, s = self._hyper(add, multiply, gindex.get(layer, position), max(len(gindex), len(layers)))
             ops.rsqrt_affine(value, n, s, out=self.inv_state[layer])
 
+    def _log_det_parts(self, hypers):
+        return self._spectrum_log_det(hypers, self.state)
+
     def _predictive_terms(self) -> PredictiveTerms:
         # sample = U_G (Z * inv) U_A^T: T = U_G^T g, Y = U_A^T X, as `_update_per_sample`
         basis = lambda layer: self._eigvecs_t(layer)[::-1]     # noqa: E731
@@ -2094,6 +2228,37 @@ class INF(Curvature):
         for layer, (ua, ug, sigma, r), pre_sample in zip(layers, regs, pre_samples):
             self.inv_state[layer] = (ua, ug, r, pre_sample)
             self._sigma[layer] = sigma
+
+    def _log_det_parts(self, hypers):
+        # det Pi = det diag(s corr+ + n) det(I + vtv) with vtv as `invert` forms it from sigma = sqrt(s lambda) and
+        # r = (s corr+ + n)^(-1/2), and log det(I + vtv) = 2 sum log diag(B) = -2 sum log diag(B^-1), B = chol(vtv + I).
+        # Everything on scratch: `invert` clamps `state`'s correction in place, this works on a clamped copy
+        layers, resolved = list(self.state), self._resolved(hypers)
+        corrs = self._corr_arena
+        if corrs is not None and corrs.is_whole([self.state[l][3] for l in layers]):
+            flat, plus, pos = ops.clamp_min0_(corrs.flat.clone()), [], 0
+            for l in layers:
+                plus.append(flat[pos:pos + self.state[l][3].numel()])
+                pos += plus[-1].numel()
+        else:
+            plus = [ops.clamp_min0_(self.state[l][3].clone()) for l in layers]
+        rows, total = ops.logsum_grid([ops.LogSumSegment.of(c, 1.0, [s for _, s in points], [n for n, _ in points])
+                                       for c, (_, points) in zip(plus, resolved)], len(hypers))
+        infos = []
+        for h in range(len(hypers)):
+            regs = []
+            for l, c, (_, points) in zip(layers, plus, resolved):
+                n, s = points[h]
+                regs.append((self.state[l][0], self.state[l][1], ops.sqrt_scale(self.state[l][2], s), ops.rsqrt_affine(c, n, s)))
+            for group in self._scratch_groups(regs):
+                vtvs = self._vtv_many([regs[k] for k in group])
+                invB = ops.chol_factor_inverse(vtvs, [1.0] * len(vtvs), check=False)
+                infos.append(ops.chol_factor_inverse.last_info)
+                part, part_total = ops.logsum_grid([ops.LogSumSegment.of(B.diagonal(), -2.0, [1.0], [0.0]) for B in invB], 1)
+                rows[torch.tensor(group, device=rows.device), h] += part[:, 0]
+                total[h] += part_total[0]
+        ops.check_factor_inverse_info(torch.cat(infos))                  # one read-back for the call
+        return rows, total
 
     # ------------------------------------------------------------------ linearised (GLM) predictive (opt-in)
     def _opt_in_predictive(self):

@@ -287,6 +287,58 @@ def tune_glm(model: torch.nn.Module, dataset: Iterable, estimator, hypers, outpu
     return dict(nll=nll, accuracy=accuracy, best=int(torch.argmin(nll)))
 
 
+def log_likelihood(model: torch.nn.Module, dataset: Iterable, device=None) -> Tuple[float, int]:
+    """``(sum, count)``: the SUM over `dataset` of the log-softmax at the label under the weights the model holds (float64,
+    accumulated on the device and read once), and the number of labelled inputs."""
+    if device is None:
+        device = next(model.parameters()).device
+    model.eval()
+    total = torch.zeros((), dtype=torch.float64, device=device)
+    count = 0
+    with torch.no_grad():
+        for images, labels in dataset:
+            logits = model(images.to(device, non_blocking=True))
+            labels = torch.as_tensor(labels).to(device, non_blocking=True).long()
+            total += torch.log_softmax(logits.double(), dim=1).gather(1, labels.view(-1, 1)).sum()
+            count += int(labels.numel())
+    return float(total.item()), count
+
+
+_data_log_likelihood = log_likelihood          # (`log_marginal_likelihood` has a keyword of the function's name)
+
+
+def log_marginal_likelihood(model: torch.nn.Module, dataset: Iterable, estimator, hypers, *, log_likelihood=None):
+    """The Laplace approximation of the log marginal likelihood (the "evidence") for every damping pair of
+    ``hypers = [(add, multiply), ...]`` - what the prior precision of a Laplace posterior is usually chosen by, with no
+    held-out labels and no backward pass:
+
+        evidence(h) = loglik - 1/2 sum_l n_l ||theta_l||^2 + 1/2 sum_l P_l log n_l - 1/2 sum_l log det Pi_l(n_l, s_l)
+
+    over the estimator's (owned) layers, with (n_l, s_l) the pair `invert` would resolve for layer l
+    (`Curvature.log_det_grid`, `Curvature.log_prior_grid`; the 2 pi terms cancel).  `multiply` is the data-set size in the
+    reference's convention: the accumulated curvature is a mean over the data, and s scales it to the sum the evidence
+    needs.  `loglik` is `log_likelihood(model, dataset)` under the weights the model holds now - the MAP weights, unless
+    the caller left a sample in it.  Passing ``log_likelihood=`` (the sum, or the ``(sum, count)`` pair) skips the data
+    pass; `dataset` may then be None.  Returns ``dict(evidence=(H,), log_likelihood=float, log_det=(H,), log_prior=(H,),
+    best=int)``: float64 CPU tensors read back once, `best` the argmax of `evidence` (the first on a tie).  ValueError on
+    an empty dataset.  On a layer-sharded estimator the three sums cover the owned layers; the caller all-reduces."""
+    hypers = list(hypers)
+    if log_likelihood is None:
+        device = next(model.parameters()).device
+        value, count = _data_log_likelihood(model, dataset, device)
+        if count == 0:
+            raise ValueError("log_marginal_likelihood: the dataset is empty")
+    else:
+        value = float(log_likelihood[0] if isinstance(log_likelihood, (tuple, list)) else log_likelihood)
+    log_det = estimator.log_det_grid(hypers)
+    log_prior = estimator.log_prior_grid(hypers)
+    evidence = (log_prior - 0.5 * log_det) + value
+    evidence, log_det, log_prior = torch.stack([evidence, log_det, log_prior]).cpu()
+    # (argmax of the first maximum: torch.argmax does not promise which of several equal entries it returns)
+    best = min(range(len(hypers)), key=lambda h: (-float(evidence[h]), h))
+    return dict(evidence=evidence, log_likelihood=value, log_det=log_det, log_prior=log_prior, best=best)
+
+
 def _joint_covariance(what: str, model: torch.nn.Module, estimator, images: torch.Tensor, outputs):
     """What `glm_predictive_joint` and `glm_predictive_mc` share: ``(logits, covariance, classes)`` from one forward pass,
     one backward pass and one `Curvature.stage_output` per selected output, and one `Curvature.functional_covariance`."""

@@ -2757,3 +2757,79 @@ def gemm_f64(A: torch.Tensor, B: torch.Tensor, alpha: float = 1.0, beta: float =
              C: Optional[torch.Tensor] = None) -> torch.Tensor:
     """float64 C = alpha * A @ B [+ beta * C] on strided 2-D GPU views."""
     return gemm_f64_batched([Gemm64(A, B, C, alpha, beta)])[0]
+
+
+LOGSUM_GRID_MAX = _lib.LOGSUM_GRID_MAX
+_LOGSUM_DTYPES = {torch.float32: _lib.DTYPE_F32, torch.float64: _lib.DTYPE_F64}
+
+
+class LogSumSegment(NamedTuple):
+    """One segment of `logsum_grid`: a float32 or float64 GPU tensor - a 1-D view with any positive stride (the diagonal of
+    a square matrix is ``M.diagonal()``: a stride of width + 1), or a contiguous tensor of any shape - read in place."""
+    tensor: torch.Tensor
+    weight: float
+    gains: Optional[Sequence[float]]       # per pair; None for a segment of squares
+    shifts: Optional[Sequence[float]]
+    mode: int = _lib.LOGSUM_LOG
+
+    @classmethod
+    def of(cls, tensor: torch.Tensor, weight: float, gains: Sequence[float], shifts: Sequence[float]):
+        """``weight * sum_e log(gains[h] * max(tensor[e], 0) + shifts[h])`` for every pair h."""
+        return cls(tensor, float(weight), [float(g) for g in gains], [float(s) for s in shifts], _lib.LOGSUM_LOG)
+
+    @classmethod
+    def squares(cls, tensor: torch.Tensor, weight: float = 1.0):
+        """``weight * sum_e tensor[e]**2``, in column 0 of its row (the other columns are 0)."""
+        return cls(tensor, float(weight), None, None, _lib.LOGSUM_SQUARES)
+
+
+def _logsum_extent(name: str, k: int, t: torch.Tensor):
+    if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype not in _LOGSUM_DTYPES:
+        raise RuntimeError(f"{name}: segment {k}: a float32 or float64 GPU tensor expected")
+    if t.dim() == 1 and (t.numel() <= 1 or t.stride(0) >= 1):
+        return t.numel(), (t.stride(0) if t.numel() > 1 else 1)
+    if t.is_contiguous():
+        return t.numel(), 1
+    raise RuntimeError(f"{name}: segment {k}: a 1-D view with a positive stride or a contiguous tensor expected, got shape "
+                       f"{tuple(t.shape)} with strides {tuple(t.stride())}")
+
+
+def logsum_grid(segments: Sequence[LogSumSegment], pairs: int):
+    """``(per_segment, total)``: float64 GPU tensors of shape (len(segments), pairs) and (pairs,) with
+    ``per_segment[i, h] = weight_i * sum_e log(gains_i[h] * max(x_i[e], 0) + shifts_i[h])`` (a segment of squares:
+    ``weight_i * sum_e x_i[e]**2`` in column 0, zeros beside it) and ``total[h]`` the sum of column h over the segments in
+    their order.  float64 from the load on, one read of the data for every pair, nothing copied; a fixed reduction order:
+    a result has the same bits alone, in a larger batch and on a repeat call (`curv_logsum_grid`).  More
+    than `LOGSUM_GRID_MAX` pairs run as chunks of that many."""
+    name = "logsum_grid"
+    segments, pairs = list(segments), int(pairs)
+    if pairs < 1:
+        raise ValueError(f"{name}: pairs {pairs} below 1")
+    if not segments:
+        raise ValueError(f"{name}: no segments")
+    extents = [_logsum_extent(name, k, s.tensor) for k, s in enumerate(segments)]
+    for k, s in enumerate(segments):
+        if s.mode == _lib.LOGSUM_LOG and (len(s.gains) != pairs or len(s.shifts) != pairs):
+            raise ValueError(f"{name}: segment {k}: {len(s.gains)} gains and {len(s.shifts)} shifts for {pairs} pairs")
+    n, dev = len(segments), segments[0].tensor.device
+    out = torch.zeros(n, pairs, dtype=torch.float64, device=dev)
+    total = torch.empty(pairs, dtype=torch.float64, device=dev)
+    L = _lib.lib()
+    arr = (_lib.curv_logsum_desc * n)()
+    for d, s, (count, stride) in zip(arr, segments, extents):
+        d.x, d.dtype, d.mode = s.tensor.data_ptr() if count else None, _LOGSUM_DTYPES[s.tensor.dtype], s.mode
+        d.count, d.stride, d.weight = count, stride, s.weight
+    for h0 in range(0, pairs, LOGSUM_GRID_MAX):
+        k = min(LOGSUM_GRID_MAX, pairs - h0)
+        for d, s, (count, _) in zip(arr, segments, extents):
+            if s.mode == _lib.LOGSUM_LOG:
+                d.gain[:k], d.shift[:k] = s.gains[h0:h0 + k], s.shifts[h0:h0 + k]
+            elif h0 > 0:
+                d.count, d.x = 0, None           # the squares went into column 0 with the first chunk
+        need = L.curv_logsum_workspace_bytes(arr, n, k)
+        if need == 0:
+            _lib.check(_lib.ERR_INVALID, "curv_logsum_workspace_bytes")
+        ws = workspace(need, dev, "logsum")
+        _lib.check(L.curv_logsum_grid(_lib.stream_ptr(), arr, n, k, out.data_ptr() + 8 * h0, pairs,
+                                      total.data_ptr() + 8 * h0, ws.data_ptr(), ws.numel()), "curv_logsum_grid")
+    return out, total

@@ -1243,6 +1243,47 @@ int curv_mul2d(void* stream, const float* A, long long a_rs, long long a_cs, con
                long long b_cs, float* out, int rows, int cols);
 
 /* ------------------------------------------------------------------------------------------------
+ * Laplace evidence: sum log(gain * x + shift) over whole-model arenas for a grid of damping pairs (csrc/logdet.hip)
+ * ---------------------------------------------------------------------------------------------- */
+/* out[i * out_stride + h] = weight_i * sum_e f_h(x_i[e * stride_i]) for segment i = 0..n-1 and pair h = 0..pairs-1, and,
+ * if `total` is given, total[h] = out[0][h] + out[1][h] + ... in table order.  Per segment:
+ *   x, dtype    `count` elements of CURV_DTYPE_F32 or CURV_DTYPE_F64, `stride` elements apart (>= 1; the diagonal of a
+ *               square matrix is a stride of width + 1); nothing outside them is read;
+ *   mode        CURV_LOGSUM_LOG: f_h(x) = log(gain[h] * max(x, 0) + shift[h]), for every pair;
+ *               CURV_LOGSUM_SQUARES: f(x) = x * x into column 0 only (the other columns of the row are left alone, and
+ *               `total` takes the segment into column 0 only);
+ *   gain, shift per-segment rows of the grid (pairs entries are read; none may be negative).
+ * fp64 from the load on: the element is widened, then multiply-add, log and sums are double; a lane takes one logarithm
+ * per pair for its 16 elements - of the product of their mantissas, with the exponents summed exactly.  No atomics: a workgroup
+ * owns one chunk of CURV_LOGSUM_CHUNK elements of one segment and writes one partial per pair into the workspace; a
+ * second launch sums a segment's partials in index order, a third the segments in table order - the same bits for a
+ * segment alone, in a batch and on a repeat call.  A segment without elements gives 0.  Columns of `out` from `pairs` on
+ * are not written (out_stride >= pairs).  The workspace (device memory, 8-byte aligned) holds the table and the
+ * partials: curv_logsum_workspace_bytes = n * CURV_LOGSUM_ROW_BYTES + (sum_i ceil(count_i / CURV_LOGSUM_CHUNK)) * pairs *
+ * 8, or 0 with the error text set for an invalid table.  Asynchronous on `stream`, nothing allocated.  n == 0 is a no-op
+ * that touches no device.  CURV_ERR_INVALID with "segment <i>" named, before anything is launched: a negative count, a
+ * null pointer with count > 0, a stride below 1, an unknown dtype or mode, a pointer not aligned to its elements, a
+ * negative (or NaN) gain or shift of a CURV_LOGSUM_LOG segment; also
+ * `pairs` outside 1 .. CURV_LOGSUM_GRID_MAX. */
+#define CURV_DTYPE_F64 3
+#define CURV_LOGSUM_GRID_MAX 16
+#define CURV_LOGSUM_CHUNK 4096
+#define CURV_LOGSUM_ROW_BYTES 304
+#define CURV_LOGSUM_LOG 0
+#define CURV_LOGSUM_SQUARES 1
+typedef struct curv_logsum_desc {
+  const void* x;
+  int32_t dtype;           /* CURV_DTYPE_F32 or CURV_DTYPE_F64 */
+  int32_t mode;            /* CURV_LOGSUM_LOG or CURV_LOGSUM_SQUARES */
+  int64_t count, stride;
+  double weight;
+  double gain[CURV_LOGSUM_GRID_MAX], shift[CURV_LOGSUM_GRID_MAX];
+} curv_logsum_desc;
+size_t curv_logsum_workspace_bytes(const curv_logsum_desc* descs, int n, int pairs);
+int curv_logsum_grid(void* stream, const curv_logsum_desc* descs, int n, int pairs, double* out, long long out_stride,
+                     double* total, void* workspace, size_t workspace_bytes);
+
+/* ------------------------------------------------------------------------------------------------
  * The one collective of the layer-sharded estimators (reference: per-layer independence,
  * curvature/curvatures.py:20-21, sample_and_replace :117-129): every rank has written the sampled parameters of its
  * own layers into `flat` (the parameters of all layers in one vector, grouped by owning rank: rank k's segment is
