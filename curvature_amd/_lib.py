@@ -13,7 +13,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc")
 INCLUDE = os.path.normpath(os.path.join(_HERE, "..", "include"))
 LIB_PATH = os.path.join(CSRC, "libcurv_hip.so")
-SOURCES = ["api.cpp", "collective.cpp", "elementwise.hip", "syrk.hip", "syrk_flat.hip", "syrk_corr.hip", "syrk_pre.hip", "syrk_small.hip", "group_factor.hip", "kfac_half.hip", "convt_factor.hip", "dilated_factor.hip", "conv3d_factor.hip", "reduce_factor.hip", "persample.hip", "persample_dw.hip", "logit_mc.hip", "invert.hip", "gemm.hip", "inf.hip", "eigh.hip", "eigh_lowrank.hip", "logdet.hip"]
+SOURCES = ["api.cpp", "collective.cpp", "elementwise.hip", "syrk.hip", "syrk_flat.hip", "syrk_corr.hip", "syrk_pre.hip", "syrk_small.hip", "group_factor.hip", "kfac_half.hip", "convt_factor.hip", "dilated_factor.hip", "conv3d_factor.hip", "reduce_factor.hip", "persample.hip", "persample_dw.hip", "norm_factor.hip", "logit_mc.hip", "invert.hip", "gemm.hip", "inf.hip", "eigh.hip", "eigh_lowrank.hip", "logdet.hip"]
 HIPCC_FLAGS = ["-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC", "-shared", "-Wall",
                "-Wno-unused-function", "-ldl"]
 
@@ -266,6 +266,19 @@ class curv_persample_dw_desc(ctypes.Structure):
                [(k, ctypes.c_longlong) for k in ("t_cs", "t_rs", "w_rs", "o_stride")]
 
 
+class curv_norm_desc(ctypes.Structure):
+    """Mirror of ``curv_norm_desc`` in include/curv_hip.h."""
+    _fields_ = [("x", ctypes.c_void_p), ("g", ctypes.c_void_p)] + \
+               [(k, ctypes.c_longlong) for k in ("x_sn", "x_sc", "x_sh", "x_sw", "x_elems",
+                                                 "g_sn", "g_sc", "g_sh", "g_sw", "g_elems")] + _SOURCE + \
+               [("mode", ctypes.c_int32), ("groups", ctypes.c_int32), ("eps", ctypes.c_float), ("has_bias", ctypes.c_int32),
+                ("mean", ctypes.c_void_p), ("var", ctypes.c_void_p), ("side", ctypes.c_int32), ("first", ctypes.c_int32),
+                ("scale", ctypes.c_float), ("alpha", ctypes.c_float), ("reserved", ctypes.c_int32),
+                ("reserved2", ctypes.c_int32), ("dst", ctypes.c_void_p), ("c_rs", ctypes.c_longlong)] + \
+               [(k, ctypes.c_void_p) for k in ("T", "Wt", "s", "out")] + \
+               [(k, ctypes.c_longlong) for k in ("t_cs", "t_rs", "w_rs", "o_stride")]
+
+
 _DW_RECORD = [("x", ctypes.c_void_p), ("g", ctypes.c_void_p)] + \
              [(k, ctypes.c_longlong) for k in ("x_sn", "x_sc", "x_sh", "x_sw", "x_elems",
                                                "g_sn", "g_sc", "g_sh", "g_sw", "g_elems")] + _SOURCE + _WINDOW + \
@@ -418,6 +431,14 @@ SIGNATURES = {
     "curv_persample_dw_quad_grid_plan_info": (_i, [ctypes.POINTER(curv_persample_dw_grid_desc), _i,
                                                   ctypes.POINTER(ctypes.c_longlong), ctypes.POINTER(ctypes.c_longlong)]),
     "curv_persample_dw_quad_grid_reduce": (_i, [_vp, ctypes.POINTER(curv_persample_dw_grid_desc), _i, _vp, _sz]),
+    "curv_kfac_norm_workspace_bytes": (_sz, [ctypes.POINTER(curv_norm_desc), _i]),
+    "curv_kfac_norm_plan_flops": (_i, [ctypes.POINTER(curv_norm_desc), _i, ctypes.POINTER(ctypes.c_longlong)]),
+    "curv_kfac_norm_accumulate": (_i, [_vp, ctypes.POINTER(curv_norm_desc), _i, _vp, _sz]),
+    "curv_persample_norm_workspace_bytes": (_sz, [ctypes.POINTER(curv_norm_desc), _i]),
+    "curv_persample_norm_plan_info": (_i, [ctypes.POINTER(curv_norm_desc), _i, ctypes.POINTER(ctypes.c_longlong),
+                                          ctypes.POINTER(ctypes.c_longlong)]),
+    "curv_persample_norm_sq_accumulate": (_i, [_vp, ctypes.POINTER(curv_norm_desc), _i, _vp, _sz]),
+    "curv_persample_norm_quad_reduce": (_i, [_vp, ctypes.POINTER(curv_norm_desc), _i, _vp, _sz]),
     "curv_persample_gram_reduce": (_i, [_vp, ctypes.POINTER(curv_persample_gram_desc), _i]),
     "curv_logit_mc_workspace_bytes": (_sz, [ctypes.POINTER(curv_logit_mc_desc), _i]),
     "curv_logit_mc_plan_flops": (_i, [ctypes.POINTER(curv_logit_mc_desc), _i, ctypes.POINTER(ctypes.c_longlong)]),
@@ -443,6 +464,9 @@ PERSAMPLE_GRID_MAX = 16             # CURV_PERSAMPLE_GRID_MAX
 DTYPE_F64 = 3                       # CURV_DTYPE_F64 (curv_logsum_desc.dtype)
 LOGSUM_GRID_MAX, LOGSUM_CHUNK, LOGSUM_ROW_BYTES = 16, 4096, 304     # CURV_LOGSUM_*
 LOGSUM_LOG, LOGSUM_SQUARES = 0, 1    # CURV_LOGSUM_LOG / _SQUARES (curv_logsum_desc.mode)
+NORM_GROUP, NORM_POSITION, NORM_GIVEN = 0, 1, 2     # CURV_NORM_* (curv_norm_desc.mode)
+NORM_SIDE_A, NORM_SIDE_G = 0, 1      # CURV_NORM_SIDE_* (curv_norm_desc.side)
+NORM_SPLIT_L, NORM_SLICE = 1024, 32  # CURV_NORM_SPLIT_L, CURV_NORM_SLICE
 GEMM_TABLE_RESIDENT = 1             # CURV_GEMM_TABLE_RESIDENT
 GEMM_PLAN_FIELDS = 8                # CURV_GEMM_PLAN_FIELDS
 ERR_NOT_PD, ERR_INVALID, ERR_WORKSPACE, ERR_HIP, ERR_NOT_CONVERGED = 1, 2, 3, 4, 5     # CURV_ERR_* of the header

@@ -21,6 +21,7 @@
 //      kernel, one chain per grid point).
 // How a plane is split follows from its own sizes only, so an item's bits do not depend on the other items of a call.
 #include "kernarg.h"
+#include "persample_dw_phase2.h"
 #include "side_build.h"
 #include "wave_sum.h"
 
@@ -665,6 +666,42 @@ int dw_products(const char* name, hipStream_t stream, const std::vector<DwItem>&
 }
 
 }  // namespace
+
+int dw_launch_sq(const char* name, hipStream_t stream, const DwSqArgs* items, int n) {
+  return for_arg_batches<DwSq, DW_BATCH, 1>(
+      n, name,
+      [&](int i, DwSq* S, long long* threads) {
+        const DwSqArgs& a = items[i];
+        S->p = a.p; S->C = a.dst; S->c_rs = a.c_rs;
+        S->N = a.N; S->Cn = a.C; S->n_g = a.n_g; S->first = a.first; S->alpha = a.alpha;
+        threads[0] = align_up((size_t)a.C * a.n_g, DW_THREADS);          // an item's threads fill whole workgroups
+      },
+      [](int, long long threads) { return threads / DW_THREADS; },
+      [&](const DwSqBatch* b, const long long*, const unsigned* grid) {
+        hipLaunchKernelGGL(ps_dw_sq_kernel, dim3(grid[0]), dim3(DW_THREADS), 0, stream, b[0]);
+        CURV_LAUNCH_CHECK();
+        return CURV_OK;
+      });
+}
+
+int dw_launch_quad(const char* name, hipStream_t stream, const DwQuadArgs* items, int n) {
+  return for_arg_batches<DwQuad, DW_BATCH, 1>(
+      n, name,
+      [&](int i, DwQuad* Q, long long* blocks) {
+        const DwQuadArgs& a = items[i];
+        Q->p = a.p; Q->T = a.T; Q->W = a.W; Q->s = a.s; Q->out = a.out;
+        Q->t_cs = a.t_cs; Q->t_rs = a.t_rs; Q->w_rs = a.w_rs; Q->o_stride = a.o_stride;
+        Q->N = a.N; Q->Cn = a.C; Q->n_g = a.n_g; Q->first = a.first; Q->alpha = a.alpha;
+        blocks[0] = a.N;
+      },
+      [](int, long long blocks) { return blocks; },
+      [&](const DwQuadBatch* b, const long long*, const unsigned* grid) {
+        hipLaunchKernelGGL(ps_dw_quad_kernel, dim3(grid[0]), dim3(DW_THREADS), 0, stream, b[0]);
+        CURV_LAUNCH_CHECK();
+        return CURV_OK;
+      });
+}
+
 }  // namespace curv
 
 using namespace curv;
@@ -714,20 +751,12 @@ extern "C" int curv_persample_dw_sq_accumulate(void* stream_, const curv_persamp
   }
   rc = dw_products(name, stream, items);
   if (rc != CURV_OK) return rc;
-  return for_arg_batches<DwSq, DW_BATCH, 1>(
-      n, name,
-      [&](int i, DwSq* S, long long* threads) {
-        const DwItem& F = items[i];
-        S->p = F.p; S->C = descs[i].dst; S->c_rs = descs[i].c_rs;
-        S->N = F.N; S->Cn = F.C; S->n_g = F.n_g; S->first = descs[i].first ? 1 : 0; S->alpha = descs[i].alpha;
-        threads[0] = align_up((size_t)F.C * F.n_g, DW_THREADS);          // an item's threads fill whole workgroups
-      },
-      [](int, long long threads) { return threads / DW_THREADS; },
-      [&](const DwSqBatch* b, const long long*, const unsigned* grid) {
-        hipLaunchKernelGGL(ps_dw_sq_kernel, dim3(grid[0]), dim3(DW_THREADS), 0, stream, b[0]);
-        CURV_LAUNCH_CHECK();
-        return CURV_OK;
-      });
+  std::vector<DwSqArgs> args(n);
+  for (int i = 0; i < n; ++i) {
+    const DwItem& F = items[i];
+    args[i] = DwSqArgs{F.p, descs[i].dst, descs[i].c_rs, F.N, F.C, F.n_g, descs[i].first ? 1 : 0, descs[i].alpha};
+  }
+  return dw_launch_sq(name, stream, args.data(), n);
 }
 
 extern "C" int curv_persample_dw_quad_reduce(void* stream_, const curv_persample_dw_desc* descs, int n, void* workspace,
@@ -747,22 +776,14 @@ extern "C" int curv_persample_dw_quad_reduce(void* stream_, const curv_persample
   }
   rc = dw_products(name, stream, items);
   if (rc != CURV_OK) return rc;
-  return for_arg_batches<DwQuad, DW_BATCH, 1>(
-      n, name,
-      [&](int i, DwQuad* Q, long long* blocks) {
-        const DwItem& F = items[i];
-        const curv_persample_dw_desc& d = descs[i];
-        Q->p = F.p; Q->T = d.T; Q->W = d.Wt; Q->s = d.s; Q->out = d.out;
-        Q->t_cs = d.t_cs; Q->t_rs = d.t_rs; Q->w_rs = d.w_rs; Q->o_stride = d.o_stride;
-        Q->N = F.N; Q->Cn = F.C; Q->n_g = F.n_g; Q->first = d.first ? 1 : 0; Q->alpha = d.alpha;
-        blocks[0] = F.N;
-      },
-      [](int, long long blocks) { return blocks; },
-      [&](const DwQuadBatch* b, const long long*, const unsigned* grid) {
-        hipLaunchKernelGGL(ps_dw_quad_kernel, dim3(grid[0]), dim3(DW_THREADS), 0, stream, b[0]);
-        CURV_LAUNCH_CHECK();
-        return CURV_OK;
-      });
+  std::vector<DwQuadArgs> args(n);
+  for (int i = 0; i < n; ++i) {
+    const DwItem& F = items[i];
+    const curv_persample_dw_desc& d = descs[i];
+    args[i] = DwQuadArgs{F.p, d.T, d.Wt, d.s, d.out, d.t_cs, d.t_rs, d.w_rs, d.o_stride, F.N, F.C, F.n_g, d.first ? 1 : 0,
+                         d.alpha};
+  }
+  return dw_launch_quad(name, stream, args.data(), n);
 }
 
 // ------------------------------------------------------------------------------------------------ K15: project, grid, Gram

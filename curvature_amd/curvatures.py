@@ -32,9 +32,30 @@ SUPPORTED_LAYERS = ['Linear', 'Conv2d', 'MultiheadAttention']
 # selectable by name but not part of the default selection (which stays what the reference selects)
 OPTIONAL_LAYERS = ['ConvTranspose2d']
 # layer classes whose parameters are a weight matrix (Wm) and an optional bias
-_MATRIX_LAYERS = ('Linear', 'Conv2d', 'ConvTranspose2d', 'Conv1d', 'Conv3d')
+_MATRIX_LAYERS = ('Linear', 'Conv2d', 'ConvTranspose2d', 'Conv1d', 'Conv3d', 'LayerNorm', 'GroupNorm', 'BatchNorm2d')
 # selectable by name only while `ops.admit_conv_nd` is on
 _ND_LAYERS = ('Conv1d', 'Conv3d')
+# selectable by name only while `ops.admit_norm_layers` is on: Wm = [weight.reshape(C, 1) | bias], one
+# 1 x (1 + has_bias) row per channel, C stacked Kronecker pairs like a depthwise 1x1 convolution
+_NORM_LAYERS = ('LayerNorm', 'GroupNorm', 'BatchNorm2d')
+_NORM_ADVICE = "KFAC, or Diagonal, with functional_variance take the layer"
+
+
+def _is_norm(layer) -> bool:
+    return layer.__class__.__name__ in _NORM_LAYERS
+
+
+def _check_norm(model, layer, what: str, takes: bool) -> None:
+    """What the estimators represent of a selected normalisation layer (`ops.admit_norm_layers`): a layer with affine
+    parameters over more than one channel, for KFAC and Diagonal."""
+    kind, name = layer.__class__.__name__, _layer_name(model, layer)
+    if not takes:
+        raise NotImplementedError(f"{what}: the normalisation layer {name} ({kind}) is not supported; {_NORM_ADVICE}")
+    if layer.weight is None:
+        raise NotImplementedError(f"{what}: {kind} layer {name} has no weight (elementwise_affine / affine is False): "
+                                  f"there is nothing to estimate")
+    if layer.weight.numel() < 2:
+        raise NotImplementedError(f"{what}: {kind} layer {name} has a single channel, which the stacked factors do not hold")
 
 
 def _is_convt(layer) -> bool:
@@ -99,11 +120,15 @@ def _wm(layer, t: Tensor) -> Tensor:
     contiguous copy of ``t.permute(1, 0, 2, 3)`` for ConvTranspose2d (whose weight is (in, out, kh, kw))."""
     if _is_convt(layer):
         return t.transpose(0, 1).reshape(t.shape[1], -1)
+    if _is_norm(layer):
+        return t.reshape(-1, 1)
     return t.reshape(t.shape[0], -1)
 
 
 def _wm_rows(layer) -> int:
     """Rows of the layer matrix Wm: output features / channels."""
+    if _is_norm(layer):
+        return layer.weight.numel()                      # (a LayerNorm with several normalised dims flattens)
     return layer.weight.shape[1] if _is_convt(layer) else layer.weight.shape[0]
 
 
@@ -127,6 +152,8 @@ def _check_reduce(model, layer) -> None:
         why = "a transposed convolution"
     elif kind == 'MultiheadAttention':
         why = "an attention layer (its records are (T, N, E), with the batch second)"
+    elif kind in _NORM_LAYERS:
+        why = "a normalisation layer"
     if why is not None:
         name = next((f"'{n}'" for n, mod in model.named_modules() if mod is layer), repr(layer))
         raise NotImplementedError(f'KFAC(approximation="reduce"): layer {name} is {why}, which the '
@@ -155,7 +182,7 @@ def _slots(layer, weight: Tensor, bias: Optional[Tensor]) -> List[_Slot]:
         v = weight.view(cin, cout, khw)
         out = [_Slot(slice(k, n0, khw), v[:, :, k].t(), False) for k in range(khw)]
     else:
-        w = weight.view(weight.shape[0], -1)
+        w = weight.view(-1, 1) if _is_norm(layer) else weight.view(weight.shape[0], -1)
         n0 = w.shape[1]
         out = [_Slot(slice(0, n0), w, True)]
     if bias is not None:
@@ -174,7 +201,7 @@ def _bank_buffers(layer, count: int, device):
     `_slots(layer, weights[k], biases[k])`.  A ConvTranspose2d's sets are held in the weight's own (in, out, kh, kw)
     layout, every other layer's as (out, in*kh*kw)."""
     w = layer.weight
-    shape = w.shape if _is_convt(layer) else (w.shape[0], w.numel() // w.shape[0])
+    shape = w.shape if _is_convt(layer) else (_wm_rows(layer), w.numel() // _wm_rows(layer))
     weights = torch.empty(count, *shape, dtype=torch.float32, device=device)
     if layer.bias is None:
         return weights, None
@@ -342,6 +369,8 @@ class Curvature(ABC):
     # KFAC / EFB / INF: every selected MultiheadAttention module contributes its two projections as layers of their own
     # (`AttentionProjection`), an extension of the reference (which raises for them)
     _mha_as_projections = False
+    # KFAC, Diagonal: the affine parameters of normalisation layers (`ops.admit_norm_layers`)
+    _takes_norm = False
     # the `_Arena`s this estimator allocated for its `state` / `inv_state` tensors (None until then): Diagonal and EFB
     # keep the first two, INF the other three (its corrections D, Lambda_lr and r)
     _state_arena = _inv_arena = _corr_arena = _lam_arena = _r_arena = None
@@ -361,7 +390,7 @@ class Curvature(ABC):
             raise TypeError
         for _type in self.layer_types:
             assert _type in SUPPORTED_LAYERS or _type in OPTIONAL_LAYERS or \
-                (ops.conv_nd_admitted() and _type in _ND_LAYERS)
+                (ops.conv_nd_admitted() and _type in _ND_LAYERS) or (ops.norm_layers_admitted() and _type in _NORM_LAYERS)
         if 'ConvTranspose2d' in self.layer_types:
             for layer in model.modules():
                 if _is_convt(layer):
@@ -370,6 +399,10 @@ class Curvature(ABC):
             for layer in model.modules():
                 if layer.__class__.__name__ in _ND_LAYERS and layer.__class__.__name__ in self.layer_types:
                     _check_conv_nd(model, layer)
+        if any(_type in _NORM_LAYERS for _type in self.layer_types):
+            for layer in model.modules():
+                if _is_norm(layer) and layer.__class__.__name__ in self.layer_types:
+                    _check_norm(model, layer, type(self).__name__, self._takes_norm)
         self.state = dict()
         self.inv_state = dict()
         # optional layer sharding across ranks (curvature_amd.sharding.Shard); None = own every layer.
@@ -577,8 +610,18 @@ class Curvature(ABC):
     def _record_layer(self, layer) -> None:
         """Record `layer`'s input (by reference) and raw grad_output into ``self.record[layer]`` at every pass."""
         self.record[layer] = [None, None]
+        if layer.__class__.__name__ == 'BatchNorm2d':
+            self.hooks.append(layer.register_forward_pre_hook(self._check_eval))
         self.hooks.append(layer.register_forward_pre_hook(self._save_input))
         self.hooks.append(layer.register_forward_hook(self._hook_output))
+
+    def _check_eval(self, module, input):
+        """A recorded BatchNorm2d must normalise with its running statistics: batch statistics couple the samples."""
+        if module.training or not module.track_running_stats:
+            raise NotImplementedError(
+                f"{type(self).__name__}: BatchNorm2d layer {_layer_name(self.model, module)} "
+                f"{'is in training mode' if module.training else 'has track_running_stats=False'}: batch statistics couple "
+                f"the samples, so the layer has no per-sample Jacobian; call model.eval() before the passes that are recorded")
 
     def _save_input(self, module, input):
         self.record[module][0] = input[0]            # by reference, like curvatures.py:307
@@ -593,7 +636,7 @@ class Curvature(ABC):
     def _save_output(self, module, grad_output):
         self.record[module][1] = grad_output         # raw; the reference stores grad * N (curvatures.py:310)
 
-    def _per_sample_layers(self, what: str, advice: str, grouped: bool = False) -> List[Module]:
+    def _per_sample_layers(self, what: str, advice: str, grouped: bool = False, norm: bool = False) -> List[Module]:
         """The selected layers, in ``modules()`` order, after checking that every one has a per-sample form P_n = g_n X_n^T:
         Linear, and Conv2d with groups 1, dilation 1 (any dilation with `ops.admit_dilated`) and integer padding; a Conv3d
         (selectable with `ops.admit_conv_nd`) with `ops.admit_conv3d_per_sample`; with
@@ -635,6 +678,9 @@ class Curvature(ABC):
             elif kind == 'MultiheadAttention' and self._mha_as_projections and wide:
                 layers.extend(AttentionProjection.of(layer))
                 continue
+            elif kind in _NORM_LAYERS and ops.norm_layers_admitted():
+                if not norm:                                 # (`norm`: the caller takes `ops.per_sample_route` "norm")
+                    why = f"a normalisation layer; {_NORM_ADVICE}"
             elif kind != 'Linear':
                 why = kind
             if why is not None:
@@ -649,7 +695,7 @@ class Curvature(ABC):
         self.record = dict()
         self._out_size = dict()
         for layer in self._per_sample_layers(f"{what}(per_sample=True)", "select other layer types or use per_sample=False",
-                                             grouped=self._per_sample_groups):
+                                             grouped=self._per_sample_groups, norm=self._takes_norm):
             if not isinstance(layer, AttentionProjection):
                 self._record_layer(layer)
                 continue
@@ -1029,6 +1075,7 @@ class Diagonal(LinearisedPredictive, Curvature):
 
     _supports_mha = True
     _per_sample_groups = True
+    _takes_norm = True
 
     def __init__(self, model: Union[Module, Sequential], layer_types: Union[List[str], str] = None, *, shard=None,
                  per_sample: bool = False):
@@ -1054,10 +1101,11 @@ class Diagonal(LinearisedPredictive, Curvature):
         # a grouped layer (ops.admit_grouped_per_sample) enters as its group slices - products of their own into row
         # blocks of the layer's state - or, a true depthwise one, through the direct kernel
         direct = [l for l in layers if ops.per_sample_route(l) == "depthwise"]
-        items = ops.per_sample_items([l for l in layers if l not in direct])
+        normed = [l for l in layers if ops.per_sample_route(l) == "norm"]
+        items = ops.per_sample_items([l for l in layers if l not in direct and l not in normed])
         operands = self._per_sample_operands("Diagonal", items) if items else []
-        records = {l: self._records_of("Diagonal", l) for l in direct}
-        device = operands[0][1].device if operands else records[direct[0]][0].device
+        records = {l: self._records_of("Diagonal", l) for l in direct + normed}
+        device = operands[0][1].device if operands else records[(direct + normed)[0]][0].device
         new = [l for l in layers if l not in self.state]
         fresh = {}
         if new:
@@ -1072,6 +1120,9 @@ class Diagonal(LinearisedPredictive, Curvature):
         ops.per_sample_sq_accumulate(jobs)                 # one product per layer or slice, all in one call
         ops.per_sample_dw_sq_accumulate([ops.PerSampleDwJob.of(l, *records[l], dst=state[l], alpha=batch_size,
                                                                first=l in fresh) for l in direct])
+        ops.per_sample_norm_sq_accumulate([ops.PerSampleNormJob.of(l, *records[l], name=_layer_name(self.model, l),
+                                                                   dst=state[l], alpha=batch_size, first=l in fresh)
+                                           for l in normed])
         for layer in layers:
             self.state[layer] = state[layer]
 
@@ -1097,7 +1148,7 @@ class Diagonal(LinearisedPredictive, Curvature):
                 continue
             if name in _MATRIX_LAYERS:
                 if layer in owned:
-                    bias_grad = layer.bias.grad.contiguous() if layer.bias is not None else None
+                    bias_grad = layer.bias.grad.contiguous().view(-1) if layer.bias is not None else None
                     keys.append(layer)
                     # state in Wm layout (out, in*kh*kw [+1]); a ConvTranspose2d gradient is permuted into it
                     items.append((_wm(layer, layer.weight.grad).contiguous(), bias_grad, fresh.get(layer, self.state.get(layer)),
@@ -1331,7 +1382,10 @@ class BlockDiagonal(Curvature):
 
 
 def _groups_of(layer) -> int:
-    """`groups` of a Conv2d (1 for every other layer)."""
+    """`groups` of a Conv2d; the channels of a normalisation layer (`ops.admit_norm_layers`: one 1 x n_g row each, the
+    stacked paths of a depthwise convolution); 1 for every other layer."""
+    if ops.is_norm_layer(layer):
+        return layer.weight.numel()
     return int(getattr(layer, "groups", 1)) if layer.__class__.__name__ == 'Conv2d' else 1
 
 
@@ -1371,6 +1425,7 @@ class KFAC(LinearisedPredictive, Curvature):
 
     _mha_as_projections = True
     _per_sample_groups = True
+    _takes_norm = True
 
     def __init__(self, model: Union[Module, Sequential], layer_types: Union[List[str], str] = None, *, shard=None,
                  approximation: str = "expand"):
@@ -1405,6 +1460,10 @@ class KFAC(LinearisedPredictive, Curvature):
                     # stack (curv_kfac_conv3d_accumulate), G as a 1x1 factor of grad_output
                     if any(d != 1 for d in layer.dilation):
                         _check_dilated(model, layer)
+                    self._record_layer(layer)
+                elif name in _NORM_LAYERS:
+                    # `_check_norm` has passed; C stacked pairs [A (C, n_g, n_g), G (C, 1, 1)] from the fused pass of
+                    # csrc/norm_factor.hip on the records as they are (a BatchNorm2d: in eval mode, `_check_eval`)
                     self._record_layer(layer)
                 elif name == 'ConvTranspose2d':
                     # Wm = weight.permute(1, 0, 2, 3).reshape(out, -1) [| bias]; A from the phase-split build
@@ -1628,6 +1687,10 @@ class KFAC(LinearisedPredictive, Curvature):
         stacked, ``(U_G^T (G, m, m), U_A^T (G, n, n), lambda_G (G, m), lambda_A (G, n))``, for a depthwise layer
         (`ops.per_sample_route`) with U_A (G, n, n) itself as a fifth entry, which its grid job reads."""
         assert self.state, "State dict is empty. Did you call 'update' prior to this?"
+        for layer in self.state:
+            if ops.is_norm_layer(layer):
+                raise NotImplementedError(f"KFAC.decompose: the normalisation layer {_layer_name(self.model, layer)} "
+                                          f"({layer.__class__.__name__}) is not supported; {_NORM_ADVICE}")
         stacked = ops.per_sample_admits_groups() and ops.per_sample_admits_grouped_joint()
         layers = [l for l, (A, G) in self.state.items() if (A.dim() == 2 and G.dim() == 2) or
                   (stacked and A.dim() == 3 and G.dim() == 3)]

@@ -515,6 +515,74 @@ def kfac_accumulate_reduce(jobs: Sequence[ReduceFactorJob], events=None) -> None
     _side_accumulate(ReduceFactorJob, jobs, events)
 
 
+class NormFactorJob(_ConvJob):
+    """One stacked factor of a normalisation layer (curv_kfac_norm_accumulate): `side` ``_lib.NORM_SIDE_A``:
+    dst (C, n_g, n_g) (+)= scale * sum [xh, 1][xh, 1]^T over samples and positions, `src` the layer's input;
+    ``_lib.NORM_SIDE_G``: dst (C, 1, 1) (+)= scale * sum g**2, `src` the grad_output.  `view`: the `NormView` of the layer
+    on its records (`norm_view`): sizes, strides, statistics mode.  `src` may also be just its shape (plan queries)."""
+    __slots__ = ("side", "view")
+
+    def __init__(self, src, dst, side, view, scale=1.0, first=False):
+        self._set(src, dst, (1, 1), (1, 1), (0, 0), view.has_bias and side == _lib.NORM_SIDE_A, scale, first)
+        self.side, self.view = int(side), view
+
+
+def _fill_norm_view(d, view, x, g, name: str) -> None:
+    """The record, geometry and statistics fields of a curv_norm_desc from a `NormView`; `x` / `g`: the records whose
+    addresses go in (tensors: float32 on the GPU), or None."""
+    d.N, d.C, d.H, d.W = view.dims
+    d.mode, d.groups, d.eps, d.has_bias = view.mode, view.groups, view.eps, int(view.has_bias)
+    for side, strides, elems in (("x", view.x_strides, view.x_elems), ("g", view.g_strides, view.g_elems)):
+        if strides is None:
+            continue
+        for k, v in zip(("sn", "sc", "sh", "sw"), strides):
+            setattr(d, f"{side}_{k}", int(v))
+        setattr(d, f"{side}_elems", int(elems))
+    for t in (x, g) + ((view.mean, view.var) if x is not None else ()):   # (a plan query reads no statistics)
+        if t is None:
+            continue
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise RuntimeError(f"{name}: curvature_amd runs on MI355X only: got a CPU tensor for {view.name} (no CPU "
+                               f"fallback)")
+        if t.dtype != torch.float32:
+            raise RuntimeError(f"{name}: {view.name} expects float32 records, got {t.dtype}")
+    if x is not None:
+        d.x = x.data_ptr()
+        if view.mean is not None:
+            d.mean, d.var = view.mean.data_ptr(), view.var.data_ptr()
+    if g is not None:
+        d.g = g.data_ptr()
+
+
+def _norm_descs(jobs: Sequence[NormFactorJob], check_tensors: bool = True):
+    arr = (_lib.curv_norm_desc * len(jobs))()
+    for d, j in zip(arr, jobs):
+        a_side = j.side == _lib.NORM_SIDE_A
+        src = j.src if check_tensors else None
+        _fill_norm_view(d, j.view, src if a_side else None, None if a_side else src, "norm factor build")
+        d.side, d.first, d.scale = j.side, int(j.first), j.scale
+        if check_tensors:
+            C, n_g = j.view.dims[1], (1 + int(j.view.has_bias)) if a_side else 1
+            _require_gpu(j.dst)
+            if tuple(j.dst.shape) != (C, n_g, n_g):
+                raise RuntimeError(f"norm factor destination must be ({C},{n_g},{n_g}), got {tuple(j.dst.shape)}")
+            d.dst = j.dst.data_ptr()
+    return arr
+
+
+def kfac_norm_plan_flops(jobs: Sequence[NormFactorJob]) -> List[int]:
+    """FLOPs the normalisation-layer build executes for each job (curv_kfac_norm_plan_flops, host only): the statistics
+    pass plus the products.  `job.src` may be a tensor or just its shape."""
+    return _side_plan_flops(NormFactorJob, jobs)
+
+
+def kfac_accumulate_norm(jobs: Sequence[NormFactorJob], events=None) -> None:
+    """Factor build of normalisation layers (curv_kfac_norm_accumulate) on the current stream: a statistics pass and a
+    product pass over the records (the standardised input is never written), then the sum over samples.  Scratch from
+    `workspace` (so CURV_DEBUG_POISON covers it).  `events` = (start, stop) ``torch.cuda.Event``s around the build."""
+    _side_accumulate(NormFactorJob, jobs, events)
+
+
 class FactorBuild(NamedTuple):
     """One kind of factor build: the job class, its descriptor filler, the names of the `ops` functions that price and
     build jobs of that class and, for the side builds, the library's symbol stem and the tag of their scratch."""
@@ -541,6 +609,7 @@ FACTOR_BUILDS = (
                 "kfac_reduce"),
     FactorBuild(Conv3dFactorJob, _conv3d_descs, "kfac_conv3d_plan_flops", "kfac_accumulate_conv3d", "curv_kfac_conv3d",
                 "kfac_conv3d"),
+    FactorBuild(NormFactorJob, _norm_descs, "kfac_norm_plan_flops", "kfac_accumulate_norm", "curv_kfac_norm", "kfac_norm"),
 )
 _BUILD_OF = {build.job: build for build in FACTOR_BUILDS}
 
@@ -635,6 +704,157 @@ def admit_conv3d_per_sample(enable: bool = True) -> bool:
 
 def conv3d_per_sample_admitted() -> bool:
     return _CONV3D_PER_SAMPLE
+
+
+# LayerNorm, GroupNorm and BatchNorm2d are opt-in as well: with the switch off - the default - every
+# selection, refusal and message is exactly what it was.
+_NORM = False
+_NORM_KINDS = ('LayerNorm', 'GroupNorm', 'BatchNorm2d')
+
+
+def admit_norm_layers(enable: bool = True) -> bool:
+    """Switch the affine parameters of normalisation layers on or off for the process; returns what it was.  On: the
+    estimators accept ``'LayerNorm'``, ``'GroupNorm'`` and ``'BatchNorm2d'`` in `layer_types` by name (they never enter the
+    default selection), `factor_jobs` routes them to two `NormFactorJob`s and `per_sample_route` answers ``"norm"``: the
+    gain and shift of channel c are the 1 x (1 + has_bias) row of a depthwise 1x1 convolution of the standardised input,
+    which csrc/norm_factor.hip forms on the fly.  KFAC and Diagonal take them (`functional_variance` included); a
+    BatchNorm2d in eval mode only.  Off: the three kinds are refused where they were."""
+    global _NORM
+    was, _NORM = _NORM, bool(enable)
+    return was
+
+
+def norm_layers_admitted() -> bool:
+    return _NORM
+
+
+def is_norm_layer(layer) -> bool:
+    """A LayerNorm, GroupNorm or BatchNorm2d while `admit_norm_layers` is on."""
+    return _NORM and layer.__class__.__name__ in _NORM_KINDS
+
+
+class NormView(NamedTuple):
+    """`norm_view` of a normalisation layer on its records: the logical (N, C, H, W) `dims`, the element strides and the
+    extent of each record (None without that record), the statistics `mode` (``_lib.NORM_*``) with `groups`, `eps` and, for
+    given statistics, the `mean` / `var` tensors; `name` for messages."""
+    dims: tuple
+    x_strides: Optional[tuple]
+    x_elems: int
+    g_strides: Optional[tuple]
+    g_elems: int
+    mode: int
+    groups: int
+    eps: float
+    has_bias: bool
+    mean: object
+    var: object
+    name: str
+
+
+def _dense_strides(shape) -> tuple:
+    out, run = [], 1
+    for v in reversed(shape):
+        out.append(run)
+        run *= int(v)
+    return tuple(reversed(out))
+
+
+def _norm_record_view(kind: str, name: str, t, k: int):
+    """(dims, strides, extent) of one record of a normalisation layer: `t` a tensor or `ShapeOnly` (taken as dense), `k`
+    the number of normalised dims of a LayerNorm.  Nothing is copied: a record whose dims do not collapse is refused."""
+    shape = tuple(int(v) for v in t.shape)
+    tensor = isinstance(t, torch.Tensor)
+    strides = tuple(int(v) for v in t.stride()) if tensor else _dense_strides(shape)
+    elems = _source_extent(t) if tensor else math.prod(shape)
+
+    def collapse(lo: int, hi: int):
+        """(size, stride) of dims [lo, hi) as one axis, or None where the strides do not allow it."""
+        size, stride = 1, 1
+        for i in reversed(range(lo, hi)):
+            if shape[i] == 1:
+                continue
+            if size > 1 and strides[i] != stride * size:
+                return None
+            if size == 1:
+                stride = strides[i]
+            size *= shape[i]
+        return size, stride
+
+    if kind == 'LayerNorm':
+        if len(shape) < k + 1:
+            raise RuntimeError(f"{name}: LayerNorm records must be (N, *, normalized_shape), got {shape}")
+        inner, mid = collapse(len(shape) - k, len(shape)), collapse(1, len(shape) - k)
+        if inner is None or (inner[0] > 1 and inner[1] != 1):
+            raise RuntimeError(f"{name}: the normalised dims of a LayerNorm record must be contiguous (shape {shape}, "
+                               f"strides {strides}); record a contiguous tensor")
+        if mid is None:
+            raise RuntimeError(f"{name}: the dims between the batch and the normalised dims of a LayerNorm record must "
+                               f"collapse to one stride (shape {shape}, strides {strides}); record a contiguous tensor")
+        return (shape[0], inner[0], mid[0], 1), (strides[0], 1, mid[1], 1), elems
+    if not 2 <= len(shape) <= 4:
+        raise RuntimeError(f"{name}: {kind} records must be (N, C), (N, C, L) or (N, C, H, W), got {shape}")
+    if kind == 'BatchNorm2d' and len(shape) != 4:
+        raise RuntimeError(f"{name}: BatchNorm2d records must be (N, C, H, W), got {shape}")
+    shape4 = shape[:2] + (1,) * (4 - len(shape)) + shape[2:]
+    strides4 = strides[:2] + (1,) * (4 - len(shape)) + strides[2:]
+    return shape4, strides4, elems
+
+
+def norm_view(layer, x=None, g=None, name: Optional[str] = None) -> NormView:
+    """The one place that turns a normalisation layer and its records (tensors, `ShapeOnly`s or None) into what
+    csrc/norm_factor.hip reads.  LayerNorm on (N, *, normalized_shape): C = the product of the normalised dims, H = the
+    product of the middle ones, W = 1, statistics per position.  GroupNorm on (N, C), (N, C, L) or (N, C, H, W): the natural
+    view, any strides (channels_last included), statistics per (sample, group).  BatchNorm2d: the natural view, the running
+    statistics - in eval mode only: batch statistics couple the samples, so there is no per-sample Jacobian."""
+    kind = layer.__class__.__name__
+    name = name or repr(layer)
+    if not is_norm_layer(layer):
+        raise NotImplementedError(f"{kind} layers are not supported (ops.admit_norm_layers() admits LayerNorm, GroupNorm "
+                                  f"and BatchNorm2d)")
+    if layer.weight is None:
+        raise NotImplementedError(f"{kind} layer {name} has no affine parameters (elementwise_affine / affine is False): "
+                                  f"there is nothing to estimate")
+    C = layer.weight.numel()
+    mean = var = None
+    groups, k = 1, 0
+    if kind == 'LayerNorm':
+        mode, k = _lib.NORM_POSITION, len(layer.normalized_shape)
+    elif kind == 'GroupNorm':
+        mode, groups = _lib.NORM_GROUP, int(layer.num_groups)
+    else:
+        mode = _lib.NORM_GIVEN
+        if layer.training or not layer.track_running_stats or layer.running_mean is None:
+            raise NotImplementedError(
+                f"BatchNorm2d layer {name} {'is in training mode' if layer.training else 'has track_running_stats=False'}: "
+                f"batch statistics couple the samples, so the layer has no per-sample Jacobian; call model.eval() (with "
+                f"track_running_stats=True) before the passes that are recorded")
+        mean, var = layer.running_mean.detach(), layer.running_var.detach()
+    views = [None if t is None else _norm_record_view(kind, name, t, k) for t in (x, g)]
+    if views[0] is None and views[1] is None:
+        raise RuntimeError(f"{name}: no recorded forward/backward pass")
+    dims = (views[0] or views[1])[0]
+    if views[0] is not None and views[1] is not None and views[0][0] != views[1][0]:
+        raise RuntimeError(f"{name}: input and grad_output differ in shape ({tuple(x.shape)} and {tuple(g.shape)})")
+    if dims[1] != C:
+        raise RuntimeError(f"{name}: the records have {dims[1]} channels, the layer {C}")
+    for t in (x, g):
+        if t is not None and t.dtype != torch.float32:
+            raise RuntimeError(f"{name}: {kind} expects float32 records, got {t.dtype}")
+    (xs, xe), (gs, ge) = ((None, 0) if v is None else v[1:] for v in views)
+    return NormView(dims, xs, xe, gs, ge, mode, groups, float(layer.eps), layer.bias is not None, mean, var, name)
+
+
+def _norm_jobs(layer, x, g, name: Optional[str] = None) -> "LayerJobs":
+    """`factor_jobs` of a normalisation layer (`admit_norm_layers`): two `NormFactorJob`s on the records as they are (no
+    copy); n = 1 + has_bias, m = 1, C stacked factors, L positions per sample."""
+    if x is None and g is None:
+        raise RuntimeError("KFAC.update: no recorded forward/backward pass for a selected layer")
+    x, g = (t.detach() if isinstance(t, torch.Tensor) else t for t in (x, g))
+    view = norm_view(layer, x, g, name)
+    a_job = None if x is None else NormFactorJob(_job_source(x), None, _lib.NORM_SIDE_A, view)
+    g_job = None if g is None else NormFactorJob(_job_source(g), None, _lib.NORM_SIDE_G, view)
+    N, C, H, W = view.dims
+    return LayerJobs(a_job, g_job, 1 + int(view.has_bias), 1, N, H * W, C)
 
 
 class ConvView(NamedTuple):
@@ -837,6 +1057,11 @@ def factor_jobs(layer, x, g, out_size=None, approximation="expand") -> LayerJobs
     (`_conv3d_jobs`).  `out_size`: the output size a ConvTranspose2d forward was
     seen to produce (it carries the effective output_padding), used when there is no `g` to read it from.  The jobs come
     without `dst`, `scale` and `first`."""
+    if is_norm_layer(layer):
+        if approximation == "reduce":
+            raise NotImplementedError(f'approximation="reduce" does not take a {layer.__class__.__name__} layer; '
+                                      f'approximation="expand" does')
+        return _norm_jobs(layer, x, g)
     if approximation == "reduce":
         return _reduce_jobs(layer, x, g)
     if approximation != "expand":
@@ -1041,7 +1266,10 @@ def per_sample_route(layer) -> str:
     """How the per-sample products of `layer` are formed (host only; the one place that decides it): ``"whole"`` - one
     product P_n = g_n X_n^T (every layer but a grouped Conv2d); ``"depthwise"`` - the direct kernel of
     csrc/persample_dw.hip (in_channels == out_channels == groups, at most `DW_MAX_TAPS` kernel taps); ``"slices"`` - one
-    product per group on channel slices of the records (`GroupSlice`: every other grouped Conv2d)."""
+    product per group on channel slices of the records (`GroupSlice`: every other grouped Conv2d); ``"norm"`` - the fused
+    pass of csrc/norm_factor.hip (LayerNorm, GroupNorm, BatchNorm2d while `admit_norm_layers` is on)."""
+    if is_norm_layer(layer):
+        return "norm"
     if layer.__class__.__name__ != 'Conv2d' or int(layer.groups) == 1:
         return "whole"
     if layer.in_channels == layer.out_channels == int(layer.groups) and \
@@ -1888,6 +2116,94 @@ def per_sample_dw_quad_reduce(jobs: Sequence[PerSampleDwJob]) -> None:
     _run_build("curv_persample_dw_workspace_bytes", "curv_persample_dw_quad_reduce",
                _per_sample_dw_descs(jobs, "per_sample_dw_quad_reduce", "quad"), len(jobs), jobs[0].out.device,
                "persample_dw")
+
+
+class PerSampleNormJob:
+    """The per-sample products of a normalisation layer (csrc/norm_factor.hip): p[n, c] = (sum g xh, sum g)
+    over the positions, from the layer's records `x` and `g` as they are (float32 GPU tensors; shapes for a plan query) seen
+    through `view` (`norm_view`).  `dst`, `out`, `T`, `W`, `s`, `alpha`, `first`: as in `PerSampleDwJob`, with
+    n_g = 1 + has_bias."""
+    __slots__ = ("x", "g", "view", "dst", "out", "T", "W", "s", "alpha", "first")
+
+    def __init__(self, x, g, view, dst=None, out=None, T=None, W=None, s=None, alpha=1.0, first=False):
+        self.x, self.g, self.view = x, g, view
+        self.dst, self.out, self.T, self.W, self.s = dst, out, T, W, s
+        self.alpha, self.first = float(alpha), bool(first)
+
+    @classmethod
+    def of(cls, layer, x, g, name: Optional[str] = None, **own):
+        """The job of a normalisation `layer` on its records."""
+        x, g = (t.detach() if isinstance(t, torch.Tensor) else t for t in (x, g))
+        if x is None or g is None:
+            raise RuntimeError(f"{name or repr(layer)}: the per-sample products need both records")
+        return cls(_job_source(x), _job_source(g), norm_view(layer, x, g, name), **own)
+
+
+def _per_sample_norm_descs(jobs: Sequence[PerSampleNormJob], name: str, reduction: Optional[str]):
+    """`reduction`: "sq", "quad" or None (a plan query: geometry only, `x` / `g` may be shapes)."""
+    arr = (_lib.curv_norm_desc * len(jobs))()
+    for d, j in zip(arr, jobs):
+        tensors = reduction is not None
+        _fill_norm_view(d, j.view, j.x if tensors else None, j.g if tensors else None, name)
+        d.first, d.alpha = int(j.first), j.alpha
+        if reduction is None:
+            continue
+        N, C, n_g = j.view.dims[0], j.view.dims[1], 1 + int(j.view.has_bias)
+        for t in (j.dst,) if reduction == "sq" else (j.out, j.T, j.W, j.s):
+            if t is not None and (not t.is_cuda or t.dtype != torch.float32):
+                raise RuntimeError(f"{name}: {j.view.name}: float32 GPU tensors expected (no CPU fallback)")
+        if reduction == "sq":
+            if j.dst is None or j.dst.dim() != 2 or tuple(j.dst.shape) != (C, n_g) or j.dst.stride(1) != 1:
+                raise RuntimeError(f"{name}: destination must be a ({C},{n_g}) view with unit column stride, got "
+                                   f"{None if j.dst is None else tuple(j.dst.shape)}")
+            d.dst, d.c_rs = j.dst.data_ptr(), j.dst.stride(0) if C > 1 else n_g
+            continue
+        if j.out is None or j.out.dim() != 1 or j.out.shape[0] != N or (N > 1 and j.out.stride(0) < 1):
+            raise RuntimeError(f"{name}: destination must be a length-{N} view with a positive stride, got "
+                               f"{None if j.out is None else tuple(j.out.shape)}")
+        d.out, d.o_stride = j.out.data_ptr(), max(j.out.stride(0), 1)
+        _dw_transform(d, j, name, C, n_g)
+        if j.W is not None:
+            if tuple(j.W.shape) != (C, n_g) or (n_g > 1 and j.W.stride(1) != 1):
+                raise RuntimeError(f"{name}: W must be a ({C},{n_g}) view with unit column stride, got {tuple(j.W.shape)}")
+            d.Wt, d.w_rs = j.W.data_ptr(), j.W.stride(0) if C > 1 else n_g
+        if j.s is not None:
+            if j.s.numel() != C or not j.s.is_contiguous():
+                raise RuntimeError(f"{name}: s must hold {C} contiguous values, got {tuple(j.s.shape)}")
+            d.s = j.s.data_ptr()
+    return arr
+
+
+def per_sample_norm_plan_info(jobs: Sequence[PerSampleNormJob]):
+    """(flops, bytes) per job (curv_persample_norm_plan_info, host only): the FLOPs of the statistics and product passes
+    and the bytes the algorithm needs (x twice - once with given statistics - and g once)."""
+    if not jobs:
+        return [], []
+    n = len(jobs)
+    arr = _per_sample_norm_descs(jobs, "per_sample_norm_plan_info", None)
+    flops, nbytes = (ctypes.c_longlong * n)(), (ctypes.c_longlong * n)()
+    _lib.check(_lib.lib().curv_persample_norm_plan_info(arr, n, flops, nbytes), "curv_persample_norm_plan_info")
+    return [int(v) for v in flops], [int(v) for v in nbytes]
+
+
+def per_sample_norm_sq_accumulate(jobs: Sequence[PerSampleNormJob]) -> None:
+    """``dst[c, j] (+)= alpha sum_n p[n, c, j]**2`` for every job (curv_persample_norm_sq_accumulate), on the current
+    stream; the statistics and the products p from `workspace`."""
+    if not jobs:
+        return
+    _run_build("curv_persample_norm_workspace_bytes", "curv_persample_norm_sq_accumulate",
+               _per_sample_norm_descs(jobs, "per_sample_norm_sq_accumulate", "sq"), len(jobs), jobs[0].dst.device,
+               "persample_norm")
+
+
+def per_sample_norm_quad_reduce(jobs: Sequence[PerSampleNormJob]) -> None:
+    """``out[n] (+)= alpha sum_c s[c]**2 sum_j W[c, j] (sum_i T[c, i, j] p[n, c, i])**2`` for every job
+    (curv_persample_norm_quad_reduce), on the current stream; the statistics and the products p from `workspace`."""
+    if not jobs:
+        return
+    _run_build("curv_persample_norm_workspace_bytes", "curv_persample_norm_quad_reduce",
+               _per_sample_norm_descs(jobs, "per_sample_norm_quad_reduce", "quad"), len(jobs), jobs[0].out.device,
+               "persample_norm")
 
 
 class PerSampleDwProjectJob(PerSampleDwJob):

@@ -52,14 +52,15 @@ class LinearisedPredictive:
 
     # ------------------------------------------------------------------ the shared steps
     def _predictive_operands(self, what: str, call: str, inputs: bool, rotated: bool, check=None,
-                             select: str = "inv_state", grouped: bool = False):
+                             select: str = "inv_state", grouped: bool = False, norm: bool = False):
         """What every reduction starts from: the checks, the selected layers that have an inverse state (`select`: the
         dict that says so - the grid needs `state` only), their per-sample operands from the current records (the g side
         only unless `inputs`; packed for a rotation if `rotated`), and the key that ties a kept X side to the recorded
         inputs themselves (tensor and version), not just to their shapes.  ``check(N)`` runs last (the caller's
         test of its own arguments against the batch of N samples).  `grouped`: the caller takes grouped convolutions
         (`ops.admit_grouped_per_sample`): their group slices stand among the layers as `ops.GroupSlice` items, and the
-        true depthwise ones come back apart, with their records.  Returns (layers, operands, key, direct), `direct` a list
+        true depthwise ones come back apart, with their records; `norm`: the caller takes normalisation layers
+        (`ops.admit_norm_layers`), which come back among them (`ops.per_sample_route` tells them apart).  Returns (layers, operands, key, direct), `direct` a list
         of (layer, input, grad_output)."""
         have = getattr(self, select)
         assert have, ("Inverse state dict is empty. Did you call 'invert' prior to this?" if select == "inv_state" else
@@ -69,12 +70,12 @@ class LinearisedPredictive:
         if getattr(self, "record", None) is None:
             raise RuntimeError(f"{what}.{call}: no recording hooks (construct with per_sample=True, or go "
                                "through evaluate.glm_predictive)")
-        layers = self._per_sample_layers(f"{what}.{call}", "select other layer types", grouped=grouped)
+        layers = self._per_sample_layers(f"{what}.{call}", "select other layer types", grouped=grouped, norm=norm)
         layers = [l for l in layers if l in have]
         assert layers, f"{select} holds none of the selected layers"
-        direct = [l for l in layers if ops.per_sample_route(l) == "depthwise"]
+        direct = [l for l in layers if ops.per_sample_route(l) in ("depthwise", "norm")]
         direct = [(l, *self._records_of(what, l)) for l in direct]
-        layers = ops.per_sample_items([l for l in layers if ops.per_sample_route(l) != "depthwise"])
+        layers = ops.per_sample_items([l for l in layers if ops.per_sample_route(l) not in ("depthwise", "norm")])
         layout = dict(rows_outer=True, in_place=False) if rotated else {}
         operands = self._per_sample_operands(what, layers, x_side=inputs, **layout) if layers else []
         if check is not None:
@@ -146,7 +147,7 @@ class LinearisedPredictive:
                 raise RuntimeError(f"{what}.functional_variance: out must be a float32 GPU view of length {N}, got "
                                    f"{tuple(out.shape)} {out.dtype} on {out.device}")
         layers, operands, key, direct = self._predictive_operands(what, "functional_variance", inputs, basis is not None,
-                                                                  check, grouped=True)
+                                                                  check, grouped=True, norm=True)
         if inputs:
             xs, ws = self._x_side("variance", layers, operands, basis, weights)
             # a depthwise layer has no packed X to keep: its recorded input is read again; (T, w**2, s) is what it keeps
@@ -159,8 +160,12 @@ class LinearisedPredictive:
         rows = torch.empty(len(layers) + len(direct), out.shape[0], dtype=torch.float32, device=out.device)
         ops.per_sample_quad_reduce([ops.PerSampleQuadJob.of(s, g, x, w, rows[k], first=True)
                                     for k, ((s, _, _), g, x, w) in enumerate(zip(operands, gs, kept["xs"], kept["ws"]))])
-        ops.per_sample_dw_quad_reduce([ops.PerSampleDwJob.of(l, x, g, out=rows[len(layers) + k], T=T, W=w, s=s, first=True)
-                                       for k, ((l, x, g), (T, w, s)) in enumerate(zip(direct, kept["direct"]))])
+        fused = {"depthwise": (ops.PerSampleDwJob, []), "norm": (ops.PerSampleNormJob, [])}
+        for k, ((l, x, g), (T, w, s)) in enumerate(zip(direct, kept["direct"])):
+            job, jobs = fused[ops.per_sample_route(l)]
+            jobs.append(job.of(l, x, g, out=rows[len(layers) + k], T=T, W=w, s=s, first=True))
+        ops.per_sample_dw_quad_reduce(fused["depthwise"][1])
+        ops.per_sample_norm_quad_reduce(fused["norm"][1])
         if kept["low"] is not None:
             # minus the squared norm of every layer's low-rank vector, into the layer's row
             ys = [torch.empty(out.shape[0], ft.shape[1], dtype=torch.float32, device=out.device) for _, _, ft in kept["low"]]
@@ -198,6 +203,10 @@ class LinearisedPredictive:
         terms = self._predictive_terms()
         what, basis, spectrum = terms.name, terms.grid_basis, terms.spectrum
         hypers, points = self._grid_points(what, hypers, terms.separable)
+        if ops.norm_layers_admitted() and getattr(self, "record", None) is not None:
+            # a selected normalisation layer is refused by name before the missing decomposition, which refuses it too
+            self._per_sample_layers(f"{what}.functional_variance_grid", "select other layer types",
+                                    grouped=ops.per_sample_admits_grouped_joint())
         if terms.grid_missing is not None:
             raise RuntimeError(f"{what}.functional_variance_grid: {terms.grid_missing}")
 

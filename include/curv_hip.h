@@ -814,6 +814,86 @@ int curv_persample_dw_quad_reduce(void* stream, const curv_persample_dw_desc* de
                                   size_t workspace_bytes);
 
 /* ------------------------------------------------------------------------------------------------
+ * Curvature of the affine parameters of LayerNorm, GroupNorm and (eval-mode) BatchNorm2d (csrc/norm_factor.hip,
+ * DESIGN.md "K22").  y[c] = gamma_c * xh[c] + beta_c is a depthwise 1x1 convolution of the standardised input
+ *     xh = (x - mu) * rsqrt(var + eps)          (var the biased variance, computed centred: per-lane Welford sums merged
+ *                                                through the set's mean - never E[x^2] - mu^2)
+ * so channel c owns the 1 x n_g row [gamma_c | beta_c], n_g = 1 + has_bias, and everything the depthwise line stores fits.
+ * xh is never written: a statistics pass reads x once and leaves (mu, rstd) per statistics set, a product pass reads x a
+ * second time and g once.  The layer is a logical (N, C, H, W) view of x and of g, float32, each read through four strides
+ * in ELEMENTS inside an extent counted from the pointer, with the rules of curv_persample_dw_desc (strides not negative,
+ * what one sample spans below 2^31 elements, nothing outside the extents is read).  `mode` names the statistics sets:
+ *     CURV_NORM_GROUP     per (n, group) over C / groups channels x H x W          (GroupNorm)
+ *     CURV_NORM_POSITION  per (n, h, w) over the C channels                        (LayerNorm on (N, *, D): C = D,
+ *                                                                                   H = the middle dims, W = 1, x_sc = 1)
+ *     CURV_NORM_GIVEN     `mean` (C) and `var` (C) device arrays                   (BatchNorm2d in eval mode)
+ * Entry points (one descriptor type; each reads its own destination fields):
+ *     curv_kfac_norm_accumulate, side CURV_NORM_SIDE_A:  dst (C, n_g, n_g) (+)= scale * sum_{n,h,w} [xh, 1][xh, 1]^T   reads x
+ *                                side CURV_NORM_SIDE_G:  dst (C, 1, 1)     (+)= scale * sum_{n,h,w} g**2              reads g
+ *     curv_persample_norm_sq_accumulate / curv_persample_norm_quad_reduce: phase 1 writes
+ *         p[n, c, 0] = sum_{h,w} g * xh      p[n, c, 1] = sum_{h,w} g   (has_bias != 0)
+ *     to the workspace; phase 2 is the reduction of curv_persample_dw_sq_accumulate / curv_persample_dw_quad_reduce - the
+ *     same kernels - with their fields (dst, c_rs; T, Wt, s, out, t_cs, t_rs, w_rs, o_stride; alpha, first) and formulas.
+ * Plain fp32 VALU arithmetic, no atomics, sums in a fixed order: lane, wave, workgroup, then slices and samples in index
+ * order.  Lanes run along the contiguous axis (w where the channel stride is not 1, c where it is); how an item is split
+ * follows from its own sizes and strides only, so its bits do not depend on the other items of the call, nor on where
+ * its records lie (an unaligned record takes the same sums through narrower loads).  Up to 16 items per launch.  Enqueues
+ * on `stream` only, never waits on the host, allocates nothing.  An empty call is a no-op.  CURV_ERR_INVALID with the item
+ * named, before anything is launched: sizes below 1, an unknown mode or side, `groups` not dividing C, eps not finite or
+ * <= 0, negative strides, an extent smaller than what sizes and strides address, a NULL record, a NULL mean / var in
+ * given mode, a nonzero `reserved`.
+ * ---------------------------------------------------------------------------------------------- */
+#define CURV_NORM_GROUP 0
+#define CURV_NORM_POSITION 1
+#define CURV_NORM_GIVEN 2
+#define CURV_NORM_SIDE_A 0
+#define CURV_NORM_SIDE_G 1
+#define CURV_NORM_SPLIT_L 1024    /* elements of a plane / statistics set from which the four waves of a workgroup share it */
+#define CURV_NORM_SLICE 32        /* positions per slice where lanes run along c */
+typedef struct curv_norm_desc {
+  const float* x;          /* not read by the G side */
+  const float* g;          /* not read by the A side */
+  long long x_sn, x_sc, x_sh, x_sw, x_elems;
+  long long g_sn, g_sc, g_sh, g_sw, g_elems;
+  int32_t N, C, H, W;
+  int32_t mode;            /* CURV_NORM_* */
+  int32_t groups;          /* CURV_NORM_GROUP: divides C; ignored otherwise */
+  float eps;
+  int32_t has_bias;
+  const float* mean;       /* CURV_NORM_GIVEN */
+  const float* var;
+  int32_t side;            /* curv_kfac_norm_accumulate: CURV_NORM_SIDE_* */
+  int32_t first;
+  float scale;             /* curv_kfac_norm_accumulate */
+  float alpha;             /* the per-sample reductions */
+  int32_t reserved;        /* 0 */
+  int32_t reserved2;       /* 0 */
+  float* dst;              /* factor: (C, n_g, n_g) / (C, 1, 1) contiguous; sq: (C, n_g) with row stride c_rs >= n_g */
+  long long c_rs;
+  const float* T;          /* curv_persample_norm_quad_reduce, as in curv_persample_dw_desc; each may be NULL */
+  const float* Wt;
+  const float* s;
+  float* out;
+  long long t_cs, t_rs, w_rs, o_stride;
+} curv_norm_desc;
+/* Device scratch (bytes, 256-byte aligned regions) for these factors / items; 0 with the error text set for an invalid
+ * descriptor.  Host only; the pointers are not read. */
+size_t curv_kfac_norm_workspace_bytes(const curv_norm_desc* descs, int n);
+size_t curv_persample_norm_workspace_bytes(const curv_norm_desc* descs, int n);
+/* Host only: FLOPs per factor: the statistics pass (6 per element; none on the G side or in given mode) plus the products
+ * (A: 2 + 2 n_g per element, G: 2). */
+int curv_kfac_norm_plan_flops(const curv_norm_desc* descs, int n, long long* out);
+/* Host only: per item the FLOPs (statistics + 2 + 2 n_g per element) and the bytes the algorithm needs, 4 N C H W times
+ * 3 (x twice, g once; given mode: 2); either array may be NULL. */
+int curv_persample_norm_plan_info(const curv_norm_desc* descs, int n, long long* flops, long long* bytes);
+/* The workspace must be 256-byte aligned.  `descs` is a host array; it may be reused as soon as the call returns. */
+int curv_kfac_norm_accumulate(void* stream, const curv_norm_desc* descs, int n, void* workspace, size_t workspace_bytes);
+int curv_persample_norm_sq_accumulate(void* stream, const curv_norm_desc* descs, int n, void* workspace,
+                                      size_t workspace_bytes);
+int curv_persample_norm_quad_reduce(void* stream, const curv_norm_desc* descs, int n, void* workspace,
+                                    size_t workspace_bytes);
+
+/* ------------------------------------------------------------------------------------------------
  * The other reductions of a depthwise layer's products (csrc/persample_dw.hip, DESIGN.md "K15"): what the joint output
  * covariance and the damping grid of the linearised predictive need.  Phase 1 is that of the entry points above, so an
  * item's products p have the same bits; the descriptors below carry the record, geometry and extent fields of
