@@ -13,7 +13,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc")
 INCLUDE = os.path.normpath(os.path.join(_HERE, "..", "include"))
 LIB_PATH = os.path.join(CSRC, "libcurv_hip.so")
-SOURCES = ["api.cpp", "collective.cpp", "elementwise.hip", "syrk.hip", "syrk_flat.hip", "syrk_corr.hip", "syrk_pre.hip", "syrk_small.hip", "group_factor.hip", "kfac_half.hip", "convt_factor.hip", "dilated_factor.hip", "conv3d_factor.hip", "reduce_factor.hip", "persample.hip", "persample_dw.hip", "norm_factor.hip", "logit_mc.hip", "invert.hip", "gemm.hip", "inf.hip", "eigh.hip", "eigh_lowrank.hip", "logdet.hip"]
+SOURCES = ["api.cpp", "collective.cpp", "elementwise.hip", "syrk.hip", "syrk_flat.hip", "syrk_corr.hip", "syrk_pre.hip", "syrk_small.hip", "group_factor.hip", "kfac_half.hip", "convt_factor.hip", "dilated_factor.hip", "conv3d_factor.hip", "reduce_factor.hip", "persample.hip", "persample_dw.hip", "norm_factor.hip", "logit_mc.hip", "head_mc.hip", "invert.hip", "gemm.hip", "inf.hip", "eigh.hip", "eigh_lowrank.hip", "logdet.hip"]
 HIPCC_FLAGS = ["-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC", "-shared", "-Wall",
                "-Wno-unused-function", "-ldl"]
 
@@ -235,6 +235,14 @@ class curv_logit_mc_desc(ctypes.Structure):
                [(k, ctypes.c_int32) for k in ("N", "K", "S", "reserved")]
 
 
+class curv_head_mc_desc(ctypes.Structure):
+    """Mirror of ``curv_head_mc_desc`` in include/curv_hip.h."""
+    _fields_ = [(k, ctypes.c_void_p) for k in ("M", "d2", "mu", "Z", "probs", "draws")] + \
+               [(k, ctypes.c_longlong) for k in ("m_rs", "d_ns", "d_cs", "mu_ns", "z_ns", "z_ss")] + \
+               [("seed", ctypes.c_ulonglong), ("offset", ctypes.c_ulonglong)] + \
+               [(k, ctypes.c_int32) for k in ("N", "K", "S", "m_lower")] + [("reserved", ctypes.c_longlong)]
+
+
 class curv_persample_pack_desc(ctypes.Structure):
     """Mirror of ``curv_persample_pack_desc`` in include/curv_hip.h."""
     _fields_ = _ENDS + _SOURCE + _WINDOW + \
@@ -443,6 +451,9 @@ SIGNATURES = {
     "curv_logit_mc_workspace_bytes": (_sz, [ctypes.POINTER(curv_logit_mc_desc), _i]),
     "curv_logit_mc_plan_flops": (_i, [ctypes.POINTER(curv_logit_mc_desc), _i, ctypes.POINTER(ctypes.c_longlong)]),
     "curv_logit_mc": (_i, [_vp, ctypes.POINTER(curv_logit_mc_desc), _i, _vp, _sz]),
+    "curv_head_mc_workspace_bytes": (_sz, [ctypes.POINTER(curv_head_mc_desc), _i]),
+    "curv_head_mc_plan_flops": (_i, [ctypes.POINTER(curv_head_mc_desc), _i, ctypes.POINTER(ctypes.c_longlong)]),
+    "curv_head_mc": (_i, [_vp, ctypes.POINTER(curv_head_mc_desc), _i, _vp, _sz]),
     "curv_clamp_min0": (_i, [_vp, _vp, _ll]),
     "curv_sqrt_scale": (_i, [_vp, _vp, _d, _vp, _ll]),
     "curv_mul": (_i, [_vp, _vp, _vp, _vp, _ll]),
@@ -460,6 +471,7 @@ REDUCE_PLANE, REDUCE_TOKEN = 0, 1    # CURV_REDUCE_* (curv_reduce_factor_desc.fo
 SMALL_MAX_FLOP = 2.0e9              # CURV_SMALL_MAX_FLOP
 CONVT_MAX_PHASES = 64               # CURV_CONVT_MAX_PHASES
 PERSAMPLE_COV_MAX_OUTPUTS = 16      # CURV_PERSAMPLE_COV_MAX_OUTPUTS
+HEAD_MC_MAX_CLASSES = 1024          # CURV_HEAD_MC_MAX_CLASSES
 PERSAMPLE_GRID_MAX = 16             # CURV_PERSAMPLE_GRID_MAX
 DTYPE_F64 = 3                       # CURV_DTYPE_F64 (curv_logsum_desc.dtype)
 LOGSUM_GRID_MAX, LOGSUM_CHUNK, LOGSUM_ROW_BYTES = 16, 4096, 304     # CURV_LOGSUM_*

@@ -160,6 +160,14 @@ def _check_reduce(model, layer) -> None:
                                   f'reduce build does not take; approximation="expand" takes it')
 
 
+class HeadTerms(NamedTuple):
+    """`Curvature.head_terms`: the logit covariance of input n is ``M diag(d2[n]) M^T``."""
+    M: Optional[Tensor]       # (K, K), or None for the identity
+    lower: bool               # M is lower triangular
+    d2: Tensor                # (N,) - one scalar per input - or (N, K)
+    variance: Tensor          # (N, K): the diagonal of the covariance
+
+
 class _Slot(NamedTuple):
     """One piece of a layer's parameters as a block of columns of its [W | b] matrix (`_slots`)."""
     cols: slice       # the columns of Wm this piece holds
@@ -868,6 +876,56 @@ class Curvature(ABC):
         raise NotImplementedError(f"{type(self).__name__}.functional_covariance: no linearised predictive for this "
                                   "estimator (KFAC, Diagonal and EFB have one)")
 
+    # ------------------------------------------------------------------ last-layer predictive
+    def head_terms(self, layer: Module, features: Tensor) -> "HeadTerms":
+        """The covariance of ALL logits of a `Linear` head under this estimator's posterior over that layer alone, in
+        closed form: the Jacobian of logit c with respect to the head's [W | b] is ``e_c phi~^T`` (phi~ the head's input,
+        with a one appended where it has a bias), so ``Sigma_n = M diag(d2_n) M^T`` with one (K, K) matrix `M` for the
+        whole batch - KFAC: L_G (`lower`), d2 (N,) = ``||L_A^T phi~_n||^2``; EFB: U_G, d2 (N, K); Diagonal: None (the
+        identity), d2 (N, K).  Returns ``HeadTerms(M, lower, d2, variance)`` with `variance` (N, K) the diagonal of
+        Sigma_n: what `evaluate.last_layer_predictive` hands to the probit softmax or, with `M` and `d2`, to
+        `ops.head_mc`.  `features`: the (N, in) input of the head, float32 / bfloat16 / float16 on the GPU (upcast).  No
+        backward pass and no limit on the number of outputs; a few skinny products (`ops.gemm_batched`, `ops.mul`,
+        `ops.mul2d`).  Implemented by KFAC, EFB and Diagonal for a `Linear` layer held in `inv_state`; everything else -
+        INF, BlockDiagonal, a layer-sharded estimator, an attention projection, another layer type, stacked factors -
+        raises NotImplementedError naming the layer and the estimator."""
+        kind = type(self).__name__
+        name = _layer_name(self.model, layer) if isinstance(layer, Module) else repr(layer)
+        what = f"{kind}.head_terms: layer {name}"
+        if type(self)._head_terms is Curvature._head_terms:
+            raise NotImplementedError(f"{what}: no closed-form last-layer predictive for {kind} (KFAC, EFB and Diagonal "
+                                      "have one)")
+        if self.shard is not None and self.shard.world > 1:
+            raise NotImplementedError(f"{what}: not available on a layer-sharded {kind} (world {self.shard.world})")
+        if isinstance(layer, AttentionProjection):
+            raise NotImplementedError(f"{what}: an attention projection of {kind} is no classification head")
+        if not isinstance(layer, torch.nn.Linear):
+            raise NotImplementedError(f"{what}: {kind} takes an nn.Linear head, got {layer.__class__.__name__}")
+        assert self.inv_state, "Inverse state dict is empty. Did you call 'invert' prior to this?"
+        if layer not in self.inv_state:
+            raise NotImplementedError(f"{what}: {kind} holds no inverse state for this layer")
+        n = layer.in_features + (layer.bias is not None)
+        if not isinstance(features, Tensor) or not features.is_cuda:
+            raise RuntimeError(f"curvature_amd runs on MI355X only: {what} got CPU features (no CPU fallback)")
+        if features.dim() != 2 or features.shape[1] != layer.in_features:
+            raise RuntimeError(f"{what}: features must be (N, {layer.in_features}), got {tuple(features.shape)}")
+        phi = torch.empty(features.shape[0], n, dtype=torch.float32, device=features.device)
+        phi[:, :layer.in_features] = features.float()
+        if layer.bias is not None:
+            phi[:, layer.in_features:] = 1.0                 # (Wm order: the bias is the last column)
+        return self._head_terms(layer, phi, what)
+
+    def _head_terms(self, layer, phi: Tensor, what: str) -> "HeadTerms":
+        raise NotImplementedError
+
+    @staticmethod
+    def _row_sums(rows: Tensor, tri: int = ops.TRI_NONE) -> Tensor:
+        """(R,) sums over the columns of the (R, C) view `rows`: a product with a column of ones (`_sum_layers`)."""
+        ones = torch.ones(rows.shape[1], 1, dtype=torch.float32, device=rows.device)
+        out = torch.empty(rows.shape[0], 1, dtype=torch.float32, device=rows.device)
+        ops.gemm_batched([ops.Gemm(rows, ones, out, tri=tri)])
+        return out.view(-1)
+
     def _opt_in_predictive(self):
         """The object that answers the four methods above for an estimator whose linearised predictive is behind a switch
         of `ops` (INF), or None: they then refuse.  Called on the class's method only - an estimator without any attribute
@@ -1223,6 +1281,15 @@ class Diagonal(LinearisedPredictive, Curvature):
         return PredictiveTerms("Diagonal", basis=None, weights=weights, grid_basis=None, spectrum=spectrum, separable=False,
                                direct=lambda layer: (None, self.inv_state[layer], None),
                                direct_grid=lambda layer: (None, None, None, self.state[layer]))
+
+    def _head_terms(self, layer, phi: Tensor, what: str) -> HeadTerms:
+        # sample = Z * inv: Var f_c = sum_j inv[c, j]^2 phi~_j^2, and the logits are independent
+        inv = self.inv_state[layer]
+        if inv.dim() != 2 or inv.shape[1] != phi.shape[1]:
+            raise NotImplementedError(f"{what}: the inverse state {tuple(inv.shape)} is not one (out, in) matrix")
+        d2 = torch.empty(phi.shape[0], inv.shape[0], dtype=torch.float32, device=phi.device)
+        ops.gemm_batched([ops.Gemm(ops.mul(phi, phi), ops.mul(inv, inv).t(), d2)])
+        return HeadTerms(None, False, d2, d2)
 
     def sample(self, layer: Union[Module, str], z: Optional[Tensor] = None) -> Tensor:
         assert self.inv_state, "Inverse state dict is empty. Did you call 'invert' prior to this?"
@@ -1737,6 +1804,20 @@ class KFAC(LinearisedPredictive, Curvature):
         out, total = ops.logsum_grid(segments, len(hypers))
         return out[0::2] + out[1::2], total
 
+    def _head_terms(self, layer, phi: Tensor, what: str) -> HeadTerms:
+        # sample = L_G Z L_A^T: Cov(f_c, f_c') = ||L_A^T phi~||^2 (L_G L_G^T)[c, c']
+        L_A, L_G = self.inv_state[layer]
+        if L_A.dim() != 2 or L_G.dim() != 2:
+            raise NotImplementedError(f"{what}: stacked (grouped) factors {tuple(L_A.shape)}, {tuple(L_G.shape)}")
+        N, dev = phi.shape[0], phi.device
+        Y = torch.empty(N, L_A.shape[1], dtype=torch.float32, device=dev)
+        ops.gemm_batched([ops.Gemm(phi, L_A, Y)])
+        d2 = self._row_sums(ops.mul(Y, Y))
+        g = self._row_sums(ops.mul2d(L_G, L_G), tri=ops.TRI_A_LOWER)       # diag(L_G L_G^T) from the lower triangle
+        variance = torch.empty(N, L_G.shape[0], dtype=torch.float32, device=dev)
+        ops.gemm_batched([ops.Gemm(d2.view(N, 1), g.view(1, -1), variance)])
+        return HeadTerms(L_G, True, d2, variance)
+
     def sample(self, layer: Module, z: Optional[Tensor] = None) -> Tensor:
         """(L_A z L_G^T)^T -> (m, n) (curvatures.py:387-392); `z` (n, m) may be supplied for parity tests."""
         assert self.inv_state, "Inverse state dict is empty. Did you call 'invert' prior to this?"
@@ -2079,6 +2160,21 @@ class EFB(LinearisedPredictive, Curvature):
         basis = lambda layer: self._eigvecs_t(layer)[::-1]     # noqa: E731
         return PredictiveTerms("EFB", basis=basis, weights=lambda layer: self.inv_state[layer], grid_basis=basis,
                                spectrum=lambda layer: (None, None, self.state[layer]), separable=False)
+
+    def _head_terms(self, layer, phi: Tensor, what: str) -> HeadTerms:
+        # sample = U_G (Z * inv) U_A^T: Cov(f) = U_G diag(w) U_G^T, w[a] = sum_b inv[a, b]^2 (U_A^T phi~)_b^2
+        U_A, U_G = self.eigvecs[layer]
+        inv = self.inv_state[layer]
+        if U_A.dim() != 2 or U_G.dim() != 2 or inv.dim() != 2:
+            raise NotImplementedError(f"{what}: stacked (grouped) factors {tuple(U_A.shape)}, {tuple(U_G.shape)}")
+        N, K, dev = phi.shape[0], U_G.shape[0], phi.device
+        Y = torch.empty(N, U_A.shape[1], dtype=torch.float32, device=dev)
+        ops.gemm_batched([ops.Gemm(phi, U_A, Y)])
+        d2 = torch.empty(N, K, dtype=torch.float32, device=dev)
+        ops.gemm_batched([ops.Gemm(ops.mul(Y, Y), ops.mul(inv, inv).t(), d2)])
+        variance = torch.empty(N, K, dtype=torch.float32, device=dev)
+        ops.gemm_batched([ops.Gemm(d2, ops.mul2d(U_G, U_G).t(), variance)])
+        return HeadTerms(U_G, False, d2, variance)
 
     def sample(self, layer: Module, z: Optional[Tensor] = None) -> Tensor:
         """(U_A (z * inv^T) U_G^T)^T = U_G (z^T * inv) U_A^T -> (m, n) (curvatures.py:453-460)."""

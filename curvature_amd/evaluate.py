@@ -445,6 +445,113 @@ def glm_predictive_mc(model: torch.nn.Module, estimator, images: torch.Tensor, o
     return (logits, covariance, probs, draws) if return_draws else (logits, covariance, probs)
 
 
+def _default_head(estimator):
+    """The last `nn.Linear` of the estimator's `inv_state` in ``model.modules()`` order, or None."""
+    held = [layer for layer in estimator.model.modules()
+            if isinstance(layer, torch.nn.Linear) and layer in estimator.inv_state]
+    return held[-1] if held else None
+
+
+def last_layer_predictive(model: torch.nn.Module, estimator, images: torch.Tensor, *, head=None,
+                          predictive: str = "probit", samples: int = 256, noise=None, return_draws: bool = False):
+    """The Laplace predictive of one batch under the posterior over the LAST `Linear` layer alone, for every class from one
+    forward pass: ``(logits, variance, probs)``, each (N, K), plus `draws` (N, samples, K) with ``return_draws=True``
+    (``predictive="mc"`` only; None otherwise).
+
+    The Jacobian of logit c with respect to the head's [W | b] is ``e_c phi~^T``, so the covariance of all K logits is
+    closed form in what the estimator holds (`Curvature.head_terms`: KFAC, EFB, Diagonal): no backward pass per output as
+    in `glm_predictive`, and no limit of `ops.PERSAMPLE_COV_MAX_OUTPUTS` outputs as in `glm_predictive_mc`.
+    ``predictive="probit"``: ``softmax(logits / sqrt(1 + pi / 8 * variance))``.  ``"mc"``: the mean softmax over `samples`
+    draws ``f ~ N(logits, M diag(d2) M^T)`` in one `ops.head_mc` call over all classes (K at most
+    `ops.HEAD_MC_MAX_CLASSES`: ValueError above).  `noise`: explicit (N, samples, K) float32 GPU z; otherwise the
+    estimator's own noise stream (`noise_seed` pins it, `noise_offset` advances by ``N * samples * ceil(K / 4)``).
+
+    The model is put into ``eval()`` mode and run once under ``torch.no_grad()``; a forward pre-hook and a forward hook on
+    `head` (default: the last `nn.Linear` of ``estimator.inv_state`` in ``modules()`` order) capture its input and output
+    and are removed on the way out.  Recording hooks, parameters and ``.grad`` are not touched.  RuntimeError, naming the
+    layer, if the head did not run, if its input is not 2-D (a head applied per token), or if the model's output is not
+    the head's output (a model that post-processes its logits).  GPU only."""
+    what = "last_layer_predictive"
+    samples = int(samples)
+    if predictive not in ("probit", "mc"):
+        raise ValueError(f"{what}: predictive must be 'probit' or 'mc', got {predictive!r}")
+    if samples < 1:
+        raise ValueError(f"{what}: samples must be at least 1, got {samples}")
+    first_param = next(model.parameters())
+    if not first_param.is_cuda or not images.is_cuda:
+        raise RuntimeError(f"curvature_amd runs on MI355X only: {what} got a CPU model or batch (no CPU fallback)")
+    if head is None:
+        assert estimator.inv_state, "Inverse state dict is empty. Did you call 'invert' prior to this?"
+        head = _default_head(estimator)
+        if head is None:
+            raise RuntimeError(f"{what}: the estimator holds no nn.Linear layer in inv_state; pass head=")
+    names = {m: n for n, m in estimator.model.named_modules()}
+    names.update({m: n for n, m in model.named_modules()})
+    name = names.get(head, repr(head))
+    if not isinstance(head, torch.nn.Module):
+        estimator.head_terms(head, None)                       # (an attention projection: the estimator's refusal)
+    model.eval()
+    seen = {}
+    hooks = [head.register_forward_pre_hook(lambda module, args: seen.__setitem__("input", args[0])),
+             head.register_forward_hook(lambda module, args, output: seen.__setitem__("output", output))]
+    try:
+        with torch.no_grad():
+            output = model(images)
+    finally:
+        for hook in hooks:
+            hook.remove()
+    if "output" not in seen:
+        raise RuntimeError(f"{what}: the head '{name}' did not run in the model's forward pass")
+    features, logits = seen["input"], seen["output"]
+    if not isinstance(features, torch.Tensor) or features.dim() != 2:
+        shape = tuple(features.shape) if isinstance(features, torch.Tensor) else type(features).__name__
+        raise RuntimeError(f"{what}: the input of the head '{name}' must be (N, features), got {shape} (a head applied "
+                           "per token is not supported)")
+    if not isinstance(output, torch.Tensor) or output.shape != logits.shape or not torch.equal(output, logits):
+        raise RuntimeError(f"{what}: the model's output is not the output of the head '{name}' (a model that "
+                           "post-processes its logits is not supported)")
+    terms = estimator.head_terms(head, features)
+    N, K = logits.shape
+    if predictive == "probit":
+        return (logits, terms.variance, _probit(logits, terms.variance)) + ((None,) if return_draws else ())
+    if K > ops.HEAD_MC_MAX_CLASSES:
+        raise ValueError(f"{what}: {K} classes; predictive='mc' takes at most ops.HEAD_MC_MAX_CLASSES = "
+                         f"{ops.HEAD_MC_MAX_CLASSES}: use predictive='probit'")
+    seed = offset = 0
+    if noise is None:
+        if getattr(estimator, "_noise_counter", None) is not None:
+            raise RuntimeError(f"{what}: the noise position is kept on the host only; switch the estimator's "
+                               "device noise counter off (use_device_noise_counter(False)) or pass noise=")
+        seed, offset = estimator._seed(), estimator.noise_offset
+        estimator.noise_offset += N * samples * ((K + 3) // 4)
+    probs = torch.empty(N, K, dtype=torch.float32, device=logits.device)
+    draws = torch.empty(N, samples, K, dtype=torch.float32, device=logits.device) if return_draws else None
+    ops.head_mc([ops.HeadMCJob(terms.M, terms.d2, logits.float().contiguous(), samples, lower=terms.lower, noise=noise,
+                               probs=probs, draws=draws, seed=seed, offset=offset)])
+    return (logits, terms.variance, probs, draws) if return_draws else (logits, terms.variance, probs)
+
+
+def eval_last_layer(model: torch.nn.Module, dataset: Iterable, estimator, predictive: str = "probit", samples: int = 256,
+                    head=None, device=None):
+    """`last_layer_predictive` over `dataset`: ``(predictions, labels)`` as numpy arrays - the loop of `eval_glm` at one
+    forward pass per batch for any number of classes.  ``predictive="mc"`` draws from the estimator's noise stream.  The
+    probabilities stay on the device and cross to the host once at the end."""
+    if predictive not in ("probit", "mc"):
+        raise ValueError(f"eval_last_layer: predictive must be 'probit' or 'mc', got {predictive!r}")
+    if device is None:
+        device = next(model.parameters()).device
+    probs, labels_all = [], []
+    for images, labels in dataset:
+        images = images.to(device, non_blocking=True)
+        probs.append(last_layer_predictive(model, estimator, images, head=head, predictive=predictive,
+                                           samples=samples)[2])
+        if labels is not None:
+            labels_all.append(labels.cpu() if isinstance(labels, torch.Tensor) else torch.as_tensor(labels))
+    predictions = torch.cat(probs) if probs else torch.empty(0, device=device)
+    labels = torch.cat(labels_all) if labels_all else torch.empty(0, dtype=torch.long)
+    return predictions.cpu().numpy(), labels.numpy()
+
+
 def eval_glm(model: torch.nn.Module, dataset: Iterable, estimator, predictive: str = "probit", outputs=None,
              samples: int = 256, device=None):
     """The GLM predictive over `dataset`: ``(predictions, labels)`` as numpy arrays, the counterpart of `eval_bnn` without

@@ -1995,6 +1995,101 @@ def logit_mc(jobs: Sequence[LogitMCJob]) -> None:
                "curv_logit_mc")
 
 
+HEAD_MC_MAX_CLASSES = _lib.HEAD_MC_MAX_CLASSES
+
+
+class HeadMCJob:
+    """probs[n, c] = mean over `samples` draws of softmax(f)[c] with f = mu[n] + M (sqrt(max(d2[n], 0)) * z)
+    (curv_head_mc): `M` a (K, K) float32 view with unit column stride (with `lower` only its lower triangle is read) or
+    None (identity: no product), `d2` an (N,) or (N, K) view with unit last stride, `mu` an (N, K) view with unit last
+    stride, K at most `HEAD_MC_MAX_CLASSES`; `noise` an (N, S, K) view of explicit z with unit last stride or None (then the
+    library's Philox stream at `seed`, `offset`; the call consumes ``N * S * ceil(K / 4)`` counters).  Outputs, contiguous,
+    one of them may be None: `probs` (N, K), `draws` (N, S, K).  `d2` and `mu` may also be None with explicit `N`, `K`
+    (plan queries, which only ask whether `M` is None)."""
+    __slots__ = ("M", "d2", "mu", "noise", "probs", "draws", "lower", "N", "K", "S", "seed", "offset")
+
+    def __init__(self, M, d2, mu, samples, *, lower=False, noise=None, probs=None, draws=None, seed: int = 0,
+                 offset: int = 0, N: Optional[int] = None, K: Optional[int] = None):
+        self.M, self.d2, self.mu, self.noise, self.probs, self.draws = M, d2, mu, noise, probs, draws
+        self.lower = bool(lower)
+        self.N = int(mu.shape[0] if N is None else N)
+        self.K = int(mu.shape[-1] if K is None else K)
+        self.S, self.seed, self.offset = int(samples), int(seed), int(offset)
+
+
+def _head_mc_descs(jobs: Sequence[HeadMCJob], check_tensors: bool = True):
+    name = "head_mc"
+    arr = (_lib.curv_head_mc_desc * len(jobs))()
+    for d, j in zip(arr, jobs):
+        N, K, S = j.N, j.K, j.S
+        d.N, d.K, d.S, d.m_lower = N, K, S, int(j.lower)
+        d.m_rs, d.mu_ns, d.d_cs, d.d_ns = K, K, 1, K
+        d.seed, d.offset = j.seed & (2 ** 64 - 1), j.offset & (2 ** 64 - 1)
+        if not check_tensors:
+            d.probs = 256                # (an item without outputs is refused; the host queries never read the address)
+            d.M = 256 if j.M is not None else None
+            continue
+        floats = (j.M, j.d2, j.mu, j.noise, j.probs, j.draws)
+        for t in floats:
+            if t is not None and not t.is_cuda:
+                raise RuntimeError("curvature_amd runs on MI355X only: got a CPU tensor (no CPU fallback)")
+        for t in floats:
+            if t is not None and t.dtype != torch.float32:
+                raise RuntimeError(f"curvature_amd expects float32 tensors, got {t.dtype}")
+        if j.mu.dim() != 2 or tuple(j.mu.shape) != (N, K) or (K > 1 and j.mu.stride(1) != 1):
+            raise RuntimeError(f"{name}: mu must be an ({N},{K}) view with unit last stride, got {tuple(j.mu.shape)}")
+        # (the stride of a dimension of size 1 says nothing: take the smallest the library allows)
+        d.mu_ns = j.mu.stride(0) if N > 1 else K
+        d.mu = j.mu.data_ptr()
+        if j.M is not None:
+            if j.M.dim() != 2 or tuple(j.M.shape) != (K, K) or (K > 1 and j.M.stride(1) != 1):
+                raise RuntimeError(f"{name}: M must be a ({K},{K}) view with unit column stride, got {tuple(j.M.shape)}")
+            d.m_rs = j.M.stride(0) if K > 1 else K
+            d.M = j.M.data_ptr()
+        if j.d2.dim() == 1 and tuple(j.d2.shape) == (N,):
+            d.d_cs, d.d_ns = 0, (j.d2.stride(0) if N > 1 else 1)
+        elif j.d2.dim() == 2 and tuple(j.d2.shape) == (N, K) and (K == 1 or j.d2.stride(1) == 1):
+            d.d_cs, d.d_ns = 1, (j.d2.stride(0) if N > 1 else K)
+        else:
+            raise RuntimeError(f"{name}: d2 must be an ({N},) or ({N},{K}) view with unit last stride, got "
+                               f"{tuple(j.d2.shape)}")
+        d.d2 = j.d2.data_ptr()
+        if j.noise is not None:
+            if j.noise.dim() != 3 or tuple(j.noise.shape) != (N, S, K) or (K > 1 and j.noise.stride(2) != 1):
+                raise RuntimeError(f"{name}: noise must be an ({N},{S},{K}) view with unit last stride, got "
+                                   f"{tuple(j.noise.shape)}")
+            d.z_ss = j.noise.stride(1) if S > 1 else K
+            d.z_ns = j.noise.stride(0) if N > 1 else (S - 1) * d.z_ss + K
+            d.Z = j.noise.data_ptr()
+        for what, t, shape in (("probs", j.probs, (N, K)), ("draws", j.draws, (N, S, K))):
+            if t is None:
+                continue
+            if tuple(t.shape) != shape or not t.is_contiguous():
+                raise RuntimeError(f"{name}: {what} must be a contiguous {shape} tensor, got {tuple(t.shape)} {t.dtype}")
+            setattr(d, what, t.data_ptr())
+    return arr
+
+
+def head_mc_plan_flops(jobs: Sequence[HeadMCJob]) -> List[int]:
+    """Multiply-add FLOPs (2 per multiply-add) of the MFMA products the plan executes per job (curv_head_mc_plan_flops,
+    host only): 0 for a job without `M`."""
+    if not jobs:
+        return []
+    return _plan_flops("curv_head_mc_plan_flops", _head_mc_descs(jobs, check_tensors=False), len(jobs))
+
+
+def head_mc(jobs: Sequence[HeadMCJob]) -> None:
+    """curv_head_mc over any number of items, on the current stream; the partial sums of items whose draws are cut into
+    chunks from `workspace` (an item of one chunk per input needs none)."""
+    if not jobs:
+        return
+    L, arr, n = _lib.lib(), _head_mc_descs(jobs), len(jobs)
+    need = L.curv_head_mc_workspace_bytes(arr, n)        # 0: nothing needed - or refused, which the call itself reports
+    ws = workspace(need, jobs[0].mu.device, "persample") if need else None
+    _lib.check(L.curv_head_mc(_lib.stream_ptr(), arr, n, ws.data_ptr() if need else None, ws.numel() if need else 0),
+               "curv_head_mc")
+
+
 class PerSampleDwJob:
     """The per-sample products of a true depthwise convolution (csrc/persample_dw.hip): `x` the (N, C, H, W) input and `g`
     the (N, C, Ho, Wo) grad_output, float32 GPU tensors of any strides (not negative), with the layer's `kernel`, `stride`,

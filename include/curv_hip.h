@@ -1218,6 +1218,68 @@ int curv_logit_mc_plan_flops(const curv_logit_mc_desc* descs, int n, long long* 
 /* One launch per batch of up to 16 items, a second where an item has chunks.  The workspace must be 256-byte aligned.
  * `descs` is a host array; it may be reused as soon as the call returns. */
 int curv_logit_mc(void* stream, const curv_logit_mc_desc* descs, int n, void* workspace, size_t workspace_bytes);
+
+/* ------------------------------------------------------------------------------------------------
+ * Monte-Carlo softmax of the LAST-LAYER Laplace predictive over all classes (csrc/head_mc.hip).  The Jacobian of logit c
+ * with respect to the head's [W | b] is e_c phi~^T, so for KFAC, EFB and Diagonal the covariance of the K logits of input
+ * n is Sigma_n = M diag(d2_n) M^T with ONE K x K matrix M for the whole batch (KFAC: L_G, lower triangular, d2_n a scalar;
+ * EFB: U_G; Diagonal: none) and a non-negative vector d2_n per input.  For each of N inputs
+ *     f_s = mu_n + M (sqrt(max(d2_n, 0)) o z_{n,s})  (s < S, z ~ N(0, I_K))
+ *     probs[n*K + c] = (1/S) sum_s softmax(f_s)[c]                                  c < K
+ * in one kernel on v_mfma_f32_32x32x2_f32 (exact fp32): the (N, S, K) draws stay in accumulators unless `draws` asks for
+ * them.  1 <= K <= CURV_HEAD_MC_MAX_CLASSES - no backward pass and no cap of 16 outputs as in curv_logit_mc.
+ *
+ * Inputs.  M: K x K floats, row stride m_rs >= K, unit column stride, no alignment beyond 4 bytes; NULL means the
+ * identity (no product at all).  m_lower != 0: entries with column > row are neither read nor multiplied (they may hold
+ * anything, NaN included), and the k-range of a block of 32 rows stops at its last row, so a triangular M costs about half
+ * the products.  d2: the value of class c of input n at d2[n*d_ns + c*d_cs], d_cs 0 (one scalar per input) or 1, d_ns at
+ * least 1 resp. K; negative values count as 0, and a row of zeros gives probs = softmax(mu_n).  mu: K floats per input,
+ * mu_ns >= K apart.  Z: explicit standard-normal noise, z_{n,s}[c] at Z[n*z_ns + s*z_ss + c] (z_ss >= K,
+ * z_ns >= (S - 1) z_ss + K), or NULL: the generator of curv_randn keyed by `seed`, with the convention of curv_logit_mc -
+ * Kq = ceil(K / 4), draw s of input n takes the counters offset + (n S + s) Kq + q, q < Kq, and value e of counter q is
+ * z[4 q + e] - so a call with Z = NULL has the bits of a call whose Z is the (N, S, 4 Kq) buffer curv_randn(seed, offset)
+ * wrote.  The position of the stream is the host-side `offset` only (the caller advances it by N S Kq).
+ *
+ * Outputs, either may be NULL but not both: probs (N x K, contiguous), draws (N x S x K, contiguous: the f_s).
+ * `reserved` must be 0.
+ *
+ * Plan.  The draws of an input are cut into tiles of 32 and the T = ceil(S / 32) tiles into chunks of
+ * ceil(T / ceil(256 / N)) tiles, one workgroup each, so that few inputs still fill the chip; with more than one chunk the
+ * partial sums (K floats per input and chunk) go to the caller's workspace and a second launch adds them in chunk order.
+ * An item whose inputs have one chunk needs no workspace: curv_head_mc_workspace_bytes is then 0 WITHOUT an error text,
+ * and `workspace` may be NULL.  The plan of an item follows from its own N, K and S only.
+ *
+ * The rules of the library: fp32 sums in a fixed order (lane, wave, workgroup, then chunks in chunk order), no atomics, so
+ * the bits of an item do not depend on the other items of the call nor on the run; nothing non-finite from finite input.
+ * Enqueues on `stream` only, never waits on the host, allocates nothing.  An empty call is a no-op; every item is checked
+ * before anything is launched, and invalid sizes or strides (K outside 1 .. CURV_HEAD_MC_MAX_CLASSES, N or S below 1, S
+ * above 2^30, N S above 2^40, m_rs < K, d_cs neither 0 nor 1, d_ns too small, mu_ns < K, bad Z strides, both outputs NULL,
+ * reserved != 0) return CURV_ERR_INVALID with the item named.
+ * ---------------------------------------------------------------------------------------------- */
+#define CURV_HEAD_MC_MAX_CLASSES 1024
+typedef struct curv_head_mc_desc {
+  const float* M;          /* may be NULL: identity */
+  const float* d2;
+  const float* mu;
+  const float* Z;          /* may be NULL */
+  float* probs;            /* may be NULL */
+  float* draws;            /* may be NULL */
+  long long m_rs, d_ns, d_cs, mu_ns, z_ns, z_ss;
+  unsigned long long seed, offset;
+  int32_t N, K, S;
+  int32_t m_lower;
+  long long reserved;
+} curv_head_mc_desc;
+/* Device scratch for these items (bytes: see Plan; 256-byte aligned per item); 0 with the error text set (naming the
+ * item) for invalid input - and 0 without one where no item needs scratch.  Host only. */
+size_t curv_head_mc_workspace_bytes(const curv_head_mc_desc* descs, int n);
+/* Host only: the multiply-add FLOPs of the MFMA products the plan executes per item: whole 32 x 32 x 32 steps,
+ * 2 N 32 T 32 32 (steps), steps = sum over the row blocks g < ceil(K / 32) of the k-steps of 32 the block takes
+ * (ceil(K / 32), with m_lower min(ceil(K / 32), g + 1)); 0 without M. */
+int curv_head_mc_plan_flops(const curv_head_mc_desc* descs, int n, long long* out);
+/* One launch per batch of up to 16 items, a second where an item has chunks.  The workspace must be 256-byte aligned.
+ * `descs` is a host array; it may be reused as soon as the call returns. */
+int curv_head_mc(void* stream, const curv_head_mc_desc* descs, int n, void* workspace, size_t workspace_bytes);
 /* v = max(v, 0) in place      curvatures.py:523 */
 int curv_clamp_min0(void* stream, float* v, long long count);
 /* out = sqrt(s*v)             curvatures.py:525 */

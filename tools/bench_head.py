@@ -1,0 +1,130 @@
+#!/usr/bin/env python
+"""Last-layer Laplace predictive at the ResNet-50 head: time of `Curvature.head_terms`, `ops.head_mc` (curv_head_mc) and
+the whole `evaluate.last_layer_predictive`, beside the torch expression for the same draws and the per-sample line they
+replace, in one run.
+
+    python tools/bench_head.py [--reps 9] [--json FILE]
+
+  * shape: N = 32 inputs, K = 1000 classes, in = 2048 (+ 1 for the bias), S = 256 draws; the model is the head alone,
+    ``Flatten -> Linear(2048, 1000)``, under a KFAC estimator after one update and an inversion;
+  * head_terms: the skinny products that give d2 and the variance;
+  * head_mc lower / dense: one `ops.head_mc` call with the library's own noise (Z = NULL), M = L_G with and without
+    `lower`; its `plan_flops` over the time as a fraction of the 157.3 TF fp32 MFMA peak;
+  * last_layer_predictive: forward pass, head_terms and head_mc ("mc") resp. the probit softmax;
+  * torch: ``randn((N, S, K))``, scale, ``matmul`` with M^T, ``softmax``, ``mean`` - the (N, S, K) tensor is written
+    and read several times;
+  * glm_predictive with ``outputs=range(16)``: one backward pass per class - the cost per 16 classes of the per-sample
+    line;
+  * the relative Frobenius difference of kernel and torch expression on the SAME explicit noise (not timed).
+HIP events around each call, the candidates alternating, median of `--reps` after two warm-up calls each.
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from curvature_amd import ops  # noqa: E402
+from curvature_amd.curvatures import KFAC  # noqa: E402
+from curvature_amd.evaluate import glm_predictive, last_layer_predictive  # noqa: E402
+
+N, K, IN, S = 32, 1000, 2048, 256
+PEAK_TF = 157.3
+
+
+def once(fn):
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    fn()
+    e1.record()
+    e1.synchronize()
+    return e0.elapsed_time(e1)
+
+
+def torch_expression(M, d2, mu, z=None):
+    if z is None:
+        z = torch.randn(N, S, K, device=mu.device)
+    f = mu[:, None, :] + torch.matmul(z * torch.sqrt(d2)[:, None, None], M.t())
+    return torch.softmax(f, dim=2).mean(dim=1)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=9)
+    ap.add_argument("--json", default=None, help="write the result as one JSON line to this file")
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_head: needs the GPU (nothing is measured without one)")
+    dev = torch.device("cuda:0")
+    torch.manual_seed(0)
+    model = torch.nn.Sequential(torch.nn.Flatten(), torch.nn.Linear(IN, K)).to(dev)
+    x = torch.randn(N, IN, device=dev)
+    labels = torch.randint(0, K, (N,), device=dev)
+    est = KFAC(model, "Linear")
+    torch.nn.functional.cross_entropy(model(x), labels).backward()
+    est.update(N)
+    model.zero_grad()
+    est.invert(add=1.0, multiply=float(N))
+    head = model[1]
+    terms = est.head_terms(head, x)
+    L_G = torch.tril(terms.M).contiguous()
+    with torch.no_grad():
+        mu = model(x).float().contiguous()
+    probs = torch.empty(N, K, device=dev)
+    state = {"offset": 0}
+
+    def head_mc(lower, z=None):
+        ops.head_mc([ops.HeadMCJob(L_G, terms.d2, mu, S, lower=lower, noise=z, probs=probs, seed=1,
+                                   offset=state["offset"])])
+        state["offset"] += N * S * ((K + 3) // 4)
+        return probs
+
+    z = torch.randn(N, S, K, device=dev)
+    want = torch_expression(L_G, terms.d2, mu, z).double()
+    row = dict(N=N, K=K, features=IN + 1, S=S)
+    for lower in (True, False):
+        mine = head_mc(lower, z).double()
+        row["rel_difference_to_torch_" + ("lower" if lower else "dense")] = \
+            float(torch.linalg.norm(mine - want) / torch.linalg.norm(want))
+    del z, want
+
+    candidates = {
+        "head_terms": lambda: est.head_terms(head, x),
+        "head_mc_lower": lambda: head_mc(True),
+        "head_mc_dense": lambda: head_mc(False),
+        "last_layer_mc": lambda: last_layer_predictive(model, est, x, predictive="mc", samples=S),
+        "last_layer_probit": lambda: last_layer_predictive(model, est, x),
+        "torch_expression": lambda: torch_expression(L_G, terms.d2, mu),
+        "glm_predictive_16_classes": lambda: glm_predictive(model, est, x, outputs=range(16)),
+    }
+    for _ in range(2):
+        for fn in candidates.values():
+            fn()
+    torch.cuda.synchronize()
+    times = {name: [] for name in candidates}
+    for _ in range(args.reps):
+        for name, fn in candidates.items():
+            times[name].append(once(fn))
+    for name, ts in times.items():
+        row[name + "_ms"] = statistics.median(ts)
+        row[name + "_ms_min"], row[name + "_ms_max"] = min(ts), max(ts)
+    for lower in (True, False):
+        tag = "lower" if lower else "dense"
+        flops = ops.head_mc_plan_flops([ops.HeadMCJob(True, None, None, S, lower=lower, N=N, K=K)])[0]
+        row[f"plan_gflop_{tag}"] = flops / 1e9
+        row[f"mfma_peak_fraction_{tag}"] = flops / (row[f"head_mc_{tag}_ms"] * 1e-3) / (PEAK_TF * 1e12)
+    row["torch_over_head_mc_lower"] = row["torch_expression_ms"] / row["head_mc_lower_ms"]
+    row["glm_1000_classes_over_last_layer_probit"] = \
+        row["glm_predictive_16_classes_ms"] * (K / 16) / row["last_layer_probit_ms"]
+    row["device"] = torch.cuda.get_device_name(0)
+    print(json.dumps(row), flush=True)
+    if args.json:
+        with open(args.json, "w") as fh:
+            fh.write(json.dumps(row) + "\n")
+
+
+if __name__ == "__main__":
+    main()
