@@ -13,7 +13,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc")
 INCLUDE = os.path.normpath(os.path.join(_HERE, "..", "include"))
 LIB_PATH = os.path.join(CSRC, "libcurv_hip.so")
-SOURCES = ["api.cpp", "collective.cpp", "elementwise.hip", "syrk.hip", "syrk_flat.hip", "syrk_corr.hip", "syrk_pre.hip", "syrk_small.hip", "group_factor.hip", "kfac_half.hip", "convt_factor.hip", "dilated_factor.hip", "conv3d_factor.hip", "reduce_factor.hip", "persample.hip", "persample_dw.hip", "norm_factor.hip", "logit_mc.hip", "head_mc.hip", "invert.hip", "gemm.hip", "inf.hip", "eigh.hip", "eigh_lowrank.hip", "logdet.hip"]
+SOURCES = ["api.cpp", "collective.cpp", "elementwise.hip", "syrk.hip", "syrk_flat.hip", "syrk_corr.hip", "syrk_pre.hip", "syrk_small.hip", "group_factor.hip", "kfac_half.hip", "convt_factor.hip", "dilated_factor.hip", "conv3d_factor.hip", "reduce_factor.hip", "persample.hip", "persample_dw.hip", "norm_factor.hip", "logit_mc.hip", "head_mc.hip", "head_grid.hip", "invert.hip", "gemm.hip", "inf.hip", "eigh.hip", "eigh_lowrank.hip", "logdet.hip"]
 HIPCC_FLAGS = ["-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC", "-shared", "-Wall",
                "-Wno-unused-function", "-ldl"]
 
@@ -243,6 +243,13 @@ class curv_head_mc_desc(ctypes.Structure):
                [(k, ctypes.c_int32) for k in ("N", "K", "S", "m_lower")] + [("reserved", ctypes.c_longlong)]
 
 
+class curv_head_grid_desc(ctypes.Structure):
+    """Mirror of ``curv_head_grid_desc`` in include/curv_hip.h (`shift` and `gain` are host arrays of H floats)."""
+    _fields_ = [(k, ctypes.c_void_p) for k in ("Y", "u", "v", "T", "out")] + \
+               [("shift", ctypes.POINTER(ctypes.c_float)), ("gain", ctypes.POINTER(ctypes.c_float))] + \
+               [(k, ctypes.c_longlong) for k in ("y_rs", "t_rs")] + [(k, ctypes.c_int32) for k in ("N", "K", "n", "H")]
+
+
 class curv_persample_pack_desc(ctypes.Structure):
     """Mirror of ``curv_persample_pack_desc`` in include/curv_hip.h."""
     _fields_ = _ENDS + _SOURCE + _WINDOW + \
@@ -454,6 +461,9 @@ SIGNATURES = {
     "curv_head_mc_workspace_bytes": (_sz, [ctypes.POINTER(curv_head_mc_desc), _i]),
     "curv_head_mc_plan_flops": (_i, [ctypes.POINTER(curv_head_mc_desc), _i, ctypes.POINTER(ctypes.c_longlong)]),
     "curv_head_mc": (_i, [_vp, ctypes.POINTER(curv_head_mc_desc), _i, _vp, _sz]),
+    "curv_head_grid_workspace_bytes": (_sz, [ctypes.POINTER(curv_head_grid_desc), _i]),
+    "curv_head_grid_plan_flops": (_i, [ctypes.POINTER(curv_head_grid_desc), _i, ctypes.POINTER(ctypes.c_longlong)]),
+    "curv_head_grid": (_i, [_vp, ctypes.POINTER(curv_head_grid_desc), _i, _vp, _sz]),
     "curv_clamp_min0": (_i, [_vp, _vp, _ll]),
     "curv_sqrt_scale": (_i, [_vp, _vp, _d, _vp, _ll]),
     "curv_mul": (_i, [_vp, _vp, _vp, _vp, _ll]),
@@ -472,6 +482,7 @@ SMALL_MAX_FLOP = 2.0e9              # CURV_SMALL_MAX_FLOP
 CONVT_MAX_PHASES = 64               # CURV_CONVT_MAX_PHASES
 PERSAMPLE_COV_MAX_OUTPUTS = 16      # CURV_PERSAMPLE_COV_MAX_OUTPUTS
 HEAD_MC_MAX_CLASSES = 1024          # CURV_HEAD_MC_MAX_CLASSES
+HEAD_GRID_MAX = 16                  # CURV_HEAD_GRID_MAX
 PERSAMPLE_GRID_MAX = 16             # CURV_PERSAMPLE_GRID_MAX
 DTYPE_F64 = 3                       # CURV_DTYPE_F64 (curv_logsum_desc.dtype)
 LOGSUM_GRID_MAX, LOGSUM_CHUNK, LOGSUM_ROW_BYTES = 16, 4096, 304     # CURV_LOGSUM_*

@@ -168,6 +168,13 @@ class HeadTerms(NamedTuple):
     variance: Tensor          # (N, K): the diagonal of the covariance
 
 
+class HeadGridTerms(NamedTuple):
+    """`Curvature.head_terms_grid`: the logit covariance of input n under pair h is ``M diag(d2[h, n]) M^T``."""
+    M: Optional[Tensor]       # (K, K), dense, or None for the identity
+    d2: Tensor                # (H, N, K)
+    variance: Tensor          # (H, N, K): the diagonals of the covariances
+
+
 class _Slot(NamedTuple):
     """One piece of a layer's parameters as a block of columns of its [W | b] matrix (`_slots`)."""
     cols: slice       # the columns of Wm this piece holds
@@ -889,9 +896,16 @@ class Curvature(ABC):
         `ops.mul2d`).  Implemented by KFAC, EFB and Diagonal for a `Linear` layer held in `inv_state`; everything else -
         INF, BlockDiagonal, a layer-sharded estimator, an attention projection, another layer type, stacked factors -
         raises NotImplementedError naming the layer and the estimator."""
+        what, phi = self._head_input("head_terms", layer, features, "inv_state")
+        return self._head_terms(layer, phi, what)
+
+    def _head_input(self, method: str, layer, features, held: str, check=None):
+        """(what, phi~): the refusals `head_terms` and `head_terms_grid` share, decided before the device is touched, then
+        the head's input as float32 with a one appended where it has a bias.  `held`: the dict that must hold the layer;
+        ``check(layer, what)``: the estimator's own refusals, made before the features are looked at."""
         kind = type(self).__name__
         name = _layer_name(self.model, layer) if isinstance(layer, Module) else repr(layer)
-        what = f"{kind}.head_terms: layer {name}"
+        what = f"{kind}.{method}: layer {name}"
         if type(self)._head_terms is Curvature._head_terms:
             raise NotImplementedError(f"{what}: no closed-form last-layer predictive for {kind} (KFAC, EFB and Diagonal "
                                       "have one)")
@@ -901,9 +915,16 @@ class Curvature(ABC):
             raise NotImplementedError(f"{what}: an attention projection of {kind} is no classification head")
         if not isinstance(layer, torch.nn.Linear):
             raise NotImplementedError(f"{what}: {kind} takes an nn.Linear head, got {layer.__class__.__name__}")
-        assert self.inv_state, "Inverse state dict is empty. Did you call 'invert' prior to this?"
-        if layer not in self.inv_state:
-            raise NotImplementedError(f"{what}: {kind} holds no inverse state for this layer")
+        if held == "inv_state":
+            assert self.inv_state, "Inverse state dict is empty. Did you call 'invert' prior to this?"
+            if layer not in self.inv_state:
+                raise NotImplementedError(f"{what}: {kind} holds no inverse state for this layer")
+        else:
+            assert self.state, "State dict is empty. Did you call 'update' prior to this?"
+            if layer not in self.state:
+                raise NotImplementedError(f"{what}: {kind} holds no state for this layer")
+        if check is not None:
+            check(layer, what)
         n = layer.in_features + (layer.bias is not None)
         if not isinstance(features, Tensor) or not features.is_cuda:
             raise RuntimeError(f"curvature_amd runs on MI355X only: {what} got CPU features (no CPU fallback)")
@@ -913,9 +934,52 @@ class Curvature(ABC):
         phi[:, :layer.in_features] = features.float()
         if layer.bias is not None:
             phi[:, layer.in_features:] = 1.0                 # (Wm order: the bias is the last column)
-        return self._head_terms(layer, phi, what)
+        return what, phi
 
     def _head_terms(self, layer, phi: Tensor, what: str) -> "HeadTerms":
+        raise NotImplementedError
+
+    def head_terms_grid(self, layer: Module, features: Tensor, hypers) -> "HeadGridTerms":
+        """`head_terms` for a whole list of damping pairs ``hypers = [(add, multiply), ...]`` at once and without an
+        inversion: ``HeadGridTerms(M, d2, variance)`` with ONE (K, K) matrix `M` for every pair and input
+        (KFAC, EFB: U_G, dense; Diagonal: None, the identity), `d2` (H, N, K) and `variance` (H, N, K) - the logit
+        covariance of input n under pair h is ``M diag(d2[h, n]) M^T``, what ``invert(*hypers[h])`` followed by
+        `head_terms` stands for.  In the posterior's eigenbasis the damping enters only the weights of the squared rotated
+        features, so the rotation ``Y = Phi~ U_A`` and one read of the spectrum serve every pair (`ops.head_grid`):
+
+            KFAC      d2[h, n, j] = (1 / s_h) / (lambda_G,j + sqrt(rho_h)) * sum_i Y[n, i]^2 / (lambda_A,i + sqrt(rho_h))
+            EFB       d2[h, n, j] = (1 / s_h) sum_i Y[n, i]^2 / (state[j, i] + rho_h)
+            Diagonal  the same with Y = Phi~
+
+        with ``rho_h = n_h / s_h`` and (n_h, s_h) the pair resolved for this layer as `invert` resolves it (per-layer lists
+        work) - the conventions of `functional_variance_grid`, KFAC with the reference's factored damping.  KFAC needs
+        `decompose()` after the last `update()` (RuntimeError otherwise).  The layer must be in `state`; `inv_state` is
+        neither needed nor touched.  More than `ops.HEAD_GRID_MAX` pairs run as chunks over the same `Y`, bit-equal to the
+        concatenation.  `variance` is one `ops.gemm_batched` of the (H N, K) view of `d2` against ``(M o M)^T``.  `features`
+        and the refusals as for `head_terms`; every pair finite and > 0 (ValueError naming the pair)."""
+        hypers = self._evidence_pairs("head_terms_grid", hypers)
+        what, phi = self._head_input("head_terms_grid", layer, features, "state", self._head_grid_check)
+        M, Y, (u, v, T), separable = self._head_grid_terms(layer, phi)
+        points = dict(self._resolved(hypers))[layer]
+        rhos = [n / s for n, s in points]
+        shifts, gains = [math.sqrt(r) for r in rhos] if separable else rhos, [1.0 / s for _, s in points]
+        H, N, K = len(hypers), phi.shape[0], layer.out_features
+        d2 = torch.empty(H, N, K, dtype=torch.float32, device=phi.device)
+        for h0 in range(0, H, ops.HEAD_GRID_MAX):
+            h1 = min(h0 + ops.HEAD_GRID_MAX, H)
+            ops.head_grid([ops.HeadGridJob(Y, u, v, T, d2[h0:h1], shifts[h0:h1], gains[h0:h1])])
+        if M is None:
+            return HeadGridTerms(None, d2, d2)
+        variance = torch.empty(H, N, K, dtype=torch.float32, device=phi.device)
+        ops.gemm_batched([ops.Gemm(d2.view(H * N, K), ops.mul2d(M, M).t(), variance.view(H * N, K))])
+        return HeadGridTerms(M, d2, variance)
+
+    def _head_grid_check(self, layer, what: str) -> None:
+        """What `head_terms_grid` needs of this layer's `state` beyond its presence, or the refusal."""
+        raise NotImplementedError
+
+    def _head_grid_terms(self, layer, phi: Tensor):
+        """(M, Y, (u, v, T), separable) of `head_terms_grid`, after `_head_grid_check`."""
         raise NotImplementedError
 
     @staticmethod
@@ -1290,6 +1354,14 @@ class Diagonal(LinearisedPredictive, Curvature):
         d2 = torch.empty(phi.shape[0], inv.shape[0], dtype=torch.float32, device=phi.device)
         ops.gemm_batched([ops.Gemm(ops.mul(phi, phi), ops.mul(inv, inv).t(), d2)])
         return HeadTerms(None, False, d2, d2)
+
+    def _head_grid_check(self, layer, what: str) -> None:
+        state = self.state[layer]
+        if state.dim() != 2 or state.shape[1] != layer.in_features + (layer.bias is not None):
+            raise NotImplementedError(f"{what}: the state {tuple(state.shape)} is not one (out, in) matrix")
+
+    def _head_grid_terms(self, layer, phi: Tensor):
+        return None, phi, (None, None, self.state[layer]), False
 
     def sample(self, layer: Union[Module, str], z: Optional[Tensor] = None) -> Tensor:
         assert self.inv_state, "Inverse state dict is empty. Did you call 'invert' prior to this?"
@@ -1818,6 +1890,22 @@ class KFAC(LinearisedPredictive, Curvature):
         ops.gemm_batched([ops.Gemm(d2.view(N, 1), g.view(1, -1), variance)])
         return HeadTerms(L_G, True, d2, variance)
 
+    def _head_grid_check(self, layer, what: str) -> None:
+        A, G = self.state[layer]
+        if A.dim() != 2 or G.dim() != 2:
+            raise NotImplementedError(f"{what}: stacked (grouped) factors {tuple(A.shape)}, {tuple(G.shape)}")
+        kept = getattr(self, "_decomposition", None)
+        if kept is None or layer not in kept:
+            raise RuntimeError(f"{what}: no eigendecomposition of the current factors: call decompose() after the last "
+                               "update()")
+
+    def _head_grid_terms(self, layer, phi: Tensor):
+        # (sqrt(s) F + sqrt(n) I)^-1 = U diag(1 / (sqrt(s) (lambda + sqrt(n / s)))) U^T on both sides: Sigma = U_G diag(d2) U_G^T
+        U_Gt, U_At, lam_G, lam_A = self._decomposition[layer][:4]
+        Y = torch.empty(phi.shape[0], U_At.shape[0], dtype=torch.float32, device=phi.device)
+        ops.gemm_batched([ops.Gemm(phi, U_At.t(), Y)])
+        return U_Gt.t().contiguous(), Y, (lam_G, lam_A, None), True     # (head_mc wants M with unit column stride)
+
     def sample(self, layer: Module, z: Optional[Tensor] = None) -> Tensor:
         """(L_A z L_G^T)^T -> (m, n) (curvatures.py:387-392); `z` (n, m) may be supplied for parity tests."""
         assert self.inv_state, "Inverse state dict is empty. Did you call 'invert' prior to this?"
@@ -2175,6 +2263,18 @@ class EFB(LinearisedPredictive, Curvature):
         variance = torch.empty(N, K, dtype=torch.float32, device=dev)
         ops.gemm_batched([ops.Gemm(d2, ops.mul2d(U_G, U_G).t(), variance)])
         return HeadTerms(U_G, False, d2, variance)
+
+    def _head_grid_check(self, layer, what: str) -> None:
+        U_A, U_G = self.eigvecs[layer]
+        if U_A.dim() != 2 or U_G.dim() != 2 or self.state[layer].dim() != 2:
+            raise NotImplementedError(f"{what}: stacked (grouped) factors {tuple(U_A.shape)}, {tuple(U_G.shape)}")
+
+    def _head_grid_terms(self, layer, phi: Tensor):
+        U_A, U_G = self.eigvecs[layer]
+        state = self.state[layer]
+        Y = torch.empty(phi.shape[0], U_A.shape[1], dtype=torch.float32, device=phi.device)
+        ops.gemm_batched([ops.Gemm(phi, U_A, Y)])
+        return U_G, Y, (None, None, state), False
 
     def sample(self, layer: Module, z: Optional[Tensor] = None) -> Tensor:
         """(U_A (z * inv^T) U_G^T)^T = U_G (z^T * inv) U_A^T -> (m, n) (curvatures.py:453-460)."""

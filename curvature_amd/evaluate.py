@@ -269,20 +269,26 @@ def tune_glm(model: torch.nn.Module, dataset: Iterable, estimator, hypers, outpu
     once), `best` the argmin of `nll` (the first on a tie).  Nothing is called on the estimator afterwards: the caller
     goes on with ``estimator.invert(*hypers[best])``."""
     hypers = list(hypers)
+    return _tune("tune_glm", model, dataset, len(hypers),
+                 lambda images: glm_predictive_grid(model, estimator, images, hypers, outputs=outputs)[2])
+
+
+def _tune(what: str, model: torch.nn.Module, dataset: Iterable, pairs: int, probs_of) -> dict:
+    """``dict(nll, accuracy, best)`` of `tune_glm` / `tune_last_layer` from ``probs_of(images)`` -> (pairs, N, classes)."""
     device = next(model.parameters()).device
-    nll = torch.zeros(len(hypers), dtype=torch.float64, device=device)
-    hits = torch.zeros(len(hypers), dtype=torch.float64, device=device)
+    nll = torch.zeros(pairs, dtype=torch.float64, device=device)
+    hits = torch.zeros(pairs, dtype=torch.float64, device=device)
     count = 0
     for images, labels in dataset:
         images = images.to(device, non_blocking=True)
         labels = torch.as_tensor(labels).to(device, non_blocking=True).long()
-        probs = glm_predictive_grid(model, estimator, images, hypers, outputs=outputs)[2]
-        index = labels.view(1, -1, 1).expand(len(hypers), -1, 1)
+        probs = probs_of(images)
+        index = labels.view(1, -1, 1).expand(pairs, -1, 1)
         nll -= torch.log(probs.gather(2, index).squeeze(2).double()).sum(1)
         hits += (probs.argmax(2) == labels.view(1, -1)).double().sum(1)
         count += int(labels.numel())
     if count == 0:
-        raise ValueError("tune_glm: the dataset is empty")
+        raise ValueError(f"{what}: the dataset is empty")
     nll, accuracy = (nll / count).cpu(), (hits / count).cpu()
     return dict(nll=nll, accuracy=accuracy, best=int(torch.argmin(nll)))
 
@@ -452,6 +458,71 @@ def _default_head(estimator):
     return held[-1] if held else None
 
 
+def _head_pass(what: str, model: torch.nn.Module, estimator, images: torch.Tensor, head, predictive: str, samples: int,
+               held: str, refuse):
+    """(head, features, logits) of one forward pass for `last_layer_predictive` (`held` "inv_state") and
+    `last_layer_predictive_grid` ("state"): the checks that need no device, the default head - the last `nn.Linear` of
+    the estimator's `held` dict in ``modules()`` order -, the two hooks on it, and what the captured tensors must be.
+    ``refuse(layer)`` raises the estimator's refusal of a head that is no module."""
+    if predictive not in ("probit", "mc"):
+        raise ValueError(f"{what}: predictive must be 'probit' or 'mc', got {predictive!r}")
+    if samples < 1:
+        raise ValueError(f"{what}: samples must be at least 1, got {samples}")
+    first_param = next(model.parameters())
+    if not first_param.is_cuda or not images.is_cuda:
+        raise RuntimeError(f"curvature_amd runs on MI355X only: {what} got a CPU model or batch (no CPU fallback)")
+    if head is None:
+        if held == "inv_state":
+            assert estimator.inv_state, "Inverse state dict is empty. Did you call 'invert' prior to this?"
+            head = _default_head(estimator)
+        else:
+            assert estimator.state, "State dict is empty. Did you call 'update' prior to this?"
+            linear = [layer for layer in estimator.model.modules()
+                      if isinstance(layer, torch.nn.Linear) and layer in estimator.state]
+            head = linear[-1] if linear else None
+        if head is None:
+            raise RuntimeError(f"{what}: the estimator holds no nn.Linear layer in {held}; pass head=")
+    names = {m: n for n, m in estimator.model.named_modules()}
+    names.update({m: n for n, m in model.named_modules()})
+    name = names.get(head, repr(head))
+    if not isinstance(head, torch.nn.Module):
+        refuse(head)                                           # (an attention projection: the estimator's refusal)
+    model.eval()
+    seen = {}
+    hooks = [head.register_forward_pre_hook(lambda module, args: seen.__setitem__("input", args[0])),
+             head.register_forward_hook(lambda module, args, output: seen.__setitem__("output", output))]
+    try:
+        with torch.no_grad():
+            output = model(images)
+    finally:
+        for hook in hooks:
+            hook.remove()
+    if "output" not in seen:
+        raise RuntimeError(f"{what}: the head '{name}' did not run in the model's forward pass")
+    features, logits = seen["input"], seen["output"]
+    if not isinstance(features, torch.Tensor) or features.dim() != 2:
+        shape = tuple(features.shape) if isinstance(features, torch.Tensor) else type(features).__name__
+        raise RuntimeError(f"{what}: the input of the head '{name}' must be (N, features), got {shape} (a head applied "
+                           "per token is not supported)")
+    if not isinstance(output, torch.Tensor) or output.shape != logits.shape or not torch.equal(output, logits):
+        raise RuntimeError(f"{what}: the model's output is not the output of the head '{name}' (a model that "
+                           "post-processes its logits is not supported)")
+    return head, features, logits
+
+
+def _head_noise(what: str, estimator, noise, counters: int):
+    """(seed, offset) of one `ops.head_mc` call: zeros with explicit `noise`, otherwise the estimator's stream, advanced
+    by `counters`."""
+    if noise is not None:
+        return 0, 0
+    if getattr(estimator, "_noise_counter", None) is not None:
+        raise RuntimeError(f"{what}: the noise position is kept on the host only; switch the estimator's "
+                           "device noise counter off (use_device_noise_counter(False)) or pass noise=")
+    seed, offset = estimator._seed(), estimator.noise_offset
+    estimator.noise_offset += counters
+    return seed, offset
+
+
 def last_layer_predictive(model: torch.nn.Module, estimator, images: torch.Tensor, *, head=None,
                           predictive: str = "probit", samples: int = 256, noise=None, return_draws: bool = False):
     """The Laplace predictive of one batch under the posterior over the LAST `Linear` layer alone, for every class from one
@@ -473,43 +544,8 @@ def last_layer_predictive(model: torch.nn.Module, estimator, images: torch.Tenso
     the head's output (a model that post-processes its logits).  GPU only."""
     what = "last_layer_predictive"
     samples = int(samples)
-    if predictive not in ("probit", "mc"):
-        raise ValueError(f"{what}: predictive must be 'probit' or 'mc', got {predictive!r}")
-    if samples < 1:
-        raise ValueError(f"{what}: samples must be at least 1, got {samples}")
-    first_param = next(model.parameters())
-    if not first_param.is_cuda or not images.is_cuda:
-        raise RuntimeError(f"curvature_amd runs on MI355X only: {what} got a CPU model or batch (no CPU fallback)")
-    if head is None:
-        assert estimator.inv_state, "Inverse state dict is empty. Did you call 'invert' prior to this?"
-        head = _default_head(estimator)
-        if head is None:
-            raise RuntimeError(f"{what}: the estimator holds no nn.Linear layer in inv_state; pass head=")
-    names = {m: n for n, m in estimator.model.named_modules()}
-    names.update({m: n for n, m in model.named_modules()})
-    name = names.get(head, repr(head))
-    if not isinstance(head, torch.nn.Module):
-        estimator.head_terms(head, None)                       # (an attention projection: the estimator's refusal)
-    model.eval()
-    seen = {}
-    hooks = [head.register_forward_pre_hook(lambda module, args: seen.__setitem__("input", args[0])),
-             head.register_forward_hook(lambda module, args, output: seen.__setitem__("output", output))]
-    try:
-        with torch.no_grad():
-            output = model(images)
-    finally:
-        for hook in hooks:
-            hook.remove()
-    if "output" not in seen:
-        raise RuntimeError(f"{what}: the head '{name}' did not run in the model's forward pass")
-    features, logits = seen["input"], seen["output"]
-    if not isinstance(features, torch.Tensor) or features.dim() != 2:
-        shape = tuple(features.shape) if isinstance(features, torch.Tensor) else type(features).__name__
-        raise RuntimeError(f"{what}: the input of the head '{name}' must be (N, features), got {shape} (a head applied "
-                           "per token is not supported)")
-    if not isinstance(output, torch.Tensor) or output.shape != logits.shape or not torch.equal(output, logits):
-        raise RuntimeError(f"{what}: the model's output is not the output of the head '{name}' (a model that "
-                           "post-processes its logits is not supported)")
+    head, features, logits = _head_pass(what, model, estimator, images, head, predictive, samples, "inv_state",
+                                        lambda layer: estimator.head_terms(layer, None))
     terms = estimator.head_terms(head, features)
     N, K = logits.shape
     if predictive == "probit":
@@ -517,18 +553,61 @@ def last_layer_predictive(model: torch.nn.Module, estimator, images: torch.Tenso
     if K > ops.HEAD_MC_MAX_CLASSES:
         raise ValueError(f"{what}: {K} classes; predictive='mc' takes at most ops.HEAD_MC_MAX_CLASSES = "
                          f"{ops.HEAD_MC_MAX_CLASSES}: use predictive='probit'")
-    seed = offset = 0
-    if noise is None:
-        if getattr(estimator, "_noise_counter", None) is not None:
-            raise RuntimeError(f"{what}: the noise position is kept on the host only; switch the estimator's "
-                               "device noise counter off (use_device_noise_counter(False)) or pass noise=")
-        seed, offset = estimator._seed(), estimator.noise_offset
-        estimator.noise_offset += N * samples * ((K + 3) // 4)
+    seed, offset = _head_noise(what, estimator, noise, N * samples * ((K + 3) // 4))
     probs = torch.empty(N, K, dtype=torch.float32, device=logits.device)
     draws = torch.empty(N, samples, K, dtype=torch.float32, device=logits.device) if return_draws else None
     ops.head_mc([ops.HeadMCJob(terms.M, terms.d2, logits.float().contiguous(), samples, lower=terms.lower, noise=noise,
                                probs=probs, draws=draws, seed=seed, offset=offset)])
     return (logits, terms.variance, probs, draws) if return_draws else (logits, terms.variance, probs)
+
+
+def last_layer_predictive_grid(model: torch.nn.Module, estimator, images: torch.Tensor, hypers, *, head=None,
+                               predictive: str = "probit", samples: int = 256, noise=None):
+    """`last_layer_predictive` for a whole list of damping pairs ``hypers = [(add, multiply), ...]`` at once, without an
+    inversion: ``(logits, variance, probs)`` with `logits` (N, K) and `variance`, `probs` of shape ``(len(hypers), N, K)`` -
+    slice h is what ``estimator.invert(*hypers[h])`` followed by `last_layer_predictive` stands for.  One forward pass,
+    one rotation of the features and one read of the spectrum serve every pair (`Curvature.head_terms_grid`: KFAC after
+    `KFAC.decompose()`, EFB, Diagonal); the estimator's `inv_state` is neither needed nor touched, so the default head is
+    the last `nn.Linear` of ``estimator.state`` in ``modules()`` order.  ``predictive="probit"``: the probit softmax,
+    broadcast over the pairs.  ``"mc"``: ONE `ops.head_mc` call with one item per pair; the items share the matrix, the
+    logits and the noise - explicit `noise` (N, samples, K) or one stretch of the estimator's stream, `noise_offset`
+    advancing once by ``N * samples * ceil(K / 4)`` - so the pairs are compared on the same draws (common random
+    numbers).  Model mode, hooks, refusals and the cap of `ops.HEAD_MC_MAX_CLASSES` classes as in
+    `last_layer_predictive`.  GPU only."""
+    what = "last_layer_predictive_grid"
+    samples = int(samples)
+    hypers = estimator._evidence_pairs("head_terms_grid", hypers)
+    head, features, logits = _head_pass(what, model, estimator, images, head, predictive, samples, "state",
+                                        lambda layer: estimator.head_terms_grid(layer, None, hypers))
+    terms = estimator.head_terms_grid(head, features, hypers)
+    N, K = logits.shape
+    if predictive == "probit":
+        return logits, terms.variance, _probit(logits, terms.variance)         # (N, K) against (H, N, K)
+    if K > ops.HEAD_MC_MAX_CLASSES:
+        raise ValueError(f"{what}: {K} classes; predictive='mc' takes at most ops.HEAD_MC_MAX_CLASSES = "
+                         f"{ops.HEAD_MC_MAX_CLASSES}: use predictive='probit'")
+    seed, offset = _head_noise(what, estimator, noise, N * samples * ((K + 3) // 4))
+    probs = torch.empty(len(hypers), N, K, dtype=torch.float32, device=logits.device)
+    mu = logits.float().contiguous()
+    ops.head_mc([ops.HeadMCJob(terms.M, terms.d2[h], mu, samples, noise=noise, probs=probs[h], seed=seed, offset=offset)
+                 for h in range(len(hypers))])
+    return logits, terms.variance, probs
+
+
+def tune_last_layer(model: torch.nn.Module, dataset: Iterable, estimator, hypers, *, predictive: str = "probit",
+                    samples: int = 256, head=None):
+    """`tune_glm` for the last-layer predictive: the damping pair of ``hypers = [(add, multiply), ...]`` under which
+    `last_layer_predictive` explains the labelled `dataset` best, from one `last_layer_predictive_grid` per batch for all
+    of them - no inversion and one forward pass per batch, where the reference's ``scripts/hyper.py`` loop pays one
+    `invert` and one pass over the data per candidate.  Returns ``dict(nll=(H,), accuracy=(H,), best=int)`` computed as
+    `tune_glm` computes them.  ``predictive="mc"`` draws from the estimator's noise stream, every pair of a batch on the
+    same draws.  The caller goes on with ``estimator.invert(*hypers[best])``."""
+    if predictive not in ("probit", "mc"):
+        raise ValueError(f"tune_last_layer: predictive must be 'probit' or 'mc', got {predictive!r}")
+    hypers = estimator._evidence_pairs("head_terms_grid", hypers)
+    return _tune("tune_last_layer", model, dataset, len(hypers),
+                 lambda images: last_layer_predictive_grid(model, estimator, images, hypers, head=head,
+                                                           predictive=predictive, samples=samples)[2])
 
 
 def eval_last_layer(model: torch.nn.Module, dataset: Iterable, estimator, predictive: str = "probit", samples: int = 256,

@@ -2090,6 +2090,115 @@ def head_mc(jobs: Sequence[HeadMCJob]) -> None:
                "curv_head_mc")
 
 
+HEAD_GRID_MAX = _lib.HEAD_GRID_MAX
+
+
+class HeadGridJob:
+    """out[h, r, j] = gain[h] * r_h[j] * sum_i Y[r, i]**2 / (T[j, i] + shift[h]) for the H pairs ``(shift[h], gain[h])``
+    (at most `HEAD_GRID_MAX`; curv_head_grid): the `d2` of `HeadMCJob` for a whole grid of damping pairs.  `Y` an (N, n)
+    float32 view with unit last stride.  The spectrum is dense - `T` a (K, n) view with unit column stride, r_h = 1 - or
+    separable - `u` (K,) and `v` (n,) contiguous, ``T[j, i] = v[i]`` and ``r_h[j] = 1 / (u[j] + shift[h])``: give `u` and
+    `v`, or `T`, and None for the other.  `shift` (finite, > 0) and `gain` (finite) are sequences of H Python floats; they
+    travel with the kernel arguments.  `out` a contiguous (H, N, K) float32 tensor, overwritten.  `Y` and `out` may also be
+    None with explicit `N`, `K`, `n`, and then the spectrum too with `separable` saying which form is meant (plan queries,
+    which read no tensor)."""
+    __slots__ = ("Y", "u", "v", "T", "out", "shift", "gain", "N", "K", "n", "separable")
+
+    def __init__(self, Y, u, v, T, out, shift, gain, *, N: Optional[int] = None, K: Optional[int] = None,
+                 n: Optional[int] = None, separable: Optional[bool] = None):
+        self.Y, self.u, self.v, self.T, self.out = Y, u, v, T, out
+        self.separable = None if separable is None else bool(separable)
+        self.shift, self.gain = [float(x) for x in shift], [float(x) for x in gain]
+        self.N = int(Y.shape[0] if N is None else N)
+        self.n = int(Y.shape[-1] if n is None else n)
+        spectrum = T if T is not None else u                 # (neither: refused with the item named when the job is used)
+        self.K = int((spectrum.shape[0] if spectrum is not None else out.shape[-1]) if K is None else K)
+
+
+def _head_grid_descs(jobs: Sequence[HeadGridJob], check_tensors: bool = True):
+    name = "head_grid"
+    arr = (_lib.curv_head_grid_desc * len(jobs))()
+    keep = []                                        # the host tables the descriptors point to
+    forms = []
+    for k, j in enumerate(jobs):                     # the pairs and the form of every job, before any tensor is looked at
+        H = len(j.shift)
+        if not 1 <= H <= HEAD_GRID_MAX or len(j.gain) != H:
+            raise ValueError(f"{name}: item {k}: {H} shifts and {len(j.gain)} gains; a job takes 1 to {HEAD_GRID_MAX} "
+                             "pairs, as many gains as shifts")
+        for h, (s, g) in enumerate(zip(j.shift, j.gain)):
+            if not (s > 0 and math.isfinite(s) and math.isfinite(g)):
+                raise ValueError(f"{name}: item {k}: pair {h}: shift {s} must be finite and > 0, gain {g} finite")
+        separable = j.separable if not check_tensors else None
+        if separable is None:
+            if (j.u is None) != (j.v is None) or (j.T is None) == (j.u is None):
+                raise RuntimeError(f"{name}: item {k}: give the spectrum as u and v (separable) or as T (dense), not both")
+            separable = j.T is None
+        forms.append(separable)
+    for k, (d, j, separable) in enumerate(zip(arr, jobs, forms)):
+        H, N, K, n = len(j.shift), j.N, j.K, j.n
+        d.N, d.K, d.n, d.H = N, K, n, H
+        d.y_rs, d.t_rs = n, n
+        tables = ((ctypes.c_float * H)(*j.shift), (ctypes.c_float * H)(*j.gain))
+        keep.append(tables)
+        d.shift, d.gain = ctypes.cast(tables[0], ctypes.POINTER(ctypes.c_float)), ctypes.cast(tables[1], ctypes.POINTER(ctypes.c_float))
+        if not check_tensors:
+            if separable:                         # (the host queries ask which pointers are null and read none)
+                d.u = d.v = 256
+            else:
+                d.T = 256
+            continue
+        floats = (j.Y, j.u, j.v, j.T, j.out)
+        for t in floats:
+            if t is not None and not t.is_cuda:
+                raise RuntimeError("curvature_amd runs on MI355X only: got a CPU tensor (no CPU fallback)")
+        for t in floats:
+            if t is not None and t.dtype != torch.float32:
+                raise RuntimeError(f"curvature_amd expects float32 tensors, got {t.dtype}")
+        if j.Y.dim() != 2 or tuple(j.Y.shape) != (N, n) or (n > 1 and j.Y.stride(1) != 1):
+            raise RuntimeError(f"{name}: item {k}: Y must be an ({N},{n}) view with unit last stride, got "
+                               f"{tuple(j.Y.shape)}")
+        # (the stride of a dimension of size 1 says nothing: take the smallest the library allows)
+        d.y_rs = j.Y.stride(0) if N > 1 else n
+        d.Y = j.Y.data_ptr()
+        if separable:
+            for what, t, rows in (("u", j.u, K), ("v", j.v, n)):
+                if t.dim() != 1 or t.shape[0] != rows or not t.is_contiguous():
+                    raise RuntimeError(f"{name}: item {k}: {what} must be a contiguous vector of {rows} values, got "
+                                       f"{tuple(t.shape)}")
+            d.u, d.v = j.u.data_ptr(), j.v.data_ptr()
+        else:
+            if j.T.dim() != 2 or tuple(j.T.shape) != (K, n) or (n > 1 and j.T.stride(1) != 1):
+                raise RuntimeError(f"{name}: item {k}: T must be a ({K},{n}) view with unit column stride, got "
+                                   f"{tuple(j.T.shape)}")
+            d.t_rs = j.T.stride(0) if K > 1 else n
+            d.T = j.T.data_ptr()
+        if tuple(j.out.shape) != (H, N, K) or not j.out.is_contiguous():
+            raise RuntimeError(f"{name}: item {k}: out must be a contiguous ({H},{N},{K}) tensor, got {tuple(j.out.shape)}")
+        d.out = j.out.data_ptr()
+    arr._tables = keep
+    return arr
+
+
+def head_grid_plan_flops(jobs: Sequence[HeadGridJob]) -> List[int]:
+    """Multiply-add FLOPs (2 per multiply-add) of the MFMA products the plan executes per job FOR ONE PAIR
+    (curv_head_grid_plan_flops, host only): whatever H; a call runs them once per pair.  0 for a separable job."""
+    if not jobs:
+        return []
+    return _plan_flops("curv_head_grid_plan_flops", _head_grid_descs(jobs, check_tensors=False), len(jobs))
+
+
+def head_grid(jobs: Sequence[HeadGridJob]) -> None:
+    """curv_head_grid over any number of items, on the current stream; the partial sums of dense items whose sum over i
+    is cut into chunks from `workspace` (an item of one chunk, and a separable one, needs none)."""
+    if not jobs:
+        return
+    L, arr, n = _lib.lib(), _head_grid_descs(jobs), len(jobs)
+    need = L.curv_head_grid_workspace_bytes(arr, n)      # 0: nothing needed - or refused, which the call itself reports
+    ws = workspace(need, jobs[0].out.device, "persample") if need else None
+    _lib.check(L.curv_head_grid(_lib.stream_ptr(), arr, n, ws.data_ptr() if need else None, ws.numel() if need else 0),
+               "curv_head_grid")
+
+
 class PerSampleDwJob:
     """The per-sample products of a true depthwise convolution (csrc/persample_dw.hip): `x` the (N, C, H, W) input and `g`
     the (N, C, Ho, Wo) grad_output, float32 GPU tensors of any strides (not negative), with the layer's `kernel`, `stride`,

@@ -1280,6 +1280,65 @@ int curv_head_mc_plan_flops(const curv_head_mc_desc* descs, int n, long long* ou
 /* One launch per batch of up to 16 items, a second where an item has chunks.  The workspace must be 256-byte aligned.
  * `descs` is a host array; it may be reused as soon as the call returns. */
 int curv_head_mc(void* stream, const curv_head_mc_desc* descs, int n, void* workspace, size_t workspace_bytes);
+
+/* ------------------------------------------------------------------------------------------------
+ * The d2 of the last-layer Laplace predictive for a whole grid of damping pairs in one pass (csrc/head_grid.hip;
+ * DESIGN.md "K24"): for h < H, input r < N and class j < K
+ *     out[(h*N + r)*K + j] = gain[h] * r_h[j] * sum_{i < n} Y[r*y_rs + i]**2 / (T[j][i] + shift[h])
+ *     dense     (T given, u and v NULL):   T[j][i] = T[j*t_rs + i],  r_h = 1                       T: K x n, t_rs >= n
+ *     separable (u and v given, T NULL):   T[j][i] = v[i],  r_h[j] = 1 / (u[j] + shift[h])         u: K floats, v: n floats
+ * With Y the head's input [phi | 1] in the posterior's eigenbasis the damping (add, multiply) enters the logit
+ * covariance M diag(d2) M^T only through these weights, with rho = add / multiply and gain = 1 / multiply:
+ *     KFAC      Y = Phi~ U_A,  u = eig(G), v = eig(A),  shift = sqrt(rho)     (M = U_G)
+ *     EFB       Y = Phi~ U_A,  T = state,               shift = rho           (M = U_G)
+ *     Diagonal  Y = Phi~,      T = state,               shift = rho           (M = identity)
+ * so slice h is the d2 of curv_head_mc for what the inversion with pair h stands for, and one call serves every pair.
+ * 1 <= H <= CURV_HEAD_GRID_MAX.  `shift` and `gain` are HOST arrays of H floats; they are copied into the kernel
+ * arguments during the call.  Every shift must be finite and > 0, every gain finite; the spectrum entries are read as
+ * they are (expected >= 0: an entry + shift of 0 divides by zero).  Y: N x n floats, row stride y_rs >= n, unit column
+ * stride; T likewise; no alignment beyond 4 bytes, and nothing outside the N x n, K x n, K and n entries is read.  out is
+ * contiguous (H, N, K); every entry is overwritten.  N, K, n >= 1 with N n, K n and CURV_HEAD_GRID_MAX N K below 2^31.
+ * The reciprocals are formed with IEEE (correctly rounded) divisions.
+ *
+ * Dense: a product on v_mfma_f32_32x32x2_f32 (exact fp32) whose B operand is generated - a lane holds a value of T in the
+ * B layout, forms the reciprocals of its pairs in registers and feeds one MFMA per pair against the shared A operand
+ * Y**2 - so T is read once per two pairs and no (H, K, n) weight tensor exists.  Plan: out is cut into 32 x 32 blocks,
+ * B = ceil(N / 32) ceil(K / 32) of them, and the S = ceil(n / 32) steps of i into chunks of
+ * max(4, ceil(S / ceil(256 / B))) steps so that few blocks still fill the chip; with more than one chunk the partial sums go to the caller's workspace
+ * (CURV_HEAD_GRID_MAX N K floats per chunk, whatever H) and a second launch adds them in chunk order.  An item of one
+ * chunk, and every separable item (one wave per (h, r): the sum over i once, then K stores), needs no workspace:
+ * curv_head_grid_workspace_bytes is then 0 WITHOUT an error text, and `workspace` may be NULL.  The plan of an item
+ * follows from its own N, K and n only - not from H nor from the other items.
+ *
+ * The rules of the library: fp32 sums in a fixed order (lane, wave, workgroup, then chunks in chunk order), no atomics;
+ * pair h is computed from shift[h] and gain[h] alone, so slice h has the same bits whatever other pairs or items share
+ * the call.  Enqueues on `stream` only, never waits on the host, allocates nothing.  An empty call is a no-op; every item
+ * is checked before anything is launched, and invalid sizes, strides, H, shift, gain or operands (u / v and T both given,
+ * or neither) return CURV_ERR_INVALID with the item named.
+ * ---------------------------------------------------------------------------------------------- */
+#define CURV_HEAD_GRID_MAX 16
+typedef struct curv_head_grid_desc {
+  const float* Y;
+  const float* u;          /* separable form: K eigenvalues of the G side ... */
+  const float* v;          /* ... and n of the A side */
+  const float* T;          /* dense form: K x n */
+  float* out;
+  const float* shift;      /* host, H floats */
+  const float* gain;       /* host, H floats */
+  long long y_rs, t_rs;
+  int32_t N, K, n;
+  int32_t H;
+} curv_head_grid_desc;
+/* Device scratch for these items (bytes: see Plan; 256-byte aligned per item); 0 with the error text set (naming the
+ * item) for invalid input - and 0 without one where no item needs scratch.  Host only. */
+size_t curv_head_grid_workspace_bytes(const curv_head_grid_desc* descs, int n);
+/* Host only: the multiply-add FLOPs of the MFMA products the plan executes per item FOR ONE PAIR - whole 32 x 32 x 32
+ * steps, 2 32 32 32 B S, at least the algorithmic 2 N K n; a call runs them once per pair, in groups of two pairs.  0
+ * for a separable item (no product). */
+int curv_head_grid_plan_flops(const curv_head_grid_desc* descs, int n, long long* out);
+/* One launch per batch of up to 8 items, a second where an item has chunks.  The workspace must be 256-byte aligned.
+ * `descs`, `shift` and `gain` are host arrays; they may be reused as soon as the call returns. */
+int curv_head_grid(void* stream, const curv_head_grid_desc* descs, int n, void* workspace, size_t workspace_bytes);
 /* v = max(v, 0) in place      curvatures.py:523 */
 int curv_clamp_min0(void* stream, float* v, long long count);
 /* out = sqrt(s*v)             curvatures.py:525 */

@@ -17,9 +17,20 @@ replace, in one run.
     line;
   * the relative Frobenius difference of kernel and torch expression on the SAME explicit noise (not timed).
 HIP events around each call, the candidates alternating, median of `--reps` after two warm-up calls each.
+
+    python tools/bench_head.py --grid [--reps 9] [--json FILE]
+
+the grid of damping pairs instead, at the same head with H = 16 pairs:
+  * head_grid dense / separable: one `ops.head_grid` call (curv_head_grid) on a (K, n) table resp. (K,) and (n,) spectra;
+    the dense form's `plan_flops` times H over its time as a fraction of the fp32 MFMA peak;
+  * composed: the same d2 from the ops that were there before - per pair `ops.rsqrt_affine` and `ops.mul` for the
+    reciprocal table and one `ops.gemm_batched` against Y o Y - and its relative difference to head_grid (not timed);
+  * last_layer_predictive_grid, probit and mc, under a Diagonal estimator that holds the head;
+  * sixteen rounds of `invert` + `last_layer_predictive` (probit and mc): what the grid replaces.
 """
 import argparse
 import json
+import math
 import os
 import statistics
 import sys
@@ -28,8 +39,8 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from curvature_amd import ops  # noqa: E402
-from curvature_amd.curvatures import KFAC  # noqa: E402
-from curvature_amd.evaluate import glm_predictive, last_layer_predictive  # noqa: E402
+from curvature_amd.curvatures import KFAC, Diagonal  # noqa: E402
+from curvature_amd.evaluate import glm_predictive, last_layer_predictive, last_layer_predictive_grid  # noqa: E402
 
 N, K, IN, S = 32, 1000, 2048, 256
 PEAK_TF = 157.3
@@ -51,14 +62,92 @@ def torch_expression(M, d2, mu, z=None):
     return torch.softmax(f, dim=2).mean(dim=1)
 
 
+def measure(candidates, reps, row):
+    for _ in range(2):
+        for fn in candidates.values():
+            fn()
+    torch.cuda.synchronize()
+    times = {name: [] for name in candidates}
+    for _ in range(reps):
+        for name, fn in candidates.items():
+            times[name].append(once(fn))
+    for name, ts in times.items():
+        row[name + "_ms"] = statistics.median(ts)
+        row[name + "_ms_min"], row[name + "_ms_max"] = min(ts), max(ts)
+
+
+def grid_row(dev, reps):
+    H, n = ops.HEAD_GRID_MAX, IN + 1
+    pairs = [(10.0 ** (-2 + 0.25 * h), float(N * (1 + h))) for h in range(H)]
+    torch.manual_seed(0)
+    model = torch.nn.Sequential(torch.nn.Flatten(), torch.nn.Linear(IN, K)).to(dev)
+    x = torch.randn(N, IN, device=dev)
+    labels = torch.randint(0, K, (N,), device=dev)
+    est = Diagonal(model, "Linear")
+    torch.nn.functional.cross_entropy(model(x), labels).backward()
+    est.update(N)
+    model.zero_grad()
+    head = model[1]
+    T = est.state[head]
+    Y = torch.cat([x, torch.ones(N, 1, device=dev)], dim=1).contiguous()
+    u, v = torch.rand(K, device=dev), torch.rand(n, device=dev)
+    rho, gain = [a / m for a, m in pairs], [1.0 / m for _, m in pairs]
+    d2 = torch.empty(H, N, K, device=dev)
+    composed = torch.empty(H, N, K, device=dev)
+
+    def compose():
+        y2 = ops.mul(Y, Y)
+        for h, (add, multiply) in enumerate(pairs):
+            inv = ops.rsqrt_affine(T, add, multiply)
+            ops.gemm_batched([ops.Gemm(y2, ops.mul(inv, inv).t(), composed[h])])
+
+    def rounds(predictive):
+        for add, multiply in pairs:
+            est.invert(add, multiply)
+            last_layer_predictive(model, est, x, predictive=predictive, samples=S)
+
+    row = dict(N=N, K=K, features=n, S=S, H=H)
+    ops.head_grid([ops.HeadGridJob(Y, None, None, T, d2, rho, gain)])
+    compose()
+    row["rel_difference_composed_to_head_grid"] = float(torch.linalg.norm(composed.double() - d2.double()) /
+                                                        torch.linalg.norm(d2.double()))
+    candidates = {
+        "head_grid_dense": lambda: ops.head_grid([ops.HeadGridJob(Y, None, None, T, d2, rho, gain)]),
+        "head_grid_separable": lambda: ops.head_grid([ops.HeadGridJob(Y, u, v, None, d2, [math.sqrt(r) for r in rho], gain)]),
+        "composed": compose,
+        "last_layer_grid_probit": lambda: last_layer_predictive_grid(model, est, x, pairs),
+        "last_layer_grid_mc": lambda: last_layer_predictive_grid(model, est, x, pairs, predictive="mc", samples=S),
+        "sixteen_rounds_probit": lambda: rounds("probit"),
+        "sixteen_rounds_mc": lambda: rounds("mc"),
+    }
+    measure(candidates, reps, row)
+    flops = H * ops.head_grid_plan_flops([ops.HeadGridJob(None, None, None, None, None, rho, gain, N=N, K=K, n=n,
+                                                          separable=False)])[0]
+    row["plan_gflop_dense"] = flops / 1e9
+    row["mfma_peak_fraction_dense"] = flops / (row["head_grid_dense_ms"] * 1e-3) / (PEAK_TF * 1e12)
+    row["composed_over_head_grid_dense"] = row["composed_ms"] / row["head_grid_dense_ms"]
+    row["sixteen_rounds_over_grid_probit"] = row["sixteen_rounds_probit_ms"] / row["last_layer_grid_probit_ms"]
+    row["sixteen_rounds_over_grid_mc"] = row["sixteen_rounds_mc_ms"] / row["last_layer_grid_mc_ms"]
+    return row
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=9)
     ap.add_argument("--json", default=None, help="write the result as one JSON line to this file")
+    ap.add_argument("--grid", action="store_true", help="measure the grid of damping pairs (K24) instead")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_head: needs the GPU (nothing is measured without one)")
     dev = torch.device("cuda:0")
+    if args.grid:
+        row = grid_row(dev, args.reps)
+        row["device"] = torch.cuda.get_device_name(0)
+        print(json.dumps(row), flush=True)
+        if args.json:
+            with open(args.json, "w") as fh:
+                fh.write(json.dumps(row) + "\n")
+        return
     torch.manual_seed(0)
     model = torch.nn.Sequential(torch.nn.Flatten(), torch.nn.Linear(IN, K)).to(dev)
     x = torch.randn(N, IN, device=dev)
@@ -100,17 +189,7 @@ def main():
         "torch_expression": lambda: torch_expression(L_G, terms.d2, mu),
         "glm_predictive_16_classes": lambda: glm_predictive(model, est, x, outputs=range(16)),
     }
-    for _ in range(2):
-        for fn in candidates.values():
-            fn()
-    torch.cuda.synchronize()
-    times = {name: [] for name in candidates}
-    for _ in range(args.reps):
-        for name, fn in candidates.items():
-            times[name].append(once(fn))
-    for name, ts in times.items():
-        row[name + "_ms"] = statistics.median(ts)
-        row[name + "_ms_min"], row[name + "_ms_max"] = min(ts), max(ts)
+    measure(candidates, args.reps, row)
     for lower in (True, False):
         tag = "lower" if lower else "dense"
         flops = ops.head_mc_plan_flops([ops.HeadMCJob(True, None, None, S, lower=lower, N=N, K=K)])[0]
