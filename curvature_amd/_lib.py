@@ -243,6 +243,13 @@ class curv_head_mc_desc(ctypes.Structure):
                [(k, ctypes.c_int32) for k in ("N", "K", "S", "m_lower")] + [("reserved", ctypes.c_longlong)]
 
 
+class curv_head_moments_desc(ctypes.Structure):
+    """Mirror of ``curv_head_moments_desc`` in include/curv_hip.h: the first 128 bytes of ``curv_head_mc_desc``, then
+    `entropy`, `probs_sq` and `reserved`."""
+    _fields_ = curv_head_mc_desc._fields_[:-1] + \
+               [("entropy", ctypes.c_void_p), ("probs_sq", ctypes.c_void_p), ("reserved", ctypes.c_longlong)]
+
+
 class curv_head_grid_desc(ctypes.Structure):
     """Mirror of ``curv_head_grid_desc`` in include/curv_hip.h (`shift` and `gain` are host arrays of H floats)."""
     _fields_ = [(k, ctypes.c_void_p) for k in ("Y", "u", "v", "T", "out")] + \
@@ -461,6 +468,10 @@ SIGNATURES = {
     "curv_head_mc_workspace_bytes": (_sz, [ctypes.POINTER(curv_head_mc_desc), _i]),
     "curv_head_mc_plan_flops": (_i, [ctypes.POINTER(curv_head_mc_desc), _i, ctypes.POINTER(ctypes.c_longlong)]),
     "curv_head_mc": (_i, [_vp, ctypes.POINTER(curv_head_mc_desc), _i, _vp, _sz]),
+    "curv_head_mc_moments_workspace_bytes": (_sz, [ctypes.POINTER(curv_head_moments_desc), _i]),
+    "curv_head_mc_moments_plan_flops": (_i, [ctypes.POINTER(curv_head_moments_desc), _i,
+                                             ctypes.POINTER(ctypes.c_longlong)]),
+    "curv_head_mc_moments": (_i, [_vp, ctypes.POINTER(curv_head_moments_desc), _i, _vp, _sz]),
     "curv_head_grid_workspace_bytes": (_sz, [ctypes.POINTER(curv_head_grid_desc), _i]),
     "curv_head_grid_plan_flops": (_i, [ctypes.POINTER(curv_head_grid_desc), _i, ctypes.POINTER(ctypes.c_longlong)]),
     "curv_head_grid": (_i, [_vp, ctypes.POINTER(curv_head_grid_desc), _i, _vp, _sz]),

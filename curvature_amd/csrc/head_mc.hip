@@ -25,6 +25,15 @@
 // caller's workspace and a second launch adds the chunks in chunk order.  Fixed order everywhere (lane, wave, workgroup,
 // chunk), no atomics; the chunk length follows from the item's own N and S (hmc_plan_of), so its bits are the same alone
 // and in a batch.  All global stores are plain vector stores.
+//
+// curv_head_mc_moments is the same kernel with two more moments of the draws (hmc_block with an HmmItem; the instantiations
+// behind curv_head_mc contain none of it): entropy[n] = (1/S) sum_s H(softmax f_s) and probs_sq[n][c] = (1/S) sum_s
+// softmax(f_s)[c]^2.  With t_c = f_s[c] - max and e_c = exp(t_c), H_s = ln(sum e) - (sum e t) / (sum e): sum e t is one more
+// running sum of pass 2 and goes the way of sum e (lane, halves, waves in wave order; a term with e = 0 - rows >= K, or an
+// exponential that underflowed - counts as 0, never as 0 * -inf).  The H_s of the 32 draws of a tile (0 for draws >= S) are
+// added by a butterfly over the lanes of a half wave, partners 16, 8, 4, 2, 1 apart in this order: every lane ends with the
+// same bits; then tiles in tile order.  The squares take the transposition tile of pass 3 beside the values.  With chunks
+// an (input, chunk) leaves 2 K + 1 partial sums - probs, squares, entropy - and the reduce launch finishes all three.
 #include "philox.h"
 #include "side_build.h"
 
@@ -44,6 +53,7 @@ constexpr int HMC_TP = 33;                     // LDS pitch of the transposition
 static_assert(HMC_K_MAX == 1024, "hmc_kernel instantiates 1, 2, 4 and 8 row blocks per wave: 4 * 8 * 32 rows");
 
 struct HmcItem {
+  static constexpr bool moments = false;
   const float* M;              // may be null: identity
   const float* d2;
   const float* mu;
@@ -61,14 +71,27 @@ struct HmcItem {
 typedef ArgBatch<HmcItem, HMC_BATCH> HmcBatch;
 static_assert(sizeof(HmcBatch) <= 3840, "kernel argument block must stay below 4 KB");
 
+// curv_head_mc_moments: `partial` is [n][chunk][2 K + 1] - probs, squares, entropy
+struct HmmItem : HmcItem {
+  static constexpr bool moments = true;
+  float* entropy;
+  float* probs_sq;
+};
+
+typedef ArgBatch<HmmItem, HMC_BATCH> HmmBatch;
+static_assert(sizeof(HmmBatch) <= 3840, "kernel argument block must stay below 4 KB");
+
 struct HmcPlan {
   int chunk_tiles, chunks;
   size_t bytes;
   long long flops;
 };
 
-bool hmc_plan_of(const curv_head_mc_desc& d, int index, HmcPlan* p) {
-  const char* const who = "curv_head_mc";
+// The checks and the plan of both entries: `outputs` says which outputs the entry has (all of them null is refused),
+// `per_chunk` how many partial sums an (input, chunk) leaves.
+template <typename Desc>
+bool hmc_plan_common(const char* who, const Desc& d, int index, bool any_output, const char* outputs, int per_chunk,
+                     HmcPlan* p) {
   if (d.K < 1 || d.K > HMC_K_MAX) {
     set_error("%s: item %d: K %d outside 1 .. %d", who, index, d.K, HMC_K_MAX);
     return false;
@@ -96,8 +119,8 @@ bool hmc_plan_of(const curv_head_mc_desc& d, int index, HmcPlan* p) {
               d.z_ss, d.K, d.z_ns);
     return false;
   }
-  if (!d.probs && !d.draws) {
-    set_error("%s: item %d: no output (probs and draws are both null)", who, index);
+  if (!any_output) {
+    set_error("%s: item %d: no output (%s null)", who, index, outputs);
     return false;
   }
   if (d.reserved != 0) {
@@ -107,12 +130,21 @@ bool hmc_plan_of(const curv_head_mc_desc& d, int index, HmcPlan* p) {
   const long long tiles = cdivll(d.S, HMC_TILE);
   p->chunk_tiles = (int)cdivll(tiles, cdivll(HMC_WGS_TARGET, d.N));
   p->chunks = (int)cdivll(tiles, p->chunk_tiles);
-  p->bytes = p->chunks > 1 ? align_up((size_t)d.N * p->chunks * d.K * sizeof(float), 256) : 0;
+  p->bytes = p->chunks > 1 ? align_up((size_t)d.N * p->chunks * per_chunk * sizeof(float), 256) : 0;
   long long steps = 0;                                       // k steps of 32 over the row blocks
   const int blocks = cdiv(d.K, 32);
   for (int g = 0; d.M != nullptr && g < blocks; ++g) steps += d.m_lower ? std::min(blocks, g + 1) : blocks;
   p->flops = 2LL * 32 * 32 * 32 * steps * tiles * d.N;
   return true;
+}
+
+bool hmc_plan_of(const curv_head_mc_desc& d, int index, HmcPlan* p) {
+  return hmc_plan_common("curv_head_mc", d, index, d.probs || d.draws, "probs and draws are both", d.K, p);
+}
+
+bool hmm_plan_of(const curv_head_moments_desc& d, int index, HmcPlan* p) {
+  return hmc_plan_common("curv_head_mc_moments", d, index, d.probs || d.draws || d.entropy || d.probs_sq,
+                         "probs, draws, entropy and probs_sq are all", 2 * d.K + 1, p);
 }
 
 size_t hmc_bytes_of(const std::vector<HmcPlan>& plans) {
@@ -143,9 +175,10 @@ __device__ __forceinline__ void hmc_quad(const HmcItem& d, long long n, int s, i
 // row of accumulator register `reg` within a 32 x 32 block (column = lane & 31)
 __device__ __forceinline__ int hmc_acc_row(int reg, int h) { return (reg & 3) + 8 * (reg >> 2) + 4 * h; }
 
-template <int NB>
-__device__ __forceinline__ void hmc_block(const HmcItem& d, long long local, float (*Bs)[32 * HMC_BP],
-                                          float (*Ts)[32 * HMC_TP], float (*red)[4][HMC_TILE], float* mu_s) {
+template <int NB, typename Item>
+__device__ __forceinline__ void hmc_block(const Item& d, long long local, float (*Bs)[32 * HMC_BP],
+                                          float (*Ts)[32 * HMC_TP], float (*red)[4][HMC_TILE], float* mu_s,
+                                          float* sq_s = nullptr) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = lane & 31, h = lane >> 5;
   const int K = d.K, S = d.S;
   const long long n = local / d.chunks;
@@ -154,6 +187,11 @@ __device__ __forceinline__ void hmc_block(const HmcItem& d, long long local, flo
   const int t0 = chunk * d.chunk_tiles, t1 = min(tiles, t0 + d.chunk_tiles);
   const int steps = (K + 31) >> 5;
   const bool lower = d.lower != 0;
+  constexpr bool MOM = Item::moments;
+  auto want = [&]() {                                          // a softmax at all
+    if constexpr (MOM) return d.probs != nullptr || d.entropy != nullptr || d.probs_sq != nullptr;
+    else return d.probs != nullptr;
+  };
 
   // a[i] = M[32 g + r][32 step + 16 h + i] of block b (g = 4 b + wave), 0 where the entry is outside M or above the diagonal
   auto load_a = [&](int b, int step, float (&a)[16]) {
@@ -183,8 +221,17 @@ __device__ __forceinline__ void hmc_block(const HmcItem& d, long long local, flo
   if (d.M == nullptr) __syncthreads();
 
   float rsum[NB];
+  float hsum = 0.f;                                            // (moments: the running sum of the entropies)
 #pragma unroll
   for (int b = 0; b < NB; ++b) rsum[b] = 0.f;
+  // (moments: the running sums of the squares stay in LDS, sq_s[row], written and read by lane (r, h = 0) of the row's
+  // wave alone - with NB more registers the instantiation of NB = 8 would spill)
+  if constexpr (MOM) {
+    if (h == 0) {
+#pragma unroll
+      for (int b = 0; b < NB; ++b) sq_s[32 * (4 * b + wave) + r] = 0.f;
+    }
+  }
 
   for (int tile = t0; tile < t1; ++tile) {
     const int s0 = tile * HMC_TILE;
@@ -273,26 +320,40 @@ __device__ __forceinline__ void hmc_block(const HmcItem& d, long long local, flo
         }
       }
     }
-    if (d.probs == nullptr) continue;
+    if (!want()) continue;
     m = fmaxf(m, __shfl_xor(m, 32));
     if (h == 0) red[0][wave][r] = m;
     __syncthreads();
     m = fmaxf(fmaxf(red[0][0][r], red[0][1][r]), fmaxf(red[0][2][r], red[0][3][r]));
-    float sum = 0.f;
+    float sum = 0.f, et = 0.f;
 #pragma unroll
     for (int b = 0; b < NB; ++b) {
 #pragma unroll
       for (int reg = 0; reg < 16; ++reg) {
-        const float e = expf(acc[b][reg] - m);
+        const float t = acc[b][reg] - m;
+        const float e = expf(t);
         acc[b][reg] = e;
         sum += e;
+        if constexpr (MOM) et += e > 0.f ? e * t : 0.f;       // (t = -inf at rows >= K)
       }
     }
     sum += __shfl_xor(sum, 32);
-    if (h == 0) red[1][wave][r] = sum;
+    if constexpr (MOM) et += __shfl_xor(et, 32);
+    if (h == 0) {
+      red[1][wave][r] = sum;
+      if constexpr (MOM) red[2][wave][r] = et;
+    }
     __syncthreads();
     sum = ((red[1][0][r] + red[1][1][r]) + red[1][2][r]) + red[1][3][r];
     const float inv = valid ? 1.0f / sum : 0.f;
+    if constexpr (MOM) {
+      // H_s of draw s0 + r, the same bits in all eight half waves; then the 32 draws of the tile
+      et = ((red[2][0][r] + red[2][1][r]) + red[2][2][r]) + red[2][3][r];
+      float hs = valid ? logf(sum) - et / sum : 0.f;
+#pragma unroll
+      for (int step = 16; step >= 1; step >>= 1) hs += __shfl_xor(hs, step);
+      hsum += hs;
+    }
 
     // ---- 3. sum over the draws of the tile, block by block through the wave's LDS tile
     float* ts = Ts[wave];
@@ -306,18 +367,53 @@ __device__ __forceinline__ void hmc_block(const HmcItem& d, long long local, flo
       for (int j = 0; j < 16; ++j) v += ts[r * HMC_TP + 16 * h + j];
       v += __shfl_xor(v, 32);
       rsum[b] += v;
+      if constexpr (MOM) {
+        if (d.probs_sq != nullptr) {                           // the same order: draws 16 h .. 16 h + 15, then the halves
+          float v2 = 0.f;
+#pragma unroll
+          for (int j = 0; j < 16; ++j) {
+            const float p = ts[r * HMC_TP + 16 * h + j];
+            v2 += p * p;
+          }
+          v2 += __shfl_xor(v2, 32);
+          if (h == 0) sq_s[32 * (4 * b + wave) + r] += v2;
+        }
+      }
       __syncthreads();
     }
   }
-  if (d.probs == nullptr) return;
+  if (!want()) return;
 
-  if (h == 0) {
+  if constexpr (MOM) {
+    float* part = d.chunks > 1 ? d.partial + (n * d.chunks + chunk) * (2 * K + 1) : nullptr;
+    if (h == 0) {
 #pragma unroll
-    for (int b = 0; b < NB; ++b) {
-      const int row = 32 * (4 * b + wave) + r;
-      if (row < K) {
-        if (d.chunks > 1) d.partial[(n * d.chunks + chunk) * K + row] = rsum[b];
-        else d.probs[n * K + row] = rsum[b] / (float)S;
+      for (int b = 0; b < NB; ++b) {
+        const int row = 32 * (4 * b + wave) + r;
+        if (row < K) {
+          if (part != nullptr) {
+            part[row] = rsum[b];
+            part[K + row] = sq_s[row];
+          } else {
+            if (d.probs != nullptr) d.probs[n * K + row] = rsum[b] / (float)S;
+            if (d.probs_sq != nullptr) d.probs_sq[n * K + row] = sq_s[row] / (float)S;
+          }
+        }
+      }
+    }
+    if (tid == 0) {
+      if (part != nullptr) part[2 * K] = hsum;
+      else if (d.entropy != nullptr) d.entropy[n] = hsum / (float)S;
+    }
+  } else {
+    if (h == 0) {
+#pragma unroll
+      for (int b = 0; b < NB; ++b) {
+        const int row = 32 * (4 * b + wave) + r;
+        if (row < K) {
+          if (d.chunks > 1) d.partial[(n * d.chunks + chunk) * K + row] = rsum[b];
+          else d.probs[n * K + row] = rsum[b] / (float)S;
+        }
       }
     }
   }
@@ -337,6 +433,21 @@ __global__ void __launch_bounds__(HMC_THREADS) hmc_kernel(const HmcBatch batch) 
   else hmc_block<8>(d, local, Bs, Ts, red, mu_s);
 }
 
+__global__ void __launch_bounds__(HMC_THREADS) hmm_kernel(const HmmBatch batch) {
+  __shared__ float Bs[2][32 * HMC_BP];
+  __shared__ float Ts[HMC_THREADS / 64][32 * HMC_TP];
+  __shared__ float red[3][4][HMC_TILE];
+  __shared__ float mu_s[HMC_K_MAX];
+  __shared__ float sq_s[HMC_K_MAX];
+  const HmmItem& d = batch.e[owner_of(batch, (long long)blockIdx.x)];
+  const long long local = (long long)blockIdx.x - d.base;
+  const int nb = (d.K + 127) >> 7;
+  if (nb <= 1) hmc_block<1>(d, local, Bs, Ts, red, mu_s, sq_s);
+  else if (nb <= 2) hmc_block<2>(d, local, Bs, Ts, red, mu_s, sq_s);
+  else if (nb <= 4) hmc_block<4>(d, local, Bs, Ts, red, mu_s, sq_s);
+  else hmc_block<8>(d, local, Bs, Ts, red, mu_s, sq_s);
+}
+
 // The chunks of an input in chunk order: one thread per (n, k).  Blocks of an item: ceil(N K / 256), none where its inputs
 // have one chunk.
 __global__ void __launch_bounds__(HMC_THREADS) hmc_reduce_kernel(const HmcBatch batch) {
@@ -349,6 +460,68 @@ __global__ void __launch_bounds__(HMC_THREADS) hmc_reduce_kernel(const HmcBatch 
   float v = 0.f;
   for (int c = 0; c < d.chunks; ++c) v += p[(long long)c * d.K];
   d.probs[idx] = v / (float)d.S;
+}
+
+// The same for the 2 K + 1 sums of an input: one thread per (n, j), j < K a probability, j < 2 K a square, j = 2 K the
+// entropy.  Blocks of an item: ceil(N (2 K + 1) / 256).
+__global__ void __launch_bounds__(HMC_THREADS) hmm_reduce_kernel(const HmmBatch batch) {
+  const HmmItem& d = batch.e[owner_of(batch, (long long)blockIdx.x)];
+  const long long idx = ((long long)blockIdx.x - d.base) * HMC_THREADS + threadIdx.x;
+  const int per = 2 * d.K + 1;
+  if (idx >= (long long)d.N * per) return;
+  const long long n = idx / per;
+  const int j = (int)(idx - n * per);
+  const float* p = d.partial + n * d.chunks * per + j;
+  float v = 0.f;
+  for (int c = 0; c < d.chunks; ++c) v += p[(long long)c * per];
+  v /= (float)d.S;
+  float* out = j < d.K ? d.probs : j < 2 * d.K ? d.probs_sq : d.entropy;
+  if (out != nullptr) out[j < d.K ? n * d.K + j : j < 2 * d.K ? n * d.K + (j - d.K) : n] = v;
+}
+
+// The body of both entries: plans, workspace, the items of a batch (`extra` fills what an Item has beyond HmcItem and
+// says whether the item has sums to reduce and how many per input), the main launch and the reduce launch.
+template <typename Item, typename Desc, typename Extra>
+int hmc_enqueue(const char* name, hipStream_t stream, const Desc* descs, int n, void* workspace, size_t workspace_bytes,
+                bool (*plan_of)(const Desc&, int, HmcPlan*), void (*kernel)(const ArgBatch<Item, HMC_BATCH>),
+                void (*reduce_kernel)(const ArgBatch<Item, HMC_BATCH>), Extra extra) {
+  std::vector<HmcPlan> plans;
+  if (!side::plans_of(name, descs, n, plan_of, &plans)) return CURV_ERR_INVALID;
+  for (int i = 0; i < n; ++i) CURV_REQUIRE(descs[i].d2 && descs[i].mu, "%s: item %d: null d2 or mu", name, i);
+  const size_t need = hmc_bytes_of(plans);
+  if (need > 0) {
+    const int rc = side::require_workspace(name, workspace, workspace_bytes, need, 256);
+    if (rc != CURV_OK) return rc;
+  }
+  size_t at = 0;
+  return for_arg_batches<Item, HMC_BATCH, 2>(
+      n, name,
+      [&](int i, Item* P, long long* units) {
+        const Desc& d = descs[i];
+        const HmcPlan& p = plans[i];
+        P->M = d.M; P->d2 = d.d2; P->mu = d.mu; P->Z = d.Z;
+        P->probs = d.probs; P->draws = d.draws;
+        P->partial = p.bytes ? (float*)((char*)workspace + at) : nullptr;
+        at += p.bytes;
+        P->m_rs = d.m_rs; P->d_ns = d.d_ns; P->d_cs = d.d_cs; P->mu_ns = d.mu_ns; P->z_ns = d.z_ns; P->z_ss = d.z_ss;
+        P->seed = d.seed; P->offset = d.offset;
+        P->N = d.N; P->K = d.K; P->S = d.S; P->lower = d.m_lower;
+        P->chunk_tiles = p.chunk_tiles; P->chunks = p.chunks;
+        P->base = 0;
+        const long long sums = extra(d, P);                     // per input; 0: nothing to reduce
+        units[0] = (long long)d.N * p.chunks;
+        units[1] = p.chunks > 1 ? cdivll((long long)d.N * sums, HMC_THREADS) : 0;
+      },
+      [](int, long long units) { return units; },
+      [&](const ArgBatch<Item, HMC_BATCH>* b, const long long*, const unsigned* grid) {
+        hipLaunchKernelGGL(kernel, dim3(grid[0]), dim3(HMC_THREADS), 0, stream, b[0]);
+        CURV_LAUNCH_CHECK();
+        if (grid[1] > 0) {
+          hipLaunchKernelGGL(reduce_kernel, dim3(grid[1]), dim3(HMC_THREADS), 0, stream, b[1]);
+          CURV_LAUNCH_CHECK();
+        }
+        return CURV_OK;
+      });
 }
 
 }  // namespace
@@ -366,43 +539,28 @@ extern "C" int curv_head_mc_plan_flops(const curv_head_mc_desc* descs, int n, lo
 
 extern "C" int curv_head_mc(void* stream_, const curv_head_mc_desc* descs, int n, void* workspace,
                             size_t workspace_bytes) {
-  const char* const name = "curv_head_mc";
   if (n <= 0) return CURV_OK;
-  hipStream_t stream = (hipStream_t)stream_;
-  std::vector<HmcPlan> plans;
-  if (!side::plans_of(name, descs, n, hmc_plan_of, &plans)) return CURV_ERR_INVALID;
-  for (int i = 0; i < n; ++i) CURV_REQUIRE(descs[i].d2 && descs[i].mu, "%s: item %d: null d2 or mu", name, i);
-  const size_t need = hmc_bytes_of(plans);
-  if (need > 0) {
-    const int rc = side::require_workspace(name, workspace, workspace_bytes, need, 256);
-    if (rc != CURV_OK) return rc;
-  }
-  size_t at = 0;
-  return for_arg_batches<HmcItem, HMC_BATCH, 2>(
-      n, name,
-      [&](int i, HmcItem* P, long long* units) {
-        const curv_head_mc_desc& d = descs[i];
-        const HmcPlan& p = plans[i];
-        P->M = d.M; P->d2 = d.d2; P->mu = d.mu; P->Z = d.Z;
-        P->probs = d.probs; P->draws = d.draws;
-        P->partial = p.bytes ? (float*)((char*)workspace + at) : nullptr;
-        at += p.bytes;
-        P->m_rs = d.m_rs; P->d_ns = d.d_ns; P->d_cs = d.d_cs; P->mu_ns = d.mu_ns; P->z_ns = d.z_ns; P->z_ss = d.z_ss;
-        P->seed = d.seed; P->offset = d.offset;
-        P->N = d.N; P->K = d.K; P->S = d.S; P->lower = d.m_lower;
-        P->chunk_tiles = p.chunk_tiles; P->chunks = p.chunks;
-        P->base = 0;
-        units[0] = (long long)d.N * p.chunks;
-        units[1] = p.chunks > 1 && d.probs ? cdivll((long long)d.N * d.K, HMC_THREADS) : 0;
-      },
-      [](int, long long units) { return units; },
-      [&](const HmcBatch* b, const long long*, const unsigned* grid) {
-        hipLaunchKernelGGL(hmc_kernel, dim3(grid[0]), dim3(HMC_THREADS), 0, stream, b[0]);
-        CURV_LAUNCH_CHECK();
-        if (grid[1] > 0) {
-          hipLaunchKernelGGL(hmc_reduce_kernel, dim3(grid[1]), dim3(HMC_THREADS), 0, stream, b[1]);
-          CURV_LAUNCH_CHECK();
-        }
-        return CURV_OK;
-      });
+  return hmc_enqueue<HmcItem>("curv_head_mc", (hipStream_t)stream_, descs, n, workspace, workspace_bytes, hmc_plan_of,
+                              hmc_kernel, hmc_reduce_kernel,
+                              [](const curv_head_mc_desc& d, HmcItem*) { return d.probs ? (long long)d.K : 0LL; });
+}
+
+extern "C" size_t curv_head_mc_moments_workspace_bytes(const curv_head_moments_desc* descs, int n) {
+  return side::workspace_bytes("curv_head_mc_moments_workspace_bytes", descs, n, hmm_plan_of, hmc_bytes_of);
+}
+
+extern "C" int curv_head_mc_moments_plan_flops(const curv_head_moments_desc* descs, int n, long long* out) {
+  return side::plan_flops("curv_head_mc_moments_plan_flops", descs, n, out, hmm_plan_of);
+}
+
+extern "C" int curv_head_mc_moments(void* stream_, const curv_head_moments_desc* descs, int n, void* workspace,
+                                    size_t workspace_bytes) {
+  if (n <= 0) return CURV_OK;
+  return hmc_enqueue<HmmItem>("curv_head_mc_moments", (hipStream_t)stream_, descs, n, workspace, workspace_bytes,
+                              hmm_plan_of, hmm_kernel, hmm_reduce_kernel,
+                              [](const curv_head_moments_desc& d, HmmItem* P) {
+                                P->entropy = d.entropy;
+                                P->probs_sq = d.probs_sq;
+                                return d.probs || d.entropy || d.probs_sq ? 2LL * d.K + 1 : 0LL;
+                              });
 }

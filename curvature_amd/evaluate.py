@@ -21,7 +21,7 @@ all-gather of the sampled parameters (a wait on the other ranks, not local work)
 """
 import contextlib
 import math
-from typing import Iterable, List, Tuple
+from typing import Iterable, List, NamedTuple, Tuple
 
 import torch
 
@@ -629,6 +629,77 @@ def eval_last_layer(model: torch.nn.Module, dataset: Iterable, estimator, predic
     predictions = torch.cat(probs) if probs else torch.empty(0, device=device)
     labels = torch.cat(labels_all) if labels_all else torch.empty(0, dtype=torch.long)
     return predictions.cpu().numpy(), labels.numpy()
+
+
+class Uncertainty(NamedTuple):
+    """What `last_layer_uncertainty` returns: `logits`, `variance`, `probs` (N, K) as `last_layer_predictive` gives them,
+    `probs_std` (N, K) the standard deviation of each class probability over the draws, and the entropies (N,) in nats:
+    `total` = H(probs), `aleatoric` = the mean entropy of the draws, `epistemic` = their difference, the mutual
+    information between the prediction and the head's weights."""
+    logits: torch.Tensor
+    variance: torch.Tensor
+    probs: torch.Tensor
+    probs_std: torch.Tensor
+    total: torch.Tensor
+    aleatoric: torch.Tensor
+    epistemic: torch.Tensor
+
+
+def last_layer_uncertainty(model: torch.nn.Module, estimator, images: torch.Tensor, *, head=None, samples: int = 256,
+                           noise=None) -> Uncertainty:
+    """The uncertainty of the last-layer Laplace predictive of one batch, split into what the data leave open and what the
+    posterior over the head's weights leaves open: `Uncertainty` (logits, variance, probs, probs_std, total, aleatoric,
+    epistemic).
+
+    One forward pass, `Curvature.head_terms` and ONE `ops.head_mc_moments` call: the draws
+    ``f ~ N(logits, M diag(d2) M^T)`` of ``last_layer_predictive(predictive="mc")`` - `logits`, `variance` and `probs` have
+    its bits on the same noise - give, without an (N, samples, K) tensor, the mean entropy of their softmax (`aleatoric`)
+    and the mean square of every class probability.  ``total = H(probs)`` with ``0 ln 0 = 0``;
+    ``epistemic = clamp(total - aleatoric, min=0)`` (non-negative by Jensen's inequality in exact arithmetic; where it is
+    small it is a difference of two nearly equal numbers, accurate relative to `total` and not to itself);
+    ``probs_std = sqrt(clamp(probs_sq - probs ** 2, min=0))``, so ``probs_std / sqrt(samples)`` is the Monte-Carlo standard
+    error of `probs`.  Noise, the cap of `ops.HEAD_MC_MAX_CLASSES` classes, model mode, hooks and refusals as in
+    `last_layer_predictive`; `noise_offset` advances by ``N * samples * ceil(K / 4)``.  GPU only."""
+    what = "last_layer_uncertainty"
+    samples = int(samples)
+    head, features, logits = _head_pass(what, model, estimator, images, head, "mc", samples, "inv_state",
+                                        lambda layer: estimator.head_terms(layer, None))
+    terms = estimator.head_terms(head, features)
+    N, K = logits.shape
+    if K > ops.HEAD_MC_MAX_CLASSES:
+        raise ValueError(f"{what}: {K} classes; the draws take at most ops.HEAD_MC_MAX_CLASSES = "
+                         f"{ops.HEAD_MC_MAX_CLASSES}")
+    seed, offset = _head_noise(what, estimator, noise, N * samples * ((K + 3) // 4))
+    probs = torch.empty(N, K, dtype=torch.float32, device=logits.device)
+    probs_sq = torch.empty(N, K, dtype=torch.float32, device=logits.device)
+    aleatoric = torch.empty(N, dtype=torch.float32, device=logits.device)
+    ops.head_mc_moments([ops.HeadMomentsJob(terms.M, terms.d2, logits.float().contiguous(), samples, lower=terms.lower,
+                                            noise=noise, probs=probs, entropy=aleatoric, probs_sq=probs_sq, seed=seed,
+                                            offset=offset)])
+    total = -torch.xlogy(probs, probs).sum(dim=1)
+    epistemic = torch.clamp(total - aleatoric, min=0.0)
+    probs_std = torch.sqrt(torch.clamp(probs_sq - probs * probs, min=0.0))
+    return Uncertainty(logits, terms.variance, probs, probs_std, total, aleatoric, epistemic)
+
+
+def eval_uncertainty(model: torch.nn.Module, dataset: Iterable, estimator, samples: int = 256, head=None, device=None):
+    """`last_layer_uncertainty` over `dataset` - the loop of `eval_last_layer`: a dict of numpy arrays `probs` (N, K),
+    `labels` (N,), `total`, `aleatoric`, `epistemic` (N,).  The draws come from the estimator's noise stream.  Everything
+    stays on the device and crosses to the host once at the end."""
+    if device is None:
+        device = next(model.parameters()).device
+    keys = ("probs", "total", "aleatoric", "epistemic")
+    parts, labels_all = {key: [] for key in keys}, []
+    for images, labels in dataset:
+        images = images.to(device, non_blocking=True)
+        result = last_layer_uncertainty(model, estimator, images, head=head, samples=samples)
+        for key in keys:
+            parts[key].append(getattr(result, key))
+        if labels is not None:
+            labels_all.append(labels.cpu() if isinstance(labels, torch.Tensor) else torch.as_tensor(labels))
+    out = {key: (torch.cat(parts[key]) if parts[key] else torch.empty(0, device=device)).cpu().numpy() for key in keys}
+    out["labels"] = (torch.cat(labels_all) if labels_all else torch.empty(0, dtype=torch.long)).numpy()
+    return out
 
 
 def eval_glm(model: torch.nn.Module, dataset: Iterable, estimator, predictive: str = "probit", outputs=None,

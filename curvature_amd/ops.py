@@ -2017,9 +2017,11 @@ class HeadMCJob:
         self.S, self.seed, self.offset = int(samples), int(seed), int(offset)
 
 
-def _head_mc_descs(jobs: Sequence[HeadMCJob], check_tensors: bool = True):
-    name = "head_mc"
-    arr = (_lib.curv_head_mc_desc * len(jobs))()
+def _head_mc_descs(jobs: Sequence[HeadMCJob], check_tensors: bool = True, name: str = "head_mc",
+                   desc=_lib.curv_head_mc_desc, outputs=(("probs", "N,K"), ("draws", "N,S,K"))):
+    """The descriptors of `head_mc` and, with the other `name`, `desc` and `outputs` (attribute, shape), of
+    `head_mc_moments`."""
+    arr = (desc * len(jobs))()
     for d, j in zip(arr, jobs):
         N, K, S = j.N, j.K, j.S
         d.N, d.K, d.S, d.m_lower = N, K, S, int(j.lower)
@@ -2029,7 +2031,8 @@ def _head_mc_descs(jobs: Sequence[HeadMCJob], check_tensors: bool = True):
             d.probs = 256                # (an item without outputs is refused; the host queries never read the address)
             d.M = 256 if j.M is not None else None
             continue
-        floats = (j.M, j.d2, j.mu, j.noise, j.probs, j.draws)
+        shapes = {"N,K": (N, K), "N,S,K": (N, S, K), "N": (N,)}
+        floats = (j.M, j.d2, j.mu, j.noise) + tuple(getattr(j, what) for what, _ in outputs)
         for t in floats:
             if t is not None and not t.is_cuda:
                 raise RuntimeError("curvature_amd runs on MI355X only: got a CPU tensor (no CPU fallback)")
@@ -2061,7 +2064,8 @@ def _head_mc_descs(jobs: Sequence[HeadMCJob], check_tensors: bool = True):
             d.z_ss = j.noise.stride(1) if S > 1 else K
             d.z_ns = j.noise.stride(0) if N > 1 else (S - 1) * d.z_ss + K
             d.Z = j.noise.data_ptr()
-        for what, t, shape in (("probs", j.probs, (N, K)), ("draws", j.draws, (N, S, K))):
+        for what, key in outputs:
+            t, shape = getattr(j, what), shapes[key]
             if t is None:
                 continue
             if tuple(t.shape) != shape or not t.is_contiguous():
@@ -2088,6 +2092,44 @@ def head_mc(jobs: Sequence[HeadMCJob]) -> None:
     ws = workspace(need, jobs[0].mu.device, "persample") if need else None
     _lib.check(L.curv_head_mc(_lib.stream_ptr(), arr, n, ws.data_ptr() if need else None, ws.numel() if need else 0),
                "curv_head_mc")
+
+
+class HeadMomentsJob(HeadMCJob):
+    """`HeadMCJob` with two more moments of the same draws (curv_head_mc_moments): `entropy` (N,), the mean over the draws
+    of the entropy of softmax(f) - the aleatoric part of the uncertainty -, and `probs_sq` (N, K), the mean of
+    softmax(f)[c] ** 2, beside `probs` (N, K; the bits `head_mc` gives for the same inputs) and `draws` (N, S, K).  All
+    four contiguous float32, any may be None but not all."""
+    __slots__ = ("entropy", "probs_sq")
+
+    def __init__(self, M, d2, mu, samples, *, lower=False, noise=None, probs=None, entropy=None, probs_sq=None, draws=None,
+                 seed: int = 0, offset: int = 0, N: Optional[int] = None, K: Optional[int] = None):
+        super().__init__(M, d2, mu, samples, lower=lower, noise=noise, probs=probs, draws=draws, seed=seed, offset=offset,
+                         N=N, K=K)
+        self.entropy, self.probs_sq = entropy, probs_sq
+
+
+def _head_moments_descs(jobs: Sequence[HeadMomentsJob], check_tensors: bool = True):
+    return _head_mc_descs(jobs, check_tensors, "head_mc_moments", _lib.curv_head_moments_desc,
+                          (("probs", "N,K"), ("draws", "N,S,K"), ("entropy", "N"), ("probs_sq", "N,K")))
+
+
+def head_mc_moments_plan_flops(jobs: Sequence[HeadMomentsJob]) -> List[int]:
+    """`head_mc_plan_flops` of the same jobs (curv_head_mc_moments_plan_flops, host only): the moments add no product."""
+    if not jobs:
+        return []
+    return _plan_flops("curv_head_mc_moments_plan_flops", _head_moments_descs(jobs, check_tensors=False), len(jobs))
+
+
+def head_mc_moments(jobs: Sequence[HeadMomentsJob]) -> None:
+    """curv_head_mc_moments over any number of items, on the current stream; the partial sums of items whose draws are
+    cut into chunks from `workspace` (an item of one chunk per input needs none)."""
+    if not jobs:
+        return
+    L, arr, n = _lib.lib(), _head_moments_descs(jobs), len(jobs)
+    need = L.curv_head_mc_moments_workspace_bytes(arr, n)    # 0: nothing needed - or refused, which the call itself reports
+    ws = workspace(need, jobs[0].mu.device, "persample") if need else None
+    _lib.check(L.curv_head_mc_moments(_lib.stream_ptr(), arr, n, ws.data_ptr() if need else None,
+                                      ws.numel() if need else 0), "curv_head_mc_moments")
 
 
 HEAD_GRID_MAX = _lib.HEAD_GRID_MAX

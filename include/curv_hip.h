@@ -1282,6 +1282,54 @@ int curv_head_mc_plan_flops(const curv_head_mc_desc* descs, int n, long long* ou
 int curv_head_mc(void* stream, const curv_head_mc_desc* descs, int n, void* workspace, size_t workspace_bytes);
 
 /* ------------------------------------------------------------------------------------------------
+ * curv_head_mc with two more moments of the draws (csrc/head_mc.hip; DESIGN.md "K25"): what splits the uncertainty of the
+ * last-layer predictive into its aleatoric and its epistemic part without the (N, S, K) draws.  The first 128 bytes of the
+ * descriptor are field for field those of curv_head_mc_desc, and f_s is exactly the f_s of curv_head_mc (same M, m_lower,
+ * d2, mu, Z / Philox convention, same counters).  Per input n
+ *     probs[n*K + c]    = (1/S) sum_s softmax(f_s)[c]        bit-equal to what curv_head_mc writes for the same fields
+ *     entropy[n]        = (1/S) sum_s H_s,   H_s = -sum_c p_c ln p_c = ln(sum_c e^{t_c}) - (sum_c e^{t_c} t_c) / (sum_c e^{t_c}),
+ *                                            t_c = f_s[c] - max_c f_s[c]
+ *     probs_sq[n*K + c] = (1/S) sum_s softmax(f_s)[c]^2
+ * so that with total = H(probs): aleatoric = entropy, epistemic (the mutual information) = total - entropy, and the
+ * variance of class c over the draws is probs_sq - probs^2.  K = 1 gives entropy = +0.0 and probs_sq = 1.0 exactly.
+ *
+ * Outputs, any may be NULL but not all four: probs (N x K), draws (N x S x K), entropy (N), probs_sq (N x K), contiguous.
+ * `reserved` must be 0.
+ *
+ * Plan.  The split rule of curv_head_mc.  With more than one chunk the partial sums of an (input, chunk) are 2 K + 1 floats
+ * - probs, squares, entropy - so an item needs align_up(N chunks (2 K + 1) 4, 256) bytes of workspace (0 WITHOUT an error
+ * text where every input has one chunk), and the reduce launch finishes all three outputs.
+ *
+ * Order of the sums: sum e t goes the way of sum e (lane, the two halves of a wave, the four waves in wave order; a term
+ * with e = 0 counts as 0); the H_s of the 32 draws of a tile are added by a butterfly over partners 16, 8, 4, 2, 1 lanes
+ * apart, then the tiles in tile order, then the chunks in chunk order; the squares go the way of probs.  No atomics, the
+ * bits of an item do not depend on the other items of the call; nothing non-finite from finite input, logits so far apart
+ * that e^t underflows included.  Everything else - validation, error texts naming the item, launches - as curv_head_mc.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct curv_head_moments_desc {
+  const float* M;          /* may be NULL: identity */
+  const float* d2;
+  const float* mu;
+  const float* Z;          /* may be NULL */
+  float* probs;            /* may be NULL */
+  float* draws;            /* may be NULL */
+  long long m_rs, d_ns, d_cs, mu_ns, z_ns, z_ss;
+  unsigned long long seed, offset;
+  int32_t N, K, S;
+  int32_t m_lower;
+  float* entropy;          /* may be NULL */
+  float* probs_sq;         /* may be NULL */
+  long long reserved;
+} curv_head_moments_desc;
+/* As curv_head_mc_workspace_bytes, with 2 K + 1 floats per input and chunk.  Host only. */
+size_t curv_head_mc_moments_workspace_bytes(const curv_head_moments_desc* descs, int n);
+/* Host only: equal to curv_head_mc_plan_flops for the same fields. */
+int curv_head_mc_moments_plan_flops(const curv_head_moments_desc* descs, int n, long long* out);
+/* One launch per batch of up to 16 items, a second where an item has chunks.  The workspace must be 256-byte aligned. */
+int curv_head_mc_moments(void* stream, const curv_head_moments_desc* descs, int n, void* workspace,
+                         size_t workspace_bytes);
+
+/* ------------------------------------------------------------------------------------------------
  * The d2 of the last-layer Laplace predictive for a whole grid of damping pairs in one pass (csrc/head_grid.hip;
  * DESIGN.md "K24"): for h < H, input r < N and class j < K
  *     out[(h*N + r)*K + j] = gain[h] * r_h[j] * sum_{i < n} Y[r*y_rs + i]**2 / (T[j][i] + shift[h])

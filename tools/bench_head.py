@@ -27,6 +27,16 @@ the grid of damping pairs instead, at the same head with H = 16 
     reciprocal table and one `ops.gemm_batched` against Y o Y - and its relative difference to head_grid (not timed);
   * last_layer_predictive_grid, probit and mc, under a Diagonal estimator that holds the head;
   * sixteen rounds of `invert` + `last_layer_predictive` (probit and mc): what the grid replaces.
+
+    python tools/bench_head.py --moments [--reps 9] [--json FILE]
+
+the entropy split at the same head, M = L_G with `lower` and dense, four candidates alternating:
+  * head_mc: `ops.head_mc`, probs alone - the kernel of K23;
+  * moments_all: `ops.head_mc_moments` with probs, entropy and probs_sq;
+  * moments_probs: `ops.head_mc_moments` with probs alone;
+  * torch: the expression that materialises the (N, S, K) softmax and forms the same three results;
+  * the relative Frobenius difference of kernel and torch expression on the SAME explicit noise, and whether the probs of
+    `head_mc_moments` have the bits of `head_mc` (not timed).
 """
 import argparse
 import json
@@ -74,6 +84,72 @@ def measure(candidates, reps, row):
     for name, ts in times.items():
         row[name + "_ms"] = statistics.median(ts)
         row[name + "_ms_min"], row[name + "_ms_max"] = min(ts), max(ts)
+
+
+def torch_moments(M, d2, mu, z=None):
+    if z is None:
+        z = torch.randn(N, S, K, device=mu.device)
+    p = torch.softmax(mu[:, None, :] + torch.matmul(z * torch.sqrt(d2)[:, None, None], M.t()), dim=2)
+    return p.mean(dim=1), -torch.xlogy(p, p).sum(dim=2).mean(dim=1), (p * p).mean(dim=1)
+
+
+def moments_row(dev, reps):
+    torch.manual_seed(0)
+    model = torch.nn.Sequential(torch.nn.Flatten(), torch.nn.Linear(IN, K)).to(dev)
+    x = torch.randn(N, IN, device=dev)
+    labels = torch.randint(0, K, (N,), device=dev)
+    est = KFAC(model, "Linear")
+    torch.nn.functional.cross_entropy(model(x), labels).backward()
+    est.update(N)
+    model.zero_grad()
+    est.invert(add=1.0, multiply=float(N))
+    terms = est.head_terms(model[1], x)
+    L_G = torch.tril(terms.M).contiguous()
+    with torch.no_grad():
+        mu = model(x).float().contiguous()
+    probs, probs_sq = torch.empty(N, K, device=dev), torch.empty(N, K, device=dev)
+    entropy = torch.empty(N, device=dev)
+    plain = torch.empty(N, K, device=dev)
+    state = {"offset": 0}
+
+    def position():
+        state["offset"] += N * S * ((K + 3) // 4)
+        return state["offset"]
+
+    def head_mc(lower, z=None):
+        ops.head_mc([ops.HeadMCJob(L_G, terms.d2, mu, S, lower=lower, noise=z, probs=plain, seed=1, offset=position())])
+
+    def moments(lower, everything, z=None):
+        more = dict(entropy=entropy, probs_sq=probs_sq) if everything else {}
+        ops.head_mc_moments([ops.HeadMomentsJob(L_G, terms.d2, mu, S, lower=lower, noise=z, probs=probs, seed=1,
+                                                offset=position(), **more)])
+
+    def rel(a, b):
+        return float(torch.linalg.norm(a.double() - b.double()) / torch.linalg.norm(b.double()))
+
+    row = dict(N=N, K=K, features=IN + 1, S=S)
+    z = torch.randn(N, S, K, device=dev)
+    want = torch_moments(L_G, terms.d2, mu, z)
+    for lower in (True, False):
+        tag = "lower" if lower else "dense"
+        head_mc(lower, z)
+        moments(lower, True, z)
+        row[f"probs_bit_equal_to_head_mc_{tag}"] = bool(torch.equal(probs, plain))
+        for name, got, ref in zip(("probs", "entropy", "probs_sq"), (probs, entropy, probs_sq), want):
+            row[f"rel_difference_to_torch_{name}_{tag}"] = rel(got, ref)
+    del z, want
+    candidates = {}
+    for lower in (True, False):
+        tag = "lower" if lower else "dense"
+        candidates[f"head_mc_{tag}"] = lambda lower=lower: head_mc(lower)
+        candidates[f"moments_all_{tag}"] = lambda lower=lower: moments(lower, True)
+        candidates[f"moments_probs_{tag}"] = lambda lower=lower: moments(lower, False)
+    candidates["torch_moments"] = lambda: torch_moments(L_G, terms.d2, mu)
+    measure(candidates, reps, row)
+    for tag in ("lower", "dense"):
+        row[f"moments_all_over_head_mc_{tag}"] = row[f"moments_all_{tag}_ms"] / row[f"head_mc_{tag}_ms"]
+        row[f"moments_probs_over_head_mc_{tag}"] = row[f"moments_probs_{tag}_ms"] / row[f"head_mc_{tag}_ms"]
+    return row
 
 
 def grid_row(dev, reps):
@@ -136,12 +212,13 @@ def main():
     ap.add_argument("--reps", type=int, default=9)
     ap.add_argument("--json", default=None, help="write the result as one JSON line to this file")
     ap.add_argument("--grid", action="store_true", help="measure the grid of damping pairs (K24) instead")
+    ap.add_argument("--moments", action="store_true", help="measure the entropy split (K25) instead")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_head: needs the GPU (nothing is measured without one)")
     dev = torch.device("cuda:0")
-    if args.grid:
-        row = grid_row(dev, args.reps)
+    if args.grid or args.moments:
+        row = grid_row(dev, args.reps) if args.grid else moments_row(dev, args.reps)
         row["device"] = torch.cuda.get_device_name(0)
         print(json.dumps(row), flush=True)
         if args.json:
