@@ -14,6 +14,7 @@ import torch
 import torch.nn.functional as F
 
 from conftest import identity_residual_bound, rel_fro
+from exact_inputs import assert_exact_range, exact_gram, nonzero_ints, pow2_scale
 
 pytestmark = pytest.mark.gpu
 BAR = 1e-4            # the parity bar of every factor
@@ -127,6 +128,84 @@ def test_factor_against_float64_and_the_plain_build_of_the_torch_stack(gpu, name
     plain = torch.full_like(dst, float("nan"))
     ops.kfac_accumulate([ops.FactorJob(stack, plain, k[1:], s[1:], p[1:], bias, scale, True)])
     assert torch.equal(dst, plain)
+
+
+def _fenced_copy(t, gpu, offset):
+    """A copy of `t` inside NaN-filled memory, `offset` floats past a 16-byte boundary."""
+    fence = torch.full((t.numel() + 4096 + 64,), float("nan"), device=gpu)
+    start = 2048 + offset
+    view = fence[start:start + t.numel()].view(t.shape)
+    view.copy_(t)
+    return view
+
+
+def _assert_exact(dst, want, what):
+    got = dst.double()
+    assert torch.equal(got, want), (what, int((got != want).sum()), float((got - want).abs().max()))
+    assert torch.equal(dst, dst.t()), what
+
+
+@functools.lru_cache(maxsize=None)
+def exact_case(name):
+    """An integer-valued source of a case (tests/exact_inputs.py), the unscaled integer Grams of its 3-D unfold in float64
+    (without and with the ones row), formed on the GPU once, and a power-of-two scale."""
+    shape, k, s, p = geometry(name)
+    gpu = torch.device("cuda:0")
+    x = nonzero_ints(shape, torch.Generator().manual_seed(sum(map(ord, name)) + 1))
+    X, L = im2col3d(x.double().to(gpu), k, s, p)
+    assert_exact_range(3, shape[0] * L, rounds=2)
+    return x, {False: exact_gram(X), True: exact_gram(X, ones_row=True)}, pow2_scale(shape[0] * L)
+
+
+@pytest.mark.parametrize("name, bias", [(n, True) for n in CASES] + [(n, False) for n in NO_BIAS])
+def test_conv3d_factor_exact_on_integer_inputs(gpu, name, bias):
+    """Every Conv3d case again, bit for bit: a source uniform in {+-1, +-2, +-3} (none zero, so every element moves the
+    result) and a power-of-two scale.  Every product and partial sum is an integer below 2^24, so the depth gather and the
+    plain build of the stack have one right answer in any summation order: ``scale * exact`` after a first call, twice
+    that after an accumulating one.  The source sits in NaN-filled memory, at an aligned start and 4
+    bytes past one."""
+    from curvature_amd import ops
+    x, exact, scale = exact_case(name)
+    n = dim_of(name, bias)
+    for offset in (0, 1):
+        xs = _fenced_copy(x, gpu, offset)
+        dst = torch.full((n, n), float("nan"), device=gpu)
+        for rounds in (1, 2):
+            ops.kfac_accumulate_conv3d([conv3d_job(name, xs, dst, bias, scale, first=rounds == 1)])
+            _assert_exact(dst, rounds * scale * exact[bias], (offset, rounds))
+
+
+@pytest.mark.parametrize("which", [0, 2], ids=["k5_p2", "k3_s2"])
+def test_conv1d_factors_exact_on_integer_inputs(gpu, which):
+    """The two Conv1d layers of `make_model1d` on integer-valued (N, C, L) records, through the jobs `ops.factor_jobs` makes
+    for them (the Conv2d build of the (N, C, 1, L) views): both factors bit for bit, as above."""
+    from curvature_amd import ops
+    layer = make_model1d(torch.device("cpu"))[which]
+    gen = torch.Generator().manual_seed(40 + which)
+    N, length = 6, 32
+    x = nonzero_ints((N, layer.in_channels, length), gen)
+    L = (length + 2 * layer.padding[0] - layer.kernel_size[0]) // layer.stride[0] + 1
+    g = nonzero_ints((N, layer.out_channels, L), gen)
+    assert_exact_range(3, N * L, rounds=2)
+    rows = F.unfold(x.double().to(gpu).unsqueeze(2), (1,) + layer.kernel_size, padding=(0,) + layer.padding,
+                    stride=(1,) + layer.stride)
+    assert rows.shape[2] == L
+    A_exact = exact_gram(rows.transpose(0, 1).reshape(rows.shape[1], -1), ones_row=True)
+    G_exact = exact_gram(g.double().to(gpu).transpose(0, 1).reshape(g.shape[1], -1))
+    scale_a = pow2_scale(N * L)
+    scale_g = 4.0 * scale_a
+    for offset in (0, 1):
+        sides = ops.factor_jobs(layer, _fenced_copy(x, gpu, offset), _fenced_copy(g, gpu, offset))
+        assert type(sides.a) is ops.FactorJob and type(sides.g) is ops.FactorJob and (sides.N, sides.L) == (N, L)
+        A = torch.full((sides.n, sides.n), float("nan"), device=gpu)
+        G = torch.full((sides.m, sides.m), float("nan"), device=gpu)
+        sides.a.dst, sides.a.scale = A, scale_a
+        sides.g.dst, sides.g.scale = G, scale_g
+        for rounds in (1, 2):
+            sides.a.first = sides.g.first = rounds == 1
+            ops.kfac_accumulate([sides.a, sides.g])
+            _assert_exact(A, rounds * scale_a * A_exact, ("A", offset, rounds))
+            _assert_exact(G, rounds * scale_g * G_exact, ("G", offset, rounds))
 
 
 def test_the_grouped_launch_case_is_above_the_small_launch_form(gpu):

@@ -2,6 +2,7 @@
 against an fp64 oracle of the zero-stuffed input, its bit properties and memory edges, and the estimators end to end on
 the DCGAN generator and the U-Net (samplers through the weight permutation, autocast, graph replay, a 2-rank shard,
 save / load, poisoned scratch)."""
+import functools
 import os
 import re
 import subprocess
@@ -11,6 +12,7 @@ import pytest
 import torch
 
 from conftest import rel_fro
+from exact_inputs import assert_exact_range, exact_gram, nonzero_ints, pow2_scale
 from test_conv_transpose_cpu import convt_patches
 
 pytestmark = pytest.mark.gpu
@@ -98,6 +100,45 @@ def _job(layer, x, out_size, dst, first=True, scale=1.0):
     from curvature_amd import ops
     return ops.ConvTFactorJob(x, dst, layer.kernel_size, layer.stride, layer.padding, out_size, layer.bias is not None,
                               scale, first)
+
+
+@functools.lru_cache(maxsize=None)
+def _exact_case(case):
+    """(layer, x, output size, A_exact, scale) of a case with an integer-valued input (tests/exact_inputs.py): the
+    unscaled integer Gram of `convt_patches` in float64, the product on the GPU, once per case."""
+    cin, cout, k, s, p, op, N, H, W, bias, osize = case
+    layer = torch.nn.ConvTranspose2d(cin, cout, k, s, p, op, bias=bias)
+    out = osize or tuple((n - 1) * layer.stride[d] - 2 * layer.padding[d] + layer.kernel_size[d] + layer.output_padding[d]
+                         for d, n in enumerate((H, W)))
+    terms = N * out[0] * out[1]
+    assert_exact_range(3, terms, rounds=2)
+    x = nonzero_ints((N, cin, H, W), torch.Generator().manual_seed(23))
+    A_exact = exact_gram(convt_patches(x, layer, out).to("cuda:0"), ones_row=bias)
+    return layer, x, out, A_exact, pow2_scale(terms)
+
+
+@pytest.mark.parametrize("case", CASES)
+def test_factors_match_exact_integers(gpu, case):
+    """Every case again, bit for bit: an input uniform in {+-1, +-2, +-3} (none zero, so every element moves the result)
+    and a power-of-two scale.  Every product and partial sum is an integer below 2^24, so the window copies, the phase
+    Grams on the fp32 MFMA and the assembly have one right answer in any summation order: ``scale * exact`` after a first
+    call, twice that after an accumulating one, exact zeros between taps of different residues included (DESIGN.md
+    section 5).  The source sits in NaN-filled memory, at an aligned start and 4 bytes past one."""
+    from curvature_amd import ops
+    layer, x, out, A_exact, scale = _exact_case(case)
+    n = A_exact.shape[0]
+    for offset in (0, 1):
+        fence = torch.full((x.numel() + 4096 + 64,), float("nan"), device=gpu)
+        start = 2048 + offset
+        xs = fence[start:start + x.numel()].view(x.shape)
+        xs.copy_(x)
+        a = torch.full((n, n), float("nan"), device=gpu)
+        for rounds in (1, 2):
+            ops.kfac_accumulate_convt([_job(layer, xs, out, a, first=rounds == 1, scale=scale)])
+            got = a.double()
+            want = rounds * scale * A_exact
+            assert torch.equal(got, want), (offset, rounds, int((got != want).sum()), float((got - want).abs().max()))
+            assert torch.equal(a, a.t()), (offset, rounds)
 
 
 def test_first_accumulate_and_determinism(gpu):

@@ -14,6 +14,7 @@ import torch
 import torch.nn.functional as F
 
 from conftest import identity_residual_bound, rel_fro
+from exact_inputs import assert_exact_range, conv_rows, exact_gram, nonzero_ints, pow2_scale
 
 pytestmark = pytest.mark.gpu
 BAR = 1e-4            # the parity bar of every factor
@@ -99,6 +100,41 @@ def test_factor_against_float64(gpu, name, bias):
     assert torch.equal(got, got.t())
     if bias:                                                                          # the ones row against itself: K / K
         assert abs(float(got[-1, -1]) - 1.0) <= 1e-6
+
+
+@functools.lru_cache(maxsize=None)
+def exact_case(name):
+    """An integer-valued source of a case (tests/exact_inputs.py), the unscaled integer Grams of its dilated ``F.unfold`` in
+    float64 (without and with the ones row), formed on the GPU once, and a power-of-two scale."""
+    N, C, H, W, k, d, p = CASES[name]
+    gpu = torch.device("cuda:0")
+    x = nonzero_ints((N, C, H, W), torch.Generator().manual_seed(sum(map(ord, name)) + 1))
+    rows = conv_rows(x.to(gpu), pair(k), 1, pair(p), dilation=pair(d))
+    assert_exact_range(3, rows.shape[1], rounds=2)
+    return x, {False: exact_gram(rows), True: exact_gram(rows, ones_row=True)}, pow2_scale(rows.shape[1])
+
+
+@pytest.mark.parametrize("name, bias", [(n, True) for n in CASES] + [(n, False) for n in NO_BIAS])
+def test_factor_exact_on_integer_inputs(gpu, name, bias):
+    """Every case again, bit for bit: a source uniform in {+-1, +-2, +-3} (none zero, so every element moves the result)
+    and a power-of-two scale.  Every product and partial sum is an integer below 2^24, so the gather pass, the plain builds
+    of the residue classes, their sum in `dst` and the bias corner of the empty classes have one right answer in any
+    summation order: ``scale * exact`` after a first call, twice that after an accumulating one.
+    The source sits in NaN-filled memory, at an aligned start and 4 bytes past one."""
+    from curvature_amd import ops
+    x, exact, scale = exact_case(name)
+    n = dim_of(name, bias)
+    for offset in (0, 1):
+        fence = torch.full((x.numel() + 4096 + 64,), float("nan"), device=gpu)
+        start = 2048 + offset
+        xs = fence[start:start + x.numel()].view(x.shape)
+        xs.copy_(x)
+        dst = torch.full((n, n), float("nan"), device=gpu)
+        for rounds in (1, 2):
+            ops.kfac_accumulate_dilated([dilated_job(name, xs, dst, bias, scale, first=rounds == 1)])
+            got, want = dst.double(), rounds * scale * exact[bias]
+            assert torch.equal(got, want), (offset, rounds, int((got != want).sum()), float((got - want).abs().max()))
+            assert torch.equal(dst, dst.t()), (offset, rounds)
 
 
 @pytest.mark.parametrize("name", ["a", "b"])

@@ -1,6 +1,7 @@
 """KFAC for grouped and depthwise convolutions: one Kronecker pair per group (curv_kfac_group_accumulate), checked against an
 fp64 F.unfold of each channel slice, against G ordinary layers run through today's KFAC, and through every sampler, the
 graph capture, save / load and a 2-rank layer shard."""
+import functools
 import os
 import subprocess
 import sys
@@ -10,6 +11,7 @@ import torch
 import torch.nn.functional as F
 
 from conftest import rel_fro
+from exact_inputs import assert_exact_range, conv_rows, exact_gram, flat_rows, nonzero_ints, pow2_scale
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -84,6 +86,68 @@ def test_factors_match_fp64_unfold(gpu, case):
     for k in range(A.shape[0]):                      # every group, not only the norm over all
         assert rel_fro(A[k], RA[k]) < TOL and rel_fro(G[k], RG[k]) < TOL
         assert torch.equal(A[k], A[k].t()) and torch.equal(G[k], G[k].t())
+
+
+@functools.lru_cache(maxsize=None)
+def _exact_case(case):
+    """(layer, x, g, stacked A_exact, stacked G_exact, scale_A, scale_G) of a case with integer-valued records
+    (tests/exact_inputs.py): the unscaled integer Gram of ``F.unfold`` of each channel slice in float64, on the GPU."""
+    cin, cout, k, stride, padding, groups, bias, N, H, *W = case
+    gpu = torch.device("cuda:0")
+    layer = torch.nn.Conv2d(cin, cout, k, stride=stride, padding=padding, groups=groups, bias=bias)
+    gen = torch.Generator().manual_seed(17)
+    x = nonzero_ints((N, cin, H, W[0] if W else H), gen)
+    with torch.no_grad():
+        out_shape = layer(x).shape
+    g = nonzero_ints(out_shape, gen)
+    terms = N * out_shape[2] * out_shape[3]
+    assert_exact_range(3, terms, rounds=2)
+    cg, mg = cin // groups, cout // groups
+    xs, gs = x.to(gpu), g.to(gpu)
+    As = [exact_gram(conv_rows(xs[:, q * cg:(q + 1) * cg], layer.kernel_size, layer.stride, layer.padding), ones_row=bias)
+          for q in range(groups)]
+    Gs = [exact_gram(flat_rows(gs[:, q * mg:(q + 1) * mg])) for q in range(groups)]
+    scale = pow2_scale(terms)
+    return layer, x, g, torch.stack(As), torch.stack(Gs), scale, 4.0 * scale
+
+
+def _fenced_copy(t, gpu, pad=4096):
+    """A copy of `t` on the GPU that starts right after and ends right before NaN-filled memory."""
+    buf = torch.full((pad + t.numel() + pad,), float("nan"), device=gpu)
+    buf[pad:pad + t.numel()] = t.reshape(-1).to(gpu)
+    return buf[pad:pad + t.numel()].view(t.shape)
+
+
+def _assert_exact(dst, want, what):
+    got = dst.double()
+    assert torch.equal(got, want), (what, int((got != want).sum()), float((got - want).abs().max()))
+    assert torch.equal(dst, dst.transpose(1, 2)), what
+
+
+@pytest.mark.parametrize("case", CASES)
+def test_factors_exact_on_integer_inputs(gpu, case):
+    """Every case again, bit for bit: records uniform in {+-1, +-2, +-3} (none zero, so every element moves the result)
+    and power-of-two scales, through the `GroupFactorJob`s `ops.factor_jobs` makes for the layer.  Every product and
+    partial sum is an integer below 2^24, so the Gram kernels, the slice reduce, the patch sums of the bias row and the
+    pixel count of its corner have one right answer in any summation order: ``scale * exact`` in every group after a
+    first call, twice that after an accumulating one."""
+    from curvature_amd import ops
+    layer, x, g, A_exact, G_exact, scale_a, scale_g = _exact_case(case)
+    sides = ops.factor_jobs(layer, _fenced_copy(x, gpu), _fenced_copy(g, gpu))
+    assert type(sides.a) is ops.GroupFactorJob and type(sides.g) is ops.GroupFactorJob
+    A = torch.full((sides.groups, sides.n, sides.n), float("nan"), device=gpu)
+    G = torch.full((sides.groups, sides.m, sides.m), float("nan"), device=gpu)
+    sides.a.dst, sides.a.scale, sides.a.first = A, scale_a, True
+    sides.g.dst, sides.g.scale, sides.g.first = G, scale_g, True
+    ops.kfac_accumulate_groups([sides.a, sides.g])
+    torch.cuda.synchronize()
+    _assert_exact(A, scale_a * A_exact, "A")
+    _assert_exact(G, scale_g * G_exact, "G")
+    sides.a.first = sides.g.first = False
+    ops.kfac_accumulate_groups([sides.a, sides.g])
+    torch.cuda.synchronize()
+    _assert_exact(A, 2 * scale_a * A_exact, "A accumulated")
+    _assert_exact(G, 2 * scale_g * G_exact, "G accumulated")
 
 
 def test_split_equivalence(gpu):

@@ -2,6 +2,7 @@
 ABI 12): every geometry against fp64 of the upcast input and against today's fp32 build of the same tensors (`.float()`
 copies), bit properties, the accumulation flags, autocast end to end, GradScaler, graph replay, a 2-rank shard and
 sources that end right before NaN-filled memory."""
+import functools
 import os
 import re
 import subprocess
@@ -12,6 +13,7 @@ import torch
 import torch.nn.functional as F
 
 from conftest import rel_fro
+from exact_inputs import assert_exact_range, conv_rows, exact_gram, flat_rows, nonzero_ints, pow2_scale, wide_ints
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -98,6 +100,105 @@ def test_geometry_against_fp64_and_fp32_path(gpu, case, dtype):
         print(f"{case} {dtype} side {side}: rel_fro vs fp64 {e64:.2e}, vs fp32 path {e32:.2e}")
         assert e64 < TOL_FP64 and e32 < TOL_FP32
         assert torch.equal(got, got.t())
+
+
+def _fenced_copy(t, gpu, pad=4096):
+    """A copy of `t` on the GPU that starts right after and ends right before NaN-filled memory."""
+    buf = torch.full((pad + t.numel() + pad,), float("nan"), device=gpu, dtype=t.dtype)
+    buf[pad:pad + t.numel()] = t.reshape(-1).to(gpu)
+    return buf[pad:pad + t.numel()].view(t.shape)
+
+
+@functools.lru_cache(maxsize=None)
+def _exact_case(case, dtype):
+    """(layer, x, g, A_exact, G_exact, scale_A, scale_G) of a case with integer-valued half-precision records
+    (tests/exact_inputs.py): the unscaled integer Grams in float64, formed on the GPU once per case."""
+    gpu = torch.device("cuda:0")
+    gen = torch.Generator().manual_seed(99)
+    if case[0] == "linear":
+        _, N, C, out, bias, *T = case
+        layer = torch.nn.Linear(C, out, bias=bias)
+        x, g = nonzero_ints((N, *T, C), gen, dtype), nonzero_ints((N, *T, out), gen, dtype)
+        rows_a, rows_g = x.to(gpu).double().reshape(-1, C).t(), g.to(gpu).double().reshape(-1, out).t()
+    else:
+        _, cin, cout, k, s, p, bias, N, H, *W = case
+        W = W[0] if W else H
+        layer = torch.nn.Conv2d(cin, cout, k, stride=s, padding=p, bias=bias)
+        Ho, Wo = (H + 2 * p - k) // s + 1, (W + 2 * p - k) // s + 1
+        x, g = nonzero_ints((N, cin, H, W), gen, dtype), nonzero_ints((N, cout, Ho, Wo), gen, dtype)
+        rows_a, rows_g = conv_rows(x.to(gpu), k, s, p), flat_rows(g.to(gpu))
+    terms = rows_a.shape[1]
+    assert rows_g.shape[1] == terms
+    assert_exact_range(3, terms, rounds=2)
+    scale = pow2_scale(terms)
+    return layer, x, g, exact_gram(rows_a, ones_row=bias), exact_gram(rows_g), scale, 4.0 * scale
+
+
+def _assert_exact(dst, want, what):
+    got = dst.double()
+    assert torch.equal(got, want), (what, int((got != want).sum()), float((got - want).abs().max()))
+    assert torch.equal(dst, dst.t()), what
+
+
+@pytest.mark.parametrize("dtype", DTYPES, ids=["bf16", "fp16"])
+@pytest.mark.parametrize("case", CASES, ids=[str(i) for i in range(len(CASES))])
+def test_geometry_exact_on_integer_inputs(gpu, case, dtype):
+    """Every geometry again, bit for bit: records uniform in {+-1, +-2, +-3} (exact in bf16 and fp16, none zero) and
+    power-of-two scales, through the jobs `ops.factor_jobs` makes for the layer.  Every product and partial sum is an
+    integer below 2^24, so the bf16 / fp16 MFMA with fp32 accumulation and the slice reduce have one right answer in any
+    summation order: ``scale * exact`` after a first call and twice that after an accumulating one (DESIGN.md section
+    5).  fp16 also with the gradients scaled by 2^12 and the G scale divided by 2^24, what ``grad_scale = 2**12`` does."""
+    from curvature_amd import ops
+    layer, x, g, A_exact, G_exact, scale_a, scale_g = _exact_case(case, dtype)
+    sides = ops.factor_jobs(layer, _fenced_copy(x, gpu), _fenced_copy(g, gpu))
+    assert type(sides.a) is ops.HalfFactorJob and type(sides.g) is ops.HalfFactorJob
+    A = torch.full((sides.n, sides.n), float("nan"), device=gpu)
+    G = torch.full((sides.m, sides.m), float("nan"), device=gpu)
+    sides.a.dst, sides.a.scale, sides.a.first = A, scale_a, True
+    sides.g.dst, sides.g.scale, sides.g.first = G, scale_g, True
+    ops.kfac_accumulate_half([sides.a, sides.g])
+    torch.cuda.synchronize()
+    _assert_exact(A, scale_a * A_exact, "A")
+    _assert_exact(G, scale_g * G_exact, "G")
+    sides.a.first = sides.g.first = False
+    ops.kfac_accumulate_half([sides.a, sides.g])
+    torch.cuda.synchronize()
+    _assert_exact(A, 2 * scale_a * A_exact, "A accumulated")
+    _assert_exact(G, 2 * scale_g * G_exact, "G accumulated")
+    if dtype == torch.float16:
+        scaled = ops.factor_jobs(layer, None, _fenced_copy(g * 2 ** 12, gpu)).g
+        G2 = torch.full_like(G, float("nan"))
+        scaled.dst, scaled.scale, scaled.first = G2, scale_g / 2.0 ** 24, True
+        ops.kfac_accumulate_half([scaled])
+        torch.cuda.synchronize()
+        _assert_exact(G2, scale_g * G_exact, "G from gradients scaled by 2^12")
+
+
+@pytest.mark.parametrize("dtype", DTYPES, ids=["bf16", "fp16"])
+@pytest.mark.parametrize("shape, kernel", [((128, 40), 1), ((2, 40, 8, 8), 1), ((2, 5, 8, 8), 3)],
+                         ids=["linear", "conv1x1", "conv3x3"])
+def test_accumulation_is_fp32(gpu, shape, kernel, dtype):
+    """Odd 8-bit integers are exact in bf16 and fp16; their products have 16 bits and the 128 terms of an entry sum to less
+    than 2^24.  The factor is the exact Gram only if the MFMA accumulates in fp32 and the slices are summed in fp32: a
+    half-precision accumulator or a narrowed partial sum holds another number (tests/test_exact_inputs_cpu.py)."""
+    from curvature_amd import ops
+    gen = torch.Generator().manual_seed(8)
+    x = wide_ints(shape, gen, 8, dtype)
+    pad = (kernel - 1) // 2
+    rows = flat_rows(x.to(gpu)) if kernel == 1 else conv_rows(x.to(gpu), kernel, 1, pad)
+    assert rows.shape[1] == 128
+    assert_exact_range(255, 128, rounds=2)
+    want = exact_gram(rows)
+    n = rows.shape[0]
+    A = torch.full((n, n), float("nan"), device=gpu)
+    job = ops.HalfFactorJob(_fenced_copy(x, gpu), A, (kernel, kernel), (1, 1), (pad, pad), False, 0.5, True)
+    ops.kfac_accumulate_half([job])
+    torch.cuda.synchronize()
+    _assert_exact(A, 0.5 * want, "first")
+    job.first = False
+    ops.kfac_accumulate_half([job])
+    torch.cuda.synchronize()
+    _assert_exact(A, want, "accumulated")
 
 
 @pytest.mark.parametrize("dtype", DTYPES, ids=["bf16", "fp16"])

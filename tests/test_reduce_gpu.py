@@ -13,6 +13,7 @@ import torch
 import torch.nn.functional as F
 
 from conftest import identity_residual_bound, rel_fro
+from exact_inputs import assert_exact_range, exact_gram, nonzero_ints, pow2_scale
 
 pytestmark = pytest.mark.gpu
 BAR = 1e-4            # the parity bar of every factor
@@ -124,6 +125,100 @@ def test_factor_and_rows_against_float64(gpu, name, bias):
     assert torch.equal(got, got.t())                                                  # symmetric bit for bit
     if bias:                                                                          # the ones column against itself: N / N
         assert abs(float(got[-1, -1]) - 1.0) <= 1e-6
+
+
+# Exactness cases (tests/exact_inputs.py).  The reduce pass multiplies a mean row by 1 / L, which is exact only where L - the
+# output pixels Ho Wo of a plane, the tokens T - is a power of two; a sum row (the G side) is exact at any L.
+# name: (shape, kernel, stride, padding, mean) for planes, (shape, mean) for tokens
+EXACT_PLANES = {
+    "p8": ((2, 3, 8, 8), 3, 1, 1, True),                 # L = 64
+    "p8x4": ((3, 5, 8, 4), 1, 1, 0, True),               # L = 32, 1x1
+    "p_s2": ((2, 3, 8, 8), 3, 2, 1, True),               # L = 16, strided window
+    "e": ((2, 4, 8, 8), 1, 2, 0, True),                  # L = 16, the sub-grid of case e
+    "many": ((4, 130, 4, 4), 3, 1, 1, True),             # L = 16, dim 1170 / 1171: many small planes per workgroup
+    "long": ((1, 2, 128, 64), 3, 1, 1, True),            # L = 8192: a plane longer than RD_TILE (4096), walked in pieces
+    "long1x1": ((2, 2, 64, 128), 1, 1, 0, True),         # the same through the 1x1 window
+    "g_sum": ((2, 3, 5, 7), 1, 1, 0, False),             # sums: any L
+    "g_long": ((1, 2, 70, 70), 1, 1, 0, False),
+}
+EXACT_TOKENS = {
+    "t16": ((2, 16, 70), True),                          # T = 16, E = 70
+    "t64": ((2, 64, 130), True),                         # T E above RD_TILE: several pieces
+    "t4wide": ((2, 4, 4500), True),                      # rows longer than the tile
+    "t_sum": ((2, 5, 7), False),
+    "tbig_sum": ((2, 300, 130), False),
+}
+EXACT = [(n, b) for n, c in EXACT_PLANES.items() for b in ((True, False) if c[4] else (False,))] + \
+        [(n, b) for n, c in EXACT_TOKENS.items() for b in ((True, False) if c[1] else (False,))]
+
+
+@functools.lru_cache(maxsize=None)
+def exact_case(name):
+    """(source, integer per-sample SUMS (N, dim) in float64, L if the row is a mean else 1, job arguments): made once."""
+    gen = torch.Generator().manual_seed(seed_of(name))
+    if name in EXACT_PLANES:
+        shape, k, s, p, mean = EXACT_PLANES[name]
+        x = nonzero_ints(shape, gen)
+        cols = F.unfold(x.double(), pair(k), padding=pair(p), stride=pair(s))
+        sums, L = cols.sum(2), cols.shape[2]
+        args = dict(kernel=pair(k), stride=pair(s), padding=pair(p), mean=mean)
+    else:
+        from curvature_amd import _lib
+        shape, mean = EXACT_TOKENS[name]
+        x = nonzero_ints(shape, gen)
+        sums, L = x.double().sum(1), shape[1]
+        args = dict(form=_lib.REDUCE_TOKEN, mean=mean)
+    if mean:
+        assert L & (L - 1) == 0, "a mean row is exact only over a power-of-two count"
+    # the rows are sums / L: dyadic fractions whose products and sums over the N samples are exact while those of the
+    # integer sums stay below 2^24 (the ones column has a one-bit significand and does not count)
+    assert_exact_range(int(sums.abs().max()), shape[0], rounds=2)
+    return x, sums, (L if mean else 1), args
+
+
+@pytest.mark.parametrize("name, bias", EXACT, ids=[f"{n}-{'bias' if b else 'nobias'}" for n, b in EXACT])
+def test_factor_exact_on_integer_inputs(gpu, name, bias):
+    """Bit for bit: a source uniform in {+-1, +-2, +-3} (none zero, so every element moves the result) and a power-of-two
+    scale.  Every per-sample sum is an integer below 2^24 whatever the order of its pieces, the division by a power-of-two
+    L is exact, and the Gram of the N rows has exact products and sums: ``scale * exact`` after a first call, twice that
+    after an accumulating one.  The reference is the integer Gram of the per-sample sums [and a
+    column of L] divided by L^2.  The source sits in NaN-filled memory, at an aligned start and 4 bytes past one; the rows
+    the pass leaves in its scratch are exact too."""
+    from curvature_amd import ops
+    x, sums, L, args = exact_case(name)
+    N = sums.shape[0]
+    rows = torch.cat([sums, torch.full((N, 1), float(L), dtype=torch.float64)], dim=1) if bias else sums
+    scale = pow2_scale(N)
+    want = (exact_gram(rows.t()) / L ** 2).to(gpu)
+    n = rows.shape[1]
+    for offset in (0, 1):
+        fence = torch.full((x.numel() + 4096 + 64,), float("nan"), device=gpu)
+        start = 2048 + offset
+        xs = fence[start:start + x.numel()].view(x.shape)
+        xs.copy_(x)
+        dst = torch.full((n, n), float("nan"), device=gpu)
+        for rounds in (1, 2):
+            ops.kfac_accumulate_reduce([ops.ReduceFactorJob(xs, dst, has_bias=bias, scale=scale, first=rounds == 1, **args)])
+            got = dst.double()
+            assert torch.equal(got, rounds * scale * want), (offset, rounds, int((got != rounds * scale * want).sum()))
+            assert torch.equal(dst, dst.t()), (offset, rounds)
+        if not ops._POISON:                              # (a poisoned workspace is refilled with NaN when it is handed out)
+            ws = ops.workspace(1, gpu, "kfac_reduce")
+            left = ws[:sums.numel() * 4].view(torch.float32).view(sums.shape).cpu().double()
+            assert torch.equal(left, sums / L), offset
+
+
+@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16], ids=["bf16", "fp16"])
+@pytest.mark.parametrize("name", ["p8", "t16", "g_sum", "tbig_sum"])
+def test_half_sources_exact_on_integer_inputs(gpu, name, dtype):
+    """The same values held as bf16 / fp16 (exact in both): the pass upcasts, so the factor is the fp32 one bit for bit."""
+    from curvature_amd import ops
+    x, sums, L, args = exact_case(name)
+    N, n = sums.shape
+    want = (exact_gram(sums.t()) / L ** 2).to(gpu) * pow2_scale(N)
+    dst = torch.full((n, n), float("nan"), device=gpu)
+    ops.kfac_accumulate_reduce([ops.ReduceFactorJob(x.to(gpu, dtype), dst, scale=pow2_scale(N), first=True, **args)])
+    assert torch.equal(dst.double(), want) and torch.equal(dst, dst.t())
 
 
 def test_padding_only_taps_are_exact_zeros(gpu):

@@ -8,6 +8,7 @@ import pytest
 import torch
 
 from conftest import rel_fro
+from exact_inputs import assert_exact_range, conv_rows, exact_gram, flat_rows, nonzero_ints, pow2_scale, wide_ints
 
 pytestmark = pytest.mark.gpu
 
@@ -177,7 +178,159 @@ def test_conv_factors(gpu, case):
         assert rel_fro(G, 2 * G_ref) < TOL, offset
 
 
-@pytest.mark.parametrize("N,C,Cout,bias", [(100, 400, 120, True), (7, 84, 10, True), (32, 513, 1000, False), (1, 5, 3, True)])
+@functools.lru_cache(maxsize=None)
+def _exact_conv_inputs(case):
+    """(x, g, A_exact, G_exact, scale_A, scale_G) of a case with integer-valued sources (tests/exact_inputs.py): the
+    unscaled integer Grams of ``F.unfold`` in float64, formed on the GPU once per case, and two power-of-two scales."""
+    N, C, H, W, k2, s2, p2, bias, Cout, Ho, Wo = _unpack(case)
+    assert_exact_range(3, N * Ho * Wo, rounds=2)
+    gen = torch.Generator().manual_seed(4321)
+    x, g = nonzero_ints((N, C, H, W), gen), nonzero_ints((N, Cout, Ho, Wo), gen)
+    A_exact = exact_gram(conv_rows(x.to("cuda:0"), k2, s2, p2), ones_row=bias)
+    G_exact = exact_gram(flat_rows(g.to("cuda:0")))
+    scale = pow2_scale(N * Ho * Wo)
+    return x, g, A_exact, G_exact, scale, 4.0 * scale
+
+
+def _assert_exact(dst, want, what):
+    """`dst` holds exactly `want` (float64, every entry a float32 value) and is exactly symmetric."""
+    got = dst.double()
+    assert torch.equal(got, want), (what, int((got != want).sum()), float((got - want).abs().max()))
+    assert torch.equal(dst, dst.t()), what
+
+
+@pytest.mark.parametrize("case", CONV_CASES)
+def test_conv_factors_exact_on_integer_inputs(gpu, case):
+    """Every case of `test_conv_factors` again, bit for bit: sources uniform in {+-1, +-2, +-3} (none zero, so every
+    element moves the result) and a power-of-two scale.  Every product and partial sum is an integer below 2^24, so the
+    fp32 MFMA, the k-slice reduce and the shifted-correlation assembly have one right answer in any summation order:
+    ``scale * exact`` after a first call, twice that after an accumulating one.  No tolerance: an element of a ragged
+    group, a last k-slice or the last pixel of the last sample that is left out or counted twice fails here, where the
+    1e-4 Frobenius bar above lets it through."""
+    from curvature_amd import ops
+    x, g, A_exact, G_exact, scale_a, scale_g = _exact_conv_inputs(case)
+    for offset in OFFSETS:
+        jobs = _conv_jobs(case, fenced_copy(x, offset), fenced_copy(g, offset), gpu)     # destinations start as NaN
+        A, G = jobs[0].dst, jobs[1].dst
+        jobs[0].scale, jobs[1].scale = scale_a, scale_g
+        ops.kfac_accumulate(jobs)
+        torch.cuda.synchronize()
+        _assert_exact(A, scale_a * A_exact, ("A", offset))
+        _assert_exact(G, scale_g * G_exact, ("G", offset))
+        for j in jobs:
+            j.first = False
+        ops.kfac_accumulate(jobs)
+        torch.cuda.synchronize()
+        _assert_exact(A, 2 * scale_a * A_exact, ("A accumulated", offset))
+        _assert_exact(G, 2 * scale_g * G_exact, ("G accumulated", offset))
+
+
+def test_one_dropped_pixel_fails_the_exact_comparison(gpu):
+    """The comparison above has teeth where the Frobenius bar has none: at ResNet-50 layer1 geometry, a source whose last
+    pixel of the last sample is zeroed (what a kernel that drops that pixel computes) moves the float64 factor by less
+    than 1e-4 relative Frobenius under relu(randn) inputs, and here changes exactly the entries the
+    integer reference says it changes - about half of the factor."""
+    from curvature_amd import ops
+    case = (8, 64, 56, 56, 3, 1, 1, False)
+    x, g, A_exact, _, scale, _ = _exact_conv_inputs(case)
+    dropped = x.clone()
+    dropped[-1, :, -1, -1] = 0
+    A_dropped = exact_gram(conv_rows(dropped.to(gpu), (3, 3), (1, 1), (1, 1)))
+    jobs = _conv_jobs(case, fenced_copy(dropped, 0), fenced_copy(g, 0), gpu)[:1]
+    jobs[0].scale = scale
+    ops.kfac_accumulate(jobs)
+    torch.cuda.synchronize()
+    got = jobs[0].dst.double()
+    assert torch.equal(got, scale * A_dropped)
+    changed = int((got != scale * A_exact).sum())
+    print(f"one pixel of 25 088 dropped: {changed} of {got.numel()} entries differ from the exact factor")
+    assert changed == int((A_dropped != A_exact).sum()) and changed > 100000
+
+
+LINEAR_CASES = [(100, 400, 120, True), (7, 84, 10, True), (32, 513, 1000, False), (1, 5, 3, True)]
+
+
+@pytest.mark.parametrize("N,C,Cout,bias", LINEAR_CASES)
+def test_linear_factors_exact_on_integer_inputs(gpu, N, C, Cout, bias):
+    """The Linear cases of `test_linear_factors` bit for bit, as `test_conv_factors_exact_on_integer_inputs`."""
+    from curvature_amd import ops
+    assert_exact_range(3, N, rounds=2)
+    gen = torch.Generator().manual_seed(77)
+    x, g = nonzero_ints((N, C), gen), nonzero_ints((N, Cout), gen)
+    A_exact = exact_gram(flat_rows(x.to(gpu)), ones_row=bias)
+    G_exact = exact_gram(flat_rows(g.to(gpu)))
+    scale_a = pow2_scale(N)
+    scale_g = 1.0 / scale_a
+    for offset in OFFSETS:
+        A = torch.full((C + bias, C + bias), float("nan"), device=gpu)
+        G = torch.full((Cout, Cout), float("nan"), device=gpu)
+        jobs = [ops.FactorJob(fenced_copy(x, offset), A, has_bias=bias, scale=scale_a, first=True),
+                ops.FactorJob(fenced_copy(g, offset), G, scale=scale_g, first=True)]
+        ops.kfac_accumulate(jobs)
+        torch.cuda.synchronize()
+        _assert_exact(A, scale_a * A_exact, ("A", offset))
+        _assert_exact(G, scale_g * G_exact, ("G", offset))
+        for j in jobs:
+            j.first = False
+        ops.kfac_accumulate(jobs)
+        torch.cuda.synchronize()
+        _assert_exact(A, 2 * scale_a * A_exact, ("A accumulated", offset))
+        _assert_exact(G, 2 * scale_g * G_exact, ("G accumulated", offset))
+
+
+@pytest.mark.parametrize("shape", [(1, 70), (1, 513), (1, 70, 1, 1)], ids=["linear70", "linear513", "conv70"])
+def test_fp32_operands_are_not_narrowed(gpu, shape):
+    """Small integers are exact in bf16 too, so a build that narrowed its fp32 operands would pass the tests above.  Here
+    N = 1 and every entry of the factor is ONE product of two odd 12-bit integers: 24 bits, exact in float32, and another
+    number once an operand was rounded to bf16, fp16 or tf32 (tests/test_exact_inputs_cpu.py shows that).  A == x x^T."""
+    from curvature_amd import ops
+    assert_exact_range(4095, 1, rounds=1)
+    gen = torch.Generator().manual_seed(12)
+    x = wide_ints(shape, gen, 12)
+    want = exact_gram(flat_rows(x.to(gpu)))
+    n = shape[1]
+    for offset in OFFSETS:
+        A = torch.full((n, n), float("nan"), device=gpu)
+        ops.kfac_accumulate([ops.FactorJob(fenced_copy(x, offset), A, scale=1.0, first=True)])
+        torch.cuda.synchronize()
+        _assert_exact(A, want, offset)
+
+
+def test_kfac_update_exact_on_integer_records(gpu):
+    """`KFAC.update` end to end on a Conv2d 3x3 / pad 1 over 8 x 8 images and a Linear, N = 4, records set to
+    integer-valued tensors: 1 / (N L) = 2^-8, N / L = 2^-4, 1 / N and N are the scales update() itself passes (the tests
+    above set their own), all powers of two, so `state` is the exact factor bit for bit after one update and twice it
+    after two."""
+    from curvature_amd.curvatures import KFAC
+    N, L = 4, 64
+    conv = torch.nn.Conv2d(3, 5, 3, padding=1)
+    linear = torch.nn.Linear(5 * L, 6)
+    model = torch.nn.Sequential(conv, torch.nn.Flatten(), linear).to(gpu)
+    assert_exact_range(3, N * L, rounds=2)
+    gen = torch.Generator().manual_seed(31)
+    records = {conv: (nonzero_ints((N, 3, 8, 8), gen), nonzero_ints((N, 5, 8, 8), gen)),
+               linear: (nonzero_ints((N, 5 * L), gen), nonzero_ints((N, 6), gen))}
+    xc, gc = (t.to(gpu) for t in records[conv])
+    xl, gl = (t.to(gpu) for t in records[linear])
+    want = {conv: (exact_gram(conv_rows(xc, 3, 1, 1), ones_row=True) / (N * L), exact_gram(flat_rows(gc)) * N / L),
+            linear: (exact_gram(flat_rows(xl), ones_row=True) / N, exact_gram(flat_rows(gl)) * N)}
+    for offset in OFFSETS:
+        kfac = KFAC(model)
+        try:
+            for layer, (x, g) in records.items():
+                kfac.record[layer] = [fenced_copy(x, offset), fenced_copy(g, offset)]
+            for rounds in (1, 2):
+                kfac.update(batch_size=N)
+                torch.cuda.synchronize()
+                for layer in (conv, linear):
+                    for side in (0, 1):
+                        _assert_exact(kfac.state[layer][side], rounds * want[layer][side], (offset, rounds, side))
+        finally:
+            for hook in kfac.hooks:
+                hook.remove()
+
+
+@pytest.mark.parametrize("N,C,Cout,bias", LINEAR_CASES)
 def test_linear_factors(gpu, N, C, Cout, bias):
     from curvature_amd import ops
     o = _oracle()
