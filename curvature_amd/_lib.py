@@ -13,7 +13,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc")
 INCLUDE = os.path.normpath(os.path.join(_HERE, "..", "include"))
 LIB_PATH = os.path.join(CSRC, "libcurv_hip.so")
-SOURCES = ["api.cpp", "collective.cpp", "elementwise.hip", "syrk.hip", "syrk_flat.hip", "syrk_corr.hip", "syrk_pre.hip", "syrk_small.hip", "group_factor.hip", "kfac_half.hip", "convt_factor.hip", "dilated_factor.hip", "conv3d_factor.hip", "reduce_factor.hip", "persample.hip", "persample_dw.hip", "norm_factor.hip", "logit_mc.hip", "head_mc.hip", "head_grid.hip", "invert.hip", "gemm.hip", "inf.hip", "eigh.hip", "eigh_lowrank.hip", "logdet.hip"]
+SOURCES = ["api.cpp", "collective.cpp", "elementwise.hip", "syrk.hip", "syrk_flat.hip", "syrk_corr.hip", "syrk_pre.hip", "syrk_small.hip", "group_factor.hip", "kfac_half.hip", "convt_factor.hip", "dilated_factor.hip", "conv3d_factor.hip", "reduce_factor.hip", "persample.hip", "persample_dw.hip", "norm_factor.hip", "embedding_factor.hip", "logit_mc.hip", "head_mc.hip", "head_grid.hip", "invert.hip", "gemm.hip", "inf.hip", "eigh.hip", "eigh_lowrank.hip", "logdet.hip"]
 HIPCC_FLAGS = ["-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC", "-shared", "-Wall",
                "-Wno-unused-function", "-ldl"]
 
@@ -301,6 +301,25 @@ class curv_norm_desc(ctypes.Structure):
                [(k, ctypes.c_longlong) for k in ("t_cs", "t_rs", "w_rs", "o_stride")]
 
 
+class curv_embedding_desc(ctypes.Structure):
+    """Mirror of ``curv_embedding_desc`` in include/curv_hip.h."""
+    _fields_ = [("idx", ctypes.c_void_p), ("positions", ctypes.c_longlong)] + \
+               [(k, ctypes.c_int32) for k in ("idx_i64", "V", "padding_idx", "first")] + \
+               [("scale", ctypes.c_float), ("reserved", ctypes.c_int32), ("a", ctypes.c_void_p)]
+
+
+class curv_embedding_walk_desc(ctypes.Structure):
+    """Mirror of ``curv_embedding_walk_desc`` in include/curv_hip.h."""
+    _fields_ = [("idx", ctypes.c_void_p), ("g", ctypes.c_void_p)] + \
+               [(k, ctypes.c_longlong) for k in ("positions", "g_sn", "g_st", "g_elems")] + \
+               [(k, ctypes.c_int32) for k in ("idx_i64", "N", "T", "V", "D", "padding_idx", "mode", "first")] + \
+               [(k, ctypes.c_void_p) for k in ("pos", "chunks", "mgroups")] + \
+               [(k, ctypes.c_int32) for k in ("n_pos", "n_chunks", "n_mgroups", "n_slots")] + \
+               [("dst", ctypes.c_void_p), ("dst_rs", ctypes.c_longlong), ("w", ctypes.c_void_p), ("w_rs", ctypes.c_longlong),
+                ("out", ctypes.c_void_p), ("o_stride", ctypes.c_longlong), ("w_kind", ctypes.c_int32),
+                ("alpha", ctypes.c_float), ("reserved", ctypes.c_int32), ("reserved2", ctypes.c_int32)]
+
+
 _DW_RECORD = [("x", ctypes.c_void_p), ("g", ctypes.c_void_p)] + \
              [(k, ctypes.c_longlong) for k in ("x_sn", "x_sc", "x_sh", "x_sw", "x_elems",
                                                "g_sn", "g_sc", "g_sh", "g_sw", "g_elems")] + _SOURCE + _WINDOW + \
@@ -461,6 +480,12 @@ SIGNATURES = {
                                           ctypes.POINTER(ctypes.c_longlong)]),
     "curv_persample_norm_sq_accumulate": (_i, [_vp, ctypes.POINTER(curv_norm_desc), _i, _vp, _sz]),
     "curv_persample_norm_quad_reduce": (_i, [_vp, ctypes.POINTER(curv_norm_desc), _i, _vp, _sz]),
+    "curv_kfac_embedding_workspace_bytes": (_sz, [ctypes.POINTER(curv_embedding_desc), _i]),
+    "curv_kfac_embedding_plan_flops": (_i, [ctypes.POINTER(curv_embedding_desc), _i, ctypes.POINTER(ctypes.c_longlong)]),
+    "curv_kfac_embedding_accumulate": (_i, [_vp, ctypes.POINTER(curv_embedding_desc), _i, _vp, _sz]),
+    "curv_persample_embedding_workspace_bytes": (_sz, [ctypes.POINTER(curv_embedding_walk_desc), _i]),
+    "curv_persample_embedding_sq_accumulate": (_i, [_vp, ctypes.POINTER(curv_embedding_walk_desc), _i, _vp, _sz]),
+    "curv_persample_embedding_quad_reduce": (_i, [_vp, ctypes.POINTER(curv_embedding_walk_desc), _i, _vp, _sz]),
     "curv_persample_gram_reduce": (_i, [_vp, ctypes.POINTER(curv_persample_gram_desc), _i]),
     "curv_logit_mc_workspace_bytes": (_sz, [ctypes.POINTER(curv_logit_mc_desc), _i]),
     "curv_logit_mc_plan_flops": (_i, [ctypes.POINTER(curv_logit_mc_desc), _i, ctypes.POINTER(ctypes.c_longlong)]),
@@ -501,6 +526,9 @@ LOGSUM_LOG, LOGSUM_SQUARES = 0, 1    # CURV_LOGSUM_LOG / _SQUARES (curv_logsum_d
 NORM_GROUP, NORM_POSITION, NORM_GIVEN = 0, 1, 2     # CURV_NORM_* (curv_norm_desc.mode)
 NORM_SIDE_A, NORM_SIDE_G = 0, 1      # CURV_NORM_SIDE_* (curv_norm_desc.side)
 NORM_SPLIT_L, NORM_SLICE = 1024, 32  # CURV_NORM_SPLIT_L, CURV_NORM_SLICE
+EMB_SPLIT_L = 128                   # CURV_EMB_SPLIT_L
+EMB_SQ, EMB_QUAD = 0, 1             # CURV_EMB_SQ / _QUAD (curv_embedding_walk_desc.mode)
+EMB_W_MATRIX, EMB_W_VECTOR = 1, 2   # CURV_EMB_W_* (curv_embedding_walk_desc.w_kind)
 GEMM_TABLE_RESIDENT = 1             # CURV_GEMM_TABLE_RESIDENT
 GEMM_PLAN_FIELDS = 8                # CURV_GEMM_PLAN_FIELDS
 ERR_NOT_PD, ERR_INVALID, ERR_WORKSPACE, ERR_HIP, ERR_NOT_CONVERGED = 1, 2, 3, 4, 5     # CURV_ERR_* of the header

@@ -32,7 +32,8 @@ SUPPORTED_LAYERS = ['Linear', 'Conv2d', 'MultiheadAttention']
 # selectable by name but not part of the default selection (which stays what the reference selects)
 OPTIONAL_LAYERS = ['ConvTranspose2d']
 # layer classes whose parameters are a weight matrix (Wm) and an optional bias
-_MATRIX_LAYERS = ('Linear', 'Conv2d', 'ConvTranspose2d', 'Conv1d', 'Conv3d', 'LayerNorm', 'GroupNorm', 'BatchNorm2d')
+_MATRIX_LAYERS = ('Linear', 'Conv2d', 'ConvTranspose2d', 'Conv1d', 'Conv3d', 'LayerNorm', 'GroupNorm', 'BatchNorm2d',
+                  'Embedding')
 # selectable by name only while `ops.admit_conv_nd` is on
 _ND_LAYERS = ('Conv1d', 'Conv3d')
 # selectable by name only while `ops.admit_norm_layers` is on: Wm = [weight.reshape(C, 1) | bias], one
@@ -56,6 +57,58 @@ def _check_norm(model, layer, what: str, takes: bool) -> None:
                                   f"there is nothing to estimate")
     if layer.weight.numel() < 2:
         raise NotImplementedError(f"{what}: {kind} layer {name} has a single channel, which the stacked factors do not hold")
+
+
+# selectable by name only while `ops.admit_embedding` is on: Wm = weight itself, (V, D), no bias; its rows are
+# the INPUT side (the transpose of the Linear(V, D, bias=False) twin on one-hot rows, whose Wm is weight.T)
+_EMBEDDING_ADVICE = "KFAC (approximation=\"expand\"), or Diagonal, with the weight samplers and functional_variance take the layer"
+
+
+def _is_embedding(layer) -> bool:
+    return layer.__class__.__name__ == 'Embedding'
+
+
+def _bias_of(layer):
+    """The layer's bias parameter, None where it has none (an Embedding has no such attribute)."""
+    return getattr(layer, 'bias', None)
+
+
+def _refuse_embedding(model, layer, what: str) -> None:
+    raise NotImplementedError(f"{what}: the embedding layer {_layer_name(model, layer)} (Embedding) is not supported; "
+                              f"{_EMBEDDING_ADVICE}")
+
+
+def _check_embedding(model, layer, what: str, takes: bool, selected: Sequence[str], shard) -> None:
+    """What the estimators represent of a selected nn.Embedding (`ops.admit_embedding`): a dense lookup of a weight of its
+    own with at least two rows, for KFAC and Diagonal on one rank."""
+    name = _layer_name(model, layer)
+    if not takes:
+        _refuse_embedding(model, layer, what)
+    why = None
+    if layer.max_norm is not None:
+        why = f"has max_norm={layer.max_norm}: the forward pass rewrites the weight, so there is no fixed mean to expand around"
+    elif layer.sparse:
+        why = "has sparse=True: its gradient is a sparse tensor, which the estimators do not read"
+    elif layer.scale_grad_by_freq:
+        why = "has scale_grad_by_freq=True: the gradient PyTorch forms is not the loss's"
+    elif layer.num_embeddings < 2:
+        why = "has a single row, which the factors do not hold"
+    if why is not None:
+        raise NotImplementedError(f"{what}: Embedding layer {name} {why}")
+    for other in model.modules():
+        if other is layer or other.__class__.__name__ not in selected:
+            continue
+        if any(p is layer.weight for p in other.parameters(recurse=False)):
+            raise NotImplementedError(f"{what}: the weight of Embedding layer {name} is also a parameter of the selected layer "
+                                      f"{_layer_name(model, other)} ({other.__class__.__name__}), a tied weight: the curvature "
+                                      f"of a shared parameter is the sum of both layers', which neither layer's factors hold")
+    _check_embedding_shard(model, layer, what, shard)
+
+
+def _check_embedding_shard(model, layer, what: str, shard) -> None:
+    if shard is not None and shard.world > 1:
+        raise NotImplementedError(f"{what}: Embedding layer {_layer_name(model, layer)} under a shard of {shard.world} ranks is "
+                                  f"not supported: the shard planner would price a V^3 inversion for its diagonal factor")
 
 
 def _is_convt(layer) -> bool:
@@ -154,6 +207,8 @@ def _check_reduce(model, layer) -> None:
         why = "an attention layer (its records are (T, N, E), with the batch second)"
     elif kind in _NORM_LAYERS:
         why = "a normalisation layer"
+    elif kind == 'Embedding':
+        why = "an embedding layer (its A factor is the diagonal of token counts)"
     if why is not None:
         name = next((f"'{n}'" for n, mod in model.named_modules() if mod is layer), repr(layer))
         raise NotImplementedError(f'KFAC(approximation="reduce"): layer {name} is {why}, which the '
@@ -207,7 +262,7 @@ def _slots(layer, weight: Tensor, bias: Optional[Tensor]) -> List[_Slot]:
 
 def _live_slots(layer) -> List[_Slot]:
     """`_slots` of the layer's own parameters (what the fused samplers write)."""
-    weight, bias = layer._parameters['weight'], layer._parameters['bias']
+    weight, bias = layer._parameters['weight'], layer._parameters.get('bias')
     return _slots(layer, weight.data, bias.data if bias is not None else None)
 
 
@@ -218,7 +273,7 @@ def _bank_buffers(layer, count: int, device):
     w = layer.weight
     shape = w.shape if _is_convt(layer) else (_wm_rows(layer), w.numel() // _wm_rows(layer))
     weights = torch.empty(count, *shape, dtype=torch.float32, device=device)
-    if layer.bias is None:
+    if _bias_of(layer) is None:
         return weights, None
     return weights, torch.empty(count, _wm_rows(layer), dtype=torch.float32, device=device)
 
@@ -386,6 +441,8 @@ class Curvature(ABC):
     _mha_as_projections = False
     # KFAC, Diagonal: the affine parameters of normalisation layers (`ops.admit_norm_layers`)
     _takes_norm = False
+    # KFAC, Diagonal: the weight of nn.Embedding layers (`ops.admit_embedding`)
+    _takes_embedding = False
     # the `_Arena`s this estimator allocated for its `state` / `inv_state` tensors (None until then): Diagonal and EFB
     # keep the first two, INF the other three (its corrections D, Lambda_lr and r)
     _state_arena = _inv_arena = _corr_arena = _lam_arena = _r_arena = None
@@ -405,7 +462,8 @@ class Curvature(ABC):
             raise TypeError
         for _type in self.layer_types:
             assert _type in SUPPORTED_LAYERS or _type in OPTIONAL_LAYERS or \
-                (ops.conv_nd_admitted() and _type in _ND_LAYERS) or (ops.norm_layers_admitted() and _type in _NORM_LAYERS)
+                (ops.conv_nd_admitted() and _type in _ND_LAYERS) or (ops.norm_layers_admitted() and _type in _NORM_LAYERS) or \
+                (ops.embedding_admitted() and _type == 'Embedding')
         if 'ConvTranspose2d' in self.layer_types:
             for layer in model.modules():
                 if _is_convt(layer):
@@ -418,6 +476,10 @@ class Curvature(ABC):
             for layer in model.modules():
                 if _is_norm(layer) and layer.__class__.__name__ in self.layer_types:
                     _check_norm(model, layer, type(self).__name__, self._takes_norm)
+        if 'Embedding' in self.layer_types:
+            for layer in model.modules():
+                if _is_embedding(layer):
+                    _check_embedding(model, layer, type(self).__name__, self._takes_embedding, self.layer_types, shard)
         self.state = dict()
         self.inv_state = dict()
         # optional layer sharding across ranks (curvature_amd.sharding.Shard); None = own every layer.
@@ -495,7 +557,7 @@ class Curvature(ABC):
         Attention modules (Diagonal only) are not part of the layer partition: rank 0 samples them and their
         projection parameters travel in the same all-gather, so that every rank ends with the same weights."""
         if self.shard is not None and (self.shard.world > 1 or self.shard.force_collective):
-            entries = [[p.data for p in (l.weight, l.bias) if p is not None] for l in self._layers()]
+            entries = [[p.data for p in (l.weight, _bias_of(l)) if p is not None] for l in self._layers()]
             owners = list(self.shard.owner)
             for layer in (self._attention() if self._supports_mha else []):
                 entries.append([p.data for p in (layer.in_proj_weight, layer.in_proj_bias, layer.out_proj.weight,
@@ -606,7 +668,7 @@ class Curvature(ABC):
     def _mean_slots(self, layer) -> List[_Slot]:
         """`_slots` of the layer's mean (MAP) parameters inside ``model_state``."""
         return _slots(layer, self.model_state_of(layer, 'weight'),
-                      self.model_state_of(layer, 'bias') if layer.bias is not None else None)
+                      self.model_state_of(layer, 'bias') if _bias_of(layer) is not None else None)
 
     def _param_ptrs(self, layers, means: bool = True):
         """(params, their addresses, the addresses of their means) of `layers`: the weight and, where there is one, the
@@ -614,9 +676,9 @@ class Curvature(ABC):
         searches them); built by C-level loops, this runs in front of every sample of a BNN loop.  `means=False`: a
         sampler that does not read the means leaves their addresses out."""
         ptr = Tensor.data_ptr
-        params = [p for l in layers for p in (l._parameters['weight'], l._parameters['bias']) if p is not None]
+        params = [p for l in layers for p in (l._parameters['weight'], l._parameters.get('bias')) if p is not None]
         mean = [self.model_state_of(l, nm) for l in layers for nm in ('weight', 'bias')
-                if l._parameters[nm] is not None] if means else ()
+                if l._parameters.get(nm) is not None] if means else ()
         return params, tuple(map(ptr, params)), tuple(map(ptr, mean))
 
     # ------------------------------------------------------------------ recording hooks (KFAC; per-sample Diagonal / EFB)
@@ -651,7 +713,8 @@ class Curvature(ABC):
     def _save_output(self, module, grad_output):
         self.record[module][1] = grad_output         # raw; the reference stores grad * N (curvatures.py:310)
 
-    def _per_sample_layers(self, what: str, advice: str, grouped: bool = False, norm: bool = False) -> List[Module]:
+    def _per_sample_layers(self, what: str, advice: str, grouped: bool = False, norm: bool = False,
+                           embedding: bool = False) -> List[Module]:
         """The selected layers, in ``modules()`` order, after checking that every one has a per-sample form P_n = g_n X_n^T:
         Linear, and Conv2d with groups 1, dilation 1 (any dilation with `ops.admit_dilated`) and integer padding; a Conv3d
         (selectable with `ops.admit_conv_nd`) with `ops.admit_conv3d_per_sample`; with
@@ -696,6 +759,9 @@ class Curvature(ABC):
             elif kind in _NORM_LAYERS and ops.norm_layers_admitted():
                 if not norm:                                 # (`norm`: the caller takes `ops.per_sample_route` "norm")
                     why = f"a normalisation layer; {_NORM_ADVICE}"
+            elif kind == 'Embedding' and ops.embedding_admitted():
+                if not embedding:                            # (the caller takes `ops.per_sample_route` "embedding")
+                    why = f"an embedding layer; {_EMBEDDING_ADVICE}"
             elif kind != 'Linear':
                 why = kind
             if why is not None:
@@ -710,7 +776,8 @@ class Curvature(ABC):
         self.record = dict()
         self._out_size = dict()
         for layer in self._per_sample_layers(f"{what}(per_sample=True)", "select other layer types or use per_sample=False",
-                                             grouped=self._per_sample_groups, norm=self._takes_norm):
+                                             grouped=self._per_sample_groups, norm=self._takes_norm,
+                                             embedding=self._takes_embedding):
             if not isinstance(layer, AttentionProjection):
                 self._record_layer(layer)
                 continue
@@ -1073,7 +1140,7 @@ class Curvature(ABC):
         hypers = self._evidence_pairs("log_prior_grid", hypers)
         assert self.state, "State dict is empty. Did you call 'update' prior to this?"
         resolved = self._resolved(hypers)
-        segments, first, biased, second, counts = [], [], [], [], []
+        segments, first, biased, second, counts, dropped = [], [], [], [], [], []
         for k, (key, _) in enumerate(resolved):
             if isinstance(key, str):
                 raise NotImplementedError(f"{type(self).__name__}.log_prior_grid: the attention entry {key!r} of `state` has "
@@ -1082,7 +1149,7 @@ class Curvature(ABC):
             if not all(v.is_contiguous() for v in views):
                 # (the tap views of a ConvTranspose2d: together they are its weight tensor, which is read whole)
                 views = [self.model_state_of(key, 'weight')] + \
-                    ([self.model_state_of(key, 'bias')] if key.bias is not None else [])
+                    ([self.model_state_of(key, 'bias')] if _bias_of(key) is not None else [])
             weight, rest = views[0], views[1:]
             first.append(len(segments))
             segments.append(ops.LogSumSegment.squares(weight))
@@ -1091,9 +1158,16 @@ class Curvature(ABC):
                 second.append(len(segments))
                 segments.append(ops.LogSumSegment.squares(rest[0]))
             counts.append(sum(v.numel() for v in views))
+            if ops.is_embedding_layer(key) and key.padding_idx is not None:
+                # the padding row is no parameter: its squares and its D entries are taken out again
+                dropped.append((k, len(segments)))
+                segments.append(ops.LogSumSegment.squares(weight[key.padding_idx:key.padding_idx + 1]))
+                counts[-1] -= key.embedding_dim
         out, _ = ops.logsum_grid(segments, 1)
         dev = out.device
         squares = out[torch.tensor(first, device=dev), 0]
+        for k, at in dropped:
+            squares[k] -= out[at, 0]
         if biased:
             squares[torch.tensor(biased, device=dev)] += out[torch.tensor(second, device=dev), 0]
         precisions = torch.tensor([[n for n, _ in points] for _, points in resolved], dtype=torch.float64, device=dev)
@@ -1138,7 +1212,7 @@ class Curvature(ABC):
         for mha in (self._attention() if self._supports_mha else []):
             owned += AttentionProjection.of(mha)
         weights = {l: torch.empty(S, *l.weight.shape, dtype=l.weight.dtype, device=l.weight.device) for l in owned}
-        biases = {l: (torch.empty(S, *l.bias.shape, dtype=l.bias.dtype, device=l.bias.device) if l.bias is not None else None)
+        biases = {l: (torch.empty(S, *l.bias.shape, dtype=l.bias.dtype, device=l.bias.device) if _bias_of(l) is not None else None)
                   for l in owned}
         gather, self._allgather_sampled = self._allgather_sampled, (lambda: None)     # the sets travel when they are loaded
         try:
@@ -1159,7 +1233,7 @@ class Curvature(ABC):
             raise IndexError("replace_from: sample index out of range")
         plans = bank.__dict__.setdefault("_copy_plans", {})
         layers = list(bank.weights.keys())
-        params = [p for l in layers for p in (l._parameters['weight'], l._parameters['bias']) if p is not None]
+        params = [p for l in layers for p in (l._parameters['weight'], l._parameters.get('bias')) if p is not None]
         key = (index, tuple(map(Tensor.data_ptr, params)))
         plan = plans.get(key)
         if plan is None:
@@ -1198,6 +1272,7 @@ class Diagonal(LinearisedPredictive, Curvature):
     _supports_mha = True
     _per_sample_groups = True
     _takes_norm = True
+    _takes_embedding = True
 
     def __init__(self, model: Union[Module, Sequential], layer_types: Union[List[str], str] = None, *, shard=None,
                  per_sample: bool = False):
@@ -1224,14 +1299,18 @@ class Diagonal(LinearisedPredictive, Curvature):
         # blocks of the layer's state - or, a true depthwise one, through the direct kernel
         direct = [l for l in layers if ops.per_sample_route(l) == "depthwise"]
         normed = [l for l in layers if ops.per_sample_route(l) == "norm"]
-        items = ops.per_sample_items([l for l in layers if l not in direct and l not in normed])
+        embedded = [l for l in layers if ops.per_sample_route(l) == "embedding"]
+        for l in embedded:
+            _check_embedding_shard(self.model, l, "Diagonal.update", self.shard)
+        fused = direct + normed + embedded
+        items = ops.per_sample_items([l for l in layers if l not in fused])
         operands = self._per_sample_operands("Diagonal", items) if items else []
-        records = {l: self._records_of("Diagonal", l) for l in direct + normed}
-        device = operands[0][1].device if operands else records[(direct + normed)[0]][0].device
+        records = {l: self._records_of("Diagonal", l) for l in fused}
+        device = operands[0][1].device if operands else records[fused[0]][0].device
         new = [l for l in layers if l not in self.state]
         fresh = {}
         if new:
-            self._state_arena = _Arena([(_wm_rows(l), l.weight.numel() // _wm_rows(l) + int(l.bias is not None))
+            self._state_arena = _Arena([(_wm_rows(l), l.weight.numel() // _wm_rows(l) + int(_bias_of(l) is not None))
                                         for l in new], device)
             fresh = dict(zip(new, self._state_arena.views))
         state = {l: fresh.get(l, self.state.get(l)) for l in layers}
@@ -1245,6 +1324,9 @@ class Diagonal(LinearisedPredictive, Curvature):
         ops.per_sample_norm_sq_accumulate([ops.PerSampleNormJob.of(l, *records[l], name=_layer_name(self.model, l),
                                                                    dst=state[l], alpha=batch_size, first=l in fresh)
                                            for l in normed])
+        ops.per_sample_embedding_sq_accumulate([ops.PerSampleEmbeddingJob.of(l, *records[l], name=_layer_name(self.model, l),
+                                                                             dst=state[l], alpha=batch_size,
+                                                                             first=l in fresh) for l in embedded])
         for layer in layers:
             self.state[layer] = state[layer]
 
@@ -1260,7 +1342,7 @@ class Diagonal(LinearisedPredictive, Curvature):
         fresh = {}
         if new:
             self._state_arena = _Arena(
-                [(_wm_rows(l), l.weight.numel() // _wm_rows(l) + int(l.bias is not None)) for l in new],
+                [(_wm_rows(l), l.weight.numel() // _wm_rows(l) + int(_bias_of(l) is not None)) for l in new],
                 new[0].weight.device)
             fresh = dict(zip(new, self._state_arena.views))
         keys, items = [], []
@@ -1269,8 +1351,10 @@ class Diagonal(LinearisedPredictive, Curvature):
             if name not in self.layer_types:
                 continue
             if name in _MATRIX_LAYERS:
+                if name == 'Embedding':
+                    _check_embedding_shard(self.model, layer, "Diagonal.update", self.shard)
                 if layer in owned:
-                    bias_grad = layer.bias.grad.contiguous().view(-1) if layer.bias is not None else None
+                    bias_grad = layer.bias.grad.contiguous().view(-1) if _bias_of(layer) is not None else None
                     keys.append(layer)
                     # state in Wm layout (out, in*kh*kw [+1]); a ConvTranspose2d gradient is permuted into it
                     items.append((_wm(layer, layer.weight.grad).contiguous(), bias_grad, fresh.get(layer, self.state.get(layer)),
@@ -1315,6 +1399,7 @@ class Diagonal(LinearisedPredictive, Curvature):
             for l in plain:
                 self.inv_state.setdefault(l, arena.get(l))
             ops.rsqrt_affine(states.flat, float(add), float(multiply), out=invs.flat)
+            self._zero_padding_rows()
             return
         for position, (layer, value) in enumerate(self.state.items()):
             # Diagonal uses lists when both are list/tuple (curvatures.py:183); same outcome as _hyper.
@@ -1324,9 +1409,31 @@ class Diagonal(LinearisedPredictive, Curvature):
             if out is None and layer in arena:
                 out = arena[layer]
             self.inv_state[layer] = ops.rsqrt_affine(value, n, s, out=out)
+        self._zero_padding_rows()
+
+    def _padded(self):
+        """[(position in `state`, layer)] of the Embedding layers with a `padding_idx`: that row is not a parameter."""
+        return [(k, l) for k, l in enumerate(self.state)
+                if not isinstance(l, str) and ops.is_embedding_layer(l) and l.padding_idx is not None]
+
+    def _zero_padding_rows(self) -> None:
+        """The `padding_idx` row of an Embedding has no posterior spread: its inverse-state entries are 0, so the samplers
+        leave it at its mean and it adds nothing to a variance."""
+        for _, layer in self._padded():
+            self.inv_state[layer][layer.padding_idx].zero_()
 
     def _log_det_parts(self, hypers):
-        return self._spectrum_log_det(hypers, self.state)
+        rows, total = self._spectrum_log_det(hypers, self.state)
+        padded = self._padded()
+        if padded:
+            # the D entries of a padding row (state 0: log n each) are no parameters: taken out again, in float64
+            resolved = self._resolved(hypers)
+            for k, layer in padded:
+                gone = torch.tensor([layer.embedding_dim * math.log(n) for n, _ in resolved[k][1]], dtype=torch.float64,
+                                    device=rows.device)
+                rows[k] -= gone
+                total -= gone
+        return rows, total
 
     @staticmethod
     def _reuse(prev: Optional[Tensor], like: Tensor) -> Optional[Tensor]:
@@ -1537,6 +1644,14 @@ def _reject_grouped(est, what: str) -> None:
                                       "supported; select other layer types or use KFAC")
 
 
+def _noise_count(first: Tensor, second: Tensor) -> int:
+    """Normal draws one sample of a layer takes, from its pair of inverse factors: n m per Kronecker pair (an Embedding's
+    first entry is the (V,) diagonal: V D)."""
+    if first.dim() == 1:
+        return first.numel() * second.size(-1)
+    return first.numel() // first.size(-1) * second.size(-1)
+
+
 def _pairs(first: Tensor, second: Tensor):
     """(L_A, L_G) of a layer as per-group lists of 2-D views: one pair for an ordinary layer, G for a grouped one."""
     if first.dim() == 3:
@@ -1565,6 +1680,7 @@ class KFAC(LinearisedPredictive, Curvature):
     _mha_as_projections = True
     _per_sample_groups = True
     _takes_norm = True
+    _takes_embedding = True
 
     def __init__(self, model: Union[Module, Sequential], layer_types: Union[List[str], str] = None, *, shard=None,
                  approximation: str = "expand"):
@@ -1603,6 +1719,11 @@ class KFAC(LinearisedPredictive, Curvature):
                 elif name in _NORM_LAYERS:
                     # `_check_norm` has passed; C stacked pairs [A (C, n_g, n_g), G (C, 1, 1)] from the fused pass of
                     # csrc/norm_factor.hip on the records as they are (a BatchNorm2d: in eval mode, `_check_eval`)
+                    self._record_layer(layer)
+                elif name == 'Embedding':
+                    # `_check_embedding` has passed; state = [a (V,), G (D, D)]: the A factor of the bias-free Linear on
+                    # one-hot rows is exactly diagonal - the token histogram of csrc/embedding_factor.hip - and G the
+                    # flat build of grad_output; the record's input is the index tensor
                     self._record_layer(layer)
                 elif name == 'ConvTranspose2d':
                     # Wm = weight.permute(1, 0, 2, 3).reshape(out, -1) [| bias]; A from the phase-split build
@@ -1646,6 +1767,9 @@ class KFAC(LinearisedPredictive, Curvature):
             forward, backward = self.record[layer]
             if (inputs and forward is None) or (grads and backward is None):
                 raise RuntimeError("KFAC.update: no recorded forward/backward pass for a selected layer")
+            embedding = ops.is_embedding_layer(layer)
+            if embedding:
+                _check_embedding_shard(self.model, layer, "KFAC.update", self.shard)
             sides = ops.factor_jobs(layer, forward, backward, self._out_size.get(layer), self.approximation)
             N, L = sides.N, sides.L
             if self.approximation == "reduce":
@@ -1655,7 +1779,8 @@ class KFAC(LinearisedPredictive, Curvature):
                 alloc = torch.empty if (inputs and grads) else torch.zeros
                 dev = (sides.a or sides.g).src.device
                 lead = (sides.groups,) if sides.groups > 1 else ()   # a grouped layer: one Kronecker pair per group
-                self.state[layer] = [alloc(*lead, sides.n, sides.n, dtype=torch.float32, device=dev),
+                a_shape = (sides.n,) if embedding else (*lead, sides.n, sides.n)   # an Embedding: the diagonal of A
+                self.state[layer] = [alloc(*a_shape, dtype=torch.float32, device=dev),
                                      alloc(*lead, sides.m, sides.m, dtype=torch.float32, device=dev)]
                 if inputs and grads:
                     self._fresh.update(((layer, 0), (layer, 1)))
@@ -1728,7 +1853,17 @@ class KFAC(LinearisedPredictive, Curvature):
             n, s = self._hyper(add, multiply, index, max(len(gindex), len(self.state)))
             old = self.inv_state.get(layer, (None, None))
             for side, factor in enumerate(value):
-                if factor.dim() == 3:
+                if factor.dim() == 1:
+                    # the diagonal A of an Embedding: l_a = 1 / sqrt(sqrt(s) a + sqrt(n)) elementwise, the diagonal of what
+                    # the sweep gives for diag(a); 0 for the padding row, which is no parameter
+                    out = old[side]
+                    if out is None or out.shape != factor.shape or out.device != factor.device:
+                        out = torch.empty_like(factor)
+                    ops.rsqrt_affine(factor, math.sqrt(n), math.sqrt(s), out=out)
+                    if layer.padding_idx is not None:
+                        out[layer.padding_idx].zero_()
+                    stacked[(layer, side)] = out
+                elif factor.dim() == 3:
                     # grouped layer: one descriptor per group slice, written in place into the stacked inverse
                     out = old[side]
                     if out is None or out.shape != factor.shape or out.device != factor.device:
@@ -1748,11 +1883,11 @@ class KFAC(LinearisedPredictive, Curvature):
                     where.append((layer, index, side, None))
         # outputs of the previous call are overwritten in place (stable addresses keep the cached launch
         # plan of sample_and_replace valid); RuntimeError if a damped factor is not positive definite
-        self._invert_where = where if stacked else None
+        self._invert_where = where if any(f.dim() == 3 for f in stacked.values()) else None
         try:
             chols = ops.chol_inv_lower(factors, adds, muls, check=check, outs=prev)
         except RuntimeError as exc:
-            if stacked:
+            if self._invert_where:
                 self._raise_not_pd(ops.chol_inv_lower.last_info, exc)
             raise
         self._invert_info = chols.info
@@ -1760,7 +1895,9 @@ class KFAC(LinearisedPredictive, Curvature):
         for layer, value in self.state.items():
             pair = []
             for side, factor in enumerate(value):
-                if factor.dim() == 3:
+                if factor.dim() == 1:
+                    pair.append(stacked[(layer, side)])
+                elif factor.dim() == 3:
                     pair.append(stacked[(layer, side)])
                     pos += factor.shape[0]
                 else:
@@ -1812,6 +1949,7 @@ class KFAC(LinearisedPredictive, Curvature):
             separable=True, grid_missing=None if kept is not None else
             "no eigendecomposition of the current factors: call decompose() after the last update()",
             # depthwise (one output channel per group): T = L_A stacked (C, n_g, n_g), s = L_G stacked (C, 1, 1), in place
+            # (an Embedding, `ops.per_sample_route` "embedding": T = l_a (V,), s = L_G (D, D))
             direct=lambda layer: (self.inv_state[layer][0], None, self.inv_state[layer][1]),
             # its grid: T = U_A stacked, u = the 1 x 1 G factors (their own eigenvalues), v = eig(A) (C, n_g)
             direct_grid=lambda layer: (kept[layer][4], kept[layer][2].view(-1), kept[layer][3], None))
@@ -1830,6 +1968,8 @@ class KFAC(LinearisedPredictive, Curvature):
             if ops.is_norm_layer(layer):
                 raise NotImplementedError(f"KFAC.decompose: the normalisation layer {_layer_name(self.model, layer)} "
                                           f"({layer.__class__.__name__}) is not supported; {_NORM_ADVICE}")
+            if ops.is_embedding_layer(layer):
+                _refuse_embedding(self.model, layer, "KFAC.decompose")
         stacked = ops.per_sample_admits_groups() and ops.per_sample_admits_grouped_joint()
         layers = [l for l, (A, G) in self.state.items() if (A.dim() == 2 and G.dim() == 2) or
                   (stacked and A.dim() == 3 and G.dim() == 3)]
@@ -1859,6 +1999,9 @@ class KFAC(LinearisedPredictive, Curvature):
             self._decomposition[layer] = kept
 
     def _log_det_parts(self, hypers):
+        for layer in self.state:
+            if ops.is_embedding_layer(layer):
+                _refuse_embedding(self.model, layer, "KFAC.log_det_grid")
         kept = getattr(self, "_decomposition", None)
         if kept is None:
             raise RuntimeError("KFAC.log_det_grid: no eigendecomposition of the current factors: call decompose() after the "
@@ -1911,6 +2054,16 @@ class KFAC(LinearisedPredictive, Curvature):
         assert self.inv_state, "Inverse state dict is empty. Did you call 'invert' prior to this?"
         first, second = self.inv_state[layer]
         n, m = first.size(-1), second.size(-1)
+        if first.dim() == 1:
+            # an Embedding: (V, D) = diag(l_a) z L_G^T, the row scale in the product's epilogue
+            if z is None:
+                z = self._randn(n, m, device=first.device)
+            if tuple(z.shape) != (n, m):
+                raise RuntimeError(f"KFAC.sample: noise of an Embedding layer must be ({n}, {m})")
+            out = torch.empty(n, m, dtype=torch.float32, device=first.device)
+            ops.gemm_batched([ops.Gemm(z, second.t(), out, epilogue=ops.EPI_MUL_E, E=first.view(n, 1).expand(n, m),
+                                       tri=ops.TRI_B_UPPER)])
+            return out
         if first.dim() == 3:
             # grouped layer: z (G, n, m); row block g of the (C_out, n) result is (L_A[g] z[g] L_G[g]^T)^T
             G = first.shape[0]
@@ -1951,8 +2104,7 @@ class KFAC(LinearisedPredictive, Curvature):
             flat, pos = None, 0
             if noise is None and owned:        # one generator launch for the whole model
                 dev = self.inv_state[owned[0][1]][0].device
-                total = sum(self.inv_state[l][0].numel() // self.inv_state[l][0].size(-1) * self.inv_state[l][1].size(-1)
-                            for _, l in owned)
+                total = sum(_noise_count(*self.inv_state[l]) for _, l in owned)
                 flat = torch.empty(total, dtype=torch.float32, device=dev)
             for _, layer in owned:
                 first, second = self.inv_state[layer]
@@ -1965,6 +2117,12 @@ class KFAC(LinearisedPredictive, Curvature):
                     pos += G * n * m
                 zs = z if G > 1 else [z]
                 slots = list(zip(_live_slots(layer), self._mean_slots(layer)))
+                if first.dim() == 1:
+                    # an Embedding: weight = mean + diag(l_a) z L_G^T in one product (no first stage: A is diagonal)
+                    (live, mean), = slots
+                    stage2.append(ops.Gemm(z, second.t(), live.view, epilogue=ops.EPI_MUL_E_ADD_F,
+                                           E=first.view(n, 1).expand(n, m), F=mean.view, tri=ops.TRI_B_UPPER))
+                    continue
                 # grouped layer: group g owns the rows [g m, (g + 1) m) of every slot - one pair of products per group
                 for g, (la, lg) in enumerate(_pairs(first, second)):
                     rows = slice(g * m, (g + 1) * m)
@@ -2013,8 +2171,7 @@ class KFAC(LinearisedPredictive, Curvature):
         if plan is None:
             cache.clear()                                    # one bank's worth of buffers at a time
             dev = self.inv_state[owned[0][1]][0].device
-            total = sum(self.inv_state[l][0].numel() // self.inv_state[l][0].size(-1) * self.inv_state[l][1].size(-1)
-                        for _, l in owned)
+            total = sum(_noise_count(*self.inv_state[l]) for _, l in owned)
             flat = torch.empty(S * total, dtype=torch.float32, device=dev) if noise is None else None
             stage_a, stage_b, weights, biases, keep = [], [], {}, {}, []
             pos = 0
@@ -2024,6 +2181,23 @@ class KFAC(LinearisedPredictive, Curvature):
                 grouped = first.dim() == 3
                 G = first.shape[0] if grouped else 1
                 shape = (S, G, n, m) if grouped else (S, n, m)
+                if first.dim() == 1:
+                    # an Embedding: set k = mean + diag(l_a) z_k L_G^T, one product per set in the second launch
+                    if noise is not None:
+                        z = noise[layer]
+                        if tuple(z.shape) != shape:
+                            raise RuntimeError(f"sample_many: noise of a layer must be {shape}")
+                    else:
+                        z = flat[pos:pos + S * n * m].view(S, n, m)
+                        pos += S * n * m
+                    wb, bb = _bank_buffers(layer, S, dev)
+                    mean, = self._mean_slots(layer)
+                    for k in range(S):
+                        stage_b.append(ops.Gemm(z[k], second.t(), wb[k], epilogue=ops.EPI_MUL_E_ADD_F,
+                                                E=first.view(n, 1).expand(n, m), F=mean.view, tri=ops.TRI_B_UPPER))
+                    keep.append(z)
+                    weights[layer], biases[layer] = wb, bb
+                    continue
                 if noise is not None:
                     z = noise[layer]
                     if tuple(z.shape) != shape:

@@ -46,6 +46,11 @@ class KFACStepGraph:
     def __init__(self, kfac: KFAC, add=0.5, multiply=1.0, batch_size: Optional[int] = None, warmup: int = 3):
         self.kfac, self.add, self.multiply, self.batch_size = kfac, add, multiply, batch_size
         dev = next(kfac.model.parameters()).device
+        for layer in kfac._layers():
+            if ops.is_embedding_layer(layer):
+                name = next((f"'{n}'" for n, mod in kfac.model.named_modules() if mod is layer), repr(layer))
+                raise NotImplementedError(f"KFACStepGraph: the embedding layer {name} (Embedding) is not supported: the "
+                                          f"eager update, invert and samplers of KFAC take it")
         if dev.type != "cuda":
             raise RuntimeError("KFACStepGraph needs the model on an MI355X")
         had_state = bool(kfac.state)

@@ -583,6 +583,53 @@ def kfac_accumulate_norm(jobs: Sequence[NormFactorJob], events=None) -> None:
     _side_accumulate(NormFactorJob, jobs, events)
 
 
+class EmbeddingFactorJob(_ConvJob):
+    """The diagonal A factor of an nn.Embedding (curv_kfac_embedding_accumulate): dst (V,) (+)= scale * the
+    count of every token in `src`, the (N, *) int64 / int32 index record (contiguous; or just its shape, for plan queries,
+    with `i64` saying which); the count of row `padding_idx` (None: no such row) is 0."""
+    __slots__ = ("V", "padding_idx", "i64")
+
+    def __init__(self, src, dst, V, padding_idx=None, scale=1.0, first=False, i64=True):
+        self._set(src, dst, (1, 1), (1, 1), (0, 0), False, scale, first)
+        self.V, self.padding_idx = int(V), None if padding_idx is None else int(padding_idx)
+        self.i64 = bool(src.dtype == torch.int64) if isinstance(src, torch.Tensor) else bool(i64)
+
+
+_INDEX_DTYPES = (torch.int64, torch.int32)
+
+
+def _embedding_descs(jobs: Sequence[EmbeddingFactorJob], check_tensors: bool = True):
+    arr = (_lib.curv_embedding_desc * len(jobs))()
+    for d, j in zip(arr, jobs):
+        shape = tuple(j.src.shape) if isinstance(j.src, torch.Tensor) else tuple(j.src)
+        d.positions, d.idx_i64, d.V = math.prod(shape), int(j.i64), j.V
+        d.padding_idx = -1 if j.padding_idx is None else j.padding_idx
+        d.first, d.scale = int(j.first), j.scale
+        if check_tensors:
+            if not j.src.is_cuda or not j.dst.is_cuda:
+                raise RuntimeError("curvature_amd runs on MI355X only: got a CPU tensor (no CPU fallback)")
+            if j.src.dtype not in _INDEX_DTYPES or not j.src.is_contiguous():
+                raise RuntimeError(f"embedding factor source must be a contiguous int64 or int32 index tensor, got {j.src.dtype}")
+            if j.dst.dtype != torch.float32 or tuple(j.dst.shape) != (j.V,) or not j.dst.is_contiguous():
+                raise RuntimeError(f"embedding factor destination must be a contiguous float32 ({j.V},) vector, got "
+                                   f"{tuple(j.dst.shape)} {j.dst.dtype}")
+            d.idx, d.a = j.src.data_ptr(), j.dst.data_ptr()
+    return arr
+
+
+def kfac_embedding_plan_flops(jobs: Sequence[EmbeddingFactorJob]) -> List[int]:
+    """What the histogram executes for each job (curv_kfac_embedding_plan_flops, host only): one add per position and one
+    multiply-add per row.  `job.src` may be a tensor or just its shape."""
+    return _side_plan_flops(EmbeddingFactorJob, jobs)
+
+
+def kfac_accumulate_embedding(jobs: Sequence[EmbeddingFactorJob], events=None) -> None:
+    """The token histograms of nn.Embedding layers (curv_kfac_embedding_accumulate) on the current stream: int32 counts in
+    `workspace` scratch, one atomic per distinct token of a wave, then ``dst (+)= scale * count``: the same bits in any
+    order.  `events` = (start, stop) ``torch.cuda.Event``s around the build."""
+    _side_accumulate(EmbeddingFactorJob, jobs, events)
+
+
 class FactorBuild(NamedTuple):
     """One kind of factor build: the job class, its descriptor filler, the names of the `ops` functions that price and
     build jobs of that class and, for the side builds, the library's symbol stem and the tag of their scratch."""
@@ -609,6 +656,8 @@ FACTOR_BUILDS = (
                 "kfac_reduce"),
     FactorBuild(Conv3dFactorJob, _conv3d_descs, "kfac_conv3d_plan_flops", "kfac_accumulate_conv3d", "curv_kfac_conv3d",
                 "kfac_conv3d"),
+    FactorBuild(EmbeddingFactorJob, _embedding_descs, "kfac_embedding_plan_flops", "kfac_accumulate_embedding",
+                "curv_kfac_embedding", "kfac_embedding"),
     FactorBuild(NormFactorJob, _norm_descs, "kfac_norm_plan_flops", "kfac_accumulate_norm", "curv_kfac_norm", "kfac_norm"),
 )
 _BUILD_OF = {build.job: build for build in FACTOR_BUILDS}
@@ -857,6 +906,63 @@ def _norm_jobs(layer, x, g, name: Optional[str] = None) -> "LayerJobs":
     return LayerJobs(a_job, g_job, 1 + int(view.has_bias), 1, N, H * W, C)
 
 
+# nn.Embedding is opt-in in the same way: with the switch off - the default - every selection, refusal and
+# message is exactly what it was.
+_EMBEDDING = False
+
+
+def admit_embedding(enable: bool = True) -> bool:
+    """Switch the weight of nn.Embedding layers on or off for the process; returns what it was.  On: KFAC and Diagonal accept
+    ``'Embedding'`` in `layer_types` by name (it never enters the default selection), `factor_jobs` routes the layer to an
+    `EmbeddingFactorJob` (the token histogram: the exactly diagonal A factor of a bias-free Linear on one-hot rows) and the
+    flat build of grad_output, and `per_sample_route` answers ``"embedding"``.  Off: the layer is refused where it was."""
+    global _EMBEDDING
+    was, _EMBEDDING = _EMBEDDING, bool(enable)
+    return was
+
+
+def embedding_admitted() -> bool:
+    return _EMBEDDING
+
+
+def is_embedding_layer(layer) -> bool:
+    """An nn.Embedding while `admit_embedding` is on."""
+    return _EMBEDDING and layer.__class__.__name__ == 'Embedding'
+
+
+def _embedding_indices(t, name: str):
+    """The index record of an Embedding as the kernels read it: int64 or int32, contiguous (read in place if it is, copied
+    by torch otherwise); a `ShapeOnly` stays one."""
+    if t.dtype not in _INDEX_DTYPES:
+        raise RuntimeError(f"{name}: an Embedding expects int64 or int32 indices, got {t.dtype}")
+    if len(t.shape) < 1 or math.prod(t.shape) < 1:
+        raise RuntimeError(f"{name}: empty index record {tuple(t.shape)}")
+    return t if isinstance(t, ShapeOnly) else t.detach().contiguous()
+
+
+def _embedding_jobs(layer, x, g, name: Optional[str] = None) -> "LayerJobs":
+    """`factor_jobs` of an nn.Embedding (`admit_embedding`): the A side an `EmbeddingFactorJob` on the (N, *) indices, the G
+    side the flat build of grad_output seen as (N T, D), routed by its dtype like a Linear's.  n = V, m = D; the positions
+    count as the expand build of a Linear on tokens counts them: N T rows of one position each."""
+    name = name or repr(layer)
+    if x is None and g is None:
+        raise RuntimeError("KFAC.update: no recorded forward/backward pass for a selected layer")
+    V, D = int(layer.num_embeddings), int(layer.embedding_dim)
+    a_job = g_job = None
+    if x is not None:
+        x = _embedding_indices(x, name)
+        a_job = EmbeddingFactorJob(_job_source(x), None, V, layer.padding_idx, i64=x.dtype == torch.int64)
+    if g is not None:
+        if g.shape[-1] != D or (x is not None and tuple(g.shape[:-1]) != tuple(x.shape)):
+            raise RuntimeError(f"{name}: grad_output {tuple(g.shape)} does not match the indices "
+                               f"{None if x is None else tuple(x.shape)} and embedding_dim {D}")
+        g = _factor_source(g, fp32=False, flatten=True)
+        src = _job_source(g)
+        g_job = FactorJob(src, None) if g.dtype == torch.float32 else HalfFactorJob(src, None, dtype=g.dtype)
+    rows = math.prod(x.shape) if x is not None else g.shape[0]
+    return LayerJobs(a_job, g_job, V, D, rows, 1, 1)
+
+
 class ConvView(NamedTuple):
     """`conv_view` of a convolution layer: its 2-D window and its records as 4-D tensors."""
     kernel: tuple
@@ -1057,11 +1163,11 @@ def factor_jobs(layer, x, g, out_size=None, approximation="expand") -> LayerJobs
     (`_conv3d_jobs`).  `out_size`: the output size a ConvTranspose2d forward was
     seen to produce (it carries the effective output_padding), used when there is no `g` to read it from.  The jobs come
     without `dst`, `scale` and `first`."""
-    if is_norm_layer(layer):
+    if is_norm_layer(layer) or is_embedding_layer(layer):
         if approximation == "reduce":
             raise NotImplementedError(f'approximation="reduce" does not take a {layer.__class__.__name__} layer; '
                                       f'approximation="expand" does')
-        return _norm_jobs(layer, x, g)
+        return _norm_jobs(layer, x, g) if is_norm_layer(layer) else _embedding_jobs(layer, x, g)
     if approximation == "reduce":
         return _reduce_jobs(layer, x, g)
     if approximation != "expand":
@@ -1267,9 +1373,12 @@ def per_sample_route(layer) -> str:
     product P_n = g_n X_n^T (every layer but a grouped Conv2d); ``"depthwise"`` - the direct kernel of
     csrc/persample_dw.hip (in_channels == out_channels == groups, at most `DW_MAX_TAPS` kernel taps); ``"slices"`` - one
     product per group on channel slices of the records (`GroupSlice`: every other grouped Conv2d); ``"norm"`` - the fused
-    pass of csrc/norm_factor.hip (LayerNorm, GroupNorm, BatchNorm2d while `admit_norm_layers` is on)."""
+    pass of csrc/norm_factor.hip (LayerNorm, GroupNorm, BatchNorm2d while `admit_norm_layers` is on); ``"embedding"`` - the
+    segment walker of csrc/embedding_factor.hip (nn.Embedding while `admit_embedding` is on)."""
     if is_norm_layer(layer):
         return "norm"
+    if is_embedding_layer(layer):
+        return "embedding"
     if layer.__class__.__name__ != 'Conv2d' or int(layer.groups) == 1:
         return "whole"
     if layer.in_channels == layer.out_channels == int(layer.groups) and \
@@ -2450,6 +2559,162 @@ def per_sample_norm_quad_reduce(jobs: Sequence[PerSampleNormJob]) -> None:
     _run_build("curv_persample_norm_workspace_bytes", "curv_persample_norm_quad_reduce",
                _per_sample_norm_descs(jobs, "per_sample_norm_quad_reduce", "quad"), len(jobs), jobs[0].out.device,
                "persample_norm")
+
+
+class EmbeddingWalk(NamedTuple):
+    """`embedding_walk_plan`: the grouped position list the segment walker of csrc/embedding_factor.hip reads (int32
+    tensors on the device of the indices).  `pos`: the kept positions n T + t, sorted by outer key, inner key, position;
+    `chunks` (C, 4): {begin, end, group, slot} - pos[begin:end] belongs to outer key `group`, at most `split` positions,
+    `slot` -1 where the chunk is its whole group, else its number among the chunks of split groups; `mgroups` (M, 3):
+    {slot_begin, slot_end, group} of every split group; `n_slots`: how many chunks have a slot."""
+    pos: torch.Tensor
+    chunks: torch.Tensor
+    mgroups: torch.Tensor
+    n_slots: int
+
+
+def embedding_walk_plan(idx: torch.Tensor, V: int, padding_idx: Optional[int], mode: int,
+                        split: int = _lib.EMB_SPLIT_L) -> EmbeddingWalk:
+    """The positions of the (N, *) index tensor `idx` grouped for the per-sample kernels: by token and, inside it, sample
+    (`mode` ``_lib.EMB_SQ``) or by sample and, inside it, token (``_lib.EMB_QUAD``), positions ascending inside both (a stable
+    sort of the N T keys); positions that hold `padding_idx` or an index outside [0, V) are left out.  Every group's list is
+    cut into chunks of at most `split` positions.  Plumbing in torch ops, on the device of `idx` (a CPU tensor gives the plan
+    on the CPU: the planner's test)."""
+    N, dev = idx.shape[0], idx.device
+    flat = idx.reshape(-1).to(torch.int64)
+    T = flat.numel() // N
+    p = torch.arange(flat.numel(), dtype=torch.int64, device=dev)
+    keep = (flat >= 0) & (flat < V)
+    if padding_idx is not None:
+        keep &= flat != padding_idx
+    p, v = p[keep], flat[keep]
+    n = torch.div(p, T, rounding_mode="floor")
+    outer, key = (v, v * N + n) if mode == _lib.EMB_SQ else (n, n * V + v)
+    order = torch.sort(key, stable=True).indices
+    pos, outer = p[order], outer[order]
+    groups, counts = torch.unique_consecutive(outer, return_counts=True)
+    starts = torch.cumsum(counts, 0) - counts
+    pieces = torch.div(counts + (split - 1), split, rounding_mode="floor")
+    which = torch.repeat_interleave(torch.arange(groups.numel(), device=dev), pieces)        # chunk -> its group's number
+    first = torch.cumsum(pieces, 0) - pieces
+    within = torch.arange(which.numel(), device=dev) - first[which]
+    begin = starts[which] + within * split
+    end = torch.minimum(begin + split, (starts + counts)[which])
+    multi = pieces[which] > 1
+    slot = torch.where(multi, torch.cumsum(multi.to(torch.int64), 0) - 1, torch.full_like(begin, -1))
+    chunks = torch.stack([begin, end, groups[which], slot], 1).to(torch.int32).contiguous()
+    split_groups = pieces > 1
+    slot_begin = (torch.cumsum(torch.where(split_groups, pieces, torch.zeros_like(pieces)), 0) - pieces)[split_groups]
+    mgroups = torch.stack([slot_begin, slot_begin + pieces[split_groups], groups[split_groups]], 1).to(torch.int32).contiguous()
+    return EmbeddingWalk(pos.to(torch.int32).contiguous(), chunks.view(-1, 4), mgroups.view(-1, 3), int(multi.sum()))
+
+
+def check_embedding_record(what: str, g) -> None:
+    """The per-sample kernels of an Embedding read float32 records only, whatever `widen_per_sample` says: RuntimeError in
+    the wording of `per_sample_dtype_fault` otherwise."""
+    if g.dtype != torch.float32:
+        raise RuntimeError(per_sample_dtype_fault(what, g) or f"{what} expects float32 records, got {g.dtype}")
+
+
+class PerSampleEmbeddingJob:
+    """The per-sample gradient of an nn.Embedding weight (csrc/embedding_factor.hip): row v of sample n is
+    P_n[v, :] = sum_{t : idx[n, t] = v} g[n, t, :], from the layer's records as they are: `idx` (N, *) int64 / int32, `g`
+    (N, *, D) float32, read through its strides where its middle dims collapse to one.  `dst` (V, D): the destination of
+    `per_sample_embedding_sq_accumulate`; `out` (N,) and `w` ((V, D) or (V,), or None for ones): those of
+    `per_sample_embedding_quad_reduce`.  `alpha`, `first`: as in `PerSampleDwJob`."""
+    __slots__ = ("idx", "g", "V", "padding_idx", "name", "dst", "out", "w", "alpha", "first")
+
+    def __init__(self, idx, g, V, padding_idx=None, name="Embedding", dst=None, out=None, w=None, alpha=1.0, first=False):
+        self.idx, self.g, self.V = idx, g, int(V)
+        self.padding_idx = None if padding_idx is None else int(padding_idx)
+        self.name, self.dst, self.out, self.w = name, dst, out, w
+        self.alpha, self.first = float(alpha), bool(first)
+
+    @classmethod
+    def of(cls, layer, x, g, name: Optional[str] = None, T=None, W=None, s=None, **own):
+        """The job of an Embedding `layer` on its records; `W`: the `w` of a quad job (the `direct` terms of an estimator
+        name it so; a layer of this kind has no `T` and no `s`)."""
+        if x is None or g is None:
+            raise RuntimeError(f"{name or repr(layer)}: the per-sample products need both records")
+        return cls(x.detach(), g.detach(), layer.num_embeddings, layer.padding_idx, name or repr(layer), w=W, **own)
+
+
+def _per_sample_embedding_descs(jobs: Sequence[PerSampleEmbeddingJob], what: str, mode: int):
+    """The descriptors of `jobs` and what they point to (index copies, record views, position lists), to be kept alive
+    until the launches are enqueued."""
+    arr = (_lib.curv_embedding_walk_desc * len(jobs))()
+    keep = []
+    for d, j in zip(arr, jobs):
+        for t in (j.idx, j.g):
+            if not isinstance(t, torch.Tensor) or not t.is_cuda:
+                raise RuntimeError(f"{what}: curvature_amd runs on MI355X only: got a CPU tensor for {j.name} (no CPU fallback)")
+        check_embedding_record(f"{what}: {j.name}", j.g)
+        idx = _embedding_indices(j.idx, f"{what}: {j.name}")
+        N, D = int(idx.shape[0]), int(j.g.shape[-1])
+        T = idx.numel() // N
+        if tuple(j.g.shape[:-1]) != tuple(idx.shape) or D < 1 or j.V < 1:
+            raise RuntimeError(f"{what}: {j.name}: grad_output {tuple(j.g.shape)} does not match the indices {tuple(idx.shape)} "
+                               f"(V {j.V}, D {D})")
+        g = j.g.reshape(N, T, D)                             # (a view where the middle dims collapse to one stride)
+        if (D > 1 and g.stride(2) != 1) or any(v < 0 for v in g.stride()):
+            g = g.contiguous()
+        walk = embedding_walk_plan(idx, j.V, j.padding_idx, mode)
+        keep += [idx, g, walk]
+        d.idx, d.g, d.positions, d.idx_i64 = idx.data_ptr(), g.data_ptr(), idx.numel(), int(idx.dtype == torch.int64)
+        d.g_sn, d.g_st, d.g_elems = (g.stride(0) if N > 1 else 0), (g.stride(1) if T > 1 else 0), _source_extent(g)
+        d.N, d.T, d.V, d.D, d.mode, d.first, d.alpha = N, T, j.V, D, mode, int(j.first), j.alpha
+        d.padding_idx = -1 if j.padding_idx is None else j.padding_idx
+        d.pos, d.chunks, d.mgroups = walk.pos.data_ptr(), walk.chunks.data_ptr(), walk.mgroups.data_ptr()
+        d.n_pos, d.n_chunks, d.n_mgroups, d.n_slots = walk.pos.numel(), walk.chunks.shape[0], walk.mgroups.shape[0], walk.n_slots
+        if mode == _lib.EMB_SQ:
+            t = j.dst
+            if t is None or not t.is_cuda or t.dtype != torch.float32 or tuple(t.shape) != (j.V, D) or \
+                    (D > 1 and t.stride(1) != 1) or (j.V > 1 and t.stride(0) < D):
+                raise RuntimeError(f"{what}: {j.name}: destination must be a float32 GPU ({j.V},{D}) view with unit column "
+                                   f"stride, got {None if t is None else (tuple(t.shape), t.dtype)}")
+            d.dst, d.dst_rs = t.data_ptr(), t.stride(0) if j.V > 1 else D
+            continue
+        t = j.out
+        if t is None or not t.is_cuda or t.dtype != torch.float32 or t.dim() != 1 or t.shape[0] != N or \
+                (N > 1 and t.stride(0) < 1):
+            raise RuntimeError(f"{what}: {j.name}: destination must be a float32 GPU length-{N} view with a positive stride, "
+                               f"got {None if t is None else (tuple(t.shape), t.dtype)}")
+        d.out, d.o_stride = t.data_ptr(), max(t.stride(0), 1)
+        if j.w is not None:
+            w = j.w
+            if not w.is_cuda or w.dtype != torch.float32:
+                raise RuntimeError(f"{what}: {j.name}: w must be a float32 GPU tensor, got {w.dtype} on {w.device}")
+            if tuple(w.shape) == (j.V, D) and (D == 1 or w.stride(1) == 1) and (j.V == 1 or w.stride(0) >= D):
+                d.w, d.w_rs, d.w_kind = w.data_ptr(), w.stride(0) if j.V > 1 else D, _lib.EMB_W_MATRIX
+            elif tuple(w.shape) == (j.V,) and w.is_contiguous():
+                d.w, d.w_kind = w.data_ptr(), _lib.EMB_W_VECTOR
+            else:
+                raise RuntimeError(f"{what}: {j.name}: w must be a ({j.V},{D}) view with unit column stride or a contiguous "
+                                   f"({j.V},) vector, got {tuple(w.shape)}")
+    return arr, keep
+
+
+def per_sample_embedding_sq_accumulate(jobs: Sequence[PerSampleEmbeddingJob]) -> None:
+    """``dst[v, :] (+)= alpha sum_n P_n[v, :]**2`` for every job (curv_persample_embedding_sq_accumulate), on the current
+    stream: the exact per-sample Fisher diagonal of an Embedding weight.  No floating-point atomics: two calls on the same
+    inputs give the same bits."""
+    if not jobs:
+        return
+    arr, keep = _per_sample_embedding_descs(jobs, "per_sample_embedding_sq_accumulate", _lib.EMB_SQ)
+    _run_build("curv_persample_embedding_workspace_bytes", "curv_persample_embedding_sq_accumulate", arr, len(jobs),
+               jobs[0].dst.device, "persample_embedding")
+    del keep
+
+
+def per_sample_embedding_quad_reduce(jobs: Sequence[PerSampleEmbeddingJob]) -> None:
+    """``out[n] (+)= alpha sum_v sum_d w[v, d] P_n[v, d]**2`` for every job (curv_persample_embedding_quad_reduce), on the
+    current stream; `w` (V, D), or (V,) broadcast over d: the Embedding's row of `functional_variance`."""
+    if not jobs:
+        return
+    arr, keep = _per_sample_embedding_descs(jobs, "per_sample_embedding_quad_reduce", _lib.EMB_QUAD)
+    _run_build("curv_persample_embedding_workspace_bytes", "curv_persample_embedding_quad_reduce", arr, len(jobs),
+               jobs[0].out.device, "persample_embedding")
+    del keep
 
 
 class PerSampleDwProjectJob(PerSampleDwJob):

@@ -52,7 +52,8 @@ class LinearisedPredictive:
 
     # ------------------------------------------------------------------ the shared steps
     def _predictive_operands(self, what: str, call: str, inputs: bool, rotated: bool, check=None,
-                             select: str = "inv_state", grouped: bool = False, norm: bool = False):
+                             select: str = "inv_state", grouped: bool = False, norm: bool = False,
+                             embedding: bool = False):
         """What every reduction starts from: the checks, the selected layers that have an inverse state (`select`: the
         dict that says so - the grid needs `state` only), their per-sample operands from the current records (the g side
         only unless `inputs`; packed for a rotation if `rotated`), and the key that ties a kept X side to the recorded
@@ -60,7 +61,8 @@ class LinearisedPredictive:
         test of its own arguments against the batch of N samples).  `grouped`: the caller takes grouped convolutions
         (`ops.admit_grouped_per_sample`): their group slices stand among the layers as `ops.GroupSlice` items, and the
         true depthwise ones come back apart, with their records; `norm`: the caller takes normalisation layers
-        (`ops.admit_norm_layers`), which come back among them (`ops.per_sample_route` tells them apart).  Returns (layers, operands, key, direct), `direct` a list
+        (`ops.admit_norm_layers`), which come back among them (`ops.per_sample_route` tells them apart), `embedding`: and
+        nn.Embedding layers (`ops.admit_embedding`), likewise.  Returns (layers, operands, key, direct), `direct` a list
         of (layer, input, grad_output)."""
         have = getattr(self, select)
         assert have, ("Inverse state dict is empty. Did you call 'invert' prior to this?" if select == "inv_state" else
@@ -70,12 +72,14 @@ class LinearisedPredictive:
         if getattr(self, "record", None) is None:
             raise RuntimeError(f"{what}.{call}: no recording hooks (construct with per_sample=True, or go "
                                "through evaluate.glm_predictive)")
-        layers = self._per_sample_layers(f"{what}.{call}", "select other layer types", grouped=grouped, norm=norm)
+        layers = self._per_sample_layers(f"{what}.{call}", "select other layer types", grouped=grouped, norm=norm,
+                                         embedding=embedding)
         layers = [l for l in layers if l in have]
         assert layers, f"{select} holds none of the selected layers"
-        direct = [l for l in layers if ops.per_sample_route(l) in ("depthwise", "norm")]
+        fused = ("depthwise", "norm", "embedding")
+        direct = [l for l in layers if ops.per_sample_route(l) in fused]
         direct = [(l, *self._records_of(what, l)) for l in direct]
-        layers = ops.per_sample_items([l for l in layers if ops.per_sample_route(l) not in ("depthwise", "norm")])
+        layers = ops.per_sample_items([l for l in layers if ops.per_sample_route(l) not in fused])
         layout = dict(rows_outer=True, in_place=False) if rotated else {}
         operands = self._per_sample_operands(what, layers, x_side=inputs, **layout) if layers else []
         if check is not None:
@@ -147,12 +151,15 @@ class LinearisedPredictive:
                 raise RuntimeError(f"{what}.functional_variance: out must be a float32 GPU view of length {N}, got "
                                    f"{tuple(out.shape)} {out.dtype} on {out.device}")
         layers, operands, key, direct = self._predictive_operands(what, "functional_variance", inputs, basis is not None,
-                                                                  check, grouped=True, norm=True)
+                                                                  check, grouped=True, norm=True, embedding=True)
         if inputs:
             xs, ws = self._x_side("variance", layers, operands, basis, weights)
             # a depthwise layer has no packed X to keep: its recorded input is read again; (T, w**2, s) is what it keeps
             terms = [self._predictive_terms().direct(l) for l, _, _ in direct]
             terms = [(T, None if w is None else ops.mul(w, w), s) for T, w, s in terms]
+            # an Embedding keeps its row weights, l_a**2 (V,) of KFAC or inv**2 (V, D) of Diagonal, as W
+            terms = [(None, W if T is None else ops.mul(T, T), s) if ops.per_sample_route(l) == "embedding" else (T, W, s)
+                     for (l, _, _), (T, W, s) in zip(direct, terms)]
             self._kept()["variance"] = dict(key=key, xs=xs, ws=ws, direct=terms,
                                             low=None if lowrank is None else [lowrank(l) for l in layers])
         kept = self._kept_entry(what, "functional_variance", "variance", key)
@@ -160,12 +167,23 @@ class LinearisedPredictive:
         rows = torch.empty(len(layers) + len(direct), out.shape[0], dtype=torch.float32, device=out.device)
         ops.per_sample_quad_reduce([ops.PerSampleQuadJob.of(s, g, x, w, rows[k], first=True)
                                     for k, ((s, _, _), g, x, w) in enumerate(zip(operands, gs, kept["xs"], kept["ws"]))])
-        fused = {"depthwise": (ops.PerSampleDwJob, []), "norm": (ops.PerSampleNormJob, [])}
+        fused = {"depthwise": (ops.PerSampleDwJob, []), "norm": (ops.PerSampleNormJob, []),
+                 "embedding": (ops.PerSampleEmbeddingJob, [])}
+        rotate = []
         for k, ((l, x, g), (T, w, s)) in enumerate(zip(direct, kept["direct"])):
             job, jobs = fused[ops.per_sample_route(l)]
+            if job is ops.PerSampleEmbeddingJob and s is not None:
+                # KFAC: the rows of grad_output times L_G, one product over the (N T, D) rows; the walker sums those
+                ops.check_embedding_record(f"{what}.functional_variance: layer {l.__class__.__name__}", g)
+                flat = g.detach().reshape(-1, g.shape[-1])
+                g = torch.empty(flat.shape, dtype=torch.float32, device=flat.device)
+                rotate.append(ops.Gemm(flat, s, g))
+                g, s = g.view(*x.shape, -1), None
             jobs.append(job.of(l, x, g, out=rows[len(layers) + k], T=T, W=w, s=s, first=True))
+        ops.gemm_batched(rotate)
         ops.per_sample_dw_quad_reduce(fused["depthwise"][1])
         ops.per_sample_norm_quad_reduce(fused["norm"][1])
+        ops.per_sample_embedding_quad_reduce(fused["embedding"][1])
         if kept["low"] is not None:
             # minus the squared norm of every layer's low-rank vector, into the layer's row
             ys = [torch.empty(out.shape[0], ft.shape[1], dtype=torch.float32, device=out.device) for _, _, ft in kept["low"]]
@@ -203,7 +221,7 @@ class LinearisedPredictive:
         terms = self._predictive_terms()
         what, basis, spectrum = terms.name, terms.grid_basis, terms.spectrum
         hypers, points = self._grid_points(what, hypers, terms.separable)
-        if ops.norm_layers_admitted() and getattr(self, "record", None) is not None:
+        if (ops.norm_layers_admitted() or ops.embedding_admitted()) and getattr(self, "record", None) is not None:
             # a selected normalisation layer is refused by name before the missing decomposition, which refuses it too
             self._per_sample_layers(f"{what}.functional_variance_grid", "select other layer types",
                                     grouped=ops.per_sample_admits_grouped_joint())

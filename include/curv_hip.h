@@ -894,6 +894,83 @@ int curv_persample_norm_quad_reduce(void* stream, const curv_norm_desc* descs, i
                                     size_t workspace_bytes);
 
 /* ------------------------------------------------------------------------------------------------
+ * Curvature of an nn.Embedding weight (csrc/embedding_factor.hip, DESIGN.md "K26").  The layer is a bias-free Linear on
+ * one-hot rows, so its input-side Kronecker factor is exactly diagonal - token counts - and its per-sample gradient row v is
+ * the sum of the grad_output rows of the positions that hold token v.  `idx`: the (N, T) token indices, contiguous, int32 or
+ * int64 (`idx_i64`), `positions` = N T < 2^31 of them.  Every kernel checks every index it reads: one outside [0, V), or
+ * equal to `padding_idx` (-1: none), contributes nothing and never addresses memory.
+ *
+ * curv_kfac_embedding_accumulate:  a[v] (+)= scale * count_v, count of the padding row 0.  The histogram is taken with
+ * int32 atomics into the workspace, one per distinct token of a wave (the lanes of a wave that hold the same token are
+ * counted by ballot first), so it does not depend on any order.
+ *
+ * The two per-sample reductions are one segment walker.  The caller supplies the grouped position list: `pos` (n_pos
+ * position numbers n T + t, sorted by an outer key, inside it by an inner key, inside that ascending), cut into `chunks`
+ * (n_chunks records {begin, end, group, slot}: pos[begin, end) belongs to outer key `group`, at most CURV_EMB_SPLIT_L
+ * positions; slot -1 where the chunk is its whole group, else the chunk's number among the n_slots chunks of split
+ * groups) and `mgroups` (n_mgroups records {slot_begin, slot_end, group}, one per split group).  A segment is a run of
+ * equal inner keys; its rows g[n, t, :] are summed in list order into r, and w r**2 is added to the group's accumulator
+ * in segment order; a split group's chunks leave (head, accumulator, tail) in the workspace and a second kernel adds them
+ * in chunk order.  The group is then written once.  No floating-point atomics: the same inputs give the same bits.
+ *     CURV_EMB_SQ    outer key = token, inner = sample:  dst[v, :] (+)= alpha * sum_n (sum_{t: idx[n,t] = v} g[n, t, :])**2
+ *     CURV_EMB_QUAD  outer key = sample, inner = token:  out[n] (+)= alpha * sum_v sum_d w[v, d] (sum_{t: idx[n,t] = v} g[n, t, d])**2
+ *                    w: (V, D) with row stride w_rs (`w_kind` CURV_EMB_W_MATRIX) or (V) (CURV_EMB_W_VECTOR)
+ * g is read through its strides g_sn, g_st in ELEMENTS (unit stride along d) inside `g_elems` elements from the pointer;
+ * one wave walks 256 contiguous floats of a group, 16 bytes per lane where pointer and strides allow it.  A record list
+ * that disagrees with `idx` loses contributions, never reads or writes outside the tensors: every entry is checked.
+ * CURV_ERR_INVALID before anything is launched: sizes below 1, N T != positions, negative strides, an extent smaller than
+ * what sizes and strides address, a NULL tensor, an unknown mode or w_kind, a nonzero `reserved`.
+ * ---------------------------------------------------------------------------------------------- */
+#define CURV_EMB_SPLIT_L 128      /* positions per chunk of a group's list */
+#define CURV_EMB_SQ 0
+#define CURV_EMB_QUAD 1
+#define CURV_EMB_W_MATRIX 1
+#define CURV_EMB_W_VECTOR 2
+typedef struct curv_embedding_desc {
+  const void* idx;
+  long long positions;
+  int32_t idx_i64;
+  int32_t V;
+  int32_t padding_idx;     /* -1: none */
+  int32_t first;
+  float scale;
+  int32_t reserved;        /* 0 */
+  float* a;                /* (V) contiguous */
+} curv_embedding_desc;
+typedef struct curv_embedding_walk_desc {
+  const void* idx;
+  const float* g;
+  long long positions, g_sn, g_st, g_elems;
+  int32_t idx_i64, N, T, V, D, padding_idx, mode, first;
+  const int32_t* pos;
+  const int32_t* chunks;   /* (n_chunks, 4) */
+  const int32_t* mgroups;  /* (n_mgroups, 3); may be NULL when n_mgroups = 0 */
+  int32_t n_pos, n_chunks, n_mgroups, n_slots;
+  float* dst;              /* CURV_EMB_SQ: (V, D), row stride dst_rs >= D */
+  long long dst_rs;
+  const float* w;          /* CURV_EMB_QUAD */
+  long long w_rs;
+  float* out;              /* CURV_EMB_QUAD: (N), stride o_stride >= 1 */
+  long long o_stride;
+  int32_t w_kind;
+  float alpha;
+  int32_t reserved;        /* 0 */
+  int32_t reserved2;       /* 0 */
+} curv_embedding_walk_desc;
+/* Device scratch (bytes); 0 with the error text set for an invalid descriptor.  Host only; the pointers are not read. */
+size_t curv_kfac_embedding_workspace_bytes(const curv_embedding_desc* descs, int n);
+size_t curv_persample_embedding_workspace_bytes(const curv_embedding_walk_desc* descs, int n);
+/* Host only: positions + V per histogram (integer adds and the final multiply-add). */
+int curv_kfac_embedding_plan_flops(const curv_embedding_desc* descs, int n, long long* out);
+/* The workspace must be 256-byte aligned.  `descs` is a host array; it may be reused as soon as the call returns. */
+int curv_kfac_embedding_accumulate(void* stream, const curv_embedding_desc* descs, int n, void* workspace,
+                                   size_t workspace_bytes);
+int curv_persample_embedding_sq_accumulate(void* stream, const curv_embedding_walk_desc* descs, int n, void* workspace,
+                                           size_t workspace_bytes);
+int curv_persample_embedding_quad_reduce(void* stream, const curv_embedding_walk_desc* descs, int n, void* workspace,
+                                         size_t workspace_bytes);
+
+/* ------------------------------------------------------------------------------------------------
  * The other reductions of a depthwise layer's products (csrc/persample_dw.hip, DESIGN.md "K15"): what the joint output
  * covariance and the damping grid of the linearised predictive need.  Phase 1 is that of the entry points above, so an
  * item's products p have the same bits; the descriptors below carry the record, geometry and extent fields of
